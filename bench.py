@@ -2,7 +2,7 @@
 """
 bench.py -- posterior samples/sec of the many-chain Gibbs fit path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -28,6 +28,8 @@ SURVEY.md section 8d (u8 state).  `cpu_baseline` is SURVEY section 8d's mode (ii
 sampler (oracle/fcdiff_oracle.c, OpenMP over chains) on the host cores, on a bounded sample.  `vb_iteration` puts the
 reference's OWN algorithm (one variational iteration, fcdiff/fit.py:75-82) beside it: GPU milliseconds against the
 restatement in the reference's structure (mode (i), Python loop over edges) and the whole-array NumPy form (mode (ii)).
+`--dump-outputs DIR`: right after the K timed steps, rank 0 writes what the loop leaves its caller (timed_outputs) as .npy
+files.  Every input is seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -72,7 +74,12 @@ def main():
     ap.add_argument("--no-corr", action="store_true", help="skip the time-series front-end (K_corr)")
     ap.add_argument("--timepoints", type=int, default=1200)
     ap.add_argument("--cpu-chains", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the sampler loop leaves its caller as DIR/<name>.npy "
+                         "(float64 / float32, at most 64 MB in all; see write_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.settle < 0:
+        ap.error("--steps must be >= 1, --warmup and --settle >= 0")
 
     import numpy as np
     import torch
@@ -173,6 +180,11 @@ def main():
         rank_ms = [float(x.item()) / args.steps * 1e3 for x in gathered]
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    # what the timed steps computed, read now: the per-kernel pass below runs the chains on
+    if args.dump_outputs:
+        outputs = timed_outputs(np, torch, eng, use_pg)
+        if rank == 0:
+            write_outputs(np, args.dump_outputs, outputs)
 
     # ---- the collective, on its own: the 8-word all-reduce of the pooled counts ----
     allreduce_us = None
@@ -372,7 +384,8 @@ def main():
         # K_corr, the front-end north_star names: (S, Nreg, T) time series -> edge-major correlations, fp64 MFMA Gram
         from fcdiff_amd.corr import correlations
         (S_all, T) = (H + U, args.timepoints)
-        ts = torch.randn((S_all, Nreg, T), dtype=torch.float64, device="cuda")
+        gen = torch.Generator(device="cuda").manual_seed(seed)
+        ts = torch.randn((S_all, Nreg, T), dtype=torch.float64, device="cuda", generator=gen)
         correlations(ts, ctx=ctx, as_numpy=False)
         torch.cuda.synchronize()
         n_rep = 20
@@ -429,6 +442,52 @@ def main():
         except Exception:
             pass
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def timed_outputs(np, torch, eng, pooled):
+    """
+    What the timed loop leaves its caller after its last step, read the way UnsharedRegionFit(method='gibbs') reads it
+    (fit._run_gibbs): q_F (C, 3) = P(f_c = k) and q_R (Nreg, U) = P(r = 1), each averaged over the chains of all ranks and
+    every sweep so far; pi (1,) and gamma (3,) of the last M-step; and this rank's chains, f (G, C) and r (G, Nreg, U).
+    """
+    t = torch
+    from fcdiff_amd.gibbs import allreduce_counts
+    cnt = t.cat([eng.cnt_f.reshape(-1).to(t.int64), eng.cnt_r.reshape(-1).to(t.int64),
+                 t.tensor([eng.n_accumulated * eng.G], dtype=t.int64, device=eng.cnt_f.device)])
+    if pooled:
+        cnt = allreduce_counts(cnt)
+    cnt = eng.host(cnt).astype(np.float64)
+    (C, NU) = (eng.C, eng.Nreg * eng.U)
+    total = max(cnt[-1], 1.0)
+    (gamma, pi) = eng.hyper_values()
+    (f, r) = eng.export_state()
+    return {"q_F": cnt[:3 * C].reshape(C, 3) / total, "q_R": cnt[3 * C:3 * C + NU].reshape(eng.Nreg, eng.U) / total,
+            "pi": np.array([pi], dtype=np.float64), "gamma": np.asarray(gamma, dtype=np.float64), "f": f, "r": r}
+
+
+def write_outputs(np, out_dir, outputs, max_bytes=DUMP_MAX_BYTES):
+    """
+    out_dir/<name>.npy for each array of timed_outputs: the marginals and (pi, gamma) in float64, the chain states (values
+    0..2) in float32.  If the states would take the files past max_bytes, f and r keep the same fixed sample of whole
+    chains: numpy RandomState(0).choice(G, n, replace=False), sorted, with n as large as fits.
+    """
+    small = {k: np.ascontiguousarray(outputs[k], dtype=np.float64) for k in ("q_F", "q_R", "pi", "gamma")}
+    (f, r) = (outputs["f"], outputs["r"])
+    G = f.shape[0]
+    room = max_bytes - sum(a.nbytes for a in small.values()) - 6 * 4096        # (6 .npy headers)
+    n = min(G, room // (4 * (f[0].size + r[0].size)))
+    if n < 1:
+        raise SystemExit("--dump-outputs: one chain's state does not fit in %d bytes at this shape" % max_bytes)
+    if n < G:
+        keep = np.sort(np.random.RandomState(0).choice(G, n, replace=False))
+        (f, r) = (f[keep], r[keep])
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = dict(small, f=f.astype(np.float32), r=r.astype(np.float32))
+    for (name, a) in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def vb_iteration(np, torch, fcdiff_amd, model0, b, bt, Nreg, H, U, cfg_name):
