@@ -22,7 +22,7 @@ reference) whose two conditionals ARE the reference's q_F /
 q_R updates evaluated at one-hot q:
 
   * Philox4x32-10 counter RNG (Salmon et al., SC'11; Random123 1.09 constants)
-  * gibbs_init / gibbs_f_step / gibbs_r_step / gibbs_stats / gibbs_logjoint
+  * gibbs_init / gibbs_f_step / gibbs_r_step / gibbs_stats / gibbs_logjoint / gibbs_mstep
 
 Parity status: every function of the first group is pinned against fixtures
 captured from the reference itself (tests/golden/G1..G12, made by
@@ -667,6 +667,26 @@ def gibbs_stats(f, r):
     """Pooled sufficient statistics of fit.py:208-220 over chains: [sum r, #f=0, #f=1, #f=2]."""
     return np.array([int(r.sum()), int((f == 0).sum()), int((f == 1).sum()), int((f == 2).sum())],
                     dtype=np.int64)
+
+
+def gibbs_mstep(counts, Nreg, U, clamp=True):
+    """
+    (pi, gamma) from the pooled counts {sum r, #f=0, #f=1, #f=2, G} of G chains: fit.py:208-213 / 215-220 at one-hot
+    q pooled over chains,
+        pi = sum r / (G Nreg U),      gamma_k = #k / (G C).
+    clamp=True adds the build's clamps (the reference has none; a zero would give ln 0 = -inf in the next sweep):
+        pi in [0.5 / n_r, 1 - 0.5 / n_r], n_r = G Nreg U;     gamma_k >= 0.5 / n_f, n_f = G C,
+    the gamma floor NOT renormalised (gamma may then sum to slightly more than 1).  Counts are Python ints: exact above 2^31.
+    """
+    c = [int(x) for x in counts]
+    n_r = float(c[4] * int(Nreg) * int(U))
+    n_f = float(c[4] * N_to_C(Nreg))
+    pi = c[0] / n_r
+    gamma = np.array([c[1 + k] / n_f for k in range(3)])
+    if clamp:
+        pi = min(max(pi, 0.5 / n_r), 1.0 - 0.5 / n_r)
+        gamma = np.maximum(gamma, 0.5 / n_f)
+    return pi, gamma
 
 
 def gibbs_logjoint(f, r, S_B, lM, lngamma, lnpi2):

@@ -21,11 +21,13 @@ from conftest import ROOT, load_golden, theta_dict
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from fcdiff_amd.gibbs import mstep_from_counts, run_chains, shard_chains  # noqa: E402
+from fcdiff_amd.gibbs import run_chains, shard_chains  # noqa: E402
+from oracle import fcdiff_oracle as O  # noqa: E402
 
 
 class OracleEngine(object):
-    """Same surface as fcdiff_amd.gibbs.GibbsEngine, computed by oracle/fcdiff_oracle.c (tests only)."""
+    """Same surface as fcdiff_amd.gibbs.GibbsEngine, computed by the oracle (oracle/fcdiff_oracle.c; the M-step by
+    oracle.fcdiff_oracle.gibbs_mstep) -- tests only."""
 
     def __init__(self, S_B, lM, Nreg, U, G, chain0, seed, gamma, pi, mode=1):
         from oracle import c_oracle as CO
@@ -47,7 +49,7 @@ class OracleEngine(object):
         return torch.from_numpy(self.CO.gibbs_stats(self.f, self.r).copy())
 
     def mstep(self, counts):
-        (self.pi, self.gamma) = mstep_from_counts(counts.numpy(), self.Nreg, self.U)
+        (self.pi, self.gamma) = O.gibbs_mstep(counts.numpy(), self.Nreg, self.U)
 
     def accumulate(self):
         self.cnt_r += self.r.sum(axis=0, dtype=np.int64)

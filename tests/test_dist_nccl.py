@@ -66,6 +66,16 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def assert_final_mstep(f, r, hyper, N=24, U=10):
+    """Every schedule here ends with an M-step on the pooled counts of the final state (6 sweeps, periods of 1 or 2 sweeps;
+    the lagged schedule applies its last pending M-step at the end): hyper = ln of the oracle's gibbs_mstep of them."""
+    from oracle import fcdiff_oracle as O
+    counts = [int(r.sum())] + [int((f == k).sum()) for k in range(3)] + [f.shape[0]]
+    (pi, gamma) = O.gibbs_mstep(counts, N, U)
+    want = np.concatenate([np.log(gamma), [np.log(1.0 - pi), np.log(pi)]])
+    np.testing.assert_allclose(hyper[0:5], want, rtol=1e-14, atol=0)
+
+
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("mstep_every,lag,direct", [(1, 0, True), (2, 0, True), (1, 0, False), (2, 1, False)])
 def test_two_gpus_equal_one_process(tmp_path, mstep_every, lag, direct):
@@ -89,6 +99,7 @@ def test_two_gpus_equal_one_process(tmp_path, mstep_every, lag, direct):
     for p in parts:
         np.testing.assert_array_equal(p["hyper"], ref["hyper"])       # the same pooled (pi, gamma) on every rank
         np.testing.assert_array_equal(p["cnt_r"], ref["cnt_r"])
+    assert_final_mstep(ref["f"], ref["r"], ref["hyper"])
 
 
 @pytest.mark.timeout(600)
@@ -124,3 +135,4 @@ def test_one_gpu_process_group_of_one_rank(tmp_path, mstep_every, lag, direct):
     assert int(b["comm_world"]) == (1 if direct else 0)            # (the library's own communicator was the one used -- or not)
     for k in ("f", "r", "hyper", "cnt_r"):
         np.testing.assert_array_equal(a[k], b[k])
+    assert_final_mstep(b["f"], b["r"], b["hyper"])

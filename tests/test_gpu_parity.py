@@ -616,9 +616,8 @@ def test_gibbs_pipelined_give_up_is_reported(env):
     c = eng.run(1, 1, mstep_every=1, want_counts=True).cpu().numpy()
     f_g, r_g = eng.export_state()
     assert c[0] == r_g.sum() and c[4] == G and [c[1 + k] for k in range(3)] == [(f_g == k).sum() for k in range(3)]
-    from fcdiff_amd.gibbs import mstep_from_counts
     (gamma, pi) = eng.hyper_values()
-    (pi_h, gamma_h) = mstep_from_counts(c, N, U)
+    (pi_h, gamma_h) = env.O.gibbs_mstep(c, N, U)
     nptest.assert_allclose(pi, pi_h, rtol=1e-14)
     nptest.assert_allclose(gamma, gamma_h, rtol=1e-14)
     ctx.close()
@@ -879,8 +878,7 @@ def test_gibbs_mstep_and_accumulate(env):
     assert c[4] == G and c[1] + c[2] + c[3] == G * eng.C and c[0] == r.sum()
     eng.mstep(counts)
     (gamma, pi) = eng.hyper_values()
-    from fcdiff_amd.gibbs import mstep_from_counts
-    (pi_h, gamma_h) = mstep_from_counts(c, N, U)
+    (pi_h, gamma_h) = env.O.gibbs_mstep(c, N, U)
     nptest.assert_allclose(pi, pi_h, rtol=1e-14)                 # fit.py:213 over chains
     nptest.assert_allclose(gamma, gamma_h, rtol=1e-14)           # fit.py:220 over chains
     nptest.assert_allclose(pi, r.mean(), rtol=1e-14)
@@ -986,11 +984,10 @@ def test_fit_gibbs_cfg3_shape_end_to_end(env):
     """
     VERDICT r3 item 6b: the path bench.py times -- UnsharedRegionFit(method='gibbs').run() -> run_chains -> fcd_gibbs_run with
     accumulation after burn-in and the (pi, gamma) M-step in every sweep's tally launch -- at BASELINE cfg 3's shape with all
-    1024 chains, against the C oracle walking the same chains with the host restatement of the M-step between sweeps:
+    1024 chains, against the C oracle walking the same chains with the oracle's M-step (gibbs_mstep) between sweeps:
     final chain state, marginal counters (a recount from the oracle's chains), pi, gamma and the fit's log-marginals.
     4 sweeps (1 burn-in): 4096 chain-sweeps of the oracle, what the suite's time budget allows.
     """
-    from fcdiff_amd.gibbs import mstep_from_counts
     (N, H, U, G, n_sweeps, burn) = (200, 50, 50, 1024, 4, 1)
     gen = env.pkg.UnsharedRegionModel()
     (_r, _t, _f, _ft, b, bt) = gen.sample_fast(N, H, U, seed=21)
@@ -1015,7 +1012,7 @@ def test_fit_gibbs_cfg3_shape_end_to_end(env):
                 cf[:, k] += (f_o == k).sum(axis=0)
             cr += r_o.sum(axis=0, dtype=np.int64)
         counts = [int(r_o.sum())] + [int((f_o == k).sum()) for k in range(3)] + [G]
-        (pi, gamma) = mstep_from_counts(counts, N, U)
+        (pi, gamma) = env.O.gibbs_mstep(counts, N, U)
     eng = fit.sampler
     (f_g, r_g) = eng.export_state()
     nptest.assert_array_equal(f_g, f_o)

@@ -80,6 +80,49 @@ def test_G7_pi_gamma():
     nptest.assert_allclose(O.update_gamma(np.log(g["q_F"])), g["gamma"], rtol=1e-14)
 
 
+def test_G7_gibbs_mstep_is_the_reference_update_at_one_hot_q():
+    """
+    The sampler's M-step (oracle gibbs_mstep, unclamped) is fit.py:208-220 at one-hot q: on q_R / q_F one-hot at a state
+    (the arg-max of the G7 fixture's q), and on the mean of the one-hot q of several chains (the updates are linear in q),
+    update_pi / update_gamma (pinned to the reference above) equal gibbs_mstep of the chains' pooled counts.
+    """
+    g = load_golden("G7_pi_gamma")
+    ((Nreg, U), C) = (g["q_R"].shape[0:2], g["q_F"].shape[0])
+    rng = np.random.RandomState(7)
+    states = [(np.argmax(g["q_F"][:, 0, :], axis=1), np.argmax(g["q_R"], axis=2))]
+    states += [(rng.randint(0, 3, size=C), (rng.rand(Nreg, U) < 0.3).astype(np.int64)) for _ in range(4)]
+    for G in (1, len(states)):
+        (f, r) = (np.array([s[0] for s in states[:G]]), np.array([s[1] for s in states[:G]]))
+        q_F = np.mean(np.eye(3)[f], axis=0)[:, None, :]                 # (C, 1, 3)
+        q_R = np.mean(np.eye(2)[r], axis=0)                             # (Nreg, U, 2)
+        counts = [int(r.sum())] + [int((f == k).sum()) for k in range(3)] + [G]
+        (pi, gamma) = O.gibbs_mstep(counts, Nreg, U, clamp=False)
+        with np.errstate(divide="ignore"):
+            nptest.assert_allclose(O.update_pi(np.log(q_R)), pi, rtol=1e-14)
+            nptest.assert_allclose(O.update_gamma(np.log(q_F)), gamma, rtol=1e-14)
+    assert 0 < pi < 1 and np.all(gamma > 0)
+
+
+@pytest.mark.parametrize("Nreg,U,G", [(5, 3, 256), (200, 50, 1 << 20)])
+def test_gibbs_mstep_host_restatement_at_the_clamps(Nreg, U, G):
+    """
+    fcdiff_amd.gibbs.mstep_from_counts (the host restatement the fit reports with) = oracle gibbs_mstep at every clamp:
+    sum r = 0 and = n_r (pi kept in [0.5/n_r, 1 - 0.5/n_r]), one and two class counts 0 (gamma_k >= 0.5/n_f, not
+    renormalised), also with G*Nreg*U and G*C above 2^31.
+    """
+    from fcdiff_amd.gibbs import mstep_from_counts
+    (nr, nf) = (G * Nreg * U, G * O.N_to_C(Nreg))
+    for counts in ([0, nf // 3, nf // 3, nf - 2 * (nf // 3), G], [nr, nf // 2, nf - nf // 2 - 1, 1, G],
+                   [nr // 3, 0, nf // 2, nf - nf // 2, G], [1, 0, nf, 0, G], [nr - 1, nf - 2, 1, 1, G]):
+        (pi, gamma) = O.gibbs_mstep(counts, Nreg, U)
+        (pi_h, gamma_h) = mstep_from_counts(counts, Nreg, U)
+        assert pi_h == pi and np.array_equal(gamma_h, gamma)
+        assert 0.5 / nr <= pi <= 1.0 - 0.5 / nr and np.all(gamma >= 0.5 / nf)
+    (pi, gamma) = O.gibbs_mstep([0, 0, nf, 0, G], Nreg, U)
+    assert pi == 0.5 / nr and gamma[0] == gamma[2] == 0.5 / nf and gamma[1] == 1.0      # the floor is not renormalised
+    assert nr > 2 ** 31 or G < 1 << 20
+
+
 def test_G8_derivative_helpers():
     g = load_golden("G8_derivatives")
     (mu, sigma, eps, eta) = (float(g["mu"]), float(g["sigma"]), float(g["epsilon"]), float(g["eta"]))
