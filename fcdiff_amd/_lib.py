@@ -84,6 +84,9 @@ SIGNATURES = {
     "fcd_gibbs_export_state": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "fcd_gibbs_import_state": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "fcd_philox_uniforms": (_int, [_p, _p, _i64, _u64, _p, _p]),
+    "fcd_gibbs_pair_tally": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p]),
+    "fcd_gibbs_set_pair_accumulator": (_int, [_p, _p, _i64, _i64, _i64]),
+    "fcd_conn_posterior": (_int, [_p, _p, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -141,6 +141,9 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->dev_err = nullptr;
     ctx->fsq = nullptr;
     ctx->fsq_bytes = 0;
+    ctx->pair_acc = nullptr;
+    ctx->pair_nreg = ctx->pair_u = 0;
+    ctx->pair_every = 1;
     ctx->acc = nullptr;
     ctx->dbg = nullptr;
     ctx->comm = nullptr;

@@ -62,6 +62,8 @@ struct fcd_ctx {
     size_t corr_tickets_n;
     void *fsq;         // square copy of the f state [w][n][m][lane] kept by fcd_gibbs_sweeps between its f and r pass
     size_t fsq_bytes;
+    uint32_t *pair_acc;            // (C, U, 3, 3) counts of (f_c, mixture case) fcd_gibbs_run adds to (fcd_gibbs_set_pair_accumulator), or nullptr
+    int64_t pair_nreg, pair_u, pair_every;
     // optional per-kernel timing with HIP events on the launch stream (fcd_prof_enable / fcd_prof_collect)
     int prof_on;
     hipEvent_t *prof_ev[FCD_PROF_SLOTS];   // pairs (begin, end)
@@ -143,6 +145,10 @@ int fcd_gibbs_r_step_sq(fcd_ctx *ctx, const double *lM, const double *lMd, const
                         const uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0,
                         uint64_t seed, int64_t sweep, int edge_mode, hipStream_t stream, const uint8_t *fsq,
                         const fcd_tally_f *tally_f = nullptr, bool *tally_f_done = nullptr, bool sentinels_in_place = false);
+// one launch of the (f_c, mixture case) count kernel of fcd_post.hip: acc (C, U, 3, 3) += counts of this state
+struct fcd_geo;
+int fcd_pair_tally_launch(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
+                          const fcd_geo &g, uint32_t *acc, hipStream_t s);
 // bracket ONE kernel launch with events when profiling is on (no-ops otherwise)
 void fcd_prof_begin(fcd_ctx *ctx, int slot, hipStream_t s);
 void fcd_prof_end(fcd_ctx *ctx, int slot, hipStream_t s);

@@ -1449,6 +1449,9 @@ extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, 
     if (!S_B || !lM || !hyper || !f_state || !r_bits) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_run: null pointer");
     if ((cnt_f == nullptr) != (cnt_r == nullptr)) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_run: cnt_f and cnt_r go together");
     if (mstep_every < 0) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_run: mstep_every < 0");
+    if (ctx->pair_acc && (ctx->pair_nreg != Nreg || ctx->pair_u != U))
+        return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_run: the attached pair accumulator was made for Nreg=%lld, U=%lld",
+                        ctx->pair_nreg, ctx->pair_u);
     hipStream_t s = (hipStream_t)stream;
     // square copy of the f state for the r pass's packing (see fcd_gibbs_sweeps)
     uint8_t *fsq = nullptr;
@@ -1521,6 +1524,11 @@ extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, 
         } else if (cts && ctx->comm) {
             // (counts asked for without an M-step in this sweep: pooled all the same -- what a caller of several ranks expects)
             rc = fcd_comm_allreduce_counts(ctx, (long long *)cts, s);
+            if (rc) return rc;
+        }
+        // (f_c, mixture case) counts of the end-of-sweep state (fcd_gibbs_set_pair_accumulator): one launch of its own
+        if (ctx->pair_acc && sweep0 + i >= accumulate_from && (sweep0 + i - accumulate_from) % ctx->pair_every == 0) {
+            rc = fcd_pair_tally_launch(ctx, f_state, r_bits, Nreg, U, G, g, ctx->pair_acc, s);
             if (rc) return rc;
         }
         ru_ready = r_U_next != nullptr;

@@ -15,6 +15,7 @@ New knobs (all optional; defaults reproduce the reference):
                  'symmetric' (doc/methods.rst:646-653).  Default: 'reference' for vb, 'symmetric' for gibbs.
     n_chains, n_sweeps, burn_in, mstep_every, mstep_lag, seed, chain0     sampler controls
     update_theta_sub, theta_sub_every                          (eta, epsilon) step: vb every iteration / gibbs every K sweeps
+    connection_marginals, connection_every                     gibbs: count (f_c, mixture case) for connection_posterior()
 
 Differences from the reference that are deliberate and documented:
   Q4  `model.pi` may be the scalar the model defines or the 2-vector [1-pi, pi] the reference's updates
@@ -30,7 +31,7 @@ import numpy as np
 
 from . import _lib
 from . import util
-from .gibbs import GibbsEngine, run_chains, allreduce_counts
+from .gibbs import GibbsEngine, run_chains, allreduce_counts, pair_sweeps_in, PAIR_COUNT_MAX
 
 
 class UnsharedRegionFit(object):
@@ -72,6 +73,10 @@ class UnsharedRegionFit(object):
         self.seed = 0
         self.chain0 = 0
         self.sampler = None       # the GibbsEngine of the last gibbs run
+        self.connection_marginals = False   # gibbs: accumulate (f_c, mixture case) counts for connection_posterior()
+        self.connection_every = 1           # ... at every this many sweeps from burn_in on
+        self.connection_counts = None       # (C, U, 3, 3) int64: those counts, pooled over chains, sweeps and ranks
+        self.connection_sweeps = 0          # number of sweeps behind connection_counts (each counts every chain once)
 
         self._ctx = None
         self._d = {}              # device tensors: lq_R, lq_F, S_B, lM, lpB, pBt, hyper, b, bt
@@ -488,8 +493,20 @@ class UnsharedRegionFit(object):
         log-joint at the recorded sweeps.
         """
         t = self._torch()
+        self.connection_counts = None
+        self.connection_sweeps = 0
+        if self.connection_marginals:
+            every = int(self.connection_every)
+            if every < 1 or every != self.connection_every:
+                raise ValueError("connection_every must be an integer >= 1")
+            n_acc = pair_sweeps_in(0, int(self.n_sweeps), int(self.burn_in), every)
+            if n_acc * int(self.n_chains) > PAIR_COUNT_MAX:
+                raise ValueError("connection counts would overflow uint32: %d chains x %d accumulated sweeps; raise "
+                                 "connection_every" % (self.n_chains, n_acc))
         eng = GibbsEngine(self._d["S_B"], self._d["lM"], N, U, self.n_chains, chain0=self.chain0, seed=self.seed,
                           edge_index=self._edge_mode(), ctx=self._context())
+        if self.connection_marginals:
+            eng.attach_pair_accumulator(self.connection_every)
         pi2 = self._pi2()
         eng.set_hyper(np.asarray(self.model.gamma, dtype=np.float64), pi2)
         eng.init(float(pi2[1]))
@@ -540,9 +557,89 @@ class UnsharedRegionFit(object):
             self._lq_F = np.log(cnt[:3 * C].reshape(C, 1, 3) / total)
             p1 = cnt[3 * C:3 * C + N * U].reshape(N, U) / total
             self._lq_R = np.log(np.stack([1.0 - p1, p1], axis=2))
+        if eng.pair_acc is not None:
+            # (uint32 on the device; pooled over ranks as int64)
+            pc = allreduce_counts(eng.pair_acc.to(t.int64) & 0xFFFFFFFF)
+            self.connection_counts = pc.cpu().numpy()
+            self.connection_sweeps = eng.pair_sweeps
         (gamma, pi) = eng.hyper_values()
         self.model.gamma = gamma
         self.model.pi = pi
+
+    # ------------------------------------------------------------------ connection-level posteriors
+    def connection_posterior(self):
+        """
+        Posterior of the anomalous connections and of each patient's connection state, per connection and patient (edge
+        order of `b` / `bt`), from the last run():
+            p_T        (C, U)     P(T_cu = 1 | data)
+            p_F_tilde  (C, U, 3)  P(F~_cu = j | data), j = negative, none, positive (rows sum to 1)
+            p_changed  (C, U)     P(F~_cu != F_c | data)
+        as a dict of float64 arrays.  Given f_c = k, the mixture case l of (r_n, r_m) -- n, m the true endpoints of c, in
+        either edge-id mode -- and bt_cu, T and F~ have a closed-form law (doc/methods.rst:70-177); it is averaged over
+        the fit's posterior of (f_c, l_cu) with theta = the model's CURRENT parameters (the plug-in convention of _lq_F /
+        _lq_R):
+          method='vb'     the mean-field weights q_F[c,k] w_l(c,u) of _lq_F, _lq_R (computed on demand);
+          method='gibbs'  the counts of (f_c = k, l_cu = l) over chains and the sweeps from burn_in on, every
+                          `connection_every`-th (Rao-Blackwellised).  Needs `connection_marginals = True` before run();
+                          raises ValueError otherwise.  The counts are kept as `connection_counts` (C, U, 3, 3), the
+                          number of sweeps behind them as `connection_sweeps`.  With
+                          update_theta_sub and theta_sub_every, counts made under earlier (eta, epsilon) are contracted
+                          with the final theta all the same.
+        """
+        t = self._torch()
+        if self.model is None or self.bt is None:
+            raise ValueError("connection_posterior() needs a model and bt: call run() first")
+        if self.method == "gibbs":
+            cnt = self.connection_counts
+            if cnt is None:
+                raise ValueError("no connection counts: set connection_marginals = True before run(method='gibbs')")
+            cnt = np.asarray(cnt)
+            if int(cnt[0, 0].sum()) == 0:
+                raise ValueError("no sweep was accumulated into the connection counts (n_sweeps <= burn_in?)")
+            if int(cnt.max()) > PAIR_COUNT_MAX:
+                raise ValueError("pooled connection counts exceed uint32; raise connection_every")
+            (N, C, U) = (util.C_to_N(cnt.shape[0]), cnt.shape[0], cnt.shape[1])
+            counts = t.as_tensor(np.ascontiguousarray(cnt.astype(np.uint32).view(np.int32)), device=self._dev())
+            return conn_posterior(self._context(), self._bt_dev(C, U), int(N), U, self.model.theta(), counts=counts)
+        if self.method != "vb":
+            raise ValueError("method must be 'vb' or 'gibbs'")
+        (N, C, U) = self._check_state(need=("lq_R", "lq_F"))
+        return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), lq_F=self._d["lq_F"],
+                              lq_R=self._d["lq_R"])
+
+    def _bt_dev(self, C, U):
+        bt = self._d.get("bt")
+        if bt is None or tuple(bt.shape) != (C, U):
+            bt = self._up(self.bt)
+            if tuple(bt.shape) != (C, U):
+                raise ValueError("bt has shape %s, the fit's state needs %s" % (tuple(bt.shape), (C, U)))
+        return bt
+
+
+def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=None):
+    """
+    {p_T (C,U), p_F_tilde (C,U,3), p_changed (C,U)} as NumPy float64 through fcd_conn_posterior: weights from `counts`
+    (C,U,3,3) uint32 (held in an int32 tensor), or from the log-probabilities lq_F (C,1,3) and lq_R (Nreg,U,2).
+    """
+    import torch
+    C = util.N_to_C(int(Nreg))
+    dev = bt_dev.device
+    if tuple(bt_dev.shape) != (C, U) or bt_dev.dtype != torch.float64:
+        raise ValueError("bt must be float64 (C, U) = %s" % ((C, U),))
+    if counts is not None:
+        if tuple(counts.shape) != (C, U, 3, 3) or counts.element_size() != 4:
+            raise ValueError("counts must be 32-bit (C, U, 3, 3)")
+    elif lq_F is None or lq_R is None or tuple(lq_F.shape) != (C, 1, 3) or tuple(lq_R.shape) != (Nreg, U, 2):
+        raise ValueError("lq_F must be (C, 1, 3) and lq_R (Nreg, U, 2)")
+    p_T = torch.empty((C, U), dtype=torch.float64, device=dev)
+    p_Ft = torch.empty((C, U, 3), dtype=torch.float64, device=dev)
+    p_ch = torch.empty((C, U), dtype=torch.float64, device=dev)
+    (th, _th) = _lib.dbl_array(theta)
+    ctx.call("fcd_conn_posterior", _lib.dptr(bt_dev.contiguous()), int(Nreg), int(U), th,
+             _lib.dptr(None if counts is None else counts.contiguous()),
+             _lib.dptr(None if lq_F is None else lq_F.contiguous()), _lib.dptr(None if lq_R is None else lq_R.contiguous()),
+             _lib.dptr(p_T), _lib.dptr(p_Ft), _lib.dptr(p_ch), _lib.stream_ptr())
+    return {"p_T": p_T.cpu().numpy(), "p_F_tilde": p_Ft.cpu().numpy(), "p_changed": p_ch.cpu().numpy()}
 
 
 def theta_sub_objective(ctx, bt_dev, W, theta, reduce=None):

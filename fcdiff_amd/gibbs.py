@@ -18,6 +18,17 @@ from . import _lib
 from . import util
 
 
+PAIR_COUNT_MAX = (1 << 32) - 1
+
+
+def pair_sweeps_in(sweep0, n_sweeps, accumulate_from, every):
+    """Number of sweeps s in [sweep0, sweep0 + n_sweeps) with s >= accumulate_from and (s - accumulate_from) % every == 0."""
+    end = sweep0 + n_sweeps
+    first = max(sweep0, accumulate_from)
+    first = accumulate_from + -(-(first - accumulate_from) // every) * every
+    return 0 if first >= end else (end - first + every - 1) // every
+
+
 def shard_chains(total_chains, world_size, rank):
     """Contiguous split of global chain ids: returns (chain0, n_local).  Earlier ranks take the remainder."""
     base, rem = divmod(int(total_chains), int(world_size))
@@ -76,6 +87,9 @@ class GibbsEngine(object):
         self.cnt_f = torch.zeros((self.C, 3), dtype=torch.int32, device=dev)
         self.cnt_r = torch.zeros((self.Nreg, self.U), dtype=torch.int32, device=dev)
         self.n_accumulated = 0
+        self.pair_acc = None        # (C, U, 3, 3) counts of (f_c, mixture case) that run() adds to (attach_pair_accumulator)
+        self.pair_every = 1
+        self.pair_sweeps = 0        # sweeps added to pair_acc so far
         self.ctx.call("fcd_ctx_reserve", self.Nreg, self.U, self.G)
         self.lMd = self.lMf = None
         if region_major:
@@ -158,16 +172,67 @@ class GibbsEngine(object):
         counters from sweep `accumulate_from` on (None: never), runs the (pi, gamma) M-step on this rank's pooled counts
         every `mstep_every` sweeps (0: never -- several ranks all-reduce the returned counts and call mstep()), and
         packs the r words of the next f pass.  Returns the counts tensor of the last sweep (or None).
+        With a pair accumulator attached (attach_pair_accumulator) the same call also adds the (f_c, mixture case) counts
+        of every `pair_every`-th sweep from `accumulate_from` on; a call that could overflow them raises ValueError.
         """
+        acc = accumulate_from is not None
+        n_pair = 0
+        if self.pair_acc is not None and acc:
+            n_pair = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), self.pair_every)
+            if (self.pair_sweeps + n_pair) * self.G > PAIR_COUNT_MAX:
+                raise ValueError("the pair accumulator would overflow uint32: %d chains x %d accumulated sweeps > %d"
+                                 % (self.G, self.pair_sweeps + n_pair, PAIR_COUNT_MAX))
+            self.ctx.call("fcd_gibbs_set_pair_accumulator", _lib.dptr(self.pair_acc), self.Nreg, self.U, self.pair_every)
+        try:
+            self._run(sweep0, n_sweeps, mstep_every, accumulate_from, want_counts)
+        finally:
+            if self.pair_acc is not None and acc:
+                # (attached for this call only: the context is shared, no other engine's sweeps may add to this buffer)
+                self.ctx.call("fcd_gibbs_set_pair_accumulator", None, 0, 0, 1)
+        self.pair_sweeps += n_pair
+        if acc:
+            self.n_accumulated += max(0, int(sweep0) + int(n_sweeps) - max(int(accumulate_from), int(sweep0)))
+        return self.counts if want_counts else None
+
+    def _run(self, sweep0, n_sweeps, mstep_every, accumulate_from, want_counts):
         acc = accumulate_from is not None
         self.ctx.call("fcd_gibbs_run", _lib.dptr(self.S_B), _lib.dptr(self.lM), _lib.dptr(self.lMf), _lib.dptr(self.lMd),
                       _lib.dptr(self.hyper), _lib.dptr(self.f_state), _lib.dptr(self.r_bits), self.Nreg, self.U, self.G,
                       self.chain0, C.c_uint64(self.seed), int(sweep0), int(n_sweeps), self.edge_mode, int(mstep_every),
                       int(accumulate_from) if acc else 0, _lib.dptr(self.counts if want_counts else None),
                       _lib.dptr(self.cnt_f if acc else None), _lib.dptr(self.cnt_r if acc else None), _lib.stream_ptr())
-        if acc:
-            self.n_accumulated += max(0, int(sweep0) + int(n_sweeps) - max(int(accumulate_from), int(sweep0)))
-        return self.counts if want_counts else None
+
+    # ---- (f_c, mixture case) counts for the connection posteriors ----
+    def attach_pair_accumulator(self, every=1):
+        """
+        From now on run() adds the end-of-sweep counts of (f_c = k, mixture case l at (c,u)) to `pair_acc` (C, U, 3, 3),
+        at every `every`-th sweep from its `accumulate_from` on (none when accumulate_from is None).  Zeroes the counts.
+        """
+        every = int(every)
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        t = self.torch
+        # (uint32 on the device, held in an int32 tensor like cnt_f; pair_counts_host() reads it back as uint32)
+        self.pair_acc = t.zeros((self.C, self.U, 3, 3), dtype=t.int32, device=self.f_state.device)
+        self.pair_every = every
+        self.pair_sweeps = 0
+        return self.pair_acc
+
+    def detach_pair_accumulator(self):
+        self.pair_acc = None
+        self.pair_sweeps = 0
+
+    def pair_counts_host(self):
+        """The attached accumulator as a NumPy uint32 array (C, U, 3, 3)."""
+        if self.pair_acc is None:
+            raise ValueError("no pair accumulator is attached")
+        return self.host(self.pair_acc).view(np.uint32)
+
+    def pair_tally(self, acc):
+        """acc (C, U, 3, 3) uint32-in-int32 tensor += the (f_c, mixture case) counts of the current state."""
+        self.ctx.call("fcd_gibbs_pair_tally", _lib.dptr(self.f_state), _lib.dptr(self.r_bits), self.Nreg, self.U, self.G,
+                      _lib.dptr(acc), _lib.stream_ptr())
+        return acc
 
     # ---- pooled statistics / M-step ----
     def stats(self):

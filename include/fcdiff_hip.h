@@ -294,6 +294,27 @@ int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, const doubl
                   uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0, uint64_t seed,
                   int64_t sweep0, int64_t n_sweeps, int edge_mode, int64_t mstep_every, int64_t accumulate_from,
                   int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r, fcd_stream stream);
+/* ---- connection-level posteriors (T and F~ of each connection and patient) -------------------------------
+ * Both fitters integrate T and F~ out into M_kl (doc/methods.rst:248-349); given f_c = k, the mixture case l of the
+ * TRUE endpoints of c (both edge-id modes) and bt_cu their law is closed-form, so a fit only has to average three
+ * tables over its posterior of (f_c, l_cu).
+ *
+ * Counts of (f_c = k, l_cu = l) over chains: acc (C, U, 3, 3) uint32, acc[c,u,k,l] += #{chains with f_c = k and mixture
+ * case l at (c,u)} of the current state (the integers fcd_gibbs_pair_counts gives as doubles). */
+int fcd_gibbs_pair_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U,
+                         int64_t G, uint32_t *acc, fcd_stream stream);
+/* Attach acc (C, U, 3, 3) uint32 for shape (Nreg, U) to the context (no device work; acc == NULL detaches): from then on
+ * every sweep s of fcd_gibbs_run with s >= accumulate_from and (s - accumulate_from) % every == 0 adds its end-of-sweep
+ * state to acc (one extra launch after the sweep's tally).  fcd_gibbs_run refuses another shape while it is attached.
+ * The caller keeps sweeps x G below 2^32. */
+int fcd_gibbs_set_pair_accumulator(fcd_ctx *ctx, uint32_t *acc, int64_t Nreg, int64_t U, int64_t every);
+/* p_T (C, U) = P(T = 1), p_F_tilde (C, U, 3) = P(F~ = j), p_changed (C, U) = P(F~ != F) for weights over (k, l) of
+ *   counts != NULL:          counts (C, U, 3, 3) uint32, normalised per (c, u) by their sum (sampler), or
+ *   counts == NULL:          q_F[c,k] w_l(c,u) from lq_F (C, 1, 3) and lq_R (Nreg, U, 2) (variational fit),
+ * bt (C, U) and theta12_host as in fcd_lik_tables.  fp64; finite where all three densities underflow. */
+int fcd_conn_posterior(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, const double *theta12_host,
+                       const uint32_t *counts, const double *lq_F, const double *lq_R, double *p_T, double *p_F_tilde,
+                       double *p_changed, fcd_stream stream);
 /* log p(f, r, b, bt; theta) of each chain = minus the first four terms of fit.py:149-152 at one-hot q.
  * out (G,) doubles. */
 int fcd_gibbs_logjoint(fcd_ctx *ctx, const double *S_B, const double *lM, const double *hyper,
