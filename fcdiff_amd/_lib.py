@@ -22,6 +22,7 @@ FCD_COMM_ID_BYTES = 128
 EDGE_REFERENCE = 0
 EDGE_SYMMETRIC = 1
 EDGE_MODES = {"reference": EDGE_REFERENCE, "symmetric": EDGE_SYMMETRIC}
+FCD_DATA_NAN_MISSING = 1      # flags of the *_ex entry points: NaN in b / bt is unobserved and integrated out
 ABI_VERSION = 4
 
 _p = C.c_void_p
@@ -55,6 +56,7 @@ SIGNATURES = {
     "fcd_c_to_nm": (_int, [_i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "fcd_hyper_set": (_int, [_p, _p, C.POINTER(_dbl), C.POINTER(_dbl), _p]),
     "fcd_lik_tables": (_int, [_p, _p, _p, _i64, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _p, _p]),
+    "fcd_lik_tables_ex": (_int, [_p, _p, _p, _i64, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _p, _int, _p, _p]),
     "fcd_model_sample": (_int, [_p, C.POINTER(_dbl), _i64, _i64, _i64, _u64, _p, _p, _p, _p, _p, _p, _p]),
     "fcd_corr_edges": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
     "fcd_vb_update_qF": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
@@ -65,6 +67,8 @@ SIGNATURES = {
     "fcd_gibbs_pair_counts": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _p, _p]),
     "fcd_theta_sub_objective": (_int, [_p, _p, _p, _i64, _i64, C.POINTER(_dbl), _p, _p]),
     "fcd_theta_full_objective": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, C.POINTER(_dbl), _p, _p]),
+    "fcd_theta_sub_objective_ex": (_int, [_p, _p, _p, _i64, _i64, C.POINTER(_dbl), _int, _p, _p]),
+    "fcd_theta_full_objective_ex": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, C.POINTER(_dbl), _int, _p, _p]),
     "fcd_gibbs_state_size": (_int, [_i64, _i64, _i64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "fcd_gibbs_init": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _u64, _dbl, _p]),
     "fcd_gibbs_edge_tables": (_int, [_p, _p, _i64, _i64, _p, _p]),
@@ -87,6 +91,7 @@ SIGNATURES = {
     "fcd_gibbs_pair_tally": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p]),
     "fcd_gibbs_set_pair_accumulator": (_int, [_p, _p, _i64, _i64, _i64]),
     "fcd_conn_posterior": (_int, [_p, _p, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _p, _p, _p, _p]),
+    "fcd_conn_posterior_ex": (_int, [_p, _p, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _int, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -12,7 +12,9 @@ def correlations(ts, fisher_z=False, ctx=None, as_numpy=True):
     """
     ts : (S, Nreg, T) float64 time series of S subjects.
     Returns (C, S) float64, row c = n(n-1)/2 + m (n > m, util.c_to_nm order), column = subject:
-    `b = out[:, healthy]`, `bt = out[:, patients]` can go straight into UnsharedRegionFit.
+    `b = out[:, healthy]`, `bt = out[:, patients]` can go straight into UnsharedRegionFit.  The edges of a constant series
+    are NaN, as numpy.corrcoef gives them: they are meant to go into a fit with `missing_data = True`, which integrates
+    them out.
     fisher_z applies atanh (default off: the model's defaults are on raw correlations, model.py:213, 236).
     """
     import torch

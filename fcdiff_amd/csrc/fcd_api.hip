@@ -145,6 +145,7 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->pair_nreg = ctx->pair_u = 0;
     ctx->pair_every = 1;
     ctx->acc = nullptr;
+    ctx->nan_slots = nullptr;
     ctx->dbg = nullptr;
     ctx->comm = nullptr;
     ctx->comm_world = ctx->comm_rank = 0;
@@ -199,6 +200,9 @@ int fcd_ctx_create(fcd_ctx **out) {
         if (e == hipSuccess) e = hipMalloc(&ctx->acc, 8 * sizeof(unsigned long long));
         ctx->n_alloc += 1;
         if (e == hipSuccess) e = hipMemset(ctx->acc, 0, 8 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMalloc(&ctx->nan_slots, FCD_NAN_SLOTS * 16 * sizeof(unsigned long long));
+        ctx->n_alloc += 1;
+        if (e == hipSuccess) e = hipMemset(ctx->nan_slots, 0, FCD_NAN_SLOTS * 16 * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipMalloc(&ctx->dbg, 8 * sizeof(unsigned long long));
         ctx->n_alloc += 1;
         if (e == hipSuccess) e = hipMemset(ctx->dbg, 0, 8 * sizeof(unsigned long long));
@@ -221,6 +225,7 @@ int fcd_ctx_destroy(fcd_ctx *ctx) {
     if (ctx->dev_err) (void)hipHostFree((void *)ctx->dev_err);
     if (ctx->fsq) (void)hipFree(ctx->fsq);
     if (ctx->acc) (void)hipFree(ctx->acc);
+    if (ctx->nan_slots) (void)hipFree(ctx->nan_slots);
     if (ctx->dbg) (void)hipFree(ctx->dbg);
     if (ctx->corr_tickets) (void)hipFree(ctx->corr_tickets);
     for (int i = 0; i < FCD_PROF_SLOTS; ++i) {
@@ -277,6 +282,7 @@ int fcd_ctx_clear_error(fcd_ctx *ctx) {
     if (ctx->dev_err) *ctx->dev_err = 0u;
     // whatever an abandoned launch left in the context-owned accumulators / tickets (zero between launches by contract)
     if (ctx->acc) FCD_HIP_TRY(hipMemset(ctx->acc, 0, 8 * sizeof(unsigned long long)));
+    if (ctx->nan_slots) FCD_HIP_TRY(hipMemset(ctx->nan_slots, 0, FCD_NAN_SLOTS * 16 * sizeof(unsigned long long)));
     if (ctx->corr_tickets && ctx->corr_tickets_n > 0)
         FCD_HIP_TRY(hipMemset(ctx->corr_tickets, 0, (size_t)ctx->corr_tickets_n * sizeof(unsigned)));
     return FCD_OK;

@@ -38,6 +38,8 @@ struct fcd_knobs {
 enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA_F_PAIR_BIG = FCD_KA_F_PAIR + 4,
        FCD_KA_R_STEP = FCD_KA_F_PAIR_BIG + 4, FCD_KA_R_PIPE = FCD_KA_R_STEP + 4, FCD_KA_CORR = FCD_KA_R_PIPE + 4, FCD_KA_N = FCD_KA_CORR + 1 };
 
+#define FCD_NAN_SLOTS 256
+
 struct fcd_ctx {
     int device;
     int num_cu;
@@ -53,6 +55,8 @@ struct fcd_ctx {
     void *log_tab;     // K_lik tables (fcd_fastmath.h): 64 x 2^(-j/64), 512 x {1/m_i, log m_i} (device, 8.5 KiB)
     volatile unsigned *dev_err;   // pinned host word: error word of the one-launch r pass, copied back after each pass
     void *acc;         // 8 x uint64, zero between launches: the tally's pooled sums [0..3] and its ticket [4]
+    void *nan_slots;   // FCD_NAN_SLOTS 128-byte lines of 16 x uint64, zero between launches: K_lik's per-block NaN counts
+                       // ([0] b, [1] bt of a line), spread so that its blocks do not queue on one address
     void *comm;        // ncclComm_t of the context (fcd_comm_init), or nullptr: fcd_gibbs_run pools its M-step counts over it
     int comm_world, comm_rank;
     void *pool_counts; // 8 x int64 (device): the counts vector the all-reduce works on in place

@@ -46,19 +46,34 @@ struct LikTabs {
 // Blocks [0, n_bt_blocks): one thread per (c,u) item; the block's 256 x 9 results are transposed through LDS so that
 //   the 72-byte records leave as fully coalesced 16-byte-per-lane stores (grid-stride over tiles of 256 items).
 // Blocks [n_bt_blocks, ...): 16 lanes per edge, S_B[c,k] = sum_h ( -z*z/2 - log(sqrt(2 pi)) - log(sigma_k) )  (fit.py:114, :171)
+//
+// MISSING (FCD_DATA_NAN_MISSING): a NaN of b or bt is unobserved and integrated out.  Both densities integrate to 1, so
+// a NaN b adds 0 to every S_B[c,k] (and lpB holds 0), and a NaN bt has N_j = 1 for every j, M_kl = e_l + (1 - e_l) = 1
+// and lM = 0 exactly (pBt holds 1).  Each block adds its NaN count to its slot line of `nan_slots` (fcd_ctx: [0] b, [1]
+// bt) with one atomic; nan_fold_kernel sums the lines.  (One address for all ~5 100 blocks at cfg3: 69.5 against 24.6 us
+// per counted build; 256 lines: 30-64 us in two runs, while the table kernel itself takes 24.8 us -- the fold waits for
+// the atomics.  profiles/missing_data_cost.txt; the fit counts only when it uploads the data.)  nan_slots == nullptr: not
+// counted.  MISSING = false never reads nan_slots: it is the kernel as it was before the flag existed, instruction for
+// instruction.
+template <bool MISSING>
 __global__ __launch_bounds__(LIK_BLOCK) void lik_kernel(const double *__restrict__ bt, int64_t n_items, LikTheta th,
                                                         const LikTabs *__restrict__ tabs, double *__restrict__ lM,
                                                         double *__restrict__ pBt, int n_bt_blocks,
                                                         const double *__restrict__ b, int64_t C, int H,
-                                                        double *__restrict__ S_B, double *__restrict__ lpB) {
+                                                        double *__restrict__ S_B, double *__restrict__ lpB,
+                                                        unsigned long long *__restrict__ nan_slots) {
     __shared__ double stage[LIK_BLOCK * 9];
     __shared__ __attribute__((aligned(16))) fcd_log_cell ltab[FCD_LOG_CELLS];
     __shared__ double etab[FCD_EXP_CELLS];
+    __shared__ int blk_nan;                // (MISSING: this block's NaN count -- 4 bytes: 6 blocks of this kernel fill a CU's
+                                           //  LDS to within 1 KiB, a workgroup reduction's scratch would leave room for 5)
     const int tid = threadIdx.x;
     if ((int)blockIdx.x >= n_bt_blocks) {
         const int sub = tid & 15;
         const int64_t c = (int64_t)(blockIdx.x - n_bt_blocks) * 16 + (tid >> 4);
         double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        int nan_b = 0;
+        if (MISSING && tid == 0) blk_nan = 0;
         if (c < C) {
             const double *row = b + c * H;
             for (int h = sub; h < H; h += 16) {
@@ -66,9 +81,16 @@ __global__ __launch_bounds__(LIK_BLOCK) void lik_kernel(const double *__restrict
                 const double z0 = (x - th.mu[0]) / th.sigma[0];
                 const double z1 = (x - th.mu[1]) / th.sigma[1];
                 const double z2 = (x - th.mu[2]) / th.sigma[2];
-                const double l0 = -(z0 * z0) / 2.0 - kLogSqrt2Pi - th.lnsigma[0];
-                const double l1 = -(z1 * z1) / 2.0 - kLogSqrt2Pi - th.lnsigma[1];
-                const double l2 = -(z2 * z2) / 2.0 - kLogSqrt2Pi - th.lnsigma[2];
+                double l0 = -(z0 * z0) / 2.0 - kLogSqrt2Pi - th.lnsigma[0];
+                double l1 = -(z1 * z1) / 2.0 - kLogSqrt2Pi - th.lnsigma[1];
+                double l2 = -(z2 * z2) / 2.0 - kLogSqrt2Pi - th.lnsigma[2];
+                if (MISSING) {
+                    const bool miss = __builtin_isnan(x);        // unobserved: ln N integrates to ln 1 = 0
+                    l0 = miss ? 0.0 : l0;
+                    l1 = miss ? 0.0 : l1;
+                    l2 = miss ? 0.0 : l2;
+                    nan_b += miss;
+                }
                 if (lpB) {
                     double *o = lpB + (c * H + h) * 3;
                     o[0] = l0; o[1] = l1; o[2] = l2;
@@ -87,17 +109,34 @@ __global__ __launch_bounds__(LIK_BLOCK) void lik_kernel(const double *__restrict
             S_B[c * 3 + 1] = s1;
             S_B[c * 3 + 2] = s2;
         }
+        if (MISSING) {
+            __syncthreads();
+            if (nan_b) atomicAdd(&blk_nan, nan_b);
+            __syncthreads();
+            if (tid == 0 && blk_nan && nan_slots)
+                atomicAdd(&nan_slots[(blockIdx.x % FCD_NAN_SLOTS) * 16 + 0], (unsigned long long)blk_nan);
+        }
         return;
     }
     for (int t = tid; t < FCD_LOG_CELLS; t += LIK_BLOCK) ltab[t] = tabs->log_tab[t];
     if (tid < FCD_EXP_CELLS) etab[tid] = tabs->exp_tab[tid];
+    if (MISSING && tid == 0) blk_nan = 0;
     __syncthreads();
     const int64_t n_tiles = (n_items + LIK_BLOCK - 1) / LIK_BLOCK;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += n_bt_blocks) {
         const int64_t base = tile * LIK_BLOCK;
         const int64_t i = base + tid;
+        bool miss = false;
         if (i < n_items) {
-            const double x = bt[i];        // (a non-temporal load here: 27.6 against 24.4 us at cfg3, 425 against 434 us at cfg5)
+            double x = bt[i];              // (a non-temporal load here: 27.6 against 24.4 us at cfg3, 425 against 434 us at cfg5)
+            if (MISSING) {
+                // unobserved: N_j = 1 for every j, so M_kl = e_l + (1 - e_l) = 1 and lM = 0 -- stored as 0.0 (not as a log
+                // that is 0 only up to rounding) over the results of a finite stand-in value: a compare and selects, no
+                // divergent branch
+                miss = __builtin_isnan(x);
+                x = miss ? th.mu[0] : x;
+                if (miss) atomicAdd(&blk_nan, 1);
+            }
             double N[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -115,9 +154,9 @@ __global__ __launch_bounds__(LIK_BLOCK) void lik_kernel(const double *__restrict
                 }
             }
             if (pBt) {
-                pBt[i * 3 + 0] = N[0];
-                pBt[i * 3 + 1] = N[1];
-                pBt[i * 3 + 2] = N[2];
+                pBt[i * 3 + 0] = miss ? 1.0 : N[0];
+                pBt[i * 3 + 1] = miss ? 1.0 : N[1];
+                pBt[i * 3 + 2] = miss ? 1.0 : N[2];
             }
             // js = the two other components in ascending order (fit.py:428-429)
             const double others[3] = {N[1] + N[2], N[0] + N[2], N[0] + N[1]};
@@ -129,7 +168,8 @@ __global__ __launch_bounds__(LIK_BLOCK) void lik_kernel(const double *__restrict
 #pragma unroll
                     for (int l = 0; l < 3; ++l) {
                         const double M = th.eps[l] * N[k] + th.omeps_half[l] * others[k];  // fit.py:430
-                        stage[tid * 9 + k * 3 + l] = fcd_log_normal(M, ltab);              // fit.py:122
+                        const double v = fcd_log_normal(M, ltab);                          // fit.py:122
+                        stage[tid * 9 + k * 3 + l] = miss ? 0.0 : v;
                     }
                 }
             } else {
@@ -139,7 +179,8 @@ __global__ __launch_bounds__(LIK_BLOCK) void lik_kernel(const double *__restrict
 #pragma unroll
                     for (int l = 0; l < 3; ++l) {
                         const double M = th.eps[l] * N[k] + th.omeps_half[l] * others[k];
-                        stage[tid * 9 + k * 3 + l] = log(M);
+                        const double v = log(M);
+                        stage[tid * 9 + k * 3 + l] = miss ? 0.0 : v;
                     }
                 }
             }
@@ -162,14 +203,42 @@ __global__ __launch_bounds__(LIK_BLOCK) void lik_kernel(const double *__restrict
         if ((n_dbl & 1) && tid == 0) dst[n_dbl - 1] = stage[n_dbl - 1];
         __syncthreads();
     }
+    if (MISSING && tid == 0 && blk_nan && nan_slots)
+        atomicAdd(&nan_slots[(blockIdx.x % FCD_NAN_SLOTS) * 16 + 1], (unsigned long long)blk_nan);
+}
+
+// n_missing2 = the sums of the slot lines, which are left zero again (one block of FCD_NAN_SLOTS threads)
+__global__ __launch_bounds__(FCD_NAN_SLOTS) void nan_fold_kernel(unsigned long long *__restrict__ nan_slots,
+                                                                 int64_t *__restrict__ n_missing2) {
+    __shared__ unsigned long long part[FCD_NAN_SLOTS / 64][2];
+    unsigned long long *line = nan_slots + threadIdx.x * 16;
+    unsigned long long v[2] = {line[0], line[1]};
+    line[0] = 0;
+    line[1] = 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        for (int o = 32; o > 0; o >>= 1) v[j] += __shfl_xor(v[j], o);
+        if (lane == 0) part[wave][j] = v[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        unsigned long long t = 0;
+        for (int q = 0; q < FCD_NAN_SLOTS / 64; ++q) t += part[q][threadIdx.x];
+        n_missing2[threadIdx.x] = (int64_t)t;
+    }
 }
 
 }  // namespace
 
-extern "C" int fcd_lik_tables(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
-                              const double *theta, double *S_B, double *lM, double *lp_B_g_F,
-                              double *p_Bt_g_Ft, fcd_stream stream) {
+extern "C" int fcd_lik_tables_ex(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                 const double *theta, double *S_B, double *lM, double *lp_B_g_F, double *p_Bt_g_Ft,
+                                 int flags, int64_t *n_missing2, fcd_stream stream) {
     if (!ctx || !b || !bt || !theta || !S_B || !lM) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_lik_tables: null pointer");
+    if (flags & ~FCD_DATA_NAN_MISSING) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_lik_tables_ex: unknown flags 0x%x", flags);
+    const bool missing = (flags & FCD_DATA_NAN_MISSING) != 0;
+    if (n_missing2 && !missing)
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_lik_tables_ex: missing counts need FCD_DATA_NAN_MISSING");
     if (C < 1 || H < 1 || U < 1) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_lik_tables: C=%lld H=%lld must be >= 1", C, H);
     if (fcd_C_to_N(C) < 0) return fcd_fail(ctx, FCD_ERR_SHAPE, "Number of connections (%lld) must be a triangular number.", C);
     if (H > INT32_MAX || U > INT32_MAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_lik_tables: H/U too large");
@@ -203,10 +272,27 @@ extern "C" int fcd_lik_tables(fcd_ctx *ctx, const double *b, const double *bt, i
     const int64_t cap = (int64_t)ctx->num_cu * 16;   // (5 per CU, all resident, each copying the tables once: the same 26 us
     if (grid > cap) grid = cap;                      //  at cfg3 and 4 % slower at cfg5 -- queued blocks even out the tail)
     const int64_t n_b_blocks = (C + 15) / 16;
+    unsigned long long *slots = n_missing2 ? reinterpret_cast<unsigned long long *>(ctx->nan_slots) : nullptr;
     fcd_prof_begin(ctx, FCD_PROF_LIK, s);
-    hipLaunchKernelGGL(lik_kernel, dim3((unsigned)(grid + n_b_blocks)), dim3(LIK_BLOCK), 0, s, bt, n_items, th,
-                       reinterpret_cast<const LikTabs *>(ctx->log_tab), lM, p_Bt_g_Ft, (int)grid, b, C, (int)H, S_B, lp_B_g_F);
+    if (missing)
+        hipLaunchKernelGGL(lik_kernel<true>, dim3((unsigned)(grid + n_b_blocks)), dim3(LIK_BLOCK), 0, s, bt, n_items, th,
+                           reinterpret_cast<const LikTabs *>(ctx->log_tab), lM, p_Bt_g_Ft, (int)grid, b, C, (int)H, S_B,
+                           lp_B_g_F, slots);
+    else
+        hipLaunchKernelGGL(lik_kernel<false>, dim3((unsigned)(grid + n_b_blocks)), dim3(LIK_BLOCK), 0, s, bt, n_items, th,
+                           reinterpret_cast<const LikTabs *>(ctx->log_tab), lM, p_Bt_g_Ft, (int)grid, b, C, (int)H, S_B,
+                           lp_B_g_F, nullptr);
     fcd_prof_end(ctx, FCD_PROF_LIK, s);
     FCD_LAUNCH_CHECK();
+    if (slots) {
+        hipLaunchKernelGGL(nan_fold_kernel, dim3(1), dim3(FCD_NAN_SLOTS), 0, s, slots, n_missing2);
+        FCD_LAUNCH_CHECK();
+    }
     return FCD_OK;
+}
+
+extern "C" int fcd_lik_tables(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                              const double *theta, double *S_B, double *lM, double *lp_B_g_F,
+                              double *p_Bt_g_Ft, fcd_stream stream) {
+    return fcd_lik_tables_ex(ctx, b, bt, C, H, U, theta, S_B, lM, lp_B_g_F, p_Bt_g_Ft, 0, nullptr, stream);
 }

@@ -87,6 +87,9 @@ struct PostTheta {
 // mean-field q_F[c,k] w_l(c,u) formed from lq_F (C,1,3) and lq_R (Nreg,U,2) (the products of weights_vb_kernel).
 // The densities enter only through ratios, so they are taken as exp(ln N_j - max_j ln N_j): one of them is exactly 1 and
 // no item is 0/0 where all three underflow.  A (k,l) with zero weight is skipped.
+// MISSING (FCD_DATA_NAN_MISSING): at a NaN bt the same closed forms with N_j = 1 for every j -- the prior law of T and F~
+// given (k,l).  MISSING = false is the kernel without the flag.
+template <bool MISSING>
 __global__ __launch_bounds__(256) void posterior_kernel(const double *__restrict__ bt, int64_t C, int U, PostTheta th,
                                                         const uint32_t *__restrict__ counts, const double *__restrict__ lq_F,
                                                         const double *__restrict__ lq_R, double *__restrict__ p_T,
@@ -118,16 +121,20 @@ __global__ __launch_bounds__(256) void posterior_kernel(const double *__restrict
             }
         }
         const double x = bt[i];
-        double a[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const double z = (x - th.mu[j]) / th.sigma[j];
-            a[j] = -(z * z) / 2.0 - th.lsigma[j];            // ln N_j up to the common ln sqrt(2 pi)
-        }
-        const double mx = fmax(a[0], fmax(a[1], a[2]));
         double N[3];
+        if (MISSING && __builtin_isnan(x)) {
+            N[0] = N[1] = N[2] = 1.0;                          // unobserved: every density integrates to 1
+        } else {
+            double a[3];
 #pragma unroll
-        for (int j = 0; j < 3; ++j) N[j] = exp(a[j] - mx);
+            for (int j = 0; j < 3; ++j) {
+                const double z = (x - th.mu[j]) / th.sigma[j];
+                a[j] = -(z * z) / 2.0 - th.lsigma[j];            // ln N_j up to the common ln sqrt(2 pi)
+            }
+            const double mx = fmax(a[0], fmax(a[1], a[2]));
+#pragma unroll
+            for (int j = 0; j < 3; ++j) N[j] = exp(a[j] - mx);
+        }
         const double S[3] = {N[1] + N[2], N[0] + N[2], N[0] + N[1]};
         double wsum = 0.0, t1 = 0.0, ch = 0.0, ft[3] = {0.0, 0.0, 0.0};
 #pragma unroll
@@ -197,10 +204,11 @@ extern "C" int fcd_gibbs_set_pair_accumulator(fcd_ctx *ctx, uint32_t *acc, int64
     return FCD_OK;
 }
 
-extern "C" int fcd_conn_posterior(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, const double *theta,
-                                  const uint32_t *counts, const double *lq_F, const double *lq_R, double *p_T, double *p_F_tilde,
-                                  double *p_changed, fcd_stream stream) {
+extern "C" int fcd_conn_posterior_ex(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, const double *theta,
+                                     const uint32_t *counts, const double *lq_F, const double *lq_R, int flags, double *p_T,
+                                     double *p_F_tilde, double *p_changed, fcd_stream stream) {
     if (!ctx || !bt || !theta || !p_T || !p_F_tilde || !p_changed) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_conn_posterior: null pointer");
+    if (flags & ~FCD_DATA_NAN_MISSING) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_conn_posterior_ex: unknown flags 0x%x", flags);
     if ((counts != nullptr) == (lq_F != nullptr || lq_R != nullptr) || (!counts && (!lq_F || !lq_R)))
         return fcd_fail(ctx, FCD_ERR_ARG, "fcd_conn_posterior: pass counts, or lq_F and lq_R");
     if (Nreg < 2 || U < 1 || U > INT32_MAX || Nreg > 46340)
@@ -227,8 +235,18 @@ extern "C" int fcd_conn_posterior(fcd_ctx *ctx, const double *bt, int64_t Nreg, 
     int64_t blocks = (items + 255) / 256;
     const int64_t cap = (int64_t)ctx->num_cu * 64;
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(posterior_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bt, C, (int)U, th, counts, lq_F,
-                       lq_R, p_T, p_F_tilde, p_changed);
+    if (flags & FCD_DATA_NAN_MISSING)
+        hipLaunchKernelGGL(posterior_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bt, C, (int)U, th, counts,
+                           lq_F, lq_R, p_T, p_F_tilde, p_changed);
+    else
+        hipLaunchKernelGGL(posterior_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bt, C, (int)U, th, counts,
+                           lq_F, lq_R, p_T, p_F_tilde, p_changed);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
+}
+
+extern "C" int fcd_conn_posterior(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, const double *theta,
+                                  const uint32_t *counts, const double *lq_F, const double *lq_R, double *p_T, double *p_F_tilde,
+                                  double *p_changed, fcd_stream stream) {
+    return fcd_conn_posterior_ex(ctx, bt, Nreg, U, theta, counts, lq_F, lq_R, 0, p_T, p_F_tilde, p_changed, stream);
 }

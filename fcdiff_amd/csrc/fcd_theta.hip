@@ -79,12 +79,16 @@ __global__ __launch_bounds__(256) void pair_counts_kernel(const uint8_t *__restr
 }
 
 constexpr int OBJ_BLOCK = 256;
+// MISSING (FCD_DATA_NAN_MISSING): an item with NaN bt adds nothing -- its M_kl = 1 for every (k,l) depends on no
+// parameter, so it contributes ln 1 = 0 to S and 0 to every derivative.  MISSING = false is the kernel without the flag.
+template <bool MISSING>
 __global__ __launch_bounds__(OBJ_BLOCK) void theta_sub_kernel(const double *__restrict__ bt, const double *__restrict__ W,
                                                               int64_t n_items, SubTheta th, double *__restrict__ partial) {
     __shared__ double red[OBJ_BLOCK / 64][3];
     double S = 0.0, gh = 0.0, ge = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * OBJ_BLOCK + threadIdx.x; i < n_items; i += (int64_t)gridDim.x * OBJ_BLOCK) {
         const double x = bt[i];
+        if (MISSING && __builtin_isnan(x)) continue;
         double N[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -134,7 +138,10 @@ __global__ __launch_bounds__(OBJ_BLOCK) void theta_sub_kernel(const double *__re
 // derivative in ln sigma^2) --, dM_kl/d theta_j = (eps_l if j == k else (1 - eps_l)/2) dN_j/d theta_j (fit.py:700-707;
 // fit.py:572-597 has the same form up to quirk Q8; doc/methods.rst:715-944): the TRUE gradient of S, which is what
 // L-BFGS-B needs.
+// MISSING (FCD_DATA_NAN_MISSING): a NaN bt item adds nothing to any sum (M = 1 whatever theta), a NaN b adds nothing to
+// the ln N / mu / sigma^2 terms (the density of an unobserved value integrates to 1).
 // ---------------------------------------------------------------------------------------------
+template <bool MISSING>
 __global__ __launch_bounds__(OBJ_BLOCK) void theta_full_kernel(const double *__restrict__ b, const double *__restrict__ bt,
                                                                const double *__restrict__ W, int64_t C, int H, int U,
                                                                SubTheta th, double *__restrict__ partial) {
@@ -149,6 +156,7 @@ __global__ __launch_bounds__(OBJ_BLOCK) void theta_full_kernel(const double *__r
     const int64_t n_bt = C * U;
     for (int64_t i = (int64_t)blockIdx.x * OBJ_BLOCK + threadIdx.x; i < n_bt; i += (int64_t)gridDim.x * OBJ_BLOCK) {
         const double x = bt[i];
+        if (MISSING && __builtin_isnan(x)) continue;
         double N[3], dNm[3], dNs[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -187,6 +195,7 @@ __global__ __launch_bounds__(OBJ_BLOCK) void theta_full_kernel(const double *__r
         for (int64_t i = (int64_t)blockIdx.x * OBJ_BLOCK + threadIdx.x; i < n_b; i += (int64_t)gridDim.x * OBJ_BLOCK) {
             const int64_t c = i / H;
             const double x = b[i];
+            if (MISSING && __builtin_isnan(x)) continue;
             const double *w0 = W + c * U * 9;              // patient 0 of the edge: sum over l = weight of f_c = k
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -276,9 +285,10 @@ extern "C" int fcd_gibbs_pair_counts(fcd_ctx *ctx, const uint8_t *f_state, const
     return FCD_OK;
 }
 
-extern "C" int fcd_theta_sub_objective(fcd_ctx *ctx, const double *bt, const double *W, int64_t C, int64_t U,
-                                       const double *theta, double *out3, fcd_stream stream) {
+extern "C" int fcd_theta_sub_objective_ex(fcd_ctx *ctx, const double *bt, const double *W, int64_t C, int64_t U,
+                                          const double *theta, int flags, double *out3, fcd_stream stream) {
     if (!ctx || !bt || !W || !theta || !out3) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_sub_objective: null pointer");
+    if (flags & ~FCD_DATA_NAN_MISSING) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_sub_objective_ex: unknown flags 0x%x", flags);
     if (C < 1 || U < 1) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_sub_objective: C=%lld U=%lld must be >= 1", C, U);
     SubTheta th;
     const double eta = theta[1], epsilon = theta[2];
@@ -302,16 +312,28 @@ extern "C" int fcd_theta_sub_objective(fcd_ctx *ctx, const double *bt, const dou
     int rc = fcd_ws_reserve(ctx, (size_t)blocks * 4 * sizeof(double));
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(theta_sub_kernel, dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, bt, W, n_items, th, (double *)ctx->ws);
+    if (flags & FCD_DATA_NAN_MISSING)
+        hipLaunchKernelGGL(theta_sub_kernel<true>, dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, bt, W, n_items, th,
+                           (double *)ctx->ws);
+    else
+        hipLaunchKernelGGL(theta_sub_kernel<false>, dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, bt, W, n_items, th,
+                           (double *)ctx->ws);
     FCD_LAUNCH_CHECK();
     hipLaunchKernelGGL(theta_sub_fold, dim3(1), dim3(256), 0, s, (const double *)ctx->ws, (int)blocks, out3);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
 }
 
-extern "C" int fcd_theta_full_objective(fcd_ctx *ctx, const double *b, const double *bt, const double *W, int64_t C, int64_t H,
-                                        int64_t U, const double *theta, double *out9, fcd_stream stream) {
+extern "C" int fcd_theta_sub_objective(fcd_ctx *ctx, const double *bt, const double *W, int64_t C, int64_t U,
+                                       const double *theta, double *out3, fcd_stream stream) {
+    return fcd_theta_sub_objective_ex(ctx, bt, W, C, U, theta, 0, out3, stream);
+}
+
+extern "C" int fcd_theta_full_objective_ex(fcd_ctx *ctx, const double *b, const double *bt, const double *W, int64_t C,
+                                           int64_t H, int64_t U, const double *theta, int flags, double *out9,
+                                           fcd_stream stream) {
     if (!ctx || !bt || !W || !theta || !out9) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_full_objective: null pointer");
+    if (flags & ~FCD_DATA_NAN_MISSING) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_full_objective_ex: unknown flags 0x%x", flags);
     if (C < 1 || U < 1 || (b && H < 1) || H > INT32_MAX || U > INT32_MAX)
         return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_full_objective: C=%lld U=%lld must be >= 1", C, U);
     SubTheta th;
@@ -337,10 +359,19 @@ extern "C" int fcd_theta_full_objective(fcd_ctx *ctx, const double *b, const dou
     int rc = fcd_ws_reserve(ctx, (size_t)blocks * 12 * sizeof(double));
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(theta_full_kernel, dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, b, bt, W, C, (int)H, (int)U, th,
-                       (double *)ctx->ws);
+    if (flags & FCD_DATA_NAN_MISSING)
+        hipLaunchKernelGGL(theta_full_kernel<true>, dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, b, bt, W, C, (int)H, (int)U, th,
+                           (double *)ctx->ws);
+    else
+        hipLaunchKernelGGL(theta_full_kernel<false>, dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, b, bt, W, C, (int)H, (int)U, th,
+                           (double *)ctx->ws);
     FCD_LAUNCH_CHECK();
     hipLaunchKernelGGL(theta_full_fold, dim3(1), dim3(256), 0, s, (const double *)ctx->ws, (int)blocks, out9);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
+}
+
+extern "C" int fcd_theta_full_objective(fcd_ctx *ctx, const double *b, const double *bt, const double *W, int64_t C, int64_t H,
+                                        int64_t U, const double *theta, double *out9, fcd_stream stream) {
+    return fcd_theta_full_objective_ex(ctx, b, bt, W, C, H, U, theta, 0, out9, stream);
 }

@@ -16,6 +16,7 @@ New knobs (all optional; defaults reproduce the reference):
     n_chains, n_sweeps, burn_in, mstep_every, mstep_lag, seed, chain0     sampler controls
     update_theta_sub, theta_sub_every                          (eta, epsilon) step: vb every iteration / gibbs every K sweeps
     connection_marginals, connection_every                     gibbs: count (f_c, mixture case) for connection_posterior()
+    missing_data                                               True: NaN entries of b / bt are unobserved and integrated out
 
 Differences from the reference that are deliberate and documented:
   Q4  `model.pi` may be the scalar the model defines or the 2-vector [1-pi, pi] the reference's updates
@@ -77,6 +78,9 @@ class UnsharedRegionFit(object):
         self.connection_every = 1           # ... at every this many sweeps from burn_in on
         self.connection_counts = None       # (C, U, 3, 3) int64: those counts, pooled over chains, sweeps and ranks
         self.connection_sweeps = 0          # number of sweeps behind connection_counts (each counts every chain once)
+        # True: every NaN of b / bt is an unobserved value, integrated out exactly (S_B sums the observed h only, lM = 0 at a
+        # missing bt); False: NaN is read as a number, as the reference reads it.  Only NaN is missing, not +-inf.
+        self.missing_data = False
 
         self._ctx = None
         self._d = {}              # device tensors: lq_R, lq_F, S_B, lM, lpB, pBt, hyper, b, bt
@@ -282,7 +286,8 @@ class UnsharedRegionFit(object):
         # 165 ms at cfg5); invalidate_data() forces the next call to upload.
         key = (self._array_key(self.b), self._array_key(self.bt), self._data_digest(b, self.data_check),
                self._data_digest(bt, self.data_check))
-        if self._d.get("data_key") != key:
+        uploaded = self._d.get("data_key") != key
+        if uploaded:
             self._d["b"], self._d["bt"] = self._up(b), self._up(bt)
             self._d["data_key"] = key
         if self._d.get("S_B") is None or tuple(self._d["S_B"].shape) != (C, 3):
@@ -294,10 +299,38 @@ class UnsharedRegionFit(object):
             lpB = t.empty((C, H, 3), dtype=t.float64, device=dev)
             pBt = t.empty((C, U, 3), dtype=t.float64, device=dev)
         (th, _th) = _lib.dbl_array(self.model.theta())
-        self._context().call("fcd_lik_tables", _lib.dptr(self._d["b"]), _lib.dptr(self._d["bt"]), C, H, U, th,
-                             _lib.dptr(self._d["S_B"]), _lib.dptr(self._d["lM"]), _lib.dptr(lpB), _lib.dptr(pBt),
-                             _lib.stream_ptr())
+        if self.missing_data:
+            # the kernel counts the NaN entries on the device; missing_counts() reads them when asked (no sync here).  The
+            # counts depend on the data alone, so they are taken when the data is uploaded: the counting build waits for
+            # its atomics (5-39 us more at cfg3 with 10 % NaN), the per-iteration builds after it run at the uncounted speed
+            count = uploaded or not self._d.get("n_missing_valid")
+            if self._d.get("n_missing") is None:
+                self._d["n_missing"] = t.zeros(2, dtype=t.int64, device=dev)
+            self._context().call("fcd_lik_tables_ex", _lib.dptr(self._d["b"]), _lib.dptr(self._d["bt"]), C, H, U, th,
+                                 _lib.dptr(self._d["S_B"]), _lib.dptr(self._d["lM"]), _lib.dptr(lpB), _lib.dptr(pBt),
+                                 _lib.FCD_DATA_NAN_MISSING, _lib.dptr(self._d["n_missing"] if count else None),
+                                 _lib.stream_ptr())
+            self._d["n_missing_valid"] = True
+        else:
+            self._context().call("fcd_lik_tables", _lib.dptr(self._d["b"]), _lib.dptr(self._d["bt"]), C, H, U, th,
+                                 _lib.dptr(self._d["S_B"]), _lib.dptr(self._d["lM"]), _lib.dptr(lpB), _lib.dptr(pBt),
+                                 _lib.stream_ptr())
+            self._d["n_missing_valid"] = False
         self._d["lpB"], self._d["pBt"] = lpB, pBt
+
+    def _flags(self):
+        return _lib.FCD_DATA_NAN_MISSING if self.missing_data else 0
+
+    def missing_counts(self):
+        """
+        (n_missing_b, n_missing_bt): the number of NaN entries of b and of bt the last table build integrated out.  Needs
+        missing_data = True and a table build (run(), _update_lps()); the counts come from the table kernel, so this
+        read waits for it.
+        """
+        if not self.missing_data or not self._d.get("n_missing_valid"):
+            raise ValueError("missing_counts() needs missing_data = True and a table build (run() or _update_lps())")
+        (nb, nbt) = self._d["n_missing"].cpu().tolist()
+        return (int(nb), int(nbt))
 
     @staticmethod
     def _array_key(a):
@@ -465,10 +498,12 @@ class UnsharedRegionFit(object):
         W = self._theta_sub_weights()
         if self.theta_sub_params == "all":
             # the reference's commented-out intent (fit.py:232-237, 250-251, 266-267, 282): mu and sigma too
-            (eta, epsilon, mu, sigma, info) = minimize_theta_full(self._context(), self._d["b"], self._d["bt"], W, self.model)
+            (eta, epsilon, mu, sigma, info) = minimize_theta_full(self._context(), self._d["b"], self._d["bt"], W, self.model,
+                                                                  missing_data=self.missing_data)
             self.model.mu, self.model.sigma = mu, sigma
         elif self.theta_sub_params == "eta_epsilon":
-            (eta, epsilon, info) = minimize_theta_sub(self._context(), self._d["bt"], W, self.model)
+            (eta, epsilon, info) = minimize_theta_sub(self._context(), self._d["bt"], W, self.model,
+                                                      missing_data=self.missing_data)
         else:
             raise ValueError("theta_sub_params must be 'eta_epsilon' or 'all'")
         self.model.eta, self.model.epsilon = eta, epsilon
@@ -530,11 +565,12 @@ class UnsharedRegionFit(object):
                 W = e.pair_counts()
                 if self.theta_sub_params == "all":
                     (eta, epsilon, mu, sigma, _info) = minimize_theta_full(self._context(), self._d["b"], self._d["bt"], W,
-                                                                           self.model, reduce=allreduce_counts)
+                                                                           self.model, reduce=allreduce_counts,
+                                                                           missing_data=self.missing_data)
                     self.model.mu, self.model.sigma = mu, sigma
                 else:
                     (eta, epsilon, _info) = minimize_theta_sub(self._context(), self._d["bt"], W, self.model,
-                                                               reduce=allreduce_counts)
+                                                               reduce=allreduce_counts, missing_data=self.missing_data)
                 self.model.eta, self.model.epsilon = eta, epsilon
                 self._update_lps()            # tables follow theta_sub ...
                 e.refresh_tables()            # ... and so do the sampler's two difference tables
@@ -585,6 +621,8 @@ class UnsharedRegionFit(object):
                           number of sweeps behind them as `connection_sweeps`.  With
                           update_theta_sub and theta_sub_every, counts made under earlier (eta, epsilon) are contracted
                           with the final theta all the same.
+        With missing_data = True a NaN bt[c,u] takes N_j = 1 in the closed forms: the prior law of T and F~ given (k, l),
+        averaged over the same weights.
         """
         t = self._torch()
         if self.model is None or self.bt is None:
@@ -600,12 +638,13 @@ class UnsharedRegionFit(object):
                 raise ValueError("pooled connection counts exceed uint32; raise connection_every")
             (N, C, U) = (util.C_to_N(cnt.shape[0]), cnt.shape[0], cnt.shape[1])
             counts = t.as_tensor(np.ascontiguousarray(cnt.astype(np.uint32).view(np.int32)), device=self._dev())
-            return conn_posterior(self._context(), self._bt_dev(C, U), int(N), U, self.model.theta(), counts=counts)
+            return conn_posterior(self._context(), self._bt_dev(C, U), int(N), U, self.model.theta(), counts=counts,
+                                  missing_data=self.missing_data)
         if self.method != "vb":
             raise ValueError("method must be 'vb' or 'gibbs'")
         (N, C, U) = self._check_state(need=("lq_R", "lq_F"))
         return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), lq_F=self._d["lq_F"],
-                              lq_R=self._d["lq_R"])
+                              lq_R=self._d["lq_R"], missing_data=self.missing_data)
 
     def _bt_dev(self, C, U):
         bt = self._d.get("bt")
@@ -616,10 +655,11 @@ class UnsharedRegionFit(object):
         return bt
 
 
-def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=None):
+def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=None, missing_data=False):
     """
     {p_T (C,U), p_F_tilde (C,U,3), p_changed (C,U)} as NumPy float64 through fcd_conn_posterior: weights from `counts`
     (C,U,3,3) uint32 (held in an int32 tensor), or from the log-probabilities lq_F (C,1,3) and lq_R (Nreg,U,2).
+    missing_data: a NaN of bt is unobserved (fcd_conn_posterior_ex with FCD_DATA_NAN_MISSING).
     """
     import torch
     C = util.N_to_C(int(Nreg))
@@ -635,52 +675,56 @@ def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=Non
     p_Ft = torch.empty((C, U, 3), dtype=torch.float64, device=dev)
     p_ch = torch.empty((C, U), dtype=torch.float64, device=dev)
     (th, _th) = _lib.dbl_array(theta)
-    ctx.call("fcd_conn_posterior", _lib.dptr(bt_dev.contiguous()), int(Nreg), int(U), th,
+    ctx.call("fcd_conn_posterior_ex", _lib.dptr(bt_dev.contiguous()), int(Nreg), int(U), th,
              _lib.dptr(None if counts is None else counts.contiguous()),
              _lib.dptr(None if lq_F is None else lq_F.contiguous()), _lib.dptr(None if lq_R is None else lq_R.contiguous()),
-             _lib.dptr(p_T), _lib.dptr(p_Ft), _lib.dptr(p_ch), _lib.stream_ptr())
+             _lib.FCD_DATA_NAN_MISSING if missing_data else 0, _lib.dptr(p_T), _lib.dptr(p_Ft), _lib.dptr(p_ch),
+             _lib.stream_ptr())
     return {"p_T": p_T.cpu().numpy(), "p_F_tilde": p_Ft.cpu().numpy(), "p_changed": p_ch.cpu().numpy()}
 
 
-def theta_sub_objective(ctx, bt_dev, W, theta, reduce=None):
+def theta_sub_objective(ctx, bt_dev, W, theta, reduce=None, missing_data=False):
     """
-    (S, dS/d eta, dS/d epsilon), S = sum W ln M(bt; eta, epsilon), through fcd_theta_sub_objective.
+    (S, dS/d eta, dS/d epsilon), S = sum W ln M(bt; eta, epsilon), through fcd_theta_sub_objective_ex.
     `reduce` (optional) sums the three numbers over ranks (multi-GPU sampler: W holds this rank's chain counts).
+    missing_data: an item with NaN bt adds nothing (its M = 1 does not depend on eta or epsilon).
     """
     import torch
     out = torch.empty(3, dtype=torch.float64, device=W.device)
     (th, _th) = _lib.dbl_array(theta)
-    ctx.call("fcd_theta_sub_objective", _lib.dptr(bt_dev), _lib.dptr(W), int(W.shape[0]), int(W.shape[1]), th,
-             _lib.dptr(out), _lib.stream_ptr())
+    ctx.call("fcd_theta_sub_objective_ex", _lib.dptr(bt_dev), _lib.dptr(W), int(W.shape[0]), int(W.shape[1]), th,
+             _lib.FCD_DATA_NAN_MISSING if missing_data else 0, _lib.dptr(out), _lib.stream_ptr())
     if reduce is not None:
         out = reduce(out)
     return out.cpu().numpy()
 
 
-def theta_full_objective(ctx, b_dev, bt_dev, W, theta, reduce=None):
+def theta_full_objective(ctx, b_dev, bt_dev, W, theta, reduce=None, missing_data=False):
     """
     {S, dS/d eta, dS/d epsilon, dS/d mu[3], dS/d sigma^2[3]} of the full theta_sub objective (fcd_theta_full_objective):
     S = E[ln p(b | f)] + E[ln p(bt | f, r)] for the weights W.  `reduce` sums the nine numbers over ranks.
     With several ranks each rank's W holds its own chain counts, but b is the same on all: pass b_dev on every rank
     (the healthy term scales with the chain counts too, so the sum over ranks is the pooled objective).
+    missing_data: a NaN bt item adds nothing to any term, a NaN b adds nothing to the ln N / mu / sigma^2 terms.
     """
     import torch
     out = torch.empty(9, dtype=torch.float64, device=W.device)
     (th, _th) = _lib.dbl_array(theta)
     H = int(b_dev.shape[1]) if b_dev is not None else 0
-    ctx.call("fcd_theta_full_objective", _lib.dptr(b_dev), _lib.dptr(bt_dev), _lib.dptr(W), int(W.shape[0]), H,
-             int(W.shape[1]), th, _lib.dptr(out), _lib.stream_ptr())
+    ctx.call("fcd_theta_full_objective_ex", _lib.dptr(b_dev), _lib.dptr(bt_dev), _lib.dptr(W), int(W.shape[0]), H,
+             int(W.shape[1]), th, _lib.FCD_DATA_NAN_MISSING if missing_data else 0, _lib.dptr(out), _lib.stream_ptr())
     if reduce is not None:
         out = reduce(out)
     return out.cpu().numpy()
 
 
-def minimize_theta_full(ctx, b_dev, bt_dev, W, model, reduce=None, bound_eps=1e-5):
+def minimize_theta_full(ctx, b_dev, bt_dev, W, model, reduce=None, bound_eps=1e-5, missing_data=False):
     """
     argmin of -(E[ln p(b | f)] + E[ln p(bt | f, r)]) over theta_sub = (eta, epsilon, mu[3], sigma^2[3]): the step the
     reference intends (fit.py:222-286 with its commented-out lines read in): pack order and sigma ** 2 as in
     fit.py:243-252, bounds of fit.py:228-237 -- eta, epsilon in (e, 1-e), mu_0 in (-1+e, -e), mu_1 in (-e, e), mu_2 in
     (e, 1-e), sigma^2 > e --, analytic gradient, L-BFGS-B.  Returns (eta, epsilon, mu, sigma, scipy result).
+    missing_data: NaN in b / bt is unobserved (theta_full_objective).
     """
     import scipy.optimize as spopt
     base = np.array(model.theta(), dtype=np.float64)
@@ -694,7 +738,7 @@ def minimize_theta_full(ctx, b_dev, bt_dev, W, model, reduce=None, bound_eps=1e-
         return th
 
     def fun(x):
-        o = theta_full_objective(ctx, b_dev, bt_dev, W, unpack(x), reduce)
+        o = theta_full_objective(ctx, b_dev, bt_dev, W, unpack(x), reduce, missing_data=missing_data)
         return (-o[0], -o[1:9])
     bnds = ((e, 1 - e), (e, 1 - e), (-1 + e, 0 - e), (0 - e, 0 + e), (0 + e, 1 - e), (0 + e, None), (0 + e, None), (0 + e, None))
     x0 = np.concatenate([[model.eta, model.epsilon], np.asarray(model.mu, dtype=np.float64),
@@ -707,10 +751,10 @@ def minimize_theta_full(ctx, b_dev, bt_dev, W, model, reduce=None, bound_eps=1e-
     return float(th[1]), float(th[2]), th[6:9].copy(), th[9:12].copy(), res
 
 
-def minimize_theta_sub(ctx, bt_dev, W, model, reduce=None, bound_eps=1e-5):
+def minimize_theta_sub(ctx, bt_dev, W, model, reduce=None, bound_eps=1e-5, missing_data=False):
     """
     argmin over (eta, epsilon) in [1e-5, 1-1e-5]^2 of -sum W ln M (fit.py:222-241), analytic gradient, L-BFGS-B.
-    Returns (eta, epsilon, scipy result).  The model is not modified.
+    Returns (eta, epsilon, scipy result).  The model is not modified.  missing_data: NaN in bt is unobserved.
     """
     import scipy.optimize as spopt
     base = np.array(model.theta(), dtype=np.float64)
@@ -718,7 +762,7 @@ def minimize_theta_sub(ctx, bt_dev, W, model, reduce=None, bound_eps=1e-5):
     def fun(x):
         th = base.copy()
         th[1], th[2] = float(x[0]), float(x[1])
-        (S, dh, de) = theta_sub_objective(ctx, bt_dev, W, th, reduce)
+        (S, dh, de) = theta_sub_objective(ctx, bt_dev, W, th, reduce, missing_data=missing_data)
         return (-S, np.array([-dh, -de]))
     bnds = ((bound_eps, 1 - bound_eps), (bound_eps, 1 - bound_eps))          # fit.py:228-231
     x0 = np.clip(np.array([model.eta, model.epsilon], dtype=np.float64), bound_eps, 1 - bound_eps)

@@ -57,6 +57,14 @@ extern "C" {
 #define FCD_EDGE_REFERENCE 0 /* nm_to_c(n,m) = n(n-1)/2 + m for EVERY ordered pair, as fit.py:185-186 calls it */
 #define FCD_EDGE_SYMMETRIC 1 /* the unordered pair's edge, as doc/methods.rst:646-653 writes it */
 
+/* `flags` of the *_ex entry points: how b / bt are read.
+ * FCD_DATA_NAN_MISSING: a NaN entry of b or bt is unobserved and is integrated out.  The fitter's densities of b and bt
+ * are plain Normals (no clip to [-1, 1]) and each integrates to 1, so a NaN b[c,h] adds 0 to S_B[c,k] for every k and a
+ * NaN bt[c,u] has N_j = 1 for every j, M_kl = 1 and lM[c,u,k,l] = 0.  Only NaN is missing (+-inf is read as a value).
+ * Every other entry point reads the data only through S_B and lM and needs no flag.  flags = 0: the plain entry points'
+ * results, bit for bit (they are the flags = 0 forms). */
+#define FCD_DATA_NAN_MISSING 1
+
 typedef struct fcd_ctx fcd_ctx;
 typedef void *fcd_stream; /* hipStream_t */
 
@@ -163,6 +171,14 @@ int fcd_hyper_set(fcd_ctx *ctx, double *hyper, const double *gamma3_host, const 
 int fcd_lik_tables(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
                    const double *theta12_host, double *S_B, double *lM, double *lp_B_g_F,
                    double *p_Bt_g_Ft, fcd_stream stream);
+/* fcd_lik_tables with flags.  With FCD_DATA_NAN_MISSING: S_B[c,k] sums over the observed h only, lM[c,u,:,:] = 0.0
+ * exactly at a NaN bt[c,u]; lp_B_g_F holds 0.0 at a NaN b and p_Bt_g_Ft 1.0 at a NaN bt.  n_missing2 (device, int64[2],
+ * may be NULL; only with the flag) receives {number of NaN in b, number of NaN in bt}, counted by
+ * the table kernel (one atomic per block, into the context's slots) and written by one more small launch on `stream`.
+ * Asynchronous like every table build. */
+int fcd_lik_tables_ex(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                      const double *theta12_host, double *S_B, double *lM, double *lp_B_g_F, double *p_Bt_g_Ft,
+                      int flags, int64_t *n_missing2, fcd_stream stream);
 
 /* ---- forward sampler: UnsharedRegionModel.sample, fcdiff/model.py:52-236, on the device ---------------
  * Counter RNG (Philox), all variables drawn in parallel; the reference's MT19937 stream is not reproduced (the host
@@ -220,6 +236,12 @@ int fcd_theta_sub_objective(fcd_ctx *ctx, const double *bt, const double *W, int
  * Deterministic. */
 int fcd_theta_full_objective(fcd_ctx *ctx, const double *b, const double *bt, const double *W, int64_t C, int64_t H,
                              int64_t U, const double *theta12_host, double *out9, fcd_stream stream);
+/* The two objectives with flags.  With FCD_DATA_NAN_MISSING an item with NaN bt adds nothing to S or its gradient (its
+ * M = 1 depends on no parameter), and a NaN b adds nothing to the mu / sigma^2 terms. */
+int fcd_theta_sub_objective_ex(fcd_ctx *ctx, const double *bt, const double *W, int64_t C, int64_t U,
+                               const double *theta12_host, int flags, double *out3, fcd_stream stream);
+int fcd_theta_full_objective_ex(fcd_ctx *ctx, const double *b, const double *bt, const double *W, int64_t C, int64_t H,
+                                int64_t U, const double *theta12_host, int flags, double *out9, fcd_stream stream);
 
 /* ---- many-chain collapsed Gibbs sampler ---------------------------------------------------
  * Build-defined (the reference ships only the variational fitter, doc/methods.rst:236-239).  Its two
@@ -315,6 +337,11 @@ int fcd_gibbs_set_pair_accumulator(fcd_ctx *ctx, uint32_t *acc, int64_t Nreg, in
 int fcd_conn_posterior(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, const double *theta12_host,
                        const uint32_t *counts, const double *lq_F, const double *lq_R, double *p_T, double *p_F_tilde,
                        double *p_changed, fcd_stream stream);
+/* fcd_conn_posterior with flags.  With FCD_DATA_NAN_MISSING the closed forms take N_j = 1 at a NaN bt[c,u]: the prior
+ * law of T and F~ given (k, l), averaged over the same weights.  Observed items are unchanged. */
+int fcd_conn_posterior_ex(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, const double *theta12_host,
+                          const uint32_t *counts, const double *lq_F, const double *lq_R, int flags, double *p_T,
+                          double *p_F_tilde, double *p_changed, fcd_stream stream);
 /* log p(f, r, b, bt; theta) of each chain = minus the first four terms of fit.py:149-152 at one-hot q.
  * out (G,) doubles. */
 int fcd_gibbs_logjoint(fcd_ctx *ctx, const double *S_B, const double *lM, const double *hyper,
