@@ -47,12 +47,6 @@ int fcd_fsq_reserve(fcd_ctx *ctx, size_t bytes) {
     return FCD_OK;
 }
 
-void fcd_sweep_ws_bytes(const fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t GW, size_t *ws_bytes, size_t *fsq_bytes) {
-    const size_t f = fcd_f_pass_ws_bytes(Nreg, U, GW), r = fcd_r_pass_ws_bytes(Nreg, U, GW, ctx->knobs.r_path);
-    *ws_bytes = f > r ? f : r;
-    *fsq_bytes = fcd_fsq_need_bytes(Nreg, U, GW);
-}
-
 // "0", "" and unset mean "default"; anything else is the number
 static double knob_env(const char *name) {
     const char *e = getenv(name);
@@ -242,12 +236,11 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G) {
     size_t need = (size_t)64 * GW * 64 * sizeof(double);        // log-joint partials
     const size_t en = (size_t)ctx->num_cu * 8 * 8 * sizeof(double);  // energy partials
     if (en > need) need = en;
-    size_t sweep = 0, fsq = 0;
-    fcd_sweep_ws_bytes(ctx, Nreg, U, GW, &sweep, &fsq);             // f / r pass scratch and the square f copy
-    if (sweep > need) need = sweep;
+    const fcd_sweep_plan pl = fcd_sweep_plan_for(ctx, Nreg, U, GW);    // f / r pass scratch and the square f copy
+    if (pl.ws_bytes > need) need = pl.ws_bytes;
     int rc = fcd_ws_reserve(ctx, need);
     if (rc) return rc;
-    return fsq ? fcd_fsq_reserve(ctx, fsq) : FCD_OK;
+    return pl.fsq_bytes ? fcd_fsq_reserve(ctx, pl.fsq_bytes) : FCD_OK;
 }
 
 int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value) {

@@ -64,7 +64,7 @@ struct fcd_ctx {
                        // [1] rows of the r pass's in-order role decided on the exact path; never reset by the library
     void *corr_tickets;            // K_corr: one ticket per subject, zero between launches (the last taker resets it)
     size_t corr_tickets_n;
-    void *fsq;         // square copy of the f state [w][n][m][lane] kept by fcd_gibbs_sweeps between its f and r pass
+    void *fsq;         // square copy of the f state [w][n][m][lane] the sweep loop keeps between its f and r pass
     size_t fsq_bytes;
     uint32_t *pair_acc;            // (C, U, 3, 3) counts of (f_c, mixture case) fcd_gibbs_run adds to (fcd_gibbs_set_pair_accumulator), or nullptr
     int64_t pair_nreg, pair_u, pair_every;
@@ -110,14 +110,8 @@ static inline int fcd_static_lds_check(fcd_ctx *ctx, const void *fn, int *done) 
 
 int fcd_comm_allreduce_counts(fcd_ctx *ctx, long long *counts, hipStream_t stream);     // fcd_comm.hip: no-op without a communicator
 int fcd_ws_reserve(fcd_ctx *ctx, size_t bytes);
-// square copy of the f state (see fcd_gibbs_sweeps): grown like the workspace
+// square copy of the f state (see fcd_sweep_plan): grown like the workspace
 int fcd_fsq_reserve(fcd_ctx *ctx, size_t bytes);
-// bytes the sweep kernels need at this shape: f pass scratch, r pass scratch (both in ctx->ws, one after the other in
-// time: the larger counts), square f copy.  ONE formula shared by fcd_ctx_reserve and the step functions.
-void fcd_sweep_ws_bytes(const fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t GW, size_t *ws_bytes, size_t *fsq_bytes);
-size_t fcd_f_pass_ws_bytes(int64_t Nreg, int64_t U, int64_t GW);     // fcd_gibbs.hip
-size_t fcd_r_pass_ws_bytes(int64_t Nreg, int64_t U, int64_t GW, int r_path);   // fcd_gibbs_r.hip
-size_t fcd_fsq_need_bytes(int64_t Nreg, int64_t U, int64_t GW);      // fcd_gibbs.hip: 0 when the fused driver keeps no square copy
 // raise a kernel's dynamic-LDS limit if this size was not set before (no HIP call otherwise)
 static inline int fcd_lds_attr(fcd_ctx *ctx, int slot, const void *fn, size_t shmem) {
     if (shmem <= 64 * 1024 || shmem <= ctx->lds_attr[slot]) return FCD_OK;
@@ -126,12 +120,6 @@ static inline int fcd_lds_attr(fcd_ctx *ctx, int slot, const void *fn, size_t sh
     ctx->lds_attr[slot] = shmem;
     return FCD_OK;
 }
-// f / r pass with the square copy of the f state (fcd_gibbs_sweeps: the f pass also writes f of edge (n, m) at [n][m] and
-// [m][n], the r pass then packs its f words from contiguous rows instead of gathering 64-byte pieces).  fsq == nullptr:
-// the plain entry points.  Symmetric edge ids only.
-int fcd_gibbs_f_step_sq(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *hyper,
-                        uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0,
-                        uint64_t seed, int64_t sweep, hipStream_t stream, uint8_t *fsq, bool ru_ready, size_t ru_off = 0);
 // The f half of the tally (pooled counts of f, marginal counters of the edges): it needs nothing of the r pass, so the r
 // pass's packing launch can carry it in extra workgroups of its own instead of the tally launch after the pass.
 struct fcd_tally_f {
@@ -141,14 +129,6 @@ struct fcd_tally_f {
     unsigned long long *acc;           // nullable: context-owned sums, [1..3] = number of f == 0, 1, 2
     uint32_t *cnt_f;                   // nullable
 };
-// tally_f != nullptr: asked to carry the f half; *tally_f_done says whether it did (the blocked path with a packing launch).
-// sentinels_in_place: the two panel-value buffers at the head of the workspace still hold the sentinels a COMPLETED pipelined
-// pass of the same shape left there (every slot gets its sentinel back when its value is consumed): the packing launch
-// need not write them again.  ru_off (f pass): where in the workspace the slot words live.
-int fcd_gibbs_r_step_sq(fcd_ctx *ctx, const double *lM, const double *lMd, const double *hyper,
-                        const uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0,
-                        uint64_t seed, int64_t sweep, int edge_mode, hipStream_t stream, const uint8_t *fsq,
-                        const fcd_tally_f *tally_f = nullptr, bool *tally_f_done = nullptr, bool sentinels_in_place = false);
 // one launch of the (f_c, mixture case) count kernel of fcd_post.hip: acc (C, U, 3, 3) += counts of this state
 struct fcd_geo;
 int fcd_pair_tally_launch(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
@@ -426,6 +406,53 @@ static inline int fcd_geo_check(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G
         return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "site index exceeds the 32-bit counter word");
     return FCD_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// host: the plan of a sweep at one shape (fcd_sweep_plan_for, fcd_gibbs_r.hip): the ONE place that decides which form each
+// pass runs and where its scratch lies.  fcd_ctx_reserve, both passes and the sweep loop read it.  It depends on the shape
+// and the knobs; a call adds whether lMf (the f forms) and lMd (the blocked r pass) are there, and its edge ids.
+// ---------------------------------------------------------------------------------------------
+enum { FCD_F_GENERIC = 0, FCD_F_PAIR = 1, FCD_F_PAIRX = 2, FCD_F_DIFF = 3 };   // f pass forms (knob f_form: 2, 3)
+constexpr int FP_EC = 8;     // edges per tile of the U <= 64 pair kernel
+struct fcd_sweep_plan {
+    int f_form, f_EC;           // f pass given lMf: form, edges per LDS tile
+    size_t f_shmem;
+    int f_NW;                   // slot-source words per region (pack_ru_word) the pair forms read, pack_ru / the tally make
+    bool r_blocked, r_idx32;    // r pass given lMd: the blocked form fits; its item indices fit 32 bits (else it refuses)
+    int r_ub;                   // ... patients per panel workgroup
+    size_t r_shmem;
+    // square copy of the f state (fcd_ctx::fsq, (GW,Nreg,Nreg,64) u8) a pair-form f pass writes and the r pass packs
+    // from (contiguous rows instead of 64-byte pieces); 0: none
+    size_t fsq_bytes;
+    // workspace byte offsets: P[0] | P[1] | f_S | r_S | r_Sn | marks of the blocked r pass, then at a 512-byte boundary the
+    // slot words r_U of a pair-form f pass (behind the r scratch: the sentinels in P survive from sweep to sweep) | ws_bytes
+    size_t P[2], f_S, r_S, r_Sn, marks, r_U, ws_bytes;
+};
+fcd_sweep_plan fcd_sweep_plan_for(const fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t GW);
+// one call of a sweep entry point; fcd_sweep_call_check (fcd_gibbs.hip) checks it and fills in g and pl
+struct fcd_sweep_call {
+    const double *S_B, *lM, *lMf, *lMd, *hyper;
+    uint8_t *f_state;
+    uint64_t *r_bits;
+    int64_t Nreg, U, G, chain0;
+    uint64_t seed;
+    int edge_mode;
+    hipStream_t s;
+    fcd_geo g;
+    fcd_sweep_plan pl;
+};
+int fcd_sweep_call_check(fcd_ctx *ctx, fcd_sweep_call &c, bool f_pass, bool r_pass, const char *who);
+// what changes from one sweep of a call to the next
+struct fcd_sweep_step {
+    int64_t sweep;
+    uint8_t *fsq;                  // square copy of the f state, or nullptr
+    bool ru_ready;                 // f pass: the previous sweep's tally has made the slot words
+    bool sentinels_in_place;       // r pass: P holds the sentinels a COMPLETED pipelined pass of this shape left behind
+    const fcd_tally_f *tally_f;    // r pass: the f half of the tally to carry in the packing launch, or nullptr ...
+    bool tally_f_done;             // ... and whether it did (out)
+};
+int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step &st);   // fcd_gibbs.hip
+int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st);         // fcd_gibbs_r.hip
 
 // ---------------------------------------------------------------------------------------------
 // Ablation build (make ABLATE=1 -> libfcdiff_hip_abl.so, NEVER the product library): kernels read a level

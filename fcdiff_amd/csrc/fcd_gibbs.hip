@@ -266,7 +266,6 @@ __global__ __launch_bounds__(256) void pack_ru_kernel(const uint64_t *__restrict
     r_U[ru_index(wn, NW, jw, lane)] = pack_ru_word(r_bits, wn, U, jw, lane);
 }
 
-constexpr int FP_EC = 8;     // edges per tile
 typedef float fcd_f2v __attribute__((ext_vector_type(2)));           // one ds_read_b64, one v_pk_add_f32
 typedef __attribute__((address_space(3))) const fcd_f2v lds_cf2v;
 
@@ -1185,97 +1184,59 @@ extern "C" int fcd_gibbs_edge_tables(fcd_ctx *ctx, const double *lM, int64_t Nre
     return FCD_OK;
 }
 
+int fcd_sweep_call_check(fcd_ctx *ctx, fcd_sweep_call &c, bool f_pass, bool r_pass, const char *who) {
+    int rc = fcd_geo_check(ctx, c.Nreg, c.U, c.G, c.chain0, c.g);
+    if (rc) return rc;
+    const bool null = (f_pass && !c.S_B) || !c.lM || !c.hyper || !c.f_state || !c.r_bits;
+    if (null || (r_pass && c.edge_mode != FCD_EDGE_REFERENCE && c.edge_mode != FCD_EDGE_SYMMETRIC)) {
+        snprintf(ctx->msg, sizeof(ctx->msg), null ? "%s: null pointer" : "%s: bad edge_mode", who);
+        return FCD_ERR_ARG;
+    }
+    if (r_pass && c.edge_mode == FCD_EDGE_REFERENCE && c.Nreg == 2)
+        return fcd_fail(ctx, FCD_ERR_INDEX, "reference edge ids: index 1 is out of bounds for axis 0 with size 1 (Nreg=2)");
+    c.pl = fcd_sweep_plan_for(ctx, c.Nreg, c.U, c.g.GW);
+    return FCD_OK;
+}
+
 extern "C" int fcd_gibbs_f_step(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *hyper,
                                 uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
                                 int64_t chain0, uint64_t seed, int64_t sweep, fcd_stream stream) {
-    return fcd_gibbs_f_step_sq(ctx, S_B, lM, lMf, hyper, f_state, r_bits, Nreg, U, G, chain0, seed, sweep, (hipStream_t)stream,
-                               nullptr, false);
+    fcd_sweep_call c = {S_B, lM, lMf, nullptr, hyper, f_state, const_cast<uint64_t *>(r_bits) /* (read only) */, Nreg, U, G,
+                        chain0, seed, FCD_EDGE_SYMMETRIC, (hipStream_t)stream};
+    int rc = fcd_sweep_call_check(ctx, c, true, false, "fcd_gibbs_f_step");
+    return rc ? rc : fcd_gibbs_f_pass(ctx, c, fcd_sweep_step{sweep});
 }
 
-// Which kernel the f step runs at a shape, and with what geometry: shared by the launch code, by the workspace
-// formula (fcd_f_pass_ws_bytes) and by the fused driver (only the pair forms write the square copy).
-enum { F_GENERIC = 0, F_PAIR = 1, F_PAIRX = 2, F_DIFF = 3 };
-struct f_plan {
-    int form, NW16, EC;
-    size_t shmem;
-    int NW;                 // slot-source words per region (pack_ru_word): what pack_ru / the tally make
-};
-static f_plan f_plan_for(bool have_lMf, int64_t Nreg, int64_t U, int64_t GW, int f_form) {
-    f_plan p = {F_GENERIC, (int)((U + 15) / 16), 0, 0, (int)((U + 15) / 16)};
-    if (!have_lMf || (size_t)U * 48 > 160 * 1024) return p;
-    const bool words_ok = GW * Nreg * p.NW16 < INT32_MAX / 4;       // r_U item index in 32 bits
-    const size_t pair_shmem = (size_t)FP_EC * ((U + 1) / 2) * 128 + FP_EC * 16 + (size_t)FP_EC * U * 48;   // fp32 records, edge constants, fp64 rows
-    if (f_form != F_PAIRX && f_form != F_DIFF && p.NW16 <= 4 && pair_shmem <= 96 * 1024 && words_ok) {
-        p.form = F_PAIR;
-        p.EC = FP_EC;
-        p.shmem = pair_shmem;
-        return p;
-    }
-    const size_t per_edge = (size_t)((U + 1) / 2) * 128, extra = 128 + 16 * 48 * 16;   // fp32 records; edge constants + a 768-byte staging scratch per wave
-    if (f_form != F_DIFF && words_ok && per_edge + extra <= 160 * 1024) {
-        // largest tile that still lets two workgroups share a CU; one edge per tile may take the whole LDS
-        int ec = 8;
-        while (ec > 1 && (size_t)ec * per_edge + extra > 80 * 1024) ec >>= 1;
-        p.form = F_PAIRX;
-        p.EC = ec;
-        p.shmem = (size_t)ec * per_edge + extra;
-        return p;
-    }
-    p.form = F_DIFF;
-    int64_t e = (int64_t)(24 * 1024 / ((size_t)U * 48));
-    if (e < 1) e = 1;
-    if (e > 8) e = 8;
-    if (e > 1) e &= ~1ll;   // even: both halves of a Philox block are used inside one tile
-    p.EC = (int)e;
-    p.shmem = (size_t)U * 48 * e;
-    return p;
-}
-
-size_t fcd_f_pass_ws_bytes(int64_t Nreg, int64_t U, int64_t GW) {
-    // per-lane slot words r_U of the pair forms (the largest user; the other forms need nothing): 16 patients per word
-    // (up to four words side by side per lane, else [word][lane]: ru_index)
-    const int64_t NW = (U + 15) / 16;
-    return (size_t)GW * Nreg * (NW <= 4 ? 4 : NW) * 64 * sizeof(uint32_t);
-}
-
-size_t fcd_fsq_need_bytes(int64_t Nreg, int64_t U, int64_t GW) {
-    const f_plan p = f_plan_for(true, Nreg, U, GW, 0);
-    const size_t need = (size_t)GW * Nreg * Nreg * 64;
-    return ((p.form == F_PAIR || p.form == F_PAIRX) && need <= ((size_t)8 << 30)) ? need : 0;
-}
-
-int fcd_gibbs_f_step_sq(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *hyper,
-                        uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0,
-                        uint64_t seed, int64_t sweep, hipStream_t stream, uint8_t *fsq, bool ru_ready, size_t ru_off) {
-    fcd_geo g;
-    int rc = fcd_geo_check(ctx, Nreg, U, G, chain0, g);
-    if (rc) return rc;
-    if (!S_B || !lM || !hyper || !f_state || !r_bits) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_f_step: null pointer");
-    const f_plan pl = f_plan_for(lMf != nullptr, Nreg, U, g.GW, ctx->knobs.f_form);
-    if (pl.form == F_GENERIC)
-        return launch_f<false>(ctx, S_B, lM, hyper, f_state, r_bits, Nreg, U, G, g, chain0, seed, sweep, nullptr,
-                               (hipStream_t)stream);
-    fcd_abl_refresh((hipStream_t)stream);
+int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step &st) {
+    const fcd_sweep_plan &pl = c.pl;
+    const fcd_geo &g = c.g;
+    const int64_t Nreg = c.Nreg, U = c.U;
+    hipStream_t s = c.s;
+    const int form = c.lMf ? pl.f_form : FCD_F_GENERIC;
+    if (form == FCD_F_GENERIC)
+        return launch_f<false>(ctx, c.S_B, c.lM, c.hyper, c.f_state, c.r_bits, Nreg, U, c.G, g, c.chain0, c.seed, st.sweep,
+                               nullptr, s);
+    fcd_abl_refresh(s);
     const int wpb = g.GW < 16 ? g.GW : 16;
-    hipStream_t s = (hipStream_t)stream;
     float margin = FCD_DRAW_F_MARGIN;
     if ((float)ctx->knobs.f_tol > margin) margin = (float)ctx->knobs.f_tol;   // test hook: huge = every draw through fcd_draw_f
-    if (pl.form == F_PAIR || pl.form == F_PAIRX) {
+    int rc;
+    if (form == FCD_F_PAIR || form == FCD_F_PAIRX) {
         // pair / triple forms: per-lane slot words over patients (scratch in the ctx workspace), records in LDS
-        rc = fcd_ws_reserve(ctx, ru_off + fcd_f_pass_ws_bytes(Nreg, U, g.GW));
+        rc = fcd_ws_reserve(ctx, pl.ws_bytes);
         if (rc) return rc;
-        uint32_t *r_U = (uint32_t *)((char *)ctx->ws + ru_off);
-        if (!ru_ready) {     // (inside fcd_gibbs_run the previous sweep's tally has made them already)
-            const int64_t items = (int64_t)g.GW * Nreg * pl.NW;
-            hipLaunchKernelGGL(pack_ru_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, r_bits, (int)Nreg, (int)U, pl.NW,
-                               g.GW, r_U);
+        uint32_t *r_U = (uint32_t *)((char *)ctx->ws + pl.r_U);
+        if (!st.ru_ready) {     // (inside the sweep loop the previous sweep's tally has made them already)
+            const int64_t items = (int64_t)g.GW * Nreg * pl.f_NW;
+            hipLaunchKernelGGL(pack_ru_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, c.r_bits, (int)Nreg, (int)U,
+                               pl.f_NW, g.GW, r_U);
             FCD_LAUNCH_CHECK();
         }
-        dim3 grid((unsigned)((g.C + pl.EC - 1) / pl.EC), (unsigned)((g.GW + wpb - 1) / wpb));
-#define FCD_F_ARGS S_B, lMf, hyper, f_state, r_U, (int)Nreg, (int)U, g.C, g.GW, (uint32_t)chain0, seed, (uint32_t)sweep, margin, fsq, (unsigned long long *)ctx->dbg
+        dim3 grid((unsigned)((g.C + pl.f_EC - 1) / pl.f_EC), (unsigned)((g.GW + wpb - 1) / wpb));
+#define FCD_F_ARGS c.S_B, c.lMf, c.hyper, c.f_state, r_U, (int)Nreg, (int)U, g.C, g.GW, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, margin, st.fsq, (unsigned long long *)ctx->dbg
 #define FCD_LAUNCH_F(KERN, SLOT)                                                                              \
     do {                                                                                                      \
-        rc = fcd_lds_attr(ctx, SLOT, reinterpret_cast<const void *>(&KERN), pl.shmem);                        \
+        rc = fcd_lds_attr(ctx, SLOT, reinterpret_cast<const void *>(&KERN), pl.f_shmem);                      \
         if (rc) return rc;                                                                                    \
         {                                                                                                     \
             static int lds0 = 0; /* (the pair form's record addresses start at LDS address 0) */              \
@@ -1283,18 +1244,18 @@ int fcd_gibbs_f_step_sq(fcd_ctx *ctx, const double *S_B, const double *lM, const
             if (rc) return rc;                                                                                \
         }                                                                                                     \
         fcd_prof_begin(ctx, FCD_PROF_F, s);                                                                   \
-        hipLaunchKernelGGL(KERN, grid, dim3(64 * wpb), pl.shmem, s, FCD_F_ARGS);                              \
+        hipLaunchKernelGGL(KERN, grid, dim3(64 * wpb), pl.f_shmem, s, FCD_F_ARGS);                            \
         fcd_prof_end(ctx, FCD_PROF_F, s);                                                                     \
     } while (0)
-        if (pl.form == F_PAIR) {
-            if (pl.NW16 == 1) FCD_LAUNCH_F(gibbs_f_pair_kernel<1>, FCD_KA_F_PAIR + 0);
-            else if (pl.NW16 == 2) FCD_LAUNCH_F(gibbs_f_pair_kernel<2>, FCD_KA_F_PAIR + 1);
-            else if (pl.NW16 == 3) FCD_LAUNCH_F(gibbs_f_pair_kernel<3>, FCD_KA_F_PAIR + 2);
+        if (form == FCD_F_PAIR) {
+            if (pl.f_NW == 1) FCD_LAUNCH_F(gibbs_f_pair_kernel<1>, FCD_KA_F_PAIR + 0);
+            else if (pl.f_NW == 2) FCD_LAUNCH_F(gibbs_f_pair_kernel<2>, FCD_KA_F_PAIR + 1);
+            else if (pl.f_NW == 3) FCD_LAUNCH_F(gibbs_f_pair_kernel<3>, FCD_KA_F_PAIR + 2);
             else FCD_LAUNCH_F(gibbs_f_pair_kernel<4>, FCD_KA_F_PAIR + 3);
         } else {
-            if (pl.EC == 8) FCD_LAUNCH_F(gibbs_f_pairx_kernel<8>, FCD_KA_F_PAIR_BIG + 0);
-            else if (pl.EC == 4) FCD_LAUNCH_F(gibbs_f_pairx_kernel<4>, FCD_KA_F_PAIR_BIG + 1);
-            else if (pl.EC == 2) FCD_LAUNCH_F(gibbs_f_pairx_kernel<2>, FCD_KA_F_PAIR_BIG + 2);
+            if (pl.f_EC == 8) FCD_LAUNCH_F(gibbs_f_pairx_kernel<8>, FCD_KA_F_PAIR_BIG + 0);
+            else if (pl.f_EC == 4) FCD_LAUNCH_F(gibbs_f_pairx_kernel<4>, FCD_KA_F_PAIR_BIG + 1);
+            else if (pl.f_EC == 2) FCD_LAUNCH_F(gibbs_f_pairx_kernel<2>, FCD_KA_F_PAIR_BIG + 2);
             else FCD_LAUNCH_F(gibbs_f_pairx_kernel<1>, FCD_KA_F_PAIR_BIG + 3);
         }
 #undef FCD_LAUNCH_F
@@ -1303,12 +1264,12 @@ int fcd_gibbs_f_step_sq(fcd_ctx *ctx, const double *S_B, const double *lM, const
         return FCD_OK;
     }
     // a patient row that fits no pair tile (U > 1280): log-odds form with scalar r masks
-    rc = fcd_lds_attr(ctx, FCD_KA_F_DIFF, reinterpret_cast<const void *>(&gibbs_f_diff_kernel), pl.shmem);
+    rc = fcd_lds_attr(ctx, FCD_KA_F_DIFF, reinterpret_cast<const void *>(&gibbs_f_diff_kernel), pl.f_shmem);
     if (rc) return rc;
-    dim3 grid((unsigned)((g.C + pl.EC - 1) / pl.EC), (unsigned)((g.GW + wpb - 1) / wpb));
+    dim3 grid((unsigned)((g.C + pl.f_EC - 1) / pl.f_EC), (unsigned)((g.GW + wpb - 1) / wpb));
     fcd_prof_begin(ctx, FCD_PROF_F, s);
-    hipLaunchKernelGGL(gibbs_f_diff_kernel, grid, dim3(64 * wpb), pl.shmem, s, S_B, lMf, hyper, f_state, r_bits,
-                       (int)Nreg, (int)U, g.C, g.GW, pl.EC, (uint32_t)chain0, seed, (uint32_t)sweep, margin);
+    hipLaunchKernelGGL(gibbs_f_diff_kernel, grid, dim3(64 * wpb), pl.f_shmem, s, c.S_B, c.lMf, c.hyper, c.f_state, c.r_bits,
+                       (int)Nreg, (int)U, g.C, g.GW, pl.f_EC, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, margin);
     fcd_prof_end(ctx, FCD_PROF_F, s);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
@@ -1328,40 +1289,6 @@ extern "C" int fcd_gibbs_stats(fcd_ctx *ctx, const uint8_t *f_state, const uint6
     hipLaunchKernelGGL(gibbs_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, s, f_state, r_bits, g.C, Nreg * U, g.GW, G,
                        reinterpret_cast<unsigned long long *>(counts));
     FCD_LAUNCH_CHECK();
-    return FCD_OK;
-}
-
-extern "C" int fcd_gibbs_sweeps(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *lMd,
-                                const double *hyper,
-                                uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0,
-                                uint64_t seed, int64_t sweep0, int64_t n_sweeps, int edge_mode, int64_t *counts,
-                                fcd_stream stream) {
-    if (n_sweeps < 0 || sweep0 < 0 || sweep0 + n_sweeps > (1ll << 32))
-        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_sweeps: sweep range [%lld, +%lld) outside the 32-bit counter word", sweep0, n_sweeps);
-    // symmetric edge ids + a pair-form f kernel + the blocked r pass: the f pass leaves a square copy of the f state
-    // from which the r pass packs its f words (contiguous rows instead of 64-byte gathers: ~40 us -> ~10 us at cfg3).
-    // The copy lives in the context (fcd_ctx_reserve sizes it; a first call at a larger shape grows it here, which
-    // synchronises -- the one case the header names).
-    uint8_t *fsq = nullptr;
-    if (ctx && lMf && lMd && edge_mode == FCD_EDGE_SYMMETRIC && Nreg >= 2 && U >= 1 && G >= 1 && true) {
-        const int64_t GW = (G + 63) / 64;
-        const f_plan pl = f_plan_for(true, Nreg, U, GW, ctx->knobs.f_form);
-        const size_t need = (size_t)GW * Nreg * Nreg * 64;
-        if ((pl.form == F_PAIR || pl.form == F_PAIRX) && need <= ((size_t)8 << 30)) {
-            int rc = fcd_fsq_reserve(ctx, need);
-            if (rc) return rc;
-            fsq = (uint8_t *)ctx->fsq;
-        }
-    }
-    for (int64_t i = 0; i < n_sweeps; ++i) {
-        int rc = fcd_gibbs_f_step_sq(ctx, S_B, lM, lMf, hyper, f_state, r_bits, Nreg, U, G, chain0, seed, sweep0 + i,
-                                     (hipStream_t)stream, fsq, false);
-        if (rc) return rc;
-        rc = fcd_gibbs_r_step_sq(ctx, lM, lMd, hyper, f_state, r_bits, Nreg, U, G, chain0, seed, sweep0 + i, edge_mode,
-                                 (hipStream_t)stream, fsq);
-        if (rc) return rc;
-    }
-    if (counts && n_sweeps > 0) return fcd_gibbs_stats(ctx, f_state, r_bits, Nreg, U, G, counts, stream);
     return FCD_OK;
 }
 
@@ -1433,73 +1360,58 @@ extern "C" int fcd_gibbs_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint6
     return launch_tally(ctx, f_state, r_bits, Nreg, U, G, g, counts, cnt_f, cnt_r, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
-// The sampler loop of ONE rank between two exchanges of pooled statistics (what UnsharedRegionFit(method='gibbs'),
-// run_chains and bench.py call).  Per sweep: f pass (1 launch), packing for the r pass (1), block steps of the r pass
-// (ceil(Nreg/16) + 1), tally (1) -- the tally also carries the M-step and the slot words of the next f pass.
-extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *lMd,
-                             double *hyper, uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
-                             int64_t chain0, uint64_t seed, int64_t sweep0, int64_t n_sweeps, int edge_mode,
-                             int64_t mstep_every, int64_t accumulate_from, int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r,
-                             fcd_stream stream) {
-    fcd_geo g;
-    int rc = fcd_geo_check(ctx, Nreg, U, G, chain0, g);
-    if (rc) return rc;
+// The sampler loop of ONE rank between two exchanges of pooled statistics: fcd_gibbs_run (what UnsharedRegionFit(method=
+// 'gibbs'), run_chains and bench.py call) and fcd_gibbs_sweeps.  Per sweep: f pass (1 launch), packing for the r pass (1),
+// r pass (one pipelined launch, or ceil(Nreg/16) + 1 block steps), tally (1) -- the tally also carries the M-step and the
+// slot words of the next f pass.  hyper_m: what the M-step writes (nullptr when mstep_every == 0); pair_acc: add the
+// (f_c, mixture case) counts to the context's pair accumulator.
+static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int64_t n_sweeps, int64_t mstep_every,
+                      int64_t accumulate_from, int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r, double *hyper_m,
+                      bool pair_acc) {
     if (n_sweeps < 0 || sweep0 < 0 || sweep0 + n_sweeps > (1ll << 32))
-        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_run: sweep range [%lld, +%lld) outside the 32-bit counter word", sweep0, n_sweeps);
-    if (!S_B || !lM || !hyper || !f_state || !r_bits) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_run: null pointer");
-    if ((cnt_f == nullptr) != (cnt_r == nullptr)) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_run: cnt_f and cnt_r go together");
-    if (mstep_every < 0) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_run: mstep_every < 0");
-    if (ctx->pair_acc && (ctx->pair_nreg != Nreg || ctx->pair_u != U))
-        return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_run: the attached pair accumulator was made for Nreg=%lld, U=%lld",
-                        ctx->pair_nreg, ctx->pair_u);
-    hipStream_t s = (hipStream_t)stream;
-    // square copy of the f state for the r pass's packing (see fcd_gibbs_sweeps)
-    uint8_t *fsq = nullptr;
-    const f_plan pl = f_plan_for(lMf != nullptr, Nreg, U, g.GW, ctx->knobs.f_form);
-    const bool pair_form = pl.form == F_PAIR || pl.form == F_PAIRX;
-    if (pair_form && lMd && edge_mode == FCD_EDGE_SYMMETRIC && true) {
-        const size_t need = (size_t)g.GW * Nreg * Nreg * 64;
-        if (need <= ((size_t)8 << 30)) {
-            rc = fcd_fsq_reserve(ctx, need);
-            if (rc) return rc;
-            fsq = (uint8_t *)ctx->fsq;
-        }
+        return fcd_fail(ctx, FCD_ERR_ARG, "sweep range [%lld, +%lld) outside the 32-bit counter word", sweep0, n_sweeps);
+    const fcd_sweep_plan &pl = c.pl;
+    const fcd_geo &g = c.g;
+    const int64_t Nreg = c.Nreg, U = c.U, G = c.G;
+    hipStream_t s = c.s;
+    const bool pair_form = c.lMf && (pl.f_form == FCD_F_PAIR || pl.f_form == FCD_F_PAIRX);
+    fcd_sweep_step st = {sweep0};
+    // the square copy of the f state: where the plan has one, both tables are there and the edge ids are symmetric
+    if (pl.fsq_bytes && c.lMf && c.lMd && c.edge_mode == FCD_EDGE_SYMMETRIC) {
+        int rc = fcd_fsq_reserve(ctx, pl.fsq_bytes);
+        if (rc) return rc;
+        st.fsq = (uint8_t *)ctx->fsq;
     }
-    // The slot words of the f pass live BEHIND the r pass's workspace inside this loop (on their own they sit at its head):
-    // the r pass's two buffers of panel values then survive from one sweep to the next, and since a completed pipelined
-    // pass leaves every slot holding its sentinel again, only the first sweep of a call has to write them (13 MB at cfg3).
-    size_t ru_off = 0;
+    // The slot words of the f pass live behind the r pass's scratch (fcd_sweep_plan): the r pass's two buffers of panel
+    // values then survive from one sweep to the next, and since a completed pipelined pass leaves every slot holding its
+    // sentinel again, only the first sweep of a call has to write them (13 MB at cfg3).
     if (pair_form) {
-        ru_off = (fcd_r_pass_ws_bytes(Nreg, U, g.GW, ctx->knobs.r_path) + 511) / 512 * 512;
-        rc = fcd_ws_reserve(ctx, ru_off + fcd_f_pass_ws_bytes(Nreg, U, g.GW));      // the tally writes the next pass's slot words there
+        int rc = fcd_ws_reserve(ctx, pl.ws_bytes);      // the tally writes the next pass's slot words there
         if (rc) return rc;
     }
-    bool ru_ready = false;
-    bool sentinels_in_place = false;
     for (int64_t i = 0; i < n_sweeps; ++i) {
-        rc = fcd_gibbs_f_step_sq(ctx, S_B, lM, lMf, hyper, f_state, r_bits, Nreg, U, G, chain0, seed, sweep0 + i, s, fsq, ru_ready, ru_off);
+        st.sweep = sweep0 + i;
+        int rc = fcd_gibbs_f_pass(ctx, c, st);
         if (rc) return rc;
         const bool last = i + 1 == n_sweeps;
         const bool do_m = mstep_every > 0 && (i + 1) % mstep_every == 0;
-        const bool do_a = cnt_f && sweep0 + i >= accumulate_from;
+        const bool do_a = cnt_f && st.sweep >= accumulate_from;
         // the f half of this sweep's tally rides in the r pass's packing launch (beside it, not after the pass)
         fcd_tally_f tf;
-        tf.f_state = f_state; tf.C = g.C; tf.G = G; tf.GW = g.GW;
+        tf.f_state = c.f_state; tf.C = g.C; tf.G = G; tf.GW = g.GW;
         tf.acc = (do_m || (last && counts)) ? (unsigned long long *)ctx->acc : nullptr;
         tf.cnt_f = do_a ? cnt_f : nullptr;
-        const bool want_f = tf.acc || tf.cnt_f;
-        bool f_done = false;
-        rc = fcd_gibbs_r_step_sq(ctx, lM, lMd, hyper, f_state, r_bits, Nreg, U, G, chain0, seed, sweep0 + i, edge_mode, s, fsq,
-                                 want_f ? &tf : nullptr, &f_done, sentinels_in_place);
+        st.tally_f = (tf.acc || tf.cnt_f) ? &tf : nullptr;
+        rc = fcd_gibbs_r_pass(ctx, c, st);
         if (rc) {
             // the packing launch may already have added this sweep's f counts into the context's accumulators and no tally
             // will draw the ticket that zeroes them: leave them clean for the next call
             if (tf.acc) (void)hipMemsetAsync(ctx->acc, 0, 8 * sizeof(unsigned long long), s);
             return rc;
         }
-        sentinels_in_place = pair_form && ctx->r_form_last == 2;        // (a pipelined pass has just been queued)
-        // the r pass's scratch is dead once its last launch is queued: the slot words of the next f pass go to its place
-        uint32_t *r_U_next = (pair_form && !last) ? (uint32_t *)((char *)ctx->ws + ru_off) : nullptr;
+        st.sentinels_in_place = pair_form && ctx->r_form_last == 2;        // (a pipelined pass has just been queued)
+        // the r pass's scratch is dead once its last launch is queued: the slot words of the next f pass go to their place
+        uint32_t *r_U_next = (pair_form && !last) ? (uint32_t *)((char *)ctx->ws + pl.r_U) : nullptr;
         int64_t *cts = (last ? counts : nullptr);
         // Several ranks (a communicator on the context): the tally leaves this rank's counts in the context's vector, RCCL sums
         // it over the ranks in place ON THIS STREAM, a one-thread kernel makes the M-step from the pooled counts -- all queued
@@ -1507,8 +1419,8 @@ extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, 
         const bool pooled = do_m && ctx->comm != nullptr;
         int64_t *tally_counts = pooled ? (int64_t *)ctx->pool_counts : cts;
         if (do_m || do_a || cts || r_U_next) {
-            rc = launch_tally(ctx, f_state, r_bits, Nreg, U, G, g, tally_counts, do_a ? cnt_f : nullptr, do_a ? cnt_r : nullptr,
-                              (do_m && !pooled) ? hyper : nullptr, r_U_next, pl.NW, s, f_done);
+            rc = launch_tally(ctx, c.f_state, c.r_bits, Nreg, U, G, g, tally_counts, do_a ? cnt_f : nullptr, do_a ? cnt_r : nullptr,
+                              (do_m && !pooled) ? hyper_m : nullptr, r_U_next, pl.f_NW, s, st.tally_f_done);
             if (rc) {
                 if (tf.acc) (void)hipMemsetAsync(ctx->acc, 0, 8 * sizeof(unsigned long long), s);
                 return rc;
@@ -1518,7 +1430,7 @@ extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, 
             rc = fcd_comm_allreduce_counts(ctx, (long long *)ctx->pool_counts, s);
             if (rc) return rc;
             hipLaunchKernelGGL(gibbs_mstep_kernel, dim3(1), dim3(1), 0, s, (const long long *)ctx->pool_counts, (double)(Nreg * U),
-                               (double)fcd_tri(Nreg), hyper);
+                               (double)fcd_tri(Nreg), hyper_m);
             FCD_LAUNCH_CHECK();
             if (cts) FCD_HIP_TRY(hipMemcpyAsync(cts, ctx->pool_counts, 8 * sizeof(long long), hipMemcpyDeviceToDevice, s));
         } else if (cts && ctx->comm) {
@@ -1527,12 +1439,44 @@ extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, 
             if (rc) return rc;
         }
         // (f_c, mixture case) counts of the end-of-sweep state (fcd_gibbs_set_pair_accumulator): one launch of its own
-        if (ctx->pair_acc && sweep0 + i >= accumulate_from && (sweep0 + i - accumulate_from) % ctx->pair_every == 0) {
-            rc = fcd_pair_tally_launch(ctx, f_state, r_bits, Nreg, U, G, g, ctx->pair_acc, s);
+        if (pair_acc && st.sweep >= accumulate_from && (st.sweep - accumulate_from) % ctx->pair_every == 0) {
+            rc = fcd_pair_tally_launch(ctx, c.f_state, c.r_bits, Nreg, U, G, g, ctx->pair_acc, s);
             if (rc) return rc;
         }
-        ru_ready = r_U_next != nullptr;
+        st.ru_ready = r_U_next != nullptr;
     }
+    return FCD_OK;
+}
+
+extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *lMd,
+                             double *hyper, uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
+                             int64_t chain0, uint64_t seed, int64_t sweep0, int64_t n_sweeps, int edge_mode,
+                             int64_t mstep_every, int64_t accumulate_from, int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r,
+                             fcd_stream stream) {
+    fcd_sweep_call c = {S_B, lM, lMf, lMd, hyper, f_state, r_bits, Nreg, U, G, chain0, seed, edge_mode, (hipStream_t)stream};
+    int rc = fcd_sweep_call_check(ctx, c, true, true, "fcd_gibbs_run");
+    if (rc) return rc;
+    if ((cnt_f == nullptr) != (cnt_r == nullptr)) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_run: cnt_f and cnt_r go together");
+    if (mstep_every < 0) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_run: mstep_every < 0");
+    if (ctx->pair_acc && (ctx->pair_nreg != Nreg || ctx->pair_u != U))
+        return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_run: the attached pair accumulator was made for Nreg=%lld, U=%lld",
+                        ctx->pair_nreg, ctx->pair_u);
+    return sweep_loop(ctx, c, sweep0, n_sweeps, mstep_every, accumulate_from, counts, cnt_f, cnt_r, hyper, ctx->pair_acc != nullptr);
+}
+
+// fcd_gibbs_run's loop without M-step, marginal counters or pair counts.  The counts are made by fcd_gibbs_stats after the
+// loop: this rank's own, never pooled over an attached communicator.
+extern "C" int fcd_gibbs_sweeps(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *lMd,
+                                const double *hyper,
+                                uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0,
+                                uint64_t seed, int64_t sweep0, int64_t n_sweeps, int edge_mode, int64_t *counts,
+                                fcd_stream stream) {
+    fcd_sweep_call c = {S_B, lM, lMf, lMd, hyper, f_state, r_bits, Nreg, U, G, chain0, seed, edge_mode, (hipStream_t)stream};
+    int rc = fcd_sweep_call_check(ctx, c, true, true, "fcd_gibbs_sweeps");
+    if (rc) return rc;
+    rc = sweep_loop(ctx, c, sweep0, n_sweeps, 0, 0, nullptr, nullptr, nullptr, nullptr, false);
+    if (rc) return rc;
+    if (counts && n_sweeps > 0) return fcd_gibbs_stats(ctx, f_state, r_bits, Nreg, U, G, counts, stream);
     return FCD_OK;
 }
 

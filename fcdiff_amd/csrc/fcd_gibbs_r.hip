@@ -27,6 +27,8 @@
 // + one fp64 add + two integer instructions.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "fcd_common.h"
 
 namespace {
@@ -241,7 +243,7 @@ struct r_step_args {
     uint32_t *flags;        // pipelined form: one mark per (chain word, patient, block); else nullptr
     int Nreg, U, NBLK, GW;
     int u_lo, u_n;          // the patients this launch serves: [u_lo, u_lo + u_n)  (patients are independent given f: a pass
-                            // may run as two half-passes on two streams, see fcd_gibbs_r_step_sq)
+                            // may run as two half-passes on two streams, see fcd_gibbs_r_pass)
     int wpb, nWG;           // chain words per workgroup, groups of chain words
     int s, nD, nP;          // step-per-launch form: the step and the number of workgroups per role
     int ncu, npad;          // ... CUs of the device; empty workgroups at [ncu, ncu + npad) (beside the D workgroups)
@@ -1444,6 +1446,8 @@ int launch_pipe(fcd_ctx *ctx, const r_step_args &a, size_t shmem, bool *fits, bo
     // on the device; a workgroup that starts late only makes the others wait -- every poll is bounded)
     *fits = (int64_t)ctx->pipe_occ[slot] * ctx->num_cu >= (int64_t)a.nD + a.nP + R_PIPE_SLOT_MARGIN;
     if (!*fits || !launch) return FCD_OK;
+    // (fcd_prof_begin records the begin event of the next pair, fcd_prof_end closes and counts it: a launch the runtime
+    // refuses between the two leaves no pair open -- the next fcd_prof_begin records that begin event again)
     fcd_prof_begin(ctx, FCD_PROF_RSTEP, s);
     if (ctx->knobs.r_coop == 1) {
         // a COOPERATIVE launch (knob r_coop = 1): the runtime itself refuses a grid that cannot be resident at once (the
@@ -1468,26 +1472,81 @@ int launch_pipe(fcd_ctx *ctx, const r_step_args &a, size_t shmem, bool *fits, bo
     return FCD_OK;
 }
 
-// workspace of the blocked path: P[2] | f_S | r_S | r_Sn | flags   (one formula for reserve and launch)
-struct r_ws_layout {
-    size_t t_bytes, f_bytes, s_bytes, flag_words, total;
-};
-static r_ws_layout r_ws_blocked(int64_t Nreg, int64_t U, int64_t GW) {
-    r_ws_layout L;
-    const int64_t NBLK = (Nreg + R_NB - 1) / R_NB;
-    L.t_bytes = (size_t)GW * U * R_NB * 64 * sizeof(double);        // one buffer of panel values
-    L.f_bytes = (size_t)GW * Nreg * NBLK * 64 * sizeof(uint2);
-    L.s_bytes = (size_t)GW * U * NBLK * 64 * sizeof(uint2);
-    L.flag_words = (size_t)GW * U * NBLK;                           // pipelined form: one mark per (word, patient, block)
-    L.total = 2 * L.t_bytes + L.f_bytes + 2 * L.s_bytes + L.flag_words * sizeof(uint32_t) + 512;
-    return L;
+// The one ub -> <UB, WPE> dispatch of the blocked pass (WPE: waves per EU its kernels are bounded to): f(UB, WPE) with
+// both as std::integral_constant
+template <class F>
+int with_ub(int ub, F &&f) {
+    if (ub == 4) return f(std::integral_constant<int, 4>(), std::integral_constant<int, 4>());
+    if (ub == 2) return f(std::integral_constant<int, 2>(), std::integral_constant<int, 8>());
+    return f(std::integral_constant<int, 1>(), std::integral_constant<int, 8>());
 }
 }  // namespace
 
-size_t fcd_r_pass_ws_bytes(int64_t Nreg, int64_t U, int64_t GW, int r_path) {
-    const size_t per_u_need = (size_t)((Nreg + R_NB - 1) / R_NB) * ((R_NB / 2) * 36 + R_NB * 6) * sizeof(double);
-    if (per_u_need > 156 * 1024 || Nreg + U > 65535) return 0;          // generic kernel: no scratch
-    return r_ws_blocked(Nreg, U, GW).total;
+fcd_sweep_plan fcd_sweep_plan_for(const fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t GW) {
+    fcd_sweep_plan p = {};
+    // ---- f pass (fcd_gibbs.hip): fp32 records of patient pairs in LDS where a tile fits, else fp64 log-odds rows
+    p.f_NW = (int)((U + 15) / 16);
+    const int f_form = ctx->knobs.f_form;
+    const bool words_ok = GW * Nreg * p.f_NW < INT32_MAX / 4;       // r_U item index in 32 bits
+    const size_t pair_shmem = (size_t)FP_EC * ((U + 1) / 2) * 128 + FP_EC * 16 + (size_t)FP_EC * U * 48;   // fp32 records, edge constants, fp64 rows
+    const size_t per_edge = (size_t)((U + 1) / 2) * 128, extra = 128 + 16 * 48 * 16;   // fp32 records; edge constants + a 768-byte staging scratch per wave
+    if ((size_t)U * 48 > 160 * 1024) {
+        p.f_form = FCD_F_GENERIC;
+    } else if (f_form != FCD_F_PAIRX && f_form != FCD_F_DIFF && p.f_NW <= 4 && pair_shmem <= 96 * 1024 && words_ok) {
+        p.f_form = FCD_F_PAIR;
+        p.f_EC = FP_EC;
+        p.f_shmem = pair_shmem;
+    } else if (f_form != FCD_F_DIFF && words_ok && per_edge + extra <= 160 * 1024) {
+        // largest tile that still lets two workgroups share a CU; one edge per tile may take the whole LDS
+        int ec = 8;
+        while (ec > 1 && (size_t)ec * per_edge + extra > 80 * 1024) ec >>= 1;
+        p.f_form = FCD_F_PAIRX;
+        p.f_EC = ec;
+        p.f_shmem = (size_t)ec * per_edge + extra;
+    } else {
+        int64_t e = (int64_t)(24 * 1024 / ((size_t)U * 48));
+        if (e < 1) e = 1;
+        if (e > 8) e = 8;
+        if (e > 1) e &= ~1ll;   // even: both halves of a Philox block are used inside one tile
+        p.f_form = FCD_F_DIFF;
+        p.f_EC = (int)e;
+        p.f_shmem = (size_t)U * 48 * e;
+    }
+    const bool pair_form = p.f_form == FCD_F_PAIR || p.f_form == FCD_F_PAIRX;
+    // ---- r pass: the blocked form where a patient's pair tile (288 B per pair of regions) and single rows fit the LDS
+    const int64_t NBLK = (Nreg + R_NB - 1) / R_NB;
+    const size_t per_u = (size_t)NBLK * ((R_NB / 2) * 36 + R_NB * 6) * sizeof(double);
+    p.r_blocked = per_u <= 156 * 1024 && Nreg + U <= 65535;
+    p.r_idx32 = GW * Nreg * NBLK <= INT32_MAX / 4 && fcd_tri(Nreg) * 64 <= INT32_MAX && GW * U * R_NB <= INT32_MAX / 64;
+    // Two workgroups must fit a CU so that their staging / pair-build / term phases overlap: 2 patients where their
+    // tile takes at most half the LDS (cfg3: 2 x 39.9 KB), else 1 (cfg5: 76.8 KB per patient; measured 3.99 ms per pass
+    // against 4.58 ms with 2 patients and one workgroup per CU)
+    p.r_ub = ((size_t)4 * per_u <= 160 * 1024 && U >= 2) ? 2 : 1;
+    {   // tuning knob: patients per panel workgroup (1, 2, 4)
+        const int v = ctx->knobs.r_ub;
+        if ((v == 1 || v == 2 || v == 4) && (size_t)v * per_u <= 156 * 1024) p.r_ub = v;
+    }
+    const size_t d_need = (size_t)(GW < 16 ? D_LDS_SPREAD : D_LDS_COMPACT) * sizeof(double);     // (the in-order role)
+    p.r_shmem = (size_t)p.r_ub * per_u > d_need ? (size_t)p.r_ub * per_u : d_need;
+    // ---- square copy of the f state (a pair-form f pass writes it)
+    const size_t fsq = (size_t)GW * Nreg * Nreg * 64;
+    p.fsq_bytes = (pair_form && fsq <= ((size_t)8 << 30)) ? fsq : 0;
+    // ---- workspace
+    size_t r_end = 0;
+    if (p.r_blocked) {
+        const size_t t_bytes = (size_t)GW * U * R_NB * 64 * sizeof(double);        // one buffer of panel values
+        const size_t s_bytes = (size_t)GW * U * NBLK * 64 * sizeof(uint2);
+        p.P[1] = t_bytes;                                                             // (P[0] = 0)
+        p.f_S = 2 * t_bytes;
+        p.r_S = p.f_S + (size_t)GW * Nreg * NBLK * 64 * sizeof(uint2);
+        p.r_Sn = p.r_S + s_bytes;
+        p.marks = p.r_Sn + s_bytes;
+        r_end = p.marks + (size_t)GW * U * NBLK * sizeof(uint32_t) + 512;       // one mark per (word, patient, block)
+    }
+    p.r_U = (r_end + 511) / 512 * 512;
+    // slot words of the pair forms: 16 patients per word, up to four words side by side per lane, else [word][lane] (ru_index)
+    p.ws_bytes = p.r_U + (pair_form ? (size_t)GW * Nreg * (p.f_NW <= 4 ? 4 : p.f_NW) * 64 * sizeof(uint32_t) : 0);
+    return p;
 }
 
 extern "C" int fcd_gibbs_region_tables(fcd_ctx *ctx, const double *lM, int64_t Nreg, int64_t U, int edge_mode, double *lMd,
@@ -1511,73 +1570,47 @@ extern "C" int fcd_gibbs_region_tables(fcd_ctx *ctx, const double *lM, int64_t N
 extern "C" int fcd_gibbs_r_step(fcd_ctx *ctx, const double *lM, const double *lMd, const double *hyper,
                                 const uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
                                 int64_t chain0, uint64_t seed, int64_t sweep, int edge_mode, fcd_stream stream) {
-    return fcd_gibbs_r_step_sq(ctx, lM, lMd, hyper, f_state, r_bits, Nreg, U, G, chain0, seed, sweep, edge_mode,
-                               (hipStream_t)stream, nullptr);
+    fcd_sweep_call c = {nullptr, lM, nullptr, lMd, hyper, const_cast<uint8_t *>(f_state) /* (read only) */, r_bits, Nreg, U, G,
+                        chain0, seed, edge_mode, (hipStream_t)stream};
+    fcd_sweep_step st = {sweep};
+    int rc = fcd_sweep_call_check(ctx, c, false, true, "fcd_gibbs_r_step");
+    return rc ? rc : fcd_gibbs_r_pass(ctx, c, st);
 }
 
-int fcd_gibbs_r_step_sq(fcd_ctx *ctx, const double *lM, const double *lMd, const double *hyper,
-                        const uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0,
-                        uint64_t seed, int64_t sweep, int edge_mode, hipStream_t stream, const uint8_t *fsq,
-                        const fcd_tally_f *tally_f, bool *tally_f_done, bool sentinels_in_place) {
-    if (tally_f_done) *tally_f_done = false;
-    fcd_geo g;
-    int rc = fcd_geo_check(ctx, Nreg, U, G, chain0, g);
-    if (rc) return rc;
-    if (!lM || !hyper || !f_state || !r_bits) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_r_step: null pointer");
+int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) {
+    st.tally_f_done = false;
     if (ctx->dev_err && *ctx->dev_err) return fcd_fail(ctx, FCD_ERR_DEVICE, "r pass: a device-side wait was abandoned in an earlier call");
-    if (edge_mode != FCD_EDGE_REFERENCE && edge_mode != FCD_EDGE_SYMMETRIC)
-        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_r_step: edge_mode %lld", edge_mode);
-    if (edge_mode == FCD_EDGE_REFERENCE && Nreg == 2)
-        return fcd_fail(ctx, FCD_ERR_INDEX, "reference edge ids: index 1 is out of bounds for axis 0 with size 1 (Nreg=2)");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t per_u_need = (size_t)((Nreg + R_NB - 1) / R_NB) * ((R_NB / 2) * 36 + R_NB * 6) * sizeof(double);
-    if (!lMd || per_u_need > 156 * 1024 || Nreg + U > 65535) {
+    const fcd_sweep_plan &pl = c.pl;
+    const fcd_geo &g = c.g;
+    const int64_t Nreg = c.Nreg, U = c.U;
+    const int edge_mode = c.edge_mode;
+    hipStream_t s = c.s;
+    if (!c.lMd || !pl.r_blocked) {
         // generic path: direct gathers from the edge-major table
         const size_t shmem = (size_t)Nreg * 8 + (size_t)R_WAVES * 2 * 64 * 8;
         if (shmem > 64 * 1024) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "r step: Nreg=%lld exceeds the LDS mask array", Nreg);
         if (U > 65535) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "r step: U=%lld exceeds the grid", U);
-        hipLaunchKernelGGL(gibbs_r_simple, dim3((unsigned)U, (unsigned)g.GW), dim3(64 * R_WAVES), shmem, s, lM, hyper, f_state,
-                           r_bits, (int)Nreg, (int)U, g.C, (uint32_t)chain0, seed, (uint32_t)sweep, edge_mode);
+        hipLaunchKernelGGL(gibbs_r_simple, dim3((unsigned)U, (unsigned)g.GW), dim3(64 * R_WAVES), shmem, s, c.lM, c.hyper,
+                           c.f_state, c.r_bits, (int)Nreg, (int)U, g.C, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, edge_mode);
         FCD_LAUNCH_CHECK();
         ctx->r_form_last = 0;
         return FCD_OK;
     }
-    // blocked path.  Workspace: P[2] | f_S | r_S | r_Sn | marks
+    // blocked path, its scratch where the plan puts it
     const int NBLK = (int)((Nreg + R_NB - 1) / R_NB);
-    const r_ws_layout L = r_ws_blocked(Nreg, U, g.GW);
-    const size_t t_bytes = L.t_bytes, f_bytes = L.f_bytes, s_bytes = L.s_bytes;
-    if ((int64_t)g.GW * Nreg * NBLK > INT32_MAX / 4 || g.C * 64 > INT32_MAX || (int64_t)g.GW * U * R_NB > INT32_MAX / 64)
-        return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "r step: Nreg=%lld with G=%lld exceeds 32-bit item indices", Nreg, G);
-    rc = fcd_ws_reserve(ctx, L.total);
+    if (!pl.r_idx32)
+        return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "r step: Nreg=%lld with G=%lld exceeds 32-bit item indices", Nreg, c.G);
+    int rc = fcd_ws_reserve(ctx, pl.ws_bytes);
     if (rc) return rc;
-    char *wsp = (char *)ctx->ws;
-    double *Pb[2] = {(double *)wsp, (double *)(wsp + t_bytes)};
-    wsp += 2 * t_bytes;
-    uint2 *f_S = (uint2 *)wsp;
-    wsp += f_bytes;
-    uint2 *r_S = (uint2 *)wsp, *r_Sn = (uint2 *)(wsp + s_bytes);
-    wsp += 2 * s_bytes;
-    uint32_t *marks = (uint32_t *)wsp;
+    char *ws = (char *)ctx->ws;
+    uint2 *f_S = (uint2 *)(ws + pl.f_S), *r_S = (uint2 *)(ws + pl.r_S);
     fcd_abl_refresh(s);
-    // patients per panel workgroup: the pair tile (288 B per pair of regions) + the single rows must fit the LDS
-    const size_t per_u = (size_t)NBLK * ((R_NB / 2) * 36 + R_NB * 6) * sizeof(double);
-    // Two workgroups must fit a CU so that their staging / pair-build / term phases overlap: 2 patients where their
-    // tile takes at most half the LDS (cfg3: 2 x 39.9 KB), else 1 (cfg5: 76.8 KB per patient; measured 3.99 ms per pass
-    // against 4.58 ms with 2 patients and one workgroup per CU)
-    int ub = ((size_t)4 * per_u <= 160 * 1024 && U >= 2) ? 2 : 1;
-    {   // tuning knob: patients per panel workgroup (1, 2, 4)
-        const int v = ctx->knobs.r_ub;
-        if ((v == 1 || v == 2 || v == 4) && (size_t)v * per_u <= 156 * 1024) ub = v;
-    }
-    size_t shmem = (size_t)ub * per_u;
-    {
-        const size_t d_need = (size_t)(g.GW < 16 ? D_LDS_SPREAD : D_LDS_COMPACT) * sizeof(double);
-        if (shmem < d_need) shmem = d_need;
-    }
+    const int ub = pl.r_ub;
+    const size_t shmem = pl.r_shmem;
     r_step_args a;
-    a.lMd = lMd; a.hyper = hyper; a.f_S = f_S;
-    a.r_S = r_S; a.r_Sn = r_Sn; a.r_bits = r_bits;
-    a.Pbuf[0] = Pb[0]; a.Pbuf[1] = Pb[1];
+    a.lMd = c.lMd; a.hyper = c.hyper; a.f_S = f_S;
+    a.r_S = r_S; a.r_Sn = (uint2 *)(ws + pl.r_Sn); a.r_bits = c.r_bits;
+    a.Pbuf[0] = (double *)(ws + pl.P[0]); a.Pbuf[1] = (double *)(ws + pl.P[1]);
     a.flags = nullptr;
     a.Nreg = (int)Nreg; a.U = (int)U; a.NBLK = NBLK; a.GW = g.GW;
     a.u_lo = 0; a.u_n = (int)U;
@@ -1585,7 +1618,7 @@ int fcd_gibbs_r_step_sq(fcd_ctx *ctx, const double *lM, const double *lMd, const
     a.nWG = (g.GW + a.wpb - 1) / a.wpb;
     a.s = 0; a.nD = 0; a.nP = 0;
     a.ncu = ctx->num_cu; a.npad = 0;
-    a.chain0 = (uint32_t)chain0; a.sweep = (uint32_t)sweep; a.seed = seed;
+    a.chain0 = (uint32_t)c.chain0; a.sweep = (uint32_t)st.sweep; a.seed = c.seed;
     a.tol = 16.0 * FCD_LOGIT_FAST_ERR;
     a.poll_limit = ctx->knobs.r_poll_limit > 0 ? ctx->knobs.r_poll_limit : R_POLL_LIMIT;
     a.withhold = ctx->knobs.r_withhold;
@@ -1609,21 +1642,19 @@ int fcd_gibbs_r_step_sq(fcd_ctx *ctx, const double *lM, const double *lMd, const
             a.nD = 2 * (int)U;
             a.npad = 0;
         }
-        if (ub == 4) rc = launch_pipe<4, 4>(ctx, a, shmem, &pipe, false, s);
-        else if (ub == 2) rc = launch_pipe<2, 8>(ctx, a, shmem, &pipe, false, s);
-        else rc = launch_pipe<1, 8>(ctx, a, shmem, &pipe, false, s);
+        rc = with_ub(ub, [&](auto UB, auto WPE) { return launch_pipe<UB, WPE>(ctx, a, shmem, &pipe, false, s); });
         if (rc) return rc;
         if (pipe) {
-            pinit.marks = marks;
-            // (the sentinels: unless a completed pipelined pass of this shape left them in place -- fcd_gibbs_run knows)
-            const bool keep = sentinels_in_place && ctx->r_form_last == 2 && !ctx->knobs.r_refill;
-            pinit.P[0] = keep ? nullptr : Pb[0];
-            pinit.P[1] = keep ? nullptr : Pb[1];
+            pinit.marks = (uint32_t *)(ws + pl.marks);
+            // (the sentinels: unless a completed pipelined pass of this shape left them in place -- the sweep loop knows)
+            const bool keep = st.sentinels_in_place && ctx->r_form_last == 2 && !ctx->knobs.r_refill;
+            pinit.P[0] = keep ? nullptr : a.Pbuf[0];
+            pinit.P[1] = keep ? nullptr : a.Pbuf[1];
         }
     }
     {
         // one launch packs the f words of every region and the r words of every patient
-        const int fb = fsq ? 2 : 1;                 // blocks per wave (pack_f_kernel)
+        const int fb = st.fsq ? 2 : 1;              // blocks per wave (pack_f_kernel)
         dim3 pgrid((unsigned)(((NBLK + fb - 1) / fb + 3) / 4), (unsigned)(Nreg + U), (unsigned)g.GW);
         // ... and, asked to, the f half of the sweep's tally in extra rows of workgroups (about two per CU: four waves each,
         // four edges per wave and round)
@@ -1631,8 +1662,8 @@ int fcd_gibbs_r_step_sq(fcd_ctx *ctx, const double *lM, const double *lMd, const
         tf.f_state = nullptr; tf.C = 0; tf.G = 0; tf.GW = 0; tf.acc = nullptr; tf.cnt_f = nullptr;
         // (only where the f state is small beside the packing's own work: at cfg5 -- 79 800 edges x 16 chain words -- the extra
         // rows cost the launch 66 us for 16 us saved in the tally after the pass: profiles/r03_kernel_stats_cfg5.txt)
-        if (tally_f && g.C * g.GW <= 600000) {
-            tf = *tally_f;
+        if (st.tally_f && g.C * g.GW <= 600000) {
+            tf = *st.tally_f;
             const int64_t per_row = (int64_t)pgrid.x * pgrid.z;
             int64_t want = (g.C + 15) / 16;                       // workgroups of one round
             if (want > 2 * (int64_t)ctx->num_cu) want = 2 * (int64_t)ctx->num_cu;
@@ -1640,44 +1671,40 @@ int fcd_gibbs_r_step_sq(fcd_ctx *ctx, const double *lM, const double *lMd, const
             if (ty < 1) ty = 1;
             if (pgrid.y + ty <= 65535) {
                 pgrid.y += (unsigned)ty;
-                if (tally_f_done) *tally_f_done = true;
+                st.tally_f_done = true;
             } else {
                 tf.f_state = nullptr;
             }
         }
         fcd_prof_begin(ctx, FCD_PROF_PACK, s);
-        if (fsq)
-            hipLaunchKernelGGL(pack_f_kernel<true>, pgrid, dim3(256), 0, s, fsq, (int)Nreg, NBLK, (int)g.C, edge_mode, f_S, r_bits,
-                               (int)U, r_S, pinit, tf);
+        if (st.fsq)
+            hipLaunchKernelGGL(pack_f_kernel<true>, pgrid, dim3(256), 0, s, st.fsq, (int)Nreg, NBLK, (int)g.C, edge_mode, f_S,
+                               c.r_bits, (int)U, r_S, pinit, tf);
         else
-            hipLaunchKernelGGL(pack_f_kernel<false>, pgrid, dim3(256), 0, s, f_state, (int)Nreg, NBLK, (int)g.C, edge_mode, f_S,
-                               r_bits, (int)U, r_S, pinit, tf);
+            hipLaunchKernelGGL(pack_f_kernel<false>, pgrid, dim3(256), 0, s, c.f_state, (int)Nreg, NBLK, (int)g.C, edge_mode, f_S,
+                               c.r_bits, (int)U, r_S, pinit, tf);
         fcd_prof_end(ctx, FCD_PROF_PACK, s);
         FCD_LAUNCH_CHECK();
     }
     ctx->r_form_last = pipe ? 2 : 1;
     if (pipe) {
         a.flags = pinit.marks;
-        if (ub == 4) rc = launch_pipe<4, 4>(ctx, a, shmem, &pipe, true, s);
-        else if (ub == 2) rc = launch_pipe<2, 8>(ctx, a, shmem, &pipe, true, s);
-        else rc = launch_pipe<1, 8>(ctx, a, shmem, &pipe, true, s);
+        rc = with_ub(ub, [&](auto UB, auto WPE) { return launch_pipe<UB, WPE>(ctx, a, shmem, &pipe, true, s); });
         if (rc || pipe) return rc;
         // the runtime refused the cooperative launch (grid not co-resident after all): the step-per-launch form instead
         ctx->r_form_last = 1;
         a.flags = nullptr;
         a.dsplit = 0;
     }
-    // one launch per block step: launch st = D(st-1) workgroups + P(st) workgroups
-    for (int st = 0; st <= NBLK; ++st) {
-        const int rows = st < NBLK ? (int)((Nreg - (int64_t)st * R_NB < R_NB) ? (Nreg - (int64_t)st * R_NB) : R_NB) : 0;
-        a.s = st;
-        a.nD = st >= 1 ? (int)U * a.nWG : 0;
+    // one launch per block step: launch step = D(step - 1) workgroups + P(step) workgroups
+    for (int step = 0; step <= NBLK; ++step) {
+        const int rows = step < NBLK ? (int)((Nreg - (int64_t)step * R_NB < R_NB) ? (Nreg - (int64_t)step * R_NB) : R_NB) : 0;
+        a.s = step;
+        a.nD = step >= 1 ? (int)U * a.nWG : 0;
         a.nP = rows * nUC * a.nWG;
         a.npad = (!ctx->knobs.r_nopad && a.nD > 0 && a.nD <= a.ncu && a.nD + a.nP > a.ncu) ? a.nD : 0;
         if (a.nD + a.nP == 0) continue;
-        if (ub == 4) rc = launch_step<4, 4>(ctx, a, shmem, s, true);
-        else if (ub == 2) rc = launch_step<2, 8>(ctx, a, shmem, s, true);
-        else rc = launch_step<1, 8>(ctx, a, shmem, s, true);
+        rc = with_ub(ub, [&](auto UB, auto WPE) { return launch_step<UB, WPE>(ctx, a, shmem, s, true); });
         if (rc) return rc;
     }
     return FCD_OK;

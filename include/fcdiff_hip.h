@@ -80,8 +80,9 @@ const char *fcd_last_message(const fcd_ctx *ctx);
  * first to avoid that. */
 int fcd_ctx_create(fcd_ctx **out);
 int fcd_ctx_destroy(fcd_ctx *ctx);
-/* Sizes every scratch buffer of the sweep at this shape (f / r pass workspace, square f copy): after it no
- * sampler entry point allocates or synchronises at shapes up to (Nreg, U, G).  Synchronises when it grows something. */
+/* Sizes every scratch buffer of the sweep at this shape (f / r pass workspace, square f copy) from the same plan the
+ * sampler entry points read (shape and knobs): after it none of them allocates or synchronises at shapes up to
+ * (Nreg, U, G) while the knobs stay as they are.  Synchronises when it grows something. */
 int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
 /* Tuning / test knobs (defaults: environment FCD_R_PATH, FCD_R_UB, FCD_R_NOPAD, FCD_R_DSPLIT, FCD_R_COOP, FCD_R_REFILL, FCD_R_TOL, FCD_F_TOL, FCD_F_FORM,
  * FCD_CORR_FORM, read once by fcd_ctx_create; 0 = default everywhere; the two test hooks at the end of the list are NOT read
@@ -277,8 +278,8 @@ int fcd_gibbs_region_tables(fcd_ctx *ctx, const double *lM, int64_t Nreg, int64_
 int fcd_gibbs_r_step(fcd_ctx *ctx, const double *lM, const double *lMd, const double *hyper,
                      const uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
                      int64_t chain0, uint64_t seed, int64_t sweep, int edge_mode, fcd_stream stream);
-/* n_sweeps x (f step, r step), sweeps numbered sweep0, sweep0+1, ...  When counts != NULL the pooled
- * statistics of the LAST sweep are stored there (see fcd_gibbs_stats). */
+/* n_sweeps x (f step, r step), sweeps numbered sweep0, sweep0+1, ...: fcd_gibbs_run's loop without M-step or counters.
+ * When counts != NULL the pooled statistics of the LAST sweep are stored there (fcd_gibbs_stats: this rank's own). */
 int fcd_gibbs_sweeps(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *lMd,
                      const double *hyper, uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0,
                      uint64_t seed, int64_t sweep0, int64_t n_sweeps, int edge_mode, int64_t *counts,

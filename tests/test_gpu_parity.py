@@ -980,6 +980,29 @@ def test_gibbs_cfg3_size_properties(env):
     nptest.assert_allclose(lj[:8], env.CO.gibbs_logjoint(f_g[:8].copy(), r_g[:8].copy(), S_B, lM, lng, lnpi2), rtol=1e-12)
 
 
+@pytest.mark.parametrize("N,H,U,G", [(200, 50, 50, 1024),     # cfg3: the U <= 64 pair kernel of the f pass
+                                     (100, 20, 80, 512)])     # U > 64: the any-U pair kernel
+def test_gibbs_reserve_covers_run_and_sweeps(env, N, H, U, G):
+    """
+    fcd_ctx_reserve (GibbsEngine.__init__) sizes every scratch buffer of the sweep: on a fresh context, run() with M-step,
+    accumulation and counts, then sweeps() with counts, allocate nothing more (no hipMalloc, no synchronisation).
+    """
+    (m, S_B, lM) = tables_for(env, N, H, U, seed=5)
+    fresh = env.lib.Context()
+    eng = env.GibbsEngine(up(env, S_B), up(env, lM), N, U, G, chain0=0, seed=77, ctx=fresh)
+    assert fresh.stat("ws_bytes") > 1 << 20            # (above the workspace's 1 MiB floor, which would hide a shortfall)
+    n_alloc = fresh.stat("n_alloc")
+    eng.set_hyper(m.gamma, m.pi2())
+    eng.init(0.05)
+    counts = eng.run(0, 3, mstep_every=1, accumulate_from=1, want_counts=True).cpu().numpy()
+    assert counts[4] == G
+    counts = eng.sweeps(3, 2, with_counts=True).cpu().numpy()
+    assert counts[4] == G
+    env.torch.cuda.synchronize()
+    assert fresh.stat("n_alloc") == n_alloc
+    fresh.check_device()
+
+
 def test_fit_gibbs_cfg3_shape_end_to_end(env):
     """
     VERDICT r3 item 6b: the path bench.py times -- UnsharedRegionFit(method='gibbs').run() -> run_chains -> fcd_gibbs_run with
