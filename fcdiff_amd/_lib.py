@@ -92,6 +92,9 @@ SIGNATURES = {
     "fcd_gibbs_set_pair_accumulator": (_int, [_p, _p, _i64, _i64, _i64]),
     "fcd_conn_posterior": (_int, [_p, _p, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _p, _p, _p, _p]),
     "fcd_conn_posterior_ex": (_int, [_p, _p, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _int, _p, _p, _p, _p]),
+    "fcd_gibbs_count_tally": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "fcd_gibbs_set_count_accumulator": (_int, [_p, _p, _p, _i64, _i64, _i64]),
+    "fcd_vb_count_posterior": (_int, [_p, _p, _i64, _i64, _p, _p, _p]),
 }
 
 _lib = None

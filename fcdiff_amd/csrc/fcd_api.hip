@@ -138,6 +138,11 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->pair_acc = nullptr;
     ctx->pair_nreg = ctx->pair_u = 0;
     ctx->pair_every = 1;
+    ctx->count_hp = ctx->count_hr = nullptr;
+    ctx->count_nreg = ctx->count_u = 0;
+    ctx->count_every = 1;
+    ctx->count_ws = nullptr;
+    ctx->count_ws_bytes = 0;
     ctx->acc = nullptr;
     ctx->nan_slots = nullptr;
     ctx->dbg = nullptr;
@@ -218,6 +223,7 @@ int fcd_ctx_destroy(fcd_ctx *ctx) {
     if (ctx->log_tab) (void)hipFree(ctx->log_tab);
     if (ctx->dev_err) (void)hipHostFree((void *)ctx->dev_err);
     if (ctx->fsq) (void)hipFree(ctx->fsq);
+    if (ctx->count_ws) (void)hipFree(ctx->count_ws);
     if (ctx->acc) (void)hipFree(ctx->acc);
     if (ctx->nan_slots) (void)hipFree(ctx->nan_slots);
     if (ctx->dbg) (void)hipFree(ctx->dbg);

@@ -68,6 +68,10 @@ struct fcd_ctx {
     size_t fsq_bytes;
     uint32_t *pair_acc;            // (C, U, 3, 3) counts of (f_c, mixture case) fcd_gibbs_run adds to (fcd_gibbs_set_pair_accumulator), or nullptr
     int64_t pair_nreg, pair_u, pair_every;
+    uint32_t *count_hp, *count_hr;  // (U, Nreg+1) / (Nreg, U+1) histograms of the anomalous-region counts fcd_gibbs_run adds to
+    int64_t count_nreg, count_u, count_every;   // (fcd_gibbs_set_count_accumulator), or nullptr
+    void *count_ws;                // per-chain counts of one tally, (U + Nreg) rows of GW*64 uint16 (fcd_count_ws_reserve)
+    size_t count_ws_bytes;
     // optional per-kernel timing with HIP events on the launch stream (fcd_prof_enable / fcd_prof_collect)
     int prof_on;
     hipEvent_t *prof_ev[FCD_PROF_SLOTS];   // pairs (begin, end)
@@ -133,6 +137,11 @@ struct fcd_tally_f {
 struct fcd_geo;
 int fcd_pair_tally_launch(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
                           const fcd_geo &g, uint32_t *acc, hipStream_t s);
+// the anomalous-region count kernels of fcd_count.hip (two launches): both histograms += the counts of this state; the
+// scratch they need is grown by fcd_count_ws_reserve (fcd_gibbs_run: before its sweep loop)
+int fcd_count_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
+int fcd_count_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
+                           uint32_t *hist_patient, uint32_t *hist_region, hipStream_t s);
 // bracket ONE kernel launch with events when profiling is on (no-ops otherwise)
 void fcd_prof_begin(fcd_ctx *ctx, int slot, hipStream_t s);
 void fcd_prof_end(fcd_ctx *ctx, int slot, hipStream_t s);

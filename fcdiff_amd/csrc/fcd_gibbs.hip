@@ -1364,10 +1364,11 @@ extern "C" int fcd_gibbs_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint6
 // 'gibbs'), run_chains and bench.py call) and fcd_gibbs_sweeps.  Per sweep: f pass (1 launch), packing for the r pass (1),
 // r pass (one pipelined launch, or ceil(Nreg/16) + 1 block steps), tally (1) -- the tally also carries the M-step and the
 // slot words of the next f pass.  hyper_m: what the M-step writes (nullptr when mstep_every == 0); pair_acc: add the
-// (f_c, mixture case) counts to the context's pair accumulator.
+// (f_c, mixture case) counts to the context's pair accumulator; count_acc: add the anomalous-region counts to the
+// context's count accumulator.
 static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int64_t n_sweeps, int64_t mstep_every,
                       int64_t accumulate_from, int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r, double *hyper_m,
-                      bool pair_acc) {
+                      bool pair_acc, bool count_acc) {
     if (n_sweeps < 0 || sweep0 < 0 || sweep0 + n_sweeps > (1ll << 32))
         return fcd_fail(ctx, FCD_ERR_ARG, "sweep range [%lld, +%lld) outside the 32-bit counter word", sweep0, n_sweeps);
     const fcd_sweep_plan &pl = c.pl;
@@ -1443,6 +1444,11 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
             rc = fcd_pair_tally_launch(ctx, c.f_state, c.r_bits, Nreg, U, G, g, ctx->pair_acc, s);
             if (rc) return rc;
         }
+        // histograms of sum_n r_nu and sum_u r_nu of the end-of-sweep state (fcd_gibbs_set_count_accumulator): the same
+        if (count_acc && st.sweep >= accumulate_from && (st.sweep - accumulate_from) % ctx->count_every == 0) {
+            rc = fcd_count_tally_launch(ctx, c.r_bits, Nreg, U, G, g, ctx->count_hp, ctx->count_hr, s);
+            if (rc) return rc;
+        }
         st.ru_ready = r_U_next != nullptr;
     }
     return FCD_OK;
@@ -1461,10 +1467,18 @@ extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, 
     if (ctx->pair_acc && (ctx->pair_nreg != Nreg || ctx->pair_u != U))
         return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_run: the attached pair accumulator was made for Nreg=%lld, U=%lld",
                         ctx->pair_nreg, ctx->pair_u);
-    return sweep_loop(ctx, c, sweep0, n_sweeps, mstep_every, accumulate_from, counts, cnt_f, cnt_r, hyper, ctx->pair_acc != nullptr);
+    if (ctx->count_hp && (ctx->count_nreg != Nreg || ctx->count_u != U))
+        return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_run: the attached count accumulator was made for Nreg=%lld, U=%lld",
+                        ctx->count_nreg, ctx->count_u);
+    if (ctx->count_hp) {
+        rc = fcd_count_ws_reserve(ctx, Nreg, U, G);          // (grown here, never inside the sweep loop)
+        if (rc) return rc;
+    }
+    return sweep_loop(ctx, c, sweep0, n_sweeps, mstep_every, accumulate_from, counts, cnt_f, cnt_r, hyper, ctx->pair_acc != nullptr,
+                      ctx->count_hp != nullptr);
 }
 
-// fcd_gibbs_run's loop without M-step, marginal counters or pair counts.  The counts are made by fcd_gibbs_stats after the
+// fcd_gibbs_run's loop without M-step, marginal counters, pair or anomalous-region counts.  The counts are made by fcd_gibbs_stats after the
 // loop: this rank's own, never pooled over an attached communicator.
 extern "C" int fcd_gibbs_sweeps(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *lMd,
                                 const double *hyper,
@@ -1474,7 +1488,7 @@ extern "C" int fcd_gibbs_sweeps(fcd_ctx *ctx, const double *S_B, const double *l
     fcd_sweep_call c = {S_B, lM, lMf, lMd, hyper, f_state, r_bits, Nreg, U, G, chain0, seed, edge_mode, (hipStream_t)stream};
     int rc = fcd_sweep_call_check(ctx, c, true, true, "fcd_gibbs_sweeps");
     if (rc) return rc;
-    rc = sweep_loop(ctx, c, sweep0, n_sweeps, 0, 0, nullptr, nullptr, nullptr, nullptr, false);
+    rc = sweep_loop(ctx, c, sweep0, n_sweeps, 0, 0, nullptr, nullptr, nullptr, nullptr, false, false);
     if (rc) return rc;
     if (counts && n_sweeps > 0) return fcd_gibbs_stats(ctx, f_state, r_bits, Nreg, U, G, counts, stream);
     return FCD_OK;

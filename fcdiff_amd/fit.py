@@ -16,6 +16,8 @@ New knobs (all optional; defaults reproduce the reference):
     n_chains, n_sweeps, burn_in, mstep_every, mstep_lag, seed, chain0     sampler controls
     update_theta_sub, theta_sub_every                          (eta, epsilon) step: vb every iteration / gibbs every K sweeps
     connection_marginals, connection_every                     gibbs: count (f_c, mixture case) for connection_posterior()
+    anomaly_counts, anomaly_counts_every                       gibbs: histograms of the anomalous-region counts for
+                                                               anomaly_count_posterior()
     missing_data                                               True: NaN entries of b / bt are unobserved and integrated out
 
 Differences from the reference that are deliberate and documented:
@@ -32,7 +34,7 @@ import numpy as np
 
 from . import _lib
 from . import util
-from .gibbs import GibbsEngine, run_chains, allreduce_counts, pair_sweeps_in, PAIR_COUNT_MAX
+from .gibbs import GibbsEngine, run_chains, allreduce_counts, pair_sweeps_in, PAIR_COUNT_MAX, COUNT_MAX_NREG, COUNT_MAX_U
 
 
 class UnsharedRegionFit(object):
@@ -78,6 +80,11 @@ class UnsharedRegionFit(object):
         self.connection_every = 1           # ... at every this many sweeps from burn_in on
         self.connection_counts = None       # (C, U, 3, 3) int64: those counts, pooled over chains, sweeps and ranks
         self.connection_sweeps = 0          # number of sweeps behind connection_counts (each counts every chain once)
+        self.anomaly_counts = False         # gibbs: histograms of sum_n r_nu and sum_u r_nu for anomaly_count_posterior()
+        self.anomaly_counts_every = 1       # ... at every this many sweeps from burn_in on
+        self.patient_count_hist = None      # (U, Nreg+1) int64: chains x sweeps (x ranks) with sum_n r_nu = k
+        self.region_count_hist = None       # (Nreg, U+1) int64: chains x sweeps (x ranks) with sum_u r_nu = k
+        self.anomaly_count_sweeps = 0       # number of sweeps behind those histograms
         # True: every NaN of b / bt is an unobserved value, integrated out exactly (S_B sums the observed h only, lM = 0 at a
         # missing bt); False: NaN is read as a number, as the reference reads it.  Only NaN is missing, not +-inf.
         self.missing_data = False
@@ -538,10 +545,25 @@ class UnsharedRegionFit(object):
             if n_acc * int(self.n_chains) > PAIR_COUNT_MAX:
                 raise ValueError("connection counts would overflow uint32: %d chains x %d accumulated sweeps; raise "
                                  "connection_every" % (self.n_chains, n_acc))
+        self.patient_count_hist = self.region_count_hist = None
+        self.anomaly_count_sweeps = 0
+        if self.anomaly_counts:
+            every = int(self.anomaly_counts_every)
+            if every < 1 or every != self.anomaly_counts_every:
+                raise ValueError("anomaly_counts_every must be an integer >= 1")
+            n_acc = pair_sweeps_in(0, int(self.n_sweeps), int(self.burn_in), every)
+            if n_acc * int(self.n_chains) > PAIR_COUNT_MAX:
+                raise ValueError("anomaly-count histograms would overflow uint32: %d chains x %d accumulated sweeps; raise "
+                                 "anomaly_counts_every" % (self.n_chains, n_acc))
+            if N > COUNT_MAX_NREG or U > COUNT_MAX_U:
+                raise ValueError("anomaly-count histograms are made for at most %d regions and %d patients (here %d, %d)"
+                                 % (COUNT_MAX_NREG, COUNT_MAX_U, N, U))
         eng = GibbsEngine(self._d["S_B"], self._d["lM"], N, U, self.n_chains, chain0=self.chain0, seed=self.seed,
                           edge_index=self._edge_mode(), ctx=self._context())
         if self.connection_marginals:
             eng.attach_pair_accumulator(self.connection_every)
+        if self.anomaly_counts:
+            eng.attach_count_accumulator(self.anomaly_counts_every)
         pi2 = self._pi2()
         eng.set_hyper(np.asarray(self.model.gamma, dtype=np.float64), pi2)
         eng.init(float(pi2[1]))
@@ -598,6 +620,11 @@ class UnsharedRegionFit(object):
             pc = allreduce_counts(eng.pair_acc.to(t.int64) & 0xFFFFFFFF)
             self.connection_counts = pc.cpu().numpy()
             self.connection_sweeps = eng.pair_sweeps
+        if eng.count_hist is not None:
+            (hp, hr) = (allreduce_counts(h.to(t.int64) & 0xFFFFFFFF) for h in eng.count_hist)
+            self.patient_count_hist = hp.cpu().numpy()
+            self.region_count_hist = hr.cpu().numpy()
+            self.anomaly_count_sweeps = eng.count_sweeps
         (gamma, pi) = eng.hyper_values()
         self.model.gamma = gamma
         self.model.pi = pi
@@ -646,6 +673,43 @@ class UnsharedRegionFit(object):
         return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), lq_F=self._d["lq_F"],
                               lq_R=self._d["lq_R"], missing_data=self.missing_data)
 
+    # ------------------------------------------------------------------ anomalous-region counts
+    def anomaly_count_posterior(self):
+        """
+        Posterior law of how many regions of each patient are anomalous and in how many patients each region is, from the
+        last run(), as a dict of NumPy float64 arrays:
+            p_patient_count  (U, Nreg+1)  P(sum_n r_nu = k | data)
+            p_region_count   (Nreg, U+1)  P(sum_u r_nu = k | data)
+            p_patient_any    (U,)         P(patient u has an anomalous region) = 1 - p_patient_count[:, 0]
+            p_region_any     (Nreg,)      P(region n is anomalous in some patient) = 1 - p_region_count[:, 0]
+        The sites are coupled (inside a patient through the mixture cases of the edges, across patients through f), so
+        these are laws of the joint, not products of the marginals of _lq_R:
+          method='vb'     the mean-field law: under q_R the sites are independent and each count is Poisson-binomial
+                          (computed on demand from _lq_R);
+          method='gibbs'  the histograms over chains and the sweeps from burn_in on, every `anomaly_counts_every`-th.
+                          Needs `anomaly_counts = True` before run(); raises ValueError otherwise.  The histograms are
+                          kept as `patient_count_hist` / `region_count_hist`, the number of sweeps behind them as
+                          `anomaly_count_sweeps`.
+        """
+        if self.model is None or self.bt is None:
+            raise ValueError("anomaly_count_posterior() needs a model and bt: call run() first")
+        if self.method == "gibbs":
+            (hp, hr) = (self.patient_count_hist, self.region_count_hist)
+            if hp is None or hr is None:
+                raise ValueError("no anomaly-count histograms: set anomaly_counts = True before run(method='gibbs')")
+            (hp, hr) = (np.asarray(hp, dtype=np.float64), np.asarray(hr, dtype=np.float64))
+            if hp.sum() == 0 or hr.sum() == 0:
+                raise ValueError("no sweep was accumulated into the anomaly-count histograms (n_sweeps <= burn_in?)")
+            p_patient = hp / hp.sum(axis=1, keepdims=True)
+            p_region = hr / hr.sum(axis=1, keepdims=True)
+        elif self.method == "vb":
+            (N, _C, U) = self._check_state(need=("lq_R",))
+            (p_patient, p_region) = count_posterior(self._context(), self._d["lq_R"], N, U)
+        else:
+            raise ValueError("method must be 'vb' or 'gibbs'")
+        return {"p_patient_count": p_patient, "p_region_count": p_region,
+                "p_patient_any": 1.0 - p_patient[:, 0], "p_region_any": 1.0 - p_region[:, 0]}
+
     def _bt_dev(self, C, U):
         bt = self._d.get("bt")
         if bt is None or tuple(bt.shape) != (C, U):
@@ -653,6 +717,22 @@ class UnsharedRegionFit(object):
             if tuple(bt.shape) != (C, U):
                 raise ValueError("bt has shape %s, the fit's state needs %s" % (tuple(bt.shape), (C, U)))
         return bt
+
+
+def count_posterior(ctx, lq_R, Nreg, U):
+    """
+    (p_patient (U, Nreg+1), p_region (Nreg, U+1)) as NumPy float64 through fcd_vb_count_posterior: the Poisson-binomial
+    laws of sum_n r_nu and sum_u r_nu with q_nu = P(r_nu = 1) from lq_R (Nreg, U, 2) float64 (need not be normalised).
+    """
+    import torch
+    if tuple(lq_R.shape) != (Nreg, U, 2) or lq_R.dtype != torch.float64:
+        raise ValueError("lq_R must be float64 (Nreg, U, 2) = %s" % ((Nreg, U, 2),))
+    dev = lq_R.device
+    p_patient = torch.empty((U, Nreg + 1), dtype=torch.float64, device=dev)
+    p_region = torch.empty((Nreg, U + 1), dtype=torch.float64, device=dev)
+    ctx.call("fcd_vb_count_posterior", _lib.dptr(lq_R.contiguous()), int(Nreg), int(U), _lib.dptr(p_patient),
+             _lib.dptr(p_region), _lib.stream_ptr())
+    return p_patient.cpu().numpy(), p_region.cpu().numpy()
 
 
 def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=None, missing_data=False):

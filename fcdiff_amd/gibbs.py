@@ -19,6 +19,7 @@ from . import util
 
 
 PAIR_COUNT_MAX = (1 << 32) - 1
+COUNT_MAX_NREG, COUNT_MAX_U = 1023, 512      # largest shape of the anomalous-region histograms (fcd_gibbs_count_tally)
 
 
 def pair_sweeps_in(sweep0, n_sweeps, accumulate_from, every):
@@ -90,6 +91,9 @@ class GibbsEngine(object):
         self.pair_acc = None        # (C, U, 3, 3) counts of (f_c, mixture case) that run() adds to (attach_pair_accumulator)
         self.pair_every = 1
         self.pair_sweeps = 0        # sweeps added to pair_acc so far
+        self.count_hist = None      # (hist_patient (U, Nreg+1), hist_region (Nreg, U+1)) that run() adds to (attach_count_accumulator)
+        self.count_every = 1
+        self.count_sweeps = 0       # sweeps added to count_hist so far
         self.ctx.call("fcd_ctx_reserve", self.Nreg, self.U, self.G)
         self.lMd = self.lMf = None
         if region_major:
@@ -173,23 +177,39 @@ class GibbsEngine(object):
         every `mstep_every` sweeps (0: never -- several ranks all-reduce the returned counts and call mstep()), and
         packs the r words of the next f pass.  Returns the counts tensor of the last sweep (or None).
         With a pair accumulator attached (attach_pair_accumulator) the same call also adds the (f_c, mixture case) counts
-        of every `pair_every`-th sweep from `accumulate_from` on; a call that could overflow them raises ValueError.
+        of every `pair_every`-th sweep from `accumulate_from` on, and with a count accumulator attached
+        (attach_count_accumulator) the histograms of the anomalous-region counts of every `count_every`-th sweep; a call
+        that could overflow either raises ValueError.
         """
         acc = accumulate_from is not None
-        n_pair = 0
-        if self.pair_acc is not None and acc:
+        pair = self.pair_acc is not None and acc
+        count = self.count_hist is not None and acc
+        (n_pair, n_count) = (0, 0)
+        if pair:
             n_pair = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), self.pair_every)
             if (self.pair_sweeps + n_pair) * self.G > PAIR_COUNT_MAX:
                 raise ValueError("the pair accumulator would overflow uint32: %d chains x %d accumulated sweeps > %d"
                                  % (self.G, self.pair_sweeps + n_pair, PAIR_COUNT_MAX))
-            self.ctx.call("fcd_gibbs_set_pair_accumulator", _lib.dptr(self.pair_acc), self.Nreg, self.U, self.pair_every)
+        if count:
+            n_count = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), self.count_every)
+            if (self.count_sweeps + n_count) * self.G > PAIR_COUNT_MAX:
+                raise ValueError("the count accumulator would overflow uint32: %d chains x %d accumulated sweeps > %d"
+                                 % (self.G, self.count_sweeps + n_count, PAIR_COUNT_MAX))
+        # (attached for this call only: the context is shared, no other engine's sweeps may add to these buffers)
         try:
+            if pair:
+                self.ctx.call("fcd_gibbs_set_pair_accumulator", _lib.dptr(self.pair_acc), self.Nreg, self.U, self.pair_every)
+            if count:
+                self.ctx.call("fcd_gibbs_set_count_accumulator", _lib.dptr(self.count_hist[0]), _lib.dptr(self.count_hist[1]),
+                              self.Nreg, self.U, self.count_every)
             self._run(sweep0, n_sweeps, mstep_every, accumulate_from, want_counts)
         finally:
-            if self.pair_acc is not None and acc:
-                # (attached for this call only: the context is shared, no other engine's sweeps may add to this buffer)
+            if pair:
                 self.ctx.call("fcd_gibbs_set_pair_accumulator", None, 0, 0, 1)
+            if count:
+                self.ctx.call("fcd_gibbs_set_count_accumulator", None, None, 0, 0, 1)
         self.pair_sweeps += n_pair
+        self.count_sweeps += n_count
         if acc:
             self.n_accumulated += max(0, int(sweep0) + int(n_sweeps) - max(int(accumulate_from), int(sweep0)))
         return self.counts if want_counts else None
@@ -233,6 +253,45 @@ class GibbsEngine(object):
         self.ctx.call("fcd_gibbs_pair_tally", _lib.dptr(self.f_state), _lib.dptr(self.r_bits), self.Nreg, self.U, self.G,
                       _lib.dptr(acc), _lib.stream_ptr())
         return acc
+
+    # ---- histograms of the anomalous-region counts ----
+    def attach_count_accumulator(self, every=1):
+        """
+        From now on run() adds the end-of-sweep histograms of sum_n r_nu (hist_patient (U, Nreg+1)) and sum_u r_nu
+        (hist_region (Nreg, U+1)) over chains to `count_hist`, at every `every`-th sweep from its `accumulate_from` on
+        (none when accumulate_from is None).  Zeroes the histograms.
+        """
+        every = int(every)
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        t = self.torch
+        dev = self.f_state.device
+        # (uint32 on the device, held in int32 tensors like pair_acc; count_hist_host() reads them back as uint32)
+        self.count_hist = (t.zeros((self.U, self.Nreg + 1), dtype=t.int32, device=dev),
+                           t.zeros((self.Nreg, self.U + 1), dtype=t.int32, device=dev))
+        self.count_every = every
+        self.count_sweeps = 0
+        return self.count_hist
+
+    def detach_count_accumulator(self):
+        self.count_hist = None
+        self.count_sweeps = 0
+
+    def count_hist_host(self):
+        """The attached histograms as NumPy uint32 arrays (hist_patient (U, Nreg+1), hist_region (Nreg, U+1))."""
+        if self.count_hist is None:
+            raise ValueError("no count accumulator is attached")
+        return tuple(self.host(h).view(np.uint32) for h in self.count_hist)
+
+    def count_tally(self, hist_patient, hist_region):
+        """hist_patient (U, Nreg+1), hist_region (Nreg, U+1) uint32-in-int32 tensors += the histograms of the current state."""
+        if (tuple(hist_patient.shape) != (self.U, self.Nreg + 1) or tuple(hist_region.shape) != (self.Nreg, self.U + 1)
+                or hist_patient.element_size() != 4 or hist_region.element_size() != 4
+                or not hist_patient.is_contiguous() or not hist_region.is_contiguous()):
+            raise ValueError("histograms must be contiguous 32-bit (U, Nreg+1) and (Nreg, U+1)")
+        self.ctx.call("fcd_gibbs_count_tally", _lib.dptr(self.r_bits), self.Nreg, self.U, self.G, _lib.dptr(hist_patient),
+                      _lib.dptr(hist_region), _lib.stream_ptr())
+        return hist_patient, hist_region
 
     # ---- pooled statistics / M-step ----
     def stats(self):

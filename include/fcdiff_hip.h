@@ -343,6 +343,27 @@ int fcd_conn_posterior(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, 
 int fcd_conn_posterior_ex(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, const double *theta12_host,
                           const uint32_t *counts, const double *lq_F, const double *lq_R, int flags, double *p_T,
                           double *p_F_tilde, double *p_changed, fcd_stream stream);
+/* ---- anomalous-region counts (how many regions of a patient, in how many patients a region) ---------------------
+ * The law of sum_n r_nu and of sum_u r_nu depends on the joint law of the sites, not on their marginals.
+ *
+ * Histograms over chains of one state: hist_patient (U, Nreg+1) uint32, hist_patient[u][k] += #{chains with
+ * sum_n r_nu = k}; hist_region (Nreg, U+1) uint32, hist_region[n][k] += #{chains with sum_u r_nu = k}.  Both from one
+ * read of r_bits.  Nreg <= 1023 and U <= 512, else FCD_ERR_UNSUPPORTED. */
+int fcd_gibbs_count_tally(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, uint32_t *hist_patient,
+                          uint32_t *hist_region, fcd_stream stream);
+/* Attach both histograms for shape (Nreg, U) to the context (no device work; both NULL detaches), with the semantics of
+ * fcd_gibbs_set_pair_accumulator: every sweep s of fcd_gibbs_run with s >= accumulate_from and
+ * (s - accumulate_from) % every == 0 adds its end-of-sweep state (two extra launches after the sweep's tally, after the
+ * pair accumulator's when both are attached; fcd_gibbs_run grows the context's scratch for them before its loop).
+ * fcd_gibbs_run refuses another shape while they are attached.  The caller keeps sweeps x G below 2^32. */
+int fcd_gibbs_set_count_accumulator(fcd_ctx *ctx, uint32_t *hist_patient, uint32_t *hist_region, int64_t Nreg, int64_t U,
+                                    int64_t every);
+/* The mean-field law of the same counts under q_R (sites independent: Poisson-binomial), fp64:
+ * p_patient (U, Nreg+1), p_patient[u][k] = P(sum_n r_nu = k); p_region (Nreg, U+1), p_region[n][k] = P(sum_u r_nu = k).
+ * q_nu = P(r_nu = 1) from lq_R (Nreg, U, 2), normalised in log space (lq_R need not be normalised).  Exact convolution
+ * recursion; q = 0 and q = 1 give exact point masses.  Nreg, U <= 4095, else FCD_ERR_UNSUPPORTED. */
+int fcd_vb_count_posterior(fcd_ctx *ctx, const double *lq_R, int64_t Nreg, int64_t U, double *p_patient, double *p_region,
+                           fcd_stream stream);
 /* log p(f, r, b, bt; theta) of each chain = minus the first four terms of fit.py:149-152 at one-hot q.
  * out (G,) doubles. */
 int fcd_gibbs_logjoint(fcd_ctx *ctx, const double *S_B, const double *lM, const double *hyper,
