@@ -34,6 +34,7 @@ import numpy as np
 
 from . import _lib
 from . import util
+from . import score as _score
 from .gibbs import GibbsEngine, run_chains, allreduce_counts, pair_sweeps_in, PAIR_COUNT_MAX, COUNT_MAX_NREG, COUNT_MAX_U
 
 
@@ -90,6 +91,7 @@ class UnsharedRegionFit(object):
         self.missing_data = False
 
         self._ctx = None
+        self._score_ctx = None    # score(): a context of its own, so that scoring never touches the fit's workspace or plan
         self._d = {}              # device tensors: lq_R, lq_F, S_B, lM, lpB, pBt, hyper, b, bt
         self._hyper_key = None
 
@@ -709,6 +711,81 @@ class UnsharedRegionFit(object):
             raise ValueError("method must be 'vb' or 'gibbs'")
         return {"p_patient_count": p_patient, "p_region_count": p_region,
                 "p_patient_any": 1.0 - p_patient[:, 0], "p_region_any": 1.0 - p_region[:, 0]}
+
+    # ------------------------------------------------------------------ scoring new patients
+    def score(self, bt_new, *, connections=False, max_iters=100, tol=1e-8, n_anneal=200, n_sweeps=50, seed=None):
+        """
+        Scores patients who were not in the fit: their anomaly maps and a per-patient likelihood measure, with the fitted
+        template and theta held fixed.  Scoring is NOT a refit: the new patients never update the template F, q_F, the
+        sampler's chains or theta, and score() leaves the fit exactly as it was (model, _lq_R, _lq_F, energy, the device
+        tables, `sampler` and its state).  Call it after run().
+
+        bt_new (C, U') correlations of the new patients in the fit's edge order (NaN = unobserved when missing_data).
+        theta is the model's CURRENT parameters, the plug-in convention of connection_posterior().  Given F and theta the
+        patients are independent (doc/methods.rst): with method='vb' a new patient's numbers are exactly those it gets when
+        scored alone; with method='gibbs' they have the same law (the random numbers of a site follow its column index).
+          method='vb'     q_F and theta held; each new patient's q_R is iterated from uniform (as _init_lps) with the fit's
+                          edge ids and taken at the first iteration where its own max_n |delta q_nu| < tol, or at
+                          max_iters (`iters` (U',) per patient; `converged` (U',) False where max_iters was reached first);
+                          elbo[u] = E_lM[u] + E_lp_R[u] - E_lq_R[u], a lower bound on E_{q_F} log p(bt_u | F).
+          method='gibbs'  each chain's template draw f_g (the end state of the fit's sampler, G = its chains) held.
+                          Annealed importance sampling over r from the prior (beta = 0) to p(r | f_g, bt) in n_anneal steps
+                          (schedule: score.ais_schedule) estimates p(bt_u | f_g) per chain: log_pred[u] = log mean_g of it,
+                          unbiased on the exp scale for the mean over the chains' f; log_pred_se (delta method) and ess
+                          (sum w)^2 / sum w^2 of the weights.  Then n_sweeps r-only sweeps at beta = 1 (each samples
+                          p(r | f_g, bt) exactly, chains equally weighted) give p_R, the count law and, with connections,
+                          the connection posteriors.  Needs edge_index 'symmetric'.  A sharded fit scores each rank's own
+                          chains and pools the counts and the AIS sums over ranks.  seed: key of the scoring sampler's random
+                          numbers (None: derived from the fit's seed; never the fit's own numbers -- see score.SCORE_SWEEP0).
+        Returns a dict of NumPy float64 arrays:
+            p_R (Nreg, U') P(r_nu = 1);  p_patient_count (U', Nreg+1);  p_patient_any (U',)
+            connections=True:  p_T (C, U'), p_F_tilde (C, U', 3), p_changed (C, U') of the new patients
+            vb:     elbo (U',), iters (U',) int64, converged (U',) bool
+            gibbs:  log_pred, log_pred_se, ess (U',); with connections also connection_counts (C, U', 3, 3) int64, the
+                    counts of (f_c, mixture case) over chains and sweeps behind the connection posteriors
+        Raises ValueError before run(), for another C, for gibbs with edge_index other than 'symmetric', beyond the
+        count-histogram limits and where the tallies could overflow.
+        """
+        if self.method not in ("vb", "gibbs"):
+            raise ValueError("method must be 'vb' or 'gibbs'")
+        fitted = (self.sampler is not None) if self.method == "gibbs" else (self._d.get("lq_F") is not None and bool(self.energy))
+        if self.model is None or not fitted:
+            raise ValueError("score() needs a fitted model: call run() first")
+        bt_new = np.ascontiguousarray(bt_new, dtype=np.float64)
+        if bt_new.ndim != 2:
+            raise ValueError("bt_new must be (C, U'), got shape %s" % (bt_new.shape,))
+        (C, U) = bt_new.shape
+        C_fit = int(self._d["lq_F"].shape[0]) if self.method == "vb" else int(self.sampler.C)
+        if C != C_fit:
+            raise ValueError("bt_new has %d connections, the fit has %d" % (C, C_fit))
+        N = int(util.C_to_N(C))
+        if U < 1 or U > COUNT_MAX_U:
+            raise ValueError("score() takes 1 to %d patients at a time (count-histogram limit), got %d" % (COUNT_MAX_U, U))
+        if N > COUNT_MAX_NREG:
+            raise ValueError("score() is made for at most %d regions (count-histogram limit), here %d" % (COUNT_MAX_NREG, N))
+        if self.method == "gibbs":
+            if self._edge_mode() != "symmetric":
+                raise ValueError("score() with method 'gibbs' needs edge_index 'symmetric'")
+            if int(n_anneal) < 1 or int(n_sweeps) < 1:
+                raise ValueError("n_anneal and n_sweeps must be >= 1")
+            if int(n_sweeps) * int(self.sampler.G) > PAIR_COUNT_MAX:
+                raise ValueError("score() tallies would overflow uint32: %d chains x %d sweeps" % (self.sampler.G, n_sweeps))
+        elif int(max_iters) < 1:
+            raise ValueError("max_iters must be >= 1")
+        if self._score_ctx is None:
+            self._score_ctx = _lib.Context()
+        ctx = self._score_ctx
+        b_dev = self._d.get("b")
+        if b_dev is None or tuple(b_dev.shape)[0] != C:
+            b_dev = self._up(self.b)
+        bt_dev = self._up(bt_new)
+        if self.method == "vb":
+            return _score.score_vb(ctx, b_dev, bt_dev, N, self._d["lq_F"], self.model, self._pi2(), self._edge_mode(),
+                                   self.missing_data, connections, max_iters, float(tol))
+        key = _score.score_key(self.seed if seed is None else seed)
+        out = _score.score_gibbs(ctx, b_dev, bt_dev, N, self.sampler, self.model, self._pi2(), self.missing_data, connections,
+                                 int(n_anneal), int(n_sweeps), key)
+        return out
 
     def _bt_dev(self, C, U):
         bt = self._d.get("bt")

@@ -364,6 +364,31 @@ int fcd_gibbs_set_count_accumulator(fcd_ctx *ctx, uint32_t *hist_patient, uint32
  * recursion; q = 0 and q = 1 give exact point masses.  Nreg, U <= 4095, else FCD_ERR_UNSUPPORTED. */
 int fcd_vb_count_posterior(fcd_ctx *ctx, const double *lq_R, int64_t Nreg, int64_t U, double *p_patient, double *p_region,
                            fcd_stream stream);
+/* ---- scoring new patients against a fitted model (UnsharedRegionFit.score) -------------------------------------------
+ * Given F and theta the patients are independent, so a new patient is scored with the fit's template held: the fit itself
+ * is never changed.
+ *
+ * Per-patient split of the variational energy terms that involve patients, for lq_F (C, 1, 3), lq_R (Nreg, U, 2) and the
+ * patients' table lM (C, U, 3, 3):  out4 (U, 4) = {E_lM[u], E_lp_R[u], E_lq_R[u], elbo[u] = E_lM + E_lp_R - E_lq_R}, with
+ *   E_lM[u] = sum_c sum_k q_F[c,k] sum_l w_l(c,u) lM[c,u,k,l]  (true endpoints of c, as in fcd_vb_energy's E_lM term),
+ * E_lp_R / E_lq_R the terms of fit.py:486 / :539 restricted to patient u.  elbo[u] is a lower bound on
+ * E_{q_F} log p(bt_u | F).  Sums over u are fcd_vb_energy's terms 3, 2 and 5.  fp64, bitwise repeatable, and patient u's
+ * numbers do not depend on the other patients of the call.  Uses the context's workspace. */
+int fcd_vb_patient_elbo(fcd_ctx *ctx, const double *lq_F, const double *lq_R, const double *lM, const double *hyper,
+                        int64_t Nreg, int64_t U, double *out4, fcd_stream stream);
+/* One step of annealed importance sampling over r with the chains' f held (symmetric edge ids: the true endpoints of c):
+ *   l_gu = sum_c lM[c, u, f_gc, l(r_gnu, r_gmu)]  at the current state (mixture case l as in fcd_gibbs_logjoint),
+ *   w[g, u] += (beta - beta_prev) l_gu            w (G, U) fp64, device,
+ *   lM_beta = beta * lM                           (C, U, 3, 3), the working table the next fcd_gibbs_region_tables and
+ *                                                 fcd_gibbs_r_step read (NULL: not written; must not alias lM or w).
+ * Started from r drawn from the prior (beta = 0) and followed, at every beta_t of a ladder ending at 1, by one r pass on
+ * the beta_t table, exp(w[g, u]) is an unbiased estimate of p(bt_u | f_g).  Two launches; uses the context's workspace. */
+int fcd_score_ais_step(fcd_ctx *ctx, const double *lM, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U,
+                       int64_t G, double beta_prev, double beta, double *w, double *lM_beta, fcd_stream stream);
+/* The per-patient fold of the AIS weights w (G, U): out4 (U, 4) = {m = max_g w[g,u], sum_g exp(w - m), sum_g exp(2 (w - m)),
+ * G} (sums 0 when m = -inf), the numbers that pool over ranks into log-mean-exp, its standard error and the effective
+ * sample size.  Chains in a fixed order: bitwise repeatable. */
+int fcd_score_ais_finish(fcd_ctx *ctx, const double *w, int64_t U, int64_t G, double *out4, fcd_stream stream);
 /* log p(f, r, b, bt; theta) of each chain = minus the first four terms of fit.py:149-152 at one-hot q.
  * out (G,) doubles. */
 int fcd_gibbs_logjoint(fcd_ctx *ctx, const double *S_B, const double *lM, const double *hyper,
