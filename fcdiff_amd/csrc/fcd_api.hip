@@ -171,10 +171,12 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->knobs.r_tol = knob_env("FCD_R_TOL");
     ctx->knobs.f_tol = knob_env("FCD_F_TOL");
     ctx->knobs.f_form = (int)knob_env("FCD_F_FORM");
+    ctx->knobs.f_pack = (int)knob_env("FCD_F_PACK");
     ctx->knobs.corr_form = (int)knob_env("FCD_CORR_FORM");
     ctx->knobs.r_poll_limit = 0;        // test hooks: through fcd_ctx_set_knob only, never from the environment
     ctx->knobs.r_withhold = 0;
     ctx->r_form_last = 0;
+    ctx->n_pack = 0;
     int rc = fcd_ws_reserve(ctx, 1u << 20);
     if (rc == FCD_OK) {
         void *pin = nullptr;
@@ -262,6 +264,7 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value) {
     else if (!strcmp(name, "r_tol")) k.r_tol = value;
     else if (!strcmp(name, "f_tol")) k.f_tol = value;
     else if (!strcmp(name, "f_form")) k.f_form = (int)value;
+    else if (!strcmp(name, "f_pack")) k.f_pack = (int)value;
     else if (!strcmp(name, "corr_form")) k.corr_form = (int)value;
     else if (!strcmp(name, "r_poll_limit")) k.r_poll_limit = (int)value;
     else if (!strcmp(name, "r_withhold")) k.r_withhold = (int)value;
@@ -293,6 +296,7 @@ int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out) {
     else if (!strcmp(name, "ws_bytes")) *out = (int64_t)ctx->ws_bytes;
     else if (!strcmp(name, "fsq_bytes")) *out = (int64_t)ctx->fsq_bytes;
     else if (!strcmp(name, "r_form_last")) *out = ctx->r_form_last;
+    else if (!strcmp(name, "pack_launches")) *out = ctx->n_pack;
     else if (!strcmp(name, "comm_world")) *out = ctx->comm ? ctx->comm_world : 0;
     else if (!strcmp(name, "dev_err")) *out = ctx->dev_err ? (int64_t)*ctx->dev_err : 0;
     else if (!strcmp(name, "f_repeats") || !strcmp(name, "r_exact_rows")) {

@@ -32,11 +32,12 @@ struct fcd_knobs {
     int r_withhold;    // TEST HOOK: 1 = the in-order role of the pipelined r pass never sets its marks (a panel wave then gives up)
     int corr_form;     // 1: K_corr in 64 x 64 blocks with a moments pass also where the one-workgroup-per-subject kernel would run
     int f_form;        // 0: automatic; 2: the any-U pair kernel also where the U <= 64 one would run; 3: scalar-mask form
+    int f_pack;        // 1: the r pass's packing launch in every sweep (default: only where the f pass cannot write the packed f words)
 };
 
 // kernels whose dynamic-LDS limit is raised with hipFuncSetAttribute: done once per (kernel, size) and remembered here
-enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA_F_PAIR_BIG = FCD_KA_F_PAIR + 4,
-       FCD_KA_R_STEP = FCD_KA_F_PAIR_BIG + 4, FCD_KA_R_PIPE = FCD_KA_R_STEP + 4, FCD_KA_CORR = FCD_KA_R_PIPE + 4, FCD_KA_N = FCD_KA_CORR + 1 };
+enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA_F_PAIR_T = FCD_KA_F_PAIR + 4,
+       FCD_KA_F_PAIR_BIG = FCD_KA_F_PAIR_T + 4, FCD_KA_R_STEP = FCD_KA_F_PAIR_BIG + 4, FCD_KA_R_PIPE = FCD_KA_R_STEP + 4, FCD_KA_CORR = FCD_KA_R_PIPE + 4, FCD_KA_N = FCD_KA_CORR + 1 };
 
 #define FCD_NAN_SLOTS 256
 
@@ -52,6 +53,7 @@ struct fcd_ctx {
     size_t pipe_occ_shmem[3];      // ... for this much dynamic LDS
     int pipe_occ_threads[3];       // ... and this many threads
     int r_form_last;               // form of the last blocked r pass: 1 step-per-launch, 2 pipelined, 3 one-launch with counters (fcd_ctx_stat)
+    long long n_pack;              // packing launches of the r pass so far (fcd_ctx_stat "pack_launches")
     void *log_tab;     // K_lik tables (fcd_fastmath.h): 64 x 2^(-j/64), 512 x {1/m_i, log m_i} (device, 8.5 KiB)
     volatile unsigned *dev_err;   // pinned host word: error word of the one-launch r pass, copied back after each pass
     void *acc;         // 8 x uint64, zero between launches: the tally's pooled sums [0..3] and its ticket [4]
@@ -315,6 +317,38 @@ __host__ __device__ static inline uint64_t fcd_active_mask(int w, int64_t G) {
 }
 
 #ifdef __HIPCC__
+constexpr int R_NB = 16;   // regions per diagonal block of the blocked r pass (even: both halves of a Philox block stay inside)
+// 8 two-bit fields of x -> the low two bits of 8 bytes (x: fields 0-3, y: fields 4-7)
+__device__ __forceinline__ uint2 spread2(uint32_t x16) {
+    uint32_t lo = x16 & 0xFFu, hi = (x16 >> 8) & 0xFFu;
+    lo = (lo | (lo << 12)) & 0x000F000Fu;
+    hi = (hi | (hi << 12)) & 0x000F000Fu;
+    lo = (lo | (lo << 6)) & 0x03030303u;
+    hi = (hi | (hi << 6)) & 0x03030303u;
+    return make_uint2(lo, hi);
+}
+// the r word of (w, u, b) the blocked r pass reads (r_S, fcd_gibbs_r.hip): bit j = r_{16 b + j, u} of this lane's chain,
+// one byte per pair of regions
+// (the whole wave, (w, u, b) wave-uniform: lane l loads the word of region 16 b + l % 16 -- ONE memory instruction instead of 16 --
+// and every lane takes its bit of each word from the lane that holds it)
+__device__ __forceinline__ uint64_t fcd_lane_word(uint64_t v, int j) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint2 fcd_r_pair_bytes(const uint64_t *__restrict__ r_bits, int Nreg, int U, int w, int u, int b,
+                                                  int lane) {
+    const int ml = b * R_NB + (lane & (R_NB - 1));
+    const uint64_t mine = r_bits[((int64_t)w * Nreg + (ml < Nreg ? ml : Nreg - 1)) * U + u];    // clamped: no branch around the load
+    uint32_t v = 0;
+#pragma unroll
+    for (int j = 0; j < R_NB; ++j) {
+        const int m = b * R_NB + j;
+        v |= (m < Nreg ? (uint32_t)((fcd_lane_word(mine, j) >> lane) & 1ull) : 0u) << j;
+    }
+    return spread2(v);
+}
+
 // The f half of the tally for workgroup lin of nblk (WAVES waves each): f_state is read once, 16 bytes per lane -- a wave
 // covers the 16 chain words x 64 chains of an edge with one load instruction; four edges per round, their loads issued
 // together (the pass is a few memory round trips long: what counts is the number of bytes in flight).  red: LDS,
@@ -455,6 +489,8 @@ int fcd_sweep_call_check(fcd_ctx *ctx, fcd_sweep_call &c, bool f_pass, bool r_pa
 struct fcd_sweep_step {
     int64_t sweep;
     uint8_t *fsq;                  // square copy of the f state, or nullptr
+    bool f_packed;                 // f pass: write the r pass's f words (f_S) in their final form (pair tiles), no square copy
+    bool r_packed;                 // r pass: the previous sweep's tally has written r_S and cleared the marks
     bool ru_ready;                 // f pass: the previous sweep's tally has made the slot words
     bool sentinels_in_place;       // r pass: P holds the sentinels a COMPLETED pipelined pass of this shape left behind
     const fcd_tally_f *tally_f;    // r pass: the f half of the tally to carry in the packing launch, or nullptr ...

@@ -247,13 +247,15 @@ __global__ __launch_bounds__(1024) void gibbs_f_diff_kernel(const double *__rest
 __host__ __device__ static inline int64_t ru_index(int64_t wn, int NW, int jw, int lane) {
     return NW <= 4 ? (wn * 64 + lane) * 4 + jw : (wn * NW + jw) * 64 + lane;
 }
+// (the whole wave, (wn, jw) wave-uniform: lane l loads the word of patient 16 jw + l % 16 -- one memory instruction instead of 16)
 __device__ __forceinline__ uint32_t pack_ru_word(const uint64_t *__restrict__ r_bits, int64_t wn, int U, int jw, int lane) {
+    const int ul = jw * 16 + (lane & 15);
+    const uint64_t mine = r_bits[wn * U + (ul < U ? ul : U - 1)];                                  // clamped: no branch around the load
     uint32_t v = 0;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         const int u = jw * 16 + j;
-        const uint64_t word = r_bits[wn * U + (u < U ? u : U - 1)];                              // clamped: no branch per load
-        v |= (u < U ? (uint32_t)((word >> lane) & 1ull) : 0u) << (4 * (j >> 1) + (j & 1));
+        v |= (u < U ? (uint32_t)((fcd_lane_word(mine, j) >> lane) & 1ull) : 0u) << (4 * (j >> 1) + (j & 1));
     }
     return v;
 }
@@ -312,17 +314,54 @@ __device__ __attribute__((noinline)) int fcd_f_exact_edge(const double *__restri
     return fcd_draw_f(0.0, c1 + b1, c2 + b2, fcd_u32(xw));
 }
 
-template <int NW16>
+// Pair-aligned tiles (PT): tile t is rows (n0, n0 + 1) = (2i, 2i + 1) of the triangle x columns [mb, mb + FT_W) inside
+// one block of 16 regions, edge e of the tile = (n0 + e / FT_W, mb + e % FT_W).  Row pair i has columns [0, n0 + 2) in
+// floor(i/2) + 1 tiles, so the tiles before row pair i number j(j+1) (i = 2j) or (j+1)^2 (i = 2j+1).  A tile then holds both
+// regions of every pair (m, m+1) of its rows and of every pair (n0, n0+1) of its columns: it writes the r pass's f words
+// (f_S, pack_f_item) in their final form -- the row half into f_S[w][n][b(m)], the column half into f_S[w][m][b(n0)] --
+// instead of the square copy the packing launch would read back.
+constexpr int FT_W = FP_EC / 2;
+__host__ __device__ static inline int64_t fpt_tiles(int64_t i) {       // tiles of the row pairs before i
+    const int64_t j = i >> 1;
+    return (i & 1) ? (j + 1) * (j + 1) : j * (j + 1);
+}
+struct fpt_tile {
+    int n0, mb;
+    int cnt0, cnt1;          // edges of row n0 / n0 + 1 in the tile (m < n, row inside the triangle)
+    int64_t cr0, cr1;        // edge id of the first column of each row
+};
+__device__ __forceinline__ fpt_tile fpt_locate(int t, int Nreg) {
+    int j = (int)((sqrtf(4.f * (float)t + 1.f) - 1.f) * 0.5f);
+    while ((int64_t)(j + 1) * (j + 2) <= t) ++j;
+    while ((int64_t)j * (j + 1) > t) --j;
+    const int t0 = j * (j + 1);
+    const int i = (t - t0 < j + 1) ? 2 * j : 2 * j + 1;
+    fpt_tile T;
+    T.n0 = 2 * i;
+    T.mb = FT_W * (t - (int)fpt_tiles(i));
+    T.cnt0 = min(FT_W, T.n0 - T.mb);
+    T.cnt1 = T.n0 + 1 < Nreg ? min(FT_W, T.n0 + 1 - T.mb) : 0;
+    T.cr0 = ((int64_t)T.n0 * (T.n0 - 1) >> 1) + T.mb;
+    T.cr1 = T.cr0 + T.n0;
+    return T;
+}
+
+template <int NW16, bool PT>
 __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__restrict__ S_B, const double *__restrict__ lMf,
                                                             const double *__restrict__ hyper, uint8_t *__restrict__ f_state,
                                                             const uint32_t *__restrict__ r_U, int Nreg, int U, int64_t C,
                                                             int GW, uint32_t chain0, uint64_t seed, uint32_t sweep, float margin, uint8_t *__restrict__ fsq,
-                                                            unsigned long long *__restrict__ dbg) {
+                                                            uint2 *__restrict__ f_S, int NBLK, unsigned long long *__restrict__ dbg) {
     // pair records [NPAIR][FP_EC][16] float2 | per-edge constants [FP_EC] float4 | singles [FP_EC][U][3][2] double
     extern __shared__ __attribute__((aligned(256))) double ptile[];
     const int NPAIR = (U + 1) >> 1;
-    const int64_t c0 = (int64_t)blockIdx.x * FP_EC;
-    const int ne = (int)((C - c0 < FP_EC) ? (C - c0) : FP_EC);
+    // the tile's edges: c0 + e, e < ne (consecutive ids); PT: edge e = (row e / FT_W, column e % FT_W), present where
+    // e % FT_W < cnt of its row, id cr + e % FT_W
+    const int64_t c0 = PT ? 0 : (int64_t)blockIdx.x * FP_EC;
+    const fpt_tile T = PT ? fpt_locate((int)blockIdx.x, Nreg) : fpt_tile{0, 0, 0, 0, 0, 0};
+    const int ne = PT ? FP_EC : (int)((C - c0 < FP_EC) ? (C - c0) : FP_EC);
+    auto has = [&](int e) -> bool { return !PT ? e < ne : (e % FT_W) < (e < FT_W ? T.cnt0 : T.cnt1); };
+    auto cid = [&](int e) -> int64_t { return !PT ? c0 + e : (e < FT_W ? T.cr0 : T.cr1) + (e % FT_W); };
     float4 *edge_k = reinterpret_cast<float4 *>(reinterpret_cast<char *>(ptile) + (size_t)FP_EC * NPAIR * 128);
     double2 *single = reinterpret_cast<double2 *>(reinterpret_cast<char *>(edge_k) + FP_EC * 16);
     const double lg1 = hyper[FCD_H_LNGAMMA + 1] - hyper[FCD_H_LNGAMMA + 0];
@@ -338,7 +377,12 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
     // the NEXT edge are requested while this edge's terms run (32 registers less than holding all 8 edges' words).
     uint32_t Zc[NW16], rn[NW16];
     int wn, wm;                          // (n, m) of the edge at hand (wave-uniform walk of the lower-triangular order)
-    fcd_edge_to_pair(c0, wn, wm);
+    if (PT) {
+        wn = T.cnt0 > 0 ? T.n0 : min(T.n0 + 1, Nreg - 1);      // (a diagonal tile past the last region may draw nothing)
+        wm = T.mb;
+    } else {
+        fcd_edge_to_pair(c0, wn, wm);
+    }
     // wave-uniform base + unsigned 32-bit (region, lane) offset: no per-lane 64-bit address arithmetic.  The (up to four)
     // slot words of a region are ONE 16-byte load (ru_index).
     const uint4 *__restrict__ ru = reinterpret_cast<const uint4 *>(r_U) + (int64_t)(w < GW ? w : 0) * Nreg * 64;
@@ -358,8 +402,8 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
     // (profiles/r04_trace_f.txt: built 3.8 us of a 17 us tile)
     const int wv0 = (int)(threadIdx.x >> 6);
     double sbv = 0.0;
-    if (wv0 < ne && lane < 3) sbv = S_B[(c0 + wv0) * 3 + lane];
-    {
+    if (wv0 < ne && has(wv0) && lane < 3) sbv = S_B[cid(wv0) * 3 + lane];
+    if (!PT) {
         // the tile's rows of lMf are one contiguous piece: coalesced 16-byte copies
         const int n_d2 = ne * U * 3;
         const double2 *src = reinterpret_cast<const double2 *>(lMf + c0 * U * 6);
@@ -369,6 +413,18 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
             const double2 v0 = src[i0], v1 = src[i1 < n_d2 ? i1 : i0];
             single[i0] = v0;
             if (i1 < n_d2) single[i1] = v1;
+        }
+    } else {
+        // two contiguous pieces, one per row: row 1's goes to edge slot FT_W
+        const int na = T.cnt0 * U * 3, n_d2 = na + T.cnt1 * U * 3, ob = FT_W * U * 3 - na;
+        const double2 *sa = reinterpret_cast<const double2 *>(lMf + T.cr0 * U * 6);
+        const double2 *sb = reinterpret_cast<const double2 *>(lMf + T.cr1 * U * 6) - na;
+        for (int i0 = threadIdx.x; i0 < n_d2; i0 += 2 * blockDim.x) {
+            const int i1 = i0 + (int)blockDim.x;
+            const int j1 = i1 < n_d2 ? i1 : i0;
+            const double2 v0 = i0 < na ? sa[i0] : sb[i0], v1 = j1 < na ? sa[j1] : sb[j1];
+            single[i0 < na ? i0 : i0 + ob] = v0;
+            if (i1 < n_d2) single[i1 < na ? i1 : i1 + ob] = v1;
         }
     }
     __syncthreads();
@@ -387,6 +443,7 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
         const int tb = (int)threadIdx.x >= half ? (int)threadIdx.x - half : (int)threadIdx.x + ((int)blockDim.x - half);
         for (int ep = tb; ep < total; ep += blockDim.x) {
             const int e = ep / NPAIR, pr = ep - e * NPAIR;
+            if (PT && !has(e)) continue;
             const int u = 2 * pr;
             const double2 *su = single + (e * U + u) * 3;
             double2 A[3], B[3];
@@ -413,6 +470,7 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
         // B_e >= sum over the pairs of max |record entry|: the sum over the patients of the largest |value| of the row
         // (wave e does edge e, lane = patient; U <= 64) -- what bounds the error of the fp32 sums below
         for (int ee = (int)(threadIdx.x >> 6); ee < ne; ee += (int)(blockDim.x >> 6)) {      // (a workgroup may have fewer waves than edges)
+            if (PT && !has(ee)) continue;
             float a = 0.f;
             if (lane < U) {
                 const double2 *su = single + (ee * U + lane) * 3;
@@ -425,7 +483,7 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
             if (lane == 0) {
                 // the edge's constants as the draw wants them: the two log-odds offsets in fp32 and the relative uncertainty
                 // of the weights that the error bound of the whole fp32 sum (NPAIR records, then the offset) amounts to
-                const int64_t c = c0 + ee;
+                const int64_t c = cid(ee);
                 double sb0, sb1, sb2;
                 if (ee == wv0) {                       // (this wave's own edge: the values asked for at the top)
                     const uint64_t bits = (uint64_t)__double_as_longlong(sbv);      // lane 0 holds S_B[c][0]; lanes 1, 2 the others
@@ -453,6 +511,8 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
     const uint32_t chain = chain0 + (uint32_t)w * 64u + lane;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     fcd_u4 rnd = {0, 0, 0, 0};
+    int64_t rnd_blk = -1;                // (PT: the Philox block in rnd; a row of the tile may span two)
+    uint32_t kt = 0;                     // (PT: the tile's draws, 2 bits per edge)
     const int NG = (NPAIR + 7) >> 3;     // groups of 8 pairs = 16 patients = one slot word
     // The records lie [pair][edge][slot] from LDS address 0 (the kernel declares no static LDS: the host asks the runtime
     // before the first launch), so with the loops over edges, groups and pairs unrolled the record's address is an
@@ -460,11 +520,19 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
 
 #pragma unroll
     for (int e = 0; e < FP_EC; ++e) {
-        if (e < ne) {
-            const int64_t c = c0 + e;
+        if (has(e)) {
+            const int64_t c = cid(e);
             // next edge: (n, m+1), or (n+1, 0) at the end of row n (clamped past the last edge: unused there)
             int nn = wn, nm = wm + 1;
-            if (nm == nn) {
+            if (PT) {
+                // PT: (n0 + 1, mb) after the last edge of row n0; clamped to regions that exist (unused there)
+                if (e + 1 >= FT_W + (e < FT_W ? 0 : FT_W) || !has(e + 1)) {
+                    nn = T.n0 + 1;
+                    nm = T.mb;
+                }
+                nn = nn < Nreg ? nn : Nreg - 1;
+                nm = nm < Nreg ? nm : Nreg - 1;
+            } else if (nm == nn) {
                 nm = 0;
                 nn = (nn + 1 < Nreg) ? nn + 1 : nn;
             }
@@ -524,8 +592,17 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
                 f_state[((int64_t)w * C + c) * 64 + lane] = (uint8_t)(acc.x > acc.y ? 1 : 2);
                 continue;
             }
-            if ((e & 3) == 0) rnd = fcd_philox((uint32_t)(c >> 2), chain, sweep, FCD_KIND_F, k0, k1);   // c0 is a multiple of 8
-            const uint32_t xw = fcd_word(rnd, e & 3);
+            uint32_t xw;
+            if (!PT) {
+                if ((e & 3) == 0) rnd = fcd_philox((uint32_t)(c >> 2), chain, sweep, FCD_KIND_F, k0, k1);   // c0 is a multiple of 8
+                xw = fcd_word(rnd, e & 3);
+            } else {
+                if ((c >> 2) != rnd_blk) {
+                    rnd_blk = c >> 2;
+                    rnd = fcd_philox((uint32_t)rnd_blk, chain, sweep, FCD_KIND_F, k0, k1);
+                }
+                xw = fcd_word(rnd, (int)(c & 3));
+            }
             bool amb = false;
             int k;
             const float bf1 = ek.x + acc.x, bf2 = ek.y + acc.y, xf = (float)xw * 2.3283064e-10f;
@@ -543,7 +620,8 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
             const long long tc2 = clock64();
 #endif
             (f_state + ((int64_t)w * C + c) * 64)[(uint32_t)lane] = (uint8_t)k;     // (scalar base + lane)
-            if (fsq) {
+            if (PT) kt |= (uint32_t)k << (2 * e);
+            if (!PT && fsq) {
                 // square copy for the r pass that follows (fcd_gibbs_sweeps): rows of it are contiguous in m
                 uint8_t *sq = fsq + (int64_t)w * Nreg * Nreg * 64;
                 (sq + ((int64_t)wn * Nreg + wm) * 64)[(uint32_t)lane] = (uint8_t)k;
@@ -568,6 +646,45 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
                 tr_rest += tc3 - tc2;
             }
 #endif
+        }
+    }
+    if (PT && f_S) {
+        // the r pass's f words (pack_f_item's bytes, (3 f(n, m) + f(n, m+1)) << 2; 0 for m == n and m >= Nreg).  K(r, j):
+        // f of (n0 + r, mb + j) -- drawn here, 0 on the diagonal and for a row beyond Nreg, and (n0, n0 + 1) is the edge
+        // (n0 + 1, n0) of row 1.  Every byte of f_S is written once per pass: the pairs of a row below its own row pair by the
+        // row halves, the diagonal pair (n0, n0 + 1) by the row halves of the tile that holds it, the pairs above by the
+        // column halves, the pairs beyond Nreg by the zeros of the diagonal tiles.
+        auto K = [&](int r, int j) -> uint32_t {
+            if (r == 0 && T.mb + j == T.n0 + 1) return (kt >> (2 * (FT_W + j - 1))) & 3u;
+            return (kt >> (2 * (r * FT_W + j))) & 3u;
+        };
+        const int ncol = min(FT_W, T.n0 + 2 - T.mb);           // columns of the tile (FT_W, or 2 on the diagonal)
+        const int b = T.mb / R_NB, p0 = (T.mb % R_NB) / 2;
+        uint8_t *fs = reinterpret_cast<uint8_t *>(f_S + (int64_t)w * Nreg * NBLK * 64 + lane);     // + ((n * NBLK + b) * 64) * 8
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (T.n0 + r >= Nreg) break;
+            uint8_t *row = fs + (int64_t)((T.n0 + r) * NBLK + b) * 512 + p0;
+            uint32_t v = 0;
+#pragma unroll
+            for (int q = 0; q < FT_W / 2; ++q) v |= ((3u * K(r, 2 * q) + K(r, 2 * q + 1)) << 2) << (8 * q);
+            if (ncol == FT_W) *reinterpret_cast<uint16_t *>(row) = (uint16_t)v;     // (FT_W = 4: two bytes, 2-aligned)
+            else *row = (uint8_t)v;
+        }
+        {
+            const int bn = T.n0 / R_NB, pn = (T.n0 % R_NB) / 2;
+#pragma unroll
+            for (int j = 0; j < FT_W; ++j)
+                if (T.mb + j < T.n0) fs[(int64_t)((T.mb + j) * NBLK + bn) * 512 + pn] = (uint8_t)((3u * K(0, j) + K(1, j)) << 2);
+        }
+        if (ncol < FT_W || T.mb + FT_W == T.n0 + 2) {
+            // the diagonal tile of the row pair: the pairs of its rows beyond Nreg (last block)
+            const int pe = (Nreg + 1) / 2 - (R_NB / 2) * (NBLK - 1);
+            for (int r = 0; r < 2; ++r) {
+                if (T.n0 + r >= Nreg) break;
+                uint8_t *row = fs + (int64_t)((T.n0 + r) * NBLK + NBLK - 1) * 512;
+                for (int p = pe; p < R_NB / 2; ++p) row[p] = 0;
+            }
         }
     }
 #ifdef FCD_ABLATE
@@ -921,8 +1038,11 @@ struct tally_args {
     uint32_t *cnt_f, *cnt_r;           // nullable (both or neither)
     double *hyper;                     // nullable: M-step target
     uint32_t *r_U;                     // nullable: slot words of the next f pass
+    uint2 *r_S;                        // nullable (with r_U): the r words of the next blocked r pass (pack_r_item) ...
+    uint32_t *marks;                   // ... and its marks, cleared
+    int NBLK;                          // blocks of 16 regions
     int n_f_blocks;                    // blocks that read the f state (0: done elsewhere)
-    int n_r_blocks;                    // blocks that count the r bits (at least; the f blocks do too); the rest make r_U
+    int n_r_blocks;                    // blocks that count the r bits (at least; the f blocks do too); the rest make r_U (and r_S)
 };
 
 __global__ __launch_bounds__(1024) void gibbs_tally_kernel(const tally_args a) {
@@ -955,12 +1075,19 @@ __global__ __launch_bounds__(1024) void gibbs_tally_kernel(const tally_args a) {
         cr += sr;
     }
     if (a.r_U && (int)blockIdx.x >= nrb) {
-        // slot words of the next f pass: one wave per (w, n, word) item, as pack_ru_kernel
-        const int U = a.U, NW = a.NW;
-        const int items = GW * a.Nreg * NW;
+        // slot words of the next f pass: one wave per (w, n, word) item, as pack_ru_kernel; then (r_S) one wave per (w, u, b)
+        // item: the next r pass's r words and cleared marks, as its packing launch would make them
+        const int U = a.U, NW = a.NW, NBLK = a.NBLK;
+        const int items_u = GW * a.Nreg * NW, items = items_u + (a.r_S ? GW * U * NBLK : 0);
         for (int item = ((int)blockIdx.x - nrb) * 16 + wave; item < items; item += ((int)gridDim.x - nrb) * 16) {
-            const int jw = item % NW, wn = item / NW;                   // wn = w*Nreg + n
-            a.r_U[ru_index(wn, NW, jw, lane)] = pack_ru_word(r_bits, wn, U, jw, lane);
+            if (item < items_u) {
+                const int jw = item % NW, wn = item / NW;                   // wn = w*Nreg + n
+                a.r_U[ru_index(wn, NW, jw, lane)] = pack_ru_word(r_bits, wn, U, jw, lane);
+            } else {
+                const int it = item - items_u, b = it % NBLK, wu = it / NBLK;      // wu = w*U + u
+                if (lane == 0) a.marks[it] = 0u;
+                a.r_S[(int64_t)it * 64 + lane] = fcd_r_pair_bytes(r_bits, a.Nreg, U, wu / U, wu % U, b, lane);
+            }
         }
     }
     if (!a.acc) return;
@@ -1233,8 +1360,15 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step
             FCD_LAUNCH_CHECK();
         }
         dim3 grid((unsigned)((g.C + pl.f_EC - 1) / pl.f_EC), (unsigned)((g.GW + wpb - 1) / wpb));
-#define FCD_F_ARGS c.S_B, c.lMf, c.hyper, c.f_state, r_U, (int)Nreg, (int)U, g.C, g.GW, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, margin, st.fsq, (unsigned long long *)ctx->dbg
-#define FCD_LAUNCH_F(KERN, SLOT)                                                                              \
+        // pair-aligned tiles that write the r pass's f words themselves (fcd_sweep_step::f_packed; U <= 64 kernel only)
+        const bool pt = st.f_packed && form == FCD_F_PAIR;
+        if (st.f_packed && (form != FCD_F_PAIR || !pl.r_blocked || st.fsq))
+            return fcd_fail(ctx, FCD_ERR_ARG, "f pass: packed f words asked for where the plan has none");
+        uint2 *f_S = pt ? (uint2 *)((char *)ctx->ws + pl.f_S) : nullptr;
+        const int NBLK = (int)((Nreg + R_NB - 1) / R_NB);
+        if (pt) grid.x = (unsigned)fpt_tiles((Nreg + 1) / 2);
+#define FCD_F_ARGS c.S_B, c.lMf, c.hyper, c.f_state, r_U, (int)Nreg, (int)U, g.C, g.GW, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, margin, st.fsq
+#define FCD_LAUNCH_F(KERN, SLOT, EXTRA)                                                                            \
     do {                                                                                                      \
         rc = fcd_lds_attr(ctx, SLOT, reinterpret_cast<const void *>(&KERN), pl.f_shmem);                      \
         if (rc) return rc;                                                                                    \
@@ -1244,20 +1378,29 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step
             if (rc) return rc;                                                                                \
         }                                                                                                     \
         fcd_prof_begin(ctx, FCD_PROF_F, s);                                                                   \
-        hipLaunchKernelGGL(KERN, grid, dim3(64 * wpb), pl.f_shmem, s, FCD_F_ARGS);                            \
+        hipLaunchKernelGGL(KERN, grid, dim3(64 * wpb), pl.f_shmem, s, FCD_F_ARGS, EXTRA);                     \
         fcd_prof_end(ctx, FCD_PROF_F, s);                                                                     \
     } while (0)
-        if (form == FCD_F_PAIR) {
-            if (pl.f_NW == 1) FCD_LAUNCH_F(gibbs_f_pair_kernel<1>, FCD_KA_F_PAIR + 0);
-            else if (pl.f_NW == 2) FCD_LAUNCH_F(gibbs_f_pair_kernel<2>, FCD_KA_F_PAIR + 1);
-            else if (pl.f_NW == 3) FCD_LAUNCH_F(gibbs_f_pair_kernel<3>, FCD_KA_F_PAIR + 2);
-            else FCD_LAUNCH_F(gibbs_f_pair_kernel<4>, FCD_KA_F_PAIR + 3);
+#define FCD_PX (unsigned long long *)ctx->dbg
+#define FCD_PT f_S, NBLK, (unsigned long long *)ctx->dbg
+        if (form == FCD_F_PAIR && pt) {
+            if (pl.f_NW == 1) FCD_LAUNCH_F((gibbs_f_pair_kernel<1, true>), FCD_KA_F_PAIR_T + 0, FCD_PT);
+            else if (pl.f_NW == 2) FCD_LAUNCH_F((gibbs_f_pair_kernel<2, true>), FCD_KA_F_PAIR_T + 1, FCD_PT);
+            else if (pl.f_NW == 3) FCD_LAUNCH_F((gibbs_f_pair_kernel<3, true>), FCD_KA_F_PAIR_T + 2, FCD_PT);
+            else FCD_LAUNCH_F((gibbs_f_pair_kernel<4, true>), FCD_KA_F_PAIR_T + 3, FCD_PT);
+        } else if (form == FCD_F_PAIR) {
+            if (pl.f_NW == 1) FCD_LAUNCH_F((gibbs_f_pair_kernel<1, false>), FCD_KA_F_PAIR + 0, FCD_PT);
+            else if (pl.f_NW == 2) FCD_LAUNCH_F((gibbs_f_pair_kernel<2, false>), FCD_KA_F_PAIR + 1, FCD_PT);
+            else if (pl.f_NW == 3) FCD_LAUNCH_F((gibbs_f_pair_kernel<3, false>), FCD_KA_F_PAIR + 2, FCD_PT);
+            else FCD_LAUNCH_F((gibbs_f_pair_kernel<4, false>), FCD_KA_F_PAIR + 3, FCD_PT);
         } else {
-            if (pl.f_EC == 8) FCD_LAUNCH_F(gibbs_f_pairx_kernel<8>, FCD_KA_F_PAIR_BIG + 0);
-            else if (pl.f_EC == 4) FCD_LAUNCH_F(gibbs_f_pairx_kernel<4>, FCD_KA_F_PAIR_BIG + 1);
-            else if (pl.f_EC == 2) FCD_LAUNCH_F(gibbs_f_pairx_kernel<2>, FCD_KA_F_PAIR_BIG + 2);
-            else FCD_LAUNCH_F(gibbs_f_pairx_kernel<1>, FCD_KA_F_PAIR_BIG + 3);
+            if (pl.f_EC == 8) FCD_LAUNCH_F(gibbs_f_pairx_kernel<8>, FCD_KA_F_PAIR_BIG + 0, FCD_PX);
+            else if (pl.f_EC == 4) FCD_LAUNCH_F(gibbs_f_pairx_kernel<4>, FCD_KA_F_PAIR_BIG + 1, FCD_PX);
+            else if (pl.f_EC == 2) FCD_LAUNCH_F(gibbs_f_pairx_kernel<2>, FCD_KA_F_PAIR_BIG + 2, FCD_PX);
+            else FCD_LAUNCH_F(gibbs_f_pairx_kernel<1>, FCD_KA_F_PAIR_BIG + 3, FCD_PX);
         }
+#undef FCD_PT
+#undef FCD_PX
 #undef FCD_LAUNCH_F
 #undef FCD_F_ARGS
         FCD_LAUNCH_CHECK();
@@ -1320,11 +1463,13 @@ extern "C" int fcd_gibbs_accumulate(fcd_ctx *ctx, const uint8_t *f_state, const 
 // one launch of gibbs_tally_kernel; counts / cnt_f+cnt_r / hyper / r_U each optional
 static int launch_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
                         const fcd_geo &g, int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r, double *hyper, uint32_t *r_U,
-                        int ru_words, hipStream_t s, bool f_done = false) {
+                        int ru_words, hipStream_t s, bool f_done = false, uint2 *r_S = nullptr, uint32_t *marks = nullptr) {
     tally_args a;
     a.f_state = f_state; a.r_bits = r_bits;
     a.C = g.C; a.NU = Nreg * U; a.G = G;
     a.GW = g.GW; a.Nreg = (int)Nreg; a.U = (int)U; a.NW = ru_words;
+    a.r_S = r_U ? r_S : nullptr; a.marks = marks;
+    a.NBLK = (int)((Nreg + R_NB - 1) / R_NB);
     a.acc = (counts || hyper) ? (unsigned long long *)ctx->acc : nullptr;
     a.counts_out = reinterpret_cast<unsigned long long *>(counts);
     a.cnt_f = cnt_f; a.cnt_r = cnt_r;
@@ -1340,7 +1485,7 @@ static int launch_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_
         if (f_done) blocks = rb;
     }
     if (r_U) {
-        int64_t ru_blocks = ((int64_t)g.GW * Nreg * a.NW + 15) / 16;
+        int64_t ru_blocks = ((int64_t)g.GW * Nreg * a.NW + (a.r_S ? (int64_t)g.GW * U * a.NBLK : 0) + 15) / 16;
         if (ru_blocks > ctx->num_cu) ru_blocks = ctx->num_cu;
         blocks += ru_blocks;
     }
@@ -1361,9 +1506,10 @@ extern "C" int fcd_gibbs_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint6
 }
 
 // The sampler loop of ONE rank between two exchanges of pooled statistics: fcd_gibbs_run (what UnsharedRegionFit(method=
-// 'gibbs'), run_chains and bench.py call) and fcd_gibbs_sweeps.  Per sweep: f pass (1 launch), packing for the r pass (1),
-// r pass (one pipelined launch, or ceil(Nreg/16) + 1 block steps), tally (1) -- the tally also carries the M-step and the
-// slot words of the next f pass.  hyper_m: what the M-step writes (nullptr when mstep_every == 0); pair_acc: add the
+// 'gibbs'), run_chains and bench.py call) and fcd_gibbs_sweeps.  Per sweep: f pass (1 launch), packing for the r pass (1, in
+// the first sweep of a call only where the f pass can write the packed f words: packed_ok), r pass (one pipelined launch, or
+// ceil(Nreg/16) + 1 block steps), tally (1) -- the tally also carries the M-step, the slot words of the next f pass and, with
+// packed_ok, the r words of the next r pass.  hyper_m: what the M-step writes (nullptr when mstep_every == 0); pair_acc: add the
 // (f_c, mixture case) counts to the context's pair accumulator; count_acc: add the anomalous-region counts to the
 // context's count accumulator.
 static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int64_t n_sweeps, int64_t mstep_every,
@@ -1378,11 +1524,17 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
     const bool pair_form = c.lMf && (pl.f_form == FCD_F_PAIR || pl.f_form == FCD_F_PAIRX);
     fcd_sweep_step st = {sweep0};
     // the square copy of the f state: where the plan has one, both tables are there and the edge ids are symmetric
+    uint8_t *fsq = nullptr;
     if (pl.fsq_bytes && c.lMf && c.lMd && c.edge_mode == FCD_EDGE_SYMMETRIC) {
         int rc = fcd_fsq_reserve(ctx, pl.fsq_bytes);
         if (rc) return rc;
-        st.fsq = (uint8_t *)ctx->fsq;
+        fsq = (uint8_t *)ctx->fsq;
     }
+    // From the second sweep of a call on, the U <= 64 f pass writes the r pass's f words itself (pair-aligned tiles) and the
+    // tally before it has made the r words and cleared the marks: no packing launch.  The first sweep, the any-U f kernel,
+    // the reference edge ids, knob r_refill and knob f_pack = 1 keep the packing launch (from the square copy).
+    const bool packed_ok = pl.f_form == FCD_F_PAIR && c.lMf && c.lMd && pl.r_blocked && pl.r_idx32 &&
+                           c.edge_mode == FCD_EDGE_SYMMETRIC && ctx->knobs.f_pack != 1 && !ctx->knobs.r_refill;
     // The slot words of the f pass live behind the r pass's scratch (fcd_sweep_plan): the r pass's two buffers of panel
     // values then survive from one sweep to the next, and since a completed pipelined pass leaves every slot holding its
     // sentinel again, only the first sweep of a call has to write them (13 MB at cfg3).
@@ -1392,12 +1544,15 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
     }
     for (int64_t i = 0; i < n_sweeps; ++i) {
         st.sweep = sweep0 + i;
+        st.f_packed = packed_ok && st.r_packed;
+        st.fsq = st.f_packed ? nullptr : fsq;
         int rc = fcd_gibbs_f_pass(ctx, c, st);
         if (rc) return rc;
         const bool last = i + 1 == n_sweeps;
         const bool do_m = mstep_every > 0 && (i + 1) % mstep_every == 0;
         const bool do_a = cnt_f && st.sweep >= accumulate_from;
-        // the f half of this sweep's tally rides in the r pass's packing launch (beside it, not after the pass)
+        // the f half of this sweep's tally rides in the r pass's packing launch (beside it, not after the pass) where there
+        // is one; else the tally after the pass counts it
         fcd_tally_f tf;
         tf.f_state = c.f_state; tf.C = g.C; tf.G = G; tf.GW = g.GW;
         tf.acc = (do_m || (last && counts)) ? (unsigned long long *)ctx->acc : nullptr;
@@ -1413,6 +1568,7 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         st.sentinels_in_place = pair_form && ctx->r_form_last == 2;        // (a pipelined pass has just been queued)
         // the r pass's scratch is dead once its last launch is queued: the slot words of the next f pass go to their place
         uint32_t *r_U_next = (pair_form && !last) ? (uint32_t *)((char *)ctx->ws + pl.r_U) : nullptr;
+        uint2 *r_S_next = (packed_ok && r_U_next) ? (uint2 *)((char *)ctx->ws + pl.r_S) : nullptr;      // (and the marks)
         int64_t *cts = (last ? counts : nullptr);
         // Several ranks (a communicator on the context): the tally leaves this rank's counts in the context's vector, RCCL sums
         // it over the ranks in place ON THIS STREAM, a one-thread kernel makes the M-step from the pooled counts -- all queued
@@ -1421,7 +1577,8 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         int64_t *tally_counts = pooled ? (int64_t *)ctx->pool_counts : cts;
         if (do_m || do_a || cts || r_U_next) {
             rc = launch_tally(ctx, c.f_state, c.r_bits, Nreg, U, G, g, tally_counts, do_a ? cnt_f : nullptr, do_a ? cnt_r : nullptr,
-                              (do_m && !pooled) ? hyper_m : nullptr, r_U_next, pl.f_NW, s, st.tally_f_done);
+                              (do_m && !pooled) ? hyper_m : nullptr, r_U_next, pl.f_NW, s, st.tally_f_done, r_S_next,
+                              (uint32_t *)((char *)ctx->ws + pl.marks));
             if (rc) {
                 if (tf.acc) (void)hipMemsetAsync(ctx->acc, 0, 8 * sizeof(unsigned long long), s);
                 return rc;
@@ -1450,6 +1607,7 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
             if (rc) return rc;
         }
         st.ru_ready = r_U_next != nullptr;
+        st.r_packed = r_S_next != nullptr;
     }
     return FCD_OK;
 }

@@ -33,7 +33,6 @@
 
 namespace {
 
-constexpr int R_NB = 16;   // regions per diagonal block (even: both halves of a Philox block stay inside)
 
 // ---------------------------------------------------------------------------------------------
 // region-major difference table: one thread per (u, n, m) record of 6 doubles
@@ -71,15 +70,7 @@ __global__ __launch_bounds__(256) void region_tables_kernel(const double *__rest
 //   (the in-order part D reads the same bytes: the old ones of its own block from r_S, the redrawn ones of the block before from r_Sn)
 // (f of a region beyond Nreg or of m == n counts as 0; those table records are zero.)
 // ---------------------------------------------------------------------------------------------
-// 8 two-bit fields of x -> the low two bits of 8 bytes (x: fields 0-3, y: fields 4-7)
-__device__ __forceinline__ uint2 spread2(uint32_t x16) {
-    uint32_t lo = x16 & 0xFFu, hi = (x16 >> 8) & 0xFFu;
-    lo = (lo | (lo << 12)) & 0x000F000Fu;
-    hi = (hi | (hi << 12)) & 0x000F000Fu;
-    lo = (lo | (lo << 6)) & 0x03030303u;
-    hi = (hi | (hi << 6)) & 0x03030303u;
-    return make_uint2(lo, hi);
-}
+// (spread2, R_NB: fcd_common.h)
 // LDS address of the dynamic array: 0.  The kernels of this file declare no static LDS (r_static_lds_check asks the
 // runtime before the first launch), so the array starts the workgroup's allocation -- and a term's address is the byte
 // offset inside the record plus an immediate, with no add of a base the compiler cannot see through.
@@ -175,15 +166,8 @@ __device__ __forceinline__ void pack_r_item(const uint64_t *__restrict__ r_bits,
             for (int i = 0; i < R_NB; ++i) dst[i * 64] = R_SENT;
         }
     }
-    uint32_t v = 0;
-#pragma unroll
-    for (int j = 0; j < R_NB; ++j) {
-        const int m = b * R_NB + j;
-        const uint64_t word = r_bits[((int64_t)w * Nreg + (m < Nreg ? m : Nreg - 1)) * U + u];    // clamped: no branch per load
-        v |= (m < Nreg ? (uint32_t)((word >> lane) & 1ull) : 0u) << j;
-    }
     const int64_t o = (((int64_t)w * U + u) * NBLK + b) * 64 + lane;
-    r_S[o] = spread2(v);
+    r_S[o] = fcd_r_pair_bytes(r_bits, Nreg, U, w, u, b, lane);
 }
 
 // grid (ceil(NBLK / (4 FB)), Nreg + U, GW): one wave per (w, n, FB blocks from b) resp. (w, u, FB blocks), no index
@@ -1652,7 +1636,10 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
             pinit.P[1] = keep ? nullptr : a.Pbuf[1];
         }
     }
-    {
+    // (f_packed + r_packed: the f pass has written the f words in their final form and the previous sweep's tally the r words
+    // and the cleared marks -- nothing to pack unless the pipelined pass needs its sentinels again)
+    const bool packed = st.f_packed && st.r_packed && (!pipe || (pinit.P[0] == nullptr && pinit.P[1] == nullptr));
+    if (!packed) {
         // one launch packs the f words of every region and the r words of every patient
         const int fb = st.fsq ? 2 : 1;              // blocks per wave (pack_f_kernel)
         dim3 pgrid((unsigned)(((NBLK + fb - 1) / fb + 3) / 4), (unsigned)(Nreg + U), (unsigned)g.GW);
@@ -1685,6 +1672,7 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
                                c.r_bits, (int)U, r_S, pinit, tf);
         fcd_prof_end(ctx, FCD_PROF_PACK, s);
         FCD_LAUNCH_CHECK();
+        ctx->n_pack += 1;
     }
     ctx->r_form_last = pipe ? 2 : 1;
     if (pipe) {

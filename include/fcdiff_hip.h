@@ -85,7 +85,7 @@ int fcd_ctx_destroy(fcd_ctx *ctx);
  * (Nreg, U, G) while the knobs stay as they are.  Synchronises when it grows something. */
 int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
 /* Tuning / test knobs (defaults: environment FCD_R_PATH, FCD_R_UB, FCD_R_NOPAD, FCD_R_DSPLIT, FCD_R_COOP, FCD_R_REFILL, FCD_R_TOL, FCD_F_TOL, FCD_F_FORM,
- * FCD_CORR_FORM, read once by fcd_ctx_create; 0 = default everywhere; the two test hooks at the end of the list are NOT read
+ * FCD_F_PACK, FCD_CORR_FORM, read once by fcd_ctx_create; 0 = default everywhere; the two test hooks at the end of the list are NOT read
  * from the environment -- a stray variable must not be able to make a fit give up):
  *   "r_path"    0: blocked r pass in its pipelined one-launch form (marks / sentinels in device memory instead of
  *                  kernel boundaries) wherever every workgroup is resident at once, else one launch per block step;
@@ -106,6 +106,8 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
  *               (up to 208 regions) would run
  *   "r_tol", "f_tol"  widen the margin inside which a fast r / f draw is repeated with the exact formula (1e30: all)
  *   "f_form"    2: the any-U pair kernel of the f pass also where the U <= 64 kernel would run; 3: scalar-mask form
+ *   "f_pack"    1: the r pass's packing launch in every sweep (default: from the second sweep of a fcd_gibbs_run call on,
+ *               the U <= 64 f pass writes the r pass's packed f words itself and the tally the r words of the next pass)
  *   "r_poll_limit", "r_withhold"  TEST HOOKS of the pipelined r pass: bound every device-side poll by this many polls /
  *               the in-order role never announces a block (a panel wave then gives its wait up, fcd_ctx_check reports it)
  * None of them changes a result: every combination walks the same chains (tests/test_gpu_parity.py).
@@ -114,7 +116,7 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
 int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value);
 /* Counters of the context: "n_alloc" device allocations made so far, "ws_bytes", "fsq_bytes"; "r_form_last" = the form
  * the last blocked r pass ran in (1 one launch per block step, 2 pipelined one-launch form, 3 one-launch form with
- * counters); "dev_err" = the error word of the pipelined r pass as the host sees it now (see fcd_ctx_check). */
+ * counters); "pack_launches" = packing launches of the r pass made so far; "dev_err" = the error word of the pipelined r pass as the host sees it now (see fcd_ctx_check). */
 int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out);
 /* FCD_ERR_DEVICE if a kernel of this context has abandoned a device-side wait (pipelined r pass: every poll of a mark or
  * of a panel value is bounded, ~1 s), else FCD_OK.  The word is written by the device: call this AFTER the stream has been
