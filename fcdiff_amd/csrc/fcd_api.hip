@@ -177,6 +177,7 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->knobs.r_withhold = 0;
     ctx->r_form_last = 0;
     ctx->n_pack = 0;
+    ctx->n_pack_tally = 0;
     int rc = fcd_ws_reserve(ctx, 1u << 20);
     if (rc == FCD_OK) {
         void *pin = nullptr;
@@ -297,6 +298,7 @@ int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out) {
     else if (!strcmp(name, "fsq_bytes")) *out = (int64_t)ctx->fsq_bytes;
     else if (!strcmp(name, "r_form_last")) *out = ctx->r_form_last;
     else if (!strcmp(name, "pack_launches")) *out = ctx->n_pack;
+    else if (!strcmp(name, "tally_f_in_pack")) *out = ctx->n_pack_tally;
     else if (!strcmp(name, "comm_world")) *out = ctx->comm ? ctx->comm_world : 0;
     else if (!strcmp(name, "dev_err")) *out = ctx->dev_err ? (int64_t)*ctx->dev_err : 0;
     else if (!strcmp(name, "f_repeats") || !strcmp(name, "r_exact_rows")) {

@@ -1482,7 +1482,8 @@ static int launch_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_
         int64_t rb = (a.NU + 1023) / 1024;
         if (rb > 64) rb = 64;
         a.n_r_blocks = (int)rb;
-        if (f_done) blocks = rb;
+        // the kernel's counting blocks are the first max(n_f_blocks, n_r_blocks): the grid must hold every one of them
+        if (rb > a.n_f_blocks) blocks = rb;
     }
     if (r_U) {
         int64_t ru_blocks = ((int64_t)g.GW * Nreg * a.NW + (a.r_S ? (int64_t)g.GW * U * a.NBLK : 0) + 15) / 16;

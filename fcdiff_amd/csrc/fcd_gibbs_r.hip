@@ -1673,6 +1673,7 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         fcd_prof_end(ctx, FCD_PROF_PACK, s);
         FCD_LAUNCH_CHECK();
         ctx->n_pack += 1;
+        if (st.tally_f_done) ctx->n_pack_tally += 1;
     }
     ctx->r_form_last = pipe ? 2 : 1;
     if (pipe) {

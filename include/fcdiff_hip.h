@@ -116,7 +116,9 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
 int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value);
 /* Counters of the context: "n_alloc" device allocations made so far, "ws_bytes", "fsq_bytes"; "r_form_last" = the form
  * the last blocked r pass ran in (1 one launch per block step, 2 pipelined one-launch form, 3 one-launch form with
- * counters); "pack_launches" = packing launches of the r pass made so far; "dev_err" = the error word of the pipelined r pass as the host sees it now (see fcd_ctx_check). */
+ * counters); "pack_launches" = packing launches of the r pass made so far; "tally_f_in_pack" = those of them that also
+ * carried the f half of the sweep's tally; "dev_err" = the error word of the pipelined r pass as the host sees it now (see
+ * fcd_ctx_check). */
 int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out);
 /* FCD_ERR_DEVICE if a kernel of this context has abandoned a device-side wait (pipelined r pass: every poll of a mark or
  * of a panel value is bounded, ~1 s), else FCD_OK.  The word is written by the device: call this AFTER the stream has been
