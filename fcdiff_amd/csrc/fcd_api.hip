@@ -160,12 +160,13 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->n_alloc = 0;
     for (int i = 0; i < FCD_KA_N; ++i) ctx->lds_attr[i] = 0;
     for (int i = 0; i < 3; ++i) ctx->pipe_occ[i] = -1;
+    ctx->pipe_grid = ctx->pipe_capacity = 0;
     // the only place the environment is read: defaults of the knobs (fcd_ctx_set_knob changes them later)
     ctx->knobs.r_path = (int)knob_env("FCD_R_PATH");
     ctx->knobs.r_ub = (int)knob_env("FCD_R_UB");
     ctx->knobs.r_nopad = (int)knob_env("FCD_R_NOPAD");
     ctx->knobs.r_dsplit = (int)knob_env("FCD_R_DSPLIT");
-    ctx->knobs.r_coop = (int)knob_env("FCD_R_COOP");
+    ctx->knobs.r_coop = (int)knob_env("FCD_R_COOP") == 1 ? 1 : 0;    // (2, the refusal test hook, not from the environment)
     ctx->knobs.qr_form = (int)knob_env("FCD_QR_FORM");
     ctx->knobs.r_refill = (int)knob_env("FCD_R_REFILL");
     ctx->knobs.r_tol = knob_env("FCD_R_TOL");
@@ -299,6 +300,8 @@ int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out) {
     else if (!strcmp(name, "r_form_last")) *out = ctx->r_form_last;
     else if (!strcmp(name, "pack_launches")) *out = ctx->n_pack;
     else if (!strcmp(name, "tally_f_in_pack")) *out = ctx->n_pack_tally;
+    else if (!strcmp(name, "pipe_grid")) *out = ctx->pipe_grid;
+    else if (!strcmp(name, "pipe_capacity")) *out = ctx->pipe_capacity;
     else if (!strcmp(name, "comm_world")) *out = ctx->comm ? ctx->comm_world : 0;
     else if (!strcmp(name, "dev_err")) *out = ctx->dev_err ? (int64_t)*ctx->dev_err : 0;
     else if (!strcmp(name, "f_repeats") || !strcmp(name, "r_exact_rows")) {

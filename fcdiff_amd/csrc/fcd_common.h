@@ -24,7 +24,8 @@ struct fcd_knobs {
     int r_refill;      // 1: the packing launch writes the panel-value sentinels in every sweep (default: only in the first sweep of a fcd_gibbs_run call)
     int qr_form;       // variational q_R update: 0 = by size; 1 = gathers from the edge-major table inside the region loop (rounds 1-3);
                        // 2 = region-major weights made first, whatever their size
-    int r_coop;        // pipelined r pass: 1 = cooperative launch (the runtime checks that the grid is co-resident; +16 us per pass), else plain
+    int r_coop;        // pipelined r pass: 1 = cooperative launch (the runtime checks that the grid is co-resident; +16 us per pass), else plain;
+                       // 2 = TEST HOOK (fcd_ctx_set_knob only): every pipelined launch acts as if the runtime had refused it, launching nothing
     int r_dsplit;      // 1: ONE in-order workgroup per patient in the pipelined r pass (default: two, 8 chain words each, where there are more than 8)
     double r_tol;      // > default: widen the margin inside which an r draw is re-decided with the exact logit
     double f_tol;      // > default: the same for the f draws
@@ -52,6 +53,8 @@ struct fcd_ctx {
     int pipe_occ[3];               // pipelined r pass: workgroups per CU of the three kernel variants (-1: not asked yet) ...
     size_t pipe_occ_shmem[3];      // ... for this much dynamic LDS
     int pipe_occ_threads[3];       // ... and this many threads
+    int64_t pipe_grid;             // last pipelined attempt of the r pass: its grid nD + nP + npad (fcd_ctx_stat "pipe_grid") ...
+    int64_t pipe_capacity;         // ... and the workgroups resident at once for it, pipe_occ * num_cu ("pipe_capacity")
     int r_form_last;               // form of the last blocked r pass: 1 step-per-launch, 2 pipelined, 3 one-launch with counters (fcd_ctx_stat)
     long long n_pack;              // packing launches of the r pass so far (fcd_ctx_stat "pack_launches")
     long long n_pack_tally;        // ... of them that carried the f half of the tally (fcd_ctx_stat "tally_f_in_pack")

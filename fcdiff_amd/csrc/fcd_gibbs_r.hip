@@ -1391,6 +1391,8 @@ __global__ __launch_bounds__(64 * R_WAVES) void gibbs_r_simple(const double *__r
 
 template <int UB, int WPE>
 int launch_step(fcd_ctx *ctx, const r_step_args &a, size_t shmem, hipStream_t s, bool prof) {
+    // (what only the pipelined form may carry: a fall-back from it must have taken both back)
+    if (a.flags || a.dsplit) return fcd_fail(ctx, FCD_ERR_ARG, "r step: launch carries the pipelined form's marks or split");
     {
         static int lds0 = 0;
         int rc0 = fcd_static_lds_check(ctx, reinterpret_cast<const void *>(&gibbs_r_step_kernel<UB, WPE>), &lds0);
@@ -1426,13 +1428,21 @@ int launch_pipe(fcd_ctx *ctx, const r_step_args &a, size_t shmem, bool *fits, bo
         ctx->pipe_occ_shmem[slot] = shmem;
         ctx->pipe_occ_threads[slot] = threads;
     }
-    // every workgroup resident at once, with a few slots to spare (the occupancy query knows nothing of other kernels
-    // on the device; a workgroup that starts late only makes the others wait -- every poll is bounded)
-    *fits = (int64_t)ctx->pipe_occ[slot] * ctx->num_cu >= (int64_t)a.nD + a.nP + R_PIPE_SLOT_MARGIN;
+    // every workgroup of the grid that is launched (the empty ones included) resident at once, with a few slots to spare
+    // (the occupancy query knows nothing of other kernels on the device; a workgroup that starts late only makes the
+    // others wait -- every poll is bounded)
+    ctx->pipe_grid = (int64_t)a.nD + a.nP + a.npad;
+    ctx->pipe_capacity = (int64_t)ctx->pipe_occ[slot] * ctx->num_cu;
+    *fits = ctx->pipe_capacity >= ctx->pipe_grid + R_PIPE_SLOT_MARGIN;
     if (!*fits || !launch) return FCD_OK;
     // (fcd_prof_begin records the begin event of the next pair, fcd_prof_end closes and counts it: a launch the runtime
     // refuses between the two leaves no pair open -- the next fcd_prof_begin records that begin event again)
     fcd_prof_begin(ctx, FCD_PROF_RSTEP, s);
+    if (ctx->knobs.r_coop == 2) {
+        // TEST HOOK (knob r_coop = 2, through fcd_ctx_set_knob only): what a refused cooperative launch does, launching nothing
+        *fits = false;
+        return FCD_OK;
+    }
     if (ctx->knobs.r_coop == 1) {
         // a COOPERATIVE launch (knob r_coop = 1): the runtime itself refuses a grid that cannot be resident at once (the
         // precondition of every device-side wait in the kernel) instead of this file's occupancy arithmetic being the only
@@ -1628,12 +1638,20 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         }
         rc = with_ub(ub, [&](auto UB, auto WPE) { return launch_pipe<UB, WPE>(ctx, a, shmem, &pipe, false, s); });
         if (rc) return rc;
+        if (!pipe && a.npad) {
+            // the empty workgroups are what does not fit: the pass without them (they only keep CUs to the in-order role)
+            a.npad = 0;
+            rc = with_ub(ub, [&](auto UB, auto WPE) { return launch_pipe<UB, WPE>(ctx, a, shmem, &pipe, false, s); });
+            if (rc) return rc;
+        }
         if (pipe) {
             pinit.marks = (uint32_t *)(ws + pl.marks);
             // (the sentinels: unless a completed pipelined pass of this shape left them in place -- the sweep loop knows)
             const bool keep = st.sentinels_in_place && ctx->r_form_last == 2 && !ctx->knobs.r_refill;
             pinit.P[0] = keep ? nullptr : a.Pbuf[0];
             pinit.P[1] = keep ? nullptr : a.Pbuf[1];
+        } else {
+            a.dsplit = 0;          // (the step form below: one in-order workgroup per patient)
         }
     }
     // (f_packed + r_packed: the f pass has written the f words in their final form and the previous sweep's tally the r words
@@ -1680,7 +1698,8 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         a.flags = pinit.marks;
         rc = with_ub(ub, [&](auto UB, auto WPE) { return launch_pipe<UB, WPE>(ctx, a, shmem, &pipe, true, s); });
         if (rc || pipe) return rc;
-        // the runtime refused the cooperative launch (grid not co-resident after all): the step-per-launch form instead
+        // the runtime refused the cooperative launch (grid not co-resident after all; or knob r_coop = 2): the step-per-launch
+        // form instead
         ctx->r_form_last = 1;
         a.flags = nullptr;
         a.dsplit = 0;

@@ -110,6 +110,8 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
  *               the U <= 64 f pass writes the r pass's packed f words itself and the tally the r words of the next pass)
  *   "r_poll_limit", "r_withhold"  TEST HOOKS of the pipelined r pass: bound every device-side poll by this many polls /
  *               the in-order role never announces a block (a panel wave then gives its wait up, fcd_ctx_check reports it)
+ *   "r_coop" = 2  TEST HOOK: every pipelined launch of the r pass acts as if the runtime had refused a cooperative launch
+ *               (it launches nothing, and the pass falls back to one launch per block step); FCD_R_COOP=2 means 0
  * None of them changes a result: every combination walks the same chains (tests/test_gpu_parity.py).
  * (Round 2 carried eight more forms behind knobs -- a one-launch form with counters, a row-sequential kernel, two-stream
  * half-passes, a pair-record table, triple records in the f pass, ... -- all measured slower; DESIGN.md keeps the numbers.) */
@@ -118,7 +120,9 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value);
  * the last blocked r pass ran in (1 one launch per block step, 2 pipelined one-launch form, 3 one-launch form with
  * counters); "pack_launches" = packing launches of the r pass made so far; "tally_f_in_pack" = those of them that also
  * carried the f half of the sweep's tally; "dev_err" = the error word of the pipelined r pass as the host sees it now (see
- * fcd_ctx_check). */
+ * fcd_ctx_check); "pipe_grid" / "pipe_capacity" = the grid of the last pipelined attempt of the r pass (its empty
+ * workgroups included) and the workgroups the occupancy query says are resident at once for it (the form is taken where
+ * pipe_grid + 8 <= pipe_capacity). */
 int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out);
 /* FCD_ERR_DEVICE if a kernel of this context has abandoned a device-side wait (pipelined r pass: every poll of a mark or
  * of a panel value is bounded, ~1 s), else FCD_OK.  The word is written by the device: call this AFTER the stream has been
