@@ -139,10 +139,12 @@ struct fcd_tally_f {
     unsigned long long *acc;           // nullable: context-owned sums, [1..3] = number of f == 0, 1, 2
     uint32_t *cnt_f;                   // nullable
 };
-// one launch of the (f_c, mixture case) count kernel of fcd_post.hip: acc (C, U, 3, 3) += counts of this state
+// one launch of the (f_c, mixture case) count kernel of fcd_post.hip: acc (C, U, 3, 3) = (accumulate ? acc : 0) + counts of
+// this state; T = uint32_t or double
 struct fcd_geo;
+template <typename T>
 int fcd_pair_tally_launch(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
-                          const fcd_geo &g, uint32_t *acc, hipStream_t s);
+                          const fcd_geo &g, T *acc, bool accumulate, hipStream_t s);
 // the anomalous-region count kernels of fcd_count.hip (two launches): both histograms += the counts of this state; the
 // scratch they need is grown by fcd_count_ws_reserve (fcd_gibbs_run: before its sweep loop)
 int fcd_count_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);

@@ -925,95 +925,31 @@ __global__ __launch_bounds__(64) void gibbs_cond_r_kernel(const double *__restri
 }
 
 // ---------------------------------------------------------------------------------------------
-// pooled statistics, marginal counters, M-step
+// (pi, gamma) M-step from pooled counts c5 = {sum r, #f=0, #f=1, #f=2, chains}: the sample version of fit.py:208-220.
+// Returns what hyper[i] receives (i = FCD_H_LNGAMMA + k: ln gamma_k; FCD_H_LNPI0: ln(1 - pi); FCD_H_LNPI1: ln pi), one
+// logarithm per slot so that the tally's lanes 0..4 take one each; fcd_gibbs_mstep loops over the five.  C edges and
+// NU = Nreg * U sites per chain.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gibbs_stats_kernel(const uint8_t *__restrict__ f_state,
-                                                          const uint64_t *__restrict__ r_bits, int64_t C, int64_t NU, int GW,
-                                                          int64_t G, unsigned long long *__restrict__ counts) {
-    __shared__ unsigned long long red[4][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long cr = 0, c0 = 0, c1 = 0, c2 = 0;
-    // f: one wave per (w, c) row of 64 bytes
-    const int64_t rows = (int64_t)GW * C;
-    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
-        const int w = (int)(row / C);
-        const uint64_t act = fcd_active_mask(w, G);
-        const int f = f_state[row * 64 + lane];
-        const uint64_t b0 = __ballot(f == 0) & act, b1 = __ballot(f == 1) & act, b2 = __ballot(f == 2) & act;
-        if (lane == 0) {
-            c0 += __popcll(b0);
-            c1 += __popcll(b1);
-            c2 += __popcll(b2);
-        }
-    }
-    // r: one thread per word
-    const int64_t words = (int64_t)GW * NU;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (int64_t)gridDim.x * blockDim.x) {
-        const int w = (int)(i / NU);
-        cr += __popcll(r_bits[i] & fcd_active_mask(w, G));
-    }
-    // integer sums: any order gives the same result
-    for (int o = 32; o > 0; o >>= 1) cr += __shfl_xor(cr, o, 64);
-    if (lane == 0) {
-        red[wave][0] = cr; red[wave][1] = c0; red[wave][2] = c1; red[wave][3] = c2;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const unsigned long long s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        if (s) atomicAdd(&counts[threadIdx.x], s);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 4) counts[4] = (unsigned long long)G;
-}
-
-// (pi, gamma) from pooled counts {sum r, #f=0, #f=1, #f=2, chains}: the sample version of fit.py:208-220
-__device__ __forceinline__ void mstep_from_counts(const unsigned long long *c5, double sites_per_chain_r, double C,
-                                                  double *__restrict__ hyper) {
+static_assert(FCD_H_LNGAMMA == 0 && FCD_H_LNPI0 == 3 && FCD_H_LNPI1 == 4, "fcd_mstep_log: slot i is hyper[i]");
+__device__ __forceinline__ double fcd_mstep_log(int i, const unsigned long long *c5, double C, double NU) {
     const double Gtot = (double)c5[4];
-    const double n_r = Gtot * sites_per_chain_r;
-    double pi = (double)c5[0] / n_r;                      // fit.py:213 over chains
-    const double lo = 0.5 / n_r;
-    pi = fmin(fmax(pi, lo), 1.0 - lo);
-    hyper[FCD_H_LNPI0] = log(1.0 - pi);
-    hyper[FCD_H_LNPI1] = log(pi);
-    const double n_f = Gtot * C;
-    for (int k = 0; k < 3; ++k) {
-        double g = (double)c5[1 + k] / n_f;               // fit.py:220 over chains
-        g = fmax(g, 0.5 / n_f);
-        hyper[FCD_H_LNGAMMA + k] = log(g);
+    double v;
+    if (i < 3) {
+        const double n_f = Gtot * C;
+        v = fmax((double)c5[1 + i] / n_f, 0.5 / n_f);             // fit.py:220 over chains
+    } else {
+        const double n_r = Gtot * NU;
+        const double lo = 0.5 / n_r;
+        const double pi = fmin(fmax((double)c5[0] / n_r, lo), 1.0 - lo);      // fit.py:213 over chains
+        v = i == 3 ? 1.0 - pi : pi;
     }
+    return log(v);
 }
 
-__global__ void gibbs_mstep_kernel(const long long *__restrict__ counts, double sites_per_chain_r, double C,
-                                   double *__restrict__ hyper) {
+__global__ void gibbs_mstep_kernel(const long long *__restrict__ counts, double C, double NU, double *__restrict__ hyper) {
     unsigned long long c5[5];
     for (int i = 0; i < 5; ++i) c5[i] = (unsigned long long)counts[i];
-    mstep_from_counts(c5, sites_per_chain_r, C, hyper);
-}
-
-__global__ __launch_bounds__(256) void gibbs_accum_kernel(const uint8_t *__restrict__ f_state,
-                                                          const uint64_t *__restrict__ r_bits, int64_t C, int64_t NU, int GW,
-                                                          int64_t G, uint32_t *__restrict__ cnt_f, uint32_t *__restrict__ cnt_r) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int64_t c = (int64_t)blockIdx.x * 4 + wave; c < C; c += (int64_t)gridDim.x * 4) {
-        uint32_t n0 = 0, n1 = 0, n2 = 0;
-        for (int w = 0; w < GW; ++w) {
-            const uint64_t act = fcd_active_mask(w, G);
-            const int f = f_state[((int64_t)w * C + c) * 64 + lane];
-            n0 += __popcll(__ballot(f == 0) & act);
-            n1 += __popcll(__ballot(f == 1) & act);
-            n2 += __popcll(__ballot(f == 2) & act);
-        }
-        if (lane == 0) {
-            cnt_f[c * 3 + 0] += n0;
-            cnt_f[c * 3 + 1] += n1;
-            cnt_f[c * 3 + 2] += n2;
-        }
-    }
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < NU; i += (int64_t)gridDim.x * blockDim.x) {
-        uint32_t s = 0;
-        for (int w = 0; w < GW; ++w) s += __popcll(r_bits[(int64_t)w * NU + i] & fcd_active_mask(w, G));
-        cnt_r[i] += s;
-    }
+    for (int i = 0; i < 5; ++i) hyper[i] = fcd_mstep_log(i, c5, C, NU);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1120,22 +1056,8 @@ __global__ __launch_bounds__(1024) void gibbs_tally_kernel(const tally_args a) {
         for (int i = 0; i < 5; ++i) c5[i] = __shfl(mine, i, 64);
         c5[4] = (unsigned long long)G;
         if (a.counts_out && threadIdx.x < 8) a.counts_out[threadIdx.x] = threadIdx.x < 5 ? c5[threadIdx.x] : 0ull;
-        if (a.hyper && threadIdx.x < 5) {
-            // the M-step of mstep_from_counts, one logarithm per lane: lanes 0..2 ln gamma_k, lane 3 ln(1 - pi), lane 4 ln pi
-            const double Gtot = (double)c5[4];
-            const int i = (int)threadIdx.x;
-            double v;
-            if (i < 3) {
-                const double n_f = Gtot * (double)C;
-                v = fmax((double)c5[1 + i] / n_f, 0.5 / n_f);             // fit.py:220 over chains
-            } else {
-                const double n_r = Gtot * (double)NU;
-                const double lo = 0.5 / n_r;
-                const double pi = fmin(fmax((double)c5[0] / n_r, lo), 1.0 - lo);      // fit.py:213 over chains
-                v = i == 3 ? 1.0 - pi : pi;
-            }
-            a.hyper[i < 3 ? FCD_H_LNGAMMA + i : (i == 3 ? FCD_H_LNPI0 : FCD_H_LNPI1)] = log(v);
-        }
+        if (a.hyper && threadIdx.x < 5)      // the M-step, one logarithm per lane
+            a.hyper[threadIdx.x] = fcd_mstep_log((int)threadIdx.x, c5, (double)C, (double)NU);
     }
 }
 
@@ -1418,44 +1340,12 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step
     return FCD_OK;
 }
 
-extern "C" int fcd_gibbs_stats(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U,
-                               int64_t G, int64_t *counts, fcd_stream stream) {
-    fcd_geo g;
-    int rc = fcd_geo_check(ctx, Nreg, U, G, 0, g);
-    if (rc) return rc;
-    if (!f_state || !r_bits || !counts) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_stats: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    FCD_HIP_TRY(hipMemsetAsync(counts, 0, 8 * sizeof(int64_t), s));
-    int64_t blocks = ((int64_t)g.GW * g.C + 3) / 4;
-    const int64_t cap = (int64_t)ctx->num_cu * 8;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(gibbs_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, s, f_state, r_bits, g.C, Nreg * U, g.GW, G,
-                       reinterpret_cast<unsigned long long *>(counts));
-    FCD_LAUNCH_CHECK();
-    return FCD_OK;
-}
-
 extern "C" int fcd_gibbs_mstep(fcd_ctx *ctx, const int64_t *counts, int64_t Nreg, int64_t U, double *hyper,
                                fcd_stream stream) {
     if (!ctx || !counts || !hyper) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_mstep: null pointer");
     if (Nreg < 2 || U < 1) return fcd_fail(ctx, FCD_ERR_SHAPE, "need Nreg >= 2 and U >= 1 (Nreg=%lld, U=%lld)", Nreg, U);
     hipLaunchKernelGGL(gibbs_mstep_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream,
-                       reinterpret_cast<const long long *>(counts), (double)(Nreg * U), (double)fcd_tri(Nreg), hyper);
-    FCD_LAUNCH_CHECK();
-    return FCD_OK;
-}
-
-extern "C" int fcd_gibbs_accumulate(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg,
-                                    int64_t U, int64_t G, uint32_t *cnt_f, uint32_t *cnt_r, fcd_stream stream) {
-    fcd_geo g;
-    int rc = fcd_geo_check(ctx, Nreg, U, G, 0, g);
-    if (rc) return rc;
-    if (!f_state || !r_bits || !cnt_f || !cnt_r) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_accumulate: null pointer");
-    int64_t blocks = (g.C + 3) / 4;
-    const int64_t cap = (int64_t)ctx->num_cu * 8;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(gibbs_accum_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, f_state, r_bits, g.C,
-                       Nreg * U, g.GW, G, cnt_f, cnt_r);
+                       reinterpret_cast<const long long *>(counts), (double)fcd_tri(Nreg), (double)(Nreg * U), hyper);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
 }
@@ -1504,6 +1394,26 @@ extern "C" int fcd_gibbs_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint6
     if ((cnt_f == nullptr) != (cnt_r == nullptr)) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_tally: cnt_f and cnt_r go together");
     if (!counts && !cnt_f) return FCD_OK;
     return launch_tally(ctx, f_state, r_bits, Nreg, U, G, g, counts, cnt_f, cnt_r, nullptr, nullptr, 0, (hipStream_t)stream);
+}
+
+// pooled counts alone: the tally with no counters (counts[0..7] overwritten)
+extern "C" int fcd_gibbs_stats(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U,
+                               int64_t G, int64_t *counts, fcd_stream stream) {
+    fcd_geo g;
+    int rc = fcd_geo_check(ctx, Nreg, U, G, 0, g);
+    if (rc) return rc;
+    if (!f_state || !r_bits || !counts) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_stats: null pointer");
+    return launch_tally(ctx, f_state, r_bits, Nreg, U, G, g, counts, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
+}
+
+// marginal counters alone: the tally with no counts (cnt_f, cnt_r +=)
+extern "C" int fcd_gibbs_accumulate(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg,
+                                    int64_t U, int64_t G, uint32_t *cnt_f, uint32_t *cnt_r, fcd_stream stream) {
+    fcd_geo g;
+    int rc = fcd_geo_check(ctx, Nreg, U, G, 0, g);
+    if (rc) return rc;
+    if (!f_state || !r_bits || !cnt_f || !cnt_r) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_accumulate: null pointer");
+    return launch_tally(ctx, f_state, r_bits, Nreg, U, G, g, nullptr, cnt_f, cnt_r, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 // The sampler loop of ONE rank between two exchanges of pooled statistics: fcd_gibbs_run (what UnsharedRegionFit(method=
@@ -1588,8 +1498,8 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         if (pooled) {
             rc = fcd_comm_allreduce_counts(ctx, (long long *)ctx->pool_counts, s);
             if (rc) return rc;
-            hipLaunchKernelGGL(gibbs_mstep_kernel, dim3(1), dim3(1), 0, s, (const long long *)ctx->pool_counts, (double)(Nreg * U),
-                               (double)fcd_tri(Nreg), hyper_m);
+            hipLaunchKernelGGL(gibbs_mstep_kernel, dim3(1), dim3(1), 0, s, (const long long *)ctx->pool_counts, (double)g.C,
+                               (double)(Nreg * U), hyper_m);
             FCD_LAUNCH_CHECK();
             if (cts) FCD_HIP_TRY(hipMemcpyAsync(cts, ctx->pool_counts, 8 * sizeof(long long), hipMemcpyDeviceToDevice, s));
         } else if (cts && ctx->comm) {
@@ -1599,7 +1509,7 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         }
         // (f_c, mixture case) counts of the end-of-sweep state (fcd_gibbs_set_pair_accumulator): one launch of its own
         if (pair_acc && st.sweep >= accumulate_from && (st.sweep - accumulate_from) % ctx->pair_every == 0) {
-            rc = fcd_pair_tally_launch(ctx, c.f_state, c.r_bits, Nreg, U, G, g, ctx->pair_acc, s);
+            rc = fcd_pair_tally_launch(ctx, c.f_state, c.r_bits, Nreg, U, G, g, ctx->pair_acc, true, s);
             if (rc) return rc;
         }
         // histograms of sum_n r_nu and sum_u r_nu of the end-of-sweep state (fcd_gibbs_set_count_accumulator): the same

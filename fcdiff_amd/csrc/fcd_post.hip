@@ -11,8 +11,10 @@
 // fit) or the counts of (f_c = k, l_cu = l) over chains and sweeps (sampler, Rao-Blackwellised).
 //
 // Two kernels:
-//   pair_tally_kernel   acc[c,u,k,l] += #{chains with f_c = k and mixture case l at (c,u)} for one state.  The f bytes of
-//                       an edge are read once (three ballots per chain word, kept in LDS); lanes run over patients.
+//   pair_tally_kernel   #{chains with f_c = k and mixture case l at (c,u)} of one state, added to a uint32 acc[c,u,k,l]
+//                       (fcd_gibbs_pair_tally, the sweep loop's accumulator) or stored in / added to an fp64 W[c,u,k,l]
+//                       (fcd_gibbs_pair_counts: the weights of the MCEM theta step).  The f bytes of an edge are read
+//                       once (three ballots per chain word, kept in LDS); lanes run over patients.
 //   posterior_kernel    weights + bt + theta -> the three outputs, one item per (c,u), fp64.
 #include "fcd_common.h"
 
@@ -24,9 +26,11 @@ constexpr int TALLY_WCH = 1024;          // chain words whose f masks one workgr
 // (f == 0, 1, 2; inactive chains cleared) -> LDS.  Step 2: thread = patient; the r words of both endpoints give the three
 // masks of the mixture cases; nine popcounts per chain word summed in registers; one read-modify-write per (c,u).
 // When all the edge's masks fit (GW <= TALLY_WCH) they are made once, whatever U; otherwise once per patient block.
+// acc = accumulate ? acc + counts : counts (uint32: wraps; fp64: the counts are exact integers either way).
+template <typename T>
 __global__ __launch_bounds__(256) void pair_tally_kernel(const uint8_t *__restrict__ f_state, const uint64_t *__restrict__ r_bits,
-                                                         int Nreg, int U, int64_t C, int GW, int64_t G, int wch,
-                                                         uint32_t *__restrict__ acc) {
+                                                         int Nreg, int U, int64_t C, int GW, int64_t G, int wch, bool accumulate,
+                                                         T *__restrict__ acc) {
     extern __shared__ uint64_t fmask[];          // [wch][3]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     const int nwch = (GW + wch - 1) / wch;
@@ -68,9 +72,9 @@ __global__ __launch_bounds__(256) void pair_tally_kernel(const uint8_t *__restri
                 }
             }
             if (u < U) {
-                uint32_t *a = acc + ((int64_t)c * U + u) * 9;
+                T *a = acc + ((int64_t)c * U + u) * 9;
 #pragma unroll
-                for (int j = 0; j < 9; ++j) a[j] += cnt[j];
+                for (int j = 0; j < 9; ++j) a[j] = accumulate ? a[j] + (T)cnt[j] : (T)cnt[j];
             }
         }
     }
@@ -164,19 +168,24 @@ __global__ __launch_bounds__(256) void posterior_kernel(const double *__restrict
 
 }  // namespace
 
+template <typename T>
 int fcd_pair_tally_launch(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
-                          const fcd_geo &g, uint32_t *acc, hipStream_t s) {
+                          const fcd_geo &g, T *acc, bool accumulate, hipStream_t s) {
     const int wch = g.GW < TALLY_WCH ? g.GW : TALLY_WCH;
     const int64_t uthreads = U < 256 ? U : 256;
     const int threads = (int)((uthreads + 63) / 64 * 64);
     int64_t blocks = g.C;
     const int64_t cap = (int64_t)ctx->num_cu * 64;
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(pair_tally_kernel, dim3((unsigned)blocks), dim3(threads), (size_t)wch * 3 * sizeof(uint64_t), s, f_state,
-                       r_bits, (int)Nreg, (int)U, g.C, g.GW, G, wch, acc);
+    hipLaunchKernelGGL(pair_tally_kernel<T>, dim3((unsigned)blocks), dim3(threads), (size_t)wch * 3 * sizeof(uint64_t), s, f_state,
+                       r_bits, (int)Nreg, (int)U, g.C, g.GW, G, wch, accumulate, acc);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
 }
+template int fcd_pair_tally_launch<uint32_t>(fcd_ctx *, const uint8_t *, const uint64_t *, int64_t, int64_t, int64_t,
+                                             const fcd_geo &, uint32_t *, bool, hipStream_t);
+template int fcd_pair_tally_launch<double>(fcd_ctx *, const uint8_t *, const uint64_t *, int64_t, int64_t, int64_t,
+                                           const fcd_geo &, double *, bool, hipStream_t);
 
 extern "C" int fcd_gibbs_pair_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U,
                                     int64_t G, uint32_t *acc, fcd_stream stream) {
@@ -184,7 +193,7 @@ extern "C" int fcd_gibbs_pair_tally(fcd_ctx *ctx, const uint8_t *f_state, const 
     int rc = fcd_geo_check(ctx, Nreg, U, G, 0, g);
     if (rc) return rc;
     if (!f_state || !r_bits || !acc) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_pair_tally: null pointer");
-    return fcd_pair_tally_launch(ctx, f_state, r_bits, Nreg, U, G, g, acc, (hipStream_t)stream);
+    return fcd_pair_tally_launch(ctx, f_state, r_bits, Nreg, U, G, g, acc, true, (hipStream_t)stream);
 }
 
 extern "C" int fcd_gibbs_set_pair_accumulator(fcd_ctx *ctx, uint32_t *acc, int64_t Nreg, int64_t U, int64_t every) {

@@ -45,39 +45,6 @@ __global__ __launch_bounds__(256) void weights_vb_kernel(const double *__restric
     }
 }
 
-// pooled counts of the sampler: W[c,u,k,l] (+)= #{chains of this rank with f_c = k and mixture case l at (c,u)}
-// one wave per (c,u); lanes = chains of a word; ballots over the nine (k,l) combinations
-__global__ __launch_bounds__(256) void pair_counts_kernel(const uint8_t *__restrict__ f_state, const uint64_t *__restrict__ r_bits,
-                                                          int Nreg, int U, int64_t C, int GW, int64_t G, int accumulate,
-                                                          double *__restrict__ W) {
-    const int lane = threadIdx.x & 63;
-    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (item >= C * U) return;
-    const int64_t c = item / U;
-    const int u = (int)(item - c * U);
-    int n, m;
-    fcd_edge_to_pair(c, n, m);
-    uint32_t cnt[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int w = 0; w < GW; ++w) {
-        const uint64_t act = fcd_active_mask(w, G);
-        const uint64_t rn = r_bits[((int64_t)w * Nreg + n) * U + u], rm = r_bits[((int64_t)w * Nreg + m) * U + u];
-        const uint64_t lm[3] = {~(rn | rm), rn & rm, rn ^ rm};       // typical, both anomalous, discordant
-        const int k = f_state[((int64_t)w * C + c) * 64 + lane];
-#pragma unroll
-        for (int kk = 0; kk < 3; ++kk) {
-            const uint64_t fk = __ballot(k == kk) & act;
-#pragma unroll
-            for (int l = 0; l < 3; ++l) cnt[kk * 3 + l] += __popcll(fk & lm[l]);
-        }
-    }
-    if (lane < 9) {
-        double v = 0.0;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) v = (lane == j) ? (double)cnt[j] : v;
-        W[item * 9 + lane] = accumulate ? W[item * 9 + lane] + v : v;
-    }
-}
-
 constexpr int OBJ_BLOCK = 256;
 // MISSING (FCD_DATA_NAN_MISSING): an item with NaN bt adds nothing -- its M_kl = 1 for every (k,l) depends on no
 // parameter, so it contributes ln 1 = 0 to S and 0 to every derivative.  MISSING = false is the kernel without the flag.
@@ -271,18 +238,14 @@ extern "C" int fcd_theta_sub_weights_vb(fcd_ctx *ctx, const double *lq_F, const 
     return FCD_OK;
 }
 
+// the sampler's W: the (f_c, mixture case) counts of pair_tally_kernel (fcd_post.hip), written as fp64
 extern "C" int fcd_gibbs_pair_counts(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U,
                                      int64_t G, int accumulate, double *W, fcd_stream stream) {
     fcd_geo g;
     int rc = fcd_geo_check(ctx, Nreg, U, G, 0, g);
     if (rc) return rc;
     if (!f_state || !r_bits || !W) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_pair_counts: null pointer");
-    const int64_t items = g.C * U;
-    if ((items + 3) / 4 > INT32_MAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_gibbs_pair_counts: C*U too large");
-    hipLaunchKernelGGL(pair_counts_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, (hipStream_t)stream, f_state, r_bits,
-                       (int)Nreg, (int)U, g.C, g.GW, G, accumulate ? 1 : 0, W);
-    FCD_LAUNCH_CHECK();
-    return FCD_OK;
+    return fcd_pair_tally_launch(ctx, f_state, r_bits, Nreg, U, G, g, W, accumulate != 0, (hipStream_t)stream);
 }
 
 extern "C" int fcd_theta_sub_objective_ex(fcd_ctx *ctx, const double *bt, const double *W, int64_t C, int64_t U,

@@ -143,10 +143,14 @@ class GibbsEngine(object):
 
     def import_state(self, f, r):
         t = self.torch
-        f = t.as_tensor(np.ascontiguousarray(f, dtype=np.uint8), device=self.f_state.device)
-        r = t.as_tensor(np.ascontiguousarray(r, dtype=np.uint8), device=self.f_state.device)
-        if tuple(f.shape) != (self.G, self.C) or tuple(r.shape) != (self.G, self.Nreg, self.U):
+        f = np.ascontiguousarray(f, dtype=np.uint8)
+        r = np.ascontiguousarray(r, dtype=np.uint8)
+        if f.shape != (self.G, self.C) or r.shape != (self.G, self.Nreg, self.U):
             raise ValueError("state shapes must be (G, C) and (G, Nreg, U)")
+        if (f > 2).any():
+            raise ValueError("f values must be 0, 1 or 2")
+        f = t.as_tensor(f, device=self.f_state.device)
+        r = t.as_tensor(r, device=self.f_state.device)
         self.ctx.call("fcd_gibbs_import_state", _lib.dptr(f), _lib.dptr(r), self.Nreg, self.U, self.G,
                       _lib.dptr(self.f_state), _lib.dptr(self.r_bits), _lib.stream_ptr())
 

@@ -231,7 +231,8 @@ int fcd_vb_theta_step(fcd_ctx *ctx, const double *lq_F, const double *lq_R, int6
  * theta12_host as in fcd_lik_tables.  Deterministic. */
 int fcd_theta_sub_weights_vb(fcd_ctx *ctx, const double *lq_F, const double *lq_R, int64_t Nreg, int64_t U, double *W,
                              fcd_stream stream);
-/* W[c,u,k,l] (+)= number of this rank's chains with f_c = k and mixture case l at (c,u)  (accumulate != 0: add). */
+/* W[c,u,k,l] (+)= number of this rank's chains with f_c = k and mixture case l at (c,u)  (accumulate != 0: add).
+ * The counts of fcd_gibbs_pair_tally, written as fp64 (exact integers). */
 int fcd_gibbs_pair_counts(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U,
                           int64_t G, int accumulate, double *W, fcd_stream stream);
 int fcd_theta_sub_objective(fcd_ctx *ctx, const double *bt, const double *W, int64_t C, int64_t U,
@@ -293,7 +294,7 @@ int fcd_gibbs_sweeps(fcd_ctx *ctx, const double *S_B, const double *lM, const do
                      uint64_t seed, int64_t sweep0, int64_t n_sweeps, int edge_mode, int64_t *counts,
                      fcd_stream stream);
 /* Pooled sufficient statistics over the G chains (the all-reduce payload):
- * counts[0..7] = {sum r, #f=0, #f=1, #f=2, G, 0, 0, 0} (int64, device, overwritten). */
+ * counts[0..7] = {sum r, #f=0, #f=1, #f=2, G, 0, 0, 0} (int64, device, overwritten).  fcd_gibbs_tally with counts only. */
 int fcd_gibbs_stats(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U,
                     int64_t G, int64_t *counts, fcd_stream stream);
 /* M-step for (pi, gamma) from pooled counts (after the cross-GPU all-reduce): the sample version of
@@ -301,11 +302,12 @@ int fcd_gibbs_stats(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits
 int fcd_gibbs_mstep(fcd_ctx *ctx, const int64_t *counts, int64_t Nreg, int64_t U, double *hyper,
                     fcd_stream stream);
 /* Running marginal counts over sweeps AND chains: cnt_f (C,3) += [f_c = k], cnt_r (Nreg,U) += r_nu
- * (uint32, device); posterior marginals = counts / (sweeps * G). */
+ * (uint32, device, wrapping); posterior marginals = counts / (sweeps * G).  fcd_gibbs_tally with counters only. */
 int fcd_gibbs_accumulate(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg,
                          int64_t U, int64_t G, uint32_t *cnt_f, uint32_t *cnt_r, fcd_stream stream);
 /* fcd_gibbs_stats and fcd_gibbs_accumulate in ONE pass over the state and ONE launch (the pooled sums are kept in
- * accumulators of the context that the kernel itself puts back to zero: no memset):
+ * accumulators of the context that the kernel itself puts back to zero: no memset; the two entry points are this launch
+ * with one half of its output):
  * counts (nullable) is overwritten as by fcd_gibbs_stats; cnt_f / cnt_r (both or neither) are incremented. */
 int fcd_gibbs_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U,
                     int64_t G, int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r, fcd_stream stream);
@@ -414,6 +416,8 @@ int fcd_gibbs_conditionals(fcd_ctx *ctx, const double *S_B, const double *lM, co
 /* Plain views of the packed state: f (G, C) uint8, r (G, Nreg, U) uint8. */
 int fcd_gibbs_export_state(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg,
                            int64_t U, int64_t G, uint8_t *f, uint8_t *r, fcd_stream stream);
+/* ... and back (an r byte other than 0 is 1).  Every f byte must be 0, 1 or 2: the state another value makes is
+ * undefined (the counting entry points may disagree on it).  The sampler itself never produces one. */
 int fcd_gibbs_import_state(fcd_ctx *ctx, const uint8_t *f, const uint8_t *r, int64_t Nreg, int64_t U,
                            int64_t G, uint8_t *f_state, uint64_t *r_bits, fcd_stream stream);
 /* 53-bit uniforms of the counter RNG for a list of (idx, chain, sweep, kind) counters:

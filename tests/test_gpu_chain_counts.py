@@ -3,19 +3,20 @@ The kernels that read the sampler's chains back out, at every chain-word layout 
 
 The sweep kernels are pinned to the C oracle bit for bit elsewhere; this file pins the bookkeeping around them -- the
 pooled counts of the M-step (fcd_gibbs_stats, the tally), the marginal counters behind _lq_F / _lq_R
-(fcd_gibbs_accumulate, the tally, fcd_gibbs_run), the per-chain log-joint and sum r of diagnostics(), the (f, mixture
-case) counts of the MCEM theta step (fcd_gibbs_pair_counts) and import / export of the state -- against a recount on
-the host that uses none of them.  States are planted with NumPy and loaded with import_state; the packed layout is then
-decoded on the host, so import is checked independently of export.
+(fcd_gibbs_accumulate, the tally, fcd_gibbs_run), the M-step itself, the per-chain log-joint and sum r of diagnostics(),
+the (f, mixture case) counts of the MCEM theta step and the connection posteriors (fcd_gibbs_pair_counts,
+fcd_gibbs_pair_tally) and import / export of the state -- against a recount on the host that uses none of them.  States
+are planted with NumPy and loaded with import_state; the packed layout is then decoded on the host, so import is
+checked independently of export.
 
 Chain words: 64 chains per word, GW = ceil(G / 64).  In the last word, lanes >= G % 64 belong to chains that do not
 exist.  The sweeps draw real values there, so every counter must mask them: where G % 64 != 0 each result is computed
 again after those lanes are poisoned (f byte 2, r bit 1) and must not change.
 
-`geometry()` restates the launch formulas of fcd_gibbs.hip / fcd_gibbs_r.hip and each shape asserts the regime it was
-picked for, so that a change of the geometry fails here instead of silently retiring the coverage.  The host oracles
-run on every chain; the pair counts (O.pair_counts, a Python loop over chains) skip the two shapes with more than
-2e7 (chain, edge, patient) items.
+`geometry()` restates the launch formulas of fcd_gibbs.hip / fcd_gibbs_r.hip / fcd_post.hip and each shape asserts the
+regime it was picked for, so that a change of the geometry fails here instead of silently retiring the coverage.  The
+host oracles run on every chain; the pair counts (O.pair_counts, a Python loop over chains) skip the two shapes with
+more than 2e7 (chain, edge, patient) items.
 """
 import numpy as np
 import numpy.testing as nptest
@@ -63,20 +64,14 @@ def _cdiv(a, b):
 def geometry(Nreg, U, G, n_cu):
     """
     Blocks and loop trips of the kernels that read the chains, for (Nreg, U, G) on a device with n_cu CUs, from the
-    launches of fcd_gibbs.hip (fcd_gibbs_stats, fcd_gibbs_accumulate, launch_tally, fcd_gibbs_logjoint,
-    fcd_gibbs_chain_rsum) and fcd_gibbs_r.hip (the packing launch's tally rows).
+    launches of fcd_gibbs.hip (launch_tally, which fcd_gibbs_stats, fcd_gibbs_accumulate, fcd_gibbs_tally and the sweep
+    loop run; fcd_gibbs_logjoint, fcd_gibbs_chain_rsum), fcd_gibbs_r.hip (the packing launch's tally rows) and
+    fcd_post.hip (fcd_pair_tally_launch, which fcd_gibbs_pair_counts and fcd_gibbs_pair_tally run).
     """
     C = Nreg * (Nreg - 1) // 2
     NU = Nreg * U
     GW = _cdiv(G, 64)
-    cap = 8 * n_cu
-    g = dict(C=C, U=U, NU=NU, G=G, GW=GW, tail=G % 64, cap=cap)
-    # gibbs_stats_kernel: min(ceil(GW C / 4), cap) blocks of 4 waves; a wave per (w, c) row, a thread per r word
-    sb = min(_cdiv(GW * C, 4), cap)
-    g.update(stats_blocks=sb, stats_f_passes=_cdiv(GW * C, 4 * sb), stats_r_passes=_cdiv(GW * NU, 256 * sb))
-    # gibbs_accum_kernel: min(ceil(C / 4), cap) blocks of 4 waves; a wave per edge, a thread per (region, patient)
-    ab = min(_cdiv(C, 4), cap)
-    g.update(acc_blocks=ab, acc_f_passes=_cdiv(C, 4 * ab), acc_r_passes=_cdiv(NU, 256 * ab))
+    g = dict(C=C, U=U, NU=NU, G=G, GW=GW, tail=G % 64)
     # gibbs_tally_kernel: min(ceil(C / 64), 2 CU) f blocks of 16 waves x 4 edges; min(ceil(NU / 1024), 64) r blocks, and
     # every f block counts r bits too; with the f half done in the packing launch only the r blocks run
     fb = min(_cdiv(C, 64), 2 * n_cu)
@@ -91,6 +86,13 @@ def geometry(Nreg, U, G, n_cu):
     rs = min(NU, 64)
     g.update(rsum_slices=rs, rsum_passes=_cdiv(NU, rs))
     g["pack_tally"] = C * GW <= PACK_TALLY_MAX
+    # pair_tally_kernel: min(C, 64 CU) workgroups, a workgroup per edge; min(U, 256) threads rounded up to a wave, a
+    # thread per patient; the f masks of min(GW, 1024) chain words in LDS at a time
+    pb = min(C, 64 * n_cu)
+    pt = _cdiv(min(U, 256), 64) * 64
+    pw = min(GW, 1024)
+    g.update(pair_blocks=pb, pair_threads=pt, pair_words=pw, pair_edge_passes=_cdiv(C, pb), pair_u_passes=_cdiv(U, pt),
+             pair_word_rounds=_cdiv(GW, pw))
     return g
 
 
@@ -110,10 +112,8 @@ REGIMES = {
     "tally f wraps, f half in tally": lambda g: g["tally_f_passes"] >= 2 and not g["pack_tally"],
     "tally r wraps": lambda g: g["tally_r_passes"] >= 2,
     "tally r wraps after pack": lambda g: g["tally_r_passes_after_pack"] >= 2 and g["pack_tally"],
-    "stats wraps": lambda g: g["stats_blocks"] == g["cap"] and g["stats_f_passes"] >= 2,
-    "stats r wraps": lambda g: g["stats_r_passes"] >= 2,
-    "accumulate wraps": lambda g: g["acc_blocks"] == g["cap"] and g["acc_f_passes"] >= 2,
-    "accumulate r wraps": lambda g: g["acc_r_passes"] >= 2,
+    "pair edges wrap": lambda g: g["pair_edge_passes"] >= 2,
+    "pair patients wrap": lambda g: g["pair_u_passes"] >= 2,
 }
 
 # (Nreg, U, G, regimes)
@@ -126,9 +126,11 @@ SHAPES = [
     (9, 5, 1025, ("17 words", "partial last word")),
     (13, 3, 2113, ("3 wg groups, last word partial",)),
     (3, 70, 130, ("U > 64", "partial last word", "rsum wraps")),
-    (300, 3, 1024, ("tally f wraps, f half in tally", "stats wraps", "accumulate wraps")),
-    (40, 2000, 63, ("tally r wraps", "tally r wraps after pack", "stats r wraps", "accumulate r wraps", "U > 64",
-                    "partial last word")),
+    (300, 3, 1024, ("tally f wraps, f half in tally", "pair edges wrap")),
+    (40, 2000, 63, ("tally r wraps", "tally r wraps after pack", "U > 64", "pair patients wrap", "partial last word")),
+    # the pair counts where pair_tally_kernel loops, within PAIR_MAX_ITEMS (the two shapes above are not)
+    (200, 2, 65, ("pair edges wrap", "partial last word")),
+    (4, 300, 65, ("pair patients wrap", "U > 64", "partial last word")),
 ]
 SHAPE_IDS = ["%dx%dx%d" % s[:3] for s in SHAPES]
 KINDS = ("random", "f2 r1", "last word only")
@@ -151,7 +153,12 @@ def test_regimes_of_the_named_shapes():
     for (Nreg, U, G, _n, _p, regimes) in RUN_SHAPES:
         check_regimes(256, Nreg, U, G, regimes)
     g = geometry(300, 3, 1024, 256)
-    assert (g["tally_f_blocks"], g["tally_f_passes"], g["stats_f_passes"], g["acc_f_passes"]) == (512, 2, 88, 6)
+    assert (g["tally_f_blocks"], g["tally_f_passes"], g["pair_blocks"], g["pair_edge_passes"]) == (512, 2, 16384, 3)
+    g = geometry(200, 2, 65, 256)
+    assert (g["pair_blocks"], g["pair_edge_passes"], g["pair_threads"], g["pair_words"]) == (16384, 2, 64, 2)
+    assert 65 * g["C"] * 2 <= PAIR_MAX_ITEMS
+    g = geometry(4, 300, 65, 256)
+    assert (g["pair_blocks"], g["pair_threads"], g["pair_u_passes"], g["pair_word_rounds"]) == (6, 256, 2, 1)
     g = geometry(200, 50, 16384, 256)                   # cfg3: one trip of the tally's f loop, one wg group
     assert (g["tally_f_passes"], g["tally_r_passes"], g["wg_groups"], g["pack_tally"]) == (1, 1, 16, False)
 
@@ -251,6 +258,22 @@ def test_import_layout_and_round_trip(env, Nreg, U, G, regimes, kind):
     nptest.assert_array_equal(re_, r)
 
 
+def test_import_refuses_f_above_2(env):
+    """f bytes are 0, 1 or 2: import_state refuses any other value before it touches the device state."""
+    (Nreg, U, G) = (5, 3, 63)
+    (f, r) = planted(Nreg, U, G, "random", seed=5)
+    eng = zero_engine(env, Nreg, U, G)
+    eng.import_state(f, r)
+    (fs, rb) = (eng.f_state.cpu().numpy().copy(), eng.r_bits.cpu().numpy().copy())
+    for bad in (3, 255):
+        f2 = f.copy()
+        f2[G - 1, 0] = bad
+        with pytest.raises(ValueError):
+            eng.import_state(f2, r)
+    nptest.assert_array_equal(eng.f_state.cpu().numpy(), fs)
+    nptest.assert_array_equal(eng.r_bits.cpu().numpy(), rb)
+
+
 # ------------------------------------------------------------------------------------------------
 # stats, accumulate, tally, chain sums, pair counts against the recount
 # ------------------------------------------------------------------------------------------------
@@ -292,6 +315,10 @@ def run_counters(env, eng, rng_seed, k_acc=2):
         out["pair"] = eng.pair_counts().cpu().numpy()
         W0 = t.as_tensor(rng.integers(0, 1000, size=(eng.C, eng.U, 3, 3)).astype(np.float64), device="cuda")
         out["pair_acc"] = eng.pair_counts(W0.clone(), accumulate=True).cpu().numpy() - W0.cpu().numpy()
+        # uint32 += on top of existing values, some above 2^31
+        A0 = rng.integers(0, (1 << 32) - 1 - eng.G, size=(eng.C, eng.U, 3, 3), dtype=np.int64)
+        A0.flat[0] = (1 << 32) - 1 - eng.G
+        out["pair_tally"] = as_u32(eng.pair_tally(from_u32(env, A0))) - A0
     env.ctx.check_device()
     return out
 
@@ -301,9 +328,9 @@ def run_counters(env, eng, rng_seed, k_acc=2):
 def test_counters_against_recount(env, Nreg, U, G, regimes, kind):
     """
     stats(), accumulate() x 2 on non-zero uint32 counters, tally() as counts only / counters only / both / again (its
-    context accumulators are reset: the same counts), r_sums() and pair_counts() (plain and accumulate=True on top of
-    existing values) against a recount of the planted state; where the last word is partial, the same again with its
-    chain-less lanes poisoned, bit for bit.
+    context accumulators are reset: the same counts), r_sums(), pair_counts() (plain and accumulate=True on top of
+    existing values) and pair_tally() (on top of existing uint32 values) against a recount of the planted state; where
+    the last word is partial, the same again with its chain-less lanes poisoned, bit for bit.
     Regression (40x2000x63): the tally's grid held only its f blocks where ceil(NU / 1024) r blocks were more; the r
     sites of the missing blocks went uncounted and no block drew the last ticket, so counts were never written.
     """
@@ -330,6 +357,7 @@ def test_counters_against_recount(env, Nreg, U, G, regimes, kind):
         W = env.O.pair_counts(f, r)
         nptest.assert_array_equal(clean["pair"], W, err_msg="pair_counts")
         nptest.assert_array_equal(clean["pair_acc"], W, err_msg="pair_counts(accumulate=True)")
+        nptest.assert_array_equal(clean["pair_tally"], W, err_msg="pair_tally")
     if G % 64:
         poison(env, eng)
         dirty = run_counters(env, eng, rng_seed=G)
@@ -436,8 +464,8 @@ def test_run_counts_against_oracle_chains(env, Nreg, U, G, n_sweeps, in_pack, re
     """
     fcd_gibbs_run(want_counts, accumulate_from = 0, an M-step after the last sweep) from the device's own init, whose
     chain-less lanes hold real draws: counts of the last sweep, cnt_f / cnt_r summed over all sweeps and the M-step's
-    hyper block against a recount of the C oracle's chains after the same sweeps.  The context's counters say where
-    the f half of each sweep's tally ran.
+    hyper block against a recount of the C oracle's chains after the same sweeps; fcd_gibbs_mstep on the returned counts
+    writes the same hyper block, byte for byte.  The context's counters say where the f half of each sweep's tally ran.
     """
     g = check_regimes(env.n_cu, Nreg, U, G, regimes)
     (m, S_B, lM, S_B_d, lM_d) = tables_for(env, Nreg, 3, U, seed=Nreg + U)
@@ -460,7 +488,8 @@ def test_run_counts_against_oracle_chains(env, Nreg, U, G, n_sweeps, in_pack, re
         sum_f += cnt_f
         sum_r += cnt_r
     (n_pack0, n_in0) = (env.ctx.stat("pack_launches"), env.ctx.stat("tally_f_in_pack"))
-    got = eng.run(0, n_sweeps, mstep_every=n_sweeps, accumulate_from=0, want_counts=True).cpu().numpy()
+    cts = eng.run(0, n_sweeps, mstep_every=n_sweeps, accumulate_from=0, want_counts=True)
+    got = cts.cpu().numpy()
     n_in = env.ctx.stat("tally_f_in_pack") - n_in0
     assert n_in == in_pack, "the packing launch carried the f half in %d sweeps, expected %d" % (n_in, in_pack)
     assert env.ctx.stat("pack_launches") - n_pack0 >= n_in
@@ -474,3 +503,5 @@ def test_run_counts_against_oracle_chains(env, Nreg, U, G, n_sweeps, in_pack, re
     h = eng.hyper.cpu().numpy()
     nptest.assert_allclose(h[0:3], np.log(gamma_h), rtol=1e-14, atol=0)
     nptest.assert_allclose(h[3:5], [np.log(1.0 - pi_h), np.log(pi_h)], rtol=1e-14, atol=0)
+    eng.mstep(cts)
+    assert eng.hyper.cpu().numpy().tobytes() == h.tobytes(), "fcd_gibbs_mstep differs from the tally's M-step"
