@@ -23,6 +23,7 @@ EDGE_REFERENCE = 0
 EDGE_SYMMETRIC = 1
 EDGE_MODES = {"reference": EDGE_REFERENCE, "symmetric": EDGE_SYMMETRIC}
 FCD_DATA_NAN_MISSING = 1      # flags of the *_ex entry points: NaN in b / bt is unobserved and integrated out
+FCD_W_PER_EDGE = 2            # theta objectives: W is (C, 1, 3, 3), one table per edge for every patient (shared regions)
 ABI_VERSION = 4
 
 _p = C.c_void_p
@@ -57,7 +58,9 @@ SIGNATURES = {
     "fcd_hyper_set": (_int, [_p, _p, C.POINTER(_dbl), C.POINTER(_dbl), _p]),
     "fcd_lik_tables": (_int, [_p, _p, _p, _i64, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _p, _p]),
     "fcd_lik_tables_ex": (_int, [_p, _p, _p, _i64, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _p, _int, _p, _p]),
+    "fcd_lik_shared_tables": (_int, [_p, _p, _p, _i64, _i64, _i64, C.POINTER(_dbl), _p, _p, _int, _p, _p]),
     "fcd_model_sample": (_int, [_p, C.POINTER(_dbl), _i64, _i64, _i64, _u64, _p, _p, _p, _p, _p, _p, _p]),
+    "fcd_model_sample_shared": (_int, [_p, C.POINTER(_dbl), _i64, _i64, _i64, _u64, _p, _p, _p, _p, _p, _p, _p]),
     "fcd_corr_edges": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
     "fcd_vb_update_qF": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
     "fcd_vb_update_qR": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _p, _p]),

@@ -63,6 +63,34 @@ __global__ __launch_bounds__(256) void sample_patients_kernel(SampTheta th, uint
     bt[i] = fmin(fmax(v, -1.0), 1.0);
 }
 
+// The shared-region model: r (Nreg,) is drawn once per region (the counter of region n is the one of site (n, 0) at
+// U = 1) and every patient's t, f~ and bt read it.  Apart from rn, rm the item is sample_patients_kernel's.
+__global__ __launch_bounds__(256) void sample_shared_patients_kernel(SampTheta th, uint64_t seed, int Nreg, int U, int64_t C,
+                                                                     uint8_t *__restrict__ r, uint8_t *__restrict__ t,
+                                                                     uint8_t *__restrict__ f, uint8_t *__restrict__ ft,
+                                                                     double *__restrict__ bt) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < Nreg) r[i] = (uint8_t)draw_r(th, seed, (int)i, 0, 1);
+    if (i >= C * U) return;
+    const int64_t c = i / U;
+    const int u = (int)(i - c * U);
+    int n, m;
+    fcd_edge_to_pair(c, n, m);
+    const int rn = draw_r(th, seed, n, 0, 1), rm = draw_r(th, seed, m, 0, 1);
+    int tt = rn & rm;
+    if (rn ^ rm) tt = unif(seed, (uint32_t)i, (uint32_t)(i >> 32), K_T, 0) < th.eta;
+    const int fc = draw_f(th, seed, c);
+    if (u == 0) f[c] = (uint8_t)fc;
+    const double keep = tt ? th.epsilon : 1.0 - th.epsilon;
+    const double x = unif(seed, (uint32_t)i, (uint32_t)(i >> 32), K_FT, 0);
+    int k = fc;
+    if (x >= keep) k = (fc + 1 + ((x - keep) >= 0.5 * (1.0 - keep) ? 1 : 0)) % 3;
+    t[i] = (uint8_t)tt;
+    ft[i] = (uint8_t)k;
+    const double v = th.mu[k] + th.sigma[k] * normal(seed, i, K_BT);
+    bt[i] = fmin(fmax(v, -1.0), 1.0);
+}
+
 __global__ __launch_bounds__(256) void sample_healthy_kernel(SampTheta th, uint64_t seed, int H, int64_t C, double *__restrict__ b) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= C * H) return;
@@ -71,13 +99,11 @@ __global__ __launch_bounds__(256) void sample_healthy_kernel(SampTheta th, uint6
     b[i] = fmin(fmax(v, -1.0), 1.0);
 }
 
-}  // namespace
-
-extern "C" int fcd_model_sample(fcd_ctx *ctx, const double *theta, int64_t Nreg, int64_t H, int64_t U, uint64_t seed, uint8_t *r,
-                                uint8_t *t, uint8_t *f, uint8_t *f_tilde, double *b, double *b_tilde, fcd_stream stream) {
-    if (!ctx || !theta || !r || !t || !f || !f_tilde || !b || !b_tilde) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_model_sample: null pointer");
+int model_sample(fcd_ctx *ctx, bool shared, const double *theta, int64_t Nreg, int64_t H, int64_t U, uint64_t seed, uint8_t *r, uint8_t *t, uint8_t *f, uint8_t *f_tilde, double *b, double *b_tilde,
+                 fcd_stream stream) {
+    if (!ctx || !theta || !r || !t || !f || !f_tilde || !b || !b_tilde) return fcd_fail(ctx, FCD_ERR_ARG, shared ? "fcd_model_sample_shared: null pointer" : "fcd_model_sample: null pointer");
     if (Nreg < 2 || H < 1 || U < 1) return fcd_fail(ctx, FCD_ERR_SHAPE, "need Nreg >= 2, H >= 1, U >= 1 (Nreg=%lld, U=%lld)", Nreg, U);
-    if (Nreg > 46340 || U > INT32_MAX || H > INT32_MAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_model_sample: shape too large");
+    if (Nreg > 46340 || U > INT32_MAX || H > INT32_MAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, shared ? "fcd_model_sample_shared: shape too large" : "fcd_model_sample: shape too large");
     SampTheta th;
     th.pi = theta[0];
     th.eta = theta[1];
@@ -91,12 +117,31 @@ extern "C" int fcd_model_sample(fcd_ctx *ctx, const double *theta, int64_t Nreg,
     }
     const int64_t C = fcd_tri(Nreg);
     int64_t items = C * U;
-    if (Nreg * U > items) items = Nreg * U;
+    const int64_t n_r = shared ? Nreg : Nreg * U;
+    if (n_r > items) items = n_r;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(sample_patients_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, th, seed, (int)Nreg, (int)U, C,
-                       r, t, f, f_tilde, b_tilde);
+    if (shared)
+        hipLaunchKernelGGL(sample_shared_patients_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, th, seed,
+                           (int)Nreg, (int)U, C, r, t, f, f_tilde, b_tilde);
+    else
+        hipLaunchKernelGGL(sample_patients_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, th, seed, (int)Nreg,
+                           (int)U, C, r, t, f, f_tilde, b_tilde);
     FCD_LAUNCH_CHECK();
     hipLaunchKernelGGL(sample_healthy_kernel, dim3((unsigned)((C * H + 255) / 256)), dim3(256), 0, s, th, seed, (int)H, C, b);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
+}
+
+}  // namespace
+
+extern "C" int fcd_model_sample(fcd_ctx *ctx, const double *theta, int64_t Nreg, int64_t H, int64_t U, uint64_t seed, uint8_t *r,
+                                uint8_t *t, uint8_t *f, uint8_t *f_tilde, double *b, double *b_tilde, fcd_stream stream) {
+    return model_sample(ctx, false, theta, Nreg, H, U, seed, r, t, f, f_tilde, b, b_tilde, stream);
+}
+
+// the shared-region model: r (Nreg,), one draw per region for all patients
+extern "C" int fcd_model_sample_shared(fcd_ctx *ctx, const double *theta, int64_t Nreg, int64_t H, int64_t U, uint64_t seed,
+                                       uint8_t *r, uint8_t *t, uint8_t *f, uint8_t *f_tilde, double *b, double *b_tilde,
+                                       fcd_stream stream) {
+    return model_sample(ctx, true, theta, Nreg, H, U, seed, r, t, f, f_tilde, b, b_tilde, stream);
 }

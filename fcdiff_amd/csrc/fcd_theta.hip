@@ -48,9 +48,19 @@ __global__ __launch_bounds__(256) void weights_vb_kernel(const double *__restric
 constexpr int OBJ_BLOCK = 256;
 // MISSING (FCD_DATA_NAN_MISSING): an item with NaN bt adds nothing -- its M_kl = 1 for every (k,l) depends on no
 // parameter, so it contributes ln 1 = 0 to S and 0 to every derivative.  MISSING = false is the kernel without the flag.
-template <bool MISSING>
+// PER_EDGE (FCD_W_PER_EDGE): W is (C,1,3,3) and item i = c*U + u reads W[c] -- the shared-region fit, whose weights do
+// not depend on the patient while the data does.  U travels in the parameter block (SubThetaEdge), so the kernel
+// arguments of the PER_EDGE = false forms are what they were.
+struct SubThetaEdge : SubTheta {
+    int U;
+};
+template <bool PER_EDGE> struct SubThetaOf { typedef SubTheta type; };
+template <> struct SubThetaOf<true> { typedef SubThetaEdge type; };
+
+template <bool MISSING, bool PER_EDGE = false>
 __global__ __launch_bounds__(OBJ_BLOCK) void theta_sub_kernel(const double *__restrict__ bt, const double *__restrict__ W,
-                                                              int64_t n_items, SubTheta th, double *__restrict__ partial) {
+                                                              int64_t n_items, typename SubThetaOf<PER_EDGE>::type th,
+                                                              double *__restrict__ partial) {
     __shared__ double red[OBJ_BLOCK / 64][3];
     double S = 0.0, gh = 0.0, ge = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * OBJ_BLOCK + threadIdx.x; i < n_items; i += (int64_t)gridDim.x * OBJ_BLOCK) {
@@ -63,12 +73,14 @@ __global__ __launch_bounds__(OBJ_BLOCK) void theta_sub_kernel(const double *__re
             N[k] = exp(-(z * z) / 2.0) / kSqrt2Pi / th.sigma[k];                    // fit.py:115
         }
         const double others[3] = {N[1] + N[2], N[0] + N[2], N[0] + N[1]};
+        int64_t wi = i;
+        if constexpr (PER_EDGE) wi = i / th.U;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const double slope = N[k] - 0.5 * others[k];                            // dM/d eps
 #pragma unroll
             for (int l = 0; l < 3; ++l) {
-                const double w = W[i * 9 + k * 3 + l];
+                const double w = W[wi * 9 + k * 3 + l];
                 if (w != 0.0) {                                                     // a zero weight never touches ln 0
                     const double M = th.eps[l] * N[k] + (1 - th.eps[l]) * 0.5 * others[k];      // fit.py:430
                     S += w * log(M);
@@ -107,8 +119,9 @@ __global__ __launch_bounds__(OBJ_BLOCK) void theta_sub_kernel(const double *__re
 // L-BFGS-B needs.
 // MISSING (FCD_DATA_NAN_MISSING): a NaN bt item adds nothing to any sum (M = 1 whatever theta), a NaN b adds nothing to
 // the ln N / mu / sigma^2 terms (the density of an unobserved value integrates to 1).
+// PER_EDGE (FCD_W_PER_EDGE): W is (C,1,3,3), one weight table per edge for all U patients (shared-region fit).
 // ---------------------------------------------------------------------------------------------
-template <bool MISSING>
+template <bool MISSING, bool PER_EDGE = false>
 __global__ __launch_bounds__(OBJ_BLOCK) void theta_full_kernel(const double *__restrict__ b, const double *__restrict__ bt,
                                                                const double *__restrict__ W, int64_t C, int H, int U,
                                                                SubTheta th, double *__restrict__ partial) {
@@ -134,12 +147,13 @@ __global__ __launch_bounds__(OBJ_BLOCK) void theta_full_kernel(const double *__r
             dNs[k] = N[k] * ((d * d - s2[k]) / (2.0 * s2[k] * s2[k]));              // d N / d sigma^2
         }
         const double others[3] = {N[1] + N[2], N[0] + N[2], N[0] + N[1]};
+        const int64_t wi = PER_EDGE ? i / U : i;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const double slope = N[k] - 0.5 * others[k];
 #pragma unroll
             for (int l = 0; l < 3; ++l) {
-                const double w = W[i * 9 + k * 3 + l];
+                const double w = W[wi * 9 + k * 3 + l];
                 if (w != 0.0) {
                     const double M = th.eps[l] * N[k] + (1 - th.eps[l]) * 0.5 * others[k];
                     acc[0] += w * log(M);
@@ -163,7 +177,7 @@ __global__ __launch_bounds__(OBJ_BLOCK) void theta_full_kernel(const double *__r
             const int64_t c = i / H;
             const double x = b[i];
             if (MISSING && __builtin_isnan(x)) continue;
-            const double *w0 = W + c * U * 9;              // patient 0 of the edge: sum over l = weight of f_c = k
+            const double *w0 = W + c * (PER_EDGE ? 1 : U) * 9;   // patient 0 of the edge: sum over l = weight of f_c = k
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const double wF = (w0[k * 3 + 0] + w0[k * 3 + 1]) + w0[k * 3 + 2];
@@ -251,8 +265,10 @@ extern "C" int fcd_gibbs_pair_counts(fcd_ctx *ctx, const uint8_t *f_state, const
 extern "C" int fcd_theta_sub_objective_ex(fcd_ctx *ctx, const double *bt, const double *W, int64_t C, int64_t U,
                                           const double *theta, int flags, double *out3, fcd_stream stream) {
     if (!ctx || !bt || !W || !theta || !out3) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_sub_objective: null pointer");
-    if (flags & ~FCD_DATA_NAN_MISSING) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_sub_objective_ex: unknown flags 0x%x", flags);
+    if (flags & ~(FCD_DATA_NAN_MISSING | FCD_W_PER_EDGE))
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_sub_objective_ex: unknown flags 0x%x", flags);
     if (C < 1 || U < 1) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_sub_objective: C=%lld U=%lld must be >= 1", C, U);
+    if ((flags & FCD_W_PER_EDGE) && U > INT32_MAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_theta_sub_objective_ex: U too large");
     SubTheta th;
     const double eta = theta[1], epsilon = theta[2];
     for (int k = 0; k < 3; ++k) {
@@ -275,7 +291,17 @@ extern "C" int fcd_theta_sub_objective_ex(fcd_ctx *ctx, const double *bt, const 
     int rc = fcd_ws_reserve(ctx, (size_t)blocks * 4 * sizeof(double));
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (flags & FCD_DATA_NAN_MISSING)
+    if (flags & FCD_W_PER_EDGE) {
+        SubThetaEdge te;
+        static_cast<SubTheta &>(te) = th;
+        te.U = (int)U;
+        if (flags & FCD_DATA_NAN_MISSING)
+            hipLaunchKernelGGL((theta_sub_kernel<true, true>), dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, bt, W, n_items, te,
+                               (double *)ctx->ws);
+        else
+            hipLaunchKernelGGL((theta_sub_kernel<false, true>), dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, bt, W, n_items, te,
+                               (double *)ctx->ws);
+    } else if (flags & FCD_DATA_NAN_MISSING)
         hipLaunchKernelGGL(theta_sub_kernel<true>, dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, bt, W, n_items, th,
                            (double *)ctx->ws);
     else
@@ -296,7 +322,8 @@ extern "C" int fcd_theta_full_objective_ex(fcd_ctx *ctx, const double *b, const 
                                            int64_t H, int64_t U, const double *theta, int flags, double *out9,
                                            fcd_stream stream) {
     if (!ctx || !bt || !W || !theta || !out9) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_full_objective: null pointer");
-    if (flags & ~FCD_DATA_NAN_MISSING) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_full_objective_ex: unknown flags 0x%x", flags);
+    if (flags & ~(FCD_DATA_NAN_MISSING | FCD_W_PER_EDGE))
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_full_objective_ex: unknown flags 0x%x", flags);
     if (C < 1 || U < 1 || (b && H < 1) || H > INT32_MAX || U > INT32_MAX)
         return fcd_fail(ctx, FCD_ERR_ARG, "fcd_theta_full_objective: C=%lld U=%lld must be >= 1", C, U);
     SubTheta th;
@@ -322,7 +349,14 @@ extern "C" int fcd_theta_full_objective_ex(fcd_ctx *ctx, const double *b, const 
     int rc = fcd_ws_reserve(ctx, (size_t)blocks * 12 * sizeof(double));
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (flags & FCD_DATA_NAN_MISSING)
+    if (flags & FCD_W_PER_EDGE) {
+        if (flags & FCD_DATA_NAN_MISSING)
+            hipLaunchKernelGGL((theta_full_kernel<true, true>), dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, b, bt, W, C, (int)H,
+                               (int)U, th, (double *)ctx->ws);
+        else
+            hipLaunchKernelGGL((theta_full_kernel<false, true>), dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, b, bt, W, C, (int)H,
+                               (int)U, th, (double *)ctx->ws);
+    } else if (flags & FCD_DATA_NAN_MISSING)
         hipLaunchKernelGGL(theta_full_kernel<true>, dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, b, bt, W, C, (int)H, (int)U, th,
                            (double *)ctx->ws);
     else

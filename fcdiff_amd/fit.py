@@ -1,6 +1,8 @@
 """
 Fits models to observed correlations -- the MI355X build of fcdiff/fit.py.
 
+`SharedRegionFit` (below) fits the shared-region model through the same machinery at one patient.
+
 `UnsharedRegionFit` keeps the reference's surface (fcdiff/fit.py:12-54): attributes `model, b, bt,
 max_iters=10, rel_tol=1e-5, energy`, private state `_lq_R (N,U,2), _lq_F (C,1,3), _lp_B_g_F (C,H,3),
 _p_Bt_g_Ft (C,U,3), _lM (C,U,3,3)` readable/assignable as NumPy arrays, `run()` and the private methods
@@ -508,15 +510,19 @@ class UnsharedRegionFit(object):
         if self.theta_sub_params == "all":
             # the reference's commented-out intent (fit.py:232-237, 250-251, 266-267, 282): mu and sigma too
             (eta, epsilon, mu, sigma, info) = minimize_theta_full(self._context(), self._d["b"], self._d["bt"], W, self.model,
-                                                                  missing_data=self.missing_data)
+                                                                  **self._theta_sub_flags())
             self.model.mu, self.model.sigma = mu, sigma
         elif self.theta_sub_params == "eta_epsilon":
             (eta, epsilon, info) = minimize_theta_sub(self._context(), self._d["bt"], W, self.model,
-                                                      missing_data=self.missing_data)
+                                                      **self._theta_sub_flags())
         else:
             raise ValueError("theta_sub_params must be 'eta_epsilon' or 'all'")
         self.model.eta, self.model.epsilon = eta, epsilon
         self._theta_sub_info = info
+
+    def _theta_sub_flags(self):
+        """How the theta_sub objectives read W and the data (keyword arguments of minimize_theta_sub / _full)."""
+        return {"missing_data": self.missing_data}
 
     def _theta_sub_weights(self):
         """W[c,u,k,l] = q_F[c,k] * w_l(c,u) on the device (fit.py:382-406, 508-510)."""
@@ -590,11 +596,11 @@ class UnsharedRegionFit(object):
                 if self.theta_sub_params == "all":
                     (eta, epsilon, mu, sigma, _info) = minimize_theta_full(self._context(), self._d["b"], self._d["bt"], W,
                                                                            self.model, reduce=allreduce_counts,
-                                                                           missing_data=self.missing_data)
+                                                                           **self._theta_sub_flags())
                     self.model.mu, self.model.sigma = mu, sigma
                 else:
                     (eta, epsilon, _info) = minimize_theta_sub(self._context(), self._d["bt"], W, self.model,
-                                                               reduce=allreduce_counts, missing_data=self.missing_data)
+                                                               reduce=allreduce_counts, **self._theta_sub_flags())
                 self.model.eta, self.model.epsilon = eta, epsilon
                 self._update_lps()            # tables follow theta_sub ...
                 e.refresh_tables()            # ... and so do the sampler's two difference tables
@@ -796,6 +802,164 @@ class UnsharedRegionFit(object):
         return bt
 
 
+class SharedRegionFit(UnsharedRegionFit):
+    """
+    Fits the shared-region model (fcdiff_amd.SharedRegionModel: one set of anomalous regions r_n for every patient) to
+    correlations.  Same attributes and knobs as UnsharedRegionFit; edge ids are always 'symmetric'.
+
+    With T and F~ integrated out per patient, the collapsed joint is
+        ln p(b, bt, f, r) = sum_n ln pi_{r_n} + sum_c [ ln gamma_{f_c} + S_B[c, f_c] + L[c, f_c, l(r_n, r_m)] ],
+        L[c, k, l] = sum_u lM[c, u, k, l],
+    the collapsed joint of the UNSHARED model with one patient whose table is L.  So run() builds S_B and L in one launch
+    (fcd_lik_shared_tables, nothing of size C*U) and then runs the unshared fit's own VB loop or sampler at U = 1 on L:
+    `_lq_R` is (N, 1, 2) (the population column), `_lq_F` (C, 1, 3), `_lM` holds L as (C, 1, 3, 3).  `energy` is minus
+    the ELBO of p(b, bt) under this model, on the unshared fit's scale.  The theta_sub step weights every patient's item
+    with its edge's (C, 1, 3, 3) weights (FCD_W_PER_EDGE).
+    """
+
+    def __init__(self):
+        super(SharedRegionFit, self).__init__()
+        self.edge_index = "symmetric"
+
+    def _edge_mode(self):
+        if self.edge_index not in (None, "symmetric"):
+            if self.edge_index == "reference":
+                raise ValueError("edge_index 'reference' (quirk Q1) exists only for parity with the reference's unshared "
+                                 "fit; SharedRegionFit uses 'symmetric'")
+            raise ValueError("edge_index must be 'symmetric' for SharedRegionFit")
+        return "symmetric"
+
+    def run(self):
+        """Builds S_B and L, then the VB loop or the sampler at U = 1 (see the class docstring)."""
+        self._edge_mode()
+        super(SharedRegionFit, self).run()
+
+    def _init_lps(self, N, H, U):
+        t = self._torch()
+        dev = self._dev()
+        C = util.N_to_C(N)
+        self._d["lq_R"] = t.full((N, 1, 2), -np.log(2), dtype=t.float64, device=dev)
+        self._d["lq_F"] = t.full((C, 1, 3), -np.log(3), dtype=t.float64, device=dev)
+        self._d["S_B"] = t.full((C, 3), float(H), dtype=t.float64, device=dev)
+        self._d["lM"] = t.zeros((C, 1, 3, 3), dtype=t.float64, device=dev)
+        self._d["lpB"] = None
+        self._d["pBt"] = None
+        self._d.pop("data_key", None)
+        self._HU = (H, U)
+
+    def _tables(self, full):
+        """S_B (C,3) and L (C,1,3,3) from the current parameters: kernel K_lik_shared (ONE launch, no C*U buffer)."""
+        t = self._torch()
+        dev = self._dev()
+        b = np.ascontiguousarray(self.b, dtype=np.float64)
+        bt = np.ascontiguousarray(self.bt, dtype=np.float64)
+        (C, H) = b.shape
+        U = bt.shape[1]
+        key = (self._array_key(self.b), self._array_key(self.bt), self._data_digest(b, self.data_check),
+               self._data_digest(bt, self.data_check))
+        uploaded = self._d.get("data_key") != key
+        if uploaded:
+            self._d["b"], self._d["bt"] = self._up(b), self._up(bt)
+            self._d["data_key"] = key
+        # the buffers are kept when their shape holds: a sampler built on them reads the new tables after refresh_tables()
+        if self._d.get("S_B") is None or tuple(self._d["S_B"].shape) != (C, 3):
+            self._d["S_B"] = t.empty((C, 3), dtype=t.float64, device=dev)
+        if self._d.get("lM") is None or tuple(self._d["lM"].shape) != (C, 1, 3, 3):
+            self._d["lM"] = t.empty((C, 1, 3, 3), dtype=t.float64, device=dev)
+        (th, _th) = _lib.dbl_array(self.model.theta())
+        count = False
+        if self.missing_data:
+            count = uploaded or not self._d.get("n_missing_valid")
+            if self._d.get("n_missing") is None:
+                self._d["n_missing"] = t.zeros(2, dtype=t.int64, device=dev)
+        self._context().call("fcd_lik_shared_tables", _lib.dptr(self._d["b"]), _lib.dptr(self._d["bt"]), C, H, U, th,
+                             _lib.dptr(self._d["S_B"]), _lib.dptr(self._d["lM"]), self._flags(),
+                             _lib.dptr(self._d["n_missing"] if count else None), _lib.stream_ptr())
+        self._d["n_missing_valid"] = bool(self.missing_data)
+        self._d["lpB"], self._d["pBt"] = None, None     # the per-item tables are never made here
+
+    def _theta_sub_flags(self):
+        return {"missing_data": self.missing_data, "per_edge": True}
+
+    def _run_gibbs(self, N, U):
+        super(SharedRegionFit, self)._run_gibbs(N, 1)
+
+    def _patients(self):
+        bt = self._d.get("bt")
+        return int(bt.shape[1]) if bt is not None else int(np.asarray(self.bt).shape[1])
+
+    # ------------------------------------------------------------------ posteriors
+    def region_posterior(self):
+        """(N,) P(r_n = 1 | data) from the last run(): q(r_n = 1) (vb) or the chains' frequency (gibbs)."""
+        lq_R = self._lq_R
+        if lq_R is None or lq_R.ndim != 3 or lq_R.shape[1] != 1:
+            raise ValueError("region_posterior() needs a run(): _lq_R must be (N, 1, 2)")
+        return np.exp(lq_R[:, 0, 1])
+
+    def connection_posterior(self):
+        """
+        Per connection and patient, as UnsharedRegionFit.connection_posterior(): p_T (C, U), p_F_tilde (C, U, 3),
+        p_changed (C, U).  Given (f_c, the mixture case of the shared r) each patient's T and F~ have the closed-form law of
+        the unshared model, so the fit's weights are broadcast to every patient:
+          method='vb'     q_R (N, 1, 2) broadcast to (N, U, 2): exact under the mean field;
+          method='gibbs'  the (C, 1, 3, 3) counts of (f_c, mixture case) broadcast to (C, U, 3, 3) (needs
+                          connection_marginals = True before run()).
+        """
+        t = self._torch()
+        if self.model is None or self.bt is None:
+            raise ValueError("connection_posterior() needs a model and bt: call run() first")
+        U = self._patients()
+        if self.method == "gibbs":
+            cnt = self.connection_counts
+            if cnt is None:
+                raise ValueError("no connection counts: set connection_marginals = True before run(method='gibbs')")
+            cnt = np.asarray(cnt)
+            if int(cnt[0, 0].sum()) == 0:
+                raise ValueError("no sweep was accumulated into the connection counts (n_sweeps <= burn_in?)")
+            if int(cnt.max()) > PAIR_COUNT_MAX:
+                raise ValueError("pooled connection counts exceed uint32; raise connection_every")
+            C = cnt.shape[0]
+            N = int(util.C_to_N(C))
+            wide = np.ascontiguousarray(np.broadcast_to(cnt.astype(np.uint32), (C, U, 3, 3)))
+            counts = t.as_tensor(wide.view(np.int32), device=self._dev())
+            return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), counts=counts,
+                                  missing_data=self.missing_data)
+        if self.method != "vb":
+            raise ValueError("method must be 'vb' or 'gibbs'")
+        (N, C, _one) = self._check_state(need=("lq_R", "lq_F"))
+        lq_R = self._d["lq_R"].expand(N, U, 2).contiguous()
+        return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), lq_F=self._d["lq_F"],
+                              lq_R=lq_R, missing_data=self.missing_data)
+
+    def anomaly_count_posterior(self):
+        """
+        The law of the number of anomalous regions sum_n r_n, from the last run():
+            p_count (N+1,)  P(sum_n r_n = k | data);   p_any  P(some region is anomalous) = 1 - p_count[0]
+          method='vb'     Poisson-binomial law of q(r_n) (fcd_vb_count_posterior at U = 1);
+          method='gibbs'  the histogram over chains and sweeps (needs anomaly_counts = True before run()).
+        """
+        if self.model is None or self.bt is None:
+            raise ValueError("anomaly_count_posterior() needs a model and bt: call run() first")
+        if self.method == "gibbs":
+            hp = self.patient_count_hist
+            if hp is None:
+                raise ValueError("no anomaly-count histograms: set anomaly_counts = True before run(method='gibbs')")
+            hp = np.asarray(hp, dtype=np.float64)[0]
+            if hp.sum() == 0:
+                raise ValueError("no sweep was accumulated into the anomaly-count histograms (n_sweeps <= burn_in?)")
+            p = hp / hp.sum()
+        elif self.method == "vb":
+            (N, _C, _one) = self._check_state(need=("lq_R",))
+            p = count_posterior(self._context(), self._d["lq_R"], N, 1)[0][0]
+        else:
+            raise ValueError("method must be 'vb' or 'gibbs'")
+        return {"p_count": p, "p_any": float(1.0 - p[0])}
+
+    def score(self, *args, **kwargs):
+        """Scoring a new patient under a population-level r is a different question; not provided."""
+        raise NotImplementedError("score() is not provided for the shared-region model")
+
+
 def count_posterior(ctx, lq_R, Nreg, U):
     """
     (p_patient (U, Nreg+1), p_region (Nreg, U+1)) as NumPy float64 through fcd_vb_count_posterior: the Poisson-binomial
@@ -840,48 +1004,64 @@ def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=Non
     return {"p_T": p_T.cpu().numpy(), "p_F_tilde": p_Ft.cpu().numpy(), "p_changed": p_ch.cpu().numpy()}
 
 
-def theta_sub_objective(ctx, bt_dev, W, theta, reduce=None, missing_data=False):
+def _objective_flags(bt_dev, W, missing_data, per_edge):
+    """(flags, U) of the theta objectives; per_edge: W is (C, 1, 3, 3) for every patient of bt (C, U)."""
+    flags = _lib.FCD_DATA_NAN_MISSING if missing_data else 0
+    if not per_edge:
+        return flags, int(W.shape[1])
+    C, U = int(bt_dev.shape[0]), int(bt_dev.shape[1])
+    if tuple(W.shape) != (C, 1, 3, 3):
+        raise ValueError("per-edge weights must be (C, 1, 3, 3) = %s, got %s" % ((C, 1, 3, 3), tuple(W.shape)))
+    return flags | _lib.FCD_W_PER_EDGE, U
+
+
+def theta_sub_objective(ctx, bt_dev, W, theta, reduce=None, missing_data=False, per_edge=False):
     """
     (S, dS/d eta, dS/d epsilon), S = sum W ln M(bt; eta, epsilon), through fcd_theta_sub_objective_ex.
     `reduce` (optional) sums the three numbers over ranks (multi-GPU sampler: W holds this rank's chain counts).
     missing_data: an item with NaN bt adds nothing (its M = 1 does not depend on eta or epsilon).
+    per_edge: W is (C, 1, 3, 3) and weights every patient's item of its edge, S = sum W[c,k,l] sum_u ln M_kl(bt_cu)
+    (FCD_W_PER_EDGE: the shared-region fit).
     """
     import torch
     out = torch.empty(3, dtype=torch.float64, device=W.device)
     (th, _th) = _lib.dbl_array(theta)
-    ctx.call("fcd_theta_sub_objective_ex", _lib.dptr(bt_dev), _lib.dptr(W), int(W.shape[0]), int(W.shape[1]), th,
-             _lib.FCD_DATA_NAN_MISSING if missing_data else 0, _lib.dptr(out), _lib.stream_ptr())
+    (flags, U) = _objective_flags(bt_dev, W, missing_data, per_edge)
+    ctx.call("fcd_theta_sub_objective_ex", _lib.dptr(bt_dev), _lib.dptr(W), int(W.shape[0]), U, th, flags, _lib.dptr(out),
+             _lib.stream_ptr())
     if reduce is not None:
         out = reduce(out)
     return out.cpu().numpy()
 
 
-def theta_full_objective(ctx, b_dev, bt_dev, W, theta, reduce=None, missing_data=False):
+def theta_full_objective(ctx, b_dev, bt_dev, W, theta, reduce=None, missing_data=False, per_edge=False):
     """
     {S, dS/d eta, dS/d epsilon, dS/d mu[3], dS/d sigma^2[3]} of the full theta_sub objective (fcd_theta_full_objective):
     S = E[ln p(b | f)] + E[ln p(bt | f, r)] for the weights W.  `reduce` sums the nine numbers over ranks.
     With several ranks each rank's W holds its own chain counts, but b is the same on all: pass b_dev on every rank
     (the healthy term scales with the chain counts too, so the sum over ranks is the pooled objective).
     missing_data: a NaN bt item adds nothing to any term, a NaN b adds nothing to the ln N / mu / sigma^2 terms.
+    per_edge: W is (C, 1, 3, 3) for every patient of bt (FCD_W_PER_EDGE), as in theta_sub_objective.
     """
     import torch
     out = torch.empty(9, dtype=torch.float64, device=W.device)
     (th, _th) = _lib.dbl_array(theta)
     H = int(b_dev.shape[1]) if b_dev is not None else 0
-    ctx.call("fcd_theta_full_objective_ex", _lib.dptr(b_dev), _lib.dptr(bt_dev), _lib.dptr(W), int(W.shape[0]), H,
-             int(W.shape[1]), th, _lib.FCD_DATA_NAN_MISSING if missing_data else 0, _lib.dptr(out), _lib.stream_ptr())
+    (flags, U) = _objective_flags(bt_dev, W, missing_data, per_edge)
+    ctx.call("fcd_theta_full_objective_ex", _lib.dptr(b_dev), _lib.dptr(bt_dev), _lib.dptr(W), int(W.shape[0]), H, U, th,
+             flags, _lib.dptr(out), _lib.stream_ptr())
     if reduce is not None:
         out = reduce(out)
     return out.cpu().numpy()
 
 
-def minimize_theta_full(ctx, b_dev, bt_dev, W, model, reduce=None, bound_eps=1e-5, missing_data=False):
+def minimize_theta_full(ctx, b_dev, bt_dev, W, model, reduce=None, bound_eps=1e-5, missing_data=False, per_edge=False):
     """
     argmin of -(E[ln p(b | f)] + E[ln p(bt | f, r)]) over theta_sub = (eta, epsilon, mu[3], sigma^2[3]): the step the
     reference intends (fit.py:222-286 with its commented-out lines read in): pack order and sigma ** 2 as in
     fit.py:243-252, bounds of fit.py:228-237 -- eta, epsilon in (e, 1-e), mu_0 in (-1+e, -e), mu_1 in (-e, e), mu_2 in
     (e, 1-e), sigma^2 > e --, analytic gradient, L-BFGS-B.  Returns (eta, epsilon, mu, sigma, scipy result).
-    missing_data: NaN in b / bt is unobserved (theta_full_objective).
+    missing_data: NaN in b / bt is unobserved (theta_full_objective).  per_edge: W is (C, 1, 3, 3) (theta_sub_objective).
     """
     import scipy.optimize as spopt
     base = np.array(model.theta(), dtype=np.float64)
@@ -895,7 +1075,7 @@ def minimize_theta_full(ctx, b_dev, bt_dev, W, model, reduce=None, bound_eps=1e-
         return th
 
     def fun(x):
-        o = theta_full_objective(ctx, b_dev, bt_dev, W, unpack(x), reduce, missing_data=missing_data)
+        o = theta_full_objective(ctx, b_dev, bt_dev, W, unpack(x), reduce, missing_data=missing_data, per_edge=per_edge)
         return (-o[0], -o[1:9])
     bnds = ((e, 1 - e), (e, 1 - e), (-1 + e, 0 - e), (0 - e, 0 + e), (0 + e, 1 - e), (0 + e, None), (0 + e, None), (0 + e, None))
     x0 = np.concatenate([[model.eta, model.epsilon], np.asarray(model.mu, dtype=np.float64),
@@ -908,10 +1088,11 @@ def minimize_theta_full(ctx, b_dev, bt_dev, W, model, reduce=None, bound_eps=1e-
     return float(th[1]), float(th[2]), th[6:9].copy(), th[9:12].copy(), res
 
 
-def minimize_theta_sub(ctx, bt_dev, W, model, reduce=None, bound_eps=1e-5, missing_data=False):
+def minimize_theta_sub(ctx, bt_dev, W, model, reduce=None, bound_eps=1e-5, missing_data=False, per_edge=False):
     """
     argmin over (eta, epsilon) in [1e-5, 1-1e-5]^2 of -sum W ln M (fit.py:222-241), analytic gradient, L-BFGS-B.
     Returns (eta, epsilon, scipy result).  The model is not modified.  missing_data: NaN in bt is unobserved.
+    per_edge: W is (C, 1, 3, 3) for every patient (theta_sub_objective).
     """
     import scipy.optimize as spopt
     base = np.array(model.theta(), dtype=np.float64)
@@ -919,7 +1100,7 @@ def minimize_theta_sub(ctx, bt_dev, W, model, reduce=None, bound_eps=1e-5, missi
     def fun(x):
         th = base.copy()
         th[1], th[2] = float(x[0]), float(x[1])
-        (S, dh, de) = theta_sub_objective(ctx, bt_dev, W, th, reduce, missing_data=missing_data)
+        (S, dh, de) = theta_sub_objective(ctx, bt_dev, W, th, reduce, missing_data=missing_data, per_edge=per_edge)
         return (-S, np.array([-dh, -de]))
     bnds = ((bound_eps, 1 - bound_eps), (bound_eps, 1 - bound_eps))          # fit.py:228-231
     x0 = np.clip(np.array([model.eta, model.epsilon], dtype=np.float64), bound_eps, 1 - bound_eps)

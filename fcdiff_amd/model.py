@@ -15,17 +15,8 @@ import numpy as np
 from . import util
 
 
-class UnsharedRegionModel(object):
-    """
-    Attributes (fcdiff/model.py:13-38)
-    ----------
-    rng : numpy.random.RandomState     random number generator (seed 0)
-    pi : float                         probability of an anomalous region
-    eta : float                        probability of an anomalous connection btw a typical and anomalous region
-    gamma : ndarray (3,)               probability of each template connection type
-    epsilon : float                    probability that a typical connection differs from the template
-    mu, sigma : ndarray (3,)           mean / standard deviation of the correlation of each connection type
-    """
+class _RegionModelParams(object):
+    """The parameters both region models share, their defaults and their packing for the C ABI."""
 
     def __init__(self):
         self.rng = np.random.RandomState(0)
@@ -35,18 +26,6 @@ class UnsharedRegionModel(object):
         self.epsilon = 0.03
         self.mu = np.array([-0.15, 0, 0.3])
         self.sigma = np.array([0.025, 0.035, 0.05])
-
-    def __str__(self):
-        return textwrap.dedent('''\
-            fcdiff.models.UnsharedRegionModel
-                rng = %s
-                pi = %g
-                eta = %g
-                gamma = %s
-                epsilon = %g
-                mu = %s
-                sigma = %s''' % (self.rng, self.pi, self.eta, self.gamma,
-                                 self.epsilon, self.mu, self.sigma))
 
     # ---- packing used by the C ABI: theta[12] = pi, eta, epsilon, gamma[3], mu[3], sigma[3] ----
     def pi2(self):
@@ -61,6 +40,31 @@ class UnsharedRegionModel(object):
                                np.asarray(self.gamma, dtype=np.float64).reshape(3),
                                np.asarray(self.mu, dtype=np.float64).reshape(3),
                                np.asarray(self.sigma, dtype=np.float64).reshape(3)]).astype(np.float64)
+
+
+class UnsharedRegionModel(_RegionModelParams):
+    """
+    Attributes (fcdiff/model.py:13-38)
+    ----------
+    rng : numpy.random.RandomState     random number generator (seed 0)
+    pi : float                         probability of an anomalous region
+    eta : float                        probability of an anomalous connection btw a typical and anomalous region
+    gamma : ndarray (3,)               probability of each template connection type
+    epsilon : float                    probability that a typical connection differs from the template
+    mu, sigma : ndarray (3,)           mean / standard deviation of the correlation of each connection type
+    """
+
+    def __str__(self):
+        return textwrap.dedent('''\
+            fcdiff.models.UnsharedRegionModel
+                rng = %s
+                pi = %g
+                eta = %g
+                gamma = %s
+                epsilon = %g
+                mu = %s
+                sigma = %s''' % (self.rng, self.pi, self.eta, self.gamma,
+                                 self.epsilon, self.mu, self.sigma))
 
     # ---- forward sampling (model.py:52-236) ----
     def sample(self, N, H, U):
@@ -190,3 +194,74 @@ class UnsharedRegionModel(object):
         f_tilde = np.zeros((Ce, U, 3), dtype=bool)
         np.put_along_axis(f_tilde, ftk[:, :, None], True, axis=2)
         return (r.cpu().numpy() > 0, t.cpu().numpy() > 0, f, f_tilde, b.cpu().numpy(), bt.cpu().numpy())
+
+
+def _onehot(k, shape):
+    out = np.zeros(shape + (3,), dtype=bool)
+    np.put_along_axis(out, np.asarray(k, dtype=np.int64)[..., None], True, axis=-1)
+    return out
+
+
+class SharedRegionModel(_RegionModelParams):
+    """
+    The shared anomalous-region model: the parameters and defaults of UnsharedRegionModel, but one set of anomalous
+    regions for the whole patient population.
+        r_n ~ Bernoulli(pi) once per region n, the same for every patient;
+        T_cu | r_n, r_m drawn independently per patient u: both typical -> 0, both anomalous -> 1, discordant ->
+        Bernoulli(eta) (doc/methods.rst:81-105);
+        F, F~, B and B~ as in the unshared model.
+    Fitted by fcdiff_amd.fit.SharedRegionFit.
+    """
+
+    def __str__(self):
+        return textwrap.dedent('''\
+            fcdiff_amd.SharedRegionModel
+                pi = %g
+                eta = %g
+                gamma = %s
+                epsilon = %g
+                mu = %s
+                sigma = %s''' % (self.pi2()[1], self.eta, self.gamma, self.epsilon, self.mu, self.sigma))
+
+    def sample(self, N, H, U, seed=0):
+        """
+        (r (N,) bool, t (C,U) bool, f (C,3) bool, f_tilde (C,U,3) bool, b (C,H) float64, b_tilde (C,U) float64), drawn
+        with numpy.random.Generator(seed) in the fitter's edge order (as UnsharedRegionModel.sample_fast).
+        """
+        g = np.random.default_rng(seed)
+        C = util.N_to_C(N)
+        il = np.tril_indices(N, -1)           # (n, m < n) row-major == util.c_to_nm order
+        r = g.random(N) < self.pi2()[1]
+        rn, rm = r[il[0]][:, None], r[il[1]][:, None]
+        t = np.where(rn ^ rm, g.random((C, U)) < self.eta, np.broadcast_to(rn & rm, (C, U)))
+        gam = np.asarray(self.gamma, dtype=np.float64)
+        fk = g.choice(3, size=C, p=gam / gam.sum())
+        e = self.epsilon
+        keep = np.where(t, g.random((C, U)) < e, g.random((C, U)) < (1 - e))
+        other = (fk[:, None] + 1 + (g.random((C, U)) < 0.5)) % 3
+        ftk = np.where(keep, fk[:, None], other)
+        mu = np.asarray(self.mu, dtype=np.float64)
+        sg = np.asarray(self.sigma, dtype=np.float64)
+        b = (mu[fk][:, None] + sg[fk][:, None] * g.standard_normal((C, H))).clip(-1, 1)
+        b_tilde = (mu[ftk] + sg[ftk] * g.standard_normal((C, U))).clip(-1, 1)
+        return (r, t, _onehot(fk, (C,)), _onehot(ftk, (C, U)), b, b_tilde)
+
+    def sample_gpu(self, N, H, U, seed=0, ctx=None):
+        """`sample` on the GPU (fcd_model_sample_shared, counter RNG): same return types and distribution."""
+        import ctypes as C
+        import torch
+        from . import _lib
+        ctx = ctx if ctx is not None else _lib.Context()
+        Ce = util.N_to_C(N)
+        dev = ctx.device
+        r = torch.empty((N,), dtype=torch.uint8, device=dev)
+        t = torch.empty((Ce, U), dtype=torch.uint8, device=dev)
+        fk = torch.empty((Ce,), dtype=torch.uint8, device=dev)
+        ftk = torch.empty((Ce, U), dtype=torch.uint8, device=dev)
+        b = torch.empty((Ce, H), dtype=torch.float64, device=dev)
+        bt = torch.empty((Ce, U), dtype=torch.float64, device=dev)
+        (th, _th) = _lib.dbl_array(self.theta())
+        ctx.call("fcd_model_sample_shared", th, N, H, U, C.c_uint64(int(seed)), _lib.dptr(r), _lib.dptr(t), _lib.dptr(fk),
+                 _lib.dptr(ftk), _lib.dptr(b), _lib.dptr(bt), _lib.stream_ptr())
+        return (r.cpu().numpy() > 0, t.cpu().numpy() > 0, _onehot(fk.cpu().numpy(), (Ce,)),
+                _onehot(ftk.cpu().numpy(), (Ce, U)), b.cpu().numpy(), bt.cpu().numpy())

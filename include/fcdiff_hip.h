@@ -64,6 +64,9 @@ extern "C" {
  * Every other entry point reads the data only through S_B and lM and needs no flag.  flags = 0: the plain entry points'
  * results, bit for bit (they are the flags = 0 forms). */
 #define FCD_DATA_NAN_MISSING 1
+/* FCD_W_PER_EDGE (fcd_theta_sub_objective_ex, fcd_theta_full_objective_ex only): W is (C, 1, 3, 3), one weight table per
+ * edge that every patient's bt[c, u] is weighted with -- the shared-region model, whose weights do not depend on u. */
+#define FCD_W_PER_EDGE 2
 
 typedef struct fcd_ctx fcd_ctx;
 typedef void *fcd_stream; /* hipStream_t */
@@ -188,6 +191,15 @@ int fcd_lik_tables(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, i
 int fcd_lik_tables_ex(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
                       const double *theta12_host, double *S_B, double *lM, double *lp_B_g_F, double *p_Bt_g_Ft,
                       int flags, int64_t *n_missing2, fcd_stream stream);
+/* The tables of the shared-region model (SharedRegionFit): S_B (C,3) as fcd_lik_tables writes it, bit for bit, and the
+ * patient sum L (C,3,3), L[c,k,l] = sum_u lM[c,u,k,l], in ONE launch that reads b and bt once and writes nothing of size
+ * C*U.  Per item the arithmetic of fcd_lik_tables; the sum over u has a fixed order (no atomics): two calls agree bit
+ * for bit.  flags as fcd_lik_tables_ex: with FCD_DATA_NAN_MISSING a NaN bt adds 0 to L, a NaN b 0 to S_B, and
+ * nan_counts (device int64[2], may be NULL; only with the flag) receives {NaN in b, NaN in bt}.  Without it a NaN
+ * gives NaN.  An underflowed density gives -inf in L as in lM. */
+int fcd_lik_shared_tables(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                          const double *theta12_host, double *S_B, double *L, int flags, int64_t *nan_counts,
+                          fcd_stream stream);
 
 /* ---- forward sampler: UnsharedRegionModel.sample, fcdiff/model.py:52-236, on the device ---------------
  * Counter RNG (Philox), all variables drawn in parallel; the reference's MT19937 stream is not reproduced (the host
@@ -195,6 +207,11 @@ int fcd_lik_tables_ex(fcd_ctx *ctx, const double *b, const double *bt, int64_t C
  * f (C,), f_tilde (C,U) uint8; b (C,H), b_tilde (C,U) float64 clipped to [-1,1].  Edges in the fitter's order. */
 int fcd_model_sample(fcd_ctx *ctx, const double *theta12_host, int64_t Nreg, int64_t H, int64_t U, uint64_t seed, uint8_t *r,
                      uint8_t *t, uint8_t *f, uint8_t *f_tilde, double *b, double *b_tilde, fcd_stream stream);
+/* The same for the shared-region model (SharedRegionModel): r (Nreg,) is drawn once per region and holds for every
+ * patient; t, f_tilde and b_tilde of each patient read it.  Other outputs as fcd_model_sample. */
+int fcd_model_sample_shared(fcd_ctx *ctx, const double *theta12_host, int64_t Nreg, int64_t H, int64_t U, uint64_t seed,
+                            uint8_t *r, uint8_t *t, uint8_t *f, uint8_t *f_tilde, double *b, double *b_tilde,
+                            fcd_stream stream);
 
 /* ---- front-end: region x time series -> edge-major correlations --------------------------------------
  * Not in the reference (its inputs are already correlations, fit.py:20-23); oracle = numpy.corrcoef.
