@@ -101,6 +101,8 @@ SIGNATURES = {
     "fcd_vb_patient_elbo": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
     "fcd_score_ais_step": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _dbl, _dbl, _p, _p, _p]),
     "fcd_score_ais_finish": (_int, [_p, _p, _i64, _i64, _p, _p]),
+    "fcd_evidence_energy": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _dbl, _dbl, _p, _p]),
+    "fcd_evidence_temper": (_int, [_p, _dbl, _i64, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64), _p]),
 }
 
 _lib = None

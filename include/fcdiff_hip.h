@@ -416,6 +416,24 @@ int fcd_score_ais_step(fcd_ctx *ctx, const double *lM, const uint8_t *f_state, c
  * G} (sums 0 when m = -inf), the numbers that pool over ranks into log-mean-exp, its standard error and the effective
  * sample size.  Chains in a fixed order: bitwise repeatable. */
 int fcd_score_ais_finish(fcd_ctx *ctx, const double *w, int64_t U, int64_t G, double *out4, fcd_stream stream);
+/* ---- model evidence by annealed importance sampling over (f, r) (UnsharedRegionFit.log_evidence) -----------------------
+ * log Z = log sum_{f,r} p(f; gamma) p(r; pi) exp(E(f, r)),  E = sum_c S_B[c, f_c] + sum_{c,u} lM[c, u, f_c, l(r_nu, r_mu)]
+ * (symmetric edge ids: the true endpoints of c), is log p(b, bt | theta).  A ladder 0 = beta_0 < ... < beta_T = 1 starts
+ * from a draw of the prior (one sweep on all-zero tables) and at every rung adds (beta_t - beta_{t-1}) E to each chain's
+ * log-weight, then sweeps once on the beta_t-scaled tables (fcd_gibbs_sweeps): exp(w_g) is an unbiased estimate of Z.
+ *
+ * One rung's weight update:  w[g] += (beta - beta_prev) E_g  at the current state, w (G,) fp64, device.  The table is staged
+ * through LDS once per 32 chain words (not once per chain word as in fcd_score_ais_step).  fp64, fixed reduction order:
+ * bitwise repeatable, and chain g's number does not depend on the other chains of the call.  Two launches; uses the
+ * context's workspace. */
+int fcd_evidence_energy(fcd_ctx *ctx, const double *S_B, const double *lM, const uint8_t *f_state, const uint64_t *r_bits,
+                        int64_t Nreg, int64_t U, int64_t G, double beta_prev, double beta, double *w, fcd_stream stream);
+/* dst[j][i] = beta * src[j][i], i < n[j], for n_tables (1 to 8) tables in ONE launch: the working tables of a rung (S_B, lM
+ * and the two difference tables, which are linear in lM).  src, dst, n are host arrays of device pointers / element counts;
+ * dst[j] may be src[j].  beta = 1 copies bit for bit.  An all-zero table is the caller's zero fill, not beta = 0
+ * (0 * -inf is NaN). */
+int fcd_evidence_temper(fcd_ctx *ctx, double beta, int64_t n_tables, const double *const *src, double *const *dst,
+                        const int64_t *n, fcd_stream stream);
 /* log p(f, r, b, bt; theta) of each chain = minus the first four terms of fit.py:149-152 at one-hot q.
  * out (G,) doubles. */
 int fcd_gibbs_logjoint(fcd_ctx *ctx, const double *S_B, const double *lM, const double *hyper,
