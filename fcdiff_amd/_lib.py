@@ -103,6 +103,7 @@ SIGNATURES = {
     "fcd_score_ais_finish": (_int, [_p, _p, _i64, _i64, _p, _p]),
     "fcd_evidence_energy": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _dbl, _dbl, _p, _p]),
     "fcd_evidence_temper": (_int, [_p, _dbl, _i64, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64), _p]),
+    "fcd_member_loglik": (_int, [_p, _p, C.POINTER(_dbl), _p, _p, _i64, _i64, _i64, _int, _int, _p, _p, _p]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
-// The arithmetic of K_lik (fcd_lik.hip) as inline helpers, for K_lik_shared (fcd_lik_shared.hip): the parameters as the
-// kernels read them, the per-item ln M_kl and the S_B blocks, statement for statement as lik_kernel has them.
+// The arithmetic of K_lik (fcd_lik.hip) as inline helpers, for K_lik_shared (fcd_lik_shared.hip) and the patient-or-control
+// kernel (fcd_member.hip): the parameters as the kernels read them, the per-item ln M_kl, the ln N_k of S_B and the S_B
+// blocks, statement for statement as lik_kernel has them.
 // lik_kernel keeps its own text: routed through these helpers its MISSING form compiles to other instructions (same
 // results, a different schedule), and the table kernel of the unshared fit is not changed by the shared one.  What
 // binds the two copies is a test: S_B of both launches is compared bit for bit, and L against the patient sum of lM.
@@ -91,6 +92,17 @@ __device__ __forceinline__ void lik_logs(const double N[3], const LikTheta &th, 
     }
 }
 
+// ln N(x; mu_k, sigma_k) = -z*z/2 - log(sqrt(2 pi)) - log(sigma_k), k = 0,1,2 (fit.py:114): the terms of S_B, and the control
+// side of fcd_member_loglik
+__device__ __forceinline__ void lik_normal_logs(double x, const LikTheta &th, double &l0, double &l1, double &l2) {
+    const double z0 = (x - th.mu[0]) / th.sigma[0];
+    const double z1 = (x - th.mu[1]) / th.sigma[1];
+    const double z2 = (x - th.mu[2]) / th.sigma[2];
+    l0 = -(z0 * z0) / 2.0 - kLogSqrt2Pi - th.lnsigma[0];
+    l1 = -(z1 * z1) / 2.0 - kLogSqrt2Pi - th.lnsigma[1];
+    l2 = -(z2 * z2) / 2.0 - kLogSqrt2Pi - th.lnsigma[2];
+}
+
 // An S_B block: 16 lanes per edge, S_B[c,k] = sum_h ( -z*z/2 - log(sqrt(2 pi)) - log(sigma_k) )  (fit.py:114, :171);
 // `sb_block` is the block's index among the S_B blocks.  MISSING: a NaN b adds 0 (and lpB holds 0); the block's NaN
 // count goes to slot line (blockIdx.x % FCD_NAN_SLOTS), word 0, through `blk_nan` (the kernel's __shared__ int).
@@ -107,12 +119,8 @@ __device__ __forceinline__ void lik_sb_block(unsigned sb_block, int tid, const d
         const double *row = b + c * H;
         for (int h = sub; h < H; h += 16) {
             const double x = row[h];
-            const double z0 = (x - th.mu[0]) / th.sigma[0];
-            const double z1 = (x - th.mu[1]) / th.sigma[1];
-            const double z2 = (x - th.mu[2]) / th.sigma[2];
-            double l0 = -(z0 * z0) / 2.0 - kLogSqrt2Pi - th.lnsigma[0];
-            double l1 = -(z1 * z1) / 2.0 - kLogSqrt2Pi - th.lnsigma[1];
-            double l2 = -(z2 * z2) / 2.0 - kLogSqrt2Pi - th.lnsigma[2];
+            double l0, l1, l2;
+            lik_normal_logs(x, th, l0, l1, l2);
             if (MISSING) {
                 const bool miss = __builtin_isnan(x);        // unobserved: ln N integrates to ln 1 = 0
                 l0 = miss ? 0.0 : l0;

@@ -95,6 +95,7 @@ class UnsharedRegionFit(object):
         self._ctx = None
         self._score_ctx = None    # score(): a context of its own, so that scoring never touches the fit's workspace or plan
         self._evidence_ctx = None # log_evidence(): the same
+        self._member_ctx = None   # membership(): the same
         self._d = {}              # device tensors: lq_R, lq_F, S_B, lM, lpB, pBt, hyper, b, bt
         self._hyper_key = None
 
@@ -794,6 +795,72 @@ class UnsharedRegionFit(object):
                                  int(n_anneal), int(n_sweeps), key)
         return out
 
+    # ------------------------------------------------------------------ patient or control
+    def membership(self, x_new, *, n_anneal=200, seed=None):
+        """
+        Sets the model's two laws side by side for subjects who were not in the fit: is x_u a patient or a control?
+
+        x_new (C, U') correlations in the fit's edge order (NaN = unobserved when missing_data: it adds 0 to both sides;
+        without missing_data NaN propagates, as in score()).  theta is the model's CURRENT parameters (the plug-in convention
+        of score()), and like score() the call works on a context of its own and leaves the fit (model, `sampler` and its
+        state, energy) exactly as it was.  method='gibbs' only.
+
+        With (f_g, r_g) the end state of the fit's sampler at chain g (the convention of score()):
+            control   lc[g, u] = sum_c log N(x_cu; mu_k, sigma_k^2), k = f_gc
+            patient   lp[g, u] = the annealed-importance-sampling log-weight over the new patient's own r_u, n_anneal rungs
+                      from the prior (score.ais_schedule; seed and the sweep numbers as in score(): score.SCORE_SWEEP0), so
+                      that E exp(lp[g, u]) = p(x_u | f_g, patient)
+        and each side is pooled over all chains (of all ranks of a sharded fit) exactly as score() pools log_pred.
+        Returns a dict of float64 (U',) arrays:
+            log_patient, log_patient_se, ess_patient    log mean_g exp(lp[g, u]) = the estimate of log p(x_u | data, patient),
+                                                        its delta-method standard error, (sum w)^2 / sum w^2 of the weights
+            log_control, log_control_se, ess_control    the same of lc: log p(x_u | data, control)
+            log_bf      log_patient - log_control: the log Bayes factor patient against control (add the log prior odds)
+            log_bf_se   sqrt(log_patient_se^2 + log_control_se^2).  Both sides are averages over the SAME chains, so they are
+                        correlated; the covariance between the two is ignored here.
+        and n_chains, the number of chains pooled.  log_patient is score()'s log_pred of the same subjects.
+        The cohort is walked in chunks (membership.CHUNK subjects): apart from a chunk's buffers, device memory does not grow
+        with U'.  Raises ValueError before run(), for method='vb', for a wrong C, a non-2-D input and for edge_index other than
+        'symmetric'.
+        """
+        from . import membership as _membership
+        (x_new, N) = self._membership_input(x_new)
+        if int(n_anneal) < 1:
+            raise ValueError("n_anneal must be >= 1")
+        ctx = self._membership_context()
+        b_dev = self._d.get("b")
+        if b_dev is None or tuple(b_dev.shape)[0] != x_new.shape[0]:
+            b_dev = self._up(self.b)
+        key = _score.score_key(self.seed if seed is None else seed)
+        return _membership.membership(ctx, self._up, x_new, N, self.sampler, self.model, self.missing_data, False, b_dev=b_dev,
+                                      pi2=self._pi2(), n_anneal=int(n_anneal), key=key)
+
+    def _membership_input(self, x_new):
+        """The checks of membership(), before anything touches the device: (x_new (C, U') float64, Nreg)."""
+        if self.method == "vb":
+            raise ValueError("membership() needs method='gibbs': the mean-field q of a 'vb' fit gives only bounds on the "
+                             "patient side, and a difference of bounds is not a bound")
+        if self.method != "gibbs":
+            raise ValueError("method must be 'gibbs'")
+        if self.model is None or self.sampler is None:
+            raise ValueError("membership() needs a fitted model: call run() first")
+        if self._edge_mode() != "symmetric":
+            raise ValueError("membership() needs edge_index 'symmetric'")
+        x_new = np.ascontiguousarray(x_new, dtype=np.float64)
+        if x_new.ndim != 2:
+            raise ValueError("x_new must be (C, U'), got shape %s" % (x_new.shape,))
+        (C, U) = x_new.shape
+        if C != int(self.sampler.C):
+            raise ValueError("x_new has %d connections, the fit has %d" % (C, int(self.sampler.C)))
+        if U < 1:
+            raise ValueError("x_new holds no subject")
+        return x_new, int(util.C_to_N(C))
+
+    def _membership_context(self):
+        if self._member_ctx is None:
+            self._member_ctx = _lib.Context()
+        return self._member_ctx
+
     # ------------------------------------------------------------------ model evidence
     def log_evidence(self, n_anneal=1000, n_chains=None, seed=None):
         """
@@ -1043,6 +1110,21 @@ class SharedRegionFit(UnsharedRegionFit):
     def score(self, *args, **kwargs):
         """Scoring a new patient under a population-level r is a different question; not provided."""
         raise NotImplementedError("score() is not provided for the shared-region model")
+
+    def membership(self, x_new, *, n_anneal=200, seed=None):
+        """
+        UnsharedRegionFit.membership() for the shared-region model: same input, same dict, same refusals.  A new patient
+        inherits the population's r, so the patient side needs no annealing (n_anneal and seed are ignored):
+            patient   lp[g, u] = sum_c log M(x_cu | f_gc, l(r_gn, r_gm)), the log of the mixture lM tabulates, at the
+                      population's r of chain g
+        pooled over the chains like the control side.  log_patient is the held-out predictive likelihood
+        log p(x_u | data, patient) of this model, the number to set against the unshared fit's score()["log_pred"].
+        One kernel (fcd_member_loglik) gives both sides straight from x_new: no (C, U', 3, 3) table is made.
+        """
+        from . import membership as _membership
+        (x_new, N) = self._membership_input(x_new)
+        return _membership.membership(self._membership_context(), self._up, x_new, N, self.sampler, self.model,
+                                      self.missing_data, True)
 
 
 def count_posterior(ctx, lq_R, Nreg, U):

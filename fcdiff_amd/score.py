@@ -181,12 +181,16 @@ def score_vb(ctx, b_dev, bt_dev, Nreg, lq_F, model, pi2, edge_mode, missing_data
     return out
 
 
-def score_gibbs(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, connections, n_anneal, n_sweeps, key):
-    """The sampler path of UnsharedRegionFit.score (see there); `sampler` is the fit's engine, read only (its f_state)."""
+def ais_weights(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, n_anneal, key):
+    """
+    The annealing ladder over r with each chain's template f_g (the end state of `sampler`, read only) held: r from the prior,
+    then per rung one fcd_score_ais_step and one r pass on the tempered table.  Returns (eng, lM, region_tables, w, sweep):
+    the scoring engine with r ~ p(r | f_g, bt) on the beta = 1 working table, the untempered table, the function that
+    rebuilds the engine's region-major table from a table, the log-weights w (G, U) with E exp(w[g, u]) = p(bt_u | f_g), and
+    the next free sweep number.
+    """
     import torch
-    from .fit import conn_posterior
     U = int(bt_dev.shape[1])
-    C = util.N_to_C(int(Nreg))
     G = sampler.G
     theta = model.theta()
     (S_B, lM) = lik_tables(ctx, b_dev, bt_dev, theta, missing_data)
@@ -214,6 +218,18 @@ def score_gibbs(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, con
         region_tables(lMw)
         eng.r_step(sweep)
         sweep += 1
+    return eng, lM, region_tables, w, sweep
+
+
+def score_gibbs(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, connections, n_anneal, n_sweeps, key):
+    """The sampler path of UnsharedRegionFit.score (see there); `sampler` is the fit's engine, read only (its f_state)."""
+    import torch
+    from .fit import conn_posterior
+    U = int(bt_dev.shape[1])
+    C = util.N_to_C(int(Nreg))
+    G = sampler.G
+    theta = model.theta()
+    (eng, lM, region_tables, w, sweep) = ais_weights(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, n_anneal, key)
     fin = torch.empty((U, 4), dtype=torch.float64, device=bt_dev.device)
     ctx.call("fcd_score_ais_finish", _lib.dptr(w), U, G, _lib.dptr(fin), _lib.stream_ptr())
     # beta = 1: the untempered table (bit for bit what the last AIS step wrote) and its region-major difference table

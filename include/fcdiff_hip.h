@@ -434,6 +434,22 @@ int fcd_evidence_energy(fcd_ctx *ctx, const double *S_B, const double *lM, const
  * (0 * -inf is NaN). */
 int fcd_evidence_temper(fcd_ctx *ctx, double beta, int64_t n_tables, const double *const *src, double *const *dst,
                         const int64_t *n, fcd_stream stream);
+/* ---- patient or control: the two per-chain log-likelihoods of new subjects (UnsharedRegionFit.membership) ----------------
+ * For subjects x (C, U) fp64 (device, the fit's edge order), theta (12 doubles, host) and the packed chain state:
+ *   out_control[g, u] = sum_c ln N(x_cu; mu_k, sigma_k),  k = f_c of chain g              (G, U) fp64, device
+ *   out_patient[g, u] = sum_c ln M_{k, l}(x_cu),          l = mixture case of chain g's (r_n, r_m) at the true endpoints of c
+ *                                                         (symmetric edge ids), the entries of lM;  NULL: not computed
+ * r_bits has r_cols columns per region: r_cols = U, one r column per subject (r_bits (GW, Nreg, U)), or r_cols = 1, ONE column
+ * for every subject (r_bits (GW, Nreg, 1): the shared-region model's population r).  r_bits may be NULL when out_patient is.
+ * flags: FCD_DATA_NAN_MISSING -- a NaN x is unobserved and adds 0 to both sides; without it NaN propagates.  A density that
+ * underflows gives -inf, as in lM.  No (C, U, 3, 3) table is made: per (c, u) the 3 + 9 logs are computed once into LDS, by the
+ * arithmetic of the table kernels, and looked up by the chains.  fp64, fixed reduction order (edge slices that depend on
+ * (Nreg, U) and the device alone): bitwise repeatable, and chain g's numbers do not depend on G or on the other chains of
+ * the call.  Fold the matrices with fcd_score_ais_finish.  Two launches; uses the context's workspace
+ * (slices x U x 64 ceil(G / 64) doubles per side). */
+int fcd_member_loglik(fcd_ctx *ctx, const double *x, const double *theta, const uint8_t *f_state, const uint64_t *r_bits,
+                      int64_t Nreg, int64_t U, int64_t G, int r_cols, int flags, double *out_control, double *out_patient,
+                      fcd_stream stream);
 /* log p(f, r, b, bt; theta) of each chain = minus the first four terms of fit.py:149-152 at one-hot q.
  * out (G,) doubles. */
 int fcd_gibbs_logjoint(fcd_ctx *ctx, const double *S_B, const double *lM, const double *hyper,
