@@ -355,21 +355,54 @@ __device__ __forceinline__ uint2 fcd_r_pair_bytes(const uint64_t *__restrict__ r
     return spread2(v);
 }
 
+// DPP move of a 32-bit word inside the rows of 16 lanes (every lane reads a lane that exists: no bound control needed)
+template <int CTRL>
+__device__ __forceinline__ uint32_t fcd_dpp_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+}
+// Four per-lane values -> their four sums over the wave, in one tree: lane l ends with the sum of p[l & 3].  The first two
+// steps halve the number of values instead of doubling the number of copies (a lane keeps the value of its own parity and
+// hands over the other), so the tree is 3 + 2 DPP moves and two cross-row exchanges for FOUR sums, against 6 exchanges
+// for each.  No sum may exceed 32 bits -- the caller packs two 16-bit counts in a word.
+__device__ __forceinline__ uint32_t fcd_wave_sum4(const uint32_t (&p)[4], int lane) {
+    const bool b0 = lane & 1, b1 = lane & 2;
+    const uint32_t x01 = (b0 ? p[1] : p[0]) + fcd_dpp_u32<0xB1>(b0 ? p[0] : p[1]);      // quad_perm [1,0,3,2]
+    const uint32_t x23 = (b0 ? p[3] : p[2]) + fcd_dpp_u32<0xB1>(b0 ? p[2] : p[3]);
+    uint32_t y = (b1 ? x23 : x01) + fcd_dpp_u32<0x4E>(b1 ? x01 : x23);                  // quad_perm [2,3,0,1]: p[l & 3] over the quad
+    y += fcd_dpp_u32<0x124>(y);             // row_ror:4 and row_ror:8 keep l & 3: the four quads of the row
+    y += fcd_dpp_u32<0x128>(y);
+    y += __shfl_xor(y, 16, 64);             // the four rows
+    y += __shfl_xor(y, 32, 64);
+    return y;
+}
+
 // The f half of the tally for workgroup lin of nblk (WAVES waves each): f_state is read once, 16 bytes per lane -- a wave
 // covers the 16 chain words x 64 chains of an edge with one load instruction; four edges per round, their loads issued
 // together (the pass is a few memory round trips long: what counts is the number of bytes in flight).  red: LDS,
 // [WAVES][3].  Integer sums: any order gives the same totals.
+// The counters: wave (lin, wave) is the only one of the launch that meets edges c0 .. c0 + 3 (every caller numbers its
+// workgroups lin = 0 .. nblk - 1 once each, and the groups of chain words of an edge are a loop of the same wave), and
+// launches that count follow each other in one stream -- so the twelve words cnt_f[3 c0 .. 3 c0 + 11] are read, added to
+// and stored by lanes 0 .. 11, the old values asked for together with the f state.  (They were four atomics per edge from
+// lane 0.)
 template <int WAVES>
 __device__ __forceinline__ void fcd_tally_f_block(const fcd_tally_f &a, int lin, int nblk, unsigned long long (*red)[3]) {
     const uint8_t *__restrict__ f_state = a.f_state;
-    uint32_t *__restrict__ cnt_f = a.cnt_f;
+    uint32_t *cnt_f = a.cnt_f;
     const int64_t C = a.C, G = a.G;
     const int GW = a.GW;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // (the wave's number as a scalar: the walk over the edges, its bounds and the totals then live in scalar registers)
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int sub = lane & 3, wrow = lane >> 2;          // 16-byte piece of the 64-byte row, chain word within a group of 16
-    unsigned long long tot1 = 0, tot2 = 0, n_edges = 0;
+    unsigned long long tot1 = 0, tot2 = 0, n_edges = 0;  // (wave-uniform)
+    const int own_e = ((lane * 11) >> 5) & 3, own_j = lane - 3 * own_e;      // lane / 3, lane % 3 for the twelve lanes that store
     constexpr int TE = 4;
     for (int64_t c0 = ((int64_t)lin * WAVES + wave) * TE; c0 < C; c0 += (int64_t)nblk * WAVES * TE) {
+        const int ne = (int)(C - c0 < TE ? C - c0 : TE);
+        const bool owner = cnt_f && lane < 3 * ne;       // lane l: counter l % 3 of edge c0 + l / 3
+        uint32_t old = 0;
+        if (owner) old = cnt_f[c0 * 3 + lane];
+        uint32_t s1 = 0, s2 = 0;                         // lane l: ones and twos of edge c0 + (l & 3), over the groups so far
         for (int wg = 0; wg < GW; wg += 16) {
             const int w = wg + wrow;
             uint4 vv[TE];
@@ -379,6 +412,7 @@ __device__ __forceinline__ void fcd_tally_f_block(const fcd_tally_f &a, int lin,
                 vv[t] = *reinterpret_cast<const uint4 *>(f_state + ((int64_t)(w < GW ? w : 0) * C + c) * 64 + sub * 16);
             }
             const uint32_t act = (w < GW) ? (uint32_t)(fcd_active_mask(w, G) >> (sub * 16)) & 0xFFFFu : 0u;
+            uint32_t p[TE];                              // ones | twos << 16: a group's sum per edge is at most 1024
 #pragma unroll
             for (int t = 0; t < TE; ++t) {
                 uint4 v = vv[t];
@@ -388,29 +422,28 @@ __device__ __forceinline__ void fcd_tally_f_block(const fcd_tally_f &a, int lin,
                     v.z &= ((((act >> 8) & 15u) * 0x00204081u) & 0x01010101u) * 0xFFu;
                     v.w &= ((((act >> 12) & 15u) * 0x00204081u) & 0x01010101u) * 0xFFu;
                 }
-                uint32_t ones = __popc(v.x & 0x01010101u) + __popc(v.y & 0x01010101u) + __popc(v.z & 0x01010101u) +
-                                __popc(v.w & 0x01010101u);
-                uint32_t twos = __popc((v.x >> 1) & 0x01010101u) + __popc((v.y >> 1) & 0x01010101u) +
-                                __popc((v.z >> 1) & 0x01010101u) + __popc((v.w >> 1) & 0x01010101u);
-                for (int o = 32; o > 0; o >>= 1) {
-                    ones += __shfl_xor(ones, o, 64);
-                    twos += __shfl_xor(twos, o, 64);
-                }
-                if (lane == 0 && c0 + t < C) {
-                    const int64_t c = c0 + t;
-                    if (cnt_f) {
-                        // (atomics because they do not wait for the old value to come back)
-                        atomicAdd(&cnt_f[c * 3 + 1], ones);
-                        atomicAdd(&cnt_f[c * 3 + 2], twos);
-                        if (wg == 0) atomicAdd(&cnt_f[c * 3 + 0], (uint32_t)G);
-                        atomicAdd(&cnt_f[c * 3 + 0], 0u - ones - twos);
-                    }
-                    tot1 += ones;
-                    tot2 += twos;
-                    if (wg == 0) n_edges += 1;
-                }
+                const uint32_t ones = __popc(v.x & 0x01010101u) + __popc(v.y & 0x01010101u) + __popc(v.z & 0x01010101u) +
+                                      __popc(v.w & 0x01010101u);
+                const uint32_t twos = __popc(v.x & 0x02020202u) + __popc(v.y & 0x02020202u) + __popc(v.z & 0x02020202u) +
+                                      __popc(v.w & 0x02020202u);
+                p[t] = ones | (twos << 16);
+            }
+            const uint32_t s = fcd_wave_sum4(p, lane);
+            s1 += s & 0xFFFFu;
+            s2 += s >> 16;
+        }
+        // the pooled totals as wave-uniform sums (lanes 0 .. 3 hold the four edges); every owner takes its edge's pair
+#pragma unroll
+        for (int t = 0; t < TE; ++t) {
+            if (t < ne) {      // (an edge past the last was read as a copy of the last)
+                tot1 += (uint32_t)__builtin_amdgcn_readlane((int)s1, t);
+                tot2 += (uint32_t)__builtin_amdgcn_readlane((int)s2, t);
             }
         }
+        const uint32_t ones = __shfl(s1, own_e, 64), twos = __shfl(s2, own_e, 64);
+        const uint32_t add = own_j == 0 ? (uint32_t)G - ones - twos : (own_j == 1 ? ones : twos);
+        n_edges += (unsigned long long)ne;
+        if (owner) cnt_f[c0 * 3 + lane] = old + add;
     }
     if (!a.acc) return;
     // one set of atomics per workgroup (same-address atomics serialise): wave sums -> LDS -> threads 0..2

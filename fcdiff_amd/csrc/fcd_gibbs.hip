@@ -981,7 +981,7 @@ struct tally_args {
     int n_r_blocks;                    // blocks that count the r bits (at least; the f blocks do too); the rest make r_U (and r_S)
 };
 
-__global__ __launch_bounds__(1024) void gibbs_tally_kernel(const tally_args a) {
+__global__ __launch_bounds__(1024, 8) void gibbs_tally_kernel(const tally_args a) {
     __shared__ unsigned long long red[16], redf[16][3];
     __shared__ int sh_last;
     const uint8_t *__restrict__ f_state = a.f_state;
