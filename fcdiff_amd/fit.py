@@ -37,7 +37,8 @@ import numpy as np
 from . import _lib
 from . import util
 from . import score as _score
-from .gibbs import GibbsEngine, run_chains, allreduce_counts, pair_sweeps_in, PAIR_COUNT_MAX, COUNT_MAX_NREG, COUNT_MAX_U
+from . import tables
+from .gibbs import GibbsEngine, run_chains, allreduce_counts, pool_u32, pair_sweeps_in, PAIR_COUNT_MAX, COUNT_MAX_NREG, COUNT_MAX_U
 
 
 class UnsharedRegionFit(object):
@@ -52,6 +53,10 @@ class UnsharedRegionFit(object):
     energy : list of float                      variational free energy per iteration (vb) or minus the
                                                 chain-mean log-joint per recorded sweep (gibbs)
     """
+
+    # SharedRegionFit: the tables are (S_B, L) of ONE patient (tables.build(shared=True)), so the state's patient extent is 1,
+    # there are no per-item tables, and _init_lps fills _lM with 0 (here the reference's 1)
+    _shared = False
 
     def __init__(self):
         self.model = None
@@ -93,9 +98,7 @@ class UnsharedRegionFit(object):
         self.missing_data = False
 
         self._ctx = None
-        self._score_ctx = None    # score(): a context of its own, so that scoring never touches the fit's workspace or plan
-        self._evidence_ctx = None # log_evidence(): the same
-        self._member_ctx = None   # membership(): the same
+        self._query_ctx = None    # score(), log_evidence(), membership(): one context apart from the fit's (_query_context)
         self._d = {}              # device tensors: lq_R, lq_F, S_B, lM, lpB, pBt, hyper, b, bt
         self._hyper_key = None
 
@@ -104,6 +107,16 @@ class UnsharedRegionFit(object):
         if self._ctx is None:
             self._ctx = _lib.Context()
         return self._ctx
+
+    def _query_context(self):
+        """
+        The context of score(), log_evidence() and membership(): never the fit's, so that a query touches neither the fit's
+        workspace nor its plan.  One serves all three: they run one after another on one stream and use the workspace only
+        inside a call.
+        """
+        if self._query_ctx is None:
+            self._query_ctx = _lib.Context()
+        return self._query_ctx
 
     def _torch(self):
         import torch
@@ -115,6 +128,20 @@ class UnsharedRegionFit(object):
     def _up(self, a):
         t = self._torch()
         return t.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=self._dev())
+
+    def _data_dev(self, key):
+        """The device copy of self.b (key 'b') or self.bt ('bt'): the fit's own where its shape still holds, else a fresh upload
+        (not kept: a query leaves the fit as it was)."""
+        (d, a) = (self._d.get(key), getattr(self, key))
+        if d is None or tuple(d.shape) != np.shape(a):
+            d = self._up(a)
+        return d
+
+    def _require_fitted(self, what):
+        """ValueError unless run() has left a fit of self.method behind: a sampler (gibbs), or q_F and an energy (vb)."""
+        fitted = (self.sampler is not None) if self.method == "gibbs" else (self._d.get("lq_F") is not None and bool(self.energy))
+        if self.model is None or not fitted:
+            raise ValueError("%s needs a fitted model: call run() first" % what)
 
     def _edge_mode(self):
         name = self.edge_index
@@ -164,9 +191,7 @@ class UnsharedRegionFit(object):
         pi2 = self._pi2()
         key = (tuple(gamma.tolist()), tuple(pi2.tolist()))
         if key != self._hyper_key:
-            (g, _g) = _lib.dbl_array(gamma)
-            (p, _p) = _lib.dbl_array(pi2)
-            self._context().call("fcd_hyper_set", _lib.dptr(self._d["hyper"]), g, p, _lib.stream_ptr())
+            tables.write_hyper(self._context(), self._d["hyper"], gamma, pi2)
             self._hyper_key = key
         return self._d["hyper"]
 
@@ -271,20 +296,21 @@ class UnsharedRegionFit(object):
         t = self._torch()
         dev = self._dev()
         C = util.N_to_C(N)
-        self._d["lq_R"] = t.full((N, U, 2), -np.log(2), dtype=t.float64, device=dev)
+        Ut = 1 if self._shared else U
+        self._d["lq_R"] = t.full((N, Ut, 2), -np.log(2), dtype=t.float64, device=dev)
         self._d["lq_F"] = t.full((C, 1, 3), -np.log(3), dtype=t.float64, device=dev)
         self._d["S_B"] = t.full((C, 3), float(H), dtype=t.float64, device=dev)
-        self._d["lM"] = t.ones((C, U, 3, 3), dtype=t.float64, device=dev)
+        self._d["lM"] = t.full((C, Ut, 3, 3), 0.0 if self._shared else 1.0, dtype=t.float64, device=dev)
         self._d["lpB"] = None
         self._d["pBt"] = None
         self._d.pop("data_key", None)        # a fit starts from the arrays as they are now (see _tables)
-        self._HU = (H, U)
 
     def _update_lps(self):
-        """Likelihood tables from the current parameters (fit.py:104-122): kernel K_lik."""
+        """Likelihood tables from the current parameters (fit.py:104-122): kernel K_lik (K_lik_shared for SharedRegionFit)."""
         self._tables(full=False)
 
     def _tables(self, full):
+        """S_B and lM (full: the per-item tables lpB, pBt too, where the model has them) in ONE launch: tables.build."""
         t = self._torch()
         dev = self._dev()
         b = np.ascontiguousarray(self.b, dtype=np.float64)
@@ -303,32 +329,29 @@ class UnsharedRegionFit(object):
         if uploaded:
             self._d["b"], self._d["bt"] = self._up(b), self._up(bt)
             self._d["data_key"] = key
-        if self._d.get("S_B") is None or tuple(self._d["S_B"].shape) != (C, 3):
-            self._d["S_B"] = t.empty((C, 3), dtype=t.float64, device=dev)
-        if self._d.get("lM") is None or tuple(self._d["lM"].shape) != (C, U, 3, 3):
-            self._d["lM"] = t.empty((C, U, 3, 3), dtype=t.float64, device=dev)
+        # the buffers are kept when their shape holds: a sampler built on them reads the new tables after refresh_tables()
+        (S_B, lM) = (self._d.get("S_B"), self._d.get("lM"))
+        if S_B is not None and tuple(S_B.shape) != (C, 3):
+            S_B = None
+        if lM is not None and tuple(lM.shape) != (C, 1 if self._shared else U, 3, 3):
+            lM = None
         lpB = pBt = None
-        if full:
+        if full and not self._shared:
             lpB = t.empty((C, H, 3), dtype=t.float64, device=dev)
             pBt = t.empty((C, U, 3), dtype=t.float64, device=dev)
-        (th, _th) = _lib.dbl_array(self.model.theta())
+        n_missing = None
         if self.missing_data:
             # the kernel counts the NaN entries on the device; missing_counts() reads them when asked (no sync here).  The
             # counts depend on the data alone, so they are taken when the data is uploaded: the counting build waits for
             # its atomics (5-39 us more at cfg3 with 10 % NaN), the per-iteration builds after it run at the uncounted speed
-            count = uploaded or not self._d.get("n_missing_valid")
             if self._d.get("n_missing") is None:
                 self._d["n_missing"] = t.zeros(2, dtype=t.int64, device=dev)
-            self._context().call("fcd_lik_tables_ex", _lib.dptr(self._d["b"]), _lib.dptr(self._d["bt"]), C, H, U, th,
-                                 _lib.dptr(self._d["S_B"]), _lib.dptr(self._d["lM"]), _lib.dptr(lpB), _lib.dptr(pBt),
-                                 _lib.FCD_DATA_NAN_MISSING, _lib.dptr(self._d["n_missing"] if count else None),
-                                 _lib.stream_ptr())
-            self._d["n_missing_valid"] = True
-        else:
-            self._context().call("fcd_lik_tables", _lib.dptr(self._d["b"]), _lib.dptr(self._d["bt"]), C, H, U, th,
-                                 _lib.dptr(self._d["S_B"]), _lib.dptr(self._d["lM"]), _lib.dptr(lpB), _lib.dptr(pBt),
-                                 _lib.stream_ptr())
-            self._d["n_missing_valid"] = False
+            if uploaded or not self._d.get("n_missing_valid"):
+                n_missing = self._d["n_missing"]
+        (self._d["S_B"], self._d["lM"]) = tables.build(self._context(), self._d["b"], self._d["bt"], self.model.theta(),
+                                                       self._flags(), shared=self._shared, S_B=S_B, lM=lM, lpB=lpB, pBt=pBt,
+                                                       n_missing=n_missing)
+        self._d["n_missing_valid"] = bool(self.missing_data)
         self._d["lpB"], self._d["pBt"] = lpB, pBt
 
     def _flags(self):
@@ -548,23 +571,11 @@ class UnsharedRegionFit(object):
         self.connection_counts = None
         self.connection_sweeps = 0
         if self.connection_marginals:
-            every = int(self.connection_every)
-            if every < 1 or every != self.connection_every:
-                raise ValueError("connection_every must be an integer >= 1")
-            n_acc = pair_sweeps_in(0, int(self.n_sweeps), int(self.burn_in), every)
-            if n_acc * int(self.n_chains) > PAIR_COUNT_MAX:
-                raise ValueError("connection counts would overflow uint32: %d chains x %d accumulated sweeps; raise "
-                                 "connection_every" % (self.n_chains, n_acc))
+            self._check_accumulator("connection_every", "connection counts")
         self.patient_count_hist = self.region_count_hist = None
         self.anomaly_count_sweeps = 0
         if self.anomaly_counts:
-            every = int(self.anomaly_counts_every)
-            if every < 1 or every != self.anomaly_counts_every:
-                raise ValueError("anomaly_counts_every must be an integer >= 1")
-            n_acc = pair_sweeps_in(0, int(self.n_sweeps), int(self.burn_in), every)
-            if n_acc * int(self.n_chains) > PAIR_COUNT_MAX:
-                raise ValueError("anomaly-count histograms would overflow uint32: %d chains x %d accumulated sweeps; raise "
-                                 "anomaly_counts_every" % (self.n_chains, n_acc))
+            self._check_accumulator("anomaly_counts_every", "anomaly-count histograms")
             if N > COUNT_MAX_NREG or U > COUNT_MAX_U:
                 raise ValueError("anomaly-count histograms are made for at most %d regions and %d patients (here %d, %d)"
                                  % (COUNT_MAX_NREG, COUNT_MAX_U, N, U))
@@ -626,12 +637,10 @@ class UnsharedRegionFit(object):
             p1 = cnt[3 * C:3 * C + N * U].reshape(N, U) / total
             self._lq_R = np.log(np.stack([1.0 - p1, p1], axis=2))
         if eng.pair_acc is not None:
-            # (uint32 on the device; pooled over ranks as int64)
-            pc = allreduce_counts(eng.pair_acc.to(t.int64) & 0xFFFFFFFF)
-            self.connection_counts = pc.cpu().numpy()
+            self.connection_counts = pool_u32(eng.pair_acc).cpu().numpy()
             self.connection_sweeps = eng.pair_sweeps
         if eng.count_hist is not None:
-            (hp, hr) = (allreduce_counts(h.to(t.int64) & 0xFFFFFFFF) for h in eng.count_hist)
+            (hp, hr) = (pool_u32(h) for h in eng.count_hist)
             self.patient_count_hist = hp.cpu().numpy()
             self.region_count_hist = hr.cpu().numpy()
             self.anomaly_count_sweeps = eng.count_sweeps
@@ -639,7 +648,34 @@ class UnsharedRegionFit(object):
         self.model.gamma = gamma
         self.model.pi = pi
 
+    def _check_accumulator(self, knob, what):
+        """A uint32 accumulator of the gibbs run: its period self.<knob> is an integer >= 1 and, at that period, chains x
+        accumulated sweeps fit the counter."""
+        every = getattr(self, knob)
+        if int(every) < 1 or int(every) != every:
+            raise ValueError("%s must be an integer >= 1" % knob)
+        n_acc = pair_sweeps_in(0, int(self.n_sweeps), int(self.burn_in), int(every))
+        if n_acc * int(self.n_chains) > PAIR_COUNT_MAX:
+            raise ValueError("%s would overflow uint32: %d chains x %d accumulated sweeps; raise %s"
+                             % (what, self.n_chains, n_acc, knob))
+
     # ------------------------------------------------------------------ connection-level posteriors
+    def _connection_counts_dev(self):
+        """
+        (counts, N, C): `connection_counts` (C, U, 3, 3) of the last gibbs run as the uint32-in-int32 device tensor
+        conn_posterior() takes; ValueError where there are none, nothing was accumulated or a pooled count is over uint32.
+        """
+        cnt = self.connection_counts
+        if cnt is None:
+            raise ValueError("no connection counts: set connection_marginals = True before run(method='gibbs')")
+        cnt = np.asarray(cnt)
+        if int(cnt[0, 0].sum()) == 0:
+            raise ValueError("no sweep was accumulated into the connection counts (n_sweeps <= burn_in?)")
+        if int(cnt.max()) > PAIR_COUNT_MAX:
+            raise ValueError("pooled connection counts exceed uint32; raise connection_every")
+        counts = self._torch().as_tensor(np.ascontiguousarray(cnt.astype(np.uint32).view(np.int32)), device=self._dev())
+        return counts, int(util.C_to_N(cnt.shape[0])), cnt.shape[0]
+
     def connection_posterior(self):
         """
         Posterior of the anomalous connections and of each patient's connection state, per connection and patient (edge
@@ -661,21 +697,12 @@ class UnsharedRegionFit(object):
         With missing_data = True a NaN bt[c,u] takes N_j = 1 in the closed forms: the prior law of T and F~ given (k, l),
         averaged over the same weights.
         """
-        t = self._torch()
         if self.model is None or self.bt is None:
             raise ValueError("connection_posterior() needs a model and bt: call run() first")
         if self.method == "gibbs":
-            cnt = self.connection_counts
-            if cnt is None:
-                raise ValueError("no connection counts: set connection_marginals = True before run(method='gibbs')")
-            cnt = np.asarray(cnt)
-            if int(cnt[0, 0].sum()) == 0:
-                raise ValueError("no sweep was accumulated into the connection counts (n_sweeps <= burn_in?)")
-            if int(cnt.max()) > PAIR_COUNT_MAX:
-                raise ValueError("pooled connection counts exceed uint32; raise connection_every")
-            (N, C, U) = (util.C_to_N(cnt.shape[0]), cnt.shape[0], cnt.shape[1])
-            counts = t.as_tensor(np.ascontiguousarray(cnt.astype(np.uint32).view(np.int32)), device=self._dev())
-            return conn_posterior(self._context(), self._bt_dev(C, U), int(N), U, self.model.theta(), counts=counts,
+            (counts, N, C) = self._connection_counts_dev()
+            U = int(counts.shape[1])
+            return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), counts=counts,
                                   missing_data=self.missing_data)
         if self.method != "vb":
             raise ValueError("method must be 'vb' or 'gibbs'")
@@ -756,9 +783,7 @@ class UnsharedRegionFit(object):
         """
         if self.method not in ("vb", "gibbs"):
             raise ValueError("method must be 'vb' or 'gibbs'")
-        fitted = (self.sampler is not None) if self.method == "gibbs" else (self._d.get("lq_F") is not None and bool(self.energy))
-        if self.model is None or not fitted:
-            raise ValueError("score() needs a fitted model: call run() first")
+        self._require_fitted("score()")
         bt_new = np.ascontiguousarray(bt_new, dtype=np.float64)
         if bt_new.ndim != 2:
             raise ValueError("bt_new must be (C, U'), got shape %s" % (bt_new.shape,))
@@ -780,12 +805,8 @@ class UnsharedRegionFit(object):
                 raise ValueError("score() tallies would overflow uint32: %d chains x %d sweeps" % (self.sampler.G, n_sweeps))
         elif int(max_iters) < 1:
             raise ValueError("max_iters must be >= 1")
-        if self._score_ctx is None:
-            self._score_ctx = _lib.Context()
-        ctx = self._score_ctx
-        b_dev = self._d.get("b")
-        if b_dev is None or tuple(b_dev.shape)[0] != C:
-            b_dev = self._up(self.b)
+        ctx = self._query_context()
+        b_dev = self._data_dev("b")
         bt_dev = self._up(bt_new)
         if self.method == "vb":
             return _score.score_vb(ctx, b_dev, bt_dev, N, self._d["lq_F"], self.model, self._pi2(), self._edge_mode(),
@@ -827,13 +848,9 @@ class UnsharedRegionFit(object):
         (x_new, N) = self._membership_input(x_new)
         if int(n_anneal) < 1:
             raise ValueError("n_anneal must be >= 1")
-        ctx = self._membership_context()
-        b_dev = self._d.get("b")
-        if b_dev is None or tuple(b_dev.shape)[0] != x_new.shape[0]:
-            b_dev = self._up(self.b)
         key = _score.score_key(self.seed if seed is None else seed)
-        return _membership.membership(ctx, self._up, x_new, N, self.sampler, self.model, self.missing_data, False, b_dev=b_dev,
-                                      pi2=self._pi2(), n_anneal=int(n_anneal), key=key)
+        return _membership.membership(self._query_context(), self._up, x_new, N, self.sampler, self.model, self.missing_data,
+                                      False, b_dev=self._data_dev("b"), pi2=self._pi2(), n_anneal=int(n_anneal), key=key)
 
     def _membership_input(self, x_new):
         """The checks of membership(), before anything touches the device: (x_new (C, U') float64, Nreg)."""
@@ -842,8 +859,7 @@ class UnsharedRegionFit(object):
                              "patient side, and a difference of bounds is not a bound")
         if self.method != "gibbs":
             raise ValueError("method must be 'gibbs'")
-        if self.model is None or self.sampler is None:
-            raise ValueError("membership() needs a fitted model: call run() first")
+        self._require_fitted("membership()")
         if self._edge_mode() != "symmetric":
             raise ValueError("membership() needs edge_index 'symmetric'")
         x_new = np.ascontiguousarray(x_new, dtype=np.float64)
@@ -855,11 +871,6 @@ class UnsharedRegionFit(object):
         if U < 1:
             raise ValueError("x_new holds no subject")
         return x_new, int(util.C_to_N(C))
-
-    def _membership_context(self):
-        if self._member_ctx is None:
-            self._member_ctx = _lib.Context()
-        return self._member_ctx
 
     # ------------------------------------------------------------------ model evidence
     def log_evidence(self, n_anneal=1000, n_chains=None, seed=None):
@@ -906,36 +917,26 @@ class UnsharedRegionFit(object):
         G = self.n_chains if n_chains is None else n_chains
         if int(G) != G or int(G) < 1:
             raise ValueError("n_chains must be an integer >= 1")
-        fitted = (self.sampler is not None) if self.method == "gibbs" else (self._d.get("lq_F") is not None and bool(self.energy))
-        if self.model is None or self.b is None or self.bt is None or not fitted:
-            raise ValueError("log_evidence() needs a fitted model: call run() first")
+        self._require_fitted("log_evidence()")
+        if self.b is None or self.bt is None:
+            raise ValueError("log_evidence() needs b and bt: call run() first")
         chain0 = int(self.chain0)
         if n_chains is not None:
             import torch.distributed as dist
             chain0 = dist.get_rank() * int(G) if (dist.is_available() and dist.is_initialized()) else 0
-        if self._evidence_ctx is None:
-            self._evidence_ctx = _lib.Context()
-        ctx = self._evidence_ctx
-        (S_B, lM) = self._evidence_tables(ctx)
+        ctx = self._query_context()
+        # fresh tables of the current theta on the query context: the fit's own are not touched
+        (S_B, lM) = tables.build(ctx, self._data_dev("b"), self._data_dev("bt"), self.model.theta(), self._flags(),
+                                 shared=self._shared)
         (C, U) = (int(lM.shape[0]), int(lM.shape[1]))
         key = _evidence.evidence_key(self.seed if seed is None else seed)
         return _evidence.log_evidence(ctx, S_B, lM, int(util.C_to_N(C)), U, self.model.gamma, self._pi2(), int(n_anneal), int(G),
                                       chain0, key)
 
-    def _evidence_tables(self, ctx):
-        """Fresh (S_B (C, 3), lM (C, U, 3, 3)) of the model's current theta on `ctx`; the fit's own tables are not touched."""
-        b = self._d.get("b")
-        bt = self._d.get("bt")
-        if b is None or bt is None or tuple(b.shape) != np.shape(self.b) or tuple(bt.shape) != np.shape(self.bt):
-            (b, bt) = (self._up(self.b), self._up(self.bt))
-        return _score.lik_tables(ctx, b, bt, self.model.theta(), self.missing_data)
-
     def _bt_dev(self, C, U):
-        bt = self._d.get("bt")
-        if bt is None or tuple(bt.shape) != (C, U):
-            bt = self._up(self.bt)
-            if tuple(bt.shape) != (C, U):
-                raise ValueError("bt has shape %s, the fit's state needs %s" % (tuple(bt.shape), (C, U)))
+        bt = self._data_dev("bt")
+        if tuple(bt.shape) != (C, U):
+            raise ValueError("bt has shape %s, the fit's state needs %s" % (tuple(bt.shape), (C, U)))
         return bt
 
 
@@ -954,6 +955,8 @@ class SharedRegionFit(UnsharedRegionFit):
     with its edge's (C, 1, 3, 3) weights (FCD_W_PER_EDGE).
     """
 
+    _shared = True
+
     def __init__(self):
         super(SharedRegionFit, self).__init__()
         self.edge_index = "symmetric"
@@ -970,65 +973,6 @@ class SharedRegionFit(UnsharedRegionFit):
         """Builds S_B and L, then the VB loop or the sampler at U = 1 (see the class docstring)."""
         self._edge_mode()
         super(SharedRegionFit, self).run()
-
-    def _init_lps(self, N, H, U):
-        t = self._torch()
-        dev = self._dev()
-        C = util.N_to_C(N)
-        self._d["lq_R"] = t.full((N, 1, 2), -np.log(2), dtype=t.float64, device=dev)
-        self._d["lq_F"] = t.full((C, 1, 3), -np.log(3), dtype=t.float64, device=dev)
-        self._d["S_B"] = t.full((C, 3), float(H), dtype=t.float64, device=dev)
-        self._d["lM"] = t.zeros((C, 1, 3, 3), dtype=t.float64, device=dev)
-        self._d["lpB"] = None
-        self._d["pBt"] = None
-        self._d.pop("data_key", None)
-        self._HU = (H, U)
-
-    def _tables(self, full):
-        """S_B (C,3) and L (C,1,3,3) from the current parameters: kernel K_lik_shared (ONE launch, no C*U buffer)."""
-        t = self._torch()
-        dev = self._dev()
-        b = np.ascontiguousarray(self.b, dtype=np.float64)
-        bt = np.ascontiguousarray(self.bt, dtype=np.float64)
-        (C, H) = b.shape
-        U = bt.shape[1]
-        key = (self._array_key(self.b), self._array_key(self.bt), self._data_digest(b, self.data_check),
-               self._data_digest(bt, self.data_check))
-        uploaded = self._d.get("data_key") != key
-        if uploaded:
-            self._d["b"], self._d["bt"] = self._up(b), self._up(bt)
-            self._d["data_key"] = key
-        # the buffers are kept when their shape holds: a sampler built on them reads the new tables after refresh_tables()
-        if self._d.get("S_B") is None or tuple(self._d["S_B"].shape) != (C, 3):
-            self._d["S_B"] = t.empty((C, 3), dtype=t.float64, device=dev)
-        if self._d.get("lM") is None or tuple(self._d["lM"].shape) != (C, 1, 3, 3):
-            self._d["lM"] = t.empty((C, 1, 3, 3), dtype=t.float64, device=dev)
-        (th, _th) = _lib.dbl_array(self.model.theta())
-        count = False
-        if self.missing_data:
-            count = uploaded or not self._d.get("n_missing_valid")
-            if self._d.get("n_missing") is None:
-                self._d["n_missing"] = t.zeros(2, dtype=t.int64, device=dev)
-        self._context().call("fcd_lik_shared_tables", _lib.dptr(self._d["b"]), _lib.dptr(self._d["bt"]), C, H, U, th,
-                             _lib.dptr(self._d["S_B"]), _lib.dptr(self._d["lM"]), self._flags(),
-                             _lib.dptr(self._d["n_missing"] if count else None), _lib.stream_ptr())
-        self._d["n_missing_valid"] = bool(self.missing_data)
-        self._d["lpB"], self._d["pBt"] = None, None     # the per-item tables are never made here
-
-    def _evidence_tables(self, ctx):
-        """Fresh (S_B (C, 3), L (C, 1, 3, 3)) of the model's current theta on `ctx` (fcd_lik_shared_tables)."""
-        t = self._torch()
-        b = self._d.get("b")
-        bt = self._d.get("bt")
-        if b is None or bt is None or tuple(b.shape) != np.shape(self.b) or tuple(bt.shape) != np.shape(self.bt):
-            (b, bt) = (self._up(self.b), self._up(self.bt))
-        (C, H) = (int(b.shape[0]), int(b.shape[1]))
-        S_B = t.empty((C, 3), dtype=t.float64, device=bt.device)
-        L = t.empty((C, 1, 3, 3), dtype=t.float64, device=bt.device)
-        (th, _th) = _lib.dbl_array(self.model.theta())
-        ctx.call("fcd_lik_shared_tables", _lib.dptr(b), _lib.dptr(bt), C, H, int(bt.shape[1]), th, _lib.dptr(S_B), _lib.dptr(L),
-                 self._flags(), _lib.dptr(None), _lib.stream_ptr())
-        return S_B, L
 
     def _theta_sub_flags(self):
         return {"missing_data": self.missing_data, "per_edge": True}
@@ -1057,23 +1001,12 @@ class SharedRegionFit(UnsharedRegionFit):
           method='gibbs'  the (C, 1, 3, 3) counts of (f_c, mixture case) broadcast to (C, U, 3, 3) (needs
                           connection_marginals = True before run()).
         """
-        t = self._torch()
         if self.model is None or self.bt is None:
             raise ValueError("connection_posterior() needs a model and bt: call run() first")
         U = self._patients()
         if self.method == "gibbs":
-            cnt = self.connection_counts
-            if cnt is None:
-                raise ValueError("no connection counts: set connection_marginals = True before run(method='gibbs')")
-            cnt = np.asarray(cnt)
-            if int(cnt[0, 0].sum()) == 0:
-                raise ValueError("no sweep was accumulated into the connection counts (n_sweeps <= burn_in?)")
-            if int(cnt.max()) > PAIR_COUNT_MAX:
-                raise ValueError("pooled connection counts exceed uint32; raise connection_every")
-            C = cnt.shape[0]
-            N = int(util.C_to_N(C))
-            wide = np.ascontiguousarray(np.broadcast_to(cnt.astype(np.uint32), (C, U, 3, 3)))
-            counts = t.as_tensor(wide.view(np.int32), device=self._dev())
+            (counts, N, C) = self._connection_counts_dev()
+            counts = counts.expand(C, U, 3, 3).contiguous()
             return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), counts=counts,
                                   missing_data=self.missing_data)
         if self.method != "vb":
@@ -1123,7 +1056,7 @@ class SharedRegionFit(UnsharedRegionFit):
         """
         from . import membership as _membership
         (x_new, N) = self._membership_input(x_new)
-        return _membership.membership(self._membership_context(), self._up, x_new, N, self.sampler, self.model,
+        return _membership.membership(self._query_context(), self._up, x_new, N, self.sampler, self.model,
                                       self.missing_data, True)
 
 

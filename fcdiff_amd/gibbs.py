@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import tables
 from . import util
 
 
@@ -46,6 +47,15 @@ def allreduce_counts(counts, group=None):
     return counts
 
 
+def pool_u32(t):
+    """
+    The sampler's tallies are uint32 held in int32 tensors (torch has no uint32 arithmetic): their values as int64, summed
+    over ranks.  Every host read of such a tally that pools goes through here.
+    """
+    import torch
+    return allreduce_counts(t.to(torch.int64) & 0xFFFFFFFF)
+
+
 def mstep_from_counts(counts, Nreg, U):
     """Host restatement of fcd_gibbs_mstep (used to report pi/gamma; the device keeps its own copy)."""
     counts = [int(x) for x in counts]
@@ -61,9 +71,9 @@ class GibbsEngine(object):
     """
     Device-resident state of G chains and the kernels that move it.
 
-    S_B (C,3) and lM (C,U,3,3) are float64 CUDA tensors produced by `fcd_lik_tables`; they are shared by
-    all chains.  State layout (include/fcdiff_hip.h): f_state (GW, C, 64) uint8, r_bits (GW, Nreg, U)
-    uint64 bit planes (held in an int64 tensor), GW = ceil(G / 64).
+    S_B (C,3) and lM (C,U,3,3) are float64 CUDA tensors produced by `tables.build` (fcd_lik_tables_ex, or
+    fcd_lik_shared_tables at U = 1); they are shared by all chains.  State layout (include/fcdiff_hip.h):
+    f_state (GW, C, 64) uint8, r_bits (GW, Nreg, U) uint64 bit planes (held in an int64 tensor), GW = ceil(G / 64).
     """
 
     def __init__(self, S_B, lM, Nreg, U, n_chains, chain0=0, seed=0, edge_index="symmetric", ctx=None,
@@ -111,9 +121,7 @@ class GibbsEngine(object):
 
     # ---- hyper-parameters ----
     def set_hyper(self, gamma, pi2):
-        (g, _g) = _lib.dbl_array(gamma)
-        (p, _p) = _lib.dbl_array(pi2)
-        self.ctx.call("fcd_hyper_set", _lib.dptr(self.hyper), g, p, _lib.stream_ptr())
+        tables.write_hyper(self.ctx, self.hyper, gamma, pi2)
 
     def hyper_values(self):
         h = self.hyper.cpu().numpy()

@@ -15,7 +15,7 @@ subjects, so apart from a chunk's own buffers nothing on the device grows with i
 import numpy as np
 
 from . import _lib
-from .score import ais_weights, gather_rows, pool_ais
+from .score import ais_weights, chain_parts, pool_ais
 
 CHUNK = 256         # subjects per device pass: (G, CHUNK) outputs per side, and the unshared side's (C, CHUNK, 3, 3) tables
 
@@ -31,15 +31,6 @@ def member_loglik(ctx, x_dev, theta, f_state, r_bits, Nreg, G, r_cols, missing_d
              int(G), int(r_cols), _lib.FCD_DATA_NAN_MISSING if missing_data else 0, _lib.dptr(lc), _lib.dptr(lp),
              _lib.stream_ptr())
     return lc, lp
-
-
-def chain_parts(ctx, w):
-    """(R, U, 4) NumPy: fcd_score_ais_finish of this rank's w (G, U), stacked over ranks."""
-    import torch
-    (G, U) = (int(w.shape[0]), int(w.shape[1]))
-    fin = torch.empty((U, 4), dtype=torch.float64, device=w.device)
-    ctx.call("fcd_score_ais_finish", _lib.dptr(w), U, G, _lib.dptr(fin), _lib.stream_ptr())
-    return gather_rows(fin)
 
 
 def pool(parts_patient, parts_control):

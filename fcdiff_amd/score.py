@@ -15,8 +15,9 @@ numbers (the AIS schedule, the pooling of the AIS sums over ranks) that the CPU 
 import numpy as np
 
 from . import _lib
+from . import tables
 from . import util
-from .gibbs import GibbsEngine, allreduce_counts, PAIR_COUNT_MAX
+from .gibbs import GibbsEngine, allreduce_counts, pool_u32, PAIR_COUNT_MAX
 
 # Random numbers of the scoring sampler.  Its Philox counter is (site, chain id, sweep, kind) like the fit's, and its sites
 # reuse the training patients' site indices, so with the fit's key and sweep numbers the r draws would reuse the uniforms
@@ -104,29 +105,21 @@ def gather_rows(t):
 
 def lik_tables(ctx, b_dev, bt_dev, theta, missing_data):
     """(S_B (C, 3), lM (C, U', 3, 3)) of new patients into fresh tensors (the table kernel needs H >= 1: b is the fit's)."""
-    import torch
-    (C, H) = (int(b_dev.shape[0]), int(b_dev.shape[1]))
-    U = int(bt_dev.shape[1])
-    dev = bt_dev.device
-    S_B = torch.empty((C, 3), dtype=torch.float64, device=dev)
-    lM = torch.empty((C, U, 3, 3), dtype=torch.float64, device=dev)
-    (th, _th) = _lib.dbl_array(theta)
-    if missing_data:
-        ctx.call("fcd_lik_tables_ex", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, th, _lib.dptr(S_B), _lib.dptr(lM),
-                 _lib.dptr(None), _lib.dptr(None), _lib.FCD_DATA_NAN_MISSING, _lib.dptr(None), _lib.stream_ptr())
-    else:
-        ctx.call("fcd_lik_tables", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, th, _lib.dptr(S_B), _lib.dptr(lM),
-                 _lib.dptr(None), _lib.dptr(None), _lib.stream_ptr())
-    return S_B, lM
+    return tables.build(ctx, b_dev, bt_dev, theta, _lib.FCD_DATA_NAN_MISSING if missing_data else 0)
 
 
 def hyper_block(ctx, gamma, pi2, device):
     import torch
-    hyper = torch.zeros(8, dtype=torch.float64, device=device)
-    (g, _g) = _lib.dbl_array(np.asarray(gamma, dtype=np.float64).reshape(3))
-    (p, _p) = _lib.dbl_array(np.asarray(pi2, dtype=np.float64).reshape(2))
-    ctx.call("fcd_hyper_set", _lib.dptr(hyper), g, p, _lib.stream_ptr())
-    return hyper
+    return tables.write_hyper(ctx, torch.zeros(8, dtype=torch.float64, device=device), gamma, pi2)
+
+
+def chain_parts(ctx, w):
+    """(R, U, 4) NumPy: fcd_score_ais_finish of this rank's log-weights w (G, U), stacked over ranks (for pool_ais)."""
+    import torch
+    (G, U) = (int(w.shape[0]), int(w.shape[1]))
+    fin = torch.empty((U, 4), dtype=torch.float64, device=w.device)
+    ctx.call("fcd_score_ais_finish", _lib.dptr(w), U, G, _lib.dptr(fin), _lib.stream_ptr())
+    return gather_rows(fin)
 
 
 def patient_elbo(ctx, lq_F, lq_R, lM, hyper, Nreg, U):
@@ -230,8 +223,6 @@ def score_gibbs(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, con
     G = sampler.G
     theta = model.theta()
     (eng, lM, region_tables, w, sweep) = ais_weights(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, n_anneal, key)
-    fin = torch.empty((U, 4), dtype=torch.float64, device=bt_dev.device)
-    ctx.call("fcd_score_ais_finish", _lib.dptr(w), U, G, _lib.dptr(fin), _lib.stream_ptr())
     # beta = 1: the untempered table (bit for bit what the last AIS step wrote) and its region-major difference table
     eng.lM = lM
     region_tables(lM)
@@ -247,9 +238,9 @@ def score_gibbs(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, con
             eng.pair_tally(acc)
     # pooled over this rank's chains and, when the fit was sharded, over every rank's
     n_chains = allreduce_counts(torch.tensor([G], dtype=torch.int64, device=bt_dev.device)).cpu().numpy()
-    cnt_r = allreduce_counts(eng.cnt_r.to(torch.int64) & 0xFFFFFFFF)
-    hp = allreduce_counts(hp.to(torch.int64) & 0xFFFFFFFF).cpu().numpy().astype(np.float64)
-    parts = gather_rows(fin)
+    cnt_r = pool_u32(eng.cnt_r)
+    hp = pool_u32(hp).cpu().numpy().astype(np.float64)
+    parts = chain_parts(ctx, w)
     p_R = cnt_r.cpu().numpy().astype(np.float64) / (float(n_chains[0]) * int(n_sweeps))
     ctx.check_device()
     p_patient = hp / hp.sum(axis=1, keepdims=True)
@@ -257,7 +248,7 @@ def score_gibbs(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, con
     out = {"p_R": p_R, "p_patient_count": p_patient, "p_patient_any": 1.0 - p_patient[:, 0], "log_pred": log_pred,
            "log_pred_se": se, "ess": ess}
     if connections:
-        pc = allreduce_counts(acc.to(torch.int64) & 0xFFFFFFFF).cpu().numpy()
+        pc = pool_u32(acc).cpu().numpy()
         if int(pc.max()) > PAIR_COUNT_MAX:
             raise ValueError("pooled connection counts exceed uint32: fewer sweeps or chains")
         out["connection_counts"] = pc

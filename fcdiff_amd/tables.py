@@ -1,0 +1,44 @@
+"""
+The two small device blocks every fit and query starts from, each written by ONE host function:
+  build        the likelihood tables (S_B, lM) of a theta -- the only caller of the table kernels in the package;
+  write_hyper  the hyper block {ln gamma, ln(1 - pi), ln pi}.
+A new feature that needs tables or a hyper block calls these; a new table variant is a new argument of build().
+"""
+import numpy as np
+
+from . import _lib
+
+
+def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB=None, pBt=None, n_missing=None):
+    """
+    (S_B (C, 3), lM) of b_dev (C, H) and bt_dev (C, U) at theta, in ONE library call on `ctx`:
+      shared=False  fcd_lik_tables_ex: lM (C, U, 3, 3) and, where given, the per-item tables lpB (C, H, 3), pBt (C, U, 3);
+      shared=True   fcd_lik_shared_tables: lM is L (C, 1, 3, 3), the sum over patients (no per-item tables).
+    S_B and lM are written in place where given (a sampler built on them reads the new tables after refresh_tables()) and
+    allocated where not.  flags: 0 or _lib.FCD_DATA_NAN_MISSING; with flags = 0 and n_missing = None the unshared call is
+    the plain fcd_lik_tables, argument for argument.  n_missing: (2,) int64 device tensor the kernel adds the NaN counts of
+    b and bt to (a counting build waits for its atomics), or None.
+    """
+    import torch
+    (C, H) = (int(b_dev.shape[0]), int(b_dev.shape[1]))
+    U = int(bt_dev.shape[1])
+    if S_B is None:
+        S_B = torch.empty((C, 3), dtype=torch.float64, device=bt_dev.device)
+    if lM is None:
+        lM = torch.empty((C, 1 if shared else U, 3, 3), dtype=torch.float64, device=bt_dev.device)
+    (th, _th) = _lib.dbl_array(theta)
+    if shared:
+        ctx.call("fcd_lik_shared_tables", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, th, _lib.dptr(S_B), _lib.dptr(lM),
+                 int(flags), _lib.dptr(n_missing), _lib.stream_ptr())
+    else:
+        ctx.call("fcd_lik_tables_ex", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, th, _lib.dptr(S_B), _lib.dptr(lM),
+                 _lib.dptr(lpB), _lib.dptr(pBt), int(flags), _lib.dptr(n_missing), _lib.stream_ptr())
+    return S_B, lM
+
+
+def write_hyper(ctx, hyper, gamma, pi2):
+    """Writes {ln gamma[3], ln pi2[2]} into the (8,) float64 device block `hyper` (fcd_hyper_set); returns it."""
+    (g, _g) = _lib.dbl_array(np.asarray(gamma, dtype=np.float64).reshape(3))
+    (p, _p) = _lib.dbl_array(np.asarray(pi2, dtype=np.float64).reshape(2))
+    ctx.call("fcd_hyper_set", _lib.dptr(hyper), g, p, _lib.stream_ptr())
+    return hyper

@@ -119,7 +119,7 @@ def test_log_evidence_argument_errors_need_no_device():
         fit.n_chains = 0
         with pytest.raises(ValueError, match="n_chains"):
             fit.log_evidence()
-        assert fit._ctx is None and fit._evidence_ctx is None
+        assert fit._ctx is None and fit._query_ctx is None
 
 
 def test_abi_of_the_new_entry_points():

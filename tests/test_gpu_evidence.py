@@ -241,7 +241,7 @@ fit.model, fit.b, fit.bt = fcdiff_amd.UnsharedRegionModel(), b, bt
 fit.method, fit.n_chains, fit.n_sweeps, fit.burn_in = "gibbs", 1024, 4, 2
 fit.run()
 out = fit.log_evidence(n_anneal=20)
-fit._evidence_ctx.check_device()
+fit._query_ctx.check_device()
 fit._context().check_device()
 print("RESULT " + json.dumps(out))
 """
