@@ -98,6 +98,9 @@ SIGNATURES = {
     "fcd_gibbs_count_tally": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "fcd_gibbs_set_count_accumulator": (_int, [_p, _p, _p, _i64, _i64, _i64]),
     "fcd_vb_count_posterior": (_int, [_p, _p, _i64, _i64, _p, _p, _p]),
+    "fcd_gibbs_coanomaly_tally": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "fcd_gibbs_set_coanomaly_accumulator": (_int, [_p, _p, _p, _i64, _i64, _i64]),
+    "fcd_vb_coanomaly": (_int, [_p, _p, _i64, _i64, _p, _p, _p]),
     "fcd_vb_patient_elbo": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
     "fcd_score_ais_step": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _dbl, _dbl, _p, _p, _p]),
     "fcd_score_ais_finish": (_int, [_p, _p, _i64, _i64, _p, _p]),

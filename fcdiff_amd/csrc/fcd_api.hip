@@ -143,6 +143,9 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->count_every = 1;
     ctx->count_ws = nullptr;
     ctx->count_ws_bytes = 0;
+    ctx->coan_rp = ctx->coan_pp = nullptr;
+    ctx->coan_nreg = ctx->coan_u = 0;
+    ctx->coan_every = 1;
     ctx->acc = nullptr;
     ctx->nan_slots = nullptr;
     ctx->dbg = nullptr;

@@ -78,6 +78,8 @@ struct fcd_ctx {
     int64_t count_nreg, count_u, count_every;   // (fcd_gibbs_set_count_accumulator), or nullptr
     void *count_ws;                // per-chain counts of one tally, (U + Nreg) rows of GW*64 uint16 (fcd_count_ws_reserve)
     size_t count_ws_bytes;
+    uint32_t *coan_rp, *coan_pp;    // (Nreg, Nreg) / (U, U) co-anomaly counts fcd_gibbs_run adds to
+    int64_t coan_nreg, coan_u, coan_every;      // (fcd_gibbs_set_coanomaly_accumulator), or nullptr
     // optional per-kernel timing with HIP events on the launch stream (fcd_prof_enable / fcd_prof_collect)
     int prof_on;
     hipEvent_t *prof_ev[FCD_PROF_SLOTS];   // pairs (begin, end)
@@ -150,6 +152,9 @@ int fcd_pair_tally_launch(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *
 int fcd_count_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
 int fcd_count_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
                            uint32_t *hist_patient, uint32_t *hist_region, hipStream_t s);
+// the co-anomaly kernel of fcd_coanomaly.hip (one launch, no scratch): both pair matrices += the counts of this state
+int fcd_coanomaly_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
+                               uint32_t *region_pairs, uint32_t *patient_pairs, hipStream_t s);
 // bracket ONE kernel launch with events when profiling is on (no-ops otherwise)
 void fcd_prof_begin(fcd_ctx *ctx, int slot, hipStream_t s);
 void fcd_prof_end(fcd_ctx *ctx, int slot, hipStream_t s);

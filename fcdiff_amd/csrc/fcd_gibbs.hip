@@ -1422,10 +1422,10 @@ extern "C" int fcd_gibbs_accumulate(fcd_ctx *ctx, const uint8_t *f_state, const 
 // ceil(Nreg/16) + 1 block steps), tally (1) -- the tally also carries the M-step, the slot words of the next f pass and, with
 // packed_ok, the r words of the next r pass.  hyper_m: what the M-step writes (nullptr when mstep_every == 0); pair_acc: add the
 // (f_c, mixture case) counts to the context's pair accumulator; count_acc: add the anomalous-region counts to the
-// context's count accumulator.
+// context's count accumulator; coan_acc: add the co-anomaly counts to the context's co-anomaly accumulator.
 static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int64_t n_sweeps, int64_t mstep_every,
                       int64_t accumulate_from, int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r, double *hyper_m,
-                      bool pair_acc, bool count_acc) {
+                      bool pair_acc, bool count_acc, bool coan_acc) {
     if (n_sweeps < 0 || sweep0 < 0 || sweep0 + n_sweeps > (1ll << 32))
         return fcd_fail(ctx, FCD_ERR_ARG, "sweep range [%lld, +%lld) outside the 32-bit counter word", sweep0, n_sweeps);
     const fcd_sweep_plan &pl = c.pl;
@@ -1517,6 +1517,11 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
             rc = fcd_count_tally_launch(ctx, c.r_bits, Nreg, U, G, g, ctx->count_hp, ctx->count_hr, s);
             if (rc) return rc;
         }
+        // co-anomaly counts of the end-of-sweep state (fcd_gibbs_set_coanomaly_accumulator): one launch, no scratch
+        if (coan_acc && st.sweep >= accumulate_from && (st.sweep - accumulate_from) % ctx->coan_every == 0) {
+            rc = fcd_coanomaly_tally_launch(ctx, c.r_bits, Nreg, U, G, g, ctx->coan_rp, ctx->coan_pp, s);
+            if (rc) return rc;
+        }
         st.ru_ready = r_U_next != nullptr;
         st.r_packed = r_S_next != nullptr;
     }
@@ -1539,15 +1544,18 @@ extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, 
     if (ctx->count_hp && (ctx->count_nreg != Nreg || ctx->count_u != U))
         return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_run: the attached count accumulator was made for Nreg=%lld, U=%lld",
                         ctx->count_nreg, ctx->count_u);
+    if (ctx->coan_rp && (ctx->coan_nreg != Nreg || ctx->coan_u != U))
+        return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_run: the attached co-anomaly accumulator was made for Nreg=%lld, U=%lld",
+                        ctx->coan_nreg, ctx->coan_u);
     if (ctx->count_hp) {
         rc = fcd_count_ws_reserve(ctx, Nreg, U, G);          // (grown here, never inside the sweep loop)
         if (rc) return rc;
     }
     return sweep_loop(ctx, c, sweep0, n_sweeps, mstep_every, accumulate_from, counts, cnt_f, cnt_r, hyper, ctx->pair_acc != nullptr,
-                      ctx->count_hp != nullptr);
+                      ctx->count_hp != nullptr, ctx->coan_rp != nullptr);
 }
 
-// fcd_gibbs_run's loop without M-step, marginal counters, pair or anomalous-region counts.  The counts are made by fcd_gibbs_stats after the
+// fcd_gibbs_run's loop without M-step, marginal counters, pair, anomalous-region or co-anomaly counts.  The counts are made by fcd_gibbs_stats after the
 // loop: this rank's own, never pooled over an attached communicator.
 extern "C" int fcd_gibbs_sweeps(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *lMd,
                                 const double *hyper,
@@ -1557,7 +1565,7 @@ extern "C" int fcd_gibbs_sweeps(fcd_ctx *ctx, const double *S_B, const double *l
     fcd_sweep_call c = {S_B, lM, lMf, lMd, hyper, f_state, r_bits, Nreg, U, G, chain0, seed, edge_mode, (hipStream_t)stream};
     int rc = fcd_sweep_call_check(ctx, c, true, true, "fcd_gibbs_sweeps");
     if (rc) return rc;
-    rc = sweep_loop(ctx, c, sweep0, n_sweeps, 0, 0, nullptr, nullptr, nullptr, nullptr, false, false);
+    rc = sweep_loop(ctx, c, sweep0, n_sweeps, 0, 0, nullptr, nullptr, nullptr, nullptr, false, false, false);
     if (rc) return rc;
     if (counts && n_sweeps > 0) return fcd_gibbs_stats(ctx, f_state, r_bits, Nreg, U, G, counts, stream);
     return FCD_OK;

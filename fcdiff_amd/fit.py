@@ -20,6 +20,8 @@ New knobs (all optional; defaults reproduce the reference):
     connection_marginals, connection_every                     gibbs: count (f_c, mixture case) for connection_posterior()
     anomaly_counts, anomaly_counts_every                       gibbs: histograms of the anomalous-region counts for
                                                                anomaly_count_posterior()
+    coanomaly, coanomaly_every                                 gibbs: counts of regions anomalous together and of patients
+                                                               sharing anomalous regions for coanomaly_posterior()
     missing_data                                               True: NaN entries of b / bt are unobserved and integrated out
 
 Differences from the reference that are deliberate and documented:
@@ -93,6 +95,12 @@ class UnsharedRegionFit(object):
         self.patient_count_hist = None      # (U, Nreg+1) int64: chains x sweeps (x ranks) with sum_n r_nu = k
         self.region_count_hist = None       # (Nreg, U+1) int64: chains x sweeps (x ranks) with sum_u r_nu = k
         self.anomaly_count_sweeps = 0       # number of sweeps behind those histograms
+        self.coanomaly = False              # gibbs: pair counts of the r sites for coanomaly_posterior()
+        self.coanomaly_every = 1            # ... at every this many sweeps from burn_in on
+        self.region_pair_counts = None      # (Nreg, Nreg) int64: (chain, sweep, patient) with r_nu = r_mu = 1, pooled over ranks
+        self.patient_pair_counts = None     # (U, U) int64: (chain, sweep, region) with r_nu = r_nv = 1, pooled over ranks
+        self.coanomaly_sweeps = 0           # number of sweeps behind those counts
+        self.coanomaly_states = 0           # ... and of chain states: sweeps x chains, summed over ranks
         # True: every NaN of b / bt is an unobserved value, integrated out exactly (S_B sums the observed h only, lM = 0 at a
         # missing bt); False: NaN is read as a number, as the reference reads it.  Only NaN is missing, not +-inf.
         self.missing_data = False
@@ -579,12 +587,18 @@ class UnsharedRegionFit(object):
             if N > COUNT_MAX_NREG or U > COUNT_MAX_U:
                 raise ValueError("anomaly-count histograms are made for at most %d regions and %d patients (here %d, %d)"
                                  % (COUNT_MAX_NREG, COUNT_MAX_U, N, U))
+        self.region_pair_counts = self.patient_pair_counts = None
+        self.coanomaly_sweeps = self.coanomaly_states = 0
+        if self.coanomaly:
+            self._check_accumulator("coanomaly_every", "co-anomaly counts", sites=max(N, U))
         eng = GibbsEngine(self._d["S_B"], self._d["lM"], N, U, self.n_chains, chain0=self.chain0, seed=self.seed,
                           edge_index=self._edge_mode(), ctx=self._context())
         if self.connection_marginals:
             eng.attach_pair_accumulator(self.connection_every)
         if self.anomaly_counts:
             eng.attach_count_accumulator(self.anomaly_counts_every)
+        if self.coanomaly:
+            eng.attach_coanomaly_accumulator(self.coanomaly_every)
         pi2 = self._pi2()
         eng.set_hyper(np.asarray(self.model.gamma, dtype=np.float64), pi2)
         eng.init(float(pi2[1]))
@@ -644,20 +658,27 @@ class UnsharedRegionFit(object):
             self.patient_count_hist = hp.cpu().numpy()
             self.region_count_hist = hr.cpu().numpy()
             self.anomaly_count_sweeps = eng.count_sweeps
+        if eng.coanomaly_acc is not None:
+            (rp, pp) = (pool_u32(a) for a in eng.coanomaly_acc)
+            self.region_pair_counts = rp.cpu().numpy()
+            self.patient_pair_counts = pp.cpu().numpy()
+            self.coanomaly_sweeps = eng.coanomaly_sweeps
+            states = t.tensor([eng.coanomaly_sweeps * eng.G], dtype=t.int64, device=eng.cnt_f.device)
+            self.coanomaly_states = int(allreduce_counts(states).cpu()[0])
         (gamma, pi) = eng.hyper_values()
         self.model.gamma = gamma
         self.model.pi = pi
 
-    def _check_accumulator(self, knob, what):
+    def _check_accumulator(self, knob, what, sites=1):
         """A uint32 accumulator of the gibbs run: its period self.<knob> is an integer >= 1 and, at that period, chains x
-        accumulated sweeps fit the counter."""
+        accumulated sweeps (x `sites`, where one counter takes that many sites of a chain) fit the counter."""
         every = getattr(self, knob)
         if int(every) < 1 or int(every) != every:
             raise ValueError("%s must be an integer >= 1" % knob)
         n_acc = pair_sweeps_in(0, int(self.n_sweeps), int(self.burn_in), int(every))
-        if n_acc * int(self.n_chains) > PAIR_COUNT_MAX:
-            raise ValueError("%s would overflow uint32: %d chains x %d accumulated sweeps; raise %s"
-                             % (what, self.n_chains, n_acc, knob))
+        if n_acc * int(self.n_chains) * int(sites) > PAIR_COUNT_MAX:
+            raise ValueError("%s would overflow uint32: %d chains x %d accumulated sweeps%s; raise %s"
+                             % (what, self.n_chains, n_acc, " x %d sites" % sites if sites > 1 else "", knob))
 
     # ------------------------------------------------------------------ connection-level posteriors
     def _connection_counts_dev(self):
@@ -746,6 +767,53 @@ class UnsharedRegionFit(object):
             raise ValueError("method must be 'vb' or 'gibbs'")
         return {"p_patient_count": p_patient, "p_region_count": p_region,
                 "p_patient_any": 1.0 - p_patient[:, 0], "p_region_any": 1.0 - p_region[:, 0]}
+
+    # ------------------------------------------------------------------ co-anomaly
+    def _coanomaly_counts(self):
+        """(region_pair_counts, patient_pair_counts, chain states behind them) of the last gibbs run, or ValueError."""
+        (rp, pp) = (self.region_pair_counts, self.patient_pair_counts)
+        if rp is None or pp is None:
+            raise ValueError("no co-anomaly counts: set coanomaly = True before run(method='gibbs')")
+        if int(self.coanomaly_states) < 1:
+            raise ValueError("no sweep was accumulated into the co-anomaly counts (n_sweeps <= burn_in?)")
+        return np.asarray(rp), np.asarray(pp), int(self.coanomaly_states)
+
+    def coanomaly_posterior(self):
+        """
+        Which regions are anomalous together and which patients share anomalous regions, from the last run(), as a dict of
+        NumPy float64 arrays:
+            p_region_pair      (Nreg, Nreg)  (1/U) sum_u P(r_nu = 1, r_mu = 1 | data): for a patient picked at random, the
+                                             chance that regions n and m are both anomalous
+            expected_patients  (Nreg, Nreg)  U times that: the expected number of patients with both
+            p_patient_pair     (U, U)        (1/Nreg) sum_n P(r_nu = 1, r_nv = 1 | data)
+            expected_regions   (U, U)        Nreg times that: the expected number of anomalous regions u and v share
+            p_region_pair_independent, p_patient_pair_independent
+                                             the first and the third if the sites were independent with the fit's marginals
+                                             (fcd_vb_coanomaly on _lq_R); joint minus independent is the excess co-anomaly
+        All are symmetric; the diagonals are the means of the marginals, (1/U) sum_u P(r_nu = 1) and (1/Nreg) sum_n
+        P(r_nu = 1).  The sites are coupled (inside a patient through the mixture cases of the edges, across patients
+        through f), so the joint entries are second moments of the joint, not products of the marginals of _lq_R:
+          method='vb'     the mean-field law: under q_R the sites are independent, so the joint entries EQUAL the
+                          independent ones (computed on demand from _lq_R);
+          method='gibbs'  the pair counts over chains and the sweeps from burn_in on, every `coanomaly_every`-th.  Needs
+                          `coanomaly = True` before run(); raises ValueError otherwise.  The counts are kept as
+                          `region_pair_counts` / `patient_pair_counts`, the number of sweeps behind them as
+                          `coanomaly_sweeps`.
+        """
+        if self.model is None or self.bt is None:
+            raise ValueError("coanomaly_posterior() needs a model and bt: call run() first")
+        if self.method == "gibbs":
+            (rp, pp, states) = self._coanomaly_counts()
+        elif self.method != "vb":
+            raise ValueError("method must be 'vb' or 'gibbs'")
+        (N, _C, U) = self._check_state(need=("lq_R",))
+        (ri, pi_) = coanomaly_independent(self._context(), self._d["lq_R"], N, U)
+        out = {"p_region_pair_independent": ri / U, "p_patient_pair_independent": pi_ / N}
+        if self.method == "gibbs":
+            out.update(coanomaly_from_counts(rp, pp, states))
+        else:
+            out.update({"p_region_pair": ri / U, "expected_patients": ri, "p_patient_pair": pi_ / N, "expected_regions": pi_})
+        return out
 
     # ------------------------------------------------------------------ scoring new patients
     def score(self, bt_new, *, connections=False, max_iters=100, tol=1e-8, n_anneal=200, n_sweeps=50, seed=None):
@@ -1040,6 +1108,18 @@ class SharedRegionFit(UnsharedRegionFit):
             raise ValueError("method must be 'vb' or 'gibbs'")
         return {"p_count": p, "p_any": float(1.0 - p[0])}
 
+    def coanomaly_posterior(self):
+        """
+        Which regions are anomalous together, from the last run():
+            p_region_pair (N, N)              P(r_n = 1, r_m = 1 | data); the diagonal is region_posterior()
+            p_region_pair_independent (N, N)  P(r_n = 1 | data) P(r_m = 1 | data) off the diagonal
+          method='vb'     the mean-field law: the two are equal (fcd_vb_coanomaly at U = 1);
+          method='gibbs'  the pair counts over chains and sweeps (needs coanomaly = True before run()).
+        There is no patient matrix: the state has one column.
+        """
+        out = super(SharedRegionFit, self).coanomaly_posterior()
+        return {"p_region_pair": out["p_region_pair"], "p_region_pair_independent": out["p_region_pair_independent"]}
+
     def score(self, *args, **kwargs):
         """Scoring a new patient under a population-level r is a different question; not provided."""
         raise NotImplementedError("score() is not provided for the shared-region model")
@@ -1074,6 +1154,40 @@ def count_posterior(ctx, lq_R, Nreg, U):
     ctx.call("fcd_vb_count_posterior", _lib.dptr(lq_R.contiguous()), int(Nreg), int(U), _lib.dptr(p_patient),
              _lib.dptr(p_region), _lib.stream_ptr())
     return p_patient.cpu().numpy(), p_region.cpu().numpy()
+
+
+def coanomaly_independent(ctx, lq_R, Nreg, U):
+    """
+    (region (Nreg, Nreg), patient (U, U)) as NumPy float64 through fcd_vb_coanomaly: sum_u q_nu q_mu and sum_n q_nu q_nv off
+    the diagonals, sum_u q_nu and sum_n q_nu on them, with q_nu = P(r_nu = 1) from lq_R (Nreg, U, 2) float64 (need not be
+    normalised).
+    """
+    import torch
+    if tuple(lq_R.shape) != (Nreg, U, 2) or lq_R.dtype != torch.float64:
+        raise ValueError("lq_R must be float64 (Nreg, U, 2) = %s" % ((Nreg, U, 2),))
+    dev = lq_R.device
+    region = torch.empty((Nreg, Nreg), dtype=torch.float64, device=dev)
+    patient = torch.empty((U, U), dtype=torch.float64, device=dev)
+    ctx.call("fcd_vb_coanomaly", _lib.dptr(lq_R.contiguous()), int(Nreg), int(U), _lib.dptr(region), _lib.dptr(patient),
+             _lib.stream_ptr())
+    return region.cpu().numpy(), patient.cpu().numpy()
+
+
+def coanomaly_from_counts(region_pair_counts, patient_pair_counts, states):
+    """
+    The joint entries of coanomaly_posterior() from the sampler's pair counts (Nreg, Nreg) and (U, U) over `states` chain
+    states (sweeps x chains, all ranks): each count over `states` is an expected number, over U or Nreg more a probability.
+    """
+    rp = np.asarray(region_pair_counts, dtype=np.float64)
+    pp = np.asarray(patient_pair_counts, dtype=np.float64)
+    (N, U) = (rp.shape[0], pp.shape[0])
+    if rp.shape != (N, N) or pp.shape != (U, U):
+        raise ValueError("pair counts must be square: (Nreg, Nreg) and (U, U)")
+    states = int(states)
+    if states < 1:
+        raise ValueError("no chain state behind the pair counts")
+    return {"p_region_pair": rp / (float(states) * U), "expected_patients": rp / float(states),
+            "p_patient_pair": pp / (float(states) * N), "expected_regions": pp / float(states)}
 
 
 def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=None, missing_data=False):

@@ -104,6 +104,9 @@ class GibbsEngine(object):
         self.count_hist = None      # (hist_patient (U, Nreg+1), hist_region (Nreg, U+1)) that run() adds to (attach_count_accumulator)
         self.count_every = 1
         self.count_sweeps = 0       # sweeps added to count_hist so far
+        self.coanomaly_acc = None   # (region_pairs (Nreg, Nreg), patient_pairs (U, U)) that run() adds to (attach_coanomaly_accumulator)
+        self.coanomaly_every = 1
+        self.coanomaly_sweeps = 0   # sweeps added to coanomaly_acc so far
         self.ctx.call("fcd_ctx_reserve", self.Nreg, self.U, self.G)
         self.lMd = self.lMf = None
         if region_major:
@@ -190,13 +193,14 @@ class GibbsEngine(object):
         packs the r words of the next f pass.  Returns the counts tensor of the last sweep (or None).
         With a pair accumulator attached (attach_pair_accumulator) the same call also adds the (f_c, mixture case) counts
         of every `pair_every`-th sweep from `accumulate_from` on, and with a count accumulator attached
-        (attach_count_accumulator) the histograms of the anomalous-region counts of every `count_every`-th sweep; a call
-        that could overflow either raises ValueError.
+        (attach_count_accumulator) the histograms of the anomalous-region counts of every `count_every`-th sweep, and with
+        a co-anomaly accumulator attached (attach_coanomaly_accumulator) the two pair matrices of every
+        `coanomaly_every`-th sweep; a call that could overflow any of them raises ValueError.
         """
         acc = accumulate_from is not None
         pair = self.pair_acc is not None and acc
         count = self.count_hist is not None and acc
-        (n_pair, n_count) = (0, 0)
+        (n_pair, n_count, n_coan) = (0, 0, 0)
         if pair:
             n_pair = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), self.pair_every)
             if (self.pair_sweeps + n_pair) * self.G > PAIR_COUNT_MAX:
@@ -207,6 +211,14 @@ class GibbsEngine(object):
             if (self.count_sweeps + n_count) * self.G > PAIR_COUNT_MAX:
                 raise ValueError("the count accumulator would overflow uint32: %d chains x %d accumulated sweeps > %d"
                                  % (self.G, self.count_sweeps + n_count, PAIR_COUNT_MAX))
+        coan = self.coanomaly_acc is not None and acc
+        if coan:
+            n_coan = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), self.coanomaly_every)
+            # (a diagonal entry counts up to G x U or G x Nreg sites per sweep)
+            if (self.coanomaly_sweeps + n_coan) * self.G * max(self.Nreg, self.U) > PAIR_COUNT_MAX:
+                raise ValueError("the co-anomaly accumulator would overflow uint32: %d chains x %d sites x %d accumulated "
+                                 "sweeps > %d" % (self.G, max(self.Nreg, self.U), self.coanomaly_sweeps + n_coan,
+                                                  PAIR_COUNT_MAX))
         # (attached for this call only: the context is shared, no other engine's sweeps may add to these buffers)
         try:
             if pair:
@@ -214,14 +226,20 @@ class GibbsEngine(object):
             if count:
                 self.ctx.call("fcd_gibbs_set_count_accumulator", _lib.dptr(self.count_hist[0]), _lib.dptr(self.count_hist[1]),
                               self.Nreg, self.U, self.count_every)
+            if coan:
+                self.ctx.call("fcd_gibbs_set_coanomaly_accumulator", _lib.dptr(self.coanomaly_acc[0]),
+                              _lib.dptr(self.coanomaly_acc[1]), self.Nreg, self.U, self.coanomaly_every)
             self._run(sweep0, n_sweeps, mstep_every, accumulate_from, want_counts)
         finally:
             if pair:
                 self.ctx.call("fcd_gibbs_set_pair_accumulator", None, 0, 0, 1)
             if count:
                 self.ctx.call("fcd_gibbs_set_count_accumulator", None, None, 0, 0, 1)
+            if coan:
+                self.ctx.call("fcd_gibbs_set_coanomaly_accumulator", None, None, 0, 0, 1)
         self.pair_sweeps += n_pair
         self.count_sweeps += n_count
+        self.coanomaly_sweeps += n_coan
         if acc:
             self.n_accumulated += max(0, int(sweep0) + int(n_sweeps) - max(int(accumulate_from), int(sweep0)))
         return self.counts if want_counts else None
@@ -304,6 +322,45 @@ class GibbsEngine(object):
         self.ctx.call("fcd_gibbs_count_tally", _lib.dptr(self.r_bits), self.Nreg, self.U, self.G, _lib.dptr(hist_patient),
                       _lib.dptr(hist_region), _lib.stream_ptr())
         return hist_patient, hist_region
+
+    # ---- co-anomaly: pairs of regions anomalous together, pairs of patients sharing anomalous regions ----
+    def attach_coanomaly_accumulator(self, every=1):
+        """
+        From now on run() adds the end-of-sweep counts region_pairs[n, m] = #{(chain, u): r_nu = r_mu = 1} (Nreg, Nreg) and
+        patient_pairs[u, v] = #{(chain, n): r_nu = r_nv = 1} (U, U) to `coanomaly_acc`, at every `every`-th sweep from its
+        `accumulate_from` on (none when accumulate_from is None).  Zeroes the matrices.
+        """
+        every = int(every)
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        t = self.torch
+        dev = self.f_state.device
+        # (uint32 on the device, held in int32 tensors like count_hist; coanomaly_host() reads them back as uint32)
+        self.coanomaly_acc = (t.zeros((self.Nreg, self.Nreg), dtype=t.int32, device=dev),
+                              t.zeros((self.U, self.U), dtype=t.int32, device=dev))
+        self.coanomaly_every = every
+        self.coanomaly_sweeps = 0
+        return self.coanomaly_acc
+
+    def detach_coanomaly_accumulator(self):
+        self.coanomaly_acc = None
+        self.coanomaly_sweeps = 0
+
+    def coanomaly_host(self):
+        """The attached matrices as NumPy uint32 arrays (region_pairs (Nreg, Nreg), patient_pairs (U, U))."""
+        if self.coanomaly_acc is None:
+            raise ValueError("no co-anomaly accumulator is attached")
+        return tuple(self.host(a).view(np.uint32) for a in self.coanomaly_acc)
+
+    def coanomaly_tally(self, region, patient):
+        """region (Nreg, Nreg), patient (U, U) uint32-in-int32 tensors += the pair counts of the current state."""
+        if (tuple(region.shape) != (self.Nreg, self.Nreg) or tuple(patient.shape) != (self.U, self.U)
+                or region.element_size() != 4 or patient.element_size() != 4
+                or not region.is_contiguous() or not patient.is_contiguous()):
+            raise ValueError("pair matrices must be contiguous 32-bit (Nreg, Nreg) and (U, U)")
+        self.ctx.call("fcd_gibbs_coanomaly_tally", _lib.dptr(self.r_bits), self.Nreg, self.U, self.G, _lib.dptr(region),
+                      _lib.dptr(patient), _lib.stream_ptr())
+        return region, patient
 
     # ---- pooled statistics / M-step ----
     def stats(self):

@@ -391,6 +391,30 @@ int fcd_gibbs_set_count_accumulator(fcd_ctx *ctx, uint32_t *hist_patient, uint32
  * recursion; q = 0 and q = 1 give exact point masses.  Nreg, U <= 4095, else FCD_ERR_UNSUPPORTED. */
 int fcd_vb_count_posterior(fcd_ctx *ctx, const double *lq_R, int64_t Nreg, int64_t U, double *p_patient, double *p_region,
                            fcd_stream stream);
+/* ---- co-anomaly (which regions are anomalous together, which patients share anomalous regions) -------------------
+ * Second moments of the joint law of the sites, which the marginals do not give.
+ *
+ * Counts over chains of one state, both symmetric and written in full:
+ *   region_pairs (Nreg, Nreg) uint32, region_pairs[n][m] += #{(chain, u) with r_nu = r_mu = 1};
+ *   patient_pairs (U, U) uint32, patient_pairs[u][v] += #{(chain, n) with r_nu = r_nv = 1}.
+ * The diagonals are sum_u r_nu and sum_n r_nu over chains.  Chains beyond G in the last word never count.  One launch,
+ * no scratch.  Any shape the sampler takes (U = 1 included). */
+int fcd_gibbs_coanomaly_tally(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
+                              uint32_t *region_pairs, uint32_t *patient_pairs, fcd_stream stream);
+/* Attach both matrices for shape (Nreg, U) to the context (no device work; both NULL detaches), with the semantics of
+ * fcd_gibbs_set_count_accumulator: every sweep s of fcd_gibbs_run with s >= accumulate_from and
+ * (s - accumulate_from) % every == 0 adds its end-of-sweep state (one extra launch after the sweep's tally, after the
+ * pair and count accumulators' when they are attached).  fcd_gibbs_run refuses another shape while they are attached.
+ * The caller keeps sweeps x G x max(Nreg, U) below 2^32. */
+int fcd_gibbs_set_coanomaly_accumulator(fcd_ctx *ctx, uint32_t *region_pairs, uint32_t *patient_pairs, int64_t Nreg,
+                                        int64_t U, int64_t every);
+/* The same two matrices per chain if the sites were independent with q_nu = P(r_nu = 1) from lq_R (Nreg, U, 2),
+ * normalised in log space (lq_R need not be normalised; q = 0 and q = 1 exact), fp64:
+ *   region (Nreg, Nreg):  sum_u q_nu q_mu off the diagonal, sum_u q_nu on it;
+ *   patient (U, U):       sum_n q_nu q_nv off the diagonal, sum_n q_nu on it.
+ * Every entry is summed in index order: results repeat bit for bit. */
+int fcd_vb_coanomaly(fcd_ctx *ctx, const double *lq_R, int64_t Nreg, int64_t U, double *region, double *patient,
+                     fcd_stream stream);
 /* ---- scoring new patients against a fitted model (UnsharedRegionFit.score) -------------------------------------------
  * Given F and theta the patients are independent, so a new patient is scored with the fit's template held: the fit itself
  * is never changed.
