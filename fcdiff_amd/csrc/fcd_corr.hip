@@ -183,11 +183,15 @@ __global__ __launch_bounds__(256) void corr_gram_kernel(const double *__restrict
 // The blocked kernel above reads every row of a subject 4 times over (64 x 64 blocks: 800 row loads for 200 regions) and
 // needs the means before it starts (a pass of its own over the input).  Here a workgroup of 16 waves stages ALL rows of
 // its subject, 16 time steps at a time, and owns all 16 x 16 tiles of the lower triangle (TPW per wave, consecutive in
-// row-major order): every input byte is loaded ONCE.  Centring is by the row's first sample x0 instead of its mean --
+// row-major order): every input byte is loaded ONCE.  Centring is by a shift x0 of the row instead of its mean --
 //     sum (x - mx)(y - my) = sum (x - x0)(y - y0) - (sum (x - x0)) (sum (y - y0)) / T
-// -- a shift that removes the cancellation the raw second moment would have (the shifted values are of the size of the
-// deviations), so one pass gives Gram matrix and row sums; the deviations are the roots of the Gram diagonal, as in
-// numpy.corrcoef.  The time axis is cut in KS slices (S subjects alone would leave most CUs idle): each workgroup
+// -- so one pass gives Gram matrix and row sums; the deviations are the roots of the Gram diagonal, as in
+// numpy.corrcoef.  The subtraction on the right loses about T 2^-53 (x0 - mx)^2 / var(x) of the result, so the shift
+// removes the cancellation of the raw second moment only where it is within a few deviations of the row's mean.  The
+// row's first sample is not: a first frame 1000 sd off (series that start before the steady state) cost 1.4e-11 at
+// T = 20 000, more than the 1e-11 this kernel is held to (tests/test_gpu_corr_edges.py).  x0 is the lower median of
+// the eight samples in the middles of the eighths of the row: up to three of them may be outliers, and it is a
+// function of the row alone, so all time slices of a subject shift alike.  The time axis is cut in KS slices (S subjects alone would leave most CUs idle): each workgroup
 // writes its partial tiles, the last of a subject to finish (a ticket) adds the slices IN SLICE ORDER (same bits
 // whoever comes last), normalises and writes the subject-major row of tmp.
 // ---------------------------------------------------------------------------------------------
@@ -235,7 +239,21 @@ __global__ __launch_bounds__(1024) void corr_gram_subject_kernel(const double *_
         prow[i] = (tid >> 3) + 128 * i;
         va[i] = prow[i] < Nreg;
         xp[i] = ts + ((int64_t)s * Nreg + (va[i] ? prow[i] : 0)) * T;
-        x0[i] = va[i] ? xp[i][0] : 0.0;
+        // the shift: lane pp of the row's eight staging lanes asks for sample pp of the eight, counts how many of them
+        // come before its own (ties in lane order: the ranks are a permutation), and rank 3 is handed round.  (A NaN
+        // among them may leave no rank 3 and the shift 0: the row's edges are NaN whatever the shift.)
+        const double v = va[i] ? xp[i][(int)(((int64_t)(2 * pp + 1) * T) >> 4)] : 0.0;
+        int rank = 0;
+#pragma unroll
+        for (int q = 1; q < 8; ++q) {
+            const double o = __shfl_xor(v, q, 64);                  // lane pp ^ q's sample
+            rank += (o < v || (o == v && (pp ^ q) < pp)) ? 1 : 0;
+        }
+        double med = rank == 3 ? v : 0.0;
+        med += __shfl_xor(med, 1, 64);
+        med += __shfl_xor(med, 2, 64);
+        med += __shfl_xor(med, 4, 64);
+        x0[i] = med;
         rs[i] = 0.0;
     }
     // fetch only ASKS for the step's values; they are shifted, masked and summed in put, behind the MFMAs of the step
