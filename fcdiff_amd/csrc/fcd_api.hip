@@ -135,17 +135,9 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->dev_err = nullptr;
     ctx->fsq = nullptr;
     ctx->fsq_bytes = 0;
-    ctx->pair_acc = nullptr;
-    ctx->pair_nreg = ctx->pair_u = 0;
-    ctx->pair_every = 1;
-    ctx->count_hp = ctx->count_hr = nullptr;
-    ctx->count_nreg = ctx->count_u = 0;
-    ctx->count_every = 1;
+    for (int k = 0; k < FCD_ACC_N; ++k) ctx->sweep_acc[k] = fcd_sweep_acc{{nullptr, nullptr}, 0, 0, 1};
     ctx->count_ws = nullptr;
     ctx->count_ws_bytes = 0;
-    ctx->coan_rp = ctx->coan_pp = nullptr;
-    ctx->coan_nreg = ctx->coan_u = 0;
-    ctx->coan_every = 1;
     ctx->acc = nullptr;
     ctx->nan_slots = nullptr;
     ctx->dbg = nullptr;

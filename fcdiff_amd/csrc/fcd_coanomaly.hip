@@ -240,23 +240,10 @@ extern "C" int fcd_gibbs_coanomaly_tally(fcd_ctx *ctx, const uint64_t *r_bits, i
 
 extern "C" int fcd_gibbs_set_coanomaly_accumulator(fcd_ctx *ctx, uint32_t *region_pairs, uint32_t *patient_pairs, int64_t Nreg,
                                                    int64_t U, int64_t every) {
-    if (!ctx) return FCD_ERR_ARG;
-    if (!region_pairs && !patient_pairs) {
-        ctx->coan_rp = ctx->coan_pp = nullptr;
-        ctx->coan_nreg = ctx->coan_u = 0;
-        ctx->coan_every = 1;
-        return FCD_OK;
-    }
-    if (!region_pairs || !patient_pairs)
-        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_set_coanomaly_accumulator: region_pairs and patient_pairs go together");
-    if (Nreg < 2 || U < 1) return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_set_coanomaly_accumulator: Nreg=%lld U=%lld", Nreg, U);
-    if (every < 1) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_set_coanomaly_accumulator: every=%lld must be >= 1", every);
-    ctx->coan_rp = region_pairs;
-    ctx->coan_pp = patient_pairs;
-    ctx->coan_nreg = Nreg;
-    ctx->coan_u = U;
-    ctx->coan_every = every;
-    return FCD_OK;
+    return fcd_sweep_acc_set(ctx, FCD_ACC_COANOMALY, region_pairs, patient_pairs, Nreg, U, every,
+                             "fcd_gibbs_set_coanomaly_accumulator: region_pairs and patient_pairs go together",
+                             "fcd_gibbs_set_coanomaly_accumulator: Nreg=%lld U=%lld", nullptr,
+                             "fcd_gibbs_set_coanomaly_accumulator: every=%lld must be >= 1");
 }
 
 extern "C" int fcd_vb_coanomaly(fcd_ctx *ctx, const double *lq_R, int64_t Nreg, int64_t U, double *region, double *patient,

@@ -42,6 +42,16 @@ enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA
 
 #define FCD_NAN_SLOTS 256
 
+// The optional tallies fcd_gibbs_run adds to caller-owned uint32 buffers after a counted sweep, in the order it makes them:
+// (C, U, 3, 3) counts of (f_c, mixture case) (fcd_gibbs_set_pair_accumulator; one buffer, held in both places), (U, Nreg+1) /
+// (Nreg, U+1) histograms of the anomalous-region counts (fcd_gibbs_set_count_accumulator), (Nreg, Nreg) / (U, U) co-anomaly
+// counts (fcd_gibbs_set_coanomaly_accumulator).  fcd_gibbs.hip holds the launch of each.
+enum { FCD_ACC_PAIR, FCD_ACC_COUNT, FCD_ACC_COANOMALY, FCD_ACC_N };
+struct fcd_sweep_acc {
+    uint32_t *buf[2];              // buf[0] == nullptr: detached
+    int64_t nreg, u, every;        // the shape it was made for; added at every this many sweeps from accumulate_from on
+};
+
 struct fcd_ctx {
     int device;
     int num_cu;
@@ -72,14 +82,9 @@ struct fcd_ctx {
     size_t corr_tickets_n;
     void *fsq;         // square copy of the f state [w][n][m][lane] the sweep loop keeps between its f and r pass
     size_t fsq_bytes;
-    uint32_t *pair_acc;            // (C, U, 3, 3) counts of (f_c, mixture case) fcd_gibbs_run adds to (fcd_gibbs_set_pair_accumulator), or nullptr
-    int64_t pair_nreg, pair_u, pair_every;
-    uint32_t *count_hp, *count_hr;  // (U, Nreg+1) / (Nreg, U+1) histograms of the anomalous-region counts fcd_gibbs_run adds to
-    int64_t count_nreg, count_u, count_every;   // (fcd_gibbs_set_count_accumulator), or nullptr
+    fcd_sweep_acc sweep_acc[FCD_ACC_N];
     void *count_ws;                // per-chain counts of one tally, (U + Nreg) rows of GW*64 uint16 (fcd_count_ws_reserve)
     size_t count_ws_bytes;
-    uint32_t *coan_rp, *coan_pp;    // (Nreg, Nreg) / (U, U) co-anomaly counts fcd_gibbs_run adds to
-    int64_t coan_nreg, coan_u, coan_every;      // (fcd_gibbs_set_coanomaly_accumulator), or nullptr
     // optional per-kernel timing with HIP events on the launch stream (fcd_prof_enable / fcd_prof_collect)
     int prof_on;
     hipEvent_t *prof_ev[FCD_PROF_SLOTS];   // pairs (begin, end)
@@ -103,6 +108,25 @@ struct fcd_ctx {
 static inline int fcd_fail(fcd_ctx *ctx, int code, const char *fmt, long long a = 0, long long b = 0) {
     if (ctx) snprintf(ctx->msg, sizeof(ctx->msg), fmt, a, b);
     return code;
+}
+
+// What the fcd_gibbs_set_*_accumulator entry points share: all buffers null detaches, else the checks and the store.  The
+// message texts are the caller's (fcd_fail formats numbers only); msg_limit is non-null where the shape is past a limit of
+// the caller's own kernels.
+static inline int fcd_sweep_acc_set(fcd_ctx *ctx, int slot, uint32_t *b0, uint32_t *b1, int64_t Nreg, int64_t U, int64_t every,
+                                    const char *msg_together, const char *msg_shape, const char *msg_limit,
+                                    const char *msg_every) {
+    if (!ctx) return FCD_ERR_ARG;
+    if (!b0 && !b1) {
+        ctx->sweep_acc[slot] = fcd_sweep_acc{{nullptr, nullptr}, 0, 0, 1};
+        return FCD_OK;
+    }
+    if (!b0 || !b1) return fcd_fail(ctx, FCD_ERR_ARG, msg_together);
+    if (Nreg < 2 || U < 1) return fcd_fail(ctx, FCD_ERR_SHAPE, msg_shape, Nreg, U);
+    if (msg_limit) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, msg_limit, Nreg, U);
+    if (every < 1) return fcd_fail(ctx, FCD_ERR_ARG, msg_every, every);
+    ctx->sweep_acc[slot] = fcd_sweep_acc{{b0, b1}, Nreg, U, every};
+    return FCD_OK;
 }
 
 // A kernel whose table addresses assume that its dynamic LDS array starts at address 0 must declare no static LDS:

@@ -219,26 +219,12 @@ extern "C" int fcd_gibbs_count_tally(fcd_ctx *ctx, const uint64_t *r_bits, int64
 
 extern "C" int fcd_gibbs_set_count_accumulator(fcd_ctx *ctx, uint32_t *hist_patient, uint32_t *hist_region, int64_t Nreg,
                                                int64_t U, int64_t every) {
-    if (!ctx) return FCD_ERR_ARG;
-    if (!hist_patient && !hist_region) {
-        ctx->count_hp = ctx->count_hr = nullptr;
-        ctx->count_nreg = ctx->count_u = 0;
-        ctx->count_every = 1;
-        return FCD_OK;
-    }
-    if (!hist_patient || !hist_region)
-        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_set_count_accumulator: hist_patient and hist_region go together");
-    if (Nreg < 2 || U < 1) return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_set_count_accumulator: Nreg=%lld U=%lld", Nreg, U);
-    if (Nreg > CNT_MAX_NREG || U > CNT_MAX_U)
-        return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_gibbs_set_count_accumulator: Nreg=%lld U=%lld (at most 1023 regions, 512 patients)",
-                        Nreg, U);
-    if (every < 1) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_set_count_accumulator: every=%lld must be >= 1", every);
-    ctx->count_hp = hist_patient;
-    ctx->count_hr = hist_region;
-    ctx->count_nreg = Nreg;
-    ctx->count_u = U;
-    ctx->count_every = every;
-    return FCD_OK;
+    const bool over = Nreg > CNT_MAX_NREG || U > CNT_MAX_U;
+    return fcd_sweep_acc_set(ctx, FCD_ACC_COUNT, hist_patient, hist_region, Nreg, U, every,
+                             "fcd_gibbs_set_count_accumulator: hist_patient and hist_region go together",
+                             "fcd_gibbs_set_count_accumulator: Nreg=%lld U=%lld",
+                             over ? "fcd_gibbs_set_count_accumulator: Nreg=%lld U=%lld (at most 1023 regions, 512 patients)" : nullptr,
+                             "fcd_gibbs_set_count_accumulator: every=%lld must be >= 1");
 }
 
 extern "C" int fcd_vb_count_posterior(fcd_ctx *ctx, const double *lq_R, int64_t Nreg, int64_t U, double *p_patient,

@@ -1416,16 +1416,35 @@ extern "C" int fcd_gibbs_accumulate(fcd_ctx *ctx, const uint8_t *f_state, const 
     return launch_tally(ctx, f_state, r_bits, Nreg, U, G, g, nullptr, cnt_f, cnt_r, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
+// One row per slot of fcd_ctx::sweep_acc: fcd_gibbs_run's refusal of an accumulator made for another shape, and the launch
+// that adds the counts of a state to its buffers.
+static int acc_launch_pair(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_geo &g, const fcd_sweep_acc &a, hipStream_t s) {
+    return fcd_pair_tally_launch<uint32_t>(ctx, c.f_state, c.r_bits, c.Nreg, c.U, c.G, g, a.buf[0], true, s);
+}
+static int acc_launch_count(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_geo &g, const fcd_sweep_acc &a, hipStream_t s) {
+    return fcd_count_tally_launch(ctx, c.r_bits, c.Nreg, c.U, c.G, g, a.buf[0], a.buf[1], s);
+}
+static int acc_launch_coanomaly(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_geo &g, const fcd_sweep_acc &a, hipStream_t s) {
+    return fcd_coanomaly_tally_launch(ctx, c.r_bits, c.Nreg, c.U, c.G, g, a.buf[0], a.buf[1], s);
+}
+static const struct {
+    const char *msg_shape;
+    int (*launch)(fcd_ctx *, const fcd_sweep_call &, const fcd_geo &, const fcd_sweep_acc &, hipStream_t);
+} SWEEP_ACC[FCD_ACC_N] = {
+    {"fcd_gibbs_run: the attached pair accumulator was made for Nreg=%lld, U=%lld", acc_launch_pair},
+    {"fcd_gibbs_run: the attached count accumulator was made for Nreg=%lld, U=%lld", acc_launch_count},
+    {"fcd_gibbs_run: the attached co-anomaly accumulator was made for Nreg=%lld, U=%lld", acc_launch_coanomaly},
+};
+
 // The sampler loop of ONE rank between two exchanges of pooled statistics: fcd_gibbs_run (what UnsharedRegionFit(method=
 // 'gibbs'), run_chains and bench.py call) and fcd_gibbs_sweeps.  Per sweep: f pass (1 launch), packing for the r pass (1, in
 // the first sweep of a call only where the f pass can write the packed f words: packed_ok), r pass (one pipelined launch, or
 // ceil(Nreg/16) + 1 block steps), tally (1) -- the tally also carries the M-step, the slot words of the next f pass and, with
-// packed_ok, the r words of the next r pass.  hyper_m: what the M-step writes (nullptr when mstep_every == 0); pair_acc: add the
-// (f_c, mixture case) counts to the context's pair accumulator; count_acc: add the anomalous-region counts to the
-// context's count accumulator; coan_acc: add the co-anomaly counts to the context's co-anomaly accumulator.
+// packed_ok, the r words of the next r pass.  hyper_m: what the M-step writes (nullptr when mstep_every == 0); acc_mask: the
+// slots of the context's sweep accumulators to add to (bit k = slot k).
 static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int64_t n_sweeps, int64_t mstep_every,
                       int64_t accumulate_from, int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r, double *hyper_m,
-                      bool pair_acc, bool count_acc, bool coan_acc) {
+                      unsigned acc_mask) {
     if (n_sweeps < 0 || sweep0 < 0 || sweep0 + n_sweeps > (1ll << 32))
         return fcd_fail(ctx, FCD_ERR_ARG, "sweep range [%lld, +%lld) outside the 32-bit counter word", sweep0, n_sweeps);
     const fcd_sweep_plan &pl = c.pl;
@@ -1507,20 +1526,14 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
             rc = fcd_comm_allreduce_counts(ctx, (long long *)cts, s);
             if (rc) return rc;
         }
-        // (f_c, mixture case) counts of the end-of-sweep state (fcd_gibbs_set_pair_accumulator): one launch of its own
-        if (pair_acc && st.sweep >= accumulate_from && (st.sweep - accumulate_from) % ctx->pair_every == 0) {
-            rc = fcd_pair_tally_launch(ctx, c.f_state, c.r_bits, Nreg, U, G, g, ctx->pair_acc, true, s);
-            if (rc) return rc;
-        }
-        // histograms of sum_n r_nu and sum_u r_nu of the end-of-sweep state (fcd_gibbs_set_count_accumulator): the same
-        if (count_acc && st.sweep >= accumulate_from && (st.sweep - accumulate_from) % ctx->count_every == 0) {
-            rc = fcd_count_tally_launch(ctx, c.r_bits, Nreg, U, G, g, ctx->count_hp, ctx->count_hr, s);
-            if (rc) return rc;
-        }
-        // co-anomaly counts of the end-of-sweep state (fcd_gibbs_set_coanomaly_accumulator): one launch, no scratch
-        if (coan_acc && st.sweep >= accumulate_from && (st.sweep - accumulate_from) % ctx->coan_every == 0) {
-            rc = fcd_coanomaly_tally_launch(ctx, c.r_bits, Nreg, U, G, g, ctx->coan_rp, ctx->coan_pp, s);
-            if (rc) return rc;
+        // the attached accumulators' counts of the end-of-sweep state: a launch of its own each (two for the histograms)
+        if (acc_mask && st.sweep >= accumulate_from) {
+            for (int k = 0; k < FCD_ACC_N; ++k) {
+                const fcd_sweep_acc &a = ctx->sweep_acc[k];
+                if (!(acc_mask >> k & 1u) || (st.sweep - accumulate_from) % a.every != 0) continue;
+                rc = SWEEP_ACC[k].launch(ctx, c, g, a, s);
+                if (rc) return rc;
+            }
         }
         st.ru_ready = r_U_next != nullptr;
         st.r_packed = r_S_next != nullptr;
@@ -1538,21 +1551,18 @@ extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, 
     if (rc) return rc;
     if ((cnt_f == nullptr) != (cnt_r == nullptr)) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_run: cnt_f and cnt_r go together");
     if (mstep_every < 0) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_run: mstep_every < 0");
-    if (ctx->pair_acc && (ctx->pair_nreg != Nreg || ctx->pair_u != U))
-        return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_run: the attached pair accumulator was made for Nreg=%lld, U=%lld",
-                        ctx->pair_nreg, ctx->pair_u);
-    if (ctx->count_hp && (ctx->count_nreg != Nreg || ctx->count_u != U))
-        return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_run: the attached count accumulator was made for Nreg=%lld, U=%lld",
-                        ctx->count_nreg, ctx->count_u);
-    if (ctx->coan_rp && (ctx->coan_nreg != Nreg || ctx->coan_u != U))
-        return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_run: the attached co-anomaly accumulator was made for Nreg=%lld, U=%lld",
-                        ctx->coan_nreg, ctx->coan_u);
-    if (ctx->count_hp) {
+    unsigned acc_mask = 0;
+    for (int k = 0; k < FCD_ACC_N; ++k) {
+        const fcd_sweep_acc &a = ctx->sweep_acc[k];
+        if (!a.buf[0]) continue;
+        if (a.nreg != Nreg || a.u != U) return fcd_fail(ctx, FCD_ERR_SHAPE, SWEEP_ACC[k].msg_shape, a.nreg, a.u);
+        acc_mask |= 1u << k;
+    }
+    if (acc_mask >> FCD_ACC_COUNT & 1u) {
         rc = fcd_count_ws_reserve(ctx, Nreg, U, G);          // (grown here, never inside the sweep loop)
         if (rc) return rc;
     }
-    return sweep_loop(ctx, c, sweep0, n_sweeps, mstep_every, accumulate_from, counts, cnt_f, cnt_r, hyper, ctx->pair_acc != nullptr,
-                      ctx->count_hp != nullptr, ctx->coan_rp != nullptr);
+    return sweep_loop(ctx, c, sweep0, n_sweeps, mstep_every, accumulate_from, counts, cnt_f, cnt_r, hyper, acc_mask);
 }
 
 // fcd_gibbs_run's loop without M-step, marginal counters, pair, anomalous-region or co-anomaly counts.  The counts are made by fcd_gibbs_stats after the
@@ -1565,7 +1575,7 @@ extern "C" int fcd_gibbs_sweeps(fcd_ctx *ctx, const double *S_B, const double *l
     fcd_sweep_call c = {S_B, lM, lMf, lMd, hyper, f_state, r_bits, Nreg, U, G, chain0, seed, edge_mode, (hipStream_t)stream};
     int rc = fcd_sweep_call_check(ctx, c, true, true, "fcd_gibbs_sweeps");
     if (rc) return rc;
-    rc = sweep_loop(ctx, c, sweep0, n_sweeps, 0, 0, nullptr, nullptr, nullptr, nullptr, false, false, false);
+    rc = sweep_loop(ctx, c, sweep0, n_sweeps, 0, 0, nullptr, nullptr, nullptr, nullptr, 0u);
     if (rc) return rc;
     if (counts && n_sweeps > 0) return fcd_gibbs_stats(ctx, f_state, r_bits, Nreg, U, G, counts, stream);
     return FCD_OK;

@@ -197,20 +197,9 @@ extern "C" int fcd_gibbs_pair_tally(fcd_ctx *ctx, const uint8_t *f_state, const 
 }
 
 extern "C" int fcd_gibbs_set_pair_accumulator(fcd_ctx *ctx, uint32_t *acc, int64_t Nreg, int64_t U, int64_t every) {
-    if (!ctx) return FCD_ERR_ARG;
-    if (!acc) {
-        ctx->pair_acc = nullptr;
-        ctx->pair_nreg = ctx->pair_u = 0;
-        ctx->pair_every = 1;
-        return FCD_OK;
-    }
-    if (Nreg < 2 || U < 1) return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_gibbs_set_pair_accumulator: Nreg=%lld U=%lld", Nreg, U);
-    if (every < 1) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_set_pair_accumulator: every=%lld must be >= 1", every);
-    ctx->pair_acc = acc;
-    ctx->pair_nreg = Nreg;
-    ctx->pair_u = U;
-    ctx->pair_every = every;
-    return FCD_OK;
+    // (one buffer, given as both: "go together" cannot arise)
+    return fcd_sweep_acc_set(ctx, FCD_ACC_PAIR, acc, acc, Nreg, U, every, nullptr, "fcd_gibbs_set_pair_accumulator: Nreg=%lld U=%lld",
+                             nullptr, "fcd_gibbs_set_pair_accumulator: every=%lld must be >= 1");
 }
 
 extern "C" int fcd_conn_posterior_ex(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, const double *theta,

@@ -34,13 +34,28 @@ Differences from the reference that are deliberate and documented (SURVEY.md sec
       implemented (`_update_theta_sub`, analytic gradient on the device) but stays OFF by default
       (`update_theta_sub = False`) so that the default trajectory is the one the fixtures pin.
 """
+import collections
+
 import numpy as np
 
 from . import _lib
 from . import util
 from . import score as _score
 from . import tables
-from .gibbs import GibbsEngine, run_chains, allreduce_counts, pool_u32, pair_sweeps_in, PAIR_COUNT_MAX, COUNT_MAX_NREG, COUNT_MAX_U
+from .gibbs import (GibbsEngine, run_chains, allreduce_counts, pool_u32, pair_sweeps_in, ACCUMULATORS, PAIR_COUNT_MAX,
+                    COUNT_MAX_NREG, COUNT_MAX_U)
+
+# The knobs of a gibbs fit that attach one of the sampler's accumulators: knob, its period knob, what the messages call it,
+# the row of gibbs.ACCUMULATORS, and the attributes the pooled buffers and the number of sweeps behind them are left in.
+FitAccumulator = collections.namedtuple("FitAccumulator", "knob every label engine results sweeps")
+GIBBS_ACCUMULATORS = (
+    FitAccumulator("connection_marginals", "connection_every", "connection counts", ACCUMULATORS[0],
+                   ("connection_counts",), "connection_sweeps"),
+    FitAccumulator("anomaly_counts", "anomaly_counts_every", "anomaly-count histograms", ACCUMULATORS[1],
+                   ("patient_count_hist", "region_count_hist"), "anomaly_count_sweeps"),
+    FitAccumulator("coanomaly", "coanomaly_every", "co-anomaly counts", ACCUMULATORS[2],
+                   ("region_pair_counts", "patient_pair_counts"), "coanomaly_sweeps"),
+)
 
 
 class UnsharedRegionFit(object):
@@ -576,29 +591,21 @@ class UnsharedRegionFit(object):
         log-joint at the recorded sweeps.
         """
         t = self._torch()
-        self.connection_counts = None
-        self.connection_sweeps = 0
-        if self.connection_marginals:
-            self._check_accumulator("connection_every", "connection counts")
-        self.patient_count_hist = self.region_count_hist = None
-        self.anomaly_count_sweeps = 0
-        if self.anomaly_counts:
-            self._check_accumulator("anomaly_counts_every", "anomaly-count histograms")
-            if N > COUNT_MAX_NREG or U > COUNT_MAX_U:
-                raise ValueError("anomaly-count histograms are made for at most %d regions and %d patients (here %d, %d)"
-                                 % (COUNT_MAX_NREG, COUNT_MAX_U, N, U))
-        self.region_pair_counts = self.patient_pair_counts = None
-        self.coanomaly_sweeps = self.coanomaly_states = 0
-        if self.coanomaly:
-            self._check_accumulator("coanomaly_every", "co-anomaly counts", sites=max(N, U))
+        self.coanomaly_states = 0
+        for a in GIBBS_ACCUMULATORS:
+            for name in a.results:
+                setattr(self, name, None)
+            setattr(self, a.sweeps, 0)
+            if getattr(self, a.knob):
+                self._check_accumulator(a.every, a.label, sites=a.engine.sites(N, U) if a.engine.sites else 1)
+        if self.anomaly_counts and (N > COUNT_MAX_NREG or U > COUNT_MAX_U):
+            raise ValueError("anomaly-count histograms are made for at most %d regions and %d patients (here %d, %d)"
+                             % (COUNT_MAX_NREG, COUNT_MAX_U, N, U))
         eng = GibbsEngine(self._d["S_B"], self._d["lM"], N, U, self.n_chains, chain0=self.chain0, seed=self.seed,
                           edge_index=self._edge_mode(), ctx=self._context())
-        if self.connection_marginals:
-            eng.attach_pair_accumulator(self.connection_every)
-        if self.anomaly_counts:
-            eng.attach_count_accumulator(self.anomaly_counts_every)
-        if self.coanomaly:
-            eng.attach_coanomaly_accumulator(self.coanomaly_every)
+        for a in GIBBS_ACCUMULATORS:
+            if getattr(self, a.knob):
+                eng._attach(a.engine, getattr(self, a.every))
         pi2 = self._pi2()
         eng.set_hyper(np.asarray(self.model.gamma, dtype=np.float64), pi2)
         eng.init(float(pi2[1]))
@@ -650,19 +657,12 @@ class UnsharedRegionFit(object):
             self._lq_F = np.log(cnt[:3 * C].reshape(C, 1, 3) / total)
             p1 = cnt[3 * C:3 * C + N * U].reshape(N, U) / total
             self._lq_R = np.log(np.stack([1.0 - p1, p1], axis=2))
-        if eng.pair_acc is not None:
-            self.connection_counts = pool_u32(eng.pair_acc).cpu().numpy()
-            self.connection_sweeps = eng.pair_sweeps
-        if eng.count_hist is not None:
-            (hp, hr) = (pool_u32(h) for h in eng.count_hist)
-            self.patient_count_hist = hp.cpu().numpy()
-            self.region_count_hist = hr.cpu().numpy()
-            self.anomaly_count_sweeps = eng.count_sweeps
+        for a in GIBBS_ACCUMULATORS:
+            if getattr(eng, a.engine.attr) is not None:
+                for (name, buf) in zip(a.results, eng._acc_buffers(a.engine)):
+                    setattr(self, name, pool_u32(buf).cpu().numpy())
+                setattr(self, a.sweeps, getattr(eng, a.engine.key + "_sweeps"))
         if eng.coanomaly_acc is not None:
-            (rp, pp) = (pool_u32(a) for a in eng.coanomaly_acc)
-            self.region_pair_counts = rp.cpu().numpy()
-            self.patient_pair_counts = pp.cpu().numpy()
-            self.coanomaly_sweeps = eng.coanomaly_sweeps
             states = t.tensor([eng.coanomaly_sweeps * eng.G], dtype=t.int64, device=eng.cnt_f.device)
             self.coanomaly_states = int(allreduce_counts(states).cpu()[0])
         (gamma, pi) = eng.hyper_values()

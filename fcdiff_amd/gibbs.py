@@ -10,6 +10,7 @@ Multi-GPU (one process per GPU, torch.distributed, backend "nccl" = RCCL): chain
 the tables, so rank k simply owns global chain ids [chain0, chain0 + G).  The only exchange is the
 all-reduce of the 8-word pooled-count vector before an M-step; there is no data-path collective.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -21,6 +22,22 @@ from . import util
 
 PAIR_COUNT_MAX = (1 << 32) - 1
 COUNT_MAX_NREG, COUNT_MAX_U = 1023, 512      # largest shape of the anomalous-region histograms (fcd_gibbs_count_tally)
+
+# The uint32 accumulators GibbsEngine.run() can add to after a counted sweep, in the order it checks and attaches them.
+# Engine attributes of one: `attr` holds the buffers (None: detached; one tensor, or a pair where `paired`), <key>_every the
+# period and <key>_sweeps the sweeps added so far.  shapes: engine -> shape of each buffer; setter: the library's entry point
+# (buffers, Nreg, U, every); sites: None, or (Nreg, U) -> how many sites of a chain one counter can take per sweep; label:
+# the accumulator's name in the error messages.
+Accumulator = collections.namedtuple("Accumulator", "key attr paired shapes setter sites label")
+ACCUMULATORS = (
+    Accumulator("pair", "pair_acc", False, lambda e: ((e.C, e.U, 3, 3),), "fcd_gibbs_set_pair_accumulator", None, "pair"),
+    Accumulator("count", "count_hist", True, lambda e: ((e.U, e.Nreg + 1), (e.Nreg, e.U + 1)),
+                "fcd_gibbs_set_count_accumulator", None, "count"),
+    # (a diagonal entry counts up to G x U or G x Nreg sites per sweep)
+    Accumulator("coanomaly", "coanomaly_acc", True, lambda e: ((e.Nreg, e.Nreg), (e.U, e.U)),
+                "fcd_gibbs_set_coanomaly_accumulator", lambda Nreg, U: max(Nreg, U), "co-anomaly"),
+)
+(_PAIR, _COUNT, _COANOMALY) = ACCUMULATORS
 
 
 def pair_sweeps_in(sweep0, n_sweeps, accumulate_from, every):
@@ -198,48 +215,28 @@ class GibbsEngine(object):
         `coanomaly_every`-th sweep; a call that could overflow any of them raises ValueError.
         """
         acc = accumulate_from is not None
-        pair = self.pair_acc is not None and acc
-        count = self.count_hist is not None and acc
-        (n_pair, n_count, n_coan) = (0, 0, 0)
-        if pair:
-            n_pair = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), self.pair_every)
-            if (self.pair_sweeps + n_pair) * self.G > PAIR_COUNT_MAX:
-                raise ValueError("the pair accumulator would overflow uint32: %d chains x %d accumulated sweeps > %d"
-                                 % (self.G, self.pair_sweeps + n_pair, PAIR_COUNT_MAX))
-        if count:
-            n_count = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), self.count_every)
-            if (self.count_sweeps + n_count) * self.G > PAIR_COUNT_MAX:
-                raise ValueError("the count accumulator would overflow uint32: %d chains x %d accumulated sweeps > %d"
-                                 % (self.G, self.count_sweeps + n_count, PAIR_COUNT_MAX))
-        coan = self.coanomaly_acc is not None and acc
-        if coan:
-            n_coan = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), self.coanomaly_every)
-            # (a diagonal entry counts up to G x U or G x Nreg sites per sweep)
-            if (self.coanomaly_sweeps + n_coan) * self.G * max(self.Nreg, self.U) > PAIR_COUNT_MAX:
-                raise ValueError("the co-anomaly accumulator would overflow uint32: %d chains x %d sites x %d accumulated "
-                                 "sweeps > %d" % (self.G, max(self.Nreg, self.U), self.coanomaly_sweeps + n_coan,
-                                                  PAIR_COUNT_MAX))
+        live = []                   # (accumulator, sweeps this call adds to it), attached ones only
+        for a in ACCUMULATORS:      # (in this order, and nothing of an accumulator is read unless it is attached)
+            if not acc or getattr(self, a.attr) is None:
+                continue
+            n = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), getattr(self, a.key + "_every"))
+            total = getattr(self, a.key + "_sweeps") + n
+            sites = a.sites(self.Nreg, self.U) if a.sites else 1
+            if total * self.G * sites > PAIR_COUNT_MAX:
+                raise ValueError("the %s accumulator would overflow uint32: %d chains x %s%d accumulated sweeps > %d"
+                                 % (a.label, self.G, "%d sites x " % sites if a.sites else "", total, PAIR_COUNT_MAX))
+            live.append((a, n))
         # (attached for this call only: the context is shared, no other engine's sweeps may add to these buffers)
         try:
-            if pair:
-                self.ctx.call("fcd_gibbs_set_pair_accumulator", _lib.dptr(self.pair_acc), self.Nreg, self.U, self.pair_every)
-            if count:
-                self.ctx.call("fcd_gibbs_set_count_accumulator", _lib.dptr(self.count_hist[0]), _lib.dptr(self.count_hist[1]),
-                              self.Nreg, self.U, self.count_every)
-            if coan:
-                self.ctx.call("fcd_gibbs_set_coanomaly_accumulator", _lib.dptr(self.coanomaly_acc[0]),
-                              _lib.dptr(self.coanomaly_acc[1]), self.Nreg, self.U, self.coanomaly_every)
+            for (a, _n) in live:
+                self.ctx.call(a.setter, *([_lib.dptr(b) for b in self._acc_buffers(a)]
+                                          + [self.Nreg, self.U, getattr(self, a.key + "_every")]))
             self._run(sweep0, n_sweeps, mstep_every, accumulate_from, want_counts)
         finally:
-            if pair:
-                self.ctx.call("fcd_gibbs_set_pair_accumulator", None, 0, 0, 1)
-            if count:
-                self.ctx.call("fcd_gibbs_set_count_accumulator", None, None, 0, 0, 1)
-            if coan:
-                self.ctx.call("fcd_gibbs_set_coanomaly_accumulator", None, None, 0, 0, 1)
-        self.pair_sweeps += n_pair
-        self.count_sweeps += n_count
-        self.coanomaly_sweeps += n_coan
+            for (a, _n) in live:
+                self.ctx.call(a.setter, *([None] * (2 if a.paired else 1) + [0, 0, 1]))
+        for (a, n) in live:
+            setattr(self, a.key + "_sweeps", getattr(self, a.key + "_sweeps") + n)
         if acc:
             self.n_accumulated += max(0, int(sweep0) + int(n_sweeps) - max(int(accumulate_from), int(sweep0)))
         return self.counts if want_counts else None
@@ -252,31 +249,47 @@ class GibbsEngine(object):
                       int(accumulate_from) if acc else 0, _lib.dptr(self.counts if want_counts else None),
                       _lib.dptr(self.cnt_f if acc else None), _lib.dptr(self.cnt_r if acc else None), _lib.stream_ptr())
 
+    # ---- the accumulators of run(): one implementation for the rows of ACCUMULATORS ----
+    def _acc_buffers(self, a):
+        bufs = getattr(self, a.attr)
+        return bufs if a.paired else (bufs,)
+
+    def _attach(self, a, every):
+        every = int(every)
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        t = self.torch
+        # (uint32 on the device, held in int32 tensors like cnt_f; _acc_host() reads them back as uint32)
+        bufs = tuple(t.zeros(shape, dtype=t.int32, device=self.f_state.device) for shape in a.shapes(self))
+        setattr(self, a.attr, bufs if a.paired else bufs[0])
+        setattr(self, a.key + "_every", every)
+        setattr(self, a.key + "_sweeps", 0)
+        return getattr(self, a.attr)
+
+    def _detach(self, a):
+        setattr(self, a.attr, None)
+        setattr(self, a.key + "_sweeps", 0)
+
+    def _acc_host(self, a):
+        if getattr(self, a.attr) is None:
+            raise ValueError("no %s accumulator is attached" % a.label)
+        out = tuple(self.host(b).view(np.uint32) for b in self._acc_buffers(a))
+        return out if a.paired else out[0]
+
     # ---- (f_c, mixture case) counts for the connection posteriors ----
     def attach_pair_accumulator(self, every=1):
         """
         From now on run() adds the end-of-sweep counts of (f_c = k, mixture case l at (c,u)) to `pair_acc` (C, U, 3, 3),
         at every `every`-th sweep from its `accumulate_from` on (none when accumulate_from is None).  Zeroes the counts.
         """
-        every = int(every)
-        if every < 1:
-            raise ValueError("every must be >= 1")
-        t = self.torch
-        # (uint32 on the device, held in an int32 tensor like cnt_f; pair_counts_host() reads it back as uint32)
-        self.pair_acc = t.zeros((self.C, self.U, 3, 3), dtype=t.int32, device=self.f_state.device)
-        self.pair_every = every
-        self.pair_sweeps = 0
-        return self.pair_acc
+        return self._attach(_PAIR, every)
 
     def detach_pair_accumulator(self):
-        self.pair_acc = None
-        self.pair_sweeps = 0
+        self._detach(_PAIR)
 
     def pair_counts_host(self):
         """The attached accumulator as a NumPy uint32 array (C, U, 3, 3)."""
-        if self.pair_acc is None:
-            raise ValueError("no pair accumulator is attached")
-        return self.host(self.pair_acc).view(np.uint32)
+        return self._acc_host(_PAIR)
 
     def pair_tally(self, acc):
         """acc (C, U, 3, 3) uint32-in-int32 tensor += the (f_c, mixture case) counts of the current state."""
@@ -291,27 +304,14 @@ class GibbsEngine(object):
         (hist_region (Nreg, U+1)) over chains to `count_hist`, at every `every`-th sweep from its `accumulate_from` on
         (none when accumulate_from is None).  Zeroes the histograms.
         """
-        every = int(every)
-        if every < 1:
-            raise ValueError("every must be >= 1")
-        t = self.torch
-        dev = self.f_state.device
-        # (uint32 on the device, held in int32 tensors like pair_acc; count_hist_host() reads them back as uint32)
-        self.count_hist = (t.zeros((self.U, self.Nreg + 1), dtype=t.int32, device=dev),
-                           t.zeros((self.Nreg, self.U + 1), dtype=t.int32, device=dev))
-        self.count_every = every
-        self.count_sweeps = 0
-        return self.count_hist
+        return self._attach(_COUNT, every)
 
     def detach_count_accumulator(self):
-        self.count_hist = None
-        self.count_sweeps = 0
+        self._detach(_COUNT)
 
     def count_hist_host(self):
         """The attached histograms as NumPy uint32 arrays (hist_patient (U, Nreg+1), hist_region (Nreg, U+1))."""
-        if self.count_hist is None:
-            raise ValueError("no count accumulator is attached")
-        return tuple(self.host(h).view(np.uint32) for h in self.count_hist)
+        return self._acc_host(_COUNT)
 
     def count_tally(self, hist_patient, hist_region):
         """hist_patient (U, Nreg+1), hist_region (Nreg, U+1) uint32-in-int32 tensors += the histograms of the current state."""
@@ -330,27 +330,14 @@ class GibbsEngine(object):
         patient_pairs[u, v] = #{(chain, n): r_nu = r_nv = 1} (U, U) to `coanomaly_acc`, at every `every`-th sweep from its
         `accumulate_from` on (none when accumulate_from is None).  Zeroes the matrices.
         """
-        every = int(every)
-        if every < 1:
-            raise ValueError("every must be >= 1")
-        t = self.torch
-        dev = self.f_state.device
-        # (uint32 on the device, held in int32 tensors like count_hist; coanomaly_host() reads them back as uint32)
-        self.coanomaly_acc = (t.zeros((self.Nreg, self.Nreg), dtype=t.int32, device=dev),
-                              t.zeros((self.U, self.U), dtype=t.int32, device=dev))
-        self.coanomaly_every = every
-        self.coanomaly_sweeps = 0
-        return self.coanomaly_acc
+        return self._attach(_COANOMALY, every)
 
     def detach_coanomaly_accumulator(self):
-        self.coanomaly_acc = None
-        self.coanomaly_sweeps = 0
+        self._detach(_COANOMALY)
 
     def coanomaly_host(self):
         """The attached matrices as NumPy uint32 arrays (region_pairs (Nreg, Nreg), patient_pairs (U, U))."""
-        if self.coanomaly_acc is None:
-            raise ValueError("no co-anomaly accumulator is attached")
-        return tuple(self.host(a).view(np.uint32) for a in self.coanomaly_acc)
+        return self._acc_host(_COANOMALY)
 
     def coanomaly_tally(self, region, patient):
         """region (Nreg, Nreg), patient (U, U) uint32-in-int32 tensors += the pair counts of the current state."""

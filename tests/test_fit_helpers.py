@@ -131,3 +131,69 @@ def test_data_digest_sees_in_place_edits():
         UnsharedRegionFit._data_digest(bt, "crc")
     assert UnsharedRegionFit._array_key(bt) == UnsharedRegionFit._array_key(bt)
     assert UnsharedRegionFit._array_key(bt) != UnsharedRegionFit._array_key(bt.copy())
+
+
+@pytest.mark.parametrize("row", [0, 1, 2])
+def test_engine_accumulators_share_one_overflow_rule(row):
+    """
+    GibbsEngine.run() over the rows of gibbs.ACCUMULATORS, on stand-ins made with __new__ (no library, no GPU): the rows are
+    checked in the table's order and nothing of a row is read unless its buffers are attached (the first stand-in has
+    nothing of the later rows: touching one is an AttributeError, not the ValueError asked for); a counter takes exactly
+    PAIR_COUNT_MAX // (G * sites) accumulated sweeps; the accumulator is attached for the call only, also when the call
+    fails, and only a call that returned advances the counter.
+    """
+    import torch
+    from fcdiff_amd import gibbs
+    a = gibbs.ACCUMULATORS[row]
+    assert (a.key, a.attr, a.label) == (("pair", "pair_acc", "pair"), ("count", "count_hist", "count"),
+                                        ("coanomaly", "coanomaly_acc", "co-anomaly"))[row]
+    (G, N, U) = (1000, 7, 12)
+    sites = a.sites(N, U) if a.sites else 1
+    assert sites == (1, 1, 12)[row]
+    limit = gibbs.PAIR_COUNT_MAX // (G * sites)
+    wording = "the %s accumulator would overflow uint32: 1000 chains x %s" % (a.label, "12 sites x " if row == 2 else "")
+
+    def stand_in(later_rows):
+        eng = gibbs.GibbsEngine.__new__(gibbs.GibbsEngine)
+        (eng.G, eng.Nreg, eng.U) = (G, N, U)
+        for other in gibbs.ACCUMULATORS[:row] + (gibbs.ACCUMULATORS[row + 1:] if later_rows else ()):
+            setattr(eng, other.attr, None)
+        setattr(eng, a.attr, (None, None) if a.paired else torch.zeros(1, dtype=torch.int32))
+        setattr(eng, a.key + "_every", 1)
+        setattr(eng, a.key + "_sweeps", 0)
+        return eng
+
+    eng = stand_in(False)
+    with pytest.raises(ValueError, match=wording + "%d accumulated sweeps" % (limit + 1)):
+        eng.run(0, limit + 1, accumulate_from=0)
+    setattr(eng, a.key + "_sweeps", limit - 4)                       # earlier sweeps count too
+    with pytest.raises(ValueError, match=wording):
+        eng.run(limit - 4, 10, accumulate_from=limit + 1)
+    setattr(eng, a.key + "_every", 3)                                # ... and only every third sweep from accumulate_from on
+    with pytest.raises(ValueError, match=wording):
+        eng.run(0, 13, accumulate_from=0)
+
+    class Recorder(object):
+        def __init__(self):
+            self.calls = []
+
+        def call(self, name, *args):
+            self.calls.append((name, args[-3:]))
+    eng = stand_in(True)
+    (eng.ctx, eng.n_accumulated, eng._run) = (Recorder(), 0, lambda *args: None)
+    eng.run(0, limit, accumulate_from=0)                             # exactly full
+    assert getattr(eng, a.key + "_sweeps") == limit
+    assert eng.ctx.calls == [(a.setter, (N, U, 1)), (a.setter, (0, 0, 1))]
+    with pytest.raises(ValueError, match=wording + "%d accumulated sweeps" % (limit + 1)):
+        eng.run(limit, 1, accumulate_from=0)
+    eng.run(limit, 5, accumulate_from=None)                          # nothing is counted, nothing attached
+    assert getattr(eng, a.key + "_sweeps") == limit and len(eng.ctx.calls) == 2
+
+    def failing(*args):
+        raise RuntimeError("the sweeps failed")
+    setattr(eng, a.key + "_sweeps", 0)
+    eng._run = failing
+    with pytest.raises(RuntimeError):
+        eng.run(0, 4, accumulate_from=1)
+    assert getattr(eng, a.key + "_sweeps") == 0
+    assert eng.ctx.calls[2:] == [(a.setter, (N, U, 1)), (a.setter, (0, 0, 1))]

@@ -407,3 +407,58 @@ def test_refusals_with_a_context(env):
     nptest.assert_array_equal(f1, f0)
     nptest.assert_array_equal(r1, r0)
     assert all(int(a.sum()) == 0 for a in eng.coanomaly_host())
+
+
+def test_each_accumulator_alone_equals_all_together(env):
+    """
+    The three accumulators of fcd_gibbs_run at periods 1 (pair), 2 (count) and 3 (co-anomaly), so that each counts other
+    sweeps: every buffer of a run with all three attached equals, bit for bit, that of a run from the same seed with this
+    one attached alone, and the sweep counters are pair_sweeps_in's.  Nreg = 6, U = 3, G = 130: three chain words, two
+    live lanes in the last.  fcd_gibbs_sweeps adds nothing, whatever is attached to the context.
+    """
+    from fcdiff_amd.gibbs import ACCUMULATORS
+    (N, U, G, n_sweeps, burn) = (6, 3, 130, 7, 2)
+    every = {"pair": 1, "count": 2, "coanomaly": 3}
+    (m, S_B, lM) = tables(env, N, 4, U, seed=11)
+    (S_B_d, lM_d) = (up(env, S_B), up(env, lM))
+
+    def run(keys):
+        e = env.GibbsEngine(S_B_d, lM_d, N, U, G, chain0=0, seed=77, edge_index="symmetric", ctx=env.ctx)
+        e.set_hyper(m.gamma, m.pi2())
+        e.init(0.3)
+        for k in keys:
+            getattr(e, "attach_%s_accumulator" % k)(every[k])
+        e.run(0, n_sweeps, mstep_every=1, accumulate_from=burn)
+        return e
+
+    def buffers(e, k):
+        got = {"pair": e.pair_counts_host, "count": e.count_hist_host, "coanomaly": e.coanomaly_host}[k]()
+        return got if isinstance(got, tuple) else (got,)
+    together = run(["pair", "count", "coanomaly"])
+    assert (together.pair_sweeps, together.count_sweeps, together.coanomaly_sweeps) == (5, 3, 2)
+    for a in ACCUMULATORS:
+        alone = run([a.key])
+        assert [getattr(alone, b.attr) is not None for b in ACCUMULATORS] == [b is a for b in ACCUMULATORS]
+        want = env.pair_sweeps_in(0, n_sweeps, burn, every[a.key])
+        assert getattr(alone, a.key + "_sweeps") == getattr(together, a.key + "_sweeps") == want
+        (one, all3) = (buffers(alone, a.key), buffers(together, a.key))
+        assert [tuple(x.shape) for x in one] == [tuple(s) for s in a.shapes(alone)]
+        for (x, y) in zip(one, all3):
+            nptest.assert_array_equal(x, y)
+    assert int(together.pair_counts_host()[0, 0].sum()) == G * 5
+    assert np.all(together.count_hist_host()[0].astype(np.int64).sum(axis=1) == G * 3)
+    (rp, pp) = (x.astype(np.int64) for x in together.coanomaly_host())
+    assert np.trace(rp) == np.trace(pp) and np.array_equal(rp, rp.T)
+    # fcd_gibbs_sweeps with all three attached to the context: it is not their caller
+    t = env.torch
+    raw = [[t.zeros(shape, dtype=t.int32, device="cuda") for shape in a.shapes(together)] for a in ACCUMULATORS]
+    try:
+        for (a, bufs) in zip(ACCUMULATORS, raw):
+            env.ctx.call(a.setter, *([env.lib.dptr(b) for b in bufs] + [N, U, 1]))
+        together.sweeps(7, 2)
+        assert all(int(b.abs().sum()) == 0 for bufs in raw for b in bufs)
+    finally:
+        for (a, bufs) in zip(ACCUMULATORS, raw):
+            env.ctx.call(a.setter, *([None] * len(bufs) + [0, 0, 1]))
+    for (x, y) in zip(buffers(together, "coanomaly"), (rp, pp)):
+        nptest.assert_array_equal(x.astype(np.int64), y)
