@@ -65,10 +65,21 @@ class UnsharedRegionFit(object):
     Attributes
     ----------
     model : fcdiff_amd.UnsharedRegionModel      initial model; updated in place by run()
-    b : ndarray (C, H), bt : ndarray (C, U)     correlations of healthy subjects / patients
+    b : ndarray (C, H), bt : ndarray (C, U)     correlations of healthy subjects / patients; bt may be (C, U, K): K sessions
+                                                of every patient (`n_sessions`), see "Repeated sessions" below
     max_iters : int, rel_tol : float            iteration cap / relative tolerance of _is_converged
     energy : list of float                      variational free energy per iteration (vb) or minus the
                                                 chain-mean log-joint per recorded sweep (gibbs)
+
+    Repeated sessions
+    -----------------
+    bt (C, U, K) holds K scans of every patient.  F~_cu is the patient's latent state of the connection and the sessions
+    are conditionally independent measurements of it, so an item's density given F~ = j is prod_k N(bt[c,u,k]; mu_j,
+    sigma_j), taken in log form by the table kernel; the state (`_lq_R` (N, U, 2), `_lM` (C, U, 3, 3)), the VB updates,
+    the sampler and every query keep their shapes.  Patients with different numbers of sessions pad with NaN and set
+    missing_data = True: a NaN session contributes nothing, and missing_counts() counts NaN session entries.  Extra
+    sessions of controls are extra columns of b.  Not provided with sessions: the theta_sub step (update_theta_sub,
+    theta_sub_every: NotImplementedError from run()) and the per-item table `_p_Bt_g_Ft` (ValueError).
     """
 
     # SharedRegionFit: the tables are (S_B, L) of ONE patient (tables.build(shared=True)), so the state's patient extent is 1,
@@ -159,6 +170,21 @@ class UnsharedRegionFit(object):
         if d is None or tuple(d.shape) != np.shape(a):
             d = self._up(a)
         return d
+
+    @property
+    def n_sessions(self):
+        """K of a bt (C, U, K); 1 for a bt (C, U) (and before bt is set)."""
+        shp = np.shape(self.bt) if self.bt is not None else ()
+        return int(shp[2]) if len(shp) == 3 else 1
+
+    def _has_sessions(self):
+        return self.bt is not None and np.ndim(self.bt) == 3
+
+    def _refuse_theta_sub_sessions(self):
+        """The theta_sub objectives read bt item by item, one scan per patient: no sessions form yet."""
+        if self._has_sessions() and (self.update_theta_sub or self.theta_sub_every):
+            raise NotImplementedError("the theta_sub step (update_theta_sub / theta_sub_every, either theta_sub_params) is not "
+                                      "provided for sessions data bt (C, U, K): its objective kernels read one scan per patient")
 
     def _require_fitted(self, what):
         """ValueError unless run() has left a fit of self.method behind: a sampler (gibbs), or q_F and an energy (vb)."""
@@ -273,6 +299,8 @@ class UnsharedRegionFit(object):
 
     @property
     def _p_Bt_g_Ft(self):
+        if self._has_sessions():
+            raise ValueError("_p_Bt_g_Ft is not made for sessions data bt (C, U, K): a product of densities underflows")
         if self._d.get("pBt") is None and self.bt is not None and self.model is not None and "lM" in self._d:
             self._tables(full=True)
         return self._get("pBt")
@@ -284,7 +312,10 @@ class UnsharedRegionFit(object):
     # ------------------------------------------------------------------ reference methods
     def run(self):
         """Runs the fitting procedure (fcdiff/fit.py:56-82; doc/methods.rst:564-600)."""
+        self._refuse_theta_sub_sessions()
         (C, H) = self.b.shape
+        if np.ndim(self.bt) not in (2, 3) or (np.ndim(self.bt) == 3 and np.shape(self.bt)[2] < 1):
+            raise ValueError("bt must be (C, U) or (C, U, K) with K >= 1 sessions, got shape %s" % (np.shape(self.bt),))
         U = self.bt.shape[1]
         N = util.C_to_N(C)
         if (N % 1) != 0:
@@ -361,7 +392,8 @@ class UnsharedRegionFit(object):
         lpB = pBt = None
         if full and not self._shared:
             lpB = t.empty((C, H, 3), dtype=t.float64, device=dev)
-            pBt = t.empty((C, U, 3), dtype=t.float64, device=dev)
+            if bt.ndim == 2:                 # (sessions: no per-item product of densities, see _p_Bt_g_Ft)
+                pBt = t.empty((C, U, 3), dtype=t.float64, device=dev)
         n_missing = None
         if self.missing_data:
             # the kernel counts the NaN entries on the device; missing_counts() reads them when asked (no sync here).  The
@@ -382,7 +414,8 @@ class UnsharedRegionFit(object):
 
     def missing_counts(self):
         """
-        (n_missing_b, n_missing_bt): the number of NaN entries of b and of bt the last table build integrated out.  Needs
+        (n_missing_b, n_missing_bt): the number of NaN entries of b and of bt the last table build integrated out (of a
+        bt (C, U, K): NaN session entries, so a patient padded from 2 to K sessions counts K - 2 per connection).  Needs
         missing_data = True and a table build (run(), _update_lps()); the counts come from the table kernel, so this
         read waits for it.
         """
@@ -404,7 +437,8 @@ class UnsharedRegionFit(object):
                   of host time per call (round 3 ran it on every _update_lps: 8.6 ms per variational iteration at cfg3,
                   165 ms at cfg5, beside 0.5 / 2.5 ms of kernels -- VERDICT r3).
         'sample'  (default) CRC-32 of 4096 elements taken with a stride that is coprime to the row length, so that
-                  every column is visited ~4096/U times: sees whole-array edits (scaling, clipping, Fisher z) and
+                  every column (of a bt (C, U, K): every session of every patient; the row is a connection's U*K
+                  values) is visited ~4096/U times: sees whole-array edits (scaling, clipping, Fisher z) and
                   whole-column edits; an edit of a few single elements between two _update_lps() calls of the same
                   fit needs invalidate_data() (documented contract; _init_lps() and run() always upload afresh).
         'none'    identity / address / shape only.
@@ -418,7 +452,7 @@ class UnsharedRegionFit(object):
             return zlib.crc32(flat.view(np.uint8))
         if mode != "sample":
             raise ValueError("data_check must be 'sample', 'full' or 'none'")
-        row = a.shape[-1] if a.ndim > 1 else 1
+        row = int(np.prod(a.shape[1:])) if a.ndim > 1 else 1      # (C, U, K): a row is a connection's U*K values
         step = max(1, flat.size // 4096)
         while gcd(step, row) != 1:
             step += 1
@@ -546,6 +580,8 @@ class UnsharedRegionFit(object):
 
     def _update_theta_sub(self):
         """
+        Not provided for sessions data bt (C, U, K): NotImplementedError before anything is launched.
+
         Updates (eta, epsilon) (fit.py:222-241): bounded minimisation of -E_lM with the other terms fixed, bounds
         (1e-5, 1 - 1e-5) on both, L-BFGS-B.  The reference's version cannot run (it calls the undefined `opt_fun`,
         fit.py:239) and would difference the objective numerically (`jac=False`); here objective AND its two analytic
@@ -554,6 +590,9 @@ class UnsharedRegionFit(object):
         out of its optimiser, fit.py:232-237, 250-251); 'all' reads those lines in: (eta, epsilon, mu, sigma^2) jointly,
         objective E[ln p(b|f)] + E[ln p(bt|f,r)] (fit.py:282), fcd_theta_full_objective.
         """
+        if self._has_sessions():
+            raise NotImplementedError("the theta_sub step is not provided for sessions data bt (C, U, K): its objective "
+                                      "kernels read one scan per patient")
         W = self._theta_sub_weights()
         if self.theta_sub_params == "all":
             # the reference's commented-out intent (fit.py:232-237, 250-251, 266-267, 282): mu and sigma too
@@ -823,7 +862,8 @@ class UnsharedRegionFit(object):
         sampler's chains or theta, and score() leaves the fit exactly as it was (model, _lq_R, _lq_F, energy, the device
         tables, `sampler` and its state).  Call it after run().
 
-        bt_new (C, U') correlations of the new patients in the fit's edge order (NaN = unobserved when missing_data).
+        bt_new (C, U') correlations of the new patients in the fit's edge order (NaN = unobserved when missing_data), or
+        (C, U', K') with K' sessions of every new patient; K' need not be the fit's n_sessions.
         theta is the model's CURRENT parameters, the plug-in convention of connection_posterior().  Given F and theta the
         patients are independent (doc/methods.rst): with method='vb' a new patient's numbers are exactly those it gets when
         scored alone; with method='gibbs' they have the same law (the random numbers of a site follow its column index).
@@ -853,9 +893,9 @@ class UnsharedRegionFit(object):
             raise ValueError("method must be 'vb' or 'gibbs'")
         self._require_fitted("score()")
         bt_new = np.ascontiguousarray(bt_new, dtype=np.float64)
-        if bt_new.ndim != 2:
-            raise ValueError("bt_new must be (C, U'), got shape %s" % (bt_new.shape,))
-        (C, U) = bt_new.shape
+        if bt_new.ndim not in (2, 3) or (bt_new.ndim == 3 and bt_new.shape[2] < 1):
+            raise ValueError("bt_new must be (C, U') or (C, U', K') with K' >= 1, got shape %s" % (bt_new.shape,))
+        (C, U) = bt_new.shape[:2]
         C_fit = int(self._d["lq_F"].shape[0]) if self.method == "vb" else int(self.sampler.C)
         if C != C_fit:
             raise ValueError("bt_new has %d connections, the fit has %d" % (C, C_fit))
@@ -1003,7 +1043,7 @@ class UnsharedRegionFit(object):
 
     def _bt_dev(self, C, U):
         bt = self._data_dev("bt")
-        if tuple(bt.shape) != (C, U):
+        if bt.dim() not in (2, 3) or tuple(bt.shape[:2]) != (C, U):
             raise ValueError("bt has shape %s, the fit's state needs %s" % (tuple(bt.shape), (C, U)))
         return bt
 
@@ -1195,12 +1235,15 @@ def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=Non
     {p_T (C,U), p_F_tilde (C,U,3), p_changed (C,U)} as NumPy float64 through fcd_conn_posterior: weights from `counts`
     (C,U,3,3) uint32 (held in an int32 tensor), or from the log-probabilities lq_F (C,1,3) and lq_R (Nreg,U,2).
     missing_data: a NaN of bt is unobserved (fcd_conn_posterior_ex with FCD_DATA_NAN_MISSING).
+    bt_dev (C, U, K): K sessions per patient (fcd_conn_posterior_sessions); an item with no observed session gets the prior law.
     """
     import torch
     C = util.N_to_C(int(Nreg))
     dev = bt_dev.device
-    if tuple(bt_dev.shape) != (C, U) or bt_dev.dtype != torch.float64:
-        raise ValueError("bt must be float64 (C, U) = %s" % ((C, U),))
+    if bt_dev.dim() not in (2, 3) or tuple(bt_dev.shape[:2]) != (C, U) or bt_dev.dtype != torch.float64:
+        raise ValueError("bt must be float64 (C, U) = %s or (C, U, K)" % ((C, U),))
+    if bt_dev.dim() == 3 and int(bt_dev.shape[2]) < 1:
+        raise ValueError("bt (C, U, K) needs K >= 1 sessions")
     if counts is not None:
         if tuple(counts.shape) != (C, U, 3, 3) or counts.element_size() != 4:
             raise ValueError("counts must be 32-bit (C, U, 3, 3)")
@@ -1210,8 +1253,9 @@ def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=Non
     p_Ft = torch.empty((C, U, 3), dtype=torch.float64, device=dev)
     p_ch = torch.empty((C, U), dtype=torch.float64, device=dev)
     (th, _th) = _lib.dbl_array(theta)
-    ctx.call("fcd_conn_posterior_ex", _lib.dptr(bt_dev.contiguous()), int(Nreg), int(U), th,
-             _lib.dptr(None if counts is None else counts.contiguous()),
+    sessions = () if bt_dev.dim() == 2 else (int(bt_dev.shape[2]),)
+    ctx.call("fcd_conn_posterior_sessions" if sessions else "fcd_conn_posterior_ex", _lib.dptr(bt_dev.contiguous()), int(Nreg),
+             int(U), *sessions, th, _lib.dptr(None if counts is None else counts.contiguous()),
              _lib.dptr(None if lq_F is None else lq_F.contiguous()), _lib.dptr(None if lq_R is None else lq_R.contiguous()),
              _lib.FCD_DATA_NAN_MISSING if missing_data else 0, _lib.dptr(p_T), _lib.dptr(p_Ft), _lib.dptr(p_ch),
              _lib.stream_ptr())

@@ -140,12 +140,16 @@ class UnsharedRegionModel(_RegionModelParams):
         return b_tilde.clip(-1, 1)
 
     # ---- same distribution, vectorised, own stream: benchmark-sized inputs in milliseconds ----
-    def sample_fast(self, N, H, U, seed=0):
+    def sample_fast(self, N, H, U, seed=0, sessions=None):
         """
         (r, t, f, f_tilde, b, b_tilde) with the shapes of `sample`, drawn with numpy.random.Generator
         (PCG64).  Edge order is the FITTER's (lower-triangular, util.c_to_nm), so the output can be
         fitted as is (no quirk-Q3 re-indexing).
+        sessions = K: b_tilde is (C, U, K), K scans of every patient that share the patient's f_tilde (conditionally
+        independent Normal draws given it).  sessions = None: one scan, b_tilde (C, U), the same draws as ever.
         """
+        if sessions is not None and (int(sessions) != sessions or int(sessions) < 1):
+            raise ValueError("sessions must be None or an integer >= 1")
         g = np.random.default_rng(seed)
         C = util.N_to_C(N)
         il = np.tril_indices(N, -1)           # (n, m < n) row-major == util.c_to_nm order
@@ -165,7 +169,10 @@ class UnsharedRegionModel(_RegionModelParams):
         mu = np.asarray(self.mu, dtype=np.float64)
         sg = np.asarray(self.sigma, dtype=np.float64)
         b = (mu[fk][:, None] + sg[fk][:, None] * g.standard_normal((C, H))).clip(-1, 1)
-        b_tilde = (mu[ftk] + sg[ftk] * g.standard_normal((C, U))).clip(-1, 1)
+        if sessions is None:
+            b_tilde = (mu[ftk] + sg[ftk] * g.standard_normal((C, U))).clip(-1, 1)
+        else:
+            b_tilde = (mu[ftk][:, :, None] + sg[ftk][:, :, None] * g.standard_normal((C, U, int(sessions)))).clip(-1, 1)
         return (r, t, f, f_tilde, b, b_tilde)
 
     def sample_gpu(self, N, H, U, seed=0, ctx=None):

@@ -104,7 +104,8 @@ def gather_rows(t):
 
 
 def lik_tables(ctx, b_dev, bt_dev, theta, missing_data):
-    """(S_B (C, 3), lM (C, U', 3, 3)) of new patients into fresh tensors (the table kernel needs H >= 1: b is the fit's)."""
+    """(S_B (C, 3), lM (C, U', 3, 3)) of new patients bt_dev (C, U') or (C, U', K') into fresh tensors (the table kernel needs
+    H >= 1: b is the fit's)."""
     return tables.build(ctx, b_dev, bt_dev, theta, _lib.FCD_DATA_NAN_MISSING if missing_data else 0)
 
 

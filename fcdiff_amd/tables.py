@@ -14,6 +14,9 @@ def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB
     (S_B (C, 3), lM) of b_dev (C, H) and bt_dev (C, U) at theta, in ONE library call on `ctx`:
       shared=False  fcd_lik_tables_ex: lM (C, U, 3, 3) and, where given, the per-item tables lpB (C, H, 3), pBt (C, U, 3);
       shared=True   fcd_lik_shared_tables: lM is L (C, 1, 3, 3), the sum over patients (no per-item tables).
+    A 3-D bt_dev (C, U, K) -- K sessions of every patient, the session index fastest -- selects the sessions form of the same
+    call (fcd_lik_tables_sessions / fcd_lik_shared_tables_sessions): the same outputs, an item's density taken over its
+    sessions in log form.  pBt is refused there (ValueError): a product of densities underflows, and nothing consumes it.
     S_B and lM are written in place where given (a sampler built on them reads the new tables after refresh_tables()) and
     allocated where not.  flags: 0 or _lib.FCD_DATA_NAN_MISSING; with flags = 0 and n_missing = None the unshared call is
     the plain fcd_lik_tables, argument for argument.  n_missing: (2,) int64 device tensor the kernel adds the NaN counts of
@@ -21,13 +24,28 @@ def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB
     """
     import torch
     (C, H) = (int(b_dev.shape[0]), int(b_dev.shape[1]))
+    if bt_dev.dim() not in (2, 3):
+        raise ValueError("bt must be (C, U) or (C, U, K), got shape %s" % (tuple(bt_dev.shape),))
     U = int(bt_dev.shape[1])
+    K = int(bt_dev.shape[2]) if bt_dev.dim() == 3 else None
+    if K is not None and pBt is not None:
+        raise ValueError("p_Bt_g_Ft is not made for sessions data: a product of densities underflows")
+    if K is not None and K < 1:
+        raise ValueError("bt (C, U, K) needs K >= 1 sessions, got shape %s" % (tuple(bt_dev.shape),))
     if S_B is None:
         S_B = torch.empty((C, 3), dtype=torch.float64, device=bt_dev.device)
     if lM is None:
         lM = torch.empty((C, 1 if shared else U, 3, 3), dtype=torch.float64, device=bt_dev.device)
     (th, _th) = _lib.dbl_array(theta)
-    if shared:
+    if K is not None:
+        bt_dev = bt_dev.contiguous()
+        if shared:
+            ctx.call("fcd_lik_shared_tables_sessions", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, K, th, _lib.dptr(S_B),
+                     _lib.dptr(lM), int(flags), _lib.dptr(n_missing), _lib.stream_ptr())
+        else:
+            ctx.call("fcd_lik_tables_sessions", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, K, th, _lib.dptr(S_B),
+                     _lib.dptr(lM), _lib.dptr(lpB), int(flags), _lib.dptr(n_missing), _lib.stream_ptr())
+    elif shared:
         ctx.call("fcd_lik_shared_tables", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, th, _lib.dptr(S_B), _lib.dptr(lM),
                  int(flags), _lib.dptr(n_missing), _lib.stream_ptr())
     else:

@@ -201,6 +201,33 @@ int fcd_lik_shared_tables(fcd_ctx *ctx, const double *b, const double *bt, int64
                           const double *theta12_host, double *S_B, double *L, int flags, int64_t *nan_counts,
                           fcd_stream stream);
 
+/* ---- repeated sessions per patient: bt (C, U, K) -----------------------------------------------------------------
+ * bt holds K >= 1 scans of every patient, contiguous with the session as the fastest index: bt[(c*U + u)*K + k].  F~_cu is
+ * the patient's latent state of the connection and the sessions are conditionally independent measurements of it:
+ *   P_j(c,u)  = prod_k N(bt[c,u,k]; mu_j, sigma_j)                (a NaN session contributes 1 with FCD_DATA_NAN_MISSING)
+ *   M_kl(c,u) = e_l P_k + (1 - e_l)/2 sum_{j != k} P_j            (e_l = _eval_M_eps, as in fcd_lik_tables)
+ * computed in log form, a_j = sum_k ln N_j (ascending k), m = max_j a_j, lM = m + ln M_kl(exp(a - m)): finite where the
+ * product of the densities underflows.  An item with no observed session has lM = 0.0 exactly; a NaN session adds exactly
+ * 0.0, so it leaves the other sessions' table bit for bit; m = -inf gives -inf.  Without the flag a NaN session makes its
+ * item NaN.  Extra sessions of CONTROLS need nothing: they are extra columns of b.
+ *
+ * fcd_lik_tables_sessions: S_B (C,3) and lp_B_g_F (C,H,3; may be NULL) equal fcd_lik_tables_ex's bit for bit, lM (C,U,3,3)
+ * as above; n_missing2 as in fcd_lik_tables_ex, its second word counting NaN session entries of bt.  There is no
+ * p_Bt_g_Ft: the product of densities is what underflows.
+ * fcd_lik_shared_tables_sessions: S_B and L (C,3,3), L[c] = sum_u lM[c,u] in fcd_lik_shared_tables' fixed order.
+ * fcd_conn_posterior_sessions: fcd_conn_posterior_ex with the densities of an item taken over its sessions; an item with
+ * no observed session gets the prior law of T and F~ given (k, l).
+ * All three refuse K < 1 (FCD_ERR_ARG), K > INT32_MAX (FCD_ERR_UNSUPPORTED), unknown flags and what their siblings refuse. */
+int fcd_lik_tables_sessions(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U, int64_t K,
+                            const double *theta12_host, double *S_B, double *lM, double *lp_B_g_F, int flags,
+                            int64_t *n_missing2, fcd_stream stream);
+int fcd_lik_shared_tables_sessions(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                   int64_t K, const double *theta12_host, double *S_B, double *L, int flags,
+                                   int64_t *nan_counts, fcd_stream stream);
+int fcd_conn_posterior_sessions(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, int64_t K,
+                                const double *theta12_host, const uint32_t *counts, const double *lq_F, const double *lq_R,
+                                int flags, double *p_T, double *p_F_tilde, double *p_changed, fcd_stream stream);
+
 /* ---- forward sampler: UnsharedRegionModel.sample, fcdiff/model.py:52-236, on the device ---------------
  * Counter RNG (Philox), all variables drawn in parallel; the reference's MT19937 stream is not reproduced (the host
  * sampler of the Python mirror does that) -- same distribution.  Type INDICES are returned: r (Nreg,U), t (C,U),
