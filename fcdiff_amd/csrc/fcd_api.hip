@@ -47,6 +47,18 @@ int fcd_fsq_reserve(fcd_ctx *ctx, size_t bytes) {
     return FCD_OK;
 }
 
+int fcd_frec_reserve(fcd_ctx *ctx, size_t bytes) {
+    if (bytes <= ctx->frec_bytes) return FCD_OK;
+    FCD_HIP_TRY(hipDeviceSynchronize());
+    if (ctx->frec) FCD_HIP_TRY(hipFree(ctx->frec));
+    ctx->frec = nullptr;
+    ctx->frec_bytes = 0;
+    FCD_HIP_TRY(hipMalloc(&ctx->frec, bytes));
+    ctx->frec_bytes = bytes;
+    ctx->n_alloc += 1;
+    return FCD_OK;
+}
+
 // "0", "" and unset mean "default"; anything else is the number
 static double knob_env(const char *name) {
     const char *e = getenv(name);
@@ -135,6 +147,8 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->dev_err = nullptr;
     ctx->fsq = nullptr;
     ctx->fsq_bytes = 0;
+    ctx->frec = nullptr;
+    ctx->frec_bytes = 0;
     for (int k = 0; k < FCD_ACC_N; ++k) ctx->sweep_acc[k] = fcd_sweep_acc{{nullptr, nullptr}, 0, 0, 1};
     ctx->count_ws = nullptr;
     ctx->count_ws_bytes = 0;
@@ -171,9 +185,11 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->knobs.corr_form = (int)knob_env("FCD_CORR_FORM");
     ctx->knobs.r_poll_limit = 0;        // test hooks: through fcd_ctx_set_knob only, never from the environment
     ctx->knobs.r_withhold = 0;
+    ctx->knobs.f_records = 0;           // (A/B runs and tests only)
     ctx->r_form_last = 0;
     ctx->n_pack = 0;
     ctx->n_pack_tally = 0;
+    ctx->n_frec_pass = ctx->n_frec_build = 0;
     int rc = fcd_ws_reserve(ctx, 1u << 20);
     if (rc == FCD_OK) {
         void *pin = nullptr;
@@ -222,6 +238,7 @@ int fcd_ctx_destroy(fcd_ctx *ctx) {
     if (ctx->log_tab) (void)hipFree(ctx->log_tab);
     if (ctx->dev_err) (void)hipHostFree((void *)ctx->dev_err);
     if (ctx->fsq) (void)hipFree(ctx->fsq);
+    if (ctx->frec) (void)hipFree(ctx->frec);
     if (ctx->count_ws) (void)hipFree(ctx->count_ws);
     if (ctx->acc) (void)hipFree(ctx->acc);
     if (ctx->nan_slots) (void)hipFree(ctx->nan_slots);
@@ -245,7 +262,14 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G) {
     if (pl.ws_bytes > need) need = pl.ws_bytes;
     int rc = fcd_ws_reserve(ctx, need);
     if (rc) return rc;
-    return pl.fsq_bytes ? fcd_fsq_reserve(ctx, pl.fsq_bytes) : FCD_OK;
+    if (pl.fsq_bytes) {
+        rc = fcd_fsq_reserve(ctx, pl.fsq_bytes);
+        if (rc) return rc;
+    }
+    // the f pass's record table: a sweep loop that finds none runs the kernel that builds its records per tile, so a
+    // device without room for it is no error
+    if (pl.frec_bytes && ctx->knobs.f_records != 1 && fcd_frec_reserve(ctx, pl.frec_bytes) != FCD_OK) (void)hipGetLastError();
+    return FCD_OK;
 }
 
 int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value) {
@@ -262,6 +286,7 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value) {
     else if (!strcmp(name, "f_tol")) k.f_tol = value;
     else if (!strcmp(name, "f_form")) k.f_form = (int)value;
     else if (!strcmp(name, "f_pack")) k.f_pack = (int)value;
+    else if (!strcmp(name, "f_records")) k.f_records = (int)value;
     else if (!strcmp(name, "corr_form")) k.corr_form = (int)value;
     else if (!strcmp(name, "r_poll_limit")) k.r_poll_limit = (int)value;
     else if (!strcmp(name, "r_withhold")) k.r_withhold = (int)value;
@@ -295,6 +320,10 @@ int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out) {
     else if (!strcmp(name, "r_form_last")) *out = ctx->r_form_last;
     else if (!strcmp(name, "pack_launches")) *out = ctx->n_pack;
     else if (!strcmp(name, "tally_f_in_pack")) *out = ctx->n_pack_tally;
+    else if (!strcmp(name, "f_rec_passes")) *out = ctx->n_frec_pass;
+    else if (!strcmp(name, "f_rec_builds")) *out = ctx->n_frec_build;
+    else if (!strcmp(name, "f_rec_bytes")) *out = (int64_t)ctx->frec_bytes;
+    else if (!strcmp(name, "f_rec_min_sweeps")) *out = F_REC_MIN_SWEEPS;
     else if (!strcmp(name, "pipe_grid")) *out = ctx->pipe_grid;
     else if (!strcmp(name, "pipe_capacity")) *out = ctx->pipe_capacity;
     else if (!strcmp(name, "comm_world")) *out = ctx->comm ? ctx->comm_world : 0;

@@ -34,11 +34,14 @@ struct fcd_knobs {
     int corr_form;     // 1: K_corr in 64 x 64 blocks with a moments pass also where the one-workgroup-per-subject kernel would run
     int f_form;        // 0: automatic; 2: the any-U pair kernel also where the U <= 64 one would run; 3: scalar-mask form
     int f_pack;        // 1: the r pass's packing launch in every sweep (default: only where the f pass cannot write the packed f words)
+    int f_records;     // pair-tile f pass reads pair records made once per call: 0 = in calls of at least F_REC_MIN_SWEEPS pair-tile
+                       // sweeps, 1 = never (every tile builds its own), 2 = whenever the pair-tile form runs
 };
 
 // kernels whose dynamic-LDS limit is raised with hipFuncSetAttribute: done once per (kernel, size) and remembered here
 enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA_F_PAIR_T = FCD_KA_F_PAIR + 4,
-       FCD_KA_F_PAIR_BIG = FCD_KA_F_PAIR_T + 4, FCD_KA_R_STEP = FCD_KA_F_PAIR_BIG + 4, FCD_KA_R_PIPE = FCD_KA_R_STEP + 4, FCD_KA_CORR = FCD_KA_R_PIPE + 4, FCD_KA_N = FCD_KA_CORR + 1 };
+       FCD_KA_F_PAIR_R = FCD_KA_F_PAIR_T + 4,
+       FCD_KA_F_PAIR_BIG = FCD_KA_F_PAIR_R + 4, FCD_KA_R_STEP = FCD_KA_F_PAIR_BIG + 4, FCD_KA_R_PIPE = FCD_KA_R_STEP + 4, FCD_KA_CORR = FCD_KA_R_PIPE + 4, FCD_KA_N = FCD_KA_CORR + 1 };
 
 #define FCD_NAN_SLOTS 256
 
@@ -68,6 +71,8 @@ struct fcd_ctx {
     int r_form_last;               // form of the last blocked r pass: 1 step-per-launch, 2 pipelined, 3 one-launch with counters (fcd_ctx_stat)
     long long n_pack;              // packing launches of the r pass so far (fcd_ctx_stat "pack_launches")
     long long n_pack_tally;        // ... of them that carried the f half of the tally (fcd_ctx_stat "tally_f_in_pack")
+    long long n_frec_pass;         // f passes that read prebuilt pair records (fcd_ctx_stat "f_rec_passes")
+    long long n_frec_build;        // launches of the kernel that builds them (fcd_ctx_stat "f_rec_builds")
     void *log_tab;     // K_lik tables (fcd_fastmath.h): 64 x 2^(-j/64), 512 x {1/m_i, log m_i} (device, 8.5 KiB)
     volatile unsigned *dev_err;   // pinned host word: error word of the one-launch r pass, copied back after each pass
     void *acc;         // 8 x uint64, zero between launches: the tally's pooled sums [0..3] and its ticket [4]
@@ -82,6 +87,8 @@ struct fcd_ctx {
     size_t corr_tickets_n;
     void *fsq;         // square copy of the f state [w][n][m][lane] the sweep loop keeps between its f and r pass
     size_t fsq_bytes;
+    void *frec;        // pair records and edge constants of the pair-tile f pass (fcd_sweep_plan::frec_bytes), valid inside ONE
+    size_t frec_bytes; // sweep-loop call: it makes them from that call's lMf before the first pass that reads them
     fcd_sweep_acc sweep_acc[FCD_ACC_N];
     void *count_ws;                // per-chain counts of one tally, (U + Nreg) rows of GW*64 uint16 (fcd_count_ws_reserve)
     size_t count_ws_bytes;
@@ -148,6 +155,8 @@ int fcd_comm_allreduce_counts(fcd_ctx *ctx, long long *counts, hipStream_t strea
 int fcd_ws_reserve(fcd_ctx *ctx, size_t bytes);
 // square copy of the f state (see fcd_sweep_plan): grown like the workspace
 int fcd_fsq_reserve(fcd_ctx *ctx, size_t bytes);
+// prebuilt pair records of the f pass: grown like the square copy
+int fcd_frec_reserve(fcd_ctx *ctx, size_t bytes);
 // raise a kernel's dynamic-LDS limit if this size was not set before (no HIP call otherwise)
 static inline int fcd_lds_attr(fcd_ctx *ctx, int slot, const void *fn, size_t shmem) {
     if (shmem <= 64 * 1024 || shmem <= ctx->lds_attr[slot]) return FCD_OK;
@@ -525,6 +534,25 @@ static inline int fcd_geo_check(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G
 // ---------------------------------------------------------------------------------------------
 enum { FCD_F_GENERIC = 0, FCD_F_PAIR = 1, FCD_F_PAIRX = 2, FCD_F_DIFF = 3 };   // f pass forms (knob f_form: 2, 3)
 constexpr int FP_EC = 8;     // edges per tile of the U <= 64 pair kernel
+constexpr int FT_W = FP_EC / 2;      // ... columns of a pair-aligned tile (two rows of the triangle)
+__host__ __device__ static inline int64_t fpt_tiles(int64_t i) {       // pair-aligned tiles of the row pairs before i
+    const int64_t j = i >> 1;
+    return (i & 1) ? (j + 1) * (j + 1) : j * (j + 1);
+}
+// Pair records made once per call (fcd_gibbs.hip, gibbs_f_records_kernel): per pair-aligned tile NPAIR x FP_EC records of
+// six 16-byte pieces (the eight of the LDS record without slots 10-11 and 14-15, which no slot word can name), then one
+// fcd_f_edge_rec per edge id.
+constexpr int F_REC_PIECES = 6;
+struct fcd_f_edge_rec {
+    double d1, d2;     // S_B[c][1] - S_B[c][0], S_B[c][2] - S_B[c][0]
+    float a;           // bound of the sum over the patients of the largest |entry| of the row (the tile's B_e)
+    float pad[3];
+};
+constexpr size_t F_REC_CAP = (size_t)256 << 20;     // no record table above this many bytes: the tiles build their own
+// A call of the sweep loop makes the records where it has at least this many pair-tile sweeps: the build launch costs 27.4 us
+// at cfg3 and a pair-tile f pass on its records runs 6.75 us shorter (108.96 -> 102.20 us; kernel trace of the timed loop,
+// profiles/f_records_per_call_cfg3.txt), so it is paid back after ceil(27.4 / 6.75) = 5 sweeps -- doubled.
+constexpr int F_REC_MIN_SWEEPS = 10;
 struct fcd_sweep_plan {
     int f_form, f_EC;           // f pass given lMf: form, edges per LDS tile
     size_t f_shmem;
@@ -535,6 +563,9 @@ struct fcd_sweep_plan {
     // square copy of the f state (fcd_ctx::fsq, (GW,Nreg,Nreg,64) u8) a pair-form f pass writes and the r pass packs
     // from (contiguous rows instead of 64-byte pieces); 0: none
     size_t fsq_bytes;
+    // prebuilt pair records of the pair-tile f pass (fcd_ctx::frec): tiles | edge constants at frec_edge; 0: none (another
+    // form, no blocked r pass, or above F_REC_CAP).  f_shmem_rec: the LDS of the kernel that reads them (no fp64 rows)
+    size_t frec_bytes, frec_edge, f_shmem_rec;
     // workspace byte offsets: P[0] | P[1] | f_S | r_S | r_Sn | marks of the blocked r pass, then at a 512-byte boundary the
     // slot words r_U of a pair-form f pass (behind the r scratch: the sentinels in P survive from sweep to sweep) | ws_bytes
     size_t P[2], f_S, r_S, r_Sn, marks, r_U, ws_bytes;
@@ -560,6 +591,7 @@ struct fcd_sweep_step {
     bool f_packed;                 // f pass: write the r pass's f words (f_S) in their final form (pair tiles), no square copy
     bool r_packed;                 // r pass: the previous sweep's tally has written r_S and cleared the marks
     bool ru_ready;                 // f pass: the previous sweep's tally has made the slot words
+    const void *f_rec;             // f pass (f_packed): pair records made for this call, or nullptr (the tiles build their own)
     bool sentinels_in_place;       // r pass: P holds the sentinels a COMPLETED pipelined pass of this shape left behind
     const fcd_tally_f *tally_f;    // r pass: the f half of the tally to carry in the packing launch, or nullptr ...
     bool tally_f_done;             // ... and whether it did (out)

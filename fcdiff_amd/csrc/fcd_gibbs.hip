@@ -270,6 +270,37 @@ __global__ __launch_bounds__(256) void pack_ru_kernel(const uint64_t *__restrict
 
 typedef float fcd_f2v __attribute__((ext_vector_type(2)));           // one ds_read_b64, one v_pk_add_f32
 typedef __attribute__((address_space(3))) const fcd_f2v lds_cf2v;
+typedef float fcd_f4v __attribute__((ext_vector_type(4)));
+
+// 16-byte piece s2 of the record of a pair of patients (slots 2 s2, 2 s2 + 1 of its 16: bit 0 / 1 = x of patient u / u + 1,
+// bit 2 / 3 = a): the sums of the two patients' rows A, B (the three mixture cases: 0 typical, 1 both, 2 discordant) in
+// fp64, rounded once to fp32; zeros for the seven impossible slots (x and a both set for a patient).
+__device__ __forceinline__ fcd_f4v fp_pair_piece(const double2 (&A)[3], const double2 (&B)[3], int s2) {
+    fcd_f4v o;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int slot = 2 * s2 + h;
+        const int x0 = slot & 1, x1 = (slot >> 1) & 1, a0 = (slot >> 2) & 1, a1 = slot >> 3;
+        const bool valid = !((x0 & a0) | (x1 & a1));
+        const int l0 = a0 ? 1 : (x0 ? 2 : 0), l1 = a1 ? 1 : (x1 ? 2 : 0);
+        const float vx = valid ? (float)(A[l0].x + B[l1].x) : 0.f, vy = valid ? (float)(A[l0].y + B[l1].y) : 0.f;
+        if (h == 0) { o.x = vx; o.y = vy; } else { o.z = vx; o.w = vy; }
+    }
+    return o;
+}
+// B_e >= sum over the pairs of max |record entry|: the sum over the patients of the largest |value| of the row (the whole
+// wave; lane = patient, su = its row, live = lane < U <= 64) -- what bounds the error of the fp32 sums of the term loop
+__device__ __forceinline__ float fp_edge_bound(const double2 *su, bool live) {
+    float a = 0.f;
+    if (live) {
+#pragma unroll
+        for (int l = 0; l < 3; ++l) a = fmaxf(a, fmaxf((float)fabs(su[l].x), (float)fabs(su[l].y)));
+        a *= 1.0000002f;                              // (the conversions of the records round to nearest)
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    return a;
+}
 
 // The exact path of the pair forms: the two log-odds sums of edge c for this lane's chain in fp64, straight from the
 // table (48 contiguous bytes per patient: L2), in the order of the fp64 pair records of rounds 2-3 (record = row u + row
@@ -320,11 +351,7 @@ __device__ __attribute__((noinline)) int fcd_f_exact_edge(const double *__restri
 // regions of every pair (m, m+1) of its rows and of every pair (n0, n0+1) of its columns: it writes the r pass's f words
 // (f_S, pack_f_item) in their final form -- the row half into f_S[w][n][b(m)], the column half into f_S[w][m][b(n0)] --
 // instead of the square copy the packing launch would read back.
-constexpr int FT_W = FP_EC / 2;
-__host__ __device__ static inline int64_t fpt_tiles(int64_t i) {       // tiles of the row pairs before i
-    const int64_t j = i >> 1;
-    return (i & 1) ? (j + 1) * (j + 1) : j * (j + 1);
-}
+// (FT_W, fpt_tiles: fcd_common.h)
 struct fpt_tile {
     int n0, mb;
     int cnt0, cnt1;          // edges of row n0 / n0 + 1 in the tile (m < n, row inside the triangle)
@@ -346,13 +373,18 @@ __device__ __forceinline__ fpt_tile fpt_locate(int t, int Nreg) {
     return T;
 }
 
-template <int NW16, bool PT>
+// PRE (pair-aligned tiles only): the records and the edges' bounds come from the table gibbs_f_records_kernel made for this call
+// (frec: per tile NPAIR x FP_EC records of F_REC_PIECES 16-byte pieces, then one fcd_f_edge_rec per edge id) -- one copy
+// into LDS and ONE barrier instead of staging, barrier, build, barrier; no fp64 rows in LDS.
+template <int NW16, bool PT, bool PRE = false>
 __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__restrict__ S_B, const double *__restrict__ lMf,
                                                             const double *__restrict__ hyper, uint8_t *__restrict__ f_state,
                                                             const uint32_t *__restrict__ r_U, int Nreg, int U, int64_t C,
                                                             int GW, uint32_t chain0, uint64_t seed, uint32_t sweep, float margin, uint8_t *__restrict__ fsq,
-                                                            uint2 *__restrict__ f_S, int NBLK, unsigned long long *__restrict__ dbg) {
-    // pair records [NPAIR][FP_EC][16] float2 | per-edge constants [FP_EC] float4 | singles [FP_EC][U][3][2] double
+                                                            uint2 *__restrict__ f_S, int NBLK, unsigned long long *__restrict__ dbg,
+                                                            const char *__restrict__ frec) {
+    static_assert(PT || !PRE, "prebuilt records are laid out by pair-aligned tile");
+    // pair records [NPAIR][FP_EC][16] float2 | per-edge constants [FP_EC] float4 | (not PRE) singles [FP_EC][U][3][2] double
     extern __shared__ __attribute__((aligned(256))) double ptile[];
     const int NPAIR = (U + 1) >> 1;
     // the tile's edges: c0 + e, e < ne (consecutive ids); PT: edge e = (row e / FT_W, column e % FT_W), present where
@@ -402,8 +434,33 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
     // (profiles/r04_trace_f.txt: built 3.8 us of a 17 us tile)
     const int wv0 = (int)(threadIdx.x >> 6);
     double sbv = 0.0;
-    if (wv0 < ne && has(wv0) && lane < 3) sbv = S_B[cid(wv0) * 3 + lane];
-    if (!PT) {
+    if (!PRE && wv0 < ne && has(wv0) && lane < 3) sbv = S_B[cid(wv0) * 3 + lane];
+    if (PRE) {
+        // this wave's edge constants first, then the tile's records: one contiguous piece of the table, coalesced 16-byte
+        // copies (two loads per thread in flight); a record's six pieces go to pieces 0-4 and 6 of its 128 bytes in LDS
+        const fcd_f_edge_rec *edge_c = reinterpret_cast<const fcd_f_edge_rec *>(frec + (size_t)gridDim.x * NPAIR * (FP_EC * F_REC_PIECES * 16));
+        const bool mine = wv0 < FP_EC && has(wv0) && lane == 0;
+        fcd_f_edge_rec ek0 = {};
+        if (mine) ek0 = edge_c[cid(wv0)];
+        const fcd_f4v *src = reinterpret_cast<const fcd_f4v *>(frec) + (size_t)blockIdx.x * NPAIR * (FP_EC * F_REC_PIECES);
+        fcd_f4v *dst4 = reinterpret_cast<fcd_f4v *>(ptile);
+        const int n16 = NPAIR * (FP_EC * F_REC_PIECES);
+        auto at = [](int i) -> int { const int r = i / F_REC_PIECES, k = i - r * F_REC_PIECES; return r * 8 + (k < 5 ? k : 6); };
+        for (int i0 = threadIdx.x; i0 < n16; i0 += 2 * blockDim.x) {
+            const int i1 = i0 + (int)blockDim.x;
+            const fcd_f4v v0 = src[i0], v1 = src[i1 < n16 ? i1 : i0];
+            dst4[at(i0)] = v0;
+            if (i1 < n16) dst4[at(i1)] = v1;
+        }
+        // hyper changes from sweep to sweep: the offsets and eta are made here, from the call's constants
+        for (int ee = wv0; ee < FP_EC; ee += (int)(blockDim.x >> 6)) {
+            if (!has(ee) || lane != 0) continue;
+            const fcd_f_edge_rec k = ee == wv0 ? ek0 : edge_c[cid(ee)];
+            const double c1 = lg1 + k.d1, c2 = lg2 + k.d2;
+            const float cm = fmaxf((float)fabs(c1), (float)fabs(c2)) * 1.0000002f;
+            edge_k[ee] = make_float4((float)c1, (float)c2, fcd_draw_f_eta(fcd_f32_sum_err(NPAIR, k.a) + fcd_f32_offset_err(cm, k.a)), 0.f);
+        }
+    } else if (!PT) {
         // the tile's rows of lMf are one contiguous piece: coalesced 16-byte copies
         const int n_d2 = ne * U * 3;
         const double2 *src = reinterpret_cast<const double2 *>(lMf + c0 * U * 6);
@@ -429,13 +486,12 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
     }
     __syncthreads();
     FCD_TRACE(trec, 1);
-    {
+    if (!PRE) {
         // pair records from the single rows in LDS, ONE THREAD PER (edge, pair): six 16-byte reads (the three mixture cases of
         // patient u and of patient u+1), the nine valid sums, rounded once to fp32, eight 16-byte writes (two slots each; the
         // seven impossible slots -- x and a both set for a patient -- as zeros).  Round 3's build gave every (pair, slot) entry a
         // thread of its own: 16 x the index arithmetic and 7/16 of the threads making zeros -- 3.7 us of a 17 us tile
         // (profiles/r04_trace_f.txt).
-        typedef float fcd_f4v __attribute__((ext_vector_type(4)));
         fcd_f4v *dst4 = reinterpret_cast<fcd_f4v *>(ptile);
         const int total = ne * NPAIR;
         // (the records are made by the UPPER half of the workgroup's waves: the lower ones make the edges' bounds below)
@@ -453,33 +509,12 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
                 B[l] = (u + 1 < U) ? su[3 + l] : make_double2(0.0, 0.0);
             }
 #pragma unroll
-            for (int s2 = 0; s2 < 8; ++s2) {
-                fcd_f4v o;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int slot = 2 * s2 + h;
-                    const int x0 = slot & 1, x1 = (slot >> 1) & 1, a0 = (slot >> 2) & 1, a1 = slot >> 3;
-                    const bool valid = !((x0 & a0) | (x1 & a1));
-                    const int l0 = a0 ? 1 : (x0 ? 2 : 0), l1 = a1 ? 1 : (x1 ? 2 : 0);          // 0 typical, 1 both, 2 discordant
-                    const float vx = valid ? (float)(A[l0].x + B[l1].x) : 0.f, vy = valid ? (float)(A[l0].y + B[l1].y) : 0.f;
-                    if (h == 0) { o.x = vx; o.y = vy; } else { o.z = vx; o.w = vy; }
-                }
-                dst4[(pr * FP_EC + e) * 8 + s2] = o;       // [pair][edge][slot]: see the reads below
-            }
+            for (int s2 = 0; s2 < 8; ++s2) dst4[(pr * FP_EC + e) * 8 + s2] = fp_pair_piece(A, B, s2);       // [pair][edge][slot]: see the reads below
         }
-        // B_e >= sum over the pairs of max |record entry|: the sum over the patients of the largest |value| of the row
-        // (wave e does edge e, lane = patient; U <= 64) -- what bounds the error of the fp32 sums below
+        // the edges' bounds B_e (wave e does edge e, lane = patient; U <= 64)
         for (int ee = (int)(threadIdx.x >> 6); ee < ne; ee += (int)(blockDim.x >> 6)) {      // (a workgroup may have fewer waves than edges)
             if (PT && !has(ee)) continue;
-            float a = 0.f;
-            if (lane < U) {
-                const double2 *su = single + (ee * U + lane) * 3;
-#pragma unroll
-                for (int l = 0; l < 3; ++l) a = fmaxf(a, fmaxf((float)fabs(su[l].x), (float)fabs(su[l].y)));
-                a *= 1.0000002f;                              // (the conversions above round to nearest)
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+            const float a = fp_edge_bound(single + (ee * U + (lane < U ? lane : 0)) * 3, lane < U);
             if (lane == 0) {
                 // the edge's constants as the draw wants them: the two log-odds offsets in fp32 and the relative uncertainty
                 // of the weights that the error bound of the whole fp32 sum (NPAIR records, then the offset) amounts to
@@ -500,8 +535,8 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
                 edge_k[ee] = make_float4((float)c1, (float)c2, fcd_draw_f_eta(fcd_f32_sum_err(NPAIR, a) + fcd_f32_offset_err(cm, a)), 0.f);
             }
         }
+        __syncthreads();
     }
-    __syncthreads();
     FCD_TRACE(trec, 2);
     if (w >= GW) return;
     if (FCD_ABL(0, 3)) return;           // ablation: staging only
@@ -693,6 +728,47 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
     FCD_TRACE_VAL(trec, 6, tr_rest);
 #endif
     FCD_TRACE(trec, 3);
+}
+
+// What the build phase of a pair-aligned tile makes depends on lMf and S_B alone, and neither can change inside one call of
+// the sweep loop: this kernel makes it for every tile of the call at once -- workgroup = tile, the same sums, the same bound
+// (wave e = edge e, lane = patient, fp_edge_bound) -- and gibbs_f_pair_kernel<.., true, true> copies it.  Layout: see PRE.
+// Pieces of edges the tile does not hold (past the diagonal) are never written and never read.
+__global__ __launch_bounds__(64 * FP_EC) void gibbs_f_records_kernel(const double *__restrict__ S_B, const double *__restrict__ lMf,
+                                                                     int Nreg, int U, char *__restrict__ frec) {
+    const int NPAIR = (U + 1) >> 1;
+    const fpt_tile T = fpt_locate((int)blockIdx.x, Nreg);
+    auto has = [&](int e) -> bool { return (e % FT_W) < (e < FT_W ? T.cnt0 : T.cnt1); };
+    auto cid = [&](int e) -> int64_t { return (e < FT_W ? T.cr0 : T.cr1) + (e % FT_W); };
+    fcd_f4v *dst4 = reinterpret_cast<fcd_f4v *>(frec) + (size_t)blockIdx.x * NPAIR * (FP_EC * F_REC_PIECES);
+    // one thread per (edge, pair), the pairs of an edge side by side: its two patients' rows are 96 contiguous bytes
+    for (int ep = threadIdx.x; ep < FP_EC * NPAIR; ep += blockDim.x) {
+        const int e = ep / NPAIR, pr = ep - e * NPAIR;
+        if (!has(e)) continue;
+        const int u = 2 * pr;
+        const double2 *su = reinterpret_cast<const double2 *>(lMf + cid(e) * U * 6) + u * 3;
+        double2 A[3], B[3];
+#pragma unroll
+        for (int l = 0; l < 3; ++l) {
+            A[l] = su[l];
+            B[l] = (u + 1 < U) ? su[3 + l] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int s2 = 0; s2 < 8; ++s2)
+            if (s2 != 5 && s2 != 7) dst4[(pr * FP_EC + e) * F_REC_PIECES + (s2 < 5 ? s2 : 5)] = fp_pair_piece(A, B, s2);
+    }
+    const int e = (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (!has(e)) return;         // (wave-uniform)
+    const int64_t c = cid(e);
+    const float a = fp_edge_bound(reinterpret_cast<const double2 *>(lMf + c * U * 6) + (lane < U ? lane : 0) * 3, lane < U);
+    if (lane == 0) {
+        fcd_f_edge_rec k = {};
+        const double sb0 = S_B[c * 3 + 0];
+        k.d1 = S_B[c * 3 + 1] - sb0;
+        k.d2 = S_B[c * 3 + 2] - sb0;
+        k.a = a;
+        reinterpret_cast<fcd_f_edge_rec *>(frec + (size_t)gridDim.x * NPAIR * (FP_EC * F_REC_PIECES * 16))[c] = k;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1284,6 +1360,9 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step
         dim3 grid((unsigned)((g.C + pl.f_EC - 1) / pl.f_EC), (unsigned)((g.GW + wpb - 1) / wpb));
         // pair-aligned tiles that write the r pass's f words themselves (fcd_sweep_step::f_packed; U <= 64 kernel only)
         const bool pt = st.f_packed && form == FCD_F_PAIR;
+        if (st.f_rec && (!pt || !pl.frec_bytes || ctx->frec_bytes < pl.frec_bytes))
+            return fcd_fail(ctx, FCD_ERR_ARG, "f pass: prebuilt records asked for where the plan has none");
+        const size_t f_shmem = st.f_rec ? pl.f_shmem_rec : pl.f_shmem;
         if (st.f_packed && (form != FCD_F_PAIR || !pl.r_blocked || st.fsq))
             return fcd_fail(ctx, FCD_ERR_ARG, "f pass: packed f words asked for where the plan has none");
         uint2 *f_S = pt ? (uint2 *)((char *)ctx->ws + pl.f_S) : nullptr;
@@ -1292,7 +1371,7 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step
 #define FCD_F_ARGS c.S_B, c.lMf, c.hyper, c.f_state, r_U, (int)Nreg, (int)U, g.C, g.GW, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, margin, st.fsq
 #define FCD_LAUNCH_F(KERN, SLOT, EXTRA)                                                                            \
     do {                                                                                                      \
-        rc = fcd_lds_attr(ctx, SLOT, reinterpret_cast<const void *>(&KERN), pl.f_shmem);                      \
+        rc = fcd_lds_attr(ctx, SLOT, reinterpret_cast<const void *>(&KERN), f_shmem);                         \
         if (rc) return rc;                                                                                    \
         {                                                                                                     \
             static int lds0 = 0; /* (the pair form's record addresses start at LDS address 0) */              \
@@ -1300,12 +1379,18 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step
             if (rc) return rc;                                                                                \
         }                                                                                                     \
         fcd_prof_begin(ctx, FCD_PROF_F, s);                                                                   \
-        hipLaunchKernelGGL(KERN, grid, dim3(64 * wpb), pl.f_shmem, s, FCD_F_ARGS, EXTRA);                     \
+        hipLaunchKernelGGL(KERN, grid, dim3(64 * wpb), f_shmem, s, FCD_F_ARGS, EXTRA);                        \
         fcd_prof_end(ctx, FCD_PROF_F, s);                                                                     \
     } while (0)
 #define FCD_PX (unsigned long long *)ctx->dbg
-#define FCD_PT f_S, NBLK, (unsigned long long *)ctx->dbg
-        if (form == FCD_F_PAIR && pt) {
+#define FCD_PT f_S, NBLK, (unsigned long long *)ctx->dbg, (const char *)st.f_rec
+        if (form == FCD_F_PAIR && pt && st.f_rec) {
+            if (pl.f_NW == 1) FCD_LAUNCH_F((gibbs_f_pair_kernel<1, true, true>), FCD_KA_F_PAIR_R + 0, FCD_PT);
+            else if (pl.f_NW == 2) FCD_LAUNCH_F((gibbs_f_pair_kernel<2, true, true>), FCD_KA_F_PAIR_R + 1, FCD_PT);
+            else if (pl.f_NW == 3) FCD_LAUNCH_F((gibbs_f_pair_kernel<3, true, true>), FCD_KA_F_PAIR_R + 2, FCD_PT);
+            else FCD_LAUNCH_F((gibbs_f_pair_kernel<4, true, true>), FCD_KA_F_PAIR_R + 3, FCD_PT);
+            ctx->n_frec_pass += 1;
+        } else if (form == FCD_F_PAIR && pt) {
             if (pl.f_NW == 1) FCD_LAUNCH_F((gibbs_f_pair_kernel<1, true>), FCD_KA_F_PAIR_T + 0, FCD_PT);
             else if (pl.f_NW == 2) FCD_LAUNCH_F((gibbs_f_pair_kernel<2, true>), FCD_KA_F_PAIR_T + 1, FCD_PT);
             else if (pl.f_NW == 3) FCD_LAUNCH_F((gibbs_f_pair_kernel<3, true>), FCD_KA_F_PAIR_T + 2, FCD_PT);
@@ -1472,10 +1557,26 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         int rc = fcd_ws_reserve(ctx, pl.ws_bytes);      // the tally writes the next pass's slot words there
         if (rc) return rc;
     }
+    // Every sweep after the first runs the pair-tile f pass where packed_ok.  A call with enough of them makes the tiles'
+    // records once, before the first: the table is good for THIS call's lMf and S_B only, and no later call reads it.
+    // Without the buffer (above F_REC_CAP, or no room on the device) the tiles build their own records as before.
+    const int64_t pt_sweeps = packed_ok ? n_sweeps - 1 : 0;
+    bool use_rec = pl.frec_bytes && ctx->knobs.f_records != 1 && pt_sweeps >= (ctx->knobs.f_records == 2 ? 1 : F_REC_MIN_SWEEPS);
+    if (use_rec && fcd_frec_reserve(ctx, pl.frec_bytes) != FCD_OK) {
+        (void)hipGetLastError();
+        use_rec = false;
+    }
     for (int64_t i = 0; i < n_sweeps; ++i) {
         st.sweep = sweep0 + i;
         st.f_packed = packed_ok && st.r_packed;
         st.fsq = st.f_packed ? nullptr : fsq;
+        if (use_rec && st.f_packed && !st.f_rec) {
+            hipLaunchKernelGGL(gibbs_f_records_kernel, dim3((unsigned)fpt_tiles((Nreg + 1) / 2)), dim3(64 * FP_EC), 0, s, c.S_B, c.lMf,
+                               (int)Nreg, (int)U, (char *)ctx->frec);
+            FCD_LAUNCH_CHECK();
+            ctx->n_frec_build += 1;
+            st.f_rec = ctx->frec;
+        }
         int rc = fcd_gibbs_f_pass(ctx, c, st);
         if (rc) return rc;
         const bool last = i + 1 == n_sweeps;

@@ -111,6 +111,12 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
  *   "f_form"    2: the any-U pair kernel of the f pass also where the U <= 64 kernel would run; 3: scalar-mask form
  *   "f_pack"    1: the r pass's packing launch in every sweep (default: from the second sweep of a fcd_gibbs_run call on,
  *               the U <= 64 f pass writes the r pass's packed f words itself and the tally the r words of the next pass)
+ *   "f_records" the pair-tile f pass (U <= 64, every sweep of a fcd_gibbs_run / fcd_gibbs_sweeps call but the first) reads
+ *               pair records and edge bounds that one launch makes for the whole call, instead of building them in every
+ *               tile: 0 = in calls with at least F_REC_MIN_SWEEPS such sweeps (stat "f_rec_min_sweeps"), 1 = never, 2 = in
+ *               every call that has one (A/B runs and tests; not read from the environment).  The table (stat
+ *               "f_rec_bytes") belongs to the context, fcd_ctx_reserve sizes it; above 256 MB, or where the device has no
+ *               room for it, the tiles build their own records
  *   "r_poll_limit", "r_withhold"  TEST HOOKS of the pipelined r pass: bound every device-side poll by this many polls /
  *               the in-order role never announces a block (a panel wave then gives its wait up, fcd_ctx_check reports it)
  *   "r_coop" = 2  TEST HOOK: every pipelined launch of the r pass acts as if the runtime had refused a cooperative launch
@@ -122,7 +128,9 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value);
 /* Counters of the context: "n_alloc" device allocations made so far, "ws_bytes", "fsq_bytes"; "r_form_last" = the form
  * the last blocked r pass ran in (1 one launch per block step, 2 pipelined one-launch form, 3 one-launch form with
  * counters); "pack_launches" = packing launches of the r pass made so far; "tally_f_in_pack" = those of them that also
- * carried the f half of the sweep's tally; "dev_err" = the error word of the pipelined r pass as the host sees it now (see
+ * carried the f half of the sweep's tally; "f_rec_passes" = f passes that read prebuilt pair records, "f_rec_builds" =
+ * launches of the kernel that makes them, "f_rec_bytes" = the size of their table, "f_rec_min_sweeps" = the threshold of
+ * knob f_records = 0; "dev_err" = the error word of the pipelined r pass as the host sees it now (see
  * fcd_ctx_check); "pipe_grid" / "pipe_capacity" = the grid of the last pipelined attempt of the r pass (its empty
  * workgroups included) and the workgroups the occupancy query says are resident at once for it (the form is taken where
  * pipe_grid + 8 <= pipe_capacity). */
