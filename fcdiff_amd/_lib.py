@@ -101,6 +101,9 @@ SIGNATURES = {
     "fcd_gibbs_count_tally": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "fcd_gibbs_set_count_accumulator": (_int, [_p, _p, _p, _i64, _i64, _i64]),
     "fcd_vb_count_posterior": (_int, [_p, _p, _i64, _i64, _p, _p, _p]),
+    "fcd_region_sets_set": (_int, [_p, _p, _p, _i64]),
+    "fcd_gibbs_region_set_tally": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "fcd_gibbs_set_region_set_accumulator": (_int, [_p, _p, _p, _i64, _i64, _i64]),
     "fcd_gibbs_coanomaly_tally": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "fcd_gibbs_set_coanomaly_accumulator": (_int, [_p, _p, _p, _i64, _i64, _i64]),
     "fcd_vb_coanomaly": (_int, [_p, _p, _i64, _i64, _p, _p, _p]),

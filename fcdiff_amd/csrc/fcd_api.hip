@@ -152,6 +152,9 @@ int fcd_ctx_create(fcd_ctx **out) {
     for (int k = 0; k < FCD_ACC_N; ++k) ctx->sweep_acc[k] = fcd_sweep_acc{{nullptr, nullptr}, 0, 0, 1};
     ctx->count_ws = nullptr;
     ctx->count_ws_bytes = 0;
+    ctx->rs_dev = nullptr;
+    ctx->rs_J = ctx->rs_smax = 0;
+    ctx->rs_max_member = -1;
     ctx->acc = nullptr;
     ctx->nan_slots = nullptr;
     ctx->dbg = nullptr;
@@ -240,6 +243,7 @@ int fcd_ctx_destroy(fcd_ctx *ctx) {
     if (ctx->fsq) (void)hipFree(ctx->fsq);
     if (ctx->frec) (void)hipFree(ctx->frec);
     if (ctx->count_ws) (void)hipFree(ctx->count_ws);
+    if (ctx->rs_dev) (void)hipFree(ctx->rs_dev);
     if (ctx->acc) (void)hipFree(ctx->acc);
     if (ctx->nan_slots) (void)hipFree(ctx->nan_slots);
     if (ctx->dbg) (void)hipFree(ctx->dbg);

@@ -48,8 +48,9 @@ enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA
 // The optional tallies fcd_gibbs_run adds to caller-owned uint32 buffers after a counted sweep, in the order it makes them:
 // (C, U, 3, 3) counts of (f_c, mixture case) (fcd_gibbs_set_pair_accumulator; one buffer, held in both places), (U, Nreg+1) /
 // (Nreg, U+1) histograms of the anomalous-region counts (fcd_gibbs_set_count_accumulator), (Nreg, Nreg) / (U, U) co-anomaly
-// counts (fcd_gibbs_set_coanomaly_accumulator).  fcd_gibbs.hip holds the launch of each.
-enum { FCD_ACC_PAIR, FCD_ACC_COUNT, FCD_ACC_COANOMALY, FCD_ACC_N };
+// counts (fcd_gibbs_set_coanomaly_accumulator), (J, U, S_max+1) / (J, U+1) histograms of the counts over the context's region
+// sets (fcd_gibbs_set_region_set_accumulator).  fcd_gibbs.hip holds the launch of each.
+enum { FCD_ACC_PAIR, FCD_ACC_COUNT, FCD_ACC_COANOMALY, FCD_ACC_REGION_SET, FCD_ACC_N };
 struct fcd_sweep_acc {
     uint32_t *buf[2];              // buf[0] == nullptr: detached
     int64_t nreg, u, every;        // the shape it was made for; added at every this many sweeps from accumulate_from on
@@ -92,6 +93,9 @@ struct fcd_ctx {
     fcd_sweep_acc sweep_acc[FCD_ACC_N];
     void *count_ws;                // per-chain counts of one tally, (U + Nreg) rows of GW*64 uint16 (fcd_count_ws_reserve)
     size_t count_ws_bytes;
+    // region sets (fcd_region_sets_set): J + 1 offsets, then the members (CSR, int32, device; owned), checked on the host
+    void *rs_dev;
+    int64_t rs_J, rs_smax, rs_max_member;      // number of sets (0: none), largest set, largest member
     // optional per-kernel timing with HIP events on the launch stream (fcd_prof_enable / fcd_prof_collect)
     int prof_on;
     hipEvent_t *prof_ev[FCD_PROF_SLOTS];   // pairs (begin, end)
@@ -188,6 +192,11 @@ int fcd_count_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, i
 // the co-anomaly kernel of fcd_coanomaly.hip (one launch, no scratch): both pair matrices += the counts of this state
 int fcd_coanomaly_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
                                uint32_t *region_pairs, uint32_t *patient_pairs, hipStream_t s);
+// the region-set kernels of fcd_region_sets.hip (two launches): both histograms += the counts of this state over the
+// context's sets; their scratch is the count tally's, grown by fcd_region_set_ws_reserve (fcd_gibbs_run: before its loop)
+int fcd_region_set_ws_reserve(fcd_ctx *ctx, int64_t U, int64_t G);
+int fcd_region_set_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
+                                uint32_t *hist_set, uint32_t *hist_prev, hipStream_t s);
 // bracket ONE kernel launch with events when profiling is on (no-ops otherwise)
 void fcd_prof_begin(fcd_ctx *ctx, int slot, hipStream_t s);
 void fcd_prof_end(fcd_ctx *ctx, int slot, hipStream_t s);

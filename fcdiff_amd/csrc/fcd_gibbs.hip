@@ -1512,6 +1512,9 @@ static int acc_launch_count(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_geo
 static int acc_launch_coanomaly(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_geo &g, const fcd_sweep_acc &a, hipStream_t s) {
     return fcd_coanomaly_tally_launch(ctx, c.r_bits, c.Nreg, c.U, c.G, g, a.buf[0], a.buf[1], s);
 }
+static int acc_launch_region_set(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_geo &g, const fcd_sweep_acc &a, hipStream_t s) {
+    return fcd_region_set_tally_launch(ctx, c.r_bits, c.Nreg, c.U, c.G, g, a.buf[0], a.buf[1], s);
+}
 static const struct {
     const char *msg_shape;
     int (*launch)(fcd_ctx *, const fcd_sweep_call &, const fcd_geo &, const fcd_sweep_acc &, hipStream_t);
@@ -1519,6 +1522,7 @@ static const struct {
     {"fcd_gibbs_run: the attached pair accumulator was made for Nreg=%lld, U=%lld", acc_launch_pair},
     {"fcd_gibbs_run: the attached count accumulator was made for Nreg=%lld, U=%lld", acc_launch_count},
     {"fcd_gibbs_run: the attached co-anomaly accumulator was made for Nreg=%lld, U=%lld", acc_launch_coanomaly},
+    {"fcd_gibbs_run: the attached region-set accumulator was made for Nreg=%lld, U=%lld", acc_launch_region_set},
 };
 
 // The sampler loop of ONE rank between two exchanges of pooled statistics: fcd_gibbs_run (what UnsharedRegionFit(method=
@@ -1661,6 +1665,10 @@ extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, 
     }
     if (acc_mask >> FCD_ACC_COUNT & 1u) {
         rc = fcd_count_ws_reserve(ctx, Nreg, U, G);          // (grown here, never inside the sweep loop)
+        if (rc) return rc;
+    }
+    if (acc_mask >> FCD_ACC_REGION_SET & 1u) {
+        rc = fcd_region_set_ws_reserve(ctx, U, G);
         if (rc) return rc;
     }
     return sweep_loop(ctx, c, sweep0, n_sweeps, mstep_every, accumulate_from, counts, cnt_f, cnt_r, hyper, acc_mask);

@@ -22,6 +22,8 @@ New knobs (all optional; defaults reproduce the reference):
                                                                anomaly_count_posterior()
     coanomaly, coanomaly_every                                 gibbs: counts of regions anomalous together and of patients
                                                                sharing anomalous regions for coanomaly_posterior()
+    region_sets, region_sets_every                             gibbs: histograms of the anomalous-region counts over sets
+                                                               of regions (networks) for region_set_posterior()
     missing_data                                               True: NaN entries of b / bt are unobserved and integrated out
 
 Differences from the reference that are deliberate and documented:
@@ -43,7 +45,7 @@ from . import util
 from . import score as _score
 from . import tables
 from .gibbs import (GibbsEngine, run_chains, allreduce_counts, pool_u32, pair_sweeps_in, ACCUMULATORS, PAIR_COUNT_MAX,
-                    COUNT_MAX_NREG, COUNT_MAX_U)
+                    COUNT_MAX_NREG, COUNT_MAX_U, region_sets_csr)
 
 # The knobs of a gibbs fit that attach one of the sampler's accumulators: knob, its period knob, what the messages call it,
 # the row of gibbs.ACCUMULATORS, and the attributes the pooled buffers and the number of sweeps behind them are left in.
@@ -127,6 +129,14 @@ class UnsharedRegionFit(object):
         self.patient_pair_counts = None     # (U, U) int64: (chain, sweep, region) with r_nu = r_nv = 1, pooled over ranks
         self.coanomaly_sweeps = 0           # number of sweeps behind those counts
         self.coanomaly_states = 0           # ... and of chain states: sweeps x chains, summed over ranks
+        self.region_sets = None             # sets of regions (networks) for region_set_posterior(): a dict name -> indices, a
+                                            # sequence of index sequences, or a boolean mask (J, Nreg); gibbs: histograms over them
+        self.region_sets_every = 1          # ... at every this many sweeps from burn_in on
+        self.region_set_hist = None         # (J, U, S_max+1) int64: chains x sweeps (x ranks) with sum_{n in S_j} r_nu = k
+        self.region_set_prevalence_hist = None      # (J, U+1) int64: ... with k patients having an anomalous region in S_j
+        self.region_set_sweeps = 0          # number of sweeps behind those histograms
+        self.region_set_names = None        # names and sizes of the sets behind them, in order
+        self.region_set_sizes = None
         # True: every NaN of b / bt is an unobserved value, integrated out exactly (S_B sums the observed h only, lM = 0 at a
         # missing bt); False: NaN is read as a number, as the reference reads it.  Only NaN is missing, not +-inf.
         self.missing_data = False
@@ -637,6 +647,13 @@ class UnsharedRegionFit(object):
             setattr(self, a.sweeps, 0)
             if getattr(self, a.knob):
                 self._check_accumulator(a.every, a.label, sites=a.engine.sites(N, U) if a.engine.sites else 1)
+        (self.region_set_hist, self.region_set_prevalence_hist, self.region_set_sweeps) = (None, None, 0)
+        (self.region_set_names, self.region_set_sizes) = (None, None)
+        if self.region_sets is not None:            # (beside the loop: the knob is a collection, not a flag)
+            region_sets_csr(self.region_sets, N)
+            self._check_accumulator("region_sets_every", "region-set histograms")
+            if U > COUNT_MAX_U:
+                raise ValueError("region-set histograms are made for at most %d patients (here %d)" % (COUNT_MAX_U, U))
         if self.anomaly_counts and (N > COUNT_MAX_NREG or U > COUNT_MAX_U):
             raise ValueError("anomaly-count histograms are made for at most %d regions and %d patients (here %d, %d)"
                              % (COUNT_MAX_NREG, COUNT_MAX_U, N, U))
@@ -645,6 +662,9 @@ class UnsharedRegionFit(object):
         for a in GIBBS_ACCUMULATORS:
             if getattr(self, a.knob):
                 eng._attach(a.engine, getattr(self, a.every))
+        if self.region_sets is not None:
+            eng.set_region_sets(self.region_sets)
+            eng.attach_region_set_accumulator(self.region_sets_every)
         pi2 = self._pi2()
         eng.set_hyper(np.asarray(self.model.gamma, dtype=np.float64), pi2)
         eng.init(float(pi2[1]))
@@ -701,6 +721,10 @@ class UnsharedRegionFit(object):
                 for (name, buf) in zip(a.results, eng._acc_buffers(a.engine)):
                     setattr(self, name, pool_u32(buf).cpu().numpy())
                 setattr(self, a.sweeps, getattr(eng, a.engine.key + "_sweeps"))
+        if eng.region_set_acc is not None:
+            (self.region_set_hist, self.region_set_prevalence_hist) = (pool_u32(b).cpu().numpy() for b in eng.region_set_acc)
+            self.region_set_sweeps = eng.region_set_sweeps
+            (self.region_set_names, self.region_set_sizes) = (list(eng.region_names), np.diff(eng.region_offsets).astype(np.int64))
         if eng.coanomaly_acc is not None:
             states = t.tensor([eng.coanomaly_sweeps * eng.G], dtype=t.int64, device=eng.cnt_f.device)
             self.coanomaly_states = int(allreduce_counts(states).cpu()[0])
@@ -806,6 +830,55 @@ class UnsharedRegionFit(object):
             raise ValueError("method must be 'vb' or 'gibbs'")
         return {"p_patient_count": p_patient, "p_region_count": p_region,
                 "p_patient_any": 1.0 - p_patient[:, 0], "p_region_any": 1.0 - p_region[:, 0]}
+
+    # ------------------------------------------------------------------ counts over sets of regions (networks)
+    def region_set_posterior(self, independent=False):
+        """
+        Posterior law of the anomalous regions inside each of the sets of `region_sets` (the networks of an atlas, say), from
+        the last run(), as a dict of NumPy float64 arrays (J sets, S_max the size of the largest):
+            names, sizes                     the sets, in the order given (a list of str, (J,) int64)
+            p_count       (J, U, S_max+1)    P(sum_{n in S_j} r_nu = k | data); zero beyond the set's size, rows sum to 1
+            p_any         (J, U)             P(patient u has an anomalous region in S_j) = 1 - p_count[..., 0]
+            expected      (J, U)             E[sum_{n in S_j} r_nu | data]
+            p_prevalence  (J, U+1)           P(exactly k patients have an anomalous region in S_j | data)
+            p_none        (J,)               P(no patient has) = p_prevalence[:, 0]
+        The sites of a patient are coupled through the mixture cases of their edges, so P(some n in S: r_nu = 1) is NOT
+        1 - prod_n (1 - P(r_nu = 1)):
+          method='gibbs', independent=False   the histograms over chains and the sweeps from burn_in on, every
+                          `region_sets_every`-th.  Needs `region_sets` set before run(); raises ValueError otherwise.  The
+                          histograms are kept as `region_set_hist` / `region_set_prevalence_hist`, the number of sweeps
+                          behind them as `region_set_sweeps`.
+          method='vb', or independent=True on either method   the mean-field law of _lq_R with the CURRENT `region_sets`:
+                          the count is Poisson-binomial over the set's rows, the prevalence Poisson-binomial over u with
+                          p_u = 1 - prod_{n in S} (1 - q1(n, u)) (both through fcd_vb_count_posterior).
+        For a sampler fit, joint minus independent is the excess, the convention of coanomaly_posterior().
+        SharedRegionFit: the patient extent is 1; p_count[j, 0] is the law of how many regions of S_j the population's map
+        holds.  Not provided: set posteriors of new patients in score() and membership().
+        """
+        if self.model is None or self.bt is None:
+            raise ValueError("region_set_posterior() needs a model and bt: call run() first")
+        if self.method not in ("vb", "gibbs"):
+            raise ValueError("method must be 'vb' or 'gibbs'")
+        if self.method == "gibbs" and not independent:
+            (hs, hv) = (self.region_set_hist, self.region_set_prevalence_hist)
+            if hs is None or hv is None:
+                raise ValueError("no region-set histograms: set region_sets before run(method='gibbs')")
+            (hs, hv) = (np.asarray(hs, dtype=np.float64), np.asarray(hv, dtype=np.float64))
+            if hs.sum() == 0 or hv.sum() == 0:
+                raise ValueError("no sweep was accumulated into the region-set histograms (n_sweeps <= burn_in?)")
+            (names, sizes) = (list(self.region_set_names), np.asarray(self.region_set_sizes, dtype=np.int64))
+            p_count = hs / hs.sum(axis=2, keepdims=True)
+            p_prev = hv / hv.sum(axis=1, keepdims=True)
+        else:
+            if self.region_sets is None:
+                raise ValueError("no region sets: set region_sets first")
+            (N, _C, U) = self._check_state(need=("lq_R",))
+            (names, offsets, members) = region_sets_csr(self.region_sets, N)
+            (p_count, p_prev) = region_set_independent(self._context(), self._d["lq_R"], N, U, offsets, members)
+            sizes = np.diff(offsets).astype(np.int64)
+        k = np.arange(p_count.shape[2], dtype=np.float64)
+        return {"names": names, "sizes": sizes, "p_count": p_count, "p_any": 1.0 - p_count[:, :, 0], "expected": p_count @ k,
+                "p_prevalence": p_prev, "p_none": p_prev[:, 0].copy()}
 
     # ------------------------------------------------------------------ co-anomaly
     def _coanomaly_counts(self):
@@ -1194,6 +1267,33 @@ def count_posterior(ctx, lq_R, Nreg, U):
     ctx.call("fcd_vb_count_posterior", _lib.dptr(lq_R.contiguous()), int(Nreg), int(U), _lib.dptr(p_patient),
              _lib.dptr(p_region), _lib.stream_ptr())
     return p_patient.cpu().numpy(), p_region.cpu().numpy()
+
+
+def region_set_independent(ctx, lq_R, Nreg, U, offsets, members):
+    """
+    (p_count (J, U, S_max+1), p_prevalence (J, U+1)) as NumPy float64 under independent sites with q_nu = P(r_nu = 1) from
+    lq_R (Nreg, U, 2) float64 (need not be normalised), for the sets (offsets, members) of region_sets_csr(): both are
+    Poisson-binomial laws, made by fcd_vb_count_posterior -- set j's count from the gathered block (|S_j|, U, 2), the
+    prevalences of all sets from one (J, U, 2) block of log(prod_n q0), log(1 - prod_n q0).
+    """
+    import torch
+    if tuple(lq_R.shape) != (Nreg, U, 2) or lq_R.dtype != torch.float64:
+        raise ValueError("lq_R must be float64 (Nreg, U, 2) = %s" % ((Nreg, U, 2),))
+    J = len(offsets) - 1
+    sizes = np.diff(offsets)
+    p_count = np.zeros((J, U, int(sizes.max()) + 1))
+    # log q0 = -log(1 + e^d), d = lq1 - lq0, to full relative accuracy near q0 = 1 (q1 = 0 and q1 = 1 exact)
+    d = lq_R[:, :, 1] - lq_R[:, :, 0]
+    lq0 = -(torch.clamp(d, min=0.0) + torch.log1p(torch.exp(-torch.abs(d))))
+    block = torch.empty((J, U, 2), dtype=torch.float64, device=lq_R.device)
+    idx = torch.as_tensor(np.asarray(members, dtype=np.int64), device=lq_R.device)
+    for j in range(J):
+        rows = idx[int(offsets[j]):int(offsets[j + 1])]
+        p_count[j, :, :sizes[j] + 1] = count_posterior(ctx, lq_R[rows].contiguous(), int(sizes[j]), U)[0]
+        block[j, :, 0] = lq0[rows].sum(dim=0)
+    block[:, :, 1] = torch.log(-torch.expm1(block[:, :, 0]))
+    p_prev = count_posterior(ctx, block, J, U)[1]
+    return p_count, p_prev
 
 
 def coanomaly_independent(ctx, lq_R, Nreg, U):

@@ -12,6 +12,7 @@ all-reduce of the 8-word pooled-count vector before an M-step; there is no data-
 """
 import collections
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -38,6 +39,59 @@ ACCUMULATORS = (
                 "fcd_gibbs_set_coanomaly_accumulator", lambda Nreg, U: max(Nreg, U), "co-anomaly"),
 )
 (_PAIR, _COUNT, _COANOMALY) = ACCUMULATORS
+# Further accumulators: run() walks them after ACCUMULATORS under the same rule, reading the engine's attribute with a default
+# of None (an engine that never heard of one makes no context call for it).  A new accumulator goes here: tests pin the three
+# rows above.  The region-set histograms take their shapes from the sets of set_region_sets().
+REGION_SET_MAX_SIZE, REGION_SET_MAX_SETS = 1023, 1024     # fcd_region_sets_set
+EXTRA_ACCUMULATORS = (
+    Accumulator("region_set", "region_set_acc", True,
+                lambda e: ((e.region_J, e.U, e.region_smax + 1), (e.region_J, e.U + 1)),
+                "fcd_gibbs_set_region_set_accumulator", None, "region-set"),
+)
+(_REGION_SET,) = EXTRA_ACCUMULATORS
+
+
+def region_sets_csr(sets, Nreg):
+    """
+    Region sets in any of their three forms -- a dict name -> sequence of region indices, a sequence of index sequences
+    (named "0", "1", ...), a boolean mask (J, Nreg) -- as (names, offsets (J+1,) int32, members int32): CSR with the members
+    of a set ascending, what fcd_region_sets_set takes.  ValueError for no set, an empty set, a duplicate, an index outside
+    [0, Nreg), more than 1023 members or more than 1024 sets.
+    """
+    Nreg = int(Nreg)
+    if isinstance(sets, dict):
+        names = [str(k) for k in sets.keys()]
+        rows = list(sets.values())
+    else:
+        mask = sets if isinstance(sets, np.ndarray) else None
+        if mask is not None and mask.dtype == np.bool_:
+            if mask.ndim != 2 or mask.shape[1] != Nreg:
+                raise ValueError("a region-set mask must be boolean (J, Nreg=%d)" % Nreg)
+            rows = [np.flatnonzero(m) for m in mask]
+        else:
+            rows = list(sets)
+        names = [str(j) for j in range(len(rows))]
+    if len(rows) < 1:
+        raise ValueError("region_sets holds no set")
+    if len(rows) > REGION_SET_MAX_SETS:
+        raise ValueError("region_sets holds %d sets (at most %d)" % (len(rows), REGION_SET_MAX_SETS))
+    (offsets, members) = ([0], [])
+    for (name, row) in zip(names, rows):
+        a = np.asarray(row)
+        if a.ndim != 1 or a.size == 0:
+            raise ValueError("region set %r is empty (or not a sequence of indices)" % name)
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("region set %r must hold integer region indices" % name)
+        a = np.sort(a.astype(np.int64))
+        if a[0] < 0 or a[-1] >= Nreg:
+            raise ValueError("region set %r has an index outside [0, %d)" % (name, Nreg))
+        if np.any(a[1:] == a[:-1]):
+            raise ValueError("region set %r names a region twice" % name)
+        if a.size > REGION_SET_MAX_SIZE:
+            raise ValueError("region set %r has %d members (at most %d)" % (name, a.size, REGION_SET_MAX_SIZE))
+        members.append(a)
+        offsets.append(offsets[-1] + a.size)
+    return names, np.asarray(offsets, dtype=np.int32), np.concatenate(members).astype(np.int32)
 
 
 def pair_sweeps_in(sweep0, n_sweeps, accumulate_from, every):
@@ -124,6 +178,12 @@ class GibbsEngine(object):
         self.coanomaly_acc = None   # (region_pairs (Nreg, Nreg), patient_pairs (U, U)) that run() adds to (attach_coanomaly_accumulator)
         self.coanomaly_every = 1
         self.coanomaly_sweeps = 0   # sweeps added to coanomaly_acc so far
+        self.region_names = None    # the sets of set_region_sets(): names, CSR offsets and members, their number, the largest
+        self.region_offsets = self.region_members = None
+        self.region_J = self.region_smax = 0
+        self.region_set_acc = None  # (hist_set (J, U, S_max+1), hist_prev (J, U+1)) that run() adds to (attach_region_set_accumulator)
+        self.region_set_every = 1
+        self.region_set_sweeps = 0  # sweeps added to region_set_acc so far
         self.ctx.call("fcd_ctx_reserve", self.Nreg, self.U, self.G)
         self.lMd = self.lMf = None
         if region_major:
@@ -212,12 +272,14 @@ class GibbsEngine(object):
         of every `pair_every`-th sweep from `accumulate_from` on, and with a count accumulator attached
         (attach_count_accumulator) the histograms of the anomalous-region counts of every `count_every`-th sweep, and with
         a co-anomaly accumulator attached (attach_coanomaly_accumulator) the two pair matrices of every
-        `coanomaly_every`-th sweep; a call that could overflow any of them raises ValueError.
+        `coanomaly_every`-th sweep, and with a region-set accumulator attached (attach_region_set_accumulator) the
+        histograms over the region sets of every `region_set_every`-th sweep; a call that could overflow any of them raises
+        ValueError.
         """
         acc = accumulate_from is not None
         live = []                   # (accumulator, sweeps this call adds to it), attached ones only
-        for a in ACCUMULATORS:      # (in this order, and nothing of an accumulator is read unless it is attached)
-            if not acc or getattr(self, a.attr) is None:
+        for a in ACCUMULATORS + EXTRA_ACCUMULATORS:     # (in this order, and nothing of an accumulator is read unless it is attached)
+            if not acc or (getattr(self, a.attr, None) if a in EXTRA_ACCUMULATORS else getattr(self, a.attr)) is None:
                 continue
             n = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), getattr(self, a.key + "_every"))
             total = getattr(self, a.key + "_sweeps") + n
@@ -229,6 +291,8 @@ class GibbsEngine(object):
         # (attached for this call only: the context is shared, no other engine's sweeps may add to these buffers)
         try:
             for (a, _n) in live:
+                if a is _REGION_SET:
+                    self._send_region_sets()
                 self.ctx.call(a.setter, *([_lib.dptr(b) for b in self._acc_buffers(a)]
                                           + [self.Nreg, self.U, getattr(self, a.key + "_every")]))
             self._run(sweep0, n_sweeps, mstep_every, accumulate_from, want_counts)
@@ -322,6 +386,71 @@ class GibbsEngine(object):
         self.ctx.call("fcd_gibbs_count_tally", _lib.dptr(self.r_bits), self.Nreg, self.U, self.G, _lib.dptr(hist_patient),
                       _lib.dptr(hist_region), _lib.stream_ptr())
         return hist_patient, hist_region
+
+    # ---- counts over sets of regions (networks): how many regions of a set, in how many patients a set is hit ----
+    def set_region_sets(self, sets):
+        """
+        The region sets of this engine's histograms, in any form region_sets_csr() takes; None clears.  They are copied to
+        the context (fcd_region_sets_set).  ValueError while the accumulator is attached: its buffers have the old shapes.
+        """
+        if self.region_set_acc is not None:
+            raise ValueError("detach the region-set accumulator before changing the sets")
+        if sets is None:
+            (self.region_names, self.region_offsets, self.region_members) = (None, None, None)
+            (self.region_J, self.region_smax) = (0, 0)
+            self.ctx.call("fcd_region_sets_set", None, None, 0)
+            self.ctx.region_sets_owner = None
+            return
+        (self.region_names, self.region_offsets, self.region_members) = region_sets_csr(sets, self.Nreg)
+        self.region_J = len(self.region_names)
+        self.region_smax = int(np.diff(self.region_offsets).max())
+        self.ctx.region_sets_owner = None
+        self._send_region_sets()
+
+    def _send_region_sets(self):
+        """The context is shared: make sure ITS sets are this engine's before a launch that writes this engine's buffers."""
+        owner = getattr(self.ctx, "region_sets_owner", None)        # (a weak reference: the context does not keep an engine alive)
+        if owner is not None and owner() is self:
+            return
+        if not self.region_J:
+            raise ValueError("no region sets: call set_region_sets() first")
+        self.ctx.call("fcd_region_sets_set", self.region_offsets.ctypes.data_as(C.c_void_p),
+                      self.region_members.ctypes.data_as(C.c_void_p), self.region_J)
+        self.ctx.region_sets_owner = weakref.ref(self)
+
+    def attach_region_set_accumulator(self, every=1):
+        """
+        From now on run() adds the end-of-sweep histograms over the sets of set_region_sets() to `region_set_acc`: hist_set
+        (J, U, S_max+1), over chains, of sum_{n in S_j} r_nu (bins beyond a set's size stay 0) and hist_prev (J, U+1) of the
+        number of patients with an anomalous region in S_j, at every `every`-th sweep from its `accumulate_from` on (none
+        when accumulate_from is None).  Zeroes the histograms.
+        """
+        if not self.region_J:
+            raise ValueError("no region sets: call set_region_sets() first")
+        if self.U > COUNT_MAX_U:
+            raise ValueError("region-set histograms are made for at most %d patients (here %d)" % (COUNT_MAX_U, self.U))
+        return self._attach(_REGION_SET, every)
+
+    def detach_region_set_accumulator(self):
+        self._detach(_REGION_SET)
+
+    def region_set_host(self):
+        """The attached histograms as NumPy uint32 arrays (hist_set (J, U, S_max+1), hist_prev (J, U+1))."""
+        return self._acc_host(_REGION_SET)
+
+    def region_set_tally(self, hist_set, hist_prev):
+        """hist_set (J, U, S_max+1), hist_prev (J, U+1) uint32-in-int32 tensors += the histograms of the current state."""
+        if not self.region_J:
+            raise ValueError("no region sets: call set_region_sets() first")
+        if (tuple(hist_set.shape) != (self.region_J, self.U, self.region_smax + 1)
+                or tuple(hist_prev.shape) != (self.region_J, self.U + 1)
+                or hist_set.element_size() != 4 or hist_prev.element_size() != 4
+                or not hist_set.is_contiguous() or not hist_prev.is_contiguous()):
+            raise ValueError("histograms must be contiguous 32-bit (J, U, S_max+1) and (J, U+1)")
+        self._send_region_sets()
+        self.ctx.call("fcd_gibbs_region_set_tally", _lib.dptr(self.r_bits), self.Nreg, self.U, self.G, _lib.dptr(hist_set),
+                      _lib.dptr(hist_prev), _lib.stream_ptr())
+        return hist_set, hist_prev
 
     # ---- co-anomaly: pairs of regions anomalous together, pairs of patients sharing anomalous regions ----
     def attach_coanomaly_accumulator(self, every=1):

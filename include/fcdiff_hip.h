@@ -426,6 +426,35 @@ int fcd_gibbs_set_count_accumulator(fcd_ctx *ctx, uint32_t *hist_patient, uint32
  * recursion; q = 0 and q = 1 give exact point masses.  Nreg, U <= 4095, else FCD_ERR_UNSUPPORTED. */
 int fcd_vb_count_posterior(fcd_ctx *ctx, const double *lq_R, int64_t Nreg, int64_t U, double *p_patient, double *p_region,
                            fcd_stream stream);
+/* ---- anomalous-region counts over sets of regions (networks of an atlas) --------------------------------------------
+ * For user-given sets S_0 .. S_{J-1} of regions: the law of sum_{n in S_j} r_nu and of #{u : r_nu = 1 for some n in S_j}.
+ * Both depend on the joint law of a patient's sites; the set of all regions gives fcd_gibbs_count_tally's hist_patient,
+ * a singleton {n} its hist_region[n].
+ *
+ * The sets of the context, CSR in HOST memory: offsets_host (J + 1, offsets[0] = 0), members_host (offsets[J]), the members
+ * of a set strictly increasing (no duplicates).  Sets may overlap and may repeat.  Everything is checked here, on the host:
+ * FCD_ERR_ARG for a null pointer, J < 1, offsets[0] != 0, an empty set, a negative member or members that do not increase;
+ * FCD_ERR_UNSUPPORTED for a set of more than 1023 members or J > 1024.  The context copies both arrays into a device buffer
+ * it owns and frees (it synchronises).  J = 0 with both arrays NULL clears.  Refused with FCD_ERR_ARG while the region-set
+ * accumulator is attached. */
+int fcd_region_sets_set(fcd_ctx *ctx, const int32_t *offsets_host, const int32_t *members_host, int64_t J);
+/* Histograms over chains of one state, with S_max the size of the largest set:
+ *   hist_set (J, U, S_max+1) uint32, hist_set[j][u][k] += #{chains with sum_{n in S_j} r_nu = k}; the bins k > |S_j| are
+ *   never touched;
+ *   hist_prev (J, U+1) uint32, hist_prev[j][k] += #{chains with #{u : r_nu = 1 for some n in S_j} = k}.
+ * Chains beyond G in the last word never count.  Two launches; the scratch, (J U + J) rows of ceil(G/64) * 64 uint16, is the
+ * count tally's, grown on demand.  FCD_ERR_ARG without sets, FCD_ERR_SHAPE if the largest member is >= Nreg,
+ * FCD_ERR_UNSUPPORTED for U > 512 or a scratch above 1 GiB. */
+int fcd_gibbs_region_set_tally(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, uint32_t *hist_set,
+                               uint32_t *hist_prev, fcd_stream stream);
+/* Attach both histograms for shape (Nreg, U) and the context's CURRENT sets (no device work; both NULL detaches), with the
+ * semantics of fcd_gibbs_set_count_accumulator: every sweep s of fcd_gibbs_run with s >= accumulate_from and
+ * (s - accumulate_from) % every == 0 adds its end-of-sweep state (two extra launches after the sweep's tally, after the other
+ * accumulators'; fcd_gibbs_run grows the scratch before its loop and refuses one above 1 GiB).  Refusals as
+ * fcd_gibbs_region_set_tally's; fcd_gibbs_run refuses another shape while they are attached, and fcd_region_sets_set
+ * refuses to change the sets.  fcd_gibbs_sweeps never adds to them.  The caller keeps sweeps x G below 2^32. */
+int fcd_gibbs_set_region_set_accumulator(fcd_ctx *ctx, uint32_t *hist_set, uint32_t *hist_prev, int64_t Nreg, int64_t U,
+                                         int64_t every);
 /* ---- co-anomaly (which regions are anomalous together, which patients share anomalous regions) -------------------
  * Second moments of the joint law of the sites, which the marginals do not give.
  *
