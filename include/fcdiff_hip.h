@@ -255,6 +255,21 @@ int fcd_model_sample_shared(fcd_ctx *ctx, const double *theta12_host, int64_t Nr
  * defaults, which are calibrated on raw correlations clipped to [-1, 1] (fcdiff/model.py:213, 236). */
 int fcd_corr_edges(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, int64_t T, int fisher_z, double *out,
                    fcd_stream stream);
+/* Cleaning in front of it: frame censoring and confound regression, per subject and over its kept frames only.
+ * ts (S, Nreg, T); confounds (S, Q, T), 0 <= Q <= 64, NULL allowed when Q == 0 (an intercept is always implied);
+ * frame_mask (S, T) bytes, non-zero keeps the frame, NULL keeps all.  A dropped frame is never read into a sum: NaN or
+ * inf stored there does not reach the result.  Rows are centred over the kept frames; constant confounds are dropped,
+ * the others scaled to unit norm and collinear ones dropped by pivoted Cholesky of their Gram matrix (remaining squared
+ * norm below 1e-10); resid = y_c - beta^T x_c from the normal equations of the columns used.
+ * resid (S, Nreg, T), caller-owned: the residuals of the kept frames in order at positions 0 .. n_kept - 1, exact zeros
+ * behind them.  A row is all zeros (its edges then come out NaN) when it is constant or holds a non-finite value over
+ * the kept frames, when its residual sum of squares is <= 1e-20 of its centred sum of squares, or when its subject has
+ * dof < 2 or a non-finite kept value in a confound (rank is then reported as 0).
+ * info (S, 3) int32, caller-owned: n_kept, rank (confound columns used), dof = n_kept - 1 - rank.
+ * The call sequence fcd_corr_clean; fcd_corr_edges(resid) gives the correlations of the residuals: zero-mean rows
+ * followed by zeros have the same correlation over T frames as over n_kept.  Deterministic; inputs are not written. */
+int fcd_corr_clean(fcd_ctx *ctx, const double *ts, const double *confounds, const uint8_t *frame_mask, int64_t S,
+                   int64_t Nreg, int64_t Q, int64_t T, double *resid, int32_t *info, fcd_stream stream);
 
 /* ---- variational updates ------------------------------------------------------------------ */
 /* UnsharedRegionFit._update_lq_F, fit.py:157-174 (+ _eval_q_R_w 382-406). */
