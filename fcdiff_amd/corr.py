@@ -116,3 +116,26 @@ def correlations(ts, fisher_z=False, ctx=None, as_numpy=True, *, confounds=None,
     if as_numpy:
         (out, info) = (out.cpu().numpy(), info.cpu().numpy() if info is not None else None)
     return (out, info) if cleaning and return_info else out
+
+
+def sampling_variance(info, fisher_z=False):
+    """
+    Per-subject sampling variance of a correlation, from the `info` (S, 3) that clean() / correlations(..., return_info=True)
+    give (column 2: the residual degrees of freedom dof = n_kept - 1 - rank): what goes into a fit's `b_noise_var` /
+    `bt_noise_var` for the subjects' columns.
+      fisher_z=True   1 / (dof - 2): the variance of atanh(r), to first order free of rho (1 / (n - 3) without confounds);
+      fisher_z=False  1 / dof: the rho = 0 value of var(r) = (1 - rho^2)^2 / dof, its largest, so an UPPER bound for every
+                      edge of the subject (a strongly correlated edge is measured better than this says).
+    Returns (S,) float64; `inf` where the denominator is <= 0 -- such a subject carries no information: drop it, or give its
+    column as NaN under missing_data (a fit refuses an infinite variance).
+    Frames of a scan are not independent: temporal autocorrelation lowers the effective degrees of freedom below dof, so
+    these variances are lower bounds on the real ones; a user who knows the effective dof of their acquisition passes
+    their own variances instead.
+    """
+    info = np.asarray(info)
+    if info.ndim != 2 or info.shape[1] != 3:
+        raise ValueError("info must have shape (S, 3): n_kept, rank, dof per subject")
+    den = info[:, 2].astype(np.float64) - (2.0 if fisher_z else 0.0)
+    out = np.full(den.shape, np.inf)
+    np.divide(1.0, den, out=out, where=den > 0)
+    return out

@@ -149,6 +149,8 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->fsq_bytes = 0;
     ctx->frec = nullptr;
     ctx->frec_bytes = 0;
+    ctx->noise_rec = nullptr;
+    ctx->noise_rec_bytes = 0;
     for (int k = 0; k < FCD_ACC_N; ++k) ctx->sweep_acc[k] = fcd_sweep_acc{{nullptr, nullptr}, 0, 0, 1};
     ctx->count_ws = nullptr;
     ctx->count_ws_bytes = 0;
@@ -242,6 +244,7 @@ int fcd_ctx_destroy(fcd_ctx *ctx) {
     if (ctx->dev_err) (void)hipHostFree((void *)ctx->dev_err);
     if (ctx->fsq) (void)hipFree(ctx->fsq);
     if (ctx->frec) (void)hipFree(ctx->frec);
+    if (ctx->noise_rec) (void)hipFree(ctx->noise_rec);
     if (ctx->count_ws) (void)hipFree(ctx->count_ws);
     if (ctx->rs_dev) (void)hipFree(ctx->rs_dev);
     if (ctx->acc) (void)hipFree(ctx->acc);

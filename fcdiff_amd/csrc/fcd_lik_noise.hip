@@ -1,0 +1,628 @@
+// Per-subject measurement noise: the likelihood tables and the connection posterior with a known sampling variance per
+// control (var_b[h]) and per patient session (var_bt[u*K + k]) on top of the population spread,
+//   b_ch    | F_c = k    ~ N(mu_k, sigma_k^2 + var_b[h])
+//   bt_cuk  | F~_cu = j  ~ N(mu_j, sigma_j^2 + var_bt[u,k])        (sessions conditionally independent)
+// in the log form of fcd_lik_sessions.hip (bt is (C, U, K), K >= 1; a 2-D bt is K = 1):
+//   a_j = sum_k [ -z*z/2 - (ln s_juk + ln sqrt(2 pi)) ],  z = (x - mu_j) * (1 / s_juk),  s_juk = sqrt(sigma_j^2 + var_bt[u,k]),
+//   m = max_j a_j,  lM = m + ln M_kl(exp(a - m))                     (ascending k; sess_logs below is the sessions kernel's)
+// A NaN session adds exactly 0.0 under FCD_DATA_NAN_MISSING whatever its variance, an item with no observed session is
+// 0.0, m = -inf gives -inf.
+//
+// The per-subject constants are made ONCE per call by noise_records_kernel, six doubles per subject-session -- 1/s_j and
+// ln s_j + ln sqrt(2 pi), j = 0..2 -- into a block the context owns (fcd_ctx::noise_rec).  The item loops then do no fp64
+// division, square root or logarithm per session: three multiplications by looked-up reciprocals where the sessions
+// kernel divides.  Layout: pairs {1/s_j, ln s_j + ln sqrt(2 pi)} of 16 bytes, state-major inside a session, patient fastest,
+//   bt records  rec[(k*3 + j)*U + u]     (double2)
+//   b records   rec[j*H + h]
+// so that the lanes of a wave, which hold consecutive patients (or consecutive h), read consecutive pairs: three 16-byte
+// LDS reads per session, global reads coalesced.  Where max(H, U*K) <= NOISE_LDS_RECORDS every block copies the records
+// of its role (item blocks the bt records, S_B blocks the b records) into dynamic LDS beside the stage buffer; above it
+// the loops read the same layout from global memory (it stays in L2: 48 bytes per subject-session).  A block that copies
+// records takes at least one tile (one pass of the shared kernel) per NOISE_COPY_PER_TILE bytes of them, so the grid is
+// smaller than the sessions kernel's where the records are many: at 400 records every block would otherwise copy 19 KB
+// to work on one tile of 16 KB.  Such a grid is held to the blocks resident at once.
+//
+// Three kernels, each its sessions sibling with the looked-up constants:
+//   lik_noise_kernel          lik_sessions_kernel: coalesced staging of bt, at most SESS_PASS sessions per pass, LDS transpose
+//                             and non-temporal stores of lM; S_B blocks with s_kh = sqrt(sigma_k^2 + var_b[h]) (the plain
+//                             lik_sb_block, bit for bit fcd_lik_tables_ex's S_B, where var_b is NULL)
+//   lik_shared_noise_kernel   lik_shared_sessions_kernel: L[c] = sum_u lM[c,u], no per-patient table is written
+//   posterior_noise_kernel    posterior_sessions_kernel
+#include "fcd_lik_common.h"
+
+#define FCD_NOISE_LDS_RECORDS 768        // fcdiff_amd/tables.py: NOISE_LDS_RECORDS (the tests take both sides of it)
+
+namespace {
+
+constexpr int SESS_PASS = 9;             // sessions per item and pass, as in fcd_lik_sessions.hip
+constexpr int NOISE_LDS_RECORDS = FCD_NOISE_LDS_RECORDS;    // 768 x 48 B = 36 KiB beside 26.5 KiB of stage buffer and tables
+constexpr int64_t NOISE_COPY_PER_TILE = 4096;               // bytes of records a block may copy per tile it takes
+
+typedef double2 NoiseRec;                // {1 / s, ln s + ln sqrt(2 pi)}
+
+// records of one call: the b records (3 H pairs, only where var_b is given), then the bt records (3 U K pairs)
+__global__ __launch_bounds__(256) void noise_records_kernel(const double *__restrict__ var_b, const double *__restrict__ var_bt,
+                                                            int H, int U, int K, LikTheta th, NoiseRec *__restrict__ rec_b,
+                                                            NoiseRec *__restrict__ rec_bt) {
+    const int64_t n_b = var_b ? (int64_t)H : 0, n_bt = (int64_t)U * K;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_b + n_bt; i += (int64_t)gridDim.x * blockDim.x) {
+        double v;
+        NoiseRec *r;
+        int64_t stride;
+        if (i < n_b) {
+            v = var_b[i];
+            r = rec_b + i;
+            stride = H;
+        } else {
+            const int64_t q = i - n_b;               // u*K + k, the order of var_bt
+            const int64_t u = q / K, k = q - u * K;
+            v = var_bt ? var_bt[q] : 0.0;
+            r = rec_bt + (k * 3) * (int64_t)U + u;
+            stride = U;
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double s = sqrt(th.sigma[j] * th.sigma[j] + v);
+            r[j * stride] = make_double2(1.0 / s, log(s) + kLogSqrt2Pi);
+        }
+    }
+}
+
+// one session's three ln N_j into a[]: r = the record of (u, k), its states `stride` pairs apart.  MISSING: a NaN session
+// adds exactly 0.0 and is counted
+template <bool MISSING>
+__device__ __forceinline__ void noise_add(double x, const LikTheta &th, const NoiseRec *r, int64_t stride, double a[3],
+                                          int &n_obs, unsigned &n_nan) {
+    double l[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const NoiseRec q = r[j * stride];
+        const double z = (x - th.mu[j]) * q.x;
+        l[j] = -(z * z) / 2.0 - q.y;
+    }
+    if (MISSING) {
+        const bool miss = __builtin_isnan(x);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) l[j] = miss ? 0.0 : l[j];
+        n_nan += miss;
+        n_obs += !miss;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) a[j] += l[j];
+}
+
+// v[k*3+l] = m + ln M_kl(exp(a - m)); `empty`: no observed session, exactly 0.0  (fcd_lik_sessions.hip's sess_logs)
+__device__ __forceinline__ void sess_logs(const double a[3], bool empty, const LikTheta &th, const double *etab,
+                                          const fcd_log_cell *ltab, double v[9]) {
+    const double m = fmax(a[0], fmax(a[1], a[2]));
+    double p[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) p[j] = fcd_exp_neg(m - a[j], etab);
+    lik_logs(p, th, ltab, v);
+    const bool dead = m == -__builtin_inf();
+#pragma unroll
+    for (int j = 0; j < 9; ++j) v[j] = empty ? 0.0 : (dead ? -__builtin_inf() : m + v[j]);
+}
+
+// lik_sb_block with s_kh = sqrt(sigma_k^2 + var_b[h]): rec = the b records [3][H]
+template <bool MISSING>
+__device__ __forceinline__ void noise_sb_block(unsigned sb_block, int tid, const double *__restrict__ b, int64_t C, int H,
+                                               const LikTheta &th, const NoiseRec *rec, double *__restrict__ S_B,
+                                               double *__restrict__ lpB, unsigned long long *__restrict__ nan_slots,
+                                               int *blk_nan) {
+    const int sub = tid & 15;
+    const int64_t c = (int64_t)sb_block * 16 + (tid >> 4);
+    double s[3] = {0.0, 0.0, 0.0};
+    int nan_b = 0;
+    if (MISSING && tid == 0) *blk_nan = 0;
+    if (c < C) {
+        const double *row = b + c * H;
+        for (int h = sub; h < H; h += 16) {
+            const double x = row[h];
+            double l[3] = {0.0, 0.0, 0.0};
+            int n_obs = 0;
+            unsigned n_nan = 0;
+            noise_add<MISSING>(x, th, rec + h, H, l, n_obs, n_nan);
+            nan_b += (int)n_nan;
+            if (lpB) {
+                double *o = lpB + (c * H + h) * 3;
+                o[0] = l[0]; o[1] = l[1]; o[2] = l[2];
+            }
+            s[0] += l[0]; s[1] += l[1]; s[2] += l[2];
+        }
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) s[j] += __shfl_xor(s[j], o, 16);
+    }
+    if (c < C && sub == 0) {
+        S_B[c * 3 + 0] = s[0];
+        S_B[c * 3 + 1] = s[1];
+        S_B[c * 3 + 2] = s[2];
+    }
+    if (MISSING) {
+        __syncthreads();
+        if (nan_b) atomicAdd(blk_nan, nan_b);
+        __syncthreads();
+        if (tid == 0 && *blk_nan && nan_slots)
+            atomicAdd(&nan_slots[(blockIdx.x % FCD_NAN_SLOTS) * 16 + 0], (unsigned long long)*blk_nan);
+    }
+}
+
+// the S_B blocks of both table kernels; rec_b == nullptr: no control variances, K_lik's own block
+template <bool MISSING, bool LDSREC>
+__device__ __forceinline__ void noise_sb_role(unsigned sb_block, int tid, const double *__restrict__ b, int64_t C, int H,
+                                              const LikTheta &th, const NoiseRec *__restrict__ rec_b, NoiseRec *rec_lds,
+                                              double *__restrict__ S_B, double *__restrict__ lpB,
+                                              unsigned long long *__restrict__ nan_slots, int *blk_nan) {
+    if (!rec_b) {
+        lik_sb_block<MISSING>(sb_block, tid, b, C, H, th, S_B, lpB, nan_slots, blk_nan);
+    } else if (LDSREC) {
+        for (int t = tid; t < 3 * H; t += LIK_BLOCK) rec_lds[t] = rec_b[t];      // (H <= NOISE_LDS_RECORDS)
+        __syncthreads();
+        noise_sb_block<MISSING>(sb_block, tid, b, C, H, th, rec_lds, S_B, lpB, nan_slots, blk_nan);
+    } else {
+        noise_sb_block<MISSING>(sb_block, tid, b, C, H, th, rec_b, S_B, lpB, nan_slots, blk_nan);
+    }
+}
+
+template <bool MISSING, bool LDSREC>
+__global__ __launch_bounds__(LIK_BLOCK) void lik_noise_kernel(const double *__restrict__ bt, int64_t n_items, int U, int K,
+                                                              LikTheta th, const LikTabs *__restrict__ tabs,
+                                                              const NoiseRec *__restrict__ rec_b,
+                                                              const NoiseRec *__restrict__ rec_bt,
+                                                              double *__restrict__ lM, int n_bt_blocks,
+                                                              const double *__restrict__ b, int64_t C, int H,
+                                                              double *__restrict__ S_B, double *__restrict__ lpB,
+                                                              unsigned long long *__restrict__ nan_slots) {
+    __shared__ __attribute__((aligned(16))) double stage[LIK_BLOCK * SESS_PASS];
+    __shared__ __attribute__((aligned(16))) fcd_log_cell ltab[FCD_LOG_CELLS];
+    __shared__ double etab[FCD_EXP_CELLS];
+    __shared__ int blk_nan;
+    extern __shared__ __attribute__((aligned(16))) NoiseRec rec_lds[];      // LDSREC: 3 max(H, U K) pairs
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= n_bt_blocks) {
+        noise_sb_role<MISSING, LDSREC>(blockIdx.x - n_bt_blocks, tid, b, C, H, th, rec_b, rec_lds, S_B, lpB, nan_slots, &blk_nan);
+        return;
+    }
+    for (int t = tid; t < FCD_LOG_CELLS; t += LIK_BLOCK) ltab[t] = tabs->log_tab[t];
+    if (tid < FCD_EXP_CELLS) etab[tid] = tabs->exp_tab[tid];
+    if (LDSREC)
+        for (int t = tid; t < 3 * U * K; t += LIK_BLOCK) rec_lds[t] = rec_bt[t];   // (U K <= NOISE_LDS_RECORDS)
+    if (MISSING && tid == 0) blk_nan = 0;
+    __syncthreads();
+    unsigned n_nan = 0;
+    const int64_t n_tiles = (n_items + LIK_BLOCK - 1) / LIK_BLOCK;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += n_bt_blocks) {
+        const int64_t base = tile * LIK_BLOCK;
+        const int n_here = (n_items - base < LIK_BLOCK) ? (int)(n_items - base) : LIK_BLOCK;
+        const unsigned u = (unsigned)((unsigned)(base % U) + (unsigned)tid) % (unsigned)U;     // the item's patient
+        double a[3] = {0.0, 0.0, 0.0};
+        int n_obs = 0;
+        for (int64_t k0 = 0; k0 < K; k0 += SESS_PASS) {
+            const int P = (K - k0 < SESS_PASS) ? (int)(K - k0) : SESS_PASS;
+            const int n = n_here * P;                               // <= 256 * 9: the pass fits the stage buffer
+            const double *src = bt + base * K + k0;                 // item q's sessions k0 .. k0 + P - 1 at src + q K
+            if (P == K) {
+                for (int j = tid; j < n; j += LIK_BLOCK) stage[j] = src[j];
+            } else {
+                for (int j = tid; j < n; j += LIK_BLOCK) {
+                    const int q = j / P;
+                    stage[j] = src[(int64_t)q * K + (j - q * P)];
+                }
+            }
+            __syncthreads();
+            if (tid < n_here) {
+                for (int s = 0; s < P; ++s) {
+                    if (LDSREC)
+                        noise_add<MISSING>(stage[tid * P + s], th, rec_lds + ((int)(k0 + s) * 3) * U + (int)u, U, a, n_obs, n_nan);
+                    else
+                        noise_add<MISSING>(stage[tid * P + s], th, rec_bt + ((k0 + s) * 3) * (int64_t)U + u, U, a, n_obs, n_nan);
+                }
+            }
+            __syncthreads();                                        // the pass is read: the next one, or the results
+        }
+        if (tid < n_here) {
+            double v[9];
+            sess_logs(a, MISSING && n_obs == 0, th, etab, ltab, v);
+#pragma unroll
+            for (int j = 0; j < 9; ++j) stage[tid * 9 + j] = v[j];
+        }
+        __syncthreads();
+        const int64_t n_dbl = (int64_t)n_here * 9;
+        double *dst = lM + base * 9;
+        // base*9*8 bytes is a multiple of 16 (LIK_BLOCK*72), so double2 stores are aligned; non-temporal as in lik_kernel
+        const int64_t n_d2 = n_dbl >> 1;
+        const double2 *s2 = reinterpret_cast<const double2 *>(stage);
+        double2 *d2 = reinterpret_cast<double2 *>(dst);
+        {
+            typedef double d2v __attribute__((ext_vector_type(2)));
+            for (int64_t j = tid; j < n_d2; j += LIK_BLOCK)
+                __builtin_nontemporal_store(*reinterpret_cast<const d2v *>(&s2[j]), reinterpret_cast<d2v *>(&d2[j]));
+        }
+        if ((n_dbl & 1) && tid == 0) dst[n_dbl - 1] = stage[n_dbl - 1];
+        __syncthreads();
+    }
+    if (MISSING) {
+        if (n_nan) atomicAdd(&blk_nan, (int)n_nan);
+        __syncthreads();
+        if (tid == 0 && blk_nan && nan_slots)
+            atomicAdd(&nan_slots[(blockIdx.x % FCD_NAN_SLOTS) * 16 + 1], (unsigned long long)blk_nan);
+    }
+}
+
+template <bool MISSING, bool LDSREC, int G>
+__global__ __launch_bounds__(LIK_BLOCK) void lik_shared_noise_kernel(const double *__restrict__ bt, int64_t C, int U, int K,
+                                                                     LikTheta th, const LikTabs *__restrict__ tabs,
+                                                                     const NoiseRec *__restrict__ rec_b,
+                                                                     const NoiseRec *__restrict__ rec_bt, double *__restrict__ L,
+                                                                     int n_l_blocks, const double *__restrict__ b, int H,
+                                                                     double *__restrict__ S_B,
+                                                                     unsigned long long *__restrict__ nan_slots) {
+    static_assert(G == 16 || G == 32 || G == 64, "lane group of 16, 32 or 64");
+    __shared__ __attribute__((aligned(16))) fcd_log_cell ltab[FCD_LOG_CELLS];
+    __shared__ double etab[FCD_EXP_CELLS];
+    __shared__ int blk_nan;
+    extern __shared__ __attribute__((aligned(16))) NoiseRec rec_lds[];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= n_l_blocks) {
+        noise_sb_role<MISSING, LDSREC>(blockIdx.x - n_l_blocks, tid, b, C, H, th, rec_b, rec_lds, S_B, nullptr, nan_slots,
+                                       &blk_nan);
+        return;
+    }
+    for (int t = tid; t < FCD_LOG_CELLS; t += LIK_BLOCK) ltab[t] = tabs->log_tab[t];
+    if (tid < FCD_EXP_CELLS) etab[tid] = tabs->exp_tab[tid];
+    if (LDSREC)
+        for (int t = tid; t < 3 * U * K; t += LIK_BLOCK) rec_lds[t] = rec_bt[t];
+    if (MISSING && tid == 0) blk_nan = 0;
+    __syncthreads();
+    constexpr int EPB = LIK_BLOCK / G;          // edges per block and pass
+    const int lane = tid & (G - 1);
+    unsigned n_nan = 0;
+    for (int64_t c0 = (int64_t)blockIdx.x * EPB; c0 < C; c0 += (int64_t)n_l_blocks * EPB) {
+        const int64_t c = c0 + tid / G;         // the same for the G lanes of a group
+        double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (c < C) {
+            for (int u = lane; u < U; u += G) {
+                const double *x = bt + (c * U + u) * K;             // the item's K sessions
+                double a[3] = {0.0, 0.0, 0.0}, v[9];
+                int n_obs = 0;
+                for (int k = 0; k < K; ++k) {
+                    if (LDSREC)
+                        noise_add<MISSING>(x[k], th, rec_lds + (k * 3) * U + u, U, a, n_obs, n_nan);
+                    else
+                        noise_add<MISSING>(x[k], th, rec_bt + ((int64_t)k * 3) * U + u, U, a, n_obs, n_nan);
+                }
+                sess_logs(a, MISSING && n_obs == 0, th, etab, ltab, v);
+#pragma unroll
+                for (int j = 0; j < 9; ++j) s[j] += v[j];
+            }
+        }
+#pragma unroll
+        for (int o = G / 2; o > 0; o >>= 1)
+#pragma unroll
+            for (int j = 0; j < 9; ++j) s[j] += __shfl_xor(s[j], o, G);
+        if (c < C && lane == 0) {
+#pragma unroll
+            for (int j = 0; j < 9; ++j) L[c * 9 + j] = s[j];
+        }
+    }
+    if (MISSING) {
+        __syncthreads();
+        if (n_nan) atomicAdd(&blk_nan, (int)n_nan);
+        __syncthreads();
+        if (tid == 0 && blk_nan && nan_slots)
+            atomicAdd(&nan_slots[(blockIdx.x % FCD_NAN_SLOTS) * 16 + 1], (unsigned long long)blk_nan);
+    }
+}
+
+template <bool MISSING, bool LDSREC>
+void lik_shared_noise_launch(int group, dim3 grid, size_t lds, hipStream_t s, const double *bt, int64_t C, int U, int K,
+                             const LikTheta &th, const LikTabs *tabs, const NoiseRec *rec_b, const NoiseRec *rec_bt, double *L,
+                             int n_l_blocks, const double *b, int H, double *S_B, unsigned long long *slots) {
+    if (group == 16)
+        hipLaunchKernelGGL((lik_shared_noise_kernel<MISSING, LDSREC, 16>), grid, dim3(LIK_BLOCK), lds, s, bt, C, U, K, th, tabs,
+                           rec_b, rec_bt, L, n_l_blocks, b, H, S_B, slots);
+    else if (group == 32)
+        hipLaunchKernelGGL((lik_shared_noise_kernel<MISSING, LDSREC, 32>), grid, dim3(LIK_BLOCK), lds, s, bt, C, U, K, th, tabs,
+                           rec_b, rec_bt, L, n_l_blocks, b, H, S_B, slots);
+    else
+        hipLaunchKernelGGL((lik_shared_noise_kernel<MISSING, LDSREC, 64>), grid, dim3(LIK_BLOCK), lds, s, bt, C, U, K, th, tabs,
+                           rec_b, rec_bt, L, n_l_blocks, b, H, S_B, slots);
+}
+
+struct NoisePostTheta {
+    double mu[3];
+    double eps;           // epsilon
+    double e[3];          // _eval_M_eps(eta, epsilon, l)
+    double pT[3];         // p(T = 1 | l) = 0, 1, eta
+};
+
+// posterior_sessions_kernel statement for statement, except that ln N_j of a session comes from the record of (u, k):
+// -z*z/2 - (ln s_juk + ln sqrt(2 pi)) with z = (x - mu_j) / s_juk through the record's reciprocal.  (The constant
+// ln sqrt(2 pi) is common to the three j of a session and leaves the law as it is.)
+template <bool MISSING>
+__global__ __launch_bounds__(256) void posterior_noise_kernel(const double *__restrict__ bt, int64_t C, int U, int K,
+                                                              NoisePostTheta th, const NoiseRec *__restrict__ rec_bt,
+                                                              const uint32_t *__restrict__ counts,
+                                                              const double *__restrict__ lq_F, const double *__restrict__ lq_R,
+                                                              double *__restrict__ p_T, double *__restrict__ p_Ft,
+                                                              double *__restrict__ p_ch) {
+    const int64_t items = C * U;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+        double W[9];
+        const int64_t c = i / U;
+        const int u = (int)(i - c * U);
+        if (counts) {
+            const uint32_t *cw = counts + i * 9;
+#pragma unroll
+            for (int j = 0; j < 9; ++j) W[j] = (double)cw[j];
+        } else {
+            int n, m;
+            fcd_edge_to_pair(c, n, m);
+            const double q0n = exp(lq_R[((int64_t)n * U + u) * 2]), q1n = exp(lq_R[((int64_t)n * U + u) * 2 + 1]);
+            const double q0m = exp(lq_R[((int64_t)m * U + u) * 2]), q1m = exp(lq_R[((int64_t)m * U + u) * 2 + 1]);
+            double w[3];
+            w[0] = q0n * q0m;
+            w[1] = q1n * q1m;
+            w[2] = q0n * q1m;
+            w[2] += q1n * q0m;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double qF = exp(lq_F[c * 3 + k]);
+#pragma unroll
+                for (int l = 0; l < 3; ++l) W[k * 3 + l] = qF * w[l];
+            }
+        }
+        const double *x = bt + i * K;
+        double a[3] = {0.0, 0.0, 0.0};
+        int n_obs = 0;
+        for (int k = 0; k < K; ++k) {
+            const double xk = x[k];
+            if (MISSING && __builtin_isnan(xk)) continue;          // unobserved: the session's densities integrate to 1
+            ++n_obs;
+            const NoiseRec *r = rec_bt + ((int64_t)k * 3) * U + u;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const NoiseRec q = r[(int64_t)j * U];
+                const double z = (xk - th.mu[j]) * q.x;
+                a[j] += -(z * z) / 2.0 - q.y;
+            }
+        }
+        double N[3];
+        if (MISSING && n_obs == 0) {
+            N[0] = N[1] = N[2] = 1.0;
+        } else {
+            const double mx = fmax(a[0], fmax(a[1], a[2]));
+#pragma unroll
+            for (int j = 0; j < 3; ++j) N[j] = exp(a[j] - mx);
+        }
+        const double S[3] = {N[1] + N[2], N[0] + N[2], N[0] + N[1]};
+        double wsum = 0.0, t1 = 0.0, ch = 0.0, ft[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+#pragma unroll
+            for (int l = 0; l < 3; ++l) {
+                const double wt = W[k * 3 + l];
+                if (wt == 0.0) continue;
+                const double off = (1 - th.e[l]) * 0.5;
+                const double M = th.e[l] * N[k] + off * S[k];
+                if (!(M > 0.0)) continue;                    // (only at epsilon in {0, 1}: a case the model gives no mass)
+                const double r = wt / M;
+                wsum += wt;
+                if (th.pT[l] != 0.0) t1 += th.pT[l] * (th.eps * N[k] + (1 - th.eps) * 0.5 * S[k]) * r;
+                ch += off * S[k] * r;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) ft[j] += ((j == k) ? th.e[l] : off) * N[j] * r;
+            }
+        }
+        const double inv = 1.0 / wsum;
+        p_T[i] = t1 * inv;
+        p_ch[i] = ch * inv;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) p_Ft[i * 3 + j] = ft[j] * inv;
+    }
+}
+
+// sessions_check's refusals (fcd_lik_sessions.hip), and the record block's size
+int noise_check(fcd_ctx *ctx, int64_t C, int64_t H, int64_t U, int64_t K, int flags, bool counted) {
+    if (flags & ~FCD_DATA_NAN_MISSING) return fcd_fail(ctx, FCD_ERR_ARG, "noise tables: unknown flags 0x%x", flags);
+    if (counted && !(flags & FCD_DATA_NAN_MISSING))
+        return fcd_fail(ctx, FCD_ERR_ARG, "noise tables: missing counts need FCD_DATA_NAN_MISSING");
+    if (C < 1 || H < 1 || U < 1) return fcd_fail(ctx, FCD_ERR_ARG, "noise tables: C=%lld and U=%lld (and H) must be >= 1", C, U);
+    if (K < 1) return fcd_fail(ctx, FCD_ERR_ARG, "noise tables: K=%lld sessions, must be >= 1", K);
+    if (fcd_C_to_N(C) < 0) return fcd_fail(ctx, FCD_ERR_SHAPE, "Number of connections (%lld) must be a triangular number.", C);
+    if (H > INT32_MAX || U > INT32_MAX || K > INT32_MAX || C * U > INT64_MAX / 8 / K || U * K > ((int64_t)1 << 31))
+        return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "noise tables: H/U/K too large");
+    return FCD_OK;
+}
+
+int noise_rec_reserve(fcd_ctx *ctx, size_t bytes) {
+    if (bytes <= ctx->noise_rec_bytes) return FCD_OK;
+    FCD_HIP_TRY(hipDeviceSynchronize());        // the old block may still be read by kernels already queued
+    if (ctx->noise_rec) FCD_HIP_TRY(hipFree(ctx->noise_rec));
+    ctx->noise_rec = nullptr;
+    ctx->noise_rec_bytes = 0;
+    const size_t want = bytes < (64u << 10) ? (64u << 10) : bytes;
+    FCD_HIP_TRY(hipMalloc(&ctx->noise_rec, want));
+    ctx->noise_rec_bytes = want;
+    ctx->n_alloc += 1;
+    return FCD_OK;
+}
+
+// the records of one call, in the context's block: *rec_b (nullptr without var_b) and *rec_bt
+int noise_records(fcd_ctx *ctx, const double *var_b, const double *var_bt, int64_t H, int64_t U, int64_t K, const LikTheta &th,
+                  hipStream_t s, const NoiseRec **rec_b, const NoiseRec **rec_bt) {
+    const int64_t n_b = var_b ? H : 0, n = n_b + U * K;
+    int rc = noise_rec_reserve(ctx, (size_t)n * 3 * sizeof(NoiseRec));
+    if (rc) return rc;
+    NoiseRec *base = static_cast<NoiseRec *>(ctx->noise_rec);
+    *rec_b = var_b ? base : nullptr;
+    *rec_bt = base + 3 * n_b;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > (int64_t)ctx->num_cu * 8) blocks = (int64_t)ctx->num_cu * 8;
+    hipLaunchKernelGGL(noise_records_kernel, dim3((unsigned)blocks), dim3(256), 0, s, var_b, var_bt, (int)H, (int)U, (int)K, th,
+                       base, base + 3 * n_b);
+    FCD_LAUNCH_CHECK();
+    return FCD_OK;
+}
+
+// tiles (passes) a block takes at least: one per NOISE_COPY_PER_TILE bytes of records it copies into LDS
+int64_t noise_tiles_per_block(size_t lds_record_bytes) {
+    const int64_t t = ((int64_t)lds_record_bytes + NOISE_COPY_PER_TILE - 1) / NOISE_COPY_PER_TILE;
+    return t < 1 ? 1 : t;
+}
+
+}  // namespace
+
+extern "C" int fcd_lik_tables_noise(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U, int64_t K,
+                                    const double *theta, const double *var_b, const double *var_bt, double *S_B, double *lM,
+                                    double *lp_B_g_F, int flags, int64_t *n_missing2, fcd_stream stream) {
+    if (!ctx || !b || !bt || !theta || !S_B || !lM) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_lik_tables_noise: null pointer");
+    int rc = noise_check(ctx, C, H, U, K, flags, n_missing2 != nullptr);
+    if (rc) return rc;
+    LikTheta th;
+    lik_theta_make(theta, th);
+    hipStream_t s = (hipStream_t)stream;
+    const NoiseRec *rec_b, *rec_bt;
+    rc = noise_records(ctx, var_b, var_bt, H, U, K, th, s, &rec_b, &rec_bt);
+    if (rc) return rc;
+    const int64_t n_items = C * U;
+    const int64_t n_tiles = (n_items + LIK_BLOCK - 1) / LIK_BLOCK;
+    const int64_t n_rec = (rec_b && H > U * K) ? H : U * K;
+    const bool in_lds = n_rec <= NOISE_LDS_RECORDS;
+    const size_t lds = in_lds ? (size_t)n_rec * 3 * sizeof(NoiseRec) : 0;
+    const int64_t per_block = noise_tiles_per_block(in_lds ? (size_t)U * K * 3 * sizeof(NoiseRec) : 0);
+    int64_t grid = (n_tiles + per_block - 1) / per_block;
+    int64_t cap = (int64_t)ctx->num_cu * 16;         // K_lik's measured choice: 16 blocks per CU, grid-stride beyond
+    if (per_block > 1) {
+        // blocks of several tiles: no more of them than are resident at once, or the few left over start when the others
+        // are done and double the time (measured at K = 8: 778 blocks of 5 tiles on 768 places)
+        const bool miss = (flags & FCD_DATA_NAN_MISSING) != 0;
+        const void *fn = miss ? reinterpret_cast<const void *>(lik_noise_kernel<true, true>)
+                              : reinterpret_cast<const void *>(lik_noise_kernel<false, true>);
+        int per_cu = 0;
+        FCD_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, LIK_BLOCK, lds));
+        if (per_cu >= 1 && (int64_t)ctx->num_cu * per_cu < cap) cap = (int64_t)ctx->num_cu * per_cu;
+    }
+    if (grid > cap) grid = cap;
+    const int64_t n_b_blocks = (C + 15) / 16;
+    unsigned long long *slots = n_missing2 ? reinterpret_cast<unsigned long long *>(ctx->nan_slots) : nullptr;
+    const LikTabs *tabs = reinterpret_cast<const LikTabs *>(ctx->log_tab);
+    const dim3 g((unsigned)(grid + n_b_blocks));
+#define FCD_NOISE_LAUNCH(MISS, INLDS, SLOTS)                                                                                  \
+    hipLaunchKernelGGL((lik_noise_kernel<MISS, INLDS>), g, dim3(LIK_BLOCK), lds, s, bt, n_items, (int)U, (int)K, th, tabs, rec_b, \
+                       rec_bt, lM, (int)grid, b, C, (int)H, S_B, lp_B_g_F, SLOTS)
+    if (flags & FCD_DATA_NAN_MISSING) {
+        if (in_lds) FCD_NOISE_LAUNCH(true, true, slots);
+        else FCD_NOISE_LAUNCH(true, false, slots);
+    } else {
+        if (in_lds) FCD_NOISE_LAUNCH(false, true, nullptr);
+        else FCD_NOISE_LAUNCH(false, false, nullptr);
+    }
+#undef FCD_NOISE_LAUNCH
+    FCD_LAUNCH_CHECK();
+    if (slots) {
+        hipLaunchKernelGGL(nan_fold_kernel, dim3(1), dim3(FCD_NAN_SLOTS), 0, s, slots, n_missing2);
+        FCD_LAUNCH_CHECK();
+    }
+    return FCD_OK;
+}
+
+extern "C" int fcd_lik_shared_tables_noise(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                           int64_t K, const double *theta, const double *var_b, const double *var_bt,
+                                           double *S_B, double *L, int flags, int64_t *nan_counts, fcd_stream stream) {
+    if (!ctx || !b || !bt || !theta || !S_B || !L) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_lik_shared_tables_noise: null pointer");
+    int rc = noise_check(ctx, C, H, U, K, flags, nan_counts != nullptr);
+    if (rc) return rc;
+    LikTheta th;
+    lik_theta_make(theta, th);
+    hipStream_t s = (hipStream_t)stream;
+    const NoiseRec *rec_b, *rec_bt;
+    rc = noise_records(ctx, var_b, var_bt, H, U, K, th, s, &rec_b, &rec_bt);
+    if (rc) return rc;
+    const int group = U <= 16 ? 16 : (U <= 32 ? 32 : 64);
+    const int64_t epb = LIK_BLOCK / group;
+    const int64_t n_rec = (rec_b && H > U * K) ? H : U * K;
+    const bool in_lds = n_rec <= NOISE_LDS_RECORDS;
+    const size_t lds = in_lds ? (size_t)n_rec * 3 * sizeof(NoiseRec) : 0;
+    const int64_t per_block = noise_tiles_per_block(in_lds ? (size_t)U * K * 3 * sizeof(NoiseRec) : 0);
+    int64_t n_l = (C + epb - 1) / epb;
+    n_l = (n_l + per_block - 1) / per_block;
+    const int64_t cap = (int64_t)ctx->num_cu * 16;   // up to 16 blocks per CU, grid-stride beyond
+    if (n_l > cap) n_l = cap;
+    const int64_t n_b_blocks = (C + 15) / 16;
+    const dim3 grid((unsigned)(n_l + n_b_blocks));
+    unsigned long long *slots = nan_counts ? reinterpret_cast<unsigned long long *>(ctx->nan_slots) : nullptr;
+    const LikTabs *tabs = reinterpret_cast<const LikTabs *>(ctx->log_tab);
+    if (flags & FCD_DATA_NAN_MISSING) {
+        if (in_lds)
+            lik_shared_noise_launch<true, true>(group, grid, lds, s, bt, C, (int)U, (int)K, th, tabs, rec_b, rec_bt, L, (int)n_l,
+                                                b, (int)H, S_B, slots);
+        else
+            lik_shared_noise_launch<true, false>(group, grid, lds, s, bt, C, (int)U, (int)K, th, tabs, rec_b, rec_bt, L,
+                                                 (int)n_l, b, (int)H, S_B, slots);
+    } else {
+        if (in_lds)
+            lik_shared_noise_launch<false, true>(group, grid, lds, s, bt, C, (int)U, (int)K, th, tabs, rec_b, rec_bt, L,
+                                                 (int)n_l, b, (int)H, S_B, nullptr);
+        else
+            lik_shared_noise_launch<false, false>(group, grid, lds, s, bt, C, (int)U, (int)K, th, tabs, rec_b, rec_bt, L,
+                                                  (int)n_l, b, (int)H, S_B, nullptr);
+    }
+    FCD_LAUNCH_CHECK();
+    if (slots) {
+        hipLaunchKernelGGL(nan_fold_kernel, dim3(1), dim3(FCD_NAN_SLOTS), 0, s, slots, nan_counts);
+        FCD_LAUNCH_CHECK();
+    }
+    return FCD_OK;
+}
+
+extern "C" int fcd_conn_posterior_noise(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, int64_t K, const double *theta,
+                                        const double *var_bt, const uint32_t *counts, const double *lq_F, const double *lq_R,
+                                        int flags, double *p_T, double *p_F_tilde, double *p_changed, fcd_stream stream) {
+    if (!ctx || !bt || !theta || !p_T || !p_F_tilde || !p_changed)
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_conn_posterior_noise: null pointer");
+    if (flags & ~FCD_DATA_NAN_MISSING) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_conn_posterior_noise: unknown flags 0x%x", flags);
+    if ((counts != nullptr) == (lq_F != nullptr || lq_R != nullptr) || (!counts && (!lq_F || !lq_R)))
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_conn_posterior_noise: pass counts, or lq_F and lq_R");
+    if (Nreg < 2 || U < 1 || U > INT32_MAX || Nreg > 46340)
+        return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_conn_posterior_noise: Nreg=%lld U=%lld", Nreg, U);
+    if (K < 1) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_conn_posterior_noise: K=%lld sessions, must be >= 1", K);
+    const int64_t C = fcd_tri(Nreg);
+    if (K > INT32_MAX || C * U > INT64_MAX / 8 / K || U * K > ((int64_t)1 << 31))
+        return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_conn_posterior_noise: K=%lld too large", K);
+    for (int k = 0; k < 3; ++k)
+        if (!(theta[9 + k] > 0.0)) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_conn_posterior_noise: sigma must be > 0");
+    LikTheta lt;
+    lik_theta_make(theta, lt);
+    hipStream_t s = (hipStream_t)stream;
+    const NoiseRec *rec_b, *rec_bt;
+    int rc = noise_records(ctx, nullptr, var_bt, 1, U, K, lt, s, &rec_b, &rec_bt);
+    if (rc) return rc;
+    NoisePostTheta th;
+    const double eta = theta[1], epsilon = theta[2];
+    for (int k = 0; k < 3; ++k) th.mu[k] = theta[6 + k];
+    th.eps = epsilon;
+    th.e[0] = 1 - epsilon;                        // _eval_M_eps, fit.py:433-444
+    th.e[1] = epsilon;
+    double e2 = eta * epsilon;
+    e2 += (1 - eta) * (1 - epsilon);
+    th.e[2] = e2;
+    th.pT[0] = 0.0;
+    th.pT[1] = 1.0;
+    th.pT[2] = eta;
+    const int64_t items = C * U;
+    int64_t blocks = (items + 255) / 256;
+    const int64_t cap = (int64_t)ctx->num_cu * 64;
+    if (blocks > cap) blocks = cap;
+    if (flags & FCD_DATA_NAN_MISSING)
+        hipLaunchKernelGGL(posterior_noise_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, bt, C, (int)U, (int)K, th, rec_bt,
+                           counts, lq_F, lq_R, p_T, p_F_tilde, p_changed);
+    else
+        hipLaunchKernelGGL(posterior_noise_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, bt, C, (int)U, (int)K, th,
+                           rec_bt, counts, lq_F, lq_R, p_T, p_F_tilde, p_changed);
+    FCD_LAUNCH_CHECK();
+    return FCD_OK;
+}

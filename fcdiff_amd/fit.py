@@ -82,6 +82,19 @@ class UnsharedRegionFit(object):
     missing_data = True: a NaN session contributes nothing, and missing_counts() counts NaN session entries.  Extra
     sessions of controls are extra columns of b.  Not provided with sessions: the theta_sub step (update_theta_sub,
     theta_sub_every: NotImplementedError from run()) and the per-item table `_p_Bt_g_Ft` (ValueError).
+
+    Measurement noise
+    -----------------
+    `b_noise_var` (H,) and `bt_noise_var` (U,) or (U, K) give every control and every patient (session) a KNOWN measurement
+    variance on top of the population spread: b_ch ~ N(mu_k, sigma_k^2 + b_noise_var[h]), bt_cuk ~ N(mu_j, sigma_j^2 +
+    bt_noise_var[u,k]); sigma is then the population spread alone, and a correlation from few frames counts for less instead
+    of looking anomalous.  corr.sampling_variance(info) gives the variances of the cleaning front-end's subjects.  A (U,)
+    with sessions data applies to every session; None is all zeros, and with both None nothing changes.  The variances
+    enter through the table build only (fcd_lik_tables_noise / fcd_lik_shared_tables_noise): both fitters of both models,
+    log_evidence(), connection_posterior() and score(bt_new, noise_var=...) take them.  Values must be finite and >= 0
+    (ValueError naming "noise" from run() / _update_lps()); to drop a subject use NaN data under missing_data, not an
+    infinite variance.  Not provided with noise variances: the theta_sub step and membership() (NotImplementedError), and
+    `_p_Bt_g_Ft` (ValueError).
     """
 
     # SharedRegionFit: the tables are (S_B, L) of ONE patient (tables.build(shared=True)), so the state's patient extent is 1,
@@ -140,6 +153,9 @@ class UnsharedRegionFit(object):
         # True: every NaN of b / bt is an unobserved value, integrated out exactly (S_B sums the observed h only, lM = 0 at a
         # missing bt); False: NaN is read as a number, as the reference reads it.  Only NaN is missing, not +-inf.
         self.missing_data = False
+        # known measurement variances on top of sigma^2 (see "Measurement noise"): (H,) / (U,) or (U, K), None = zeros
+        self.b_noise_var = None
+        self.bt_noise_var = None
 
         self._ctx = None
         self._query_ctx = None    # score(), log_evidence(), membership(): one context apart from the fit's (_query_context)
@@ -195,6 +211,60 @@ class UnsharedRegionFit(object):
         if self._has_sessions() and (self.update_theta_sub or self.theta_sub_every):
             raise NotImplementedError("the theta_sub step (update_theta_sub / theta_sub_every, either theta_sub_params) is not "
                                       "provided for sessions data bt (C, U, K): its objective kernels read one scan per patient")
+
+    def _has_noise(self):
+        return self.b_noise_var is not None or self.bt_noise_var is not None
+
+    def _refuse_theta_sub_noise(self):
+        """The theta_sub objectives know one sigma per state: an objective that separates sigma from the variances is not made."""
+        if self._has_noise() and (self.update_theta_sub or self.theta_sub_every):
+            raise NotImplementedError("the theta_sub step (update_theta_sub / theta_sub_every, either theta_sub_params) is not "
+                                      "provided with noise variances (b_noise_var / bt_noise_var): its objective kernels take "
+                                      "one sigma per state")
+
+    @staticmethod
+    def _noise_array(v, shapes, name):
+        a = np.ascontiguousarray(v, dtype=np.float64)
+        if a.shape not in shapes:
+            raise ValueError("noise: %s must have shape %s, got %s" % (name, " or ".join(str(x) for x in shapes), a.shape))
+        if not np.all(np.isfinite(a)) or np.any(a < 0):
+            raise ValueError("noise: %s must be finite and >= 0 (to drop a subject give NaN data under missing_data, not an "
+                             "infinite variance)" % name)
+        return a
+
+    _OWN = object()          # _noise_host(bt_var=...): the fit's own bt_noise_var
+
+    def _noise_host(self, bt_shape=None, bt_var=_OWN, name="bt_noise_var"):
+        """
+        None without noise variances, else (var_b (H,) or None, var_bt (U, K) or None) as checked float64 arrays; a (U,)
+        is repeated over the sessions.  Host only: ValueError naming "noise" for a wrong shape, a negative, NaN or inf.
+        bt_shape / bt_var: the patients of a query (score()) in place of the fit's own.
+        """
+        bt_var = self.bt_noise_var if bt_var is UnsharedRegionFit._OWN else bt_var
+        if self.b_noise_var is None and bt_var is None:
+            return None
+        shp = tuple(np.shape(self.bt)) if bt_shape is None else tuple(bt_shape)
+        (U, K) = (int(shp[1]), int(shp[2]) if len(shp) == 3 else 1)
+        vb = vbt = None
+        if self.b_noise_var is not None:
+            vb = self._noise_array(self.b_noise_var, ((int(np.shape(self.b)[1]),),), "b_noise_var")
+        if bt_var is not None:
+            vbt = self._noise_array(bt_var, ((U,), (U, K)), name)
+            if vbt.ndim == 1:
+                vbt = np.ascontiguousarray(np.repeat(vbt[:, None], K, axis=1))
+        return (vb, vbt)
+
+    def _noise_dev(self):
+        """The device copies of _noise_host() (None without noise variances), made again whenever the host values change."""
+        host = self._noise_host()
+        if host is None:
+            return None
+        key = tuple(None if a is None else (a.shape, a.tobytes()) for a in host)
+        cur = self._d.get("noise")
+        if cur is None or cur[0] != key:
+            cur = (key, tuple(None if a is None else self._up(a) for a in host))
+            self._d["noise"] = cur
+        return cur[1]
 
     def _require_fitted(self, what):
         """ValueError unless run() has left a fit of self.method behind: a sampler (gibbs), or q_F and an energy (vb)."""
@@ -311,6 +381,8 @@ class UnsharedRegionFit(object):
     def _p_Bt_g_Ft(self):
         if self._has_sessions():
             raise ValueError("_p_Bt_g_Ft is not made for sessions data bt (C, U, K): a product of densities underflows")
+        if self._has_noise():
+            raise ValueError("_p_Bt_g_Ft is not made with noise variances: the noise tables are log-form only")
         if self._d.get("pBt") is None and self.bt is not None and self.model is not None and "lM" in self._d:
             self._tables(full=True)
         return self._get("pBt")
@@ -323,6 +395,7 @@ class UnsharedRegionFit(object):
     def run(self):
         """Runs the fitting procedure (fcdiff/fit.py:56-82; doc/methods.rst:564-600)."""
         self._refuse_theta_sub_sessions()
+        self._refuse_theta_sub_noise()
         (C, H) = self.b.shape
         if np.ndim(self.bt) not in (2, 3) or (np.ndim(self.bt) == 3 and np.shape(self.bt)[2] < 1):
             raise ValueError("bt must be (C, U) or (C, U, K) with K >= 1 sessions, got shape %s" % (np.shape(self.bt),))
@@ -334,6 +407,7 @@ class UnsharedRegionFit(object):
         if self.model is None:
             msg = "Model has not been initialized."
             raise ValueError(msg)
+        self._noise_host()               # (a ValueError for bad noise variances before any context exists)
         N = int(N)
         self._init_lps(N, H, U)
         self._update_lps()
@@ -375,6 +449,7 @@ class UnsharedRegionFit(object):
 
     def _tables(self, full):
         """S_B and lM (full: the per-item tables lpB, pBt too, where the model has them) in ONE launch: tables.build."""
+        self._noise_host()               # (a ValueError for bad noise variances before any context exists)
         t = self._torch()
         dev = self._dev()
         b = np.ascontiguousarray(self.b, dtype=np.float64)
@@ -402,7 +477,7 @@ class UnsharedRegionFit(object):
         lpB = pBt = None
         if full and not self._shared:
             lpB = t.empty((C, H, 3), dtype=t.float64, device=dev)
-            if bt.ndim == 2:                 # (sessions: no per-item product of densities, see _p_Bt_g_Ft)
+            if bt.ndim == 2 and not self._has_noise():       # (sessions, noise: no per-item densities, see _p_Bt_g_Ft)
                 pBt = t.empty((C, U, 3), dtype=t.float64, device=dev)
         n_missing = None
         if self.missing_data:
@@ -415,12 +490,22 @@ class UnsharedRegionFit(object):
                 n_missing = self._d["n_missing"]
         (self._d["S_B"], self._d["lM"]) = tables.build(self._context(), self._d["b"], self._d["bt"], self.model.theta(),
                                                        self._flags(), shared=self._shared, S_B=S_B, lM=lM, lpB=lpB, pBt=pBt,
-                                                       n_missing=n_missing)
+                                                       n_missing=n_missing, **self._noise_kw())
         self._d["n_missing_valid"] = bool(self.missing_data)
         self._d["lpB"], self._d["pBt"] = lpB, pBt
 
     def _flags(self):
         return _lib.FCD_DATA_NAN_MISSING if self.missing_data else 0
+
+    def _noise_kw(self):
+        """{} without noise variances (tables.build is then called as before, argument for argument), else its `noise`."""
+        noise = self._noise_dev()
+        return {} if noise is None else {"noise": noise}
+
+    def _noise_bt_kw(self):
+        """conn_posterior()'s `noise_var` of the fit's own patients: {} where bt_noise_var is None."""
+        noise = self._noise_dev()
+        return {} if noise is None or noise[1] is None else {"noise_var": noise[1]}
 
     def missing_counts(self):
         """
@@ -590,7 +675,7 @@ class UnsharedRegionFit(object):
 
     def _update_theta_sub(self):
         """
-        Not provided for sessions data bt (C, U, K): NotImplementedError before anything is launched.
+        Not provided for sessions data bt (C, U, K) nor with noise variances: NotImplementedError before anything is launched.
 
         Updates (eta, epsilon) (fit.py:222-241): bounded minimisation of -E_lM with the other terms fixed, bounds
         (1e-5, 1 - 1e-5) on both, L-BFGS-B.  The reference's version cannot run (it calls the undefined `opt_fun`,
@@ -603,6 +688,9 @@ class UnsharedRegionFit(object):
         if self._has_sessions():
             raise NotImplementedError("the theta_sub step is not provided for sessions data bt (C, U, K): its objective "
                                       "kernels read one scan per patient")
+        if self._has_noise():
+            raise NotImplementedError("the theta_sub step is not provided with noise variances (b_noise_var / bt_noise_var): "
+                                      "its objective kernels take one sigma per state")
         W = self._theta_sub_weights()
         if self.theta_sub_params == "all":
             # the reference's commented-out intent (fit.py:232-237, 250-251, 266-267, 282): mu and sigma too
@@ -787,12 +875,12 @@ class UnsharedRegionFit(object):
             (counts, N, C) = self._connection_counts_dev()
             U = int(counts.shape[1])
             return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), counts=counts,
-                                  missing_data=self.missing_data)
+                                  missing_data=self.missing_data, **self._noise_bt_kw())
         if self.method != "vb":
             raise ValueError("method must be 'vb' or 'gibbs'")
         (N, C, U) = self._check_state(need=("lq_R", "lq_F"))
         return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), lq_F=self._d["lq_F"],
-                              lq_R=self._d["lq_R"], missing_data=self.missing_data)
+                              lq_R=self._d["lq_R"], missing_data=self.missing_data, **self._noise_bt_kw())
 
     # ------------------------------------------------------------------ anomalous-region counts
     def anomaly_count_posterior(self):
@@ -928,7 +1016,8 @@ class UnsharedRegionFit(object):
         return out
 
     # ------------------------------------------------------------------ scoring new patients
-    def score(self, bt_new, *, connections=False, max_iters=100, tol=1e-8, n_anneal=200, n_sweeps=50, seed=None):
+    def score(self, bt_new, *, connections=False, max_iters=100, tol=1e-8, n_anneal=200, n_sweeps=50, seed=None,
+              noise_var=None):
         """
         Scores patients who were not in the fit: their anomaly maps and a per-patient likelihood measure, with the fitted
         template and theta held fixed.  Scoring is NOT a refit: the new patients never update the template F, q_F, the
@@ -937,6 +1026,9 @@ class UnsharedRegionFit(object):
 
         bt_new (C, U') correlations of the new patients in the fit's edge order (NaN = unobserved when missing_data), or
         (C, U', K') with K' sessions of every new patient; K' need not be the fit's n_sessions.
+        noise_var (U',) or (U', K'): the new patients' measurement variances (see "Measurement noise"; a (U',) applies to
+        every session).  A fit with noise variances refuses noise_var=None (ValueError): the caller says what the new
+        patients' are, zeros included.  The control side keeps the fit's b_noise_var.
         theta is the model's CURRENT parameters, the plug-in convention of connection_posterior().  Given F and theta the
         patients are independent (doc/methods.rst): with method='vb' a new patient's numbers are exactly those it gets when
         scored alone; with method='gibbs' they have the same law (the random numbers of a site follow its column index).
@@ -986,15 +1078,20 @@ class UnsharedRegionFit(object):
                 raise ValueError("score() tallies would overflow uint32: %d chains x %d sweeps" % (self.sampler.G, n_sweeps))
         elif int(max_iters) < 1:
             raise ValueError("max_iters must be >= 1")
+        if self._has_noise() and noise_var is None:
+            raise ValueError("score(): the fit has noise variances, so the new patients' noise_var must be given (zeros are allowed)")
+        noise = self._noise_host(bt_shape=bt_new.shape, bt_var=noise_var, name="noise_var")
         ctx = self._query_context()
         b_dev = self._data_dev("b")
         bt_dev = self._up(bt_new)
+        if noise is not None:
+            noise = tuple(None if a is None else self._up(a) for a in noise)
         if self.method == "vb":
             return _score.score_vb(ctx, b_dev, bt_dev, N, self._d["lq_F"], self.model, self._pi2(), self._edge_mode(),
-                                   self.missing_data, connections, max_iters, float(tol))
+                                   self.missing_data, connections, max_iters, float(tol), noise=noise)
         key = _score.score_key(self.seed if seed is None else seed)
         out = _score.score_gibbs(ctx, b_dev, bt_dev, N, self.sampler, self.model, self._pi2(), self.missing_data, connections,
-                                 int(n_anneal), int(n_sweeps), key)
+                                 int(n_anneal), int(n_sweeps), key, noise=noise)
         return out
 
     # ------------------------------------------------------------------ patient or control
@@ -1023,15 +1120,21 @@ class UnsharedRegionFit(object):
         and n_chains, the number of chains pooled.  log_patient is score()'s log_pred of the same subjects.
         The cohort is walked in chunks (membership.CHUNK subjects): apart from a chunk's buffers, device memory does not grow
         with U'.  Raises ValueError before run(), for method='vb', for a wrong C, a non-2-D input and for edge_index other than
-        'symmetric'.
+        'symmetric'; NotImplementedError for a fit with noise variances.
         """
         from . import membership as _membership
+        self._refuse_membership_noise()
         (x_new, N) = self._membership_input(x_new)
         if int(n_anneal) < 1:
             raise ValueError("n_anneal must be >= 1")
         key = _score.score_key(self.seed if seed is None else seed)
         return _membership.membership(self._query_context(), self._up, x_new, N, self.sampler, self.model, self.missing_data,
                                       False, b_dev=self._data_dev("b"), pi2=self._pi2(), n_anneal=int(n_anneal), key=key)
+
+    def _refuse_membership_noise(self):
+        if self._has_noise():
+            raise NotImplementedError("membership() is not provided with noise variances (b_noise_var / bt_noise_var): its "
+                                      "kernels take one sigma per state")
 
     def _membership_input(self, x_new):
         """The checks of membership(), before anything touches the device: (x_new (C, U') float64, Nreg)."""
@@ -1108,7 +1211,7 @@ class UnsharedRegionFit(object):
         ctx = self._query_context()
         # fresh tables of the current theta on the query context: the fit's own are not touched
         (S_B, lM) = tables.build(ctx, self._data_dev("b"), self._data_dev("bt"), self.model.theta(), self._flags(),
-                                 shared=self._shared)
+                                 shared=self._shared, **self._noise_kw())
         (C, U) = (int(lM.shape[0]), int(lM.shape[1]))
         key = _evidence.evidence_key(self.seed if seed is None else seed)
         return _evidence.log_evidence(ctx, S_B, lM, int(util.C_to_N(C)), U, self.model.gamma, self._pi2(), int(n_anneal), int(G),
@@ -1189,13 +1292,13 @@ class SharedRegionFit(UnsharedRegionFit):
             (counts, N, C) = self._connection_counts_dev()
             counts = counts.expand(C, U, 3, 3).contiguous()
             return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), counts=counts,
-                                  missing_data=self.missing_data)
+                                  missing_data=self.missing_data, **self._noise_bt_kw())
         if self.method != "vb":
             raise ValueError("method must be 'vb' or 'gibbs'")
         (N, C, _one) = self._check_state(need=("lq_R", "lq_F"))
         lq_R = self._d["lq_R"].expand(N, U, 2).contiguous()
         return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), lq_F=self._d["lq_F"],
-                              lq_R=lq_R, missing_data=self.missing_data)
+                              lq_R=lq_R, missing_data=self.missing_data, **self._noise_bt_kw())
 
     def anomaly_count_posterior(self):
         """
@@ -1248,6 +1351,7 @@ class SharedRegionFit(UnsharedRegionFit):
         One kernel (fcd_member_loglik) gives both sides straight from x_new: no (C, U', 3, 3) table is made.
         """
         from . import membership as _membership
+        self._refuse_membership_noise()
         (x_new, N) = self._membership_input(x_new)
         return _membership.membership(self._query_context(), self._up, x_new, N, self.sampler, self.model,
                                       self.missing_data, True)
@@ -1330,12 +1434,14 @@ def coanomaly_from_counts(region_pair_counts, patient_pair_counts, states):
             "p_patient_pair": pp / (float(states) * N), "expected_regions": pp / float(states)}
 
 
-def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=None, missing_data=False):
+def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=None, missing_data=False, noise_var=None):
     """
     {p_T (C,U), p_F_tilde (C,U,3), p_changed (C,U)} as NumPy float64 through fcd_conn_posterior: weights from `counts`
     (C,U,3,3) uint32 (held in an int32 tensor), or from the log-probabilities lq_F (C,1,3) and lq_R (Nreg,U,2).
     missing_data: a NaN of bt is unobserved (fcd_conn_posterior_ex with FCD_DATA_NAN_MISSING).
     bt_dev (C, U, K): K sessions per patient (fcd_conn_posterior_sessions); an item with no observed session gets the prior law.
+    noise_var: float64 device tensor (U, K) ((U,) or (U, 1) for a 2-D bt) of known measurement variances on top of sigma^2
+    (fcd_conn_posterior_noise, for a bt of either rank); None: none.
     """
     import torch
     C = util.N_to_C(int(Nreg))
@@ -1354,8 +1460,15 @@ def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=Non
     p_ch = torch.empty((C, U), dtype=torch.float64, device=dev)
     (th, _th) = _lib.dbl_array(theta)
     sessions = () if bt_dev.dim() == 2 else (int(bt_dev.shape[2]),)
-    ctx.call("fcd_conn_posterior_sessions" if sessions else "fcd_conn_posterior_ex", _lib.dptr(bt_dev.contiguous()), int(Nreg),
-             int(U), *sessions, th, _lib.dptr(None if counts is None else counts.contiguous()),
+    name = "fcd_conn_posterior_sessions" if sessions else "fcd_conn_posterior_ex"
+    noise = ()
+    if noise_var is not None:
+        K = sessions[0] if sessions else 1
+        if noise_var.dtype != torch.float64 or tuple(noise_var.shape) not in ((U, K),) + (() if sessions else ((U,),)):
+            raise ValueError("noise_var must be float64 (U, K) = %s" % ((U, K),))
+        (name, sessions, noise) = ("fcd_conn_posterior_noise", (K,), (_lib.dptr(noise_var.contiguous()),))
+    ctx.call(name, _lib.dptr(bt_dev.contiguous()), int(Nreg),
+             int(U), *sessions, th, *noise, _lib.dptr(None if counts is None else counts.contiguous()),
              _lib.dptr(None if lq_F is None else lq_F.contiguous()), _lib.dptr(None if lq_R is None else lq_R.contiguous()),
              _lib.FCD_DATA_NAN_MISSING if missing_data else 0, _lib.dptr(p_T), _lib.dptr(p_Ft), _lib.dptr(p_ch),
              _lib.stream_ptr())

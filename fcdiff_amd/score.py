@@ -103,10 +103,11 @@ def gather_rows(t):
     return np.stack([y.cpu().numpy() for y in lst])
 
 
-def lik_tables(ctx, b_dev, bt_dev, theta, missing_data):
+def lik_tables(ctx, b_dev, bt_dev, theta, missing_data, noise=None):
     """(S_B (C, 3), lM (C, U', 3, 3)) of new patients bt_dev (C, U') or (C, U', K') into fresh tensors (the table kernel needs
-    H >= 1: b is the fit's)."""
-    return tables.build(ctx, b_dev, bt_dev, theta, _lib.FCD_DATA_NAN_MISSING if missing_data else 0)
+    H >= 1: b is the fit's).  noise: tables.build's (the controls' variances of the fit, the new patients' own), or None."""
+    kw = {} if noise is None else {"noise": noise}
+    return tables.build(ctx, b_dev, bt_dev, theta, _lib.FCD_DATA_NAN_MISSING if missing_data else 0, **kw)
 
 
 def hyper_block(ctx, gamma, pi2, device):
@@ -135,13 +136,13 @@ def patient_elbo(ctx, lq_F, lq_R, lM, hyper, Nreg, U):
     return out.cpu().numpy()
 
 
-def score_vb(ctx, b_dev, bt_dev, Nreg, lq_F, model, pi2, edge_mode, missing_data, connections, max_iters, tol):
+def score_vb(ctx, b_dev, bt_dev, Nreg, lq_F, model, pi2, edge_mode, missing_data, connections, max_iters, tol, noise=None):
     """The variational path of UnsharedRegionFit.score (see there); lq_F is the fit's, read only."""
     import torch
     from .fit import count_posterior, conn_posterior
     U = int(bt_dev.shape[1])
     theta = model.theta()
-    (_S_B, lM) = lik_tables(ctx, b_dev, bt_dev, theta, missing_data)
+    (_S_B, lM) = lik_tables(ctx, b_dev, bt_dev, theta, missing_data, noise)
     hyper = hyper_block(ctx, model.gamma, pi2, bt_dev.device)
     lq_R = torch.full((Nreg, U, 2), -np.log(2), dtype=torch.float64, device=bt_dev.device)      # uniform, as _init_lps
     # Each patient stops on its own: its q_R is taken at the first iteration where its own max_n |delta q| < tol.  The update
@@ -171,11 +172,12 @@ def score_vb(ctx, b_dev, bt_dev, Nreg, lq_F, model, pi2, edge_mode, missing_data
     out = {"p_R": np.exp(lq_R[:, :, 1].cpu().numpy()), "p_patient_count": p_patient, "p_patient_any": 1.0 - p_patient[:, 0],
            "elbo": terms[:, 3].copy(), "iters": iters, "converged": converged}
     if connections:
-        out.update(conn_posterior(ctx, bt_dev, Nreg, U, theta, lq_F=lq_F, lq_R=lq_R, missing_data=missing_data))
+        out.update(conn_posterior(ctx, bt_dev, Nreg, U, theta, lq_F=lq_F, lq_R=lq_R, missing_data=missing_data,
+                                  noise_var=None if noise is None else noise[1]))
     return out
 
 
-def ais_weights(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, n_anneal, key):
+def ais_weights(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, n_anneal, key, noise=None):
     """
     The annealing ladder over r with each chain's template f_g (the end state of `sampler`, read only) held: r from the prior,
     then per rung one fcd_score_ais_step and one r pass on the tempered table.  Returns (eng, lM, region_tables, w, sweep):
@@ -187,7 +189,7 @@ def ais_weights(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, n_a
     U = int(bt_dev.shape[1])
     G = sampler.G
     theta = model.theta()
-    (S_B, lM) = lik_tables(ctx, b_dev, bt_dev, theta, missing_data)
+    (S_B, lM) = lik_tables(ctx, b_dev, bt_dev, theta, missing_data, noise)
     lMw = lM.clone()                         # the working (tempered) table the r pass reads
     # (built without its tables: no f pass runs while scoring, so the f pass's edge tables are never made; the r pass's
     # region-major table is made here when the fit's sampler had one, and after every rung of the ladder below)
@@ -215,7 +217,8 @@ def ais_weights(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, n_a
     return eng, lM, region_tables, w, sweep
 
 
-def score_gibbs(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, connections, n_anneal, n_sweeps, key):
+def score_gibbs(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, connections, n_anneal, n_sweeps, key,
+                noise=None):
     """The sampler path of UnsharedRegionFit.score (see there); `sampler` is the fit's engine, read only (its f_state)."""
     import torch
     from .fit import conn_posterior
@@ -223,7 +226,8 @@ def score_gibbs(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, con
     C = util.N_to_C(int(Nreg))
     G = sampler.G
     theta = model.theta()
-    (eng, lM, region_tables, w, sweep) = ais_weights(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, n_anneal, key)
+    (eng, lM, region_tables, w, sweep) = ais_weights(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, n_anneal, key,
+                                                       noise)
     # beta = 1: the untempered table (bit for bit what the last AIS step wrote) and its region-major difference table
     eng.lM = lM
     region_tables(lM)
@@ -254,5 +258,6 @@ def score_gibbs(ctx, b_dev, bt_dev, Nreg, sampler, model, pi2, missing_data, con
             raise ValueError("pooled connection counts exceed uint32: fewer sweeps or chains")
         out["connection_counts"] = pc
         counts = torch.as_tensor(np.ascontiguousarray(pc.astype(np.uint32).view(np.int32)), device=bt_dev.device)
-        out.update(conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=counts, missing_data=missing_data))
+        out.update(conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=counts, missing_data=missing_data,
+                                  noise_var=None if noise is None else noise[1]))
     return out

@@ -8,8 +8,12 @@ import numpy as np
 
 from . import _lib
 
+# fcd_lik_noise.hip's FCD_NOISE_LDS_RECORDS: up to this many per-subject records (max(H, U K)) the noise tables keep them in
+# LDS, above it they are read from global memory.  Tests build on both sides of it.
+NOISE_LDS_RECORDS = 768
 
-def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB=None, pBt=None, n_missing=None):
+
+def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB=None, pBt=None, n_missing=None, noise=None):
     """
     (S_B (C, 3), lM) of b_dev (C, H) and bt_dev (C, U) at theta, in ONE library call on `ctx`:
       shared=False  fcd_lik_tables_ex: lM (C, U, 3, 3) and, where given, the per-item tables lpB (C, H, 3), pBt (C, U, 3);
@@ -21,6 +25,10 @@ def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB
     allocated where not.  flags: 0 or _lib.FCD_DATA_NAN_MISSING; with flags = 0 and n_missing = None the unshared call is
     the plain fcd_lik_tables, argument for argument.  n_missing: (2,) int64 device tensor the kernel adds the NaN counts of
     b and bt to (a counting build waits for its atomics), or None.
+    noise: None, or (var_b_dev, var_bt_dev): known measurement variances on top of sigma^2, float64 device tensors (H,) and
+    (U,) / (U, K) matching bt_dev, either of them None for all zeros.  It selects fcd_lik_tables_noise /
+    fcd_lik_shared_tables_noise for a bt of either rank (a 2-D bt is K = 1); pBt is refused (ValueError), as with sessions.
+    The values are the caller's to check (finite, >= 0): nothing here reads them.
     """
     import torch
     (C, H) = (int(b_dev.shape[0]), int(b_dev.shape[1]))
@@ -37,7 +45,25 @@ def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB
     if lM is None:
         lM = torch.empty((C, 1 if shared else U, 3, 3), dtype=torch.float64, device=bt_dev.device)
     (th, _th) = _lib.dbl_array(theta)
-    if K is not None:
+    if noise is not None:
+        if pBt is not None:
+            raise ValueError("p_Bt_g_Ft is not made with noise variances: the noise tables are log-form only")
+        (var_b, var_bt) = noise
+        Kn = 1 if K is None else K
+        if var_b is not None and (tuple(var_b.shape) != (H,) or var_b.dtype != torch.float64):
+            raise ValueError("noise: var_b must be float64 (H,) = %s" % ((H,),))
+        if var_bt is not None and (var_bt.dtype != torch.float64 or tuple(var_bt.shape) not in ((U, Kn),) + (((U,),) if K is None else ())):
+            raise ValueError("noise: var_bt must be float64 (U, K) = %s" % ((U, Kn),))
+        (bt_dev, var_b, var_bt) = (bt_dev.contiguous(), None if var_b is None else var_b.contiguous(),
+                                   None if var_bt is None else var_bt.contiguous())
+        if shared:
+            ctx.call("fcd_lik_shared_tables_noise", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, Kn, th, _lib.dptr(var_b),
+                     _lib.dptr(var_bt), _lib.dptr(S_B), _lib.dptr(lM), int(flags), _lib.dptr(n_missing), _lib.stream_ptr())
+        else:
+            ctx.call("fcd_lik_tables_noise", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, Kn, th, _lib.dptr(var_b),
+                     _lib.dptr(var_bt), _lib.dptr(S_B), _lib.dptr(lM), _lib.dptr(lpB), int(flags), _lib.dptr(n_missing),
+                     _lib.stream_ptr())
+    elif K is not None:
         bt_dev = bt_dev.contiguous()
         if shared:
             ctx.call("fcd_lik_shared_tables_sessions", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, K, th, _lib.dptr(S_B),

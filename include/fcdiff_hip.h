@@ -236,6 +236,36 @@ int fcd_conn_posterior_sessions(fcd_ctx *ctx, const double *bt, int64_t Nreg, in
                                 const double *theta12_host, const uint32_t *counts, const double *lq_F, const double *lq_R,
                                 int flags, double *p_T, double *p_F_tilde, double *p_changed, fcd_stream stream);
 
+/* ---- per-subject measurement noise: known sampling variances on top of the population spread --------------------------
+ * Every control h and every session k of every patient u may carry a known variance v >= 0 (the sampling variance of its
+ * correlations, e.g. from the number of frames kept):
+ *   b_ch   | F_c = k   ~ N(mu_k, sigma_k^2 + var_b[h])
+ *   bt_cuk | F~_cu = j ~ N(mu_j, sigma_j^2 + var_bt[u*K + k])      (sessions conditionally independent, as above)
+ * sigma is then the population spread alone.  var_b is H doubles and var_bt U*K doubles (session fastest), both DEVICE
+ * pointers; NULL means all zeros, and all zeros is the model of the sessions entry points.  bt is (C, U, K) as above, K = 1
+ * for one scan per patient.  The tables are the sessions tables in log form with s_juk = sqrt(sigma_j^2 + var_bt[u,k]) in
+ * place of sigma_j:  a_j = sum_k [-z^2/2 - (ln s_juk + ln sqrt(2 pi))], z = (x - mu_j)/s_juk, lM = m + ln M_kl(exp(a - m)).
+ * A NaN entry adds exactly 0.0 under FCD_DATA_NAN_MISSING whatever its variance, an item with no observed session is 0.0,
+ * m = -inf gives -inf; the NaN counts are those of the sessions entry points.  1/s and ln s + ln sqrt(2 pi) are made once
+ * per call into a block the context owns (one small launch) and looked up per item: no division, square root or logarithm
+ * per session.  Variances are not checked on the device: the caller passes finite values >= 0.
+ *
+ * fcd_lik_tables_noise: S_B (C,3), lM (C,U,3,3), lp_B_g_F (C,H,3; may be NULL).  With var_b NULL, S_B and lp_B_g_F equal
+ * fcd_lik_tables_ex's bit for bit.
+ * fcd_lik_shared_tables_noise: S_B and L (C,3,3) = sum_u lM[c,u]; the per-patient table is never written.
+ * fcd_conn_posterior_noise: fcd_conn_posterior_sessions with the densities of these variances.
+ * Refusals as the sessions entry points: K < 1 FCD_ERR_ARG, non-triangular C FCD_ERR_SHAPE, K > INT32_MAX or
+ * U*K > 2^31 FCD_ERR_UNSUPPORTED, unknown flags FCD_ERR_ARG. */
+int fcd_lik_tables_noise(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U, int64_t K,
+                         const double *theta12_host, const double *var_b, const double *var_bt, double *S_B, double *lM,
+                         double *lp_B_g_F, int flags, int64_t *n_missing2, fcd_stream stream);
+int fcd_lik_shared_tables_noise(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U, int64_t K,
+                                const double *theta12_host, const double *var_b, const double *var_bt, double *S_B,
+                                double *L, int flags, int64_t *nan_counts, fcd_stream stream);
+int fcd_conn_posterior_noise(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, int64_t K, const double *theta12_host,
+                             const double *var_bt, const uint32_t *counts, const double *lq_F, const double *lq_R,
+                             int flags, double *p_T, double *p_F_tilde, double *p_changed, fcd_stream stream);
+
 /* ---- forward sampler: UnsharedRegionModel.sample, fcdiff/model.py:52-236, on the device ---------------
  * Counter RNG (Philox), all variables drawn in parallel; the reference's MT19937 stream is not reproduced (the host
  * sampler of the Python mirror does that) -- same distribution.  Type INDICES are returned: r (Nreg,U), t (C,U),
