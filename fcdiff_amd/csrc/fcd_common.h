@@ -90,7 +90,7 @@ struct fcd_ctx {
     size_t fsq_bytes;
     void *frec;        // pair records and edge constants of the pair-tile f pass (fcd_sweep_plan::frec_bytes), valid inside ONE
     size_t frec_bytes; // sweep-loop call: it makes them from that call's lMf before the first pass that reads them
-    void *noise_rec;   // per-subject constants of the measurement-noise tables (fcd_lik_noise.hip), valid inside ONE call:
+    void *noise_rec;   // per-subject constants of the measurement-noise tables (fcd_lik_sessions.hip), valid inside ONE call:
     size_t noise_rec_bytes;        // six doubles per control and per patient session, made by that call's first launch
     fcd_sweep_acc sweep_acc[FCD_ACC_N];
     void *count_ws;                // per-chain counts of one tally, (U + Nreg) rows of GW*64 uint16 (fcd_count_ws_reserve)

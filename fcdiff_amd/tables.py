@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 
-# fcd_lik_noise.hip's FCD_NOISE_LDS_RECORDS: up to this many per-subject records (max(H, U K)) the noise tables keep them in
+# fcd_lik_sessions.hip's FCD_NOISE_LDS_RECORDS: up to this many per-subject records (max(H, U K)) the noise tables keep them in
 # LDS, above it they are read from global memory.  Tests build on both sides of it.
 NOISE_LDS_RECORDS = 768
 

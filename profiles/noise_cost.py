@@ -1,5 +1,5 @@
 """
-Cost of the measurement-noise tables (fcd_lik_noise.hip) on one MI355X, at cfg3's shape (Nreg 200, H = U = 50).
+Cost of the measurement-noise tables (fcd_lik_sessions.hip) on one MI355X, at cfg3's shape (Nreg 200, H = U = 50).
 
 In one process, after a warm-up of every variant, the variants are timed in alternation (HIP events around --launches
 back-to-back calls, --rounds rounds, best round per variant), at K = 1, 2, 4, 8:

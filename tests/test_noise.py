@@ -120,7 +120,7 @@ def test_library_exports_the_noise_entry_points():
 
 
 def test_the_record_placement_constant_is_the_kernels():
-    src = open(os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc", "fcd_lik_noise.hip")).read()
+    src = open(os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc", "fcd_lik_sessions.hip")).read()
     m = re.search(r"#define\s+FCD_NOISE_LDS_RECORDS\s+(\d+)", src)
     assert m and int(m.group(1)) == tables.NOISE_LDS_RECORDS
 
