@@ -108,6 +108,9 @@ SIGNATURES = {
     "fcd_region_sets_set": (_int, [_p, _p, _p, _i64]),
     "fcd_gibbs_region_set_tally": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "fcd_gibbs_set_region_set_accumulator": (_int, [_p, _p, _p, _i64, _i64, _i64]),
+    "fcd_patient_groups_set": (_int, [_p, _p, _p, _i64, _p, _i64, _int]),
+    "fcd_gibbs_patient_group_tally": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "fcd_gibbs_set_patient_group_accumulator": (_int, [_p, _p, _p, _i64, _i64, _i64]),
     "fcd_gibbs_coanomaly_tally": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "fcd_gibbs_set_coanomaly_accumulator": (_int, [_p, _p, _p, _i64, _i64, _i64]),
     "fcd_vb_coanomaly": (_int, [_p, _p, _i64, _i64, _p, _p, _p]),

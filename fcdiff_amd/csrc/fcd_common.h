@@ -49,8 +49,9 @@ enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA
 // (C, U, 3, 3) counts of (f_c, mixture case) (fcd_gibbs_set_pair_accumulator; one buffer, held in both places), (U, Nreg+1) /
 // (Nreg, U+1) histograms of the anomalous-region counts (fcd_gibbs_set_count_accumulator), (Nreg, Nreg) / (U, U) co-anomaly
 // counts (fcd_gibbs_set_coanomaly_accumulator), (J, U, S_max+1) / (J, U+1) histograms of the counts over the context's region
-// sets (fcd_gibbs_set_region_set_accumulator).  fcd_gibbs.hip holds the launch of each.
-enum { FCD_ACC_PAIR, FCD_ACC_COUNT, FCD_ACC_COANOMALY, FCD_ACC_REGION_SET, FCD_ACC_N };
+// sets (fcd_gibbs_set_region_set_accumulator), (J, R, Umax+1) / flat joint histograms of the counts over the context's patient
+// groups and contrasts (fcd_gibbs_set_patient_group_accumulator).  fcd_gibbs.hip holds the launch of each.
+enum { FCD_ACC_PAIR, FCD_ACC_COUNT, FCD_ACC_COANOMALY, FCD_ACC_REGION_SET, FCD_ACC_PATIENT_GROUP, FCD_ACC_N };
 struct fcd_sweep_acc {
     uint32_t *buf[2];              // buf[0] == nullptr: detached
     int64_t nreg, u, every;        // the shape it was made for; added at every this many sweeps from accumulate_from on
@@ -98,6 +99,12 @@ struct fcd_ctx {
     // region sets (fcd_region_sets_set): J + 1 offsets, then the members (CSR, int32, device; owned), checked on the host
     void *rs_dev;
     int64_t rs_J, rs_smax, rs_max_member;      // number of sets (0: none), largest set, largest member
+    // patient groups and contrasts (fcd_patient_groups_set): one device buffer (owned; layout in fcd_patient_groups.hip) of the
+    // CSR, the contrasts, a bit mask over u per group and the contrasts' bin offsets, checked on the host
+    void *pg_dev;
+    int64_t pg_J, pg_P, pg_umax, pg_max_member;        // groups (0: none), contrasts, largest group, largest member
+    int64_t pg_total, pg_bins_max;                     // members in all groups; joint bins of the largest contrast
+    int pg_with_rs;                                    // 1: the context's region sets are rows after the regions
     // optional per-kernel timing with HIP events on the launch stream (fcd_prof_enable / fcd_prof_collect)
     int prof_on;
     hipEvent_t *prof_ev[FCD_PROF_SLOTS];   // pairs (begin, end)
@@ -189,6 +196,7 @@ int fcd_pair_tally_launch(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *
 // the anomalous-region count kernels of fcd_count.hip (two launches): both histograms += the counts of this state; the
 // scratch they need is grown by fcd_count_ws_reserve (fcd_gibbs_run: before its sweep loop)
 int fcd_count_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
+int fcd_count_ws_grow(fcd_ctx *ctx, size_t bytes);      // ... and by the tallies that share it: at least this many bytes
 int fcd_count_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
                            uint32_t *hist_patient, uint32_t *hist_region, hipStream_t s);
 // the co-anomaly kernel of fcd_coanomaly.hip (one launch, no scratch): both pair matrices += the counts of this state
@@ -199,6 +207,11 @@ int fcd_coanomaly_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nre
 int fcd_region_set_ws_reserve(fcd_ctx *ctx, int64_t U, int64_t G);
 int fcd_region_set_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
                                 uint32_t *hist_set, uint32_t *hist_prev, hipStream_t s);
+// the patient-group kernels of fcd_patient_groups.hip (two launches): both histograms += the counts of this state over the
+// context's groups and contrasts; same scratch, grown by fcd_patient_group_ws_reserve (fcd_gibbs_run: before its loop)
+int fcd_patient_group_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t G);
+int fcd_patient_group_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
+                                   uint32_t *hist_group, uint32_t *hist_joint, hipStream_t s);
 // bracket ONE kernel launch with events when profiling is on (no-ops otherwise)
 void fcd_prof_begin(fcd_ctx *ctx, int slot, hipStream_t s);
 void fcd_prof_end(fcd_ctx *ctx, int slot, hipStream_t s);

@@ -172,8 +172,7 @@ __global__ __launch_bounds__(PB_THREADS) void poisson_binomial_kernel(const doub
 
 }  // namespace
 
-int fcd_count_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G) {
-    const size_t bytes = (size_t)(Nreg + U) * (size_t)((G + 63) / 64) * 64 * sizeof(uint16_t);
+int fcd_count_ws_grow(fcd_ctx *ctx, size_t bytes) {
     if (bytes <= ctx->count_ws_bytes) return FCD_OK;
     FCD_HIP_TRY(hipDeviceSynchronize());
     if (ctx->count_ws) FCD_HIP_TRY(hipFree(ctx->count_ws));
@@ -183,6 +182,10 @@ int fcd_count_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G) {
     ctx->count_ws_bytes = bytes;
     ctx->n_alloc += 1;
     return FCD_OK;
+}
+
+int fcd_count_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G) {
+    return fcd_count_ws_grow(ctx, (size_t)(Nreg + U) * (size_t)((G + 63) / 64) * 64 * sizeof(uint16_t));
 }
 
 int fcd_count_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,

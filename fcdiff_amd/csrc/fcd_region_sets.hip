@@ -125,15 +125,7 @@ int fcd_region_set_ws_reserve(fcd_ctx *ctx, int64_t U, int64_t G) {
     const size_t bytes = scratch_bytes(ctx, U, G);
     if (bytes > RS_MAX_SCRATCH)
         return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "region sets: %lld sets x %lld patients need more than 1 GiB of scratch", ctx->rs_J, U);
-    if (bytes <= ctx->count_ws_bytes) return FCD_OK;
-    FCD_HIP_TRY(hipDeviceSynchronize());
-    if (ctx->count_ws) FCD_HIP_TRY(hipFree(ctx->count_ws));
-    ctx->count_ws = nullptr;
-    ctx->count_ws_bytes = 0;
-    FCD_HIP_TRY(hipMalloc(&ctx->count_ws, bytes));
-    ctx->count_ws_bytes = bytes;
-    ctx->n_alloc += 1;
-    return FCD_OK;
+    return fcd_count_ws_grow(ctx, bytes);
 }
 
 // (the caller has checked the sets against the shape: shape_check)
@@ -162,6 +154,8 @@ extern "C" int fcd_region_sets_set(fcd_ctx *ctx, const int32_t *offsets_host, co
     if (!ctx) return FCD_ERR_ARG;
     if (ctx->sweep_acc[FCD_ACC_REGION_SET].buf[0])
         return fcd_fail(ctx, FCD_ERR_ARG, "fcd_region_sets_set: the region-set accumulator is attached");
+    if (ctx->pg_with_rs && ctx->sweep_acc[FCD_ACC_PATIENT_GROUP].buf[0])
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_region_sets_set: the patient-group accumulator is attached with the sets as rows");
     const bool clear = J == 0 && !offsets_host && !members_host;
     int64_t smax = 0, max_member = -1, total = 0;
     if (!clear) {

@@ -24,6 +24,10 @@ New knobs (all optional; defaults reproduce the reference):
                                                                sharing anomalous regions for coanomaly_posterior()
     region_sets, region_sets_every                             gibbs: histograms of the anomalous-region counts over sets
                                                                of regions (networks) for region_set_posterior()
+    patient_groups, patient_group_contrasts, patient_groups_every
+                                                               gibbs: histograms of the number of anomalous patients per
+                                                               group of patients, and joint ones per contrast of two groups,
+                                                               for patient_group_posterior()
     missing_data                                               True: NaN entries of b / bt are unobserved and integrated out
 
 Differences from the reference that are deliberate and documented:
@@ -45,7 +49,7 @@ from . import util
 from . import score as _score
 from . import tables
 from .gibbs import (GibbsEngine, run_chains, allreduce_counts, pool_u32, pair_sweeps_in, ACCUMULATORS, PAIR_COUNT_MAX,
-                    COUNT_MAX_NREG, COUNT_MAX_U, region_sets_csr)
+                    COUNT_MAX_NREG, COUNT_MAX_U, region_sets_csr, patient_groups_csr, patient_group_contrasts)
 
 # The knobs of a gibbs fit that attach one of the sampler's accumulators: knob, its period knob, what the messages call it,
 # the row of gibbs.ACCUMULATORS, and the attributes the pooled buffers and the number of sweeps behind them are left in.
@@ -150,6 +154,17 @@ class UnsharedRegionFit(object):
         self.region_set_sweeps = 0          # number of sweeps behind those histograms
         self.region_set_names = None        # names and sizes of the sets behind them, in order
         self.region_set_sizes = None
+        self.patient_groups = None          # groups of patients for patient_group_posterior(): a dict name -> indices, a
+                                            # sequence of index sequences, or a boolean mask (J, U); gibbs: histograms over them
+        self.patient_group_contrasts = None # pairs (a, b) of names or indices of two disjoint groups: joint histograms of (k_a, k_b)
+        self.patient_groups_every = 1       # ... at every this many sweeps from burn_in on
+        self.patient_group_hist = None      # (J, R, Umax+1) int64: chains x sweeps (x ranks) with k patients of g_j anomalous at row rho
+        self.patient_group_joint_hist = None        # per contrast (R, |a|+1, |b|+1) int64: ... with (k_a, k_b) at row rho
+        self.patient_group_sweeps = 0       # number of sweeps behind those histograms
+        self.patient_group_names = None     # names and sizes of the groups behind them, the names of the R rows (the regions,
+        self.patient_group_sizes = None     # then "set:<name>" for the region sets), and the contrasts as pairs of group indices
+        self.patient_group_rows = None
+        self.patient_group_pairs = None
         # True: every NaN of b / bt is an unobserved value, integrated out exactly (S_B sums the observed h only, lM = 0 at a
         # missing bt); False: NaN is read as a number, as the reference reads it.  Only NaN is missing, not +-inf.
         self.missing_data = False
@@ -742,6 +757,13 @@ class UnsharedRegionFit(object):
             self._check_accumulator("region_sets_every", "region-set histograms")
             if U > COUNT_MAX_U:
                 raise ValueError("region-set histograms are made for at most %d patients (here %d)" % (COUNT_MAX_U, U))
+        (self.patient_group_hist, self.patient_group_joint_hist, self.patient_group_sweeps) = (None, None, 0)
+        (self.patient_group_names, self.patient_group_sizes) = (None, None)
+        (self.patient_group_rows, self.patient_group_pairs) = (None, None)
+        if self.patient_groups is not None:
+            self._refuse_patient_groups_shared()
+            patient_group_contrasts(self.patient_group_contrasts, *patient_groups_csr(self.patient_groups, U))
+            self._check_accumulator("patient_groups_every", "patient-group histograms")
         if self.anomaly_counts and (N > COUNT_MAX_NREG or U > COUNT_MAX_U):
             raise ValueError("anomaly-count histograms are made for at most %d regions and %d patients (here %d, %d)"
                              % (COUNT_MAX_NREG, COUNT_MAX_U, N, U))
@@ -753,6 +775,9 @@ class UnsharedRegionFit(object):
         if self.region_sets is not None:
             eng.set_region_sets(self.region_sets)
             eng.attach_region_set_accumulator(self.region_sets_every)
+        if self.patient_groups is not None:         # (after the region sets: they are rows of these histograms)
+            eng.set_patient_groups(self.patient_groups, self.patient_group_contrasts)
+            eng.attach_patient_group_accumulator(self.patient_groups_every)
         pi2 = self._pi2()
         eng.set_hyper(np.asarray(self.model.gamma, dtype=np.float64), pi2)
         eng.init(float(pi2[1]))
@@ -813,6 +838,16 @@ class UnsharedRegionFit(object):
             (self.region_set_hist, self.region_set_prevalence_hist) = (pool_u32(b).cpu().numpy() for b in eng.region_set_acc)
             self.region_set_sweeps = eng.region_set_sweeps
             (self.region_set_names, self.region_set_sizes) = (list(eng.region_names), np.diff(eng.region_offsets).astype(np.int64))
+        if getattr(eng, "patient_group_acc", None) is not None:
+            (hg, hj) = (pool_u32(b).cpu().numpy() for b in eng.patient_group_acc)
+            sizes = np.diff(eng.group_offsets).astype(np.int64)
+            self.patient_group_hist = hg
+            self.patient_group_joint_hist = [
+                hj[hg.shape[1] * lo:hg.shape[1] * hi].reshape(hg.shape[1], sizes[a] + 1, sizes[b] + 1)
+                for ((a, b), lo, hi) in zip(eng.group_contrasts, eng.group_bin_offsets[:-1], eng.group_bin_offsets[1:])]
+            self.patient_group_sweeps = eng.patient_group_sweeps
+            (self.patient_group_names, self.patient_group_sizes) = (list(eng.group_names), sizes)
+            (self.patient_group_rows, self.patient_group_pairs) = (eng.patient_group_row_names(), eng.group_contrasts.copy())
         if eng.coanomaly_acc is not None:
             states = t.tensor([eng.coanomaly_sweeps * eng.G], dtype=t.int64, device=eng.cnt_f.device)
             self.coanomaly_states = int(allreduce_counts(states).cpu()[0])
@@ -967,6 +1002,79 @@ class UnsharedRegionFit(object):
         k = np.arange(p_count.shape[2], dtype=np.float64)
         return {"names": names, "sizes": sizes, "p_count": p_count, "p_any": 1.0 - p_count[:, :, 0], "expected": p_count @ k,
                 "p_prevalence": p_prev, "p_none": p_prev[:, 0].copy()}
+
+    # ------------------------------------------------------------------ groups of patients and contrasts between them
+    def _refuse_patient_groups_shared(self):
+        if self._shared:
+            raise ValueError("patient_groups compare the patients' own anomaly maps; SharedRegionFit has one population-level r")
+
+    def patient_group_posterior(self, independent=False, level=0.95):
+        """
+        Is row rho anomalous more often in one group of patients than in another?  For the groups of `patient_groups` and the
+        contrasts of `patient_group_contrasts` (pairs of two disjoint groups), from the last run(), as a dict (J groups, Umax
+        the size of the largest, P contrasts; R rows: the Nreg regions and, with `region_sets`, the sets after them, whose
+        indicator is "patient u has an anomalous region in S"):
+            names, sizes, row_names          the groups in the order given (list of str, (J,) int64); "0" .. "Nreg-1", "set:<name>"
+            p_count       (J, R, Umax+1)     P(k_j = k | data), k_j = number of patients of g_j anomalous at the row; zero
+                                             beyond the group's size, rows sum to 1
+            prevalence    (J, R)             E[k_j] / |g_j|
+            contrasts                        the contrasts as pairs (name of a, name of b)
+            p_joint       list of P arrays (R, |a|+1, |b|+1)     P(k_a = i, k_b = l | data)
+            p_greater, p_less, p_equal  (P, R)     P(k_a/|a| > k_b/|b|), <, = (compared as integers, k_a |b| against k_b |a|)
+            diff_mean     (P, R)             E[k_a/|a| - k_b/|b|]
+            diff_interval (P, R, 2)          the central `level` interval of the law of k_a/|a| - k_b/|b|: the smallest values
+                                             of the difference at which its cumulative probability reaches (1 - level)/2 and
+                                             (1 + level)/2 (to within 1e-12)
+        Patients are coupled through f, so k_j is NOT Poisson-binomial in the per-patient marginals, and the law of a
+        difference needs the joint law of both counts:
+          method='gibbs', independent=False   the histograms over chains and the sweeps from burn_in on, every
+                          `patient_groups_every`-th.  Needs `patient_groups` set before run(); raises ValueError otherwise.
+                          The histograms are kept as `patient_group_hist` / `patient_group_joint_hist` (one array per
+                          contrast), the number of sweeps behind them as `patient_group_sweeps`.
+          method='vb', or independent=True on either method   the mean-field law of _lq_R with the CURRENT groups, contrasts
+                          and region sets: k_j is Poisson-binomial over the group's columns, at a set row with
+                          p_u = 1 - prod_{n in S} (1 - q1(n, u)) (both through fcd_vb_count_posterior); the joint of a
+                          contrast is the outer product of its two marginals (its groups are disjoint).
+        For a sampler fit, joint minus independent is the excess, the convention of coanomaly_posterior().
+        SharedRegionFit has one population-level r: ValueError.  Not provided: groups in score() and membership().
+        """
+        self._refuse_patient_groups_shared()
+        if self.model is None or self.bt is None:
+            raise ValueError("patient_group_posterior() needs a model and bt: call run() first")
+        if self.method not in ("vb", "gibbs"):
+            raise ValueError("method must be 'vb' or 'gibbs'")
+        if not 0.0 < float(level) < 1.0:
+            raise ValueError("level must lie in (0, 1)")
+        if self.method == "gibbs" and not independent:
+            (hg, hj) = (self.patient_group_hist, self.patient_group_joint_hist)
+            if hg is None or hj is None:
+                raise ValueError("no patient-group histograms: set patient_groups before run(method='gibbs')")
+            hg = np.asarray(hg, dtype=np.float64)
+            if hg.sum() == 0:
+                raise ValueError("no sweep was accumulated into the patient-group histograms (n_sweeps <= burn_in?)")
+            (names, sizes) = (list(self.patient_group_names), np.asarray(self.patient_group_sizes, dtype=np.int64))
+            (row_names, pairs) = (list(self.patient_group_rows), np.asarray(self.patient_group_pairs, dtype=np.int64).reshape(-1, 2))
+            p_count = hg / hg.sum(axis=2, keepdims=True)
+            p_joint = [np.asarray(h, dtype=np.float64) / np.asarray(h, dtype=np.float64).sum(axis=(1, 2), keepdims=True) for h in hj]
+        else:
+            if self.patient_groups is None:
+                raise ValueError("no patient groups: set patient_groups first")
+            (N, _C, U) = self._check_state(need=("lq_R",))
+            (names, offsets, members) = patient_groups_csr(self.patient_groups, U)
+            (pairs, _bins) = patient_group_contrasts(self.patient_group_contrasts, names, offsets, members)
+            sizes = np.diff(offsets).astype(np.int64)
+            row_names = [str(n) for n in range(N)]
+            sets = None
+            if self.region_sets is not None:
+                sets = region_sets_csr(self.region_sets, N)
+                row_names += ["set:" + name for name in sets[0]]
+            p_count = patient_group_independent(self._context(), self._d["lq_R"], N, U, offsets, members,
+                                                None if sets is None else sets[1:])
+            p_joint = [p_count[a, :, :sizes[a] + 1, None] * p_count[b, :, None, :sizes[b] + 1] for (a, b) in pairs]
+        out = {"names": names, "sizes": sizes, "row_names": row_names, "p_count": p_count,
+               "contrasts": [(names[a], names[b]) for (a, b) in pairs], "p_joint": p_joint}
+        out.update(patient_group_summaries(p_count, p_joint, sizes, pairs, level))
+        return out
 
     # ------------------------------------------------------------------ co-anomaly
     def _coanomaly_counts(self):
@@ -1256,6 +1364,8 @@ class SharedRegionFit(UnsharedRegionFit):
     def run(self):
         """Builds S_B and L, then the VB loop or the sampler at U = 1 (see the class docstring)."""
         self._edge_mode()
+        if self.patient_groups is not None:
+            self._refuse_patient_groups_shared()
         super(SharedRegionFit, self).run()
 
     def _theta_sub_flags(self):
@@ -1389,15 +1499,84 @@ def region_set_independent(ctx, lq_R, Nreg, U, offsets, members):
     # log q0 = -log(1 + e^d), d = lq1 - lq0, to full relative accuracy near q0 = 1 (q1 = 0 and q1 = 1 exact)
     d = lq_R[:, :, 1] - lq_R[:, :, 0]
     lq0 = -(torch.clamp(d, min=0.0) + torch.log1p(torch.exp(-torch.abs(d))))
-    block = torch.empty((J, U, 2), dtype=torch.float64, device=lq_R.device)
     idx = torch.as_tensor(np.asarray(members, dtype=np.int64), device=lq_R.device)
     for j in range(J):
         rows = idx[int(offsets[j]):int(offsets[j + 1])]
         p_count[j, :, :sizes[j] + 1] = count_posterior(ctx, lq_R[rows].contiguous(), int(sizes[j]), U)[0]
-        block[j, :, 0] = lq0[rows].sum(dim=0)
-    block[:, :, 1] = torch.log(-torch.expm1(block[:, :, 0]))
-    p_prev = count_posterior(ctx, block, J, U)[1]
+    p_prev = count_posterior(ctx, _region_set_any_block(lq_R, lq0, offsets, idx), J, U)[1]
     return p_count, p_prev
+
+
+def _region_set_any_block(lq_R, lq0, offsets, idx):
+    """(J, U, 2) of log(prod_{n in S_j} q0(n, u)), log(1 - that): the log-law of "patient u has an anomalous region in S_j"."""
+    import torch
+    J = len(offsets) - 1
+    block = torch.empty((J, lq_R.shape[1], 2), dtype=torch.float64, device=lq_R.device)
+    for j in range(J):
+        block[j, :, 0] = lq0[idx[int(offsets[j]):int(offsets[j + 1])]].sum(dim=0)
+    block[:, :, 1] = torch.log(-torch.expm1(block[:, :, 0]))
+    return block
+
+
+def patient_group_independent(ctx, lq_R, Nreg, U, offsets, members, sets=None):
+    """
+    p_count (J, R, Umax+1) as NumPy float64 under independent sites with q_nu = P(r_nu = 1) from lq_R (Nreg, U, 2) float64 (need
+    not be normalised), for the patient groups (offsets, members) of patient_groups_csr(): the number of patients of g_j
+    anomalous at a row is Poisson-binomial over the group's columns, made by fcd_vb_count_posterior from the gathered block
+    (Nreg, |g_j|, 2); sets = (offsets, members) of region_sets_csr() adds the J_S set rows from the block of
+    region_set_independent(), log(prod_n q0), log(1 - prod_n q0).
+    """
+    import torch
+    if tuple(lq_R.shape) != (Nreg, U, 2) or lq_R.dtype != torch.float64:
+        raise ValueError("lq_R must be float64 (Nreg, U, 2) = %s" % ((Nreg, U, 2),))
+    rows = lq_R
+    if sets is not None:
+        d = lq_R[:, :, 1] - lq_R[:, :, 0]
+        lq0 = -(torch.clamp(d, min=0.0) + torch.log1p(torch.exp(-torch.abs(d))))
+        idx = torch.as_tensor(np.asarray(sets[1], dtype=np.int64), device=lq_R.device)
+        rows = torch.cat([lq_R, _region_set_any_block(lq_R, lq0, sets[0], idx)], dim=0)
+    R = int(rows.shape[0])
+    J = len(offsets) - 1
+    sizes = np.diff(offsets)
+    p_count = np.zeros((J, R, int(sizes.max()) + 1))
+    cols = torch.as_tensor(np.asarray(members, dtype=np.int64), device=lq_R.device)
+    for j in range(J):
+        block = rows[:, cols[int(offsets[j]):int(offsets[j + 1])]].contiguous()
+        p_count[j, :, :sizes[j] + 1] = count_posterior(ctx, block, R, int(sizes[j]))[1]
+    return p_count
+
+
+def patient_group_summaries(p_count, p_joint, sizes, pairs, level=0.95):
+    """
+    The derived quantities of patient_group_posterior() from the laws alone (host arithmetic): prevalence (J, R) = E[k_j]/|g_j|
+    from p_count (J, R, Umax+1); per contrast (a, b) of `pairs` with its joint law p_joint[p] (R, |a|+1, |b|+1): p_greater,
+    p_less, p_equal (P, R) of k_a/|a| against k_b/|b| -- decided on the integers k_a |b| - k_b |a|, so equal rates of groups of
+    unequal sizes are equal --, diff_mean (P, R) and diff_interval (P, R, 2), the central `level` interval of the difference.
+    """
+    p_count = np.asarray(p_count, dtype=np.float64)
+    sizes = np.asarray(sizes, dtype=np.int64)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    (P, R) = (len(pairs), p_count.shape[1])
+    out = {"prevalence": (p_count @ np.arange(p_count.shape[2], dtype=np.float64)) / sizes[:, None].astype(np.float64)}
+    for key in ("p_greater", "p_less", "p_equal", "diff_mean"):
+        out[key] = np.zeros((P, R))
+    out["diff_interval"] = np.zeros((P, R, 2))
+    (q_lo, q_hi) = ((1.0 - level) / 2.0, (1.0 + level) / 2.0)
+    for (p, (a, b)) in enumerate(pairs):
+        (na, nb) = (int(sizes[a]), int(sizes[b]))
+        pj = np.asarray(p_joint[p], dtype=np.float64).reshape(R, (na + 1) * (nb + 1))
+        num = (np.arange(na + 1, dtype=np.int64)[:, None] * nb - np.arange(nb + 1, dtype=np.int64)[None, :] * na).reshape(-1)
+        out["p_greater"][p] = pj[:, num > 0].sum(axis=1)
+        out["p_less"][p] = pj[:, num < 0].sum(axis=1)
+        out["p_equal"][p] = pj[:, num == 0].sum(axis=1)
+        diff = num.astype(np.float64) / float(na * nb)
+        out["diff_mean"][p] = pj @ diff
+        order = np.argsort(num, kind="stable")
+        cum = np.cumsum(pj[:, order], axis=1)
+        for (i, q) in enumerate((q_lo, q_hi)):
+            at = np.minimum((cum < q - 1e-12).sum(axis=1), len(order) - 1)
+            out["diff_interval"][p, :, i] = diff[order][at]
+    return out
 
 
 def coanomaly_independent(ctx, lq_R, Nreg, U):

@@ -49,6 +49,60 @@ EXTRA_ACCUMULATORS = (
                 "fcd_gibbs_set_region_set_accumulator", None, "region-set"),
 )
 (_REGION_SET,) = EXTRA_ACCUMULATORS
+# The patient-group histograms, in a tuple of their own (tests unpack the two above by length): run() walks it last, under the
+# rule of EXTRA_ACCUMULATORS.  Shapes from set_patient_groups(): (J, R, Umax+1) and the flat joint histograms of the contrasts.
+PATIENT_GROUP_MAX_U, PATIENT_GROUP_MAX_GROUPS, PATIENT_GROUP_MAX_CONTRASTS = 512, 64, 64     # fcd_patient_groups_set
+PATIENT_GROUP_MAX_BINS = 16384          # (|a|+1)(|b|+1) of a contrast: the LDS of the workgroup that owns a joint row
+GROUP_ACCUMULATORS = (
+    Accumulator("patient_group", "patient_group_acc", True,
+                lambda e: ((e.group_J, e.patient_group_rows(), e.group_umax + 1),
+                           (max(1, e.patient_group_rows() * int(e.group_bin_offsets[-1])),)),
+                "fcd_gibbs_set_patient_group_accumulator", None, "patient-group"),
+)
+(_PATIENT_GROUP,) = GROUP_ACCUMULATORS
+
+
+# the wording of _index_sets_csr()'s refusals for the two axes: knob, one set, many, a member, the mask's name and extent
+_REGION_WORDS = ("region_sets", "region set", "sets", "region", "region-set", "Nreg")
+_PATIENT_WORDS = ("patient_groups", "patient group", "groups", "patient", "patient-group", "U")
+
+
+def _index_sets_csr(sets, extent, words, max_sets, max_size=None):
+    """What region_sets_csr() and patient_groups_csr() share: the three input forms, the refusals, the CSR arrays."""
+    (knob, one, many, member, mask_name, extent_name) = words
+    if isinstance(sets, dict):
+        names = [str(k) for k in sets.keys()]
+        rows = list(sets.values())
+    else:
+        mask = sets if isinstance(sets, np.ndarray) else None
+        if mask is not None and mask.dtype == np.bool_:
+            if mask.ndim != 2 or mask.shape[1] != extent:
+                raise ValueError("a %s mask must be boolean (J, %s=%d)" % (mask_name, extent_name, extent))
+            rows = [np.flatnonzero(m) for m in mask]
+        else:
+            rows = list(sets)
+        names = [str(j) for j in range(len(rows))]
+    if len(rows) < 1:
+        raise ValueError("%s holds no %s" % (knob, many[:-1]))
+    if len(rows) > max_sets:
+        raise ValueError("%s holds %d %s (at most %d)" % (knob, len(rows), many, max_sets))
+    (offsets, members) = ([0], [])
+    for (name, row) in zip(names, rows):
+        a = np.asarray(row)
+        if a.ndim != 1 or a.size == 0:
+            raise ValueError("%s %r is empty (or not a sequence of indices)" % (one, name))
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("%s %r must hold integer %s indices" % (one, name, member))
+        a = np.sort(a.astype(np.int64))
+        if a[0] < 0 or a[-1] >= extent:
+            raise ValueError("%s %r has an index outside [0, %d)" % (one, name, extent))
+        if np.any(a[1:] == a[:-1]):
+            raise ValueError("%s %r names a %s twice" % (one, name, member))
+        if max_size is not None and a.size > max_size:
+            raise ValueError("%s %r has %d members (at most %d)" % (one, name, a.size, max_size))
+        members.append(a)
+        offsets.append(offsets[-1] + a.size)
+    return names, np.asarray(offsets, dtype=np.int32), np.concatenate(members).astype(np.int32)
 
 
 def region_sets_csr(sets, Nreg):
@@ -58,40 +112,61 @@ def region_sets_csr(sets, Nreg):
     of a set ascending, what fcd_region_sets_set takes.  ValueError for no set, an empty set, a duplicate, an index outside
     [0, Nreg), more than 1023 members or more than 1024 sets.
     """
-    Nreg = int(Nreg)
-    if isinstance(sets, dict):
-        names = [str(k) for k in sets.keys()]
-        rows = list(sets.values())
-    else:
-        mask = sets if isinstance(sets, np.ndarray) else None
-        if mask is not None and mask.dtype == np.bool_:
-            if mask.ndim != 2 or mask.shape[1] != Nreg:
-                raise ValueError("a region-set mask must be boolean (J, Nreg=%d)" % Nreg)
-            rows = [np.flatnonzero(m) for m in mask]
-        else:
-            rows = list(sets)
-        names = [str(j) for j in range(len(rows))]
-    if len(rows) < 1:
-        raise ValueError("region_sets holds no set")
-    if len(rows) > REGION_SET_MAX_SETS:
-        raise ValueError("region_sets holds %d sets (at most %d)" % (len(rows), REGION_SET_MAX_SETS))
-    (offsets, members) = ([0], [])
-    for (name, row) in zip(names, rows):
-        a = np.asarray(row)
-        if a.ndim != 1 or a.size == 0:
-            raise ValueError("region set %r is empty (or not a sequence of indices)" % name)
-        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
-            raise ValueError("region set %r must hold integer region indices" % name)
-        a = np.sort(a.astype(np.int64))
-        if a[0] < 0 or a[-1] >= Nreg:
-            raise ValueError("region set %r has an index outside [0, %d)" % (name, Nreg))
-        if np.any(a[1:] == a[:-1]):
-            raise ValueError("region set %r names a region twice" % name)
-        if a.size > REGION_SET_MAX_SIZE:
-            raise ValueError("region set %r has %d members (at most %d)" % (name, a.size, REGION_SET_MAX_SIZE))
-        members.append(a)
-        offsets.append(offsets[-1] + a.size)
-    return names, np.asarray(offsets, dtype=np.int32), np.concatenate(members).astype(np.int32)
+    return _index_sets_csr(sets, int(Nreg), _REGION_WORDS, REGION_SET_MAX_SETS, REGION_SET_MAX_SIZE)
+
+
+def patient_groups_csr(groups, U):
+    """
+    Groups of patients in any of their three forms -- a dict name -> sequence of patient indices, a sequence of index
+    sequences (named "0", "1", ...), a boolean mask (J, U) -- as (names, offsets (J+1,) int32, members int32): CSR with the
+    members of a group ascending, what fcd_patient_groups_set takes.  The ValueErrors of region_sets_csr() on the patient
+    axis: no group, an empty group, a duplicate, an index outside [0, U), more than 64 groups or more than 512 patients.
+    """
+    U = int(U)
+    if U > PATIENT_GROUP_MAX_U:
+        raise ValueError("patient groups are made for at most %d patients (here %d)" % (PATIENT_GROUP_MAX_U, U))
+    return _index_sets_csr(groups, U, _PATIENT_WORDS, PATIENT_GROUP_MAX_GROUPS)
+
+
+def patient_group_contrasts(contrasts, names, offsets, members):
+    """
+    Contrasts between the groups of patient_groups_csr() -- pairs (a, b) of group names or indices, or None -- as
+    (pairs (P, 2) int32, bin_offsets (P+1,) int64): bin_offsets[p] = sum_{q < p} (|a_q|+1)(|b_q|+1), the start of contrast p's
+    joint histogram of one row.  ValueError for an unknown name or index, a contrast that names a group twice, overlapping
+    groups, more than 64 contrasts or a contrast of more than 16384 joint bins.
+    """
+    J = len(names)
+    rows = [] if contrasts is None else list(contrasts)
+    if len(rows) > PATIENT_GROUP_MAX_CONTRASTS:
+        raise ValueError("patient_group_contrasts holds %d contrasts (at most %d)" % (len(rows), PATIENT_GROUP_MAX_CONTRASTS))
+
+    def index(key):
+        if isinstance(key, str):
+            if key not in names:
+                raise ValueError("a contrast names the unknown patient group %r" % key)
+            return names.index(key)
+        if isinstance(key, (bool, np.bool_)) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) < J:
+            raise ValueError("a contrast names the patient group %r: not a name or an index in [0, %d)" % (key, J))
+        return int(key)
+    sizes = np.diff(offsets).astype(np.int64)
+    pairs = np.zeros((len(rows), 2), dtype=np.int32)
+    bin_offsets = np.zeros(len(rows) + 1, dtype=np.int64)
+    for (p, row) in enumerate(rows):
+        row = tuple(row)
+        if len(row) != 2:
+            raise ValueError("a contrast is a pair of patient groups, got %r" % (row,))
+        (a, b) = (index(row[0]), index(row[1]))
+        if a == b:
+            raise ValueError("contrast %d names patient group %r twice" % (p, names[a]))
+        if np.intersect1d(members[offsets[a]:offsets[a + 1]], members[offsets[b]:offsets[b + 1]]).size:
+            raise ValueError("the patient groups %r and %r of contrast %d overlap" % (names[a], names[b], p))
+        bins = int((sizes[a] + 1) * (sizes[b] + 1))
+        if bins > PATIENT_GROUP_MAX_BINS:
+            raise ValueError("contrast %d of patient groups %r and %r has %d joint bins (at most %d)"
+                             % (p, names[a], names[b], bins, PATIENT_GROUP_MAX_BINS))
+        pairs[p] = (a, b)
+        bin_offsets[p + 1] = bin_offsets[p] + bins
+    return pairs, bin_offsets
 
 
 def pair_sweeps_in(sweep0, n_sweeps, accumulate_from, every):
@@ -184,6 +259,14 @@ class GibbsEngine(object):
         self.region_set_acc = None  # (hist_set (J, U, S_max+1), hist_prev (J, U+1)) that run() adds to (attach_region_set_accumulator)
         self.region_set_every = 1
         self.region_set_sweeps = 0  # sweeps added to region_set_acc so far
+        self.group_names = None     # the groups of set_patient_groups(): names, CSR offsets and members, contrasts (P, 2) and
+        self.group_offsets = self.group_members = self.group_contrasts = None      # the bin offsets of their joint histograms
+        self.group_bin_offsets = None
+        self.group_J = self.group_umax = 0
+        self.group_with_sets = False        # the rows of patient_group_acc include the region sets it was attached with
+        self.patient_group_acc = None       # (hist_group (J, R, Umax+1), hist_joint flat) that run() adds to (attach_patient_group_accumulator)
+        self.patient_group_every = 1
+        self.patient_group_sweeps = 0       # sweeps added to patient_group_acc so far
         self.ctx.call("fcd_ctx_reserve", self.Nreg, self.U, self.G)
         self.lMd = self.lMf = None
         if region_major:
@@ -273,13 +356,15 @@ class GibbsEngine(object):
         (attach_count_accumulator) the histograms of the anomalous-region counts of every `count_every`-th sweep, and with
         a co-anomaly accumulator attached (attach_coanomaly_accumulator) the two pair matrices of every
         `coanomaly_every`-th sweep, and with a region-set accumulator attached (attach_region_set_accumulator) the
-        histograms over the region sets of every `region_set_every`-th sweep; a call that could overflow any of them raises
-        ValueError.
+        histograms over the region sets of every `region_set_every`-th sweep, and with a patient-group accumulator attached
+        (attach_patient_group_accumulator) the histograms over the patient groups of every `patient_group_every`-th sweep; a
+        call that could overflow any of them raises ValueError.
         """
         acc = accumulate_from is not None
         live = []                   # (accumulator, sweeps this call adds to it), attached ones only
-        for a in ACCUMULATORS + EXTRA_ACCUMULATORS:     # (in this order, and nothing of an accumulator is read unless it is attached)
-            if not acc or (getattr(self, a.attr, None) if a in EXTRA_ACCUMULATORS else getattr(self, a.attr)) is None:
+        # (in this order, and nothing of an accumulator is read unless it is attached)
+        for a in ACCUMULATORS + EXTRA_ACCUMULATORS + GROUP_ACCUMULATORS:
+            if not acc or (getattr(self, a.attr) if a in ACCUMULATORS else getattr(self, a.attr, None)) is None:
                 continue
             n = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), getattr(self, a.key + "_every"))
             total = getattr(self, a.key + "_sweeps") + n
@@ -293,6 +378,8 @@ class GibbsEngine(object):
             for (a, _n) in live:
                 if a is _REGION_SET:
                     self._send_region_sets()
+                if a is _PATIENT_GROUP:
+                    self._send_patient_groups()
                 self.ctx.call(a.setter, *([_lib.dptr(b) for b in self._acc_buffers(a)]
                                           + [self.Nreg, self.U, getattr(self, a.key + "_every")]))
             self._run(sweep0, n_sweeps, mstep_every, accumulate_from, want_counts)
@@ -395,6 +482,8 @@ class GibbsEngine(object):
         """
         if self.region_set_acc is not None:
             raise ValueError("detach the region-set accumulator before changing the sets")
+        if getattr(self, "patient_group_acc", None) is not None:
+            raise ValueError("detach the patient-group accumulator before changing the sets: they may be rows of it")
         if sets is None:
             (self.region_names, self.region_offsets, self.region_members) = (None, None, None)
             (self.region_J, self.region_smax) = (0, 0)
@@ -451,6 +540,95 @@ class GibbsEngine(object):
         self.ctx.call("fcd_gibbs_region_set_tally", _lib.dptr(self.r_bits), self.Nreg, self.U, self.G, _lib.dptr(hist_set),
                       _lib.dptr(hist_prev), _lib.stream_ptr())
         return hist_set, hist_prev
+
+    # ---- counts over groups of patients and contrasts between two groups ----
+    def set_patient_groups(self, groups, contrasts=None):
+        """
+        The patient groups of this engine's histograms, in any form patient_groups_csr() takes, and the contrasts between
+        them (pairs of names or indices of disjoint groups; patient_group_contrasts()); groups=None clears.  They are copied
+        to the context (fcd_patient_groups_set).  ValueError while the accumulator is attached: its buffers have the old shapes.
+        """
+        if self.patient_group_acc is not None:
+            raise ValueError("detach the patient-group accumulator before changing the groups")
+        self.ctx.patient_groups_owner = None
+        if groups is None:
+            if contrasts is not None:
+                raise ValueError("contrasts without patient groups")
+            (self.group_names, self.group_offsets, self.group_members) = (None, None, None)
+            (self.group_contrasts, self.group_bin_offsets) = (None, None)
+            (self.group_J, self.group_umax) = (0, 0)
+            self.ctx.call("fcd_patient_groups_set", None, None, 0, None, 0, 0)
+            return
+        (names, offsets, members) = patient_groups_csr(groups, self.U)
+        (pairs, bin_offsets) = patient_group_contrasts(contrasts, names, offsets, members)
+        (self.group_names, self.group_offsets, self.group_members) = (names, offsets, members)
+        (self.group_contrasts, self.group_bin_offsets) = (pairs, bin_offsets)
+        self.group_J = len(names)
+        self.group_umax = int(np.diff(offsets).max())
+        self._send_patient_groups()
+
+    def patient_group_rows(self):
+        """R: the regions and, while an attached accumulator has them or else if region sets are set, the region sets after them."""
+        with_sets = self.group_with_sets if self.patient_group_acc is not None else bool(self.region_J)
+        return self.Nreg + (self.region_J if with_sets else 0)
+
+    def patient_group_row_names(self):
+        """The names of the R rows: the region indices as str, then "set:<name>" for the region sets."""
+        R = self.patient_group_rows()
+        return [str(n) for n in range(self.Nreg)] + ["set:" + s for s in (self.region_names or [])[:R - self.Nreg]]
+
+    def _send_patient_groups(self):
+        """As _send_region_sets(): the shared context holds this engine's groups (and, as rows, its region sets) before a launch."""
+        if not self.group_J:
+            raise ValueError("no patient groups: call set_patient_groups() first")
+        with_sets = self.patient_group_rows() > self.Nreg
+        if with_sets:
+            self._send_region_sets()
+        owner = getattr(self.ctx, "patient_groups_owner", None)
+        if owner is not None and owner[0]() is self and owner[1] == with_sets:
+            return
+        self.ctx.call("fcd_patient_groups_set", self.group_offsets.ctypes.data_as(C.c_void_p),
+                      self.group_members.ctypes.data_as(C.c_void_p), self.group_J,
+                      self.group_contrasts.ctypes.data_as(C.c_void_p) if len(self.group_contrasts) else None,
+                      len(self.group_contrasts), 1 if with_sets else 0)
+        self.ctx.patient_groups_owner = (weakref.ref(self), with_sets)
+
+    def attach_patient_group_accumulator(self, every=1):
+        """
+        From now on run() adds the end-of-sweep histograms over the groups of set_patient_groups() to `patient_group_acc`:
+        hist_group (J, R, Umax+1), over chains, of the number of patients of g_j anomalous at row rho (bins beyond a group's
+        size stay 0) and hist_joint, flat: block p of contrast (a, b) is (R, |a|+1, |b|+1), the joint histogram of (k_a, k_b),
+        and starts at R * group_bin_offsets[p] (one placeholder word without contrasts).  The rows are the regions and, if
+        region sets are set NOW, the sets after them; at every `every`-th sweep from its `accumulate_from` on (none when
+        accumulate_from is None).  Zeroes the histograms.
+        """
+        if not self.group_J:
+            raise ValueError("no patient groups: call set_patient_groups() first")
+        self.patient_group_acc = None
+        self.group_with_sets = bool(self.region_J)
+        return self._attach(_PATIENT_GROUP, every)
+
+    def detach_patient_group_accumulator(self):
+        self._detach(_PATIENT_GROUP)
+
+    def patient_group_host(self):
+        """The attached histograms as NumPy uint32 arrays (hist_group (J, R, Umax+1), hist_joint flat)."""
+        return self._acc_host(_PATIENT_GROUP)
+
+    def patient_group_tally(self, hist_group, hist_joint):
+        """hist_group (J, R, Umax+1), hist_joint (max(1, R * bins of all contrasts),) uint32-in-int32 tensors += the histograms of the current state."""
+        if not self.group_J:
+            raise ValueError("no patient groups: call set_patient_groups() first")
+        R = self.patient_group_rows()
+        if (tuple(hist_group.shape) != (self.group_J, R, self.group_umax + 1)
+                or hist_joint.numel() != max(1, R * int(self.group_bin_offsets[-1]))
+                or hist_group.element_size() != 4 or hist_joint.element_size() != 4
+                or not hist_group.is_contiguous() or not hist_joint.is_contiguous()):
+            raise ValueError("histograms must be contiguous 32-bit (J, R, Umax+1) and R x the joint bins of all contrasts")
+        self._send_patient_groups()
+        self.ctx.call("fcd_gibbs_patient_group_tally", _lib.dptr(self.r_bits), self.Nreg, self.U, self.G, _lib.dptr(hist_group),
+                      _lib.dptr(hist_joint), _lib.stream_ptr())
+        return hist_group, hist_joint
 
     # ---- co-anomaly: pairs of regions anomalous together, pairs of patients sharing anomalous regions ----
     def attach_coanomaly_accumulator(self, every=1):

@@ -481,7 +481,7 @@ int fcd_vb_count_posterior(fcd_ctx *ctx, const double *lq_R, int64_t Nreg, int64
  * FCD_ERR_ARG for a null pointer, J < 1, offsets[0] != 0, an empty set, a negative member or members that do not increase;
  * FCD_ERR_UNSUPPORTED for a set of more than 1023 members or J > 1024.  The context copies both arrays into a device buffer
  * it owns and frees (it synchronises).  J = 0 with both arrays NULL clears.  Refused with FCD_ERR_ARG while the region-set
- * accumulator is attached. */
+ * accumulator is attached, or the patient-group accumulator with the sets as rows. */
 int fcd_region_sets_set(fcd_ctx *ctx, const int32_t *offsets_host, const int32_t *members_host, int64_t J);
 /* Histograms over chains of one state, with S_max the size of the largest set:
  *   hist_set (J, U, S_max+1) uint32, hist_set[j][u][k] += #{chains with sum_{n in S_j} r_nu = k}; the bins k > |S_j| are
@@ -500,6 +500,46 @@ int fcd_gibbs_region_set_tally(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nre
  * refuses to change the sets.  fcd_gibbs_sweeps never adds to them.  The caller keeps sweeps x G below 2^32. */
 int fcd_gibbs_set_region_set_accumulator(fcd_ctx *ctx, uint32_t *hist_set, uint32_t *hist_prev, int64_t Nreg, int64_t U,
                                          int64_t every);
+/* ---- anomaly prevalence over groups of patients, and contrasts between two groups -------------------------------------
+ * For user-given groups g_0 .. g_{J-1} of patients and every row rho: the law of k_j = #{u in g_j : the row's indicator is 1
+ * in patient u}; for every contrast (a, b) of two DISJOINT groups the joint law of (k_a, k_b).  The rows are the Nreg regions
+ * (indicator r_nu) and, if the groups were set with_region_sets, after them the context's J_S region sets (indicator "some n
+ * in S has r_nu = 1"): R = Nreg + J_S.  Patients are coupled through f, so neither law follows from per-patient marginals.
+ * The group of all patients gives fcd_gibbs_count_tally's hist_region at a region row and fcd_gibbs_region_set_tally's
+ * hist_prev at a set row.
+ *
+ * The groups of the context, CSR in HOST memory: offsets_host (J + 1, offsets[0] = 0), members_host (offsets[J]), the members
+ * of a group strictly increasing; groups may overlap.  contrasts_host: P pairs (a, b) of group indices (NULL with P = 0).
+ * Everything is checked here, on the host: FCD_ERR_ARG for a null pointer, J < 1, P < 0, offsets[0] != 0, an empty group, a
+ * negative member, members that do not increase, a contrast that names a group outside [0, J) or one group twice, or whose
+ * groups overlap; FCD_ERR_UNSUPPORTED for a member >= 512 (U <= 512), J > 64, P > 64, or a contrast of more than 16384 joint
+ * bins (|a|+1)(|b|+1) -- 64 KiB of uint32, the LDS of the one workgroup that owns a joint row; the message names the contrast.
+ * The context copies the CSR, the contrasts, a bit mask over u per group (8 words, of which the kernels read ceil(U/64)) and
+ * the contrasts' bin offsets into a device buffer it owns and frees (it synchronises).  J = 0 with offsets, members and
+ * contrasts NULL and P = 0 clears.  Refused with FCD_ERR_ARG while the patient-group accumulator is attached. */
+int fcd_patient_groups_set(fcd_ctx *ctx, const int32_t *offsets_host, const int32_t *members_host, int64_t J,
+                           const int32_t *contrasts_host, int64_t P, int with_region_sets);
+/* Histograms over chains of one state, with Umax the size of the largest group:
+ *   hist_group (J, R, Umax+1) uint32, hist_group[j][rho][k] += #{chains with k_j(rho) = k}; the bins k > |g_j| are never
+ *   touched;
+ *   hist_joint, flat uint32: block p of contrast (a, b) is (R, |a|+1, |b|+1) and starts at word R * boff[p],
+ *   boff[p] = sum_{q < p} (|a_q|+1)(|b_q|+1); hist_joint[R boff[p] + (rho (|a|+1) + k_a)(|b|+1) + k_b] += #{chains with that
+ *   pair of counts}.  R * boff[P] words in all; with P = 0 a placeholder of one word, never touched.
+ * Chains beyond G in the last word never count, and patients beyond U in the last 64-patient chunk read as 0.  Two launches;
+ * the scratch, J R rows of ceil(G/64) * 64 uint16, is the count tally's, grown on demand.  FCD_ERR_ARG without groups, or
+ * without region sets when the groups were set with them; FCD_ERR_SHAPE if the largest member of a group is >= U or the
+ * largest member of a region set is >= Nreg; FCD_ERR_UNSUPPORTED for U > 512 or a scratch above 1 GiB. */
+int fcd_gibbs_patient_group_tally(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
+                                  uint32_t *hist_group, uint32_t *hist_joint, fcd_stream stream);
+/* Attach both histograms for shape (Nreg, U) and the context's CURRENT groups (and region sets, if they are rows) -- no device
+ * work; both NULL detaches --, with the semantics of fcd_gibbs_set_region_set_accumulator: every sweep s of fcd_gibbs_run with
+ * s >= accumulate_from and (s - accumulate_from) % every == 0 adds its end-of-sweep state (two extra launches, after the other
+ * accumulators'; fcd_gibbs_run grows the scratch before its loop and refuses one above 1 GiB).  Refusals as
+ * fcd_gibbs_patient_group_tally's; while attached fcd_gibbs_run refuses another shape, fcd_patient_groups_set refuses to
+ * change the groups and, with the sets as rows, fcd_region_sets_set to change the sets.  fcd_gibbs_sweeps never adds to them.
+ * The caller keeps sweeps x G below 2^32. */
+int fcd_gibbs_set_patient_group_accumulator(fcd_ctx *ctx, uint32_t *hist_group, uint32_t *hist_joint, int64_t Nreg, int64_t U,
+                                            int64_t every);
 /* ---- co-anomaly (which regions are anomalous together, which patients share anomalous regions) -------------------
  * Second moments of the joint law of the sites, which the marginals do not give.
  *
