@@ -69,6 +69,8 @@ SIGNATURES = {
     "fcd_model_sample_shared": (_int, [_p, C.POINTER(_dbl), _i64, _i64, _i64, _u64, _p, _p, _p, _p, _p, _p, _p]),
     "fcd_corr_edges": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
     "fcd_corr_clean": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p]),
+    "fcd_edge_cov_fit": (_int, [_p, _p, _i64, _i64, _p, _i64, _int, _p, _p, _p, _p]),
+    "fcd_edge_cov_apply": (_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p]),
     "fcd_vb_update_qF": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
     "fcd_vb_update_qR": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _p, _p]),
     "fcd_vb_energy": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p]),

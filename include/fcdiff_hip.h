@@ -301,6 +301,32 @@ int fcd_corr_edges(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, int6
 int fcd_corr_clean(fcd_ctx *ctx, const double *ts, const double *confounds, const uint8_t *frame_mask, int64_t S,
                    int64_t Nreg, int64_t Q, int64_t T, double *resid, int32_t *info, fcd_stream stream);
 
+/* ---- covariate adjustment of the connections, fitted on the controls -----------------------------------------------------
+ * Not in the reference; oracle = tests/covariates_ref.py.  For every connection c, ordinary least squares with an implied
+ * intercept over the controls observed at c:  b[c,h] = alpha_c + sum_q beta[c,q] z[h,q] + e.
+ * b (C, H) and z (H, Q) fp64, 0 <= Q <= 16 (z and beta may be NULL when Q == 0); C need not be triangular.  z is finite (not
+ * checked here).  flags: FCD_DATA_NAN_MISSING -- a NaN b[c,h] leaves control h out of connection c's fit; without it every
+ * control counts (n_obs = H) and a NaN makes that row of beta, and its resid_var, NaN.
+ * The rules of fcd_corr_clean: columns are centred over the connection's observed controls; a column constant over them
+ * (min == max) is dropped; the others are scaled to unit norm (remaining squared norm exactly 1 before the first pivot);
+ * collinear columns are dropped by diagonally pivoted Cholesky of the Gram matrix (remaining squared norm below 1e-10, ties
+ * to the lowest column index); beta from the normal equations of the columns used.
+ * beta (C, Q): in the units of the columns of z, 0 for a column not used.  resid_var (C,): sum of squared residuals / dof,
+ * from the residuals themselves.  info (C, 4) int32: n_obs, rank (columns used), dof = n_obs - 1 - rank, bit mask of the
+ * columns used.  A connection with dof < 1 is not fitted: beta row 0, rank and mask reported as 0 (dof as found), resid_var
+ * NaN.  Any H: the design is walked four controls at a time and never held whole on chip.  Two launches; uses the context's
+ * workspace (2 x H x 16 doubles + 144 bytes): fcd_ctx_reserve knows nothing of H and does not size it, so a call with H > 4095
+ * (more than the workspace's first megabyte) grows it once, as any call with a larger shape than before does.
+ * Deterministic; inputs are not written.
+ * FCD_ERR_UNSUPPORTED for Q > 16, unknown flags or H > 2^26; FCD_ERR_ARG for C < 1, H < 1, Q < 0 or a null pointer. */
+int fcd_edge_cov_fit(fcd_ctx *ctx, const double *b, int64_t C, int64_t H, const double *z, int64_t Q, int flags, double *beta,
+                     double *resid_var, int32_t *info, fcd_stream stream);
+/* out[c,s] = x[c,s] - d,  d = sum_q beta[c,q] (z[s,q] - z_ref[q]) added up over q ascending from 0.0, one rounded product and
+ * one rounded sum per term: a NumPy loop's result bit for bit.  x, out (C, S), z (S, Q), z_ref (Q,), beta (C, Q),
+ * all device.  NaN stays NaN.  Sessions are the caller's flattening of (U, K) to S.  One launch.  Refusals as above. */
+int fcd_edge_cov_apply(fcd_ctx *ctx, const double *x, int64_t C, int64_t S, const double *z, int64_t Q, const double *z_ref,
+                       const double *beta, double *out, fcd_stream stream);
+
 /* ---- variational updates ------------------------------------------------------------------ */
 /* UnsharedRegionFit._update_lq_F, fit.py:157-174 (+ _eval_q_R_w 382-406). */
 int fcd_vb_update_qF(fcd_ctx *ctx, const double *lq_R, const double *S_B, const double *lM,
