@@ -20,9 +20,9 @@ def histograms(r):
     return hp.reshape(U, N + 1), hr.reshape(N, U + 1)
 
 
-def q_of(lq_R):
-    """(q0, q1) = (P(r = 0), P(r = 1)) from log-weights lq_R (..., 2), normalised in log space."""
-    lq_R = np.asarray(lq_R, dtype=np.float64)
+def q_of(lq_R, dtype=np.float64):
+    """(q0, q1) = (P(r = 0), P(r = 1)) from log-weights lq_R (..., 2), normalised in log space, computed in `dtype`."""
+    lq_R = np.asarray(lq_R, dtype=dtype)
     (l0, l1) = (lq_R[..., 0], lq_R[..., 1])
     mx = np.maximum(l0, l1)
     (e0, e1) = (np.exp(l0 - mx), np.exp(l1 - mx))
@@ -30,9 +30,9 @@ def q_of(lq_R):
     return e0 / s, e1 / s
 
 
-def poisson_binomial(q0, q1):
-    """Law of the number of successes of independent sites with P(0) = q0[i], P(1) = q1[i]: (len + 1,) float64."""
-    P = np.zeros(len(q0) + 1)
+def poisson_binomial(q0, q1, dtype=np.float64):
+    """Law of the number of successes of independent sites with P(0) = q0[i], P(1) = q1[i]: (len + 1,) of `dtype`."""
+    P = np.zeros(len(q0) + 1, dtype=dtype)
     P[0] = 1.0
     for (i, (a, b)) in enumerate(zip(q0, q1)):
         nxt = P[:i + 2] * a
@@ -41,10 +41,11 @@ def poisson_binomial(q0, q1):
     return P
 
 
-def count_posterior(lq_R):
-    """lq_R (Nreg, U, 2) -> (p_patient (U, Nreg+1), p_region (Nreg, U+1)) under independent sites."""
-    (q0, q1) = q_of(lq_R)
+def count_posterior(lq_R, dtype=np.float64):
+    """lq_R (Nreg, U, 2) -> (p_patient (U, Nreg+1), p_region (Nreg, U+1)) under independent sites; the whole recursion runs in
+    `dtype` (np.longdouble: a reference with more digits than the kernel's fp64)."""
+    (q0, q1) = q_of(lq_R, dtype)
     (N, U) = q0.shape
-    p_patient = np.stack([poisson_binomial(q0[:, u], q1[:, u]) for u in range(U)])
-    p_region = np.stack([poisson_binomial(q0[n, :], q1[n, :]) for n in range(N)])
+    p_patient = np.stack([poisson_binomial(q0[:, u], q1[:, u], dtype) for u in range(U)])
+    p_region = np.stack([poisson_binomial(q0[n, :], q1[n, :], dtype) for n in range(N)])
     return p_patient, p_region

@@ -16,7 +16,8 @@ again after those lanes are poisoned (f byte 2, r bit 1) and must not change.
 `geometry()` restates the launch formulas of fcd_gibbs.hip / fcd_gibbs_r.hip / fcd_post.hip and each shape asserts the
 regime it was picked for, so that a change of the geometry fails here instead of silently retiring the coverage.  The
 host oracles run on every chain; the pair counts (O.pair_counts, a Python loop over chains) skip the two shapes with
-more than 2e7 (chain, edge, patient) items.
+more than 2e7 (chain, edge, patient) items.  Two shapes with more than 1024 chain words (PAIR_ROUND_SHAPES) run the pair
+counts alone, where pair_tally_kernel takes the f masks of an edge in two rounds.
 """
 import numpy as np
 import numpy.testing as nptest
@@ -114,6 +115,7 @@ REGIMES = {
     "tally r wraps after pack": lambda g: g["tally_r_passes_after_pack"] >= 2 and g["pack_tally"],
     "pair edges wrap": lambda g: g["pair_edge_passes"] >= 2,
     "pair patients wrap": lambda g: g["pair_u_passes"] >= 2,
+    "pair word rounds": lambda g: g["pair_word_rounds"] >= 2,
 }
 
 # (Nreg, U, G, regimes)
@@ -133,6 +135,14 @@ SHAPES = [
     (4, 300, 65, ("pair patients wrap", "U > 64", "partial last word")),
 ]
 SHAPE_IDS = ["%dx%dx%d" % s[:3] for s in SHAPES]
+# more chain words than pair_tally_kernel holds f masks for (1024): GW = 1026, a second round of two words, the last with one
+# chain; the second shape has two patient blocks as well, so the masks of every round are rebuilt per block.  The counters
+# that walk every chain on the host would take too long at this G: these shapes run the pair counts alone
+# (test_pair_counts_over_two_word_rounds), against the vectorised recount of conn_posterior_ref.
+PAIR_ROUND_SHAPES = [
+    (3, 2, 65601, ("pair word rounds", "partial last word")),
+    (2, 300, 65601, ("pair word rounds", "pair patients wrap", "U > 64", "partial last word")),
+]
 KINDS = ("random", "f2 r1", "last word only")
 
 
@@ -152,6 +162,12 @@ def test_regimes_of_the_named_shapes():
         check_regimes(256, Nreg, U, G, regimes)
     for (Nreg, U, G, _n, _p, regimes) in RUN_SHAPES:
         check_regimes(256, Nreg, U, G, regimes)
+    for (Nreg, U, G, regimes) in PAIR_ROUND_SHAPES:
+        g = check_regimes(256, Nreg, U, G, regimes)
+        assert (g["GW"], g["pair_words"], g["pair_word_rounds"], g["tail"]) == (1026, 1024, 2, 1)
+        assert G * g["C"] * U <= PAIR_MAX_ITEMS
+    assert geometry(2, 300, 65601, 256)["pair_u_passes"] == 2
+    assert all(geometry(*s[:3], 256)["pair_word_rounds"] == 1 for s in SHAPES)
     g = geometry(300, 3, 1024, 256)
     assert (g["tally_f_blocks"], g["tally_f_passes"], g["pair_blocks"], g["pair_edge_passes"]) == (512, 2, 16384, 3)
     g = geometry(200, 2, 65, 256)
@@ -364,6 +380,42 @@ def test_counters_against_recount(env, Nreg, U, G, regimes, kind):
         assert set(dirty) == set(clean)
         for key in clean:
             assert clean[key].tobytes() == dirty[key].tobytes(), "%s changed with the chain-less lanes poisoned" % key
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("Nreg,U,G,regimes", PAIR_ROUND_SHAPES, ids=["%dx%dx%d" % s[:3] for s in PAIR_ROUND_SHAPES])
+def test_pair_counts_over_two_word_rounds(env, Nreg, U, G, regimes, kind):
+    """
+    pair_counts() (plain, and accumulate=True on top of existing values) and pair_tally() (on top of existing uint32 values,
+    some above 2^31) where the f masks of an edge take two rounds of chain words, against the vectorised recount of
+    conn_posterior_ref.pair_counts; bit for bit the same with the chain-less lanes of the last word poisoned.  Every output
+    starts from a sentinel or from known values, so an item left unwritten shows.
+    """
+    import conn_posterior_ref as CPR
+    check_regimes(env.n_cu, Nreg, U, G, regimes)
+    t = env.torch
+    (f, r) = planted(Nreg, U, G, kind, seed=Nreg * 7 + U * 13 + G)
+    W = CPR.pair_counts(f, r)
+    assert W.sum() == G * W.shape[0] * U
+    eng = zero_engine(env, Nreg, U, G)
+    eng.import_state(f, r)
+    rng = np.random.default_rng(G + U)
+    W0 = rng.integers(0, 1000, size=(eng.C, U, 3, 3)).astype(np.float64)
+    A0 = rng.integers(1, (1 << 32) - 1 - G, size=(eng.C, U, 3, 3), dtype=np.int64)
+    A0.flat[0] = (1 << 32) - 1 - G
+
+    def run():
+        plain = eng.pair_counts(t.full((eng.C, U, 3, 3), float("nan"), dtype=t.float64, device="cuda")).cpu().numpy()
+        acc = eng.pair_counts(up(env, W0), accumulate=True).cpu().numpy() - W0
+        tally = as_u32(eng.pair_tally(from_u32(env, A0))) - A0
+        env.ctx.check_device()
+        return plain, acc, tally
+    clean = run()
+    for (got, name) in zip(clean, ("pair_counts", "pair_counts(accumulate=True)", "pair_tally")):
+        nptest.assert_array_equal(got, W, err_msg=name)
+    poison(env, eng)
+    for (a, b, name) in zip(clean, run(), ("pair_counts", "pair_counts(accumulate=True)", "pair_tally")):
+        assert a.tobytes() == b.tobytes(), "%s changed with the chain-less lanes poisoned" % name
 
 
 # ------------------------------------------------------------------------------------------------
