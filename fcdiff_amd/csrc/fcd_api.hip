@@ -195,9 +195,12 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->knobs.r_poll_limit = 0;        // test hooks: through fcd_ctx_set_knob only, never from the environment
     ctx->knobs.r_withhold = 0;
     ctx->knobs.f_records = 0;           // (A/B runs and tests only)
+    ctx->knobs.tally_in_r = (int)knob_env("FCD_TALLY_IN_R");
+    ctx->knobs.r_keep_words = (int)knob_env("FCD_R_KEEP_WORDS");
     ctx->r_form_last = 0;
     ctx->n_pack = 0;
     ctx->n_pack_tally = 0;
+    ctx->n_r_tally = 0;
     ctx->n_frec_pass = ctx->n_frec_build = 0;
     int rc = fcd_ws_reserve(ctx, 1u << 20);
     if (rc == FCD_OK) {
@@ -300,6 +303,8 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value) {
     else if (!strcmp(name, "f_pack")) k.f_pack = (int)value;
     else if (!strcmp(name, "f_records")) k.f_records = (int)value;
     else if (!strcmp(name, "corr_form")) k.corr_form = (int)value;
+    else if (!strcmp(name, "tally_in_r")) k.tally_in_r = (int)value;
+    else if (!strcmp(name, "r_keep_words")) k.r_keep_words = (int)value;
     else if (!strcmp(name, "r_poll_limit")) k.r_poll_limit = (int)value;
     else if (!strcmp(name, "r_withhold")) k.r_withhold = (int)value;
     else return fcd_fail(ctx, FCD_ERR_ARG, "fcd_ctx_set_knob: unknown knob");
@@ -332,6 +337,8 @@ int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out) {
     else if (!strcmp(name, "r_form_last")) *out = ctx->r_form_last;
     else if (!strcmp(name, "pack_launches")) *out = ctx->n_pack;
     else if (!strcmp(name, "tally_f_in_pack")) *out = ctx->n_pack_tally;
+    else if (!strcmp(name, "tally_f_in_r")) *out = ctx->n_r_tally;
+    else if (!strcmp(name, "tally_in_r_max_rounds")) *out = R_TALLY_MAX_ROUNDS;
     else if (!strcmp(name, "f_rec_passes")) *out = ctx->n_frec_pass;
     else if (!strcmp(name, "f_rec_builds")) *out = ctx->n_frec_build;
     else if (!strcmp(name, "f_rec_bytes")) *out = (int64_t)ctx->frec_bytes;

@@ -14,7 +14,7 @@
 #define FCD_PROF_PACK 3
 
 // Tuning / test knobs.  Read ONCE from the environment by fcd_ctx_create (FCD_R_PATH, FCD_R_UB, FCD_R_NOPAD, FCD_R_TOL,
-// FCD_F_TOL, FCD_F_FORM, FCD_R_POLL_LIMIT, FCD_R_WITHHOLD: "0" / unset = default), changed afterwards only through
+// FCD_F_TOL, FCD_F_FORM, FCD_TALLY_IN_R, FCD_R_KEEP_WORDS, ...: "0" / unset = default), changed afterwards only through
 // fcd_ctx_set_knob: no entry point reads the environment.
 struct fcd_knobs {
     int r_path;        // 0: blocked r pass -- pipelined one-launch form where its grid fits the device at once, else one launch
@@ -36,6 +36,11 @@ struct fcd_knobs {
     int f_pack;        // 1: the r pass's packing launch in every sweep (default: only where the f pass cannot write the packed f words)
     int f_records;     // pair-tile f pass reads pair records made once per call: 0 = in calls of at least F_REC_MIN_SWEEPS pair-tile
                        // sweeps, 1 = never (every tile builds its own), 2 = whenever the pair-tile form runs
+    int tally_in_r;    // f half of the tally inside the pipelined r pass (its in-order workgroups, before their first block): 0 = where
+                       // a wave's rounds are at most R_TALLY_MAX_ROUNDS, 1 = never (the tally after the pass counts f), 2 = wherever
+                       // the form allows (16-wave in-order workgroups)
+    int r_keep_words;  // 1: the tally makes the next pass's r words from the r bits (default: the pass's two r-word buffers swap
+                       // roles from sweep to sweep -- what a pass wrote as r_Sn is the next pass's r_S)
 };
 
 // kernels whose dynamic-LDS limit is raised with hipFuncSetAttribute: done once per (kernel, size) and remembered here
@@ -73,6 +78,7 @@ struct fcd_ctx {
     int r_form_last;               // form of the last blocked r pass: 1 step-per-launch, 2 pipelined, 3 one-launch with counters (fcd_ctx_stat)
     long long n_pack;              // packing launches of the r pass so far (fcd_ctx_stat "pack_launches")
     long long n_pack_tally;        // ... of them that carried the f half of the tally (fcd_ctx_stat "tally_f_in_pack")
+    long long n_r_tally;           // pipelined r pass launches that carried it (fcd_ctx_stat "tally_f_in_r")
     long long n_frec_pass;         // f passes that read prebuilt pair records (fcd_ctx_stat "f_rec_passes")
     long long n_frec_build;        // launches of the kernel that builds them (fcd_ctx_stat "f_rec_builds")
     void *log_tab;     // K_lik tables (fcd_fastmath.h): 64 x 2^(-j/64), 512 x {1/m_i, log m_i} (device, 8.5 KiB)
@@ -187,6 +193,13 @@ struct fcd_tally_f {
     unsigned long long *acc;           // nullable: context-owned sums, [1..3] = number of f == 0, 1, 2
     uint32_t *cnt_f;                   // nullable
 };
+// The pipelined r pass carries it too, in its in-order workgroups (16 waves each, nD of them), which can do nothing before
+// the first panel step has published its values.  Only where that wait covers the count: a wave walks
+// R = ceil(C / (64 nD)) * ceil(GW / 16) rounds of four edges x 16 chain words, and the pass carries the f half where
+// R <= R_TALLY_MAX_ROUNDS (cfg3: R = 4; few patients mean few in-order workgroups and many rounds, which would sit on the
+// pass's serial path).  Measured at Nreg 200, 1024 chains (profiles/tally_in_r_pass_cfg3.txt): per launch that carries it the
+// pass grows by 0.7 us at R = 4 and 0.4-1.6 us at R = 5 -- inside what repeated runs differ by -- and by 7-8 us at R = 6 and 7.
+constexpr int R_TALLY_MAX_ROUNDS = 5;
 // one launch of the (f_c, mixture case) count kernel of fcd_post.hip: acc (C, U, 3, 3) = (accumulate ? acc : 0) + counts of
 // this state; T = uint32_t or double
 struct fcd_geo;
@@ -613,12 +626,14 @@ struct fcd_sweep_step {
     int64_t sweep;
     uint8_t *fsq;                  // square copy of the f state, or nullptr
     bool f_packed;                 // f pass: write the r pass's f words (f_S) in their final form (pair tiles), no square copy
-    bool r_packed;                 // r pass: the previous sweep's tally has written r_S and cleared the marks
+    bool r_packed;                 // r pass: r_S holds the r words (the previous pass wrote them, or the tally made them) and the
+                                   // previous sweep's tally has cleared the marks
     bool ru_ready;                 // f pass: the previous sweep's tally has made the slot words
     const void *f_rec;             // f pass (f_packed): pair records made for this call, or nullptr (the tiles build their own)
     bool sentinels_in_place;       // r pass: P holds the sentinels a COMPLETED pipelined pass of this shape left behind
-    const fcd_tally_f *tally_f;    // r pass: the f half of the tally to carry in the packing launch, or nullptr ...
-    bool tally_f_done;             // ... and whether it did (out)
+    const fcd_tally_f *tally_f;    // r pass: the f half of the tally to carry in the packing launch or in the pipelined launch, or
+    bool tally_f_done;             // nullptr ... and whether one of them did (out)
+    bool r_flip;                   // r pass: the two r-word buffers of the plan have swapped roles (r_S lies at pl.r_Sn, r_Sn at pl.r_S)
 };
 int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step &st);   // fcd_gibbs.hip
 int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st);         // fcd_gibbs_r.hip

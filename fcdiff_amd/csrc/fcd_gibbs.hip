@@ -1050,8 +1050,8 @@ struct tally_args {
     uint32_t *cnt_f, *cnt_r;           // nullable (both or neither)
     double *hyper;                     // nullable: M-step target
     uint32_t *r_U;                     // nullable: slot words of the next f pass
-    uint2 *r_S;                        // nullable (with r_U): the r words of the next blocked r pass (pack_r_item) ...
-    uint32_t *marks;                   // ... and its marks, cleared
+    uint2 *r_S;                        // nullable (with r_U; knob r_keep_words): the r words of the next blocked r pass (pack_r_item)
+    uint32_t *marks;                   // nullable (with r_U): its marks, cleared
     int NBLK;                          // blocks of 16 regions
     int n_f_blocks;                    // blocks that read the f state (0: done elsewhere)
     int n_r_blocks;                    // blocks that count the r bits (at least; the f blocks do too); the rest make r_U (and r_S)
@@ -1087,14 +1087,20 @@ __global__ __launch_bounds__(1024, 8) void gibbs_tally_kernel(const tally_args a
         cr += sr;
     }
     if (a.r_U && (int)blockIdx.x >= nrb) {
-        // slot words of the next f pass: one wave per (w, n, word) item, as pack_ru_kernel; then (r_S) one wave per (w, u, b)
-        // item: the next r pass's r words and cleared marks, as its packing launch would make them
+        // slot words of the next f pass: one wave per (w, n, word) item, as pack_ru_kernel; then the next r pass's marks,
+        // cleared as its packing launch would: 64 of the GW U NBLK marks per item.  Its r words are the ones the pass before
+        // this launch wrote (the two buffers swap roles) -- or (r_S, knob r_keep_words) made here from the r bits, one wave
+        // per (w, u, b) item that also clears the item's mark.
         const int U = a.U, NW = a.NW, NBLK = a.NBLK;
-        const int items_u = GW * a.Nreg * NW, items = items_u + (a.r_S ? GW * U * NBLK : 0);
+        const int n_marks = a.marks ? GW * U * NBLK : 0;
+        const int items_u = GW * a.Nreg * NW, items = items_u + (a.r_S ? n_marks : (n_marks + 63) / 64);
         for (int item = ((int)blockIdx.x - nrb) * 16 + wave; item < items; item += ((int)gridDim.x - nrb) * 16) {
             if (item < items_u) {
                 const int jw = item % NW, wn = item / NW;                   // wn = w*Nreg + n
                 a.r_U[ru_index(wn, NW, jw, lane)] = pack_ru_word(r_bits, wn, U, jw, lane);
+            } else if (!a.r_S) {
+                const int m = (item - items_u) * 64 + lane;
+                if (m < n_marks) a.marks[m] = 0u;
             } else {
                 const int it = item - items_u, b = it % NBLK, wu = it / NBLK;      // wu = w*U + u
                 if (lane == 0) a.marks[it] = 0u;
@@ -1443,7 +1449,7 @@ static int launch_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_
     a.f_state = f_state; a.r_bits = r_bits;
     a.C = g.C; a.NU = Nreg * U; a.G = G;
     a.GW = g.GW; a.Nreg = (int)Nreg; a.U = (int)U; a.NW = ru_words;
-    a.r_S = r_U ? r_S : nullptr; a.marks = marks;
+    a.marks = r_U ? marks : nullptr; a.r_S = a.marks ? r_S : nullptr;
     a.NBLK = (int)((Nreg + R_NB - 1) / R_NB);
     a.acc = (counts || hyper) ? (unsigned long long *)ctx->acc : nullptr;
     a.counts_out = reinterpret_cast<unsigned long long *>(counts);
@@ -1461,7 +1467,11 @@ static int launch_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_
         if (rb > a.n_f_blocks) blocks = rb;
     }
     if (r_U) {
-        int64_t ru_blocks = ((int64_t)g.GW * Nreg * a.NW + (a.r_S ? (int64_t)g.GW * U * a.NBLK : 0) + 15) / 16;
+        const int64_t n_marks = a.marks ? (int64_t)g.GW * U * a.NBLK : 0;
+        int64_t ru_blocks = ((int64_t)g.GW * Nreg * a.NW + (a.r_S ? n_marks : (n_marks + 63) / 64) + 15) / 16;
+        // At most one per CU.  With the f half counted elsewhere the grid is then one round of the device's places (two
+        // 1024-thread workgroups per CU: 10 + 256 of 512 at cfg3); filling the round -- 2 num_cu less the counting workgroups,
+        // 1.6 items per wave instead of 3.2 -- measured the same (profiles/tally_in_r_pass_cfg3.txt).
         if (ru_blocks > ctx->num_cu) ru_blocks = ctx->num_cu;
         blocks += ru_blocks;
     }
@@ -1533,7 +1543,8 @@ static const struct {
 // 'gibbs'), run_chains and bench.py call) and fcd_gibbs_sweeps.  Per sweep: f pass (1 launch), packing for the r pass (1, in
 // the first sweep of a call only where the f pass can write the packed f words: packed_ok), r pass (one pipelined launch, or
 // ceil(Nreg/16) + 1 block steps), tally (1) -- the tally also carries the M-step, the slot words of the next f pass and, with
-// packed_ok, the r words of the next r pass.  hyper_m: what the M-step writes (nullptr when mstep_every == 0); acc_mask: the
+// packed_ok, the cleared marks of the next r pass (whose r words are the ones this pass wrote); its f half rides in the packing
+// launch or in the pipelined r pass where they take it.  hyper_m: what the M-step writes (nullptr when mstep_every == 0); acc_mask: the
 // slots of the context's sweep accumulators to add to (bit k = slot k).
 static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int64_t n_sweeps, int64_t mstep_every,
                       int64_t accumulate_from, int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r, double *hyper_m,
@@ -1553,8 +1564,8 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         if (rc) return rc;
         fsq = (uint8_t *)ctx->fsq;
     }
-    // From the second sweep of a call on, the U <= 64 f pass writes the r pass's f words itself (pair-aligned tiles) and the
-    // tally before it has made the r words and cleared the marks: no packing launch.  The first sweep, the any-U f kernel,
+    // From the second sweep of a call on, the U <= 64 f pass writes the r pass's f words itself (pair-aligned tiles), the r
+    // pass before it has left the r words and the tally before it has cleared the marks: no packing launch.  The first sweep, the any-U f kernel,
     // the reference edge ids, knob r_refill and knob f_pack = 1 keep the packing launch (from the square copy).
     const bool packed_ok = pl.f_form == FCD_F_PAIR && c.lMf && c.lMd && pl.r_blocked && pl.r_idx32 &&
                            c.edge_mode == FCD_EDGE_SYMMETRIC && ctx->knobs.f_pack != 1 && !ctx->knobs.r_refill;
@@ -1591,7 +1602,8 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         const bool do_m = mstep_every > 0 && (i + 1) % mstep_every == 0;
         const bool do_a = cnt_f && st.sweep >= accumulate_from;
         // the f half of this sweep's tally rides in the r pass's packing launch (beside it, not after the pass) where there
-        // is one; else the tally after the pass counts it
+        // is one, else in the pipelined pass's in-order workgroups (while they wait) where the rule allows; else the tally
+        // after the pass counts it
         fcd_tally_f tf;
         tf.f_state = c.f_state; tf.C = g.C; tf.G = G; tf.GW = g.GW;
         tf.acc = (do_m || (last && counts)) ? (unsigned long long *)ctx->acc : nullptr;
@@ -1599,7 +1611,7 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         st.tally_f = (tf.acc || tf.cnt_f) ? &tf : nullptr;
         rc = fcd_gibbs_r_pass(ctx, c, st);
         if (rc) {
-            // the packing launch may already have added this sweep's f counts into the context's accumulators and no tally
+            // the packing launch (or a pipelined pass) may already have added this sweep's f counts into the context's accumulators and no tally
             // will draw the ticket that zeroes them: leave them clean for the next call
             if (tf.acc) (void)hipMemsetAsync(ctx->acc, 0, 8 * sizeof(unsigned long long), s);
             return rc;
@@ -1607,7 +1619,12 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         st.sentinels_in_place = pair_form && ctx->r_form_last == 2;        // (a pipelined pass has just been queued)
         // the r pass's scratch is dead once its last launch is queued: the slot words of the next f pass go to their place
         uint32_t *r_U_next = (pair_form && !last) ? (uint32_t *)((char *)ctx->ws + pl.r_U) : nullptr;
-        uint2 *r_S_next = (packed_ok && r_U_next) ? (uint2 *)((char *)ctx->ws + pl.r_S) : nullptr;      // (and the marks)
+        // ... and the r words of the next r pass with its marks, cleared.  The words are there already: what this pass wrote
+        // as r_Sn (the redrawn bytes of every block) is the next pass's r_S, so the two buffers swap roles -- inside this
+        // call; every call starts from the plan's assignment.  Knob r_keep_words: the tally makes them from the r bits.
+        const bool r_next = packed_ok && r_U_next;
+        const bool keep_words = ctx->knobs.r_keep_words == 1;
+        uint2 *r_S_next = (r_next && keep_words) ? (uint2 *)((char *)ctx->ws + (st.r_flip ? pl.r_Sn : pl.r_S)) : nullptr;
         int64_t *cts = (last ? counts : nullptr);
         // Several ranks (a communicator on the context): the tally leaves this rank's counts in the context's vector, RCCL sums
         // it over the ranks in place ON THIS STREAM, a one-thread kernel makes the M-step from the pooled counts -- all queued
@@ -1617,7 +1634,7 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         if (do_m || do_a || cts || r_U_next) {
             rc = launch_tally(ctx, c.f_state, c.r_bits, Nreg, U, G, g, tally_counts, do_a ? cnt_f : nullptr, do_a ? cnt_r : nullptr,
                               (do_m && !pooled) ? hyper_m : nullptr, r_U_next, pl.f_NW, s, st.tally_f_done, r_S_next,
-                              (uint32_t *)((char *)ctx->ws + pl.marks));
+                              r_next ? (uint32_t *)((char *)ctx->ws + pl.marks) : nullptr);
             if (rc) {
                 if (tf.acc) (void)hipMemsetAsync(ctx->acc, 0, 8 * sizeof(unsigned long long), s);
                 return rc;
@@ -1645,7 +1662,8 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
             }
         }
         st.ru_ready = r_U_next != nullptr;
-        st.r_packed = r_S_next != nullptr;
+        st.r_packed = r_next;
+        if (r_next && !keep_words) st.r_flip = !st.r_flip;
     }
     return FCD_OK;
 }

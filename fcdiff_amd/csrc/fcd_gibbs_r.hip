@@ -237,6 +237,8 @@ struct r_step_args {
     int poll_limit;         // pipelined form: polls before a wait is given up (R_POLL_LIMIT; smaller only through the test hook)
     int withhold;           // TEST HOOK (knob r_withhold): the in-order role never sets its marks
     int dsplit;             // pipelined form: two in-order workgroups per patient (8 chain words each, two CUs)
+    fcd_tally_f tf;         // pipelined form: the f half of the sweep's tally, counted by the in-order workgroups before their
+                            // first block (f_state == nullptr: nothing rides; 16-wave workgroups only)
 };
 
 // agent-scope (memory-side) access to what crosses workgroups inside the pipelined launch; plain otherwise
@@ -1286,6 +1288,11 @@ __global__ __launch_bounds__(1024, WPE) void gibbs_r_pipe_kernel(const r_step_ar
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int blk = blockIdx.x;
     if (blk < a.nD) {
+        // The f half of the tally, once per workgroup and launch (not per group of chain words): the in-order role cannot
+        // start before P(0) has published its values, and the f state is final since the f pass.  Workgroup ids 0 .. nD - 1
+        // occur once each: every cnt_f word has one owner wave.  Its scratch is the start of the dynamic LDS (this kernel
+        // keeps no static LDS); the function's closing barrier comes before the first staging writes there.
+        if (a.tf.f_state) fcd_tally_f_block<16>(a.tf, blk, a.nD, reinterpret_cast<unsigned long long (*)[3]>(smem));
         // (dsplit: two workgroups per patient, workgroup blk and blk + U: 8 chain words each)
         const int half = a.dsplit ? blk / a.u_n : -1;
         for (int wg = 0; wg < a.nWG; ++wg) pipe_diag(a, a.u_lo + (a.dsplit ? blk % a.u_n : blk), wg, half, smem, err);
@@ -1605,13 +1612,14 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
     int rc = fcd_ws_reserve(ctx, pl.ws_bytes);
     if (rc) return rc;
     char *ws = (char *)ctx->ws;
-    uint2 *f_S = (uint2 *)(ws + pl.f_S), *r_S = (uint2 *)(ws + pl.r_S);
+    // (the sweep loop swaps the two r-word buffers from sweep to sweep: what a pass wrote as r_Sn the next one reads as r_S)
+    uint2 *f_S = (uint2 *)(ws + pl.f_S), *r_S = (uint2 *)(ws + (st.r_flip ? pl.r_Sn : pl.r_S));
     fcd_abl_refresh(s);
     const int ub = pl.r_ub;
     const size_t shmem = pl.r_shmem;
     r_step_args a;
     a.lMd = c.lMd; a.hyper = c.hyper; a.f_S = f_S;
-    a.r_S = r_S; a.r_Sn = (uint2 *)(ws + pl.r_Sn); a.r_bits = c.r_bits;
+    a.r_S = r_S; a.r_Sn = (uint2 *)(ws + (st.r_flip ? pl.r_S : pl.r_Sn)); a.r_bits = c.r_bits;
     a.Pbuf[0] = (double *)(ws + pl.P[0]); a.Pbuf[1] = (double *)(ws + pl.P[1]);
     a.flags = nullptr;
     a.Nreg = (int)Nreg; a.U = (int)U; a.NBLK = NBLK; a.GW = g.GW;
@@ -1624,6 +1632,7 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
     a.tol = 16.0 * FCD_LOGIT_FAST_ERR;
     a.poll_limit = ctx->knobs.r_poll_limit > 0 ? ctx->knobs.r_poll_limit : R_POLL_LIMIT;
     a.withhold = ctx->knobs.r_withhold;
+    a.tf.f_state = nullptr; a.tf.C = 0; a.tf.G = 0; a.tf.GW = 0; a.tf.acc = nullptr; a.tf.cnt_f = nullptr;
     if (ctx->knobs.r_tol > a.tol) a.tol = ctx->knobs.r_tol;   // test hook: a huge value sends every draw through the exact path
     const int nUC = (int)((U + ub - 1) / ub);
     // Pipelined one-launch form (the default where it fits; knob r_path = 3 keeps the step-per-launch form): needs every
@@ -1662,8 +1671,8 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
             a.dsplit = 0;          // (the step form below: one in-order workgroup per patient)
         }
     }
-    // (f_packed + r_packed: the f pass has written the f words in their final form and the previous sweep's tally the r words
-    // and the cleared marks -- nothing to pack unless the pipelined pass needs its sentinels again)
+    // (f_packed + r_packed: the f pass has written the f words in their final form, the r words are in place and the previous
+    // sweep's tally has cleared the marks -- nothing to pack unless the pipelined pass needs its sentinels again)
     const bool packed = st.f_packed && st.r_packed && (!pipe || (pinit.P[0] == nullptr && pinit.P[1] == nullptr));
     if (!packed) {
         // one launch packs the f words of every region and the r words of every patient
@@ -1704,13 +1713,29 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
     ctx->r_form_last = pipe ? 2 : 1;
     if (pipe) {
         a.flags = pinit.marks;
+        // the f half of the tally, unless the packing launch above has it: in the in-order workgroups where they have 16 waves
+        // (fcd_tally_f_block<16> sums 16 rows of its scratch) and the count fits their wait (R_TALLY_MAX_ROUNDS)
+        bool ride = false;
+        if (st.tally_f && !st.tally_f_done && ctx->knobs.tally_in_r != 1 && a.wpb == 16) {
+            const int64_t rounds = ((g.C + 64 * (int64_t)a.nD - 1) / (64 * (int64_t)a.nD)) * ((g.GW + 15) / 16);
+            ride = ctx->knobs.tally_in_r == 2 || rounds <= R_TALLY_MAX_ROUNDS;
+        }
+        if (ride) a.tf = *st.tally_f;
         rc = with_ub(ub, [&](auto UB, auto WPE) { return launch_pipe<UB, WPE>(ctx, a, shmem, &pipe, true, s); });
-        if (rc || pipe) return rc;
+        if (rc) return rc;
+        if (pipe) {
+            if (ride) {         // (only now: the launch is in the stream)
+                st.tally_f_done = true;
+                ctx->n_r_tally += 1;
+            }
+            return FCD_OK;
+        }
         // the runtime refused the cooperative launch (grid not co-resident after all; or knob r_coop = 2): the step-per-launch
-        // form instead
+        // form instead, and the tally after the pass counts f
         ctx->r_form_last = 1;
         a.flags = nullptr;
         a.dsplit = 0;
+        a.tf.f_state = nullptr;
     }
     // one launch per block step: launch step = D(step - 1) workgroups + P(step) workgroups
     for (int step = 0; step <= NBLK; ++step) {

@@ -88,7 +88,7 @@ int fcd_ctx_destroy(fcd_ctx *ctx);
  * (Nreg, U, G) while the knobs stay as they are.  Synchronises when it grows something. */
 int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
 /* Tuning / test knobs (defaults: environment FCD_R_PATH, FCD_R_UB, FCD_R_NOPAD, FCD_R_DSPLIT, FCD_R_COOP, FCD_R_REFILL, FCD_R_TOL, FCD_F_TOL, FCD_F_FORM,
- * FCD_F_PACK, FCD_CORR_FORM, read once by fcd_ctx_create; 0 = default everywhere; the two test hooks at the end of the list are NOT read
+ * FCD_F_PACK, FCD_CORR_FORM, FCD_TALLY_IN_R, FCD_R_KEEP_WORDS, read once by fcd_ctx_create; 0 = default everywhere; the two test hooks at the end of the list are NOT read
  * from the environment -- a stray variable must not be able to make a fit give up):
  *   "r_path"    0: blocked r pass in its pipelined one-launch form (marks / sentinels in device memory instead of
  *                  kernel boundaries) wherever every workgroup is resident at once, else one launch per block step;
@@ -117,6 +117,14 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
  *               every call that has one (A/B runs and tests; not read from the environment).  The table (stat
  *               "f_rec_bytes") belongs to the context, fcd_ctx_reserve sizes it; above 256 MB, or where the device has no
  *               room for it, the tiles build their own records
+ *   "tally_in_r" the f half of a sweep's tally (pooled counts of f, cnt_f) inside the pipelined r pass, counted by its in-order
+ *               workgroups before their first block, while they wait for the first panel values: 0 = where those workgroups
+ *               have 16 waves and a wave walks at most "tally_in_r_max_rounds" rounds of four edges (cfg3: 4 rounds), 1 = never
+ *               (the tally launch after the pass counts f), 2 = wherever the workgroups have 16 waves.  The packing launch
+ *               of a call's first sweep keeps the f half it carries (stat "tally_f_in_pack"); the step-per-launch form carries none
+ *   "r_keep_words" 1: the tally makes the next r pass's r words from the r bits (default: inside a fcd_gibbs_run /
+ *               fcd_gibbs_sweeps call the pass's two r-word buffers swap roles from sweep to sweep -- the words a pass wrote
+ *               are the next pass's -- and the tally only clears the marks)
  *   "r_poll_limit", "r_withhold"  TEST HOOKS of the pipelined r pass: bound every device-side poll by this many polls /
  *               the in-order role never announces a block (a panel wave then gives its wait up, fcd_ctx_check reports it)
  *   "r_coop" = 2  TEST HOOK: every pipelined launch of the r pass acts as if the runtime had refused a cooperative launch
@@ -128,7 +136,8 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value);
 /* Counters of the context: "n_alloc" device allocations made so far, "ws_bytes", "fsq_bytes"; "r_form_last" = the form
  * the last blocked r pass ran in (1 one launch per block step, 2 pipelined one-launch form, 3 one-launch form with
  * counters); "pack_launches" = packing launches of the r pass made so far; "tally_f_in_pack" = those of them that also
- * carried the f half of the sweep's tally; "f_rec_passes" = f passes that read prebuilt pair records, "f_rec_builds" =
+ * carried the f half of the sweep's tally; "tally_f_in_r" = launches of the pipelined r pass that carried it,
+ * "tally_in_r_max_rounds" = the threshold of knob tally_in_r = 0; "f_rec_passes" = f passes that read prebuilt pair records, "f_rec_builds" =
  * launches of the kernel that makes them, "f_rec_bytes" = the size of their table, "f_rec_min_sweeps" = the threshold of
  * knob f_records = 0; "dev_err" = the error word of the pipelined r pass as the host sees it now (see
  * fcd_ctx_check); "pipe_grid" / "pipe_capacity" = the grid of the last pipelined attempt of the r pass (its empty
