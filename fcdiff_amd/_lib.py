@@ -113,6 +113,9 @@ SIGNATURES = {
     "fcd_patient_groups_set": (_int, [_p, _p, _p, _i64, _p, _i64, _int]),
     "fcd_gibbs_patient_group_tally": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "fcd_gibbs_set_patient_group_accumulator": (_int, [_p, _p, _p, _i64, _i64, _i64]),
+    "fcd_patient_traits_set": (_int, [_p, _p, _p, _i64, _i64, _int]),
+    "fcd_gibbs_patient_trait_tally": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "fcd_gibbs_set_patient_trait_accumulator": (_int, [_p, _p, _p, _i64, _i64, _i64]),
     "fcd_gibbs_coanomaly_tally": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "fcd_gibbs_set_coanomaly_accumulator": (_int, [_p, _p, _p, _i64, _i64, _i64]),
     "fcd_vb_coanomaly": (_int, [_p, _p, _i64, _i64, _p, _p, _p]),

@@ -161,6 +161,9 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->pg_J = ctx->pg_P = ctx->pg_umax = ctx->pg_total = ctx->pg_bins_max = 0;
     ctx->pg_max_member = -1;
     ctx->pg_with_rs = 0;
+    ctx->pt_dev = nullptr;
+    ctx->pt_Q = ctx->pt_U = ctx->pt_umax = 0;
+    ctx->pt_with_rs = 0;
     ctx->acc = nullptr;
     ctx->nan_slots = nullptr;
     ctx->dbg = nullptr;
@@ -255,6 +258,7 @@ int fcd_ctx_destroy(fcd_ctx *ctx) {
     if (ctx->count_ws) (void)hipFree(ctx->count_ws);
     if (ctx->rs_dev) (void)hipFree(ctx->rs_dev);
     if (ctx->pg_dev) (void)hipFree(ctx->pg_dev);
+    if (ctx->pt_dev) (void)hipFree(ctx->pt_dev);
     if (ctx->acc) (void)hipFree(ctx->acc);
     if (ctx->nan_slots) (void)hipFree(ctx->nan_slots);
     if (ctx->dbg) (void)hipFree(ctx->dbg);

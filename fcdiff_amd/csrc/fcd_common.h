@@ -55,10 +55,12 @@ enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA
 // (Nreg, U+1) histograms of the anomalous-region counts (fcd_gibbs_set_count_accumulator), (Nreg, Nreg) / (U, U) co-anomaly
 // counts (fcd_gibbs_set_coanomaly_accumulator), (J, U, S_max+1) / (J, U+1) histograms of the counts over the context's region
 // sets (fcd_gibbs_set_region_set_accumulator), (J, R, Umax+1) / flat joint histograms of the counts over the context's patient
-// groups and contrasts (fcd_gibbs_set_patient_group_accumulator).  fcd_gibbs.hip holds the launch of each.
-enum { FCD_ACC_PAIR, FCD_ACC_COUNT, FCD_ACC_COANOMALY, FCD_ACC_REGION_SET, FCD_ACC_PATIENT_GROUP, FCD_ACC_N };
+// groups and contrasts (fcd_gibbs_set_patient_group_accumulator), (Q, R, Umax+1+128+3) uint32 / (Q, R, Umax+1) int64 rank-sum
+// histograms and sums over the context's patient traits (fcd_gibbs_set_patient_trait_accumulator).  fcd_gibbs.hip holds the
+// launch of each.
+enum { FCD_ACC_PAIR, FCD_ACC_COUNT, FCD_ACC_COANOMALY, FCD_ACC_REGION_SET, FCD_ACC_PATIENT_GROUP, FCD_ACC_PATIENT_TRAIT, FCD_ACC_N };
 struct fcd_sweep_acc {
-    uint32_t *buf[2];              // buf[0] == nullptr: detached
+    uint32_t *buf[2];              // buf[0] == nullptr: detached (the patient-trait slot keeps its int64 buffer in buf[1])
     int64_t nreg, u, every;        // the shape it was made for; added at every this many sweeps from accumulate_from on
 };
 
@@ -111,6 +113,11 @@ struct fcd_ctx {
     int64_t pg_J, pg_P, pg_umax, pg_max_member;        // groups (0: none), contrasts, largest group, largest member
     int64_t pg_total, pg_bins_max;                     // members in all groups; joint bins of the largest contrast
     int pg_with_rs;                                    // 1: the context's region sets are rows after the regions
+    // patient traits (fcd_patient_traits_set): one device buffer (owned) of the words 2 score + known (Q, U) and the numbers
+    // of known patients (Q), checked on the host
+    void *pt_dev;
+    int64_t pt_Q, pt_U, pt_umax;                       // traits (0: none), the patients they were set for, largest n_q
+    int pt_with_rs;                                    // 1: the context's region sets are rows after the regions
     // optional per-kernel timing with HIP events on the launch stream (fcd_prof_enable / fcd_prof_collect)
     int prof_on;
     hipEvent_t *prof_ev[FCD_PROF_SLOTS];   // pairs (begin, end)
@@ -225,6 +232,11 @@ int fcd_region_set_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nr
 int fcd_patient_group_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t G);
 int fcd_patient_group_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
                                    uint32_t *hist_group, uint32_t *hist_joint, hipStream_t s);
+// the patient-trait kernels of fcd_patient_traits.hip (two launches): histogram and sums += the rank-sum statistics of this
+// state over the context's traits; same scratch, grown by fcd_patient_trait_ws_reserve (fcd_gibbs_run: before its loop)
+int fcd_patient_trait_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t G);
+int fcd_patient_trait_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
+                                   uint32_t *trait_hist, int64_t *trait_sum, hipStream_t s);
 // bracket ONE kernel launch with events when profiling is on (no-ops otherwise)
 void fcd_prof_begin(fcd_ctx *ctx, int slot, hipStream_t s);
 void fcd_prof_end(fcd_ctx *ctx, int slot, hipStream_t s);

@@ -1528,6 +1528,9 @@ static int acc_launch_region_set(fcd_ctx *ctx, const fcd_sweep_call &c, const fc
 static int acc_launch_patient_group(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_geo &g, const fcd_sweep_acc &a, hipStream_t s) {
     return fcd_patient_group_tally_launch(ctx, c.r_bits, c.Nreg, c.U, c.G, g, a.buf[0], a.buf[1], s);
 }
+static int acc_launch_patient_trait(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_geo &g, const fcd_sweep_acc &a, hipStream_t s) {
+    return fcd_patient_trait_tally_launch(ctx, c.r_bits, c.Nreg, c.U, c.G, g, a.buf[0], (int64_t *)a.buf[1], s);
+}
 static const struct {
     const char *msg_shape;
     int (*launch)(fcd_ctx *, const fcd_sweep_call &, const fcd_geo &, const fcd_sweep_acc &, hipStream_t);
@@ -1537,6 +1540,7 @@ static const struct {
     {"fcd_gibbs_run: the attached co-anomaly accumulator was made for Nreg=%lld, U=%lld", acc_launch_coanomaly},
     {"fcd_gibbs_run: the attached region-set accumulator was made for Nreg=%lld, U=%lld", acc_launch_region_set},
     {"fcd_gibbs_run: the attached patient-group accumulator was made for Nreg=%lld, U=%lld", acc_launch_patient_group},
+    {"fcd_gibbs_run: the attached patient-trait accumulator was made for Nreg=%lld, U=%lld", acc_launch_patient_trait},
 };
 
 // The sampler loop of ONE rank between two exchanges of pooled statistics: fcd_gibbs_run (what UnsharedRegionFit(method=
@@ -1695,6 +1699,10 @@ extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, 
     }
     if (acc_mask >> FCD_ACC_PATIENT_GROUP & 1u) {
         rc = fcd_patient_group_ws_reserve(ctx, Nreg, G);
+        if (rc) return rc;
+    }
+    if (acc_mask >> FCD_ACC_PATIENT_TRAIT & 1u) {
+        rc = fcd_patient_trait_ws_reserve(ctx, Nreg, G);
         if (rc) return rc;
     }
     return sweep_loop(ctx, c, sweep0, n_sweeps, mstep_every, accumulate_from, counts, cnt_f, cnt_r, hyper, acc_mask);

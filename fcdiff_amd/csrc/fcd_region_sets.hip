@@ -156,6 +156,8 @@ extern "C" int fcd_region_sets_set(fcd_ctx *ctx, const int32_t *offsets_host, co
         return fcd_fail(ctx, FCD_ERR_ARG, "fcd_region_sets_set: the region-set accumulator is attached");
     if (ctx->pg_with_rs && ctx->sweep_acc[FCD_ACC_PATIENT_GROUP].buf[0])
         return fcd_fail(ctx, FCD_ERR_ARG, "fcd_region_sets_set: the patient-group accumulator is attached with the sets as rows");
+    if (ctx->pt_with_rs && ctx->sweep_acc[FCD_ACC_PATIENT_TRAIT].buf[0])
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_region_sets_set: the patient-trait accumulator is attached with the sets as rows");
     const bool clear = J == 0 && !offsets_host && !members_host;
     int64_t smax = 0, max_member = -1, total = 0;
     if (!clear) {

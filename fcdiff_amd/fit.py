@@ -28,6 +28,9 @@ New knobs (all optional; defaults reproduce the reference):
                                                                gibbs: histograms of the number of anomalous patients per
                                                                group of patients, and joint ones per contrast of two groups,
                                                                for patient_group_posterior()
+    patient_traits, patient_traits_every                       gibbs: rank-sum (AUC) histograms between the anomalous and the
+                                                               other patients of a row, per trait of the patients, for
+                                                               patient_trait_posterior()
     missing_data                                               True: NaN entries of b / bt are unobserved and integrated out
 
 Differences from the reference that are deliberate and documented:
@@ -49,7 +52,8 @@ from . import util
 from . import score as _score
 from . import tables
 from .gibbs import (GibbsEngine, run_chains, allreduce_counts, pool_u32, pair_sweeps_in, ACCUMULATORS, PAIR_COUNT_MAX,
-                    COUNT_MAX_NREG, COUNT_MAX_U, region_sets_csr, patient_groups_csr, patient_group_contrasts)
+                    COUNT_MAX_NREG, COUNT_MAX_U, region_sets_csr, patient_groups_csr, patient_group_contrasts,
+                    patient_traits_scores, PATIENT_TRAIT_BINS)
 
 # The knobs of a gibbs fit that attach one of the sampler's accumulators: knob, its period knob, what the messages call it,
 # the row of gibbs.ACCUMULATORS, and the attributes the pooled buffers and the number of sweeps behind them are left in.
@@ -165,6 +169,15 @@ class UnsharedRegionFit(object):
         self.patient_group_sizes = None     # then "set:<name>" for the region sets), and the contrasts as pairs of group indices
         self.patient_group_rows = None
         self.patient_group_pairs = None
+        self.patient_traits = None          # traits of the patients for patient_trait_posterior(): a dict name -> (U,) values, a
+                                            # sequence of such vectors or an array (Q, U); NaN = not known for this patient
+        self.patient_traits_every = 1       # ... at every this many sweeps from burn_in on
+        self.patient_trait_hist = None      # (Q, R, Umax+1 + 128 + 3) int64: chains x sweeps (x ranks) by k, by AUC bin, by sign of A
+        self.patient_trait_sum = None       # (Q, R, Umax+1) int64: the sum of A over the states with that k
+        self.patient_trait_sweeps = 0       # number of sweeps behind them
+        self.patient_trait_names = None     # names of the traits behind them, how many patients each is known for, and the
+        self.patient_trait_n_known = None   # names of the R rows (the regions, then "set:<name>" for the region sets)
+        self.patient_trait_rows = None
         # True: every NaN of b / bt is an unobserved value, integrated out exactly (S_B sums the observed h only, lM = 0 at a
         # missing bt); False: NaN is read as a number, as the reference reads it.  Only NaN is missing, not +-inf.
         self.missing_data = False
@@ -764,6 +777,12 @@ class UnsharedRegionFit(object):
             self._refuse_patient_groups_shared()
             patient_group_contrasts(self.patient_group_contrasts, *patient_groups_csr(self.patient_groups, U))
             self._check_accumulator("patient_groups_every", "patient-group histograms")
+        (self.patient_trait_hist, self.patient_trait_sum, self.patient_trait_sweeps) = (None, None, 0)
+        (self.patient_trait_names, self.patient_trait_n_known, self.patient_trait_rows) = (None, None, None)
+        if self.patient_traits is not None:
+            self._refuse_patient_traits_shared()
+            patient_traits_scores(self.patient_traits, U)
+            self._check_accumulator("patient_traits_every", "patient-trait histograms")
         if self.anomaly_counts and (N > COUNT_MAX_NREG or U > COUNT_MAX_U):
             raise ValueError("anomaly-count histograms are made for at most %d regions and %d patients (here %d, %d)"
                              % (COUNT_MAX_NREG, COUNT_MAX_U, N, U))
@@ -778,6 +797,9 @@ class UnsharedRegionFit(object):
         if self.patient_groups is not None:         # (after the region sets: they are rows of these histograms)
             eng.set_patient_groups(self.patient_groups, self.patient_group_contrasts)
             eng.attach_patient_group_accumulator(self.patient_groups_every)
+        if self.patient_traits is not None:         # (after the region sets, for the same reason)
+            eng.set_patient_traits(self.patient_traits)
+            eng.attach_patient_trait_accumulator(self.patient_traits_every)
         pi2 = self._pi2()
         eng.set_hyper(np.asarray(self.model.gamma, dtype=np.float64), pi2)
         eng.init(float(pi2[1]))
@@ -848,6 +870,13 @@ class UnsharedRegionFit(object):
             self.patient_group_sweeps = eng.patient_group_sweeps
             (self.patient_group_names, self.patient_group_sizes) = (list(eng.group_names), sizes)
             (self.patient_group_rows, self.patient_group_pairs) = (eng.patient_group_row_names(), eng.group_contrasts.copy())
+        if getattr(eng, "patient_trait_acc", None) is not None:
+            (th, ts) = eng.patient_trait_acc
+            self.patient_trait_hist = pool_u32(th).cpu().numpy()
+            self.patient_trait_sum = allreduce_counts(ts.clone()).cpu().numpy()        # (int64 already)
+            self.patient_trait_sweeps = eng.patient_trait_sweeps
+            (self.patient_trait_names, self.patient_trait_n_known) = (list(eng.trait_names), eng.trait_n_known.copy())
+            self.patient_trait_rows = eng.patient_trait_row_names()
         if eng.coanomaly_acc is not None:
             states = t.tensor([eng.coanomaly_sweeps * eng.G], dtype=t.int64, device=eng.cnt_f.device)
             self.coanomaly_states = int(allreduce_counts(states).cpu()[0])
@@ -1074,6 +1103,60 @@ class UnsharedRegionFit(object):
         out = {"names": names, "sizes": sizes, "row_names": row_names, "p_count": p_count,
                "contrasts": [(names[a], names[b]) for (a, b) in pairs], "p_joint": p_joint}
         out.update(patient_group_summaries(p_count, p_joint, sizes, pairs, level))
+        return out
+
+    # ------------------------------------------------------------------ anomalies against an ordered trait of the patients
+    def _refuse_patient_traits_shared(self):
+        if self._shared:
+            raise ValueError("patient_traits relate the patients' own anomaly maps to a trait; SharedRegionFit has one "
+                             "population-level r")
+
+    def patient_trait_posterior(self, level=0.95):
+        """
+        Do the patients that are anomalous at row rho have the higher (or lower) trait?  For every trait of `patient_traits`
+        (values per patient; NaN = not known) and every row -- the Nreg regions and, with `region_sets`, the sets after them,
+        whose indicator is "patient u has an anomalous region in S" --, the posterior law of the rank-sum (Mann-Whitney)
+        statistic between the known patients that are anomalous at the row and those that are not:
+        AUC = P(an anomalous patient has the higher trait) + P(tie) / 2.  No threshold on the trait is needed, and only its
+        order counts.  A state with k anomalous among the n_q known patients is DEFINED where 0 < k < n_q.  From the last
+        run(method='gibbs'), as a dict (Q traits, Umax the largest n_q, R rows, NB = 128):
+            names, n_known, rows             the traits in the order given (list of str, (Q,) int64); "0" .. "Nreg-1", "set:<name>"
+            p_count     (Q, R, Umax+1)       P(k = i | data); zero beyond n_q, rows sum to 1
+            p_defined   (Q, R)               P(0 < k < n_q | data)
+            p_greater, p_less, p_equal  (Q, R)     P(AUC > 1/2), <, = among the defined states (decided on integers); NaN
+                                             where no state is defined
+            auc_mean    (Q, R)               E[AUC | defined], exact: from the sums of the integer statistic per k; NaN likewise
+            auc_hist    (Q, R, NB), auc_edges (NB+1,)     the law of AUC among the defined states in bins of width 1/NB (the
+                                             last bin holds AUC = 1); NaN likewise
+            auc_interval (Q, R, 2)           the outer edges of the bins in which the cumulative law reaches (1 - level)/2 from
+                                             below and from above (to within 1e-12): never narrower than the central `level`
+                                             interval of the AUC itself; NaN likewise
+            sweeps                           the number of sweeps behind the histograms
+        For a binary trait (ones, zeros) the sign of AUC - 1/2 is the sign of the rate difference of the patient-group
+        contrast (ones, zeros).  The patients are coupled through f, so the law does not follow from the per-patient marginals:
+        the histograms are counted over chains and the sweeps from burn_in on, every `patient_traits_every`-th, and kept as
+        `patient_trait_hist` / `patient_trait_sum`.  Needs `patient_traits` set before run(method='gibbs'); ValueError
+        otherwise, and for method='vb' (the law needs the sampler's chains) and SharedRegionFit (one population-level r).
+        Not provided: a mean-field or independent=True form (it needs a (k, A) convolution per row), and traits in score()
+        and membership().
+        """
+        self._refuse_patient_traits_shared()
+        if self.method != "gibbs":
+            raise ValueError("patient_trait_posterior() needs method='gibbs': the law of the rank-sum statistic needs the "
+                             "sampler's chains (the patients are coupled through f)")
+        if not 0.0 < float(level) < 1.0:
+            raise ValueError("level must lie in (0, 1)")
+        (th, ts) = (self.patient_trait_hist, self.patient_trait_sum)
+        if th is None or ts is None:
+            if self.patient_traits is None:
+                raise ValueError("no patient traits: set patient_traits before run(method='gibbs')")
+            raise ValueError("no patient-trait histograms: call run(method='gibbs') first")
+        n_known = np.asarray(self.patient_trait_n_known, dtype=np.int64)
+        if np.asarray(th)[:, :, :int(n_known.max()) + 1].sum() == 0:
+            raise ValueError("no sweep was accumulated into the patient-trait histograms (n_sweeps <= burn_in?)")
+        out = {"names": list(self.patient_trait_names), "n_known": n_known, "rows": list(self.patient_trait_rows),
+               "sweeps": int(self.patient_trait_sweeps)}
+        out.update(patient_trait_summaries(th, ts, n_known, level))
         return out
 
     # ------------------------------------------------------------------ co-anomaly
@@ -1366,6 +1449,8 @@ class SharedRegionFit(UnsharedRegionFit):
         self._edge_mode()
         if self.patient_groups is not None:
             self._refuse_patient_groups_shared()
+        if self.patient_traits is not None:
+            self._refuse_patient_traits_shared()
         super(SharedRegionFit, self).run()
 
     def _theta_sub_flags(self):
@@ -1576,6 +1661,41 @@ def patient_group_summaries(p_count, p_joint, sizes, pairs, level=0.95):
         for (i, q) in enumerate((q_lo, q_hi)):
             at = np.minimum((cum < q - 1e-12).sum(axis=1), len(order) - 1)
             out["diff_interval"][p, :, i] = diff[order][at]
+    return out
+
+
+def patient_trait_summaries(trait_hist, trait_sum, n_known, level=0.95):
+    """
+    The derived quantities of patient_trait_posterior() from the two accumulated buffers alone (host arithmetic): trait_hist
+    (Q, R, Umax+1 + NB + 3) and trait_sum (Q, R, Umax+1) as fcd_gibbs_patient_trait_tally fills them, n_known (Q,).  Returns
+    p_count, p_defined, p_greater, p_less, p_equal, auc_mean, auc_hist, auc_edges, auc_interval.
+    """
+    NB = PATIENT_TRAIT_BINS
+    h = np.asarray(trait_hist).astype(np.int64)
+    s = np.asarray(trait_sum).astype(np.int64)
+    n_known = np.asarray(n_known, dtype=np.int64)
+    (Q, R, K) = s.shape
+    if h.shape != (Q, R, K + NB + 3) or n_known.shape != (Q,) or int(n_known.max()) + 1 != K:
+        raise ValueError("trait_hist must be (Q, R, Umax+1+%d+3) and trait_sum (Q, R, Umax+1) with Umax = max(n_known)" % NB)
+    (counts, bins, signs) = (h[:, :, :K], h[:, :, K:K + NB], h[:, :, K + NB:])
+    total = counts.sum(axis=2).astype(np.float64)
+    defined = signs.sum(axis=2).astype(np.float64)
+    k = np.arange(K, dtype=np.int64)[None, :]
+    d2 = 2 * k * (n_known[:, None] - k)                              # 2 k (n_q - k); <= 0 where the state is not defined
+    weight = np.where(d2 > 0, 1.0 / np.maximum(d2, 1), 0.0)          # (Q, K)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = {"p_count": counts / total[:, :, None], "p_defined": defined / total,
+               "p_less": signs[:, :, 0] / defined, "p_equal": signs[:, :, 1] / defined, "p_greater": signs[:, :, 2] / defined,
+               "auc_mean": 0.5 + (s * weight[:, None, :]).sum(axis=2) / defined,
+               "auc_hist": bins / defined[:, :, None], "auc_edges": np.arange(NB + 1, dtype=np.float64) / NB}
+    alpha = (1.0 - float(level)) / 2.0
+    up = np.cumsum(out["auc_hist"], axis=2)
+    down = np.cumsum(out["auc_hist"][:, :, ::-1], axis=2)
+    lo = np.minimum((up < alpha - 1e-12).sum(axis=2), NB - 1)        # first bin at which the mass from below reaches alpha
+    hi = NB - 1 - np.minimum((down < alpha - 1e-12).sum(axis=2), NB - 1)
+    interval = np.stack([lo / float(NB), (hi + 1) / float(NB)], axis=2)
+    interval[defined == 0] = np.nan
+    out["auc_interval"] = interval
     return out
 
 

@@ -60,6 +60,17 @@ GROUP_ACCUMULATORS = (
                 "fcd_gibbs_set_patient_group_accumulator", None, "patient-group"),
 )
 (_PATIENT_GROUP,) = GROUP_ACCUMULATORS
+# The rank-sum (AUC) accumulator of the patient traits, again in a tuple of its own, walked last.  Its first buffer is uint32
+# like the others, (Q, R, Umax+1 + NB + 3); the second, (Q, R, Umax+1), is INT64 (sums of signed scores):
+# attach_patient_trait_accumulator() makes it, patient_trait_host() reads it as it is.
+PATIENT_TRAIT_MAX_U, PATIENT_TRAIT_MAX_TRAITS, PATIENT_TRAIT_BINS = 512, 16, 128     # fcd_patient_traits_set
+TRAIT_ACCUMULATORS = (
+    Accumulator("patient_trait", "patient_trait_acc", True,
+                lambda e: ((e.trait_Q, e.patient_trait_rows(), e.trait_umax + 1 + PATIENT_TRAIT_BINS + 3),
+                           (e.trait_Q, e.patient_trait_rows(), e.trait_umax + 1)),
+                "fcd_gibbs_set_patient_trait_accumulator", None, "patient-trait"),
+)
+(_PATIENT_TRAIT,) = TRAIT_ACCUMULATORS
 
 
 # the wording of _index_sets_csr()'s refusals for the two axes: knob, one set, many, a member, the mask's name and extent
@@ -169,6 +180,53 @@ def patient_group_contrasts(contrasts, names, offsets, members):
     return pairs, bin_offsets
 
 
+def patient_traits_scores(traits, U):
+    """
+    Traits of the patients -- a dict name -> (U,) values, a sequence of such vectors (named "0", "1", ...) or an array (Q, U);
+    NaN: not known for this patient -- as (names, scores (Q, U) int32, known (Q, U) bool, n_known (Q,) int64), what
+    fcd_patient_traits_set takes: scores[q, u] = 2 midrank_u - (n_q + 1) over the n_q known patients of trait q (tied values
+    share a midrank; integers in [-(n_q - 1), n_q - 1] that sum to 0), 0 where the trait is not known.  A binary trait with n1
+    ones and n0 zeros gives -n1 on the zeros and n0 on the ones.  ValueError for no trait, more than 16 traits, more than 512
+    patients, a vector that is not (U,) numbers, an infinite value, fewer than two known patients, or known values all equal.
+    """
+    U = int(U)
+    if U > PATIENT_TRAIT_MAX_U:
+        raise ValueError("patient traits are made for at most %d patients (here %d)" % (PATIENT_TRAIT_MAX_U, U))
+    if isinstance(traits, dict):
+        names = [str(k) for k in traits.keys()]
+        rows = list(traits.values())
+    else:
+        if isinstance(traits, np.ndarray) and traits.ndim != 2:
+            raise ValueError("a patient-trait array must be (Q, U=%d)" % U)
+        rows = list(traits)
+        names = [str(q) for q in range(len(rows))]
+    if len(rows) < 1:
+        raise ValueError("patient_traits holds no trait")
+    if len(rows) > PATIENT_TRAIT_MAX_TRAITS:
+        raise ValueError("patient_traits holds %d traits (at most %d)" % (len(rows), PATIENT_TRAIT_MAX_TRAITS))
+    scores = np.zeros((len(rows), U), dtype=np.int32)
+    known = np.zeros((len(rows), U), dtype=np.bool_)
+    for (q, (name, row)) in enumerate(zip(names, rows)):
+        try:
+            y = np.asarray(row, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("patient trait %r must hold numbers" % name)
+        if y.shape != (U,):
+            raise ValueError("patient trait %r must be a vector of U=%d values" % (name, U))
+        if np.isinf(y).any():
+            raise ValueError("patient trait %r has an infinite value (NaN marks a patient it is not known for)" % name)
+        known[q] = ~np.isnan(y)
+        n = int(known[q].sum())
+        if n < 2:
+            raise ValueError("patient trait %r is known for %d patients (at least 2)" % (name, n))
+        (_values, inverse, counts) = np.unique(y[known[q]], return_inverse=True, return_counts=True)
+        if counts.size < 2:
+            raise ValueError("the known values of patient trait %r are all equal" % name)
+        below = np.cumsum(counts)                       # 2 midrank = 2 below - count + 1 (ranks from 1)
+        scores[q, known[q]] = (2 * below - counts)[inverse.reshape(-1)] - n
+    return names, scores, known, known.sum(axis=1).astype(np.int64)
+
+
 def pair_sweeps_in(sweep0, n_sweeps, accumulate_from, every):
     """Number of sweeps s in [sweep0, sweep0 + n_sweeps) with s >= accumulate_from and (s - accumulate_from) % every == 0."""
     end = sweep0 + n_sweeps
@@ -267,6 +325,13 @@ class GibbsEngine(object):
         self.patient_group_acc = None       # (hist_group (J, R, Umax+1), hist_joint flat) that run() adds to (attach_patient_group_accumulator)
         self.patient_group_every = 1
         self.patient_group_sweeps = 0       # sweeps added to patient_group_acc so far
+        self.trait_names = None     # the traits of set_patient_traits(): names, scores (Q, U) int32, known (Q, U) bool, n_known (Q,)
+        self.trait_scores = self.trait_known = self.trait_n_known = None
+        self.trait_Q = self.trait_umax = 0
+        self.trait_with_sets = False        # the rows of patient_trait_acc include the region sets it was attached with
+        self.patient_trait_acc = None       # (trait_hist (Q, R, Umax+1+NB+3) uint32-in-int32, trait_sum (Q, R, Umax+1) int64) that run() adds to
+        self.patient_trait_every = 1
+        self.patient_trait_sweeps = 0       # sweeps added to patient_trait_acc so far
         self.ctx.call("fcd_ctx_reserve", self.Nreg, self.U, self.G)
         self.lMd = self.lMf = None
         if region_major:
@@ -357,13 +422,14 @@ class GibbsEngine(object):
         a co-anomaly accumulator attached (attach_coanomaly_accumulator) the two pair matrices of every
         `coanomaly_every`-th sweep, and with a region-set accumulator attached (attach_region_set_accumulator) the
         histograms over the region sets of every `region_set_every`-th sweep, and with a patient-group accumulator attached
-        (attach_patient_group_accumulator) the histograms over the patient groups of every `patient_group_every`-th sweep; a
-        call that could overflow any of them raises ValueError.
+        (attach_patient_group_accumulator) the histograms over the patient groups of every `patient_group_every`-th sweep, and
+        with a patient-trait accumulator attached (attach_patient_trait_accumulator) the rank-sum histograms and sums of every
+        `patient_trait_every`-th sweep; a call that could overflow any of them raises ValueError.
         """
         acc = accumulate_from is not None
         live = []                   # (accumulator, sweeps this call adds to it), attached ones only
         # (in this order, and nothing of an accumulator is read unless it is attached)
-        for a in ACCUMULATORS + EXTRA_ACCUMULATORS + GROUP_ACCUMULATORS:
+        for a in ACCUMULATORS + EXTRA_ACCUMULATORS + GROUP_ACCUMULATORS + TRAIT_ACCUMULATORS:
             if not acc or (getattr(self, a.attr) if a in ACCUMULATORS else getattr(self, a.attr, None)) is None:
                 continue
             n = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), getattr(self, a.key + "_every"))
@@ -380,6 +446,8 @@ class GibbsEngine(object):
                     self._send_region_sets()
                 if a is _PATIENT_GROUP:
                     self._send_patient_groups()
+                if a is _PATIENT_TRAIT:
+                    self._send_patient_traits()
                 self.ctx.call(a.setter, *([_lib.dptr(b) for b in self._acc_buffers(a)]
                                           + [self.Nreg, self.U, getattr(self, a.key + "_every")]))
             self._run(sweep0, n_sweeps, mstep_every, accumulate_from, want_counts)
@@ -484,6 +552,8 @@ class GibbsEngine(object):
             raise ValueError("detach the region-set accumulator before changing the sets")
         if getattr(self, "patient_group_acc", None) is not None:
             raise ValueError("detach the patient-group accumulator before changing the sets: they may be rows of it")
+        if getattr(self, "patient_trait_acc", None) is not None:
+            raise ValueError("detach the patient-trait accumulator before changing the sets: they may be rows of it")
         if sets is None:
             (self.region_names, self.region_offsets, self.region_members) = (None, None, None)
             (self.region_J, self.region_smax) = (0, 0)
@@ -629,6 +699,96 @@ class GibbsEngine(object):
         self.ctx.call("fcd_gibbs_patient_group_tally", _lib.dptr(self.r_bits), self.Nreg, self.U, self.G, _lib.dptr(hist_group),
                       _lib.dptr(hist_joint), _lib.stream_ptr())
         return hist_group, hist_joint
+
+    # ---- rank-sum (AUC) statistics between the anomalous and the other patients of a row, per patient trait ----
+    def set_patient_traits(self, traits):
+        """
+        The patient traits of this engine's rank-sum histograms, in any form patient_traits_scores() takes; None clears.  They
+        are copied to the context (fcd_patient_traits_set).  ValueError while the accumulator is attached: its buffers have the
+        old shapes.
+        """
+        if self.patient_trait_acc is not None:
+            raise ValueError("detach the patient-trait accumulator before changing the traits")
+        self.ctx.patient_traits_owner = None
+        if traits is None:
+            (self.trait_names, self.trait_scores, self.trait_known, self.trait_n_known) = (None, None, None, None)
+            (self.trait_Q, self.trait_umax) = (0, 0)
+            self.ctx.call("fcd_patient_traits_set", None, None, 0, 0, 0)
+            return
+        (names, scores, known, n_known) = patient_traits_scores(traits, self.U)
+        (self.trait_names, self.trait_n_known) = (names, n_known)
+        (self.trait_scores, self.trait_known) = (np.ascontiguousarray(scores), np.ascontiguousarray(known.astype(np.uint8)))
+        self.trait_Q = len(names)
+        self.trait_umax = int(n_known.max())
+        self._send_patient_traits()
+
+    def patient_trait_rows(self):
+        """R: the regions and, while an attached accumulator has them or else if region sets are set, the region sets after them."""
+        with_sets = self.trait_with_sets if self.patient_trait_acc is not None else bool(self.region_J)
+        return self.Nreg + (self.region_J if with_sets else 0)
+
+    def patient_trait_row_names(self):
+        """The names of the R rows: the region indices as str, then "set:<name>" for the region sets."""
+        R = self.patient_trait_rows()
+        return [str(n) for n in range(self.Nreg)] + ["set:" + s for s in (self.region_names or [])[:R - self.Nreg]]
+
+    def _send_patient_traits(self):
+        """As _send_patient_groups(): the shared context holds this engine's traits (and, as rows, its region sets) before a launch."""
+        if not self.trait_Q:
+            raise ValueError("no patient traits: call set_patient_traits() first")
+        with_sets = self.patient_trait_rows() > self.Nreg
+        if with_sets:
+            self._send_region_sets()
+        owner = getattr(self.ctx, "patient_traits_owner", None)
+        if owner is not None and owner[0]() is self and owner[1] == with_sets:
+            return
+        self.ctx.call("fcd_patient_traits_set", self.trait_scores.ctypes.data_as(C.c_void_p),
+                      self.trait_known.ctypes.data_as(C.c_void_p), self.trait_Q, self.U, 1 if with_sets else 0)
+        self.ctx.patient_traits_owner = (weakref.ref(self), with_sets)
+
+    def attach_patient_trait_accumulator(self, every=1):
+        """
+        From now on run() adds the end-of-sweep rank-sum statistics of the traits of set_patient_traits() to `patient_trait_acc`,
+        with k the number of known patients of trait q anomalous at row rho and A the sum of their scores (Umax = the largest
+        n_q, NB = 128): trait_hist (Q, R, Umax+1 + NB + 3) uint32 -- [0 .. n_q] the histogram of k over chains,
+        [Umax+1 .. Umax+NB] the AUC bins min(NB-1, floor(NB (A + d) / (2 d))), d = k (n_q - k), of the states with 0 < k < n_q,
+        the last three words those states with A < 0, = 0, > 0 -- and trait_sum (Q, R, Umax+1) int64, [k] the sum of A over the
+        states with that k.  The rows are the regions and, if region sets are set NOW, the sets after them; at every `every`-th
+        sweep from its `accumulate_from` on (none when accumulate_from is None).  Zeroes both.
+        """
+        if not self.trait_Q:
+            raise ValueError("no patient traits: call set_patient_traits() first")
+        self.patient_trait_acc = None
+        self.trait_with_sets = bool(self.region_J)
+        (hist, _placeholder) = self._attach(_PATIENT_TRAIT, every)
+        t = self.torch
+        self.patient_trait_acc = (hist, t.zeros(_PATIENT_TRAIT.shapes(self)[1], dtype=t.int64, device=hist.device))
+        return self.patient_trait_acc
+
+    def detach_patient_trait_accumulator(self):
+        self._detach(_PATIENT_TRAIT)
+
+    def patient_trait_host(self):
+        """The attached buffers as NumPy arrays (trait_hist (Q, R, Umax+1+NB+3) uint32, trait_sum (Q, R, Umax+1) int64)."""
+        if self.patient_trait_acc is None:
+            raise ValueError("no patient-trait accumulator is attached")
+        (hist, total) = self.patient_trait_acc
+        return self.host(hist).view(np.uint32), self.host(total)
+
+    def patient_trait_tally(self, trait_hist, trait_sum):
+        """trait_hist (Q, R, Umax+1+NB+3) uint32-in-int32, trait_sum (Q, R, Umax+1) int64 tensors += the statistics of the current state."""
+        if not self.trait_Q:
+            raise ValueError("no patient traits: call set_patient_traits() first")
+        R = self.patient_trait_rows()
+        if (tuple(trait_hist.shape) != (self.trait_Q, R, self.trait_umax + 1 + PATIENT_TRAIT_BINS + 3)
+                or tuple(trait_sum.shape) != (self.trait_Q, R, self.trait_umax + 1)
+                or trait_hist.element_size() != 4 or trait_sum.dtype != self.torch.int64
+                or not trait_hist.is_contiguous() or not trait_sum.is_contiguous()):
+            raise ValueError("buffers must be contiguous 32-bit (Q, R, Umax+1+%d+3) and int64 (Q, R, Umax+1)" % PATIENT_TRAIT_BINS)
+        self._send_patient_traits()
+        self.ctx.call("fcd_gibbs_patient_trait_tally", _lib.dptr(self.r_bits), self.Nreg, self.U, self.G, _lib.dptr(trait_hist),
+                      _lib.dptr(trait_sum), _lib.stream_ptr())
+        return trait_hist, trait_sum
 
     # ---- co-anomaly: pairs of regions anomalous together, pairs of patients sharing anomalous regions ----
     def attach_coanomaly_accumulator(self, every=1):

@@ -516,7 +516,7 @@ int fcd_vb_count_posterior(fcd_ctx *ctx, const double *lq_R, int64_t Nreg, int64
  * FCD_ERR_ARG for a null pointer, J < 1, offsets[0] != 0, an empty set, a negative member or members that do not increase;
  * FCD_ERR_UNSUPPORTED for a set of more than 1023 members or J > 1024.  The context copies both arrays into a device buffer
  * it owns and frees (it synchronises).  J = 0 with both arrays NULL clears.  Refused with FCD_ERR_ARG while the region-set
- * accumulator is attached, or the patient-group accumulator with the sets as rows. */
+ * accumulator is attached, or the patient-group or patient-trait accumulator with the sets as rows. */
 int fcd_region_sets_set(fcd_ctx *ctx, const int32_t *offsets_host, const int32_t *members_host, int64_t J);
 /* Histograms over chains of one state, with S_max the size of the largest set:
  *   hist_set (J, U, S_max+1) uint32, hist_set[j][u][k] += #{chains with sum_{n in S_j} r_nu = k}; the bins k > |S_j| are
@@ -574,6 +574,44 @@ int fcd_gibbs_patient_group_tally(fcd_ctx *ctx, const uint64_t *r_bits, int64_t 
  * change the groups and, with the sets as rows, fcd_region_sets_set to change the sets.  fcd_gibbs_sweeps never adds to them.
  * The caller keeps sweeps x G below 2^32. */
 int fcd_gibbs_set_patient_group_accumulator(fcd_ctx *ctx, uint32_t *hist_group, uint32_t *hist_joint, int64_t Nreg, int64_t U,
+                                            int64_t every);
+/* ---- anomalies against an ordered patient trait: rank-sum (AUC) laws per row ------------------------------------------
+ * For Q traits of the patients (severity, duration, dose ...) and every row rho of the patient-group histograms (the Nreg
+ * regions and, if the traits were set with_region_sets, the context's J_S region sets after them: R = Nreg + J_S), the law of
+ * the Mann-Whitney statistic between the patients that are anomalous at the row and those that are not.  The caller ranks
+ * trait q over its n_q known patients and passes doubled, centred midranks a_u = 2 midrank_u - (n_q + 1): integers in
+ * [-(n_q - 1), n_q - 1] that sum to 0, tied values sharing a midrank.  A chain state gives, per (q, rho),
+ *     k = #{u known : indicator 1},    A = sum_{u known, indicator 1} a_u,
+ * and where 0 < k < n_q (the state is DEFINED)  AUC = 1/2 + A / (2 k (n_q - k)) = P(an anomalous patient has the higher
+ * trait) + P(tie) / 2;  A + k (n_q - k) = 2 U_stat >= 0.  All of it is integer arithmetic.
+ *
+ * The traits of the context, in HOST memory: scores_host int32 (Q, U), known_host uint8 (Q, U) (non-zero: known).  Everything
+ * a kernel indexes with is checked here: FCD_ERR_ARG for a null pointer, Q < 1, U < 1, a trait with n_q < 2, a score where the
+ * trait is not known, |score| > n_q - 1, scores that do not sum to 0 or known patients that all have one score;
+ * FCD_ERR_UNSUPPORTED for Q > 16 or U > 512.  The context copies the words 2 score + known and the n_q into a device buffer it
+ * owns and frees (it synchronises).  Q = 0 with both arrays NULL clears.  Refused with FCD_ERR_ARG while the patient-trait
+ * accumulator is attached. */
+int fcd_patient_traits_set(fcd_ctx *ctx, const int32_t *scores_host, const uint8_t *known_host, int64_t Q, int64_t U,
+                           int with_region_sets);
+/* Histograms over chains of one state, with Umax = max_q n_q and NB = 128:
+ *   trait_hist (Q, R, Umax+1 + NB + 3) uint32: [k] += #{chains with that k}, k <= n_q (the bins beyond n_q are never touched);
+ *   [Umax+1 + b] += #{defined chains with min(NB-1, floor(NB (A + d) / (2 d))) = b}, d = k (n_q - k): AUC bins of width 1/NB;
+ *   the last three words += #{defined chains with A < 0, A = 0, A > 0};
+ *   trait_sum (Q, R, Umax+1) int64: [k] += sum of A over the chains with that k.
+ * Chains beyond G in the last word never count.  Two launches; the scratch, Q R rows of ceil(G/64) * 64 (uint16, int32) pairs,
+ * is the count tally's, grown on demand.  FCD_ERR_ARG without traits, or without region sets when the traits were set with
+ * them; FCD_ERR_SHAPE if U is not the U of the traits or the largest member of a region set is >= Nreg; FCD_ERR_UNSUPPORTED
+ * for a scratch above 1 GiB. */
+int fcd_gibbs_patient_trait_tally(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
+                                  uint32_t *trait_hist, int64_t *trait_sum, fcd_stream stream);
+/* Attach both buffers for shape (Nreg, U) and the context's CURRENT traits (and region sets, if they are rows) -- no device
+ * work; both NULL detaches --, with the semantics of fcd_gibbs_set_patient_group_accumulator: every sweep s of fcd_gibbs_run
+ * with s >= accumulate_from and (s - accumulate_from) % every == 0 adds its end-of-sweep state (two extra launches, after the
+ * other accumulators'; fcd_gibbs_run grows the scratch before its loop and refuses one above 1 GiB).  Refusals as
+ * fcd_gibbs_patient_trait_tally's; while attached fcd_gibbs_run refuses another shape, fcd_patient_traits_set refuses to change
+ * the traits and, with the sets as rows, fcd_region_sets_set to change the sets.  fcd_gibbs_sweeps never adds to them.  The
+ * caller keeps sweeps x G below 2^32. */
+int fcd_gibbs_set_patient_trait_accumulator(fcd_ctx *ctx, uint32_t *trait_hist, int64_t *trait_sum, int64_t Nreg, int64_t U,
                                             int64_t every);
 /* ---- co-anomaly (which regions are anomalous together, which patients share anomalous regions) -------------------
  * Second moments of the joint law of the sites, which the marginals do not give.
