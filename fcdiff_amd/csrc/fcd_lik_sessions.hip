@@ -34,7 +34,7 @@
 // records every block would otherwise copy 19 KB to work on one tile of 16 KB.  Such a grid is held to the blocks
 // resident at once.
 //
-// Three kernels:
+// Four kernels:
 //   lik_sessions_kernel         K_lik's launch: item blocks (one thread per (c,u), results through the LDS transpose and
 //                               non-temporal 16-byte stores) and S_B blocks: lik_sb_block where there are no control
 //                               variances (so S_B and lp_B_g_F equal fcd_lik_tables_ex's bit for bit), else the same block
@@ -44,6 +44,8 @@
 //                               the records) and no more.
 //   lik_shared_sessions_kernel  K_lik_shared's launch with the session-summed item: L[c] = sum_u lM[c,u], no per-patient
 //                               table is written.
+//   lik_grouped_kernel          the shared launch with the patient sum segmented by known groups of patients: L[c, g] (see
+//                               the kernel).
 //   posterior_sessions_kernel   fcd_post.hip's posterior_kernel with a_j summed over the item's sessions; an item with no
 //                               observed session gets the prior law.
 // The tuned 2-D kernels (lik_kernel, lik_shared_kernel, posterior_kernel) keep their own text and are not changed by this
@@ -353,6 +355,114 @@ __global__ __launch_bounds__(LIK_BLOCK) void lik_shared_sessions_kernel(const do
     }
 }
 
+// The grouped tables (fcdiff_amd.fit.GroupedRegionFit): L[c, g] = sum over the members u of group g of lM[c, u], the patient
+// sum of lik_shared_sessions_kernel segmented by KNOWN groups.  order (U,) lists the patients sorted by group, offsets (G + 1,)
+// each group's span in it.  A lane group of W = 16, 32 or 64 lanes serves one (edge, group) pair and the grid strides over
+// the C G pairs; lane i takes the members order[offsets[g] + i], + W, ... from the contiguous row bt[c, :], nine running sums
+// per lane, a butterfly of shuffles, and lane 0 writes the 72-byte record at (c G + g) 9: no atomics in the sums, so two calls
+// agree bit for bit.  W follows the shared kernels' rule (<= 16, <= 32, else 64) on the LARGEST group, which every block
+// reads off `offsets` itself (G + 1 words from L2): the index arrays stay on the device and the host needs no copy of them.
+// One group is therefore lik_shared_sessions_kernel statement for statement, and singletons give the unshared items' nine
+// values unchanged (a one-term sum and a butterfly of zeros).  A member index outside [0, U) is skipped, never read.
+template <bool MISSING, int TERMS, int W>
+__device__ __forceinline__ void grouped_pairs(const double *__restrict__ bt, int64_t C, int U, int K, const LikTheta &th,
+                                              const double *etab, const fcd_log_cell *ltab, const NoiseRec *__restrict__ rec_bt,
+                                              const NoiseRec *rec_lds, const int32_t *__restrict__ order,
+                                              const int64_t *__restrict__ offsets, int G, double *__restrict__ L, int n_l_blocks,
+                                              unsigned &n_nan) {
+    constexpr int PPB = LIK_BLOCK / W;          // pairs per block and pass
+    const int tid = threadIdx.x;
+    const int lane = tid & (W - 1);
+    const int64_t n_pairs = C * G;
+    for (int64_t p0 = (int64_t)blockIdx.x * PPB; p0 < n_pairs; p0 += (int64_t)n_l_blocks * PPB) {
+        const int64_t p = p0 + tid / W;         // the same for the W lanes of a group
+        double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (p < n_pairs) {
+            const int64_t c = p / G;
+            const int g = (int)(p - c * G);
+            int64_t lo = offsets[g], hi = offsets[g + 1];
+            lo = lo < 0 ? 0 : lo;
+            hi = hi > U ? U : hi;
+            const double *row = bt + c * U * K;                     // the edge's U K doubles: the gather stays inside them
+            for (int64_t i = lo + lane; i < hi; i += W) {
+                const unsigned u = (unsigned)order[i];
+                if (u >= (unsigned)U) continue;
+                const double *x = row + (int64_t)u * K;             // the item's K sessions
+                double a[3] = {0.0, 0.0, 0.0}, v[9];
+                int n_obs = 0;
+                for (int k = 0; k < K; ++k)
+                    sess_add<MISSING, TERMS>(x[k], th, sess_rec<TERMS>(rec_bt, rec_lds, k, U, u), U, a, n_obs, n_nan);
+                sess_logs(a, MISSING && n_obs == 0, th, etab, ltab, v);
+#pragma unroll
+                for (int j = 0; j < 9; ++j) s[j] += v[j];
+            }
+        }
+#pragma unroll
+        for (int o = W / 2; o > 0; o >>= 1)
+#pragma unroll
+            for (int j = 0; j < 9; ++j) s[j] += __shfl_xor(s[j], o, W);
+        if (p < n_pairs && lane == 0) {
+#pragma unroll
+            for (int j = 0; j < 9; ++j) L[p * 9 + j] = s[j];
+        }
+    }
+}
+
+template <bool MISSING, int TERMS>
+__global__ __launch_bounds__(LIK_BLOCK) void lik_grouped_kernel(const double *__restrict__ bt, int64_t C, int U, int K, LikTheta th,
+                                                                const LikTabs *__restrict__ tabs,
+                                                                const NoiseRec *__restrict__ rec_b,
+                                                                const NoiseRec *__restrict__ rec_bt,
+                                                                const int32_t *__restrict__ order,
+                                                                const int64_t *__restrict__ offsets, int G,
+                                                                double *__restrict__ L, int n_l_blocks,
+                                                                const double *__restrict__ b, int H, double *__restrict__ S_B,
+                                                                unsigned long long *__restrict__ nan_slots) {
+    __shared__ __attribute__((aligned(16))) fcd_log_cell ltab[FCD_LOG_CELLS];
+    __shared__ double etab[FCD_EXP_CELLS];
+    __shared__ int blk_nan;
+    __shared__ int largest;                                                 // members of the largest group
+    extern __shared__ __attribute__((aligned(16))) NoiseRec rec_lds[];      // TERMS_LDS: 3 max(H, U K) pairs; else unused
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= n_l_blocks) {
+        sess_sb_role<MISSING, TERMS>(blockIdx.x - n_l_blocks, tid, b, C, H, th, rec_b, rec_lds, S_B, nullptr, nan_slots, &blk_nan);
+        return;
+    }
+    for (int t = tid; t < FCD_LOG_CELLS; t += LIK_BLOCK) ltab[t] = tabs->log_tab[t];
+    if (tid < FCD_EXP_CELLS) etab[tid] = tabs->exp_tab[tid];
+    if (TERMS == TERMS_LDS)
+        for (int t = tid; t < 3 * U * K; t += LIK_BLOCK) rec_lds[t] = rec_bt[t];   // (U K <= NOISE_LDS_RECORDS)
+    if (tid == 0) {
+        blk_nan = 0;
+        largest = 0;
+    }
+    __syncthreads();
+    {
+        int64_t mine = 0;
+        for (int g = tid; g < G; g += LIK_BLOCK) {
+            const int64_t n = offsets[g + 1] - offsets[g];
+            mine = n > mine ? n : mine;
+        }
+        if (mine > 0) atomicMax(&largest, mine > U ? U : (int)mine);
+    }
+    __syncthreads();
+    const int big = largest;
+    unsigned n_nan = 0;
+    if (big <= 16)
+        grouped_pairs<MISSING, TERMS, 16>(bt, C, U, K, th, etab, ltab, rec_bt, rec_lds, order, offsets, G, L, n_l_blocks, n_nan);
+    else if (big <= 32)
+        grouped_pairs<MISSING, TERMS, 32>(bt, C, U, K, th, etab, ltab, rec_bt, rec_lds, order, offsets, G, L, n_l_blocks, n_nan);
+    else
+        grouped_pairs<MISSING, TERMS, 64>(bt, C, U, K, th, etab, ltab, rec_bt, rec_lds, order, offsets, G, L, n_l_blocks, n_nan);
+    if (MISSING) {
+        __syncthreads();
+        if (n_nan) atomicAdd(&blk_nan, (int)n_nan);
+        __syncthreads();
+        if (tid == 0 && blk_nan && nan_slots)
+            atomicAdd(&nan_slots[(blockIdx.x % FCD_NAN_SLOTS) * 16 + 1], (unsigned long long)blk_nan);
+    }
+}
+
 struct SessPostTheta {
     double mu[3], sigma[3], lsigma[3];      // (sigma and lsigma: TERMS_SIGMA only)
     double eps;           // epsilon
@@ -618,6 +728,34 @@ int lik_shared_sessions_launch(fcd_ctx *ctx, const double *b, const double *bt, 
     return sess_nan_fold(slots, nan_counts, s);
 }
 
+template <bool MISSING>
+auto lik_grouped_fn(int terms) {
+    return terms == TERMS_SIGMA    ? lik_grouped_kernel<MISSING, TERMS_SIGMA>
+           : terms == TERMS_GLOBAL ? lik_grouped_kernel<MISSING, TERMS_GLOBAL>
+                                   : lik_grouped_kernel<MISSING, TERMS_LDS>;
+}
+
+// the grouped tables: a lane group per (edge, group) pair and pass, then the S_B blocks, with the terms of `t`.  The lane
+// width is the kernel's to choose (it reads the largest group off `offsets`), so the grid is sized for the widest, 4 pairs
+// per block: under the cap of 16 blocks per CU a narrower width leaves the last blocks without a pair, nothing more.
+int lik_grouped_launch(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U, int64_t K,
+                       const LikTheta &th, const SessTerms &t, const int32_t *order, const int64_t *offsets, int64_t G, double *S_B,
+                       double *L, int flags, int64_t *nan_counts, hipStream_t s) {
+    const auto kernel = (flags & FCD_DATA_NAN_MISSING) ? lik_grouped_fn<true>(t.terms) : lik_grouped_fn<false>(t.terms);
+    const int64_t ppb = LIK_BLOCK / 64;
+    int64_t n_l = (C * G + ppb - 1) / ppb;
+    n_l = (n_l + t.per_block - 1) / t.per_block;
+    const int64_t cap = (int64_t)ctx->num_cu * 16;
+    if (n_l > cap) n_l = cap;
+    const int64_t n_b_blocks = (C + 15) / 16;
+    unsigned long long *slots = nan_counts ? reinterpret_cast<unsigned long long *>(ctx->nan_slots) : nullptr;
+    const LikTabs *tabs = reinterpret_cast<const LikTabs *>(ctx->log_tab);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(n_l + n_b_blocks)), dim3(LIK_BLOCK), t.lds, s, bt, C, (int)U, (int)K, th, tabs,
+                       t.rec_b, t.rec_bt, order, offsets, (int)G, L, (int)n_l, b, (int)H, S_B, slots);
+    FCD_LAUNCH_CHECK();
+    return sess_nan_fold(slots, nan_counts, s);
+}
+
 // both connection posteriors; who = the entry point's name, `records`: the terms come from var_bt's records (NULL: v = 0)
 int conn_posterior_sessions(fcd_ctx *ctx, const char *who, bool records, const double *bt, int64_t Nreg, int64_t U, int64_t K,
                             const double *theta, const double *var_bt, const uint32_t *counts, const double *lq_F,
@@ -726,6 +864,28 @@ extern "C" int fcd_lik_shared_tables_noise(fcd_ctx *ctx, const double *b, const 
     rc = noise_terms(ctx, var_b, var_bt, H, U, K, th, (hipStream_t)stream, t);
     if (rc) return rc;
     return lik_shared_sessions_launch(ctx, b, bt, C, H, U, K, th, t, S_B, L, flags, nan_counts, (hipStream_t)stream);
+}
+
+// order and offsets are device arrays: their contents (a permutation of the patients, spans that start at 0, end at U and
+// never shrink to nothing) are the caller's to check on its host copy before the upload; nothing here waits for the device
+extern "C" int fcd_lik_grouped_tables(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U, int64_t K,
+                                      const double *theta, const double *var_b, const double *var_bt, const int32_t *order,
+                                      const int64_t *offsets, int64_t G, double *S_B, double *L, int flags, int64_t *nan_counts,
+                                      fcd_stream stream) {
+    if (!ctx || !b || !bt || !theta || !order || !offsets || !S_B || !L)
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_lik_grouped_tables: null pointer");
+    const bool records = var_b || var_bt;
+    int rc = sess_check(ctx, "grouped tables", records, C, H, U, K, flags, nan_counts != nullptr);
+    if (rc) return rc;
+    if (G < 1 || G > U) return fcd_fail(ctx, FCD_ERR_ARG, "grouped tables: G=%lld groups, must be 1 .. U=%lld", G, U);
+    LikTheta th;
+    lik_theta_make(theta, th);
+    SessTerms t;
+    if (records) {
+        rc = noise_terms(ctx, var_b, var_bt, H, U, K, th, (hipStream_t)stream, t);
+        if (rc) return rc;
+    }
+    return lik_grouped_launch(ctx, b, bt, C, H, U, K, th, t, order, offsets, G, S_B, L, flags, nan_counts, (hipStream_t)stream);
 }
 
 extern "C" int fcd_conn_posterior_noise(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64_t U, int64_t K, const double *theta,

@@ -1,7 +1,8 @@
 """
 Fits models to observed correlations -- the MI355X build of fcdiff/fit.py.
 
-`SharedRegionFit` (below) fits the shared-region model through the same machinery at one patient.
+`SharedRegionFit` (below) fits the shared-region model through the same machinery at one patient, `GroupedRegionFit` the
+grouped-region model (one anomaly map per known group of patients) at one pseudo-patient per group.
 
 `UnsharedRegionFit` keeps the reference's surface (fcdiff/fit.py:12-54): attributes `model, b, bt,
 max_iters=10, rel_tol=1e-5, energy`, private state `_lq_R (N,U,2), _lq_F (C,1,3), _lp_B_g_F (C,H,3),
@@ -51,6 +52,7 @@ from . import _lib
 from . import util
 from . import score as _score
 from . import tables
+from .model import group_labels_csr, group_of_patient
 from .gibbs import (GibbsEngine, run_chains, allreduce_counts, pool_u32, pair_sweeps_in, ACCUMULATORS, PAIR_COUNT_MAX,
                     COUNT_MAX_NREG, COUNT_MAX_U, region_sets_csr, patient_groups_csr, patient_group_contrasts,
                     patient_traits_scores, PATIENT_TRAIT_BINS)
@@ -108,6 +110,21 @@ class UnsharedRegionFit(object):
     # SharedRegionFit: the tables are (S_B, L) of ONE patient (tables.build(shared=True)), so the state's patient extent is 1,
     # there are no per-item tables, and _init_lps fills _lM with 0 (here the reference's 1)
     _shared = False
+
+    def _patient_extent(self, U):
+        """
+        The patient extent of the state (`_lq_R` (N, ., 2), `_lM` (C, ., 3, 3)) and of the sampler for U patients in bt: U
+        here, 1 for SharedRegionFit (one population column), the number of groups for GroupedRegionFit.
+        """
+        return int(U)
+
+    def _groups_kw(self):
+        """{} (tables.build is called as before, argument for argument); GroupedRegionFit: its `groups`."""
+        return {}
+
+    def _expand_weights(self, W):
+        """Weights or counts (C, extent, 3, 3) of the state as the theta_sub objectives read them; GroupedRegionFit expands."""
+        return W
 
     def __init__(self):
         self.model = None
@@ -442,7 +459,7 @@ class UnsharedRegionFit(object):
         if self.method == "vb":
             self._run_vb()
         elif self.method == "gibbs":
-            self._run_gibbs(N, U)
+            self._run_gibbs(N, self._patient_extent(U))
         else:
             raise ValueError("method must be 'vb' or 'gibbs'")
 
@@ -462,7 +479,7 @@ class UnsharedRegionFit(object):
         t = self._torch()
         dev = self._dev()
         C = util.N_to_C(N)
-        Ut = 1 if self._shared else U
+        Ut = self._patient_extent(U)
         self._d["lq_R"] = t.full((N, Ut, 2), -np.log(2), dtype=t.float64, device=dev)
         self._d["lq_F"] = t.full((C, 1, 3), -np.log(3), dtype=t.float64, device=dev)
         self._d["S_B"] = t.full((C, 3), float(H), dtype=t.float64, device=dev)
@@ -500,10 +517,10 @@ class UnsharedRegionFit(object):
         (S_B, lM) = (self._d.get("S_B"), self._d.get("lM"))
         if S_B is not None and tuple(S_B.shape) != (C, 3):
             S_B = None
-        if lM is not None and tuple(lM.shape) != (C, 1 if self._shared else U, 3, 3):
+        if lM is not None and tuple(lM.shape) != (C, self._patient_extent(U), 3, 3):
             lM = None
         lpB = pBt = None
-        if full and not self._shared:
+        if full and not self._shared and not self._groups_kw():
             lpB = t.empty((C, H, 3), dtype=t.float64, device=dev)
             if bt.ndim == 2 and not self._has_noise():       # (sessions, noise: no per-item densities, see _p_Bt_g_Ft)
                 pBt = t.empty((C, U, 3), dtype=t.float64, device=dev)
@@ -518,7 +535,7 @@ class UnsharedRegionFit(object):
                 n_missing = self._d["n_missing"]
         (self._d["S_B"], self._d["lM"]) = tables.build(self._context(), self._d["b"], self._d["bt"], self.model.theta(),
                                                        self._flags(), shared=self._shared, S_B=S_B, lM=lM, lpB=lpB, pBt=pBt,
-                                                       n_missing=n_missing, **self._noise_kw())
+                                                       n_missing=n_missing, **self._noise_kw(), **self._groups_kw())
         self._d["n_missing_valid"] = bool(self.missing_data)
         self._d["lpB"], self._d["pBt"] = lpB, pBt
 
@@ -745,7 +762,7 @@ class UnsharedRegionFit(object):
         W = t.empty((util.N_to_C(N), U, 3, 3), dtype=t.float64, device=self._dev())
         self._context().call("fcd_theta_sub_weights_vb", _lib.dptr(lq_F), _lib.dptr(lq_R), N, U, _lib.dptr(W),
                              _lib.stream_ptr())
-        return W
+        return self._expand_weights(W)
 
     # ------------------------------------------------------------------ gibbs
     def _run_gibbs(self, N, U):
@@ -820,7 +837,7 @@ class UnsharedRegionFit(object):
                     traces_r.append(e.host(e.r_sums()))
             if self.update_theta_sub and self.theta_sub_every and (i + 1) % self.theta_sub_every == 0 and i + 1 < self.n_sweeps:
                 # Monte-Carlo EM for (eta, epsilon): pooled counts of (f_c, mixture case) over all chains of all ranks
-                W = e.pair_counts()
+                W = self._expand_weights(e.pair_counts())
                 if self.theta_sub_params == "all":
                     (eta, epsilon, mu, sigma, _info) = minimize_theta_full(self._context(), self._d["b"], self._d["bt"], W,
                                                                            self.model, reduce=allreduce_counts,
@@ -1402,7 +1419,7 @@ class UnsharedRegionFit(object):
         ctx = self._query_context()
         # fresh tables of the current theta on the query context: the fit's own are not touched
         (S_B, lM) = tables.build(ctx, self._data_dev("b"), self._data_dev("bt"), self.model.theta(), self._flags(),
-                                 shared=self._shared, **self._noise_kw())
+                                 shared=self._shared, **self._noise_kw(), **self._groups_kw())
         (C, U) = (int(lM.shape[0]), int(lM.shape[1]))
         key = _evidence.evidence_key(self.seed if seed is None else seed)
         return _evidence.log_evidence(ctx, S_B, lM, int(util.C_to_N(C)), U, self.model.gamma, self._pi2(), int(n_anneal), int(G),
@@ -1456,8 +1473,8 @@ class SharedRegionFit(UnsharedRegionFit):
     def _theta_sub_flags(self):
         return {"missing_data": self.missing_data, "per_edge": True}
 
-    def _run_gibbs(self, N, U):
-        super(SharedRegionFit, self)._run_gibbs(N, 1)
+    def _patient_extent(self, U):
+        return 1
 
     def _patients(self):
         bt = self._d.get("bt")
@@ -1550,6 +1567,252 @@ class SharedRegionFit(UnsharedRegionFit):
         (x_new, N) = self._membership_input(x_new)
         return _membership.membership(self._query_context(), self._up, x_new, N, self.sampler, self.model,
                                       self.missing_data, True)
+
+
+GROUP_CONTRAST_MAX = 64          # gibbs.PATIENT_GROUP_MAX_CONTRASTS: the contrasts ride on the patient-group accumulator
+
+
+class GroupedRegionFit(UnsharedRegionFit):
+    """
+    Fits the grouped-region model (fcdiff_amd.GroupedRegionModel: one set of anomalous regions r_ng per KNOWN group of
+    patients) to correlations.  Same attributes and knobs as UnsharedRegionFit, and
+        group_labels     (U,) ints or strings: the group of every patient (diagnosis subtype, arm, site, ...; group_labels_csr)
+        group_contrasts  pairs (name_a, name_b) of two labels, for group_contrast_posterior()
+    Edge ids are always 'symmetric'.
+
+    With T and F~ integrated out per patient, the collapsed joint is that of the UNSHARED model at G pseudo-patients whose
+    tables are the sums over the groups' members,
+        L[c, g, k, l] = sum_{u in group g} lM[c, u, k, l].
+    So run() builds S_B and L in one launch (fcd_lik_grouped_tables, nothing of size C*U) and then runs the unshared fit's
+    own VB loop or sampler at patient extent G: `_lq_R` is (N, G, 2), `_lq_F` (C, 1, 3), `_lM` holds L as (C, G, 3, 3), the
+    columns in the order of `group_names` (the sorted labels).  `energy` is minus the ELBO of p(b, bt) under this model, on
+    the unshared fit's scale.  missing_data, sessions bt (C, U, K), b_noise_var / bt_noise_var and missing_counts() work as
+    in the other fits.  One label for everyone is SharedRegionFit, a label per patient UnsharedRegionFit with 'symmetric'
+    ids; the three have the same parameters, so their log_evidence() differ by log Bayes factors: "do these subgroups have
+    different anomaly maps?" is a number.
+
+    Inherited with the GROUPS as their "patients": anomaly_count_posterior() (p_patient_count (G, Nreg+1), p_region_count
+    (Nreg, G+1): in how many groups a region is anomalous), coanomaly_posterior() (the patient matrix is (G, G): how many
+    anomalous regions two groups share), region_set_posterior() (per set and group) and log_evidence().
+    connection_posterior() is per connection and PATIENT.  The theta_sub step expands the group weights to the patients
+    (W[:, group_of_u]) and calls the unshared objectives unchanged; it stays refused with sessions or noise variances.
+    Not provided: score() and membership() (NotImplementedError: which group's map a new patient gets is a separate
+    question), user-set patient_groups / patient_traits (ValueError: their "patients" would be the groups; use group_contrasts).
+    """
+
+    def __init__(self):
+        super(GroupedRegionFit, self).__init__()
+        self.edge_index = "symmetric"
+        self.group_labels = None
+        self.group_contrasts = None
+        self.group_names = None             # the sorted labels behind the state's columns, set by run()
+        self.group_contrast_names = None    # the contrasts of the last run() as pairs of labels
+
+    def _edge_mode(self):
+        if self.edge_index not in (None, "symmetric"):
+            if self.edge_index == "reference":
+                raise ValueError("edge_index 'reference' (quirk Q1) exists only for parity with the reference's unshared "
+                                 "fit; GroupedRegionFit uses 'symmetric'")
+            raise ValueError("edge_index must be 'symmetric' for GroupedRegionFit")
+        return "symmetric"
+
+    # ------------------------------------------------------------------ the groups
+    def _patients(self):
+        return int(np.shape(self.bt)[1])
+
+    def _groups_host(self, U=None):
+        """(names, offsets (G+1,) int64, order (U,) int32, group_of (U,) int64) of group_labels: host only, ValueError as
+        group_labels_csr()."""
+        if self.group_labels is None:
+            raise ValueError("GroupedRegionFit needs group_labels: one label per patient")
+        (names, offsets, order) = group_labels_csr(self.group_labels, self._patients() if U is None else U)
+        return names, offsets, order, group_of_patient(offsets, order)
+
+    def _patient_extent(self, U):
+        return len(self._groups_host(U)[0])
+
+    def _groups_dev(self):
+        """The device copies of the CSR arrays and of group_of, made again whenever the labels change."""
+        (names, offsets, order, group_of) = self._groups_host()
+        key = (offsets.tobytes(), order.tobytes())
+        cur = self._d.get("groups")
+        if cur is None or cur[0] != key:
+            t = self._torch()
+            dev = self._dev()
+            cur = (key, t.as_tensor(order, device=dev), t.as_tensor(offsets, device=dev), t.as_tensor(group_of, device=dev),
+                   len(names))
+            self._d["groups"] = cur
+        return cur[1:]
+
+    def _groups_kw(self):
+        (order, offsets, _group_of, G) = self._groups_dev()
+        return {"groups": (order, offsets, G)}
+
+    def _expand_weights(self, W):
+        return W.index_select(1, self._groups_dev()[2]).contiguous()
+
+    def _contrast_columns(self, names):
+        """group_contrasts as pairs of columns of the state: ValueError for an unknown label, a contrast of a group with
+        itself, a contrast given twice, more than 64."""
+        rows = [] if self.group_contrasts is None else list(self.group_contrasts)
+        if len(rows) > GROUP_CONTRAST_MAX:
+            raise ValueError("group_contrasts holds %d contrasts (at most %d)" % (len(rows), GROUP_CONTRAST_MAX))
+        pairs = []
+        for row in rows:
+            row = tuple(row)
+            if len(row) != 2:
+                raise ValueError("a group contrast is a pair of labels, got %r" % (row,))
+            for name in row:
+                if name not in names:
+                    raise ValueError("a group contrast names the unknown group %r" % (name,))
+            pair = (names.index(row[0]), names.index(row[1]))
+            if pair[0] == pair[1]:
+                raise ValueError("a group contrast names the group %r twice" % (row[0],))
+            if pair in pairs:
+                raise ValueError("the group contrast %r is given twice" % (row,))
+            pairs.append(pair)
+        return pairs
+
+    def _refuse_patient_knobs(self):
+        if self.patient_groups is not None or self.patient_group_contrasts is not None:
+            raise ValueError("GroupedRegionFit takes no patient_groups: the state's columns are the groups of group_labels; "
+                             "set group_contrasts and read group_contrast_posterior()")
+        if self.patient_traits is not None:
+            raise ValueError("GroupedRegionFit takes no patient_traits: the state's columns are groups of patients, not patients")
+
+    def run(self):
+        """Builds S_B and L (C, G, 3, 3), then the VB loop or the sampler at patient extent G (see the class docstring)."""
+        self._edge_mode()
+        self._refuse_patient_knobs()
+        if self.bt is None or np.ndim(self.bt) not in (2, 3):
+            raise ValueError("bt must be (C, U) or (C, U, K), got shape %s" % (np.shape(self.bt),))
+        names = self._groups_host()[0]
+        pairs = self._contrast_columns(names)
+        super(GroupedRegionFit, self).run()
+        self.group_names = list(names)
+        self.group_contrast_names = [(names[a], names[b]) for (a, b) in pairs]
+
+    def _run_gibbs(self, N, G):
+        """The sampler at G columns; the contrasts ride on the patient-group accumulator as contrasts of singleton groups."""
+        names = self._groups_host()[0]
+        pairs = self._contrast_columns(names)
+        if pairs:
+            cols = sorted(set(c for pair in pairs for c in pair))
+            self.patient_groups = [[c] for c in cols]
+            self.patient_group_contrasts = [(cols.index(a), cols.index(b)) for (a, b) in pairs]
+        try:
+            super(GroupedRegionFit, self)._run_gibbs(N, G)
+        finally:
+            (self.patient_groups, self.patient_group_contrasts) = (None, None)
+
+    # ------------------------------------------------------------------ posteriors
+    def region_posterior(self):
+        """
+        {"p_region" (N, G): P(r_ng = 1 | data), "group_names": the G labels of its columns} from the last run(): q(r_ng = 1)
+        (vb) or the chains' frequency (gibbs).
+        """
+        lq_R = self._lq_R
+        if lq_R is None or lq_R.ndim != 3 or self.group_names is None or lq_R.shape[1] != len(self.group_names):
+            raise ValueError("region_posterior() needs a run(): _lq_R must be (N, G, 2)")
+        return {"p_region": np.exp(lq_R[:, :, 1]), "group_names": list(self.group_names)}
+
+    def connection_posterior(self):
+        """
+        Per connection and PATIENT, as UnsharedRegionFit.connection_posterior(): p_T (C, U), p_F_tilde (C, U, 3), p_changed
+        (C, U).  Given (f_c, the mixture case of its group's r) each patient's T and F~ have the closed-form law of the
+        unshared model, so the group's weights are gathered to its patients:
+          method='vb'     q_R (N, G, 2) gathered to (N, U, 2) with the patients' groups: exact under the mean field;
+          method='gibbs'  the (C, G, 3, 3) counts of (f_c, mixture case) gathered to (C, U, 3, 3) (needs
+                          connection_marginals = True before run()).
+        """
+        if self.model is None or self.bt is None:
+            raise ValueError("connection_posterior() needs a model and bt: call run() first")
+        U = self._patients()
+        group_of = self._groups_dev()[2]
+        if self.method == "gibbs":
+            (counts, N, C) = self._connection_counts_dev()
+            counts = counts.index_select(1, group_of).contiguous()
+            return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), counts=counts,
+                                  missing_data=self.missing_data, **self._noise_bt_kw())
+        if self.method != "vb":
+            raise ValueError("method must be 'vb' or 'gibbs'")
+        (N, C, _G) = self._check_state(need=("lq_R", "lq_F"))
+        lq_R = self._d["lq_R"].index_select(1, group_of).contiguous()
+        return conn_posterior(self._context(), self._bt_dev(C, U), N, U, self.model.theta(), lq_F=self._d["lq_F"],
+                              lq_R=lq_R, missing_data=self.missing_data, **self._noise_bt_kw())
+
+    def group_contrast_posterior(self, independent=False):
+        """
+        Do two groups differ at a row?  For every contrast (a, b) of `group_contrasts` and every row -- the Nreg regions and,
+        with `region_sets`, the sets after them, whose indicator is "the group has an anomalous region in S" --, the joint law
+        of the two groups' indicators, from the last run(), as a dict (P contrasts, R rows):
+            contrasts, row_names             the contrasts as pairs of labels; "0" .. "Nreg-1", "set:<name>"
+            p_both, p_only_a, p_only_b, p_neither  (P, R)     P(a and b anomalous at the row | data), a alone, b alone, neither
+            p_a, p_b  (P, R)                 the two marginals, p_both + p_only_a and p_both + p_only_b
+        The groups are coupled through f, so the joint is not the product of the marginals:
+          method='gibbs', independent=False   read off the (R, 2, 2) joint histograms of the contrasts, counted by the
+                          patient-group accumulator over chains and the sweeps from burn_in on, every
+                          `patient_groups_every`-th.  Needs `group_contrasts` set before run(); ValueError otherwise.
+          method='vb', or independent=True on either method   the mean-field product of the marginals of _lq_R with the
+                          CURRENT group_contrasts and region sets (at a set row p = 1 - prod_{n in S} (1 - q1(n, g))).
+        """
+        if self.model is None or self.bt is None or self.group_names is None:
+            raise ValueError("group_contrast_posterior() needs a fitted model: call run() first")
+        if self.method not in ("vb", "gibbs"):
+            raise ValueError("method must be 'vb' or 'gibbs'")
+        names = list(self.group_names)
+        if self.method == "gibbs" and not independent:
+            hj = self.patient_group_joint_hist
+            if not self.group_contrast_names or hj is None:
+                raise ValueError("no group-contrast histograms: set group_contrasts before run(method='gibbs')")
+            joint = np.stack([np.asarray(h, dtype=np.float64) for h in hj], axis=0)          # (P, R, 2, 2)
+            if joint.sum() == 0:
+                raise ValueError("no sweep was accumulated into the group-contrast histograms (n_sweeps <= burn_in?)")
+            joint = joint / joint.sum(axis=(2, 3), keepdims=True)
+            (contrasts, row_names) = (list(self.group_contrast_names), list(self.patient_group_rows))
+        else:
+            pairs = self._contrast_columns(names)
+            if not pairs:
+                raise ValueError("no group contrasts: set group_contrasts first")
+            lq_R = self._lq_R
+            if lq_R is None or lq_R.ndim != 3 or lq_R.shape[1] != len(names):
+                raise ValueError("group_contrast_posterior() needs a run(): _lq_R must be (N, G, 2)")
+            N = lq_R.shape[0]
+            q1 = 1.0 / (1.0 + np.exp(lq_R[:, :, 0] - lq_R[:, :, 1]))                            # (N, G), normalised
+            rows = [q1]
+            row_names = [str(n) for n in range(N)]
+            if self.region_sets is not None:
+                (set_names, offsets, members) = region_sets_csr(self.region_sets, N)
+                rows.append(np.stack([1.0 - np.prod(1.0 - q1[members[offsets[j]:offsets[j + 1]]], axis=0)
+                                      for j in range(len(set_names))], axis=0))
+                row_names += ["set:" + name for name in set_names]
+            p = np.concatenate(rows, axis=0)                                                    # (R, G)
+            joint = np.stack([np.stack([np.stack([(1 - p[:, a]) * (1 - p[:, b]), (1 - p[:, a]) * p[:, b]], axis=1),
+                                        np.stack([p[:, a] * (1 - p[:, b]), p[:, a] * p[:, b]], axis=1)], axis=1)
+                              for (a, b) in pairs], axis=0)
+            contrasts = [(names[a], names[b]) for (a, b) in pairs]
+        return {"contrasts": contrasts, "row_names": row_names, "p_both": joint[:, :, 1, 1], "p_only_a": joint[:, :, 1, 0],
+                "p_only_b": joint[:, :, 0, 1], "p_neither": joint[:, :, 0, 0], "p_a": joint[:, :, 1, :].sum(axis=2),
+                "p_b": joint[:, :, :, 1].sum(axis=2)}
+
+    def patient_group_posterior(self, *args, **kwargs):
+        """Not provided: the state's columns are the groups of group_labels; see group_contrast_posterior()."""
+        raise ValueError("GroupedRegionFit has no patient_group_posterior(): the state's columns are the groups of "
+                         "group_labels; set group_contrasts and read group_contrast_posterior()")
+
+    def patient_trait_posterior(self, *args, **kwargs):
+        """Not provided: the state's columns are groups of patients, not patients."""
+        raise ValueError("GroupedRegionFit has no patient_trait_posterior(): the state's columns are groups of patients")
+
+    def score(self, *args, **kwargs):
+        """Not provided: which group's map a new patient gets is a separate question."""
+        raise NotImplementedError("score() is not provided for the grouped-region model: which group's map a new patient "
+                                  "gets is a separate question")
+
+    def membership(self, *args, **kwargs):
+        """Not provided: which group's map a new patient gets is a separate question."""
+        raise NotImplementedError("membership() is not provided for the grouped-region model: which group's map a new "
+                                  "patient gets is a separate question")
 
 
 def count_posterior(ctx, lq_R, Nreg, U):

@@ -15,6 +15,47 @@ import numpy as np
 from . import util
 
 
+def group_labels_csr(labels, U):
+    """
+    Known group labels of the patients as (names, offsets (G+1,) int64, order (U,) int32): names the sorted unique labels,
+    order the patients sorted by group -- the members of a group in ascending patient index -- and offsets each group's span
+    in it, what fcd_lik_grouped_tables takes.  Every patient is in exactly one group and no group is empty by construction.
+    labels: a (U,) sequence of ints or of strings.  ValueError for another length or rank, a None or NaN label, a label
+    that is neither an int nor a str (or a mix of the two), and more than U groups.
+    """
+    U = int(U)
+    if isinstance(labels, (str, bytes)) or np.ndim(labels) != 1 or len(labels) != U:
+        raise ValueError("group labels must be a sequence of one label per patient, (U,) = (%d,)" % U)
+    vals = []
+    for v in (labels.tolist() if isinstance(labels, np.ndarray) else list(labels)):
+        if isinstance(v, (bool, np.bool_)) or v is None or (isinstance(v, (float, np.floating)) and v != v):
+            raise ValueError("group labels must be ints or strings, one per patient: got %r (None / NaN: every patient is in "
+                             "exactly one group)" % (v,))
+        if isinstance(v, (int, np.integer)):
+            vals.append(int(v))
+        elif isinstance(v, str):
+            vals.append(str(v))
+        else:
+            raise ValueError("group labels must be ints or strings, got %r" % (v,))
+    if len(set(type(v) for v in vals)) > 1:
+        raise ValueError("group labels must be all ints or all strings")
+    names = sorted(set(vals))
+    if len(names) > U or len(names) < 1:
+        raise ValueError("group labels name %d groups for %d patients" % (len(names), U))
+    index = {name: g for (g, name) in enumerate(names)}
+    group_of = np.array([index[v] for v in vals], dtype=np.int64)
+    order = np.argsort(group_of, kind="stable").astype(np.int32)
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(group_of, minlength=len(names)))]).astype(np.int64)
+    return names, offsets, order
+
+
+def group_of_patient(offsets, order):
+    """(U,) int64: the group index of every patient, from the CSR arrays of group_labels_csr()."""
+    group_of = np.empty(len(order), dtype=np.int64)
+    group_of[np.asarray(order, dtype=np.int64)] = np.repeat(np.arange(len(offsets) - 1), np.diff(offsets))
+    return group_of
+
+
 class _RegionModelParams(object):
     """The parameters both region models share, their defaults and their packing for the C ABI."""
 
@@ -272,3 +313,60 @@ class SharedRegionModel(_RegionModelParams):
                  _lib.dptr(ftk), _lib.dptr(b), _lib.dptr(bt), _lib.stream_ptr())
         return (r.cpu().numpy() > 0, t.cpu().numpy() > 0, _onehot(fk.cpu().numpy(), (Ce,)),
                 _onehot(ftk.cpu().numpy(), (Ce, U)), b.cpu().numpy(), bt.cpu().numpy())
+
+
+class GroupedRegionModel(_RegionModelParams):
+    """
+    The grouped anomalous-region model: the parameters and defaults of the other two models, and one set of anomalous
+    regions per KNOWN group of patients (diagnosis subtype, medication arm, site, ...).
+        r_ng ~ Bernoulli(pi) once per region n and group g; a patient reads the column of its group;
+        T_cu | r_n, r_m drawn independently per patient u, F, F~, B and B~ as in SharedRegionModel.
+    One group for everyone is SharedRegionModel, a group per patient UnsharedRegionModel.  Fitted by
+    fcdiff_amd.fit.GroupedRegionFit.
+    """
+
+    def __str__(self):
+        return textwrap.dedent('''\
+            fcdiff_amd.GroupedRegionModel
+                pi = %g
+                eta = %g
+                gamma = %s
+                epsilon = %g
+                mu = %s
+                sigma = %s''' % (self.pi2()[1], self.eta, self.gamma, self.epsilon, self.mu, self.sigma))
+
+    def sample(self, N, H, labels, seed=0, sessions=None):
+        """
+        (r (N,G) bool, t (C,U) bool, f (C,3) bool, f_tilde (C,U,3) bool, b (C,H) float64, b_tilde (C,U) float64) for the U
+        patients of `labels` (group_labels_csr: G groups, the columns of r in the order of its sorted names), drawn with
+        numpy.random.Generator(seed) in the fitter's edge order and in SharedRegionModel.sample's order of draws: with one
+        label for everyone it returns that sample, r as a column.
+        sessions = K: b_tilde is (C, U, K), K scans of every patient that share the patient's f_tilde (as
+        UnsharedRegionModel.sample_fast).
+        """
+        if sessions is not None and (int(sessions) != sessions or int(sessions) < 1):
+            raise ValueError("sessions must be None or an integer >= 1")
+        U = len(labels)
+        (names, offsets, order) = group_labels_csr(labels, U)
+        group_of = group_of_patient(offsets, order)
+        g = np.random.default_rng(seed)
+        C = util.N_to_C(N)
+        il = np.tril_indices(N, -1)           # (n, m < n) row-major == util.c_to_nm order
+        r = g.random((N, len(names))) < self.pi2()[1]
+        ru = r[:, group_of]                   # (N, U): every patient reads its group's column
+        rn, rm = ru[il[0]], ru[il[1]]
+        t = np.where(rn ^ rm, g.random((C, U)) < self.eta, rn & rm)
+        gam = np.asarray(self.gamma, dtype=np.float64)
+        fk = g.choice(3, size=C, p=gam / gam.sum())
+        e = self.epsilon
+        keep = np.where(t, g.random((C, U)) < e, g.random((C, U)) < (1 - e))
+        other = (fk[:, None] + 1 + (g.random((C, U)) < 0.5)) % 3
+        ftk = np.where(keep, fk[:, None], other)
+        mu = np.asarray(self.mu, dtype=np.float64)
+        sg = np.asarray(self.sigma, dtype=np.float64)
+        b = (mu[fk][:, None] + sg[fk][:, None] * g.standard_normal((C, H))).clip(-1, 1)
+        if sessions is None:
+            b_tilde = (mu[ftk] + sg[ftk] * g.standard_normal((C, U))).clip(-1, 1)
+        else:
+            b_tilde = (mu[ftk][:, :, None] + sg[ftk][:, :, None] * g.standard_normal((C, U, int(sessions)))).clip(-1, 1)
+        return (r, t, _onehot(fk, (C,)), _onehot(ftk, (C, U)), b, b_tilde)

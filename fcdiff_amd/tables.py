@@ -13,7 +13,8 @@ from . import _lib
 NOISE_LDS_RECORDS = 768
 
 
-def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB=None, pBt=None, n_missing=None, noise=None):
+def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB=None, pBt=None, n_missing=None, noise=None,
+          groups=None):
     """
     (S_B (C, 3), lM) of b_dev (C, H) and bt_dev (C, U) at theta, in ONE library call on `ctx`:
       shared=False  fcd_lik_tables_ex: lM (C, U, 3, 3) and, where given, the per-item tables lpB (C, H, 3), pBt (C, U, 3);
@@ -29,6 +30,12 @@ def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB
     (U,) / (U, K) matching bt_dev, either of them None for all zeros.  It selects fcd_lik_tables_noise /
     fcd_lik_shared_tables_noise for a bt of either rank (a 2-D bt is K = 1); pBt is refused (ValueError), as with sessions.
     The values are the caller's to check (finite, >= 0): nothing here reads them.
+    groups: None, or (order_dev, offsets_dev, G): known groups of patients, as fit.group_labels_csr() makes them -- order (U,)
+    int32 the patients sorted by group, offsets (G + 1,) int64 each group's span in it, both device tensors.  It selects
+    fcd_lik_grouped_tables: lM is L (C, G, 3, 3), the sum of lM over each group's patients, for a bt of either rank (a 2-D bt
+    is K = 1) and with or without `noise`.  There are no per-item tables (lpB, pBt: ValueError), and shared=True with groups
+    is a ValueError (one group is the shared table).  The contents of the two index tensors are the caller's to check on the
+    host (group_labels_csr does): nothing here reads them.
     """
     import torch
     (C, H) = (int(b_dev.shape[0]), int(b_dev.shape[1]))
@@ -40,22 +47,38 @@ def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB
         raise ValueError("p_Bt_g_Ft is not made for sessions data: a product of densities underflows")
     if K is not None and K < 1:
         raise ValueError("bt (C, U, K) needs K >= 1 sessions, got shape %s" % (tuple(bt_dev.shape),))
+    if groups is not None:
+        if shared:
+            raise ValueError("groups and shared=True exclude each other: one group of all patients is the shared table")
+        if lpB is not None or pBt is not None:
+            raise ValueError("the grouped tables have no per-item tables (lp_B_g_F, p_Bt_g_Ft)")
+        (order, offsets, G) = groups
+        G = int(G)
+        if not 1 <= G <= U:
+            raise ValueError("groups: G = %d groups, must be 1 .. U = %d" % (G, U))
+        if tuple(order.shape) != (U,) or order.dtype != torch.int32:
+            raise ValueError("groups: order must be int32 (U,) = %s" % ((U,),))
+        if tuple(offsets.shape) != (G + 1,) or offsets.dtype != torch.int64:
+            raise ValueError("groups: offsets must be int64 (G + 1,) = %s" % ((G + 1,),))
+        if lM is not None and tuple(lM.shape) != (C, G, 3, 3):
+            raise ValueError("groups: lM must be (C, G, 3, 3) = %s, got %s" % ((C, G, 3, 3), tuple(lM.shape)))
     if S_B is None:
         S_B = torch.empty((C, 3), dtype=torch.float64, device=bt_dev.device)
     if lM is None:
-        lM = torch.empty((C, 1 if shared else U, 3, 3), dtype=torch.float64, device=bt_dev.device)
+        lM = torch.empty((C, (1 if shared else U) if groups is None else G, 3, 3), dtype=torch.float64, device=bt_dev.device)
     (th, _th) = _lib.dbl_array(theta)
-    if noise is not None:
+    if groups is not None:
+        Kn = 1 if K is None else K
+        (var_b, var_bt) = (None, None) if noise is None else _noise_checked(noise, H, U, K)
+        ctx.call("fcd_lik_grouped_tables", _lib.dptr(b_dev), _lib.dptr(bt_dev.contiguous()), C, H, U, Kn, th, _lib.dptr(var_b),
+                 _lib.dptr(var_bt), _lib.dptr(order.contiguous()), _lib.dptr(offsets.contiguous()), G, _lib.dptr(S_B),
+                 _lib.dptr(lM), int(flags), _lib.dptr(n_missing), _lib.stream_ptr())
+    elif noise is not None:
         if pBt is not None:
             raise ValueError("p_Bt_g_Ft is not made with noise variances: the noise tables are log-form only")
-        (var_b, var_bt) = noise
         Kn = 1 if K is None else K
-        if var_b is not None and (tuple(var_b.shape) != (H,) or var_b.dtype != torch.float64):
-            raise ValueError("noise: var_b must be float64 (H,) = %s" % ((H,),))
-        if var_bt is not None and (var_bt.dtype != torch.float64 or tuple(var_bt.shape) not in ((U, Kn),) + (((U,),) if K is None else ())):
-            raise ValueError("noise: var_bt must be float64 (U, K) = %s" % ((U, Kn),))
-        (bt_dev, var_b, var_bt) = (bt_dev.contiguous(), None if var_b is None else var_b.contiguous(),
-                                   None if var_bt is None else var_bt.contiguous())
+        (var_b, var_bt) = _noise_checked(noise, H, U, K)
+        bt_dev = bt_dev.contiguous()
         if shared:
             ctx.call("fcd_lik_shared_tables_noise", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, Kn, th, _lib.dptr(var_b),
                      _lib.dptr(var_bt), _lib.dptr(S_B), _lib.dptr(lM), int(flags), _lib.dptr(n_missing), _lib.stream_ptr())
@@ -78,6 +101,18 @@ def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB
         ctx.call("fcd_lik_tables_ex", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, th, _lib.dptr(S_B), _lib.dptr(lM),
                  _lib.dptr(lpB), _lib.dptr(pBt), int(flags), _lib.dptr(n_missing), _lib.stream_ptr())
     return S_B, lM
+
+
+def _noise_checked(noise, H, U, K):
+    """(var_b, var_bt) of build()'s `noise`, contiguous, after its shape and dtype checks (K: None for a 2-D bt)."""
+    import torch
+    (var_b, var_bt) = noise
+    Kn = 1 if K is None else K
+    if var_b is not None and (tuple(var_b.shape) != (H,) or var_b.dtype != torch.float64):
+        raise ValueError("noise: var_b must be float64 (H,) = %s" % ((H,),))
+    if var_bt is not None and (var_bt.dtype != torch.float64 or tuple(var_bt.shape) not in ((U, Kn),) + (((U,),) if K is None else ())):
+        raise ValueError("noise: var_bt must be float64 (U, K) = %s" % ((U, Kn),))
+    return (None if var_b is None else var_b.contiguous(), None if var_bt is None else var_bt.contiguous())
 
 
 def write_hyper(ctx, hyper, gamma, pi2):

@@ -275,6 +275,31 @@ int fcd_conn_posterior_noise(fcd_ctx *ctx, const double *bt, int64_t Nreg, int64
                              const double *var_bt, const uint32_t *counts, const double *lq_F, const double *lq_R,
                              int flags, double *p_T, double *p_F_tilde, double *p_changed, fcd_stream stream);
 
+/* ---- known groups of patients: one table per group ------------------------------------------------------------------
+ * fcd_lik_grouped_tables: S_B (C,3) and L (C,G,3,3),
+ *   L[c, g, k, l] = sum over the patients u of group g of lM[c, u, k, l],
+ * the tables of the grouped-region model (one anomaly map per known group of patients): the collapsed joint of the unshared
+ * model at G pseudo-patients.  Nothing of size C*U is written.  bt is (C, U, K) as in the sessions entry points, K = 1 for
+ * one scan per patient.  var_b and var_bt both NULL select the sigma form (the terms of fcd_lik_shared_tables_sessions),
+ * otherwise the record form of fcd_lik_shared_tables_noise with the variances given (a NULL one is all zeros); the record of
+ * patient u is looked up with the gathered u.
+ * order (U int32) lists the patients sorted by group and offsets (G + 1 int64) gives each group's span in it; both are
+ * DEVICE pointers.  Every patient is in exactly one group and no group is empty: offsets[0] = 0, offsets[G] = U, strictly
+ * increasing, order a permutation of 0 .. U-1.  The contents are the caller's to check on its host copy (fcdiff_amd.fit
+ * .group_labels_csr makes and checks them); the call does not wait for the device to read them.  An order entry outside
+ * [0, U) is skipped by the kernel, never dereferenced.
+ * The sums have a fixed order (lane i of a group of 16, 32 or 64 lanes -- by the largest group, fcd_lik_shared_tables' rule --
+ * takes members i, i + width, ... in `order`, then a butterfly), so two calls agree bit for bit; with one group L equals
+ * fcd_lik_shared_tables_sessions' / _noise's bit for bit, with U singleton groups in patient order it equals
+ * fcd_lik_tables_sessions' / _noise's lM.  S_B equals theirs bit for bit in every case.  nan_counts as in the shared entry
+ * points (each patient is in one group, so each NaN is counted once).
+ * Refusals: null pointers, unknown flags, K < 1, G < 1 or G > U FCD_ERR_ARG; non-triangular C FCD_ERR_SHAPE; K > INT32_MAX,
+ * or U*K > 2^31 in the record form, FCD_ERR_UNSUPPORTED. */
+int fcd_lik_grouped_tables(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U, int64_t K,
+                           const double *theta12_host, const double *var_b, const double *var_bt, const int32_t *order,
+                           const int64_t *offsets, int64_t G, double *S_B, double *L, int flags, int64_t *nan_counts,
+                           fcd_stream stream);
+
 /* ---- forward sampler: UnsharedRegionModel.sample, fcdiff/model.py:52-236, on the device ---------------
  * Counter RNG (Philox), all variables drawn in parallel; the reference's MT19937 stream is not reproduced (the host
  * sampler of the Python mirror does that) -- same distribution.  Type INDICES are returned: r (Nreg,U), t (C,U),
