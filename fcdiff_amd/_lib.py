@@ -67,6 +67,8 @@ SIGNATURES = {
     "fcd_conn_posterior_noise": (_int, [_p, _p, _i64, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _p, _int, _p, _p, _p, _p]),
     "fcd_lik_grouped_tables": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _p, _i64, _p, _p, _int, _p,
                                       _p]),
+    "fcd_lik_weighted_tables": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p]),
+    "fcd_vb_subtype_loglik": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p]),
     "fcd_model_sample": (_int, [_p, C.POINTER(_dbl), _i64, _i64, _i64, _u64, _p, _p, _p, _p, _p, _p, _p]),
     "fcd_model_sample_shared": (_int, [_p, C.POINTER(_dbl), _i64, _i64, _i64, _u64, _p, _p, _p, _p, _p, _p, _p]),
     "fcd_corr_edges": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),

@@ -2,7 +2,8 @@
 Fits models to observed correlations -- the MI355X build of fcdiff/fit.py.
 
 `SharedRegionFit` (below) fits the shared-region model through the same machinery at one patient, `GroupedRegionFit` the
-grouped-region model (one anomaly map per known group of patients) at one pseudo-patient per group.
+grouped-region model (one anomaly map per known group of patients) at one pseudo-patient per group, `SubtypeRegionFit` the
+same model with the groups unknown (latent subtypes, VB) at one pseudo-patient per subtype.
 
 `UnsharedRegionFit` keeps the reference's surface (fcdiff/fit.py:12-54): attributes `model, b, bt,
 max_iters=10, rel_tol=1e-5, energy`, private state `_lq_R (N,U,2), _lq_F (C,1,3), _lp_B_g_F (C,H,3),
@@ -121,6 +122,13 @@ class UnsharedRegionFit(object):
     def _groups_kw(self):
         """{} (tables.build is called as before, argument for argument); GroupedRegionFit: its `groups`."""
         return {}
+
+    def _built_table(self, U):
+        """
+        (key of self._d, patient extent) of the table the data build writes: the state's own `lM`; SubtypeRegionFit: the
+        per-patient table it keeps beside the state's L.
+        """
+        return "lM", self._patient_extent(U)
 
     def _expand_weights(self, W):
         """Weights or counts (C, extent, 3, 3) of the state as the theta_sub objectives read them; GroupedRegionFit expands."""
@@ -514,10 +522,11 @@ class UnsharedRegionFit(object):
             self._d["b"], self._d["bt"] = self._up(b), self._up(bt)
             self._d["data_key"] = key
         # the buffers are kept when their shape holds: a sampler built on them reads the new tables after refresh_tables()
-        (S_B, lM) = (self._d.get("S_B"), self._d.get("lM"))
+        (key_lM, extent) = self._built_table(U)
+        (S_B, lM) = (self._d.get("S_B"), self._d.get(key_lM))
         if S_B is not None and tuple(S_B.shape) != (C, 3):
             S_B = None
-        if lM is not None and tuple(lM.shape) != (C, self._patient_extent(U), 3, 3):
+        if lM is not None and tuple(lM.shape) != (C, extent, 3, 3):
             lM = None
         lpB = pBt = None
         if full and not self._shared and not self._groups_kw():
@@ -533,9 +542,9 @@ class UnsharedRegionFit(object):
                 self._d["n_missing"] = t.zeros(2, dtype=t.int64, device=dev)
             if uploaded or not self._d.get("n_missing_valid"):
                 n_missing = self._d["n_missing"]
-        (self._d["S_B"], self._d["lM"]) = tables.build(self._context(), self._d["b"], self._d["bt"], self.model.theta(),
-                                                       self._flags(), shared=self._shared, S_B=S_B, lM=lM, lpB=lpB, pBt=pBt,
-                                                       n_missing=n_missing, **self._noise_kw(), **self._groups_kw())
+        (self._d["S_B"], self._d[key_lM]) = tables.build(self._context(), self._d["b"], self._d["bt"], self.model.theta(),
+                                                         self._flags(), shared=self._shared, S_B=S_B, lM=lM, lpB=lpB, pBt=pBt,
+                                                         n_missing=n_missing, **self._noise_kw(), **self._groups_kw())
         self._d["n_missing_valid"] = bool(self.missing_data)
         self._d["lpB"], self._d["pBt"] = lpB, pBt
 
@@ -1597,7 +1606,8 @@ class GroupedRegionFit(UnsharedRegionFit):
     connection_posterior() is per connection and PATIENT.  The theta_sub step expands the group weights to the patients
     (W[:, group_of_u]) and calls the unshared objectives unchanged; it stays refused with sessions or noise variances.
     Not provided: score() and membership() (NotImplementedError: which group's map a new patient gets is a separate
-    question), user-set patient_groups / patient_traits (ValueError: their "patients" would be the groups; use group_contrasts).
+    question, answered by SubtypeRegionFit.assign()), user-set patient_groups / patient_traits (ValueError: their "patients"
+    would be the groups; use group_contrasts).
     """
 
     def __init__(self):
@@ -1815,6 +1825,387 @@ class GroupedRegionFit(UnsharedRegionFit):
                                   "patient gets is a separate question")
 
 
+SUBTYPE_MAX = tables.SUBTYPE_MAX
+
+
+def _digamma(x):
+    import scipy.special
+    return scipy.special.digamma(x)
+
+
+def _gammaln(x):
+    import scipy.special
+    return scipy.special.gammaln(x)
+
+
+def subtype_E_ln_rho(n, alpha):
+    """E ln rho_g = psi(alpha + n_g) - psi(G alpha + sum n) under q(rho) = Dirichlet(alpha + n), (G,) float64."""
+    n = np.asarray(n, dtype=np.float64)
+    return _digamma(alpha + n) - _digamma(len(n) * alpha + n.sum())
+
+
+def subtype_softmax(logits):
+    """Row-wise softmax of (U, G) log-weights, by the row maximum."""
+    a = logits - logits.max(axis=1, keepdims=True)
+    e = np.exp(a)
+    return e / e.sum(axis=1, keepdims=True)
+
+
+def subtype_energy_terms(resp, alpha):
+    """
+    What the z and rho factors add to the free energy at responsibilities resp (U, G) with q(rho) = Dirichlet(alpha + n),
+    n = sum_u resp:  - sum_{u,g} s (E ln rho_g - ln s)  +  KL(Dir(alpha + n) || Dir(alpha)),  taking 0 ln 0 = 0.
+    """
+    s = np.asarray(resp, dtype=np.float64)
+    (U, G) = s.shape
+    n = s.sum(axis=0)
+    el = subtype_E_ln_rho(n, alpha)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ent = np.where(s > 0, s * np.log(s), 0.0)
+    cross = float((s * el[None, :]).sum() - ent.sum())
+    kl = float(_gammaln(G * alpha + n.sum()) - _gammaln(alpha + n).sum() - _gammaln(G * alpha) + G * _gammaln(alpha)
+               + (n * el).sum())
+    return -cross + kl
+
+
+class SubtypeRegionFit(UnsharedRegionFit):
+    """
+    Fits the subtype-region model (fcdiff_amd.SubtypeRegionModel: GroupedRegionModel with the group of every patient
+    unknown) by mean-field VB: z_u ~ Categorical(rho), rho ~ Dirichlet(alpha, ..., alpha) integrated out, one anomaly map
+    r_ng per subtype.  UnsharedRegionFit's attributes, and
+        n_subtypes              G, 1 .. min(8, U)
+        rho_concentration       alpha of the Dirichlet prior (1.0)
+        n_restarts              restarts from seeded initial responsibilities (4); the one with the lowest final energy is kept
+        seed                    restart i starts from z0 = default_rng(seed + i).permutation(U) % G, s = 0.1/G + 0.9 onehot(z0)
+        init_responsibilities   None, or (U, G) rows of probabilities: ONE run from them, no restarts
+    Edge ids are always 'symmetric', method is always 'vb'.
+
+    The family is q(f) q(r) q(z) q(rho) with responsibilities s[u, g] = q(z_u = g) and q(rho) = Dirichlet(alpha + n),
+    n_g = sum_u s[u, g].  The expected collapsed log-likelihood is the unshared model's E_lM term at G pseudo-patients with
+        L[c, g, k, l] = sum_u s[u, g] lM[c, u, k, l]
+    (GroupedRegionFit is the one-hot case), so q_F, q_R, the pi and gamma steps and the energy are the unshared fit's own
+    kernels at patient extent G on L.  One outer iteration: q_F, q_R (on L), pi and gamma, then
+        E[u, g] = sum_c sum_k q_F[c,k] sum_l w_l^g(c) lM[c, u, k, l]          (fcd_vb_subtype_loglik)
+        s[u, :] = softmax_g(E[u, g] + psi(alpha + n_g) - psi(G alpha + U))    (n of the s before the step)
+        L = sum_u s lM                                                        (fcd_lik_weighted_tables)
+    and `energy` = the inherited energy at L(s) - sum s (E ln rho - ln s) + KL(Dir(alpha + n) || Dir(alpha)): minus a lower
+    bound on log p(b, bt | theta).  Every step is an exact coordinate maximiser, so the energy never rises.
+    run() keeps the per-patient table (C, U, 3, 3) -- `_lM_patients`, built ONCE: theta_sub is not fitted, so it does not
+    change -- beside L (`_lM`, (C, G, 3, 3)); `_lq_R` is (N, G, 2).  missing_data, sessions bt (C, U, K), b_noise_var /
+    bt_noise_var and missing_counts() work through that table build as in the other fits.  After the fit the subtypes are
+    renumbered by decreasing n_g (ties by index), so the result does not depend on the label permutation of the start.
+    run() leaves `energy` (the kept restart's, the start and every outer iteration), `restart_energies` (every restart's
+    last) and `responsibilities` (U, G).
+
+    Queries: subtype_posterior(), region_posterior(), connection_posterior() (per connection and PATIENT), assign(bt_new)
+    (which subtype's map a new patient gets), and, with the SUBTYPES as their "patients" as in GroupedRegionFit,
+    anomaly_count_posterior(), coanomaly_posterior(), region_set_posterior().
+    Not provided: method='gibbs' and update_theta_sub (NotImplementedError from run()), score(), membership() and
+    log_evidence() (NotImplementedError: the inherited forms would read L as a data table), patient_groups /
+    patient_traits (ValueError).
+    """
+
+    def __init__(self):
+        super(SubtypeRegionFit, self).__init__()
+        self.edge_index = "symmetric"
+        self.n_subtypes = None
+        self.rho_concentration = 1.0
+        self.n_restarts = 4
+        self.init_responsibilities = None
+        self.responsibilities = None        # (U, G) float64 of the last run(), columns by decreasing n_g
+        self.restart_energies = None        # the last energy of every restart of the last run()
+
+    def _edge_mode(self):
+        if self.edge_index not in (None, "symmetric"):
+            if self.edge_index == "reference":
+                raise ValueError("edge_index 'reference' (quirk Q1) exists only for parity with the reference's unshared "
+                                 "fit; SubtypeRegionFit uses 'symmetric'")
+            raise ValueError("edge_index must be 'symmetric' for SubtypeRegionFit")
+        return "symmetric"
+
+    # ------------------------------------------------------------------ shapes and refusals
+    def _patients(self):
+        return int(np.shape(self.bt)[1])
+
+    def _n_subtypes(self, U=None):
+        U = self._patients() if U is None else int(U)
+        G = self.n_subtypes
+        if G is None or isinstance(G, bool) or int(G) != G or not 1 <= int(G) <= min(SUBTYPE_MAX, U):
+            raise ValueError("n_subtypes must be an integer in 1 .. min(%d, U = %d), got %r" % (SUBTYPE_MAX, U, G))
+        return int(G)
+
+    def _patient_extent(self, U):
+        return self._n_subtypes(U)
+
+    def _built_table(self, U):
+        return "lM_u", int(U)
+
+    def _alpha(self):
+        a = float(self.rho_concentration)
+        if not (a > 0 and np.isfinite(a)):
+            raise ValueError("rho_concentration must be a finite number > 0, got %r" % (self.rho_concentration,))
+        return a
+
+    def _refuse_knobs(self):
+        if self.method == "gibbs":
+            raise NotImplementedError("SubtypeRegionFit has no sampler (method='gibbs'): the subtypes are fitted by VB only, a "
+                                      "sampler for z is not made")
+        if self.method != "vb":
+            raise ValueError("method must be 'vb' for SubtypeRegionFit")
+        if self.update_theta_sub or self.theta_sub_every:
+            raise NotImplementedError("the theta_sub step is not provided with subtypes: the fit keeps one per-patient table for "
+                                      "all iterations, which a change of (eta, epsilon) would invalidate")
+        if self.patient_groups is not None or self.patient_group_contrasts is not None:
+            raise ValueError("SubtypeRegionFit takes no patient_groups: the state's columns are the subtypes, not patients")
+        if self.patient_traits is not None:
+            raise ValueError("SubtypeRegionFit takes no patient_traits: the state's columns are the subtypes, not patients")
+
+    @staticmethod
+    def _checked_responsibilities(resp, U, G, name):
+        s = np.array(resp, dtype=np.float64)
+        if s.shape != (U, G):
+            raise ValueError("%s must have shape (U, G) = %s, got %s" % (name, (U, G), s.shape))
+        if not np.all(np.isfinite(s)) or np.any(s < 0):
+            raise ValueError("%s must be finite and >= 0" % name)
+        if np.any(np.abs(s.sum(axis=1) - 1.0) > 1e-9):
+            raise ValueError("every row of %s must sum to 1" % name)
+        return np.ascontiguousarray(s)
+
+    def _starts(self, U, G):
+        """The initial responsibilities of the run(s): the user's alone, or those of the seeded restarts."""
+        if self.init_responsibilities is not None:
+            return [self._checked_responsibilities(self.init_responsibilities, U, G, "init_responsibilities")]
+        R = self.n_restarts
+        if isinstance(R, bool) or int(R) != R or int(R) < 1:
+            raise ValueError("n_restarts must be an integer >= 1, got %r" % (R,))
+        out = []
+        for i in range(int(R)):
+            z0 = np.random.default_rng(int(self.seed) + i).permutation(U) % G
+            s = np.full((U, G), 0.1 / G)
+            s[np.arange(U), z0] += 0.9
+            out.append(s)
+        return out
+
+    # ------------------------------------------------------------------ state
+    @property
+    def _lM_patients(self):
+        """(C, U, 3, 3): the per-patient table the responsibilities weight (`_lM` is L (C, G, 3, 3))."""
+        return self._get("lM_u")
+
+    def _resp_dev(self):
+        """The device copy of `responsibilities`, made again whenever the host values change."""
+        s = self.responsibilities
+        if s is None:
+            raise ValueError("no responsibilities: call run() first")
+        (N, C, G) = self._check_state(need=("lq_R",))
+        s = self._checked_responsibilities(s, self._patients(), G, "responsibilities")
+        key = s.tobytes()
+        cur = self._d.get("resp")
+        if cur is None or cur[0] != key:
+            cur = (key, self._up(s))
+            self._d["resp"] = cur
+        return cur[1]
+
+    def _update_lps(self):
+        """The per-patient table from the current parameters and, once there are responsibilities, L from it."""
+        self._tables(full=False)
+        if self.responsibilities is not None:
+            self._update_weighted_table()
+
+    def _update_weighted_table(self):
+        """L = sum_u s[u, g] lM[c, u] into the state's `_lM`, in place: fcd_lik_weighted_tables through tables.build."""
+        resp = self._resp_dev()
+        (_S_B, self._d["lM"]) = tables.build(self._context(), self._d["b"], self._d["bt"], self.model.theta(), self._flags(),
+                                             S_B=self._d["S_B"], lM=self._d["lM"], weights=(self._d["lM_u"], resp))
+
+    def _expected_loglik(self, ctx, lM_u):
+        """E (U', G) of the patients of the table lM_u (C, U', 3, 3) at the fit's q_F and q_R: fcd_vb_subtype_loglik."""
+        t = self._torch()
+        (N, C, G) = self._check_state(need=("lq_R", "lq_F"))
+        if lM_u.dim() != 4 or tuple(lM_u.shape[2:]) != (3, 3) or int(lM_u.shape[0]) != C:
+            raise ValueError("the per-patient table must be (C, U, 3, 3) with C = %d, got %s" % (C, tuple(lM_u.shape)))
+        U = int(lM_u.shape[1])
+        E = t.empty((U, G), dtype=t.float64, device=self._dev())
+        ctx.call("fcd_vb_subtype_loglik", _lib.dptr(self._d["lq_F"]), _lib.dptr(self._d["lq_R"]), _lib.dptr(lM_u.contiguous()),
+                 N, U, G, _lib.dptr(E), _lib.stream_ptr())
+        return E.cpu().numpy()
+
+    def _update_responsibilities(self):
+        """s[u, :] = softmax_g(E[u, g] + E ln rho_g) with q(rho) of the responsibilities before the step."""
+        E = self._expected_loglik(self._context(), self._d["lM_u"])
+        el = subtype_E_ln_rho(self.responsibilities.sum(axis=0), self._alpha())
+        self.responsibilities = subtype_softmax(E + el[None, :])
+
+    def _eval_energy(self):
+        """The inherited free energy at L(s) plus the terms of z and rho (subtype_energy_terms)."""
+        return super(SubtypeRegionFit, self)._eval_energy() + subtype_energy_terms(self.responsibilities, self._alpha())
+
+    # ------------------------------------------------------------------ the fit
+    def run(self):
+        """The restarts of the VB loop of the class docstring; keeps the one with the lowest final energy."""
+        self._edge_mode()
+        self._refuse_knobs()
+        if self.model is None:
+            raise ValueError("Model has not been initialized.")
+        if self.bt is None or np.ndim(self.bt) not in (2, 3) or (np.ndim(self.bt) == 3 and np.shape(self.bt)[2] < 1):
+            raise ValueError("bt must be (C, U) or (C, U, K) with K >= 1 sessions, got shape %s" % (np.shape(self.bt),))
+        (C, H) = np.shape(self.b)
+        U = self._patients()
+        N = util.C_to_N(C)
+        if (N % 1) != 0:
+            raise ValueError("Number of connections (%u) must be a triangular number." % C)
+        N = int(N)
+        G = self._n_subtypes(U)
+        self._alpha()
+        starts = self._starts(U, G)
+        self._noise_host()               # (a ValueError for bad noise variances before any context exists)
+        (pi0, gamma0) = (self.model.pi, np.array(self.model.gamma, dtype=np.float64))
+        self.responsibilities = None
+        # _init_lps is called for what outlives the restarts: it forgets the device copies of b / bt (a run starts from the
+        # arrays as they are now) and allocates S_B and the (C, G, 3, 3) buffer L is written into.  Its uniform lq_R / lq_F
+        # are replaced at the start of every restart (_run_from).
+        self._init_lps(N, H, U)
+        self._tables(full=False)         # S_B and the per-patient table, once for every restart and iteration
+        best = None
+        self.restart_energies = []
+        for s0 in starts:
+            (self.model.pi, self.model.gamma) = (pi0, gamma0.copy())
+            energy = self._run_from(s0, N, C, G)
+            self.restart_energies.append(energy[-1])
+            if best is None or energy[-1] < best["energy"][-1]:
+                best = dict(energy=energy, resp=self.responsibilities, lq_R=self._d["lq_R"], lq_F=self._d["lq_F"],
+                            pi=self.model.pi, gamma=self.model.gamma)
+        # the kept restart, its subtypes by decreasing n_g (ties by index), and L at those responsibilities
+        order = np.argsort(-best["resp"].sum(axis=0), kind="stable")
+        self.energy = best["energy"]
+        (self.model.pi, self.model.gamma) = (best["pi"], best["gamma"])
+        self.responsibilities = np.ascontiguousarray(best["resp"][:, order])
+        self._d["lq_F"] = best["lq_F"]
+        self._d["lq_R"] = best["lq_R"].index_select(1, self._torch().as_tensor(order, device=self._dev())).contiguous()
+        self._update_weighted_table()
+
+    def _run_from(self, s0, N, C, G):
+        """One VB run from responsibilities s0 on the tables already built; returns its energies."""
+        t = self._torch()
+        dev = self._dev()
+        self._d["lq_R"] = t.full((N, G, 2), -np.log(2), dtype=t.float64, device=dev)
+        self._d["lq_F"] = t.full((C, 1, 3), -np.log(3), dtype=t.float64, device=dev)
+        self.responsibilities = s0
+        self._update_weighted_table()
+        self.energy = [self._eval_energy()]
+        for i in range(1, self.max_iters + 1):
+            self._update_lq_F()
+            self._update_lq_R()
+            self._update_theta()
+            self._update_responsibilities()
+            self._update_weighted_table()
+            self.energy.append(self._eval_energy())
+            if self._is_converged(i):
+                break
+        return self.energy
+
+    # ------------------------------------------------------------------ posteriors
+    def _require_subtypes(self, what):
+        self._require_fitted(what)
+        if self.responsibilities is None:
+            raise ValueError("%s needs a fitted model: call run() first" % what)
+
+    def subtype_posterior(self):
+        """
+        The subtypes of the patients, from the last run(), as a dict:
+            responsibilities (U, G)  q(z_u = g);   labels (U,) int64  their argmax
+            rho_mean (G,)            E rho_g = (alpha + n_g) / (G alpha + U);   n_effective (G,)  n_g = sum_u s[u, g]
+            coassignment (U, U)      s s^T: the probability under q that two patients share a subtype (the diagonal is sum_g s^2)
+        """
+        self._require_subtypes("subtype_posterior()")
+        s = np.array(self.responsibilities, dtype=np.float64)
+        (U, G) = s.shape
+        alpha = self._alpha()
+        n = s.sum(axis=0)
+        return {"responsibilities": s, "labels": np.argmax(s, axis=1).astype(np.int64), "rho_mean": (alpha + n) / (G * alpha + U),
+                "n_effective": n, "coassignment": s @ s.T}
+
+    def region_posterior(self):
+        """{"p_region" (N, G): q(r_ng = 1), "subtype_names": the G column indices} from the last run()."""
+        self._require_subtypes("region_posterior()")
+        lq_R = self._lq_R
+        return {"p_region": np.exp(lq_R[:, :, 1]), "subtype_names": list(range(lq_R.shape[1]))}
+
+    def connection_posterior(self):
+        """
+        Per connection and PATIENT, as UnsharedRegionFit.connection_posterior(): p_T (C, U), p_F_tilde (C, U, 3), p_changed
+        (C, U).  Given z_u = g the patient's T and F~ have the closed-form law of the unshared model under subtype g's q_R,
+        so the result is the mixture over g, weighted with s[u, g], of G calls of the unshared kernel with q_R[:, g] broadcast
+        to every patient, summed on the device.  Sessions and noise variances work as in the unshared fit.
+        """
+        self._require_subtypes("connection_posterior()")
+        (N, C, G) = self._check_state(need=("lq_R", "lq_F"))
+        U = self._patients()
+        resp = self._resp_dev()
+        bt = self._bt_dev(C, U)
+        out = None
+        for g in range(G):
+            lq_R = self._d["lq_R"][:, g:g + 1, :].expand(N, U, 2).contiguous()
+            post = conn_posterior(self._context(), bt, N, U, self.model.theta(), lq_F=self._d["lq_F"], lq_R=lq_R,
+                                  missing_data=self.missing_data, as_tensors=True, **self._noise_bt_kw())
+            w = resp[:, g]
+            post = {"p_T": post["p_T"] * w[None, :], "p_F_tilde": post["p_F_tilde"] * w[None, :, None],
+                    "p_changed": post["p_changed"] * w[None, :]}
+            out = post if out is None else {k: out[k] + post[k] for k in out}
+        return {k: v.cpu().numpy() for (k, v) in out.items()}
+
+    def assign(self, bt_new, noise_var=None):
+        """
+        Which subtype's map does a new patient get?  The fit is held and left exactly as it was (q_F, q_R, q(rho), theta, the
+        tables).  bt_new (C, U') or (C, U', K'), any K', in the fit's edge order (NaN = unobserved when missing_data);
+        noise_var (U',) or (U', K') as in score(): a fit with noise variances refuses None (ValueError).  Returns a dict:
+            expected_loglik (U', G)    E[u, g], the expected log-likelihood of patient u under subtype g's map
+            responsibilities (U', G)   softmax_g(E[u, g] + E ln rho_g), E ln rho of the fit's q(rho)
+        A patient's row does not depend on the other patients of the call.
+        """
+        self._require_subtypes("assign()")
+        bt_new = np.ascontiguousarray(bt_new, dtype=np.float64)
+        if bt_new.ndim not in (2, 3) or (bt_new.ndim == 3 and bt_new.shape[2] < 1):
+            raise ValueError("bt_new must be (C, U') or (C, U', K') with K' >= 1, got shape %s" % (bt_new.shape,))
+        (C, U) = bt_new.shape[:2]
+        C_fit = int(self._d["lq_F"].shape[0])
+        if C != C_fit:
+            raise ValueError("bt_new has %d connections, the fit has %d" % (C, C_fit))
+        if U < 1:
+            raise ValueError("assign() needs at least one patient")
+        if self._has_noise() and noise_var is None:
+            raise ValueError("assign(): the fit has noise variances, so the new patients' noise_var must be given (zeros are allowed)")
+        noise = self._noise_host(bt_shape=bt_new.shape, bt_var=noise_var, name="noise_var")
+        if noise is not None:
+            noise = tuple(None if a is None else self._up(a) for a in noise)
+        ctx = self._query_context()
+        (_S_B, lM_u) = _score.lik_tables(ctx, self._data_dev("b"), self._up(bt_new), self.model.theta(), self.missing_data, noise)
+        E = self._expected_loglik(ctx, lM_u)
+        el = subtype_E_ln_rho(np.asarray(self.responsibilities, dtype=np.float64).sum(axis=0), self._alpha())
+        return {"responsibilities": subtype_softmax(E + el[None, :]), "expected_loglik": E}
+
+    def patient_group_posterior(self, *args, **kwargs):
+        """Not provided: the state's columns are the subtypes, not patients."""
+        raise ValueError("SubtypeRegionFit has no patient_group_posterior(): the state's columns are the subtypes")
+
+    def patient_trait_posterior(self, *args, **kwargs):
+        """Not provided: the state's columns are the subtypes, not patients."""
+        raise ValueError("SubtypeRegionFit has no patient_trait_posterior(): the state's columns are the subtypes")
+
+    def score(self, *args, **kwargs):
+        """Not provided: see assign() for the subtype of a new patient."""
+        raise NotImplementedError("score() is not provided for the subtype-region model: assign() gives a new patient's subtype")
+
+    def membership(self, *args, **kwargs):
+        """Not provided: there is no sampler fit of this model."""
+        raise NotImplementedError("membership() is not provided for the subtype-region model: it needs a sampler fit")
+
+    def log_evidence(self, *args, **kwargs):
+        """Not provided: the inherited AIS would treat L as a data table, which it is not; -energy[-1] is the comparison number."""
+        raise NotImplementedError("log_evidence() is not provided for the subtype-region model: the inherited annealing would "
+                                  "read the weighted table L as data; compare models by the ELBO, -energy[-1]")
+
+
 def count_posterior(ctx, lq_R, Nreg, U):
     """
     (p_patient (U, Nreg+1), p_region (Nreg, U+1)) as NumPy float64 through fcd_vb_count_posterior: the Poisson-binomial
@@ -1996,7 +2387,8 @@ def coanomaly_from_counts(region_pair_counts, patient_pair_counts, states):
             "p_patient_pair": pp / (float(states) * N), "expected_regions": pp / float(states)}
 
 
-def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=None, missing_data=False, noise_var=None):
+def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=None, missing_data=False, noise_var=None,
+                   as_tensors=False):
     """
     {p_T (C,U), p_F_tilde (C,U,3), p_changed (C,U)} as NumPy float64 through fcd_conn_posterior: weights from `counts`
     (C,U,3,3) uint32 (held in an int32 tensor), or from the log-probabilities lq_F (C,1,3) and lq_R (Nreg,U,2).
@@ -2004,6 +2396,7 @@ def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=Non
     bt_dev (C, U, K): K sessions per patient (fcd_conn_posterior_sessions); an item with no observed session gets the prior law.
     noise_var: float64 device tensor (U, K) ((U,) or (U, 1) for a 2-D bt) of known measurement variances on top of sigma^2
     (fcd_conn_posterior_noise, for a bt of either rank); None: none.
+    as_tensors: the three as device tensors, for a caller that combines several calls on the device.
     """
     import torch
     C = util.N_to_C(int(Nreg))
@@ -2034,6 +2427,8 @@ def conn_posterior(ctx, bt_dev, Nreg, U, theta, counts=None, lq_F=None, lq_R=Non
              _lib.dptr(None if lq_F is None else lq_F.contiguous()), _lib.dptr(None if lq_R is None else lq_R.contiguous()),
              _lib.FCD_DATA_NAN_MISSING if missing_data else 0, _lib.dptr(p_T), _lib.dptr(p_Ft), _lib.dptr(p_ch),
              _lib.stream_ptr())
+    if as_tensors:
+        return {"p_T": p_T, "p_F_tilde": p_Ft, "p_changed": p_ch}
     return {"p_T": p_T.cpu().numpy(), "p_F_tilde": p_Ft.cpu().numpy(), "p_changed": p_ch.cpu().numpy()}
 
 

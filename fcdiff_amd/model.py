@@ -370,3 +370,60 @@ class GroupedRegionModel(_RegionModelParams):
         else:
             b_tilde = (mu[ftk][:, :, None] + sg[ftk][:, :, None] * g.standard_normal((C, U, int(sessions)))).clip(-1, 1)
         return (r, t, _onehot(fk, (C,)), _onehot(ftk, (C, U)), b, b_tilde)
+
+
+class SubtypeRegionModel(_RegionModelParams):
+    """
+    The subtype-region model: GroupedRegionModel with the group of every patient drawn instead of given.  The parameters
+    and defaults of the other models, and
+        n_subtypes : int         number of latent subtypes G
+        rho : None or (G,)       probabilities of the subtypes; None: 1/G each
+        z_u ~ Categorical(rho) per patient; r_ng ~ Bernoulli(pi) per region and subtype; patient u reads column z_u;
+        T, F, F~, B and B~ as in GroupedRegionModel.
+    Fitted by fcdiff_amd.fit.SubtypeRegionFit, which puts a Dirichlet prior on rho and integrates it out.
+    """
+
+    def __init__(self):
+        super(SubtypeRegionModel, self).__init__()
+        self.n_subtypes = 2
+        self.rho = None
+
+    def __str__(self):
+        return textwrap.dedent('''\
+            fcdiff_amd.SubtypeRegionModel
+                n_subtypes = %d
+                rho = %s
+                pi = %g
+                eta = %g
+                gamma = %s
+                epsilon = %g
+                mu = %s
+                sigma = %s''' % (self.n_subtypes, self.rho, self.pi2()[1], self.eta, self.gamma, self.epsilon, self.mu, self.sigma))
+
+    def rho_vector(self):
+        """(G,) float64 probabilities of the subtypes.  ValueError for n_subtypes < 1, a wrong length, a negative or NaN entry
+        or a sum that is not 1."""
+        G = int(self.n_subtypes)
+        if G != self.n_subtypes or G < 1:
+            raise ValueError("n_subtypes must be an integer >= 1, got %r" % (self.n_subtypes,))
+        if self.rho is None:
+            return np.full(G, 1.0 / G)
+        rho = np.asarray(self.rho, dtype=np.float64)
+        if rho.shape != (G,) or not np.all(rho >= 0) or abs(rho.sum() - 1.0) > 1e-9:
+            raise ValueError("rho must be %d probabilities that sum to 1, got %r" % (G, self.rho))
+        return rho / rho.sum()
+
+    def sample(self, N, H, U, seed=0, sessions=None):
+        """
+        (z (U,) int64, r, t, f, f_tilde, b, b_tilde): the subtype of every patient, drawn with a generator of its own
+        (numpy.random.default_rng([seed, n_subtypes])), then GroupedRegionModel.sample(N, H, z, seed, sessions) of this
+        model's parameters, element for element -- with one subtype that is SharedRegionModel.sample's draw, r as a column.
+        As there, the columns of r (N, .) are the subtypes that OCCUR in z, in ascending order: a subtype no patient
+        drew has no column.
+        """
+        rho = self.rho_vector()
+        z = np.random.default_rng([int(seed), len(rho)]).choice(len(rho), size=int(U), p=rho).astype(np.int64)
+        grouped = GroupedRegionModel()
+        for name in ("pi", "eta", "gamma", "epsilon", "mu", "sigma"):
+            setattr(grouped, name, getattr(self, name))
+        return (z,) + grouped.sample(N, H, [int(v) for v in z], seed=seed, sessions=sessions)

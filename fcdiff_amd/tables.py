@@ -11,10 +11,13 @@ from . import _lib
 # fcd_lik_sessions.hip's FCD_NOISE_LDS_RECORDS: up to this many per-subject records (max(H, U K)) the noise tables keep them in
 # LDS, above it they are read from global memory.  Tests build on both sides of it.
 NOISE_LDS_RECORDS = 768
+# fcd_subtype.hip's SUBTYPE_MAX: the most subtypes (columns of the responsibilities) the weighted table and the subtype
+# log-likelihood are built for
+SUBTYPE_MAX = 8
 
 
 def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB=None, pBt=None, n_missing=None, noise=None,
-          groups=None):
+          groups=None, weights=None):
     """
     (S_B (C, 3), lM) of b_dev (C, H) and bt_dev (C, U) at theta, in ONE library call on `ctx`:
       shared=False  fcd_lik_tables_ex: lM (C, U, 3, 3) and, where given, the per-item tables lpB (C, H, 3), pBt (C, U, 3);
@@ -36,8 +39,17 @@ def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB
     is K = 1) and with or without `noise`.  There are no per-item tables (lpB, pBt: ValueError), and shared=True with groups
     is a ValueError (one group is the shared table).  The contents of the two index tensors are the caller's to check on the
     host (group_labels_csr does): nothing here reads them.
+    weights: None, or (lM_patients, resp): the per-patient table (C, U, 3, 3) of an earlier unshared build of the same data and
+    responsibilities resp (U, G), 1 <= G <= SUBTYPE_MAX, both float64 device tensors.  It selects fcd_lik_weighted_tables: lM
+    is L (C, G, 3, 3), L[c, g] = sum_u resp[u, g] lM_patients[c, u], written in place where given -- the table of the
+    subtype-region model at its current responsibilities (`groups` is its one-hot case).  The data is not read again (noise,
+    sessions and missing data are in lM_patients already) and S_B is returned as given: b_dev, bt_dev and theta only say the
+    shape.  shared=True or groups with weights is a ValueError, and so are per-item tables and n_missing.  The values of resp
+    are the caller's to check; a weight that is exactly 0 adds nothing, whatever the entry.
     """
     import torch
+    if weights is not None:
+        return _build_weighted(ctx, b_dev, bt_dev, shared, S_B, lM, lpB, pBt, n_missing, groups, weights)
     (C, H) = (int(b_dev.shape[0]), int(b_dev.shape[1]))
     if bt_dev.dim() not in (2, 3):
         raise ValueError("bt must be (C, U) or (C, U, K), got shape %s" % (tuple(bt_dev.shape),))
@@ -101,6 +113,38 @@ def build(ctx, b_dev, bt_dev, theta, flags, shared=False, S_B=None, lM=None, lpB
         ctx.call("fcd_lik_tables_ex", _lib.dptr(b_dev), _lib.dptr(bt_dev), C, H, U, th, _lib.dptr(S_B), _lib.dptr(lM),
                  _lib.dptr(lpB), _lib.dptr(pBt), int(flags), _lib.dptr(n_missing), _lib.stream_ptr())
     return S_B, lM
+
+
+def _build_weighted(ctx, b_dev, bt_dev, shared, S_B, L, lpB, pBt, n_missing, groups, weights):
+    """build()'s `weights` form: (S_B as given, L) through fcd_lik_weighted_tables, after its argument checks."""
+    import torch
+    if shared or groups is not None:
+        raise ValueError("weights excludes shared=True and groups: responsibilities of one column are the shared table, "
+                         "one-hot ones the grouped table")
+    if lpB is not None or pBt is not None or n_missing is not None:
+        raise ValueError("the weighted table reads the per-patient table, not the data: no per-item tables (lp_B_g_F, p_Bt_g_Ft) "
+                         "and no NaN counts")
+    if bt_dev.dim() not in (2, 3):
+        raise ValueError("bt must be (C, U) or (C, U, K), got shape %s" % (tuple(bt_dev.shape),))
+    (C, U) = (int(b_dev.shape[0]), int(bt_dev.shape[1]))
+    if not isinstance(weights, (tuple, list)) or len(weights) != 2:
+        raise ValueError("weights must be (lM_patients (C, U, 3, 3), resp (U, G))")
+    (lM_u, resp) = weights
+    if tuple(lM_u.shape) != (C, U, 3, 3) or lM_u.dtype != torch.float64:
+        raise ValueError("weights: the per-patient table must be float64 (C, U, 3, 3) = %s, got %s"
+                         % ((C, U, 3, 3), tuple(lM_u.shape)))
+    if resp.dim() != 2 or int(resp.shape[0]) != U or resp.dtype != torch.float64:
+        raise ValueError("weights: resp must be float64 (U, G) with U = %d, got %s" % (U, tuple(resp.shape)))
+    G = int(resp.shape[1])
+    if not 1 <= G <= SUBTYPE_MAX:
+        raise ValueError("weights: G = %d subtypes, must be 1 .. %d" % (G, SUBTYPE_MAX))
+    if L is None:
+        L = torch.empty((C, G, 3, 3), dtype=torch.float64, device=lM_u.device)
+    elif tuple(L.shape) != (C, G, 3, 3) or L.dtype != torch.float64 or not L.is_contiguous():
+        raise ValueError("weights: lM must be a contiguous float64 (C, G, 3, 3) = %s, got %s" % ((C, G, 3, 3), tuple(L.shape)))
+    ctx.call("fcd_lik_weighted_tables", _lib.dptr(lM_u.contiguous()), _lib.dptr(resp.contiguous()), C, U, G, _lib.dptr(L),
+             _lib.stream_ptr())
+    return S_B, L
 
 
 def _noise_checked(noise, H, U, K):

@@ -300,6 +300,29 @@ int fcd_lik_grouped_tables(fcd_ctx *ctx, const double *b, const double *bt, int6
                            const int64_t *offsets, int64_t G, double *S_B, double *L, int flags, int64_t *nan_counts,
                            fcd_stream stream);
 
+/* ---- latent subtypes of patients: the two passes of the subtype-region model over the per-patient table ----------------
+ * With responsibilities resp[u, g] = q(z_u = g), U patients and 1 <= G <= 8 subtypes, both fp64, both reading
+ * lM (C, U, 3, 3) exactly once for all G, both with a fixed summation order and no atomics (two calls agree bit for bit).
+ *
+ * fcd_lik_weighted_tables: L (C, G, 3, 3),
+ *   L[c, g, k, l] = sum_u resp[u, g] lM[c, u, k, l],
+ * the table of the unshared model at G pseudo-patients that the variational updates of the subtype-region model run on
+ * (fcd_lik_grouped_tables' L is the one-hot case).  A weight that is exactly 0 adds 0.0 whatever the entry, so 0 * -inf is 0;
+ * with a positive weight -inf stays -inf.  resp is (U, G) row-major, a DEVICE pointer, not checked.  No workspace.
+ *
+ * fcd_vb_subtype_loglik: E (U, G),
+ *   E[u, g] = sum_c sum_k q_F[c,k] sum_l w_l^g(c) lM[c, u, k, l]
+ * with lq_F (C, 1, 3), lq_R (Nreg, G, 2) the subtypes' q_R and w^g(c) its mixture-case weights at the true endpoints of c, in
+ * the case order and with the products of fcd_vb_patient_elbo's E_lM term (q * lM is a plain product).  E[u, :] does not
+ * depend on the other patients of the call.  Uses the context's workspace.
+ *
+ * Refusals: null pointers, G < 1 or G > 8, U < 1, L aliasing lM FCD_ERR_ARG; a non-triangular C or Nreg < 2 FCD_ERR_SHAPE;
+ * Nreg > 46340, U > 2^24 or more than 2^31 - 1 workgroups FCD_ERR_UNSUPPORTED. */
+int fcd_lik_weighted_tables(fcd_ctx *ctx, const double *lM, const double *resp, int64_t C, int64_t U, int64_t G, double *L,
+                            fcd_stream stream);
+int fcd_vb_subtype_loglik(fcd_ctx *ctx, const double *lq_F, const double *lq_R, const double *lM, int64_t Nreg, int64_t U,
+                          int64_t G, double *E, fcd_stream stream);
+
 /* ---- forward sampler: UnsharedRegionModel.sample, fcdiff/model.py:52-236, on the device ---------------
  * Counter RNG (Philox), all variables drawn in parallel; the reference's MT19937 stream is not reproduced (the host
  * sampler of the Python mirror does that) -- same distribution.  Type INDICES are returned: r (Nreg,U), t (C,U),
