@@ -18,7 +18,7 @@
 //   coanomaly_vb_kernel   the same two matrices if the sites were independent with marginals q_nu from lq_R (the mean
 //                         field's law): sum_u q_nu q_mu and sum_n q_nu q_nv off the diagonals, sum_u q_nu and sum_n q_nu
 //                         on them (r^2 = r).  fp64, summed in index order: results repeat bit for bit.
-#include "fcd_common.h"
+#include "fcd_tally.h"
 
 namespace {
 
@@ -154,9 +154,8 @@ __global__ __launch_bounds__(CO_THREADS) void coanomaly_kernel(const uint64_t *_
     else co_tile<false>(r_bits, Nreg, U, GW, G, pt, b - rg.blocks, lds);
 }
 
-// Tile (by, bx) of the region matrix (blockIdx.z = 0) or the patient matrix (1); q_nu = P(r_nu = 1) from lq_R, normalised in
-// log space as poisson_binomial_kernel does (q = 0 and q = 1 exact), made where the chunk is staged.  Every output sums
-// its terms in index order.
+// Tile (by, bx) of the region matrix (blockIdx.z = 0) or the patient matrix (1); q_nu = P(r_nu = 1) from lq_R (tally_q: q = 0
+// and q = 1 exact), made where the chunk is staged.  Every output sums its terms in index order.
 __global__ __launch_bounds__(VB_T * VB_T) void coanomaly_vb_kernel(const double *__restrict__ lq_R, int Nreg, int U,
                                                                    double *__restrict__ region, double *__restrict__ patient) {
     __shared__ double qa[VB_T][VB_KC + 1], qb[VB_T][VB_KC + 1];
@@ -175,14 +174,8 @@ __global__ __launch_bounds__(VB_T * VB_T) void coanomaly_vb_kernel(const double 
             // region: k = u runs along lq_R's rows; patient: the output index u does
             const int row = reg ? x / VB_KC : x % VB_T, kk = reg ? x % VB_KC : x / VB_T;
             const int gr = (side ? j0 : i0) + row, gk = k0 + kk;
-            double q = 0.0;
-            if (gr < L && gk < K) {
-                const int64_t site = reg ? (int64_t)gr * U + gk : (int64_t)gk * U + gr;
-                const double l0 = lq_R[site * 2], l1 = lq_R[site * 2 + 1];
-                const double mx = fmax(l0, l1);
-                const double e0 = exp(l0 - mx), e1 = exp(l1 - mx);
-                q = e1 / (e0 + e1);
-            }
+            double q0, q = 0.0;
+            if (gr < L && gk < K) tally_q(lq_R, reg ? (int64_t)gr * U + gk : (int64_t)gk * U + gr, q0, q);
             (side ? qb : qa)[row][kk] = q;
         }
         __syncthreads();

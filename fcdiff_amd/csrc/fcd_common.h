@@ -142,6 +142,15 @@ static inline int fcd_fail(fcd_ctx *ctx, int code, const char *fmt, long long a 
     if (ctx) snprintf(ctx->msg, sizeof(ctx->msg), fmt, a, b);
     return code;
 }
+// the same for a message "<who>: <text>", text = fmt with its numbers (`who` is a name, not a format)
+static inline int fcd_fail_who(fcd_ctx *ctx, int code, const char *who, const char *fmt, long long a = 0, long long b = 0) {
+    if (ctx) {
+        char tail[192];
+        snprintf(tail, sizeof(tail), fmt, a, b);
+        snprintf(ctx->msg, sizeof(ctx->msg), "%s: %s", who, tail);
+    }
+    return code;
+}
 
 // What the fcd_gibbs_set_*_accumulator entry points share: all buffers null detaches, else the checks and the store.  The
 // message texts are the caller's (fcd_fail formats numbers only); msg_limit is non-null where the shape is past a limit of
@@ -214,7 +223,8 @@ template <typename T>
 int fcd_pair_tally_launch(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
                           const fcd_geo &g, T *acc, bool accumulate, hipStream_t s);
 // the anomalous-region count kernels of fcd_count.hip (two launches): both histograms += the counts of this state; the
-// scratch they need is grown by fcd_count_ws_reserve (fcd_gibbs_run: before its sweep loop)
+// scratch they need is grown by fcd_count_ws_reserve (fcd_gibbs_run: before its sweep loop, through its table of the slots,
+// which is why the four *_ws_reserve take the same arguments)
 int fcd_count_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
 int fcd_count_ws_grow(fcd_ctx *ctx, size_t bytes);      // ... and by the tallies that share it: at least this many bytes
 int fcd_count_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
@@ -224,17 +234,17 @@ int fcd_coanomaly_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nre
                                uint32_t *region_pairs, uint32_t *patient_pairs, hipStream_t s);
 // the region-set kernels of fcd_region_sets.hip (two launches): both histograms += the counts of this state over the
 // context's sets; their scratch is the count tally's, grown by fcd_region_set_ws_reserve (fcd_gibbs_run: before its loop)
-int fcd_region_set_ws_reserve(fcd_ctx *ctx, int64_t U, int64_t G);
+int fcd_region_set_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
 int fcd_region_set_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
                                 uint32_t *hist_set, uint32_t *hist_prev, hipStream_t s);
 // the patient-group kernels of fcd_patient_groups.hip (two launches): both histograms += the counts of this state over the
 // context's groups and contrasts; same scratch, grown by fcd_patient_group_ws_reserve (fcd_gibbs_run: before its loop)
-int fcd_patient_group_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t G);
+int fcd_patient_group_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
 int fcd_patient_group_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
                                    uint32_t *hist_group, uint32_t *hist_joint, hipStream_t s);
 // the patient-trait kernels of fcd_patient_traits.hip (two launches): histogram and sums += the rank-sum statistics of this
 // state over the context's traits; same scratch, grown by fcd_patient_trait_ws_reserve (fcd_gibbs_run: before its loop)
-int fcd_patient_trait_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t G);
+int fcd_patient_trait_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
 int fcd_patient_trait_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
                                    uint32_t *trait_hist, int64_t *trait_sum, hipStream_t s);
 // bracket ONE kernel launch with events when profiling is on (no-ops otherwise)

@@ -12,7 +12,7 @@
 //                             sum_u r_nu = k}: one workgroup per row, bins in LDS, the row updated once without atomics.
 //   poisson_binomial_kernel   the mean-field law of the same counts under q_R (sites independent: Poisson-binomial), the
 //                             exact fp64 convolution recursion, one workgroup per row.
-#include "fcd_common.h"
+#include "fcd_tally.h"
 
 namespace {
 
@@ -28,8 +28,8 @@ constexpr int PB_MAX_SITES = PB_THREADS * PB_MAXK - 1;
 
 // Phase 1.  Grid-stride over chain words w.  Per tile of tn rows (n0 .. n0 + rows) of word w, staged with all threads' loads
 // in flight together:
-//   patient role  thread u < U: carry-save adds of the tile's column u into pl[] (bit b of chain j's count in bit j of
-//                 pl[b]); after the last tile the 64 counts go to sums row u, four per 8-byte store.
+//   patient role  thread u < U: carry-save adds of the tile's column u into its tally_planes; after the last tile the 64
+//                 counts go to sums row u.
 //   region role   wave v: rows j = v, v + nwaves, ... of the tile; lane j counts chain j's bits over u (broadcast LDS
 //                 reads) and writes it to sums row U + n0 + j (64 lanes, one 128-byte line).
 // sums: (U + Nreg) rows of GP = GW * 64 uint16, chain-major within a row; chains beyond G hold whatever their bits give.
@@ -40,9 +40,8 @@ __global__ __launch_bounds__(CNT_THREADS) void count_sums_kernel(const uint64_t 
     const int64_t GP = (int64_t)GW * 64;
     for (int w = blockIdx.x; w < GW; w += gridDim.x) {
         const uint64_t *rw = r_bits + (int64_t)w * Nreg * U;
-        uint64_t pl[CNT_PLANES];
-#pragma unroll
-        for (int b = 0; b < CNT_PLANES; ++b) pl[b] = 0;
+        tally_planes<CNT_PLANES> pl;
+        pl.clear();
         for (int n0 = 0; n0 < Nreg; n0 += tn) {
             const int rows = min(tn, Nreg - n0);
             const int nw = rows * U;                 // <= CNT_TILE_WORDS: contiguous in r_bits ([w][n][u])
@@ -61,15 +60,7 @@ __global__ __launch_bounds__(CNT_THREADS) void count_sums_kernel(const uint64_t 
             }
             __syncthreads();
             if (tid < U) {
-                for (int j = 0; j < rows; ++j) {
-                    uint64_t carry = tile[j * U + tid];
-#pragma unroll
-                    for (int b = 0; b < CNT_PLANES; ++b) {
-                        const uint64_t t = pl[b] & carry;
-                        pl[b] ^= carry;
-                        carry = t;
-                    }
-                }
+                for (int j = 0; j < rows; ++j) pl.add(tile[j * U + tid]);
             }
             for (int j = wave; j < rows; j += nwaves) {
                 const uint64_t *row = tile + j * U;
@@ -79,48 +70,23 @@ __global__ __launch_bounds__(CNT_THREADS) void count_sums_kernel(const uint64_t 
                 sums[(int64_t)(U + n0 + j) * GP + (int64_t)w * 64 + lane] = (uint16_t)cnt;
             }
         }
-        if (tid < U) {
-            uint64_t *dst = reinterpret_cast<uint64_t *>(sums + (int64_t)tid * GP + (int64_t)w * 64);
-            for (int j0 = 0; j0 < 64; j0 += 4) {
-                uint64_t packed = 0;
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    uint64_t k = 0;
-#pragma unroll
-                    for (int b = 0; b < CNT_PLANES; ++b) k |= ((pl[b] >> (j0 + jj)) & 1ull) << b;
-                    packed |= k << (16 * jj);
-                }
-                dst[j0 / 4] = packed;
-            }
-        }
+        if (tid < U) pl.store16(sums + (int64_t)tid * GP + (int64_t)w * 64);
     }
 }
 
 // Phase 2.  One workgroup per histogram row: rows 0 .. U-1 patient u (bins 0 .. Nreg), rows U .. U+Nreg-1 region n (bins
-// 0 .. U).  The row's G counts are binned with LDS atomics, then added to the row in place: the row belongs to this
-// workgroup alone, so no global atomics (same-address device-scope atomics from every chain word cost ~70 us per tally
-// at cfg3 in the first form of this kernel).
+// 0 .. U), binned by tally_bin_row.
 __global__ __launch_bounds__(256) void count_hist_kernel(const uint16_t *__restrict__ sums, int Nreg, int U, int GW, int64_t G,
                                                          uint32_t *__restrict__ hist_p, uint32_t *__restrict__ hist_r) {
     extern __shared__ uint32_t bins[];           // [L + 1]
-    const int row = blockIdx.x, tid = threadIdx.x;
+    const int row = blockIdx.x;
     const bool patient = row < U;
-    const int L = patient ? Nreg : U;
     uint32_t *out = patient ? hist_p + (int64_t)row * (Nreg + 1) : hist_r + (int64_t)(row - U) * (U + 1);
-    const uint16_t *src = sums + (int64_t)row * GW * 64;
-    for (int k = tid; k <= L; k += blockDim.x) bins[k] = 0;
-    __syncthreads();
-    for (int64_t g = tid; g < G; g += blockDim.x) atomicAdd(&bins[min((int)src[g], L)], 1u);
-    __syncthreads();
-    for (int k = tid; k <= L; k += blockDim.x) {
-        const uint32_t c = bins[k];
-        if (c) out[k] += c;
-    }
+    tally_bin_row(sums + (int64_t)row * GW * 64, G, patient ? Nreg : U, bins, out);
 }
 
 // Rows 0 .. U-1: patient u over the sites n = 0 .. Nreg-1; rows U .. U+Nreg-1: region n over u = 0 .. U-1.
-// q0 = P(r = 0), q1 = P(r = 1) from lq_R, normalised in log space (the larger log-weight subtracted), so lq_R need not be
-// normalised and q = 0 / q = 1 come out exact.  P[k+1] = P(count = k) with P[0] = 0; each site is one step
+// q0 = P(r = 0), q1 = P(r = 1) from lq_R (tally_q).  P[k+1] = P(count = k) with P[0] = 0; each site is one step
 //   P'(k) = P(k) q0 + P(k-1) q1
 // over the bins that can be non-zero, all threads reading before any writes.  Point masses stay exact at q in {0, 1}.
 __global__ __launch_bounds__(PB_THREADS) void poisson_binomial_kernel(const double *__restrict__ lq_R, int Nreg, int U,
@@ -139,14 +105,7 @@ __global__ __launch_bounds__(PB_THREADS) void poisson_binomial_kernel(const doub
     for (int i0 = 0; i0 < L; i0 += PB_THREADS) {
         __syncthreads();                         // the previous chunk of q is used (and P is initialised)
         const int i = i0 + tid;
-        if (i < L) {
-            const double l0 = lq_R[(site0 + (int64_t)i * step) * 2], l1 = lq_R[(site0 + (int64_t)i * step) * 2 + 1];
-            const double mx = fmax(l0, l1);
-            const double e0 = exp(l0 - mx), e1 = exp(l1 - mx);
-            const double s = e0 + e1;
-            q0[tid] = e0 / s;
-            q1[tid] = e1 / s;
-        }
+        if (i < L) tally_q(lq_R, site0 + (int64_t)i * step, q0[tid], q1[tid]);
         __syncthreads();
         const int ni = min(PB_THREADS, L - i0);
         for (int j = 0; j < ni; ++j) {
@@ -185,7 +144,7 @@ int fcd_count_ws_grow(fcd_ctx *ctx, size_t bytes) {
 }
 
 int fcd_count_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G) {
-    return fcd_count_ws_grow(ctx, (size_t)(Nreg + U) * (size_t)((G + 63) / 64) * 64 * sizeof(uint16_t));
+    return tally_ws_reserve(ctx, Nreg + U, G, sizeof(uint16_t));
 }
 
 int fcd_count_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
@@ -198,10 +157,7 @@ int fcd_count_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, i
     uint16_t *sums = (uint16_t *)ctx->count_ws;
     int64_t tn = CNT_TILE_WORDS / U;
     if (tn > Nreg) tn = Nreg;
-    int64_t blocks = g.GW;
-    const int64_t cap = (int64_t)ctx->num_cu * 8;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(count_sums_kernel, dim3((unsigned)blocks), dim3(CNT_THREADS), (size_t)(tn * U) * sizeof(uint64_t), s,
+    hipLaunchKernelGGL(count_sums_kernel, dim3(tally_grid(ctx, g.GW)), dim3(CNT_THREADS), (size_t)(tn * U) * sizeof(uint64_t), s,
                        r_bits, (int)Nreg, (int)U, g.GW, (int)tn, sums);
     FCD_LAUNCH_CHECK();
     const int64_t L = Nreg > U ? Nreg : U;

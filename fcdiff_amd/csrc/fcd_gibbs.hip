@@ -1534,13 +1534,17 @@ static int acc_launch_patient_trait(fcd_ctx *ctx, const fcd_sweep_call &c, const
 static const struct {
     const char *msg_shape;
     int (*launch)(fcd_ctx *, const fcd_sweep_call &, const fcd_geo &, const fcd_sweep_acc &, hipStream_t);
+    int (*reserve)(fcd_ctx *, int64_t Nreg, int64_t U, int64_t G);     // its scratch (fcd_gibbs_run: before the loop), or nullptr
 } SWEEP_ACC[FCD_ACC_N] = {
-    {"fcd_gibbs_run: the attached pair accumulator was made for Nreg=%lld, U=%lld", acc_launch_pair},
-    {"fcd_gibbs_run: the attached count accumulator was made for Nreg=%lld, U=%lld", acc_launch_count},
-    {"fcd_gibbs_run: the attached co-anomaly accumulator was made for Nreg=%lld, U=%lld", acc_launch_coanomaly},
-    {"fcd_gibbs_run: the attached region-set accumulator was made for Nreg=%lld, U=%lld", acc_launch_region_set},
-    {"fcd_gibbs_run: the attached patient-group accumulator was made for Nreg=%lld, U=%lld", acc_launch_patient_group},
-    {"fcd_gibbs_run: the attached patient-trait accumulator was made for Nreg=%lld, U=%lld", acc_launch_patient_trait},
+    {"fcd_gibbs_run: the attached pair accumulator was made for Nreg=%lld, U=%lld", acc_launch_pair, nullptr},
+    {"fcd_gibbs_run: the attached count accumulator was made for Nreg=%lld, U=%lld", acc_launch_count, fcd_count_ws_reserve},
+    {"fcd_gibbs_run: the attached co-anomaly accumulator was made for Nreg=%lld, U=%lld", acc_launch_coanomaly, nullptr},
+    {"fcd_gibbs_run: the attached region-set accumulator was made for Nreg=%lld, U=%lld", acc_launch_region_set,
+     fcd_region_set_ws_reserve},
+    {"fcd_gibbs_run: the attached patient-group accumulator was made for Nreg=%lld, U=%lld", acc_launch_patient_group,
+     fcd_patient_group_ws_reserve},
+    {"fcd_gibbs_run: the attached patient-trait accumulator was made for Nreg=%lld, U=%lld", acc_launch_patient_trait,
+     fcd_patient_trait_ws_reserve},
 };
 
 // The sampler loop of ONE rank between two exchanges of pooled statistics: fcd_gibbs_run (what UnsharedRegionFit(method=
@@ -1689,20 +1693,9 @@ extern "C" int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, 
         if (a.nreg != Nreg || a.u != U) return fcd_fail(ctx, FCD_ERR_SHAPE, SWEEP_ACC[k].msg_shape, a.nreg, a.u);
         acc_mask |= 1u << k;
     }
-    if (acc_mask >> FCD_ACC_COUNT & 1u) {
-        rc = fcd_count_ws_reserve(ctx, Nreg, U, G);          // (grown here, never inside the sweep loop)
-        if (rc) return rc;
-    }
-    if (acc_mask >> FCD_ACC_REGION_SET & 1u) {
-        rc = fcd_region_set_ws_reserve(ctx, U, G);
-        if (rc) return rc;
-    }
-    if (acc_mask >> FCD_ACC_PATIENT_GROUP & 1u) {
-        rc = fcd_patient_group_ws_reserve(ctx, Nreg, G);
-        if (rc) return rc;
-    }
-    if (acc_mask >> FCD_ACC_PATIENT_TRAIT & 1u) {
-        rc = fcd_patient_trait_ws_reserve(ctx, Nreg, G);
+    for (int k = 0; k < FCD_ACC_N; ++k) {
+        if (!(acc_mask >> k & 1u) || !SWEEP_ACC[k].reserve) continue;
+        rc = SWEEP_ACC[k].reserve(ctx, Nreg, U, G);          // (grown here, never inside the sweep loop)
         if (rc) return rc;
     }
     return sweep_loop(ctx, c, sweep0, n_sweeps, mstep_every, accumulate_from, counts, cnt_f, cnt_r, hyper, acc_mask);

@@ -571,24 +571,17 @@ __global__ __launch_bounds__(256) void posterior_sessions_kernel(const double *_
 // ---------------------------------------------------------------------------------------------
 // host
 
-// a refusal "<who><text>": fcd_fail formats numbers only, so the prefix is put into the format (`who` holds no %)
-int sess_fail(fcd_ctx *ctx, int code, const char *who, const char *text, long long a = 0, long long b = 0) {
-    char fmt[192];
-    snprintf(fmt, sizeof(fmt), "%s%s", who, text);
-    return fcd_fail(ctx, code, fmt, a, b);
-}
-
 // the checks the table entry points share with their 2-D siblings; who = "sessions tables" or "noise tables".  `records`:
 // the record forms, whose kernels index the U K records of a state with 32 bits
 int sess_check(fcd_ctx *ctx, const char *who, bool records, int64_t C, int64_t H, int64_t U, int64_t K, int flags, bool counted) {
-    if (flags & ~FCD_DATA_NAN_MISSING) return sess_fail(ctx, FCD_ERR_ARG, who, ": unknown flags 0x%x", flags);
+    if (flags & ~FCD_DATA_NAN_MISSING) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "unknown flags 0x%x", flags);
     if (counted && !(flags & FCD_DATA_NAN_MISSING))
-        return sess_fail(ctx, FCD_ERR_ARG, who, ": missing counts need FCD_DATA_NAN_MISSING");
-    if (C < 1 || H < 1 || U < 1) return sess_fail(ctx, FCD_ERR_ARG, who, ": C=%lld and U=%lld (and H) must be >= 1", C, U);
-    if (K < 1) return sess_fail(ctx, FCD_ERR_ARG, who, ": K=%lld sessions, must be >= 1", K);
+        return fcd_fail_who(ctx, FCD_ERR_ARG, who, "missing counts need FCD_DATA_NAN_MISSING");
+    if (C < 1 || H < 1 || U < 1) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "C=%lld and U=%lld (and H) must be >= 1", C, U);
+    if (K < 1) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "K=%lld sessions, must be >= 1", K);
     if (fcd_C_to_N(C) < 0) return fcd_fail(ctx, FCD_ERR_SHAPE, "Number of connections (%lld) must be a triangular number.", C);
     if (H > INT32_MAX || U > INT32_MAX || K > INT32_MAX || C * U > INT64_MAX / 8 / K || (records && U * K > ((int64_t)1 << 31)))
-        return sess_fail(ctx, FCD_ERR_UNSUPPORTED, who, ": H/U/K too large");
+        return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "H/U/K too large");
     return FCD_OK;
 }
 
@@ -760,22 +753,22 @@ int lik_grouped_launch(fcd_ctx *ctx, const double *b, const double *bt, int64_t 
 int conn_posterior_sessions(fcd_ctx *ctx, const char *who, bool records, const double *bt, int64_t Nreg, int64_t U, int64_t K,
                             const double *theta, const double *var_bt, const uint32_t *counts, const double *lq_F,
                             const double *lq_R, int flags, double *p_T, double *p_F_tilde, double *p_changed, hipStream_t s) {
-    if (!ctx || !bt || !theta || !p_T || !p_F_tilde || !p_changed) return sess_fail(ctx, FCD_ERR_ARG, who, ": null pointer");
-    if (flags & ~FCD_DATA_NAN_MISSING) return sess_fail(ctx, FCD_ERR_ARG, who, ": unknown flags 0x%x", flags);
+    if (!ctx || !bt || !theta || !p_T || !p_F_tilde || !p_changed) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "null pointer");
+    if (flags & ~FCD_DATA_NAN_MISSING) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "unknown flags 0x%x", flags);
     if ((counts != nullptr) == (lq_F != nullptr || lq_R != nullptr) || (!counts && (!lq_F || !lq_R)))
-        return sess_fail(ctx, FCD_ERR_ARG, who, ": pass counts, or lq_F and lq_R");
-    if (Nreg < 2 || U < 1 || U > INT32_MAX || Nreg > 46340) return sess_fail(ctx, FCD_ERR_SHAPE, who, ": Nreg=%lld U=%lld", Nreg, U);
-    if (K < 1) return sess_fail(ctx, FCD_ERR_ARG, who, ": K=%lld sessions, must be >= 1", K);
+        return fcd_fail_who(ctx, FCD_ERR_ARG, who, "pass counts, or lq_F and lq_R");
+    if (Nreg < 2 || U < 1 || U > INT32_MAX || Nreg > 46340) return fcd_fail_who(ctx, FCD_ERR_SHAPE, who, "Nreg=%lld U=%lld", Nreg, U);
+    if (K < 1) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "K=%lld sessions, must be >= 1", K);
     const int64_t C = fcd_tri(Nreg);
     if (K > INT32_MAX || C * U > INT64_MAX / 8 / K || (records && U * K > ((int64_t)1 << 31)))
-        return sess_fail(ctx, FCD_ERR_UNSUPPORTED, who, ": K=%lld too large", K);
+        return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "K=%lld too large", K);
     SessPostTheta th;
     const double eta = theta[1], epsilon = theta[2];
     for (int k = 0; k < 3; ++k) {
         th.mu[k] = theta[6 + k];
         th.sigma[k] = theta[9 + k];
         th.lsigma[k] = log(th.sigma[k]);
-        if (!(th.sigma[k] > 0.0)) return sess_fail(ctx, FCD_ERR_ARG, who, ": sigma must be > 0");
+        if (!(th.sigma[k] > 0.0)) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "sigma must be > 0");
     }
     th.eps = epsilon;
     th.e[0] = 1 - epsilon;                        // _eval_M_eps, fit.py:433-444

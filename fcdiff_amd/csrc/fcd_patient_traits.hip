@@ -8,7 +8,7 @@
 // and, where 0 < k < n_q,  AUC = 1/2 + A / (2 k (n_q - k)),  A + k (n_q - k) = 2 U_stat >= 0.  The patients are coupled
 // through f, so the law of (k, A) does not follow from the per-patient marginals; only the sampler's chains carry it.
 // The traits live on the context (fcd_patient_traits_set: checked on the host, so no index a kernel makes can be out of
-// range).  Kernels, in the idiom of fcd_patient_groups.hip (no same-address global atomics):
+// range).  Kernels, from the parts of fcd_tally.h as those of fcd_patient_groups.hip:
 //   patient_trait_sums_kernel   one workgroup per (chain word w, row rho): the row's U words are staged in LDS, lane c is chain
 //                               c and walks the patients with broadcast LDS reads; (uint16 k, int32 A) per (q, rho, chain) go
 //                               to the context's scratch.
@@ -16,7 +16,7 @@
 //                               once without global atomics.
 #include <stdlib.h>
 
-#include "fcd_common.h"
+#include "fcd_tally.h"
 
 namespace {
 
@@ -25,15 +25,13 @@ constexpr int PT_WAVES = PT_THREADS / 64;
 constexpr int PT_MAX_U = 512;
 constexpr int PT_MAX_TRAITS = 16;
 constexpr int PT_NB = 128;                       // AUC bins of width 1/128
-constexpr size_t PT_MAX_SCRATCH = (size_t)1 << 30;
 
 __host__ __device__ inline int pt_u8(int U) { return (U + 7) & ~7; }
 
 // Phase 1.  Grid-stride over the pairs (rho, w), w fastest; blockDim = PT_THREADS; dynamic LDS: Q * U8 int32, U8 = U rounded up
 // to a multiple of 8 (the walk is unrolled by 8).
 //   all threads   once: sk[q][u] = enc[q][u] = 2 a_u + known_u, ZERO for U <= u < U8.
-//   all threads   stage the row: roww[t] = r_bits[w][n][t] for a region row, the OR over the set's members for a set row
-//                 (coalesced over t), and ZERO for U <= t < 64 ceil(U/64): the tail of the last chunk is never stale LDS.
+//   all threads   stage the row (tally_stage_row): whole 64-patient chunks, zero past U.
 //   wave v        traits v, v + 4, ...: lane c takes bit c of roww[u] and the trait's word of u (both broadcast reads) and adds
 //                 the known bit to k, the score to A.  No transpose.
 // ks, As: (Q * R) rows of GP = GW * 64 values, row q * R + rho, chain-major; chains beyond G hold whatever their bits give.
@@ -46,7 +44,7 @@ __global__ __launch_bounds__(PT_THREADS) void patient_trait_sums_kernel(const ui
     __shared__ uint64_t roww[PT_MAX_U];
     extern __shared__ int32_t sk[];              // [Q][U8]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int NC = (U + 63) / 64, U8 = pt_u8(U);
+    const int U8 = pt_u8(U);
     const int64_t GP = (int64_t)GW * 64;
     const int64_t npairs = (int64_t)R * GW;
     for (int i = tid; i < Q * U8; i += PT_THREADS) {
@@ -56,19 +54,7 @@ __global__ __launch_bounds__(PT_THREADS) void patient_trait_sums_kernel(const ui
     // (read only after the first barrier below: the grid never exceeds the number of pairs)
     for (int64_t p = blockIdx.x; p < npairs; p += gridDim.x) {
         const int rho = (int)(p / GW), w = (int)(p % GW);
-        const uint64_t *base = r_bits + (int64_t)w * Nreg * U;
-        for (int t = tid; t < NC * 64; t += PT_THREADS) {
-            uint64_t v = 0;
-            if (t < U) {
-                if (rho < Nreg) {
-                    v = base[(int64_t)rho * U + t];
-                } else {
-                    const int i0 = rs_offsets[rho - Nreg], i1 = rs_offsets[rho - Nreg + 1];
-                    for (int i = i0; i < i1; ++i) v |= base[(int64_t)rs_members[i] * U + t];
-                }
-            }
-            roww[t] = v;
-        }
+        tally_stage_row<PT_THREADS>(r_bits + (int64_t)w * Nreg * U, rs_offsets, rs_members, rho, Nreg, U, roww);
         __syncthreads();
         for (int q = wave; q < Q; q += PT_WAVES) {
             const int32_t *s = sk + q * U8;
@@ -108,7 +94,7 @@ __global__ __launch_bounds__(256) void patient_trait_hist_kernel(const uint16_t 
         const int n = nq[row / R];
         const uint16_t *sk = ks + (int64_t)row * GP;
         const int32_t *sa = As + (int64_t)row * GP;
-        for (int i = tid; i < W; i += blockDim.x) bins[i] = 0;
+        tally_bins_clear(bins, W);
         for (int i = tid; i <= Umax; i += blockDim.x) sums[i] = 0;
         __syncthreads();
         for (int64_t g = tid; g < G; g += blockDim.x) {
@@ -125,11 +111,7 @@ __global__ __launch_bounds__(256) void patient_trait_hist_kernel(const uint16_t 
             }
         }
         __syncthreads();
-        uint32_t *out = trait_hist + (int64_t)row * W;
-        for (int i = tid; i < W; i += blockDim.x) {
-            const uint32_t c = bins[i];
-            if (c) out[i] += c;                                       // (bins n_q < i <= Umax stay 0: never touched)
-        }
+        tally_bins_flush(bins, W, trait_hist + (int64_t)row * W);   // (bins n_q < i <= Umax stay 0: never touched)
         long long *outs = trait_sum + (int64_t)row * (Umax + 1);
         for (int i = tid; i <= Umax; i += blockDim.x) {
             const long long v = (long long)sums[i];
@@ -139,65 +121,42 @@ __global__ __launch_bounds__(256) void patient_trait_hist_kernel(const uint16_t 
     }
 }
 
-int pt_fail(fcd_ctx *ctx, int code, const char *who, const char *fmt, long long a = 0, long long b = 0) {
-    if (ctx) {
-        char tail[192];
-        snprintf(tail, sizeof(tail), fmt, a, b);
-        snprintf(ctx->msg, sizeof(ctx->msg), "%s: %s", who, tail);
-    }
-    return code;
-}
-
-int64_t rows_of(const fcd_ctx *ctx, int64_t Nreg) { return Nreg + (ctx->pt_with_rs ? ctx->rs_J : 0); }
-
 // the refusals the tally, the accumulator and the scratch reservation share: no traits, traits made for another number of
-// patients; with set rows, no sets or a set member outside the regions (as fcd_patient_groups.hip's shape_check)
+// patients; with set rows, what tally_set_rows_check refuses
 int shape_check(fcd_ctx *ctx, int64_t Nreg, int64_t U, const char *who) {
-    if (ctx->pt_Q < 1) return pt_fail(ctx, FCD_ERR_ARG, who, "no patient traits (fcd_patient_traits_set)");
-    if (U != ctx->pt_U) return pt_fail(ctx, FCD_ERR_SHAPE, who, "the traits were set for %lld patients, not U=%lld", ctx->pt_U, U);
-    if (ctx->pt_with_rs) {
-        if (ctx->rs_J < 1) return pt_fail(ctx, FCD_ERR_ARG, who, "the traits were set with region sets and there are none");
-        if (ctx->rs_max_member >= Nreg)
-            return pt_fail(ctx, FCD_ERR_SHAPE, who, "member %lld of a region set with Nreg=%lld", ctx->rs_max_member, Nreg);
-    }
-    return FCD_OK;
+    if (ctx->pt_Q < 1) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "no patient traits (fcd_patient_traits_set)");
+    if (U != ctx->pt_U) return fcd_fail_who(ctx, FCD_ERR_SHAPE, who, "the traits were set for %lld patients, not U=%lld", ctx->pt_U, U);
+    return tally_set_rows_check(ctx, Nreg, ctx->pt_with_rs, who, "traits");
 }
 
 }  // namespace
 
-// grows the scratch of the count tallies by the route fcd_patient_group_ws_reserve takes (the caller has run shape_check):
-// Q R rows of GP uint16, then as many of int32
-int fcd_patient_trait_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t G) {
-    const int64_t R = rows_of(ctx, Nreg);
-    const size_t bytes = (size_t)(ctx->pt_Q * R) * (size_t)((G + 63) / 64) * 64 * (sizeof(uint16_t) + sizeof(int32_t));
-    if (bytes > PT_MAX_SCRATCH)
-        return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "patient traits: %lld traits x %lld rows need more than 1 GiB of scratch", ctx->pt_Q, R);
-    return fcd_count_ws_grow(ctx, bytes);
+// (the caller has run shape_check)  Q R rows of GP uint16, then as many of int32
+int fcd_patient_trait_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t, int64_t G) {
+    const int64_t R = tally_rows(ctx, Nreg, ctx->pt_with_rs);
+    return tally_ws_reserve(ctx, ctx->pt_Q * R, G, sizeof(uint16_t) + sizeof(int32_t),
+                            "patient traits: %lld traits x %lld rows need more than 1 GiB of scratch", ctx->pt_Q, R);
 }
 
 // (the caller has checked the traits against the shape: shape_check)
 int fcd_patient_trait_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
                                    uint32_t *trait_hist, int64_t *trait_sum, hipStream_t s) {
-    int rc = fcd_patient_trait_ws_reserve(ctx, Nreg, G);    // (no-op when fcd_gibbs_run has grown it)
+    int rc = fcd_patient_trait_ws_reserve(ctx, Nreg, U, G); // (no-op when fcd_gibbs_run has grown it)
     if (rc) return rc;
-    const int Q = (int)ctx->pt_Q, R = (int)rows_of(ctx, Nreg), Umax = (int)ctx->pt_umax;
+    const int Q = (int)ctx->pt_Q, R = (int)tally_rows(ctx, Nreg, ctx->pt_with_rs), Umax = (int)ctx->pt_umax;
     const int64_t GP = (int64_t)g.GW * 64;
     uint16_t *ks = (uint16_t *)ctx->count_ws;
     int32_t *As = (int32_t *)(ks + (int64_t)Q * R * GP);    // (GP is a multiple of 64: aligned)
     const int32_t *enc = (const int32_t *)ctx->pt_dev, *nq = enc + (int64_t)Q * U;
     const int32_t *rs_offsets = ctx->pt_with_rs ? (const int32_t *)ctx->rs_dev : nullptr;
     const int32_t *rs_members = ctx->pt_with_rs ? rs_offsets + ctx->rs_J + 1 : nullptr;
-    const int64_t cap = (int64_t)ctx->num_cu * 8;
-    int64_t blocks = (int64_t)R * g.GW;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(patient_trait_sums_kernel, dim3((unsigned)blocks), dim3(PT_THREADS), (size_t)Q * pt_u8((int)U) * sizeof(int32_t),
-                       s, r_bits, rs_offsets, rs_members, enc, Q, (int)Nreg, R, (int)U, g.GW, ks, As);
+    hipLaunchKernelGGL(patient_trait_sums_kernel, dim3(tally_grid(ctx, (int64_t)R * g.GW)), dim3(PT_THREADS),
+                       (size_t)Q * pt_u8((int)U) * sizeof(int32_t), s, r_bits, rs_offsets, rs_members, enc, Q, (int)Nreg, R, (int)U, g.GW,
+                       ks, As);
     FCD_LAUNCH_CHECK();
-    blocks = (int64_t)Q * R;
-    if (blocks > cap) blocks = cap;
     const size_t shmem = (size_t)(Umax + 1) * sizeof(unsigned long long) + (size_t)(Umax + 1 + PT_NB + 3) * sizeof(uint32_t);
-    hipLaunchKernelGGL(patient_trait_hist_kernel, dim3((unsigned)blocks), dim3(256), shmem, s, ks, As, nq, Q * R, R, Umax, g.GW, G,
-                       trait_hist, (long long *)trait_sum);
+    hipLaunchKernelGGL(patient_trait_hist_kernel, dim3(tally_grid(ctx, (int64_t)Q * R)), dim3(256), shmem, s, ks, As, nq, Q * R, R, Umax,
+                       g.GW, G, trait_hist, (long long *)trait_sum);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
 }
@@ -206,18 +165,17 @@ extern "C" int fcd_patient_traits_set(fcd_ctx *ctx, const int32_t *scores_host, 
                                       int with_region_sets) {
     static const char *who = "fcd_patient_traits_set";
     if (!ctx) return FCD_ERR_ARG;
-    if (ctx->sweep_acc[FCD_ACC_PATIENT_TRAIT].buf[0]) return pt_fail(ctx, FCD_ERR_ARG, who, "the patient-trait accumulator is attached");
+    if (ctx->sweep_acc[FCD_ACC_PATIENT_TRAIT].buf[0]) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "the patient-trait accumulator is attached");
     if (Q == 0 && !scores_host && !known_host) {
-        if (ctx->pt_dev) (void)hipFree(ctx->pt_dev);        // (waits for the tallies that read it)
-        ctx->pt_dev = nullptr;
+        (void)tally_table_replace(ctx, &ctx->pt_dev, nullptr, 0);
         ctx->pt_Q = ctx->pt_U = ctx->pt_umax = 0;
         ctx->pt_with_rs = 0;
         return FCD_OK;
     }
-    if (!scores_host || !known_host) return pt_fail(ctx, FCD_ERR_ARG, who, "null pointer");
-    if (Q < 1 || U < 1) return pt_fail(ctx, FCD_ERR_ARG, who, "Q=%lld U=%lld", Q, U);
-    if (Q > PT_MAX_TRAITS) return pt_fail(ctx, FCD_ERR_UNSUPPORTED, who, "Q=%lld (at most 16 traits)", Q);
-    if (U > PT_MAX_U) return pt_fail(ctx, FCD_ERR_UNSUPPORTED, who, "U=%lld (at most 512 patients)", U);
+    if (!scores_host || !known_host) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "null pointer");
+    if (Q < 1 || U < 1) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "Q=%lld U=%lld", Q, U);
+    if (Q > PT_MAX_TRAITS) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "Q=%lld (at most 16 traits)", Q);
+    if (U > PT_MAX_U) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "U=%lld (at most 512 patients)", U);
     const size_t words = (size_t)(Q * U + Q);
     int32_t *host = (int32_t *)calloc(words, sizeof(int32_t));      // enc (Q, U) | n_q (Q)
     if (!host) return (int)hipErrorOutOfMemory;
@@ -227,7 +185,7 @@ extern "C" int fcd_patient_traits_set(fcd_ctx *ctx, const int32_t *scores_host, 
         int64_t n = 0, sum = 0;
         for (int64_t u = 0; u < U; ++u) n += known_host[q * U + u] ? 1 : 0;
         if (n < 2) {
-            rc = pt_fail(ctx, FCD_ERR_ARG, who, "trait %lld is known for %lld patients (at least 2)", q, n);
+            rc = fcd_fail_who(ctx, FCD_ERR_ARG, who, "trait %lld is known for %lld patients (at least 2)", q, n);
             break;
         }
         bool distinct = false;
@@ -235,11 +193,11 @@ extern "C" int fcd_patient_traits_set(fcd_ctx *ctx, const int32_t *scores_host, 
             const int64_t a = scores_host[q * U + u];
             const bool kn = known_host[q * U + u] != 0;
             if (!kn && a != 0) {
-                rc = pt_fail(ctx, FCD_ERR_ARG, who, "trait %lld has a score where it is not known (patient %lld)", q, u);
+                rc = fcd_fail_who(ctx, FCD_ERR_ARG, who, "trait %lld has a score where it is not known (patient %lld)", q, u);
                 break;
             }
             if (a > n - 1 || a < -(n - 1)) {
-                rc = pt_fail(ctx, FCD_ERR_ARG, who, "trait %lld has a score beyond n_q - 1 = %lld", q, n - 1);
+                rc = fcd_fail_who(ctx, FCD_ERR_ARG, who, "trait %lld has a score beyond n_q - 1 = %lld", q, n - 1);
                 break;
             }
             if (kn && a != 0) distinct = true;               // (the sum is 0: one non-zero score means two distinct ones)
@@ -247,26 +205,14 @@ extern "C" int fcd_patient_traits_set(fcd_ctx *ctx, const int32_t *scores_host, 
             host[q * U + u] = (int32_t)(a * 2 + (kn ? 1 : 0));
         }
         if (rc) break;
-        if (sum != 0) rc = pt_fail(ctx, FCD_ERR_ARG, who, "the scores of trait %lld sum to %lld, not 0", q, sum);
-        else if (!distinct) rc = pt_fail(ctx, FCD_ERR_ARG, who, "the known patients of trait %lld all have one score", q);
+        if (sum != 0) rc = fcd_fail_who(ctx, FCD_ERR_ARG, who, "the scores of trait %lld sum to %lld, not 0", q, sum);
+        else if (!distinct) rc = fcd_fail_who(ctx, FCD_ERR_ARG, who, "the known patients of trait %lld all have one score", q);
         host[Q * U + q] = (int32_t)n;
         if (n > umax) umax = n;
     }
-    if (rc) {
-        free(host);
-        return rc;
-    }
-    void *dev = nullptr;
-    hipError_t e = hipMalloc(&dev, words * sizeof(int32_t));
-    if (e == hipSuccess) {
-        ctx->n_alloc += 1;
-        e = hipMemcpy(dev, host, words * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) (void)hipFree(dev);
-    }
+    if (!rc) rc = tally_table_replace(ctx, &ctx->pt_dev, host, words * sizeof(int32_t));
     free(host);
-    if (e != hipSuccess) return (int)e;
-    if (ctx->pt_dev) (void)hipFree(ctx->pt_dev);            // (waits for the tallies that read it)
-    ctx->pt_dev = dev;
+    if (rc) return rc;
     ctx->pt_Q = Q;
     ctx->pt_U = U;
     ctx->pt_umax = umax;
@@ -280,7 +226,7 @@ extern "C" int fcd_gibbs_patient_trait_tally(fcd_ctx *ctx, const uint64_t *r_bit
     fcd_geo g;
     int rc = fcd_geo_check(ctx, Nreg, U, G, 0, g);
     if (rc) return rc;
-    if (!r_bits || !trait_hist || !trait_sum) return pt_fail(ctx, FCD_ERR_ARG, who, "null pointer");
+    if (!r_bits || !trait_hist || !trait_sum) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "null pointer");
     rc = shape_check(ctx, Nreg, U, who);
     if (rc) return rc;
     return fcd_patient_trait_tally_launch(ctx, r_bits, Nreg, U, G, g, trait_hist, trait_sum, (hipStream_t)stream);

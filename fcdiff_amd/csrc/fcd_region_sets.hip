@@ -3,14 +3,14 @@
 // how many patients the set is hit).  Like the counts of fcd_count.hip -- which these generalise: the set of all regions
 // gives hist_patient, a singleton {n} gives hist_region[n] -- they depend on the joint law of the sites, which only the
 // sampler's chains carry.  The sets live on the context (fcd_region_sets_set: CSR, checked on the host, so no index a
-// kernel reads can be out of range).  Kernels, in the idiom of fcd_count.hip (no same-address global atomics):
+// kernel reads can be out of range).  Kernels, from the parts of fcd_tally.h as those of fcd_count.hip:
 //   region_set_sums_kernel    one workgroup per (chain word w, set j): thread u adds the set's rows of column u into
 //                             bit-sliced (vertical) counters, one per chain, and writes the 64 counts as uint16 to the
 //                             context's scratch; the OR of the planes is the "any" word of (j, u), and one wave with
 //                             lane = chain counts its bit over u.
 //   region_set_hist_kernel    one workgroup per histogram row (J*U rows of hist_set, J of hist_prev): bins in LDS, the row
 //                             updated once without atomics.
-#include "fcd_common.h"
+#include "fcd_tally.h"
 
 namespace {
 
@@ -19,12 +19,11 @@ constexpr int RS_PLANES = 10;           // bit planes of the vertical counters: 
 constexpr int RS_MAX_U = RS_THREADS;
 constexpr int RS_MAX_SIZE = (1 << RS_PLANES) - 1;
 constexpr int RS_MAX_SETS = 1024;
-constexpr size_t RS_MAX_SCRATCH = (size_t)1 << 30;
 
 // Phase 1.  Grid-stride over the pairs (j, w), w fastest.  blockDim = U rounded up to whole waves.
 //   thread u < U   walks the members of S_j (the member index is uniform over the workgroup; the loads of r_bits[w][n][u] are
-//                  coalesced over u), carry-save adds into pl[] (bit b of chain c's count in bit c of pl[b]); the 64 counts go
-//                  to sums row j*U + u, four per 8-byte store; the OR of the planes to LDS.
+//                  coalesced over u), carry-save adds into its tally_planes; the 64 counts go to sums row j*U + u, the OR
+//                  of the planes to LDS.
 //   wave 0         lane c counts chain c's bit of the "any" words over u (broadcast LDS reads): sums row J*U + j.
 // sums: (J*U + J) rows of GP = GW * 64 uint16, chain-major within a row; chains beyond G hold whatever their bits give.
 __global__ __launch_bounds__(RS_THREADS) void region_set_sums_kernel(const uint64_t *__restrict__ r_bits,
@@ -40,35 +39,12 @@ __global__ __launch_bounds__(RS_THREADS) void region_set_sums_kernel(const uint6
         const int i0 = offsets[j], i1 = offsets[j + 1];
         if (tid < U) {
             const uint64_t *col = r_bits + (int64_t)w * Nreg * U + tid;
-            uint64_t pl[RS_PLANES];
-#pragma unroll
-            for (int b = 0; b < RS_PLANES; ++b) pl[b] = 0;
+            tally_planes<RS_PLANES> pl;
+            pl.clear();
 #pragma unroll 4
-            for (int i = i0; i < i1; ++i) {
-                uint64_t carry = col[(int64_t)members[i] * U];
-#pragma unroll
-                for (int b = 0; b < RS_PLANES; ++b) {
-                    const uint64_t t = pl[b] & carry;
-                    pl[b] ^= carry;
-                    carry = t;
-                }
-            }
-            uint64_t any = 0;
-#pragma unroll
-            for (int b = 0; b < RS_PLANES; ++b) any |= pl[b];
-            anyw[tid] = any;
-            uint64_t *dst = reinterpret_cast<uint64_t *>(sums + ((int64_t)j * U + tid) * GP + (int64_t)w * 64);
-            for (int c0 = 0; c0 < 64; c0 += 4) {
-                uint64_t packed = 0;
-#pragma unroll
-                for (int cc = 0; cc < 4; ++cc) {
-                    uint64_t k = 0;
-#pragma unroll
-                    for (int b = 0; b < RS_PLANES; ++b) k |= ((pl[b] >> (c0 + cc)) & 1ull) << b;
-                    packed |= k << (16 * cc);
-                }
-                dst[c0 / 4] = packed;
-            }
+            for (int i = i0; i < i1; ++i) pl.add(col[(int64_t)members[i] * U]);
+            anyw[tid] = pl.any();
+            pl.store16(sums + ((int64_t)j * U + tid) * GP + (int64_t)w * 64);
         }
         __syncthreads();
         if (tid < 64) {
@@ -83,31 +59,18 @@ __global__ __launch_bounds__(RS_THREADS) void region_set_sums_kernel(const uint6
 
 // Phase 2.  One workgroup per histogram row: rows 0 .. J*U-1 are (set j, patient u) with bins 0 .. |S_j| of hist_set
 // (J, U, S_max+1) -- the bins beyond the set's size are never touched --, rows J*U .. J*U+J-1 set j with bins 0 .. U of
-// hist_prev (J, U+1).  The row's G counts are binned with LDS atomics, then added to the row in place: the row belongs to
-// this workgroup alone.
+// hist_prev (J, U+1), binned by tally_bin_row.
 __global__ __launch_bounds__(256) void region_set_hist_kernel(const uint16_t *__restrict__ sums,
                                                               const int32_t *__restrict__ offsets, int J, int U, int S_max, int GW,
                                                               int64_t G, uint32_t *__restrict__ hist_set,
                                                               uint32_t *__restrict__ hist_prev) {
     extern __shared__ uint32_t bins[];           // [L + 1]
-    const int row = blockIdx.x, tid = threadIdx.x;
+    const int row = blockIdx.x;
     const bool per_patient = row < J * U;
     const int j = per_patient ? row / U : row - J * U;
     const int L = per_patient ? offsets[j + 1] - offsets[j] : U;
     uint32_t *out = per_patient ? hist_set + (int64_t)row * (S_max + 1) : hist_prev + (int64_t)j * (U + 1);
-    const uint16_t *src = sums + (int64_t)row * GW * 64;
-    for (int k = tid; k <= L; k += blockDim.x) bins[k] = 0;
-    __syncthreads();
-    for (int64_t g = tid; g < G; g += blockDim.x) atomicAdd(&bins[min((int)src[g], L)], 1u);
-    __syncthreads();
-    for (int k = tid; k <= L; k += blockDim.x) {
-        const uint32_t c = bins[k];
-        if (c) out[k] += c;
-    }
-}
-
-size_t scratch_bytes(const fcd_ctx *ctx, int64_t U, int64_t G) {
-    return (size_t)(ctx->rs_J * U + ctx->rs_J) * (size_t)((G + 63) / 64) * 64 * sizeof(uint16_t);
+    tally_bin_row(sums + (int64_t)row * GW * 64, G, L, bins, out);
 }
 
 // the refusals the tally and the accumulator share: no sets, a member outside the regions, more patients than threads
@@ -120,28 +83,22 @@ int shape_check(fcd_ctx *ctx, int64_t Nreg, int64_t U, const char *msg_none, con
 
 }  // namespace
 
-// grows the scratch of the count tallies (they run one after another on one stream) as fcd_count_ws_reserve does
-int fcd_region_set_ws_reserve(fcd_ctx *ctx, int64_t U, int64_t G) {
-    const size_t bytes = scratch_bytes(ctx, U, G);
-    if (bytes > RS_MAX_SCRATCH)
-        return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "region sets: %lld sets x %lld patients need more than 1 GiB of scratch", ctx->rs_J, U);
-    return fcd_count_ws_grow(ctx, bytes);
+int fcd_region_set_ws_reserve(fcd_ctx *ctx, int64_t, int64_t U, int64_t G) {
+    return tally_ws_reserve(ctx, ctx->rs_J * U + ctx->rs_J, G, sizeof(uint16_t),
+                            "region sets: %lld sets x %lld patients need more than 1 GiB of scratch", ctx->rs_J, U);
 }
 
 // (the caller has checked the sets against the shape: shape_check)
 int fcd_region_set_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
                                 uint32_t *hist_set, uint32_t *hist_prev, hipStream_t s) {
-    int rc = fcd_region_set_ws_reserve(ctx, U, G);          // (no-op when fcd_gibbs_run has grown it)
+    int rc = fcd_region_set_ws_reserve(ctx, Nreg, U, G);    // (no-op when fcd_gibbs_run has grown it)
     if (rc) return rc;
     uint16_t *sums = (uint16_t *)ctx->count_ws;
     const int32_t *offsets = (const int32_t *)ctx->rs_dev, *members = offsets + ctx->rs_J + 1;
     const int J = (int)ctx->rs_J, S_max = (int)ctx->rs_smax;
-    int64_t blocks = (int64_t)J * g.GW;
-    const int64_t cap = (int64_t)ctx->num_cu * 8;
-    if (blocks > cap) blocks = cap;
     const int threads = (int)((U + 63) / 64) * 64;
-    hipLaunchKernelGGL(region_set_sums_kernel, dim3((unsigned)blocks), dim3(threads), 0, s, r_bits, offsets, members, J, (int)Nreg,
-                       (int)U, g.GW, sums);
+    hipLaunchKernelGGL(region_set_sums_kernel, dim3(tally_grid(ctx, (int64_t)J * g.GW)), dim3(threads), 0, s, r_bits, offsets, members,
+                       J, (int)Nreg, (int)U, g.GW, sums);
     FCD_LAUNCH_CHECK();
     const int64_t L = S_max > U ? S_max : U;
     hipLaunchKernelGGL(region_set_hist_kernel, dim3((unsigned)(J * U + J)), dim3(256), (size_t)(L + 1) * sizeof(uint32_t), s, sums,
@@ -164,37 +121,20 @@ extern "C" int fcd_region_sets_set(fcd_ctx *ctx, const int32_t *offsets_host, co
         if (!offsets_host || !members_host) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_region_sets_set: null pointer");
         if (J < 1) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_region_sets_set: J=%lld", J);
         if (J > RS_MAX_SETS) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_region_sets_set: J=%lld (at most 1024 sets)", J);
-        if (offsets_host[0] != 0) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_region_sets_set: offsets[0]=%lld", offsets_host[0]);
-        for (int64_t j = 0; j < J; ++j) {
-            const int64_t i0 = offsets_host[j], size = (int64_t)offsets_host[j + 1] - i0;
-            if (size < 1) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_region_sets_set: set %lld is empty", j);
-            if (size > RS_MAX_SIZE)
-                return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_region_sets_set: set %lld has %lld members (at most 1023)", j, size);
-            for (int64_t i = i0; i < i0 + size; ++i) {
-                const int64_t n = members_host[i];
-                if (n < 0) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_region_sets_set: set %lld has the negative member %lld", j, n);
-                if (i > i0 && n <= members_host[i - 1])
-                    return fcd_fail(ctx, FCD_ERR_ARG, "fcd_region_sets_set: the members of set %lld do not increase at %lld", j, n);
-                if (n > max_member) max_member = n;
-            }
-            if (size > smax) smax = size;
+        const auto fail = [ctx](int code, const char *fmt, long long a, long long b) {
+            return fcd_fail_who(ctx, code, "fcd_region_sets_set", fmt, a, b);
+        };
+        int rc = tally_csr_check(fail, "set", offsets_host, members_host, J, &smax, &max_member);
+        if (rc) return rc;
+        for (int64_t j = 0; j < J && smax > RS_MAX_SIZE; ++j) {
+            const int64_t size = offsets_host[j + 1] - offsets_host[j];
+            if (size > RS_MAX_SIZE) return fail(FCD_ERR_UNSUPPORTED, "set %lld has %lld members (at most 1023)", j, size);
         }
         total = offsets_host[J];
     }
-    void *dev = nullptr;
-    if (!clear) {
-        FCD_HIP_TRY(hipMalloc(&dev, (size_t)(J + 1 + total) * sizeof(int32_t)));
-        ctx->n_alloc += 1;
-        hipError_t e = hipMemcpy(dev, offsets_host, (size_t)(J + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = hipMemcpy((int32_t *)dev + J + 1, members_host, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(dev);
-            return (int)e;
-        }
-    }
-    if (ctx->rs_dev) (void)hipFree(ctx->rs_dev);            // (waits for the tallies that read it)
-    ctx->rs_dev = dev;
+    int rc = tally_table_replace(ctx, &ctx->rs_dev, offsets_host, clear ? 0 : (size_t)(J + 1) * sizeof(int32_t), members_host,
+                                 (size_t)total * sizeof(int32_t));
+    if (rc) return rc;
     ctx->rs_J = clear ? 0 : J;
     ctx->rs_smax = smax;
     ctx->rs_max_member = max_member;
