@@ -1,0 +1,247 @@
+"""
+Classical baselines to hold the model-based results against.  Not part of the reference; oracle = tests/baseline_ref.py.
+
+normative()   per patient: "which regions of this patient are abnormal?" -- the z-score of every patient connection against
+              the controls, summarised per region, with a null made by treating each control in turn as the patient
+              (leave-one-out).  What UnsharedRegionFit answers with a posterior.
+group_test()  per population: "which regions are abnormal in this disease?" -- Student's two-sample t per connection, the
+              sum of t^2 per region, family-wise error control by the permutation law of the maximum statistic.  What
+              SharedRegionFit answers with a posterior.
+
+b (C, H) controls and bt (C, U) patients, NumPy arrays or torch tensors, float64, connections in util.c_to_nm order;
+E(n) = the N - 1 connections that touch region n.  Both run on the device (fcd_baseline_normative,
+fcd_baseline_group_perm of include/fcdiff_hip.h) and have no CPU fallback; the p-values are made on the host from what the
+device returns, with the conventions >= and (1 + count) / (1 + number of valid null values).
+"""
+import numpy as np
+
+from . import _lib
+
+MAX_CONTROLS = 1024       # normative(): a control row lives in one wave's LDS
+MAX_SUBJECTS = 1024       # group_test(): the labels of a permutation are 8 words per lane
+_U_CHUNK = 1 << 16        # patients per call of normative()
+
+
+def _shape(x):
+    return tuple(int(v) for v in (x.shape if hasattr(x, "shape") else np.shape(x)))
+
+
+def _has_nan(x):
+    if hasattr(x, "detach"):
+        import torch
+        return bool(torch.isnan(x).any().item())
+    return bool(np.isnan(np.asarray(x, dtype=np.float64)).any())
+
+
+def _n_regions(C):
+    N = int(round((np.sqrt(8.0 * C + 1.0) - 1.0) / 2.0)) + 1
+    if C < 1 or N * (N - 1) // 2 != C:
+        raise ValueError("%d connections: not a triangular number N (N - 1) / 2" % C)
+    return N
+
+
+def _check_pair(b, bt, who):
+    """Shapes of (b, bt) -> (C, N, H, U); sessions and a non-triangular C are refused."""
+    (sb, st) = (_shape(b), _shape(bt))
+    if len(st) == 3:
+        raise NotImplementedError("%s: bt of shape (C, U, K): sessions are not provided here" % who)
+    if len(sb) != 2 or len(st) != 2:
+        raise ValueError("%s: b must have shape (C, H) and bt (C, U)" % who)
+    if sb[0] != st[0]:
+        raise ValueError("%s: b has %d connections, bt %d" % (who, sb[0], st[0]))
+    if sb[1] < 1 or st[1] < 1:
+        raise ValueError("%s: at least one control and one patient" % who)
+    return sb[0], _n_regions(sb[0]), sb[1], st[1]
+
+
+def _device_f64(x, ctx):
+    import torch
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=ctx.device)
+    return t.to(device=ctx.device, dtype=torch.float64).contiguous()
+
+
+def _count_ge(null, values):
+    """#{valid null >= value} per value, and the number of valid (not NaN) null values."""
+    srt = np.sort(null[~np.isnan(null)])
+    return srt.shape[0] - np.searchsorted(srt, values, side="left"), srt.shape[0]
+
+
+def _p_against(null, values):
+    """(1 + #{valid null >= value}) / (1 + #valid null), NaN where the value is NaN.  null (M,) against values of any shape."""
+    (ge, n_valid) = _count_ge(null, values)
+    return np.where(np.isnan(values), np.nan, (1.0 + ge) / (1.0 + n_valid))
+
+
+def normative_pvalues(msq, msq0):
+    """
+    The host half of normative(): (max0, p_region, p_fwe) from msq (N, U) and the leave-one-out msq0 (N, H).
+    max0[h] = max over n of msq0[n,h], ignoring NaN (NaN if a control has no defined region).
+    """
+    with np.errstate(invalid="ignore"):
+        max0 = np.where(np.isnan(msq0).all(axis=0), np.nan, np.fmax.reduce(msq0, axis=0))
+    p_region = np.stack([_p_against(msq0[n], msq[n]) for n in range(msq.shape[0])])
+    p_fwe = _p_against(max0, msq)
+    return max0, p_region, p_fwe
+
+
+def normative(b, bt, *, missing_data=False, z_threshold=3.0, return_z=False, ctx=None, as_numpy=True):
+    """
+    Normative z-scores of the patients against the controls, per region.  b (C, H), bt (C, U).
+
+    Per connection c over the controls observed there: n_c, mean m_c, s_c^2 = sum (x - m_c)^2 / (n_c - 1).
+        z[c,u]  = (bt[c,u] - m_c) / (s_c sqrt(1 + 1/n_c))
+        z0[c,h] = (b[c,h] - m_-h) / (s_-h sqrt(1 + 1/(n_c - 1)))     mean and deviation of the OTHER observed controls,
+                                                                    their sums taken directly, never by downdating
+    A score is NaN where n_c < 3, where the deviation is not > 0, or where the value itself is unobserved.
+    Per region n and subject: n_edges = defined scores over E(n), msq = mean of z^2 over them (NaN if none), n_over = those
+    with |z| > z_threshold.  p_region[n,u] is taken against the controls' msq0[n,:], p_fwe[n,u] against max0[h] = max_n
+    msq0[n,h].
+
+    The leave-one-out null has one degree of freedom fewer than the patient score (n_c - 1 controls stand behind a z0, n_c
+    behind a z): its tails are a little heavier than the patients' own null, so the p-values err on the conservative side.
+
+    Returns a dict: msq, n_edges, n_over (N, U); msq0, n_edges0, n_over0 (N, H); max0 (H,); p_region, p_fwe (N, U);
+    n_controls (C,); with return_z also z (C, U) and z0 (C, H).  NumPy arrays, or device tensors with as_numpy=False.
+    missing_data=False: a NaN anywhere is a ValueError; with it a NaN is unobserved.  At most 1024 controls
+    (NotImplementedError above); any number of patients, walked in chunks.  Sessions (C, U, K) are not provided.
+    """
+    import torch
+    (C, N, H, U) = _check_pair(b, bt, "normative")
+    if H > MAX_CONTROLS:
+        raise NotImplementedError("normative: %d controls, at most %d" % (H, MAX_CONTROLS))
+    if not missing_data and (_has_nan(b) or _has_nan(bt)):
+        raise ValueError("normative: NaN in b or bt; pass missing_data=True to treat NaN as unobserved")
+    ctx = ctx if ctx is not None else _lib.Context()
+    (bd, btd) = (_device_f64(b, ctx), _device_f64(bt, ctx))
+    dev = ctx.device
+
+    def f64(*sh):
+        return torch.empty(sh, dtype=torch.float64, device=dev)
+
+    def i32(*sh):
+        return torch.empty(sh, dtype=torch.int32, device=dev)
+
+    (msq0, ne0, no0, n_controls) = (f64(N, H), i32(N, H), i32(N, H), i32(C))
+    (msq, ne, no) = (f64(N, U), i32(N, U), i32(N, U))
+    z0 = f64(C, H) if return_z else None
+    z = f64(C, U) if return_z else None
+    for u0 in range(0, U, _U_CHUNK):
+        nu = min(_U_CHUNK, U - u0)
+        whole = nu == U
+        bt_c = btd if whole else btd[:, u0:u0 + nu].contiguous()
+        (m_c, e_c, o_c) = (msq, ne, no) if whole else (f64(N, nu), i32(N, nu), i32(N, nu))
+        z_c = z if (whole or z is None) else f64(C, nu)
+        ctx.call("fcd_baseline_normative", _lib.dptr(bd), _lib.dptr(bt_c), C, H, nu, float(z_threshold), _lib.dptr(msq0),
+                 _lib.dptr(ne0), _lib.dptr(no0), _lib.dptr(m_c), _lib.dptr(e_c), _lib.dptr(o_c), _lib.dptr(n_controls),
+                 _lib.dptr(z0), _lib.dptr(z_c), _lib.stream_ptr())
+        if not whole:
+            msq[:, u0:u0 + nu] = m_c
+            ne[:, u0:u0 + nu] = e_c
+            no[:, u0:u0 + nu] = o_c
+            if z is not None:
+                z[:, u0:u0 + nu] = z_c
+    out = {"msq": msq, "n_edges": ne.long(), "n_over": no.long(), "msq0": msq0, "n_edges0": ne0.long(), "n_over0": no0.long(),
+           "n_controls": n_controls.long()}
+    if return_z:
+        out["z"] = z
+        out["z0"] = z0
+    (max0, p_region, p_fwe) = normative_pvalues(msq.cpu().numpy(), msq0.cpu().numpy())
+    if as_numpy:
+        out = dict((k, v.cpu().numpy()) for (k, v) in out.items())
+        out.update(max0=max0, p_region=p_region, p_fwe=p_fwe)
+    else:
+        out.update(max0=torch.as_tensor(max0, device=dev), p_region=torch.as_tensor(p_region, device=dev),
+                   p_fwe=torch.as_tensor(p_fwe, device=dev))
+    return out
+
+
+def draw_labels(n_perm, H, U, seed=0):
+    """(n_perm, H + U) uint8 rows with exactly U ones: numpy.random.default_rng(seed), rng.permutation(H + U)[:U] per row."""
+    rng = np.random.default_rng(seed)
+    S = H + U
+    labels = np.zeros((int(n_perm), S), dtype=np.uint8)
+    for p in range(int(n_perm)):
+        labels[p, rng.permutation(S)[:U]] = 1
+    return labels
+
+
+def _check_labels(labels, S, U):
+    lab = labels.detach().cpu().numpy() if hasattr(labels, "detach") else np.asarray(labels)
+    if lab.ndim != 2 or lab.shape[1] != S or lab.shape[0] < 1:
+        raise ValueError("group_test: labels must have shape (P, %d) with P >= 1, not %s" % (S, lab.shape))
+    if not np.isin(lab, (0, 1)).all():
+        raise ValueError("group_test: labels must hold 0 and 1 only")
+    lab = np.ascontiguousarray(lab.astype(np.uint8))
+    if not (lab.sum(axis=1, dtype=np.int64) == U).all():
+        raise ValueError("group_test: every row of labels must hold exactly U = %d ones" % U)
+    return lab
+
+
+def group_test(b, bt, n_perm=10000, *, seed=0, labels=None, ctx=None, as_numpy=True):
+    """
+    Mass-univariate two-sample test of patients against controls with permutation inference.  b (C, H), bt (C, U), complete.
+
+    X = [b | bt] (C, S), S = H + U, rows centred on their mean over all subjects, Q_c = sum x^2.  For a labelling l in
+    {0,1}^S with exactly U ones: A = sum l_s x_s, SS_w = Q_c - A^2 S/(U H), Student's t with pooled variance
+    t = A (S/(U H)) / sqrt(SS_w/(S - 2) * S/(U H)), and per region R[n] = sum over E(n) of t^2.  The observed labelling has
+    its ones on the last U subjects.  labels: (P, S) of 0/1 with U ones per row; not given, n_perm rows are drawn on the
+    host (draw_labels(n_perm, H, U, seed)).  A row equal to the observed labelling counts, and gives the observed statistics
+    bit for bit; results repeat bit for bit from call to call.
+
+    Returns a dict: t (C,), region (N,) observed; null_max_t (P,) = max_c |t|, null_max_region (P,) = max_n R;
+    count_t (C,) int64 = #{p: |t_pc| >= |t_c|}, count_region (N,) int64 = #{p: R_pn >= R_n}; p_t, p_region =
+    (1 + count) / (1 + P); p_fwe_t, p_fwe_region = the same against the maxima; labels (P, S) uint8 as used.
+    A NaN is a ValueError (missing data is not provided here); more than 1024 subjects a NotImplementedError.
+    Not provided: sessions, noise variances, Welch's t, cluster or network-based statistics.
+    """
+    import torch
+    (C, N, H, U) = _check_pair(b, bt, "group_test")
+    S = H + U
+    if S > MAX_SUBJECTS:
+        raise NotImplementedError("group_test: %d subjects, at most %d" % (S, MAX_SUBJECTS))
+    if S < 3:
+        raise ValueError("group_test: %d subjects, a pooled variance needs 3" % S)
+    if _has_nan(b) or _has_nan(bt):
+        raise ValueError("group_test: NaN in b or bt; the data must be complete (missing data is not provided here)")
+    if labels is None:
+        if int(n_perm) < 1:
+            raise ValueError("group_test: n_perm must be >= 1")
+        lab = draw_labels(n_perm, H, U, seed)
+    else:
+        lab = _check_labels(labels, S, U)
+    P = int(lab.shape[0])
+    ctx = ctx if ctx is not None else _lib.Context()
+    (bd, btd) = (_device_f64(b, ctx), _device_f64(bt, ctx))
+    dev = ctx.device
+    labd = torch.as_tensor(lab, device=dev)
+    t = torch.empty((C,), dtype=torch.float64, device=dev)
+    region = torch.empty((N,), dtype=torch.float64, device=dev)
+    null_max_t = torch.empty((P,), dtype=torch.float64, device=dev)
+    null_max_region = torch.empty((P,), dtype=torch.float64, device=dev)
+    count_t = torch.empty((C,), dtype=torch.int64, device=dev)
+    count_region = torch.empty((N,), dtype=torch.int64, device=dev)
+    ctx.call("fcd_baseline_group_perm", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(labd), P, _lib.dptr(t),
+             _lib.dptr(region), _lib.dptr(null_max_t), _lib.dptr(null_max_region), _lib.dptr(count_t), _lib.dptr(count_region),
+             _lib.stream_ptr())
+    out = {"t": t, "region": region, "null_max_t": null_max_t, "null_max_region": null_max_region, "count_t": count_t,
+           "count_region": count_region}
+    host = dict((k, v.cpu().numpy()) for (k, v) in out.items())
+    pv = group_pvalues(host["t"], host["region"], host["null_max_t"], host["null_max_region"], host["count_t"],
+                       host["count_region"])
+    if as_numpy:
+        out = host
+        out.update(pv)
+        out["labels"] = lab
+    else:
+        out.update(dict((k, torch.as_tensor(v, device=dev)) for (k, v) in pv.items()))
+        out["labels"] = labd
+    return out
+
+
+def group_pvalues(t, region, null_max_t, null_max_region, count_t, count_region):
+    """The host half of group_test(): p_t, p_region, p_fwe_t, p_fwe_region, each (1 + count) / (1 + P)."""
+    P = null_max_t.shape[0]
+    return {"p_t": (1.0 + count_t) / (1.0 + P),
+            "p_region": (1.0 + count_region) / (1.0 + P),
+            "p_fwe_t": (1.0 + _count_ge(null_max_t, np.abs(t))[0]) / (1.0 + P),
+            "p_fwe_region": (1.0 + _count_ge(null_max_region, region)[0]) / (1.0 + P)}

@@ -1,0 +1,532 @@
+// K_base: the two classical baselines (fcd_baseline_normative, fcd_baseline_group_perm).  Not in the reference; oracle =
+// tests/baseline_ref.py.  E(n) = the N - 1 connections that touch region n, walked as k = 0 .. N - 2 with the other endpoint
+// m = k (k < n) or k + 1: rows tri(n) + k are contiguous for k < n, rows tri(m) + n are strided for k >= n.  A connection
+// is met by both its endpoints; what is written once per connection (z, z0, n_controls, t, count_t) is written by the
+// endpoint n > m.  Caller's stream, fixed reduction orders, no floating-point atomics: two calls agree bit for bit.
+//
+// Normative scores
+//   baseline_normative_kernel   grid (N, chunks of 64 subjects), 4 waves.  A wave takes connections k = wave, wave + 4, ...:
+//                      the control row goes into the wave's LDS row once; count, mean and sum of squares about the mean in two
+//                      passes, lanes over the controls, butterfly sums.  Then lane = subject (controls first, then patients):
+//                      a patient lane scores its bt value, a control lane takes the deleted sums of the other controls
+//                      straight from the LDS row (every lane reads the same address: a broadcast) -- 2 H reads, no downdate.
+//                      z^2, the count of defined scores and of |z| > threshold stay in registers over the wave's
+//                      connections; the four waves meet in LDS and wave 0 adds them in wave order.
+//
+// Permutation group test (statistics in their t^2 form: one division per value, the root only where a t leaves the device)
+//   group_centre_kernel   one wave per row of X = [b | bt]: mean over the S subjects, x - mean, Q = sum (x - mean)^2, written
+//                      K-step major: XT[j][c][0..3] = subjects 4 j .. 4 j + 3 of row c, zeros behind S.
+//   group_pack_kernel  the labels of 16 permutations x 128 subjects as one uint32 per lane: bit j of lane l = label of
+//                      permutation l & 15 at subject 4 (32 w + j) + (l >> 4) -- what that lane feeds the MFMA as A at
+//                      K-step 32 w + j.  labels == nullptr: the observed labelling (ones on the last U subjects).
+//   gp_tile_mma        what the two kernels below share: a tile of 16 permutations x 16 connections over all K-steps in
+//                      ascending order.  Per K-step ONE 8-byte load per lane (lane l: row of connection l & 15, subject
+//                      4 j + (l >> 4) -- 512 contiguous bytes where the 16 rows are contiguous, 32-byte pieces where they are
+//                      strided: the same address formula, the lane's row offset is all that differs), the label bit
+//                      expanded to 0.0 / 1.0 in two VALU instructions, one v_mfma_f64_16x16x4_f64 per group.  Then
+//                      gp_t2: g = A^2 S/(U H), t^2 = g (S - 2) / (Q - g).
+//   group_observed_kernel   the observed labelling as one packed row: a wave per 16 consecutive connections, each connection
+//                      once; writes t and t^2.  group_observed_region_kernel adds t^2 over E(n) exactly as the permutation
+//                      kernel adds a row's (lane = column of the tile, tiles in order, then the butterfly).  A row of
+//                      labels equal to the observed labelling therefore gives the observed statistics bit for bit: the
+//                      same operations on the same numbers in the same order.  (The permutation kernel itself at P = 1
+//                      did the same in 112 us at 200 regions -- 200 single waves, each 13 tiles of dependent loads long.)
+//   baseline_group_kernel   grid (N, blocks of 128 permutations), 4 waves x 2 groups of 16 permutations.  A wave reads its
+//                      label words once into registers (at most 2 x 8), then walks E(n) in tiles of 16 connections.
+//                      Epilogue per tile: per lane a running sum and max of t^2 over the tiles (tile order), folded over
+//                      the 16 lanes of a permutation by a fixed butterfly after the last tile; t^2 >= observed t^2 counted
+//                      per connection (integer atomics).  Writes the (n, p) partials.
+//   group_fold_kernel  workgroup n: the exceedance count of region n, threads over the permutations; the workgroups behind
+//                      them: thread = permutation, max over n of both partials.  No atomics.
+#include "fcd_common.h"
+
+namespace {
+
+typedef double double4_t __attribute__((ext_vector_type(4)));
+
+constexpr int BN_WAVES = 4;
+constexpr int BN_HMAX = 1024;            // controls of the normative kernel: one LDS row per wave
+constexpr int GP_WAVES = 4, GP_G = 2;    // waves per workgroup, groups of 16 permutations per wave
+constexpr int GP_PB = GP_WAVES * GP_G * 16;
+constexpr int GP_SMAX = 1024;            // subjects of the group test: 8 label words of 32 K-steps per lane and group
+constexpr int GP_NW = GP_SMAX / 128;
+
+// Orders a wave's LDS traffic: what its lanes wrote before is what they read after.
+__device__ __forceinline__ void bl_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ int bl_wave_sum_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// connection k of E(n), 0 <= k < N - 1: the other endpoint and the row
+__device__ __forceinline__ int64_t bl_edge(int n, int k, int &m) {
+    m = k < n ? k : k + 1;
+    return n > m ? fcd_tri(n) + m : fcd_tri(m) + n;
+}
+
+struct norm_args {
+    const double *b, *bt;
+    int N, H, U;
+    double thr;
+    double *msq0, *msq;
+    int32_t *ne0, *ne, *no0, *no, *n_controls;
+    double *z0, *z;      // nullable
+};
+
+__global__ __launch_bounds__(64 * BN_WAVES) void baseline_normative_kernel(norm_args a) {
+    __shared__ double row[BN_WAVES][BN_HMAX];
+    __shared__ double red_sq[BN_WAVES][64];
+    __shared__ int red_cnt[BN_WAVES][64], red_over[BN_WAVES][64];
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n = blockIdx.x, N = a.N, H = a.H, U = a.U;
+    const int64_t j = (int64_t)blockIdx.y * 64 + lane;        // subject: controls, then patients
+    const bool is_ctl = j < H, live = j < (int64_t)H + U;
+    const int64_t u = j - H;
+    const double nan = __builtin_nan("");
+    double *rw = row[wv];
+    double sq = 0.0;
+    int cnt = 0, over = 0;
+    for (int k = wv; k < N - 1; k += BN_WAVES) {
+        int m;
+        const int64_t c = bl_edge(n, k, m);
+        const double *__restrict__ br = a.b + c * H;
+        int nobs = 0;
+        double s = 0.0;
+        for (int h = lane; h < H; h += 64) {
+            const double v = br[h];
+            rw[h] = v;
+            if (v == v) {
+                ++nobs;
+                s += v;
+            }
+        }
+        nobs = bl_wave_sum_int(nobs);
+        s = fcd_wave_sum(s);
+        bl_wave_sync();
+        const double mean = s / (double)nobs;
+        double ss = 0.0;
+        for (int h = lane; h < H; h += 64) {
+            const double v = rw[h];
+            if (v == v) {
+                const double d = v - mean;
+                ss += d * d;
+            }
+        }
+        ss = fcd_wave_sum(ss);                               // (all lanes: before the subjects part ways)
+        double zv = nan;
+        if (nobs >= 3) {                                     // (wave-uniform)
+            if (is_ctl) {
+                const int hj = (int)j;
+                const double x = rw[hj];
+                if (x == x) {
+                    // the other nobs - 1 observed controls: their sums as they stand, nothing taken off a full sum
+                    double s1 = 0.0;
+                    for (int q = 0; q < H; ++q) {
+                        const double v = rw[q];
+                        if (q != hj && v == v) s1 += v;
+                    }
+                    const double m1 = s1 / (double)(nobs - 1);
+                    double ss1 = 0.0;
+                    for (int q = 0; q < H; ++q) {
+                        const double v = rw[q];
+                        if (q != hj && v == v) {
+                            const double d = v - m1;
+                            ss1 += d * d;
+                        }
+                    }
+                    const double sd1 = sqrt(ss1 / (double)(nobs - 2));
+                    if (sd1 > 0.0) zv = (x - m1) / (sd1 * sqrt(1.0 + 1.0 / (double)(nobs - 1)));
+                }
+            } else if (live) {
+                const double x = a.bt[c * U + u];
+                const double sd = sqrt(ss / (double)(nobs - 1));
+                if (x == x && sd > 0.0) zv = (x - mean) / (sd * sqrt(1.0 + 1.0 / (double)nobs));
+            }
+        }
+        if (zv == zv) {
+            sq += zv * zv;
+            ++cnt;
+            over += fabs(zv) > a.thr ? 1 : 0;
+        }
+        if (k < n) {                                         // the endpoint n > m writes what exists once per connection
+            if (is_ctl) {
+                if (a.z0) a.z0[c * H + j] = zv;
+            } else if (live) {
+                if (a.z) a.z[c * U + u] = zv;
+            }
+            if (blockIdx.y == 0 && lane == 0) a.n_controls[c] = nobs;
+        }
+        bl_wave_sync();                                      // the row is overwritten by the next connection
+    }
+    red_sq[wv][lane] = sq;
+    red_cnt[wv][lane] = cnt;
+    red_over[wv][lane] = over;
+    __syncthreads();
+    if (wv != 0 || !live) return;
+    double tsq = 0.0;
+    int tc = 0, to = 0;
+#pragma unroll
+    for (int w = 0; w < BN_WAVES; ++w) {
+        tsq += red_sq[w][lane];
+        tc += red_cnt[w][lane];
+        to += red_over[w][lane];
+    }
+    const double msq = tc > 0 ? tsq / (double)tc : nan;
+    if (is_ctl) {
+        a.msq0[(int64_t)n * H + j] = msq;
+        a.ne0[(int64_t)n * H + j] = tc;
+        a.no0[(int64_t)n * H + j] = to;
+    } else {
+        a.msq[(int64_t)n * U + u] = msq;
+        a.ne[(int64_t)n * U + u] = tc;
+        a.no[(int64_t)n * U + u] = to;
+    }
+}
+
+// ---- group test ----------------------------------------------------------------------------------------------------------
+
+// workspace of one call: XT (KS, C, 4) | Q (C) | t2obs (C) | Rpart (N, P) | Mpart (N, P) | label words (PG, nw, 64) uint32
+struct gp_ws {
+    double *XT, *Q, *t2obs, *Rpart, *Mpart;
+    uint32_t *LW;
+};
+__host__ static inline size_t gp_ws_bytes(int64_t C, int64_t N, int64_t P, int KS, int nw) {
+    const int64_t PG = (P + 15) / 16;
+    return (size_t)((int64_t)KS * C * 4 + 2 * C + 2 * N * P) * sizeof(double) + (size_t)(PG * nw * 64) * sizeof(uint32_t);
+}
+__host__ static inline gp_ws gp_ws_at(void *ws, int64_t C, int64_t N, int64_t P, int KS) {
+    gp_ws o;
+    o.XT = (double *)ws;
+    o.Q = o.XT + (int64_t)KS * C * 4;
+    o.t2obs = o.Q + C;
+    o.Rpart = o.t2obs + C;
+    o.Mpart = o.Rpart + N * P;
+    o.LW = (uint32_t *)(o.Mpart + N * P);
+    return o;
+}
+
+constexpr int GC_WAVES = 4;
+__global__ __launch_bounds__(64 * GC_WAVES) void group_centre_kernel(const double *__restrict__ b, const double *__restrict__ bt,
+                                                                     int64_t C, int H, int U, int KS, double *__restrict__ XT,
+                                                                     double *__restrict__ Q) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t c = (int64_t)blockIdx.x * GC_WAVES + wv;
+    if (c >= C) return;
+    const int S = H + U;
+    const double *__restrict__ br = b + c * H, *__restrict__ tr = bt + c * U;
+    double s = 0.0;
+    for (int i = lane; i < S; i += 64) s += i < H ? br[i] : tr[i - H];
+    const double mean = fcd_wave_sum(s) / (double)S;
+    double q = 0.0;
+    for (int i = lane; i < 4 * KS; i += 64) {
+        double xc = 0.0;
+        if (i < S) xc = (i < H ? br[i] : tr[i - H]) - mean;
+        q += xc * xc;
+        XT[((int64_t)(i >> 2) * C + c) * 4 + (i & 3)] = xc;
+    }
+    q = fcd_wave_sum(q);
+    if (lane == 0) Q[c] = q;
+}
+
+__global__ __launch_bounds__(256) void group_pack_kernel(const uint8_t *__restrict__ labels, int64_t P, int H, int S, int nw,
+                                                         uint32_t *__restrict__ LW) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x, PG = (P + 15) / 16;
+    if (idx >= PG * nw * 64) return;
+    const int lane = (int)(idx & 63), w = (int)((idx >> 6) % nw);
+    const int64_t p = ((idx >> 6) / nw) * 16 + (lane & 15);
+    uint32_t word = 0;
+    if (p < P) {
+        for (int j = 0; j < 32; ++j) {
+            const int s = 4 * (32 * w + j) + (lane >> 4);
+            if (s < S) {
+                const bool one = labels ? labels[p * S + s] != 0 : s >= H;
+                word |= (one ? 1u : 0u) << j;
+            }
+        }
+    }
+    LW[idx] = word;
+}
+
+struct gp_args {
+    gp_ws ws;
+    int64_t C, P;
+    int N, KS, nw;
+    double kf, dof;                    // S / (U H), S - 2
+    double *t;                         // the observed kernel's
+    unsigned long long *count_t;       // the permutation kernel's
+};
+
+// bit j of a label word -> 0.0 / 1.0: the sign-extended bit masks the high word of 1.0
+__device__ __forceinline__ double gp_label(uint32_t word, int j) {
+    return __hiloint2double(__builtin_amdgcn_sbfe((int)word, (unsigned)j, 1u) & 0x3FF00000, 0);
+}
+
+// One tile: acc[g] = labels of group g (16 permutations) x 16 rows, over all KS K-steps in ascending order.  xp: this lane's
+// row at subject lane >> 4 of K-step 0.  Four K-steps at a time, their loads issued together.
+template <int G>
+__device__ __forceinline__ void gp_tile_mma(const double *__restrict__ xp, int64_t jstride, const uint32_t (&lw)[G][GP_NW], int nw,
+                                            int KS, double4_t (&acc)[G]) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) acc[g] = double4_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int w = 0; w < GP_NW; ++w) {
+        if (w < nw) {                                        // (uniform)
+            const int jn = KS - 32 * w < 32 ? KS - 32 * w : 32;
+            const double *__restrict__ xw = xp + (int64_t)(32 * w) * jstride;
+            int j = 0;
+            for (; j + 4 <= jn; j += 4) {
+                double bv[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) bv[i] = xw[(int64_t)(j + i) * jstride];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int g = 0; g < G; ++g)
+                        acc[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(gp_label(lw[g][w], j + i), bv[i], acc[g], 0, 0, 0);
+            }
+            for (; j < jn; ++j) {
+                const double bv = xw[(int64_t)j * jstride];
+#pragma unroll
+                for (int g = 0; g < G; ++g)
+                    acc[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(gp_label(lw[g][w], j), bv, acc[g], 0, 0, 0);
+            }
+        }
+    }
+}
+
+// t^2 from the sum A over the labelled subjects: g = A^2 S/(U H), t^2 = g (S - 2) / (Q - g)
+__device__ __forceinline__ double gp_t2(double A, double Qc, double kf, double dof) {
+    const double gq = A * A * kf;
+    return gq * dof / (Qc - gq);
+}
+
+// The observed labelling (the one row the pack kernel made of it): a wave per 16 consecutive connections, each connection
+// once.  Row 0 of the tile is the labelling: lanes 0 .. 15, result element 0.
+__global__ __launch_bounds__(64 * GP_WAVES) void group_observed_kernel(gp_args a) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t C = a.C, c0 = ((int64_t)blockIdx.x * GP_WAVES + wv) * 16;
+    if (c0 >= C) return;
+    const int col = lane & 15, ks = lane >> 4;
+    const int64_t c = c0 + col < C ? c0 + col : C - 1;       // (a column past the last reads the last row and writes nothing)
+    uint32_t lw[1][GP_NW];
+#pragma unroll
+    for (int w = 0; w < GP_NW; ++w) lw[0][w] = w < a.nw ? a.ws.LW[w * 64 + lane] : 0u;
+    double4_t acc[1];
+    gp_tile_mma<1>(a.ws.XT + c * 4 + ks, C * 4, lw, a.nw, a.KS, acc);
+    if (ks == 0 && c0 + col < C) {
+        const double A = acc[0][0];
+        const double t2 = gp_t2(A, a.ws.Q[c], a.kf, a.dof);
+        a.ws.t2obs[c] = t2;
+        a.t[c] = copysign(sqrt(t2), A);
+    }
+}
+
+// ... and its region sums, added up exactly as the permutation kernel adds a row's: lane = column of the tile, a running sum
+// over the tiles in tile order, then the butterfly over the 16 columns.
+__global__ __launch_bounds__(64) void group_observed_region_kernel(const double *__restrict__ t2obs, int N, double *__restrict__ region) {
+    const int n = blockIdx.x, col = threadIdx.x & 15;
+    double rs = 0.0;
+    for (int k0 = 0; k0 < N - 1; k0 += 16) {
+        const int k = k0 + col;
+        const bool valid = k < N - 1;
+        int m;
+        double t2 = t2obs[bl_edge(n, valid ? k : N - 2, m)];
+        if (!valid) t2 = 0.0;
+        rs += t2;
+    }
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) rs += __shfl_xor(rs, o, 64);
+    if (threadIdx.x == 0) region[n] = rs;
+}
+
+__global__ __launch_bounds__(64 * GP_WAVES) void baseline_group_kernel(gp_args a) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n = blockIdx.x, N = a.N, nw = a.nw;
+    const int64_t C = a.C, P = a.P, PG = (P + 15) / 16;
+    const int64_t pg0 = ((int64_t)blockIdx.y * GP_WAVES + wv) * GP_G;
+    if (pg0 >= PG) return;                                   // (no workgroup barrier below)
+    const int col = lane & 15, ks = lane >> 4;
+    uint32_t lw[GP_G][GP_NW];
+#pragma unroll
+    for (int g = 0; g < GP_G; ++g)
+#pragma unroll
+        for (int w = 0; w < GP_NW; ++w) lw[g][w] = (w < nw && pg0 + g < PG) ? a.ws.LW[((pg0 + g) * nw + w) * 64 + lane] : 0u;
+    double rs[GP_G][4], mx[GP_G][4];
+#pragma unroll
+    for (int g = 0; g < GP_G; ++g)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rs[g][r] = mx[g][r] = 0.0;
+    for (int k0 = 0; k0 < N - 1; k0 += 16) {
+        const int k = k0 + col;
+        const bool valid = k < N - 1;
+        int m;
+        const int64_t c = bl_edge(n, valid ? k : N - 2, m);  // (a column past the last reads the last row and is masked)
+        double4_t acc[GP_G];
+        gp_tile_mma<GP_G>(a.ws.XT + c * 4 + ks, C * 4, lw, nw, a.KS, acc);
+        // result element r of group g: permutation (pg0 + g) 16 + ks + 4 r, connection k0 + col
+        const double Qc = a.ws.Q[c], t2o = a.ws.t2obs[c];
+        const bool own = valid && k < n;
+        int cnt = 0;
+#pragma unroll
+        for (int g = 0; g < GP_G; ++g) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                double t2 = gp_t2(acc[g][r], Qc, a.kf, a.dof);
+                if (!valid) t2 = 0.0;
+                rs[g][r] += t2;
+                mx[g][r] = fmax(mx[g][r], t2);
+                const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
+                cnt += (own && p < P && t2 >= t2o) ? 1 : 0;
+            }
+        }
+        cnt += __shfl_xor(cnt, 16, 64);
+        cnt += __shfl_xor(cnt, 32, 64);
+        if (own && ks == 0 && cnt) atomicAdd(&a.count_t[c], (unsigned long long)cnt);
+    }
+#pragma unroll
+    for (int g = 0; g < GP_G; ++g) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double s = rs[g][r], v = mx[g][r];
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                s += __shfl_xor(s, o, 64);
+                v = fmax(v, __shfl_xor(v, o, 64));
+            }
+            const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
+            if (col == 0 && p < P) {
+                a.ws.Rpart[(int64_t)n * P + p] = s;
+                a.ws.Mpart[(int64_t)n * P + p] = v;
+            }
+        }
+    }
+}
+
+// Workgroups 0 .. N - 1: the exceedance count of region blockIdx.x, threads over the permutations (integer sums, no atomics).
+// The workgroups behind them: thread = permutation, the maxima over the regions of both partials.
+__global__ __launch_bounds__(256) void group_fold_kernel(const double *__restrict__ Rpart, const double *__restrict__ Mpart,
+                                                         const double *__restrict__ region, int N, int64_t P,
+                                                         double *__restrict__ null_max_region, double *__restrict__ null_max_t,
+                                                         int64_t *__restrict__ count_region) {
+    __shared__ int red[4];
+    if ((int)blockIdx.x < N) {
+        const int n = blockIdx.x;
+        const double Ro = region[n];
+        const double *__restrict__ Rn = Rpart + (int64_t)n * P;
+        int cnt = 0;
+        for (int64_t p = threadIdx.x; p < P; p += 256) cnt += Rn[p] >= Ro ? 1 : 0;
+        cnt = bl_wave_sum_int(cnt);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+        __syncthreads();
+        if (threadIdx.x == 0) count_region[n] = (int64_t)red[0] + red[1] + red[2] + red[3];
+        return;
+    }
+    const int64_t p = (int64_t)(blockIdx.x - N) * 256 + threadIdx.x;
+    if (p >= P) return;
+    double mr = 0.0, mt = 0.0;
+#pragma unroll 8
+    for (int n = 0; n < N; ++n) {
+        mr = fmax(mr, Rpart[(int64_t)n * P + p]);
+        mt = fmax(mt, Mpart[(int64_t)n * P + p]);
+    }
+    null_max_region[p] = mr;
+    null_max_t[p] = sqrt(mt);
+}
+
+}  // namespace
+
+extern "C" int fcd_baseline_normative(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                      double z_threshold, double *msq0, int32_t *n_edges0, int32_t *n_over0, double *msq,
+                                      int32_t *n_edges, int32_t *n_over, int32_t *n_controls, double *z0, double *z,
+                                      fcd_stream stream) {
+    if (!ctx || !b || !bt || !msq0 || !n_edges0 || !n_over0 || !msq || !n_edges || !n_over || !n_controls)
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_baseline_normative: null pointer");
+    if (C < 1 || H < 1 || U < 1) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_baseline_normative: C, H=%lld and U=%lld must be >= 1", H, U);
+    const int64_t N = fcd_C_to_N(C);
+    if (N < 2) return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_baseline_normative: C=%lld is not a triangular number", C);
+    if (H > BN_HMAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_baseline_normative: H=%lld controls, at most %lld", H, BN_HMAX);
+    const int64_t gy = (H + U + 63) / 64;
+    if (N > 46340 || gy > 65535)
+        return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_baseline_normative: shape too large (Nreg=%lld, U=%lld)", N, U);
+    norm_args a;
+    a.b = b;
+    a.bt = bt;
+    a.N = (int)N;
+    a.H = (int)H;
+    a.U = (int)U;
+    a.thr = z_threshold;
+    a.msq0 = msq0;
+    a.msq = msq;
+    a.ne0 = n_edges0;
+    a.ne = n_edges;
+    a.no0 = n_over0;
+    a.no = n_over;
+    a.n_controls = n_controls;
+    a.z0 = z0;
+    a.z = z;
+    hipLaunchKernelGGL(baseline_normative_kernel, dim3((unsigned)N, (unsigned)gy), dim3(64 * BN_WAVES), 0, (hipStream_t)stream, a);
+    FCD_LAUNCH_CHECK();
+    return FCD_OK;
+}
+
+extern "C" int fcd_baseline_group_perm(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                       const uint8_t *labels, int64_t P, double *t, double *region, double *null_max_t,
+                                       double *null_max_region, int64_t *count_t, int64_t *count_region, fcd_stream stream) {
+    if (!ctx || !b || !bt || !labels || !t || !region || !null_max_t || !null_max_region || !count_t || !count_region)
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_baseline_group_perm: null pointer");
+    if (C < 1 || H < 1 || U < 1 || P < 1)
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_baseline_group_perm: C, H, U=%lld and P=%lld must be >= 1", U, P);
+    const int64_t S = H + U;
+    if (S < 3) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_baseline_group_perm: %lld subjects, a pooled variance needs 3", S);
+    const int64_t N = fcd_C_to_N(C);
+    if (N < 2) return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_baseline_group_perm: C=%lld is not a triangular number", C);
+    if (S > GP_SMAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_baseline_group_perm: %lld subjects, at most %lld", S, GP_SMAX);
+    const int64_t gy = (P + GP_PB - 1) / GP_PB;
+    if (N > 46340 || gy > 65535 || (C + GC_WAVES - 1) / GC_WAVES > INT32_MAX || N * P > (1ll << 34))
+        return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_baseline_group_perm: shape too large (Nreg=%lld, P=%lld)", N, P);
+    const int KS = (int)((S + 3) / 4), nw = (KS + 31) / 32;
+    hipStream_t st = (hipStream_t)stream;
+    // Nothing of the workspace outlives the call.
+    int rc = fcd_ws_reserve(ctx, gp_ws_bytes(C, N, P, KS, nw));
+    if (rc) return rc;
+    gp_args a;
+    a.ws = gp_ws_at(ctx->ws, C, N, P, KS);
+    a.C = C;
+    a.N = (int)N;
+    a.KS = KS;
+    a.nw = nw;
+    a.kf = (double)S / ((double)U * (double)H);
+    a.dof = (double)(S - 2);
+    a.t = t;
+    a.count_t = reinterpret_cast<unsigned long long *>(count_t);
+    FCD_HIP_TRY(hipMemsetAsync(count_t, 0, (size_t)C * sizeof(int64_t), st));
+    hipLaunchKernelGGL(group_centre_kernel, dim3((unsigned)((C + GC_WAVES - 1) / GC_WAVES)), dim3(64 * GC_WAVES), 0, st, b, bt, C, (int)H,
+                       (int)U, KS, a.ws.XT, a.ws.Q);
+    FCD_LAUNCH_CHECK();
+    // the observed labelling: one packed row through the same tile product and the same t^2, each connection once
+    a.P = 1;
+    hipLaunchKernelGGL(group_pack_kernel, dim3((unsigned)((nw * 64 + 255) / 256)), dim3(256), 0, st, (const uint8_t *)nullptr, (int64_t)1,
+                       (int)H, (int)S, nw, a.ws.LW);
+    FCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(group_observed_kernel, dim3((unsigned)((C + 16 * GP_WAVES - 1) / (16 * GP_WAVES))), dim3(64 * GP_WAVES), 0, st, a);
+    FCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(group_observed_region_kernel, dim3((unsigned)N), dim3(64), 0, st, a.ws.t2obs, (int)N, region);
+    FCD_LAUNCH_CHECK();
+    a.P = P;
+    const int64_t PG = (P + 15) / 16;
+    hipLaunchKernelGGL(group_pack_kernel, dim3((unsigned)((PG * nw * 64 + 255) / 256)), dim3(256), 0, st, labels, P, (int)H, (int)S, nw,
+                       a.ws.LW);
+    FCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(baseline_group_kernel, dim3((unsigned)N, (unsigned)gy), dim3(64 * GP_WAVES), 0, st, a);
+    FCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)(N + (P + 255) / 256)), dim3(256), 0, st, a.ws.Rpart, a.ws.Mpart, region, (int)N, P,
+                       null_max_region, null_max_t, count_region);
+    FCD_LAUNCH_CHECK();
+    return FCD_OK;
+}

@@ -384,6 +384,39 @@ int fcd_edge_cov_fit(fcd_ctx *ctx, const double *b, int64_t C, int64_t H, const 
 int fcd_edge_cov_apply(fcd_ctx *ctx, const double *x, int64_t C, int64_t S, const double *z, int64_t Q, const double *z_ref,
                        const double *beta, double *out, fcd_stream stream);
 
+/* ---- classical baselines ---------------------------------------------------------------------------------------------------
+ * Not in the reference; oracle = tests/baseline_ref.py.  b (C, H) controls, bt (C, U) patients, fp64, device; C triangular,
+ * connections in the order of fcd_c_to_nm.  E(n) = the Nreg - 1 connections that touch region n.  Both calls are deterministic
+ * (fixed reduction orders, integer atomics only) and write no input.
+ *
+ * Normative scores.  Per connection over the controls observed there (a NaN is unobserved): n_c, mean m_c, s_c^2 = sum
+ * (x - m_c)^2 / (n_c - 1) in two passes.  z[c,u] = (bt[c,u] - m_c) / (s_c sqrt(1 + 1/n_c)); the leave-one-out score of control h,
+ * z0[c,h], is the same with mean and deviation of the OTHER n_c - 1 observed controls, their sums taken directly (no
+ * downdate), and n_c - 1 for n_c.  A score is NaN where n_c < 3, where the deviation is not > 0, or where the value is NaN.
+ * Per region n and subject: n_edges = defined scores over E(n), msq = mean of z^2 over them (NaN if none), n_over = those
+ * with |z| > z_threshold.  msq0, n_edges0, n_over0 (Nreg, H) and msq, n_edges, n_over (Nreg, U); n_controls (C,) = n_c;
+ * z0 (C, H) and z (C, U) may be NULL (not written).  One launch, no workspace.
+ * FCD_ERR_SHAPE for a non-triangular C; FCD_ERR_UNSUPPORTED for H > 1024 (a control row lives in LDS) or
+ * H + U > 65535 * 64; FCD_ERR_ARG for a null pointer or a size < 1. */
+int fcd_baseline_normative(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U, double z_threshold,
+                           double *msq0, int32_t *n_edges0, int32_t *n_over0, double *msq, int32_t *n_edges, int32_t *n_over,
+                           int32_t *n_controls, double *z0, double *z, fcd_stream stream);
+/* Two-sample permutation test.  X = [b | bt] (C, S), S = H + U, complete (NaN is not checked here and spreads), rows centred on
+ * their mean over S, Q_c = sum x^2.  For a labelling l in {0,1}^S with U ones: A = sum l_s x_s, g = A^2 S/(U H),
+ * t^2 = g (S - 2) / (Q_c - g) -- the square of Student's pooled-variance t -- t = sign(A) sqrt(t^2), R[n] = sum over E(n) of t^2.
+ * labels (P, S) bytes, non-zero = 1 (that a row has U ones is the caller's to check).  The observed labelling has its ones on
+ * the last U subjects; it runs through the same tile product, the same t^2 and the same order of sums as the permutations,
+ * so a row of labels equal to it gives its statistics bit for bit.
+ * t (C,), region (Nreg,): observed.  null_max_t (P,) = max_c |t|, null_max_region (P,) = max_n R.  count_t (C,) = number of
+ * rows with t^2 >= the observed t^2, count_region (Nreg,) = rows with R >= the observed R.  No (P, C) array exists anywhere:
+ * the sums A are an fp64 MFMA product whose tiles are reduced in registers.  Seven launches; uses the context's workspace
+ * (about 8 C S + 16 Nreg P bytes), grown on demand.
+ * FCD_ERR_SHAPE for a non-triangular C; FCD_ERR_UNSUPPORTED for S > 1024 (the labels of a permutation are 8 words per lane)
+ * or P > 65535 * 128; FCD_ERR_ARG for a null pointer, a size < 1 or S < 3. */
+int fcd_baseline_group_perm(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                            const uint8_t *labels, int64_t P, double *t, double *region, double *null_max_t,
+                            double *null_max_region, int64_t *count_t, int64_t *count_region, fcd_stream stream);
+
 /* ---- variational updates ------------------------------------------------------------------ */
 /* UnsharedRegionFit._update_lq_F, fit.py:157-174 (+ _eval_q_R_w 382-406). */
 int fcd_vb_update_qF(fcd_ctx *ctx, const double *lq_R, const double *S_B, const double *lM,
