@@ -7,6 +7,10 @@ normative()   per patient: "which regions of this patient are abnormal?" -- the 
 group_test()  per population: "which regions are abnormal in this disease?" -- Student's two-sample t per connection, the
               sum of t^2 per region, family-wise error control by the permutation law of the maximum statistic.  What
               SharedRegionFit answers with a posterior.
+network_test()  per population: "which sub-network is abnormal in this disease?" -- the network-based statistic: the t of
+              group_test() thresholded, the connected components of the suprathreshold graph, family-wise error control by
+              the permutation law of the largest component.  graph_components() gives the components of any mask.
+              Oracle = tests/network_ref.py; fcd_baseline_network_bits, fcd_graph_components.
 
 b (C, H) controls and bt (C, U) patients, NumPy arrays or torch tensors, float64, connections in util.c_to_nm order;
 E(n) = the N - 1 connections that touch region n.  Both run on the device (fcd_baseline_normative,
@@ -192,7 +196,7 @@ def group_test(b, bt, n_perm=10000, *, seed=0, labels=None, ctx=None, as_numpy=T
     count_t (C,) int64 = #{p: |t_pc| >= |t_c|}, count_region (N,) int64 = #{p: R_pn >= R_n}; p_t, p_region =
     (1 + count) / (1 + P); p_fwe_t, p_fwe_region = the same against the maxima; labels (P, S) uint8 as used.
     A NaN is a ValueError (missing data is not provided here); more than 1024 subjects a NotImplementedError.
-    Not provided: sessions, noise variances, Welch's t, cluster or network-based statistics.
+    Not provided: sessions, noise variances, Welch's t, cluster statistics.  The network-based statistic is network_test().
     """
     import torch
     (C, N, H, U) = _check_pair(b, bt, "group_test")
@@ -245,3 +249,179 @@ def group_pvalues(t, region, null_max_t, null_max_region, count_t, count_region)
             "p_region": (1.0 + count_region) / (1.0 + P),
             "p_fwe_t": (1.0 + _count_ge(null_max_t, np.abs(t))[0]) / (1.0 + P),
             "p_fwe_region": (1.0 + _count_ge(null_max_region, region)[0]) / (1.0 + P)}
+
+
+# ---- network-based statistic -------------------------------------------------------------------------------------------------
+
+MAX_REGIONS = 1024        # graph_components(), network_test(): a row of bits lives in one workgroup's LDS (64 KB at 1024)
+_P_CHUNK = 1 << 14        # labellings per call of network_test(): bounds the bit workspace (W words each)
+TAILS = {"both": 0, "greater": 1, "less": 2}
+
+
+def _pair_index(N):
+    """(n, m) of every connection, in util.c_to_nm order."""
+    (n, m) = np.tril_indices(N, -1)
+    return n.astype(np.int64), m.astype(np.int64)
+
+
+def _component_tables(component, edge_mask):
+    """(label, edges, regions) of the components of one graph, by decreasing extent and then by label."""
+    N = component.shape[0]
+    n_of = _pair_index(N)[0]
+    edges = np.bincount(component[n_of[edge_mask]], minlength=N)
+    regions = np.bincount(component[component >= 0], minlength=N)
+    label = np.flatnonzero(edges > 0)
+    label = label[np.lexsort((label, -edges[label]))].astype(np.int64)
+    return label, edges[label].astype(np.int64), regions[label].astype(np.int64)
+
+
+def network_pvalues(component_edges, null_max_extent):
+    """The host half of network_test(): p_fwe[k] = (1 + #{p: null_max_extent[p] >= component_edges[k]}) / (1 + P)."""
+    (ge, P) = _count_ge(np.asarray(null_max_extent, dtype=np.float64).reshape(-1),
+                        np.asarray(component_edges, dtype=np.float64).reshape(-1))
+    return (1.0 + ge) / (1.0 + P)
+
+
+def _components_call(ctx, bits, B, C, N, component, n_edges, max_extent, max_regions):
+    ctx.call("fcd_graph_components", _lib.dptr(bits), B, C, _lib.dptr(component), _lib.dptr(n_edges), _lib.dptr(max_extent),
+             _lib.dptr(max_regions), _lib.stream_ptr())
+
+
+def graph_components(mask, *, ctx=None, as_numpy=True):
+    """
+    Connected components of the graphs on N regions whose edges are the set entries of mask, (C,) or (B, C), bool or 0/1,
+    NumPy or torch, connections in util.c_to_nm order.  On the device (fcd_graph_components), one workgroup per graph.
+
+    A component's label is the smallest region in it, its extent its number of connections; a region without a connection
+    belongs to none and has label -1.  Returns a dict: component (B, N) int64; n_edges, max_extent, max_regions (B,) int64 =
+    set connections, extent of the largest component, regions of the component with the most regions.  For a 1-D mask the
+    leading axis is dropped and component_label, component_edges, component_regions (K,) list the K >= 0 components by
+    decreasing extent, then by label.  NumPy arrays, or device tensors with as_numpy=False.
+    A non-triangular C is a ValueError, more than 1024 regions a NotImplementedError.
+    """
+    import torch
+    sh = _shape(mask)
+    if len(sh) not in (1, 2) or (len(sh) == 2 and sh[0] < 1):
+        raise ValueError("graph_components: mask must have shape (C,) or (B, C) with B >= 1, not %s" % (sh,))
+    C = sh[-1]
+    N = _n_regions(C)
+    if N > MAX_REGIONS:
+        raise NotImplementedError("graph_components: %d regions, at most %d" % (N, MAX_REGIONS))
+    ctx = ctx if ctx is not None else _lib.Context()
+    dev = ctx.device
+    m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(mask))
+    m = m.to(device=dev).reshape(-1, C)
+    if not bool(((m == 0) | (m == 1)).all().item()):
+        raise ValueError("graph_components: mask must hold 0 and 1 (or booleans) only")
+    B = int(m.shape[0])
+    W = (C + 31) // 32
+    # bit c & 31 of word c >> 5, as bytes: bit c & 7 of byte c >> 3
+    padded = torch.zeros((B, 32 * W), dtype=torch.int32, device=dev)
+    padded[:, :C] = m.to(torch.int32)
+    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32, device=dev)
+    bits = (padded.view(B, 4 * W, 8) * weights).sum(dim=2).to(torch.uint8).contiguous()
+    component = torch.empty((B, N), dtype=torch.int32, device=dev)
+    (n_edges, max_extent, max_regions) = (torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(3))
+    _components_call(ctx, bits, B, C, N, component, n_edges, max_extent, max_regions)
+    out = {"component": component.long(), "n_edges": n_edges.long(), "max_extent": max_extent.long(),
+           "max_regions": max_regions.long()}
+    if len(sh) == 1:
+        out = dict((k, v[0]) for (k, v) in out.items())
+        tables = _component_tables(out["component"].cpu().numpy(), m[0].cpu().numpy().astype(bool))
+        names = ("component_label", "component_edges", "component_regions")
+        if as_numpy:
+            out = dict((k, v.cpu().numpy()) for (k, v) in out.items())
+            out.update(zip(names, tables))
+        else:
+            out.update((k, torch.as_tensor(v, device=dev)) for (k, v) in zip(names, tables))
+        return out
+    return dict((k, v.cpu().numpy()) for (k, v) in out.items()) if as_numpy else out
+
+
+def network_test(b, bt, threshold, n_perm=10000, *, tail="both", seed=0, labels=None, ctx=None, as_numpy=True):
+    """
+    The network-based statistic (Zalesky, Fornito & Bullmore 2010): which sub-networks differ between patients and controls?
+    b (C, H), bt (C, U), complete.
+
+    Data, labellings, centring and the pooled-variance t are group_test()'s; the observed labelling has its ones on the last U
+    subjects.  A connection is suprathreshold where |t| > threshold (tail="both"), t > threshold ("greater": patients above
+    controls, the sign of group_test's t) or t < -threshold ("less"); threshold > 0 in t units.  The components are those
+    of the graph on the N regions whose edges are the suprathreshold connections: a component's extent is its number of
+    connections, its label the smallest region in it; a region without a suprathreshold connection has label -1.  The
+    family-wise error is controlled by the permutation law of the largest extent.  labels as in group_test(); a row equal
+    to the observed labelling counts, and gives the observed bits exactly.  Labellings are walked in chunks; the results do
+    not depend on the chunk size and repeat exactly from call to call.
+
+    Returns a dict: t (C,); edge_mask (C,) bool; component (N,) int64; component_label, component_edges, component_regions
+    (K,) int64, the K >= 0 observed components by decreasing extent, then by label; null_max_extent, null_max_regions,
+    null_n_edges (P,) int64 = per labelling the largest extent, the regions of the component with the most regions, the
+    suprathreshold connections; p_fwe (K,) = (1 + #{p: null_max_extent[p] >= extent}) / (1 + P); p_fwe_region (N,) = the p of
+    the region's component, NaN at label -1; labels (P, S) uint8 as used; threshold, tail.
+    Refused: everything group_test() refuses; a threshold that is not finite and > 0 or an unknown tail (ValueError); more
+    than 1024 regions (NotImplementedError).  Not provided: the intensity form sum (|t| - threshold) (it would need a value
+    per bit), TFCE, sessions, noise variances, missing data.
+    """
+    import torch
+    (C, N, H, U) = _check_pair(b, bt, "network_test")
+    S = H + U
+    if S > MAX_SUBJECTS:
+        raise NotImplementedError("network_test: %d subjects, at most %d" % (S, MAX_SUBJECTS))
+    if N > MAX_REGIONS:
+        raise NotImplementedError("network_test: %d regions, at most %d" % (N, MAX_REGIONS))
+    if S < 3:
+        raise ValueError("network_test: %d subjects, a pooled variance needs 3" % S)
+    thr = float(threshold)
+    if not np.isfinite(thr) or thr <= 0.0:
+        raise ValueError("network_test: threshold must be finite and > 0, not %r" % (threshold,))
+    if tail not in TAILS:
+        raise ValueError("network_test: tail must be one of 'both', 'greater', 'less', not %r" % (tail,))
+    if _has_nan(b) or _has_nan(bt):
+        raise ValueError("network_test: NaN in b or bt; the data must be complete (missing data is not provided here)")
+    if labels is None:
+        if int(n_perm) < 1:
+            raise ValueError("network_test: n_perm must be >= 1")
+        lab = draw_labels(n_perm, H, U, seed)
+    else:
+        lab = _check_labels(labels, S, U)
+    P = int(lab.shape[0])
+    ctx = ctx if ctx is not None else _lib.Context()
+    (bd, btd) = (_device_f64(b, ctx), _device_f64(bt, ctx))
+    dev = ctx.device
+    labd = torch.as_tensor(lab, device=dev)
+    W = (C + 31) // 32
+
+    def i32(*sh):
+        return torch.empty(sh, dtype=torch.int32, device=dev)
+
+    def bits_call(lab_c, n, bits, t):
+        ctx.call("fcd_baseline_network_bits", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(lab_c), n, thr, TAILS[tail],
+                 _lib.dptr(bits), _lib.dptr(t), _lib.stream_ptr())
+
+    # the observed labelling: the same kernels at P = 1
+    t = torch.empty((C,), dtype=torch.float64, device=dev)
+    bits_obs = i32(1, W)
+    bits_call(None, 1, bits_obs, t)
+    (component, obs_edges, obs_extent, obs_regions) = (i32(1, N), i32(1), i32(1), i32(1))
+    _components_call(ctx, bits_obs, 1, C, N, component, obs_edges, obs_extent, obs_regions)
+    (null_n_edges, null_max_extent, null_max_regions) = (i32(P), i32(P), i32(P))
+    for p0 in range(0, P, _P_CHUNK):
+        n = min(_P_CHUNK, P - p0)
+        bits = i32(n, W)
+        bits_call(labd[p0:p0 + n], n, bits, None)
+        _components_call(ctx, bits, n, C, N, None, null_n_edges[p0:p0 + n], null_max_extent[p0:p0 + n],
+                         null_max_regions[p0:p0 + n])
+    host = {"t": t.cpu().numpy(), "component": component[0].long().cpu().numpy(),
+            "null_max_extent": null_max_extent.long().cpu().numpy(), "null_max_regions": null_max_regions.long().cpu().numpy(),
+            "null_n_edges": null_n_edges.long().cpu().numpy()}
+    host["edge_mask"] = np.unpackbits(bits_obs.cpu().numpy().view(np.uint8).reshape(-1), bitorder="little")[:C].astype(bool)
+    (label, edges, regions) = _component_tables(host["component"], host["edge_mask"])
+    host.update(component_label=label, component_edges=edges, component_regions=regions)
+    host["p_fwe"] = network_pvalues(edges, host["null_max_extent"])
+    p_of = np.full(N + 1, np.nan)                            # (label -1 reads the last entry)
+    p_of[label] = host["p_fwe"]
+    host["p_fwe_region"] = p_of[host["component"]]
+    out = host if as_numpy else dict((k, torch.as_tensor(v, device=dev)) for (k, v) in host.items())
+    out["labels"] = lab if as_numpy else labd
+    out["threshold"] = thr
+    out["tail"] = tail
+    return out

@@ -38,6 +38,17 @@
 //                      per connection (integer atomics).  Writes the (n, p) partials.
 //   group_fold_kernel  workgroup n: the exceedance count of region n, threads over the permutations; the workgroups behind
 //                      them: thread = permutation, max over n of both partials.  No atomics.
+//
+// Network-based statistic (fcd_baseline_network_bits, fcd_graph_components): threshold t, take the connected components
+//   network_bits_kernel      group_centre_kernel, group_pack_kernel, gp_tile_mma and gp_t2 as above, but each connection once
+//                      (half of the permutation kernel's matrix work) and nothing kept but one bit per (labelling, connection):
+//                      a wave takes 16 consecutive connections x 4 groups of 16 labellings; one ballot per result element
+//                      holds the 16 connections of four labellings, stored as four uint16 (plain vector stores).  The
+//                      observed labelling is a call with P = 1 through the same kernel.
+//   graph_components_kernel  one workgroup per row of bits, the row in LDS (64 KB at 1024 regions, the limit).  label[x] = x;
+//                      per round every set bit (n, m) pulls the larger label, and the region that label names, down to the
+//                      smaller (LDS atomicMin), then label[x] = label[label[x]]; until a round changes nothing, at most N
+//                      rounds.  Then extents, regions, maxima with integer LDS atomics.
 #include "fcd_common.h"
 
 namespace {
@@ -439,6 +450,163 @@ __global__ __launch_bounds__(256) void group_fold_kernel(const double *__restric
     null_max_t[p] = sqrt(mt);
 }
 
+// ---- network-based statistic ----------------------------------------------------------------------------------------------
+
+constexpr int NB_G = 4;                  // groups of 16 labellings per wave of the bits kernel
+constexpr int NB_NMAX = 1024;            // regions of the components kernel: a row of bits lives in LDS (64 KB at 1024)
+constexpr int CC_T = 256;                // its threads
+
+// workspace of one bits call: XT (KS, C, 4) | Q (C) | label words (PG, nw, 64) uint32
+__host__ static inline size_t nb_ws_bytes(int64_t C, int64_t P, int KS, int nw) {
+    return (size_t)((int64_t)KS * C * 4 + C) * sizeof(double) + (size_t)((P + 15) / 16 * nw * 64) * sizeof(uint32_t);
+}
+
+struct nb_args {
+    const double *XT, *Q;
+    const uint32_t *LW;
+    int64_t C, P, W2;                  // W2 = 2 W: the 16-bit pieces of a row of bits
+    int KS, nw, tail;
+    double kf, dof, thr2;
+    uint16_t *bits;
+    double *t;                         // nullable: the t of labelling 0
+};
+
+// A wave: 16 consecutive connections (piece blockIdx.x * 4 + wave of a row of bits) x NB_G groups of 16 labellings, each
+// connection once.  Result element r of group g in lane l: labelling (pg0 + g) 16 + (l >> 4) + 4 r, connection c0 + (l & 15),
+// so the ballot of a compare holds, in its 16-bit field ks, the 16 connections of labelling (pg0 + g) 16 + ks + 4 r: lane
+// 16 ks stores it.  A piece behind the last connection (C <= 32 W - 16) is written as zeros.
+__global__ __launch_bounds__(64 * GP_WAVES) void network_bits_kernel(nb_args a) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t piece = (int64_t)blockIdx.x * GP_WAVES + wv;
+    if (piece >= a.W2) return;                               // (no workgroup barrier below)
+    const int64_t C = a.C, P = a.P, PG = (P + 15) / 16, c0 = piece * 16;
+    const int64_t pg0 = (int64_t)blockIdx.y * NB_G;
+    const int col = lane & 15, ks = lane >> 4;
+    if (c0 >= C) {
+#pragma unroll
+        for (int g = 0; g < NB_G; ++g) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
+                if (col == 0 && p < P) a.bits[p * a.W2 + piece] = (uint16_t)0;
+            }
+        }
+        return;
+    }
+    const bool valid = c0 + col < C;
+    const int64_t c = valid ? c0 + col : C - 1;              // (a column past the last reads the last row and contributes 0)
+    uint32_t lw[NB_G][GP_NW];
+#pragma unroll
+    for (int g = 0; g < NB_G; ++g)
+#pragma unroll
+        for (int w = 0; w < GP_NW; ++w) lw[g][w] = (w < a.nw && pg0 + g < PG) ? a.LW[((pg0 + g) * a.nw + w) * 64 + lane] : 0u;
+    double4_t acc[NB_G];
+    gp_tile_mma<NB_G>(a.XT + c * 4 + ks, C * 4, lw, a.nw, a.KS, acc);
+    const double Qc = a.Q[c];
+#pragma unroll
+    for (int g = 0; g < NB_G; ++g) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double A = acc[g][r];
+            const double t2 = gp_t2(A, Qc, a.kf, a.dof);
+            const bool side = a.tail == 0 || (a.tail == 1 ? A > 0.0 : A < 0.0);
+            const unsigned long long mask = __ballot(valid && side && t2 > a.thr2);
+            const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
+            if (col == 0 && p < P) a.bits[p * a.W2 + piece] = (uint16_t)(mask >> (16 * ks));
+            if (a.t && p == 0 && valid) a.t[c] = copysign(sqrt(t2), A);
+        }
+    }
+}
+
+// the set bits of word w of a row: (n, m) of connection 32 w by the corrected root, then moved along the word
+template <typename F>
+__device__ __forceinline__ void cc_for_bits(int w, uint32_t word, F f) {
+    if (!word) return;
+    int n, m, at = 0;
+    fcd_edge_to_pair((int64_t)w * 32, n, m);
+    while (word) {
+        const int j = __ffs((int)word) - 1;
+        word &= word - 1u;
+        m += j - at;
+        at = j;
+        while (m >= n) {
+            m -= n;
+            ++n;
+        }
+        f(n, m);
+    }
+}
+
+// One workgroup per row of bits.  LDS: the row's W words | label[N] | extent[N] | regions[N] | changed, n_edges, max_extent,
+// max_regions.  label[x] <= x is always a region of x's component and only ever falls; at the fixed point of the edge step it
+// is the component's smallest region.  Integer atomics only: the result does not depend on their order.
+__global__ __launch_bounds__(CC_T) void graph_components_kernel(const uint32_t *__restrict__ bits, int64_t C, int N, int W,
+                                                                int32_t *__restrict__ component, int32_t *__restrict__ n_edges,
+                                                                int32_t *__restrict__ max_extent, int32_t *__restrict__ max_regions) {
+    extern __shared__ uint32_t cc_lds[];
+    uint32_t *words = cc_lds;
+    int *label = (int *)(words + W), *extent = label + N, *regions = extent + N, *sc = regions + N;
+    const int tid = threadIdx.x;
+    const uint32_t *__restrict__ src = bits + (int64_t)blockIdx.x * W;
+    const uint32_t last = (C & 31) ? (1u << (C & 31)) - 1u : ~0u;          // bits behind C are ignored
+    for (int w = tid; w < W; w += CC_T) words[w] = src[w] & (w == W - 1 ? last : ~0u);
+    for (int x = tid; x < N; x += CC_T) {
+        label[x] = x;
+        extent[x] = 0;
+        regions[x] = 0;
+    }
+    if (tid < 4) sc[tid] = 0;
+    __syncthreads();
+    // At most N rounds: the minimum reaches every region of its component in N - 1 rounds even without the jumps.
+    for (int round = 0; round < N; ++round) {
+        int ch = 0;
+        for (int w = tid; w < W; w += CC_T) {
+            cc_for_bits(w, words[w], [&](int n, int m) {
+                const int ln = label[n], lm = label[m];
+                if (ln != lm) {
+                    const int lo = ln < lm ? ln : lm, hi = ln < lm ? lm : ln;
+                    atomicMin(&label[hi], lo);
+                    atomicMin(&label[ln < lm ? m : n], lo);
+                    ch = 1;
+                }
+            });
+        }
+        if (ch) sc[0] = 1;
+        __syncthreads();
+        const int changed = sc[0];
+        for (int x = tid; x < N; x += CC_T) {                // pointer jumping
+            const int l = label[x], ll = label[l];
+            if (ll < l) atomicMin(&label[x], ll);
+        }
+        __syncthreads();
+        if (!changed) break;                                 // (uniform: every thread read the same word between two barriers)
+        if (tid == 0) sc[0] = 0;
+        __syncthreads();
+    }
+    for (int w = tid; w < W; w += CC_T) cc_for_bits(w, words[w], [&](int n, int) { atomicAdd(&extent[label[n]], 1); });
+    __syncthreads();
+    for (int x = tid; x < N; x += CC_T) {
+        const int l = label[x];
+        if (extent[l] > 0) atomicAdd(&regions[l], 1);
+    }
+    __syncthreads();
+    for (int x = tid; x < N; x += CC_T) {
+        const int e = extent[x], l = label[x];
+        if (e > 0) {
+            atomicAdd(&sc[1], e);
+            atomicMax(&sc[2], e);
+            atomicMax(&sc[3], regions[x]);
+        }
+        if (component) component[(int64_t)blockIdx.x * N + x] = extent[l] > 0 ? l : -1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        n_edges[blockIdx.x] = sc[1];
+        max_extent[blockIdx.x] = sc[2];
+        max_regions[blockIdx.x] = sc[3];
+    }
+}
+
 }  // namespace
 
 extern "C" int fcd_baseline_normative(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
@@ -527,6 +695,74 @@ extern "C" int fcd_baseline_group_perm(fcd_ctx *ctx, const double *b, const doub
     FCD_LAUNCH_CHECK();
     hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)(N + (P + 255) / 256)), dim3(256), 0, st, a.ws.Rpart, a.ws.Mpart, region, (int)N, P,
                        null_max_region, null_max_t, count_region);
+    FCD_LAUNCH_CHECK();
+    return FCD_OK;
+}
+
+extern "C" int fcd_baseline_network_bits(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                         const uint8_t *labels, int64_t P, double threshold, int tail, uint32_t *bits, double *t,
+                                         fcd_stream stream) {
+    if (!ctx || !b || !bt || !bits) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_baseline_network_bits: null pointer");
+    if (C < 1 || H < 1 || U < 1 || P < 1)
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_baseline_network_bits: C, H, U=%lld and P=%lld must be >= 1", U, P);
+    if (!labels && P != 1) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_baseline_network_bits: the observed labelling (labels == NULL) is P = 1, not %lld", P);
+    if (!(threshold > 0.0) || !(threshold <= 1.7976931348623157e308))
+        return fcd_fail(ctx, FCD_ERR_ARG, "fcd_baseline_network_bits: the threshold must be finite and > 0");
+    if (tail < FCD_TAIL_BOTH || tail > FCD_TAIL_LESS) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_baseline_network_bits: unknown tail %lld", tail);
+    const int64_t S = H + U;
+    if (S < 3) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_baseline_network_bits: %lld subjects, a pooled variance needs 3", S);
+    const int64_t N = fcd_C_to_N(C);
+    if (N < 2) return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_baseline_network_bits: C=%lld is not a triangular number", C);
+    if (N > NB_NMAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_baseline_network_bits: %lld regions, at most %lld", N, NB_NMAX);
+    if (S > GP_SMAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_baseline_network_bits: %lld subjects, at most %lld", S, GP_SMAX);
+    const int64_t PG = (P + 15) / 16, gy = (PG + NB_G - 1) / NB_G, W = (C + 31) / 32;
+    if (gy > 65535) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_baseline_network_bits: shape too large (Nreg=%lld, P=%lld)", N, P);
+    const int KS = (int)((S + 3) / 4), nw = (KS + 31) / 32;
+    hipStream_t st = (hipStream_t)stream;
+    // Nothing of the workspace outlives the call.
+    int rc = fcd_ws_reserve(ctx, nb_ws_bytes(C, P, KS, nw));
+    if (rc) return rc;
+    double *XT = (double *)ctx->ws, *Q = XT + (int64_t)KS * C * 4;
+    uint32_t *LW = (uint32_t *)(Q + C);
+    hipLaunchKernelGGL(group_centre_kernel, dim3((unsigned)((C + GC_WAVES - 1) / GC_WAVES)), dim3(64 * GC_WAVES), 0, st, b, bt, C, (int)H,
+                       (int)U, KS, XT, Q);
+    FCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(group_pack_kernel, dim3((unsigned)((PG * nw * 64 + 255) / 256)), dim3(256), 0, st, labels, P, (int)H, (int)S, nw, LW);
+    FCD_LAUNCH_CHECK();
+    nb_args a;
+    a.XT = XT;
+    a.Q = Q;
+    a.LW = LW;
+    a.C = C;
+    a.P = P;
+    a.W2 = 2 * W;
+    a.KS = KS;
+    a.nw = nw;
+    a.tail = tail;
+    a.kf = (double)S / ((double)U * (double)H);
+    a.dof = (double)(S - 2);
+    a.thr2 = threshold * threshold;
+    a.bits = reinterpret_cast<uint16_t *>(bits);
+    a.t = t;
+    hipLaunchKernelGGL(network_bits_kernel, dim3((unsigned)((2 * W + GP_WAVES - 1) / GP_WAVES), (unsigned)gy), dim3(64 * GP_WAVES), 0, st, a);
+    FCD_LAUNCH_CHECK();
+    return FCD_OK;
+}
+
+extern "C" int fcd_graph_components(fcd_ctx *ctx, const uint32_t *bits, int64_t B, int64_t C, int32_t *component, int32_t *n_edges,
+                                    int32_t *max_extent, int32_t *max_regions, fcd_stream stream) {
+    if (!ctx || !bits || !n_edges || !max_extent || !max_regions) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_graph_components: null pointer");
+    if (B < 1 || C < 1) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_graph_components: B=%lld and C=%lld must be >= 1", B, C);
+    const int64_t N = fcd_C_to_N(C);
+    if (N < 2) return fcd_fail(ctx, FCD_ERR_SHAPE, "fcd_graph_components: C=%lld is not a triangular number", C);
+    if (N > NB_NMAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_graph_components: %lld regions, at most %lld", N, NB_NMAX);
+    if (B > INT32_MAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_graph_components: shape too large (Nreg=%lld, B=%lld)", N, B);
+    const int64_t W = (C + 31) / 32;
+    const size_t shmem = (size_t)(W + 3 * N + 4) * sizeof(uint32_t);
+    int rc = fcd_lds_attr(ctx, FCD_KA_COMPONENTS, (const void *)graph_components_kernel, shmem);
+    if (rc) return rc;
+    hipLaunchKernelGGL(graph_components_kernel, dim3((unsigned)B), dim3(CC_T), shmem, (hipStream_t)stream, bits, C, (int)N, (int)W, component,
+                       n_edges, max_extent, max_regions);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
 }

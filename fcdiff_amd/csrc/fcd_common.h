@@ -46,7 +46,8 @@ struct fcd_knobs {
 // kernels whose dynamic-LDS limit is raised with hipFuncSetAttribute: done once per (kernel, size) and remembered here
 enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA_F_PAIR_T = FCD_KA_F_PAIR + 4,
        FCD_KA_F_PAIR_R = FCD_KA_F_PAIR_T + 4,
-       FCD_KA_F_PAIR_BIG = FCD_KA_F_PAIR_R + 4, FCD_KA_R_STEP = FCD_KA_F_PAIR_BIG + 4, FCD_KA_R_PIPE = FCD_KA_R_STEP + 4, FCD_KA_CORR = FCD_KA_R_PIPE + 4, FCD_KA_N = FCD_KA_CORR + 1 };
+       FCD_KA_F_PAIR_BIG = FCD_KA_F_PAIR_R + 4, FCD_KA_R_STEP = FCD_KA_F_PAIR_BIG + 4, FCD_KA_R_PIPE = FCD_KA_R_STEP + 4, FCD_KA_CORR = FCD_KA_R_PIPE + 4, FCD_KA_COMPONENTS = FCD_KA_CORR + 1,
+       FCD_KA_N = FCD_KA_COMPONENTS + 1 };
 
 #define FCD_NAN_SLOTS 256
 

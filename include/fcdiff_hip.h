@@ -416,6 +416,33 @@ int fcd_baseline_normative(fcd_ctx *ctx, const double *b, const double *bt, int6
 int fcd_baseline_group_perm(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
                             const uint8_t *labels, int64_t P, double *t, double *region, double *null_max_t,
                             double *null_max_region, int64_t *count_t, int64_t *count_region, fcd_stream stream);
+/* Network-based statistic (Zalesky et al. 2010), in two halves.
+ * The bits: the t^2 of the permutation test above (same centring, same tile product, same formula), each connection once,
+ * kept as ONE BIT per (labelling, connection): set where t^2 > threshold^2 and, for FCD_TAIL_GREATER / _LESS, the sum A over
+ * the labelled subjects is > 0 / < 0 (patients above / below controls).  bits (P, W) uint32, W = ceil(C / 32): bit c & 31 of
+ * word c >> 5; the bits behind C in the last word are written as 0.  labels (P, S) bytes as above, or NULL with P = 1: the
+ * observed labelling, which goes through the same kernel, so a row of labels equal to it gives its bits exactly.
+ * t (C,), nullable: the signed t of labelling 0 (what the observed call is asked for).  No (P, C) array of doubles exists.
+ * Three launches; workspace about 8 C S bytes.
+ * FCD_ERR_SHAPE for a non-triangular C; FCD_ERR_UNSUPPORTED for more than 1024 regions, S > 1024 or P > 65535 * 64;
+ * FCD_ERR_ARG for a null pointer, a size < 1, S < 3, labels == NULL with P != 1, a threshold that is not finite and > 0, or
+ * an unknown tail. */
+#define FCD_TAIL_BOTH 0
+#define FCD_TAIL_GREATER 1
+#define FCD_TAIL_LESS 2
+int fcd_baseline_network_bits(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                              const uint8_t *labels, int64_t P, double threshold, int tail, uint32_t *bits, double *t,
+                              fcd_stream stream);
+/* The components: per row of bits (B, W) the connected components of the graph on the Nreg regions whose edges are the set
+ * bits; bits behind C in the last word are ignored.  A component's label is its smallest region, its extent its number of
+ * connections.  component (B, Nreg), nullable: the label of each region's component, -1 for a region without an edge.
+ * n_edges, max_extent, max_regions (B,): set bits, extent of the largest component, regions of the component with the most
+ * regions (0 where no bit is set).  One workgroup per row, the row in LDS; integer atomics only, so two calls agree exactly.
+ * One launch, no workspace.
+ * FCD_ERR_SHAPE for a non-triangular C; FCD_ERR_UNSUPPORTED for more than 1024 regions (a row of bits is 64 KB there);
+ * FCD_ERR_ARG for a null pointer other than component, or a size < 1. */
+int fcd_graph_components(fcd_ctx *ctx, const uint32_t *bits, int64_t B, int64_t C, int32_t *component, int32_t *n_edges,
+                         int32_t *max_extent, int32_t *max_regions, fcd_stream stream);
 
 /* ---- variational updates ------------------------------------------------------------------ */
 /* UnsharedRegionFit._update_lq_F, fit.py:157-174 (+ _eval_q_R_w 382-406). */
