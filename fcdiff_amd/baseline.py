@@ -37,6 +37,19 @@ def _has_nan(x):
     return bool(np.isnan(np.asarray(x, dtype=np.float64)).any())
 
 
+def _has_inf(x):
+    if hasattr(x, "detach"):
+        import torch
+        return bool(torch.isinf(x).any().item())
+    return bool(np.isinf(np.asarray(x, dtype=np.float64)).any())
+
+
+def _refuse_nonfinite(b, bt, who, tail):
+    """ValueError for a NaN or an infinite value in b or bt."""
+    if _has_nan(b) or _has_nan(bt) or _has_inf(b) or _has_inf(bt):
+        raise ValueError("%s: NaN or infinite value in b or bt; %s" % (who, tail))
+
+
 def _n_regions(C):
     N = int(round((np.sqrt(8.0 * C + 1.0) - 1.0) / 2.0)) + 1
     if C < 1 or N * (N - 1) // 2 != C:
@@ -106,15 +119,18 @@ def normative(b, bt, *, missing_data=False, z_threshold=3.0, return_z=False, ctx
 
     Returns a dict: msq, n_edges, n_over (N, U); msq0, n_edges0, n_over0 (N, H); max0 (H,); p_region, p_fwe (N, U);
     n_controls (C,); with return_z also z (C, U) and z0 (C, H).  NumPy arrays, or device tensors with as_numpy=False.
-    missing_data=False: a NaN anywhere is a ValueError; with it a NaN is unobserved.  At most 1024 controls
+    missing_data=False: a NaN or an infinite value anywhere is a ValueError; with it a NaN is unobserved and an infinite
+    value is still refused.  At most 1024 controls
     (NotImplementedError above); any number of patients, walked in chunks.  Sessions (C, U, K) are not provided.
     """
     import torch
     (C, N, H, U) = _check_pair(b, bt, "normative")
     if H > MAX_CONTROLS:
         raise NotImplementedError("normative: %d controls, at most %d" % (H, MAX_CONTROLS))
-    if not missing_data and (_has_nan(b) or _has_nan(bt)):
-        raise ValueError("normative: NaN in b or bt; pass missing_data=True to treat NaN as unobserved")
+    if not missing_data:
+        _refuse_nonfinite(b, bt, "normative", "pass missing_data=True to treat NaN as unobserved")
+    elif _has_inf(b) or _has_inf(bt):
+        raise ValueError("normative: infinite value in b or bt; missing_data=True admits NaN (unobserved) only")
     ctx = ctx if ctx is not None else _lib.Context()
     (bd, btd) = (_device_f64(b, ctx), _device_f64(bt, ctx))
     dev = ctx.device
@@ -195,7 +211,16 @@ def group_test(b, bt, n_perm=10000, *, seed=0, labels=None, ctx=None, as_numpy=T
     Returns a dict: t (C,), region (N,) observed; null_max_t (P,) = max_c |t|, null_max_region (P,) = max_n R;
     count_t (C,) int64 = #{p: |t_pc| >= |t_c|}, count_region (N,) int64 = #{p: R_pn >= R_n}; p_t, p_region =
     (1 + count) / (1 + P); p_fwe_t, p_fwe_region = the same against the maxima; labels (P, S) uint8 as used.
-    A NaN is a ValueError (missing data is not provided here); more than 1024 subjects a NotImplementedError.
+
+    Degenerate connections.  A connection whose S values are all equal (min == max, the rule of the covariate fit) is
+    constant: its centred values and Q_c are exactly 0.  Its t is NaN; it adds exactly 0 to every region sum, observed and
+    permuted, and enters no maximum; count_t[c] = 0 and p_t[c], p_fwe_t[c] are NaN.  A region whose connections are all
+    constant has region = 0, count_region = P and p_region = 1.  No other input gives a NaN, and no region sum ever sees a
+    negative term: where SS_w, a difference of two rounded numbers, is not > 0 with Q_c > 0 (complete separation of the two
+    groups), t^2 = +inf and t = +/-inf with the sign of A, and inf >= inf counts as IEEE arithmetic has it.
+
+    A NaN or an infinite value is a ValueError (missing data is not provided here); more than 1024 subjects a
+    NotImplementedError.
     Not provided: sessions, noise variances, Welch's t, cluster statistics.  The network-based statistic is network_test().
     """
     import torch
@@ -205,8 +230,7 @@ def group_test(b, bt, n_perm=10000, *, seed=0, labels=None, ctx=None, as_numpy=T
         raise NotImplementedError("group_test: %d subjects, at most %d" % (S, MAX_SUBJECTS))
     if S < 3:
         raise ValueError("group_test: %d subjects, a pooled variance needs 3" % S)
-    if _has_nan(b) or _has_nan(bt):
-        raise ValueError("group_test: NaN in b or bt; the data must be complete (missing data is not provided here)")
+    _refuse_nonfinite(b, bt, "group_test", "the data must be complete and finite (missing data is not provided here)")
     if labels is None:
         if int(n_perm) < 1:
             raise ValueError("group_test: n_perm must be >= 1")
@@ -243,11 +267,15 @@ def group_test(b, bt, n_perm=10000, *, seed=0, labels=None, ctx=None, as_numpy=T
 
 
 def group_pvalues(t, region, null_max_t, null_max_region, count_t, count_region):
-    """The host half of group_test(): p_t, p_region, p_fwe_t, p_fwe_region, each (1 + count) / (1 + P)."""
+    """
+    The host half of group_test(): p_t, p_region, p_fwe_t, p_fwe_region, each (1 + count) / (1 + P).  p_t and p_fwe_t are NaN
+    where t is NaN (a constant connection); an infinite value is counted by >= like any other (inf >= inf).
+    """
     P = null_max_t.shape[0]
-    return {"p_t": (1.0 + count_t) / (1.0 + P),
+    dead = np.isnan(t)
+    return {"p_t": np.where(dead, np.nan, (1.0 + count_t) / (1.0 + P)),
             "p_region": (1.0 + count_region) / (1.0 + P),
-            "p_fwe_t": (1.0 + _count_ge(null_max_t, np.abs(t))[0]) / (1.0 + P),
+            "p_fwe_t": np.where(dead, np.nan, (1.0 + _count_ge(null_max_t, np.abs(t))[0]) / (1.0 + P)),
             "p_fwe_region": (1.0 + _count_ge(null_max_region, region)[0]) / (1.0 + P)}
 
 
@@ -350,7 +378,9 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", seed=0, labels=
     connections, its label the smallest region in it; a region without a suprathreshold connection has label -1.  The
     family-wise error is controlled by the permutation law of the largest extent.  labels as in group_test(); a row equal
     to the observed labelling counts, and gives the observed bits exactly.  Labellings are walked in chunks; the results do
-    not depend on the chunk size and repeat exactly from call to call.
+    not depend on the chunk size and repeat exactly from call to call.  Degenerate connections as in group_test(): a constant
+    connection has t = NaN and is never suprathreshold, under any labelling; a completely separated one has t = +/-inf and is
+    suprathreshold on its side.
 
     Returns a dict: t (C,); edge_mask (C,) bool; component (N,) int64; component_label, component_edges, component_regions
     (K,) int64, the K >= 0 observed components by decreasing extent, then by label; null_max_extent, null_max_regions,
@@ -375,8 +405,7 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", seed=0, labels=
         raise ValueError("network_test: threshold must be finite and > 0, not %r" % (threshold,))
     if tail not in TAILS:
         raise ValueError("network_test: tail must be one of 'both', 'greater', 'less', not %r" % (tail,))
-    if _has_nan(b) or _has_nan(bt):
-        raise ValueError("network_test: NaN in b or bt; the data must be complete (missing data is not provided here)")
+    _refuse_nonfinite(b, bt, "network_test", "the data must be complete and finite (missing data is not provided here)")
     if labels is None:
         if int(n_perm) < 1:
             raise ValueError("network_test: n_perm must be >= 1")

@@ -25,6 +25,14 @@
 //                      strided: the same address formula, the lane's row offset is all that differs), the label bit
 //                      expanded to 0.0 / 1.0 in two VALU instructions, one v_mfma_f64_16x16x4_f64 per group.  Then
 //                      gp_t2: g = A^2 S/(U H), t^2 = g (S - 2) / (Q - g).
+//   Degenerate connections (pinned by tests/test_gpu_baseline_exact.py; no extra pass, no extra launch):
+//     constant         all S values equal (min == max, K_cov's rule; the centre kernel compares every value it reads with the
+//                      first): centred values and Q exactly 0.  t = NaN (group test and bits kernel), exactly 0 to every region
+//                      sum, observed and permuted, no part in any maximum, never suprathreshold, count_t = 0.  A region whose
+//                      connections are all constant has region = 0 and count_region = P.
+//     separated        SS_w = Q - g not > 0 with Q > 0 (Q - g is a difference of two rounded numbers): t^2 = +inf, t = +/-inf
+//                      with the sign of A; inf >= inf counts.  No other finite input gives a NaN, and no region sum ever sees
+//                      a negative term.
 //   group_observed_kernel   the observed labelling as one packed row: a wave per 16 consecutive connections, each connection
 //                      once; writes t and t^2.  group_observed_region_kernel adds t^2 over E(n) exactly as the permutation
 //                      kernel adds a row's (lane = column of the tile, tiles in order, then the butterfly).  A row of
@@ -231,13 +239,20 @@ __global__ __launch_bounds__(64 * GC_WAVES) void group_centre_kernel(const doubl
     if (c >= C) return;
     const int S = H + U;
     const double *__restrict__ br = b + c * H, *__restrict__ tr = bt + c * U;
+    const double x0 = br[0];
     double s = 0.0;
-    for (int i = lane; i < S; i += 64) s += i < H ? br[i] : tr[i - H];
+    bool same = true;
+    for (int i = lane; i < S; i += 64) {
+        const double v = i < H ? br[i] : tr[i - H];
+        s += v;
+        same = same && v == x0;
+    }
+    const bool constant = __ballot(!same) == 0ull;           // all S values equal: centred values and Q are exactly 0
     const double mean = fcd_wave_sum(s) / (double)S;
     double q = 0.0;
     for (int i = lane; i < 4 * KS; i += 64) {
         double xc = 0.0;
-        if (i < S) xc = (i < H ? br[i] : tr[i - H]) - mean;
+        if (i < S && !constant) xc = (i < H ? br[i] : tr[i - H]) - mean;
         q += xc * xc;
         XT[((int64_t)(i >> 2) * C + c) * 4 + (i & 3)] = xc;
     }
@@ -311,10 +326,15 @@ __device__ __forceinline__ void gp_tile_mma(const double *__restrict__ xp, int64
     }
 }
 
-// t^2 from the sum A over the labelled subjects: g = A^2 S/(U H), t^2 = g (S - 2) / (Q - g)
+// t^2 from the sum A over the labelled subjects: g = A^2 S/(U H), t^2 = g (S - 2) / (Q - g).  Q - g is a difference of two
+// rounded numbers: where it is not > 0 (complete separation) t^2 = +inf, never negative.  A constant connection (Q = 0) has
+// t^2 = NaN; its callers give it no part in any sum, maximum, count or bit.  Two compares and two selects per value.
 __device__ __forceinline__ double gp_t2(double A, double Qc, double kf, double dof) {
-    const double gq = A * A * kf;
-    return gq * dof / (Qc - gq);
+    const double gq = A * A * kf, den = Qc - gq;
+    double t2 = gq * dof / den;
+    if (!(den > 0.0)) t2 = __builtin_inf();
+    if (!(Qc > 0.0)) t2 = __builtin_nan("");
+    return t2;
 }
 
 // The observed labelling (the one row the pack kernel made of it): a wave per 16 consecutive connections, each connection
@@ -348,7 +368,7 @@ __global__ __launch_bounds__(64) void group_observed_region_kernel(const double 
         const bool valid = k < N - 1;
         int m;
         double t2 = t2obs[bl_edge(n, valid ? k : N - 2, m)];
-        if (!valid) t2 = 0.0;
+        if (!valid || t2 != t2) t2 = 0.0;                    // (NaN: a constant connection adds exactly 0)
         rs += t2;
     }
 #pragma unroll
@@ -382,14 +402,15 @@ __global__ __launch_bounds__(64 * GP_WAVES) void baseline_group_kernel(gp_args a
         gp_tile_mma<GP_G>(a.ws.XT + c * 4 + ks, C * 4, lw, nw, a.KS, acc);
         // result element r of group g: permutation (pg0 + g) 16 + ks + 4 r, connection k0 + col
         const double Qc = a.ws.Q[c], t2o = a.ws.t2obs[c];
-        const bool own = valid && k < n;
+        const bool live = valid && Qc > 0.0;                 // a constant connection: 0 to the sums, no maximum, no count
+        const bool own = live && k < n;
         int cnt = 0;
 #pragma unroll
         for (int g = 0; g < GP_G; ++g) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 double t2 = gp_t2(acc[g][r], Qc, a.kf, a.dof);
-                if (!valid) t2 = 0.0;
+                if (!live) t2 = 0.0;
                 rs[g][r] += t2;
                 mx[g][r] = fmax(mx[g][r], t2);
                 const int64_t p = (pg0 + g) * 16 + ks + 4 * r;

@@ -408,7 +408,10 @@ int fcd_baseline_normative(fcd_ctx *ctx, const double *b, const double *bt, int6
  * the last U subjects; it runs through the same tile product, the same t^2 and the same order of sums as the permutations,
  * so a row of labels equal to it gives its statistics bit for bit.
  * t (C,), region (Nreg,): observed.  null_max_t (P,) = max_c |t|, null_max_region (P,) = max_n R.  count_t (C,) = number of
- * rows with t^2 >= the observed t^2, count_region (Nreg,) = rows with R >= the observed R.  No (P, C) array exists anywhere:
+ * rows with t^2 >= the observed t^2, count_region (Nreg,) = rows with R >= the observed R.
+ * A constant connection (all S values equal) has centred values and Q of exactly 0: t = NaN, exactly 0 to every R, no part in
+ * a maximum, count_t = 0, never a set bit below.  Where Q_c - g, a difference of two rounded numbers, is not > 0 with Q_c > 0,
+ * t^2 = +inf and t = +/-inf with the sign of A; inf >= inf counts.  No other finite input gives a NaN.  No (P, C) array exists anywhere:
  * the sums A are an fp64 MFMA product whose tiles are reduced in registers.  Seven launches; uses the context's workspace
  * (about 8 C S + 16 Nreg P bytes), grown on demand.
  * FCD_ERR_SHAPE for a non-triangular C; FCD_ERR_UNSUPPORTED for S > 1024 (the labels of a permutation are 8 words per lane)

@@ -119,14 +119,36 @@ def normative(b, bt, z_threshold=3.0):
             "n_over0": n_over0, "max0": max0, "p_region": p_region, "p_fwe": p_fwe, "n_controls": n_controls}
 
 
+def centre(X):
+    """Rows centred on their mean, and their sums of squares.  A constant row (min == max) is exactly 0 with q = 0."""
+    (C, S) = X.shape
+    xc = np.zeros((C, S))
+    q = np.zeros(C)
+    for c in range(C):
+        if min(X[c]) == max(X[c]):
+            continue
+        m = sum(float(v) for v in X[c]) / S
+        for s in range(S):
+            xc[c, s] = X[c, s] - m
+            q[c] += xc[c, s] ** 2
+    return xc, q
+
+
 def _t_of(x, q, lab, S, U, H):
-    """Student's pooled-variance t of one centred row x (sum of squares q) under the labelling lab."""
+    """
+    Student's pooled-variance t of one centred row x (sum of squares q) under the labelling lab.  NaN for a constant row
+    (q = 0); +/-inf with the sign of A where SS_w, a difference of two rounded numbers, is not > 0.
+    """
+    if q == 0.0:
+        return math.nan
     A = 0.0
     for s in range(S):
         if lab[s]:
             A += x[s]
     k = S / (U * H)
     ss_w = q - A * A * k
+    if not ss_w > 0.0:
+        return math.copysign(math.inf, A)
     return A * k / math.sqrt(ss_w / (S - 2) * k)
 
 
@@ -139,18 +161,13 @@ def group_test(b, bt, labels):
     P = labels.shape[0]
     X = np.concatenate([b, bt], axis=1)
     E = edges_of(N)
-    xc = np.zeros((C, S))
-    q = np.zeros(C)
-    for c in range(C):
-        m = sum(float(v) for v in X[c]) / S
-        for s in range(S):
-            xc[c, s] = X[c, s] - m
-            q[c] += xc[c, s] ** 2
+    (xc, q) = centre(X)
     observed = [0] * H + [1] * U
+    live = q != 0.0                                              # a constant connection: t NaN, no part in any sum, maximum or count
 
     def stats(lab):
         t = np.array([_t_of(xc[c], q[c], lab, S, U, H) for c in range(C)])
-        R = np.array([sum(t[c] ** 2 for c in E[n]) for n in range(N)])
+        R = np.array([sum(t[c] ** 2 for c in E[n] if live[c]) for n in range(N)])
         return t, R
 
     (t, region) = stats(observed)
@@ -158,13 +175,16 @@ def group_test(b, bt, labels):
     Rp = np.zeros((P, N))
     for p in range(P):
         (tp[p], Rp[p]) = stats(labels[p])
-    null_max_t = np.abs(tp).max(axis=1)
+    null_max_t = np.array([max([0.0] + [abs(tp[p, c]) for c in range(C) if live[c]]) for p in range(P)])
     null_max_region = Rp.max(axis=1)
-    count_t = np.array([sum(1 for p in range(P) if abs(tp[p, c]) >= abs(t[c])) for c in range(C)], dtype=np.int64)
+    count_t = np.array([sum(1 for p in range(P) if live[c] and abs(tp[p, c]) >= abs(t[c])) for c in range(C)], dtype=np.int64)
     count_region = np.array([sum(1 for p in range(P) if Rp[p, n] >= region[n]) for n in range(N)], dtype=np.int64)
+    dead = np.isnan(t)
     return {"t": t, "region": region, "null_max_t": null_max_t, "null_max_region": null_max_region, "count_t": count_t,
-            "count_region": count_region, "p_t": (1.0 + count_t) / (1.0 + P), "p_region": (1.0 + count_region) / (1.0 + P),
-            "p_fwe_t": np.array([(1.0 + sum(1 for v in null_max_t if v >= abs(t[c]))) / (1.0 + P) for c in range(C)]),
+            "count_region": count_region, "p_t": np.where(dead, np.nan, (1.0 + count_t) / (1.0 + P)),
+            "p_region": (1.0 + count_region) / (1.0 + P),
+            "p_fwe_t": np.array([math.nan if dead[c] else (1.0 + sum(1 for v in null_max_t if v >= abs(t[c]))) / (1.0 + P)
+                                 for c in range(C)]),
             "p_fwe_region": np.array([(1.0 + sum(1 for v in null_max_region if v >= region[n])) / (1.0 + P) for n in range(N)]),
             "null_t": tp, "null_region": Rp}
 

@@ -55,13 +55,7 @@ def group_t(b, bt, labels):
     U = bt.shape[1]
     S = H + U
     X = np.concatenate([b, bt], axis=1)
-    xc = np.zeros((C, S))
-    q = np.zeros(C)
-    for c in range(C):
-        m = sum(float(v) for v in X[c]) / S
-        for s in range(S):
-            xc[c, s] = X[c, s] - m
-            q[c] += xc[c, s] ** 2
+    (xc, q) = BR.centre(X)
     observed = [0] * H + [1] * U
     t = np.array([BR._t_of(xc[c], q[c], observed, S, U, H) for c in range(C)])
     tp = np.array([[BR._t_of(xc[c], q[c], lab, S, U, H) for c in range(C)] for lab in labels]).reshape(len(labels), C)
