@@ -145,6 +145,7 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->ws_bytes = 0;
     ctx->log_tab = nullptr;
     ctx->dev_err = nullptr;
+    ctx->f_sure_hint = nullptr;
     ctx->fsq = nullptr;
     ctx->fsq_bytes = 0;
     ctx->frec = nullptr;
@@ -198,13 +199,14 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->knobs.r_poll_limit = 0;        // test hooks: through fcd_ctx_set_knob only, never from the environment
     ctx->knobs.r_withhold = 0;
     ctx->knobs.f_records = 0;           // (A/B runs and tests only)
+    ctx->knobs.f_sure = 0;
     ctx->knobs.tally_in_r = (int)knob_env("FCD_TALLY_IN_R");
     ctx->knobs.r_keep_words = (int)knob_env("FCD_R_KEEP_WORDS");
     ctx->r_form_last = 0;
     ctx->n_pack = 0;
     ctx->n_pack_tally = 0;
     ctx->n_r_tally = 0;
-    ctx->n_frec_pass = ctx->n_frec_build = 0;
+    ctx->n_frec_pass = ctx->n_frec_build = ctx->n_fsure_pass = 0;
     int rc = fcd_ws_reserve(ctx, 1u << 20);
     if (rc == FCD_OK) {
         void *pin = nullptr;
@@ -212,10 +214,17 @@ int fcd_ctx_create(fcd_ctx **out) {
         if (rc == FCD_OK) {
             ctx->dev_err = (volatile unsigned *)pin;
             *ctx->dev_err = 0u;
+            rc = (int)hipHostMalloc(&pin, sizeof(unsigned), hipHostMallocDefault);
+        }
+        if (rc == FCD_OK) {
+            ctx->f_sure_hint = (volatile unsigned *)pin;
+            *ctx->f_sure_hint = 0u;         // (build numbers start at 1)
         }
     }
     if (rc) {
         if (ctx->ws) (void)hipFree(ctx->ws);
+        if (ctx->dev_err) (void)hipHostFree((void *)ctx->dev_err);
+        if (ctx->f_sure_hint) (void)hipHostFree((void *)ctx->f_sure_hint);
         delete ctx;
         return rc;
     }
@@ -252,6 +261,7 @@ int fcd_ctx_destroy(fcd_ctx *ctx) {
     if (ctx->ws) e = hipFree(ctx->ws);
     if (ctx->log_tab) (void)hipFree(ctx->log_tab);
     if (ctx->dev_err) (void)hipHostFree((void *)ctx->dev_err);
+    if (ctx->f_sure_hint) (void)hipHostFree((void *)ctx->f_sure_hint);
     if (ctx->fsq) (void)hipFree(ctx->fsq);
     if (ctx->frec) (void)hipFree(ctx->frec);
     if (ctx->noise_rec) (void)hipFree(ctx->noise_rec);
@@ -306,6 +316,7 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value) {
     else if (!strcmp(name, "f_form")) k.f_form = (int)value;
     else if (!strcmp(name, "f_pack")) k.f_pack = (int)value;
     else if (!strcmp(name, "f_records")) k.f_records = (int)value;
+    else if (!strcmp(name, "f_sure")) k.f_sure = (int)value;
     else if (!strcmp(name, "corr_form")) k.corr_form = (int)value;
     else if (!strcmp(name, "tally_in_r")) k.tally_in_r = (int)value;
     else if (!strcmp(name, "r_keep_words")) k.r_keep_words = (int)value;
@@ -347,15 +358,16 @@ int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out) {
     else if (!strcmp(name, "f_rec_builds")) *out = ctx->n_frec_build;
     else if (!strcmp(name, "f_rec_bytes")) *out = (int64_t)ctx->frec_bytes;
     else if (!strcmp(name, "f_rec_min_sweeps")) *out = F_REC_MIN_SWEEPS;
+    else if (!strcmp(name, "f_sure_passes")) *out = ctx->n_fsure_pass;
     else if (!strcmp(name, "pipe_grid")) *out = ctx->pipe_grid;
     else if (!strcmp(name, "pipe_capacity")) *out = ctx->pipe_capacity;
     else if (!strcmp(name, "comm_world")) *out = ctx->comm ? ctx->comm_world : 0;
     else if (!strcmp(name, "dev_err")) *out = ctx->dev_err ? (int64_t)*ctx->dev_err : 0;
-    else if (!strcmp(name, "f_repeats") || !strcmp(name, "r_exact_rows")) {
+    else if (!strcmp(name, "f_repeats") || !strcmp(name, "r_exact_rows") || !strcmp(name, "f_sure_tiles") || !strcmp(name, "f_sure_fallbacks")) {
         // event counters kept on the device (a synchronising read: diagnostics only)
         unsigned long long v[8];
         FCD_HIP_TRY(hipMemcpy(v, ctx->dbg, sizeof(v), hipMemcpyDeviceToHost));
-        *out = (int64_t)v[name[0] == 'f' ? 0 : 1];
+        *out = (int64_t)v[name[0] == 'r' ? 1 : !strcmp(name, "f_repeats") ? 0 : !strcmp(name, "f_sure_tiles") ? 2 : 3];
     }
     else return FCD_ERR_ARG;
     return FCD_OK;

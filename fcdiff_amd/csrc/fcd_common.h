@@ -36,6 +36,7 @@ struct fcd_knobs {
     int f_pack;        // 1: the r pass's packing launch in every sweep (default: only where the f pass cannot write the packed f words)
     int f_records;     // pair-tile f pass reads pair records made once per call: 0 = in calls of at least F_REC_MIN_SWEEPS pair-tile
                        // sweeps, 1 = never (every tile builds its own), 2 = whenever the pair-tile form runs
+    int f_sure;        // 1: never the decided-tile path of the pair-tile f pass (A/B runs and tests; default: where the table has such tiles)
     int tally_in_r;    // f half of the tally inside the pipelined r pass (its in-order workgroups, before their first block): 0 = where
                        // a wave's rounds are at most R_TALLY_MAX_ROUNDS, 1 = never (the tally after the pass counts f), 2 = wherever
                        // the form allows (16-wave in-order workgroups)
@@ -45,8 +46,8 @@ struct fcd_knobs {
 
 // kernels whose dynamic-LDS limit is raised with hipFuncSetAttribute: done once per (kernel, size) and remembered here
 enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA_F_PAIR_T = FCD_KA_F_PAIR + 4,
-       FCD_KA_F_PAIR_R = FCD_KA_F_PAIR_T + 4,
-       FCD_KA_F_PAIR_BIG = FCD_KA_F_PAIR_R + 4, FCD_KA_R_STEP = FCD_KA_F_PAIR_BIG + 4, FCD_KA_R_PIPE = FCD_KA_R_STEP + 4, FCD_KA_CORR = FCD_KA_R_PIPE + 4, FCD_KA_COMPONENTS = FCD_KA_CORR + 1,
+       FCD_KA_F_PAIR_R = FCD_KA_F_PAIR_T + 4, FCD_KA_F_PAIR_S = FCD_KA_F_PAIR_R + 4,
+       FCD_KA_F_PAIR_BIG = FCD_KA_F_PAIR_S + 4, FCD_KA_R_STEP = FCD_KA_F_PAIR_BIG + 4, FCD_KA_R_PIPE = FCD_KA_R_STEP + 4, FCD_KA_CORR = FCD_KA_R_PIPE + 4, FCD_KA_COMPONENTS = FCD_KA_CORR + 1,
        FCD_KA_N = FCD_KA_COMPONENTS + 1 };
 
 #define FCD_NAN_SLOTS 256
@@ -84,6 +85,9 @@ struct fcd_ctx {
     long long n_r_tally;           // pipelined r pass launches that carried it (fcd_ctx_stat "tally_f_in_r")
     long long n_frec_pass;         // f passes that read prebuilt pair records (fcd_ctx_stat "f_rec_passes")
     long long n_frec_build;        // launches of the kernel that builds them (fcd_ctx_stat "f_rec_builds")
+    long long n_fsure_pass;        // f passes that ran the kernel with the decided-tile path (fcd_ctx_stat "f_sure_passes")
+    volatile unsigned *f_sure_hint;    // pinned host word: the records kernel of build number n_frec_build leaves twice that number
+                                       // here, + 1 where some tile of its table has every edge decided (FCD_F_SURE_DRIFT nats in hand)
     void *log_tab;     // K_lik tables (fcd_fastmath.h): 64 x 2^(-j/64), 512 x {1/m_i, log m_i} (device, 8.5 KiB)
     volatile unsigned *dev_err;   // pinned host word: error word of the one-launch r pass, copied back after each pass
     void *acc;         // 8 x uint64, zero between launches: the tally's pooled sums [0..3] and its ticket [4]
@@ -93,7 +97,9 @@ struct fcd_ctx {
     int comm_world, comm_rank;
     void *pool_counts; // 8 x int64 (device): the counts vector the all-reduce works on in place
     void *dbg;         // 8 x uint64 event counters (fcd_ctx_stat): [0] waves of the f pass that repeated an edge's sums in fp64,
-                       // [1] rows of the r pass's in-order role decided on the exact path; never reset by the library
+                       // [1] rows of the r pass's in-order role decided on the exact path, [2] workgroups of the pair-tile f pass
+                       // that took the decided-tile path ("f_sure_tiles"), [3] decided ones its vote sent back
+                       // ("f_sure_fallbacks"), never reset by the library; [4] the record build's word "some tile is decided", zero between calls
     void *corr_tickets;            // K_corr: one ticket per subject, zero between launches (the last taker resets it)
     size_t corr_tickets_n;
     void *fsq;         // square copy of the f state [w][n][m][lane] the sweep loop keeps between its f and r pass
@@ -606,8 +612,44 @@ constexpr int F_REC_PIECES = 6;
 struct fcd_f_edge_rec {
     double d1, d2;     // S_B[c][1] - S_B[c][0], S_B[c][2] - S_B[c][0]
     float a;           // bound of the sum over the patients of the largest |entry| of the row (the tile's B_e)
-    float pad[3];
+    float b[6];        // lo1, hi1, lo2, hi2, lo12, hi12 of fcd_f_edge_mode, rounded outward; NaN where a table entry is not finite
+    float pad;
 };
+// An edge whose draw the tables decide.  The f pass's exact log-odds against type 0 are b_k = c_k + sum_u d_k(z_u), k = 1, 2:
+// c_k = (ln gamma_k - ln gamma_0) + S_B[c][k] - S_B[c][0], (d_1, d_2)(z) = lMf[c][u][z][:], z_u in {typical, both, discordant}
+// set by the r state.  With, over the patients,
+//   lo1 = sum_u min_z d_1,  hi1 = sum_u max_z d_1,  lo2, hi2 likewise,  lo12 = sum_u min_z (d_1 - d_2),  hi12 = sum_u max_z (d_1 - d_2)
+// (fp64, rounded outward: gibbs_f_records_kernel), type m leads the other two by more than T in EVERY r state if
+//   m = 0:  -(c1 + hi1) > T  and  -(c2 + hi2) > T
+//   m = 1:    c1 + lo1  > T  and    (c1 - c2) + lo12  > T
+//   m = 2:    c2 + lo2  > T  and  -((c1 - c2) + hi12) > T
+// -> m, or -1 (no such type; every comparison is false for a NaN, and an infinite c_k makes delta infinite).
+// T = FCD_F_SURE_T = 16.  Let L be the exact lead, delta = fcd_f32_sum_err + fcd_f32_offset_err the edge's bound on |bf_k - b_k| of
+// the term loop's fp32 sums, M = max |bf_k| <= cm + a + delta, u = 2^-24.  (1) L > 15: fcd_draw_f_sure's argument holds for the
+// exact sums, fcd_draw_f returns the argmax for x in [1e-6, 1 - 1e-6].  (2) fcd_draw_f_sure computes (mx - mid) - eta from the
+// fp32 sums: the lead among (0, bf1, bf2) is >= L - 2 delta; mid = ((bf1 + bf2) - mx) - mn rounds three times (2uM, 3uM, uM),
+// mx - mid and - eta once each (2uM, u(2M + eta)): together < 10.1 uM <= 6.1e-7 (cm + a + delta) <= 5.1 delta, because
+// delta >= fcd_f32_offset_err = 1.2e-7 (cm + a).  So the test passes, with the fp32 argmax the exact one, where
+// L > 15.01 + eta + 7.1 delta.  An edge counts only with delta <= FCD_F_SURE_DELTA_CAP = 1/32, which caps
+// eta = fcd_draw_f_eta(delta) <= expm1(1/16) 1.001 + 2e-5 < 0.065: 15.01 + 0.065 + 0.222 = 15.30.  The rest of T covers the
+// fp64 roundings of c_k + bound (1.2e-16 relative, of magnitudes that keep delta under its cap: < 1e-10).
+// tests/test_f_sure_rule.py restates the rule in NumPy.
+#define FCD_F_SURE_T 16.0
+#define FCD_F_SURE_DELTA_CAP 0.03125f
+#define FCD_F_SURE_DRIFT 6.0      // the table's hint (fcd_ctx::f_sure_hint) uses T - this: gamma moves with the M-steps of a call
+__host__ __device__ static inline int fcd_f_edge_mode(double c1, double c2, const float *b, float delta, double T) {
+    if (!(delta <= FCD_F_SURE_DELTA_CAP)) return -1;
+    const double c12 = c1 - c2;
+    if (-(c1 + (double)b[1]) > T && -(c2 + (double)b[3]) > T) return 0;
+    if (c1 + (double)b[0] > T && c12 + (double)b[4] > T) return 1;
+    if (c2 + (double)b[2] > T && -(c12 + (double)b[5]) > T) return 2;
+    return -1;
+}
+// (c1, c2, delta) of an edge from its record and the sweep's hyper, as the pair-tile kernel makes its constants
+__host__ __device__ static inline float fcd_f_edge_delta(double c1, double c2, int NPAIR, float a) {
+    const float cm = fmaxf((float)fabs(c1), (float)fabs(c2)) * 1.0000002f;
+    return fcd_f32_sum_err(NPAIR, a) + fcd_f32_offset_err(cm, a);
+}
 constexpr size_t F_REC_CAP = (size_t)256 << 20;     // no record table above this many bytes: the tiles build their own
 // A call of the sweep loop makes the records where it has at least this many pair-tile sweeps: the build launch costs 27.4 us
 // at cfg3 and a pair-tile f pass on its records runs 6.75 us shorter (108.96 -> 102.20 us; kernel trace of the timed loop,
@@ -657,6 +699,7 @@ struct fcd_sweep_step {
     const fcd_tally_f *tally_f;    // r pass: the f half of the tally to carry in the packing launch or in the pipelined launch, or
     bool tally_f_done;             // nullptr ... and whether one of them did (out)
     bool r_flip;                   // r pass: the two r-word buffers of the plan have swapped roles (r_S lies at pl.r_Sn, r_Sn at pl.r_S)
+    bool f_sure;                   // f pass (f_rec): some tile of the call's table has all its edges decided (fcd_ctx::f_sure_hint)
 };
 int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step &st);   // fcd_gibbs.hip
 int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st);         // fcd_gibbs_r.hip

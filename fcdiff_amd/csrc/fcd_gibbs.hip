@@ -11,6 +11,7 @@
 // Algorithmic bytes per sweep of G chains: 2*72*C*U (lM once per pass) + 24*C +
 // G*(2*C + 3*Nreg*U) of state.  Arithmetic: 3 (f) + 4 (r) fp64 adds per (edge, patient, chain).
 #include "fcd_common.h"
+#include <chrono>
 
 namespace {
 
@@ -373,10 +374,58 @@ __device__ __forceinline__ fpt_tile fpt_locate(int t, int Nreg) {
     return T;
 }
 
+// The r pass's f words of a pair-aligned tile from its draws kt (2 bits per edge), for this lane's chain of chain word w.
+__device__ __forceinline__ void fpt_write_f_words(const fpt_tile &T, uint32_t kt, int w, int lane, uint2 *__restrict__ f_S, int Nreg, int NBLK) {
+    // the r pass's f words (pack_f_item's bytes, (3 f(n, m) + f(n, m+1)) << 2; 0 for m == n and m >= Nreg).  K(r, j):
+    // f of (n0 + r, mb + j) -- drawn here, 0 on the diagonal and for a row beyond Nreg, and (n0, n0 + 1) is the edge
+    // (n0 + 1, n0) of row 1.  Every byte of f_S is written once per pass: the pairs of a row below its own row pair by the
+    // row halves, the diagonal pair (n0, n0 + 1) by the row halves of the tile that holds it, the pairs above by the
+    // column halves, the pairs beyond Nreg by the zeros of the diagonal tiles.
+    auto K = [&](int r, int j) -> uint32_t {
+        if (r == 0 && T.mb + j == T.n0 + 1) return (kt >> (2 * (FT_W + j - 1))) & 3u;
+        return (kt >> (2 * (r * FT_W + j))) & 3u;
+    };
+    const int ncol = min(FT_W, T.n0 + 2 - T.mb);           // columns of the tile (FT_W, or 2 on the diagonal)
+    const int b = T.mb / R_NB, p0 = (T.mb % R_NB) / 2;
+    uint8_t *fs = reinterpret_cast<uint8_t *>(f_S + (int64_t)w * Nreg * NBLK * 64 + lane);     // + ((n * NBLK + b) * 64) * 8
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        if (T.n0 + r >= Nreg) break;
+        uint8_t *row = fs + (int64_t)((T.n0 + r) * NBLK + b) * 512 + p0;
+        uint32_t v = 0;
+#pragma unroll
+        for (int q = 0; q < FT_W / 2; ++q) v |= ((3u * K(r, 2 * q) + K(r, 2 * q + 1)) << 2) << (8 * q);
+        if (ncol == FT_W) *reinterpret_cast<uint16_t *>(row) = (uint16_t)v;     // (FT_W = 4: two bytes, 2-aligned)
+        else *row = (uint8_t)v;
+    }
+    {
+        const int bn = T.n0 / R_NB, pn = (T.n0 % R_NB) / 2;
+#pragma unroll
+        for (int j = 0; j < FT_W; ++j)
+            if (T.mb + j < T.n0) fs[(int64_t)((T.mb + j) * NBLK + bn) * 512 + pn] = (uint8_t)((3u * K(0, j) + K(1, j)) << 2);
+    }
+    if (ncol < FT_W || T.mb + FT_W == T.n0 + 2) {
+        // the diagonal tile of the row pair: the pairs of its rows beyond Nreg (last block)
+        const int pe = (Nreg + 1) / 2 - (R_NB / 2) * (NBLK - 1);
+        for (int r = 0; r < 2; ++r) {
+            if (T.n0 + r >= Nreg) break;
+            uint8_t *row = fs + (int64_t)((T.n0 + r) * NBLK + NBLK - 1) * 512;
+            for (int p = pe; p < R_NB / 2; ++p) row[p] = 0;
+        }
+    }
+}
+
 // PRE (pair-aligned tiles only): the records and the edges' bounds come from the table gibbs_f_records_kernel made for this call
 // (frec: per tile NPAIR x FP_EC records of F_REC_PIECES 16-byte pieces, then one fcd_f_edge_rec per edge id) -- one copy
 // into LDS and ONE barrier instead of staging, barrier, build, barrier; no fp64 rows in LDS.
-template <int NW16, bool PT, bool PRE = false>
+// SURE (with PRE; the host takes it where the table has such tiles, margin <= 1 and knob f_sure is not 1): a tile whose
+// present edges are all decided by the table's bounds and this sweep's hyper (fcd_f_edge_mode) draws no sums.  The parent
+// path would have taken fcd_draw_f_sure on every such edge, in every lane whose uniform lies in its range, so the waves draw
+// the tile's Philox words as the edge loop does and test that range only; one vote of the workgroup (a word per wave behind
+// the edge constants, one barrier) and, if no lane anywhere is out of range, k = the edge's mode: no slot words, no record
+// copy, no term loops.  Otherwise the WHOLE tile runs the code below unchanged -- same draws, same repeats.  The rule's
+// inputs and instructions are the same in all waves of a workgroup (w >= GW included), so all of them meet the barrier or none.
+template <int NW16, bool PT, bool PRE = false, bool SURE = false>
 __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__restrict__ S_B, const double *__restrict__ lMf,
                                                             const double *__restrict__ hyper, uint8_t *__restrict__ f_state,
                                                             const uint32_t *__restrict__ r_U, int Nreg, int U, int64_t C,
@@ -384,7 +433,8 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
                                                             uint2 *__restrict__ f_S, int NBLK, unsigned long long *__restrict__ dbg,
                                                             const char *__restrict__ frec) {
     static_assert(PT || !PRE, "prebuilt records are laid out by pair-aligned tile");
-    // pair records [NPAIR][FP_EC][16] float2 | per-edge constants [FP_EC] float4 | (not PRE) singles [FP_EC][U][3][2] double
+    static_assert(PRE || !SURE, "the edges' bounds are part of the prebuilt records");
+    // pair records [NPAIR][FP_EC][16] float2 | per-edge constants [FP_EC] float4 | (PRE) 16 vote words | (not PRE) singles [FP_EC][U][3][2] double
     extern __shared__ __attribute__((aligned(256))) double ptile[];
     const int NPAIR = (U + 1) >> 1;
     // the tile's edges: c0 + e, e < ne (consecutive ids); PT: edge e = (row e / FT_W, column e % FT_W), present where
@@ -403,6 +453,61 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
     [[maybe_unused]] const int trec = (int)blockIdx.x < 4096 ? (int)blockIdx.x : 4095;      // (diagnostic build: profiles/trace_f.py)
     FCD_TRACE(trec, 0);
     FCD_TRACE_VAL(trec, 7, (__builtin_amdgcn_s_getreg((31 << 11) | 20) << 16) | (__builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xffff));
+    if constexpr (SURE) {
+        // lane e < FP_EC of every wave: edge e's rule
+        const fcd_f_edge_rec *edge_c = reinterpret_cast<const fcd_f_edge_rec *>(frec + (size_t)gridDim.x * NPAIR * (FP_EC * F_REC_PIECES * 16));
+        const int le = lane & (FP_EC - 1);
+        const bool present = lane < FP_EC && has(le);
+        int mode = -1;
+        if (present) {
+            const fcd_f_edge_rec k = edge_c[cid(le)];
+            const double c1 = lg1 + k.d1, c2 = lg2 + k.d2;
+            mode = fcd_f_edge_mode(c1, c2, k.b, fcd_f_edge_delta(c1, c2, NPAIR, k.a), FCD_F_SURE_T);
+        }
+        const uint32_t pm = (uint32_t)__ballot(present), dm = (uint32_t)__ballot(mode >= 0);
+        if (pm != 0u && dm == pm) {           // (workgroup-uniform)
+            const uint32_t m1 = (uint32_t)__ballot(mode == 1), m2 = (uint32_t)__ballot(mode == 2);
+            bool out = false;               // this lane's uniform of some edge is outside fcd_draw_f_sure's range
+            if (w < GW) {
+                const uint32_t chain = chain0 + (uint32_t)w * 64u + lane;
+                fcd_u4 rnd = {0, 0, 0, 0};
+                int64_t rnd_blk = -1;
+#pragma unroll
+                for (int e = 0; e < FP_EC; ++e) {
+                    if (!has(e)) continue;
+                    const int64_t c = cid(e);
+                    if ((c >> 2) != rnd_blk) {
+                        rnd_blk = c >> 2;
+                        rnd = fcd_philox((uint32_t)rnd_blk, chain, sweep, FCD_KIND_F, (uint32_t)seed, (uint32_t)(seed >> 32));
+                    }
+                    const float xf = (float)fcd_word(rnd, (int)(c & 3)) * 2.3283064e-10f;
+                    out = out || !(xf > 1e-6f && xf < 0.999999f);
+                }
+            }
+            uint32_t *vote = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(edge_k) + FP_EC * 16);
+            const bool wave_out = __ballot(out) != 0ull;
+            if (lane == 0) vote[threadIdx.x >> 6] = wave_out ? 1u : 0u;
+            __syncthreads();
+            const bool back = __ballot(lane < (int)(blockDim.x >> 6) && vote[lane < 16 ? lane : 0] != 0u) != 0ull;
+            if (!back) {
+                if (threadIdx.x == 0) atomicAdd(dbg + 2, 1ull);
+                if (w >= GW) return;
+                uint32_t kt = 0;
+#pragma unroll
+                for (int e = 0; e < FP_EC; ++e) {
+                    if (!has(e)) continue;
+                    const uint32_t k = ((m1 >> e) & 1u) | (((m2 >> e) & 1u) << 1);
+                    (f_state + ((int64_t)w * C + cid(e)) * 64)[(uint32_t)lane] = (uint8_t)k;
+                    kt |= k << (2 * e);
+                }
+                if (f_S) fpt_write_f_words(T, kt, w, lane, f_S, Nreg, NBLK);
+                FCD_TRACE(trec, 3);
+                return;
+            }
+            // the vote words are read; the copy below writes other addresses, and its barrier comes before anything else
+            if (threadIdx.x == 0) atomicAdd(dbg + 3, 1ull);
+        }
+    }
     // the r words of the tile's edges: loaded before the barrier so their latency hides behind the staging.
     // Consecutive edges c = n(n-1)/2 + m share n: its words are fetched once per run, not once per edge.
     // Slot numbers (x_u, x_u+1, a_u, a_u+1) of 8 pairs of patients per word, for the edge at hand only: the words of
@@ -683,45 +788,7 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
 #endif
         }
     }
-    if (PT && f_S) {
-        // the r pass's f words (pack_f_item's bytes, (3 f(n, m) + f(n, m+1)) << 2; 0 for m == n and m >= Nreg).  K(r, j):
-        // f of (n0 + r, mb + j) -- drawn here, 0 on the diagonal and for a row beyond Nreg, and (n0, n0 + 1) is the edge
-        // (n0 + 1, n0) of row 1.  Every byte of f_S is written once per pass: the pairs of a row below its own row pair by the
-        // row halves, the diagonal pair (n0, n0 + 1) by the row halves of the tile that holds it, the pairs above by the
-        // column halves, the pairs beyond Nreg by the zeros of the diagonal tiles.
-        auto K = [&](int r, int j) -> uint32_t {
-            if (r == 0 && T.mb + j == T.n0 + 1) return (kt >> (2 * (FT_W + j - 1))) & 3u;
-            return (kt >> (2 * (r * FT_W + j))) & 3u;
-        };
-        const int ncol = min(FT_W, T.n0 + 2 - T.mb);           // columns of the tile (FT_W, or 2 on the diagonal)
-        const int b = T.mb / R_NB, p0 = (T.mb % R_NB) / 2;
-        uint8_t *fs = reinterpret_cast<uint8_t *>(f_S + (int64_t)w * Nreg * NBLK * 64 + lane);     // + ((n * NBLK + b) * 64) * 8
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            if (T.n0 + r >= Nreg) break;
-            uint8_t *row = fs + (int64_t)((T.n0 + r) * NBLK + b) * 512 + p0;
-            uint32_t v = 0;
-#pragma unroll
-            for (int q = 0; q < FT_W / 2; ++q) v |= ((3u * K(r, 2 * q) + K(r, 2 * q + 1)) << 2) << (8 * q);
-            if (ncol == FT_W) *reinterpret_cast<uint16_t *>(row) = (uint16_t)v;     // (FT_W = 4: two bytes, 2-aligned)
-            else *row = (uint8_t)v;
-        }
-        {
-            const int bn = T.n0 / R_NB, pn = (T.n0 % R_NB) / 2;
-#pragma unroll
-            for (int j = 0; j < FT_W; ++j)
-                if (T.mb + j < T.n0) fs[(int64_t)((T.mb + j) * NBLK + bn) * 512 + pn] = (uint8_t)((3u * K(0, j) + K(1, j)) << 2);
-        }
-        if (ncol < FT_W || T.mb + FT_W == T.n0 + 2) {
-            // the diagonal tile of the row pair: the pairs of its rows beyond Nreg (last block)
-            const int pe = (Nreg + 1) / 2 - (R_NB / 2) * (NBLK - 1);
-            for (int r = 0; r < 2; ++r) {
-                if (T.n0 + r >= Nreg) break;
-                uint8_t *row = fs + (int64_t)((T.n0 + r) * NBLK + NBLK - 1) * 512;
-                for (int p = pe; p < R_NB / 2; ++p) row[p] = 0;
-            }
-        }
-    }
+    if (PT && f_S) fpt_write_f_words(T, kt, w, lane, f_S, Nreg, NBLK);
 #ifdef FCD_ABLATE
     FCD_TRACE_VAL(trec, 4, tr_terms);
     FCD_TRACE_VAL(trec, 5, tr_draw);
@@ -734,8 +801,12 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
 // the sweep loop: this kernel makes it for every tile of the call at once -- workgroup = tile, the same sums, the same bound
 // (wave e = edge e, lane = patient, fp_edge_bound) -- and gibbs_f_pair_kernel<.., true, true> copies it.  Layout: see PRE.
 // Pieces of edges the tile does not hold (past the diagonal) are never written and never read.
+// It also leaves every edge's bounds for the rule of decided edges (fcd_f_edge_mode) and, where some tile has all its edges
+// decided at the call's starting hyper with FCD_F_SURE_DRIFT nats in hand, a 1 in *any_tile: a table without such a tile is
+// read by the kernel without the decided-tile path.
 __global__ __launch_bounds__(64 * FP_EC) void gibbs_f_records_kernel(const double *__restrict__ S_B, const double *__restrict__ lMf,
-                                                                     int Nreg, int U, char *__restrict__ frec) {
+                                                                     const double *__restrict__ hyper, int Nreg, int U,
+                                                                     char *__restrict__ frec, unsigned *__restrict__ any_tile) {
     const int NPAIR = (U + 1) >> 1;
     const fpt_tile T = fpt_locate((int)blockIdx.x, Nreg);
     auto has = [&](int e) -> bool { return (e % FT_W) < (e < FT_W ? T.cnt0 : T.cnt1); };
@@ -758,17 +829,60 @@ __global__ __launch_bounds__(64 * FP_EC) void gibbs_f_records_kernel(const doubl
             if (s2 != 5 && s2 != 7) dst4[(pr * FP_EC + e) * F_REC_PIECES + (s2 < 5 ? s2 : 5)] = fp_pair_piece(A, B, s2);
     }
     const int e = (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (!has(e)) return;         // (wave-uniform)
-    const int64_t c = cid(e);
-    const float a = fp_edge_bound(reinterpret_cast<const double2 *>(lMf + c * U * 6) + (lane < U ? lane : 0) * 3, lane < U);
-    if (lane == 0) {
-        fcd_f_edge_rec k = {};
-        const double sb0 = S_B[c * 3 + 0];
-        k.d1 = S_B[c * 3 + 1] - sb0;
-        k.d2 = S_B[c * 3 + 2] - sb0;
-        k.a = a;
-        reinterpret_cast<fcd_f_edge_rec *>(frec + (size_t)gridDim.x * NPAIR * (FP_EC * F_REC_PIECES * 16))[c] = k;
+    __shared__ int open_edges;       // edges of the tile that the hint's rule leaves open
+    if (threadIdx.x == 0) open_edges = 0;
+    __syncthreads();
+    if (has(e)) {                // (wave-uniform)
+        const int64_t c = cid(e);
+        const double2 *su = reinterpret_cast<const double2 *>(lMf + c * U * 6) + (lane < U ? lane : 0) * 3;
+        const float a = fp_edge_bound(su, lane < U);
+        // the six bounds of fcd_f_edge_mode: this patient's smallest and largest d_1, d_2 and d_1 - d_2 over the three cases
+        double b[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        bool finite = true;
+        if (lane < U) {
+#pragma unroll
+            for (int l = 0; l < 3; ++l) {
+                const double v[3] = {su[l].x, su[l].y, su[l].x - su[l].y};
+                finite = finite && isfinite(v[0]) && isfinite(v[1]);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    b[2 * q] = l == 0 ? v[q] : fmin(b[2 * q], v[q]);
+                    b[2 * q + 1] = l == 0 ? v[q] : fmax(b[2 * q + 1], v[q]);
+                }
+            }
+        }
+        finite = __ballot(!finite) == 0ull;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) b[q] = fcd_wave_sum(b[q]);
+        if (lane == 0) {
+            fcd_f_edge_rec k = {};
+            const double sb0 = S_B[c * 3 + 0];
+            k.d1 = S_B[c * 3 + 1] - sb0;
+            k.d2 = S_B[c * 3 + 2] - sb0;
+            k.a = a;
+            // outward: the wave's sums of up to 64 terms are off by at most 6 x 2^-53 x sum |term| <= 1.4e-15 a (|d_1 - d_2| <= twice
+            // the row's largest |entry|, and its own rounding), then the conversions round away from the interval
+            const double slack = 8e-15 * (double)a;
+#pragma unroll
+            for (int q = 0; q < 6; ++q)
+                k.b[q] = !finite ? __builtin_nanf("") : (q & 1) ? __double2float_ru(b[q] + slack) : __double2float_rd(b[q] - slack);
+            reinterpret_cast<fcd_f_edge_rec *>(frec + (size_t)gridDim.x * NPAIR * (FP_EC * F_REC_PIECES * 16))[c] = k;
+            const double c1 = (hyper[FCD_H_LNGAMMA + 1] - hyper[FCD_H_LNGAMMA + 0]) + k.d1;
+            const double c2 = (hyper[FCD_H_LNGAMMA + 2] - hyper[FCD_H_LNGAMMA + 0]) + k.d2;
+            if (fcd_f_edge_mode(c1, c2, k.b, fcd_f_edge_delta(c1, c2, NPAIR, a), FCD_F_SURE_T - FCD_F_SURE_DRIFT) < 0) open_edges = 1;
+        }
     }
+    __syncthreads();
+    // (every tile that has the property stores the same word: no atomic, no fence -- gibbs_f_hint_kernel reads it behind
+    // this launch)
+    if (threadIdx.x == 0 && !open_edges && (T.cnt0 > 0 || T.cnt1 > 0)) *any_tile = 1u;
+}
+// ... and hands it to the host: 2 build + any into the pinned word the sweep loop polls (written once, complete), the device
+// word cleared for the next build.
+__global__ void gibbs_f_hint_kernel(unsigned *__restrict__ any_tile, volatile unsigned *hint, unsigned build) {
+    const unsigned any = *any_tile != 0u ? 1u : 0u;
+    *any_tile = 0u;
+    __hip_atomic_store(const_cast<unsigned *>(hint), 2u * build + any, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1390,7 +1504,15 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step
     } while (0)
 #define FCD_PX (unsigned long long *)ctx->dbg
 #define FCD_PT f_S, NBLK, (unsigned long long *)ctx->dbg, (const char *)st.f_rec
-        if (form == FCD_F_PAIR && pt && st.f_rec) {
+        if (form == FCD_F_PAIR && pt && st.f_rec && st.f_sure && !(margin > 1.f) && ctx->knobs.f_sure != 1) {
+            // (a table without decided tiles, the test hook f_tol and knob f_sure = 1 keep the kernel below)
+            if (pl.f_NW == 1) FCD_LAUNCH_F((gibbs_f_pair_kernel<1, true, true, true>), FCD_KA_F_PAIR_S + 0, FCD_PT);
+            else if (pl.f_NW == 2) FCD_LAUNCH_F((gibbs_f_pair_kernel<2, true, true, true>), FCD_KA_F_PAIR_S + 1, FCD_PT);
+            else if (pl.f_NW == 3) FCD_LAUNCH_F((gibbs_f_pair_kernel<3, true, true, true>), FCD_KA_F_PAIR_S + 2, FCD_PT);
+            else FCD_LAUNCH_F((gibbs_f_pair_kernel<4, true, true, true>), FCD_KA_F_PAIR_S + 3, FCD_PT);
+            ctx->n_frec_pass += 1;
+            ctx->n_fsure_pass += 1;
+        } else if (form == FCD_F_PAIR && pt && st.f_rec) {
             if (pl.f_NW == 1) FCD_LAUNCH_F((gibbs_f_pair_kernel<1, true, true>), FCD_KA_F_PAIR_R + 0, FCD_PT);
             else if (pl.f_NW == 2) FCD_LAUNCH_F((gibbs_f_pair_kernel<2, true, true>), FCD_KA_F_PAIR_R + 1, FCD_PT);
             else if (pl.f_NW == 3) FCD_LAUNCH_F((gibbs_f_pair_kernel<3, true, true>), FCD_KA_F_PAIR_R + 2, FCD_PT);
@@ -1554,6 +1676,24 @@ static const struct {
 // packed_ok, the cleared marks of the next r pass (whose r words are the ones this pass wrote); its f half rides in the packing
 // launch or in the pipelined r pass where they take it.  hyper_m: what the M-step writes (nullptr when mstep_every == 0); acc_mask: the
 // slots of the context's sweep accumulators to add to (bit k = slot k).
+// The hint of the record build just queued (gibbs_f_hint_kernel writes 2 build + any): polled in the
+// pinned word for as long as a build can reasonably take, then behind a synchronisation of the stream.
+static int fcd_f_sure_hint_wait(fcd_ctx *ctx, hipStream_t s, bool &any) {
+    const unsigned build = (unsigned)(ctx->n_frec_build & 0x3fffffff);
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned v = *ctx->f_sure_hint;
+    for (unsigned spin = 1; (v >> 1) != build; ++spin, v = *ctx->f_sure_hint) {
+        if ((spin & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
+            FCD_HIP_TRY(hipStreamSynchronize(s));
+            v = *ctx->f_sure_hint;
+            if ((v >> 1) != build) return fcd_fail(ctx, FCD_ERR_DEVICE, "f pass: the record build left no hint");
+            break;
+        }
+    }
+    any = (v & 1u) != 0u;
+    return FCD_OK;
+}
+
 static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int64_t n_sweeps, int64_t mstep_every,
                       int64_t accumulate_from, int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r, double *hyper_m,
                       unsigned acc_mask) {
@@ -1593,15 +1733,27 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         (void)hipGetLastError();
         use_rec = false;
     }
+    // The build is queued BEFORE the first sweep (which does not read it): by the time the second sweep is queued its hint --
+    // has the table decided tiles? -- has long arrived in its pinned word, and the host reads it there without a call into the
+    // runtime and without the device ever running dry (fcd_f_sure_hint_wait).
+    bool rec_built = false;
+    if (use_rec) {
+        ctx->n_frec_build += 1;
+        hipLaunchKernelGGL(gibbs_f_records_kernel, dim3((unsigned)fpt_tiles((Nreg + 1) / 2)), dim3(64 * FP_EC), 0, s, c.S_B, c.lMf,
+                           c.hyper, (int)Nreg, (int)U, (char *)ctx->frec, (unsigned *)((unsigned long long *)ctx->dbg + 4));
+        FCD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(gibbs_f_hint_kernel, dim3(1), dim3(1), 0, s, (unsigned *)((unsigned long long *)ctx->dbg + 4), ctx->f_sure_hint,
+                           (unsigned)(ctx->n_frec_build & 0x3fffffff));
+        FCD_LAUNCH_CHECK();
+        rec_built = true;
+    }
     for (int64_t i = 0; i < n_sweeps; ++i) {
         st.sweep = sweep0 + i;
         st.f_packed = packed_ok && st.r_packed;
         st.fsq = st.f_packed ? nullptr : fsq;
-        if (use_rec && st.f_packed && !st.f_rec) {
-            hipLaunchKernelGGL(gibbs_f_records_kernel, dim3((unsigned)fpt_tiles((Nreg + 1) / 2)), dim3(64 * FP_EC), 0, s, c.S_B, c.lMf,
-                               (int)Nreg, (int)U, (char *)ctx->frec);
-            FCD_LAUNCH_CHECK();
-            ctx->n_frec_build += 1;
+        if (rec_built && st.f_packed && !st.f_rec) {
+            int rc = fcd_f_sure_hint_wait(ctx, s, st.f_sure);
+            if (rc) return rc;
             st.f_rec = ctx->frec;
         }
         int rc = fcd_gibbs_f_pass(ctx, c, st);

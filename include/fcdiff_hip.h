@@ -117,6 +117,10 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
  *               every call that has one (A/B runs and tests; not read from the environment).  The table (stat
  *               "f_rec_bytes") belongs to the context, fcd_ctx_reserve sizes it; above 256 MB, or where the device has no
  *               room for it, the tiles build their own records
+ *   "f_sure"    1: never the decided-tile path of the pair-tile f pass on those records (default: in calls whose table has a
+ *               tile with every edge decided by the tables -- the mode leads by more than 16 nats in every r state -- such
+ *               tiles draw their Philox words, test them against the range of the draw without exponential and, if every lane
+ *               of the workgroup is inside, write the modes: no sums.  A/B runs and tests; not read from the environment)
  *   "tally_in_r" the f half of a sweep's tally (pooled counts of f, cnt_f) inside the pipelined r pass, counted by its in-order
  *               workgroups before their first block, while they wait for the first panel values: 0 = where those workgroups
  *               have 16 waves and a wave walks at most "tally_in_r_max_rounds" rounds of four edges (cfg3: 4 rounds), 1 = never
@@ -139,7 +143,9 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value);
  * carried the f half of the sweep's tally; "tally_f_in_r" = launches of the pipelined r pass that carried it,
  * "tally_in_r_max_rounds" = the threshold of knob tally_in_r = 0; "f_rec_passes" = f passes that read prebuilt pair records, "f_rec_builds" =
  * launches of the kernel that makes them, "f_rec_bytes" = the size of their table, "f_rec_min_sweeps" = the threshold of
- * knob f_records = 0; "dev_err" = the error word of the pipelined r pass as the host sees it now (see
+ * knob f_records = 0; "f_sure_passes" = f passes that ran the kernel with the decided-tile path, "f_sure_tiles" = workgroups (a
+ * pair-aligned tile x 16 chain words) that took it, "f_sure_fallbacks" = decided ones that a uniform outside the range sent back to
+ * the sums (the last two and "f_repeats", "r_exact_rows" are device counters: reading them synchronises); "dev_err" = the error word of the pipelined r pass as the host sees it now (see
  * fcd_ctx_check); "pipe_grid" / "pipe_capacity" = the grid of the last pipelined attempt of the r pass (its empty
  * workgroups included) and the workgroups the occupancy query says are resident at once for it (the form is taken where
  * pipe_grid + 8 <= pipe_capacity). */
