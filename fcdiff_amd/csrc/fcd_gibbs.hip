@@ -157,11 +157,16 @@ __global__ __launch_bounds__(256) void edge_tables_kernel(const double *__restri
     }
 }
 
+// (the lanes whose log-odds are not finite, and their draw from the absolute log-weights: defined with the pair forms below)
+__device__ __forceinline__ bool fcd_f_open(double b1, double b2);
+__device__ int fcd_f_abs_edge_masks(const double *__restrict__ row9, const double *__restrict__ sb, const double *__restrict__ hyper,
+                                    const uint64_t *__restrict__ rn, const uint64_t *__restrict__ rm, int U, int lane, double x);
+
 __global__ __launch_bounds__(1024) void gibbs_f_diff_kernel(const double *__restrict__ S_B, const double *__restrict__ lMf,
                                                             const double *__restrict__ hyper, uint8_t *__restrict__ f_state,
                                                             const uint64_t *__restrict__ r_bits, int Nreg, int U, int64_t C,
                                                             int GW, int Ec, uint32_t chain0, uint64_t seed, uint32_t sweep,
-                                                            float margin) {
+                                                            float margin, const double *__restrict__ lM) {
     extern __shared__ __attribute__((aligned(16))) double tile[];   // [Ec][U][3][2]
     const int64_t c0 = (int64_t)blockIdx.x * Ec;
     const int ne = (int)((C - c0 < Ec) ? (C - c0) : Ec);
@@ -224,7 +229,14 @@ __global__ __launch_bounds__(1024) void gibbs_f_diff_kernel(const double *__rest
         const double x = fcd_u32(fcd_word(rnd, (int)(c & 3)));
         bool amb;
         int k = fcd_draw_f_fast(b1, b2, x, 2e-5f, margin, &amb);
-        if (__ballot(amb) != 0ull) k = fcd_draw_f(0.0, b1, b2, x);      // too close to a boundary somewhere in the wave
+        if (__ballot(amb) != 0ull) {                                     // too close to a boundary somewhere in the wave
+            k = fcd_draw_f(0.0, b1, b2, x);
+            const bool open = fcd_f_open(b1, b2);                       // (type 0 impossible: the absolute log-weights decide)
+            if (__ballot(open) != 0ull) {
+                const int ka = fcd_f_abs_edge_masks(lM + c * U * 9, S_B + c * 3, hyper, rn, rm, U, lane, x);
+                if (open) k = ka;
+            }
+        }
         f_state[((int64_t)w * C + c) * 64 + lane] = (uint8_t)k;
     }
 }
@@ -331,8 +343,54 @@ __device__ __forceinline__ void fcd_f_exact_group(const double *__restrict__ row
     }
 }
 
+// Log-odds against type 0 say nothing where type 0 itself is impossible: a0 = -inf (gamma_0 = 0, or an entry lM[c][u][0][l] =
+// -inf of a density that underflowed) makes b1, b2 +inf or NaN, and fcd_draw_f(0, b1, b2, x) then answers 2 whatever the
+// weights of types 1 and 2.  The law is fcd_draw_f of the ABSOLUTE log-weights, as gibbs_f_kernel and the oracle make them:
+// a_k = ln gamma_k + (S_B[c][k] + sum_u lM[c][u][k][l_u]), the sum in the order of the patients from 0.0.  The exact repeats of
+// the log-odds forms end here for the lanes whose b1 or b2 is not finite (fcd_f_open); an edge without such a lane -- every
+// edge of finite tables and positive gamma -- never comes here.  Three gathers of the row lM[c] (72 bytes per patient: L2), by
+// what the form holds of the r state: slot words of 8 pairs of patients, or the bit planes.
+__device__ __forceinline__ bool fcd_f_open(double b1, double b2) { return !(isfinite(b1) && isfinite(b2)); }
+__device__ __forceinline__ void fcd_f_abs_group(const double *__restrict__ row9, int U, int u0, int np, uint32_t zs, double (&a)[3]) {
+#pragma unroll 1
+    for (int p = 0; p < np; ++p) {
+        const uint32_t f = (zs >> (4 * p)) & 15u;
+        const int l0 = (f & 4u) ? 1 : ((f & 1u) ? 2 : 0), l1 = (f & 8u) ? 1 : ((f & 2u) ? 2 : 0);   // 0 typical, 1 both, 2 discordant
+        const int u = u0 + 2 * p;
+        const double *q = row9 + (int64_t)u * 9 + l0;
+        a[0] += q[0]; a[1] += q[3]; a[2] += q[6];
+        if (u + 1 < U) {
+            const double *q1 = row9 + (int64_t)(u + 1) * 9 + l1;
+            a[0] += q1[0]; a[1] += q1[3]; a[2] += q1[6];
+        }
+    }
+}
+__device__ __forceinline__ int fcd_f_abs_draw(const double *__restrict__ sb, const double *__restrict__ hyper, const double (&a)[3], double x) {
+    return fcd_draw_f(hyper[FCD_H_LNGAMMA + 0] + (sb[0] + a[0]), hyper[FCD_H_LNGAMMA + 1] + (sb[1] + a[1]),
+                      hyper[FCD_H_LNGAMMA + 2] + (sb[2] + a[2]), x);
+}
+// (the scalar-mask form: rn, rm = the bit planes of the edge's two regions, one word per patient, bit = lane)
+__device__ __attribute__((noinline)) int fcd_f_abs_edge_masks(const double *__restrict__ row9, const double *__restrict__ sb,
+                                                              const double *__restrict__ hyper, const uint64_t *__restrict__ rn,
+                                                              const uint64_t *__restrict__ rm, int U, int lane, double x) {
+    double a[3] = {0.0, 0.0, 0.0};
+#pragma unroll 1
+    for (int u = 0; u < U; ++u) {
+        const int bn = (int)((rn[u] >> lane) & 1ull), bm = (int)((rm[u] >> lane) & 1ull);
+        const double *q = row9 + (int64_t)u * 9 + ((bn & bm) ? 1 : ((bn ^ bm) ? 2 : 0));
+        a[0] += q[0]; a[1] += q[3]; a[2] += q[6];
+    }
+    return fcd_f_abs_draw(sb, hyper, a, x);
+}
+
 // The exact path of the U <= 64 kernel as ONE out-of-line function: inlined into the eight unrolled edge bodies it was most of
 // the kernel's text (fp64 exponentials, the gather loop), and the hot path had to be fetched around it.
+// Returns the draw, + FCD_F_OPEN in the lanes of fcd_f_open.  The kernel notes those lanes per edge in the spare half of its
+// word of draws and, AFTER its edge loop, asks fcd_f_abs_edge for each noted edge: the call inside the unrolled edge bodies
+// keeps its arguments, and what the second call needs (the tables, the edge, the lane's chain) lives through the whole kernel
+// anyway -- the registers of the edge loop stay what they were.
+constexpr int FCD_F_OPEN = 4;
+constexpr int FCD_DBG_LM = 5;        // the context's device words that hold lM and hyper of the call's record table (word 4: any_tile)
 __device__ __attribute__((noinline)) int fcd_f_exact_edge(const double *__restrict__ row, double c1, double c2, uint32_t z0, uint32_t z1,
                                                           uint32_t z2, uint32_t z3, int U, uint32_t xw) {
     const int NPAIR = (U + 1) >> 1, NG = (NPAIR + 7) >> 3;
@@ -343,7 +401,26 @@ __device__ __attribute__((noinline)) int fcd_f_exact_edge(const double *__restri
         const uint32_t zs = g == 0 ? z0 : g == 1 ? z1 : g == 2 ? z2 : z3;
         fcd_f_exact_group(row, U, 16 * g, min(8, NPAIR - 8 * g), zs, first, b1, b2);
     }
-    return fcd_draw_f(0.0, c1 + b1, c2 + b2, fcd_u32(xw));
+    b1 = c1 + b1;
+    b2 = c2 + b2;
+    return fcd_draw_f(0.0, b1, b2, fcd_u32(xw)) | (fcd_f_open(b1, b2) ? FCD_F_OPEN : 0);
+}
+// Edge c = (n, m) of the U <= 64 kernel from the absolute log-weights, for this lane's chain: the slot words of the two regions
+// (ru: the chain word's, four side by side per region and lane -- ru_index) and the draw's Philox word are made again.
+__device__ __attribute__((noinline)) int fcd_f_abs_edge(const double *__restrict__ lM, const double *__restrict__ S_B,
+                                                        const double *__restrict__ hyper, const uint4 *__restrict__ ru, int64_t c, int n,
+                                                        int m, int U, uint32_t chain, uint32_t sweep, uint64_t seed) {
+    const int NPAIR = (U + 1) >> 1, NG = (NPAIR + 7) >> 3;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint4 vn = ru[(uint32_t)(n * 64) + lane], vm = ru[(uint32_t)(m * 64) + lane];
+    double a[3] = {0.0, 0.0, 0.0};
+#pragma unroll 1
+    for (int g = 0; g < NG; ++g) {
+        const uint32_t rn = g == 0 ? vn.x : g == 1 ? vn.y : g == 2 ? vn.z : vn.w, rm = g == 0 ? vm.x : g == 1 ? vm.y : g == 2 ? vm.z : vm.w;
+        fcd_f_abs_group(lM + c * U * 9, U, 16 * g, min(8, NPAIR - 8 * g), (rn ^ rm) | ((rn & rm) << 2), a);
+    }
+    const fcd_u4 rnd = fcd_philox((uint32_t)(c >> 2), chain, sweep, FCD_KIND_F, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return fcd_f_abs_draw(S_B + c * 3, hyper, a, fcd_u32(fcd_word(rnd, (int)(c & 3))));
 }
 
 // Pair-aligned tiles (PT): tile t is rows (n0, n0 + 1) = (2i, 2i + 1) of the triangle x columns [mb, mb + FT_W) inside
@@ -431,7 +508,7 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
                                                             const uint32_t *__restrict__ r_U, int Nreg, int U, int64_t C,
                                                             int GW, uint32_t chain0, uint64_t seed, uint32_t sweep, float margin, uint8_t *__restrict__ fsq,
                                                             uint2 *__restrict__ f_S, int NBLK, unsigned long long *__restrict__ dbg,
-                                                            const char *__restrict__ frec) {
+                                                            const char *__restrict__ frec, const double *__restrict__ lM) {
     static_assert(PT || !PRE, "prebuilt records are laid out by pair-aligned tile");
     static_assert(PRE || !SURE, "the edges' bounds are part of the prebuilt records");
     // pair records [NPAIR][FP_EC][16] float2 | per-edge constants [FP_EC] float4 | (PRE) 16 vote words | (not PRE) singles [FP_EC][U][3][2] double
@@ -753,6 +830,8 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
                 // somewhere in the wave the fp32 sums cannot decide the draw: the edge again, in fp64, for the whole wave
                 k = fcd_f_exact_edge(lMf + c * U * 6, lg1 + (S_B[c * 3 + 1] - S_B[c * 3 + 0]), lg2 + (S_B[c * 3 + 2] - S_B[c * 3 + 0]), Zc[0],
                                      NW16 > 1 ? Zc[NW16 > 1 ? 1 : 0] : 0u, NW16 > 2 ? Zc[NW16 > 2 ? 2 : 0] : 0u, NW16 > 3 ? Zc[NW16 > 3 ? 3 : 0] : 0u, U, xw);
+                kt |= (uint32_t)(k >> 2) << (16 + e);       // (FCD_F_OPEN: this lane's draw of edge e is made again behind the loop)
+                k &= 3;
                 if (lane == 0) atomicAdd(dbg, 1ull);
             }
 #ifdef FCD_ABLATE
@@ -786,6 +865,37 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
                 tr_rest += tc3 - tc2;
             }
 #endif
+        }
+    }
+    if (__builtin_expect(__ballot(kt >> 16) != 0ull, 0)) {
+        // some lane's log-odds of some edge were not finite (type 0 impossible there): those draws again, from the absolute
+        // log-weights -- never on finite tables with positive gamma.  On the call's record table (PRE) lM and hyper are read from
+        // the device words gibbs_f_hint_kernel left them in, not from the arguments: a value that has to live to the end of the kernel
+        // costs every wave scalar moves in its prologue (the decided-tile path is little else), and dbg lives that long anyway.
+        const double *__restrict__ lMa = PRE ? reinterpret_cast<const double *>(dbg[FCD_DBG_LM]) : lM;
+        const double *__restrict__ hya = PRE ? reinterpret_cast<const double *>(dbg[FCD_DBG_LM + 1]) : hyper;
+#pragma unroll 1
+        for (int e = 0; e < FP_EC; ++e) {
+            const bool open = (kt >> (16 + e)) & 1u;
+            if (__ballot(open) == 0ull) continue;
+            const int64_t c = cid(e);
+            int n, m;
+            if (PT) {
+                n = T.n0 + (e < FT_W ? 0 : 1);
+                m = T.mb + e % FT_W;
+            } else {
+                fcd_edge_to_pair(c, n, m);
+            }
+            const uint32_t ka = (uint32_t)fcd_f_abs_edge(lMa, S_B, hya, ru, c, n, m, U, chain, sweep, seed);
+            if (open) {
+                kt = (kt & ~(3u << (2 * e))) | (ka << (2 * e));
+                (f_state + ((int64_t)w * C + c) * 64)[(uint32_t)lane] = (uint8_t)ka;
+                if (!PT && fsq) {
+                    uint8_t *sq = fsq + (int64_t)w * Nreg * Nreg * 64;
+                    (sq + ((int64_t)n * Nreg + m) * 64)[(uint32_t)lane] = (uint8_t)ka;
+                    (sq + ((int64_t)m * Nreg + n) * 64)[(uint32_t)lane] = (uint8_t)ka;
+                }
+            }
         }
     }
     if (PT && f_S) fpt_write_f_words(T, kt, w, lane, f_S, Nreg, NBLK);
@@ -879,9 +989,14 @@ __global__ __launch_bounds__(64 * FP_EC) void gibbs_f_records_kernel(const doubl
 }
 // ... and hands it to the host: 2 build + any into the pinned word the sweep loop polls (written once, complete), the device
 // word cleared for the next build.
-__global__ void gibbs_f_hint_kernel(unsigned *__restrict__ any_tile, volatile unsigned *hint, unsigned build) {
+// It also leaves the call's lM and hyper where the kernels that read the table find them (dbg[FCD_DBG_LM], [FCD_DBG_LM + 1]:
+// the words behind any_tile's).
+__global__ void gibbs_f_hint_kernel(unsigned *__restrict__ any_tile, volatile unsigned *hint, unsigned build, const double *lM,
+                                    const double *hyper) {
     const unsigned any = *any_tile != 0u ? 1u : 0u;
     *any_tile = 0u;
+    reinterpret_cast<unsigned long long *>(any_tile)[1] = (unsigned long long)(uintptr_t)lM;
+    reinterpret_cast<unsigned long long *>(any_tile)[2] = (unsigned long long)(uintptr_t)hyper;
     __hip_atomic_store(const_cast<unsigned *>(hint), 2u * build + any, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -901,7 +1016,7 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pairx_kernel(const double *__
                                                                 const uint32_t *__restrict__ r_U, int Nreg, int U, int64_t C,
                                                                 int GW, uint32_t chain0, uint64_t seed, uint32_t sweep,
                                                                 float margin, uint8_t *__restrict__ fsq,
-                                                                unsigned long long *__restrict__ dbg) {
+                                                                unsigned long long *__restrict__ dbg, const double *__restrict__ lM) {
     // pairs [EC][NPAIR][16] float2 | per-edge constants [8] float4 | staging scratch [waves][2][24] double2
     extern __shared__ __attribute__((aligned(256))) double ptile[];
     const int NPAIR = (U + 1) >> 1, NW16 = (U + 15) >> 4;
@@ -1076,6 +1191,17 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pairx_kernel(const double *__
             b1 = lg1 + ((S_B[c * 3 + 1] - S_B[c * 3 + 0]) + b1);
             b2 = lg2 + ((S_B[c * 3 + 2] - S_B[c * 3 + 0]) + b2);
             k = fcd_draw_f(0.0, b1, b2, fcd_u32(xw));
+            const bool open = fcd_f_open(b1, b2);                       // (type 0 impossible: the absolute log-weights decide)
+            if (__ballot(open) != 0ull) {
+                double a[3] = {0.0, 0.0, 0.0};
+#pragma unroll 1
+                for (int g = 0; g < NG; ++g) {
+                    const uint32_t a_ = ruw(wn, g), b_ = ruw(wm, g);
+                    fcd_f_abs_group(lM + c * U * 9, U, 16 * g, min(8, NPAIR - 8 * g), (a_ ^ b_) | ((a_ & b_) << 2), a);
+                }
+                const int ka = fcd_f_abs_draw(S_B + c * 3, hyper, a, fcd_u32(xw));
+                if (open) k = ka;
+            }
             if (lane == 0) atomicAdd(dbg, 1ull);
         }
         (f_state + ((int64_t)w * C + c) * 64)[(uint32_t)lane] = (uint8_t)k;     // (scalar base + lane)
@@ -1502,8 +1628,8 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step
         hipLaunchKernelGGL(KERN, grid, dim3(64 * wpb), f_shmem, s, FCD_F_ARGS, EXTRA);                        \
         fcd_prof_end(ctx, FCD_PROF_F, s);                                                                     \
     } while (0)
-#define FCD_PX (unsigned long long *)ctx->dbg
-#define FCD_PT f_S, NBLK, (unsigned long long *)ctx->dbg, (const char *)st.f_rec
+#define FCD_PX (unsigned long long *)ctx->dbg, c.lM
+#define FCD_PT f_S, NBLK, (unsigned long long *)ctx->dbg, (const char *)st.f_rec, c.lM
         if (form == FCD_F_PAIR && pt && st.f_rec && st.f_sure && !(margin > 1.f) && ctx->knobs.f_sure != 1) {
             // (a table without decided tiles, the test hook f_tol and knob f_sure = 1 keep the kernel below)
             if (pl.f_NW == 1) FCD_LAUNCH_F((gibbs_f_pair_kernel<1, true, true, true>), FCD_KA_F_PAIR_S + 0, FCD_PT);
@@ -1547,7 +1673,7 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step
     dim3 grid((unsigned)((g.C + pl.f_EC - 1) / pl.f_EC), (unsigned)((g.GW + wpb - 1) / wpb));
     fcd_prof_begin(ctx, FCD_PROF_F, s);
     hipLaunchKernelGGL(gibbs_f_diff_kernel, grid, dim3(64 * wpb), pl.f_shmem, s, c.S_B, c.lMf, c.hyper, c.f_state, c.r_bits,
-                       (int)Nreg, (int)U, g.C, g.GW, pl.f_EC, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, margin);
+                       (int)Nreg, (int)U, g.C, g.GW, pl.f_EC, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, margin, c.lM);
     fcd_prof_end(ctx, FCD_PROF_F, s);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
@@ -1743,7 +1869,7 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
                            c.hyper, (int)Nreg, (int)U, (char *)ctx->frec, (unsigned *)((unsigned long long *)ctx->dbg + 4));
         FCD_LAUNCH_CHECK();
         hipLaunchKernelGGL(gibbs_f_hint_kernel, dim3(1), dim3(1), 0, s, (unsigned *)((unsigned long long *)ctx->dbg + 4), ctx->f_sure_hint,
-                           (unsigned)(ctx->n_frec_build & 0x3fffffff));
+                           (unsigned)(ctx->n_frec_build & 0x3fffffff), c.lM, c.hyper);
         FCD_LAUNCH_CHECK();
         rec_built = true;
     }
