@@ -12,6 +12,10 @@ network_test()  per population: "which sub-network is abnormal in this disease?"
               the permutation law of the largest component.  graph_components() gives the components of any mask.
               Oracle = tests/network_ref.py; fcd_baseline_network_bits, fcd_graph_components.
 
+group_test() and network_test() take missing_data=True (a NaN is an unobserved value) and variance="welch"; a call with
+either goes through fcd_baseline_group_perm_opt / fcd_baseline_network_bits_opt, the default call through the entry points
+it always used.  Oracle = tests/baseline_missing_ref.py.
+
 b (C, H) controls and bt (C, U) patients, NumPy arrays or torch tensors, float64, connections in util.c_to_nm order;
 E(n) = the N - 1 connections that touch region n.  Both run on the device (fcd_baseline_normative,
 fcd_baseline_group_perm of include/fcdiff_hip.h) and have no CPU fallback; the p-values are made on the host from what the
@@ -197,9 +201,27 @@ def _check_labels(labels, S, U):
     return lab
 
 
-def group_test(b, bt, n_perm=10000, *, seed=0, labels=None, ctx=None, as_numpy=True):
+FLAG_MISSING = 1          # FCD_BASELINE_MISSING, FCD_BASELINE_WELCH of include/fcdiff_hip.h
+FLAG_WELCH = 2
+
+
+def _options(who, b, bt, H, U, missing_data, variance):
+    """The host checks of missing_data and variance -> flags of the calls with options (0: the default call)."""
+    if variance not in ("pooled", "welch"):
+        raise ValueError("%s: variance must be 'pooled' or 'welch', not %r" % (who, variance))
+    if variance == "welch" and (H < 2 or U < 2):
+        raise ValueError("%s: variance='welch' needs two controls and two patients, not H = %d and U = %d" % (who, H, U))
+    if not missing_data:
+        _refuse_nonfinite(b, bt, who, "the data must be complete and finite (pass missing_data=True to treat NaN as unobserved)")
+    elif _has_inf(b) or _has_inf(bt):
+        raise ValueError("%s: infinite value in b or bt; missing_data=True admits NaN (unobserved) only" % who)
+    return (FLAG_MISSING if missing_data else 0) | (FLAG_WELCH if variance == "welch" else 0)
+
+
+def group_test(b, bt, n_perm=10000, *, missing_data=False, variance="pooled", seed=0, labels=None, ctx=None, as_numpy=True):
     """
-    Mass-univariate two-sample test of patients against controls with permutation inference.  b (C, H), bt (C, U), complete.
+    Mass-univariate two-sample test of patients against controls with permutation inference.  b (C, H), bt (C, U), complete
+    unless missing_data=True.  What follows first describes the default call (missing_data=False, variance="pooled").
 
     X = [b | bt] (C, S), S = H + U, rows centred on their mean over all subjects, Q_c = sum x^2.  For a labelling l in
     {0,1}^S with exactly U ones: A = sum l_s x_s, SS_w = Q_c - A^2 S/(U H), Student's t with pooled variance
@@ -219,9 +241,25 @@ def group_test(b, bt, n_perm=10000, *, seed=0, labels=None, ctx=None, as_numpy=T
     negative term: where SS_w, a difference of two rounded numbers, is not > 0 with Q_c > 0 (complete separation of the two
     groups), t^2 = +inf and t = +/-inf with the sign of A, and inf >= inf counts as IEEE arithmetic has it.
 
-    A NaN or an infinite value is a ValueError (missing data is not provided here); more than 1024 subjects a
-    NotImplementedError.
-    Not provided: sessions, noise variances, Welch's t, cluster statistics.  The network-based statistic is network_test().
+    missing_data=True: a NaN is an unobserved value (an infinite value stays a ValueError).  Per connection, O = the subjects
+    observed there, n = |O|; the row is centred on its mean over O, x_s = 0 for a missing subject, Q = sum x^2; it is constant
+    where all observed values are equal.  The labellings are what they are without it: U ones over all S subjects, observed
+    or not.  Per labelling n1 = the labelled subjects in O, n0 = n - n1, A = sum l_s x_s, B = sum l_s x_s^2, k = n / (n1 n0);
+    the mean difference is A k.  The pooled t^2 = g (n - 2) / (Q - g), g = A^2 k, is defined iff the connection is not constant,
+    n >= 3, n1 >= 1 and n0 >= 1; on complete data it is the default call bit for bit.  Two keys are added: n_controls,
+    n_patients (C,) int64, the observed values per connection under the observed labelling.
+    variance="welch": Welch's unequal-variance t (no degrees of freedom are needed: the inference is by permutation).
+    SS1 = max(B - A^2/n1, 0), SS0 = max((Q - B) - A^2/n0, 0), v = SS1/(n1 (n1 - 1)) + SS0/(n0 (n0 - 1)), t^2 = (A k)^2 / v with
+    the sign of A; defined iff the connection is not constant, n1 >= 2 and n0 >= 2; where v is not > 0, t^2 = +inf if A != 0
+    and 0 if A = 0.  H < 2 or U < 2 is a ValueError.
+    A value that is undefined under a labelling adds exactly 0 to every region sum and enters no maximum, but counts as an
+    exceedance in count_t: the conservative choice, a labelling that cannot be evaluated never makes a p-value smaller.  A
+    connection that is undefined under the observed labelling is dead exactly as a constant one is: t NaN, count_t 0, p_t and
+    p_fwe_t NaN, no part in region or in any permuted sum or maximum.  The identity-row property and the repeatability hold
+    with either option.
+
+    Without missing_data a NaN or an infinite value is a ValueError; more than 1024 subjects a NotImplementedError.
+    Not provided: sessions, noise variances, cluster statistics.  The network-based statistic is network_test().
     """
     import torch
     (C, N, H, U) = _check_pair(b, bt, "group_test")
@@ -230,7 +268,7 @@ def group_test(b, bt, n_perm=10000, *, seed=0, labels=None, ctx=None, as_numpy=T
         raise NotImplementedError("group_test: %d subjects, at most %d" % (S, MAX_SUBJECTS))
     if S < 3:
         raise ValueError("group_test: %d subjects, a pooled variance needs 3" % S)
-    _refuse_nonfinite(b, bt, "group_test", "the data must be complete and finite (missing data is not provided here)")
+    flags = _options("group_test", b, bt, H, U, missing_data, variance)
     if labels is None:
         if int(n_perm) < 1:
             raise ValueError("group_test: n_perm must be >= 1")
@@ -248,11 +286,19 @@ def group_test(b, bt, n_perm=10000, *, seed=0, labels=None, ctx=None, as_numpy=T
     null_max_region = torch.empty((P,), dtype=torch.float64, device=dev)
     count_t = torch.empty((C,), dtype=torch.int64, device=dev)
     count_region = torch.empty((N,), dtype=torch.int64, device=dev)
-    ctx.call("fcd_baseline_group_perm", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(labd), P, _lib.dptr(t),
-             _lib.dptr(region), _lib.dptr(null_max_t), _lib.dptr(null_max_region), _lib.dptr(count_t), _lib.dptr(count_region),
-             _lib.stream_ptr())
     out = {"t": t, "region": region, "null_max_t": null_max_t, "null_max_region": null_max_region, "count_t": count_t,
            "count_region": count_region}
+    if flags == 0:
+        ctx.call("fcd_baseline_group_perm", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(labd), P, _lib.dptr(t),
+                 _lib.dptr(region), _lib.dptr(null_max_t), _lib.dptr(null_max_region), _lib.dptr(count_t),
+                 _lib.dptr(count_region), _lib.stream_ptr())
+    else:
+        counts = [torch.empty((C,), dtype=torch.int64, device=dev) for _ in range(2)] if missing_data else [None, None]
+        ctx.call("fcd_baseline_group_perm_opt", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(labd), P, flags, _lib.dptr(t),
+                 _lib.dptr(region), _lib.dptr(null_max_t), _lib.dptr(null_max_region), _lib.dptr(count_t),
+                 _lib.dptr(count_region), _lib.dptr(counts[0]), _lib.dptr(counts[1]), _lib.stream_ptr())
+        if missing_data:
+            out.update(n_controls=counts[0], n_patients=counts[1])
     host = dict((k, v.cpu().numpy()) for (k, v) in out.items())
     pv = group_pvalues(host["t"], host["region"], host["null_max_t"], host["null_max_region"], host["count_t"],
                        host["count_region"])
@@ -366,21 +412,25 @@ def graph_components(mask, *, ctx=None, as_numpy=True):
     return dict((k, v.cpu().numpy()) for (k, v) in out.items()) if as_numpy else out
 
 
-def network_test(b, bt, threshold, n_perm=10000, *, tail="both", seed=0, labels=None, ctx=None, as_numpy=True):
+def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=False, variance="pooled", seed=0, labels=None,
+                 ctx=None, as_numpy=True):
     """
     The network-based statistic (Zalesky, Fornito & Bullmore 2010): which sub-networks differ between patients and controls?
-    b (C, H), bt (C, U), complete.
+    b (C, H), bt (C, U), complete unless missing_data=True.
 
-    Data, labellings, centring and the pooled-variance t are group_test()'s; the observed labelling has its ones on the last U
-    subjects.  A connection is suprathreshold where |t| > threshold (tail="both"), t > threshold ("greater": patients above
-    controls, the sign of group_test's t) or t < -threshold ("less"); threshold > 0 in t units.  The components are those
-    of the graph on the N regions whose edges are the suprathreshold connections: a component's extent is its number of
-    connections, its label the smallest region in it; a region without a suprathreshold connection has label -1.  The
-    family-wise error is controlled by the permutation law of the largest extent.  labels as in group_test(); a row equal
-    to the observed labelling counts, and gives the observed bits exactly.  Labellings are walked in chunks; the results do
-    not depend on the chunk size and repeat exactly from call to call.  Degenerate connections as in group_test(): a constant
-    connection has t = NaN and is never suprathreshold, under any labelling; a completely separated one has t = +/-inf and is
-    suprathreshold on its side.
+    Data, labellings, centring and the t are group_test()'s, its options missing_data and variance ("pooled" or "welch")
+    with their rules included: a value that is undefined under a labelling is never suprathreshold, a connection that is
+    undefined under the observed labelling has t = NaN and is never suprathreshold under any labelling, and
+    missing_data=True adds the keys n_controls and n_patients (C,) int64.  In the default call the t is the pooled-variance
+    t; the observed labelling has its ones on the last U subjects.  A connection is suprathreshold where |t| > threshold
+    (tail="both"), t > threshold ("greater": patients above controls, the sign of group_test's t) or t < -threshold
+    ("less"); threshold > 0 in t units.  The components are those of the graph on the N regions whose edges are the
+    suprathreshold connections: a component's extent is its number of connections, its label the smallest region in it; a
+    region without a suprathreshold connection has label -1.  The family-wise error is controlled by the permutation law of
+    the largest extent.  labels as in group_test(); a row equal to the observed labelling counts, and gives the observed bits
+    exactly.  Labellings are walked in chunks; the results do not depend on the chunk size and repeat exactly from call to
+    call.  Degenerate connections as in group_test(): a constant connection has t = NaN and is never suprathreshold, under
+    any labelling; a completely separated one has t = +/-inf and is suprathreshold on its side.
 
     Returns a dict: t (C,); edge_mask (C,) bool; component (N,) int64; component_label, component_edges, component_regions
     (K,) int64, the K >= 0 observed components by decreasing extent, then by label; null_max_extent, null_max_regions,
@@ -389,7 +439,7 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", seed=0, labels=
     the region's component, NaN at label -1; labels (P, S) uint8 as used; threshold, tail.
     Refused: everything group_test() refuses; a threshold that is not finite and > 0 or an unknown tail (ValueError); more
     than 1024 regions (NotImplementedError).  Not provided: the intensity form sum (|t| - threshold) (it would need a value
-    per bit), TFCE, sessions, noise variances, missing data.
+    per bit), TFCE, sessions, noise variances.
     """
     import torch
     (C, N, H, U) = _check_pair(b, bt, "network_test")
@@ -405,7 +455,7 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", seed=0, labels=
         raise ValueError("network_test: threshold must be finite and > 0, not %r" % (threshold,))
     if tail not in TAILS:
         raise ValueError("network_test: tail must be one of 'both', 'greater', 'less', not %r" % (tail,))
-    _refuse_nonfinite(b, bt, "network_test", "the data must be complete and finite (missing data is not provided here)")
+    flags = _options("network_test", b, bt, H, U, missing_data, variance)
     if labels is None:
         if int(n_perm) < 1:
             raise ValueError("network_test: n_perm must be >= 1")
@@ -423,8 +473,12 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", seed=0, labels=
         return torch.empty(sh, dtype=torch.int32, device=dev)
 
     def bits_call(lab_c, n, bits, t):
-        ctx.call("fcd_baseline_network_bits", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(lab_c), n, thr, TAILS[tail],
-                 _lib.dptr(bits), _lib.dptr(t), _lib.stream_ptr())
+        if flags == 0:
+            ctx.call("fcd_baseline_network_bits", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(lab_c), n, thr, TAILS[tail],
+                     _lib.dptr(bits), _lib.dptr(t), _lib.stream_ptr())
+        else:
+            ctx.call("fcd_baseline_network_bits_opt", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(lab_c), n, thr,
+                     TAILS[tail], flags, _lib.dptr(bits), _lib.dptr(t), _lib.stream_ptr())
 
     # the observed labelling: the same kernels at P = 1
     t = torch.empty((C,), dtype=torch.float64, device=dev)
@@ -449,6 +503,9 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", seed=0, labels=
     p_of = np.full(N + 1, np.nan)                            # (label -1 reads the last entry)
     p_of[label] = host["p_fwe"]
     host["p_fwe_region"] = p_of[host["component"]]
+    if missing_data:
+        host["n_controls"] = (~torch.isnan(bd)).sum(dim=1).cpu().numpy()
+        host["n_patients"] = (~torch.isnan(btd)).sum(dim=1).cpu().numpy()
     out = host if as_numpy else dict((k, torch.as_tensor(v, device=dev)) for (k, v) in host.items())
     out["labels"] = lab if as_numpy else labd
     out["threshold"] = thr

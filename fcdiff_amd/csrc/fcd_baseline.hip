@@ -53,6 +53,8 @@
 //                      a wave takes 16 consecutive connections x 4 groups of 16 labellings; one ballot per result element
 //                      holds the 16 connections of four labellings, stored as four uint16 (plain vector stores).  The
 //                      observed labelling is a call with P = 1 through the same kernel.
+//                      (fcd_baseline_group_perm_opt, fcd_baseline_network_bits_opt: the same with missing data and Welch's t,
+//                      kernels of their own at the end of the namespace; oracle = tests/baseline_missing_ref.py.)
 //   graph_components_kernel  one workgroup per row of bits, the row in LDS (64 KB at 1024 regions, the limit).  label[x] = x;
 //                      per round every set bit (n, m) pulls the larger label, and the region that label names, down to the
 //                      smaller (LDS atomicMin), then label[x] = label[label[x]]; until a round changes nothing, at most N
@@ -628,6 +630,364 @@ __global__ __launch_bounds__(CC_T) void graph_components_kernel(const uint32_t *
     }
 }
 
+// ---- the two options: missing data (MISS) and Welch's t (WELCH) ------------------------------------------------------------
+// Never instantiated with both off: that case is the kernels above, untouched.  Per group of 16 labellings up to three
+// accumulators through the same tile product: A = L X as above (XT holds 0 at a missing subject), n1 = L M (MISS; M the 0/1
+// observation mask, exact small integers in any order) and B = L X^2 (WELCH; the square of the value already loaded).
+// The mask takes the label words' treatment: MW[(w C + c) 4 + ks], bit j = subject 4 (32 w + j) + ks of row c is observed,
+// so a lane fetches one uint32 per 32 K-steps (256 contiguous bytes per word where the 16 rows are contiguous).
+//   definedness      pooled: Q > 0, n >= 3, n1 >= 1, n0 >= 1; Welch: Q > 0, n1 >= 2, n0 >= 2.  Undefined under a labelling: 0 to
+//                    the sums, no maximum, no bit, but an exceedance in count_t.  Undefined under the observed labelling:
+//                    t2obs = NaN, the connection is dead (as a constant one).
+
+constexpr int NBO_G = 2;                 // groups of 16 labellings per wave of the bits kernel with options (3 accumulators each)
+
+// per connection, beside XT and Q: mask words, n = observed subjects, n1 of the observed labelling (observed patients)
+struct gpo_conn {
+    const uint32_t *MW;
+    const int32_t *NN, *NO;
+    double nS, nU;                     // what n and n1 are on complete data (MISS off)
+};
+
+__global__ __launch_bounds__(64 * GC_WAVES) void group_centre_missing_kernel(const double *__restrict__ b, const double *__restrict__ bt,
+                                                                             int64_t C, int H, int U, int KS, int nw,
+                                                                             double *__restrict__ XT, double *__restrict__ Q,
+                                                                             uint32_t *__restrict__ MW, int32_t *__restrict__ NN,
+                                                                             int32_t *__restrict__ NO, int64_t *__restrict__ n_controls,
+                                                                             int64_t *__restrict__ n_patients) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t c = (int64_t)blockIdx.x * GC_WAVES + wv;
+    if (c >= C) return;
+    const int S = H + U;
+    const double *__restrict__ br = b + c * H, *__restrict__ tr = bt + c * U;
+    double s = 0.0, x0l = 0.0;
+    int nc = 0, np = 0, first = INT32_MAX;
+    bool same = true;
+    for (int i = lane; i < S; i += 64) {
+        const double v = i < H ? br[i] : tr[i - H];
+        if (v == v) {
+            s += v;
+            if (i < H) ++nc; else ++np;
+            if (first == INT32_MAX) {
+                first = i;
+                x0l = v;
+            }
+            same = same && v == x0l;
+        }
+    }
+    // the first observed value of the row: every lane's values equal its own first, and that equals the row's first
+    int fmin = first;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) fmin = min(fmin, __shfl_xor(fmin, o, 64));
+    const double x0 = __shfl(x0l, fmin & 63, 64);
+    same = same && (first == INT32_MAX || x0l == x0);
+    const bool constant = __ballot(!same) == 0ull;           // all observed values equal (none included): x and Q exactly 0
+    nc = bl_wave_sum_int(nc);
+    np = bl_wave_sum_int(np);
+    const int n = nc + np;
+    const double mean = fcd_wave_sum(s) / (double)n;
+    double q = 0.0;
+    for (int i = lane; i < 4 * KS; i += 64) {
+        double xc = 0.0;
+        if (i < S && !constant) {
+            const double v = i < H ? br[i] : tr[i - H];
+            if (v == v) xc = v - mean;
+        }
+        q += xc * xc;
+        XT[((int64_t)(i >> 2) * C + c) * 4 + (i & 3)] = xc;
+    }
+    q = fcd_wave_sum(q);
+    if (lane < 4 * nw) {                                     // one mask word per lane: K-word lane >> 2, subject phase lane & 3
+        const int w = lane >> 2, ks = lane & 3;
+        uint32_t word = 0;
+        for (int j = 0; j < 32; ++j) {
+            const int i = 4 * (32 * w + j) + ks;
+            if (i < S) {
+                const double v = i < H ? br[i] : tr[i - H];
+                word |= (v == v ? 1u : 0u) << j;
+            }
+        }
+        MW[((int64_t)w * C + c) * 4 + ks] = word;
+    }
+    if (lane == 0) {
+        Q[c] = q;
+        NN[c] = n;
+        NO[c] = np;
+        if (n_controls) n_controls[c] = nc;
+        if (n_patients) n_patients[c] = np;
+    }
+}
+
+__global__ __launch_bounds__(256) void group_fill_counts_kernel(int64_t C, int64_t H, int64_t U, int64_t *__restrict__ n_controls,
+                                                                int64_t *__restrict__ n_patients) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    if (n_controls) n_controls[c] = H;
+    if (n_patients) n_patients[c] = U;
+}
+
+// gp_tile_mma with the accumulators of the options.  mp: this lane's mask word of K-word 0 (MISS), wstride words to the next.
+template <int G, bool MISS, bool WELCH>
+__device__ __forceinline__ void gpo_tile_mma(const double *__restrict__ xp, int64_t jstride, const uint32_t *__restrict__ mp,
+                                             int64_t wstride, const uint32_t (&lw)[G][GP_NW], int nw, int KS, double4_t (&acc)[G],
+                                             double4_t (&accn)[G], double4_t (&accb)[G]) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) acc[g] = accn[g] = accb[g] = double4_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int w = 0; w < GP_NW; ++w) {
+        if (w < nw) {                                        // (uniform)
+            const int jn = KS - 32 * w < 32 ? KS - 32 * w : 32;
+            const double *__restrict__ xw = xp + (int64_t)(32 * w) * jstride;
+            uint32_t mw = 0u;
+            if (MISS) mw = mp[(int64_t)w * wstride];
+            int j = 0;
+            for (; j + 4 <= jn; j += 4) {
+                double bv[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) bv[i] = xw[(int64_t)(j + i) * jstride];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const double mv = gp_label(mw, j + i), b2 = bv[i] * bv[i];
+#pragma unroll
+                    for (int g = 0; g < G; ++g) {
+                        const double la = gp_label(lw[g][w], j + i);
+                        acc[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(la, bv[i], acc[g], 0, 0, 0);
+                        if (MISS) accn[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(la, mv, accn[g], 0, 0, 0);
+                        if (WELCH) accb[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(la, b2, accb[g], 0, 0, 0);
+                    }
+                }
+            }
+            for (; j < jn; ++j) {
+                const double bv = xw[(int64_t)j * jstride];
+                const double mv = gp_label(mw, j), b2 = bv * bv;
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const double la = gp_label(lw[g][w], j);
+                    acc[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(la, bv, acc[g], 0, 0, 0);
+                    if (MISS) accn[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(la, mv, accn[g], 0, 0, 0);
+                    if (WELCH) accb[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(la, b2, accb[g], 0, 0, 0);
+                }
+            }
+        }
+    }
+}
+
+// The tile product of a wave's 16 connections.  Complete-tile shortcut: where all 16 are complete (n = S), every labelling has
+// n1 = U there and the mask product is left out; the branch is wave-uniform and the results are the same bits either way
+// (the counts are exact).  Returns whether accn was counted.  FCD_GPO_NO_SHORTCUT: a timing build without it.
+template <int G, bool MISS, bool WELCH>
+__device__ __forceinline__ bool gpo_tile(const double *__restrict__ xp, int64_t jstride, const uint32_t *__restrict__ mp, int64_t wstride,
+                                         const uint32_t (&lw)[G][GP_NW], int nw, int KS, double nc, double nS, double4_t (&acc)[G],
+                                         double4_t (&accn)[G], double4_t (&accb)[G]) {
+#ifndef FCD_GPO_NO_SHORTCUT
+    if (MISS && __ballot(nc != nS) == 0ull) {
+        gpo_tile_mma<G, false, WELCH>(xp, jstride, mp, wstride, lw, nw, KS, acc, accn, accb);
+        return false;
+    }
+#endif
+    gpo_tile_mma<G, MISS, WELCH>(xp, jstride, mp, wstride, lw, nw, KS, acc, accn, accb);
+    return MISS;
+}
+
+// t^2 of one value from A = sum l x, B = sum l x^2, n1 = sum l m, and the connection's n and Q; k = n / (n1 n0).
+// Pooled: g = A^2 k, t^2 = g (n - 2) / (Q - g), +inf where Q - g is not > 0: gp_t2 operation for operation where n = S, n1 = U.
+// Welch: SS1 = max(B - A^2/n1, 0), SS0 = max((Q - B) - A^2/n0, 0), v = SS1/(n1 (n1 - 1)) + SS0/(n0 (n0 - 1)), t^2 = (A k)^2 / v;
+// v not > 0: +inf if A != 0, else 0.  def: whether the value is defined; what is returned where it is not is the caller's to drop.
+template <bool WELCH>
+__device__ __forceinline__ double gpo_t2(double A, double B, double n1, double n, double Qc, bool &def) {
+    const double n0 = n - n1, k = n / (n1 * n0);
+    if (!WELCH) {
+        def = Qc > 0.0 && n >= 3.0 && n1 >= 1.0 && n0 >= 1.0;
+        const double gq = A * A * k, den = Qc - gq;
+        double t2 = gq * (n - 2.0) / den;
+        if (!(den > 0.0)) t2 = __builtin_inf();
+        return t2;
+    }
+    def = Qc > 0.0 && n1 >= 2.0 && n0 >= 2.0;
+    const double a2 = A * A;
+    double ss1 = B - a2 / n1, ss0 = (Qc - B) - a2 / n0;
+    ss1 = ss1 > 0.0 ? ss1 : 0.0;
+    ss0 = ss0 > 0.0 ? ss0 : 0.0;
+    const double v = ss1 / (n1 * (n1 - 1.0)) + ss0 / (n0 * (n0 - 1.0)), d = A * k;
+    double t2 = d * d / v;
+    if (!(v > 0.0)) t2 = A != 0.0 ? __builtin_inf() : 0.0;
+    return t2;
+}
+
+struct gpo_args {
+    gp_args g;                         // kf and dof unused
+    gpo_conn k;
+};
+
+template <bool MISS, bool WELCH>
+__global__ __launch_bounds__(64 * GP_WAVES) void group_observed_opt_kernel(gpo_args a) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t C = a.g.C, c0 = ((int64_t)blockIdx.x * GP_WAVES + wv) * 16;
+    if (c0 >= C) return;
+    const int col = lane & 15, ks = lane >> 4;
+    const int64_t c = c0 + col < C ? c0 + col : C - 1;       // (a column past the last reads the last row and writes nothing)
+    uint32_t lw[1][GP_NW];
+#pragma unroll
+    for (int w = 0; w < GP_NW; ++w) lw[0][w] = w < a.g.nw ? a.g.ws.LW[w * 64 + lane] : 0u;
+    double4_t acc[1], accn[1], accb[1];
+    gpo_tile_mma<1, MISS, WELCH>(a.g.ws.XT + c * 4 + ks, C * 4, MISS ? a.k.MW + c * 4 + ks : nullptr, C * 4, lw, a.g.nw, a.g.KS, acc,
+                                 accn, accb);
+    if (ks == 0 && c0 + col < C) {
+        const double A = acc[0][0];
+        bool def;
+        double t2 = gpo_t2<WELCH>(A, accb[0][0], MISS ? accn[0][0] : a.k.nU, MISS ? (double)a.k.NN[c] : a.k.nS, a.g.ws.Q[c], def);
+        if (!def) t2 = __builtin_nan("");
+        a.g.ws.t2obs[c] = t2;
+        a.g.t[c] = copysign(sqrt(t2), A);
+    }
+}
+
+template <bool MISS, bool WELCH>
+__global__ __launch_bounds__(64 * GP_WAVES) void baseline_group_opt_kernel(gpo_args a) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n = blockIdx.x, N = a.g.N, nw = a.g.nw;
+    const int64_t C = a.g.C, P = a.g.P, PG = (P + 15) / 16;
+    const int64_t pg0 = ((int64_t)blockIdx.y * GP_WAVES + wv) * GP_G;
+    if (pg0 >= PG) return;                                   // (no workgroup barrier below)
+    const int col = lane & 15, ks = lane >> 4;
+    uint32_t lw[GP_G][GP_NW];
+#pragma unroll
+    for (int g = 0; g < GP_G; ++g)
+#pragma unroll
+        for (int w = 0; w < GP_NW; ++w) lw[g][w] = (w < nw && pg0 + g < PG) ? a.g.ws.LW[((pg0 + g) * nw + w) * 64 + lane] : 0u;
+    double rs[GP_G][4], mx[GP_G][4];
+#pragma unroll
+    for (int g = 0; g < GP_G; ++g)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rs[g][r] = mx[g][r] = 0.0;
+    for (int k0 = 0; k0 < N - 1; k0 += 16) {
+        const int k = k0 + col;
+        const bool valid = k < N - 1;
+        int m;
+        const int64_t c = bl_edge(n, valid ? k : N - 2, m);  // (a column past the last reads the last row and is masked)
+        double4_t acc[GP_G], accn[GP_G], accb[GP_G];
+        const double nc = MISS ? (double)a.k.NN[c] : a.k.nS;
+        const bool counted = gpo_tile<GP_G, MISS, WELCH>(a.g.ws.XT + c * 4 + ks, C * 4, MISS ? a.k.MW + c * 4 + ks : nullptr, C * 4, lw, nw,
+                                                         a.g.KS, nc, a.k.nS, acc, accn, accb);
+        // result element r of group g: permutation (pg0 + g) 16 + ks + 4 r, connection k0 + col
+        const double Qc = a.g.ws.Q[c], t2o = a.g.ws.t2obs[c];
+        const bool live = valid && t2o == t2o;               // dead under the observed labelling: 0 to the sums, no maximum, no count
+        const bool own = live && k < n;
+        int cnt = 0;
+#pragma unroll
+        for (int g = 0; g < GP_G; ++g) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                bool def;
+                double t2 = gpo_t2<WELCH>(acc[g][r], accb[g][r], counted ? accn[g][r] : a.k.nU, nc, Qc, def);
+                const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
+                cnt += (own && p < P && (!def || t2 >= t2o)) ? 1 : 0;      // a labelling that cannot be evaluated counts
+                if (!live || !def) t2 = 0.0;
+                rs[g][r] += t2;
+                mx[g][r] = fmax(mx[g][r], t2);
+            }
+        }
+        cnt += __shfl_xor(cnt, 16, 64);
+        cnt += __shfl_xor(cnt, 32, 64);
+        if (own && ks == 0 && cnt) atomicAdd(&a.g.count_t[c], (unsigned long long)cnt);
+    }
+#pragma unroll
+    for (int g = 0; g < GP_G; ++g) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double s = rs[g][r], v = mx[g][r];
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                s += __shfl_xor(s, o, 64);
+                v = fmax(v, __shfl_xor(v, o, 64));
+            }
+            const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
+            if (col == 0 && p < P) {
+                a.g.ws.Rpart[(int64_t)n * P + p] = s;
+                a.g.ws.Mpart[(int64_t)n * P + p] = v;
+            }
+        }
+    }
+}
+
+struct nbo_args {
+    nb_args b;                         // kf and dof unused
+    gpo_conn k;
+};
+
+// network_bits_kernel with the options: NBO_G groups of 16 labellings per wave.  A connection that is undefined under the observed
+// labelling (from its own n, its observed patients and Q: no second pass) has no bit under any labelling.
+template <bool MISS, bool WELCH>
+__global__ __launch_bounds__(64 * GP_WAVES) void network_bits_opt_kernel(nbo_args a) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t piece = (int64_t)blockIdx.x * GP_WAVES + wv;
+    if (piece >= a.b.W2) return;                             // (no workgroup barrier below)
+    const int64_t C = a.b.C, P = a.b.P, PG = (P + 15) / 16, c0 = piece * 16;
+    const int64_t pg0 = (int64_t)blockIdx.y * NBO_G;
+    const int col = lane & 15, ks = lane >> 4;
+    if (c0 >= C) {
+#pragma unroll
+        for (int g = 0; g < NBO_G; ++g) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
+                if (col == 0 && p < P) a.b.bits[p * a.b.W2 + piece] = (uint16_t)0;
+            }
+        }
+        return;
+    }
+    const bool valid = c0 + col < C;
+    const int64_t c = valid ? c0 + col : C - 1;              // (a column past the last reads the last row and contributes 0)
+    uint32_t lw[NBO_G][GP_NW];
+#pragma unroll
+    for (int g = 0; g < NBO_G; ++g)
+#pragma unroll
+        for (int w = 0; w < GP_NW; ++w) lw[g][w] = (w < a.b.nw && pg0 + g < PG) ? a.b.LW[((pg0 + g) * a.b.nw + w) * 64 + lane] : 0u;
+    double4_t acc[NBO_G], accn[NBO_G], accb[NBO_G];
+    const double nc = MISS ? (double)a.k.NN[c] : a.k.nS;
+    const bool counted = gpo_tile<NBO_G, MISS, WELCH>(a.b.XT + c * 4 + ks, C * 4, MISS ? a.k.MW + c * 4 + ks : nullptr, C * 4, lw, a.b.nw,
+                                                      a.b.KS, nc, a.k.nS, acc, accn, accb);
+    const double Qc = a.b.Q[c], n1o = MISS ? (double)a.k.NO[c] : a.k.nU;
+    bool alive;
+    (void)gpo_t2<WELCH>(0.0, 0.0, n1o, nc, Qc, alive);       // defined under the observed labelling?
+#pragma unroll
+    for (int g = 0; g < NBO_G; ++g) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double A = acc[g][r];
+            bool def;
+            const double t2 = gpo_t2<WELCH>(A, accb[g][r], counted ? accn[g][r] : a.k.nU, nc, Qc, def);
+            const bool side = a.b.tail == 0 || (a.b.tail == 1 ? A > 0.0 : A < 0.0);
+            const unsigned long long mask = __ballot(valid && alive && def && side && t2 > a.b.thr2);
+            const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
+            if (col == 0 && p < P) a.b.bits[p * a.b.W2 + piece] = (uint16_t)(mask >> (16 * ks));
+            if (a.b.t && p == 0 && valid) a.b.t[c] = (alive && def) ? copysign(sqrt(t2), A) : __builtin_nan("");
+        }
+    }
+}
+
+// what the two calls with options check alike; who = the call's name
+__host__ static int gpo_check(fcd_ctx *ctx, const char *who, int64_t C, int64_t H, int64_t U, int64_t P, int flags) {
+    if (C < 1 || H < 1 || U < 1 || P < 1) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "C, H, U=%lld and P=%lld must be >= 1", U, P);
+    if (flags & ~(FCD_BASELINE_MISSING | FCD_BASELINE_WELCH)) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "unknown flags 0x%llx", flags);
+    if (H + U < 3) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "%lld subjects, a pooled variance needs 3", H + U);
+    if ((flags & FCD_BASELINE_WELCH) && (H < 2 || U < 2))
+        return fcd_fail_who(ctx, FCD_ERR_ARG, who, "welch: H=%lld and U=%lld must be >= 2, a variance per group", H, U);
+    if (fcd_C_to_N(C) < 2) return fcd_fail_who(ctx, FCD_ERR_SHAPE, who, "C=%lld is not a triangular number", C);
+    if (H + U > GP_SMAX) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "%lld subjects, at most %lld", H + U, GP_SMAX);
+    return FCD_OK;
+}
+
+// XT (KS, C, 4) | Q (C) | ... the caller's ... ; behind everything: MW (nw, C, 4) uint32 | NN (C) int32 | NO (C) int32
+__host__ static inline size_t gpo_conn_bytes(int64_t C, int nw) { return (size_t)((int64_t)nw * C * 4 + 2 * C) * sizeof(uint32_t); }
+
+#define GPO_DISPATCH(kern, flags, ...)                                                                     \
+    do {                                                                                                   \
+        if ((flags) == FCD_BASELINE_MISSING) hipLaunchKernelGGL((kern<true, false>), __VA_ARGS__);        \
+        else if ((flags) == FCD_BASELINE_WELCH) hipLaunchKernelGGL((kern<false, true>), __VA_ARGS__);     \
+        else hipLaunchKernelGGL((kern<true, true>), __VA_ARGS__);                                          \
+    } while (0)
+
 }  // namespace
 
 extern "C" int fcd_baseline_normative(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
@@ -766,6 +1126,145 @@ extern "C" int fcd_baseline_network_bits(fcd_ctx *ctx, const double *b, const do
     a.bits = reinterpret_cast<uint16_t *>(bits);
     a.t = t;
     hipLaunchKernelGGL(network_bits_kernel, dim3((unsigned)((2 * W + GP_WAVES - 1) / GP_WAVES), (unsigned)gy), dim3(64 * GP_WAVES), 0, st, a);
+    FCD_LAUNCH_CHECK();
+    return FCD_OK;
+}
+
+extern "C" int fcd_baseline_group_perm_opt(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                           const uint8_t *labels, int64_t P, int flags, double *t, double *region, double *null_max_t,
+                                           double *null_max_region, int64_t *count_t, int64_t *count_region, int64_t *n_controls,
+                                           int64_t *n_patients, fcd_stream stream) {
+    const char *who = "fcd_baseline_group_perm_opt";
+    if (!ctx || !b || !bt || !labels || !t || !region || !null_max_t || !null_max_region || !count_t || !count_region)
+        return fcd_fail_who(ctx, FCD_ERR_ARG, who, "null pointer");
+    int rc = gpo_check(ctx, who, C, H, U, P, flags);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (!flags) {                                            // no option: the call without them, and the counts it implies
+        rc = fcd_baseline_group_perm(ctx, b, bt, C, H, U, labels, P, t, region, null_max_t, null_max_region, count_t, count_region, stream);
+        if (rc || (!n_controls && !n_patients)) return rc;
+        hipLaunchKernelGGL(group_fill_counts_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, C, H, U, n_controls, n_patients);
+        FCD_LAUNCH_CHECK();
+        return FCD_OK;
+    }
+    const int64_t S = H + U, N = fcd_C_to_N(C);
+    const int64_t gy = (P + GP_PB - 1) / GP_PB;
+    if (N > 46340 || gy > 65535 || (C + GC_WAVES - 1) / GC_WAVES > INT32_MAX || N * P > (1ll << 34))
+        return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "shape too large (Nreg=%lld, P=%lld)", N, P);
+    const int KS = (int)((S + 3) / 4), nw = (KS + 31) / 32;
+    const bool miss = flags & FCD_BASELINE_MISSING;
+    // Nothing of the workspace outlives the call.
+    const size_t base = gp_ws_bytes(C, N, P, KS, nw);
+    rc = fcd_ws_reserve(ctx, base + gpo_conn_bytes(C, nw));
+    if (rc) return rc;
+    gpo_args a;
+    a.g.ws = gp_ws_at(ctx->ws, C, N, P, KS);
+    uint32_t *MW = (uint32_t *)((char *)ctx->ws + base);
+    int32_t *NN = (int32_t *)(MW + (int64_t)nw * C * 4), *NO = NN + C;
+    a.k.MW = MW;
+    a.k.NN = NN;
+    a.k.NO = NO;
+    a.k.nS = (double)S;
+    a.k.nU = (double)U;
+    a.g.C = C;
+    a.g.N = (int)N;
+    a.g.KS = KS;
+    a.g.nw = nw;
+    a.g.kf = 0.0;
+    a.g.dof = 0.0;
+    a.g.t = t;
+    a.g.count_t = reinterpret_cast<unsigned long long *>(count_t);
+    FCD_HIP_TRY(hipMemsetAsync(count_t, 0, (size_t)C * sizeof(int64_t), st));
+    const dim3 gc((unsigned)((C + GC_WAVES - 1) / GC_WAVES));
+    if (miss) {
+        hipLaunchKernelGGL(group_centre_missing_kernel, gc, dim3(64 * GC_WAVES), 0, st, b, bt, C, (int)H, (int)U, KS, nw, a.g.ws.XT, a.g.ws.Q,
+                           MW, NN, NO, n_controls, n_patients);
+        FCD_LAUNCH_CHECK();
+    } else {
+        hipLaunchKernelGGL(group_centre_kernel, gc, dim3(64 * GC_WAVES), 0, st, b, bt, C, (int)H, (int)U, KS, a.g.ws.XT, a.g.ws.Q);
+        FCD_LAUNCH_CHECK();
+        if (n_controls || n_patients) {
+            hipLaunchKernelGGL(group_fill_counts_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, C, H, U, n_controls, n_patients);
+            FCD_LAUNCH_CHECK();
+        }
+    }
+    // the observed labelling: one packed row through the same tile product and the same t^2, each connection once
+    a.g.P = 1;
+    hipLaunchKernelGGL(group_pack_kernel, dim3((unsigned)((nw * 64 + 255) / 256)), dim3(256), 0, st, (const uint8_t *)nullptr, (int64_t)1,
+                       (int)H, (int)S, nw, a.g.ws.LW);
+    FCD_LAUNCH_CHECK();
+    GPO_DISPATCH(group_observed_opt_kernel, flags, dim3((unsigned)((C + 16 * GP_WAVES - 1) / (16 * GP_WAVES))), dim3(64 * GP_WAVES), 0, st, a);
+    FCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(group_observed_region_kernel, dim3((unsigned)N), dim3(64), 0, st, a.g.ws.t2obs, (int)N, region);
+    FCD_LAUNCH_CHECK();
+    a.g.P = P;
+    const int64_t PG = (P + 15) / 16;
+    hipLaunchKernelGGL(group_pack_kernel, dim3((unsigned)((PG * nw * 64 + 255) / 256)), dim3(256), 0, st, labels, P, (int)H, (int)S, nw,
+                       a.g.ws.LW);
+    FCD_LAUNCH_CHECK();
+    GPO_DISPATCH(baseline_group_opt_kernel, flags, dim3((unsigned)N, (unsigned)gy), dim3(64 * GP_WAVES), 0, st, a);
+    FCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)(N + (P + 255) / 256)), dim3(256), 0, st, a.g.ws.Rpart, a.g.ws.Mpart, region, (int)N, P,
+                       null_max_region, null_max_t, count_region);
+    FCD_LAUNCH_CHECK();
+    return FCD_OK;
+}
+
+extern "C" int fcd_baseline_network_bits_opt(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                             const uint8_t *labels, int64_t P, double threshold, int tail, int flags, uint32_t *bits,
+                                             double *t, fcd_stream stream) {
+    const char *who = "fcd_baseline_network_bits_opt";
+    if (!ctx || !b || !bt || !bits) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "null pointer");
+    int rc = gpo_check(ctx, who, C, H, U, P, flags);
+    if (rc) return rc;
+    if (!flags) return fcd_baseline_network_bits(ctx, b, bt, C, H, U, labels, P, threshold, tail, bits, t, stream);
+    if (!labels && P != 1) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "the observed labelling (labels == NULL) is P = 1, not %lld", P);
+    if (!(threshold > 0.0) || !(threshold <= 1.7976931348623157e308))
+        return fcd_fail_who(ctx, FCD_ERR_ARG, who, "the threshold must be finite and > 0");
+    if (tail < FCD_TAIL_BOTH || tail > FCD_TAIL_LESS) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "unknown tail %lld", tail);
+    const int64_t S = H + U, N = fcd_C_to_N(C);
+    if (N > NB_NMAX) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "%lld regions, at most %lld", N, NB_NMAX);
+    const int64_t PG = (P + 15) / 16, gy = (PG + NBO_G - 1) / NBO_G, W = (C + 31) / 32;
+    if (gy > 65535) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "shape too large (Nreg=%lld, P=%lld)", N, P);
+    const int KS = (int)((S + 3) / 4), nw = (KS + 31) / 32;
+    hipStream_t st = (hipStream_t)stream;
+    // Nothing of the workspace outlives the call.
+    const size_t base = nb_ws_bytes(C, P, KS, nw);
+    rc = fcd_ws_reserve(ctx, base + gpo_conn_bytes(C, nw));
+    if (rc) return rc;
+    double *XT = (double *)ctx->ws, *Q = XT + (int64_t)KS * C * 4;
+    uint32_t *LW = (uint32_t *)(Q + C), *MW = (uint32_t *)((char *)ctx->ws + base);
+    int32_t *NN = (int32_t *)(MW + (int64_t)nw * C * 4), *NO = NN + C;
+    const dim3 gc((unsigned)((C + GC_WAVES - 1) / GC_WAVES));
+    if (flags & FCD_BASELINE_MISSING)
+        hipLaunchKernelGGL(group_centre_missing_kernel, gc, dim3(64 * GC_WAVES), 0, st, b, bt, C, (int)H, (int)U, KS, nw, XT, Q, MW, NN, NO,
+                           (int64_t *)nullptr, (int64_t *)nullptr);
+    else
+        hipLaunchKernelGGL(group_centre_kernel, gc, dim3(64 * GC_WAVES), 0, st, b, bt, C, (int)H, (int)U, KS, XT, Q);
+    FCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(group_pack_kernel, dim3((unsigned)((PG * nw * 64 + 255) / 256)), dim3(256), 0, st, labels, P, (int)H, (int)S, nw, LW);
+    FCD_LAUNCH_CHECK();
+    nbo_args a;
+    a.b.XT = XT;
+    a.b.Q = Q;
+    a.b.LW = LW;
+    a.b.C = C;
+    a.b.P = P;
+    a.b.W2 = 2 * W;
+    a.b.KS = KS;
+    a.b.nw = nw;
+    a.b.tail = tail;
+    a.b.kf = 0.0;
+    a.b.dof = 0.0;
+    a.b.thr2 = threshold * threshold;
+    a.b.bits = reinterpret_cast<uint16_t *>(bits);
+    a.b.t = t;
+    a.k.MW = MW;
+    a.k.NN = NN;
+    a.k.NO = NO;
+    a.k.nS = (double)S;
+    a.k.nU = (double)U;
+    GPO_DISPATCH(network_bits_opt_kernel, flags, dim3((unsigned)((2 * W + GP_WAVES - 1) / GP_WAVES), (unsigned)gy), dim3(64 * GP_WAVES), 0, st, a);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
 }

@@ -442,6 +442,37 @@ int fcd_baseline_group_perm(fcd_ctx *ctx, const double *b, const double *bt, int
 int fcd_baseline_network_bits(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
                               const uint8_t *labels, int64_t P, double threshold, int tail, uint32_t *bits, double *t,
                               fcd_stream stream);
+/* The two calls above with options, flags = FCD_BASELINE_MISSING | FCD_BASELINE_WELCH; flags = 0 is the call above itself.
+ * FCD_BASELINE_MISSING: a NaN in b or bt is an unobserved value (an infinite value is not checked here and spreads).  Per
+ * connection c: O = the subjects observed there, n = |O|; the row is centred on its mean over O, x_s = 0 for a missing
+ * subject, Q = sum x^2; the connection is constant where all observed values are equal (x and Q exactly 0).  Per labelling l
+ * (still U ones over all S subjects, observed or not): n1 = sum over O of l_s, n0 = n - n1, A = sum l_s x_s, B = sum l_s x_s^2,
+ * k = n / (n1 n0); the mean difference is A k.  Without the flag n = S and n1 = U.
+ *   pooled (no FCD_BASELINE_WELCH)  defined iff the connection is not constant, n >= 3, n1 >= 1 and n0 >= 1.  g = A^2 k,
+ *       t^2 = g (n - 2) / (Q - g), +inf where Q - g is not > 0; on complete data the call above operation for operation.
+ *   FCD_BASELINE_WELCH  defined iff the connection is not constant, n1 >= 2 and n0 >= 2.  SS1 = max(B - A^2/n1, 0),
+ *       SS0 = max((Q - B) - A^2/n0, 0), v = SS1/(n1 (n1 - 1)) + SS0/(n0 (n0 - 1)), t^2 = (A k)^2 / v; where v is not > 0,
+ *       t^2 = +inf if A != 0 and 0 if A = 0.
+ * The sign of t is that of A.  A value that is undefined under a labelling adds exactly 0 to every region sum, enters no
+ * maximum and is never a set bit, but counts as an exceedance in count_t (a labelling that cannot be evaluated never makes a
+ * p-value smaller).  A connection that is undefined under the observed labelling is dead, as a constant one: t = NaN,
+ * count_t = 0, no part in region or in any permuted sum, maximum or bit.  A row of labels equal to the observed labelling
+ * still gives the observed statistics bit for bit.  n_controls, n_patients (C,), each nullable: the observed controls and
+ * patients per connection (H and U without FCD_BASELINE_MISSING).  The accumulators n1 and B go through the same fp64 MFMA tile
+ * product as A; the observation mask travels as bits (nw C 16 bytes of workspace more, nw = ceil(S / 128)).
+ * Refusals as for the calls above; other bits in flags FCD_ERR_UNSUPPORTED; FCD_BASELINE_WELCH with H < 2 or U < 2
+ * FCD_ERR_ARG; fcd_baseline_network_bits_opt takes P <= 65535 * 32 with a flag set. */
+#define FCD_BASELINE_MISSING 1
+#define FCD_BASELINE_WELCH 2
+int fcd_baseline_group_perm_opt(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                const uint8_t *labels, int64_t P, int flags, double *t, double *region, double *null_max_t,
+                                double *null_max_region, int64_t *count_t, int64_t *count_region, int64_t *n_controls,
+                                int64_t *n_patients, fcd_stream stream);
+/* The bits with the same options and rules: a value undefined under its labelling, and every value of a connection that is
+ * undefined under the observed labelling, is never a set bit; t (labelling 0) is NaN there. */
+int fcd_baseline_network_bits_opt(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                  const uint8_t *labels, int64_t P, double threshold, int tail, int flags, uint32_t *bits,
+                                  double *t, fcd_stream stream);
 /* The components: per row of bits (B, W) the connected components of the graph on the Nreg regions whose edges are the set
  * bits; bits behind C in the last word are ignored.  A component's label is its smallest region, its extent its number of
  * connections.  component (B, Nreg), nullable: the label of each region's component, -1 for a region without an edge.
