@@ -80,6 +80,8 @@ SIGNATURES = {
     "fcd_baseline_network_bits": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _dbl, _int, _p, _p, _p]),
     "fcd_baseline_group_perm_opt": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _int, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "fcd_baseline_network_bits_opt": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _dbl, _int, _int, _p, _p, _p]),
+    "fcd_baseline_group_glm": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
+    "fcd_baseline_network_bits_glm": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _dbl, _int, _p, _p, _p]),
     "fcd_graph_components": (_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
     "fcd_vb_update_qF": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
     "fcd_vb_update_qR": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _p, _p]),

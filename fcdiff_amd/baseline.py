@@ -16,6 +16,11 @@ group_test() and network_test() take missing_data=True (a NaN is an unobserved v
 either goes through fcd_baseline_group_perm_opt / fcd_baseline_network_bits_opt, the default call through the entry points
 it always used.  Oracle = tests/baseline_missing_ref.py.
 
+group_test() and network_test() take nuisance covariates z_b (H, Q), z_bt (U, Q) (the covariates module's names and shapes):
+the permutation GLM of Freedman & Lane, whole permutations of the subjects in place of labellings, through
+fcd_baseline_group_glm / fcd_baseline_network_bits_glm.  glm_design() makes the design on the host, draw_permutations() the
+permutations.  Oracle = tests/baseline_glm_ref.py.
+
 b (C, H) controls and bt (C, U) patients, NumPy arrays or torch tensors, float64, connections in util.c_to_nm order;
 E(n) = the N - 1 connections that touch region n.  Both run on the device (fcd_baseline_normative,
 fcd_baseline_group_perm of include/fcdiff_hip.h) and have no CPU fallback; the p-values are made on the host from what the
@@ -218,7 +223,148 @@ def _options(who, b, bt, H, U, missing_data, variance):
     return (FLAG_MISSING if missing_data else 0) | (FLAG_WELCH if variance == "welch" else 0)
 
 
-def group_test(b, bt, n_perm=10000, *, missing_data=False, variance="pooled", seed=0, labels=None, ctx=None, as_numpy=True):
+# ---- nuisance covariates: the permutation GLM ----------------------------------------------------------------------------------
+
+GLM_MAX_COLUMNS = 8       # covariate columns kept: the design has at most 9 columns (fcd_baseline_group_glm)
+GLM_DROP_TOL = 1e-10      # covariates.fit_adjustment's rule: remaining squared norm of a unit column below this -> dropped
+GLM_CONTRAST_TOL = 1e-10  # ||x_r||^2 must be > this multiple of ||x_c||^2: the group is not a function of the covariates
+
+
+def draw_permutations(n_perm, S, seed=0):
+    """(n_perm, S) int64 rows, each a permutation of 0 .. S - 1: numpy.random.default_rng(seed), one rng.permutation(S) per row."""
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.permutation(int(S)) for _ in range(int(n_perm))]).astype(np.int64).reshape(int(n_perm), int(S))
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def _sweep(v, basis):
+    """v minus its mean and its components along the orthonormal basis, twice (the second pass takes the first's rounding)."""
+    for _ in range(2):
+        v = v - v.mean()
+        for w in basis:
+            v = v - w * w.dot(v)
+    return v
+
+
+def glm_design(z_b, z_bt):
+    """
+    The design of the permutation GLM from the covariates z_b (H, Q) of the controls and z_bt (U, Q) of the patients.  Host
+    only, NumPy float64.  The rules are covariates.fit_adjustment's: the columns of Z = [z_b; z_bt] are centred over the
+    S = H + U subjects, a constant one (min == max) is dropped, the others are scaled to unit norm, collinear ones are dropped
+    by diagonally pivoted Cholesky of their Gram matrix (remaining squared norm below 1e-10, ties to the lowest index).  The
+    Q' columns kept give an orthonormal basis w_1 .. w_Q' of the centred nuisance space (Gram-Schmidt in pivot order, twice);
+    x = the group indicator (1 on the last U subjects), x_c = x - U/S, x_r = x_c - sum_q w_q (w_q^T x_c), w_0 = x_r / ||x_r||.
+
+    Returns (W, info): W (S, Q' + 1) = [w_0, w_1, .., w_Q'], columns orthonormal and orthogonal to the constant; info a dict
+    with used (Q,) bool, the columns kept, in the order of the columns of z; rank = Q'; dof = S - Q' - 2.
+    ValueError: shapes that do not agree, a NaN or an infinite value, S < Q' + 3, or ||x_r||^2 not > 1e-10 ||x_c||^2 (the
+    group is a function of the covariates).  NotImplementedError: Q' > 8.
+    """
+    (zb, zt) = (np.asarray(_host(z_b), dtype=np.float64), np.asarray(_host(z_bt), dtype=np.float64))
+    if zb.ndim != 2 or zt.ndim != 2 or zb.shape[1] != zt.shape[1] or zb.shape[0] < 1 or zt.shape[0] < 1:
+        raise ValueError("glm_design: z_b must have shape (H, Q) and z_bt (U, Q), not %s and %s" % (zb.shape, zt.shape))
+    if not (np.isfinite(zb).all() and np.isfinite(zt).all()):
+        raise ValueError("glm_design: NaN or infinite value in z_b or z_bt")
+    (H, U, Q) = (zb.shape[0], zt.shape[0], zb.shape[1])
+    S = H + U
+    Z = np.concatenate([zb, zt], axis=0)
+    Zc = Z - Z.mean(axis=0)[None, :]
+    live = [q for q in range(Q) if Z[:, q].min() != Z[:, q].max()]
+    V = np.zeros((S, Q))
+    for q in live:
+        V[:, q] = Zc[:, q] / np.sqrt(Zc[:, q].dot(Zc[:, q]))
+    G = V.T.dot(V)
+    for q in range(Q):
+        G[q, q] = 1.0 if q in live else 0.0
+    (piv, taken) = ([], np.zeros(Q, dtype=bool))
+    for _k in range(Q):
+        dg = np.where(taken, -1.0, np.diagonal(G))
+        p = int(np.argmax(dg))                                   # (ties to the lowest index)
+        if not dg[p] >= GLM_DROP_TOL:
+            break
+        lpp = np.sqrt(dg[p])
+        free = ~taken
+        free[p] = False
+        G[free, p] = G[free, p] / lpp
+        G[np.ix_(free, free)] -= np.outer(G[free, p], G[free, p])
+        taken[p] = True
+        piv.append(p)
+    rank = len(piv)
+    if rank > GLM_MAX_COLUMNS:
+        raise NotImplementedError("glm_design: %d covariate columns kept, at most %d" % (rank, GLM_MAX_COLUMNS))
+    if S < rank + 3:
+        raise ValueError("glm_design: %d subjects, %d covariate columns need %d" % (S, rank, rank + 3))
+    basis = []
+    for p in piv:
+        v = _sweep(V[:, p], basis)
+        basis.append(v / np.sqrt(v.dot(v)))
+    x = np.concatenate([np.zeros(H), np.ones(U)])
+    xc = x - float(U) / float(S)
+    xr = _sweep(xc, basis)
+    if not xr.dot(xr) > GLM_CONTRAST_TOL * xc.dot(xc):
+        raise ValueError("glm_design: the group is a linear function of the covariates (||x_r||^2 = %.3g ||x_c||^2)"
+                         % (xr.dot(xr) / xc.dot(xc)))
+    W = np.ascontiguousarray(np.stack([xr / np.sqrt(xr.dot(xr))] + basis, axis=1))
+    used = np.zeros(Q, dtype=bool)
+    used[piv] = True
+    return W, {"used": used, "rank": rank, "dof": S - rank - 2}
+
+
+def _check_permutations(who, permutations, S):
+    perm = _host(permutations)
+    if perm.ndim != 2 or perm.shape[1] != S or perm.shape[0] < 1:
+        raise ValueError("%s: permutations must have shape (P, %d) with P >= 1, not %s" % (who, S, perm.shape))
+    if perm.dtype.kind not in "iu":
+        raise ValueError("%s: permutations must hold integers" % who)
+    perm = np.ascontiguousarray(perm.astype(np.int64))
+    if not (np.sort(perm, axis=1) == np.arange(S, dtype=np.int64)[None, :]).all():
+        raise ValueError("%s: every row of permutations must be a permutation of 0 .. %d" % (who, S - 1))
+    return perm
+
+
+def _glm_setup(who, b, bt, H, U, z_b, z_bt, permutations, labels, missing_data, variance, n_perm, seed):
+    """
+    The host checks of a call with covariates, all before a context exists -> (W, info, permutations (P, S) int64), or None
+    for a call without them.
+    """
+    if (z_b is None) != (z_bt is None):
+        raise ValueError("%s: z_b and z_bt must be given together" % who)
+    if z_b is None:
+        if permutations is not None:
+            raise ValueError("%s: permutations belong to a call with covariates (z_b, z_bt); without them pass labels" % who)
+        return None
+    if labels is not None:
+        raise ValueError("%s: labels with covariates: a labelling does not say whose covariates go where; pass permutations" % who)
+    if variance not in ("pooled", "welch"):
+        raise ValueError("%s: variance must be 'pooled' or 'welch', not %r" % (who, variance))
+    if missing_data or variance == "welch":
+        raise NotImplementedError("%s: covariates with missing_data=True or variance='welch' are not provided: every "
+                                  "connection would have its own design" % who)
+    (sb, st) = (_shape(z_b), _shape(z_bt))
+    if len(sb) != 2 or len(st) != 2 or sb[0] != H or st[0] != U or sb[1] != st[1]:
+        raise ValueError("%s: z_b must have shape (%d, Q) and z_bt (%d, Q), not %s and %s" % (who, H, U, sb, st))
+    _refuse_nonfinite(b, bt, who, "the data must be complete and finite")
+    (W, info) = glm_design(z_b, z_bt)
+    if permutations is None:
+        if int(n_perm) < 1:
+            raise ValueError("%s: n_perm must be >= 1" % who)
+        perm = draw_permutations(n_perm, H + U, seed)
+    else:
+        perm = _check_permutations(who, permutations, H + U)
+    return W, info, perm
+
+
+def _device_perms(perm, dev):
+    """(P, S) int64 on the host -> the uint16 the device reads, as an int16 tensor (the same bits)."""
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(perm.astype(np.uint16)).view(np.int16), device=dev)
+
+
+def group_test(b, bt, n_perm=10000, *, missing_data=False, variance="pooled", seed=0, labels=None, z_b=None, z_bt=None,
+               permutations=None, ctx=None, as_numpy=True):
     """
     Mass-univariate two-sample test of patients against controls with permutation inference.  b (C, H), bt (C, U), complete
     unless missing_data=True.  What follows first describes the default call (missing_data=False, variance="pooled").
@@ -258,6 +404,25 @@ def group_test(b, bt, n_perm=10000, *, missing_data=False, variance="pooled", se
     p_fwe_t NaN, no part in region or in any permuted sum or maximum.  The identity-row property and the repeatability hold
     with either option.
 
+    z_b (H, Q), z_bt (U, Q): nuisance covariates (age, sex, site dummies, motion, ...) by the permutation GLM of Freedman &
+    Lane (1983; Winkler et al. 2014), what FSL randomise, PALM and the NBS toolbox run.  glm_design(z_b, z_bt) gives the
+    orthonormal W = [w_0, w_1 .. w_Q'] (w_0 the group indicator residualised on the Q' covariate columns kept) and
+    dof = S - Q' - 2.  Per connection e = the residuals of the row on the nuisance model [1, Z], Q_e = sum e^2.  A
+    permutation pi of 0 .. S - 1 gives subject s the design row pi[s] (the residuals permuted by its inverse under the fixed
+    design): d_q = sum_s W[pi[s], q] e_s, t^2 = d_0^2 dof / (Q_e - sum_q d_q^2), t with the sign of d_0 (t > 0: patients
+    above controls).  The observed statistics are those of the identity.  permutations: (P, S) integers, every row a
+    permutation; not given, draw_permutations(n_perm, S, seed).  labels= is refused: a labelling does not say whose
+    covariates go where.  A row equal to the identity counts and gives the observed statistics bit for bit.  The rules for
+    constant and separated connections hold unchanged; dead too (t NaN and all that follows) is a connection with
+    Q_e <= (8 S (Q' + 1) 2^-52)^2 Q_c: a linear function of the covariates to rounding.  The dict gains permutations (P, S)
+    int64 as used and design_info (glm_design's: used, rank, dof); labels is (pi >= H).  Where every column is dropped
+    (Q' = 0) the call is the default call with those labels, bit for bit.  ValueError before any context exists: z_b without
+    z_bt, shapes that do not agree, a NaN or an infinite covariate, S < Q' + 3, a group that is a linear function of the
+    covariates, a row that is no permutation.  NotImplementedError: Q' > 8.
+    Not provided with covariates: missing_data or Welch's t (every connection would have its own design: NotImplementedError),
+    more than 8 columns, contrasts other than the group (the C entry point tests column 0 of any orthonormal design), F-tests,
+    exchangeability blocks (permuting within site), sessions, noise variances.
+
     Without missing_data a NaN or an infinite value is a ValueError; more than 1024 subjects a NotImplementedError.
     Not provided: sessions, noise variances, cluster statistics.  The network-based statistic is network_test().
     """
@@ -268,6 +433,9 @@ def group_test(b, bt, n_perm=10000, *, missing_data=False, variance="pooled", se
         raise NotImplementedError("group_test: %d subjects, at most %d" % (S, MAX_SUBJECTS))
     if S < 3:
         raise ValueError("group_test: %d subjects, a pooled variance needs 3" % S)
+    glm = _glm_setup("group_test", b, bt, H, U, z_b, z_bt, permutations, labels, missing_data, variance, n_perm, seed)
+    if glm is not None:
+        return _group_test_glm(b, bt, C, N, H, U, glm, ctx, as_numpy)
     flags = _options("group_test", b, bt, H, U, missing_data, variance)
     if labels is None:
         if int(n_perm) < 1:
@@ -309,6 +477,46 @@ def group_test(b, bt, n_perm=10000, *, missing_data=False, variance="pooled", se
     else:
         out.update(dict((k, torch.as_tensor(v, device=dev)) for (k, v) in pv.items()))
         out["labels"] = labd
+    return out
+
+
+def _group_test_glm(b, bt, C, N, H, U, glm, ctx, as_numpy):
+    """group_test() with covariates, behind its host checks."""
+    import torch
+    (W, info, perm) = glm
+    lab = (perm >= H).astype(np.uint8)
+    if info["rank"] == 0:                                        # every column dropped: the default call with those labels
+        out = group_test(b, bt, labels=lab, ctx=ctx, as_numpy=as_numpy)
+        out["permutations"] = perm if as_numpy else torch.as_tensor(perm, device=out["t"].device)
+        out["design_info"] = info
+        return out
+    P = int(perm.shape[0])
+    ctx = ctx if ctx is not None else _lib.Context()
+    (bd, btd) = (_device_f64(b, ctx), _device_f64(bt, ctx))
+    dev = ctx.device
+    (Wd, permd) = (_device_f64(W, ctx), _device_perms(perm, dev))
+    t = torch.empty((C,), dtype=torch.float64, device=dev)
+    region = torch.empty((N,), dtype=torch.float64, device=dev)
+    null_max_t = torch.empty((P,), dtype=torch.float64, device=dev)
+    null_max_region = torch.empty((P,), dtype=torch.float64, device=dev)
+    count_t = torch.empty((C,), dtype=torch.int64, device=dev)
+    count_region = torch.empty((N,), dtype=torch.int64, device=dev)
+    out = {"t": t, "region": region, "null_max_t": null_max_t, "null_max_region": null_max_region, "count_t": count_t,
+           "count_region": count_region}
+    ctx.call("fcd_baseline_group_glm", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(Wd), int(W.shape[1]), _lib.dptr(permd), P,
+             _lib.dptr(t), _lib.dptr(region), _lib.dptr(null_max_t), _lib.dptr(null_max_region), _lib.dptr(count_t),
+             _lib.dptr(count_region), _lib.stream_ptr())
+    host = dict((k, v.cpu().numpy()) for (k, v) in out.items())
+    pv = group_pvalues(host["t"], host["region"], host["null_max_t"], host["null_max_region"], host["count_t"],
+                       host["count_region"])
+    if as_numpy:
+        out = host
+        out.update(pv)
+        out.update(labels=lab, permutations=perm)
+    else:
+        out.update(dict((k, torch.as_tensor(v, device=dev)) for (k, v) in pv.items()))
+        out.update(labels=torch.as_tensor(lab, device=dev), permutations=torch.as_tensor(perm, device=dev))
+    out["design_info"] = info
     return out
 
 
@@ -413,7 +621,7 @@ def graph_components(mask, *, ctx=None, as_numpy=True):
 
 
 def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=False, variance="pooled", seed=0, labels=None,
-                 ctx=None, as_numpy=True):
+                 z_b=None, z_bt=None, permutations=None, ctx=None, as_numpy=True):
     """
     The network-based statistic (Zalesky, Fornito & Bullmore 2010): which sub-networks differ between patients and controls?
     b (C, H), bt (C, U), complete unless missing_data=True.
@@ -437,9 +645,13 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=Fa
     null_n_edges (P,) int64 = per labelling the largest extent, the regions of the component with the most regions, the
     suprathreshold connections; p_fwe (K,) = (1 + #{p: null_max_extent[p] >= extent}) / (1 + P); p_fwe_region (N,) = the p of
     the region's component, NaN at label -1; labels (P, S) uint8 as used; threshold, tail.
+    z_b (H, Q), z_bt (U, Q), permutations: nuisance covariates exactly as in group_test() -- its permutation GLM, its t
+    (the side of "greater" / "less" is the sign of d_0), its refusals (labels=, missing_data and Welch's t included) and its
+    keys permutations and design_info; labels is (pi >= H).  A row equal to the identity gives the observed bits exactly;
+    permutations are walked in chunks as labellings are.  Where every column is dropped the call is the default call.
     Refused: everything group_test() refuses; a threshold that is not finite and > 0 or an unknown tail (ValueError); more
     than 1024 regions (NotImplementedError).  Not provided: the intensity form sum (|t| - threshold) (it would need a value
-    per bit), TFCE, sessions, noise variances.
+    per bit), TFCE, sessions, noise variances; with covariates also what group_test() lists.
     """
     import torch
     (C, N, H, U) = _check_pair(b, bt, "network_test")
@@ -455,25 +667,42 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=Fa
         raise ValueError("network_test: threshold must be finite and > 0, not %r" % (threshold,))
     if tail not in TAILS:
         raise ValueError("network_test: tail must be one of 'both', 'greater', 'less', not %r" % (tail,))
-    flags = _options("network_test", b, bt, H, U, missing_data, variance)
-    if labels is None:
-        if int(n_perm) < 1:
-            raise ValueError("network_test: n_perm must be >= 1")
-        lab = draw_labels(n_perm, H, U, seed)
+    glm = _glm_setup("network_test", b, bt, H, U, z_b, z_bt, permutations, labels, missing_data, variance, n_perm, seed)
+    if glm is not None and glm[1]["rank"] == 0:                  # every column dropped: the default call with those labels
+        out = network_test(b, bt, thr, tail=tail, labels=(glm[2] >= H).astype(np.uint8), ctx=ctx, as_numpy=as_numpy)
+        out["permutations"] = glm[2] if as_numpy else torch.as_tensor(glm[2], device=out["t"].device)
+        out["design_info"] = glm[1]
+        return out
+    if glm is not None:
+        flags = 0
+        lab = (glm[2] >= H).astype(np.uint8)
     else:
-        lab = _check_labels(labels, S, U)
+        flags = _options("network_test", b, bt, H, U, missing_data, variance)
+        if labels is None:
+            if int(n_perm) < 1:
+                raise ValueError("network_test: n_perm must be >= 1")
+            lab = draw_labels(n_perm, H, U, seed)
+        else:
+            lab = _check_labels(labels, S, U)
     P = int(lab.shape[0])
     ctx = ctx if ctx is not None else _lib.Context()
     (bd, btd) = (_device_f64(b, ctx), _device_f64(bt, ctx))
     dev = ctx.device
     labd = torch.as_tensor(lab, device=dev)
     W = (C + 31) // 32
+    if glm is not None:
+        (designd, rows) = (_device_f64(glm[0], ctx), _device_perms(glm[2], dev))
+    else:
+        rows = labd
 
     def i32(*sh):
         return torch.empty(sh, dtype=torch.int32, device=dev)
 
     def bits_call(lab_c, n, bits, t):
-        if flags == 0:
+        if glm is not None:
+            ctx.call("fcd_baseline_network_bits_glm", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(designd),
+                     int(designd.shape[1]), _lib.dptr(lab_c), n, thr, TAILS[tail], _lib.dptr(bits), _lib.dptr(t), _lib.stream_ptr())
+        elif flags == 0:
             ctx.call("fcd_baseline_network_bits", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(lab_c), n, thr, TAILS[tail],
                      _lib.dptr(bits), _lib.dptr(t), _lib.stream_ptr())
         else:
@@ -490,7 +719,7 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=Fa
     for p0 in range(0, P, _P_CHUNK):
         n = min(_P_CHUNK, P - p0)
         bits = i32(n, W)
-        bits_call(labd[p0:p0 + n], n, bits, None)
+        bits_call(rows[p0:p0 + n], n, bits, None)
         _components_call(ctx, bits, n, C, N, None, null_n_edges[p0:p0 + n], null_max_extent[p0:p0 + n],
                          null_max_regions[p0:p0 + n])
     host = {"t": t.cpu().numpy(), "component": component[0].long().cpu().numpy(),
@@ -508,6 +737,9 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=Fa
         host["n_patients"] = (~torch.isnan(btd)).sum(dim=1).cpu().numpy()
     out = host if as_numpy else dict((k, torch.as_tensor(v, device=dev)) for (k, v) in host.items())
     out["labels"] = lab if as_numpy else labd
+    if glm is not None:
+        out["permutations"] = glm[2] if as_numpy else torch.as_tensor(glm[2], device=dev)
+        out["design_info"] = glm[1]
     out["threshold"] = thr
     out["tail"] = tail
     return out

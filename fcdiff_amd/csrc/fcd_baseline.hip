@@ -55,6 +55,9 @@
 //                      observed labelling is a call with P = 1 through the same kernel.
 //                      (fcd_baseline_group_perm_opt, fcd_baseline_network_bits_opt: the same with missing data and Welch's t,
 //                      kernels of their own at the end of the namespace; oracle = tests/baseline_missing_ref.py.)
+//                      (fcd_baseline_group_glm, fcd_baseline_network_bits_glm: the same with nuisance covariates, the A operand a
+//                      double read from the design in LDS by a permuted index; kernels of their own behind those, where they
+//                      are described; oracle = tests/baseline_glm_ref.py.)
 //   graph_components_kernel  one workgroup per row of bits, the row in LDS (64 KB at 1024 regions, the limit).  label[x] = x;
 //                      per round every set bit (n, m) pulls the larger label, and the region that label names, down to the
 //                      smaller (LDS atomicMin), then label[x] = label[label[x]]; until a round changes nothing, at most N
@@ -988,6 +991,348 @@ __host__ static inline size_t gpo_conn_bytes(int64_t C, int nw) { return (size_t
         else hipLaunchKernelGGL((kern<true, true>), __VA_ARGS__);                                          \
     } while (0)
 
+// ---- nuisance covariates: the permutation GLM of Freedman & Lane ------------------------------------------------------------
+// fcd_baseline_group_glm, fcd_baseline_network_bits_glm; oracle = tests/baseline_glm_ref.py.  The design W (S, R) is orthonormal,
+// every column orthogonal to the constant; column 0 is tested given the others.  Per connection e = the residuals of the row on
+// [1, w_1 .. w_{R-1}], Q_e = sum e^2; per permutation pi, d_q = sum_s W[pi[s], q] e_s, t^2 = d_0^2 dof / (Q_e - sum_q d_q^2),
+// dof = S - R - 1, the sign of t that of d_0.  The A operand of the MFMA is no longer a bit but a double picked by an index:
+//   glm_centre_kernel  group_centre_kernel with the residualisation: columns 1 .. R - 1 of W in LDS (column-major), the mean, the
+//                      R - 1 coefficients a_q = sum w_q (x - mean) as wave sums, q ascending, then e = (x - mean) - sum_q w_q a_q
+//                      (q ascending), Q_e and Q_c = sum (x - mean)^2.  Writes XT exactly as group_centre_kernel does.  Dead rows
+//                      (e and Q exactly 0): constant ones (min == max), and those with Q_e <= dead2 Q_c, dead2 =
+//                      (8 S R 2^-52)^2: a row that is a linear function of the covariates to rounding (derivation: DESIGN.md).
+//   glm_pack_kernel    the indices of 16 permutations x 4 K-steps as four uint16 in one uint64 per lane: field i of lane l of
+//                      quad j4 = perms[16 pg + (l & 15)][4 (4 j4 + i) + (l >> 4)], what that lane feeds the MFMA as the row of
+//                      W at K-step 4 j4 + i.  S -- a row of zeros behind W in LDS -- behind the last subject, behind the last
+//                      permutation and for an index that is out of range.  perms == nullptr: the identity.
+//   glm_tile_mma       W as (S + 1, RT) rows in the workgroup's LDS, RT = 2, 3, 5 or 9 >= R, zero columns behind R.  Per
+//                      K-step the B value is loaded once (gp_tile_mma's addressing) and feeds all RT MFMAs of every group;
+//                      per group one 8-byte index load per four K-steps, per MFMA one 8-byte LDS read at the lane's own row.
+//   glm_t2             gp_t2 on (d_0, sum_q d_q^2, Q_e, dof), under the same guards.
+//   glm_observed_kernel, glm_group_kernel, glm_bits_kernel   group_observed_kernel, baseline_group_kernel and
+//                      network_bits_kernel around that tile product: the same running sums and maxima in tile order, the same
+//                      butterfly, integer atomics by the endpoint n > m, one ballot per (group, element).  The observed
+//                      statistics are the identity permutation through the same product, so a row of perms equal to the
+//                      identity gives them bit for bit.  group_observed_region_kernel and group_fold_kernel are reused.
+
+constexpr int GL_G = 2;                  // groups of 16 permutations per wave, both kernels: GL_G * RT accumulators of 8 VGPRs
+constexpr int GL_RMAX = 9;
+
+__global__ __launch_bounds__(64 * GC_WAVES) void glm_centre_kernel(const double *__restrict__ b, const double *__restrict__ bt, int64_t C,
+                                                                   int H, int U, int KS, const double *__restrict__ design, int R,
+                                                                   double dead2, double *__restrict__ XT, double *__restrict__ Q) {
+    extern __shared__ double gl_wc[];                        // column q >= 1 of W at gl_wc[(q - 1) S + s]
+    const int S = H + U;
+    for (int i = threadIdx.x; i < (R - 1) * S; i += 64 * GC_WAVES) gl_wc[i] = design[(int64_t)(i % S) * R + (i / S + 1)];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t c = (int64_t)blockIdx.x * GC_WAVES + wv;
+    if (c >= C) return;                                      // (no workgroup barrier below)
+    const double *__restrict__ br = b + c * H, *__restrict__ tr = bt + c * U;
+    const double x0 = br[0];
+    double s = 0.0;
+    bool same = true;
+    for (int i = lane; i < S; i += 64) {
+        const double v = i < H ? br[i] : tr[i - H];
+        s += v;
+        same = same && v == x0;
+    }
+    const bool constant = __ballot(!same) == 0ull;           // all S values equal: centred values and Q are exactly 0
+    const double mean = fcd_wave_sum(s) / (double)S;
+    double a[GL_RMAX - 1];
+#pragma unroll
+    for (int q = 0; q < GL_RMAX - 1; ++q) {
+        a[q] = 0.0;
+        if (q < R - 1) {                                     // (uniform)
+            double d = 0.0;
+            for (int i = lane; i < S; i += 64) {
+                const double xc = constant ? 0.0 : (i < H ? br[i] : tr[i - H]) - mean;
+                d += gl_wc[q * S + i] * xc;
+            }
+            a[q] = fcd_wave_sum(d);
+        }
+    }
+    double qe = 0.0, qc = 0.0;
+    for (int i = lane; i < 4 * KS; i += 64) {
+        double xc = 0.0, e = 0.0;
+        if (i < S && !constant) {
+            xc = (i < H ? br[i] : tr[i - H]) - mean;
+            e = xc;
+#pragma unroll
+            for (int q = 0; q < GL_RMAX - 1; ++q)
+                if (q < R - 1) e -= gl_wc[q * S + i] * a[q];
+        }
+        qe += e * e;
+        qc += xc * xc;
+        XT[((int64_t)(i >> 2) * C + c) * 4 + (i & 3)] = e;
+    }
+    qe = fcd_wave_sum(qe);
+    qc = fcd_wave_sum(qc);
+    const bool dead = !(qe > dead2 * qc);                    // constant (0 > 0), or nothing left beside the covariates
+    if (dead)
+        for (int i = lane; i < 4 * KS; i += 64) XT[((int64_t)(i >> 2) * C + c) * 4 + (i & 3)] = 0.0;
+    if (lane == 0) Q[c] = dead ? 0.0 : qe;
+}
+
+__global__ __launch_bounds__(256) void glm_pack_kernel(const uint16_t *__restrict__ perms, int64_t P, int S, int KS4,
+                                                       uint64_t *__restrict__ PI) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x, PG = (P + 15) / 16;
+    if (idx >= PG * KS4 * 64) return;
+    const int lane = (int)(idx & 63), j4 = (int)((idx >> 6) % KS4);
+    const int64_t p = ((idx >> 6) / KS4) * 16 + (lane & 15);
+    uint64_t word = 0;
+    for (int i = 0; i < 4; ++i) {
+        const int s = 4 * (4 * j4 + i) + (lane >> 4);
+        uint32_t v = (uint32_t)S;
+        if (p < P && s < S) {
+            v = perms ? (uint32_t)perms[p * S + s] : (uint32_t)s;
+            if (v > (uint32_t)S) v = (uint32_t)S;
+        }
+        word |= (uint64_t)v << (16 * i);
+    }
+    PI[idx] = word;
+}
+
+// W into the workgroup's LDS as (S + 1, RT) rows: zero columns behind R, a row of zeros behind S.  Ends with a barrier.
+template <int RT>
+__device__ __forceinline__ void glm_load_design(const double *__restrict__ design, int S, int R, double *wl) {
+    for (int i = threadIdx.x; i < (S + 1) * RT; i += 64 * GP_WAVES) {
+        const int s = i / RT, q = i - s * RT;
+        wl[i] = (s < S && q < R) ? design[(int64_t)s * R + q] : 0.0;
+    }
+    __syncthreads();
+}
+
+// One tile: acc[g][q] = column q of W, permuted as group g's 16 permutations have it, x 16 rows, over all KS K-steps in
+// ascending order; KS is a multiple of 4 here (the centre kernel writes zeros behind S, the pack kernel the zero row).  xp as in gp_tile_mma; ip[g]: this lane's index word of quad 0 of group g, 64 words to the next quad.
+template <int RT, int G>
+__device__ __forceinline__ void glm_tile_mma(const double *__restrict__ xp, int64_t jstride, const uint64_t *(&ip)[G],
+                                             const double *wl, int KS, double4_t (&acc)[G][RT]) {
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int q = 0; q < RT; ++q) acc[g][q] = double4_t{0.0, 0.0, 0.0, 0.0};
+    for (int j4 = 0; j4 < (KS >> 2); ++j4) {
+        uint64_t iw[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) iw[g] = ip[g][(int64_t)j4 * 64];
+        const double *__restrict__ xw = xp + (int64_t)(4 * j4) * jstride;
+        double bv[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) bv[i] = xw[(int64_t)i * jstride];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const double *row = wl + (uint32_t)((iw[g] >> (16 * i)) & 0xFFFFu) * RT;
+#pragma unroll
+                for (int q = 0; q < RT; ++q) acc[g][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(row[q], bv[i], acc[g][q], 0, 0, 0);
+            }
+            // the LDS reads of one K-step at a time: hoisted over all four they cost 8 G RT registers more (scratch at RT = 9)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
+// t^2 of result element r from d_q = acc[q][r]: t^2 = d_0^2 dof / (Q_e - sum_q d_q^2), the sum over q ascending.  gp_t2's
+// guards: +inf where the denominator is not > 0, NaN for a dead connection (Q_e = 0).
+template <int RT>
+__device__ __forceinline__ double glm_t2(const double4_t (&d)[RT], int r, double Qe, double dof) {
+    double ss = 0.0;
+#pragma unroll
+    for (int q = 0; q < RT; ++q) ss += d[q][r] * d[q][r];
+    const double den = Qe - ss;
+    double t2 = d[0][r] * d[0][r] * dof / den;
+    if (!(den > 0.0)) t2 = __builtin_inf();
+    if (!(Qe > 0.0)) t2 = __builtin_nan("");
+    return t2;
+}
+
+struct glm_args {
+    gp_ws ws;                          // LW unused
+    const uint64_t *PI;
+    const double *design;
+    int64_t C, P;
+    int N, KS, S, R;
+    double dof;
+    double *t;                         // the observed kernel's
+    unsigned long long *count_t;       // the permutation kernel's
+};
+
+template <int RT>
+__global__ __launch_bounds__(64 * GP_WAVES) void glm_observed_kernel(glm_args a) {
+    extern __shared__ double gl_w[];
+    glm_load_design<RT>(a.design, a.S, a.R, gl_w);
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t C = a.C, c0 = ((int64_t)blockIdx.x * GP_WAVES + wv) * 16;
+    if (c0 >= C) return;                                     // (no workgroup barrier below)
+    const int col = lane & 15, ks = lane >> 4;
+    const int64_t c = c0 + col < C ? c0 + col : C - 1;       // (a column past the last reads the last row and writes nothing)
+    const uint64_t *ip[1] = {a.PI + lane};
+    double4_t acc[1][RT];
+    glm_tile_mma<RT, 1>(a.ws.XT + c * 4 + ks, C * 4, ip, gl_w, a.KS, acc);
+    if (ks == 0 && c0 + col < C) {
+        const double t2 = glm_t2<RT>(acc[0], 0, a.ws.Q[c], a.dof);
+        a.ws.t2obs[c] = t2;
+        a.t[c] = copysign(sqrt(t2), acc[0][0][0]);
+    }
+}
+
+template <int RT>
+__global__ __launch_bounds__(64 * GP_WAVES) void glm_group_kernel(glm_args a) {
+    extern __shared__ double gl_w[];
+    glm_load_design<RT>(a.design, a.S, a.R, gl_w);
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n = blockIdx.x, N = a.N, KS4 = a.KS >> 2;
+    const int64_t C = a.C, P = a.P, PG = (P + 15) / 16;
+    const int64_t pg0 = ((int64_t)blockIdx.y * GP_WAVES + wv) * GL_G;
+    if (pg0 >= PG) return;                                   // (no workgroup barrier below)
+    const int col = lane & 15, ks = lane >> 4;
+    const uint64_t *ip[GL_G];
+#pragma unroll
+    for (int g = 0; g < GL_G; ++g) ip[g] = a.PI + (pg0 + g < PG ? pg0 + g : PG - 1) * KS4 * 64 + lane;      // (behind the last: masked)
+    double rs[GL_G][4], mx[GL_G][4];
+#pragma unroll
+    for (int g = 0; g < GL_G; ++g)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rs[g][r] = mx[g][r] = 0.0;
+    for (int k0 = 0; k0 < N - 1; k0 += 16) {
+        const int k = k0 + col;
+        const bool valid = k < N - 1;
+        int m;
+        const int64_t c = bl_edge(n, valid ? k : N - 2, m);  // (a column past the last reads the last row and is masked)
+        double4_t acc[GL_G][RT];
+        glm_tile_mma<RT, GL_G>(a.ws.XT + c * 4 + ks, C * 4, ip, gl_w, a.KS, acc);
+        // result element r of group g: permutation (pg0 + g) 16 + ks + 4 r, connection k0 + col
+        const double Qc = a.ws.Q[c], t2o = a.ws.t2obs[c];
+        const bool live = valid && Qc > 0.0;                 // a dead connection: 0 to the sums, no maximum, no count
+        const bool own = live && k < n;
+        int cnt = 0;
+#pragma unroll
+        for (int g = 0; g < GL_G; ++g) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                double t2 = glm_t2<RT>(acc[g], r, Qc, a.dof);
+                if (!live) t2 = 0.0;
+                rs[g][r] += t2;
+                mx[g][r] = fmax(mx[g][r], t2);
+                const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
+                cnt += (own && p < P && t2 >= t2o) ? 1 : 0;
+            }
+        }
+        cnt += __shfl_xor(cnt, 16, 64);
+        cnt += __shfl_xor(cnt, 32, 64);
+        if (own && ks == 0 && cnt) atomicAdd(&a.count_t[c], (unsigned long long)cnt);
+    }
+#pragma unroll
+    for (int g = 0; g < GL_G; ++g) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double s = rs[g][r], v = mx[g][r];
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                s += __shfl_xor(s, o, 64);
+                v = fmax(v, __shfl_xor(v, o, 64));
+            }
+            const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
+            if (col == 0 && p < P) {
+                a.ws.Rpart[(int64_t)n * P + p] = s;
+                a.ws.Mpart[(int64_t)n * P + p] = v;
+            }
+        }
+    }
+}
+
+struct glm_bits_args {
+    const double *XT, *Q, *design;
+    const uint64_t *PI;
+    int64_t C, P, W2;                  // W2 = 2 W: the 16-bit pieces of a row of bits
+    int KS, S, R, tail;
+    double dof, thr2;
+    uint16_t *bits;
+    double *t;                         // nullable: the t of permutation 0
+};
+
+// network_bits_kernel's layout of waves, ballots and stores, GL_G groups of 16 permutations per wave.
+template <int RT>
+__global__ __launch_bounds__(64 * GP_WAVES) void glm_bits_kernel(glm_bits_args a) {
+    extern __shared__ double gl_w[];
+    glm_load_design<RT>(a.design, a.S, a.R, gl_w);
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t piece = (int64_t)blockIdx.x * GP_WAVES + wv;
+    if (piece >= a.W2) return;                               // (no workgroup barrier below)
+    const int64_t C = a.C, P = a.P, PG = (P + 15) / 16, c0 = piece * 16;
+    const int64_t pg0 = (int64_t)blockIdx.y * GL_G;
+    const int col = lane & 15, ks = lane >> 4, KS4 = a.KS >> 2;
+    if (c0 >= C) {
+#pragma unroll
+        for (int g = 0; g < GL_G; ++g) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
+                if (col == 0 && p < P) a.bits[p * a.W2 + piece] = (uint16_t)0;
+            }
+        }
+        return;
+    }
+    const bool valid = c0 + col < C;
+    const int64_t c = valid ? c0 + col : C - 1;              // (a column past the last reads the last row and contributes 0)
+    const uint64_t *ip[GL_G];
+#pragma unroll
+    for (int g = 0; g < GL_G; ++g) ip[g] = a.PI + (pg0 + g < PG ? pg0 + g : PG - 1) * KS4 * 64 + lane;      // (behind the last: masked)
+    double4_t acc[GL_G][RT];
+    glm_tile_mma<RT, GL_G>(a.XT + c * 4 + ks, C * 4, ip, gl_w, a.KS, acc);
+    const double Qc = a.Q[c];
+#pragma unroll
+    for (int g = 0; g < GL_G; ++g) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double d0 = acc[g][0][r];
+            const double t2 = glm_t2<RT>(acc[g], r, Qc, a.dof);
+            const bool side = a.tail == 0 || (a.tail == 1 ? d0 > 0.0 : d0 < 0.0);
+            const unsigned long long mask = __ballot(valid && side && t2 > a.thr2);
+            const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
+            if (col == 0 && p < P) a.bits[p * a.W2 + piece] = (uint16_t)(mask >> (16 * ks));
+            if (a.t && p == 0 && valid) a.t[c] = copysign(sqrt(t2), d0);
+        }
+    }
+}
+
+// what the two calls with a design check alike; who = the call's name
+__host__ static int glm_check(fcd_ctx *ctx, const char *who, int64_t C, int64_t H, int64_t U, int64_t R, int64_t P) {
+    if (C < 1 || H < 1 || U < 1 || P < 1) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "C, H, U=%lld and P=%lld must be >= 1", U, P);
+    if (R < 1 || R > GL_RMAX) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "R=%lld design columns, 1 to %lld", R, GL_RMAX);
+    if (H + U > GP_SMAX) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "%lld subjects, at most %lld", H + U, GP_SMAX);
+    if (H + U < R + 2) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "%lld subjects, R=%lld design columns need R + 2", H + U, R);
+    if (fcd_C_to_N(C) < 2) return fcd_fail_who(ctx, FCD_ERR_SHAPE, who, "C=%lld is not a triangular number", C);
+    return FCD_OK;
+}
+
+__host__ static inline int glm_width(int R) { return R <= 2 ? 0 : R <= 3 ? 1 : R <= 5 ? 2 : 3; }      // RT = 2, 3, 5, 9
+__host__ static inline double glm_dead2(int64_t S, int64_t R) {
+    const double tol = 8.0 * (double)S * (double)R * 2.220446049250313e-16;
+    return tol * tol;
+}
+
+// kern<RT> with (S + 1) RT doubles of dynamic LDS, its limit raised where that is more than 64 KB; which = 0, 1, 2 of FCD_KA_GLM
+#define GLM_LAUNCH_RT(kern, RT, which, grid, st, arg)                                                                              \
+    do {                                                                                                                           \
+        const size_t shmem__ = (size_t)((arg).S + 1) * (RT) * sizeof(double);                                                      \
+        int rc__ = fcd_lds_attr(ctx, FCD_KA_GLM + 4 * (which) + glm_width(RT), reinterpret_cast<const void *>(&kern<RT>), shmem__); \
+        if (rc__) return rc__;                                                                                                     \
+        hipLaunchKernelGGL((kern<RT>), grid, dim3(64 * GP_WAVES), shmem__, st, arg);                                               \
+    } while (0)
+#define GLM_LAUNCH(kern, which, grid, st, arg)                               \
+    do {                                                                     \
+        switch (glm_width((arg).R)) {                                        \
+        case 0: GLM_LAUNCH_RT(kern, 2, which, grid, st, arg); break;         \
+        case 1: GLM_LAUNCH_RT(kern, 3, which, grid, st, arg); break;         \
+        case 2: GLM_LAUNCH_RT(kern, 5, which, grid, st, arg); break;         \
+        default: GLM_LAUNCH_RT(kern, 9, which, grid, st, arg); break;        \
+        }                                                                    \
+        FCD_LAUNCH_CHECK();                                                  \
+    } while (0)
+
 }  // namespace
 
 extern "C" int fcd_baseline_normative(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
@@ -1284,5 +1629,108 @@ extern "C" int fcd_graph_components(fcd_ctx *ctx, const uint32_t *bits, int64_t 
     hipLaunchKernelGGL(graph_components_kernel, dim3((unsigned)B), dim3(CC_T), shmem, (hipStream_t)stream, bits, C, (int)N, (int)W, component,
                        n_edges, max_extent, max_regions);
     FCD_LAUNCH_CHECK();
+    return FCD_OK;
+}
+
+extern "C" int fcd_baseline_group_glm(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                      const double *design, int64_t R, const uint16_t *perms, int64_t P, double *t, double *region,
+                                      double *null_max_t, double *null_max_region, int64_t *count_t, int64_t *count_region,
+                                      fcd_stream stream) {
+    const char *who = "fcd_baseline_group_glm";
+    if (!ctx || !b || !bt || !design || !perms || !t || !region || !null_max_t || !null_max_region || !count_t || !count_region)
+        return fcd_fail_who(ctx, FCD_ERR_ARG, who, "null pointer");
+    int rc = glm_check(ctx, who, C, H, U, R, P);
+    if (rc) return rc;
+    const int64_t S = H + U, N = fcd_C_to_N(C);
+    const int64_t gy = (P + GP_WAVES * GL_G * 16 - 1) / (GP_WAVES * GL_G * 16);
+    if (N > 46340 || gy > 65535 || (C + GC_WAVES - 1) / GC_WAVES > INT32_MAX || N * P > (1ll << 34))
+        return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "shape too large (Nreg=%lld, P=%lld)", N, P);
+    const int KS4 = (int)((S + 15) / 16), KS = 4 * KS4;      // K-steps in whole quads: one index word each
+    const int64_t PG = (P + 15) / 16;
+    hipStream_t st = (hipStream_t)stream;
+    // Nothing of the workspace outlives the call.  gp_ws without label words | index words (PG, KS4, 64) uint64
+    const size_t base = gp_ws_bytes(C, N, P, KS, 0);
+    rc = fcd_ws_reserve(ctx, base + (size_t)(PG * KS4 * 64) * sizeof(uint64_t));
+    if (rc) return rc;
+    glm_args a;
+    a.ws = gp_ws_at(ctx->ws, C, N, P, KS);
+    uint64_t *PI = (uint64_t *)((char *)ctx->ws + base);
+    a.PI = PI;
+    a.design = design;
+    a.C = C;
+    a.N = (int)N;
+    a.KS = KS;
+    a.S = (int)S;
+    a.R = (int)R;
+    a.dof = (double)(S - R - 1);
+    a.t = t;
+    a.count_t = reinterpret_cast<unsigned long long *>(count_t);
+    FCD_HIP_TRY(hipMemsetAsync(count_t, 0, (size_t)C * sizeof(int64_t), st));
+    hipLaunchKernelGGL(glm_centre_kernel, dim3((unsigned)((C + GC_WAVES - 1) / GC_WAVES)), dim3(64 * GC_WAVES),
+                       (size_t)((R - 1) * S) * sizeof(double), st, b, bt, C, (int)H, (int)U, KS, design, (int)R, glm_dead2(S, R), a.ws.XT,
+                       a.ws.Q);
+    FCD_LAUNCH_CHECK();
+    // the observed statistics: the identity as one packed row through the same tile product and the same t^2, each connection once
+    a.P = 1;
+    hipLaunchKernelGGL(glm_pack_kernel, dim3((unsigned)((KS4 * 64 + 255) / 256)), dim3(256), 0, st, (const uint16_t *)nullptr, (int64_t)1,
+                       (int)S, KS4, PI);
+    FCD_LAUNCH_CHECK();
+    GLM_LAUNCH(glm_observed_kernel, 0, dim3((unsigned)((C + 16 * GP_WAVES - 1) / (16 * GP_WAVES))), st, a);
+    hipLaunchKernelGGL(group_observed_region_kernel, dim3((unsigned)N), dim3(64), 0, st, a.ws.t2obs, (int)N, region);
+    FCD_LAUNCH_CHECK();
+    a.P = P;
+    hipLaunchKernelGGL(glm_pack_kernel, dim3((unsigned)((PG * KS4 * 64 + 255) / 256)), dim3(256), 0, st, perms, P, (int)S, KS4, PI);
+    FCD_LAUNCH_CHECK();
+    GLM_LAUNCH(glm_group_kernel, 1, dim3((unsigned)N, (unsigned)gy), st, a);
+    hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)(N + (P + 255) / 256)), dim3(256), 0, st, a.ws.Rpart, a.ws.Mpart, region, (int)N, P,
+                       null_max_region, null_max_t, count_region);
+    FCD_LAUNCH_CHECK();
+    return FCD_OK;
+}
+
+extern "C" int fcd_baseline_network_bits_glm(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                             const double *design, int64_t R, const uint16_t *perms, int64_t P, double threshold,
+                                             int tail, uint32_t *bits, double *t, fcd_stream stream) {
+    const char *who = "fcd_baseline_network_bits_glm";
+    if (!ctx || !b || !bt || !design || !bits) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "null pointer");
+    int rc = glm_check(ctx, who, C, H, U, R, P);
+    if (rc) return rc;
+    if (!perms && P != 1) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "the identity (perms == NULL) is P = 1, not %lld", P);
+    if (!(threshold > 0.0) || !(threshold <= 1.7976931348623157e308))
+        return fcd_fail_who(ctx, FCD_ERR_ARG, who, "the threshold must be finite and > 0");
+    if (tail < FCD_TAIL_BOTH || tail > FCD_TAIL_LESS) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "unknown tail %lld", tail);
+    const int64_t S = H + U, N = fcd_C_to_N(C);
+    if (N > NB_NMAX) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "%lld regions, at most %lld", N, NB_NMAX);
+    const int64_t PG = (P + 15) / 16, gy = (PG + GL_G - 1) / GL_G, W = (C + 31) / 32;
+    if (gy > 65535) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "shape too large (Nreg=%lld, P=%lld)", N, P);
+    const int KS4 = (int)((S + 15) / 16), KS = 4 * KS4;      // K-steps in whole quads: one index word each
+    hipStream_t st = (hipStream_t)stream;
+    // Nothing of the workspace outlives the call.  XT (KS, C, 4) | Q (C) | index words (PG, KS4, 64) uint64
+    rc = fcd_ws_reserve(ctx, (size_t)((int64_t)KS * C * 4 + C) * sizeof(double) + (size_t)(PG * KS4 * 64) * sizeof(uint64_t));
+    if (rc) return rc;
+    double *XT = (double *)ctx->ws, *Q = XT + (int64_t)KS * C * 4;
+    uint64_t *PI = (uint64_t *)(Q + C);
+    hipLaunchKernelGGL(glm_centre_kernel, dim3((unsigned)((C + GC_WAVES - 1) / GC_WAVES)), dim3(64 * GC_WAVES),
+                       (size_t)((R - 1) * S) * sizeof(double), st, b, bt, C, (int)H, (int)U, KS, design, (int)R, glm_dead2(S, R), XT, Q);
+    FCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(glm_pack_kernel, dim3((unsigned)((PG * KS4 * 64 + 255) / 256)), dim3(256), 0, st, perms, P, (int)S, KS4, PI);
+    FCD_LAUNCH_CHECK();
+    glm_bits_args a;
+    a.XT = XT;
+    a.Q = Q;
+    a.design = design;
+    a.PI = PI;
+    a.C = C;
+    a.P = P;
+    a.W2 = 2 * W;
+    a.KS = KS;
+    a.S = (int)S;
+    a.R = (int)R;
+    a.tail = tail;
+    a.dof = (double)(S - R - 1);
+    a.thr2 = threshold * threshold;
+    a.bits = reinterpret_cast<uint16_t *>(bits);
+    a.t = t;
+    GLM_LAUNCH(glm_bits_kernel, 2, dim3((unsigned)((2 * W + GP_WAVES - 1) / GP_WAVES), (unsigned)gy), st, a);
     return FCD_OK;
 }

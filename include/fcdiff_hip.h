@@ -473,6 +473,33 @@ int fcd_baseline_group_perm_opt(fcd_ctx *ctx, const double *b, const double *bt,
 int fcd_baseline_network_bits_opt(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
                                   const uint8_t *labels, int64_t P, double threshold, int tail, int flags, uint32_t *bits,
                                   double *t, fcd_stream stream);
+/* The two calls with nuisance covariates: the permutation GLM of Freedman & Lane (1983).  design (S, R) fp64, row-major, on the
+ * device: its columns are orthonormal and each is orthogonal to the constant vector (the caller's to make so; fcdiff_amd's
+ * baseline.glm_design does); column 0 is the contrast, tested given columns 1 .. R - 1.  The library does not know where the
+ * design came from: any regressor, residualised on the others and the constant and scaled to unit norm, can stand in column 0.
+ * Per connection e = the row minus its mean minus sum_{q >= 1} w_q (w_q^T row), Q_e = sum e^2.  perms (P, S) uint16, each row
+ * a permutation of 0 .. S - 1 (the caller's to check; an index > S - 1 is read as a row of zeros): subject s gets design row
+ * perms[p][s].  d_q = sum_s design[perms[p][s]][q] e_s, t^2 = d_0^2 dof / (Q_e - sum_q d_q^2) with dof = S - R - 1,
+ * t = sign(d_0) sqrt(t^2), R[n] = sum over E(n) of t^2.  The observed statistics are those of the identity, run through the same
+ * tile product, the same t^2 and the same order of sums, so a row of perms equal to the identity gives them bit for bit.
+ * Outputs and rules as for fcd_baseline_group_perm: a constant connection is dead (t = NaN, 0 to every R, no maximum,
+ * count_t = 0, never a set bit); where the denominator is not > 0 with the connection alive, t^2 = +inf with the sign of d_0.
+ * Dead too: a connection with Q_e <= (8 S R 2^-52)^2 Q_c, Q_c the centred sum of squares of the row -- a linear function of the
+ * covariates to rounding.  The d_q are an fp64 MFMA product whose A operand is read from the design in LDS by the permuted
+ * index; no (P, C) array exists.  Seven launches; workspace about 8 C S + 16 Nreg P + P S / 2 bytes.
+ * FCD_ERR_SHAPE for a non-triangular C; FCD_ERR_UNSUPPORTED for R < 1, R > 9, S > 1024 or P > 65535 * 128; FCD_ERR_ARG for a
+ * null pointer, a size < 1 or S < R + 2. */
+int fcd_baseline_group_glm(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                           const double *design, int64_t R, const uint16_t *perms, int64_t P, double *t, double *region,
+                           double *null_max_t, double *null_max_region, int64_t *count_t, int64_t *count_region,
+                           fcd_stream stream);
+/* The bits of fcd_baseline_network_bits from the t^2 above; the side of FCD_TAIL_GREATER / _LESS is the sign of d_0.  perms may be
+ * NULL with P = 1: the identity.  t (C,), nullable: the signed t of permutation 0.  Three launches.
+ * Refusals as above and as fcd_baseline_network_bits: more than 1024 regions or P > 65535 * 32 FCD_ERR_UNSUPPORTED; perms == NULL
+ * with P != 1, a threshold that is not finite and > 0, or an unknown tail FCD_ERR_ARG. */
+int fcd_baseline_network_bits_glm(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
+                                  const double *design, int64_t R, const uint16_t *perms, int64_t P, double threshold, int tail,
+                                  uint32_t *bits, double *t, fcd_stream stream);
 /* The components: per row of bits (B, W) the connected components of the graph on the Nreg regions whose edges are the set
  * bits; bits behind C in the last word are ignored.  A component's label is its smallest region, its extent its number of
  * connections.  component (B, Nreg), nullable: the label of each region's component, -1 for a region without an edge.
