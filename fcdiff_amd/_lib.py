@@ -55,6 +55,8 @@ SIGNATURES = {
     "fcd_C_to_N": (_i64, [_i64]),
     "fcd_nm_to_c": (_i64, [_i64, _i64]),
     "fcd_c_to_nm": (_int, [_i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    "fcd_f_run_count": (_i64, [_i64]),
+    "fcd_f_run_locate": (_int, [_i64, _i64, C.POINTER(_i64)]),
     "fcd_hyper_set": (_int, [_p, _p, C.POINTER(_dbl), C.POINTER(_dbl), _p]),
     "fcd_lik_tables": (_int, [_p, _p, _p, _i64, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _p, _p]),
     "fcd_lik_tables_ex": (_int, [_p, _p, _p, _i64, _i64, _i64, C.POINTER(_dbl), _p, _p, _p, _p, _int, _p, _p]),

@@ -200,13 +200,14 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->knobs.r_withhold = 0;
     ctx->knobs.f_records = 0;           // (A/B runs and tests only)
     ctx->knobs.f_sure = 0;
+    ctx->knobs.f_runs = 0;
     ctx->knobs.tally_in_r = (int)knob_env("FCD_TALLY_IN_R");
     ctx->knobs.r_keep_words = (int)knob_env("FCD_R_KEEP_WORDS");
     ctx->r_form_last = 0;
     ctx->n_pack = 0;
     ctx->n_pack_tally = 0;
     ctx->n_r_tally = 0;
-    ctx->n_frec_pass = ctx->n_frec_build = ctx->n_fsure_pass = 0;
+    ctx->n_frec_pass = ctx->n_frec_build = ctx->n_fsure_pass = ctx->n_frun_pass = 0;
     int rc = fcd_ws_reserve(ctx, 1u << 20);
     if (rc == FCD_OK) {
         void *pin = nullptr;
@@ -317,6 +318,7 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value) {
     else if (!strcmp(name, "f_pack")) k.f_pack = (int)value;
     else if (!strcmp(name, "f_records")) k.f_records = (int)value;
     else if (!strcmp(name, "f_sure")) k.f_sure = (int)value;
+    else if (!strcmp(name, "f_runs")) k.f_runs = (int)value;
     else if (!strcmp(name, "corr_form")) k.corr_form = (int)value;
     else if (!strcmp(name, "tally_in_r")) k.tally_in_r = (int)value;
     else if (!strcmp(name, "r_keep_words")) k.r_keep_words = (int)value;
@@ -359,6 +361,7 @@ int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out) {
     else if (!strcmp(name, "f_rec_bytes")) *out = (int64_t)ctx->frec_bytes;
     else if (!strcmp(name, "f_rec_min_sweeps")) *out = F_REC_MIN_SWEEPS;
     else if (!strcmp(name, "f_sure_passes")) *out = ctx->n_fsure_pass;
+    else if (!strcmp(name, "f_run_passes")) *out = ctx->n_frun_pass;
     else if (!strcmp(name, "pipe_grid")) *out = ctx->pipe_grid;
     else if (!strcmp(name, "pipe_capacity")) *out = ctx->pipe_capacity;
     else if (!strcmp(name, "comm_world")) *out = ctx->comm ? ctx->comm_world : 0;
@@ -391,6 +394,16 @@ int fcd_c_to_nm(int64_t c, int64_t *n, int64_t *m) {
     fcd_edge_to_pair(c, nn, mm);
     *n = nn;
     *m = mm;
+    return FCD_OK;
+}
+
+int64_t fcd_f_run_count(int64_t Nreg) { return Nreg < 2 ? (int64_t)FCD_ERR_SHAPE : fpr_runs((Nreg + 1) / 2); }
+
+int fcd_f_run_locate(int64_t Nreg, int64_t t, int64_t *out9) {
+    if (Nreg < 2 || Nreg > (1 << 20) || !out9 || t < 0 || t >= fpr_runs((Nreg + 1) / 2)) return FCD_ERR_ARG;
+    const fpr_run R = fpr_locate((int)t, (int)Nreg);
+    const int64_t v[9] = {R.n0, R.mb, R.cnt0, R.cnt1, R.tile0, R.ntile, R.cr0, R.cr1, fpr_philox_blocks(R)};
+    for (int i = 0; i < 9; ++i) out9[i] = v[i];
     return FCD_OK;
 }
 

@@ -37,6 +37,9 @@ struct fcd_knobs {
     int f_records;     // pair-tile f pass reads pair records made once per call: 0 = in calls of at least F_REC_MIN_SWEEPS pair-tile
                        // sweeps, 1 = never (every tile builds its own), 2 = whenever the pair-tile form runs
     int f_sure;        // 1: never the decided-tile path of the pair-tile f pass (A/B runs and tests; default: where the table has such tiles)
+    int f_runs;        // form of the decided path: 0 = block-wide runs of tiles (gibbs_f_run_kernel) where the record build found EVERY
+                       // tile decided, the per-tile kernel elsewhere; 1 = never the run form; 2 = the run form wherever the
+                       // decided path is taken at all (tests: open edges inside the run kernel)
     int tally_in_r;    // f half of the tally inside the pipelined r pass (its in-order workgroups, before their first block): 0 = where
                        // a wave's rounds are at most R_TALLY_MAX_ROUNDS, 1 = never (the tally after the pass counts f), 2 = wherever
                        // the form allows (16-wave in-order workgroups)
@@ -87,8 +90,10 @@ struct fcd_ctx {
     long long n_frec_pass;         // f passes that read prebuilt pair records (fcd_ctx_stat "f_rec_passes")
     long long n_frec_build;        // launches of the kernel that builds them (fcd_ctx_stat "f_rec_builds")
     long long n_fsure_pass;        // f passes that ran the kernel with the decided-tile path (fcd_ctx_stat "f_sure_passes")
-    volatile unsigned *f_sure_hint;    // pinned host word: the records kernel of build number n_frec_build leaves twice that number
-                                       // here, + 1 where some tile of its table has every edge decided (FCD_F_SURE_DRIFT nats in hand)
+    long long n_frun_pass;         // ... of them in the run form, gibbs_f_run_kernel (fcd_ctx_stat "f_run_passes")
+    volatile unsigned *f_sure_hint;    // pinned host word: the records kernel of build number n_frec_build leaves four times that
+                                       // number here, + 1 where some tile of its table has every edge decided (FCD_F_SURE_DRIFT
+                                       // nats in hand), + 2 where every tile has
     void *log_tab;     // K_lik tables (fcd_fastmath.h): 64 x 2^(-j/64), 512 x {1/m_i, log m_i} (device, 8.5 KiB)
     volatile unsigned *dev_err;   // pinned host word: error word of the one-launch r pass, copied back after each pass
     void *acc;         // 8 x uint64, zero between launches: the tally's pooled sums [0..3] and its ticket [4]
@@ -100,7 +105,8 @@ struct fcd_ctx {
     void *dbg;         // 8 x uint64 event counters (fcd_ctx_stat): [0] waves of the f pass that repeated an edge's sums in fp64,
                        // [1] rows of the r pass's in-order role decided on the exact path, [2] workgroups of the pair-tile f pass
                        // that took the decided-tile path ("f_sure_tiles"), [3] decided ones its vote sent back
-                       // ("f_sure_fallbacks"), never reset by the library; [4] the record build's word "some tile is decided", zero between calls
+                       // ("f_sure_fallbacks"), never reset by the library; [4] the record build's two words "some tile is decided" (low half) and
+                       // "some tile is open" (high half), zero between calls; [5], [6] the call's lM and hyper (FCD_DBG_LM)
     void *corr_tickets;            // K_corr: one ticket per subject, zero between launches (the last taker resets it)
     size_t corr_tickets_n;
     void *fsq;         // square copy of the f state [w][n][m][lane] the sweep loop keeps between its f and r pass
@@ -606,6 +612,47 @@ __host__ __device__ static inline int64_t fpt_tiles(int64_t i) {       // pair-a
     const int64_t j = i >> 1;
     return (i & 1) ? (j + 1) * (j + 1) : j * (j + 1);
 }
+// Block-wide runs of pair-aligned tiles (fcd_gibbs.hip, gibbs_f_run_kernel): run t is the tiles of one row pair (n0, n0 + 1)
+// whose columns lie in one block of FR_W = 16 regions (R_NB), [mb, mb + FR_W): up to four tiles, 32 edges, edge e = (row e / FR_W,
+// column e % FR_W), present where e % FR_W < cnt of its row, id cr + e % FR_W.  Row pair i has floor(i/8) + 1 runs, so the runs
+// before row pair i = 8q + r number 4q(q+1) + r(q+1).
+constexpr int FR_W = 4 * FT_W;
+constexpr int FR_WAVES = 8;      // chain words (waves) per workgroup of the run kernel: 8 measured 46.5 us at cfg3, 16 54.4, 4 57.9
+struct fpr_run {
+    int n0, mb;
+    int cnt0, cnt1;          // edges of row n0 / n0 + 1 in the run (m < n, row inside the triangle)
+    int tile0, ntile;        // its pair-aligned tiles: tile0 .. tile0 + ntile - 1 (fpt_locate)
+    int64_t cr0, cr1;        // edge id of the first column of each row
+};
+__host__ __device__ static inline int64_t fpr_runs(int64_t i) {        // runs of the row pairs before i
+    const int64_t q = i >> 3;
+    return 4 * q * (q + 1) + (i & 7) * (q + 1);
+}
+__host__ __device__ static inline fpr_run fpr_locate(int t, int Nreg) {
+    int q = (int)((sqrtf((float)t + 1.f) - 1.f) * 0.5f);
+    while ((int64_t)4 * (q + 1) * (q + 2) <= t) ++q;
+    while ((int64_t)4 * q * (q + 1) > t) --q;
+    const int rem = t - 4 * q * (q + 1);
+    const int i = 8 * q + rem / (q + 1);
+    fpr_run R;
+    R.n0 = 2 * i;
+    R.mb = FR_W * (rem % (q + 1));
+    const int c0 = R.n0 - R.mb, c1 = R.n0 + 1 - R.mb;
+    R.cnt0 = c0 < FR_W ? c0 : FR_W;
+    R.cnt1 = R.n0 + 1 < Nreg ? (c1 < FR_W ? c1 : FR_W) : 0;
+    R.tile0 = (int)fpt_tiles(i) + R.mb / FT_W;
+    R.ntile = ((c1 + 1 < FR_W ? c1 + 1 : FR_W) + FT_W - 1) / FT_W;
+    R.cr0 = ((int64_t)R.n0 * (R.n0 - 1) >> 1) + R.mb;
+    R.cr1 = R.cr0 + R.n0;
+    return R;
+}
+// the Philox blocks a run draws: per row the 4-id blocks its consecutive edge ids touch, each once
+__host__ __device__ static inline int fpr_philox_blocks(const fpr_run &R) {
+    int n = 0;
+    if (R.cnt0 > 0) n += (int)(((R.cr0 + R.cnt0 - 1) >> 2) - (R.cr0 >> 2)) + 1;
+    if (R.cnt1 > 0) n += (int)(((R.cr1 + R.cnt1 - 1) >> 2) - (R.cr1 >> 2)) + 1;
+    return n;
+}
 // Pair records made once per call (fcd_gibbs.hip, gibbs_f_records_kernel): per pair-aligned tile NPAIR x FP_EC records of
 // six 16-byte pieces (the eight of the LDS record without slots 10-11 and 14-15, which no slot word can name), then one
 // fcd_f_edge_rec per edge id.
@@ -668,7 +715,9 @@ struct fcd_sweep_plan {
     size_t fsq_bytes;
     // prebuilt pair records of the pair-tile f pass (fcd_ctx::frec): tiles | edge constants at frec_edge; 0: none (another
     // form, no blocked r pass, or above F_REC_CAP).  f_shmem_rec: the LDS of the kernel that reads them (no fp64 rows)
-    size_t frec_bytes, frec_edge, f_shmem_rec;
+    // frec_votes: behind the edge constants one word per (run, group of 16 chain words), zero between passes -- where the two
+    // 8-wave workgroups of such an item meet for the counters (gibbs_f_run_kernel)
+    size_t frec_bytes, frec_edge, frec_votes, f_shmem_rec;
     // workspace byte offsets: P[0] | P[1] | f_S | r_S | r_Sn | marks of the blocked r pass, then at a 512-byte boundary the
     // slot words r_U of a pair-form f pass (behind the r scratch: the sentinels in P survive from sweep to sweep) | ws_bytes
     size_t P[2], f_S, r_S, r_Sn, marks, r_U, ws_bytes;
@@ -701,6 +750,7 @@ struct fcd_sweep_step {
     bool tally_f_done;             // nullptr ... and whether one of them did (out)
     bool r_flip;                   // r pass: the two r-word buffers of the plan have swapped roles (r_S lies at pl.r_Sn, r_Sn at pl.r_S)
     bool f_sure;                   // f pass (f_rec): some tile of the call's table has all its edges decided (fcd_ctx::f_sure_hint)
+    bool f_all;                    // ... and every tile has: the decided path runs in its run form (gibbs_f_run_kernel)
 };
 int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step &st);   // fcd_gibbs.hip
 int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st);         // fcd_gibbs_r.hip

@@ -452,6 +452,8 @@ __device__ __forceinline__ fpt_tile fpt_locate(int t, int Nreg) {
 }
 
 // The r pass's f words of a pair-aligned tile from its draws kt (2 bits per edge), for this lane's chain of chain word w.
+// (ROWS = false: without the row halves -- gibbs_f_run_kernel writes those of a full run itself, eight bytes at a time)
+template <bool ROWS = true>
 __device__ __forceinline__ void fpt_write_f_words(const fpt_tile &T, uint32_t kt, int w, int lane, uint2 *__restrict__ f_S, int Nreg, int NBLK) {
     // the r pass's f words (pack_f_item's bytes, (3 f(n, m) + f(n, m+1)) << 2; 0 for m == n and m >= Nreg).  K(r, j):
     // f of (n0 + r, mb + j) -- drawn here, 0 on the diagonal and for a row beyond Nreg, and (n0, n0 + 1) is the edge
@@ -467,7 +469,7 @@ __device__ __forceinline__ void fpt_write_f_words(const fpt_tile &T, uint32_t kt
     uint8_t *fs = reinterpret_cast<uint8_t *>(f_S + (int64_t)w * Nreg * NBLK * 64 + lane);     // + ((n * NBLK + b) * 64) * 8
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-        if (T.n0 + r >= Nreg) break;
+        if (!ROWS || T.n0 + r >= Nreg) break;
         uint8_t *row = fs + (int64_t)((T.n0 + r) * NBLK + b) * 512 + p0;
         uint32_t v = 0;
 #pragma unroll
@@ -916,9 +918,12 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
 // read by the kernel without the decided-tile path.
 __global__ __launch_bounds__(64 * FP_EC) void gibbs_f_records_kernel(const double *__restrict__ S_B, const double *__restrict__ lMf,
                                                                      const double *__restrict__ hyper, int Nreg, int U,
-                                                                     char *__restrict__ frec, unsigned *__restrict__ any_tile) {
+                                                                     char *__restrict__ frec, unsigned *__restrict__ any_tile,
+                                                                     unsigned *__restrict__ votes, int n_votes) {
     const int NPAIR = (U + 1) >> 1;
     const fpt_tile T = fpt_locate((int)blockIdx.x, Nreg);
+    // (the run kernel's vote words: zero before the call's first pass; every pass leaves them zero)
+    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < n_votes; i += (int)(gridDim.x * blockDim.x)) votes[i] = 0u;
     auto has = [&](int e) -> bool { return (e % FT_W) < (e < FT_W ? T.cnt0 : T.cnt1); };
     auto cid = [&](int e) -> int64_t { return (e < FT_W ? T.cr0 : T.cr1) + (e % FT_W); };
     fcd_f4v *dst4 = reinterpret_cast<fcd_f4v *>(frec) + (size_t)blockIdx.x * NPAIR * (FP_EC * F_REC_PIECES);
@@ -985,19 +990,285 @@ __global__ __launch_bounds__(64 * FP_EC) void gibbs_f_records_kernel(const doubl
     __syncthreads();
     // (every tile that has the property stores the same word: no atomic, no fence -- gibbs_f_hint_kernel reads it behind
     // this launch)
-    if (threadIdx.x == 0 && !open_edges && (T.cnt0 > 0 || T.cnt1 > 0)) *any_tile = 1u;
+    // ... and every tile that lacks it stores a 1 into the word beside it: "some tile is open"
+    if (threadIdx.x == 0 && (T.cnt0 > 0 || T.cnt1 > 0)) any_tile[open_edges ? 1 : 0] = 1u;
 }
-// ... and hands it to the host: 2 build + any into the pinned word the sweep loop polls (written once, complete), the device
-// word cleared for the next build.
+// ... and hands it to the host: 4 build + 2 all + any into the pinned word the sweep loop polls (written once, complete; all =
+// some tile is decided and none is open), the device words cleared for the next build.
 // It also leaves the call's lM and hyper where the kernels that read the table find them (dbg[FCD_DBG_LM], [FCD_DBG_LM + 1]:
 // the words behind any_tile's).
 __global__ void gibbs_f_hint_kernel(unsigned *__restrict__ any_tile, volatile unsigned *hint, unsigned build, const double *lM,
                                     const double *hyper) {
-    const unsigned any = *any_tile != 0u ? 1u : 0u;
-    *any_tile = 0u;
+    const unsigned any = any_tile[0] != 0u ? 1u : 0u, all = (any && any_tile[1] == 0u) ? 1u : 0u;
+    any_tile[0] = 0u;
+    any_tile[1] = 0u;
     reinterpret_cast<unsigned long long *>(any_tile)[1] = (unsigned long long)(uintptr_t)lM;
     reinterpret_cast<unsigned long long *>(any_tile)[2] = (unsigned long long)(uintptr_t)hyper;
-    __hip_atomic_store(const_cast<unsigned *>(hint), 2u * build + any, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(const_cast<unsigned *>(hint), 4u * build + 2u * all + any, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The decided path in block-wide runs (fpr_run, fcd_common.h): work item = (run, chain word), one wave; workgroup = the run
+// x the (up to) FR_WAVES = 8 chain words of blockIdx.y.  No LDS image, no barrier before the stores, and no tile ever goes
+// back as a whole: lane e < 32 evaluates edge e's rule once per run, every lane draws the run's Philox blocks once per row
+// (a tile's two rows of four ids straddle 3.45 blocks, a run's two rows of sixteen 8.9 for up to four tiles) and tests the
+// words of the present edges against fcd_draw_f_sure's range.  An edge the rule leaves open, or for which some lane of THIS wave is out of
+// range, is drawn by this wave as gibbs_f_pair_kernel draws it (fcd_f_run_edge); every other edge gets its mode, which is
+// what that kernel gives every (wave, edge) without an out-of-range lane, on either of its paths.
+// ---------------------------------------------------------------------------------------------
+// One edge's draw for the whole wave, as the term loop of gibbs_f_pair_kernel and what follows it make it: the fp32 sums in
+// that loop's order (full groups of eight pairs: even pairs into acc, odd pairs into acc1, the sums starting from the first
+// terms; a short last group into acc; then acc += acc1), from the call's record table in global memory
+// (rec: the edge's record of pair 0; a record is F_REC_PIECES 16-byte pieces, pair p lies p * FP_EC records on; Z: the slot
+// words of the edge's two regions).  Returns the draw, + FPR_AMB where some lane of the wave asks for the exact path: the
+// kernel calls that itself, so that this function calls none and needs no stack.
+constexpr int FPR_AMB = 8;
+__device__ __attribute__((noinline)) int fcd_f_run_edge(const char *__restrict__ rec, const fcd_f_edge_rec *__restrict__ ke_p,
+                                                        const double *__restrict__ hyper, uint4 Z, int U, uint32_t xw, float margin) {
+    const int NPAIR = (U + 1) >> 1, NG = (NPAIR + 7) >> 3;
+    auto term = [&](int p, uint32_t slot) -> fcd_f2v {
+        const uint32_t s2 = slot >> 1;
+        return *reinterpret_cast<const fcd_f2v *>(rec + (size_t)p * (FP_EC * F_REC_PIECES * 16) + (s2 < 5 ? s2 : 5) * 16 + (slot & 1u) * 8);
+    };
+    fcd_f2v acc = {0.f, 0.f}, acc1 = {0.f, 0.f};
+#pragma unroll 1
+    for (int g = 0; g < NG; ++g) {
+        const uint32_t zs = g == 0 ? Z.x : g == 1 ? Z.y : g == 2 ? Z.z : Z.w;
+        const int np = NPAIR - 8 * g;
+        if (np >= 8) {
+#pragma unroll 1
+            for (int p = 0; p < 8; p += 2) {
+                const fcd_f2v v0 = term(8 * g + p, (zs >> (4 * p)) & 15u), v1 = term(8 * g + p + 1, (zs >> (4 * p + 4)) & 15u);
+                if (g == 0 && p == 0) {
+                    acc = v0;
+                    acc1 = v1;
+                } else {
+                    acc += v0;
+                    acc1 += v1;
+                }
+            }
+        } else {
+#pragma unroll 1
+            for (int p = 0; p < np; ++p) acc += term(8 * g + p, (zs >> (4 * p)) & 15u);
+        }
+    }
+    acc += acc1;
+    const fcd_f_edge_rec ke = *ke_p;
+    const double lg1 = hyper[FCD_H_LNGAMMA + 1] - hyper[FCD_H_LNGAMMA + 0], lg2 = hyper[FCD_H_LNGAMMA + 2] - hyper[FCD_H_LNGAMMA + 0];
+    const double c1 = lg1 + ke.d1, c2 = lg2 + ke.d2;
+    const float cm = fmaxf((float)fabs(c1), (float)fabs(c2)) * 1.0000002f;
+    const float eta = fcd_draw_f_eta(fcd_f32_sum_err(NPAIR, ke.a) + fcd_f32_offset_err(cm, ke.a));
+    const float bf1 = (float)c1 + acc.x, bf2 = (float)c2 + acc.y, xf = (float)xw * 2.3283064e-10f;
+    bool amb = false;
+    int k;
+    if (margin > 1.f || __ballot(!fcd_draw_f_sure(bf1, bf2, xf, eta, &k)) != 0ull) k = fcd_draw_f_fast32(bf1, bf2, xf, eta, margin, &amb);
+    return k | (__ballot(amb) != 0ull ? FPR_AMB : 0);
+}
+
+// the two-bit fields 2j of x <- bit j of m (j < 16)
+__device__ __forceinline__ uint32_t fpr_spread16(uint32_t m) {
+    m = (m | (m << 8)) & 0x00FF00FFu;
+    m = (m | (m << 4)) & 0x0F0F0F0Fu;
+    m = (m | (m << 2)) & 0x33333333u;
+    return (m | (m << 1)) & 0x55555555u;
+}
+// the r pass's eight f bytes of one (row, block) from the row's sixteen draws (2 bits per column): byte p = (3 f(2p) + f(2p + 1)) << 2
+__device__ __forceinline__ uint2 fpr_row_word(uint32_t K) {
+    const uint32_t v = 3u * (K & 0x33333333u) + ((K >> 2) & 0x33333333u);      // nibble p: 3 f(2p) + f(2p + 1) <= 8
+    uint32_t lo = v & 0xFFFFu, hi = v >> 16;
+    lo = (lo | (lo << 8)) & 0x00FF00FFu;
+    hi = (hi | (hi << 8)) & 0x00FF00FFu;
+    lo = (lo | (lo << 4)) & 0x0F0F0F0Fu;
+    hi = (hi | (hi << 4)) & 0x0F0F0F0Fu;
+    return make_uint2(lo << 2, hi << 2);
+}
+
+__global__ __launch_bounds__(64 * FR_WAVES) void gibbs_f_run_kernel(const double *__restrict__ S_B, const double *__restrict__ lMf,
+                                                           const double *__restrict__ hyper, uint8_t *__restrict__ f_state,
+                                                           const uint32_t *__restrict__ r_U, int Nreg, int U, int64_t C, int GW,
+                                                           uint32_t chain0, uint64_t seed, uint32_t sweep, float margin,
+                                                           uint2 *__restrict__ f_S, int NBLK, unsigned long long *__restrict__ dbg,
+                                                           const char *__restrict__ frec, const double *__restrict__ lM, int n_tiles,
+                                                           unsigned *__restrict__ votes) {
+    static_assert(16 % FR_WAVES == 0, "a workgroup's chain words lie in one group of 16");
+    static_assert(FR_W == R_NB && FR_W == 16 && FT_W == 4, "a run is one block of the r pass's f words: sixteen columns, four tiles");
+    __shared__ uint32_t vote[FR_WAVES];  // per wave: the run's tiles (bit q) in which some lane's uniform is out of range
+    const int NPAIR = (U + 1) >> 1;
+    const fpr_run R = fpr_locate((int)blockIdx.x, Nreg);
+    const int lane = threadIdx.x & 63;
+    const int wv = (int)(threadIdx.x >> 6);
+    const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.y * (blockDim.x >> 6)) + wv);
+    const size_t rec_tile = (size_t)NPAIR * (FP_EC * F_REC_PIECES * 16);        // bytes of a tile's records
+    const fcd_f_edge_rec *edge_c = reinterpret_cast<const fcd_f_edge_rec *>(frec + (size_t)n_tiles * rec_tile);
+    // lane e < 32: edge e's rule at this sweep's hyper
+    const int lr = (lane >> 4) & 1, lj = lane & (FR_W - 1);
+    const bool present = lane < 2 * FR_W && lj < (lr ? R.cnt1 : R.cnt0);
+    int mode = -1;
+    if (present) {
+        const fcd_f_edge_rec k = edge_c[(lr ? R.cr1 : R.cr0) + lj];
+        const double c1 = (hyper[FCD_H_LNGAMMA + 1] - hyper[FCD_H_LNGAMMA + 0]) + k.d1;
+        const double c2 = (hyper[FCD_H_LNGAMMA + 2] - hyper[FCD_H_LNGAMMA + 0]) + k.d2;
+        mode = fcd_f_edge_mode(c1, c2, k.b, fcd_f_edge_delta(c1, c2, NPAIR, k.a), FCD_F_SURE_T);
+    }
+    const uint32_t pm = (uint32_t)__ballot(present), dm = (uint32_t)__ballot(mode >= 0);
+    const uint32_t m1 = (uint32_t)__ballot(mode == 1), m2 = (uint32_t)__ballot(mode == 2);
+    uint32_t oe = 0;                     // edges for which some lane of this wave is out of range (wave-uniform)
+    if (w < GW) {
+        const uint32_t chain = chain0 + (uint32_t)w * 64u + lane;
+        uint32_t out = 0;                // this lane's
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int cnt = r ? R.cnt1 : R.cnt0;
+            if (cnt == 0) continue;
+            const int64_t cr = r ? R.cr1 : R.cr0;
+            const int64_t b1 = (cr + cnt - 1) >> 2;
+#pragma unroll 1
+            for (int64_t b = cr >> 2; b <= b1; ++b) {
+                const fcd_u4 rnd = fcd_philox((uint32_t)b, chain, sweep, FCD_KIND_F, (uint32_t)seed, (uint32_t)(seed >> 32));
+                const int j0 = (int)(4 * b - cr);        // column (from the run's first) of the block's word 0
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float xf = (float)fcd_word(rnd, q) * 2.3283064e-10f;
+                    const bool bad = !(xf > 1e-6f && xf < 0.999999f);
+                    if (bad && j0 + q >= 0 && j0 + q < cnt) out |= 1u << (FR_W * r + j0 + q);
+                }
+            }
+        }
+        if (__ballot(out != 0u) != 0ull) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) out |= (uint32_t)__shfl_xor((int)out, o, 64);
+            oe = (uint32_t)__builtin_amdgcn_readfirstlane((int)out);
+        }
+        // the draws, 2 bits per column: the modes, then this wave's own draws of its exceptional edges
+        uint32_t K0 = (fpr_spread16(m1 & 0xFFFFu) | (fpr_spread16(m2 & 0xFFFFu) << 1));
+        uint32_t K1 = (fpr_spread16(m1 >> 16) | (fpr_spread16(m2 >> 16) << 1));
+        const uint32_t X = (pm & ~dm) | oe;
+        if (__builtin_expect(X != 0u, 0)) {
+            const uint4 *__restrict__ ru = reinterpret_cast<const uint4 *>(r_U) + (int64_t)w * Nreg * 64;
+            uint32_t x = X;
+#pragma unroll 1
+            while (x != 0u) {
+                const int e = __builtin_ctz(x);
+                x &= x - 1u;
+                const int r = e >> 4, j = e & (FR_W - 1);
+                const int64_t c = (r ? R.cr1 : R.cr0) + j;
+                // the edge's record: tile tile0 + j / FT_W, edge (r, j % FT_W) of it
+                const char *rec = frec + (size_t)(R.tile0 + j / FT_W) * rec_tile + (size_t)(r * FT_W + j % FT_W) * (F_REC_PIECES * 16);
+                const fcd_u4 rnd = fcd_philox((uint32_t)(c >> 2), chain, sweep, FCD_KIND_F, (uint32_t)seed, (uint32_t)(seed >> 32));
+                const uint32_t xw = fcd_word(rnd, (int)(c & 3));
+                const int n = R.n0 + r, m = R.mb + j;
+                const uint4 vn = ru[(uint32_t)(n * 64) + (uint32_t)lane], vm = ru[(uint32_t)(m * 64) + (uint32_t)lane];
+                const uint4 Z = make_uint4((vn.x ^ vm.x) | ((vn.x & vm.x) << 2), (vn.y ^ vm.y) | ((vn.y & vm.y) << 2),
+                                           (vn.z ^ vm.z) | ((vn.z & vm.z) << 2), (vn.w ^ vm.w) | ((vn.w & vm.w) << 2));
+                uint32_t k = (uint32_t)fcd_f_run_edge(rec, edge_c + c, hyper, Z, U, xw, margin);
+                if (k & FPR_AMB) {
+                    // somewhere in the wave the fp32 sums cannot decide the draw: the edge again, in fp64, for the whole wave
+                    const double lg1 = hyper[FCD_H_LNGAMMA + 1] - hyper[FCD_H_LNGAMMA + 0], lg2 = hyper[FCD_H_LNGAMMA + 2] - hyper[FCD_H_LNGAMMA + 0];
+                    k = (uint32_t)fcd_f_exact_edge(lMf + c * U * 6, lg1 + (S_B[c * 3 + 1] - S_B[c * 3 + 0]), lg2 + (S_B[c * 3 + 2] - S_B[c * 3 + 0]),
+                                                   Z.x, Z.y, Z.z, Z.w, U, xw);
+                    if (lane == 0) atomicAdd(dbg, 1ull);
+                    const bool open = (k & FCD_F_OPEN) != 0;
+                    k &= 3u;
+                    if (__ballot(open) != 0ull) {
+                        const uint32_t ka = (uint32_t)fcd_f_abs_edge(lM, S_B, hyper, ru, c, n, m, U, chain, sweep, seed);
+                        if (open) k = ka;
+                    }
+                }
+                if (r) K1 = (K1 & ~(3u << (2 * j))) | (k << (2 * j));
+                else K0 = (K0 & ~(3u << (2 * j))) | (k << (2 * j));
+            }
+        }
+        // f_state: the edges of a row are consecutive 64-byte lines.  A row without an exceptional edge: lane l writes 16 bytes
+        // of edge l / 4 (its mode in every chain), one store; any other row edge by edge, a byte per lane.
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int cnt = r ? R.cnt1 : R.cnt0;
+            if (cnt == 0) continue;
+            uint8_t *line = f_state + ((int64_t)w * C + (r ? R.cr1 : R.cr0)) * 64;
+            const uint32_t Kr = r ? K1 : K0;
+            if (((X >> (FR_W * r)) & 0xFFFFu) == 0u) {
+                if ((lane >> 2) < cnt) {
+                    const uint32_t v = ((Kr >> (2 * (lane >> 2))) & 3u) * 0x01010101u;
+                    reinterpret_cast<uint4 *>(line)[lane] = make_uint4(v, v, v, v);
+                }
+            } else {
+#pragma unroll 1
+                for (int j = 0; j < cnt; ++j) (line + j * 64)[(uint32_t)lane] = (uint8_t)((Kr >> (2 * j)) & 3u);
+            }
+        }
+        if (f_S) {
+            // the r pass's f words.  A full run (sixteen columns below the diagonal pair or up to it): the eight bytes of each
+            // row's (n, block) word in one store; column halves and zeros tile by tile.  Any other run: tile by tile.
+            const bool full = R.n0 + 2 - R.mb >= FR_W;
+            if (full) {
+                // (the diagonal pair of row n0: (n0, n0 + 1) is the edge (n0 + 1, n0) of row 1)
+                const int jd = R.n0 + 1 - R.mb;
+                const uint32_t K0d = jd < FR_W ? K0 | (((K1 >> (2 * (jd - 1))) & 3u) << (2 * jd)) : K0;
+                uint2 *word = f_S + (int64_t)w * Nreg * NBLK * 64 + lane;
+                word[(int64_t)(R.n0 * NBLK + R.mb / R_NB) * 64] = fpr_row_word(K0d);
+                if (R.n0 + 1 < Nreg) word[(int64_t)((R.n0 + 1) * NBLK + R.mb / R_NB) * 64] = fpr_row_word(K1);
+            }
+#pragma unroll 1
+            for (int q = 0; q < R.ntile; ++q) {
+                fpt_tile T;
+                T.n0 = R.n0;
+                T.mb = R.mb + FT_W * q;
+                T.cnt0 = min(FT_W, T.n0 - T.mb);
+                T.cnt1 = T.n0 + 1 < Nreg ? min(FT_W, T.n0 + 1 - T.mb) : 0;
+                T.cr0 = R.cr0 + FT_W * q;
+                T.cr1 = R.cr1 + FT_W * q;
+                const uint32_t kt = ((K0 >> (8 * q)) & 0xFFu) | (((K1 >> (8 * q)) & 0xFFu) << 8);
+                if (full) fpt_write_f_words<false>(T, kt, w, lane, f_S, Nreg, NBLK);
+                else fpt_write_f_words<true>(T, kt, w, lane, f_S, Nreg, NBLK);
+            }
+        }
+    }
+    // the counters keep their meaning: per (pair-aligned tile, group of 16 chain words) with every present edge decided,
+    // f_sure_tiles where no lane of the group is out of range, f_sure_fallbacks where one is -- one word per wave, one barrier
+    // BEHIND the stores; the (up to 16 / FR_WAVES) workgroups of a group then meet in the item's word of the record table: each
+    // adds 1 << 16 and its tiles in a nibble of its own, the last one counts and leaves the word zero for the next pass
+    uint32_t ot = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (oe & (0x000F000Fu << (FT_W * q))) ot |= 1u << q;
+    if (lane == 0) vote[wv] = ot;
+    __syncthreads();
+    if (wv == 0) {
+        const uint32_t v = lane < (int)(blockDim.x >> 6) ? vote[lane & (FR_WAVES - 1)] : 0u;
+        uint32_t bm = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (__ballot((v >> q) & 1u) != 0ull) bm |= 1u << q;
+        // the group's workgroups: its chain words [16 y, min(16 y + 16, GW)) in pieces of blockDim.x / 64
+        const int w0 = (int)(blockIdx.y * (blockDim.x >> 6)), wpg = (int)(blockDim.x >> 6);
+        const int n_wg = (min(16, GW - (w0 & ~15)) + wpg - 1) / wpg;
+        bool last = true;
+        if (n_wg > 1) {
+            uint32_t all = 0;
+            if (lane == 0) {
+                unsigned *word = votes + (size_t)blockIdx.x * (size_t)((GW + 15) >> 4) + (size_t)(w0 >> 4);
+                const uint32_t mine = 0x10000u | (bm << (4 * ((w0 & 15) / wpg)));
+                all = atomicAdd(word, mine) + mine;
+                if ((int)(all >> 16) == n_wg) atomicExch(word, 0u);
+            }
+            all = (uint32_t)__builtin_amdgcn_readfirstlane((int)all);
+            last = (int)(all >> 16) == n_wg;
+            bm = (all | (all >> 4) | (all >> 8) | (all >> 12)) & 15u;
+        }
+        uint32_t n_sure = 0, n_back = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t tm = (0x000F000Fu << (FT_W * q)) & pm;
+            if (last && tm != 0u && (tm & ~dm) == 0u) {
+                if ((bm >> q) & 1u) n_back += 1;
+                else n_sure += 1;
+            }
+        }
+        if (lane == 0) {
+            if (n_sure) atomicAdd(dbg + 2, (unsigned long long)n_sure);
+            if (n_back) atomicAdd(dbg + 3, (unsigned long long)n_back);
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1630,7 +1901,20 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step
     } while (0)
 #define FCD_PX (unsigned long long *)ctx->dbg, c.lM
 #define FCD_PT f_S, NBLK, (unsigned long long *)ctx->dbg, (const char *)st.f_rec, c.lM
-        if (form == FCD_F_PAIR && pt && st.f_rec && st.f_sure && !(margin > 1.f) && ctx->knobs.f_sure != 1) {
+        const bool sure = form == FCD_F_PAIR && pt && st.f_rec && st.f_sure && !(margin > 1.f) && ctx->knobs.f_sure != 1;
+        if (sure && ctx->knobs.f_runs != 1 && (st.f_all || ctx->knobs.f_runs == 2)) {
+            // every tile decided at the hint (or knob f_runs = 2): the decided path in block-wide runs -- no dynamic LDS
+            const int rw = wpb < FR_WAVES ? wpb : FR_WAVES;
+            dim3 rgrid((unsigned)fpr_runs((Nreg + 1) / 2), (unsigned)((g.GW + rw - 1) / rw));
+            fcd_prof_begin(ctx, FCD_PROF_F, s);
+            hipLaunchKernelGGL(gibbs_f_run_kernel, rgrid, dim3(64 * rw), 0, s, c.S_B, c.lMf, c.hyper, c.f_state, r_U, (int)Nreg, (int)U, g.C,
+                               g.GW, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, margin, f_S, NBLK, (unsigned long long *)ctx->dbg,
+                               (const char *)st.f_rec, c.lM, (int)grid.x, (unsigned *)((char *)st.f_rec + pl.frec_votes));
+            fcd_prof_end(ctx, FCD_PROF_F, s);
+            ctx->n_frec_pass += 1;
+            ctx->n_fsure_pass += 1;
+            ctx->n_frun_pass += 1;
+        } else if (sure) {
             // (a table without decided tiles, the test hook f_tol and knob f_sure = 1 keep the kernel below)
             if (pl.f_NW == 1) FCD_LAUNCH_F((gibbs_f_pair_kernel<1, true, true, true>), FCD_KA_F_PAIR_S + 0, FCD_PT);
             else if (pl.f_NW == 2) FCD_LAUNCH_F((gibbs_f_pair_kernel<2, true, true, true>), FCD_KA_F_PAIR_S + 1, FCD_PT);
@@ -1802,21 +2086,22 @@ static const struct {
 // packed_ok, the cleared marks of the next r pass (whose r words are the ones this pass wrote); its f half rides in the packing
 // launch or in the pipelined r pass where they take it.  hyper_m: what the M-step writes (nullptr when mstep_every == 0); acc_mask: the
 // slots of the context's sweep accumulators to add to (bit k = slot k).
-// The hint of the record build just queued (gibbs_f_hint_kernel writes 2 build + any): polled in the
+// The hint of the record build just queued (gibbs_f_hint_kernel writes 4 build + 2 all + any): polled in the
 // pinned word for as long as a build can reasonably take, then behind a synchronisation of the stream.
-static int fcd_f_sure_hint_wait(fcd_ctx *ctx, hipStream_t s, bool &any) {
+static int fcd_f_sure_hint_wait(fcd_ctx *ctx, hipStream_t s, bool &any, bool &all) {
     const unsigned build = (unsigned)(ctx->n_frec_build & 0x3fffffff);
     const auto t0 = std::chrono::steady_clock::now();
     unsigned v = *ctx->f_sure_hint;
-    for (unsigned spin = 1; (v >> 1) != build; ++spin, v = *ctx->f_sure_hint) {
+    for (unsigned spin = 1; (v >> 2) != build; ++spin, v = *ctx->f_sure_hint) {
         if ((spin & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
             FCD_HIP_TRY(hipStreamSynchronize(s));
             v = *ctx->f_sure_hint;
-            if ((v >> 1) != build) return fcd_fail(ctx, FCD_ERR_DEVICE, "f pass: the record build left no hint");
+            if ((v >> 2) != build) return fcd_fail(ctx, FCD_ERR_DEVICE, "f pass: the record build left no hint");
             break;
         }
     }
     any = (v & 1u) != 0u;
+    all = (v & 2u) != 0u;
     return FCD_OK;
 }
 
@@ -1866,7 +2151,8 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
     if (use_rec) {
         ctx->n_frec_build += 1;
         hipLaunchKernelGGL(gibbs_f_records_kernel, dim3((unsigned)fpt_tiles((Nreg + 1) / 2)), dim3(64 * FP_EC), 0, s, c.S_B, c.lMf,
-                           c.hyper, (int)Nreg, (int)U, (char *)ctx->frec, (unsigned *)((unsigned long long *)ctx->dbg + 4));
+                           c.hyper, (int)Nreg, (int)U, (char *)ctx->frec, (unsigned *)((unsigned long long *)ctx->dbg + 4),
+                           (unsigned *)((char *)ctx->frec + pl.frec_votes), (int)((pl.frec_bytes - pl.frec_votes) / sizeof(unsigned)));
         FCD_LAUNCH_CHECK();
         hipLaunchKernelGGL(gibbs_f_hint_kernel, dim3(1), dim3(1), 0, s, (unsigned *)((unsigned long long *)ctx->dbg + 4), ctx->f_sure_hint,
                            (unsigned)(ctx->n_frec_build & 0x3fffffff), c.lM, c.hyper);
@@ -1878,7 +2164,7 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         st.f_packed = packed_ok && st.r_packed;
         st.fsq = st.f_packed ? nullptr : fsq;
         if (rec_built && st.f_packed && !st.f_rec) {
-            int rc = fcd_f_sure_hint_wait(ctx, s, st.f_sure);
+            int rc = fcd_f_sure_hint_wait(ctx, s, st.f_sure, st.f_all);
             if (rc) return rc;
             st.f_rec = ctx->frec;
         }

@@ -1537,7 +1537,8 @@ fcd_sweep_plan fcd_sweep_plan_for(const fcd_ctx *ctx, int64_t Nreg, int64_t U, i
         const size_t NPAIR = (size_t)(U + 1) / 2;
         p.f_shmem_rec = (size_t)FP_EC * NPAIR * 128 + FP_EC * 16 + 64;       // (+ the 16 vote words of a decided tile)
         p.frec_edge = (size_t)fpt_tiles((Nreg + 1) / 2) * NPAIR * FP_EC * F_REC_PIECES * 16;
-        p.frec_bytes = p.frec_edge + (size_t)fcd_tri(Nreg) * sizeof(fcd_f_edge_rec);
+        p.frec_votes = p.frec_edge + (size_t)fcd_tri(Nreg) * sizeof(fcd_f_edge_rec);
+        p.frec_bytes = p.frec_votes + (size_t)fpr_runs((Nreg + 1) / 2) * (size_t)((GW + 15) / 16) * sizeof(unsigned);
         if (p.frec_bytes > F_REC_CAP) p.frec_bytes = 0;
     }
     // ---- workspace

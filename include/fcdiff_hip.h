@@ -121,6 +121,12 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
  *               tile with every edge decided by the tables -- the mode leads by more than 16 nats in every r state -- such
  *               tiles draw their Philox words, test them against the range of the draw without exponential and, if every lane
  *               of the workgroup is inside, write the modes: no sums.  A/B runs and tests; not read from the environment)
+ *   "f_runs"    the form of that path: 0 = where the record build finds EVERY tile decided, one wave per (block-wide run of up
+ *               to four tiles, chain word) draws each Philox block of a row once, writes the modes with 16- and 8-byte stores
+ *               and draws by itself the few edges for which one of its lanes is out of range (no workgroup-wide vote, no tile
+ *               goes back as a whole); elsewhere the per-tile kernel; 1 = never the run form; 2 = the run form wherever the
+ *               path is taken at all (tests: edges the rule leaves open are then drawn inside the run kernel).  Not read
+ *               from the environment
  *   "tally_in_r" the f half of a sweep's tally (pooled counts of f, cnt_f) inside the pipelined r pass, counted by its in-order
  *               workgroups before their first block, while they wait for the first panel values: 0 = where those workgroups
  *               have 16 waves and a wave walks at most "tally_in_r_max_rounds" rounds of four edges (cfg3: 4 rounds), 1 = never
@@ -143,8 +149,9 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value);
  * carried the f half of the sweep's tally; "tally_f_in_r" = launches of the pipelined r pass that carried it,
  * "tally_in_r_max_rounds" = the threshold of knob tally_in_r = 0; "f_rec_passes" = f passes that read prebuilt pair records, "f_rec_builds" =
  * launches of the kernel that makes them, "f_rec_bytes" = the size of their table, "f_rec_min_sweeps" = the threshold of
- * knob f_records = 0; "f_sure_passes" = f passes that ran the kernel with the decided-tile path, "f_sure_tiles" = workgroups (a
- * pair-aligned tile x 16 chain words) that took it, "f_sure_fallbacks" = decided ones that a uniform outside the range sent back to
+ * knob f_records = 0; "f_sure_passes" = f passes that ran a kernel with the decided-tile path, "f_run_passes" = those of them in
+ * the run form (knob f_runs), "f_sure_tiles" = (pair-aligned tile x 16 chain words) items that took it, "f_sure_fallbacks" = decided
+ * ones in which a uniform outside the range sent the tile (run form: only that wave's edge) back to
  * the sums (the last two and "f_repeats", "r_exact_rows" are device counters: reading them synchronises); "dev_err" = the error word of the pipelined r pass as the host sees it now (see
  * fcd_ctx_check); "pipe_grid" / "pipe_capacity" = the grid of the last pipelined attempt of the r pass (its empty
  * workgroups included) and the workgroups the occupancy query says are resident at once for it (the form is taken where
@@ -191,6 +198,11 @@ int64_t fcd_N_to_C(int64_t Nreg);
 int64_t fcd_C_to_N(int64_t C);
 int64_t fcd_nm_to_c(int64_t n, int64_t m);
 int fcd_c_to_nm(int64_t c, int64_t *n, int64_t *m);
+/* The block-wide runs of the f pass's decided path (knob "f_runs"): fcd_f_run_count = their number at Nreg regions;
+ * fcd_f_run_locate writes run t's out[0..8] = first row n0 (rows n0, n0 + 1), first column, edges of row n0 and of row n0 + 1,
+ * first pair-aligned tile, number of tiles, edge id of each row's first column, and the Philox blocks the run draws. */
+int64_t fcd_f_run_count(int64_t Nreg);
+int fcd_f_run_locate(int64_t Nreg, int64_t t, int64_t *out9);
 
 /* ---- hyper-parameter block ---------------------------------------------------------------- */
 /* Writes hyper[0..7] from host values: gamma[3] and the 2-vector pi2 = {1-pi, pi} the reference

@@ -4,7 +4,8 @@
 Sweep time at Nreg 200, U 50, 1024 chains in one fcd_gibbs_run call, on
   weak    H 2, broad components (sigma 0.2 / 0.25 / 0.3, mu -0.05 / 0 / 0.05): no edge decided -- the record build leaves no
           hint and the call runs the kernel without the path;
-  cfg3    H 50, the model's components: every tile decided.
+  cfg3    H 50, the model's components: every tile decided -- the decided path runs in its run form (stat f_run_passes);
+  mixed   H 20: most tiles decided, not all -- the per-tile kernel with the decided-tile path.
 Prints one JSON line with ms per sweep of `--runs` calls of `--sweeps` sweeps each and the f_sure counters.  Run it once per
 build to compare two builds (FCDIFF_HIP_LIB names another library of the same ABI), alternating; knob f_sure = 1
 (--off) switches the path off inside one build.
@@ -24,7 +25,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--data", choices=("weak", "cfg3"), default="weak")
+    ap.add_argument("--data", choices=("weak", "cfg3", "mixed"), default="weak")
     ap.add_argument("--sweeps", type=int, default=300)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--off", action="store_true", help="knob f_sure = 1: never the decided-tile path")
@@ -32,7 +33,7 @@ def main():
     import fcdiff_amd
     from fcdiff_amd.gibbs import GibbsEngine
     (Nreg, U, G) = (200, 50, 1024)
-    H = 2 if args.data == "weak" else 50
+    H = {"weak": 2, "cfg3": 50, "mixed": 20}[args.data]
     model = fcdiff_amd.UnsharedRegionModel()
     if args.data == "weak":
         model.sigma = np.array([0.2, 0.25, 0.3])
@@ -56,7 +57,7 @@ def main():
             return ctx.stat(name)
         except Exception:      # noqa: BLE001  (a build from before the counters)
             return None
-    names = ("f_rec_passes", "f_sure_passes", "f_sure_tiles", "f_sure_fallbacks", "f_repeats")
+    names = ("f_rec_passes", "f_sure_passes", "f_run_passes", "f_sure_tiles", "f_sure_fallbacks", "f_repeats")
     s0 = [stat(k) for k in names]
     ms = []
     sweep = 64
