@@ -17,6 +17,10 @@ Sources (the first part of a set's name):
   from-data     b, bt and a model with epsilon = 0 (M[k, typical] = N_k exactly) and sigma_0 well below sigma_1,2: at a few
                 outlying bt only N_0 underflows, lM[c, u, 0, 0] = -inf; through the oracle's lik_tables (the GPU test builds
                 the same table with the library's kernel)
+  firm          all nine entries -inf at one patient of each placement edge and nowhere else; on every edge without such an
+                item S_B of type c % 3 is raised until the f pass's rule of decided edges (tests/f_sure_ref.py) decides the
+                edge with FIRM_MARGIN nats in hand.  The tiles around the -inf edges are then on the decided-tile path while
+                those edges -- their bounds are NaN -- stay open: the decided forms meet non-finite log-odds inside live tiles
 
 Placement.  `item` and `plant-*` touch the edges PLACE: row 0 and row 15 of a full block of 16 regions, region 32 of
 Nreg = 33 (the one-row last block), partners inside the block (the non-finite value is an in-block term of the r pass) and
@@ -34,9 +38,11 @@ import functools
 import numpy as np
 
 import boundary_probes as BP
+import f_sure_ref as R
 from oracle import c_oracle as CO
 
 NINF = -np.inf
+FIRM_MARGIN = 40.0                                                 # nats over 0 of the decided mode's comparisons of `firm` (the rule asks for 16)
 SUBSETS = ((0,), (1,), (2,), (0, 1), (0, 2), (1, 2))               # the six proper non-empty subsets of the types
 PATTERNS = SUBSETS + ((0, 1, 2),)                                  # ... and all three: the seven patterns of -inf among (a0, a1, a2)
 ONE_L = (0, 2, 1)                                                  # mixture cases of plant-one-l, in turn (at pi = 0.3: 49, 42, 9 % of the chains)
@@ -133,12 +139,18 @@ def build(source, Nreg, U, G, seed, sweep=0, chain0=0):
     (f0, r0) = CO.gibbs_init(G, Nreg, U, 0.3, seed, chain0)
     T.planted = dict(edge=np.zeros(0, dtype=np.int64))
     recentre = []
-    if "item" in parts:
-        hit = rng.random((C, U)) < 0.01
+    if "item" in parts or "firm" in parts:
+        hit = rng.random((C, U)) < 0.01 if "item" in parts else np.zeros((C, U), dtype=bool)
         for (i, (n, m)) in enumerate(place_edges(Nreg)):
             hit[edge_id(n, m), (i * 3 + 1) % U] = True
         lM[hit] = NINF
         T.items = hit
+    if "firm" in parts:
+        with np.errstate(invalid="ignore"):
+            (_a, bounds) = R.edge_bounds(R.edge_table(lM))
+            short = FIRM_MARGIN - R.margins(S_B, lng, bounds)
+        for c in np.nonzero(~hit.any(axis=1))[0]:
+            S_B[c, c % 3] += short[c, c % 3]
     if "plant-all-l" in parts or "plant-one-l" in parts:
         P = _planted(Nreg, U, rng, 6 if Nreg < 33 else 8)
         for (c, u, s, l) in zip(P["edge"], P["u"], P["subset"], P["l"]):
@@ -182,6 +194,17 @@ def r_pattern(s):
     return (s[..., 0] == NINF).astype(np.int64) + 2 * (s[..., 1] == NINF).astype(np.int64)
 
 
+def decided_rule(T):
+    """What the f pass's rule of decided edges says of the set's table at its hyper (tests/f_sure_ref.py, on the CPU):
+    -> (the record build's hint: some tile is decided with FCD_F_SURE_DRIFT nats in hand, the mode of every edge at the
+    hint's threshold, -1 where open, the edges whose bounds are NaN)."""
+    assert T.U <= 64
+    with np.errstate(invalid="ignore", over="ignore"):
+        (a, b) = R.edge_bounds(R.edge_table(T.lM))
+        mode = R.edge_modes(T.S_B, T.lng, T.U, a, b, R.T - R.DRIFT)
+        return R.hint(T.Nreg, T.S_B, T.lng, T.U, a, b), mode, np.nonzero(np.isnan(b).any(axis=1))[0]
+
+
 def f_uniforms(T, s=0):
     """(G, C) float64: the uniform of every f draw of compared sweep s."""
     return BP.f_words(T.seed, T.C, T.chain0 + np.arange(T.G), T.sweep + s).astype(np.float64) * (1.0 / 4294967296.0)
@@ -217,6 +240,7 @@ SETS = {
     "pi1-33-7": ("pi1",) + BIG + (171,), "pi1-17-64": ("pi1", 17, 64, 128, 172),
     "pi0+item-33-7": ("pi0+item",) + BIG + (181,), "pi0+item-33-70": ("pi0+item", 33, 70, 128, 182),
     "from-data-33-7": ("from-data",) + BIG + (191,), "from-data-16-2": ("from-data", 16, 2, 128, 192),
+    "firm-33-7": ("firm",) + BIG + (201,), "firm-17-64": ("firm", 17, 64, 128, 203),
 }
 
 

@@ -90,8 +90,9 @@ def new_engine(env, m, call, N, U, G, seed, chain0):
     return eng
 
 
-def run_case(env, m, N, U, G, seed, chain0, calls):
-    """-> the rise of STATS under f_sure = 1 and under f_sure = 0, and the prediction (passes, tiles, fallbacks)"""
+def run_case(env, m, N, U, G, seed, chain0, calls, after_call=None):
+    """-> the rise of STATS under f_sure = 1 and under f_sure = 0, and the prediction (passes, tiles, fallbacks);
+    after_call(knob f_sure, index of the call): called behind every call of both runs, to read the context's counters"""
     what = "N=%d U=%d G=%d" % (N, U, G)
     try:
         env.ctx.set_knob("f_records", 2)
@@ -127,6 +128,8 @@ def run_case(env, m, N, U, G, seed, chain0, calls):
             for (i, c) in enumerate(calls):
                 prepare(env, eng, m, c, i == 0)
                 counts = eng.run(sweep, c.n, mstep_every=1 if c.mstep else 0, accumulate_from=0, want_counts=True).cpu().numpy().copy()
+                if after_call is not None:
+                    after_call(knob, i)
                 if knob == 0:
                     later = [(sweep + j, hs[i][j][0:3]) for j in range(1, c.n)]      # (the first sweep of a call runs edge tiles)
                     pred += np.array(R.predict(N, U, G, chain0, seed, c.S_B, R.edge_table(c.lM), hs[i][0][0:3], later))

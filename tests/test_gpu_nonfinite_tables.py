@@ -16,6 +16,7 @@ import numpy.testing as nptest
 import pytest
 
 import boundary_probes as BP
+import f_sure_ref as FR
 import nonfinite_tables as NT
 from oracle import fcdiff_oracle as O
 
@@ -60,7 +61,8 @@ def up(env, a):
 
 
 # The forms of test_gpu_draw_boundaries.PATHS, and: every r draw / every f draw through its exact path (r_tol, f_tol), the
-# pair-tile f pass on records made once per call with and without the decided-tile rule (f_records = 2; f_sure = 1 is "off").
+# pair-tile f pass on records made once per call with and without the decided-tile rule (f_records = 2; f_sure = 1 is "off"),
+# and the decided path in its run form whatever the hint says of the other tiles (f_runs = 2: gibbs_f_run_kernel).
 PATHS = {
     "steps": dict(driver="steps", knobs={}),
     "packed": dict(driver="sweeps", knobs={}, pipelined=True),
@@ -73,24 +75,28 @@ PATHS = {
     "f_tol": dict(driver="sweeps", knobs={"f_tol": 1e30}, pipelined=True),
     "run+rec": dict(driver="run", knobs={"f_records": 2}, pipelined=True),
     "run+rec-nosure": dict(driver="run", knobs={"f_records": 2, "f_sure": 1}, pipelined=True),
+    "run+rec+runs": dict(driver="run", knobs={"f_records": 2, "f_runs": 2}, pipelined=True),
 }
+REC_PATHS = ("run+rec", "run+rec+runs")                               # the decided-tile rule is on: check_sweeps asserts which form ran
 STEP_FORMS = ("steps", "anyU+rstep", "generic")                       # no pipelined r pass in them
-COUNTS_REPEATS = ("steps", "packed", "run", "anyU+rstep", "dsplit", "r_tol", "f_tol", "run+rec", "run+rec-nosure")
+COUNTS_REPEATS = ("steps", "packed", "run", "anyU+rstep", "dsplit", "r_tol", "f_tol", "run+rec", "run+rec-nosure", "run+rec+runs")
 # not the full product: every source meets every f form (pair, pair tiles, any-U, scalar masks, generic) and every r form
 # (pipelined, one in-order workgroup, step per launch, one patient per panel workgroup, generic); gamma0 and item meet all paths
 _A = ["steps", "packed", "dsplit", "generic"]
 _B = ["run", "anyU+rstep", "mask+ub1"]
 _X = ["r_tol", "f_tol", "run+rec", "run+rec-nosure", "run"]
+_R = ["run+rec", "run+rec+runs"]
 PLAN = {
-    "item-33-7": _A + _X, "item-16-2": ["mask+ub1", "anyU+rstep", "generic"], "item-17-64": _B, "item-33-70": ["run", "steps"],
+    "item-33-7": _A + _X + ["run+rec+runs"], "item-16-2": ["mask+ub1", "anyU+rstep", "generic"], "item-17-64": _B + _R, "item-33-70": ["run", "steps"],
     "gamma0-33-7": _A + _X, "gamma0-16-2": ["mask+ub1", "anyU+rstep", "generic"], "gamma0-17-64": _B, "gamma0-33-70": ["run", "steps"],
     "gamma0-16-1": ["steps", "run", "mask+ub1"],
     "plant-all-l-33-7": _A, "plant-all-l-17-64": _B,
-    "plant-one-l-33-7": _A + ["run+rec"], "plant-one-l-16-2": _B, "plant-one-l-33-70": ["steps", "run"],
+    "plant-one-l-33-7": _A + _R, "plant-one-l-16-2": _B, "plant-one-l-33-70": ["steps", "run"],
     "gamma1-33-7": _A, "gamma1-16-1": _B, "gamma2-33-7": _A, "gamma2-33-70": _B,
     "pi0-33-7": _A + ["r_tol"], "pi0-16-2": _B, "pi1-33-7": _A + ["r_tol"], "pi1-17-64": _B,
-    "pi0+item-33-7": _A + ["r_tol"], "pi0+item-33-70": _B,
-    "from-data-33-7": _A + ["run+rec"], "from-data-16-2": _B,
+    "pi0+item-33-7": _A + ["r_tol"] + _R, "pi0+item-33-70": _B,
+    "from-data-33-7": _A + _R, "from-data-16-2": _B,
+    "firm-33-7": ["packed", "f_tol", "run+rec-nosure"] + _R, "firm-17-64": ["run"] + _R,
 }
 assert set(PLAN) == set(NT.SETS)
 CASES = [(s, p) for (s, ps) in PLAN.items() for p in ps]
@@ -107,11 +113,12 @@ def engine(env, T, spec, S_B=None, lM=None):
 
 
 def run_case(env, knobs, T, path, n_sweeps, S_B=None, lM=None):
-    """Import the initial state, run n_sweeps through `path`, export; returns (f, r, f_repeats, engine)."""
+    """Import the initial state, run n_sweeps through `path`, export; returns (f, r, f_repeats, engine, the rise of F_FORMS)."""
     spec = PATHS[path]
     knobs(**spec["knobs"])
     eng = engine(env, T, spec, S_B, lM)
     rep0 = env.ctx.stat("f_repeats")
+    forms0 = [env.ctx.stat(k) for k in F_FORMS]
     if spec["driver"] == "steps":
         for s in range(n_sweeps):
             eng.f_step(T.sweep + s)
@@ -126,7 +133,21 @@ def run_case(env, knobs, T, path, n_sweeps, S_B=None, lM=None):
     assert env.ctx.stat("dev_err") == 0
     if spec.get("pipelined") and T.U <= 8:
         assert env.ctx.stat("r_form_last") == 2
-    return f_g, r_g, env.ctx.stat("f_repeats") - rep0, eng
+    return f_g, r_g, env.ctx.stat("f_repeats") - rep0, eng, tuple(env.ctx.stat(k) - v for (k, v) in zip(F_FORMS, forms0))
+
+
+F_FORMS = ("f_rec_passes", "f_sure_passes", "f_run_passes")
+
+
+def expected_forms(T, path, n_sweeps):
+    """The rise of F_FORMS over a call of n_sweeps on a REC_PATHS path: every sweep after the first reads the call's records;
+    it runs the decided-tile path where the CPU's restatement of the record build's hint finds a decided tile, and that in
+    the run form under f_runs = 2 only -- none of these tables has every tile decided, the auto choice's condition."""
+    (hint, mode, _nan) = NT.decided_rule(T)
+    n_tiles_open = any(len(t) and (mode[t] < 0).any() for t in FR.tiles(T.Nreg))
+    assert n_tiles_open, "a set with every tile decided at the hint: the auto choice takes the run form too"
+    n = n_sweeps - 1
+    return (n, n if hint else 0, n if (hint and path == "run+rec+runs") else 0)
 
 
 def report(T, s, f_g, r_g):
@@ -156,8 +177,10 @@ def check_sweeps(env, knobs, T, name, path, S_B=None, lM=None):
     draws), then two from the same start: the issue's check."""
     reps = 0
     for n_sweeps in (1, 2):
-        (f_g, r_g, rep, _eng) = run_case(env, knobs, T, path, n_sweeps, S_B, lM)
+        (f_g, r_g, rep, _eng, forms) = run_case(env, knobs, T, path, n_sweeps, S_B, lM)
         reps = rep
+        if path in REC_PATHS:
+            assert forms == expected_forms(T, path, n_sweeps), (name, path, n_sweeps, forms)
         if not (np.array_equal(f_g, T.f_after[n_sweeps - 1]) and np.array_equal(r_g, T.r_after[n_sweeps - 1])):
             pytest.fail("%s / %s: %d f and %d r states differ from the oracle after %d sweep(s)\n%s"
                         % (name, path, int((f_g != T.f_after[n_sweeps - 1]).sum()), int((r_g != T.r_after[n_sweeps - 1]).sum()), n_sweeps,

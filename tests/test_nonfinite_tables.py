@@ -77,7 +77,7 @@ def test_inputs_hold_finite_values_and_minus_inf_only(name):
     for a in (T.lM, T.lng, T.lnpi2) + tuple(T.cond_f) + tuple(T.cond_r):
         assert not np.isnan(a).any() and not (a == np.inf).any()
     src = source(name)
-    assert np.isfinite(T.lM).all() == (not any(p in src for p in ("item", "plant", "from-data")))
+    assert np.isfinite(T.lM).all() == (not any(p in src for p in ("item", "plant", "from-data", "firm")))
     if "from-data" in src:
         # only N_0 underflows, only at the outliers, only in the typical case: M[0, typical] = N_0 at epsilon = 0
         bad = T.lM == -np.inf
@@ -161,6 +161,30 @@ def test_placements_are_hit():
                 assert (rp[:, n, :] != 0).any() and (rp[:, m, :] != 0).any(), (name, n, m)
         if src == "plant-one-l":
             assert len({n for n in rows if (rp[:, n, :] != 0).any()}) >= 2
+
+
+def test_firm_sets_put_the_minus_inf_edges_inside_decided_tiles():
+    """`firm`: the rule of decided edges (tests/f_sure_ref.py) decides every edge but the placement edges, whose bounds are
+    NaN; so the record build's hint says "some tile, not every tile", each -inf edge is the open edge of a tile whose other
+    edges are decided, and the oracle draws the decided mode on every decided edge in both compared sweeps."""
+    import f_sure_ref as R
+    names = [n for n in SETS if source(n) == "firm"]
+    assert {NT.SETS[n][1:3] for n in names} == {(33, 7), (17, 64)}
+    for name in names:
+        T = NT.build_set(name)
+        (hint, mode, nan_bounds) = NT.decided_rule(T)
+        place = sorted(NT.edge_id(n, m) for (n, m) in NT.place_edges(T.Nreg))
+        rest = np.setdiff1d(np.arange(T.C), place)
+        assert hint and nan_bounds.tolist() == place == np.nonzero(T.items.any(axis=1))[0].tolist(), name
+        assert (mode[place] == -1).all() and np.array_equal(mode[rest], rest % 3), name
+        n_tiles = sum(len(t) > 0 for t in R.tiles(T.Nreg))
+        decided = R.decided_tiles(T.Nreg, mode)
+        assert 0 < len(decided) == n_tiles - len({min(t) for t in R.tiles(T.Nreg) if len(t) and (mode[t] < 0).any()}) < n_tiles, name
+        assert any(len(t) > 1 and (mode[t] < 0).sum() == 1 for t in R.tiles(T.Nreg) if len(t)), name
+        for s in range(NT.N_SWEEPS):
+            assert (NT.f_pattern(T.cond_f[s])[:, place] == 6).all(), name
+            assert np.array_equal(T.f_after[s][:, rest], np.broadcast_to(mode[rest], (T.G, len(rest)))), name
+        print("%s: %d of %d tiles decided at the hint, %d edges with NaN bounds" % (name, len(decided), n_tiles, len(place)))
 
 
 def test_difference_form_draw_fails_on_these_sets():
