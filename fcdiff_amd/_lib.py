@@ -75,6 +75,7 @@ SIGNATURES = {
     "fcd_model_sample_shared": (_int, [_p, C.POINTER(_dbl), _i64, _i64, _i64, _u64, _p, _p, _p, _p, _p, _p, _p]),
     "fcd_corr_edges": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
     "fcd_corr_clean": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p]),
+    "fcd_corr_partial": (_int, [_p, _p, _i64, _i64, _i64, _p, _int, _dbl, _int, _p, _p, _p, _p]),
     "fcd_edge_cov_fit": (_int, [_p, _p, _i64, _i64, _p, _i64, _int, _p, _p, _p, _p]),
     "fcd_edge_cov_apply": (_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p]),
     "fcd_baseline_normative": (_int, [_p, _p, _p, _i64, _i64, _i64, _dbl, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -4,6 +4,9 @@ fitter takes.  Not part of the reference (fcdiff/fit.py:20-23 starts from correl
 
 clean() / correlations(confounds=, frame_mask=) put frame censoring and confound regression in front of the
 correlation, on the device (fcd_corr_clean, include/fcdiff_hip.h); their oracle is tests/corr_clean_ref.py.
+
+partial_correlations() / correlations(kind="partial") give partial correlations from a shrunk correlation matrix instead
+(fcd_corr_partial); oracle tests/partial_corr_ref.py.
 """
 import numpy as np
 
@@ -86,7 +89,74 @@ def clean(ts, *, confounds=None, frame_mask=None, ctx=None, as_numpy=True):
     return (resid.cpu().numpy(), info.cpu().numpy()) if as_numpy else (resid, info)
 
 
-def correlations(ts, fisher_z=False, ctx=None, as_numpy=True, *, confounds=None, frame_mask=None, return_info=False):
+def _check_shrinkage(shrinkage):
+    """(mode, value) of the C entry point; raises before any context exists."""
+    if isinstance(shrinkage, str):
+        if shrinkage != "ledoit_wolf":
+            raise ValueError("shrinkage must be 'ledoit_wolf' or a number in [0, 1], not %r" % (shrinkage,))
+        return (1, 0.0)
+    if isinstance(shrinkage, bool) or not isinstance(shrinkage, (int, float, np.integer, np.floating)):
+        raise ValueError("shrinkage must be 'ledoit_wolf' or a number in [0, 1], not %r" % (shrinkage,))
+    a = float(shrinkage)
+    if not (0.0 <= a <= 1.0):
+        raise ValueError("shrinkage %r lies outside [0, 1]" % (shrinkage,))
+    return (0, a)
+
+
+def partial_correlations(ts, shrinkage="ledoit_wolf", fisher_z=False, ctx=None, as_numpy=True, *, confounds=None,
+                         frame_mask=None, return_info=False, _max_chunk=None):
+    """
+    Partial correlations of every subject's regions, from a shrunk correlation matrix, on the device (fcd_corr_partial,
+    include/fcdiff_hip.h; oracle tests/partial_corr_ref.py).  ts : (S, Nreg, T) float64, 2 <= Nreg <= 1024.
+    Returns (C, S) float64 in the layout of correlations().
+    Per subject, over its n frames (T, or n_kept after cleaning): R = the correlation matrix of the live regions,
+    R_a = (1 - a) R + a I, Theta = R_a^-1, rho_ij = -Theta_ij / sqrt(Theta_ii Theta_jj), clipped to [-1, 1].
+    shrinkage : "ledoit_wolf" (Ledoit & Wolf 2004 on the standardised rows, per subject) or a fixed a in [0, 1].
+    A region whose edges correlations() gives as NaN (constant, all-zero residual, non-finite) is dead: it leaves the
+    problem and its edges are NaN.  A subject with fewer than two live regions is all NaN (status 2); so is one whose R_a is
+    numerically singular (a pivot <= 1e-12: a = 0 with n - 1 < p, or duplicate rows; status 1) -- nothing is regularised
+    behind the caller's back.  NaN edges are meant for a fit with `missing_data = True`.
+    fisher_z applies atanh.  confounds, frame_mask: as correlations(); the partial correlations are those of clean()'s
+    residuals over the kept frames.
+    return_info=True returns (out, info): info = {"alpha": (S,) the a used, "n_live": (S,), "status": (S,), "clean": the
+    (S, 3) array of clean() or None}.
+    Partial correlations are smaller in magnitude than correlations: the model's mu and sigma defaults do not fit them.
+    """
+    import torch
+    (mode, value) = _check_shrinkage(shrinkage)
+    cleaning = confounds is not None or frame_mask is not None
+    if cleaning:
+        _check_clean_shapes(ts, confounds, frame_mask)
+    elif len(_shape(ts)) != 3:
+        raise ValueError("ts must have shape (S, Nreg, T)")
+    ctx = ctx if ctx is not None else _lib.Context()
+    (cinfo, nfr) = (None, None)
+    if cleaning:
+        (t, cinfo) = _clean_device(ts, confounds, frame_mask, ctx)
+        nfr = cinfo[:, 0].contiguous()
+    else:
+        t = _device_f64(ts, ctx)
+    (S, Nreg, T) = (int(t.shape[0]), int(t.shape[1]), int(t.shape[2]))
+    out = torch.empty((util.N_to_C(Nreg), S), dtype=torch.float64, device=ctx.device)
+    alpha = torch.empty((S,), dtype=torch.float64, device=ctx.device)
+    pinfo = torch.empty((S, 2), dtype=torch.int32, device=ctx.device)
+    if _max_chunk is not None:
+        ctx.set_knob("partial_chunk", int(_max_chunk))
+    try:
+        ctx.call("fcd_corr_partial", _lib.dptr(t), S, Nreg, T, _lib.dptr(nfr), mode, value, 1 if fisher_z else 0, _lib.dptr(out),
+                 _lib.dptr(alpha), _lib.dptr(pinfo), _lib.stream_ptr())
+    finally:
+        if _max_chunk is not None:
+            ctx.set_knob("partial_chunk", 0)
+    info = {"alpha": alpha, "n_live": pinfo[:, 0], "status": pinfo[:, 1], "clean": cinfo}
+    if as_numpy:
+        out = out.cpu().numpy()
+        info = {k: (v.cpu().numpy() if v is not None else None) for (k, v) in info.items()}
+    return (out, info) if return_info else out
+
+
+def correlations(ts, fisher_z=False, ctx=None, as_numpy=True, *, confounds=None, frame_mask=None, return_info=False,
+                 kind="correlation"):
     """
     ts : (S, Nreg, T) float64 time series of S subjects.
     Returns (C, S) float64, row c = n(n-1)/2 + m (n > m, util.c_to_nm order), column = subject:
@@ -96,7 +166,13 @@ def correlations(ts, fisher_z=False, ctx=None, as_numpy=True, *, confounds=None,
     fisher_z applies atanh (default off: the model's defaults are on raw correlations, model.py:213, 236).
     confounds (S, Q, T), frame_mask (S, T): the correlations are those of the residuals clean() gives, over the kept frames
     (see clean); a region or subject with nothing left has NaN edges.  return_info=True returns (out, info).
+    kind="partial" is partial_correlations(..., shrinkage="ledoit_wolf") with the same arguments (its info is a dict).
     """
+    if kind == "partial":
+        return partial_correlations(ts, "ledoit_wolf", fisher_z, ctx, as_numpy, confounds=confounds, frame_mask=frame_mask,
+                                    return_info=return_info)
+    if kind != "correlation":
+        raise ValueError("kind must be 'correlation' or 'partial', not %r" % (kind,))
     import torch
     cleaning = confounds is not None or frame_mask is not None or return_info
     if cleaning:
@@ -118,7 +194,7 @@ def correlations(ts, fisher_z=False, ctx=None, as_numpy=True, *, confounds=None,
     return (out, info) if cleaning and return_info else out
 
 
-def sampling_variance(info, fisher_z=False):
+def sampling_variance(info, fisher_z=False, n_conditioned=0):
     """
     Per-subject sampling variance of a correlation, from the `info` (S, 3) that clean() / correlations(..., return_info=True)
     give (column 2: the residual degrees of freedom dof = n_kept - 1 - rank): what goes into a fit's `b_noise_var` /
@@ -131,11 +207,18 @@ def sampling_variance(info, fisher_z=False):
     Frames of a scan are not independent: temporal autocorrelation lowers the effective degrees of freedom below dof, so
     these variances are lower bounds on the real ones; a user who knows the effective dof of their acquisition passes
     their own variances instead.
+    n_conditioned (a number, or (S,)) is subtracted from dof: a partial correlation conditions on the other p - 2 live regions,
+    so pass p - 2 for an UNSHRUNK one (partial_correlations(..., shrinkage=0.0)) -- the classical 1 / (dof - (p - 2) - 2) under
+    Fisher z.  With shrinkage a > 0 the estimate is biased towards 0 and has less variance than this; the value is then only a
+    guide.  The default 0 is the plain correlation's variance.
     """
     info = np.asarray(info)
     if info.ndim != 2 or info.shape[1] != 3:
         raise ValueError("info must have shape (S, 3): n_kept, rank, dof per subject")
-    den = info[:, 2].astype(np.float64) - (2.0 if fisher_z else 0.0)
+    nc = np.asarray(n_conditioned, dtype=np.float64)
+    if nc.ndim > 1 or (nc.ndim == 1 and nc.shape[0] != info.shape[0]) or not np.all(nc >= 0):
+        raise ValueError("n_conditioned must be a non-negative number or one per subject")
+    den = info[:, 2].astype(np.float64) - nc - (2.0 if fisher_z else 0.0)
     out = np.full(den.shape, np.inf)
     np.divide(1.0, den, out=out, where=den > 0)
     return out

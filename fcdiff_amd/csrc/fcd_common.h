@@ -43,6 +43,7 @@ struct fcd_knobs {
     int tally_in_r;    // f half of the tally inside the pipelined r pass (its in-order workgroups, before their first block): 0 = where
                        // a wave's rounds are at most R_TALLY_MAX_ROUNDS, 1 = never (the tally after the pass counts f), 2 = wherever
                        // the form allows (16-wave in-order workgroups)
+    int partial_chunk; // > 0: fcd_corr_partial walks at most this many subjects per chunk (tests: the chunking changes no bit)
     int r_keep_words;  // 1: the tally makes the next pass's r words from the r bits (default: the pass's two r-word buffers swap
                        // roles from sweep to sweep -- what a pass wrote as r_Sn is the next pass's r_S)
 };
@@ -52,7 +53,8 @@ enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA
        FCD_KA_F_PAIR_R = FCD_KA_F_PAIR_T + 4, FCD_KA_F_PAIR_S = FCD_KA_F_PAIR_R + 4,
        FCD_KA_F_PAIR_BIG = FCD_KA_F_PAIR_S + 4, FCD_KA_R_STEP = FCD_KA_F_PAIR_BIG + 4, FCD_KA_R_PIPE = FCD_KA_R_STEP + 4, FCD_KA_CORR = FCD_KA_R_PIPE + 4, FCD_KA_COMPONENTS = FCD_KA_CORR + 1,
        FCD_KA_GLM = FCD_KA_COMPONENTS + 1,      // 3 kernels (observed, permutations, bits) x 4 design widths
-       FCD_KA_N = FCD_KA_GLM + 12 };
+       FCD_KA_PARTIAL = FCD_KA_GLM + 12,        // fcd_corr_partial's inversion kernel
+       FCD_KA_N = FCD_KA_PARTIAL + 1 };
 
 #define FCD_NAN_SLOTS 256
 
@@ -202,6 +204,13 @@ static inline int fcd_static_lds_check(fcd_ctx *ctx, const void *fn, int *done) 
 
 int fcd_comm_allreduce_counts(fcd_ctx *ctx, long long *counts, hipStream_t stream);     // fcd_comm.hip: no-op without a communicator
 int fcd_ws_reserve(fcd_ctx *ctx, size_t bytes);
+// fcd_corr_edges for a caller inside the library (fcd_corr_partial): its scratch starts ws_off bytes into the context's
+// workspace (the caller's own lies in front; `out` may point there once the caller has reserved ws_off +
+// fcd_corr_edges_ws_bytes), and the subject kernel slices the time axis as a call of S_slices subjects would -- a caller that
+// walks its subjects in chunks passes the whole call's S, so that the chunking changes no bit.  fcd_corr_edges is (.., 0, S, ..).
+int fcd_corr_edges_at(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, int64_t T, int fisher_z, double *out, size_t ws_off,
+                      int64_t S_slices, hipStream_t stream);
+size_t fcd_corr_edges_ws_bytes(const fcd_ctx *ctx, int64_t S, int64_t Nreg, int64_t T, int64_t S_slices);
 // square copy of the f state (see fcd_sweep_plan): grown like the workspace
 int fcd_fsq_reserve(fcd_ctx *ctx, size_t bytes);
 // prebuilt pair records of the f pass: grown like the square copy

@@ -444,30 +444,55 @@ __global__ __launch_bounds__(256) void corr_transpose_kernel(const double *__res
 
 }  // namespace
 
+// The subject kernel's slices of the time axis: about one workgroup per CU for a call of S_slices subjects (S subjects alone
+// would leave most CUs idle), no slice shorter than 2 steps of 32 samples
+static int64_t corr_time_slices(const fcd_ctx *ctx, int64_t T, int64_t S_slices) {
+    const int64_t steps_all = (T + 31) / 32;                        // (the kernel's steps: 32 samples)
+    int64_t KS = ctx->num_cu / S_slices;
+    if (KS > steps_all / 2) KS = steps_all / 2;
+    if (KS < 1) KS = 1;
+    if (KS > 16) KS = 16;
+    return KS;
+}
+// Up to 208 regions (16 waves x CORR_TPW tiles of 16 x 16 cover the lower triangle) the subject kernel runs
+constexpr int CORR_TPW = 6;
+static bool corr_subject_form(const fcd_ctx *ctx, int64_t Nreg) {
+    const int64_t RT = (Nreg + 15) / 16;
+    return RT * (RT + 1) / 2 <= 16 * CORR_TPW && ctx->knobs.corr_form != 1;
+}
+
+size_t fcd_corr_edges_ws_bytes(const fcd_ctx *ctx, int64_t S, int64_t Nreg, int64_t T, int64_t S_slices) {
+    const size_t C = (size_t)fcd_tri(Nreg);
+    if (corr_subject_form(ctx, Nreg)) {
+        const size_t RT = (size_t)((Nreg + 15) / 16), psz = RT * (RT + 1) / 2 * 256 + RT * 16;
+        return ((size_t)S * (size_t)corr_time_slices(ctx, T, S_slices) * psz + (size_t)S * C) * sizeof(double);
+    }
+    return ((size_t)S * Nreg * 2 + (size_t)S * C) * sizeof(double);
+}
+
 extern "C" int fcd_corr_edges(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, int64_t T, int fisher_z, double *out,
                               fcd_stream stream) {
+    return fcd_corr_edges_at(ctx, ts, S, Nreg, T, fisher_z, out, 0, S, (hipStream_t)stream);
+}
+
+int fcd_corr_edges_at(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, int64_t T, int fisher_z, double *out, size_t ws_off,
+                      int64_t S_slices, hipStream_t stream) {
     if (!ctx || !ts || !out) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_corr_edges: null pointer");
     if (S < 1 || Nreg < 2 || T < 2) return fcd_fail(ctx, FCD_ERR_SHAPE, "need S >= 1, Nreg >= 2, T >= 2 (Nreg=%lld, T=%lld)", Nreg, T);
     if (S > 65535 || Nreg > 46340 || T > INT32_MAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_corr_edges: shape too large");
     const int64_t rows = S * Nreg, C = fcd_tri(Nreg);
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = stream;
     if ((S + 31) / 32 > 65535) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_corr_edges: grid too large");
-    // Up to 208 regions (16 waves x 6 tiles of 16 x 16 cover the lower triangle): one workgroup per (subject, time slice)
-    constexpr int TPW = 6;
+    // one workgroup per (subject, time slice)
+    constexpr int TPW = CORR_TPW;
     const int RT = (int)((Nreg + 15) / 16), RP = RT * 16, NT = RT * (RT + 1) / 2;
-    if (NT <= 16 * TPW && ctx->knobs.corr_form != 1) {
-        // slices of the time axis: about one workgroup per CU (S subjects alone would leave most CUs idle), no slice
-        // shorter than 2 steps of 32 samples
-        const int64_t steps_all = (T + 31) / 32;                        // (the kernel's steps: 32 samples)
-        int64_t KS = ctx->num_cu / S;
-        if (KS > steps_all / 2) KS = steps_all / 2;
-        if (KS < 1) KS = 1;
-        if (KS > 16) KS = 16;
+    if (corr_subject_form(ctx, Nreg)) {
+        const int64_t KS = corr_time_slices(ctx, T, S_slices);
         const int64_t NWG = S * KS;
         const int PMAX = (int)KS;
         const size_t psz = (size_t)NT * 256 + RP;
         const size_t part_bytes = (size_t)S * PMAX * psz * sizeof(double);
-        int rc = fcd_ws_reserve(ctx, part_bytes + (size_t)S * C * sizeof(double));
+        int rc = fcd_ws_reserve(ctx, ws_off + part_bytes + (size_t)S * C * sizeof(double));
         if (rc) return rc;
         // the tickets live in the context, zero between launches (the last taker of a subject puts its ticket back):
         // no memset launch per call.  Growing them synchronises, like growing the scratch.
@@ -481,8 +506,8 @@ extern "C" int fcd_corr_edges(fcd_ctx *ctx, const double *ts, int64_t S, int64_t
             ctx->corr_tickets_n = (size_t)S;
         }
         unsigned *ticket = (unsigned *)ctx->corr_tickets;
-        double *part = (double *)ctx->ws;
-        double *tmp = (double *)((char *)ctx->ws + part_bytes);
+        double *part = (double *)((char *)ctx->ws + ws_off);
+        double *tmp = (double *)((char *)ctx->ws + ws_off + part_bytes);
         const size_t shmem = ((size_t)2 * RP * 34 + 3 * RP) * sizeof(double);      // (panels [2][RP][34]: the kernel's SLD)
         rc = fcd_lds_attr(ctx, FCD_KA_CORR, reinterpret_cast<const void *>(&corr_gram_subject_kernel<TPW>), shmem);
         if (rc) return rc;
@@ -496,9 +521,9 @@ extern "C" int fcd_corr_edges(fcd_ctx *ctx, const double *ts, int64_t S, int64_t
     // more regions: 64 x 64 blocks, the means and deviations in a pass of their own
     // workspace: means and deviations of the rows, then the subject-major copy of the result (grows the context's
     // scratch, which synchronises, the first time a shape needs it)
-    int rc = fcd_ws_reserve(ctx, ((size_t)rows * 2 + (size_t)S * C) * sizeof(double));
+    int rc = fcd_ws_reserve(ctx, ws_off + ((size_t)rows * 2 + (size_t)S * C) * sizeof(double));
     if (rc) return rc;
-    double *mean = (double *)ctx->ws, *sdev = mean + rows, *tmp = sdev + rows;
+    double *mean = (double *)((char *)ctx->ws + ws_off), *sdev = mean + rows, *tmp = sdev + rows;
     hipLaunchKernelGGL(corr_moments_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ts, rows, (int)T, mean, sdev);
     FCD_LAUNCH_CHECK();
     const int64_t nb = (Nreg + CB - 1) / CB;

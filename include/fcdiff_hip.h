@@ -107,6 +107,7 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
  *               whatever their size (the default below that: cfg3)
  *   "corr_form" 1: fcd_corr_edges in 64 x 64 blocks with a moments pass also where the one-workgroup-per-subject kernel
  *               (up to 208 regions) would run
+ *   "partial_chunk"  > 0: fcd_corr_partial walks at most this many subjects per chunk (tests; not read from the environment)
  *   "r_tol", "f_tol"  widen the margin inside which a fast r / f draw is repeated with the exact formula (1e30: all)
  *   "f_form"    2: the any-U pair kernel of the f pass also where the U <= 64 kernel would run; 3: scalar-mask form
  *   "f_pack"    1: the r pass's packing launch in every sweep (default: from the second sweep of a fcd_gibbs_run call on,
@@ -375,6 +376,31 @@ int fcd_corr_edges(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, int6
  * followed by zeros have the same correlation over T frames as over n_kept.  Deterministic; inputs are not written. */
 int fcd_corr_clean(fcd_ctx *ctx, const double *ts, const double *confounds, const uint8_t *frame_mask, int64_t S,
                    int64_t Nreg, int64_t Q, int64_t T, double *resid, int32_t *info, fcd_stream stream);
+/* Partial correlations with shrinkage towards the identity, per subject; oracle = tests/partial_corr_ref.py.
+ * ts (S, Nreg, T), 2 <= Nreg <= 1024; n_frames (S,) int32 or NULL (= T): subject s counts its first n = n_frames[s] frames.
+ * With n < T the rows must be what fcd_corr_clean leaves -- zero mean over the first n frames, exact zeros behind them
+ * (pass its info[:, 0]); the padding then enters no sum.
+ *   1  A region is dead for the subject where fcd_corr_edges gives NaN on all of its edges (a constant or all-zero row, a
+ *      non-finite value).  Dead regions leave the problem: p = the number of live ones, all their edges come out NaN, and
+ *      the inverse below is that of the live p x p block.
+ *   2  R = the sample correlation matrix of the live rows (its off-diagonals are fcd_corr_edges' values).
+ *   3  R_a = (1 - a) R + a I.  shrink_mode 0: a = shrink_value in [0, 1].  shrink_mode 1: Ledoit & Wolf (2004) on the
+ *      standardised rows z_it = (x_it - m_i) / s_i, s_i^2 = sum_t (x_it - m_i)^2 / n:  q_t = sum_i z_it^2, B = sum_t q_t^2,
+ *      F = p + 2 sum_{i>j} R_ij^2, beta = (B / n - F) / (p n), delta = (F - p) / p, a = 0 if delta <= 0 or beta <= 0, else
+ *      min(beta, delta) / delta.
+ *   4  Theta = R_a^-1 by blocked Gauss-Jordan without pivoting.  A pivot <= 1e-12 (a = 0 with n - 1 < p, duplicate rows):
+ *      the subject is numerically singular, all of its edges are NaN and its status says so; nothing is regularised.
+ *   5  out[c][s] = -Theta_nm / sqrt(Theta_nn Theta_mm) clipped to [-1, 1], c = n(n-1)/2 + m (n > m); fisher_z != 0: atanh.
+ * out (C, S); alpha (S,): the a used (NaN where status is 2 or 3); info (S, 2) int32: p_live, status -- 0 ok, 1 singular,
+ * 2 p_live < 2, 3 n_frames[s] outside [0, T] (checked on the device); every status but 0 leaves the subject's column NaN.
+ * The correlations are made by fcd_corr_edges' kernels; subjects are walked in chunks whose dense matrices stay below
+ * 256 MB (knob "partial_chunk": at most so many subjects per chunk), which changes no bit.  Uses the context's workspace.
+ * Deterministic (fixed reduction orders, no floating-point atomics); inputs are not written.
+ * FCD_ERR_ARG: null pointer, S, Nreg or T < 1, shrink_value outside [0, 1] or NaN in mode 0.  FCD_ERR_UNSUPPORTED: Nreg > 1024,
+ * unknown shrink_mode, S > 65535.  FCD_ERR_SHAPE: Nreg < 2 or T < 2, as fcd_corr_edges. */
+int fcd_corr_partial(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, int64_t T, const int32_t *n_frames,
+                     int shrink_mode, double shrink_value, int fisher_z, double *out, double *alpha, int32_t *info,
+                     fcd_stream stream);
 
 /* ---- covariate adjustment of the connections, fitted on the controls -----------------------------------------------------
  * Not in the reference; oracle = tests/covariates_ref.py.  For every connection c, ordinary least squares with an implied
