@@ -80,7 +80,13 @@ const char *fcd_last_message(const fcd_ctx *ctx);
 /* Context on the CURRENT hip device: reduction workspace + device properties.  create/destroy
  * allocate/free device memory (they synchronise); nothing else does, except that a call needing a
  * larger workspace than any before grows it (hipDeviceSynchronize + hipMalloc) -- call fcd_ctx_reserve
- * first to avoid that. */
+ * first to avoid that.
+ * Streams: every device entry point queues ALL of its work (launches, memsets, copies) on the fcd_stream it is given and
+ * returns without waiting for it, unless its comment says otherwise.  A context serves ONE stream at a time: its workspace,
+ * tickets and accumulators are shared by all of its calls, so consecutive calls on DIFFERENT streams need the caller's own
+ * ordering between them (an event or a synchronisation); calls on one stream need none.  Any number of contexts may run
+ * side by side, each on a stream of its own: there is no process-wide device state.  Growth of a context's scratch
+ * synchronises the DEVICE, every stream of it (stat "n_alloc" counts the growths). */
 int fcd_ctx_create(fcd_ctx **out);
 int fcd_ctx_destroy(fcd_ctx *ctx);
 /* Sizes every scratch buffer of the sweep at this shape (f / r pass workspace, square f copy) from the same plan the
@@ -633,7 +639,8 @@ int fcd_gibbs_r_step(fcd_ctx *ctx, const double *lM, const double *lMd, const do
                      const uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
                      int64_t chain0, uint64_t seed, int64_t sweep, int edge_mode, fcd_stream stream);
 /* n_sweeps x (f step, r step), sweeps numbered sweep0, sweep0+1, ...: fcd_gibbs_run's loop without M-step or counters.
- * When counts != NULL the pooled statistics of the LAST sweep are stored there (fcd_gibbs_stats: this rank's own). */
+ * When counts != NULL the pooled statistics of the LAST sweep are stored there (fcd_gibbs_stats: this rank's own).
+ * Waits for the stream as fcd_gibbs_run does (below) in a call that builds the f pass's records. */
 int fcd_gibbs_sweeps(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *lMd,
                      const double *hyper, uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0,
                      uint64_t seed, int64_t sweep0, int64_t n_sweeps, int edge_mode, int64_t *counts,
@@ -666,7 +673,14 @@ int fcd_gibbs_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits
  *   counts (nullable) receives the pooled statistics of the LAST sweep.
  * 4 launches per sweep (f pass; packing, which also carries the f half of the tally in workgroups of its own; pipelined r
  * pass; the rest of the tally: r counts, slot words, M-step) where the pipelined r pass fits the device at once, else
- * ceil(Nreg/16) + 4 (one launch per block step). */
+ * ceil(Nreg/16) + 4 (one launch per block step).
+ * NOT fully asynchronous: a call that builds the f pass's pair records (knob "f_records": by default a call with at least
+ * F_REC_MIN_SWEEPS pair-tile sweeps) queues the build and the first sweep, then reads the build's hint -- has the table
+ * decided tiles? -- from a pinned word before it queues the second sweep.  The host polls that word, so it waits until the
+ * stream has run everything queued before the build, the build and its hint kernel (whatever the caller queued on the
+ * stream before the call included); after two seconds it falls back to hipStreamSynchronize.  Only this stream is waited
+ * for.  A call without a record build (one sweep, knob f_records = 1, a shape without the pair-tile f pass) returns without
+ * waiting. */
 int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *lMd,
                   double *hyper,
                   uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0, uint64_t seed,
