@@ -434,37 +434,43 @@ def group_test(b, bt, n_perm=10000, *, missing_data=False, variance="pooled", se
     if S < 3:
         raise ValueError("group_test: %d subjects, a pooled variance needs 3" % S)
     glm = _glm_setup("group_test", b, bt, H, U, z_b, z_bt, permutations, labels, missing_data, variance, n_perm, seed)
+    if glm is not None and glm[1]["rank"] == 0:                  # every column dropped: the default call with those labels
+        out = group_test(b, bt, labels=(glm[2] >= H).astype(np.uint8), ctx=ctx, as_numpy=as_numpy)
+        out["permutations"] = glm[2] if as_numpy else torch.as_tensor(glm[2], device=out["t"].device)
+        out["design_info"] = glm[1]
+        return out
     if glm is not None:
-        return _group_test_glm(b, bt, C, N, H, U, glm, ctx, as_numpy)
-    flags = _options("group_test", b, bt, H, U, missing_data, variance)
-    if labels is None:
-        if int(n_perm) < 1:
-            raise ValueError("group_test: n_perm must be >= 1")
-        lab = draw_labels(n_perm, H, U, seed)
+        flags = 0
+        lab = (glm[2] >= H).astype(np.uint8)
     else:
-        lab = _check_labels(labels, S, U)
+        flags = _options("group_test", b, bt, H, U, missing_data, variance)
+        if labels is None:
+            if int(n_perm) < 1:
+                raise ValueError("group_test: n_perm must be >= 1")
+            lab = draw_labels(n_perm, H, U, seed)
+        else:
+            lab = _check_labels(labels, S, U)
     P = int(lab.shape[0])
     ctx = ctx if ctx is not None else _lib.Context()
     (bd, btd) = (_device_f64(b, ctx), _device_f64(bt, ctx))
     dev = ctx.device
     labd = torch.as_tensor(lab, device=dev)
-    t = torch.empty((C,), dtype=torch.float64, device=dev)
-    region = torch.empty((N,), dtype=torch.float64, device=dev)
-    null_max_t = torch.empty((P,), dtype=torch.float64, device=dev)
-    null_max_region = torch.empty((P,), dtype=torch.float64, device=dev)
-    count_t = torch.empty((C,), dtype=torch.int64, device=dev)
-    count_region = torch.empty((N,), dtype=torch.int64, device=dev)
-    out = {"t": t, "region": region, "null_max_t": null_max_t, "null_max_region": null_max_region, "count_t": count_t,
-           "count_region": count_region}
-    if flags == 0:
-        ctx.call("fcd_baseline_group_perm", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(labd), P, _lib.dptr(t),
-                 _lib.dptr(region), _lib.dptr(null_max_t), _lib.dptr(null_max_region), _lib.dptr(count_t),
-                 _lib.dptr(count_region), _lib.stream_ptr())
+    out = dict((k, torch.empty((n,), dtype=dt, device=dev)) for (k, n, dt) in (
+        ("t", C, torch.float64), ("region", N, torch.float64), ("null_max_t", P, torch.float64),
+        ("null_max_region", P, torch.float64), ("count_t", C, torch.int64), ("count_region", N, torch.int64)))
+    counts = [torch.empty((C,), dtype=torch.int64, device=dev) for _ in range(2)] if missing_data else [None, None]
+
+    def call(name, *rows, tail=()):
+        ctx.call(name, _lib.dptr(bd), _lib.dptr(btd), C, H, U, *rows, *[_lib.dptr(v) for v in out.values()],
+                 *[_lib.dptr(v) for v in tail], _lib.stream_ptr())
+
+    if glm is not None:
+        (designd, permd) = (_device_f64(glm[0], ctx), _device_perms(glm[2], dev))
+        call("fcd_baseline_group_glm", _lib.dptr(designd), int(designd.shape[1]), _lib.dptr(permd), P)
+    elif flags == 0:
+        call("fcd_baseline_group_perm", _lib.dptr(labd), P)
     else:
-        counts = [torch.empty((C,), dtype=torch.int64, device=dev) for _ in range(2)] if missing_data else [None, None]
-        ctx.call("fcd_baseline_group_perm_opt", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(labd), P, flags, _lib.dptr(t),
-                 _lib.dptr(region), _lib.dptr(null_max_t), _lib.dptr(null_max_region), _lib.dptr(count_t),
-                 _lib.dptr(count_region), _lib.dptr(counts[0]), _lib.dptr(counts[1]), _lib.stream_ptr())
+        call("fcd_baseline_group_perm_opt", _lib.dptr(labd), P, flags, tail=counts)
         if missing_data:
             out.update(n_controls=counts[0], n_patients=counts[1])
     host = dict((k, v.cpu().numpy()) for (k, v) in out.items())
@@ -473,50 +479,12 @@ def group_test(b, bt, n_perm=10000, *, missing_data=False, variance="pooled", se
     if as_numpy:
         out = host
         out.update(pv)
-        out["labels"] = lab
     else:
         out.update(dict((k, torch.as_tensor(v, device=dev)) for (k, v) in pv.items()))
-        out["labels"] = labd
-    return out
-
-
-def _group_test_glm(b, bt, C, N, H, U, glm, ctx, as_numpy):
-    """group_test() with covariates, behind its host checks."""
-    import torch
-    (W, info, perm) = glm
-    lab = (perm >= H).astype(np.uint8)
-    if info["rank"] == 0:                                        # every column dropped: the default call with those labels
-        out = group_test(b, bt, labels=lab, ctx=ctx, as_numpy=as_numpy)
-        out["permutations"] = perm if as_numpy else torch.as_tensor(perm, device=out["t"].device)
-        out["design_info"] = info
-        return out
-    P = int(perm.shape[0])
-    ctx = ctx if ctx is not None else _lib.Context()
-    (bd, btd) = (_device_f64(b, ctx), _device_f64(bt, ctx))
-    dev = ctx.device
-    (Wd, permd) = (_device_f64(W, ctx), _device_perms(perm, dev))
-    t = torch.empty((C,), dtype=torch.float64, device=dev)
-    region = torch.empty((N,), dtype=torch.float64, device=dev)
-    null_max_t = torch.empty((P,), dtype=torch.float64, device=dev)
-    null_max_region = torch.empty((P,), dtype=torch.float64, device=dev)
-    count_t = torch.empty((C,), dtype=torch.int64, device=dev)
-    count_region = torch.empty((N,), dtype=torch.int64, device=dev)
-    out = {"t": t, "region": region, "null_max_t": null_max_t, "null_max_region": null_max_region, "count_t": count_t,
-           "count_region": count_region}
-    ctx.call("fcd_baseline_group_glm", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(Wd), int(W.shape[1]), _lib.dptr(permd), P,
-             _lib.dptr(t), _lib.dptr(region), _lib.dptr(null_max_t), _lib.dptr(null_max_region), _lib.dptr(count_t),
-             _lib.dptr(count_region), _lib.stream_ptr())
-    host = dict((k, v.cpu().numpy()) for (k, v) in out.items())
-    pv = group_pvalues(host["t"], host["region"], host["null_max_t"], host["null_max_region"], host["count_t"],
-                       host["count_region"])
-    if as_numpy:
-        out = host
-        out.update(pv)
-        out.update(labels=lab, permutations=perm)
-    else:
-        out.update(dict((k, torch.as_tensor(v, device=dev)) for (k, v) in pv.items()))
-        out.update(labels=torch.as_tensor(lab, device=dev), permutations=torch.as_tensor(perm, device=dev))
-    out["design_info"] = info
+    out["labels"] = lab if as_numpy else labd
+    if glm is not None:
+        out["permutations"] = glm[2] if as_numpy else torch.as_tensor(glm[2], device=dev)
+        out["design_info"] = glm[1]
     return out
 
 

@@ -34,8 +34,11 @@ sys.path.insert(0, ROOT)
 
 PS = (1000, 10000)
 THRESHOLD = 3.0
-KERNELS = ("network_bits_kernel", "graph_components_kernel", "group_centre_kernel", "group_pack_kernel", "baseline_group_kernel",
-           "group_observed_kernel", "group_observed_region_kernel", "group_fold_kernel")
+# matched as substrings of the traced names: the shells are templates over the statistic (network_bits_kernel<stat_plain>, ...).
+# baseline_group_kernel is what group_perm_kernel was called before the three statistics shared their shells: a library of
+# that time is traced with the same script.
+KERNELS = ("network_bits_kernel", "graph_components_kernel", "group_centre_kernel", "group_pack_kernel", "group_perm_kernel",
+           "baseline_group_kernel", "group_observed_kernel", "group_observed_region_kernel", "group_fold_kernel")
 
 
 def merge_stats(path, out, calls):
