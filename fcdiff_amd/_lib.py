@@ -78,6 +78,8 @@ SIGNATURES = {
     "fcd_corr_partial": (_int, [_p, _p, _i64, _i64, _i64, _p, _int, _dbl, _int, _p, _p, _p, _p]),
     "fcd_edge_cov_fit": (_int, [_p, _p, _i64, _i64, _p, _i64, _int, _p, _p, _p, _p]),
     "fcd_edge_cov_apply": (_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p]),
+    "fcd_site_harmonize_fit": (_int, [_p, _p]),          # (ctx, const fcd_harmonize_desc *): HarmonizeDesc below
+    "fcd_site_harmonize_apply": (_int, [_p, _p]),
     "fcd_baseline_normative": (_int, [_p, _p, _p, _i64, _i64, _i64, _dbl, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "fcd_baseline_group_perm": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
     "fcd_baseline_network_bits": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _dbl, _int, _p, _p, _p]),
@@ -141,6 +143,26 @@ SIGNATURES = {
     "fcd_evidence_temper": (_int, [_p, _dbl, _i64, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64), _p]),
     "fcd_member_loglik": (_int, [_p, _p, C.POINTER(_dbl), _p, _p, _i64, _i64, _i64, _int, _int, _p, _p, _p]),
 }
+
+FCD_HARMONIZE_NO_EB = 2      # flags of fcd_harmonize_desc: no empirical Bayes, the stars are the hats
+
+
+class HarmonizeDesc(C.Structure):
+    """fcd_harmonize_desc of include/fcdiff_hip.h, member for member; make() fills `size` and leaves the rest zero / NULL."""
+    _fields_ = ([("size", C.c_uint32), ("flags", C.c_uint32)]
+                + [(k, _i64) for k in ("C", "H", "S", "B", "Q", "Qp")]
+                + [(k, _p) for k in ("stream", "b", "site", "W", "x", "z", "T", "z_bar", "z_ref", "grand_mean", "pooled_sd", "beta",
+                                     "gamma_hat", "delta2_hat", "gamma_star", "delta2_star", "shift", "scale", "n_obs", "n_iter",
+                                     "info", "prior", "prior_info", "out")])
+
+    @classmethod
+    def make(cls, **members):
+        d = cls()
+        d.size = C.sizeof(cls)
+        for (k, v) in members.items():
+            setattr(d, k, v)
+        return d
+
 
 _lib = None
 

@@ -332,6 +332,8 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value) {
 
 int fcd_ctx_check(fcd_ctx *ctx) {
     if (!ctx) return FCD_ERR_ARG;
+    if (ctx->dev_err && *ctx->dev_err == 2u)      // (fcd_harmonize.hip)
+        return fcd_fail(ctx, FCD_ERR_DEVICE, "fcd_site_harmonize: a site id outside 0..B-1 reached the device");
     if (ctx->dev_err && *ctx->dev_err)
         return fcd_fail(ctx, FCD_ERR_DEVICE, "a device-side wait of the pipelined r pass was abandoned: the chain state is unusable");
     return FCD_OK;

@@ -434,6 +434,85 @@ int fcd_edge_cov_fit(fcd_ctx *ctx, const double *b, int64_t C, int64_t H, const 
 int fcd_edge_cov_apply(fcd_ctx *ctx, const double *x, int64_t C, int64_t S, const double *z, int64_t Q, const double *z_ref,
                        const double *beta, double *out, fcd_stream stream);
 
+/* ---- site harmonisation (ComBat) fitted on the controls ---------------------------------------------------------------------
+ * Not in the reference; oracle = tests/harmonize_ref.py.  Location and scale per site and connection, shrunk by empirical
+ * Bayes towards the site's law over all connections (Johnson et al. 2007), the site parameters fitted on the controls alone
+ * and then applied to anybody.  Both entry points take one descriptor; a member an entry point does not name is not read.
+ *
+ * Fit, per connection c over the controls observed there (FCD_DATA_NAN_MISSING: a NaN b[c,h] is unobserved and adds 0;
+ * without it every control counts and a NaN makes the connection "not fitted"), i(h) = site[h], n_i observed at site i,
+ * n = sum n_i, B_c = sites with n_i >= 1:
+ *   1  ybar_i = mean of site i;  d = W^T y;  e_h = (y_h - ybar_i(h)) - sum_q d_q W[h,q];  beta = T d;
+ *      sigma2 = sum_h e_h^2 / n (divided by n, not by the degrees of freedom), from the residuals themselves;
+ *   2  alpha_i = ybar_i - (z_bar_i - z_ref) . beta;  abar = sum_i (n_i / n) alpha_i;  gamma_hat_i = (alpha_i - abar) / sigma
+ *      where n_i >= 1;  delta2_hat_i = sum_{h in i} e_h^2 / (sigma2 (n_i - 1)) where n_i >= 2;  NaN where they do not exist;
+ *   3  status (info[c][3]): 0 fitted; 1 n - B_c - Qp < 1; 2 sum e^2 == 0; 3 a NaN that is not missing data; 4 a site id
+ *      outside 0..B-1 among the H (every connection; the context's error word is set too: fcd_ctx_check,
+ *      fcd_ctx_clear_error).  Not fitted: grand_mean, pooled_sd, the row of beta and the gamma / delta2 columns are NaN,
+ *      shift 0, scale 1, n_iter 0, and the connection enters no prior;
+ *   4  per site over the fitted connections where the estimate exists: gamma_bar, tau2 = mean and variance (ddof 1) of
+ *      gamma_hat_i, m, s2 those of delta2_hat_i, each in two passes (mean, then centred squares), a = (2 s2 + m^2) / s2,
+ *      b = (m s2 + m^3) / s2.  Undefined (prior_info[i][2] == 0, a and b NaN) with fewer than two members in either set or
+ *      where tau2 or s2 is not > 0 and finite: the site's pairs are then left alone (stars NaN, shift 0, scale 1);
+ *   5  per (site, fitted connection) the fixed point of  gamma <- (n_i tau2 gamma_hat + delta2 gamma_bar) / (n_i tau2 + delta2),
+ *      delta2 <- (((n_i - 1) delta2_hat + n_i (gamma_hat - gamma)^2) / 2 + b) / (n_i / 2 + a - 1)  from (gamma_hat, delta2_hat),
+ *      until |step of gamma| <= 1e-13 (1 + |gamma|) and |step of delta2| <= 1e-13 delta2, at most 1000 steps; n_iter is the
+ *      number of steps, NEGATIVE where the cap was hit.  n_i == 1: (n_i - 1) delta2_hat is 0 and delta2 starts at b / (a - 1);
+ *      n_i == 0: the prior, gamma_bar and b / (a - 1), 0 steps.  (ComBat stops all connections jointly at 1e-4: the same
+ *      fixed point, solved tightly.)  FCD_HARMONIZE_NO_EB: the stars are the hats, no prior is made (all NaN, counts 0), and
+ *      a pair with n_i < 2 or delta2_hat == 0 is left alone (shift 0, scale 1);
+ *   6  shift = sigma gamma_star, scale = sqrt(delta2_star).
+ * Apply, for subject s at site[s] with covariates z[s]:  d = sum_q beta[c,q] (z[s,q] - z_ref[q]) over q ascending from 0.0,
+ * m = grand_mean[c] + d,  out = ((x - m) - shift) / scale + m, one rounded operation per step in this order; NaN stays NaN.
+ * A pair with shift == 0 and scale == 1 is copied: out has x's bits.  A site id outside 0..B-1 gives NaN and sets the
+ * context's error word.
+ * Three launches for the fit (plus one per 128 doubles of T and of z_bar), one for apply; the fit uses 4.6 KB of the context's
+ * workspace.  Deterministic (fixed summation orders, no floating-point atomics); inputs are not written.
+ * FCD_ERR_ARG: null context, descriptor or needed pointer, size != sizeof(fcd_harmonize_desc), C, B, H (fit) or S (apply)
+ * < 1, Q < 0, Qp outside 0..Q.  FCD_ERR_UNSUPPORTED: unknown flags, B > 64, Q > 8, H > 4096, Qp > 0 together with
+ * FCD_DATA_NAN_MISSING (every connection would need a design of its own). */
+#define FCD_HARMONIZE_NO_EB 2
+typedef struct fcd_harmonize_desc {
+    uint32_t size;             /* sizeof(fcd_harmonize_desc): the version of the layout */
+    uint32_t flags;            /* FCD_DATA_NAN_MISSING | FCD_HARMONIZE_NO_EB (fit) */
+    int64_t C;                 /* connections (need not be triangular) */
+    int64_t H;                 /* fit: controls, <= 4096 */
+    int64_t S;                 /* apply: subjects (sessions flattened by the caller) */
+    int64_t B;                 /* sites, <= 64 */
+    int64_t Q;                 /* covariate columns, <= 8 */
+    int64_t Qp;                /* fit: columns of the design that are used, <= Q */
+    fcd_stream stream;         /* every launch goes here */
+    /* device, read */
+    const double *b;           /* fit: (C, H) */
+    const uint8_t *site;       /* fit: (H,), apply: (S,); values 0..B-1 */
+    const double *W;           /* fit: (H, Qp) orthonormal basis of the used columns, each centred within every site */
+    const double *x;           /* apply: (C, S) */
+    const double *z;           /* apply: (S, Q) */
+    /* host, read before the call returns (NULL where Q == 0) */
+    const double *T;           /* fit: (Q, Qp), beta = T (W^T y) in the units of the original columns */
+    const double *z_bar;       /* fit: (B, Q) the sites' means of the covariates */
+    const double *z_ref;       /* both: (Q,) the point the harmonised values refer to */
+    /* device, written by the fit; apply reads grand_mean, beta, shift and scale */
+    double *grand_mean;        /* (C,) abar */
+    double *pooled_sd;         /* (C,) sigma */
+    double *beta;              /* (C, Q) */
+    double *gamma_hat;         /* (B, C), as the five planes below */
+    double *delta2_hat;
+    double *gamma_star;
+    double *delta2_star;
+    double *shift;
+    double *scale;
+    int32_t *n_obs;            /* (B, C) n_i */
+    int32_t *n_iter;           /* (B, C) */
+    int32_t *info;             /* (C, 4) n, B_c, Qp, status */
+    double *prior;             /* (6, B) gamma_bar, tau2, m, s2, a, b */
+    int32_t *prior_info;       /* (B, 3) members of the gamma set, of the delta2 set, 1 where the prior is defined */
+    /* device, written by apply */
+    double *out;               /* (C, S) */
+} fcd_harmonize_desc;
+int fcd_site_harmonize_fit(fcd_ctx *ctx, const fcd_harmonize_desc *d);
+int fcd_site_harmonize_apply(fcd_ctx *ctx, const fcd_harmonize_desc *d);
+
 /* ---- classical baselines ---------------------------------------------------------------------------------------------------
  * Not in the reference; oracle = tests/baseline_ref.py.  b (C, H) controls, bt (C, U) patients, fp64, device; C triangular,
  * connections in the order of fcd_c_to_nm.  E(n) = the Nreg - 1 connections that touch region n.  Both calls are deterministic
