@@ -205,11 +205,31 @@ def random_mask(rs, S, T, drop):
     return m
 
 
-def make_input(seed, S, Nreg, T, Q, drop=0.0, level=0.0, scales=False):
+def chunk_masks(S, T, seed):
+    """Masks at the seams of clean_index_kernel's 256-frame chunks and clean_resid_kernel's 256-position blocks, S >= 5 and
+    T >= 513: subject 0 keeps frames 256 .. 455 only (nothing kept in the first chunk, n_kept = 200), subject 1 exactly
+    frames 0 .. 255 (n_kept = 256, nothing behind the first chunk), subject 2 everything but 256 .. 511 (a whole middle
+    chunk dropped), subject 3 everything but frame 0 and 254 .. 257 (a dropped run across the chunk edge), the others
+    random_mask at 0.3."""
+    assert S >= 5 and T >= 513
+    m = random_mask(np.random.RandomState(seed), S, T, 0.3)
+    m[0] = False
+    m[0, 256:456] = True
+    m[1] = False
+    m[1, :256] = True
+    m[2] = True
+    m[2, 256:512] = False
+    m[3] = True
+    m[3, 0] = False
+    m[3, 254:258] = False
+    return m
+
+
+def make_input(seed, S, Nreg, T, Q, drop=0.0, level=0.0, scales=False, mask=None):
     """
     ts (S, Nreg, T): unit noise + a shared component + an O(1) combination of the confounds, on `level`;
     confounds (S, Q, T): unit noise times per-column scales (1e-3 .. 1e3 when `scales`) on a level of its own;
-    mask: None when drop == 0, else random_mask.
+    mask: None when drop == 0, else random_mask; mask="chunk": chunk_masks(S, T, Nreg + T) instead.
     """
     rs = np.random.RandomState(seed)
     sc = np.logspace(-3, 3, Q) if (scales and Q > 1) else np.ones(Q)
@@ -219,8 +239,11 @@ def make_input(seed, S, Nreg, T, Q, drop=0.0, level=0.0, scales=False):
     ts = rs.standard_normal((S, Nreg, T)) + 0.7 * rs.standard_normal((S, 1, T)) + level
     if Q:
         ts = ts + np.einsum("snq,sqt->snt", a, z)
-    mask = random_mask(rs, S, T, drop) if drop > 0 else None
-    return (ts, cf if Q else None, mask)
+    m = random_mask(rs, S, T, drop) if drop > 0 else None
+    if mask is not None:
+        assert mask == "chunk" and drop == 0
+        m = chunk_masks(S, T, Nreg + T)
+    return (ts, cf if Q else None, m)
 
 
 def assert_conditions(cleaned, collinear=False):
@@ -234,7 +257,8 @@ def assert_conditions(cleaned, collinear=False):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the inputs tests/test_gpu_corr_clean.py compares against clean_ld; tests/test_corr_clean.py runs corr_fp64 on each
+# the inputs tests/test_gpu_corr_clean.py and tests/test_gpu_corr_clean_long.py compare against clean_ld;
+# tests/test_corr_clean.py runs corr_fp64 on each
 # ---------------------------------------------------------------------------------------------------------------------
 GPU_INPUTS = (
     [dict(seed=100 + N + T, S=3, Nreg=N, T=T, Q=0, drop=0.2, level=2.0) for N in (5, 16, 17, 33) for T in (37, 64, 65)]
@@ -246,12 +270,27 @@ GPU_INPUTS = (
 )
 
 
+# Long scans (tests/test_gpu_corr_clean_long.py): every QP instantiation of clean_resid_kernel that GPU_INPUTS leaves out
+# (Q = 25 and 32: QP 32; 41 and 48: 48; 49 and 56: 56), T around one block of 256 output positions (one lane in the second
+# block at T = 257), several blocks at T = 513 and 700 -- beyond 96 frames K_corr's subject kernel slices the time axis, and
+# behind n_kept its slices hold nothing but the zero padding -- and the chunk-mask cases.
+CHUNK_INPUTS = [dict(seed=800 + N + T, S=5, Nreg=N, T=T, Q=Q, drop=0.0, level=2.0, mask="chunk")
+                for (N, T, Q) in ((17, 513, 5), (33, 700, 9), (17, 700, 0))]
+GPU_LONG_INPUTS = (
+    [dict(seed=600 + Q, S=2, Nreg=17, T=320, Q=Q, drop=0.15, level=1.0) for Q in (25, 32, 41, 48, 49, 56)]
+    + [dict(seed=700 + N + T, S=3, Nreg=N, T=T, Q=Q, drop=0.3, level=2.0)
+       for (N, T, Q) in ((5, 255, 3), (5, 256, 3), (5, 257, 3), (33, 513, 5), (70, 700, 9))]
+    + CHUNK_INPUTS
+)
+
+
 def input_id(kw):
-    return "S%d-N%d-T%d-Q%d-d%g-l%g%s" % (kw["S"], kw["Nreg"], kw["T"], kw["Q"], kw["drop"], kw["level"], "-sc" if kw.get("scales") else "")
+    return "S%d-N%d-T%d-Q%d-d%g-l%g%s%s" % (kw["S"], kw["Nreg"], kw["T"], kw["Q"], kw["drop"], kw["level"],
+                                            "-sc" if kw.get("scales") else "", "-chunk" if kw.get("mask") else "")
 
 
 def gpu_case(kw):
-    """(ts, confounds, mask, clean_ld result) of one entry of GPU_INPUTS, the conditions asserted.  The `scales` cases carry a
+    """(ts, confounds, mask, clean_ld result) of one entry of GPU_INPUTS or GPU_LONG_INPUTS, the conditions asserted.  The `scales` cases carry a
     duplicated column behind the set whose condition number is checked."""
     (ts, cf, mask) = make_input(**kw)
     cleaned = clean_ld(ts, cf, mask)

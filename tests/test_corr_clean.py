@@ -1,9 +1,10 @@
 """
 The cleaning front-end without a GPU: the long-double oracle of tests/corr_clean_ref.py against two independent
 statements of the same quantity (numpy.linalg.lstsq residuals; the partial-correlation identity), its drop rule, the
-fp64 restatement of the kernels' pipeline against it on every input of tests/test_gpu_corr_clean.py (so that the bound
-used there, corr_ref.BOUND, is shown to be fair), and the host-side argument checks of fcdiff_amd.corr, which raise
-before any context exists.
+fp64 restatement of the kernels' pipeline against it on every input of tests/test_gpu_corr_clean.py and
+tests/test_gpu_corr_clean_long.py (so that the bound used there, corr_ref.BOUND, is shown to be fair), that those inputs
+sit on the seams they are meant for, and the host-side argument checks of fcdiff_amd.corr, which raise before any
+context exists.
 """
 import numpy as np
 import numpy.testing as nptest
@@ -97,7 +98,7 @@ def test_no_residual_rule():
 # ---------------------------------------------------------------------------------------------------------------------
 # the fp64 restatement of the kernels' pipeline stays inside the bound on the inputs of the GPU tests
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kw", CR.GPU_INPUTS, ids=CR.input_id)
+@pytest.mark.parametrize("kw", CR.GPU_INPUTS + CR.GPU_LONG_INPUTS, ids=CR.input_id)
 def test_fp64_restatement_within_bound(kw):
     (ts, cf, mask, cleaned) = CR.gpu_case(kw)
     (exp, info) = CR.corr_clean_ld(ts, cf, mask, cleaned=cleaned)
@@ -106,6 +107,30 @@ def test_fp64_restatement_within_bound(kw):
     assert np.isfinite(exp).all()
     (_d, excess) = R.worst_excess(got, exp, **R.BOUND)
     assert excess < 1.0, "fp64 restatement at %.3g of the bound" % excess
+
+
+def test_gpu_inputs_reach_every_resid_instantiation():
+    """clean_resid_kernel<QP> has nine instantiations, QP = 8 ceil(Q / 8) for Q = 0 .. 64: each is launched by some input."""
+    qs = set(kw["Q"] for kw in CR.GPU_INPUTS + CR.GPU_LONG_INPUTS)
+    assert set((Q + 7) // 8 for Q in qs) == set(range(9))
+
+
+def test_chunk_masks_sit_on_the_seams():
+    """n_kept exactly on a block of 256 positions, below it with two blocks of nothing but zero fill behind, and one past it;
+    the masks' dropped and kept runs where clean_index_kernel's 256-frame chunks meet."""
+    assert len(CR.CHUNK_INPUTS) == 3 and all(kw in CR.GPU_LONG_INPUTS for kw in CR.CHUNK_INPUTS)
+    seen = set()
+    for kw in CR.CHUNK_INPUTS:
+        (S, T) = (kw["S"], kw["T"])
+        m = CR.chunk_masks(S, T, kw["Nreg"] + T)
+        assert m.shape == (S, T) and m.dtype == bool and np.array_equal(m, CR.make_input(**kw)[2])
+        nk = m.sum(axis=1)
+        assert nk[:4].tolist() == [200, 256, T - 256, T - 5] and 0 < nk[4] < T
+        assert not m[0, :256].any() and not m[1, 256:].any() and not m[2, 256:512].any() and m[2, 255] and m[2, 512]
+        assert not m[3, 254:258].any() and m[3, 253] and m[3, 258] and not m[3, 0]
+        assert T > 512
+        seen.update(nk.tolist())
+    assert {200, 256, 257} <= seen
 
 
 def test_fp64_restatement_residuals():

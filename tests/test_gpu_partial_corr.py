@@ -9,9 +9,11 @@ kappa = cond(R_alpha) from the oracle.  With shrinkage the bound is at most 1.6e
 grows ill-conditioned with Nreg (kappa up to 1e7 at 65 regions, the bound with it), so alpha = 0 also runs on a benign mix
 (partial_corr_ref.make_series, mix = 0.3 / sqrt(Nreg)) where the bound is asserted to be below 1e-9.
 The inversion walks the matrix in blocks of NB = 16 columns and has one form; the shapes sit around NB, 2 NB and the
-64-region blocks of the correlation kernels.
+64-region blocks of the correlation kernels.  The batches sit around the 32-subject tiles of pc_dense_kernel and
+pc_emit_kernel (S = 31 .. 70, chunks that cut them), the long cleaned scans around the 256-frame blocks of pc_frame_kernel.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import numpy.testing as nptest
@@ -199,6 +201,103 @@ def test_chunking_changes_no_bit(env, shape):
         assert np.array_equal(a, b, equal_nan=True), chunk
         for k in ("alpha", "n_live", "status"):
             assert np.array_equal(ia[k], ib[k]), (chunk, k)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Batches past one 32-subject tile of pc_dense_kernel / pc_emit_kernel (blockIdx.y > 0, tile rows beyond the ninth, a full
+# tile, one subject in the last tile), chunks that cut the tiles, and scans whose frame blocks behind n_frames are empty.
+# Every case is held to tight=True: its oracle bound is below 1e-9.
+# ---------------------------------------------------------------------------------------------------------------------
+BATCHES = [(31, 5, 40), (32, 5, 41), (33, 17, 69), (65, 5, 40), (70, 17, 69), (40, 33, 300)]
+
+
+@functools.lru_cache(maxsize=None)
+def batch_series(shape):
+    (S, N, T) = shape
+    return PR.make_series(3000 + S + N, S, N, T)
+
+
+@pytest.mark.parametrize("shape", BATCHES, ids=lambda v: "S%d-N%d-T%d" % v)
+def test_batches_past_one_tile(env, shape):
+    ts = batch_series(shape)
+    for sh in (0.1, "ledoit_wolf"):
+        (got, info) = check(env, ts, sh, what="S %d, shrinkage %s" % (shape[0], sh), tight=True)
+        assert np.isfinite(got).all() and (info["status"] == 0).all()
+        z = env.corr.partial_correlations(ts, shrinkage=sh, fisher_z=True, ctx=env.ctx)
+        nptest.assert_allclose(z, np.arctanh(got), rtol=1e-13, atol=0)
+
+
+@pytest.mark.parametrize("chunk", [7, 31, 32, 33])
+def test_chunks_that_cut_tiles(env, chunk):
+    """s_base = 7, 14, ... in front of partial tiles; 31, 62 one short of a tile; 32, 64 on the tile edge; 33, 66 one past it."""
+    shape = (70, 17, 69)
+    ts = batch_series(shape)
+    (a, ia) = env.corr.partial_correlations(ts, ctx=env.ctx, return_info=True)
+    assert np.isfinite(a).all()
+    (b, ib) = env.corr.partial_correlations(ts, ctx=env.ctx, return_info=True, _max_chunk=chunk)
+    assert np.array_equal(a, b, equal_nan=True), chunk
+    for k in ("alpha", "n_live", "status"):
+        assert np.array_equal(ia[k], ib[k]), (chunk, k)
+
+
+def test_a_subject_alone_past_one_tile(env):
+    # T < 96: one time slice whatever S is, as in test_deterministic_and_independent_of_the_batch
+    shape = (65, 5, 40)
+    ts = batch_series(shape)
+    for sh in ("ledoit_wolf", 0.1):
+        (a, ia) = env.corr.partial_correlations(ts, shrinkage=sh, ctx=env.ctx, return_info=True)
+        assert np.isfinite(a).all()
+        for s in (0, 31, 32, 33, 63, 64):
+            (one, io) = env.corr.partial_correlations(ts[s:s + 1], shrinkage=sh, ctx=env.ctx, return_info=True)
+            assert np.array_equal(one[:, 0], a[:, s]) and io["alpha"][0] == ia["alpha"][s], s
+
+
+def test_statuses_inside_a_full_tile(env):
+    (S, N, T, Q) = (40, 5, 60, 2)
+    (ts, cf, _m) = CR.make_input(900, S, N, T, Q, level=1.0)
+    mask = CR.random_mask(np.random.RandomState(901), S, T, 0.2)
+    mask[5] = False                                                    # nothing kept
+    mask[33] = False
+    mask[33, 10:14] = True                                             # dof 1
+    ts[34, 1] = 3.0                                                    # a dead region
+    ts[39, 2, 7] = np.nan                                              # a kept NaN: a dead region
+    mask[39, 7] = True
+    cleaned = CR.clean_ld(ts, cf, mask)
+    n_kept = cleaned["info"][:, 0]
+    assert cleaned["info"][5].tolist() == [0, 0, -1] and cleaned["info"][33].tolist() == [4, Q, 1]
+    resid = cleaned["resid"].astype(np.float64)
+    regular = np.array([s for s in range(S) if s not in (5, 33, 34, 39)])
+    CR.assert_conditions(CR.clean_ld(ts[regular], cf[regular], mask[regular]))
+    for sh in ("ledoit_wolf", 0.1):
+        (got, info) = env.corr.partial_correlations(ts, shrinkage=sh, ctx=env.ctx, confounds=cf, frame_mask=mask, return_info=True)
+        assert np.array_equal(info["clean"], cleaned["info"])
+        check(env, resid, sh, n_frames=n_kept, got=got, info=info, what="statuses in a tile, shrinkage %s" % sh, tight=True)
+        assert np.flatnonzero(info["status"]).tolist() == [5, 33] and info["status"][[5, 33]].tolist() == [2, 2]
+        assert np.flatnonzero(info["n_live"] != N).tolist() == [5, 33, 34, 39] and info["n_live"][[5, 33, 34, 39]].tolist() == [0, 0, 4, 4]
+        assert np.isnan(got[:, [5, 33]]).all()
+        # the neighbours do not notice (36 and 40 subjects have the same slice count at T = 60)
+        ref = env.corr.partial_correlations(ts[regular], shrinkage=sh, ctx=env.ctx, confounds=cf[regular], frame_mask=mask[regular])
+        for s in (4, 6, 32, 35):
+            at = int(np.flatnonzero(regular == s)[0])
+            assert np.isfinite(got[:, s]).all() and np.array_equal(got[:, s], ref[:, at]), s
+
+
+@pytest.mark.parametrize("kw", CR.CHUNK_INPUTS, ids=CR.input_id)
+def test_long_cleaned_scans(env, kw):
+    """n_frames = 200 and 256 at T = 513 and 700: workgroups of pc_frame_kernel whose 256 frames all lie behind n, exact zeros
+    among the NBT partial sums of pc_shrink_kernel; n_frames one past and far past a block for the other subjects."""
+    (ts, cf, mask, cleaned) = CR.gpu_case(kw)
+    n_kept = cleaned["info"][:, 0]
+    assert n_kept[:2].tolist() == [200, 256] and kw["T"] > 512
+    resid = cleaned["resid"].astype(np.float64)
+    for sh in ("ledoit_wolf", 0.1):
+        (got, info) = env.corr.partial_correlations(ts, shrinkage=sh, ctx=env.ctx, confounds=cf, frame_mask=mask, return_info=True)
+        assert np.array_equal(info["clean"], cleaned["info"])
+        check(env, resid, sh, n_frames=n_kept, got=got, info=info, what="long cleaned scan, shrinkage %s" % sh, tight=True)
+        assert np.isfinite(got).all()
+        if sh == "ledoit_wolf":
+            (same, si) = env.corr.correlations(ts, ctx=env.ctx, kind="partial", confounds=cf, frame_mask=mask, return_info=True)
+            assert np.array_equal(same, got) and np.array_equal(si["alpha"], info["alpha"])
 
 
 def test_end_to_end(env):
