@@ -80,6 +80,9 @@ SIGNATURES = {
     "fcd_edge_cov_apply": (_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p]),
     "fcd_site_harmonize_fit": (_int, [_p, _p]),          # (ctx, const fcd_harmonize_desc *): HarmonizeDesc below
     "fcd_site_harmonize_apply": (_int, [_p, _p]),
+    "fcd_sym_eigh": (_int, [_p, _p]),                    # (ctx, const fcd_eigh_desc *): EighDesc below
+    "fcd_tangent_fit": (_int, [_p, _p]),                 # (ctx, const fcd_tangent_desc *): TangentDesc below
+    "fcd_tangent_apply": (_int, [_p, _p]),
     "fcd_baseline_normative": (_int, [_p, _p, _p, _i64, _i64, _i64, _dbl, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "fcd_baseline_group_perm": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
     "fcd_baseline_network_bits": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _dbl, _int, _p, _p, _p]),
@@ -162,6 +165,25 @@ class HarmonizeDesc(C.Structure):
         for (k, v) in members.items():
             setattr(d, k, v)
         return d
+
+
+FCD_TANGENT_EUCLIDEAN = 1    # flags of fcd_tangent_desc (fit): the reference is the arithmetic mean
+
+
+class EighDesc(C.Structure):
+    """fcd_eigh_desc of include/fcdiff_hip.h, member for member."""
+    make = classmethod(HarmonizeDesc.make.__func__)
+    _fields_ = ([("size", C.c_uint32), ("flags", C.c_uint32), ("B", _i64), ("n", _i64)]
+                + [(k, _p) for k in ("stream", "A", "w", "V", "status")])
+
+
+class TangentDesc(C.Structure):
+    """fcd_tangent_desc of include/fcdiff_hip.h, member for member."""
+    make = classmethod(HarmonizeDesc.make.__func__)
+    _fields_ = ([("size", C.c_uint32), ("flags", C.c_uint32), ("S", _i64), ("Nreg", _i64), ("T", _i64),
+                 ("shrink_mode", C.c_int32), ("max_iter", C.c_int32), ("shrink_value", _dbl), ("tol", _dbl)]
+                + [(k, _p) for k in ("stream", "ts", "n_frames", "alpha", "info", "G", "G_half", "W", "used", "n_iter",
+                                     "grad_norm", "out", "diag")])
 
 
 _lib = None

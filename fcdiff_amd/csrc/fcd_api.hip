@@ -202,6 +202,7 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->knobs.f_sure = 0;
     ctx->knobs.f_runs = 0;
     ctx->knobs.partial_chunk = 0;
+    ctx->knobs.tangent_chunk = 0;
     ctx->knobs.tally_in_r = (int)knob_env("FCD_TALLY_IN_R");
     ctx->knobs.r_keep_words = (int)knob_env("FCD_R_KEEP_WORDS");
     ctx->r_form_last = 0;
@@ -322,6 +323,7 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value) {
     else if (!strcmp(name, "f_runs")) k.f_runs = (int)value;
     else if (!strcmp(name, "corr_form")) k.corr_form = (int)value;
     else if (!strcmp(name, "partial_chunk")) k.partial_chunk = (int)value;
+    else if (!strcmp(name, "tangent_chunk")) k.tangent_chunk = (int)value;
     else if (!strcmp(name, "tally_in_r")) k.tally_in_r = (int)value;
     else if (!strcmp(name, "r_keep_words")) k.r_keep_words = (int)value;
     else if (!strcmp(name, "r_poll_limit")) k.r_poll_limit = (int)value;

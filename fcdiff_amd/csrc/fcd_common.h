@@ -44,6 +44,7 @@ struct fcd_knobs {
                        // a wave's rounds are at most R_TALLY_MAX_ROUNDS, 1 = never (the tally after the pass counts f), 2 = wherever
                        // the form allows (16-wave in-order workgroups)
     int partial_chunk; // > 0: fcd_corr_partial walks at most this many subjects per chunk (tests: the chunking changes no bit)
+    int tangent_chunk; // > 0: the same for fcd_tangent_fit and fcd_tangent_apply
     int r_keep_words;  // 1: the tally makes the next pass's r words from the r bits (default: the pass's two r-word buffers swap
                        // roles from sweep to sweep -- what a pass wrote as r_Sn is the next pass's r_S)
 };
@@ -54,7 +55,8 @@ enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA
        FCD_KA_F_PAIR_BIG = FCD_KA_F_PAIR_S + 4, FCD_KA_R_STEP = FCD_KA_F_PAIR_BIG + 4, FCD_KA_R_PIPE = FCD_KA_R_STEP + 4, FCD_KA_CORR = FCD_KA_R_PIPE + 4, FCD_KA_COMPONENTS = FCD_KA_CORR + 1,
        FCD_KA_GLM = FCD_KA_COMPONENTS + 1,      // 3 kernels (observed, permutations, bits) x 4 design widths
        FCD_KA_PARTIAL = FCD_KA_GLM + 12,        // fcd_corr_partial's inversion kernel
-       FCD_KA_N = FCD_KA_PARTIAL + 1 };
+       FCD_KA_EIGH = FCD_KA_PARTIAL + 1,        // fcd_sym_eigh's Jacobi kernel
+       FCD_KA_N = FCD_KA_EIGH + 1 };
 
 #define FCD_NAN_SLOTS 256
 
@@ -211,6 +213,21 @@ int fcd_ws_reserve(fcd_ctx *ctx, size_t bytes);
 int fcd_corr_edges_at(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, int64_t T, int fisher_z, double *out, size_t ws_off,
                       int64_t S_slices, hipStream_t stream);
 size_t fcd_corr_edges_ws_bytes(const fcd_ctx *ctx, int64_t S, int64_t Nreg, int64_t T, int64_t S_slices);
+// The front half of fcd_corr_partial for a caller inside the library (fcd_corr_partial itself, fcd_tangent_*): one chunk of Sc
+// subjects from time series to the dense shrunk correlation matrices.  A (Sc, PL, PL), PL = 16 ceil(Nreg / 16): R_alpha on the
+// live block, identity rows for dead and padding regions and for every row of a subject whose status is set; alpha and
+// info (p_live, status 0 / 2 / 3) at s0 + s of the call's arrays; the live flags (Sc, PL) int32 at w.o_live.  The plan lays
+// the scratch out from `base` bytes into the context's workspace (the caller reserves w.end + its own + edges_off's
+// fcd_corr_edges_ws_bytes); A may lie anywhere on the device: w.o_A is the slot the plan keeps for it, none with
+// with_A = false.  S_call as fcd_corr_edges_at's S_slices: the chunking changes no bit.
+struct fcd_shrunk_ws {
+    size_t o_redge, o_A, o_live, o_rowF, o_F, o_mean, o_isd, o_q, end;
+    int PL, RT, NBT;
+};
+void fcd_corr_shrunk_plan(int64_t SC, int64_t Nreg, int64_t T, size_t base, fcd_shrunk_ws &w, bool with_A = true);
+int fcd_corr_shrunk_at(fcd_ctx *ctx, const double *x, int64_t Sc, int64_t Nreg, int64_t T, const int32_t *n_frames, int64_t s0,
+                       int64_t S_call, int shrink_mode, double shrink_value, const fcd_shrunk_ws &w, size_t edges_off, double *A,
+                       double *alpha, int32_t *info, hipStream_t stream);
 // square copy of the f state (see fcd_sweep_plan): grown like the workspace
 int fcd_fsq_reserve(fcd_ctx *ctx, size_t bytes);
 // prebuilt pair records of the f pass: grown like the square copy

@@ -425,6 +425,58 @@ inline size_t pc_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
+void fcd_corr_shrunk_plan(int64_t SC, int64_t Nreg, int64_t T, size_t base, fcd_shrunk_ws &w, bool with_A) {
+    const int64_t C = fcd_tri(Nreg);
+    w.RT = (int)((Nreg + PNB - 1) / PNB);
+    w.PL = w.RT * PNB;
+    w.NBT = (int)((T + PC_TB - 1) / PC_TB);
+    const int PL = w.PL;
+    w.o_redge = base;
+    w.o_A = w.o_redge + pc_align((size_t)C * SC * sizeof(double));
+    w.o_live = w.o_A + (with_A ? pc_align((size_t)SC * PL * PL * sizeof(double)) : 0);
+    w.o_rowF = w.o_live + pc_align((size_t)SC * PL * sizeof(int32_t));
+    w.o_F = w.o_rowF + pc_align((size_t)SC * PL * sizeof(double));
+    w.o_mean = w.o_F + pc_align((size_t)SC * sizeof(double));
+    w.o_isd = w.o_mean + pc_align((size_t)SC * Nreg * sizeof(double));
+    w.o_q = w.o_isd + pc_align((size_t)SC * Nreg * sizeof(double));
+    w.end = w.o_q + pc_align((size_t)SC * w.NBT * sizeof(double));
+}
+
+int fcd_corr_shrunk_at(fcd_ctx *ctx, const double *x, int64_t Sc, int64_t Nreg, int64_t T, const int32_t *n_frames, int64_t s0,
+                       int64_t S_call, int shrink_mode, double shrink_value, const fcd_shrunk_ws &w, size_t edges_off, double *A,
+                       double *alpha, int32_t *info, hipStream_t st) {
+    const int64_t C = fcd_tri(Nreg);
+    const int PL = w.PL, NBT = w.NBT;
+    char *ws = (char *)ctx->ws;
+    double *redge = (double *)(ws + w.o_redge), *Fsum = (double *)(ws + w.o_F);
+    double *mean = (double *)(ws + w.o_mean), *isd = (double *)(ws + w.o_isd), *qpart = (double *)(ws + w.o_q);
+    double *rowF = (double *)(ws + w.o_rowF);
+    int32_t *live = (int32_t *)(ws + w.o_live);
+    // the time slices of the correlation kernel follow the CALL's S, not the chunk's: the chunking changes no bit
+    int rc = fcd_corr_edges_at(ctx, x, Sc, Nreg, T, 0, redge, edges_off, S_call, st);
+    if (rc) return rc;
+    const dim3 tgrid((unsigned)((C + 31) / 32), (unsigned)((Sc + 31) / 32));
+    hipLaunchKernelGGL(pc_dense_kernel, tgrid, dim3(256), 0, st, redge, Sc, C, PL, A);
+    FCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pc_rows_kernel, dim3((unsigned)(PL / 4), (unsigned)Sc), dim3(256), 0, st, A, (int)Nreg, PL, live, rowF);
+    FCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pc_total_kernel, dim3((unsigned)Sc), dim3(64), 0, st, live, rowF, PL, (int)T, n_frames, s0, Fsum, info);
+    FCD_LAUNCH_CHECK();
+    if (shrink_mode == 1) {
+        const int64_t rows = Sc * Nreg;
+        hipLaunchKernelGGL(pc_moments_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, rows, (int)Nreg, PL, (int)T,
+                           n_frames, s0, live, info, mean, isd);
+        FCD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(pc_frame_kernel, dim3((unsigned)NBT, (unsigned)Sc), dim3(PC_TB), 0, st, x, (int)Nreg, (int)T, n_frames,
+                           s0, mean, isd, NBT, qpart);
+        FCD_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(pc_shrink_kernel, dim3((unsigned)PL, (unsigned)Sc), dim3(256), 0, st, A, (int)Nreg, PL, (int)T, n_frames, s0,
+                       live, Fsum, qpart, NBT, shrink_mode, shrink_value, info, alpha);
+    FCD_LAUNCH_CHECK();
+    return FCD_OK;
+}
+
 extern "C" int fcd_corr_partial(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, int64_t T, const int32_t *n_frames,
                                 int shrink_mode, double shrink_value, int fisher_z, double *out, double *alpha, int32_t *info,
                                 fcd_stream stream) {
@@ -439,7 +491,6 @@ extern "C" int fcd_corr_partial(fcd_ctx *ctx, const double *ts, int64_t S, int64
     hipStream_t st = (hipStream_t)stream;
     const int64_t C = fcd_tri(Nreg);
     const int RT = (int)((Nreg + PNB - 1) / PNB), PL = RT * PNB;
-    const int NBT = (int)((T + PC_TB - 1) / PC_TB);
     // subjects per chunk: the dense matrices stay below PC_MAT_BYTES (knob "partial_chunk": fewer, for tests)
     int64_t SC = (int64_t)(PC_MAT_BYTES / ((size_t)PL * PL * sizeof(double)));
     if (ctx->knobs.partial_chunk > 0 && SC > ctx->knobs.partial_chunk) SC = ctx->knobs.partial_chunk;
@@ -451,50 +502,24 @@ extern "C" int fcd_corr_partial(fcd_ctx *ctx, const double *ts, int64_t S, int64
     const size_t shmem = ((size_t)PNB * WLD + PNB * 17) * sizeof(double);
     int rc = fcd_lds_attr(ctx, FCD_KA_PARTIAL, reinterpret_cast<const void *>(&pc_invert_kernel), shmem);
     if (rc) return rc;
-    // this call's part of the workspace, in front of what the correlation kernels take (sized by the first, largest chunk)
-    const size_t o_redge = 0;
-    const size_t o_A = o_redge + pc_align((size_t)C * SC * sizeof(double));
-    const size_t o_live = o_A + pc_align((size_t)SC * PL * PL * sizeof(double));
-    const size_t o_rowF = o_live + pc_align((size_t)SC * PL * sizeof(int32_t));
-    const size_t o_F = o_rowF + pc_align((size_t)SC * PL * sizeof(double));
-    const size_t o_mean = o_F + pc_align((size_t)SC * sizeof(double));
-    const size_t o_isd = o_mean + pc_align((size_t)SC * Nreg * sizeof(double));
-    const size_t o_q = o_isd + pc_align((size_t)SC * Nreg * sizeof(double));
-    const size_t o_dinv = o_q + pc_align((size_t)SC * NBT * sizeof(double));
+    // this call's part of the workspace, in front of what the correlation kernels take (sized by the first, largest chunk):
+    // the front half's (fcd_corr_shrunk_plan), then the inverse's diagonal
+    fcd_shrunk_ws w;
+    fcd_corr_shrunk_plan(SC, Nreg, T, 0, w);
+    const size_t o_dinv = w.end;
     const size_t mine = o_dinv + pc_align((size_t)SC * PL * sizeof(double));
     rc = fcd_ws_reserve(ctx, mine + fcd_corr_edges_ws_bytes(ctx, SC, Nreg, T, S));
     if (rc) return rc;
     char *ws = (char *)ctx->ws;
-    double *redge = (double *)(ws + o_redge), *A = (double *)(ws + o_A), *Fsum = (double *)(ws + o_F);
-    double *mean = (double *)(ws + o_mean), *isd = (double *)(ws + o_isd), *qpart = (double *)(ws + o_q);
-    double *dinv = (double *)(ws + o_dinv), *rowF = (double *)(ws + o_rowF);
-    int32_t *live = (int32_t *)(ws + o_live);
+    double *A = (double *)(ws + w.o_A), *dinv = (double *)(ws + o_dinv);
+    const int32_t *live = (const int32_t *)(ws + w.o_live);
     const unsigned inv_threads = RT >= 8 ? 1024u : 256u;
     for (int64_t s0 = 0; s0 < S; s0 += SC) {
         const int64_t Sc = S - s0 < SC ? S - s0 : SC;
-        const double *x = ts + s0 * Nreg * T;
-        // the time slices of the correlation kernel follow the CALL's S, not the chunk's: the chunking changes no bit
-        rc = fcd_corr_edges_at(ctx, x, Sc, Nreg, T, 0, redge, mine, S, st);
+        rc = fcd_corr_shrunk_at(ctx, ts + s0 * Nreg * T, Sc, Nreg, T, n_frames, s0, S, shrink_mode, shrink_value, w, mine, A, alpha,
+                                info, st);
         if (rc) return rc;
         const dim3 tgrid((unsigned)((C + 31) / 32), (unsigned)((Sc + 31) / 32));
-        hipLaunchKernelGGL(pc_dense_kernel, tgrid, dim3(256), 0, st, redge, Sc, C, PL, A);
-        FCD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(pc_rows_kernel, dim3((unsigned)(PL / 4), (unsigned)Sc), dim3(256), 0, st, A, (int)Nreg, PL, live, rowF);
-        FCD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(pc_total_kernel, dim3((unsigned)Sc), dim3(64), 0, st, live, rowF, PL, (int)T, n_frames, s0, Fsum, info);
-        FCD_LAUNCH_CHECK();
-        if (shrink_mode == 1) {
-            const int64_t rows = Sc * Nreg;
-            hipLaunchKernelGGL(pc_moments_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, rows, (int)Nreg, PL, (int)T,
-                               n_frames, s0, live, info, mean, isd);
-            FCD_LAUNCH_CHECK();
-            hipLaunchKernelGGL(pc_frame_kernel, dim3((unsigned)NBT, (unsigned)Sc), dim3(PC_TB), 0, st, x, (int)Nreg, (int)T, n_frames,
-                               s0, mean, isd, NBT, qpart);
-            FCD_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(pc_shrink_kernel, dim3((unsigned)PL, (unsigned)Sc), dim3(256), 0, st, A, (int)Nreg, PL, (int)T, n_frames, s0,
-                           live, Fsum, qpart, NBT, shrink_mode, shrink_value, info, alpha);
-        FCD_LAUNCH_CHECK();
         hipLaunchKernelGGL(pc_invert_kernel, dim3((unsigned)Sc), dim3(inv_threads), shmem, st, A, PL, RT, WLD, s0, info, dinv);
         FCD_LAUNCH_CHECK();
         hipLaunchKernelGGL(pc_emit_kernel, tgrid, dim3(256), 0, st, A, dinv, live, info, PL, Sc, s0, S, C, fisher_z ? 1 : 0, out);

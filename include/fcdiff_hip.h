@@ -114,6 +114,7 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
  *   "corr_form" 1: fcd_corr_edges in 64 x 64 blocks with a moments pass also where the one-workgroup-per-subject kernel
  *               (up to 208 regions) would run
  *   "partial_chunk"  > 0: fcd_corr_partial walks at most this many subjects per chunk (tests; not read from the environment)
+ *   "tangent_chunk"  > 0: the same for fcd_tangent_fit and fcd_tangent_apply
  *   "r_tol", "f_tol"  widen the margin inside which a fast r / f draw is repeated with the exact formula (1e30: all)
  *   "f_form"    2: the any-U pair kernel of the f pass also where the U <= 64 kernel would run; 3: scalar-mask form
  *   "f_pack"    1: the r pass's packing launch in every sweep (default: from the second sweep of a fcd_gibbs_run call on,
@@ -512,6 +513,100 @@ typedef struct fcd_harmonize_desc {
 } fcd_harmonize_desc;
 int fcd_site_harmonize_fit(fcd_ctx *ctx, const fcd_harmonize_desc *d);
 int fcd_site_harmonize_apply(fcd_ctx *ctx, const fcd_harmonize_desc *d);
+
+/* ---- batched symmetric eigendecomposition -------------------------------------------------------------------------------------
+ * A (B, n, n) fp64, device, symmetric (only the lower triangle is read), not necessarily definite; 1 <= n <= 1024.
+ * w (B, n): the eigenvalues ascending; V (B, n, n): column k of V[b] is the unit eigenvector of w[b][k]; status (B,) int32:
+ * 0 ok, 1 a non-finite entry (or entries whose squares overflow), 2 not converged; w and V of a matrix whose status is not 0
+ * are NaN, and it changes nothing of its neighbours in the batch.
+ * Two-sided parallel cyclic Jacobi, one workgroup per matrix: round-robin pairing (a bye for odd n), an off-diagonal at or
+ * below 2^-58 ||A||_F is not rotated, a sweep without a rotation ends the loop, 40 sweeps at the most.  A diagonal matrix is
+ * therefore returned as it is (sorted), exactly.  Up to n = 96 the matrix and the eigenvectors stay in LDS; above, they live in
+ * the context's workspace (2 n^2 doubles per matrix of a chunk of at most 512 MB).  Deterministic; A is not written.
+ * FCD_ERR_ARG: null context, descriptor or pointer, size != sizeof(fcd_eigh_desc), B or n < 1.  FCD_ERR_UNSUPPORTED: n > 1024,
+ * B > 2^24, flags != 0. */
+typedef struct fcd_eigh_desc {
+    uint32_t size;             /* sizeof(fcd_eigh_desc): the version of the layout */
+    uint32_t flags;            /* 0 */
+    int64_t B;                 /* matrices */
+    int64_t n;                 /* their order, <= 1024 */
+    fcd_stream stream;         /* every launch goes here */
+    const double *A;           /* device, read: (B, n, n) */
+    double *w;                 /* device, written: (B, n) */
+    double *V;                 /* (B, n, n) */
+    int32_t *status;           /* (B,) */
+} fcd_eigh_desc;
+int fcd_sym_eigh(fcd_ctx *ctx, const fcd_eigh_desc *d);
+
+/* ---- tangent-space connectivity fitted on the controls ----------------------------------------------------------------------
+ * Not in the reference; oracle = tests/tangent_ref.py (Varoquaux et al. 2010; kind="tangent" of nilearn, on correlation
+ * matrices).  Both entry points take one descriptor; a member an entry point does not name is not read.
+ *
+ * Per subject s, over its first n = n_frames[s] frames (NULL: T; rows as fcd_corr_partial wants them):
+ *   1  live regions, R, alpha and R_a = (1 - a) R + a I exactly as rules 1 - 3 of fcd_corr_partial (the same kernels).  The
+ *      correlation matrix is shrunk, not the covariance: the result does not depend on the scale of a region's series.
+ *   2  A matrix function acts on the whole matrix, so a dead region cannot leave the problem for one subject only: a subject
+ *      with 2 <= p_live < Nreg has status 4 and is all NaN.  The remedy is the caller's: drop that region for everyone.
+ *   3  status (info[s][1]): 0 ok; 1 numerically singular -- the fit asks lambda_min(R_a) <= 1e-12 lambda_max(R_a) of every
+ *      control, apply asks the same of M_s = W R_a W, which has R_a's inertia (a = 0 with n - 1 < p, duplicate rows); 2
+ *      p_live < 2; 3 n_frames[s] outside [0, T]; 4 a dead region; 5 the eigensolver gave up on a matrix of this subject (a
+ *      non-finite entry, as a non-finite W makes them, or no convergence).  Every status but 0 leaves the subject NaN;
+ *      nothing is regularised.  alpha is NaN for 2 and 3, as fcd_corr_partial's.
+ * Fit (ts = the controls, S of them):
+ *   4  used[s] = 1 where status is 0.  Fewer than two used controls: FCD_ERR_ARG.
+ *   5  G = the arithmetic mean of the used R_a, added in the order of the controls.  FCD_TANGENT_EUCLIDEAN: that is the
+ *      reference.  Otherwise the Frechet mean of the affine-invariant metric by the fixed point, from that G:
+ *         W = G^-1/2;  Tbar = mean over the used controls, in their order, of logm(W R_a,s W);
+ *         stop if ||Tbar||_F <= tol sqrt(Nreg) (converged) or after max_iter evaluations of Tbar (not converged);
+ *         G <- G^1/2 expm(Tbar) G^1/2
+ *      *n_iter = the number of evaluations of Tbar, NEGATIVE where the cap was hit; *grad_norm = the last ||Tbar||_F (NaN for
+ *      the Euclidean reference); G, G_half and W always belong to one and the same G.  A G with an eigenvalue <= 1e-12 of its
+ *      largest, or whose decomposition fails: FCD_ERR_ARG after the outputs are written.
+ *   6  The fit synchronises the stream once to count the used controls and once per iteration to read the norm.
+ * Apply (ts = any subjects; W = G^-1/2 (Nreg, Nreg), symmetric, from a fit or from the caller):
+ *   7  T_s = logm(W R_a,s W): M_s = W R_a W (the lower tiles computed and mirrored), M_s = V L V^T by fcd_sym_eigh's kernel,
+ *      T_s = V log(L) V^T (lower tiles, mirrored).  out[c][s] = T_s[n][m], c = n(n-1)/2 + m (n > m), unscaled (no sqrt 2);
+ *      diag[i][s] = T_s[i][i].  Never synchronises.  W lies on the device and is not looked at by the host: a non-finite W
+ *      gives every subject status 5.
+ * Subjects are walked in chunks whose matrices stay below 128 MB each (knob "tangent_chunk"); the mean over the controls is a
+ * running sum in their order, so the chunking changes no bit, and a subject alone gives the bits it has inside a batch.
+ * Deterministic (fixed reduction orders, no floating-point atomics); inputs are not written.  Uses the context's workspace;
+ * the fit keeps the R_a of all controls there (S x PL^2 doubles, PL = 16 ceil(Nreg / 16)).
+ * FCD_ERR_ARG: null context, descriptor or needed pointer, size != sizeof(fcd_tangent_desc), S, Nreg or T < 1, shrink_value
+ * outside [0, 1] or NaN in mode 0, tol not > 0 or max_iter < 1 for the geometric fit.  FCD_ERR_UNSUPPORTED: unknown flags or
+ * shrink_mode, Nreg > 1024, S > 65535, a fit above 64 GiB of workspace.  FCD_ERR_SHAPE: Nreg < 2 or T < 2. */
+#define FCD_TANGENT_EUCLIDEAN 1
+typedef struct fcd_tangent_desc {
+    uint32_t size;             /* sizeof(fcd_tangent_desc): the version of the layout */
+    uint32_t flags;            /* fit: FCD_TANGENT_EUCLIDEAN */
+    int64_t S;                 /* subjects (fit: controls), <= 65535 */
+    int64_t Nreg;              /* 2 .. 1024 */
+    int64_t T;                 /* frames */
+    int32_t shrink_mode;       /* 0: alpha = shrink_value; 1: Ledoit-Wolf per subject */
+    int32_t max_iter;          /* fit, geometric: >= 1 */
+    double shrink_value;
+    double tol;                /* fit, geometric: > 0 */
+    fcd_stream stream;         /* every launch goes here */
+    /* device, read */
+    const double *ts;          /* (S, Nreg, T) */
+    const int32_t *n_frames;   /* (S,) or NULL */
+    /* device, written by both */
+    double *alpha;             /* (S,) */
+    int32_t *info;             /* (S, 2) p_live, status */
+    /* device, written by the fit; apply reads W */
+    double *G;                 /* (Nreg, Nreg) */
+    double *G_half;            /* (Nreg, Nreg) G^1/2 */
+    double *W;                 /* (Nreg, Nreg) G^-1/2 */
+    uint8_t *used;             /* (S,) */
+    /* host, written by the fit */
+    int32_t *n_iter;
+    double *grad_norm;
+    /* device, written by apply */
+    double *out;               /* (C, S) */
+    double *diag;              /* (Nreg, S) */
+} fcd_tangent_desc;
+int fcd_tangent_fit(fcd_ctx *ctx, const fcd_tangent_desc *d);
+int fcd_tangent_apply(fcd_ctx *ctx, const fcd_tangent_desc *d);
 
 /* ---- classical baselines ---------------------------------------------------------------------------------------------------
  * Not in the reference; oracle = tests/baseline_ref.py.  b (C, H) controls, bt (C, U) patients, fp64, device; C triangular,
