@@ -201,6 +201,8 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->knobs.f_records = 0;           // (A/B runs and tests only)
     ctx->knobs.f_sure = 0;
     ctx->knobs.f_runs = 0;
+    ctx->knobs.r_sure = 0;
+    ctx->knobs.r_sure_x = 0.0;
     ctx->knobs.partial_chunk = 0;
     ctx->knobs.tangent_chunk = 0;
     ctx->knobs.tally_in_r = (int)knob_env("FCD_TALLY_IN_R");
@@ -210,6 +212,7 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->n_pack_tally = 0;
     ctx->n_r_tally = 0;
     ctx->n_frec_pass = ctx->n_frec_build = ctx->n_fsure_pass = ctx->n_frun_pass = 0;
+    ctx->n_rsure_pass = ctx->n_rsure_build = 0;
     int rc = fcd_ws_reserve(ctx, 1u << 20);
     if (rc == FCD_OK) {
         void *pin = nullptr;
@@ -217,11 +220,12 @@ int fcd_ctx_create(fcd_ctx **out) {
         if (rc == FCD_OK) {
             ctx->dev_err = (volatile unsigned *)pin;
             *ctx->dev_err = 0u;
-            rc = (int)hipHostMalloc(&pin, sizeof(unsigned), hipHostMallocDefault);
+            rc = (int)hipHostMalloc(&pin, 2 * sizeof(unsigned), hipHostMallocDefault);
         }
         if (rc == FCD_OK) {
             ctx->f_sure_hint = (volatile unsigned *)pin;
-            *ctx->f_sure_hint = 0u;         // (build numbers start at 1)
+            ctx->f_sure_hint[0] = 0u;       // (build numbers start at 1)
+            ctx->f_sure_hint[1] = 0u;       // (the r pass's bound build)
         }
     }
     if (rc) {
@@ -244,9 +248,9 @@ int fcd_ctx_create(fcd_ctx **out) {
         if (e == hipSuccess) e = hipMalloc(&ctx->nan_slots, FCD_NAN_SLOTS * 16 * sizeof(unsigned long long));
         ctx->n_alloc += 1;
         if (e == hipSuccess) e = hipMemset(ctx->nan_slots, 0, FCD_NAN_SLOTS * 16 * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc(&ctx->dbg, 8 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMalloc(&ctx->dbg, 16 * sizeof(unsigned long long));
         ctx->n_alloc += 1;
-        if (e == hipSuccess) e = hipMemset(ctx->dbg, 0, 8 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMemset(ctx->dbg, 0, 16 * sizeof(unsigned long long));
         if (e != hipSuccess) {
             fcd_ctx_destroy(ctx);
             return (int)e;
@@ -321,6 +325,8 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value) {
     else if (!strcmp(name, "f_records")) k.f_records = (int)value;
     else if (!strcmp(name, "f_sure")) k.f_sure = (int)value;
     else if (!strcmp(name, "f_runs")) k.f_runs = (int)value;
+    else if (!strcmp(name, "r_sure")) k.r_sure = (int)value;
+    else if (!strcmp(name, "r_sure_x")) k.r_sure_x = value;
     else if (!strcmp(name, "corr_form")) k.corr_form = (int)value;
     else if (!strcmp(name, "partial_chunk")) k.partial_chunk = (int)value;
     else if (!strcmp(name, "tangent_chunk")) k.tangent_chunk = (int)value;
@@ -368,6 +374,13 @@ int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out) {
     else if (!strcmp(name, "f_rec_min_sweeps")) *out = F_REC_MIN_SWEEPS;
     else if (!strcmp(name, "f_sure_passes")) *out = ctx->n_fsure_pass;
     else if (!strcmp(name, "f_run_passes")) *out = ctx->n_frun_pass;
+    else if (!strcmp(name, "r_sure_passes")) *out = ctx->n_rsure_pass;
+    else if (!strcmp(name, "r_sure_builds")) *out = ctx->n_rsure_build;
+    else if (!strcmp(name, "r_sure_sites") || !strcmp(name, "r_sure_exceptions")) {
+        unsigned long long v[16];
+        FCD_HIP_TRY(hipMemcpy(v, ctx->dbg, sizeof(v), hipMemcpyDeviceToHost));
+        *out = (int64_t)v[!strcmp(name, "r_sure_sites") ? 8 : 9];
+    }
     else if (!strcmp(name, "pipe_grid")) *out = ctx->pipe_grid;
     else if (!strcmp(name, "pipe_capacity")) *out = ctx->pipe_capacity;
     else if (!strcmp(name, "comm_world")) *out = ctx->comm ? ctx->comm_world : 0;

@@ -47,6 +47,9 @@ struct fcd_knobs {
     int tangent_chunk; // > 0: the same for fcd_tangent_fit and fcd_tangent_apply
     int r_keep_words;  // 1: the tally makes the next pass's r words from the r bits (default: the pass's two r-word buffers swap
                        // roles from sweep to sweep -- what a pass wrote as r_Sn is the next pass's r_S)
+    int r_sure;        // sparse r pass (gibbs_r_sparse_kernel: the sums of sites the tables decide are skipped): 0 = where the call's
+                       // bound build finds at least R_SURE_MIN_SHARE of the sites decided, 1 = never, 2 = wherever the bounds exist
+    double r_sure_x;   // TEST HOOK: > 1e-6 widens the range of x a decided site leaves to the full evaluation (0.25: half of all draws)
 };
 
 // kernels whose dynamic-LDS limit is raised with hipFuncSetAttribute: done once per (kernel, size) and remembered here
@@ -87,7 +90,8 @@ struct fcd_ctx {
     int pipe_occ_threads[3];       // ... and this many threads
     int64_t pipe_grid;             // last pipelined attempt of the r pass: its grid nD + nP + npad (fcd_ctx_stat "pipe_grid") ...
     int64_t pipe_capacity;         // ... and the workgroups resident at once for it, pipe_occ * num_cu ("pipe_capacity")
-    int r_form_last;               // form of the last blocked r pass: 1 step-per-launch, 2 pipelined, 3 one-launch with counters (fcd_ctx_stat)
+    int r_form_last;               // form of the last blocked r pass: 1 step-per-launch, 2 pipelined, 3 one-launch with counters,
+                                   // 4 sparse (knob r_sure) (fcd_ctx_stat)
     long long n_pack;              // packing launches of the r pass so far (fcd_ctx_stat "pack_launches")
     long long n_pack_tally;        // ... of them that carried the f half of the tally (fcd_ctx_stat "tally_f_in_pack")
     long long n_r_tally;           // pipelined r pass launches that carried it (fcd_ctx_stat "tally_f_in_r")
@@ -95,9 +99,13 @@ struct fcd_ctx {
     long long n_frec_build;        // launches of the kernel that builds them (fcd_ctx_stat "f_rec_builds")
     long long n_fsure_pass;        // f passes that ran the kernel with the decided-tile path (fcd_ctx_stat "f_sure_passes")
     long long n_frun_pass;         // ... of them in the run form, gibbs_f_run_kernel (fcd_ctx_stat "f_run_passes")
+    long long n_rsure_pass;        // r passes in the sparse form (fcd_ctx_stat "r_sure_passes")
+    long long n_rsure_build;       // launches of the kernel that builds its site bounds (fcd_ctx_stat "r_sure_builds")
     volatile unsigned *f_sure_hint;    // pinned host word: the records kernel of build number n_frec_build leaves four times that
                                        // number here, + 1 where some tile of its table has every edge decided (FCD_F_SURE_DRIFT
-                                       // nats in hand), + 2 where every tile has
+                                       // nats in hand), + 2 where every tile has.  The word behind it is the r pass's: the
+                                       // bound build of number n_rsure_build leaves four times that number, + 1 where at least
+                                       // R_SURE_MIN_SHARE of the sites are decided, + 2 where any is
     void *log_tab;     // K_lik tables (fcd_fastmath.h): 64 x 2^(-j/64), 512 x {1/m_i, log m_i} (device, 8.5 KiB)
     volatile unsigned *dev_err;   // pinned host word: error word of the one-launch r pass, copied back after each pass
     void *acc;         // 8 x uint64, zero between launches: the tally's pooled sums [0..3] and its ticket [4]
@@ -106,11 +114,14 @@ struct fcd_ctx {
     void *comm;        // ncclComm_t of the context (fcd_comm_init), or nullptr: fcd_gibbs_run pools its M-step counts over it
     int comm_world, comm_rank;
     void *pool_counts; // 8 x int64 (device): the counts vector the all-reduce works on in place
-    void *dbg;         // 8 x uint64 event counters (fcd_ctx_stat): [0] waves of the f pass that repeated an edge's sums in fp64,
+    void *dbg;         // 16 x uint64 event counters (fcd_ctx_stat): [0] waves of the f pass that repeated an edge's sums in fp64,
                        // [1] rows of the r pass's in-order role decided on the exact path, [2] workgroups of the pair-tile f pass
                        // that took the decided-tile path ("f_sure_tiles"), [3] decided ones its vote sent back
                        // ("f_sure_fallbacks"), never reset by the library; [4] the record build's two words "some tile is decided" (low half) and
-                       // "some tile is open" (high half), zero between calls; [5], [6] the call's lM and hyper (FCD_DBG_LM)
+                       // "some tile is open" (high half), zero between calls; [5], [6] the call's lM and hyper (FCD_DBG_LM);
+                       // [8] (site, chain word) items a sparse r pass left to its tables ("r_sure_sites"), [9] decided ones it
+                       // evaluated in full all the same ("r_sure_exceptions"); [10] sites the bound build found decided, zero
+                       // between calls; [11..15] the call's starting hyper (gibbs_f_hint_kernel: the bound build reads it there)
     void *corr_tickets;            // K_corr: one ticket per subject, zero between launches (the last taker resets it)
     size_t corr_tickets_n;
     void *fsq;         // square copy of the f state [w][n][m][lane] the sweep loop keeps between its f and r pass
@@ -747,6 +758,11 @@ struct fcd_sweep_plan {
     // workspace byte offsets: P[0] | P[1] | f_S | r_S | r_Sn | marks of the blocked r pass, then at a 512-byte boundary the
     // slot words r_U of a pair-form f pass (behind the r scratch: the sentinels in P survive from sweep to sweep) | ws_bytes
     size_t P[2], f_S, r_S, r_Sn, marks, r_U, ws_bytes;
+    // the sparse r pass's per-call tables and per-pass words, behind the slot words (rs_bytes == 0: none -- no record table):
+    // bounds hi | lo (Nreg, U) fp64, the rows of differences (U, Nreg, Nreg) fp64 with base(n,u) on the diagonal, mode words
+    // (Nreg, NBLK) uint2, row flags (Nreg) u32, then per pass the sites to visit (GW, Nreg) u64 over u and "the row's f words
+    // differ from the modes" (GW, Nreg) u32
+    size_t rs_bnd, rs_dtab, rs_mword, rs_rowflag, rs_visit, rs_fneq, rs_bytes;
 };
 fcd_sweep_plan fcd_sweep_plan_for(const fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t GW);
 // one call of a sweep entry point; fcd_sweep_call_check (fcd_gibbs.hip) checks it and fills in g and pl
@@ -777,9 +793,27 @@ struct fcd_sweep_step {
     bool r_flip;                   // r pass: the two r-word buffers of the plan have swapped roles (r_S lies at pl.r_Sn, r_Sn at pl.r_S)
     bool f_sure;                   // f pass (f_rec): some tile of the call's table has all its edges decided (fcd_ctx::f_sure_hint)
     bool f_all;                    // ... and every tile has: the decided path runs in its run form (gibbs_f_run_kernel)
+    bool r_sure;                   // r pass: the sparse form (the call's site bounds are built and the rule of the knob r_sure chose it)
 };
 int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step &st);   // fcd_gibbs.hip
 int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st);         // fcd_gibbs_r.hip
+// Decided sites of the r pass (fcd_gibbs_r.hip, gibbs_r_sparse_kernel).  With the edge modes k* of fcd_f_edge_mode at the call's
+// starting hyper and T - FCD_F_SURE_DRIFT, the log-odds of r_nu = 1 are  off + sum_{m != n} lMd[u][n][m][f_nm][r_m],
+// off = ln pi - ln(1 - pi).  Where every edge of row n has a mode and every f_nm equals it,
+//   lo(n,u) = sum_m min_t lMd[u][n][m][k*][t]  <=  sum  <=  hi(n,u) = sum_m max_t lMd[u][n][m][k*][t]
+// in every r state.  The site is decided 0 iff hi + off < -R_SURE_T, decided 1 iff lo + off > R_SURE_T: logit(x) >= -13.82
+// for x >= 1e-6, so  logit(x) < v  is false (true) for every x in [1e-6, 1 - 1e-6]; the 2.18 nats in hand cover the outward
+// rounding of the bounds, the fp64 error of the kernels' own sums and FCD_LOGIT_FAST_ERR.  The share of decided sites from
+// which the sparse form is chosen: see DESIGN.md, "Decided sites of the r pass".
+#define R_SURE_T 16.0
+#define R_SURE_X 1e-6
+// Measured at Nreg 200, U 50, 1024 chains with the tables scaled by beta (ms per sweep, pipelined form against sparse form, share
+// of the (site, word) items the passes left to the tables): beta 1: 0.289 / 0.151 (0.949); 0.5: 0.289 / 0.198 (0.931);
+// 0.35: 0.289 / 0.335 (0.769); 0.3: 0.289 / 0.427 (0.523); H = 20 controls, where one row in ten has an edge without a mode and
+// is walked in full: 0.314 / 0.461 (0.869).  The sparse form wins at 0.93 and loses at 0.87 and below.
+constexpr double R_SURE_MIN_SHARE = 0.9;
+// the bound build and its hint (queued by the sweep loop once the f hint says that some tile is decided)
+int fcd_gibbs_r_bounds_build(fcd_ctx *ctx, const fcd_sweep_call &c);
 
 // ---------------------------------------------------------------------------------------------
 // Ablation build (make ABLATE=1 -> libfcdiff_hip_abl.so, NEVER the product library): kernels read a level

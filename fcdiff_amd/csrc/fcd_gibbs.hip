@@ -1004,6 +1004,8 @@ __global__ void gibbs_f_hint_kernel(unsigned *__restrict__ any_tile, volatile un
     any_tile[1] = 0u;
     reinterpret_cast<unsigned long long *>(any_tile)[1] = (unsigned long long)(uintptr_t)lM;
     reinterpret_cast<unsigned long long *>(any_tile)[2] = (unsigned long long)(uintptr_t)hyper;
+    // ... and the starting hyper itself for the r pass's bound build, which runs after the first M-step (dbg[11..15]; any_tile = dbg + 4)
+    for (int i = 0; i < 5; ++i) reinterpret_cast<double *>(any_tile)[7 + i] = hyper[i];
     __hip_atomic_store(const_cast<unsigned *>(hint), 4u * build + 2u * all + any, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -2104,6 +2106,24 @@ static int fcd_f_sure_hint_wait(fcd_ctx *ctx, hipStream_t s, bool &any, bool &al
     all = (v & 2u) != 0u;
     return FCD_OK;
 }
+// the same for the r pass's bound build (the word behind: 4 build + 2 any + share): the build runs behind the call's first
+// sweep, so this wait lasts until the device has finished that sweep -- once per call, with the second sweep already queued
+static int fcd_r_sure_hint_wait(fcd_ctx *ctx, hipStream_t s, bool &share, bool &any) {
+    const unsigned build = (unsigned)(ctx->n_rsure_build & 0x3fffffff);
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned v = ctx->f_sure_hint[1];
+    for (unsigned spin = 1; (v >> 2) != build; ++spin, v = ctx->f_sure_hint[1]) {
+        if ((spin & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
+            FCD_HIP_TRY(hipStreamSynchronize(s));
+            v = ctx->f_sure_hint[1];
+            if ((v >> 2) != build) return fcd_fail(ctx, FCD_ERR_DEVICE, "r pass: the bound build left no hint");
+            break;
+        }
+    }
+    share = (v & 1u) != 0u;
+    any = (v & 2u) != 0u;
+    return FCD_OK;
+}
 
 static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int64_t n_sweeps, int64_t mstep_every,
                       int64_t accumulate_from, int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r, double *hyper_m,
@@ -2159,15 +2179,38 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         FCD_LAUNCH_CHECK();
         rec_built = true;
     }
+    // The sparse r pass (fcd_gibbs_r.hip, "Decided sites of the r pass") reads bounds made once per call from the same record
+    // table: where the f hint says that some tile is decided (weak tables: nothing is launched), the build is queued with the
+    // sweep that learns it, its own hint -- what share of the sites is decided -- is read one sweep later, and the passes
+    // from then on run the sparse form where the rule of knob r_sure chooses it.  A forced exact path (r_tol) and the knobs
+    // that pick a form of the blocked pass keep the old forms.
+    const fcd_knobs &kn = ctx->knobs;
+    const bool rs_ok = pl.rs_bytes && kn.r_sure != 1 && !(kn.r_tol > 16.0 * FCD_LOGIT_FAST_ERR) && !kn.r_path && !kn.r_coop &&
+                       !kn.r_dsplit;
+    int rs_state = 0;              // 0: no build yet, 1: build queued, 2: the sparse form runs, -1: it does not
     for (int64_t i = 0; i < n_sweeps; ++i) {
         st.sweep = sweep0 + i;
         st.f_packed = packed_ok && st.r_packed;
         st.fsq = st.f_packed ? nullptr : fsq;
+        if (rs_state == 1 && st.f_packed) {
+            bool share = false, any = false;
+            int rc = fcd_r_sure_hint_wait(ctx, s, share, any);
+            if (rc) return rc;
+            rs_state = (kn.r_sure == 2 || share) ? 2 : -1;
+        }
         if (rec_built && st.f_packed && !st.f_rec) {
             int rc = fcd_f_sure_hint_wait(ctx, s, st.f_sure, st.f_all);
             if (rc) return rc;
             st.f_rec = ctx->frec;
+            if (rs_ok && (st.f_sure || kn.r_sure == 2)) {
+                rc = fcd_gibbs_r_bounds_build(ctx, c);
+                if (rc) return rc;
+                rs_state = 1;
+            } else {
+                rs_state = -1;
+            }
         }
+        st.r_sure = rs_state == 2 && st.f_packed && st.r_packed;
         int rc = fcd_gibbs_f_pass(ctx, c, st);
         if (rc) return rc;
         const bool last = i + 1 == n_sweeps;

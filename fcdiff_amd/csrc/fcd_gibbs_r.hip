@@ -18,6 +18,8 @@
 // ceil(Nreg / 16) + 1 launches per pass; the serial part rides beside the parallel part of the next block.
 // gibbs_r_pipe_kernel is the same pass in ONE launch (every workgroup resident, hand-over through marks and sentinels in
 // device memory): the default wherever its grid fits the device at once.
+// On a call's record table whose bounds decide most sites, the SPARSE form (gibbs_r_range_kernel + gibbs_r_sparse_kernel, below)
+// skips the sums of the decided sites altogether and walks the few others in order.
 //
 // lMd (U, Nreg, Nreg, 3, 2) is a region-major DIFFERENCE table made once per table build:
 //   lMd[u][n][m][k][t] = t ? lM[c,u,k,1] - lM[c,u,k,2] : lM[c,u,k,2] - lM[c,u,k,0],   c = edge(n, m)
@@ -1396,6 +1398,374 @@ __global__ __launch_bounds__(64 * R_WAVES) void gibbs_r_simple(const double *__r
     for (int n = tid; n < Nreg; n += 64 * R_WAVES) rcol[(int64_t)n * U] = mask[n];
 }
 
+// ---------------------------------------------------------------------------------------------
+// SPARSE form: the sums of sites the tables decide are skipped (the rule: fcd_common.h, R_SURE_T; DESIGN.md, "Decided
+// sites of the r pass").  Per call gibbs_r_bounds_kernel makes, for every site (n, u), the bounds lo / hi of its sum over
+// every r state with the f row at its modes, the row of differences lMd[k*][1] - lMd[k*][0] with the sum base(n,u) -- every
+// other region healthy -- on its diagonal, and for every row its mode words (the f words of f_S with every edge at its mode)
+// and a flag "some edge of the row has no mode" (such a row has no decided site).  Per pass:
+//   gibbs_r_range_kernel   wave = (chain word, region n): is the row's f word the mode word in every chain?  Then for every
+//                          patient pair the Philox block the oracle draws and the rule with THIS sweep's pi: a decided site
+//                          whose x lies in [x_lo, 1 - x_lo] in every chain gets its r word at once; every other site -- open,
+//                          or an exception: x out of range in some chain, or the f row off its modes -- is left in the row's
+//                          64-bit "visit" word over the patients.  Independent of r, parallel over the sites.
+//   gibbs_r_sparse_kernel  wave = (patient, chain word): walks the sites to visit in increasing n with the r words of the
+//                          whole column in LDS (decided ones already final, visited ones old until redrawn).  Where the row is
+//                          at its modes   v = off + base + sum_{m: r_m = 1 in some chain} [r_m] (lMd[k*][1] - lMd[k*][0]):
+//                          the row of differences is one coalesced load, asked for a site ahead; the regions with a set bit
+//                          are added under each chain's bit from lane-broadcast operands.
+//                          Otherwise the row's terms are gathered per chain from lMd with the chain's own f.  Same draw as
+//                          the blocked forms (fast logit, exact one within a.tol).  It leaves r_bits and the pair bytes r_Sn.
+// Rounding: base is a tree sum of Nreg - 1 terms and the walk adds at most Nreg differences to it, so v differs from the
+// blocked forms' sum (another tree over the same terms) by at most (Nreg + 20) 2^-53 sum|terms| -- 2.6e-14 x sum|terms|
+// at Nreg 200, nine orders below a.tol = 3.2e-4 for sums of thousands of nats; DESIGN.md (c): no draw of the parity
+// runs comes closer to a tie than 1000 x what re-ordering can move.
+// ---------------------------------------------------------------------------------------------
+struct r_sparse_args {
+    const double *lMd, *hyper;
+    const uint2 *f_S;
+    uint2 *r_Sn;
+    uint64_t *r_bits;
+    const double *bnd;              // hi | lo, (Nreg, U) each
+    const double *dtab;             // (U, Nreg, Nreg): lMd[u][n][m][k*][1] - lMd[u][n][m][k*][0]; [u][n][n] = base(n,u), NaN where
+                                    // the row has an edge without a mode or an entry that is not finite
+    const uint2 *mword;             // (Nreg, NBLK)
+    const uint32_t *rowflag;        // (Nreg)
+    uint64_t *visit;                // (GW, Nreg)
+    uint32_t *fneq;                 // (GW, Nreg): row flag, or the f words differ from the mode words in some chain
+    unsigned long long *cnt;        // [0] items left to the tables, [1] decided items evaluated in full
+    int Nreg, U, NBLK, GW;
+    int64_t G;
+    uint32_t chain0, sweep;
+    uint64_t seed;
+    double tol, x_lo;
+};
+
+constexpr int RS_WAVES = 4;
+
+__global__ __launch_bounds__(256) void gibbs_r_bounds_kernel(const double *__restrict__ lMd, const fcd_f_edge_rec *__restrict__ erec,
+                                                             const double *__restrict__ hyper0, int Nreg, int U, int NBLK,
+                                                             double *__restrict__ bnd, double *__restrict__ dtab,
+                                                             uint2 *__restrict__ mword, uint32_t *__restrict__ rowflag,
+                                                             unsigned long long *__restrict__ n_decided) {
+    extern __shared__ uint8_t km[];              // [16 NBLK]: mode of (n, m), 0 where there is no such edge, 3 = no mode
+    __shared__ int open_row;
+    const int n = (int)blockIdx.x, NPAIR = (U + 1) >> 1;
+    if (threadIdx.x == 0) open_row = 0;
+    __syncthreads();
+    const double g1 = hyper0[FCD_H_LNGAMMA + 1] - hyper0[FCD_H_LNGAMMA + 0], g2 = hyper0[FCD_H_LNGAMMA + 2] - hyper0[FCD_H_LNGAMMA + 0];
+    for (int m = threadIdx.x; m < NBLK * R_NB; m += blockDim.x) {
+        int k = 0;
+        if (m < Nreg && m != n) {
+            const fcd_f_edge_rec rec = erec[fcd_pair_to_edge(n, m, FCD_EDGE_SYMMETRIC)];
+            const double c1 = g1 + rec.d1, c2 = g2 + rec.d2;
+            k = fcd_f_edge_mode(c1, c2, rec.b, fcd_f_edge_delta(c1, c2, NPAIR, rec.a), FCD_F_SURE_T - FCD_F_SURE_DRIFT);
+            if (k < 0) {
+                k = 3;
+                open_row = 1;
+            }
+        }
+        km[m] = (uint8_t)k;
+    }
+    __syncthreads();
+    const bool open = open_row != 0;
+    if (threadIdx.x == 0) rowflag[n] = open ? 1u : 0u;
+    for (int b = threadIdx.x; b < NBLK; b += blockDim.x) {
+        uint32_t v[2] = {0u, 0u};
+        for (int p = 0; p < R_NB / 2; ++p) {
+            const uint32_t k0 = km[b * R_NB + 2 * p] & 3u, k1 = km[b * R_NB + 2 * p + 1] & 3u;
+            v[p >> 2] |= (((k0 == 3u ? 0u : k0) * 3u + (k1 == 3u ? 0u : k1)) << 2) << (8 * (p & 3));
+        }
+        mword[n * NBLK + b] = make_uint2(v[0], v[1]);
+    }
+    const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6);
+    const double off = hyper0[FCD_H_LNPI1] - hyper0[FCD_H_LNPI0];
+    unsigned long long dec = 0;
+    for (int u = wave; u < U; u += (int)(blockDim.x >> 6)) {
+        const double *__restrict__ row = lMd + ((int64_t)u * Nreg + n) * Nreg * 6;
+        double *__restrict__ drow = dtab + ((int64_t)u * Nreg + n) * Nreg;
+        double hi = 0.0, lo = 0.0, base = 0.0, mag = 0.0;
+        bool bad = false;
+        for (int m = lane; m < Nreg; m += 64) {
+            if (m == n) continue;
+            const int k = km[m];
+            const double *p = row + m * 6;
+            double mx, mn;
+            if (k < 3) {
+                const double t0 = p[2 * k], t1 = p[2 * k + 1];
+                bad = bad || !isfinite(t0) || !isfinite(t1);
+                mx = fmax(t0, t1);
+                mn = fmin(t0, t1);
+                base += t0;
+                drow[m] = t1 - t0;
+            } else {
+                drow[m] = 0.0;
+                mx = mn = p[0];
+                bad = bad || !isfinite(p[0]);
+                for (int x = 1; x < 6; ++x) {
+                    bad = bad || !isfinite(p[x]);
+                    mx = fmax(mx, p[x]);
+                    mn = fmin(mn, p[x]);
+                }
+            }
+            hi += mx;
+            lo += mn;
+            mag += fmax(fabs(mx), fabs(mn));
+        }
+        hi = fcd_wave_sum(hi);
+        lo = fcd_wave_sum(lo);
+        base = fcd_wave_sum(base);
+        mag = fcd_wave_sum(mag);
+        bad = __ballot(bad) != 0ull;
+        if (lane == 0) {
+            // outward: a sum of Nreg terms in any order is off by at most Nreg 2^-53 sum|terms|
+            const double slack = (double)(Nreg + 8) * 1.2e-16 * mag;
+            const double nan = __builtin_nan("");
+            const int64_t NU = (int64_t)Nreg * U, i = (int64_t)n * U + u;
+            const double h = bad ? nan : hi + slack, l = bad ? nan : lo - slack;
+            bnd[i] = h;
+            bnd[NU + i] = l;
+            drow[n] = (bad || open) ? nan : base;
+            if (!open && (h + off < -R_SURE_T || l + off > R_SURE_T)) dec += 1;
+        }
+    }
+    if (lane == 0 && dec) atomicAdd(n_decided, dec);
+}
+
+// 4 build + 2 "some site is decided" + "at least `share` of the sites are" into the pinned word the sweep loop polls
+__global__ void gibbs_r_hint_kernel(unsigned long long *__restrict__ n_decided, volatile unsigned *hint, unsigned build,
+                                    double total, double share) {
+    const unsigned long long d = *n_decided;
+    *n_decided = 0ull;
+    __hip_atomic_store(const_cast<unsigned *>(hint), 4u * build + (d > 0ull ? 2u : 0u) + ((double)d >= share * total ? 1u : 0u),
+                       __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// grid (ceil(Nreg / RS_WAVES), GW): wave = (w, n)
+__global__ __launch_bounds__(64 * RS_WAVES) void gibbs_r_range_kernel(const r_sparse_args a) {
+    __shared__ unsigned red[2];
+    if (threadIdx.x < 2) red[threadIdx.x] = 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int n = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * RS_WAVES + (threadIdx.x >> 6)));
+    const int w = (int)blockIdx.y;
+    const int Nreg = a.Nreg, U = a.U, NBLK = a.NBLK, NPAIR = (U + 1) >> 1;
+    if (n < Nreg) {
+        const uint64_t act = fcd_active_mask(w, a.G);
+        const bool rf = a.rowflag[n] != 0u;
+        bool neq = false;
+        if (!rf) {
+            const uint2 *__restrict__ fw = a.f_S + ((int64_t)w * Nreg + n) * NBLK * 64 + lane;
+            const uint2 *__restrict__ mw = a.mword + n * NBLK;
+            for (int b = 0; b < NBLK; ++b) {
+                const uint2 f = fw[b * 64], m = mw[b];
+                neq = neq || f.x != m.x || f.y != m.y;
+            }
+        }
+        const bool off_modes = rf || (__ballot(neq) & act) != 0ull;
+        const double off = a.hyper[FCD_H_LNPI1] - a.hyper[FCD_H_LNPI0];
+        const double x_lo = a.x_lo, x_hi = 1.0 - a.x_lo;
+        const uint32_t chain = a.chain0 + (uint32_t)w * 64u + (uint32_t)lane;
+        const int64_t NU = (int64_t)Nreg * U;
+        // the rule for the row's patients, lane = patient: one pair of loads instead of two scalar loads per site
+        uint64_t dec0, dec1;
+        {
+            const int ul = lane < U ? lane : U - 1;
+            const double hi = a.bnd[(int64_t)n * U + ul], lo = a.bnd[NU + (int64_t)n * U + ul];
+            const bool d0 = hi + off < -R_SURE_T, d1 = !d0 && lo + off > R_SURE_T;          // (NaN bounds: neither)
+            dec0 = __ballot(!rf && lane < U && d0);
+            dec1 = __ballot(!rf && lane < U && d1);
+        }
+        const uint64_t all_u = U >= 64 ? ~0ull : ((1ull << U) - 1ull);
+        uint64_t visit = all_u & ~(dec0 | dec1), ones = 0ull;
+        unsigned n_sure = 0u, n_exc = 0u;
+        if (off_modes) {
+            // every decided site of the row is an exception: no uniform to look at
+            n_exc = (unsigned)__builtin_popcountll(dec0 | dec1);
+            visit = all_u;
+        } else {
+            for (int j = 0; j < NPAIR; ++j) {
+                if ((((dec0 | dec1) >> (2 * j)) & 3ull) == 0ull) continue;      // (both sites open: the walk draws the block)
+                const fcd_u4 x = fcd_philox((uint32_t)(n * NPAIR + j), chain, a.sweep, FCD_KIND_R, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int u = 2 * j + h;
+                    const bool d0 = (dec0 >> u) & 1ull, d1 = (dec1 >> u) & 1ull;
+                    if (u >= U || !(d0 || d1)) continue;
+                    const double xx = h ? fcd_u53(x.z, x.w) : fcd_u53(x.x, x.y);
+                    const bool out = d0 ? !(xx >= x_lo) : !(xx <= x_hi);
+                    if ((__ballot(out) & act) != 0ull) {
+                        n_exc += 1u;
+                        visit |= 1ull << u;
+                    } else {
+                        n_sure += 1u;
+                        if (d1) ones |= 1ull << u;
+                    }
+                }
+            }
+        }
+        if (lane == 0) {
+            a.visit[(int64_t)w * Nreg + n] = visit;
+            a.fneq[(int64_t)w * Nreg + n] = off_modes ? 1u : 0u;
+            if (n_sure) atomicAdd(&red[0], n_sure);
+            if (n_exc) atomicAdd(&red[1], n_exc);
+        }
+        if (lane < U && !((visit >> lane) & 1ull)) a.r_bits[((int64_t)w * Nreg + n) * U + lane] = ((ones >> lane) & 1ull) ? act : 0ull;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && red[threadIdx.x]) atomicAdd(&a.cnt[threadIdx.x], (unsigned long long)red[threadIdx.x]);
+}
+
+__device__ __forceinline__ void rs_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// grid (U, ceil(GW / RS_WAVES)): wave = (u, w); dynamic LDS per wave: (16 NBLK) uint64, the r words of the wave's column, then
+// RS_MAXCH words: the sites to visit, 64 regions a word.
+// The walk is one serial chain per wave -- what a site costs on that chain is what the pass costs -- so everything of the NEXT
+// site is asked for before this site's sum runs: its Philox block, its row of differences (with base on the diagonal) and its
+// flag, all through vector loads that depend on nothing the walk computes (a scalar load would be waited for with everything
+// else the wave has asked the scalar cache and the LDS for).
+constexpr int RS_CH = 4;        // chunks of 64 regions whose entries are prefetched (regions beyond: gathered at the site itself)
+constexpr int RS_MAXCH = 16;    // 64-region chunks of the largest Nreg the blocked forms take (832)
+struct rs_site {
+    double xx, th;
+    uint32_t off_modes;
+    double dl[RS_CH];
+};
+__global__ __launch_bounds__(64 * RS_WAVES) void gibbs_r_sparse_kernel(const r_sparse_args a) {
+    extern __shared__ uint64_t rs_lds[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int u = (int)blockIdx.x, w = (int)blockIdx.y * RS_WAVES + wave;
+    const int Nreg = a.Nreg, U = a.U, NBLK = a.NBLK, NP = NBLK * R_NB, NPAIR = (U + 1) >> 1;
+    if (w >= a.GW) return;                       // (no workgroup barrier below)
+    uint64_t *rm = rs_lds + (size_t)wave * (NP + RS_MAXCH);
+    uint64_t *vm = rm + NP;
+    uint64_t *__restrict__ rcol = a.r_bits + (int64_t)w * Nreg * U + u;
+    const int nchunk = (Nreg + 63) >> 6;
+    for (int m = lane; m < NP; m += 64) rm[m] = m < Nreg ? rcol[(int64_t)m * U] : 0ull;
+    for (int c = 0; c < nchunk; ++c) {
+        const int nl = c * 64 + lane;
+        const uint64_t todo = __ballot(nl < Nreg && ((a.visit[(int64_t)w * Nreg + (nl < Nreg ? nl : 0)] >> u) & 1ull));
+        if (lane == 0) vm[c] = todo;
+    }
+    rs_wave_sync();
+    const double off = a.hyper[FCD_H_LNPI1] - a.hyper[FCD_H_LNPI0];
+    const uint32_t chain = a.chain0 + (uint32_t)w * 64u + (uint32_t)lane;
+    // the site after n in the wave's list (n = -1: the first), or -1
+    auto next_site = [&](int n) -> int {
+        int c = n < 0 ? 0 : n >> 6;
+        uint64_t t = c < nchunk ? vm[c] : 0ull;
+        if (n >= 0) t &= (n & 63) == 63 ? 0ull : ~0ull << ((n & 63) + 1);
+        while (t == 0ull && ++c < nchunk) t = vm[c];
+        return __builtin_amdgcn_readfirstlane(t ? c * 64 + (int)__builtin_ctzll(t) : -1);
+    };
+    uint32_t zlane = 0u;                         // (a zero the compiler cannot see through: wave-uniform addresses in vector loads)
+    asm volatile("" : "+v"(zlane));
+    auto fetch = [&](int n) -> rs_site {
+        rs_site S;
+        const fcd_u4 x = fcd_philox((uint32_t)(n * NPAIR + (u >> 1)), chain, a.sweep, FCD_KIND_R, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+        S.xx = (u & 1) ? fcd_u53(x.z, x.w) : fcd_u53(x.x, x.y);
+        S.th = fcd_logit_fast(S.xx);
+        S.off_modes = (a.fneq + (int64_t)w * Nreg + n)[zlane];
+        const double *__restrict__ drow = a.dtab + ((int64_t)u * Nreg + n) * Nreg;
+#pragma unroll
+        for (int q = 0; q < RS_CH; ++q) {
+            const int m = q * 64 + lane;
+            S.dl[q] = drow[m < Nreg ? m : Nreg - 1];
+        }
+        return S;
+    };
+    // v += the entries dl of the regions whose word has a set bit, each under this chain's bit
+    auto add_terms = [&](double &v, uint64_t word, double dl) {
+        uint64_t bm = __ballot(word != 0ull);
+        while (bm) {
+            const int j = (int)__builtin_ctzll(bm);
+            bm &= bm - 1ull;
+            const uint64_t wj = fcd_lane_word(word, j);
+            const double dj = __longlong_as_double((long long)fcd_lane_word((uint64_t)__double_as_longlong(dl), j));
+            v += ((wj >> lane) & 1ull) ? dj : 0.0;
+        }
+    };
+    int n = next_site(-1);
+    rs_site S = {};
+    if (n >= 0) S = fetch(n);
+    while (n >= 0) {
+        const int n2 = next_site(n);
+        rs_site S2 = {};
+        if (n2 >= 0) S2 = fetch(n2);
+        const double *__restrict__ row = a.lMd + ((int64_t)u * Nreg + n) * Nreg * 6;
+        const double *__restrict__ drow = a.dtab + ((int64_t)u * Nreg + n) * Nreg;
+        // base(n,u): the diagonal entry of the row
+        double base = 0.0;
+        if ((n >> 6) < RS_CH) {
+#pragma unroll
+            for (int q = 0; q < RS_CH; ++q)
+                if (q == (n >> 6)) base = __longlong_as_double((long long)fcd_lane_word((uint64_t)__double_as_longlong(S.dl[q]), n & 63));
+        } else {
+            base = (drow + n)[zlane];
+        }
+        double v = off;
+        if (!(S.off_modes != 0u || base != base)) {
+            v += base;
+#pragma unroll
+            for (int q = 0; q < RS_CH; ++q) {
+                const int m = q * 64 + lane;
+                add_terms(v, (m < Nreg && m != n) ? rm[m] : 0ull, S.dl[q]);
+            }
+            // (regions beyond the prefetched chunks: loaded here)
+            for (int c0 = RS_CH; c0 < nchunk; ++c0) {
+                const int m = c0 * 64 + lane;
+                const uint64_t word = (m < Nreg && m != n) ? rm[m] : 0ull;
+                add_terms(v, word, word ? drow[m] : 0.0);
+            }
+        } else {
+            // the row's terms per chain, with the chain's own f (pair bytes of f_S: q = 3 f(n,m) + f(n,m+1), shifted by 2)
+            const uint2 *__restrict__ fw = a.f_S + ((int64_t)w * Nreg + n) * NBLK * 64 + lane;
+            for (int b = 0; b < NBLK; ++b) {
+                const uint2 f = fw[b * 64];
+                double t[R_NB];
+#pragma unroll
+                for (int j = 0; j < R_NB; ++j) {
+                    const int m = b * R_NB + j, p = j >> 1;
+                    const uint32_t q = (((p < 4 ? f.x : f.y) >> (8 * (p & 3))) & 0xffu) >> 2;
+                    const uint32_t k = (j & 1) ? q % 3u : q / 3u;
+                    const bool on = m < Nreg && m != n;
+                    const uint32_t bit = (uint32_t)((rm[m] >> lane) & 1ull);
+                    const double val = row[(on ? m : 0) * 6 + (on ? 2 * k + bit : 0u)];
+                    t[j] = on ? val : 0.0;
+                }
+#pragma unroll
+                for (int j = 0; j < R_NB; ++j) v += t[j];
+            }
+        }
+        v -= S.th;
+        if (__ballot(fabs(v) < a.tol) != 0ull) {
+            // too close to call with the fast threshold: the exact one in its place
+            if (S.xx > 0.0) v += S.th - fcd_logit(S.xx);          // (x = 0: both thresholds are -inf, v = +inf already)
+        }
+        const uint64_t ball = __ballot(v > 0.0);
+        if (lane == 0) {
+            rm[n] = ball;
+            rcol[(int64_t)n * U] = ball;
+        }
+        rs_wave_sync();
+        n = n2;
+        S = S2;
+    }
+    // the pair bytes of every block for the next pass
+    uint2 *__restrict__ dst = a.r_Sn + ((int64_t)w * U + u) * NBLK * 64 + lane;
+    for (int b = 0; b < NBLK; ++b) {
+        uint32_t v16 = 0u;
+#pragma unroll
+        for (int j = 0; j < R_NB; ++j) v16 |= (uint32_t)((rm[b * R_NB + j] >> lane) & 1ull) << j;
+        dst[b * 64] = spread2(v16);
+    }
+}
+
 template <int UB, int WPE>
 int launch_step(fcd_ctx *ctx, const r_step_args &a, size_t shmem, hipStream_t s, bool prof) {
     // (what only the pipelined form may carry: a fall-back from it must have taken both back)
@@ -1556,6 +1926,19 @@ fcd_sweep_plan fcd_sweep_plan_for(const fcd_ctx *ctx, int64_t Nreg, int64_t U, i
     p.r_U = (r_end + 511) / 512 * 512;
     // slot words of the pair forms: 16 patients per word, up to four words side by side per lane, else [word][lane] (ru_index)
     p.ws_bytes = p.r_U + (pair_form ? (size_t)GW * Nreg * (p.f_NW <= 4 ? 4 : p.f_NW) * 64 * sizeof(uint32_t) : 0);
+    // ---- the sparse r pass: where the call's record table exists (its edge constants give the modes) and U <= 64 (one
+    // 64-bit word over the patients per row)
+    if (p.frec_bytes && U <= 64) {
+        auto up = [](size_t x) { return (x + 511) / 512 * 512; };
+        p.rs_bnd = up(p.ws_bytes);
+        p.rs_dtab = up(p.rs_bnd + (size_t)2 * Nreg * U * sizeof(double));
+        p.rs_mword = up(p.rs_dtab + (size_t)U * Nreg * Nreg * sizeof(double));
+        p.rs_rowflag = up(p.rs_mword + (size_t)Nreg * NBLK * sizeof(uint2));
+        p.rs_visit = up(p.rs_rowflag + (size_t)Nreg * sizeof(uint32_t));
+        p.rs_fneq = up(p.rs_visit + (size_t)GW * Nreg * sizeof(uint64_t));
+        p.ws_bytes = up(p.rs_fneq + (size_t)GW * Nreg * sizeof(uint32_t));
+        p.rs_bytes = p.ws_bytes - p.rs_bnd;
+    }
     return p;
 }
 
@@ -1585,6 +1968,29 @@ extern "C" int fcd_gibbs_r_step(fcd_ctx *ctx, const double *lM, const double *lM
     fcd_sweep_step st = {sweep};
     int rc = fcd_sweep_call_check(ctx, c, false, true, "fcd_gibbs_r_step");
     return rc ? rc : fcd_gibbs_r_pass(ctx, c, st);
+}
+
+// The sparse form's per-call tables from the call's record table (its edge constants) and lMd: queued by the sweep loop
+// behind the call's first sweep, with the hint that tells the host what share of the sites is decided.
+int fcd_gibbs_r_bounds_build(fcd_ctx *ctx, const fcd_sweep_call &c) {
+    const fcd_sweep_plan &pl = c.pl;
+    if (!pl.rs_bytes || !ctx->frec || !c.lMd || !ctx->f_sure_hint)
+        return fcd_fail(ctx, FCD_ERR_ARG, "r pass: bound build without the call's record table");
+    int rc = fcd_ws_reserve(ctx, pl.ws_bytes);
+    if (rc) return rc;
+    char *ws = (char *)ctx->ws;
+    const int Nreg = (int)c.Nreg, U = (int)c.U, NBLK = (Nreg + R_NB - 1) / R_NB;
+    unsigned long long *dbg = (unsigned long long *)ctx->dbg;
+    ctx->n_rsure_build += 1;
+    hipLaunchKernelGGL(gibbs_r_bounds_kernel, dim3((unsigned)Nreg), dim3(256), (size_t)NBLK * R_NB, c.s, c.lMd,
+                       (const fcd_f_edge_rec *)((const char *)ctx->frec + pl.frec_edge), (const double *)(dbg + 11), Nreg, U, NBLK,
+                       (double *)(ws + pl.rs_bnd), (double *)(ws + pl.rs_dtab), (uint2 *)(ws + pl.rs_mword),
+                       (uint32_t *)(ws + pl.rs_rowflag), dbg + 10);
+    FCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(gibbs_r_hint_kernel, dim3(1), dim3(1), 0, c.s, dbg + 10, ctx->f_sure_hint + 1,
+                       (unsigned)(ctx->n_rsure_build & 0x3fffffff), (double)c.Nreg * (double)c.U, R_SURE_MIN_SHARE);
+    FCD_LAUNCH_CHECK();
+    return FCD_OK;
 }
 
 int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) {
@@ -1635,6 +2041,31 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
     a.withhold = ctx->knobs.r_withhold;
     a.tf.f_state = nullptr; a.tf.C = 0; a.tf.G = 0; a.tf.GW = 0; a.tf.acc = nullptr; a.tf.cnt_f = nullptr;
     if (ctx->knobs.r_tol > a.tol) a.tol = ctx->knobs.r_tol;   // test hook: a huge value sends every draw through the exact path
+    if (st.r_sure) {
+        // the sparse form: the f and r words are in their final form (the sweep loop asks for it only then), the marks stay
+        // cleared, the panel buffers are not touched; the tally after the pass counts f
+        if (!pl.rs_bytes || !st.f_packed || !st.r_packed) return fcd_fail(ctx, FCD_ERR_ARG, "r pass: sparse form without its tables");
+        r_sparse_args q;
+        q.lMd = c.lMd; q.hyper = c.hyper; q.f_S = f_S; q.r_Sn = a.r_Sn; q.r_bits = c.r_bits;
+        q.bnd = (const double *)(ws + pl.rs_bnd); q.dtab = (const double *)(ws + pl.rs_dtab);
+        q.mword = (const uint2 *)(ws + pl.rs_mword); q.rowflag = (const uint32_t *)(ws + pl.rs_rowflag);
+        q.visit = (uint64_t *)(ws + pl.rs_visit); q.fneq = (uint32_t *)(ws + pl.rs_fneq);
+        q.cnt = (unsigned long long *)ctx->dbg + 8;
+        q.Nreg = (int)Nreg; q.U = (int)U; q.NBLK = NBLK; q.GW = g.GW; q.G = c.G;
+        q.chain0 = a.chain0; q.sweep = a.sweep; q.seed = a.seed;
+        q.tol = a.tol;
+        q.x_lo = ctx->knobs.r_sure_x > R_SURE_X ? ctx->knobs.r_sure_x : R_SURE_X;
+        // (both launches inside the r step's profiling pair: fcd_prof_collect keeps one name for the r pass)
+        fcd_prof_begin(ctx, FCD_PROF_RSTEP, s);
+        hipLaunchKernelGGL(gibbs_r_range_kernel, dim3((unsigned)((Nreg + RS_WAVES - 1) / RS_WAVES), (unsigned)g.GW), dim3(64 * RS_WAVES), 0, s, q);
+        hipLaunchKernelGGL(gibbs_r_sparse_kernel, dim3((unsigned)U, (unsigned)((g.GW + RS_WAVES - 1) / RS_WAVES)), dim3(64 * RS_WAVES),
+                           (size_t)RS_WAVES * (NBLK * R_NB + RS_MAXCH) * sizeof(uint64_t), s, q);
+        fcd_prof_end(ctx, FCD_PROF_RSTEP, s);
+        FCD_LAUNCH_CHECK();
+        ctx->r_form_last = 4;
+        ctx->n_rsure_pass += 1;
+        return FCD_OK;
+    }
     const int nUC = (int)((U + ub - 1) / ub);
     // Pipelined one-launch form (the default where it fits; knob r_path = 3 keeps the step-per-launch form): needs every
     // workgroup resident at once (with a few slots to spare) and the pinned error word.

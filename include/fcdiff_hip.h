@@ -135,6 +135,14 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
  *               goes back as a whole); elsewhere the per-tile kernel; 1 = never the run form; 2 = the run form wherever the
  *               path is taken at all (tests: edges the rule leaves open are then drawn inside the run kernel).  Not read
  *               from the environment
+ *   "r_sure"    the sparse form of the r pass on a call's record table (knob f_records' gate): a site whose draw the tables
+ *               decide -- with every edge of its row at its mode the log-odds of r = 1 stay below -16 (above 16) in every r
+ *               state -- gets its r word from a range test of its uniform, the other sites are walked in order with sums of a
+ *               few terms.  0 = in calls whose bound build finds at least nine tenths of the sites decided (and only with "r_tol" at
+ *               its default and "r_path", "r_coop", "r_dsplit" unset), 1 = never, 2 = wherever the bounds exist (tests).  Not
+ *               read from the environment
+ *   "r_sure_x"  TEST HOOK: > 1e-6 widens the range of uniforms that sends a decided site to the full evaluation (0.25: half
+ *               of all draws)
  *   "tally_in_r" the f half of a sweep's tally (pooled counts of f, cnt_f) inside the pipelined r pass, counted by its in-order
  *               workgroups before their first block, while they wait for the first panel values: 0 = where those workgroups
  *               have 16 waves and a wave walks at most "tally_in_r_max_rounds" rounds of four edges (cfg3: 4 rounds), 1 = never
@@ -160,7 +168,12 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value);
  * knob f_records = 0; "f_sure_passes" = f passes that ran a kernel with the decided-tile path, "f_run_passes" = those of them in
  * the run form (knob f_runs), "f_sure_tiles" = (pair-aligned tile x 16 chain words) items that took it, "f_sure_fallbacks" = decided
  * ones in which a uniform outside the range sent the tile (run form: only that wave's edge) back to
- * the sums (the last two and "f_repeats", "r_exact_rows" are device counters: reading them synchronises); "dev_err" = the error word of the pipelined r pass as the host sees it now (see
+ * the sums (the last two and "f_repeats", "r_exact_rows" are device counters: reading them synchronises);
+ * "r_form_last" = 4: the sparse form (knob r_sure); "r_sure_passes" = r passes in that form, "r_sure_builds" = launches of the
+ * kernel that makes its bounds (once per call, and only where the f pass's hint says that some tile is decided),
+ * "r_sure_sites" = (site, 64-chain word) items such passes left to the tables, "r_sure_exceptions" = decided items they
+ * evaluated in full all the same -- a uniform out of range in some chain, or the row's f off its modes (device counters);
+ * "dev_err" = the error word of the pipelined r pass as the host sees it now (see
  * fcd_ctx_check); "pipe_grid" / "pipe_capacity" = the grid of the last pipelined attempt of the r pass (its empty
  * workgroups included) and the workgroups the occupancy query says are resident at once for it (the form is taken where
  * pipe_grid + 8 <= pipe_capacity). */
