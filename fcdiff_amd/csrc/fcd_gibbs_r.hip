@@ -1411,15 +1411,16 @@ __global__ __launch_bounds__(64 * R_WAVES) void gibbs_r_simple(const double *__r
 //                          64-bit "visit" word over the patients.  Independent of r, parallel over the sites.
 //   gibbs_r_sparse_kernel  wave = (patient, chain word): walks the sites to visit in increasing n with the r words of the
 //                          whole column in LDS (decided ones already final, visited ones old until redrawn).  Where the row is
-//                          at its modes   v = off + base + sum_{m: r_m = 1 in some chain} [r_m] (lMd[k*][1] - lMd[k*][0]):
-//                          the row of differences is one coalesced load, asked for a site ahead; the regions with a set bit
-//                          are added under each chain's bit from lane-broadcast operands.
+//                          at its modes   v = off + base + sum_{m: r_m = 1 in some chain} [r_m] (lMd[k*][1] - lMd[k*][0]);
+//                          the list is walked in segments of RS_SEG sites, everything the chain does not compute -- loads,
+//                          Philox blocks, the regions outside the segment -- ahead of each segment's chain (see the kernel).
 //                          Otherwise the row's terms are gathered per chain from lMd with the chain's own f.  Same draw as
 //                          the blocked forms (fast logit, exact one within a.tol).  It leaves r_bits and the pair bytes r_Sn.
-// Rounding: base is a tree sum of Nreg - 1 terms and the walk adds at most Nreg differences to it, so v differs from the
-// blocked forms' sum (another tree over the same terms) by at most (Nreg + 20) 2^-53 sum|terms| -- 2.6e-14 x sum|terms|
-// at Nreg 200, nine orders below a.tol = 3.2e-4 for sums of thousands of nats; DESIGN.md (c): no draw of the parity
-// runs comes closer to a tie than 1000 x what re-ordering can move.
+// Rounding: base is a tree sum of Nreg - 1 terms and the walk adds at most Nreg differences to it -- first those of the regions
+// outside the segment in increasing m, then those of the segment in increasing j: one more order of the same terms -- so v
+// differs from the blocked forms' sum (another tree over the same terms) by at most (Nreg + 20) 2^-53 sum|terms|, whatever the
+// order: 2.6e-14 x sum|terms| at Nreg 200, nine orders below a.tol = 3.2e-4 for sums of thousands of nats; DESIGN.md (c): no
+// draw of the parity runs comes closer to a tie than 1000 x what re-ordering can move.
 // ---------------------------------------------------------------------------------------------
 struct r_sparse_args {
     const double *lMd, *hyper;
@@ -1622,146 +1623,241 @@ __device__ __forceinline__ void rs_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// grid (U, ceil(GW / RS_WAVES)): wave = (u, w); dynamic LDS per wave: (16 NBLK) uint64, the r words of the wave's column, then
-// RS_MAXCH words: the sites to visit, 64 regions a word.
-// The walk is one serial chain per wave -- what a site costs on that chain is what the pass costs -- so everything of the NEXT
-// site is asked for before this site's sum runs: its Philox block, its row of differences (with base on the diagonal) and its
-// flag, all through vector loads that depend on nothing the walk computes (a scalar load would be waited for with everything
-// else the wave has asked the scalar cache and the LDS for).
-constexpr int RS_CH = 4;        // chunks of 64 regions whose entries are prefetched (regions beyond: gathered at the site itself)
+// grid (U GW): one wave per workgroup = (u, w), u fastest, lane = chain.  The walk is one serial chain per wave -- what a site costs on that
+// chain is what the pass costs -- and the visit list is complete before the walk starts, so the list is cut into segments of at
+// most RS_SEG consecutive listed sites and every segment runs in two phases:
+//   phase 1  (no dependency between sites) lane j gathers, for the segment's site n_j, its flag, base = dtab[u][n_j][n_j], its r
+//            word, and one wave-wide load per row i of the in-segment matrix D[i][j] = dtab[u][n_i][n_j]; every load is issued
+//            before the first value is waited for, and the Philox blocks of the segment's sites run under their latency.  Per site
+//            and lane it leaves th_i = fcd_logit_fast(x_i) and P_i = off + base_i + the entries of the regions OUTSIDE the segment
+//            with a set bit in some chain (in increasing m), under each chain's bit: the column as it stands when the segment
+//            starts -- final for decided regions and for earlier segments, old for later ones.
+//   phase 2  the chain: lane = chain keeps the segment's bits of its own chain in one register (bit j new for j < i, old for
+//            j > i) and the wave one mask of the j with a set bit in any chain;  v = P_i + sum_{j in mask, j != i} bit_j D[i][j]
+//            in increasing j, v -= th_i, the exact logit within a.tol, ballot.  P_i and th_i come from LDS one site ahead; the
+//            row of D is read at wave-uniform addresses (a broadcast), eight j a group, groups without a set bit skipped.
+// Slow sites (flag set, or a NaN base) stay on the chain with the per-chain gather over lMd from the LDS column, which lane 0
+// keeps current for them and for the epilogue.
+// Dynamic LDS: P [RS_SEG][64] double, D [RS_SEG][RS_SEG] double, the r words of the column (16 NBLK), the visit words and the
+// segment's words (RS_MAXCH each, 64 regions a word), th [RS_SEG][64] float, the segment's sites [RS_SEG] int.
+constexpr int RS_SEG = 32;      // sites per segment (16 or 32: the segment's bits are one 32-bit register)
 constexpr int RS_MAXCH = 16;    // 64-region chunks of the largest Nreg the blocked forms take (832)
-struct rs_site {
-    double xx, th;
-    uint32_t off_modes;
-    double dl[RS_CH];
-};
-__global__ __launch_bounds__(64 * RS_WAVES) void gibbs_r_sparse_kernel(const r_sparse_args a) {
+static_assert(RS_SEG == 16 || RS_SEG == 32, "the walk's segment is 16 or 32 sites");
+static inline size_t rs_walk_lds(int NBLK) {
+    return (size_t)(RS_SEG * 64 + RS_SEG * RS_SEG + NBLK * R_NB + 2 * RS_MAXCH) * 8 + (size_t)RS_SEG * 64 * 4 + (size_t)RS_SEG * 4;
+}
+__device__ __forceinline__ double rs_lane_f64(double v, int j) {
+    return __longlong_as_double((long long)fcd_lane_word((uint64_t)__double_as_longlong(v), j));
+}
+__device__ __forceinline__ uint64_t rs_uniform64(uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+__global__ __launch_bounds__(64) void gibbs_r_sparse_kernel(const r_sparse_args a) {
     extern __shared__ uint64_t rs_lds[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int u = (int)blockIdx.x, w = (int)blockIdx.y * RS_WAVES + wave;
+    constexpr int S = RS_SEG;
+    const int lane = (int)threadIdx.x;
     const int Nreg = a.Nreg, U = a.U, NBLK = a.NBLK, NP = NBLK * R_NB, NPAIR = (U + 1) >> 1;
-    if (w >= a.GW) return;                       // (no workgroup barrier below)
-    uint64_t *rm = rs_lds + (size_t)wave * (NP + RS_MAXCH);
-    uint64_t *vm = rm + NP;
+    const int u = (int)(blockIdx.x % (unsigned)U), w = (int)(blockIdx.x / (unsigned)U);
+    double *Pl = reinterpret_cast<double *>(rs_lds);          // [S][64]
+    double *Dl = Pl + S * 64;                                  // [S][S]
+    uint64_t *rm = reinterpret_cast<uint64_t *>(Dl + S * S);   // [NP]
+    uint64_t *vm = rm + NP;                                    // [RS_MAXCH]
+    uint64_t *sw = vm + RS_MAXCH;                              // [RS_MAXCH]
+    float *thl = reinterpret_cast<float *>(sw + RS_MAXCH);     // [S][64]
+    int *sn = reinterpret_cast<int *>(thl + S * 64);           // [S]
     uint64_t *__restrict__ rcol = a.r_bits + (int64_t)w * Nreg * U + u;
     const int nchunk = (Nreg + 63) >> 6;
-    for (int m = lane; m < NP; m += 64) rm[m] = m < Nreg ? rcol[(int64_t)m * U] : 0ull;
-    for (int c = 0; c < nchunk; ++c) {
-        const int nl = c * 64 + lane;
-        const uint64_t todo = __ballot(nl < Nreg && ((a.visit[(int64_t)w * Nreg + (nl < Nreg ? nl : 0)] >> u) & 1ull));
-        if (lane == 0) vm[c] = todo;
+    // the column and the visit words, four 64-region words a round: every load of a round is issued before the first is waited for
+    for (int c0 = 0; c0 < nchunk; c0 += 4) {
+        uint64_t col[4], vis[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int m = (c0 + k) * 64 + lane, mc = m < Nreg ? m : 0;
+            col[k] = rcol[(int64_t)mc * U];
+            vis[k] = a.visit[(int64_t)w * Nreg + mc];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int m = (c0 + k) * 64 + lane;
+            if (m < NP) rm[m] = m < Nreg ? col[k] : 0ull;               // (NP <= 64 nchunk)
+            const uint64_t todo = __ballot(m < Nreg && ((vis[k] >> u) & 1ull));
+            if (lane == 0 && c0 + k < nchunk) vm[c0 + k] = todo;
+        }
     }
     rs_wave_sync();
     const double off = a.hyper[FCD_H_LNPI1] - a.hyper[FCD_H_LNPI0];
     const uint32_t chain = a.chain0 + (uint32_t)w * 64u + (uint32_t)lane;
-    // the site after n in the wave's list (n = -1: the first), or -1
-    auto next_site = [&](int n) -> int {
-        int c = n < 0 ? 0 : n >> 6;
-        uint64_t t = c < nchunk ? vm[c] : 0ull;
-        if (n >= 0) t &= (n & 63) == 63 ? 0ull : ~0ull << ((n & 63) + 1);
-        while (t == 0ull && ++c < nchunk) t = vm[c];
-        return __builtin_amdgcn_readfirstlane(t ? c * 64 + (int)__builtin_ctzll(t) : -1);
+    const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
+    const double *__restrict__ utab = a.dtab + (int64_t)u * Nreg * Nreg;
+    auto uniform_of = [&](int n) -> double {
+        const fcd_u4 x = fcd_philox((uint32_t)(n * NPAIR + (u >> 1)), chain, a.sweep, FCD_KIND_R, k0, k1);
+        return (u & 1) ? fcd_u53(x.z, x.w) : fcd_u53(x.x, x.y);
     };
-    uint32_t zlane = 0u;                         // (a zero the compiler cannot see through: wave-uniform addresses in vector loads)
-    asm volatile("" : "+v"(zlane));
-    auto fetch = [&](int n) -> rs_site {
-        rs_site S;
-        const fcd_u4 x = fcd_philox((uint32_t)(n * NPAIR + (u >> 1)), chain, a.sweep, FCD_KIND_R, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-        S.xx = (u & 1) ? fcd_u53(x.z, x.w) : fcd_u53(x.x, x.y);
-        S.th = fcd_logit_fast(S.xx);
-        S.off_modes = (a.fneq + (int64_t)w * Nreg + n)[zlane];
-        const double *__restrict__ drow = a.dtab + ((int64_t)u * Nreg + n) * Nreg;
-#pragma unroll
-        for (int q = 0; q < RS_CH; ++q) {
-            const int m = q * 64 + lane;
-            S.dl[q] = drow[m < Nreg ? m : Nreg - 1];
+    int pos = 0;                                 // the first region the segments before this one have not covered
+    for (;;) {
+        // the segment's sites: the next (at most S) set bits of the visit words from pos on, in order; sw = the words of its regions
+        int cnt = 0, last = -1;
+        for (int c = 0; c < nchunk; ++c) {
+            uint64_t t = rs_uniform64(vm[c]);
+            if (c < (pos >> 6) || cnt >= S) t = 0ull;
+            else if (c == (pos >> 6)) t &= ~0ull << (pos & 63);
+            const int before = (int)__builtin_popcountll(t & ((1ull << lane) - 1ull));
+            const bool mine = ((t >> lane) & 1ull) && cnt + before < S;
+            const uint64_t take = __ballot(mine);
+            if (mine) sn[cnt + before] = c * 64 + lane;
+            if (lane == 0) sw[c] = take;
+            if (take) last = c * 64 + 63 - (int)__builtin_clzll(take);
+            cnt += (int)__builtin_popcountll(take);
         }
-        return S;
-    };
-    // v += the entries dl of the regions whose word has a set bit, each under this chain's bit
-    auto add_terms = [&](double &v, uint64_t word, double dl) {
-        uint64_t bm = __ballot(word != 0ull);
-        while (bm) {
-            const int j = (int)__builtin_ctzll(bm);
-            bm &= bm - 1ull;
-            const uint64_t wj = fcd_lane_word(word, j);
-            const double dj = __longlong_as_double((long long)fcd_lane_word((uint64_t)__double_as_longlong(dl), j));
-            v += ((wj >> lane) & 1ull) ? dj : 0.0;
-        }
-    };
-    int n = next_site(-1);
-    rs_site S = {};
-    if (n >= 0) S = fetch(n);
-    while (n >= 0) {
-        const int n2 = next_site(n);
-        rs_site S2 = {};
-        if (n2 >= 0) S2 = fetch(n2);
-        const double *__restrict__ row = a.lMd + ((int64_t)u * Nreg + n) * Nreg * 6;
-        const double *__restrict__ drow = a.dtab + ((int64_t)u * Nreg + n) * Nreg;
-        // base(n,u): the diagonal entry of the row
-        double base = 0.0;
-        if ((n >> 6) < RS_CH) {
+        if (cnt == 0) break;
+        pos = last + 1;
+        rs_wave_sync();
+        // ---- phase 1: everything the chain does not compute
+        const int nj = sn[lane < cnt ? lane : 0];                        // lane j: site j of the segment (lanes beyond: site 0)
+        const double basej = utab[(int64_t)nj * Nreg + nj];
+        const uint32_t fnj = a.fneq[(int64_t)w * Nreg + nj];
+        const uint64_t wj = lane < cnt ? rm[nj] : 0ull;
+        double d[S];
 #pragma unroll
-            for (int q = 0; q < RS_CH; ++q)
-                if (q == (n >> 6)) base = __longlong_as_double((long long)fcd_lane_word((uint64_t)__double_as_longlong(S.dl[q]), n & 63));
-        } else {
-            base = (drow + n)[zlane];
-        }
-        double v = off;
-        if (!(S.off_modes != 0u || base != base)) {
-            v += base;
+        for (int i = 0; i < S; ++i) d[i] = 0.0;
 #pragma unroll
-            for (int q = 0; q < RS_CH; ++q) {
-                const int m = q * 64 + lane;
-                add_terms(v, (m < Nreg && m != n) ? rm[m] : 0ull, S.dl[q]);
+        for (int g = 0; g < S / 8; ++g) {
+            if (g * 8 < cnt) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const int i = g * 8 + k;
+                    const int ni = __builtin_amdgcn_readlane(nj, i < cnt ? i : 0);
+                    d[i] = utab[(int64_t)ni * Nreg + nj];
+                }
             }
-            // (regions beyond the prefetched chunks: loaded here)
-            for (int c0 = RS_CH; c0 < nchunk; ++c0) {
-                const int m = c0 * 64 + lane;
-                const uint64_t word = (m < Nreg && m != n) ? rm[m] : 0ull;
-                add_terms(v, word, word ? drow[m] : 0.0);
-            }
-        } else {
-            // the row's terms per chain, with the chain's own f (pair bytes of f_S: q = 3 f(n,m) + f(n,m+1), shifted by 2)
-            const uint2 *__restrict__ fw = a.f_S + ((int64_t)w * Nreg + n) * NBLK * 64 + lane;
-            for (int b = 0; b < NBLK; ++b) {
-                const uint2 f = fw[b * 64];
-                double t[R_NB];
+        }
+        // the segment's bits of this lane's chain, and the j with a set bit in any chain
+        uint32_t bits = 0u;
+        for (int j = 0; j < cnt; ++j) bits |= (uint32_t)((fcd_lane_word(wj, j) >> lane) & 1ull) << j;
+        uint32_t mask = (uint32_t)__ballot(wj != 0ull);
+        // (the Philox blocks first: nothing in them waits for a load)
+        for (int i = 0; i < cnt; ++i) {
+            const int ni = __builtin_amdgcn_readlane(nj, i);
+            thl[i * 64 + lane] = (float)fcd_logit_fast(uniform_of(ni));          // (fcd_logit_fast returns a float's value)
+        }
+        const uint32_t slow = (uint32_t)__ballot(lane < cnt && (fnj != 0u || basej != basej));
+        for (int i = 0; i < cnt; ++i) Pl[i * 64 + lane] = off + rs_lane_f64(basej, i);
 #pragma unroll
-                for (int j = 0; j < R_NB; ++j) {
-                    const int m = b * R_NB + j, p = j >> 1;
-                    const uint32_t q = (((p < 4 ? f.x : f.y) >> (8 * (p & 3))) & 0xffu) >> 2;
-                    const uint32_t k = (j & 1) ? q % 3u : q / 3u;
-                    const bool on = m < Nreg && m != n;
-                    const uint32_t bit = (uint32_t)((rm[m] >> lane) & 1ull);
-                    const double val = row[(on ? m : 0) * 6 + (on ? 2 * k + bit : 0u)];
-                    t[j] = on ? val : 0.0;
+        for (int g = 0; g < S / 8; ++g) {
+            if (g * 8 < cnt) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    if (lane < S) Dl[(g * 8 + k) * S + lane] = d[g * 8 + k];
+            }
+        }
+        // the regions outside the segment with a set bit in some chain, four gathers in flight
+        for (int c = 0; c < nchunk; ++c) {
+            const int m = c * 64 + lane;
+            const uint64_t word = m < Nreg ? rm[m] : 0ull;
+            uint64_t om = __ballot(word != 0ull) & ~rs_uniform64(sw[c]);
+            while (om) {
+                int l[4];
+                double val[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    l[k] = om ? (int)__builtin_ctzll(om) : -1;
+                    om &= om - 1ull;                                     // (0 stays 0)
+                    val[k] = utab[(int64_t)nj * Nreg + c * 64 + (l[k] < 0 ? 0 : l[k])];
                 }
 #pragma unroll
-                for (int j = 0; j < R_NB; ++j) v += t[j];
+                for (int k = 0; k < 4; ++k) {
+                    if (l[k] < 0) break;
+                    const bool on = (fcd_lane_word(word, l[k]) >> lane) & 1ull;
+                    for (int i = 0; i < cnt; ++i) {
+                        const double di = rs_lane_f64(val[k], i);
+                        if (on) Pl[i * 64 + lane] += di;
+                    }
+                }
             }
         }
-        v -= S.th;
-        if (__ballot(fabs(v) < a.tol) != 0ull) {
-            // too close to call with the fast threshold: the exact one in its place
-            if (S.xx > 0.0) v += S.th - fcd_logit(S.xx);          // (x = 0: both thresholds are -inf, v = +inf already)
-        }
-        const uint64_t ball = __ballot(v > 0.0);
-        if (lane == 0) {
-            rm[n] = ball;
-            rcol[(int64_t)n * U] = ball;
+        rs_wave_sync();
+        // ---- phase 2: the chain
+        double Pn = Pl[lane];
+        float tn = thl[lane];
+        for (int i = 0; i < cnt; ++i) {
+            const int n = __builtin_amdgcn_readlane(nj, i);
+            const double Pi = Pn, th = (double)tn;
+            {
+                const int i2 = i + 1 < cnt ? i + 1 : i;
+                Pn = Pl[i2 * 64 + lane];
+                tn = thl[i2 * 64 + lane];
+            }
+            double v;
+            if (!((slow >> i) & 1u)) {
+                // eight j a group, a group none of whose j has a set bit skipped: the row's entries are LDS reads at wave-uniform
+                // addresses (a broadcast: no lane moves), all of a site's reads issued before its first addition
+                const double *Di = Dl + i * S;
+                const uint32_t mm = mask & ~(1u << i), bm = bits & ~(1u << i);
+                double dd[S];
+#pragma unroll
+                for (int g = 0; g < S / 8; ++g) {
+                    if ((mm >> (8 * g)) & 0xffu) {
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) dd[g * 8 + k] = Di[g * 8 + k];
+                    }
+                }
+                v = Pi;
+#pragma unroll
+                for (int g = 0; g < S / 8; ++g) {
+                    if ((mm >> (8 * g)) & 0xffu) {
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) v += ((bm >> (g * 8 + k)) & 1u) ? dd[g * 8 + k] : 0.0;
+                    }
+                }
+            } else {
+                // the row's terms per chain, with the chain's own f (pair bytes of f_S: q = 3 f(n,m) + f(n,m+1), shifted by 2)
+                rs_wave_sync();
+                v = off;
+                const double *__restrict__ row = a.lMd + ((int64_t)u * Nreg + n) * Nreg * 6;
+                const uint2 *__restrict__ fw = a.f_S + ((int64_t)w * Nreg + n) * NBLK * 64 + lane;
+                for (int b = 0; b < NBLK; ++b) {
+                    const uint2 f = fw[b * 64];
+                    double t[R_NB];
+#pragma unroll
+                    for (int j = 0; j < R_NB; ++j) {
+                        const int m = b * R_NB + j, p = j >> 1;
+                        const uint32_t q = (((p < 4 ? f.x : f.y) >> (8 * (p & 3))) & 0xffu) >> 2;
+                        const uint32_t k = (j & 1) ? q % 3u : q / 3u;
+                        const bool on = m < Nreg && m != n;
+                        const uint32_t bit = (uint32_t)((rm[m] >> lane) & 1ull);
+                        const double val = row[(on ? m : 0) * 6 + (on ? 2 * k + bit : 0u)];
+                        t[j] = on ? val : 0.0;
+                    }
+#pragma unroll
+                    for (int j = 0; j < R_NB; ++j) v += t[j];
+                }
+            }
+            v -= th;
+            if (__ballot(fabs(v) < a.tol) != 0ull) {
+                // too close to call with the fast threshold: the exact one in its place (the uniform drawn again: rare)
+                const double xx = uniform_of(n);
+                if (xx > 0.0) v += th - fcd_logit(xx);                  // (x = 0: both thresholds are -inf, v = +inf already)
+            }
+            const uint64_t ball = __ballot(v > 0.0);
+            if (lane == 0) {
+                rm[n] = ball;
+                rcol[(int64_t)n * U] = ball;
+            }
+            bits = (bits & ~(1u << i)) | ((uint32_t)((ball >> lane) & 1ull) << i);
+            mask = (mask & ~(1u << i)) | (ball ? 1u << i : 0u);
         }
         rs_wave_sync();
-        n = n2;
-        S = S2;
+        if (cnt < S) break;                      // (the list ended inside this segment)
     }
     // the pair bytes of every block for the next pass
     uint2 *__restrict__ dst = a.r_Sn + ((int64_t)w * U + u) * NBLK * 64 + lane;
+    const uint32_t *rm32 = reinterpret_cast<const uint32_t *>(rm) + (lane >> 5);      // the half of a word that holds this lane's bit
     for (int b = 0; b < NBLK; ++b) {
         uint32_t v16 = 0u;
 #pragma unroll
-        for (int j = 0; j < R_NB; ++j) v16 |= (uint32_t)((rm[b * R_NB + j] >> lane) & 1ull) << j;
+        for (int j = 0; j < R_NB; ++j) v16 |= ((rm32[2 * (b * R_NB + j)] >> (lane & 31)) & 1u) << j;
         dst[b * 64] = spread2(v16);
     }
 }
@@ -2058,8 +2154,7 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         // (both launches inside the r step's profiling pair: fcd_prof_collect keeps one name for the r pass)
         fcd_prof_begin(ctx, FCD_PROF_RSTEP, s);
         hipLaunchKernelGGL(gibbs_r_range_kernel, dim3((unsigned)((Nreg + RS_WAVES - 1) / RS_WAVES), (unsigned)g.GW), dim3(64 * RS_WAVES), 0, s, q);
-        hipLaunchKernelGGL(gibbs_r_sparse_kernel, dim3((unsigned)U, (unsigned)((g.GW + RS_WAVES - 1) / RS_WAVES)), dim3(64 * RS_WAVES),
-                           (size_t)RS_WAVES * (NBLK * R_NB + RS_MAXCH) * sizeof(uint64_t), s, q);
+        hipLaunchKernelGGL(gibbs_r_sparse_kernel, dim3((unsigned)(U * g.GW)), dim3(64), rs_walk_lds(NBLK), s, q);
         fcd_prof_end(ctx, FCD_PROF_RSTEP, s);
         FCD_LAUNCH_CHECK();
         ctx->r_form_last = 4;
