@@ -269,7 +269,7 @@ def _check_tangent_fit(ts, shrinkage, reference, tol, max_iter, confounds, frame
     return (mode, value, H, Nreg, T)
 
 
-def sym_eigh(A, ctx=None, as_numpy=True):
+def sym_eigh(A, ctx=None, as_numpy=True, _max_chunk=None):
     """
     Eigendecomposition of a batch of symmetric matrices on the device (fcd_sym_eigh, include/fcdiff_hip.h): parallel cyclic
     Jacobi, one workgroup per matrix.  A : (B, n, n) or (n, n) float64, n <= 1024, not necessarily definite; only the lower
@@ -292,7 +292,13 @@ def sym_eigh(A, ctx=None, as_numpy=True):
     status = torch.empty((B,), dtype=torch.int32, device=ctx.device)
     d = _lib.EighDesc.make(B=B, n=n, stream=_lib.stream_ptr(), A=_lib.dptr(a), w=_lib.dptr(w), V=_lib.dptr(V), status=_lib.dptr(status))
     import ctypes
-    ctx.call("fcd_sym_eigh", ctypes.byref(d))
+    if _max_chunk is not None:
+        ctx.set_knob("tangent_chunk", int(_max_chunk))
+    try:
+        ctx.call("fcd_sym_eigh", ctypes.byref(d))
+    finally:
+        if _max_chunk is not None:
+            ctx.set_knob("tangent_chunk", 0)
     if len(_shape(A)) == 2:
         (w, V, status) = (w[0], V[0], status[0])
     return (w.cpu().numpy(), V.cpu().numpy(), status.cpu().numpy()) if as_numpy else (w, V, status)

@@ -44,7 +44,7 @@ struct fcd_knobs {
                        // a wave's rounds are at most R_TALLY_MAX_ROUNDS, 1 = never (the tally after the pass counts f), 2 = wherever
                        // the form allows (16-wave in-order workgroups)
     int partial_chunk; // > 0: fcd_corr_partial walks at most this many subjects per chunk (tests: the chunking changes no bit)
-    int tangent_chunk; // > 0: the same for fcd_tangent_fit and fcd_tangent_apply
+    int tangent_chunk; // > 0: the same for fcd_tangent_fit and fcd_tangent_apply (subjects) and fcd_sym_eigh (matrices)
     int r_keep_words;  // 1: the tally makes the next pass's r words from the r bits (default: the pass's two r-word buffers swap
                        // roles from sweep to sweep -- what a pass wrote as r_Sn is the next pass's r_S)
     int r_sure;        // sparse r pass (gibbs_r_sparse_kernel: the sums of sites the tables decide are skipped): 0 = where the call's

@@ -100,6 +100,7 @@ __global__ __launch_bounds__(1024) void eig_jacobi_kernel(const double *__restri
                             const double app = A[p * ld + p], aqq = A[q * ld + q];
                             const double theta = (aqq - app) / (2.0 * apq);
                             double t;
+                            // (never taken: |apq| > 2^-58 ||A||_F and |aqq - app| <= 2 ||A||_F bound |theta| by 2^58)
                             if (fabs(theta) > 1e150) t = 0.5 / theta;
                             else t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
                             c = 1.0 / sqrt(t * t + 1.0);
@@ -480,6 +481,7 @@ extern "C" int fcd_sym_eigh(fcd_ctx *ctx, const fcd_eigh_desc *d) {
     const int n = (int)d->n;
     const int64_t n2 = (int64_t)n * n;
     int64_t BC = (int64_t)(4 * TG_MAT_BYTES / ((size_t)2 * n2 * sizeof(double)));
+    if (ctx->knobs.tangent_chunk > 0 && BC > ctx->knobs.tangent_chunk) BC = ctx->knobs.tangent_chunk;
     if (BC < 1) BC = 1;
     if (BC > d->B) BC = d->B;
     int rc = fcd_ws_reserve(ctx, eig_work_bytes(BC, n));

@@ -114,7 +114,8 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
  *   "corr_form" 1: fcd_corr_edges in 64 x 64 blocks with a moments pass also where the one-workgroup-per-subject kernel
  *               (up to 208 regions) would run
  *   "partial_chunk"  > 0: fcd_corr_partial walks at most this many subjects per chunk (tests; not read from the environment)
- *   "tangent_chunk"  > 0: the same for fcd_tangent_fit and fcd_tangent_apply
+ *   "tangent_chunk"  > 0: the same for fcd_tangent_fit and fcd_tangent_apply, and at most this many matrices per launch of
+ *               fcd_sym_eigh
  *   "r_tol", "f_tol"  widen the margin inside which a fast r / f draw is repeated with the exact formula (1e30: all)
  *   "f_form"    2: the any-U pair kernel of the f pass also where the U <= 64 kernel would run; 3: scalar-mask form
  *   "f_pack"    1: the r pass's packing launch in every sweep (default: from the second sweep of a fcd_gibbs_run call on,
@@ -535,7 +536,8 @@ int fcd_site_harmonize_apply(fcd_ctx *ctx, const fcd_harmonize_desc *d);
  * Two-sided parallel cyclic Jacobi, one workgroup per matrix: round-robin pairing (a bye for odd n), an off-diagonal at or
  * below 2^-58 ||A||_F is not rotated, a sweep without a rotation ends the loop, 40 sweeps at the most.  A diagonal matrix is
  * therefore returned as it is (sorted), exactly.  Up to n = 96 the matrix and the eigenvectors stay in LDS; above, they live in
- * the context's workspace (2 n^2 doubles per matrix of a chunk of at most 512 MB).  Deterministic; A is not written.
+ * the context's workspace (2 n^2 doubles per matrix of a chunk of at most 512 MB, or of at most "tangent_chunk" matrices where
+ * that knob is > 0; successive chunks reuse it, and the chunking changes no bit).  Deterministic; A is not written.
  * FCD_ERR_ARG: null context, descriptor or pointer, size != sizeof(fcd_eigh_desc), B or n < 1.  FCD_ERR_UNSUPPORTED: n > 1024,
  * B > 2^24, flags != 0. */
 typedef struct fcd_eigh_desc {

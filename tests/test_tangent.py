@@ -107,6 +107,59 @@ def test_recorded_ratios_have_not_grown():
     assert TR.MARGIN == 16.0
 
 
+def test_recorded_edge_ratios_have_not_grown():
+    r = TR.measure_r(edge=True)
+    print(r)
+    for (k, v) in r.items():
+        assert v <= getattr(TR, k), (k, v)
+        assert v >= 0.25 * getattr(TR, k), "%s = %g: the record %g is stale" % (k, v, getattr(TR, k))
+    # the tables of tests/test_gpu_tangent.py are not these
+    assert not set(TR.tangent_edge_cases()) & set(TR.tangent_cases()) and sorted(r) == sorted(k + "_EDGE" for k in TR.measure_r(names=[]))
+
+
+def test_edge_inputs_are_what_their_names_say():
+    """the conditioning, the scales and the shapes that tests/test_gpu_tangent_edges.py relies on, on the oracle alone"""
+    cases = TR.tangent_edge_cases()
+    # the ladder: kappa(M_s) of every subject in the decade of 1 / alpha, status 0 on both routes (measure_r asserts the second)
+    for a in TR.LADDER_ALPHAS:
+        ref = TR.tangent_edge_reference("ladder_%g" % a)
+        assert cases["ladder_%g" % a]["kappa"] == (1 / a, 10 / a) and cases["ladder_%g" % a]["ts"].shape == (4, 17, TR.LADDER_FRAMES)
+        assert np.array_equal(ref["status"], np.zeros(4)) and np.all(ref["kappa"] >= 1 / a) and np.all(ref["kappa"] < 10 / a), (a, ref["kappa"])
+    # either side of EIG_MIN.  The side that fails is more than 100 times below it.  The side that passes is 51 times above it:
+    # kappa = 2e10 is 1 / (50 EIG_MIN), and the fp64 chain moves lambda_min / lambda_max by about n eps kappa = 1e-4 of itself,
+    # so neither case sits anywhere near the boundary
+    (lo, hi) = (TR.tangent_edge_reference("boundary_%g" % a) for a in TR.BOUNDARY_ALPHAS)
+    assert list(lo["status"]) == [0, 0, 0, 0] and list(hi["status"]) == [0, 1, 1, 1]
+    assert np.all(lo["ratio"][1:] >= 50 * TR.EIG_MIN) and np.all(hi["ratio"][1:] <= TR.EIG_MIN / 100) and np.all(lo["kappa"][1:] > 1.5e10)
+    assert lo["kappa"][0] <= 100 and hi["kappa"][0] <= 100
+    assert 17 * TR.EPS * np.nanmax(lo["kappa"]) * 16 * TR.R_T < 1e-3
+    # no padding: 32 and 96 regions are whole tiles; 97 is past the LDS form, 32 | 33 the two workgroup sizes
+    assert cases["apply_32_40_33"]["ts"].shape == (33, 32, 40) and cases["apply_97_60_3"]["ts"].shape == (3, 97, 60)
+    assert TR.EIGH_EDGE_SIZES == (1, 32, 96, 97) and all(TR.eigh_edge_cases()["size_%d" % n].shape == (3, n, n) for n in TR.EIGH_EDGE_SIZES)
+    # the graded matrix: 16 decades, and the fp64 Jacobi of the device's rule (2^-58 ||A||_F) converges on it in a few sweeps
+    G = TR.graded_matrix()
+    w_ld = TR.eigh_edge_reference("graded_%d" % TR.SCALE_N)[0]
+    assert 1e15 < float(w_ld[-1] / w_ld[0]) < 1e17 and w_ld[0] > 0
+    (w, V, sweeps) = TR.jacobi_eigh(G, np.float64)
+    (e_w, e_res, e_orth) = TR.eigh_errors(G, w, V, w_ld)
+    print("graded: fp64 Jacobi %d sweeps, eigenvalues %.3g, residual %.3g, orthogonality %.3g" % (sweeps, e_w, e_res, e_orth))
+    assert sweeps <= 8 and max(e_w, e_res, e_orth) <= TR.MARGIN * TR.R_EIGH_ORTH
+    # a power of two scales every step of the fp64 Jacobi exactly: the threshold too (sqrt of an exact 4^k multiple)
+    A = TR.scale_matrix()
+    (w0, V0, s0) = TR.jacobi_eigh(A, np.float64)
+    for k in TR.SCALE_EXACT:
+        (wk, Vk, sk) = TR.jacobi_eigh(np.ldexp(A, k), np.float64)
+        assert sk == s0 and wk.tobytes() == np.ldexp(w0, k).tobytes() and Vk.tobytes() == V0.tobytes(), k
+    # the extreme scales: the squares leave the normal range at one end and stay finite at the other; one step further they overflow
+    with np.errstate(over="ignore", under="ignore"):
+        sq = [float((np.ldexp(A, k) ** 2).sum()) for k in TR.SCALE_EXTREME + (TR.SCALE_OVERFLOW,)]
+    assert sq[0] < 2.0 ** -1022 and np.isfinite(sq[1]) and sq[1] > 2.0 ** 1000 and np.isinf(sq[2]) and np.isfinite(np.ldexp(A, TR.SCALE_OVERFLOW)).all()
+    # the private chunk bound of the eigensolver
+    import inspect
+    from fcdiff_amd import corr
+    assert inspect.signature(corr.sym_eigh).parameters["_max_chunk"].default is None
+
+
 def test_host_side_refusals_need_no_gpu():
     from fcdiff_amd import corr
     ts = np.zeros((3, 5, 20))
