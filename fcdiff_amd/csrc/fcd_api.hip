@@ -167,6 +167,7 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->pt_with_rs = 0;
     ctx->acc = nullptr;
     ctx->nan_slots = nullptr;
+    ctx->f_slots = nullptr;
     ctx->dbg = nullptr;
     ctx->comm = nullptr;
     ctx->comm_world = ctx->comm_rank = 0;
@@ -203,6 +204,7 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->knobs.f_runs = 0;
     ctx->knobs.r_sure = 0;
     ctx->knobs.r_sure_x = 0.0;
+    ctx->knobs.tally_in_f = 0;
     ctx->knobs.partial_chunk = 0;
     ctx->knobs.tangent_chunk = 0;
     ctx->knobs.tally_in_r = (int)knob_env("FCD_TALLY_IN_R");
@@ -211,6 +213,7 @@ int fcd_ctx_create(fcd_ctx **out) {
     ctx->n_pack = 0;
     ctx->n_pack_tally = 0;
     ctx->n_r_tally = 0;
+    ctx->n_f_tally = 0;
     ctx->n_frec_pass = ctx->n_frec_build = ctx->n_fsure_pass = ctx->n_frun_pass = 0;
     ctx->n_rsure_pass = ctx->n_rsure_build = 0;
     int rc = fcd_ws_reserve(ctx, 1u << 20);
@@ -245,6 +248,9 @@ int fcd_ctx_create(fcd_ctx **out) {
         if (e == hipSuccess) e = hipMalloc(&ctx->acc, 8 * sizeof(unsigned long long));
         ctx->n_alloc += 1;
         if (e == hipSuccess) e = hipMemset(ctx->acc, 0, 8 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMalloc(&ctx->f_slots, FCD_F_SLOTS * 8 * sizeof(unsigned long long));
+        ctx->n_alloc += 1;
+        if (e == hipSuccess) e = hipMemset(ctx->f_slots, 0, FCD_F_SLOTS * 8 * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipMalloc(&ctx->nan_slots, FCD_NAN_SLOTS * 16 * sizeof(unsigned long long));
         ctx->n_alloc += 1;
         if (e == hipSuccess) e = hipMemset(ctx->nan_slots, 0, FCD_NAN_SLOTS * 16 * sizeof(unsigned long long));
@@ -277,6 +283,7 @@ int fcd_ctx_destroy(fcd_ctx *ctx) {
     if (ctx->pg_dev) (void)hipFree(ctx->pg_dev);
     if (ctx->pt_dev) (void)hipFree(ctx->pt_dev);
     if (ctx->acc) (void)hipFree(ctx->acc);
+    if (ctx->f_slots) (void)hipFree(ctx->f_slots);
     if (ctx->nan_slots) (void)hipFree(ctx->nan_slots);
     if (ctx->dbg) (void)hipFree(ctx->dbg);
     if (ctx->corr_tickets) (void)hipFree(ctx->corr_tickets);
@@ -331,6 +338,7 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value) {
     else if (!strcmp(name, "partial_chunk")) k.partial_chunk = (int)value;
     else if (!strcmp(name, "tangent_chunk")) k.tangent_chunk = (int)value;
     else if (!strcmp(name, "tally_in_r")) k.tally_in_r = (int)value;
+    else if (!strcmp(name, "tally_in_f")) k.tally_in_f = (int)value;
     else if (!strcmp(name, "r_keep_words")) k.r_keep_words = (int)value;
     else if (!strcmp(name, "r_poll_limit")) k.r_poll_limit = (int)value;
     else if (!strcmp(name, "r_withhold")) k.r_withhold = (int)value;
@@ -352,6 +360,7 @@ int fcd_ctx_clear_error(fcd_ctx *ctx) {
     if (ctx->dev_err) *ctx->dev_err = 0u;
     // whatever an abandoned launch left in the context-owned accumulators / tickets (zero between launches by contract)
     if (ctx->acc) FCD_HIP_TRY(hipMemset(ctx->acc, 0, 8 * sizeof(unsigned long long)));
+    if (ctx->f_slots) FCD_HIP_TRY(hipMemset(ctx->f_slots, 0, FCD_F_SLOTS * 8 * sizeof(unsigned long long)));
     if (ctx->nan_slots) FCD_HIP_TRY(hipMemset(ctx->nan_slots, 0, FCD_NAN_SLOTS * 16 * sizeof(unsigned long long)));
     if (ctx->corr_tickets && ctx->corr_tickets_n > 0)
         FCD_HIP_TRY(hipMemset(ctx->corr_tickets, 0, (size_t)ctx->corr_tickets_n * sizeof(unsigned)));
@@ -367,6 +376,7 @@ int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out) {
     else if (!strcmp(name, "pack_launches")) *out = ctx->n_pack;
     else if (!strcmp(name, "tally_f_in_pack")) *out = ctx->n_pack_tally;
     else if (!strcmp(name, "tally_f_in_r")) *out = ctx->n_r_tally;
+    else if (!strcmp(name, "tally_f_in_f")) *out = ctx->n_f_tally;
     else if (!strcmp(name, "tally_in_r_max_rounds")) *out = R_TALLY_MAX_ROUNDS;
     else if (!strcmp(name, "f_rec_passes")) *out = ctx->n_frec_pass;
     else if (!strcmp(name, "f_rec_builds")) *out = ctx->n_frec_build;

@@ -43,6 +43,9 @@ struct fcd_knobs {
     int tally_in_r;    // f half of the tally inside the pipelined r pass (its in-order workgroups, before their first block): 0 = where
                        // a wave's rounds are at most R_TALLY_MAX_ROUNDS, 1 = never (the tally after the pass counts f), 2 = wherever
                        // the form allows (16-wave in-order workgroups)
+    int tally_in_f;    // f half of the tally inside the f pass's run kernel (gibbs_f_run_kernel counts what it stores): 0 = where a
+                       // sparse r pass follows in the same sweep (nothing else then carries it), 1 = never, 2 = wherever the run
+                       // form runs (tests: ahead of the pipelined and the step form)
     int partial_chunk; // > 0: fcd_corr_partial walks at most this many subjects per chunk (tests: the chunking changes no bit)
     int tangent_chunk; // > 0: the same for fcd_tangent_fit and fcd_tangent_apply (subjects) and fcd_sym_eigh (matrices)
     int r_keep_words;  // 1: the tally makes the next pass's r words from the r bits (default: the pass's two r-word buffers swap
@@ -62,6 +65,7 @@ enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA
        FCD_KA_N = FCD_KA_EIGH + 1 };
 
 #define FCD_NAN_SLOTS 256
+#define FCD_F_SLOTS 64
 
 // The optional tallies fcd_gibbs_run adds to caller-owned uint32 buffers after a counted sweep, in the order it makes them:
 // (C, U, 3, 3) counts of (f_c, mixture case) (fcd_gibbs_set_pair_accumulator; one buffer, held in both places), (U, Nreg+1) /
@@ -95,6 +99,7 @@ struct fcd_ctx {
     long long n_pack;              // packing launches of the r pass so far (fcd_ctx_stat "pack_launches")
     long long n_pack_tally;        // ... of them that carried the f half of the tally (fcd_ctx_stat "tally_f_in_pack")
     long long n_r_tally;           // pipelined r pass launches that carried it (fcd_ctx_stat "tally_f_in_r")
+    long long n_f_tally;           // f passes whose run kernel counted it (fcd_ctx_stat "tally_f_in_f")
     long long n_frec_pass;         // f passes that read prebuilt pair records (fcd_ctx_stat "f_rec_passes")
     long long n_frec_build;        // launches of the kernel that builds them (fcd_ctx_stat "f_rec_builds")
     long long n_fsure_pass;        // f passes that ran the kernel with the decided-tile path (fcd_ctx_stat "f_sure_passes")
@@ -109,6 +114,9 @@ struct fcd_ctx {
     void *log_tab;     // K_lik tables (fcd_fastmath.h): 64 x 2^(-j/64), 512 x {1/m_i, log m_i} (device, 8.5 KiB)
     volatile unsigned *dev_err;   // pinned host word: error word of the one-launch r pass, copied back after each pass
     void *acc;         // 8 x uint64, zero between launches: the tally's pooled sums [0..3] and its ticket [4]
+    void *f_slots;     // FCD_F_SLOTS 64-byte lines of 8 x uint64, zero between sweeps: the pooled f counts of a run kernel that counts
+                       // ([0] zeros, [1] ones, [2] twos of a line), spread so that its workgroups do not queue on acc's line;
+                       // folded into acc[1..3] by the r pass behind it (fcd_f_slots_fold)
     void *nan_slots;   // FCD_NAN_SLOTS 128-byte lines of 16 x uint64, zero between launches: K_lik's per-block NaN counts
                        // ([0] b, [1] bt of a line), spread so that its blocks do not queue on one address
     void *comm;        // ncclComm_t of the context (fcd_comm_init), or nullptr: fcd_gibbs_run pools its M-step counts over it
@@ -252,7 +260,9 @@ static inline int fcd_lds_attr(fcd_ctx *ctx, int slot, const void *fn, size_t sh
     return FCD_OK;
 }
 // The f half of the tally (pooled counts of f, marginal counters of the edges): it needs nothing of the r pass, so the r
-// pass's packing launch can carry it in extra workgroups of its own instead of the tally launch after the pass.
+// pass's packing launch can carry it in extra workgroups of its own instead of the tally launch after the pass -- and the f
+// pass's run kernel can leave the same sums as it stores the draws, without reading the state back (cnt_f: atomic adds; the
+// pooled sums through the slot lines of fcd_f_slots_fold, not into acc's one line).
 struct fcd_tally_f {
     const uint8_t *f_state;
     int64_t C, G;
@@ -533,6 +543,22 @@ __device__ __forceinline__ uint32_t fcd_wave_sum4(const uint32_t (&p)[4], int la
 // launches that count follow each other in one stream -- so the twelve words cnt_f[3 c0 .. 3 c0 + 11] are read, added to
 // and stored by lanes 0 .. 11, the old values asked for together with the f state.  (They were four atomics per edge from
 // lane 0.)
+// The pooled f counts of a run kernel that counts (fcd_gibbs.hip, gibbs_f_run_kernel): every workgroup adds its three sums to
+// one of FCD_F_SLOTS lines instead of acc's one -- same-address atomics serialise at the memory side, about 80 per us, and 4200
+// of them at cfg3 made the kernel 26 us longer (profiles/f_run_counts_cfg3.txt).  ONE wave of a later launch in the stream,
+// before the tally, takes the lines (and leaves them zero) and adds the totals to acc[1..3]: three atomics in all.
+__device__ __forceinline__ void fcd_f_slots_fold(unsigned long long *slots, unsigned long long *acc, int lane) {
+    static_assert(FCD_F_SLOTS == 64, "one line per lane");
+    unsigned long long v[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] = atomicExch(&slots[lane * 8 + k], 0ull);     // (read at the memory side and reset)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+        if (lane == 0 && v[k]) (void)__hip_atomic_fetch_add(acc + 1 + k, v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 template <int WAVES>
 __device__ __forceinline__ void fcd_tally_f_block(const fcd_tally_f &a, int lin, int nblk, unsigned long long (*red)[3]) {
     const uint8_t *__restrict__ f_state = a.f_state;
@@ -788,14 +814,15 @@ struct fcd_sweep_step {
     bool ru_ready;                 // f pass: the previous sweep's tally has made the slot words
     const void *f_rec;             // f pass (f_packed): pair records made for this call, or nullptr (the tiles build their own)
     bool sentinels_in_place;       // r pass: P holds the sentinels a COMPLETED pipelined pass of this shape left behind
-    const fcd_tally_f *tally_f;    // r pass: the f half of the tally to carry in the packing launch or in the pipelined launch, or
-    bool tally_f_done;             // nullptr ... and whether one of them did (out)
+    const fcd_tally_f *tally_f;    // f and r pass: the f half of the tally to carry in the run kernel, the packing launch or the
+    bool tally_f_done;             // pipelined launch, or nullptr ... and whether one of them did (cleared by the sweep loop, set by the carrier)
+    bool f_fold;                   // r pass: the run kernel has left the pooled f counts in fcd_ctx::f_slots; fold them into acc
     bool r_flip;                   // r pass: the two r-word buffers of the plan have swapped roles (r_S lies at pl.r_Sn, r_Sn at pl.r_S)
     bool f_sure;                   // f pass (f_rec): some tile of the call's table has all its edges decided (fcd_ctx::f_sure_hint)
     bool f_all;                    // ... and every tile has: the decided path runs in its run form (gibbs_f_run_kernel)
     bool r_sure;                   // r pass: the sparse form (the call's site bounds are built and the rule of the knob r_sure chose it)
 };
-int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step &st);   // fcd_gibbs.hip
+int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st);         // fcd_gibbs.hip
 int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st);         // fcd_gibbs_r.hip
 // Decided sites of the r pass (fcd_gibbs_r.hip, gibbs_r_sparse_kernel).  With the edge modes k* of fcd_f_edge_mode at the call's
 // starting hyper and T - FCD_F_SURE_DRIFT, the log-odds of r_nu = 1 are  off + sum_{m != n} lMd[u][n][m][f_nm][r_m],

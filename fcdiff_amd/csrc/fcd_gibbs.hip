@@ -1017,6 +1017,8 @@ __global__ void gibbs_f_hint_kernel(unsigned *__restrict__ any_tile, volatile un
 // words of the present edges against fcd_draw_f_sure's range.  An edge the rule leaves open, or for which some lane of THIS wave is out of
 // range, is drawn by this wave as gibbs_f_pair_kernel draws it (fcd_f_run_edge); every other edge gets its mode, which is
 // what that kernel gives every (wave, edge) without an out-of-range lane, on either of its paths.
+// Given slots or cnt_f it also counts what it stores -- the f half of the sweep's tally (knob tally_in_f; DESIGN.md, "The f
+// counts in the run kernel"): with both null it does what it did before.
 // ---------------------------------------------------------------------------------------------
 // One edge's draw for the whole wave, as the term loop of gibbs_f_pair_kernel and what follows it make it: the fp32 sums in
 // that loop's order (full groups of eight pairs: even pairs into acc, odd pairs into acc1, the sums starting from the first
@@ -1091,10 +1093,15 @@ __global__ __launch_bounds__(64 * FR_WAVES) void gibbs_f_run_kernel(const double
                                                            uint32_t chain0, uint64_t seed, uint32_t sweep, float margin,
                                                            uint2 *__restrict__ f_S, int NBLK, unsigned long long *__restrict__ dbg,
                                                            const char *__restrict__ frec, const double *__restrict__ lM, int n_tiles,
-                                                           unsigned *__restrict__ votes) {
+                                                           unsigned *__restrict__ votes, int64_t G,
+                                                           unsigned long long *__restrict__ slots, uint32_t *__restrict__ cnt_f) {
     static_assert(16 % FR_WAVES == 0, "a workgroup's chain words lie in one group of 16");
     static_assert(FR_W == R_NB && FR_W == 16 && FT_W == 4, "a run is one block of the r pass's f words: sixteen columns, four tiles");
     __shared__ uint32_t vote[FR_WAVES];  // per wave: the run's tiles (bit q) in which some lane's uniform is out of range
+    // per wave and edge (slots or cnt_f given: this launch counts f, the f half of the sweep's tally): the edge's ones | twos << 16
+    // over the wave's valid chains -- at most 64 each
+    __shared__ uint32_t pairs[FR_WAVES][2 * FR_W];
+    const bool counting = slots != nullptr || cnt_f != nullptr;       // (kernel arguments: wave-uniform)
     const int NPAIR = (U + 1) >> 1;
     const fpr_run R = fpr_locate((int)blockIdx.x, Nreg);
     const int lane = threadIdx.x & 63;
@@ -1180,6 +1187,26 @@ __global__ __launch_bounds__(64 * FR_WAVES) void gibbs_f_run_kernel(const double
                 else K0 = (K0 & ~(3u << (2 * j))) | (k << (2 * j));
             }
         }
+        if (counting) {
+            // The f half of the tally, from what this wave is about to store: an edge outside X has its mode in every lane,
+            // so its count is the word's valid chains on the side the mode names -- wave-uniform numbers, no ballot; an edge
+            // of X has per-lane draws, final in K0 / K1 (after the fp64 repeat and the open-edge draw), and is counted
+            // there.  Lane e < 32 takes edge e's pair.
+            const uint64_t act = fcd_active_mask(w, G);
+            const uint32_t nvalid = (uint32_t)__popcll(act);
+            uint32_t pair = 0;
+            if (lane < 2 * FR_W) pair = ((m1 >> lane) & 1u) ? nvalid : (((m2 >> lane) & 1u) ? nvalid << 16 : 0u);
+            uint32_t x = X;
+#pragma unroll 1
+            while (x != 0u) {
+                const int e = __builtin_ctz(x);
+                x &= x - 1u;
+                const uint32_t k = (((e >> 4) ? K1 : K0) >> (2 * (e & (FR_W - 1)))) & 3u;
+                const uint32_t n1 = (uint32_t)__popcll(__ballot(k == 1u) & act), n2 = (uint32_t)__popcll(__ballot(k == 2u) & act);
+                if (lane == e) pair = n1 | (n2 << 16);
+            }
+            if (lane < 2 * FR_W) pairs[wv][lane] = pair;
+        }
         // f_state: the edges of a row are consecutive 64-byte lines.  A row without an exceptional edge: lane l writes 16 bytes
         // of edge l / 4 (its mode in every chain), one store; any other row edge by edge, a byte per lane.
 #pragma unroll
@@ -1235,6 +1262,41 @@ __global__ __launch_bounds__(64 * FR_WAVES) void gibbs_f_run_kernel(const double
         if (oe & (0x000F000Fu << (FT_W * q))) ot |= 1u << q;
     if (lane == 0) vote[wv] = ot;
     __syncthreads();
+    if (counting && wv == (int)(blockDim.x >> 6) - 1) {
+        // the waves' rows summed, one edge per lane (the workgroup's last wave: the first has the votes); the workgroups of
+        // the other chain words meet the same edges, so the counters take atomic adds -- none returns, none adds zero
+        const int w0 = (int)(blockIdx.y * (blockDim.x >> 6));
+        const int nwv = min((int)(blockDim.x >> 6), GW - w0);              // waves that hold a chain word (their rows are written)
+        const int64_t rem = G - (int64_t)w0 * 64;
+        const uint32_t nv = (uint32_t)(rem < (int64_t)nwv * 64 ? rem : (int64_t)nwv * 64);      // their valid chains
+        uint32_t sum = 0;
+        if (present)
+            for (int q = 0; q < nwv; ++q) sum += pairs[q][lane];        // (each half at most 8 x 64)
+        const uint32_t ones = sum & 0xFFFFu, twos = sum >> 16;
+        if (cnt_f && present) {
+            uint32_t *ctr = cnt_f + ((lr ? R.cr1 : R.cr0) + lj) * 3;
+            const uint32_t zeros = nv - ones - twos;
+            if (zeros) (void)__hip_atomic_fetch_add(ctr + 0, zeros, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (ones) (void)__hip_atomic_fetch_add(ctr + 1, ones, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (twos) (void)__hip_atomic_fetch_add(ctr + 2, twos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (slots) {
+            // the pooled totals (zeros, ones, twos over the present edges: what fcd_tally_f_block adds to acc[1..3]) go to
+            // one of FCD_F_SLOTS lines, one atomic each per workgroup; a wave of the r pass behind this launch folds the
+            // lines into acc (fcd_f_slots_fold).  32 edges x 512: both halves stay below 2^16
+            uint32_t tot = sum;
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o, 64);
+            if (lane == 0) {
+                unsigned long long *line = slots + ((blockIdx.x + 29u * blockIdx.y) & (FCD_F_SLOTS - 1)) * 8;
+                const unsigned long long t1 = tot & 0xFFFFu, t2 = tot >> 16;
+                const unsigned long long t0 = (unsigned long long)__popc(pm) * nv - t1 - t2;
+                if (t0) (void)__hip_atomic_fetch_add(line + 0, t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (t1) (void)__hip_atomic_fetch_add(line + 1, t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (t2) (void)__hip_atomic_fetch_add(line + 2, t2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
     if (wv == 0) {
         const uint32_t v = lane < (int)(blockDim.x >> 6) ? vote[lane & (FR_WAVES - 1)] : 0u;
         uint32_t bm = 0;
@@ -1848,10 +1910,11 @@ extern "C" int fcd_gibbs_f_step(fcd_ctx *ctx, const double *S_B, const double *l
     fcd_sweep_call c = {S_B, lM, lMf, nullptr, hyper, f_state, const_cast<uint64_t *>(r_bits) /* (read only) */, Nreg, U, G,
                         chain0, seed, FCD_EDGE_SYMMETRIC, (hipStream_t)stream};
     int rc = fcd_sweep_call_check(ctx, c, true, false, "fcd_gibbs_f_step");
-    return rc ? rc : fcd_gibbs_f_pass(ctx, c, fcd_sweep_step{sweep});
+    fcd_sweep_step st = {sweep};
+    return rc ? rc : fcd_gibbs_f_pass(ctx, c, st);
 }
 
-int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step &st) {
+int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) {
     const fcd_sweep_plan &pl = c.pl;
     const fcd_geo &g = c.g;
     const int64_t Nreg = c.Nreg, U = c.U;
@@ -1908,11 +1971,24 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, const fcd_sweep_step
             // every tile decided at the hint (or knob f_runs = 2): the decided path in block-wide runs -- no dynamic LDS
             const int rw = wpb < FR_WAVES ? wpb : FR_WAVES;
             dim3 rgrid((unsigned)fpr_runs((Nreg + 1) / 2), (unsigned)((g.GW + rw - 1) / rw));
+            // The f half of the sweep's tally rides in this launch (the kernel counts what it stores) where nothing else
+            // carries it for less: ahead of a sparse r pass, which has no packing launch and no waiting workgroups.  Knob
+            // tally_in_f: 1 = never, 2 = wherever this form runs.
+            const fcd_tally_f *tf = nullptr;
+            if (st.tally_f && !st.tally_f_done && ctx->knobs.tally_in_f != 1 && (st.r_sure || ctx->knobs.tally_in_f == 2))
+                tf = st.tally_f;
             fcd_prof_begin(ctx, FCD_PROF_F, s);
             hipLaunchKernelGGL(gibbs_f_run_kernel, rgrid, dim3(64 * rw), 0, s, c.S_B, c.lMf, c.hyper, c.f_state, r_U, (int)Nreg, (int)U, g.C,
                                g.GW, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, margin, f_S, NBLK, (unsigned long long *)ctx->dbg,
-                               (const char *)st.f_rec, c.lM, (int)grid.x, (unsigned *)((char *)st.f_rec + pl.frec_votes));
+                               (const char *)st.f_rec, c.lM, (int)grid.x, (unsigned *)((char *)st.f_rec + pl.frec_votes), c.G,
+                               (tf && tf->acc) ? (unsigned long long *)ctx->f_slots : nullptr, tf ? tf->cnt_f : nullptr);
             fcd_prof_end(ctx, FCD_PROF_F, s);
+            FCD_LAUNCH_CHECK();
+            if (tf) {           // (only now: the launch is in the stream)
+                st.tally_f_done = true;
+                st.f_fold = tf->acc != nullptr;     // (the r pass folds the pooled counts into acc: fcd_f_slots_fold)
+                ctx->n_f_tally += 1;
+            }
             ctx->n_frec_pass += 1;
             ctx->n_fsure_pass += 1;
             ctx->n_frun_pass += 1;
@@ -2211,24 +2287,29 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
             }
         }
         st.r_sure = rs_state == 2 && st.f_packed && st.r_packed;
-        int rc = fcd_gibbs_f_pass(ctx, c, st);
-        if (rc) return rc;
         const bool last = i + 1 == n_sweeps;
         const bool do_m = mstep_every > 0 && (i + 1) % mstep_every == 0;
         const bool do_a = cnt_f && st.sweep >= accumulate_from;
-        // the f half of this sweep's tally rides in the r pass's packing launch (beside it, not after the pass) where there
+        // the f half of this sweep's tally rides in the f pass's run kernel, which counts what it stores, where a sparse r
+        // pass follows (knob tally_in_f); else in the r pass's packing launch (beside it, not after the pass) where there
         // is one, else in the pipelined pass's in-order workgroups (while they wait) where the rule allows; else the tally
-        // after the pass counts it
+        // after the pass counts it.  Whoever carries it sets tally_f_done, and nobody behind it counts again.
         fcd_tally_f tf;
         tf.f_state = c.f_state; tf.C = g.C; tf.G = G; tf.GW = g.GW;
         tf.acc = (do_m || (last && counts)) ? (unsigned long long *)ctx->acc : nullptr;
         tf.cnt_f = do_a ? cnt_f : nullptr;
         st.tally_f = (tf.acc || tf.cnt_f) ? &tf : nullptr;
+        st.tally_f_done = false;
+        st.f_fold = false;
+        int rc = fcd_gibbs_f_pass(ctx, c, st);
+        if (rc) return rc;      // (the run kernel's launch is the pass's last step: a pass that fails has counted nothing)
         rc = fcd_gibbs_r_pass(ctx, c, st);
         if (rc) {
-            // the packing launch (or a pipelined pass) may already have added this sweep's f counts into the context's accumulators and no tally
+            // the run kernel, the packing launch or a pipelined pass may already have added this sweep's f counts into the context's accumulators and no tally
             // will draw the ticket that zeroes them: leave them clean for the next call
             if (tf.acc) (void)hipMemsetAsync(ctx->acc, 0, 8 * sizeof(unsigned long long), s);
+            // (... and a run kernel that counted has left them in its slot lines if the pass failed before it folded them)
+            if (st.f_fold) (void)hipMemsetAsync(ctx->f_slots, 0, FCD_F_SLOTS * 8 * sizeof(unsigned long long), s);
             return rc;
         }
         st.sentinels_in_place = pair_form && ctx->r_form_last == 2;        // (a pipelined pass has just been queued)

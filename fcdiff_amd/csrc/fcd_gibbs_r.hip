@@ -1435,6 +1435,8 @@ struct r_sparse_args {
     uint64_t *visit;                // (GW, Nreg)
     uint32_t *fneq;                 // (GW, Nreg): row flag, or the f words differ from the mode words in some chain
     unsigned long long *cnt;        // [0] items left to the tables, [1] decided items evaluated in full
+    unsigned long long *fold_slots; // nullable: the pooled f counts the f pass's run kernel left in fcd_ctx::f_slots ...
+    unsigned long long *fold_acc;   // ... which one wave of the range kernel folds into the context's sums (fcd_f_slots_fold)
     int Nreg, U, NBLK, GW;
     int64_t G;
     uint32_t chain0, sweep;
@@ -1542,11 +1544,19 @@ __global__ void gibbs_r_hint_kernel(unsigned long long *__restrict__ n_decided, 
                        __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// the pooled f counts of a run kernel that counted, folded into acc ahead of an r pass that is not sparse (knob tally_in_f = 2
+// only: under the auto rule the sparse pass's range kernel folds them)
+__global__ __launch_bounds__(64) void gibbs_f_fold_kernel(unsigned long long *slots, unsigned long long *acc) {
+    fcd_f_slots_fold(slots, acc, (int)threadIdx.x);
+}
+
 // grid (ceil(Nreg / RS_WAVES), GW): wave = (w, n)
 __global__ __launch_bounds__(64 * RS_WAVES) void gibbs_r_range_kernel(const r_sparse_args a) {
     __shared__ unsigned red[2];
     if (threadIdx.x < 2) red[threadIdx.x] = 0u;
     __syncthreads();
+    // (the first wave of the launch, before its own work: the round trip runs under it; the tally is the launch after the walk)
+    if (a.fold_slots && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) fcd_f_slots_fold(a.fold_slots, a.fold_acc, (int)threadIdx.x);
     const int lane = threadIdx.x & 63;
     const int n = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * RS_WAVES + (threadIdx.x >> 6)));
     const int w = (int)blockIdx.y;
@@ -2090,8 +2100,14 @@ int fcd_gibbs_r_bounds_build(fcd_ctx *ctx, const fcd_sweep_call &c) {
 }
 
 int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) {
-    st.tally_f_done = false;
+    // (st.tally_f_done: the sweep loop clears it before the f pass, whose run kernel may have counted f already)
     if (ctx->dev_err && *ctx->dev_err) return fcd_fail(ctx, FCD_ERR_DEVICE, "r pass: a device-side wait was abandoned in an earlier call");
+    if (st.f_fold && !st.r_sure) {
+        // (the pooled f counts of a run kernel that counted: the sparse form folds them in its range kernel, the others here)
+        hipLaunchKernelGGL(gibbs_f_fold_kernel, dim3(1), dim3(64), 0, c.s, (unsigned long long *)ctx->f_slots, (unsigned long long *)ctx->acc);
+        FCD_LAUNCH_CHECK();
+        st.f_fold = false;
+    }
     const fcd_sweep_plan &pl = c.pl;
     const fcd_geo &g = c.g;
     const int64_t Nreg = c.Nreg, U = c.U;
@@ -2139,7 +2155,8 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
     if (ctx->knobs.r_tol > a.tol) a.tol = ctx->knobs.r_tol;   // test hook: a huge value sends every draw through the exact path
     if (st.r_sure) {
         // the sparse form: the f and r words are in their final form (the sweep loop asks for it only then), the marks stay
-        // cleared, the panel buffers are not touched; the tally after the pass counts f
+        // cleared, the panel buffers are not touched; the f pass before it has counted f (knob tally_in_f), else the tally
+        // after the pass does
         if (!pl.rs_bytes || !st.f_packed || !st.r_packed) return fcd_fail(ctx, FCD_ERR_ARG, "r pass: sparse form without its tables");
         r_sparse_args q;
         q.lMd = c.lMd; q.hyper = c.hyper; q.f_S = f_S; q.r_Sn = a.r_Sn; q.r_bits = c.r_bits;
@@ -2147,6 +2164,8 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         q.mword = (const uint2 *)(ws + pl.rs_mword); q.rowflag = (const uint32_t *)(ws + pl.rs_rowflag);
         q.visit = (uint64_t *)(ws + pl.rs_visit); q.fneq = (uint32_t *)(ws + pl.rs_fneq);
         q.cnt = (unsigned long long *)ctx->dbg + 8;
+        q.fold_slots = st.f_fold ? (unsigned long long *)ctx->f_slots : nullptr;
+        q.fold_acc = (unsigned long long *)ctx->acc;
         q.Nreg = (int)Nreg; q.U = (int)U; q.NBLK = NBLK; q.GW = g.GW; q.G = c.G;
         q.chain0 = a.chain0; q.sweep = a.sweep; q.seed = a.seed;
         q.tol = a.tol;
@@ -2157,6 +2176,7 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         hipLaunchKernelGGL(gibbs_r_sparse_kernel, dim3((unsigned)(U * g.GW)), dim3(64), rs_walk_lds(NBLK), s, q);
         fcd_prof_end(ctx, FCD_PROF_RSTEP, s);
         FCD_LAUNCH_CHECK();
+        st.f_fold = false;
         ctx->r_form_last = 4;
         ctx->n_rsure_pass += 1;
         return FCD_OK;
@@ -2211,7 +2231,8 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         tf.f_state = nullptr; tf.C = 0; tf.G = 0; tf.GW = 0; tf.acc = nullptr; tf.cnt_f = nullptr;
         // (only where the f state is small beside the packing's own work: at cfg5 -- 79 800 edges x 16 chain words -- the extra
         // rows cost the launch 66 us for 16 us saved in the tally after the pass: profiles/r03_kernel_stats_cfg5.txt)
-        if (st.tally_f && g.C * g.GW <= 600000) {
+        bool carried = false;
+        if (st.tally_f && !st.tally_f_done && g.C * g.GW <= 600000) {
             tf = *st.tally_f;
             const int64_t per_row = (int64_t)pgrid.x * pgrid.z;
             int64_t want = (g.C + 15) / 16;                       // workgroups of one round
@@ -2220,7 +2241,7 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
             if (ty < 1) ty = 1;
             if (pgrid.y + ty <= 65535) {
                 pgrid.y += (unsigned)ty;
-                st.tally_f_done = true;
+                carried = true;
             } else {
                 tf.f_state = nullptr;
             }
@@ -2235,7 +2256,10 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         fcd_prof_end(ctx, FCD_PROF_PACK, s);
         FCD_LAUNCH_CHECK();
         ctx->n_pack += 1;
-        if (st.tally_f_done) ctx->n_pack_tally += 1;
+        if (carried) {
+            st.tally_f_done = true;
+            ctx->n_pack_tally += 1;
+        }
     }
     ctx->r_form_last = pipe ? 2 : 1;
     if (pipe) {

@@ -149,6 +149,9 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
  *               have 16 waves and a wave walks at most "tally_in_r_max_rounds" rounds of four edges (cfg3: 4 rounds), 1 = never
  *               (the tally launch after the pass counts f), 2 = wherever the workgroups have 16 waves.  The packing launch
  *               of a call's first sweep keeps the f half it carries (stat "tally_f_in_pack"); the step-per-launch form carries none
+ *   "tally_in_f" the f half of a sweep's tally counted by the f pass's run kernel as it stores its draws (no pass reads the f
+ *               state back): 0 = in sweeps whose r pass is sparse (nothing else then carries it), 1 = never, 2 = wherever the
+ *               run form runs (tests).  Not read from the environment
  *   "r_keep_words" 1: the tally makes the next r pass's r words from the r bits (default: inside a fcd_gibbs_run /
  *               fcd_gibbs_sweeps call the pass's two r-word buffers swap roles from sweep to sweep -- the words a pass wrote
  *               are the next pass's -- and the tally only clears the marks)
@@ -164,6 +167,7 @@ int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value);
  * the last blocked r pass ran in (1 one launch per block step, 2 pipelined one-launch form, 3 one-launch form with
  * counters); "pack_launches" = packing launches of the r pass made so far; "tally_f_in_pack" = those of them that also
  * carried the f half of the sweep's tally; "tally_f_in_r" = launches of the pipelined r pass that carried it,
+ * "tally_f_in_f" = f passes whose run kernel counted it (knob tally_in_f; no sweep is counted by two of the three),
  * "tally_in_r_max_rounds" = the threshold of knob tally_in_r = 0; "f_rec_passes" = f passes that read prebuilt pair records, "f_rec_builds" =
  * launches of the kernel that makes them, "f_rec_bytes" = the size of their table, "f_rec_min_sweeps" = the threshold of
  * knob f_records = 0; "f_sure_passes" = f passes that ran a kernel with the decided-tile path, "f_run_passes" = those of them in

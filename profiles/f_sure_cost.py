@@ -57,7 +57,7 @@ def main():
             return ctx.stat(name)
         except Exception:      # noqa: BLE001  (a build from before the counters)
             return None
-    names = ("f_rec_passes", "f_sure_passes", "f_run_passes", "f_sure_tiles", "f_sure_fallbacks", "f_repeats")
+    names = ("f_rec_passes", "f_sure_passes", "f_run_passes", "f_sure_tiles", "f_sure_fallbacks", "f_repeats", "tally_f_in_f")
     s0 = [stat(k) for k in names]
     ms = []
     sweep = 64
