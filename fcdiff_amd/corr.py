@@ -48,7 +48,13 @@ def _check_clean_shapes(ts, confounds, frame_mask):
 def _device_f64(x, ctx):
     import torch
     t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=ctx.device)
-    return t.to(device=ctx.device, dtype=torch.float64).contiguous()
+    return _aligned16(t.to(device=ctx.device, dtype=torch.float64).contiguous())
+
+
+def _aligned16(t):
+    """t, or a copy of it where t is a view that starts off a 16-byte boundary (a caller's slice of a flat buffer): the
+    correlation kernels read the rows of an even-T series 16 bytes at a time and the library refuses such a pointer."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 def _clean_device(ts, confounds, frame_mask, ctx):
@@ -182,8 +188,7 @@ def correlations(ts, fisher_z=False, ctx=None, as_numpy=True, *, confounds=None,
     if cleaning:
         (t, info) = _clean_device(ts, confounds, frame_mask, ctx)
     else:
-        t = ts if isinstance(ts, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(ts, dtype=np.float64), device=ctx.device)
-        t = t.to(device=ctx.device, dtype=torch.float64).contiguous()
+        t = _device_f64(ts, ctx)
     if t.dim() != 3:
         raise ValueError("ts must have shape (S, Nreg, T)")
     (S, Nreg, T) = (int(t.shape[0]), int(t.shape[1]), int(t.shape[2]))

@@ -188,6 +188,17 @@ static inline int fcd_fail_who(fcd_ctx *ctx, int code, const char *who, const ch
     }
     return code;
 }
+// The alignment contract of include/fcdiff_hip.h: a device pointer whose kernels read or write it as 16-byte vectors must be
+// 16-byte aligned (DESIGN.md has the table of them).  Checked on the host before any launch; a null pointer passes (an
+// entry point refuses or accepts a null argument by its own rules).
+static inline int fcd_fail_align16(fcd_ctx *ctx, const char *who, const char *name) {
+    if (ctx) snprintf(ctx->msg, sizeof(ctx->msg), "%s: argument %s must be 16-byte aligned", who, name);
+    return FCD_ERR_ARG;
+}
+#define FCD_ALIGN16(ctx, who, name, ptr)                                                         \
+    do {                                                                                         \
+        if ((uintptr_t)(const void *)(ptr) & 15u) return fcd_fail_align16((ctx), (who), (name)); \
+    } while (0)
 
 // What the fcd_gibbs_set_*_accumulator entry points share: all buffers null detaches, else the checks and the store.  The
 // message texts are the caller's (fcd_fail formats numbers only); msg_limit is non-null where the shape is past a limit of

@@ -480,6 +480,8 @@ int fcd_corr_edges_at(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, i
     if (!ctx || !ts || !out) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_corr_edges: null pointer");
     if (S < 1 || Nreg < 2 || T < 2) return fcd_fail(ctx, FCD_ERR_SHAPE, "need S >= 1, Nreg >= 2, T >= 2 (Nreg=%lld, T=%lld)", Nreg, T);
     if (S > 65535 || Nreg > 46340 || T > INT32_MAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_corr_edges: shape too large");
+    // T even: both Gram kernels stage a row as double2 (odd T takes their 8-byte path, rows start 8 bytes off anyway)
+    if ((T & 1) == 0) FCD_ALIGN16(ctx, "fcd_corr_edges", "ts", ts);
     const int64_t rows = S * Nreg, C = fcd_tri(Nreg);
     hipStream_t s = stream;
     if ((S + 31) / 32 > 65535) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_corr_edges: grid too large");

@@ -488,6 +488,7 @@ extern "C" int fcd_corr_partial(fcd_ctx *ctx, const double *ts, int64_t S, int64
     if (Nreg > 1024) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_corr_partial: %lld regions, at most 1024", Nreg);
     if (Nreg < 2 || T < 2) return fcd_fail(ctx, FCD_ERR_SHAPE, "need S >= 1, Nreg >= 2, T >= 2 (Nreg=%lld, T=%lld)", Nreg, T);
     if (S > 65535 || T > INT32_MAX) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "fcd_corr_partial: shape too large");
+    if ((T & 1) == 0) FCD_ALIGN16(ctx, "fcd_corr_partial", "ts", ts);          // fcd_corr_edges' kernels read its rows as double2
     hipStream_t st = (hipStream_t)stream;
     const int64_t C = fcd_tri(Nreg);
     const int RT = (int)((Nreg + PNB - 1) / PNB), PL = RT * PNB;

@@ -454,6 +454,7 @@ int tg_check(fcd_ctx *ctx, const fcd_tangent_desc *d, const char *who) {
     if (d->Nreg > 1024) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "%lld regions, at most 1024", d->Nreg);
     if (d->Nreg < 2 || d->T < 2) return fcd_fail_who(ctx, FCD_ERR_SHAPE, who, "need Nreg >= 2, T >= 2 (Nreg=%lld, T=%lld)", d->Nreg, d->T);
     if (d->S > 65535 || d->T > INT32_MAX) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "shape too large (S=%lld, T=%lld)", d->S, d->T);
+    if ((d->T & 1) == 0) FCD_ALIGN16(ctx, who, "ts", d->ts);          // fcd_corr_edges' kernels read its rows as double2
     return FCD_OK;
 }
 

@@ -1898,6 +1898,10 @@ int fcd_sweep_call_check(fcd_ctx *ctx, fcd_sweep_call &c, bool f_pass, bool r_pa
         snprintf(ctx->msg, sizeof(ctx->msg), null ? "%s: null pointer" : "%s: bad edge_mode", who);
         return FCD_ERR_ARG;
     }
+    // the passes read and write 16 bytes of an f_state line per lane and take the difference tables as double2
+    FCD_ALIGN16(ctx, who, "f_state", c.f_state);
+    FCD_ALIGN16(ctx, who, "lMf", c.lMf);
+    FCD_ALIGN16(ctx, who, "lMd", c.lMd);
     if (r_pass && c.edge_mode == FCD_EDGE_REFERENCE && c.Nreg == 2)
         return fcd_fail(ctx, FCD_ERR_INDEX, "reference edge ids: index 1 is out of bounds for axis 0 with size 1 (Nreg=2)");
     c.pl = fcd_sweep_plan_for(ctx, c.Nreg, c.U, c.g.GW);
@@ -2096,6 +2100,7 @@ extern "C" int fcd_gibbs_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint6
     int rc = fcd_geo_check(ctx, Nreg, U, G, 0, g);
     if (rc) return rc;
     if (!f_state || !r_bits) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_tally: null pointer");
+    FCD_ALIGN16(ctx, "fcd_gibbs_tally", "f_state", f_state);          // gibbs_tally_kernel reads 16 bytes of a line per lane
     if ((cnt_f == nullptr) != (cnt_r == nullptr)) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_tally: cnt_f and cnt_r go together");
     if (!counts && !cnt_f) return FCD_OK;
     return launch_tally(ctx, f_state, r_bits, Nreg, U, G, g, counts, cnt_f, cnt_r, nullptr, nullptr, 0, (hipStream_t)stream);
@@ -2108,6 +2113,7 @@ extern "C" int fcd_gibbs_stats(fcd_ctx *ctx, const uint8_t *f_state, const uint6
     int rc = fcd_geo_check(ctx, Nreg, U, G, 0, g);
     if (rc) return rc;
     if (!f_state || !r_bits || !counts) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_stats: null pointer");
+    FCD_ALIGN16(ctx, "fcd_gibbs_stats", "f_state", f_state);          // gibbs_tally_kernel reads 16 bytes of a line per lane
     return launch_tally(ctx, f_state, r_bits, Nreg, U, G, g, counts, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
@@ -2118,6 +2124,7 @@ extern "C" int fcd_gibbs_accumulate(fcd_ctx *ctx, const uint8_t *f_state, const 
     int rc = fcd_geo_check(ctx, Nreg, U, G, 0, g);
     if (rc) return rc;
     if (!f_state || !r_bits || !cnt_f || !cnt_r) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_gibbs_accumulate: null pointer");
+    FCD_ALIGN16(ctx, "fcd_gibbs_accumulate", "f_state", f_state);          // gibbs_tally_kernel reads 16 bytes of a line per lane
     return launch_tally(ctx, f_state, r_bits, Nreg, U, G, g, nullptr, cnt_f, cnt_r, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 

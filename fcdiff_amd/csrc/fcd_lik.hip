@@ -235,6 +235,7 @@ extern "C" int fcd_lik_tables_ex(fcd_ctx *ctx, const double *b, const double *bt
                                  const double *theta, double *S_B, double *lM, double *lp_B_g_F, double *p_Bt_g_Ft,
                                  int flags, int64_t *n_missing2, fcd_stream stream) {
     if (!ctx || !b || !bt || !theta || !S_B || !lM) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_lik_tables: null pointer");
+    FCD_ALIGN16(ctx, "fcd_lik_tables", "lM", lM);          // lik_kernel stores it as double2
     if (flags & ~FCD_DATA_NAN_MISSING) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_lik_tables_ex: unknown flags 0x%x", flags);
     const bool missing = (flags & FCD_DATA_NAN_MISSING) != 0;
     if (n_missing2 && !missing)

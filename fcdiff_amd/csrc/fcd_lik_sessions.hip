@@ -805,6 +805,7 @@ extern "C" int fcd_lik_tables_sessions(fcd_ctx *ctx, const double *b, const doub
                                        const double *theta, double *S_B, double *lM, double *lp_B_g_F, int flags,
                                        int64_t *n_missing2, fcd_stream stream) {
     if (!ctx || !b || !bt || !theta || !S_B || !lM) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_lik_tables_sessions: null pointer");
+    FCD_ALIGN16(ctx, "fcd_lik_tables_sessions", "lM", lM);          // lik_sessions_kernel stores it as double2
     int rc = sess_check(ctx, "sessions tables", false, C, H, U, K, flags, n_missing2 != nullptr);
     if (rc) return rc;
     LikTheta th;
@@ -835,6 +836,7 @@ extern "C" int fcd_lik_tables_noise(fcd_ctx *ctx, const double *b, const double 
                                     const double *theta, const double *var_b, const double *var_bt, double *S_B, double *lM,
                                     double *lp_B_g_F, int flags, int64_t *n_missing2, fcd_stream stream) {
     if (!ctx || !b || !bt || !theta || !S_B || !lM) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_lik_tables_noise: null pointer");
+    FCD_ALIGN16(ctx, "fcd_lik_tables_noise", "lM", lM);
     int rc = sess_check(ctx, "noise tables", true, C, H, U, K, flags, n_missing2 != nullptr);
     if (rc) return rc;
     LikTheta th;

@@ -252,6 +252,7 @@ extern "C" int fcd_score_ais_step(fcd_ctx *ctx, const double *lM, const uint8_t 
     int rc = fcd_geo_check(ctx, Nreg, U, G, 0, g);
     if (rc) return rc;
     if (!lM || !f_state || !r_bits || !w) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_score_ais_step: null pointer");
+    FCD_ALIGN16(ctx, "fcd_score_ais_step", "f_state", f_state);          // score_ais_kernel stages its lines as 32-bit words
     if (lM_beta == w || (const double *)lM_beta == lM)
         return fcd_fail(ctx, FCD_ERR_ARG, "fcd_score_ais_step: lM_beta must not alias lM or w");
     const int NW = (int)(U < AIS_MAX_WAVES ? U : AIS_MAX_WAVES);

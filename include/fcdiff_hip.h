@@ -31,6 +31,37 @@
  * Chain state of the Gibbs sampler, G chains padded to GW = ceil(G/64) words of 64 chains:
  *   f_state  (GW, C, 64)   uint8 in {0,1,2}: f_c of chain 64*w + lane at [(w*C + c)*64 + lane]
  *   r_bits   (GW, Nreg, U) uint64: bit `lane` of [(w*Nreg + n)*U + u] is r_{n,u} of chain 64*w+lane
+ *
+ * ALIGNMENT of device pointers.  Every device pointer must be aligned to its element type (8 bytes for double, int64_t
+ * and uint64_t, 4 for the 32-bit types, 2 for uint16_t).  The pointers listed below must be 16-byte aligned as well: their
+ * kernels read or write them as 16-byte (f_state in two places: 4-byte) vectors, and nothing narrower is built.  A
+ * violation is refused on the host, before any launch, with FCD_ERR_ARG and the message
+ * "<entry point>: argument <name> must be 16-byte aligned"; a null pointer passes this check (each entry point says which
+ * of its pointers may be null).  A buffer from hipMalloc or from PyTorch's allocator always qualifies; a slice of one, or
+ * a table packed into an arena at an odd number of doubles, may not.  DESIGN.md ("Alignment of caller pointers") has the
+ * access behind every line, and tests/test_alignment_contract.py reads this list:
+ *   align16: fcd_lik_tables(lM)
+ *   align16: fcd_lik_tables_ex(lM)
+ *   align16: fcd_lik_tables_sessions(lM)
+ *   align16: fcd_lik_tables_noise(lM)
+ *   align16: fcd_corr_edges(ts)                           when T is even
+ *   align16: fcd_corr_partial(ts)                         when T is even
+ *   align16: fcd_tangent_fit(ts)                          when T is even
+ *   align16: fcd_tangent_apply(ts)                        when T is even
+ *   align16: fcd_gibbs_f_step(f_state, lMf)
+ *   align16: fcd_gibbs_r_step(f_state, lMd)
+ *   align16: fcd_gibbs_sweeps(f_state, lMf, lMd)
+ *   align16: fcd_gibbs_run(f_state, lMf, lMd)
+ *   align16: fcd_gibbs_tally(f_state)
+ *   align16: fcd_gibbs_stats(f_state)
+ *   align16: fcd_gibbs_accumulate(f_state)
+ *   align16: fcd_score_ais_step(f_state)
+ * Three entry points choose their path by the address and take element-aligned pointers at full correctness, 16-byte
+ * ones faster; their own comments say so:
+ *   by-address: fcd_edge_cov_apply(x, out)
+ *   by-address: fcd_site_harmonize_apply(x, out)
+ *   by-address: fcd_evidence_temper(src, dst)
+ * Every other pointer of every entry point is read and written one element at a time.
  */
 #ifndef FCDIFF_HIP_H
 #define FCDIFF_HIP_H
@@ -240,7 +271,8 @@ int fcd_hyper_set(fcd_ctx *ctx, double *hyper, const double *gamma3_host, const 
  * Same arithmetic as the reference: linear-space Normal densities, M_kl = eps_l N_k +
  * (1-eps_l)/2 sum_{j!=k} N_j, lM = log M (so a fully underflowed density gives -inf exactly as
  * there).  lp_B_g_F (C,H,3) and p_Bt_g_Ft (C,U,3) are written only when non-NULL (the fit path
- * never reads them; the Python mirror exposes them lazily). */
+ * never reads them; the Python mirror exposes them lazily).
+ * Alignment: lM must be 16-byte aligned (ALIGNMENT, top of this file). */
 int fcd_lik_tables(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
                    const double *theta12_host, double *S_B, double *lM, double *lp_B_g_F,
                    double *p_Bt_g_Ft, fcd_stream stream);
@@ -248,7 +280,8 @@ int fcd_lik_tables(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, i
  * exactly at a NaN bt[c,u]; lp_B_g_F holds 0.0 at a NaN b and p_Bt_g_Ft 1.0 at a NaN bt.  n_missing2 (device, int64[2],
  * may be NULL; only with the flag) receives {number of NaN in b, number of NaN in bt}, counted by
  * the table kernel (one atomic per block, into the context's slots) and written by one more small launch on `stream`.
- * Asynchronous like every table build. */
+ * Asynchronous like every table build.
+ * Alignment: lM must be 16-byte aligned (ALIGNMENT, top of this file). */
 int fcd_lik_tables_ex(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U,
                       const double *theta12_host, double *S_B, double *lM, double *lp_B_g_F, double *p_Bt_g_Ft,
                       int flags, int64_t *n_missing2, fcd_stream stream);
@@ -278,7 +311,8 @@ int fcd_lik_shared_tables(fcd_ctx *ctx, const double *b, const double *bt, int64
  * fcd_lik_shared_tables_sessions: S_B and L (C,3,3), L[c] = sum_u lM[c,u] in fcd_lik_shared_tables' fixed order.
  * fcd_conn_posterior_sessions: fcd_conn_posterior_ex with the densities of an item taken over its sessions; an item with
  * no observed session gets the prior law of T and F~ given (k, l).
- * All three refuse K < 1 (FCD_ERR_ARG), K > INT32_MAX (FCD_ERR_UNSUPPORTED), unknown flags and what their siblings refuse. */
+ * All three refuse K < 1 (FCD_ERR_ARG), K > INT32_MAX (FCD_ERR_UNSUPPORTED), unknown flags and what their siblings refuse.
+ * Alignment: lM must be 16-byte aligned (ALIGNMENT, top of this file). */
 int fcd_lik_tables_sessions(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U, int64_t K,
                             const double *theta12_host, double *S_B, double *lM, double *lp_B_g_F, int flags,
                             int64_t *n_missing2, fcd_stream stream);
@@ -308,7 +342,8 @@ int fcd_conn_posterior_sessions(fcd_ctx *ctx, const double *bt, int64_t Nreg, in
  * fcd_lik_shared_tables_noise: S_B and L (C,3,3) = sum_u lM[c,u]; the per-patient table is never written.
  * fcd_conn_posterior_noise: fcd_conn_posterior_sessions with the densities of these variances.
  * Refusals as the sessions entry points: K < 1 FCD_ERR_ARG, non-triangular C FCD_ERR_SHAPE, K > INT32_MAX or
- * U*K > 2^31 FCD_ERR_UNSUPPORTED, unknown flags FCD_ERR_ARG. */
+ * U*K > 2^31 FCD_ERR_UNSUPPORTED, unknown flags FCD_ERR_ARG.
+ * Alignment: lM must be 16-byte aligned (ALIGNMENT, top of this file). */
 int fcd_lik_tables_noise(fcd_ctx *ctx, const double *b, const double *bt, int64_t C, int64_t H, int64_t U, int64_t K,
                          const double *theta12_host, const double *var_b, const double *var_bt, double *S_B, double *lM,
                          double *lp_B_g_F, int flags, int64_t *n_missing2, fcd_stream stream);
@@ -383,7 +418,8 @@ int fcd_model_sample_shared(fcd_ctx *ctx, const double *theta12_host, int64_t Nr
  * Not in the reference (its inputs are already correlations, fit.py:20-23); oracle = numpy.corrcoef.
  * ts (S, Nreg, T) -> out (C, S), out[c][s] = corrcoef(ts[s])[n, m] for c = n(n-1)/2 + m, n > m: the layout of
  * b / bt.  fp64 MFMA Gram product per subject.  fisher_z != 0 applies atanh; keep it 0 with the reference's model
- * defaults, which are calibrated on raw correlations clipped to [-1, 1] (fcdiff/model.py:213, 236). */
+ * defaults, which are calibrated on raw correlations clipped to [-1, 1] (fcdiff/model.py:213, 236).
+ * Alignment: ts must be 16-byte aligned when T is even (ALIGNMENT, top of this file). */
 int fcd_corr_edges(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, int64_t T, int fisher_z, double *out,
                    fcd_stream stream);
 /* Cleaning in front of it: frame censoring and confound regression, per subject and over its kept frames only.
@@ -422,7 +458,8 @@ int fcd_corr_clean(fcd_ctx *ctx, const double *ts, const double *confounds, cons
  * 256 MB (knob "partial_chunk": at most so many subjects per chunk), which changes no bit.  Uses the context's workspace.
  * Deterministic (fixed reduction orders, no floating-point atomics); inputs are not written.
  * FCD_ERR_ARG: null pointer, S, Nreg or T < 1, shrink_value outside [0, 1] or NaN in mode 0.  FCD_ERR_UNSUPPORTED: Nreg > 1024,
- * unknown shrink_mode, S > 65535.  FCD_ERR_SHAPE: Nreg < 2 or T < 2, as fcd_corr_edges. */
+ * unknown shrink_mode, S > 65535.  FCD_ERR_SHAPE: Nreg < 2 or T < 2, as fcd_corr_edges.
+ * Alignment: ts must be 16-byte aligned when T is even (ALIGNMENT, top of this file). */
 int fcd_corr_partial(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, int64_t T, const int32_t *n_frames,
                      int shrink_mode, double shrink_value, int fisher_z, double *out, double *alpha, int32_t *info,
                      fcd_stream stream);
@@ -449,7 +486,9 @@ int fcd_edge_cov_fit(fcd_ctx *ctx, const double *b, int64_t C, int64_t H, const 
                      double *resid_var, int32_t *info, fcd_stream stream);
 /* out[c,s] = x[c,s] - d,  d = sum_q beta[c,q] (z[s,q] - z_ref[q]) added up over q ascending from 0.0, one rounded product and
  * one rounded sum per term: a NumPy loop's result bit for bit.  x, out (C, S), z (S, Q), z_ref (Q,), beta (C, Q),
- * all device.  NaN stays NaN.  Sessions are the caller's flattening of (U, K) to S.  One launch.  Refusals as above. */
+ * all device.  NaN stays NaN.  Sessions are the caller's flattening of (U, K) to S.  One launch.  Refusals as above.
+ * Alignment: the path is chosen by the address -- x and out both 16-byte aligned and S even take the 16-byte path,
+ * anything else the 8-byte one, with the same bits (ALIGNMENT, top of this file). */
 int fcd_edge_cov_apply(fcd_ctx *ctx, const double *x, int64_t C, int64_t S, const double *z, int64_t Q, const double *z_ref,
                        const double *beta, double *out, fcd_stream stream);
 
@@ -530,6 +569,8 @@ typedef struct fcd_harmonize_desc {
     double *out;               /* (C, S) */
 } fcd_harmonize_desc;
 int fcd_site_harmonize_fit(fcd_ctx *ctx, const fcd_harmonize_desc *d);
+/* fcd_site_harmonize_apply: Alignment: the path is chosen by the address -- x and out both 16-byte aligned and S even take the 16-byte path,
+ * anything else the 8-byte one, with the same bits (ALIGNMENT, top of this file). */
 int fcd_site_harmonize_apply(fcd_ctx *ctx, const fcd_harmonize_desc *d);
 
 /* ---- batched symmetric eigendecomposition -------------------------------------------------------------------------------------
@@ -624,7 +665,9 @@ typedef struct fcd_tangent_desc {
     double *out;               /* (C, S) */
     double *diag;              /* (Nreg, S) */
 } fcd_tangent_desc;
+/* fcd_tangent_fit: Alignment: ts must be 16-byte aligned when T is even (ALIGNMENT, top of this file). */
 int fcd_tangent_fit(fcd_ctx *ctx, const fcd_tangent_desc *d);
+/* fcd_tangent_apply: Alignment: ts must be 16-byte aligned when T is even (ALIGNMENT, top of this file). */
 int fcd_tangent_apply(fcd_ctx *ctx, const fcd_tangent_desc *d);
 
 /* ---- classical baselines ---------------------------------------------------------------------------------------------------
@@ -813,7 +856,8 @@ int fcd_gibbs_init(fcd_ctx *ctx, uint8_t *f_state, uint64_t *r_bits, int64_t Nre
 int fcd_gibbs_edge_tables(fcd_ctx *ctx, const double *lM, int64_t Nreg, int64_t U, double *lMf, fcd_stream stream);
 /* Redraw every f_c of every chain given r (edges are conditionally independent).  With lMf only the two
  * log-odds against type 0 are accumulated (one 16-byte read + two adds per term); lMf == NULL runs the
- * kernel that accumulates the three sums of fit.py:170-173 from lM directly. */
+ * kernel that accumulates the three sums of fit.py:170-173 from lM directly.
+ * Alignment: f_state and lMf must be 16-byte aligned (ALIGNMENT, top of this file). */
 int fcd_gibbs_f_step(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *hyper,
                      uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
                      int64_t chain0, uint64_t seed, int64_t sweep, fcd_stream stream);
@@ -827,19 +871,22 @@ int fcd_gibbs_region_tables(fcd_ctx *ctx, const double *lM, int64_t Nreg, int64_
  * and chains in parallel).  With lMd (made with the SAME edge_mode) the blocked path runs: panel kernels
  * stream lMd rows through LDS, small diagonal kernels resolve the in-order dependence (only s1 - s0
  * is formed, as a sum of table differences: same conditional, one add per term).  lMd == NULL
- * selects the generic kernel that gathers from lM directly (any shape, much slower). */
+ * selects the generic kernel that gathers from lM directly (any shape, much slower).
+ * Alignment: f_state and lMd must be 16-byte aligned (ALIGNMENT, top of this file). */
 int fcd_gibbs_r_step(fcd_ctx *ctx, const double *lM, const double *lMd, const double *hyper,
                      const uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G,
                      int64_t chain0, uint64_t seed, int64_t sweep, int edge_mode, fcd_stream stream);
 /* n_sweeps x (f step, r step), sweeps numbered sweep0, sweep0+1, ...: fcd_gibbs_run's loop without M-step or counters.
  * When counts != NULL the pooled statistics of the LAST sweep are stored there (fcd_gibbs_stats: this rank's own).
- * Waits for the stream as fcd_gibbs_run does (below) in a call that builds the f pass's records. */
+ * Waits for the stream as fcd_gibbs_run does (below) in a call that builds the f pass's records.
+ * Alignment: f_state, lMf and lMd must be 16-byte aligned (ALIGNMENT, top of this file). */
 int fcd_gibbs_sweeps(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *lMd,
                      const double *hyper, uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0,
                      uint64_t seed, int64_t sweep0, int64_t n_sweeps, int edge_mode, int64_t *counts,
                      fcd_stream stream);
 /* Pooled sufficient statistics over the G chains (the all-reduce payload):
- * counts[0..7] = {sum r, #f=0, #f=1, #f=2, G, 0, 0, 0} (int64, device, overwritten).  fcd_gibbs_tally with counts only. */
+ * counts[0..7] = {sum r, #f=0, #f=1, #f=2, G, 0, 0, 0} (int64, device, overwritten).  fcd_gibbs_tally with counts only.
+ * Alignment: f_state must be 16-byte aligned (ALIGNMENT, top of this file). */
 int fcd_gibbs_stats(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U,
                     int64_t G, int64_t *counts, fcd_stream stream);
 /* M-step for (pi, gamma) from pooled counts (after the cross-GPU all-reduce): the sample version of
@@ -847,13 +894,15 @@ int fcd_gibbs_stats(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits
 int fcd_gibbs_mstep(fcd_ctx *ctx, const int64_t *counts, int64_t Nreg, int64_t U, double *hyper,
                     fcd_stream stream);
 /* Running marginal counts over sweeps AND chains: cnt_f (C,3) += [f_c = k], cnt_r (Nreg,U) += r_nu
- * (uint32, device, wrapping); posterior marginals = counts / (sweeps * G).  fcd_gibbs_tally with counters only. */
+ * (uint32, device, wrapping); posterior marginals = counts / (sweeps * G).  fcd_gibbs_tally with counters only.
+ * Alignment: f_state must be 16-byte aligned (ALIGNMENT, top of this file). */
 int fcd_gibbs_accumulate(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg,
                          int64_t U, int64_t G, uint32_t *cnt_f, uint32_t *cnt_r, fcd_stream stream);
 /* fcd_gibbs_stats and fcd_gibbs_accumulate in ONE pass over the state and ONE launch (the pooled sums are kept in
  * accumulators of the context that the kernel itself puts back to zero: no memset; the two entry points are this launch
  * with one half of its output):
- * counts (nullable) is overwritten as by fcd_gibbs_stats; cnt_f / cnt_r (both or neither) are incremented. */
+ * counts (nullable) is overwritten as by fcd_gibbs_stats; cnt_f / cnt_r (both or neither) are incremented.
+ * Alignment: f_state must be 16-byte aligned (ALIGNMENT, top of this file). */
 int fcd_gibbs_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U,
                     int64_t G, int64_t *counts, uint32_t *cnt_f, uint32_t *cnt_r, fcd_stream stream);
 /* The sampler loop of one rank between two exchanges of pooled statistics -- what the fit loop calls:
@@ -873,7 +922,8 @@ int fcd_gibbs_tally(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *r_bits
  * stream has run everything queued before the build, the build and its hint kernel (whatever the caller queued on the
  * stream before the call included); after two seconds it falls back to hipStreamSynchronize.  Only this stream is waited
  * for.  A call without a record build (one sweep, knob f_records = 1, a shape without the pair-tile f pass) returns without
- * waiting. */
+ * waiting.
+ * Alignment: f_state, lMf and lMd must be 16-byte aligned (ALIGNMENT, top of this file). */
 int fcd_gibbs_run(fcd_ctx *ctx, const double *S_B, const double *lM, const double *lMf, const double *lMd,
                   double *hyper,
                   uint8_t *f_state, uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, int64_t chain0, uint64_t seed,
@@ -1075,7 +1125,8 @@ int fcd_vb_patient_elbo(fcd_ctx *ctx, const double *lq_F, const double *lq_R, co
  *   lM_beta = beta * lM                           (C, U, 3, 3), the working table the next fcd_gibbs_region_tables and
  *                                                 fcd_gibbs_r_step read (NULL: not written; must not alias lM or w).
  * Started from r drawn from the prior (beta = 0) and followed, at every beta_t of a ladder ending at 1, by one r pass on
- * the beta_t table, exp(w[g, u]) is an unbiased estimate of p(bt_u | f_g).  Two launches; uses the context's workspace. */
+ * the beta_t table, exp(w[g, u]) is an unbiased estimate of p(bt_u | f_g).  Two launches; uses the context's workspace.
+ * Alignment: f_state must be 16-byte aligned (ALIGNMENT, top of this file). */
 int fcd_score_ais_step(fcd_ctx *ctx, const double *lM, const uint8_t *f_state, const uint64_t *r_bits, int64_t Nreg, int64_t U,
                        int64_t G, double beta_prev, double beta, double *w, double *lM_beta, fcd_stream stream);
 /* The per-patient fold of the AIS weights w (G, U): out4 (U, 4) = {m = max_g w[g,u], sum_g exp(w - m), sum_g exp(2 (w - m)),
@@ -1097,7 +1148,9 @@ int fcd_evidence_energy(fcd_ctx *ctx, const double *S_B, const double *lM, const
 /* dst[j][i] = beta * src[j][i], i < n[j], for n_tables (1 to 8) tables in ONE launch: the working tables of a rung (S_B, lM
  * and the two difference tables, which are linear in lM).  src, dst, n are host arrays of device pointers / element counts;
  * dst[j] may be src[j].  beta = 1 copies bit for bit.  An all-zero table is the caller's zero fill, not beta = 0
- * (0 * -inf is NaN). */
+ * (0 * -inf is NaN).
+ * Alignment: the path is chosen by the address -- src[j] and dst[j] both 16-byte aligned take the 16-byte path,
+ * anything else the 8-byte one, with the same bits (ALIGNMENT, top of this file). */
 int fcd_evidence_temper(fcd_ctx *ctx, double beta, int64_t n_tables, const double *const *src, double *const *dst,
                         const int64_t *n, fcd_stream stream);
 /* ---- patient or control: the two per-chain log-likelihoods of new subjects (UnsharedRegionFit.membership) ----------------
