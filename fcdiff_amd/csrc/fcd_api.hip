@@ -21,49 +21,32 @@ void fcd_abl_refresh(hipStream_t s) {
 }
 #endif
 
-int fcd_ws_reserve(fcd_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->ws_bytes) return FCD_OK;
+int fcd_buf_reserve(fcd_ctx *ctx, fcd_dev_buf &b, size_t bytes) {
+    if (bytes <= b.bytes) return FCD_OK;
     // grow: the old block may still be in use by kernels already queued, so drain first
     FCD_HIP_TRY(hipDeviceSynchronize());
-    if (ctx->ws) FCD_HIP_TRY(hipFree(ctx->ws));
-    ctx->ws = nullptr;
-    ctx->ws_bytes = 0;
-    size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-    FCD_HIP_TRY(hipMalloc(&ctx->ws, want));
-    ctx->ws_bytes = want;
-    ctx->n_alloc += 1;
+    void *old = b.p;
+    b.p = nullptr;
+    b.bytes = 0;
+    if (old) FCD_HIP_TRY(hipFree(old));
+    const size_t want = bytes < b.min_bytes ? b.min_bytes : bytes;
+    void *p = nullptr;
+    FCD_HIP_TRY(hipMalloc(&p, want));
+    if (b.counted) ctx->n_alloc += 1;
+    if (b.zeroed) {
+        const hipError_t e = hipMemset(p, 0, want);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return (int)e;
+        }
+    }
+    b.p = p;
+    b.bytes = want;
     return FCD_OK;
 }
-
-int fcd_fsq_reserve(fcd_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->fsq_bytes) return FCD_OK;
-    FCD_HIP_TRY(hipDeviceSynchronize());
-    if (ctx->fsq) FCD_HIP_TRY(hipFree(ctx->fsq));
-    ctx->fsq = nullptr;
-    ctx->fsq_bytes = 0;
-    FCD_HIP_TRY(hipMalloc(&ctx->fsq, bytes));
-    ctx->fsq_bytes = bytes;
-    ctx->n_alloc += 1;
-    return FCD_OK;
-}
-
-int fcd_frec_reserve(fcd_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->frec_bytes) return FCD_OK;
-    FCD_HIP_TRY(hipDeviceSynchronize());
-    if (ctx->frec) FCD_HIP_TRY(hipFree(ctx->frec));
-    ctx->frec = nullptr;
-    ctx->frec_bytes = 0;
-    FCD_HIP_TRY(hipMalloc(&ctx->frec, bytes));
-    ctx->frec_bytes = bytes;
-    ctx->n_alloc += 1;
-    return FCD_OK;
-}
-
-// "0", "" and unset mean "default"; anything else is the number
-static double knob_env(const char *name) {
-    const char *e = getenv(name);
-    return (e && *e) ? atof(e) : 0.0;
-}
+// the grow-only blocks of a context, for what walks them all
+static fcd_dev_buf fcd_ctx::*const ctx_bufs[] = {&fcd_ctx::ws,        &fcd_ctx::fsq,      &fcd_ctx::frec,
+                                                 &fcd_ctx::noise_rec, &fcd_ctx::count_ws, &fcd_ctx::corr_tickets};
 
 void fcd_prof_begin(fcd_ctx *ctx, int slot, hipStream_t s) {
     if (!ctx->prof_on) return;
@@ -141,126 +124,36 @@ int fcd_ctx_create(fcd_ctx **out) {
     if (!ctx) return (int)hipErrorOutOfMemory;
     ctx->device = dev;
     ctx->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    ctx->ws = nullptr;
-    ctx->ws_bytes = 0;
-    ctx->log_tab = nullptr;
-    ctx->dev_err = nullptr;
-    ctx->f_sure_hint = nullptr;
-    ctx->fsq = nullptr;
-    ctx->fsq_bytes = 0;
-    ctx->frec = nullptr;
-    ctx->frec_bytes = 0;
-    ctx->noise_rec = nullptr;
-    ctx->noise_rec_bytes = 0;
-    for (int k = 0; k < FCD_ACC_N; ++k) ctx->sweep_acc[k] = fcd_sweep_acc{{nullptr, nullptr}, 0, 0, 1};
-    ctx->count_ws = nullptr;
-    ctx->count_ws_bytes = 0;
-    ctx->rs_dev = nullptr;
-    ctx->rs_J = ctx->rs_smax = 0;
-    ctx->rs_max_member = -1;
-    ctx->pg_dev = nullptr;
-    ctx->pg_J = ctx->pg_P = ctx->pg_umax = ctx->pg_total = ctx->pg_bins_max = 0;
-    ctx->pg_max_member = -1;
-    ctx->pg_with_rs = 0;
-    ctx->pt_dev = nullptr;
-    ctx->pt_Q = ctx->pt_U = ctx->pt_umax = 0;
-    ctx->pt_with_rs = 0;
-    ctx->acc = nullptr;
-    ctx->nan_slots = nullptr;
-    ctx->f_slots = nullptr;
-    ctx->dbg = nullptr;
-    ctx->comm = nullptr;
-    ctx->comm_world = ctx->comm_rank = 0;
-    ctx->pool_counts = nullptr;
-    ctx->corr_tickets = nullptr;
-    ctx->corr_tickets_n = 0;
-    ctx->prof_on = 0;
-    for (int i = 0; i < FCD_PROF_SLOTS; ++i) {
-        ctx->prof_ev[i] = nullptr;
-        ctx->prof_n[i] = ctx->prof_cap[i] = 0;
-    }
-    ctx->msg[0] = 0;
-    ctx->n_alloc = 0;
-    for (int i = 0; i < FCD_KA_N; ++i) ctx->lds_attr[i] = 0;
-    for (int i = 0; i < 3; ++i) ctx->pipe_occ[i] = -1;
-    ctx->pipe_grid = ctx->pipe_capacity = 0;
     // the only place the environment is read: defaults of the knobs (fcd_ctx_set_knob changes them later)
-    ctx->knobs.r_path = (int)knob_env("FCD_R_PATH");
-    ctx->knobs.r_ub = (int)knob_env("FCD_R_UB");
-    ctx->knobs.r_nopad = (int)knob_env("FCD_R_NOPAD");
-    ctx->knobs.r_dsplit = (int)knob_env("FCD_R_DSPLIT");
-    ctx->knobs.r_coop = (int)knob_env("FCD_R_COOP") == 1 ? 1 : 0;    // (2, the refusal test hook, not from the environment)
-    ctx->knobs.qr_form = (int)knob_env("FCD_QR_FORM");
-    ctx->knobs.r_refill = (int)knob_env("FCD_R_REFILL");
-    ctx->knobs.r_tol = knob_env("FCD_R_TOL");
-    ctx->knobs.f_tol = knob_env("FCD_F_TOL");
-    ctx->knobs.f_form = (int)knob_env("FCD_F_FORM");
-    ctx->knobs.f_pack = (int)knob_env("FCD_F_PACK");
-    ctx->knobs.corr_form = (int)knob_env("FCD_CORR_FORM");
-    ctx->knobs.r_poll_limit = 0;        // test hooks: through fcd_ctx_set_knob only, never from the environment
-    ctx->knobs.r_withhold = 0;
-    ctx->knobs.f_records = 0;           // (A/B runs and tests only)
-    ctx->knobs.f_sure = 0;
-    ctx->knobs.f_runs = 0;
-    ctx->knobs.r_sure = 0;
-    ctx->knobs.r_sure_x = 0.0;
-    ctx->knobs.tally_in_f = 0;
-    ctx->knobs.partial_chunk = 0;
-    ctx->knobs.tangent_chunk = 0;
-    ctx->knobs.tally_in_r = (int)knob_env("FCD_TALLY_IN_R");
-    ctx->knobs.r_keep_words = (int)knob_env("FCD_R_KEEP_WORDS");
-    ctx->r_form_last = 0;
-    ctx->n_pack = 0;
-    ctx->n_pack_tally = 0;
-    ctx->n_r_tally = 0;
-    ctx->n_f_tally = 0;
-    ctx->n_frec_pass = ctx->n_frec_build = ctx->n_fsure_pass = ctx->n_frun_pass = 0;
-    ctx->n_rsure_pass = ctx->n_rsure_build = 0;
-    int rc = fcd_ws_reserve(ctx, 1u << 20);
+    fcd_knobs_from_env(ctx->knobs, [](const char *name) -> const char * { return getenv(name); });
+    // tables of K_lik's exp and log (fcd_fastmath.h): 2^(-j/64) and {1/m_i, log m_i}, made with the host's libm
+    struct { double exp_tab[FCD_EXP_CELLS]; fcd_log_cell log_tab[FCD_LOG_CELLS]; } tabs;
+    fcd_fm_make_tables(tabs.exp_tab, tabs.log_tab, exp2, log);
+    // a fixed-size device block, zero-filled
+    auto zeroed = [&](void **p, size_t bytes) -> int {
+        FCD_HIP_TRY(hipMalloc(p, bytes));
+        ctx->n_alloc += 1;
+        FCD_HIP_TRY(hipMemset(*p, 0, bytes));
+        return FCD_OK;
+    };
+    int rc = fcd_ws_reserve(ctx, ctx->ws.min_bytes);
+    if (rc == FCD_OK) rc = (int)hipHostMalloc((void **)&ctx->dev_err, sizeof(unsigned), hipHostMallocDefault);
+    if (rc == FCD_OK) rc = (int)hipHostMalloc((void **)&ctx->hint, sizeof(fcd_hint_words), hipHostMallocDefault);
     if (rc == FCD_OK) {
-        void *pin = nullptr;
-        rc = (int)hipHostMalloc(&pin, sizeof(unsigned), hipHostMallocDefault);
-        if (rc == FCD_OK) {
-            ctx->dev_err = (volatile unsigned *)pin;
-            *ctx->dev_err = 0u;
-            rc = (int)hipHostMalloc(&pin, 2 * sizeof(unsigned), hipHostMallocDefault);
-        }
-        if (rc == FCD_OK) {
-            ctx->f_sure_hint = (volatile unsigned *)pin;
-            ctx->f_sure_hint[0] = 0u;       // (build numbers start at 1)
-            ctx->f_sure_hint[1] = 0u;       // (the r pass's bound build)
-        }
+        *ctx->dev_err = 0u;
+        ctx->hint->f = 0u;      // (build numbers start at 1)
+        ctx->hint->r = 0u;
+        rc = (int)hipMalloc(&ctx->log_tab, sizeof(tabs));
+        ctx->n_alloc += 1;
     }
+    if (rc == FCD_OK) rc = (int)hipMemcpy(ctx->log_tab, &tabs, sizeof(tabs), hipMemcpyHostToDevice);
+    if (rc == FCD_OK) rc = zeroed(&ctx->acc, FCD_ACC_BYTES);
+    if (rc == FCD_OK) rc = zeroed(&ctx->f_slots, FCD_F_SLOTS_BYTES);
+    if (rc == FCD_OK) rc = zeroed(&ctx->nan_slots, FCD_NAN_SLOTS_BYTES);
+    if (rc == FCD_OK) rc = zeroed((void **)&ctx->words, sizeof(fcd_dev_words));
     if (rc) {
-        if (ctx->ws) (void)hipFree(ctx->ws);
-        if (ctx->dev_err) (void)hipHostFree((void *)ctx->dev_err);
-        if (ctx->f_sure_hint) (void)hipHostFree((void *)ctx->f_sure_hint);
-        delete ctx;
+        fcd_ctx_destroy(ctx);
         return rc;
-    }
-    {
-        // tables of K_lik's exp and log (fcd_fastmath.h): 2^(-j/64) and {1/m_i, log m_i}, made with the host's libm
-        struct { double exp_tab[FCD_EXP_CELLS]; fcd_log_cell log_tab[FCD_LOG_CELLS]; } tabs;
-        fcd_fm_make_tables(tabs.exp_tab, tabs.log_tab, exp2, log);
-        hipError_t e = hipMalloc(&ctx->log_tab, sizeof(tabs));
-        ctx->n_alloc += 1;
-        if (e == hipSuccess) e = hipMemcpy(ctx->log_tab, &tabs, sizeof(tabs), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&ctx->acc, 8 * sizeof(unsigned long long));
-        ctx->n_alloc += 1;
-        if (e == hipSuccess) e = hipMemset(ctx->acc, 0, 8 * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc(&ctx->f_slots, FCD_F_SLOTS * 8 * sizeof(unsigned long long));
-        ctx->n_alloc += 1;
-        if (e == hipSuccess) e = hipMemset(ctx->f_slots, 0, FCD_F_SLOTS * 8 * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc(&ctx->nan_slots, FCD_NAN_SLOTS * 16 * sizeof(unsigned long long));
-        ctx->n_alloc += 1;
-        if (e == hipSuccess) e = hipMemset(ctx->nan_slots, 0, FCD_NAN_SLOTS * 16 * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc(&ctx->dbg, 16 * sizeof(unsigned long long));
-        ctx->n_alloc += 1;
-        if (e == hipSuccess) e = hipMemset(ctx->dbg, 0, 16 * sizeof(unsigned long long));
-        if (e != hipSuccess) {
-            fcd_ctx_destroy(ctx);
-            return (int)e;
-        }
     }
     *out = ctx;
     return FCD_OK;
@@ -269,24 +162,16 @@ int fcd_ctx_create(fcd_ctx **out) {
 int fcd_ctx_destroy(fcd_ctx *ctx) {
     if (!ctx) return FCD_OK;
     (void)fcd_comm_destroy(ctx);
-    if (ctx->pool_counts) (void)hipFree(ctx->pool_counts);
-    hipError_t e = hipSuccess;
-    if (ctx->ws) e = hipFree(ctx->ws);
-    if (ctx->log_tab) (void)hipFree(ctx->log_tab);
+    const hipError_t e = ctx->ws.p ? hipFree(ctx->ws.p) : hipSuccess;       // (the one result reported)
+    ctx->ws.p = nullptr;
+    for (auto b : ctx_bufs)
+        if ((ctx->*b).p) (void)hipFree((ctx->*b).p);
+    void *const dev[] = {ctx->pool_counts, ctx->log_tab, ctx->rs_dev, ctx->pg_dev, ctx->pt_dev,
+                         ctx->acc,         ctx->f_slots, ctx->nan_slots, ctx->words};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
     if (ctx->dev_err) (void)hipHostFree((void *)ctx->dev_err);
-    if (ctx->f_sure_hint) (void)hipHostFree((void *)ctx->f_sure_hint);
-    if (ctx->fsq) (void)hipFree(ctx->fsq);
-    if (ctx->frec) (void)hipFree(ctx->frec);
-    if (ctx->noise_rec) (void)hipFree(ctx->noise_rec);
-    if (ctx->count_ws) (void)hipFree(ctx->count_ws);
-    if (ctx->rs_dev) (void)hipFree(ctx->rs_dev);
-    if (ctx->pg_dev) (void)hipFree(ctx->pg_dev);
-    if (ctx->pt_dev) (void)hipFree(ctx->pt_dev);
-    if (ctx->acc) (void)hipFree(ctx->acc);
-    if (ctx->f_slots) (void)hipFree(ctx->f_slots);
-    if (ctx->nan_slots) (void)hipFree(ctx->nan_slots);
-    if (ctx->dbg) (void)hipFree(ctx->dbg);
-    if (ctx->corr_tickets) (void)hipFree(ctx->corr_tickets);
+    if (ctx->hint) (void)hipHostFree((void *)ctx->hint);
     for (int i = 0; i < FCD_PROF_SLOTS; ++i) {
         for (int j = 0; j < 2 * ctx->prof_cap[i]; ++j) (void)hipEventDestroy(ctx->prof_ev[i][j]);
         delete[] ctx->prof_ev[i];
@@ -305,50 +190,23 @@ int fcd_ctx_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G) {
     if (pl.ws_bytes > need) need = pl.ws_bytes;
     int rc = fcd_ws_reserve(ctx, need);
     if (rc) return rc;
-    if (pl.fsq_bytes) {
-        rc = fcd_fsq_reserve(ctx, pl.fsq_bytes);
-        if (rc) return rc;
-    }
+    rc = fcd_buf_reserve(ctx, ctx->fsq, pl.fsq_bytes);
+    if (rc) return rc;
     // the f pass's record table: a sweep loop that finds none runs the kernel that builds its records per tile, so a
     // device without room for it is no error
-    if (pl.frec_bytes && ctx->knobs.f_records != 1 && fcd_frec_reserve(ctx, pl.frec_bytes) != FCD_OK) (void)hipGetLastError();
+    if (pl.frec_bytes && ctx->knobs.f_records != 1 && fcd_buf_reserve(ctx, ctx->frec, pl.frec_bytes) != FCD_OK) (void)hipGetLastError();
     return FCD_OK;
 }
 
 int fcd_ctx_set_knob(fcd_ctx *ctx, const char *name, double value) {
     if (!ctx || !name) return FCD_ERR_ARG;
-    fcd_knobs &k = ctx->knobs;
-    if (!strcmp(name, "r_path")) k.r_path = (int)value;
-    else if (!strcmp(name, "r_ub")) k.r_ub = (int)value;
-    else if (!strcmp(name, "r_nopad")) k.r_nopad = (int)value;
-    else if (!strcmp(name, "r_dsplit")) k.r_dsplit = (int)value;
-    else if (!strcmp(name, "r_coop")) k.r_coop = (int)value;
-    else if (!strcmp(name, "qr_form")) k.qr_form = (int)value;
-    else if (!strcmp(name, "r_refill")) k.r_refill = (int)value;
-    else if (!strcmp(name, "r_tol")) k.r_tol = value;
-    else if (!strcmp(name, "f_tol")) k.f_tol = value;
-    else if (!strcmp(name, "f_form")) k.f_form = (int)value;
-    else if (!strcmp(name, "f_pack")) k.f_pack = (int)value;
-    else if (!strcmp(name, "f_records")) k.f_records = (int)value;
-    else if (!strcmp(name, "f_sure")) k.f_sure = (int)value;
-    else if (!strcmp(name, "f_runs")) k.f_runs = (int)value;
-    else if (!strcmp(name, "r_sure")) k.r_sure = (int)value;
-    else if (!strcmp(name, "r_sure_x")) k.r_sure_x = value;
-    else if (!strcmp(name, "corr_form")) k.corr_form = (int)value;
-    else if (!strcmp(name, "partial_chunk")) k.partial_chunk = (int)value;
-    else if (!strcmp(name, "tangent_chunk")) k.tangent_chunk = (int)value;
-    else if (!strcmp(name, "tally_in_r")) k.tally_in_r = (int)value;
-    else if (!strcmp(name, "tally_in_f")) k.tally_in_f = (int)value;
-    else if (!strcmp(name, "r_keep_words")) k.r_keep_words = (int)value;
-    else if (!strcmp(name, "r_poll_limit")) k.r_poll_limit = (int)value;
-    else if (!strcmp(name, "r_withhold")) k.r_withhold = (int)value;
-    else return fcd_fail(ctx, FCD_ERR_ARG, "fcd_ctx_set_knob: unknown knob");
+    if (!fcd_knobs_set(ctx->knobs, name, value)) return fcd_fail(ctx, FCD_ERR_ARG, "fcd_ctx_set_knob: unknown knob");
     return FCD_OK;
 }
 
 int fcd_ctx_check(fcd_ctx *ctx) {
     if (!ctx) return FCD_ERR_ARG;
-    if (ctx->dev_err && *ctx->dev_err == 2u)      // (fcd_harmonize.hip)
+    if (ctx->dev_err && *ctx->dev_err == FCD_DEV_ERR_HARM_SITE)
         return fcd_fail(ctx, FCD_ERR_DEVICE, "fcd_site_harmonize: a site id outside 0..B-1 reached the device");
     if (ctx->dev_err && *ctx->dev_err)
         return fcd_fail(ctx, FCD_ERR_DEVICE, "a device-side wait of the pipelined r pass was abandoned: the chain state is unusable");
@@ -359,19 +217,19 @@ int fcd_ctx_clear_error(fcd_ctx *ctx) {
     if (!ctx) return FCD_ERR_ARG;
     if (ctx->dev_err) *ctx->dev_err = 0u;
     // whatever an abandoned launch left in the context-owned accumulators / tickets (zero between launches by contract)
-    if (ctx->acc) FCD_HIP_TRY(hipMemset(ctx->acc, 0, 8 * sizeof(unsigned long long)));
-    if (ctx->f_slots) FCD_HIP_TRY(hipMemset(ctx->f_slots, 0, FCD_F_SLOTS * 8 * sizeof(unsigned long long)));
-    if (ctx->nan_slots) FCD_HIP_TRY(hipMemset(ctx->nan_slots, 0, FCD_NAN_SLOTS * 16 * sizeof(unsigned long long)));
-    if (ctx->corr_tickets && ctx->corr_tickets_n > 0)
-        FCD_HIP_TRY(hipMemset(ctx->corr_tickets, 0, (size_t)ctx->corr_tickets_n * sizeof(unsigned)));
+    if (ctx->acc) FCD_HIP_TRY(hipMemset(ctx->acc, 0, FCD_ACC_BYTES));
+    if (ctx->f_slots) FCD_HIP_TRY(hipMemset(ctx->f_slots, 0, FCD_F_SLOTS_BYTES));
+    if (ctx->nan_slots) FCD_HIP_TRY(hipMemset(ctx->nan_slots, 0, FCD_NAN_SLOTS_BYTES));
+    for (auto b : ctx_bufs)
+        if ((ctx->*b).zeroed && (ctx->*b).p) FCD_HIP_TRY(hipMemset((ctx->*b).p, 0, (ctx->*b).bytes));
     return FCD_OK;
 }
 
 int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out) {
     if (!ctx || !name || !out) return FCD_ERR_ARG;
     if (!strcmp(name, "n_alloc")) *out = ctx->n_alloc;
-    else if (!strcmp(name, "ws_bytes")) *out = (int64_t)ctx->ws_bytes;
-    else if (!strcmp(name, "fsq_bytes")) *out = (int64_t)ctx->fsq_bytes;
+    else if (!strcmp(name, "ws_bytes")) *out = (int64_t)ctx->ws.bytes;
+    else if (!strcmp(name, "fsq_bytes")) *out = (int64_t)ctx->fsq.bytes;
     else if (!strcmp(name, "r_form_last")) *out = ctx->r_form_last;
     else if (!strcmp(name, "pack_launches")) *out = ctx->n_pack;
     else if (!strcmp(name, "tally_f_in_pack")) *out = ctx->n_pack_tally;
@@ -380,26 +238,27 @@ int fcd_ctx_stat(const fcd_ctx *ctx, const char *name, int64_t *out) {
     else if (!strcmp(name, "tally_in_r_max_rounds")) *out = R_TALLY_MAX_ROUNDS;
     else if (!strcmp(name, "f_rec_passes")) *out = ctx->n_frec_pass;
     else if (!strcmp(name, "f_rec_builds")) *out = ctx->n_frec_build;
-    else if (!strcmp(name, "f_rec_bytes")) *out = (int64_t)ctx->frec_bytes;
+    else if (!strcmp(name, "f_rec_bytes")) *out = (int64_t)ctx->frec.bytes;
     else if (!strcmp(name, "f_rec_min_sweeps")) *out = F_REC_MIN_SWEEPS;
     else if (!strcmp(name, "f_sure_passes")) *out = ctx->n_fsure_pass;
     else if (!strcmp(name, "f_run_passes")) *out = ctx->n_frun_pass;
     else if (!strcmp(name, "r_sure_passes")) *out = ctx->n_rsure_pass;
     else if (!strcmp(name, "r_sure_builds")) *out = ctx->n_rsure_build;
-    else if (!strcmp(name, "r_sure_sites") || !strcmp(name, "r_sure_exceptions")) {
-        unsigned long long v[16];
-        FCD_HIP_TRY(hipMemcpy(v, ctx->dbg, sizeof(v), hipMemcpyDeviceToHost));
-        *out = (int64_t)v[!strcmp(name, "r_sure_sites") ? 8 : 9];
-    }
     else if (!strcmp(name, "pipe_grid")) *out = ctx->pipe_grid;
     else if (!strcmp(name, "pipe_capacity")) *out = ctx->pipe_capacity;
     else if (!strcmp(name, "comm_world")) *out = ctx->comm ? ctx->comm_world : 0;
     else if (!strcmp(name, "dev_err")) *out = ctx->dev_err ? (int64_t)*ctx->dev_err : 0;
-    else if (!strcmp(name, "f_repeats") || !strcmp(name, "r_exact_rows") || !strcmp(name, "f_sure_tiles") || !strcmp(name, "f_sure_fallbacks")) {
+    else if (!strcmp(name, "f_repeats") || !strcmp(name, "r_exact_rows") || !strcmp(name, "f_sure_tiles") ||
+             !strcmp(name, "f_sure_fallbacks") || !strcmp(name, "r_sure_sites") || !strcmp(name, "r_sure_exceptions")) {
         // event counters kept on the device (a synchronising read: diagnostics only)
-        unsigned long long v[8];
-        FCD_HIP_TRY(hipMemcpy(v, ctx->dbg, sizeof(v), hipMemcpyDeviceToHost));
-        *out = (int64_t)v[name[0] == 'r' ? 1 : !strcmp(name, "f_repeats") ? 0 : !strcmp(name, "f_sure_tiles") ? 2 : 3];
+        fcd_dev_words v;
+        FCD_HIP_TRY(hipMemcpy(&v, ctx->words, sizeof(v), hipMemcpyDeviceToHost));
+        *out = (int64_t)(!strcmp(name, "f_repeats")           ? v.f_repeats
+                         : !strcmp(name, "r_exact_rows")      ? v.r_exact_rows
+                         : !strcmp(name, "f_sure_tiles")      ? v.f_sure_tiles
+                         : !strcmp(name, "f_sure_fallbacks")  ? v.f_sure_fallbacks
+                         : !strcmp(name, "r_sure_sites")      ? v.r_sure_sites
+                                                              : v.r_sure_exceptions);
     }
     else return FCD_ERR_ARG;
     return FCD_OK;

@@ -1323,7 +1323,7 @@ __host__ static int gp_run(fcd_ctx *ctx, const char *who, const bl_in &d, const 
     const size_t base = (size_t)((int64_t)KS * C * 4 + 2 * C + 2 * N * P) * sizeof(double);
     int rc = fcd_ws_reserve(ctx, base + h.bytes(d, KS));
     if (rc) return rc;
-    double *XT = (double *)ctx->ws, *Q = XT + (int64_t)KS * C * 4;
+    double *XT = (double *)ctx->ws.p, *Q = XT + (int64_t)KS * C * 4;
     gp_kargs<A> a;
     a.c.XT = XT;
     a.c.Q = Q;
@@ -1337,7 +1337,7 @@ __host__ static int gp_run(fcd_ctx *ctx, const char *who, const bl_in &d, const 
     a.c.t = o.t;
     a.c.count_t = reinterpret_cast<unsigned long long *>(o.count_t);
     FCD_HIP_TRY(hipMemsetAsync(o.count_t, 0, (size_t)C * sizeof(int64_t), st));
-    if ((rc = h.setup(ctx, st, d, KS, XT, Q, (char *)ctx->ws + base, a.s))) return rc;
+    if ((rc = h.setup(ctx, st, d, KS, XT, Q, (char *)ctx->ws.p + base, a.s))) return rc;
     if ((rc = h.pack(st, d, KS, a.s, true))) return rc;
     rc = h.pick([&](auto s) {
         typedef decltype(s) Stat;
@@ -1370,7 +1370,7 @@ __host__ static int nb_run(fcd_ctx *ctx, const char *who, const bl_in &d, const 
     const size_t base = (size_t)((int64_t)KS * C * 4 + C) * sizeof(double);
     int rc = fcd_ws_reserve(ctx, base + h.bytes(d, KS));
     if (rc) return rc;
-    double *XT = (double *)ctx->ws, *Q = XT + (int64_t)KS * C * 4;
+    double *XT = (double *)ctx->ws.p, *Q = XT + (int64_t)KS * C * 4;
     nb_kargs<A> a;
     a.c.XT = XT;
     a.c.Q = Q;
@@ -1382,7 +1382,7 @@ __host__ static int nb_run(fcd_ctx *ctx, const char *who, const bl_in &d, const 
     a.c.thr2 = threshold * threshold;
     a.c.bits = reinterpret_cast<uint16_t *>(bits);
     a.c.t = t;
-    if ((rc = h.setup(ctx, st, d, KS, XT, Q, (char *)ctx->ws + base, a.s))) return rc;
+    if ((rc = h.setup(ctx, st, d, KS, XT, Q, (char *)ctx->ws.p + base, a.s))) return rc;
     if ((rc = h.pack(st, d, KS, a.s, false))) return rc;
     return h.pick([&](auto s) {
         typedef decltype(s) Stat;

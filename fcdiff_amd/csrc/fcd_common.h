@@ -1,59 +1,19 @@
 // Shared host/device helpers of libfcdiff_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
 #include "../../include/fcdiff_hip.h"
+#include "fcd_knobs.h"
 
 #define FCD_PROF_SLOTS 4
 #define FCD_PROF_LIK 0
 #define FCD_PROF_F 1
 #define FCD_PROF_RSTEP 2
 #define FCD_PROF_PACK 3
-
-// Tuning / test knobs.  Read ONCE from the environment by fcd_ctx_create (FCD_R_PATH, FCD_R_UB, FCD_R_NOPAD, FCD_R_TOL,
-// FCD_F_TOL, FCD_F_FORM, FCD_TALLY_IN_R, FCD_R_KEEP_WORDS, ...: "0" / unset = default), changed afterwards only through
-// fcd_ctx_set_knob: no entry point reads the environment.
-struct fcd_knobs {
-    int r_path;        // 0: blocked r pass -- pipelined one-launch form where its grid fits the device at once, else one launch
-                       // per block step; 3: one launch per block step always
-    int r_ub;          // patients per panel workgroup of the blocked r pass: 0 = automatic, else 1 / 2 / 4
-    int r_nopad;       // 1: no empty workgroups beside the in-order workgroups
-    int r_refill;      // 1: the packing launch writes the panel-value sentinels in every sweep (default: only in the first sweep of a fcd_gibbs_run call)
-    int qr_form;       // variational q_R update: 0 = by size; 1 = gathers from the edge-major table inside the region loop (rounds 1-3);
-                       // 2 = region-major weights made first, whatever their size
-    int r_coop;        // pipelined r pass: 1 = cooperative launch (the runtime checks that the grid is co-resident; +16 us per pass), else plain;
-                       // 2 = TEST HOOK (fcd_ctx_set_knob only): every pipelined launch acts as if the runtime had refused it, launching nothing
-    int r_dsplit;      // 1: ONE in-order workgroup per patient in the pipelined r pass (default: two, 8 chain words each, where there are more than 8)
-    double r_tol;      // > default: widen the margin inside which an r draw is re-decided with the exact logit
-    double f_tol;      // > default: the same for the f draws
-    int r_poll_limit;  // TEST HOOK: > 0 bounds every device-side poll of the pipelined r pass by this many polls (default 2^20, ~1 s)
-    int r_withhold;    // TEST HOOK: 1 = the in-order role of the pipelined r pass never sets its marks (a panel wave then gives up)
-    int corr_form;     // 1: K_corr in 64 x 64 blocks with a moments pass also where the one-workgroup-per-subject kernel would run
-    int f_form;        // 0: automatic; 2: the any-U pair kernel also where the U <= 64 one would run; 3: scalar-mask form
-    int f_pack;        // 1: the r pass's packing launch in every sweep (default: only where the f pass cannot write the packed f words)
-    int f_records;     // pair-tile f pass reads pair records made once per call: 0 = in calls of at least F_REC_MIN_SWEEPS pair-tile
-                       // sweeps, 1 = never (every tile builds its own), 2 = whenever the pair-tile form runs
-    int f_sure;        // 1: never the decided-tile path of the pair-tile f pass (A/B runs and tests; default: where the table has such tiles)
-    int f_runs;        // form of the decided path: 0 = block-wide runs of tiles (gibbs_f_run_kernel) where the record build found EVERY
-                       // tile decided, the per-tile kernel elsewhere; 1 = never the run form; 2 = the run form wherever the
-                       // decided path is taken at all (tests: open edges inside the run kernel)
-    int tally_in_r;    // f half of the tally inside the pipelined r pass (its in-order workgroups, before their first block): 0 = where
-                       // a wave's rounds are at most R_TALLY_MAX_ROUNDS, 1 = never (the tally after the pass counts f), 2 = wherever
-                       // the form allows (16-wave in-order workgroups)
-    int tally_in_f;    // f half of the tally inside the f pass's run kernel (gibbs_f_run_kernel counts what it stores): 0 = where a
-                       // sparse r pass follows in the same sweep (nothing else then carries it), 1 = never, 2 = wherever the run
-                       // form runs (tests: ahead of the pipelined and the step form)
-    int partial_chunk; // > 0: fcd_corr_partial walks at most this many subjects per chunk (tests: the chunking changes no bit)
-    int tangent_chunk; // > 0: the same for fcd_tangent_fit and fcd_tangent_apply (subjects) and fcd_sym_eigh (matrices)
-    int r_keep_words;  // 1: the tally makes the next pass's r words from the r bits (default: the pass's two r-word buffers swap
-                       // roles from sweep to sweep -- what a pass wrote as r_Sn is the next pass's r_S)
-    int r_sure;        // sparse r pass (gibbs_r_sparse_kernel: the sums of sites the tables decide are skipped): 0 = where the call's
-                       // bound build finds at least R_SURE_MIN_SHARE of the sites decided, 1 = never, 2 = wherever the bounds exist
-    double r_sure_x;   // TEST HOOK: > 1e-6 widens the range of x a decided site leaves to the full evaluation (0.25: half of all draws)
-};
 
 // kernels whose dynamic-LDS limit is raised with hipFuncSetAttribute: done once per (kernel, size) and remembered here
 enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA_F_PAIR_T = FCD_KA_F_PAIR + 4,
@@ -66,6 +26,61 @@ enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA
 
 #define FCD_NAN_SLOTS 256
 #define FCD_F_SLOTS 64
+// bytes of the context's fixed-size device blocks (fcd_ctx::acc, f_slots, nan_slots): what is allocated is what is cleared
+constexpr size_t FCD_ACC_BYTES = 8 * sizeof(unsigned long long);
+constexpr size_t FCD_F_SLOTS_BYTES = FCD_F_SLOTS * 8 * sizeof(unsigned long long);
+constexpr size_t FCD_NAN_SLOTS_BYTES = FCD_NAN_SLOTS * 16 * sizeof(unsigned long long);
+
+// A device block the context owns and only ever grows (fcd_buf_reserve: drain the device, free, allocate).  min_bytes: what
+// the first growth asks for at least.  zeroed / counted: the block is zero-filled when it grows / the growth adds one to
+// fcd_ctx::n_alloc.  Every block is counted and left as allocated but K_corr's tickets: their kernels find them zero and
+// leave them zero, so a new block must start that way, and n_alloc has never included them -- the stat is what callers
+// compare across calls, so it stays that way.
+struct fcd_dev_buf {
+    void *p;
+    size_t bytes;
+    size_t min_bytes;
+    bool zeroed, counted;
+};
+
+// The context's device words (fcd_ctx::words), 16 x 8 bytes: event counters read by fcd_ctx_stat under the names in quotes
+// and never reset by the library, and what the kernels of one sweep-loop call hand to each other.  The offsets are fixed
+// (static_asserts below): a kernel takes the block, or a pointer to one member.
+struct fcd_dev_words {
+    unsigned long long f_repeats;          // waves of the f pass that repeated an edge's sums in fp64 ("f_repeats")
+    unsigned long long r_exact_rows;       // rows of the r pass's in-order role decided on the exact path ("r_exact_rows")
+    unsigned long long f_sure_tiles;       // workgroups of the pair-tile f pass that took the decided-tile path ("f_sure_tiles")
+    unsigned long long f_sure_fallbacks;   // ... decided ones its vote sent back ("f_sure_fallbacks")
+    unsigned tile_decided, tile_open;      // the record build's "some tile is decided" / "some tile is open", zero between calls
+    const double *lM, *hyper;              // the call's lM and hyper, for the kernels that read its record table
+    unsigned long long reserved7;
+    unsigned long long r_sure_sites;       // (site, chain word) items a sparse r pass left to its tables ("r_sure_sites")
+    unsigned long long r_sure_exceptions;  // ... decided ones it evaluated in full all the same ("r_sure_exceptions")
+    unsigned long long r_decided;          // sites the r pass's bound build found decided, zero between calls
+    double hyper0[5];                      // the call's starting hyper (gibbs_f_hint_kernel: the bound build reads it there)
+};
+static_assert(sizeof(fcd_dev_words) == 128, "sixteen 8-byte words");
+static_assert(offsetof(fcd_dev_words, f_repeats) == 0 && offsetof(fcd_dev_words, r_exact_rows) == 8 &&
+                  offsetof(fcd_dev_words, f_sure_tiles) == 16 && offsetof(fcd_dev_words, f_sure_fallbacks) == 24,
+              "words 0-3");
+static_assert(offsetof(fcd_dev_words, tile_decided) == 32 && offsetof(fcd_dev_words, tile_open) == 36, "word 4");
+static_assert(offsetof(fcd_dev_words, lM) == 40 && offsetof(fcd_dev_words, hyper) == 48 &&
+                  offsetof(fcd_dev_words, reserved7) == 56,
+              "words 5-7");
+static_assert(offsetof(fcd_dev_words, r_sure_sites) == 64 && offsetof(fcd_dev_words, r_sure_exceptions) == 72 &&
+                  offsetof(fcd_dev_words, r_decided) == 80 && offsetof(fcd_dev_words, hyper0) == 88,
+              "words 8-15");
+
+// The pinned hint words the sweep loop polls (fcd_hint_wait).  f: the records kernel of build number n_frec_build leaves four
+// times that number, + 1 where some tile of its table has every edge decided (FCD_F_SURE_DRIFT nats in hand), + 2 where
+// every tile has.  r: the bound build of number n_rsure_build leaves four times that number, + 1 where at least
+// R_SURE_MIN_SHARE of the sites are decided, + 2 where any is.
+struct fcd_hint_words {
+    unsigned f, r;
+};
+// What the pinned error word (fcd_ctx::dev_err) carries; fcd_ctx_check turns it into a message
+constexpr unsigned FCD_DEV_ERR_R_ABANDONED = 1u;   // a device-side wait of the pipelined r pass was given up
+constexpr unsigned FCD_DEV_ERR_HARM_SITE = 2u;     // fcd_site_harmonize: a site id outside 0..B-1
 
 // The optional tallies fcd_gibbs_run adds to caller-owned uint32 buffers after a counted sweep, in the order it makes them:
 // (C, U, 3, 3) counts of (f_c, mixture case) (fcd_gibbs_set_pair_accumulator; one buffer, held in both places), (U, Nreg+1) /
@@ -78,18 +93,18 @@ enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA
 enum { FCD_ACC_PAIR, FCD_ACC_COUNT, FCD_ACC_COANOMALY, FCD_ACC_REGION_SET, FCD_ACC_PATIENT_GROUP, FCD_ACC_PATIENT_TRAIT, FCD_ACC_N };
 struct fcd_sweep_acc {
     uint32_t *buf[2];              // buf[0] == nullptr: detached (the patient-trait slot keeps its int64 buffer in buf[1])
-    int64_t nreg, u, every;        // the shape it was made for; added at every this many sweeps from accumulate_from on
+    int64_t nreg = 0, u = 0, every = 1;    // the shape it was made for; added at every this many sweeps from accumulate_from on
 };
 
+// Everything starts at zero (fcd_ctx_create value-initialises) but the members that say otherwise.
 struct fcd_ctx {
     int device;
-    int num_cu;
-    void *ws;          // reduction / partial-sum workspace
-    size_t ws_bytes;
+    int num_cu;        // of the device's properties (fcd_ctx_create)
+    fcd_dev_buf ws = {nullptr, 0, (size_t)1 << 20, false, true};      // reduction / partial-sum workspace
     fcd_knobs knobs;
     long long n_alloc;             // device allocations made by this context so far (fcd_ctx_stat "n_alloc")
     size_t lds_attr[FCD_KA_N];     // largest dynamic-LDS size already set per kernel
-    int pipe_occ[3];               // pipelined r pass: workgroups per CU of the three kernel variants (-1: not asked yet) ...
+    int pipe_occ[3] = {-1, -1, -1};        // pipelined r pass: workgroups per CU of the three kernel variants (-1: not asked yet) ...
     size_t pipe_occ_shmem[3];      // ... for this much dynamic LDS
     int pipe_occ_threads[3];       // ... and this many threads
     int64_t pipe_grid;             // last pipelined attempt of the r pass: its grid nD + nP + npad (fcd_ctx_stat "pipe_grid") ...
@@ -106,14 +121,10 @@ struct fcd_ctx {
     long long n_frun_pass;         // ... of them in the run form, gibbs_f_run_kernel (fcd_ctx_stat "f_run_passes")
     long long n_rsure_pass;        // r passes in the sparse form (fcd_ctx_stat "r_sure_passes")
     long long n_rsure_build;       // launches of the kernel that builds its site bounds (fcd_ctx_stat "r_sure_builds")
-    volatile unsigned *f_sure_hint;    // pinned host word: the records kernel of build number n_frec_build leaves four times that
-                                       // number here, + 1 where some tile of its table has every edge decided (FCD_F_SURE_DRIFT
-                                       // nats in hand), + 2 where every tile has.  The word behind it is the r pass's: the
-                                       // bound build of number n_rsure_build leaves four times that number, + 1 where at least
-                                       // R_SURE_MIN_SHARE of the sites are decided, + 2 where any is
+    volatile fcd_hint_words *hint;     // pinned host words of the two hint builds
     void *log_tab;     // K_lik tables (fcd_fastmath.h): 64 x 2^(-j/64), 512 x {1/m_i, log m_i} (device, 8.5 KiB)
-    volatile unsigned *dev_err;   // pinned host word: error word of the one-launch r pass, copied back after each pass
-    void *acc;         // 8 x uint64, zero between launches: the tally's pooled sums [0..3] and its ticket [4]
+    volatile unsigned *dev_err;   // pinned host word: error word of the one-launch r pass (FCD_DEV_ERR_*), polled by its kernels
+    void *acc;         // FCD_ACC_BYTES: 8 x uint64, zero between launches: the tally's pooled sums [0..3] and its ticket [4]
     void *f_slots;     // FCD_F_SLOTS 64-byte lines of 8 x uint64, zero between sweeps: the pooled f counts of a run kernel that counts
                        // ([0] zeros, [1] ones, [2] twos of a line), spread so that its workgroups do not queue on acc's line;
                        // folded into acc[1..3] by the r pass behind it (fcd_f_slots_fold)
@@ -122,32 +133,23 @@ struct fcd_ctx {
     void *comm;        // ncclComm_t of the context (fcd_comm_init), or nullptr: fcd_gibbs_run pools its M-step counts over it
     int comm_world, comm_rank;
     void *pool_counts; // 8 x int64 (device): the counts vector the all-reduce works on in place
-    void *dbg;         // 16 x uint64 event counters (fcd_ctx_stat): [0] waves of the f pass that repeated an edge's sums in fp64,
-                       // [1] rows of the r pass's in-order role decided on the exact path, [2] workgroups of the pair-tile f pass
-                       // that took the decided-tile path ("f_sure_tiles"), [3] decided ones its vote sent back
-                       // ("f_sure_fallbacks"), never reset by the library; [4] the record build's two words "some tile is decided" (low half) and
-                       // "some tile is open" (high half), zero between calls; [5], [6] the call's lM and hyper (FCD_DBG_LM);
-                       // [8] (site, chain word) items a sparse r pass left to its tables ("r_sure_sites"), [9] decided ones it
-                       // evaluated in full all the same ("r_sure_exceptions"); [10] sites the bound build found decided, zero
-                       // between calls; [11..15] the call's starting hyper (gibbs_f_hint_kernel: the bound build reads it there)
-    void *corr_tickets;            // K_corr: one ticket per subject, zero between launches (the last taker resets it)
-    size_t corr_tickets_n;
-    void *fsq;         // square copy of the f state [w][n][m][lane] the sweep loop keeps between its f and r pass
-    size_t fsq_bytes;
-    void *frec;        // pair records and edge constants of the pair-tile f pass (fcd_sweep_plan::frec_bytes), valid inside ONE
-    size_t frec_bytes; // sweep-loop call: it makes them from that call's lMf before the first pass that reads them
-    void *noise_rec;   // per-subject constants of the measurement-noise tables (fcd_lik_sessions.hip), valid inside ONE call:
-    size_t noise_rec_bytes;        // six doubles per control and per patient session, made by that call's first launch
+    fcd_dev_words *words;          // device (see the struct)
+    fcd_dev_buf corr_tickets = {nullptr, 0, 0, true, false};   // K_corr: one ticket per subject, zero between launches (the last taker resets it)
+    fcd_dev_buf fsq = {nullptr, 0, 0, false, true};    // square copy of the f state [w][n][m][lane] the sweep loop keeps between its f and r pass
+    fcd_dev_buf frec = {nullptr, 0, 0, false, true};   // pair records and edge constants of the pair-tile f pass (fcd_sweep_plan::frec_bytes), valid
+                                                       // inside ONE sweep-loop call: it makes them from that call's lMf before the first pass that reads them
+    // per-subject constants of the measurement-noise tables (fcd_lik_sessions.hip), valid inside ONE call: six doubles per
+    // control and per patient session, made by that call's first launch
+    fcd_dev_buf noise_rec = {nullptr, 0, (size_t)64 << 10, false, true};
     fcd_sweep_acc sweep_acc[FCD_ACC_N];
-    void *count_ws;                // per-chain counts of one tally, (U + Nreg) rows of GW*64 uint16 (fcd_count_ws_reserve)
-    size_t count_ws_bytes;
+    fcd_dev_buf count_ws = {nullptr, 0, 0, false, true};       // per-chain counts of one tally, (U + Nreg) rows of GW*64 uint16 (fcd_count_ws_reserve)
     // region sets (fcd_region_sets_set): J + 1 offsets, then the members (CSR, int32, device; owned), checked on the host
     void *rs_dev;
-    int64_t rs_J, rs_smax, rs_max_member;      // number of sets (0: none), largest set, largest member
+    int64_t rs_J, rs_smax, rs_max_member = -1; // number of sets (0: none), largest set, largest member
     // patient groups and contrasts (fcd_patient_groups_set): one device buffer (owned; layout in fcd_patient_groups.hip) of the
     // CSR, the contrasts, a bit mask over u per group and the contrasts' bin offsets, checked on the host
     void *pg_dev;
-    int64_t pg_J, pg_P, pg_umax, pg_max_member;        // groups (0: none), contrasts, largest group, largest member
+    int64_t pg_J, pg_P, pg_umax, pg_max_member = -1;   // groups (0: none), contrasts, largest group, largest member
     int64_t pg_total, pg_bins_max;                     // members in all groups; joint bins of the largest contrast
     int pg_with_rs;                                    // 1: the context's region sets are rows after the regions
     // patient traits (fcd_patient_traits_set): one device buffer (owned) of the words 2 score + known (Q, U) and the numbers
@@ -235,7 +237,9 @@ static inline int fcd_static_lds_check(fcd_ctx *ctx, const void *fn, int *done) 
 }
 
 int fcd_comm_allreduce_counts(fcd_ctx *ctx, long long *counts, hipStream_t stream);     // fcd_comm.hip: no-op without a communicator
-int fcd_ws_reserve(fcd_ctx *ctx, size_t bytes);
+// grow a context-owned block to at least this many bytes (no HIP call where it is large enough); a failed growth leaves it empty
+int fcd_buf_reserve(fcd_ctx *ctx, fcd_dev_buf &b, size_t bytes);
+static inline int fcd_ws_reserve(fcd_ctx *ctx, size_t bytes) { return fcd_buf_reserve(ctx, ctx->ws, bytes); }
 // fcd_corr_edges for a caller inside the library (fcd_corr_partial): its scratch starts ws_off bytes into the context's
 // workspace (the caller's own lies in front; `out` may point there once the caller has reserved ws_off +
 // fcd_corr_edges_ws_bytes), and the subject kernel slices the time axis as a call of S_slices subjects would -- a caller that
@@ -258,10 +262,6 @@ void fcd_corr_shrunk_plan(int64_t SC, int64_t Nreg, int64_t T, size_t base, fcd_
 int fcd_corr_shrunk_at(fcd_ctx *ctx, const double *x, int64_t Sc, int64_t Nreg, int64_t T, const int32_t *n_frames, int64_t s0,
                        int64_t S_call, int shrink_mode, double shrink_value, const fcd_shrunk_ws &w, size_t edges_off, double *A,
                        double *alpha, int32_t *info, hipStream_t stream);
-// square copy of the f state (see fcd_sweep_plan): grown like the workspace
-int fcd_fsq_reserve(fcd_ctx *ctx, size_t bytes);
-// prebuilt pair records of the f pass: grown like the square copy
-int fcd_frec_reserve(fcd_ctx *ctx, size_t bytes);
 // raise a kernel's dynamic-LDS limit if this size was not set before (no HIP call otherwise)
 static inline int fcd_lds_attr(fcd_ctx *ctx, int slot, const void *fn, size_t shmem) {
     if (shmem <= 64 * 1024 || shmem <= ctx->lds_attr[slot]) return FCD_OK;
@@ -298,7 +298,6 @@ int fcd_pair_tally_launch(fcd_ctx *ctx, const uint8_t *f_state, const uint64_t *
 // scratch they need is grown by fcd_count_ws_reserve (fcd_gibbs_run: before its sweep loop, through its table of the slots,
 // which is why the four *_ws_reserve take the same arguments)
 int fcd_count_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G);
-int fcd_count_ws_grow(fcd_ctx *ctx, size_t bytes);      // ... and by the tallies that share it: at least this many bytes
 int fcd_count_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, int64_t U, int64_t G, const fcd_geo &g,
                            uint32_t *hist_patient, uint32_t *hist_region, hipStream_t s);
 // the co-anomaly kernel of fcd_coanomaly.hip (one launch, no scratch): both pair matrices += the counts of this state
@@ -758,7 +757,7 @@ struct fcd_f_edge_rec {
 // tests/test_f_sure_rule.py restates the rule in NumPy.
 #define FCD_F_SURE_T 16.0
 #define FCD_F_SURE_DELTA_CAP 0.03125f
-#define FCD_F_SURE_DRIFT 6.0      // the table's hint (fcd_ctx::f_sure_hint) uses T - this: gamma moves with the M-steps of a call
+#define FCD_F_SURE_DRIFT 6.0      // the table's hint (fcd_ctx::hint) uses T - this: gamma moves with the M-steps of a call
 __host__ __device__ static inline int fcd_f_edge_mode(double c1, double c2, const float *b, float delta, double T) {
     if (!(delta <= FCD_F_SURE_DELTA_CAP)) return -1;
     const double c12 = c1 - c2;
@@ -829,7 +828,7 @@ struct fcd_sweep_step {
     bool tally_f_done;             // pipelined launch, or nullptr ... and whether one of them did (cleared by the sweep loop, set by the carrier)
     bool f_fold;                   // r pass: the run kernel has left the pooled f counts in fcd_ctx::f_slots; fold them into acc
     bool r_flip;                   // r pass: the two r-word buffers of the plan have swapped roles (r_S lies at pl.r_Sn, r_Sn at pl.r_S)
-    bool f_sure;                   // f pass (f_rec): some tile of the call's table has all its edges decided (fcd_ctx::f_sure_hint)
+    bool f_sure;                   // f pass (f_rec): some tile of the call's table has all its edges decided (fcd_ctx::hint)
     bool f_all;                    // ... and every tile has: the decided path runs in its run form (gibbs_f_run_kernel)
     bool r_sure;                   // r pass: the sparse form (the call's site bounds are built and the rule of the knob r_sure chose it)
 };

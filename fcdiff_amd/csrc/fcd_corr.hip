@@ -498,18 +498,11 @@ int fcd_corr_edges_at(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, i
         if (rc) return rc;
         // the tickets live in the context, zero between launches (the last taker of a subject puts its ticket back):
         // no memset launch per call.  Growing them synchronises, like growing the scratch.
-        if (ctx->corr_tickets_n < (size_t)S) {
-            FCD_HIP_TRY(hipDeviceSynchronize());
-            if (ctx->corr_tickets) (void)hipFree(ctx->corr_tickets);
-            ctx->corr_tickets = nullptr;
-            ctx->corr_tickets_n = 0;
-            FCD_HIP_TRY(hipMalloc(&ctx->corr_tickets, (size_t)S * sizeof(unsigned)));
-            FCD_HIP_TRY(hipMemset(ctx->corr_tickets, 0, (size_t)S * sizeof(unsigned)));
-            ctx->corr_tickets_n = (size_t)S;
-        }
-        unsigned *ticket = (unsigned *)ctx->corr_tickets;
-        double *part = (double *)((char *)ctx->ws + ws_off);
-        double *tmp = (double *)((char *)ctx->ws + ws_off + part_bytes);
+        rc = fcd_buf_reserve(ctx, ctx->corr_tickets, (size_t)S * sizeof(unsigned));
+        if (rc) return rc;
+        unsigned *ticket = (unsigned *)ctx->corr_tickets.p;
+        double *part = (double *)((char *)ctx->ws.p + ws_off);
+        double *tmp = (double *)((char *)ctx->ws.p + ws_off + part_bytes);
         const size_t shmem = ((size_t)2 * RP * 34 + 3 * RP) * sizeof(double);      // (panels [2][RP][34]: the kernel's SLD)
         rc = fcd_lds_attr(ctx, FCD_KA_CORR, reinterpret_cast<const void *>(&corr_gram_subject_kernel<TPW>), shmem);
         if (rc) return rc;
@@ -525,7 +518,7 @@ int fcd_corr_edges_at(fcd_ctx *ctx, const double *ts, int64_t S, int64_t Nreg, i
     // scratch, which synchronises, the first time a shape needs it)
     int rc = fcd_ws_reserve(ctx, ws_off + ((size_t)rows * 2 + (size_t)S * C) * sizeof(double));
     if (rc) return rc;
-    double *mean = (double *)((char *)ctx->ws + ws_off), *sdev = mean + rows, *tmp = sdev + rows;
+    double *mean = (double *)((char *)ctx->ws.p + ws_off), *sdev = mean + rows, *tmp = sdev + rows;
     hipLaunchKernelGGL(corr_moments_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ts, rows, (int)T, mean, sdev);
     FCD_LAUNCH_CHECK();
     const int64_t nb = (Nreg + CB - 1) / CB;

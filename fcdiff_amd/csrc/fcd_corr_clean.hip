@@ -448,7 +448,7 @@ extern "C" int fcd_corr_clean(fcd_ctx *ctx, const double *ts, const double *conf
     const size_t n_int = (size_t)S * T + (size_t)S + (size_t)rows + (size_t)S + (size_t)S * QMAX;
     int rc = fcd_ws_reserve(ctx, n_dbl * sizeof(double) + n_int * sizeof(int));
     if (rc) return rc;
-    double *G = (double *)ctx->ws, *beta = G + nG, *Lc = beta + nB, *mean = Lc + nL, *ss = mean + rows, *scale = ss + rows;
+    double *G = (double *)ctx->ws.p, *beta = G + nG, *Lc = beta + nB, *mean = Lc + nL, *ss = mean + rows, *scale = ss + rows;
     int *idx = (int *)(scale + rows), *nk = idx + (size_t)S * T, *flag = nk + S, *sflag = flag + rows, *piv = sflag + S;
     const int N = (int)Nreg, Qi = (int)Q, Ti = (int)T;
     hipLaunchKernelGGL(clean_index_kernel, dim3((unsigned)S), dim3(256), 0, st, frame_mask, Ti, idx, nk);

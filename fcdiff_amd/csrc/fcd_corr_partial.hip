@@ -447,7 +447,7 @@ int fcd_corr_shrunk_at(fcd_ctx *ctx, const double *x, int64_t Sc, int64_t Nreg, 
                        double *alpha, int32_t *info, hipStream_t st) {
     const int64_t C = fcd_tri(Nreg);
     const int PL = w.PL, NBT = w.NBT;
-    char *ws = (char *)ctx->ws;
+    char *ws = (char *)ctx->ws.p;
     double *redge = (double *)(ws + w.o_redge), *Fsum = (double *)(ws + w.o_F);
     double *mean = (double *)(ws + w.o_mean), *isd = (double *)(ws + w.o_isd), *qpart = (double *)(ws + w.o_q);
     double *rowF = (double *)(ws + w.o_rowF);
@@ -511,7 +511,7 @@ extern "C" int fcd_corr_partial(fcd_ctx *ctx, const double *ts, int64_t S, int64
     const size_t mine = o_dinv + pc_align((size_t)SC * PL * sizeof(double));
     rc = fcd_ws_reserve(ctx, mine + fcd_corr_edges_ws_bytes(ctx, SC, Nreg, T, S));
     if (rc) return rc;
-    char *ws = (char *)ctx->ws;
+    char *ws = (char *)ctx->ws.p;
     double *A = (double *)(ws + w.o_A), *dinv = (double *)(ws + o_dinv);
     const int32_t *live = (const int32_t *)(ws + w.o_live);
     const unsigned inv_threads = RT >= 8 ? 1024u : 256u;

@@ -490,7 +490,7 @@ extern "C" int fcd_sym_eigh(fcd_ctx *ctx, const fcd_eigh_desc *d) {
     for (int64_t b0 = 0; b0 < d->B; b0 += BC) {
         const int64_t Bc = d->B - b0 < BC ? d->B - b0 : BC;
         rc = eig_launch(ctx, st, d->A + b0 * n2, n, n2, n, Bc, d->w + b0 * n, n, d->V + b0 * n2, n, n2, n, d->status + b0, 1,
-                        (double *)ctx->ws);
+                        (double *)ctx->ws.p);
         if (rc) return rc;
     }
     return FCD_OK;
@@ -513,7 +513,7 @@ extern "C" int fcd_tangent_apply(fcd_ctx *ctx, const fcd_tangent_desc *d) {
     const size_t mine = tg_bufs_plan(SC, n, PL, o_W + tg_align((size_t)P2 * sizeof(double)), off);
     rc = fcd_ws_reserve(ctx, mine + fcd_corr_edges_ws_bytes(ctx, SC, Nreg, T, S));
     if (rc) return rc;
-    char *ws = (char *)ctx->ws;
+    char *ws = (char *)ctx->ws.p;
     double *A = (double *)(ws + w.o_A), *Wp = (double *)(ws + o_W);
     const tg_bufs b = tg_bufs_at(ws, off, n, PL);
     hipLaunchKernelGGL(tg_pad_kernel, dim3((unsigned)((P2 + 255) / 256)), dim3(256), 0, st, d->W, n, PL, Wp);
@@ -561,7 +561,7 @@ extern "C" int fcd_tangent_fit(fcd_ctx *ctx, const fcd_tangent_desc *d) {
     if (mine > ((size_t)64 << 30)) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "H=%lld controls of %lld regions need more than 64 GiB", H, Nreg);
     rc = fcd_ws_reserve(ctx, mine + fcd_corr_edges_ws_bytes(ctx, SC, Nreg, T, H));
     if (rc) return rc;
-    char *ws = (char *)ctx->ws;
+    char *ws = (char *)ctx->ws.p;
     double *RA = (double *)(ws + o_RA), *Gp = (double *)(ws + o_G), *Ghp = (double *)(ws + o_Gh), *Wp = (double *)(ws + o_W);
     double *Tb = (double *)(ws + o_Tb), *norm_d = (double *)(ws + o_sc);
     int32_t *gstat = (int32_t *)(ws + o_sc + 8);

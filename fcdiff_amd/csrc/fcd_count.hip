@@ -131,18 +131,6 @@ __global__ __launch_bounds__(PB_THREADS) void poisson_binomial_kernel(const doub
 
 }  // namespace
 
-int fcd_count_ws_grow(fcd_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->count_ws_bytes) return FCD_OK;
-    FCD_HIP_TRY(hipDeviceSynchronize());
-    if (ctx->count_ws) FCD_HIP_TRY(hipFree(ctx->count_ws));
-    ctx->count_ws = nullptr;
-    ctx->count_ws_bytes = 0;
-    FCD_HIP_TRY(hipMalloc(&ctx->count_ws, bytes));
-    ctx->count_ws_bytes = bytes;
-    ctx->n_alloc += 1;
-    return FCD_OK;
-}
-
 int fcd_count_ws_reserve(fcd_ctx *ctx, int64_t Nreg, int64_t U, int64_t G) {
     return tally_ws_reserve(ctx, Nreg + U, G, sizeof(uint16_t));
 }
@@ -154,7 +142,7 @@ int fcd_count_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nreg, i
                         Nreg, U);
     int rc = fcd_count_ws_reserve(ctx, Nreg, U, G);         // (no-op when fcd_gibbs_run has grown it)
     if (rc) return rc;
-    uint16_t *sums = (uint16_t *)ctx->count_ws;
+    uint16_t *sums = (uint16_t *)ctx->count_ws.p;
     int64_t tn = CNT_TILE_WORDS / U;
     if (tn > Nreg) tn = Nreg;
     hipLaunchKernelGGL(count_sums_kernel, dim3(tally_grid(ctx, g.GW)), dim3(CNT_THREADS), (size_t)(tn * U) * sizeof(uint64_t), s,

@@ -439,7 +439,7 @@ extern "C" int fcd_edge_cov_fit(fcd_ctx *ctx, const double *b, int64_t C, int64_
     // Nothing of the workspace outlives the call.
     int rc = fcd_ws_reserve(ctx, (size_t)(2 * H * CQ + CQ) * sizeof(double) + 4 * sizeof(int));
     if (rc) return rc;
-    const cov_ws ws = cov_ws_at(ctx->ws, H);
+    const cov_ws ws = cov_ws_at(ctx->ws.p, H);
     if (Q > 0) {
         hipLaunchKernelGGL(cov_design_kernel, dim3(1), dim3(64), 0, st, z, (int)H, (int)Q, ws);
         FCD_LAUNCH_CHECK();

@@ -208,7 +208,7 @@ extern "C" int fcd_evidence_energy(fcd_ctx *ctx, const double *S_B, const double
     const int64_t GP = (int64_t)g.GW * 64;
     rc = fcd_ws_reserve(ctx, (size_t)S * (size_t)GP * sizeof(double));
     if (rc) return rc;
-    double *part = (double *)ctx->ws;
+    double *part = (double *)ctx->ws.p;
     hipStream_t s = (hipStream_t)stream;
     const int groups = (g.GW + EV_NW * EV_K - 1) / (EV_NW * EV_K);
     hipLaunchKernelGGL(evidence_energy_kernel, dim3((unsigned)S, (unsigned)groups), dim3(64 * EV_NW), 0, s, S_B, lM, f_state, r_bits,

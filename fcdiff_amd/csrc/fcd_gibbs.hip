@@ -390,7 +390,6 @@ __device__ __attribute__((noinline)) int fcd_f_abs_edge_masks(const double *__re
 // keeps its arguments, and what the second call needs (the tables, the edge, the lane's chain) lives through the whole kernel
 // anyway -- the registers of the edge loop stay what they were.
 constexpr int FCD_F_OPEN = 4;
-constexpr int FCD_DBG_LM = 5;        // the context's device words that hold lM and hyper of the call's record table (word 4: any_tile)
 __device__ __attribute__((noinline)) int fcd_f_exact_edge(const double *__restrict__ row, double c1, double c2, uint32_t z0, uint32_t z1,
                                                           uint32_t z2, uint32_t z3, int U, uint32_t xw) {
     const int NPAIR = (U + 1) >> 1, NG = (NPAIR + 7) >> 3;
@@ -509,7 +508,7 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
                                                             const double *__restrict__ hyper, uint8_t *__restrict__ f_state,
                                                             const uint32_t *__restrict__ r_U, int Nreg, int U, int64_t C,
                                                             int GW, uint32_t chain0, uint64_t seed, uint32_t sweep, float margin, uint8_t *__restrict__ fsq,
-                                                            uint2 *__restrict__ f_S, int NBLK, unsigned long long *__restrict__ dbg,
+                                                            uint2 *__restrict__ f_S, int NBLK, fcd_dev_words *__restrict__ dbg,
                                                             const char *__restrict__ frec, const double *__restrict__ lM) {
     static_assert(PT || !PRE, "prebuilt records are laid out by pair-aligned tile");
     static_assert(PRE || !SURE, "the edges' bounds are part of the prebuilt records");
@@ -569,7 +568,7 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
             __syncthreads();
             const bool back = __ballot(lane < (int)(blockDim.x >> 6) && vote[lane < 16 ? lane : 0] != 0u) != 0ull;
             if (!back) {
-                if (threadIdx.x == 0) atomicAdd(dbg + 2, 1ull);
+                if (threadIdx.x == 0) atomicAdd(&dbg->f_sure_tiles, 1ull);
                 if (w >= GW) return;
                 uint32_t kt = 0;
 #pragma unroll
@@ -584,7 +583,7 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
                 return;
             }
             // the vote words are read; the copy below writes other addresses, and its barrier comes before anything else
-            if (threadIdx.x == 0) atomicAdd(dbg + 3, 1ull);
+            if (threadIdx.x == 0) atomicAdd(&dbg->f_sure_fallbacks, 1ull);
         }
     }
     // the r words of the tile's edges: loaded before the barrier so their latency hides behind the staging.
@@ -834,7 +833,7 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
                                      NW16 > 1 ? Zc[NW16 > 1 ? 1 : 0] : 0u, NW16 > 2 ? Zc[NW16 > 2 ? 2 : 0] : 0u, NW16 > 3 ? Zc[NW16 > 3 ? 3 : 0] : 0u, U, xw);
                 kt |= (uint32_t)(k >> 2) << (16 + e);       // (FCD_F_OPEN: this lane's draw of edge e is made again behind the loop)
                 k &= 3;
-                if (lane == 0) atomicAdd(dbg, 1ull);
+                if (lane == 0) atomicAdd(&dbg->f_repeats, 1ull);
             }
 #ifdef FCD_ABLATE
             asm volatile("" ::"v"(k));
@@ -874,8 +873,8 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
         // log-weights -- never on finite tables with positive gamma.  On the call's record table (PRE) lM and hyper are read from
         // the device words gibbs_f_hint_kernel left them in, not from the arguments: a value that has to live to the end of the kernel
         // costs every wave scalar moves in its prologue (the decided-tile path is little else), and dbg lives that long anyway.
-        const double *__restrict__ lMa = PRE ? reinterpret_cast<const double *>(dbg[FCD_DBG_LM]) : lM;
-        const double *__restrict__ hya = PRE ? reinterpret_cast<const double *>(dbg[FCD_DBG_LM + 1]) : hyper;
+        const double *__restrict__ lMa = PRE ? dbg->lM : lM;
+        const double *__restrict__ hya = PRE ? dbg->hyper : hyper;
 #pragma unroll 1
         for (int e = 0; e < FP_EC; ++e) {
             const bool open = (kt >> (16 + e)) & 1u;
@@ -914,11 +913,11 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pair_kernel(const double *__r
 // (wave e = edge e, lane = patient, fp_edge_bound) -- and gibbs_f_pair_kernel<.., true, true> copies it.  Layout: see PRE.
 // Pieces of edges the tile does not hold (past the diagonal) are never written and never read.
 // It also leaves every edge's bounds for the rule of decided edges (fcd_f_edge_mode) and, where some tile has all its edges
-// decided at the call's starting hyper with FCD_F_SURE_DRIFT nats in hand, a 1 in *any_tile: a table without such a tile is
+// decided at the call's starting hyper with FCD_F_SURE_DRIFT nats in hand, a 1 in dbg->tile_decided: a table without such a tile is
 // read by the kernel without the decided-tile path.
 __global__ __launch_bounds__(64 * FP_EC) void gibbs_f_records_kernel(const double *__restrict__ S_B, const double *__restrict__ lMf,
                                                                      const double *__restrict__ hyper, int Nreg, int U,
-                                                                     char *__restrict__ frec, unsigned *__restrict__ any_tile,
+                                                                     char *__restrict__ frec, fcd_dev_words *__restrict__ dbg,
                                                                      unsigned *__restrict__ votes, int n_votes) {
     const int NPAIR = (U + 1) >> 1;
     const fpt_tile T = fpt_locate((int)blockIdx.x, Nreg);
@@ -991,21 +990,20 @@ __global__ __launch_bounds__(64 * FP_EC) void gibbs_f_records_kernel(const doubl
     // (every tile that has the property stores the same word: no atomic, no fence -- gibbs_f_hint_kernel reads it behind
     // this launch)
     // ... and every tile that lacks it stores a 1 into the word beside it: "some tile is open"
-    if (threadIdx.x == 0 && (T.cnt0 > 0 || T.cnt1 > 0)) any_tile[open_edges ? 1 : 0] = 1u;
+    if (threadIdx.x == 0 && (T.cnt0 > 0 || T.cnt1 > 0)) *(open_edges ? &dbg->tile_open : &dbg->tile_decided) = 1u;
 }
 // ... and hands it to the host: 4 build + 2 all + any into the pinned word the sweep loop polls (written once, complete; all =
 // some tile is decided and none is open), the device words cleared for the next build.
-// It also leaves the call's lM and hyper where the kernels that read the table find them (dbg[FCD_DBG_LM], [FCD_DBG_LM + 1]:
-// the words behind any_tile's).
-__global__ void gibbs_f_hint_kernel(unsigned *__restrict__ any_tile, volatile unsigned *hint, unsigned build, const double *lM,
+// It also leaves the call's lM and hyper where the kernels that read the table find them (dbg->lM, dbg->hyper).
+__global__ void gibbs_f_hint_kernel(fcd_dev_words *__restrict__ dbg, volatile unsigned *hint, unsigned build, const double *lM,
                                     const double *hyper) {
-    const unsigned any = any_tile[0] != 0u ? 1u : 0u, all = (any && any_tile[1] == 0u) ? 1u : 0u;
-    any_tile[0] = 0u;
-    any_tile[1] = 0u;
-    reinterpret_cast<unsigned long long *>(any_tile)[1] = (unsigned long long)(uintptr_t)lM;
-    reinterpret_cast<unsigned long long *>(any_tile)[2] = (unsigned long long)(uintptr_t)hyper;
-    // ... and the starting hyper itself for the r pass's bound build, which runs after the first M-step (dbg[11..15]; any_tile = dbg + 4)
-    for (int i = 0; i < 5; ++i) reinterpret_cast<double *>(any_tile)[7 + i] = hyper[i];
+    const unsigned any = dbg->tile_decided != 0u ? 1u : 0u, all = (any && dbg->tile_open == 0u) ? 1u : 0u;
+    dbg->tile_decided = 0u;
+    dbg->tile_open = 0u;
+    dbg->lM = lM;
+    dbg->hyper = hyper;
+    // ... and the starting hyper itself for the r pass's bound build, which runs after the first M-step
+    for (int i = 0; i < 5; ++i) dbg->hyper0[i] = hyper[i];
     __hip_atomic_store(const_cast<unsigned *>(hint), 4u * build + 2u * all + any, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -1091,7 +1089,7 @@ __global__ __launch_bounds__(64 * FR_WAVES) void gibbs_f_run_kernel(const double
                                                            const double *__restrict__ hyper, uint8_t *__restrict__ f_state,
                                                            const uint32_t *__restrict__ r_U, int Nreg, int U, int64_t C, int GW,
                                                            uint32_t chain0, uint64_t seed, uint32_t sweep, float margin,
-                                                           uint2 *__restrict__ f_S, int NBLK, unsigned long long *__restrict__ dbg,
+                                                           uint2 *__restrict__ f_S, int NBLK, fcd_dev_words *__restrict__ dbg,
                                                            const char *__restrict__ frec, const double *__restrict__ lM, int n_tiles,
                                                            unsigned *__restrict__ votes, int64_t G,
                                                            unsigned long long *__restrict__ slots, uint32_t *__restrict__ cnt_f) {
@@ -1175,7 +1173,7 @@ __global__ __launch_bounds__(64 * FR_WAVES) void gibbs_f_run_kernel(const double
                     const double lg1 = hyper[FCD_H_LNGAMMA + 1] - hyper[FCD_H_LNGAMMA + 0], lg2 = hyper[FCD_H_LNGAMMA + 2] - hyper[FCD_H_LNGAMMA + 0];
                     k = (uint32_t)fcd_f_exact_edge(lMf + c * U * 6, lg1 + (S_B[c * 3 + 1] - S_B[c * 3 + 0]), lg2 + (S_B[c * 3 + 2] - S_B[c * 3 + 0]),
                                                    Z.x, Z.y, Z.z, Z.w, U, xw);
-                    if (lane == 0) atomicAdd(dbg, 1ull);
+                    if (lane == 0) atomicAdd(&dbg->f_repeats, 1ull);
                     const bool open = (k & FCD_F_OPEN) != 0;
                     k &= 3u;
                     if (__ballot(open) != 0ull) {
@@ -1329,8 +1327,8 @@ __global__ __launch_bounds__(64 * FR_WAVES) void gibbs_f_run_kernel(const double
             }
         }
         if (lane == 0) {
-            if (n_sure) atomicAdd(dbg + 2, (unsigned long long)n_sure);
-            if (n_back) atomicAdd(dbg + 3, (unsigned long long)n_back);
+            if (n_sure) atomicAdd(&dbg->f_sure_tiles, (unsigned long long)n_sure);
+            if (n_back) atomicAdd(&dbg->f_sure_fallbacks, (unsigned long long)n_back);
         }
     }
 }
@@ -1351,7 +1349,7 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pairx_kernel(const double *__
                                                                 const uint32_t *__restrict__ r_U, int Nreg, int U, int64_t C,
                                                                 int GW, uint32_t chain0, uint64_t seed, uint32_t sweep,
                                                                 float margin, uint8_t *__restrict__ fsq,
-                                                                unsigned long long *__restrict__ dbg, const double *__restrict__ lM) {
+                                                                fcd_dev_words *__restrict__ dbg, const double *__restrict__ lM) {
     // pairs [EC][NPAIR][16] float2 | per-edge constants [8] float4 | staging scratch [waves][2][24] double2
     extern __shared__ __attribute__((aligned(256))) double ptile[];
     const int NPAIR = (U + 1) >> 1, NW16 = (U + 15) >> 4;
@@ -1537,7 +1535,7 @@ __global__ __launch_bounds__(1024, 8) void gibbs_f_pairx_kernel(const double *__
                 const int ka = fcd_f_abs_draw(S_B + c * 3, hyper, a, fcd_u32(xw));
                 if (open) k = ka;
             }
-            if (lane == 0) atomicAdd(dbg, 1ull);
+            if (lane == 0) atomicAdd(&dbg->f_repeats, 1ull);
         }
         (f_state + ((int64_t)w * C + c) * 64)[(uint32_t)lane] = (uint8_t)k;     // (scalar base + lane)
         if (fsq) {
@@ -1936,7 +1934,7 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         // pair / triple forms: per-lane slot words over patients (scratch in the ctx workspace), records in LDS
         rc = fcd_ws_reserve(ctx, pl.ws_bytes);
         if (rc) return rc;
-        uint32_t *r_U = (uint32_t *)((char *)ctx->ws + pl.r_U);
+        uint32_t *r_U = (uint32_t *)((char *)ctx->ws.p + pl.r_U);
         if (!st.ru_ready) {     // (inside the sweep loop the previous sweep's tally has made them already)
             const int64_t items = (int64_t)g.GW * Nreg * pl.f_NW;
             hipLaunchKernelGGL(pack_ru_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, c.r_bits, (int)Nreg, (int)U,
@@ -1946,12 +1944,12 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         dim3 grid((unsigned)((g.C + pl.f_EC - 1) / pl.f_EC), (unsigned)((g.GW + wpb - 1) / wpb));
         // pair-aligned tiles that write the r pass's f words themselves (fcd_sweep_step::f_packed; U <= 64 kernel only)
         const bool pt = st.f_packed && form == FCD_F_PAIR;
-        if (st.f_rec && (!pt || !pl.frec_bytes || ctx->frec_bytes < pl.frec_bytes))
+        if (st.f_rec && (!pt || !pl.frec_bytes || ctx->frec.bytes < pl.frec_bytes))
             return fcd_fail(ctx, FCD_ERR_ARG, "f pass: prebuilt records asked for where the plan has none");
         const size_t f_shmem = st.f_rec ? pl.f_shmem_rec : pl.f_shmem;
         if (st.f_packed && (form != FCD_F_PAIR || !pl.r_blocked || st.fsq))
             return fcd_fail(ctx, FCD_ERR_ARG, "f pass: packed f words asked for where the plan has none");
-        uint2 *f_S = pt ? (uint2 *)((char *)ctx->ws + pl.f_S) : nullptr;
+        uint2 *f_S = pt ? (uint2 *)((char *)ctx->ws.p + pl.f_S) : nullptr;
         const int NBLK = (int)((Nreg + R_NB - 1) / R_NB);
         if (pt) grid.x = (unsigned)fpt_tiles((Nreg + 1) / 2);
 #define FCD_F_ARGS c.S_B, c.lMf, c.hyper, c.f_state, r_U, (int)Nreg, (int)U, g.C, g.GW, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, margin, st.fsq
@@ -1968,8 +1966,8 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         hipLaunchKernelGGL(KERN, grid, dim3(64 * wpb), f_shmem, s, FCD_F_ARGS, EXTRA);                        \
         fcd_prof_end(ctx, FCD_PROF_F, s);                                                                     \
     } while (0)
-#define FCD_PX (unsigned long long *)ctx->dbg, c.lM
-#define FCD_PT f_S, NBLK, (unsigned long long *)ctx->dbg, (const char *)st.f_rec, c.lM
+#define FCD_PX ctx->words, c.lM
+#define FCD_PT f_S, NBLK, ctx->words, (const char *)st.f_rec, c.lM
         const bool sure = form == FCD_F_PAIR && pt && st.f_rec && st.f_sure && !(margin > 1.f) && ctx->knobs.f_sure != 1;
         if (sure && ctx->knobs.f_runs != 1 && (st.f_all || ctx->knobs.f_runs == 2)) {
             // every tile decided at the hint (or knob f_runs = 2): the decided path in block-wide runs -- no dynamic LDS
@@ -1983,7 +1981,7 @@ int fcd_gibbs_f_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
                 tf = st.tally_f;
             fcd_prof_begin(ctx, FCD_PROF_F, s);
             hipLaunchKernelGGL(gibbs_f_run_kernel, rgrid, dim3(64 * rw), 0, s, c.S_B, c.lMf, c.hyper, c.f_state, r_U, (int)Nreg, (int)U, g.C,
-                               g.GW, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, margin, f_S, NBLK, (unsigned long long *)ctx->dbg,
+                               g.GW, (uint32_t)c.chain0, c.seed, (uint32_t)st.sweep, margin, f_S, NBLK, ctx->words,
                                (const char *)st.f_rec, c.lM, (int)grid.x, (unsigned *)((char *)st.f_rec + pl.frec_votes), c.G,
                                (tf && tf->acc) ? (unsigned long long *)ctx->f_slots : nullptr, tf ? tf->cnt_f : nullptr);
             fcd_prof_end(ctx, FCD_PROF_F, s);
@@ -2171,40 +2169,26 @@ static const struct {
 // packed_ok, the cleared marks of the next r pass (whose r words are the ones this pass wrote); its f half rides in the packing
 // launch or in the pipelined r pass where they take it.  hyper_m: what the M-step writes (nullptr when mstep_every == 0); acc_mask: the
 // slots of the context's sweep accumulators to add to (bit k = slot k).
-// The hint of the record build just queued (gibbs_f_hint_kernel writes 4 build + 2 all + any): polled in the
-// pinned word for as long as a build can reasonably take, then behind a synchronisation of the stream.
-static int fcd_f_sure_hint_wait(fcd_ctx *ctx, hipStream_t s, bool &any, bool &all) {
-    const unsigned build = (unsigned)(ctx->n_frec_build & 0x3fffffff);
+// The hint of a build just queued (gibbs_f_hint_kernel writes 4 build + 2 all + any, gibbs_r_hint_kernel 4 build + 2 any + share):
+// polled in its pinned word (ctx->hint->f or ->r) for as long as a build can reasonably take, then behind a synchronisation of
+// the stream.  n_build: the number of the build awaited; msg: what to say where none arrives; bit0 / bit1: the hint's two low
+// bits.  The r pass's bound build runs behind the call's first sweep, so its wait lasts until the device has finished that
+// sweep -- once per call, with the second sweep already queued.
+static int fcd_hint_wait(fcd_ctx *ctx, hipStream_t s, const volatile unsigned *word, long long n_build, const char *msg, bool &bit0,
+                         bool &bit1) {
+    const unsigned build = (unsigned)(n_build & 0x3fffffff);
     const auto t0 = std::chrono::steady_clock::now();
-    unsigned v = *ctx->f_sure_hint;
-    for (unsigned spin = 1; (v >> 2) != build; ++spin, v = *ctx->f_sure_hint) {
+    unsigned v = *word;
+    for (unsigned spin = 1; (v >> 2) != build; ++spin, v = *word) {
         if ((spin & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
             FCD_HIP_TRY(hipStreamSynchronize(s));
-            v = *ctx->f_sure_hint;
-            if ((v >> 2) != build) return fcd_fail(ctx, FCD_ERR_DEVICE, "f pass: the record build left no hint");
+            v = *word;
+            if ((v >> 2) != build) return fcd_fail(ctx, FCD_ERR_DEVICE, msg);
             break;
         }
     }
-    any = (v & 1u) != 0u;
-    all = (v & 2u) != 0u;
-    return FCD_OK;
-}
-// the same for the r pass's bound build (the word behind: 4 build + 2 any + share): the build runs behind the call's first
-// sweep, so this wait lasts until the device has finished that sweep -- once per call, with the second sweep already queued
-static int fcd_r_sure_hint_wait(fcd_ctx *ctx, hipStream_t s, bool &share, bool &any) {
-    const unsigned build = (unsigned)(ctx->n_rsure_build & 0x3fffffff);
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned v = ctx->f_sure_hint[1];
-    for (unsigned spin = 1; (v >> 2) != build; ++spin, v = ctx->f_sure_hint[1]) {
-        if ((spin & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-            FCD_HIP_TRY(hipStreamSynchronize(s));
-            v = ctx->f_sure_hint[1];
-            if ((v >> 2) != build) return fcd_fail(ctx, FCD_ERR_DEVICE, "r pass: the bound build left no hint");
-            break;
-        }
-    }
-    share = (v & 1u) != 0u;
-    any = (v & 2u) != 0u;
+    bit0 = (v & 1u) != 0u;
+    bit1 = (v & 2u) != 0u;
     return FCD_OK;
 }
 
@@ -2222,9 +2206,9 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
     // the square copy of the f state: where the plan has one, both tables are there and the edge ids are symmetric
     uint8_t *fsq = nullptr;
     if (pl.fsq_bytes && c.lMf && c.lMd && c.edge_mode == FCD_EDGE_SYMMETRIC) {
-        int rc = fcd_fsq_reserve(ctx, pl.fsq_bytes);
+        int rc = fcd_buf_reserve(ctx, ctx->fsq, pl.fsq_bytes);
         if (rc) return rc;
-        fsq = (uint8_t *)ctx->fsq;
+        fsq = (uint8_t *)ctx->fsq.p;
     }
     // From the second sweep of a call on, the U <= 64 f pass writes the r pass's f words itself (pair-aligned tiles), the r
     // pass before it has left the r words and the tally before it has cleared the marks: no packing launch.  The first sweep, the any-U f kernel,
@@ -2243,21 +2227,21 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
     // Without the buffer (above F_REC_CAP, or no room on the device) the tiles build their own records as before.
     const int64_t pt_sweeps = packed_ok ? n_sweeps - 1 : 0;
     bool use_rec = pl.frec_bytes && ctx->knobs.f_records != 1 && pt_sweeps >= (ctx->knobs.f_records == 2 ? 1 : F_REC_MIN_SWEEPS);
-    if (use_rec && fcd_frec_reserve(ctx, pl.frec_bytes) != FCD_OK) {
+    if (use_rec && fcd_buf_reserve(ctx, ctx->frec, pl.frec_bytes) != FCD_OK) {
         (void)hipGetLastError();
         use_rec = false;
     }
     // The build is queued BEFORE the first sweep (which does not read it): by the time the second sweep is queued its hint --
     // has the table decided tiles? -- has long arrived in its pinned word, and the host reads it there without a call into the
-    // runtime and without the device ever running dry (fcd_f_sure_hint_wait).
+    // runtime and without the device ever running dry (fcd_hint_wait).
     bool rec_built = false;
     if (use_rec) {
         ctx->n_frec_build += 1;
         hipLaunchKernelGGL(gibbs_f_records_kernel, dim3((unsigned)fpt_tiles((Nreg + 1) / 2)), dim3(64 * FP_EC), 0, s, c.S_B, c.lMf,
-                           c.hyper, (int)Nreg, (int)U, (char *)ctx->frec, (unsigned *)((unsigned long long *)ctx->dbg + 4),
-                           (unsigned *)((char *)ctx->frec + pl.frec_votes), (int)((pl.frec_bytes - pl.frec_votes) / sizeof(unsigned)));
+                           c.hyper, (int)Nreg, (int)U, (char *)ctx->frec.p, ctx->words,
+                           (unsigned *)((char *)ctx->frec.p + pl.frec_votes), (int)((pl.frec_bytes - pl.frec_votes) / sizeof(unsigned)));
         FCD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(gibbs_f_hint_kernel, dim3(1), dim3(1), 0, s, (unsigned *)((unsigned long long *)ctx->dbg + 4), ctx->f_sure_hint,
+        hipLaunchKernelGGL(gibbs_f_hint_kernel, dim3(1), dim3(1), 0, s, ctx->words, &ctx->hint->f,
                            (unsigned)(ctx->n_frec_build & 0x3fffffff), c.lM, c.hyper);
         FCD_LAUNCH_CHECK();
         rec_built = true;
@@ -2277,14 +2261,14 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         st.fsq = st.f_packed ? nullptr : fsq;
         if (rs_state == 1 && st.f_packed) {
             bool share = false, any = false;
-            int rc = fcd_r_sure_hint_wait(ctx, s, share, any);
+            int rc = fcd_hint_wait(ctx, s, &ctx->hint->r, ctx->n_rsure_build, "r pass: the bound build left no hint", share, any);
             if (rc) return rc;
             rs_state = (kn.r_sure == 2 || share) ? 2 : -1;
         }
         if (rec_built && st.f_packed && !st.f_rec) {
-            int rc = fcd_f_sure_hint_wait(ctx, s, st.f_sure, st.f_all);
+            int rc = fcd_hint_wait(ctx, s, &ctx->hint->f, ctx->n_frec_build, "f pass: the record build left no hint", st.f_sure, st.f_all);
             if (rc) return rc;
-            st.f_rec = ctx->frec;
+            st.f_rec = ctx->frec.p;
             if (rs_ok && (st.f_sure || kn.r_sure == 2)) {
                 rc = fcd_gibbs_r_bounds_build(ctx, c);
                 if (rc) return rc;
@@ -2314,20 +2298,20 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         if (rc) {
             // the run kernel, the packing launch or a pipelined pass may already have added this sweep's f counts into the context's accumulators and no tally
             // will draw the ticket that zeroes them: leave them clean for the next call
-            if (tf.acc) (void)hipMemsetAsync(ctx->acc, 0, 8 * sizeof(unsigned long long), s);
+            if (tf.acc) (void)hipMemsetAsync(ctx->acc, 0, FCD_ACC_BYTES, s);
             // (... and a run kernel that counted has left them in its slot lines if the pass failed before it folded them)
-            if (st.f_fold) (void)hipMemsetAsync(ctx->f_slots, 0, FCD_F_SLOTS * 8 * sizeof(unsigned long long), s);
+            if (st.f_fold) (void)hipMemsetAsync(ctx->f_slots, 0, FCD_F_SLOTS_BYTES, s);
             return rc;
         }
         st.sentinels_in_place = pair_form && ctx->r_form_last == 2;        // (a pipelined pass has just been queued)
         // the r pass's scratch is dead once its last launch is queued: the slot words of the next f pass go to their place
-        uint32_t *r_U_next = (pair_form && !last) ? (uint32_t *)((char *)ctx->ws + pl.r_U) : nullptr;
+        uint32_t *r_U_next = (pair_form && !last) ? (uint32_t *)((char *)ctx->ws.p + pl.r_U) : nullptr;
         // ... and the r words of the next r pass with its marks, cleared.  The words are there already: what this pass wrote
         // as r_Sn (the redrawn bytes of every block) is the next pass's r_S, so the two buffers swap roles -- inside this
         // call; every call starts from the plan's assignment.  Knob r_keep_words: the tally makes them from the r bits.
         const bool r_next = packed_ok && r_U_next;
         const bool keep_words = ctx->knobs.r_keep_words == 1;
-        uint2 *r_S_next = (r_next && keep_words) ? (uint2 *)((char *)ctx->ws + (st.r_flip ? pl.r_Sn : pl.r_S)) : nullptr;
+        uint2 *r_S_next = (r_next && keep_words) ? (uint2 *)((char *)ctx->ws.p + (st.r_flip ? pl.r_Sn : pl.r_S)) : nullptr;
         int64_t *cts = (last ? counts : nullptr);
         // Several ranks (a communicator on the context): the tally leaves this rank's counts in the context's vector, RCCL sums
         // it over the ranks in place ON THIS STREAM, a one-thread kernel makes the M-step from the pooled counts -- all queued
@@ -2337,9 +2321,9 @@ static int sweep_loop(fcd_ctx *ctx, const fcd_sweep_call &c, int64_t sweep0, int
         if (do_m || do_a || cts || r_U_next) {
             rc = launch_tally(ctx, c.f_state, c.r_bits, Nreg, U, G, g, tally_counts, do_a ? cnt_f : nullptr, do_a ? cnt_r : nullptr,
                               (do_m && !pooled) ? hyper_m : nullptr, r_U_next, pl.f_NW, s, st.tally_f_done, r_S_next,
-                              r_next ? (uint32_t *)((char *)ctx->ws + pl.marks) : nullptr);
+                              r_next ? (uint32_t *)((char *)ctx->ws.p + pl.marks) : nullptr);
             if (rc) {
-                if (tf.acc) (void)hipMemsetAsync(ctx->acc, 0, 8 * sizeof(unsigned long long), s);
+                if (tf.acc) (void)hipMemsetAsync(ctx->acc, 0, FCD_ACC_BYTES, s);
                 return rc;
             }
         }
@@ -2424,9 +2408,9 @@ extern "C" int fcd_gibbs_logjoint(fcd_ctx *ctx, const double *S_B, const double 
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(gibbs_logjoint_kernel, dim3((unsigned)g.GW, LJ_SLICES), dim3(64), 0, s, S_B, lM, hyper, f_state,
-                       r_bits, (int)Nreg, (int)U, g.C, g.GW, (double *)ctx->ws);
+                       r_bits, (int)Nreg, (int)U, g.C, g.GW, (double *)ctx->ws.p);
     FCD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gibbs_logjoint_fold, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, (const double *)ctx->ws,
+    hipLaunchKernelGGL(gibbs_logjoint_fold, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, (const double *)ctx->ws.p,
                        (int64_t)g.GW * 64, G, out);
     FCD_LAUNCH_CHECK();
     return FCD_OK;

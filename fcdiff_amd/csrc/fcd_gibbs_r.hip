@@ -733,7 +733,7 @@ constexpr int R_POLL_LIMIT = 1 << 20;                              // x (sleep +
 
 // err: the context's pinned host word.  ok: false once this wave has given up (it then never waits again).
 __device__ __forceinline__ void pipe_give_up(volatile unsigned *err, bool &ok) {
-    __hip_atomic_store(const_cast<unsigned *>(err), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(const_cast<unsigned *>(err), FCD_DEV_ERR_R_ABANDONED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     ok = false;
 }
 __device__ __forceinline__ void pipe_poll_mark(const uint32_t *mark, int limit, volatile unsigned *err, bool &ok) {
@@ -1434,7 +1434,7 @@ struct r_sparse_args {
     const uint32_t *rowflag;        // (Nreg)
     uint64_t *visit;                // (GW, Nreg)
     uint32_t *fneq;                 // (GW, Nreg): row flag, or the f words differ from the mode words in some chain
-    unsigned long long *cnt;        // [0] items left to the tables, [1] decided items evaluated in full
+    fcd_dev_words *words;           // r_sure_sites: items left to the tables, r_sure_exceptions: decided items evaluated in full
     unsigned long long *fold_slots; // nullable: the pooled f counts the f pass's run kernel left in fcd_ctx::f_slots ...
     unsigned long long *fold_acc;   // ... which one wave of the range kernel folds into the context's sums (fcd_f_slots_fold)
     int Nreg, U, NBLK, GW;
@@ -1624,7 +1624,8 @@ __global__ __launch_bounds__(64 * RS_WAVES) void gibbs_r_range_kernel(const r_sp
         if (lane < U && !((visit >> lane) & 1ull)) a.r_bits[((int64_t)w * Nreg + n) * U + lane] = ((ones >> lane) & 1ull) ? act : 0ull;
     }
     __syncthreads();
-    if (threadIdx.x < 2 && red[threadIdx.x]) atomicAdd(&a.cnt[threadIdx.x], (unsigned long long)red[threadIdx.x]);
+    if (threadIdx.x < 2 && red[threadIdx.x])
+        atomicAdd(threadIdx.x ? &a.words->r_sure_exceptions : &a.words->r_sure_sites, (unsigned long long)red[threadIdx.x]);
 }
 
 __device__ __forceinline__ void rs_wave_sync() {
@@ -2080,20 +2081,19 @@ extern "C" int fcd_gibbs_r_step(fcd_ctx *ctx, const double *lM, const double *lM
 // behind the call's first sweep, with the hint that tells the host what share of the sites is decided.
 int fcd_gibbs_r_bounds_build(fcd_ctx *ctx, const fcd_sweep_call &c) {
     const fcd_sweep_plan &pl = c.pl;
-    if (!pl.rs_bytes || !ctx->frec || !c.lMd || !ctx->f_sure_hint)
+    if (!pl.rs_bytes || !ctx->frec.p || !c.lMd || !ctx->hint)
         return fcd_fail(ctx, FCD_ERR_ARG, "r pass: bound build without the call's record table");
     int rc = fcd_ws_reserve(ctx, pl.ws_bytes);
     if (rc) return rc;
-    char *ws = (char *)ctx->ws;
+    char *ws = (char *)ctx->ws.p;
     const int Nreg = (int)c.Nreg, U = (int)c.U, NBLK = (Nreg + R_NB - 1) / R_NB;
-    unsigned long long *dbg = (unsigned long long *)ctx->dbg;
     ctx->n_rsure_build += 1;
     hipLaunchKernelGGL(gibbs_r_bounds_kernel, dim3((unsigned)Nreg), dim3(256), (size_t)NBLK * R_NB, c.s, c.lMd,
-                       (const fcd_f_edge_rec *)((const char *)ctx->frec + pl.frec_edge), (const double *)(dbg + 11), Nreg, U, NBLK,
+                       (const fcd_f_edge_rec *)((const char *)ctx->frec.p + pl.frec_edge), ctx->words->hyper0, Nreg, U, NBLK,
                        (double *)(ws + pl.rs_bnd), (double *)(ws + pl.rs_dtab), (uint2 *)(ws + pl.rs_mword),
-                       (uint32_t *)(ws + pl.rs_rowflag), dbg + 10);
+                       (uint32_t *)(ws + pl.rs_rowflag), &ctx->words->r_decided);
     FCD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gibbs_r_hint_kernel, dim3(1), dim3(1), 0, c.s, dbg + 10, ctx->f_sure_hint + 1,
+    hipLaunchKernelGGL(gibbs_r_hint_kernel, dim3(1), dim3(1), 0, c.s, &ctx->words->r_decided, &ctx->hint->r,
                        (unsigned)(ctx->n_rsure_build & 0x3fffffff), (double)c.Nreg * (double)c.U, R_SURE_MIN_SHARE);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
@@ -2130,7 +2130,7 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, "r step: Nreg=%lld with G=%lld exceeds 32-bit item indices", Nreg, c.G);
     int rc = fcd_ws_reserve(ctx, pl.ws_bytes);
     if (rc) return rc;
-    char *ws = (char *)ctx->ws;
+    char *ws = (char *)ctx->ws.p;
     // (the sweep loop swaps the two r-word buffers from sweep to sweep: what a pass wrote as r_Sn the next one reads as r_S)
     uint2 *f_S = (uint2 *)(ws + pl.f_S), *r_S = (uint2 *)(ws + (st.r_flip ? pl.r_Sn : pl.r_S));
     fcd_abl_refresh(s);
@@ -2163,7 +2163,7 @@ int fcd_gibbs_r_pass(fcd_ctx *ctx, const fcd_sweep_call &c, fcd_sweep_step &st) 
         q.bnd = (const double *)(ws + pl.rs_bnd); q.dtab = (const double *)(ws + pl.rs_dtab);
         q.mword = (const uint2 *)(ws + pl.rs_mword); q.rowflag = (const uint32_t *)(ws + pl.rs_rowflag);
         q.visit = (uint64_t *)(ws + pl.rs_visit); q.fneq = (uint32_t *)(ws + pl.rs_fneq);
-        q.cnt = (unsigned long long *)ctx->dbg + 8;
+        q.words = ctx->words;
         q.fold_slots = st.f_fold ? (unsigned long long *)ctx->f_slots : nullptr;
         q.fold_acc = (unsigned long long *)ctx->acc;
         q.Nreg = (int)Nreg; q.U = (int)U; q.NBLK = NBLK; q.GW = g.GW; q.G = c.G;

@@ -40,7 +40,6 @@ constexpr int HH = 4096;                 // controls: the site ids of all of the
 constexpr int HC = 256;                  // controls of a row staged per wave at once
 constexpr int HW = 2048;                 // doubles of W staged per workgroup
 constexpr int FIT_WAVES = 4;
-constexpr unsigned HARM_ERR_SITE = 2u;   // the context's error word: a site id outside 0..B-1
 constexpr int EB_MAX_STEPS = 1000;
 constexpr double EB_TOL = 1e-13;
 
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(64 * FIT_WAVES) void harm_fit_kernel(const harm_fit
     __syncthreads();
     const bool bad = s_bad != 0;
     if (bad && blockIdx.x == 0 && tid == 0)
-        __hip_atomic_store(const_cast<unsigned *>(a.err), HARM_ERR_SITE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(const_cast<unsigned *>(a.err), FCD_DEV_ERR_HARM_SITE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     const double *Wp = w_staged ? s_W : a.W;
     double *row = s_row[wv];
     // lane = (group, site): Bp = B rounded up to a power of two, SG = 64 / Bp groups; group g of site i takes the controls
@@ -391,7 +390,7 @@ __global__ __launch_bounds__(256) void harm_apply_kernel(const double *__restric
     }
     __syncthreads();
     if (s_bad && blockIdx.x == 0 && tid == 0)
-        __hip_atomic_store(const_cast<unsigned *>(err), HARM_ERR_SITE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(const_cast<unsigned *>(err), FCD_DEV_ERR_HARM_SITE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     constexpr int W = VEC ? 2 : 1, TPR = AS / W, RPI = 256 / TPR;   // columns per lane, lanes per row, rows per iteration
     const int j = (tid % TPR) * W, rr = tid / TPR;
     if (j >= ns) return;
@@ -474,7 +473,7 @@ extern "C" int fcd_site_harmonize_fit(fcd_ctx *ctx, const fcd_harmonize_desc *d)
     const int nT = Q * Qp, nM = B * Q;
     rc = fcd_ws_reserve(ctx, (size_t)(HQ * HQ + HB * HQ) * sizeof(double));
     if (rc) return rc;
-    double *wsT = (double *)ctx->ws, *wsM = wsT + HQ * HQ;
+    double *wsT = (double *)ctx->ws.p, *wsM = wsT + HQ * HQ;
     if (nT + nM > 0) {
         double host[HQ * HQ + HB * HQ];
         for (int e = 0; e < nT; ++e) host[e] = d->T[e];

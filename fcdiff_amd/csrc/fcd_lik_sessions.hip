@@ -585,26 +585,13 @@ int sess_check(fcd_ctx *ctx, const char *who, bool records, int64_t C, int64_t H
     return FCD_OK;
 }
 
-int noise_rec_reserve(fcd_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->noise_rec_bytes) return FCD_OK;
-    FCD_HIP_TRY(hipDeviceSynchronize());        // the old block may still be read by kernels already queued
-    if (ctx->noise_rec) FCD_HIP_TRY(hipFree(ctx->noise_rec));
-    ctx->noise_rec = nullptr;
-    ctx->noise_rec_bytes = 0;
-    const size_t want = bytes < (64u << 10) ? (64u << 10) : bytes;
-    FCD_HIP_TRY(hipMalloc(&ctx->noise_rec, want));
-    ctx->noise_rec_bytes = want;
-    ctx->n_alloc += 1;
-    return FCD_OK;
-}
-
 // the records of one call, in the context's block: *rec_b (nullptr without var_b) and *rec_bt
 int noise_records(fcd_ctx *ctx, const double *var_b, const double *var_bt, int64_t H, int64_t U, int64_t K, const LikTheta &th,
                   hipStream_t s, const NoiseRec **rec_b, const NoiseRec **rec_bt) {
     const int64_t n_b = var_b ? H : 0, n = n_b + U * K;
-    int rc = noise_rec_reserve(ctx, (size_t)n * 3 * sizeof(NoiseRec));
+    int rc = fcd_buf_reserve(ctx, ctx->noise_rec, (size_t)n * 3 * sizeof(NoiseRec));
     if (rc) return rc;
-    NoiseRec *base = static_cast<NoiseRec *>(ctx->noise_rec);
+    NoiseRec *base = static_cast<NoiseRec *>(ctx->noise_rec.p);
     *rec_b = var_b ? base : nullptr;
     *rec_bt = base + 3 * n_b;
     int64_t blocks = (n + 255) / 256;

@@ -178,7 +178,7 @@ extern "C" int fcd_member_loglik(fcd_ctx *ctx, const double *x, const double *th
     const size_t n_part = (size_t)S * (size_t)U * (size_t)GP;
     rc = fcd_ws_reserve(ctx, n_part * sizeof(double) * (out_patient ? 2 : 1));
     if (rc) return rc;
-    double *part_c = (double *)ctx->ws, *part_p = out_patient ? part_c + n_part : nullptr;
+    double *part_c = (double *)ctx->ws.p, *part_p = out_patient ? part_c + n_part : nullptr;
     const LikTabs *tabs = reinterpret_cast<const LikTabs *>(ctx->log_tab);
     const int missing = (flags & FCD_DATA_NAN_MISSING) ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;

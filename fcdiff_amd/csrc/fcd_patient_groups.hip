@@ -143,7 +143,7 @@ int fcd_patient_group_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t
                                    uint32_t *hist_group, uint32_t *hist_joint, hipStream_t s) {
     int rc = fcd_patient_group_ws_reserve(ctx, Nreg, U, G); // (no-op when fcd_gibbs_run has grown it)
     if (rc) return rc;
-    uint16_t *sums = (uint16_t *)ctx->count_ws;
+    uint16_t *sums = (uint16_t *)ctx->count_ws.p;
     const int J = (int)ctx->pg_J, P = (int)ctx->pg_P, R = (int)tally_rows(ctx, Nreg, ctx->pg_with_rs), Umax = (int)ctx->pg_umax;
     const pg_layout l = layout_of(J, ctx->pg_total, P);
     const char *dev = (const char *)ctx->pg_dev;

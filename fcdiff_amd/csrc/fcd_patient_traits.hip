@@ -145,7 +145,7 @@ int fcd_patient_trait_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t
     if (rc) return rc;
     const int Q = (int)ctx->pt_Q, R = (int)tally_rows(ctx, Nreg, ctx->pt_with_rs), Umax = (int)ctx->pt_umax;
     const int64_t GP = (int64_t)g.GW * 64;
-    uint16_t *ks = (uint16_t *)ctx->count_ws;
+    uint16_t *ks = (uint16_t *)ctx->count_ws.p;
     int32_t *As = (int32_t *)(ks + (int64_t)Q * R * GP);    // (GP is a multiple of 64: aligned)
     const int32_t *enc = (const int32_t *)ctx->pt_dev, *nq = enc + (int64_t)Q * U;
     const int32_t *rs_offsets = ctx->pt_with_rs ? (const int32_t *)ctx->rs_dev : nullptr;

@@ -93,7 +93,7 @@ int fcd_region_set_tally_launch(fcd_ctx *ctx, const uint64_t *r_bits, int64_t Nr
                                 uint32_t *hist_set, uint32_t *hist_prev, hipStream_t s) {
     int rc = fcd_region_set_ws_reserve(ctx, Nreg, U, G);    // (no-op when fcd_gibbs_run has grown it)
     if (rc) return rc;
-    uint16_t *sums = (uint16_t *)ctx->count_ws;
+    uint16_t *sums = (uint16_t *)ctx->count_ws.p;
     const int32_t *offsets = (const int32_t *)ctx->rs_dev, *members = offsets + ctx->rs_J + 1;
     const int J = (int)ctx->rs_J, S_max = (int)ctx->rs_smax;
     const int threads = (int)((U + 63) / 64) * 64;

@@ -234,7 +234,7 @@ extern "C" int fcd_vb_patient_elbo(fcd_ctx *ctx, const double *lq_F, const doubl
     const int64_t S = elbo_slices(C);
     rc = fcd_ws_reserve(ctx, (size_t)S * (size_t)U * sizeof(double));
     if (rc) return rc;
-    double *part = (double *)ctx->ws;
+    double *part = (double *)ctx->ws.p;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(patient_elbo_edges, dim3((unsigned)S, (unsigned)((U + 63) / 64)), dim3(64 * EL_WAVES), 0, s, lq_F, lq_R, lM,
                        C, (int)U, (int)S, part);
@@ -276,7 +276,7 @@ extern "C" int fcd_score_ais_step(fcd_ctx *ctx, const double *lM, const uint8_t 
     if (S < 1) S = 1;
     rc = fcd_ws_reserve(ctx, (size_t)S * (size_t)U * (size_t)GP * sizeof(double));
     if (rc) return rc;
-    double *part = (double *)ctx->ws;
+    double *part = (double *)ctx->ws.p;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)g.GW, (unsigned)S, (unsigned)NPG), block((unsigned)(64 * NW));
     if (PT == 1)

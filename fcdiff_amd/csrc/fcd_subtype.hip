@@ -215,7 +215,7 @@ extern "C" int fcd_vb_subtype_loglik(fcd_ctx *ctx, const double *lq_F, const dou
     const int64_t nF = C * 3, nR = Nreg * G * 2;
     int rc = fcd_ws_reserve(ctx, (size_t)(nF + nR + S * U * G) * sizeof(double));
     if (rc) return rc;
-    double *qF = (double *)ctx->ws, *qR = qF + nF, *part = qR + nR;
+    double *qF = (double *)ctx->ws.p, *qR = qF + nF, *part = qR + nR;
     hipStream_t s = (hipStream_t)stream;
     int64_t blocks = (nF + nR + 255) / 256;
     const int64_t cap = (int64_t)ctx->num_cu * 8;

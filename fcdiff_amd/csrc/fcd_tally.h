@@ -209,7 +209,7 @@ static inline int tally_ws_reserve(fcd_ctx *ctx, int64_t rows, int64_t G, size_t
                                    long long a = 0, long long b = 0) {
     const size_t bytes = (size_t)rows * (size_t)((G + 63) / 64) * 64 * bytes_per_count;
     if (refusal && bytes > ((size_t)1 << 30)) return fcd_fail(ctx, FCD_ERR_UNSUPPORTED, refusal, a, b);
-    return fcd_count_ws_grow(ctx, bytes);
+    return fcd_buf_reserve(ctx, ctx->count_ws, bytes);
 }
 
 // grid of a grid-stride tally launch: eight workgroups per CU at the most

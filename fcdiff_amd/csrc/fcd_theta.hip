@@ -297,18 +297,18 @@ extern "C" int fcd_theta_sub_objective_ex(fcd_ctx *ctx, const double *bt, const 
         te.U = (int)U;
         if (flags & FCD_DATA_NAN_MISSING)
             hipLaunchKernelGGL((theta_sub_kernel<true, true>), dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, bt, W, n_items, te,
-                               (double *)ctx->ws);
+                               (double *)ctx->ws.p);
         else
             hipLaunchKernelGGL((theta_sub_kernel<false, true>), dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, bt, W, n_items, te,
-                               (double *)ctx->ws);
+                               (double *)ctx->ws.p);
     } else if (flags & FCD_DATA_NAN_MISSING)
         hipLaunchKernelGGL(theta_sub_kernel<true>, dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, bt, W, n_items, th,
-                           (double *)ctx->ws);
+                           (double *)ctx->ws.p);
     else
         hipLaunchKernelGGL(theta_sub_kernel<false>, dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, bt, W, n_items, th,
-                           (double *)ctx->ws);
+                           (double *)ctx->ws.p);
     FCD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(theta_sub_fold, dim3(1), dim3(256), 0, s, (const double *)ctx->ws, (int)blocks, out3);
+    hipLaunchKernelGGL(theta_sub_fold, dim3(1), dim3(256), 0, s, (const double *)ctx->ws.p, (int)blocks, out3);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
 }
@@ -352,18 +352,18 @@ extern "C" int fcd_theta_full_objective_ex(fcd_ctx *ctx, const double *b, const 
     if (flags & FCD_W_PER_EDGE) {
         if (flags & FCD_DATA_NAN_MISSING)
             hipLaunchKernelGGL((theta_full_kernel<true, true>), dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, b, bt, W, C, (int)H,
-                               (int)U, th, (double *)ctx->ws);
+                               (int)U, th, (double *)ctx->ws.p);
         else
             hipLaunchKernelGGL((theta_full_kernel<false, true>), dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, b, bt, W, C, (int)H,
-                               (int)U, th, (double *)ctx->ws);
+                               (int)U, th, (double *)ctx->ws.p);
     } else if (flags & FCD_DATA_NAN_MISSING)
         hipLaunchKernelGGL(theta_full_kernel<true>, dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, b, bt, W, C, (int)H, (int)U, th,
-                           (double *)ctx->ws);
+                           (double *)ctx->ws.p);
     else
         hipLaunchKernelGGL(theta_full_kernel<false>, dim3((unsigned)blocks), dim3(OBJ_BLOCK), 0, s, b, bt, W, C, (int)H, (int)U, th,
-                           (double *)ctx->ws);
+                           (double *)ctx->ws.p);
     FCD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(theta_full_fold, dim3(1), dim3(256), 0, s, (const double *)ctx->ws, (int)blocks, out9);
+    hipLaunchKernelGGL(theta_full_fold, dim3(1), dim3(256), 0, s, (const double *)ctx->ws.p, (int)blocks, out9);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
 }

@@ -553,7 +553,7 @@ extern "C" int fcd_vb_update_qR(fcd_ctx *ctx, const double *lq_F, const double *
     const bool weights = Nreg <= 65535 && ctx->knobs.qr_form != 1 && ((size_t)nW * sizeof(double) <= ((size_t)192 << 20) || ctx->knobs.qr_form == 2);
     rc = fcd_ws_reserve(ctx, (size_t)(nF + (weights ? nW : 0)) * sizeof(double));
     if (rc) return rc;
-    double *qF = (double *)ctx->ws;
+    double *qF = (double *)ctx->ws.p;
     double *W = qF + nF;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(vb_expF_kernel, dim3((unsigned)((nF + 255) / 256 < 1024 ? (nF + 255) / 256 : 1024)), dim3(256), 0, s, lq_F, nF, qF);
@@ -599,9 +599,9 @@ extern "C" int fcd_vb_energy(fcd_ctx *ctx, const double *lq_F, const double *lq_
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(vb_energy_edges, dim3((unsigned)n_blocks), dim3(EN_BLOCK), 0, s, lq_F, lq_R, S_B, lM, hyper, C,
-                       (int)U, Nreg * U, (double *)ctx->ws);
+                       (int)U, Nreg * U, (double *)ctx->ws.p);
     FCD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(vb_energy_fold, dim3(1), dim3(256), 0, s, (const double *)ctx->ws, (int)n_blocks, terms6);
+    hipLaunchKernelGGL(vb_energy_fold, dim3(1), dim3(256), 0, s, (const double *)ctx->ws.p, (int)n_blocks, terms6);
     FCD_LAUNCH_CHECK();
     return FCD_OK;
 }
@@ -614,9 +614,9 @@ extern "C" int fcd_vb_theta_step(fcd_ctx *ctx, const double *lq_F, const double 
     rc = fcd_ws_reserve(ctx, (size_t)TH_PARTS * 4 * sizeof(double));
     if (rc) return rc;
     hipLaunchKernelGGL(vb_theta_part_kernel, dim3(TH_PARTS), dim3(256), 0, (hipStream_t)stream, lq_F, lq_R, fcd_tri(Nreg), Nreg * U,
-                       (double *)ctx->ws);
+                       (double *)ctx->ws.p);
     FCD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(vb_theta_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const double *)ctx->ws, TH_PARTS, fcd_tri(Nreg),
+    hipLaunchKernelGGL(vb_theta_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const double *)ctx->ws.p, TH_PARTS, fcd_tri(Nreg),
                        Nreg * U, out4, hyper);
     FCD_LAUNCH_CHECK();
     return FCD_OK;

@@ -1157,7 +1157,7 @@ def _b_chain_counts(d):
 # ---------------------------------------------------------------------------------------------------------------------
 # Gibbs sampler: the sweep loops.  Four sweeps, an M-step every two, every accumulator attached; the difference tables are
 # made by the same call sequence (fcd_gibbs_edge_tables / _region_tables), on the same stream.
-# fcd_gibbs_run and fcd_gibbs_sweeps wait for the device where a call builds the f pass's records: fcd_f_sure_hint_wait
+# fcd_gibbs_run and fcd_gibbs_sweeps wait for the device where a call builds the f pass's records: fcd_hint_wait
 # (fcd_gibbs.hip) polls the pinned hint word the record build leaves, and synchronises the stream after two seconds.  Every
 # case below has such a build (knob f_records = 2, or four sweeps on the pair-tile pass), so syncs_stream is True.
 # ---------------------------------------------------------------------------------------------------------------------
