@@ -91,6 +91,8 @@ SIGNATURES = {
     "fcd_baseline_group_glm": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
     "fcd_baseline_network_bits_glm": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _dbl, _int, _p, _p, _p]),
     "fcd_graph_components": (_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
+    "fcd_baseline_network_excess": (_int, [_p, _p]),     # (ctx, const fcd_network_excess_desc *): NetworkExcessDesc below
+    "fcd_graph_components_weighted": (_int, [_p, _p]),   # (ctx, const fcd_components_desc *): ComponentsDesc below
     "fcd_vb_update_qF": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
     "fcd_vb_update_qR": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _p, _p]),
     "fcd_vb_energy": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
@@ -184,6 +186,22 @@ class TangentDesc(C.Structure):
                  ("shrink_mode", C.c_int32), ("max_iter", C.c_int32), ("shrink_value", _dbl), ("tol", _dbl)]
                 + [(k, _p) for k in ("stream", "ts", "n_frames", "alpha", "info", "G", "G_half", "W", "used", "n_iter",
                                      "grad_norm", "out", "diag")])
+
+
+class NetworkExcessDesc(C.Structure):
+    """fcd_network_excess_desc of include/fcdiff_hip.h, member for member."""
+    make = classmethod(HarmonizeDesc.make.__func__)
+    _fields_ = ([("size", C.c_uint32), ("flags", C.c_uint32)] + [(k, _i64) for k in ("C", "H", "U", "P")]
+                + [("threshold", _dbl), ("tail", C.c_int32), ("R", C.c_int32)]
+                + [(k, _p) for k in ("stream", "b", "bt", "labels", "design", "perms", "bits", "excess", "t")])
+
+
+class ComponentsDesc(C.Structure):
+    """fcd_components_desc of include/fcdiff_hip.h, member for member."""
+    make = classmethod(HarmonizeDesc.make.__func__)
+    _fields_ = ([("size", C.c_uint32), ("flags", C.c_uint32), ("B", _i64), ("C", _i64)]
+                + [(k, _p) for k in ("stream", "bits", "weights", "component", "n_edges", "max_extent", "max_regions", "intensity",
+                                     "max_intensity")])
 
 
 _lib = None

@@ -11,6 +11,9 @@ network_test()  per population: "which sub-network is abnormal in this disease?"
               group_test() thresholded, the connected components of the suprathreshold graph, family-wise error control by
               the permutation law of the largest component.  graph_components() gives the components of any mask.
               Oracle = tests/network_ref.py; fcd_baseline_network_bits, fcd_graph_components.
+              statistic="intensity" sizes a component by the sum of |t| - threshold over its connections instead of their
+              number, graph_components(mask, weights) by any weights.  Oracle = tests/network_intensity_ref.py;
+              fcd_baseline_network_excess, fcd_graph_components_weighted.
 
 group_test() and network_test() take missing_data=True (a NaN is an unobserved value) and variance="welch"; a call with
 either goes through fcd_baseline_group_perm_opt / fcd_baseline_network_bits_opt, the default call through the entry points
@@ -505,7 +508,14 @@ def group_pvalues(t, region, null_max_t, null_max_region, count_t, count_region)
 
 MAX_REGIONS = 1024        # graph_components(), network_test(): a row of bits lives in one workgroup's LDS (64 KB at 1024)
 _P_CHUNK = 1 << 14        # labellings per call of network_test(): bounds the bit workspace (W words each)
+_X_BYTES = 256 << 20      # statistic="intensity": the (n, 32 W) doubles of a chunk's excess values (partial_correlations' dense-chunk figure)
 TAILS = {"both": 0, "greater": 1, "less": 2}
+STATISTICS = ("extent", "intensity")
+
+
+def _excess_chunk(W):
+    """Labellings whose excess values, 32 W doubles each, fit in _X_BYTES; at least 1."""
+    return max(1, _X_BYTES // (8 * 32 * W))
 
 
 def _pair_index(N):
@@ -532,12 +542,43 @@ def network_pvalues(component_edges, null_max_extent):
     return (1.0 + ge) / (1.0 + P)
 
 
+def network_intensity_pvalues(component_intensity, null_max_intensity):
+    """The same by intensity: p_fwe[k] = (1 + #{p: null_max_intensity[p] >= component_intensity[k]}) / (1 + P); inf >= inf counts."""
+    (ge, P) = _count_ge(np.asarray(null_max_intensity, dtype=np.float64).reshape(-1),
+                        np.asarray(component_intensity, dtype=np.float64).reshape(-1))
+    return (1.0 + ge) / (1.0 + P)
+
+
 def _components_call(ctx, bits, B, C, N, component, n_edges, max_extent, max_regions):
     ctx.call("fcd_graph_components", _lib.dptr(bits), B, C, _lib.dptr(component), _lib.dptr(n_edges), _lib.dptr(max_extent),
              _lib.dptr(max_regions), _lib.stream_ptr())
 
 
-def graph_components(mask, *, ctx=None, as_numpy=True):
+def _weighted_components_call(ctx, bits, weights, B, C, component, n_edges, max_extent, max_regions, intensity, max_intensity):
+    import ctypes
+    d = _lib.ComponentsDesc.make(B=B, C=C, stream=_lib.stream_ptr(), bits=_lib.dptr(bits), weights=_lib.dptr(weights),
+                                 component=_lib.dptr(component), n_edges=_lib.dptr(n_edges), max_extent=_lib.dptr(max_extent),
+                                 max_regions=_lib.dptr(max_regions), intensity=_lib.dptr(intensity),
+                                 max_intensity=_lib.dptr(max_intensity))
+    ctx.call("fcd_graph_components_weighted", ctypes.byref(d))
+
+
+def _check_weights(mask, weights, sh):
+    """weights as a float64 torch tensor of the mask's shape, >= 0 and not NaN where the mask is set (checked where it lies)."""
+    import torch
+    w = weights if isinstance(weights, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(weights))
+    if tuple(w.shape) != tuple(sh):
+        raise ValueError("graph_components: weights must have the mask's shape %s, not %s" % (sh, tuple(w.shape)))
+    if w.dtype != torch.float64:
+        raise ValueError("graph_components: weights must be float64, not %s" % (w.dtype,))
+    m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(mask))
+    at = w[(m != 0).to(w.device)]
+    if bool((torch.isnan(at) | (at < 0.0)).any().item()):
+        raise ValueError("graph_components: weights must be >= 0 and not NaN where the mask is set")
+    return w
+
+
+def graph_components(mask, weights=None, *, ctx=None, as_numpy=True):
     """
     Connected components of the graphs on N regions whose edges are the set entries of mask, (C,) or (B, C), bool or 0/1,
     NumPy or torch, connections in util.c_to_nm order.  On the device (fcd_graph_components), one workgroup per graph.
@@ -547,6 +588,11 @@ def graph_components(mask, *, ctx=None, as_numpy=True):
     set connections, extent of the largest component, regions of the component with the most regions.  For a 1-D mask the
     leading axis is dropped and component_label, component_edges, component_regions (K,) list the K >= 0 components by
     decreasing extent, then by label.  NumPy arrays, or device tensors with as_numpy=False.
+    weights, float64 of the mask's shape: a weight per connection, read only where the mask is set, >= 0 and not NaN there
+    (+inf is allowed; ValueError otherwise) -- t excesses, or the posterior mass of a thresholded connection_posterior().  The
+    call (fcd_graph_components_weighted) then adds max_weight (B,) float64, the largest sum of weights over a component (0.0
+    for an empty graph), and for a 1-D mask component_weight (K,), the sum of each listed component.  The sums are taken in
+    a fixed order without floating-point atomics: they repeat exactly and do not depend on B or on a graph's place.
     A non-triangular C is a ValueError, more than 1024 regions a NotImplementedError.
     """
     import torch
@@ -557,6 +603,8 @@ def graph_components(mask, *, ctx=None, as_numpy=True):
     N = _n_regions(C)
     if N > MAX_REGIONS:
         raise NotImplementedError("graph_components: %d regions, at most %d" % (N, MAX_REGIONS))
+    if weights is not None:
+        weights = _check_weights(mask, weights, sh)
     ctx = ctx if ctx is not None else _lib.Context()
     dev = ctx.device
     m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(mask))
@@ -568,17 +616,29 @@ def graph_components(mask, *, ctx=None, as_numpy=True):
     # bit c & 31 of word c >> 5, as bytes: bit c & 7 of byte c >> 3
     padded = torch.zeros((B, 32 * W), dtype=torch.int32, device=dev)
     padded[:, :C] = m.to(torch.int32)
-    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32, device=dev)
-    bits = (padded.view(B, 4 * W, 8) * weights).sum(dim=2).to(torch.uint8).contiguous()
+    place = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32, device=dev)
+    bits = (padded.view(B, 4 * W, 8) * place).sum(dim=2).to(torch.uint8).contiguous()
     component = torch.empty((B, N), dtype=torch.int32, device=dev)
     (n_edges, max_extent, max_regions) = (torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(3))
-    _components_call(ctx, bits, B, C, N, component, n_edges, max_extent, max_regions)
+    if weights is None:
+        _components_call(ctx, bits, B, C, N, component, n_edges, max_extent, max_regions)
+    else:
+        wd = torch.zeros((B, 32 * W), dtype=torch.float64, device=dev)
+        wd[:, :C] = weights.to(device=dev).reshape(-1, C)
+        intensity = torch.empty((B, N), dtype=torch.float64, device=dev)
+        max_weight = torch.empty((B,), dtype=torch.float64, device=dev)
+        _weighted_components_call(ctx, bits, wd, B, C, component, n_edges, max_extent, max_regions, intensity, max_weight)
     out = {"component": component.long(), "n_edges": n_edges.long(), "max_extent": max_extent.long(),
            "max_regions": max_regions.long()}
+    if weights is not None:
+        out["max_weight"] = max_weight
     if len(sh) == 1:
         out = dict((k, v[0]) for (k, v) in out.items())
         tables = _component_tables(out["component"].cpu().numpy(), m[0].cpu().numpy().astype(bool))
         names = ("component_label", "component_edges", "component_regions")
+        if weights is not None:
+            tables = tables + (intensity[0].cpu().numpy()[tables[0]],)
+            names = names + ("component_weight",)
         if as_numpy:
             out = dict((k, v.cpu().numpy()) for (k, v) in out.items())
             out.update(zip(names, tables))
@@ -589,7 +649,7 @@ def graph_components(mask, *, ctx=None, as_numpy=True):
 
 
 def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=False, variance="pooled", seed=0, labels=None,
-                 z_b=None, z_bt=None, permutations=None, ctx=None, as_numpy=True):
+                 z_b=None, z_bt=None, permutations=None, ctx=None, as_numpy=True, statistic="extent"):
     """
     The network-based statistic (Zalesky, Fornito & Bullmore 2010): which sub-networks differ between patients and controls?
     b (C, H), bt (C, U), complete unless missing_data=True.
@@ -617,9 +677,20 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=Fa
     (the side of "greater" / "less" is the sign of d_0), its refusals (labels=, missing_data and Welch's t included) and its
     keys permutations and design_info; labels is (pi >= H).  A row equal to the identity gives the observed bits exactly;
     permutations are walked in chunks as labellings are.  Where every column is dropped the call is the default call.
-    Refused: everything group_test() refuses; a threshold that is not finite and > 0 or an unknown tail (ValueError); more
-    than 1024 regions (NotImplementedError).  Not provided: the intensity form sum (|t| - threshold) (it would need a value
-    per bit), TFCE, sessions, noise variances; with covariates also what group_test() lists.
+    statistic="intensity": the other component size of the NBS toolbox, for effects that are strong but confined to few
+    connections.  The excess of a suprathreshold connection is e = max(|t| - threshold, 0) (+inf at t = +/-inf), a
+    component's intensity the sum of e over its connections, and the family-wise error is controlled by the permutation law
+    of the largest intensity (0.0 for an empty graph).  Every key above keeps its value bit for bit -- the component tables
+    stay ordered by decreasing extent, then by label -- except that p_fwe and p_fwe_region are by intensity,
+    (1 + #{p: null_max_intensity[p] >= intensity}) / (1 + P), inf >= inf counting as in group_test().  Added:
+    component_intensity (K,) float64; null_max_intensity (P,) float64; p_fwe_extent (K,), the p_fwe of the extent call;
+    statistic.  All three forms of the t are served, with their rules; a value exists only where a bit is set, and the sums
+    are taken in a fixed order without floating-point atomics, so the results repeat exactly, a row equal to the observed
+    labelling (the identity) gives the observed intensities bit for bit, and neither chunk length (the second keeps a
+    chunk's excess values within 256 MB) changes a bit.
+    Refused: everything group_test() refuses; a threshold that is not finite and > 0, an unknown tail or an unknown
+    statistic (ValueError); more than 1024 regions (NotImplementedError).  Not provided: TFCE, sessions, noise variances;
+    with covariates also what group_test() lists.
     """
     import torch
     (C, N, H, U) = _check_pair(b, bt, "network_test")
@@ -635,9 +706,12 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=Fa
         raise ValueError("network_test: threshold must be finite and > 0, not %r" % (threshold,))
     if tail not in TAILS:
         raise ValueError("network_test: tail must be one of 'both', 'greater', 'less', not %r" % (tail,))
+    if statistic not in STATISTICS:
+        raise ValueError("network_test: statistic must be one of 'extent', 'intensity', not %r" % (statistic,))
     glm = _glm_setup("network_test", b, bt, H, U, z_b, z_bt, permutations, labels, missing_data, variance, n_perm, seed)
     if glm is not None and glm[1]["rank"] == 0:                  # every column dropped: the default call with those labels
-        out = network_test(b, bt, thr, tail=tail, labels=(glm[2] >= H).astype(np.uint8), ctx=ctx, as_numpy=as_numpy)
+        out = network_test(b, bt, thr, tail=tail, labels=(glm[2] >= H).astype(np.uint8), ctx=ctx, as_numpy=as_numpy,
+                           statistic=statistic)
         out["permutations"] = glm[2] if as_numpy else torch.as_tensor(glm[2], device=out["t"].device)
         out["design_info"] = glm[1]
         return out
@@ -666,8 +740,23 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=Fa
     def i32(*sh):
         return torch.empty(sh, dtype=torch.int32, device=dev)
 
-    def bits_call(lab_c, n, bits, t):
-        if glm is not None:
+    intensity = statistic == "intensity"
+
+    def f64(*sh):
+        return torch.empty(sh, dtype=torch.float64, device=dev)
+
+    def bits_call(lab_c, n, bits, t, excess=None):
+        if excess is not None:                                 # one entry point for the three statistics
+            import ctypes
+            d = _lib.NetworkExcessDesc.make(flags=flags, C=C, H=H, U=U, P=n, threshold=thr, tail=TAILS[tail], stream=_lib.stream_ptr(),
+                                            b=_lib.dptr(bd), bt=_lib.dptr(btd), bits=_lib.dptr(bits), excess=_lib.dptr(excess),
+                                            t=_lib.dptr(t))
+            if glm is not None:
+                (d.design, d.R, d.perms) = (_lib.dptr(designd), int(designd.shape[1]), _lib.dptr(lab_c))
+            else:
+                d.labels = _lib.dptr(lab_c)
+            ctx.call("fcd_baseline_network_excess", ctypes.byref(d))
+        elif glm is not None:
             ctx.call("fcd_baseline_network_bits_glm", _lib.dptr(bd), _lib.dptr(btd), C, H, U, _lib.dptr(designd),
                      int(designd.shape[1]), _lib.dptr(lab_c), n, thr, TAILS[tail], _lib.dptr(bits), _lib.dptr(t), _lib.stream_ptr())
         elif flags == 0:
@@ -680,16 +769,31 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=Fa
     # the observed labelling: the same kernels at P = 1
     t = torch.empty((C,), dtype=torch.float64, device=dev)
     bits_obs = i32(1, W)
-    bits_call(None, 1, bits_obs, t)
     (component, obs_edges, obs_extent, obs_regions) = (i32(1, N), i32(1), i32(1), i32(1))
-    _components_call(ctx, bits_obs, 1, C, N, component, obs_edges, obs_extent, obs_regions)
     (null_n_edges, null_max_extent, null_max_regions) = (i32(P), i32(P), i32(P))
-    for p0 in range(0, P, _P_CHUNK):
-        n = min(_P_CHUNK, P - p0)
+    if intensity:
+        # a value only where a bit is set: the buffers are never initialised, and only read at set bits
+        (obs_sums, obs_max, null_max_intensity) = (f64(1, N), f64(1), f64(P))
+        excess_obs = f64(1, 32 * W)
+        bits_call(None, 1, bits_obs, t, excess_obs)
+        _weighted_components_call(ctx, bits_obs, excess_obs, 1, C, component, obs_edges, obs_extent, obs_regions, obs_sums, obs_max)
+        chunk = min(_P_CHUNK, _excess_chunk(W))
+    else:
+        bits_call(None, 1, bits_obs, t)
+        _components_call(ctx, bits_obs, 1, C, N, component, obs_edges, obs_extent, obs_regions)
+        chunk = _P_CHUNK
+    for p0 in range(0, P, chunk):
+        n = min(chunk, P - p0)
         bits = i32(n, W)
-        bits_call(rows[p0:p0 + n], n, bits, None)
-        _components_call(ctx, bits, n, C, N, None, null_n_edges[p0:p0 + n], null_max_extent[p0:p0 + n],
-                         null_max_regions[p0:p0 + n])
+        if intensity:
+            excess = f64(n, 32 * W)
+            bits_call(rows[p0:p0 + n], n, bits, None, excess)
+            _weighted_components_call(ctx, bits, excess, n, C, None, null_n_edges[p0:p0 + n], null_max_extent[p0:p0 + n],
+                                      null_max_regions[p0:p0 + n], None, null_max_intensity[p0:p0 + n])
+        else:
+            bits_call(rows[p0:p0 + n], n, bits, None)
+            _components_call(ctx, bits, n, C, N, None, null_n_edges[p0:p0 + n], null_max_extent[p0:p0 + n],
+                             null_max_regions[p0:p0 + n])
     host = {"t": t.cpu().numpy(), "component": component[0].long().cpu().numpy(),
             "null_max_extent": null_max_extent.long().cpu().numpy(), "null_max_regions": null_max_regions.long().cpu().numpy(),
             "null_n_edges": null_n_edges.long().cpu().numpy()}
@@ -697,6 +801,11 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=Fa
     (label, edges, regions) = _component_tables(host["component"], host["edge_mask"])
     host.update(component_label=label, component_edges=edges, component_regions=regions)
     host["p_fwe"] = network_pvalues(edges, host["null_max_extent"])
+    if intensity:
+        host["component_intensity"] = obs_sums[0].cpu().numpy()[label]
+        host["null_max_intensity"] = null_max_intensity.cpu().numpy()
+        host["p_fwe_extent"] = host["p_fwe"]
+        host["p_fwe"] = network_intensity_pvalues(host["component_intensity"], host["null_max_intensity"])
     p_of = np.full(N + 1, np.nan)                            # (label -1 reads the last entry)
     p_of[label] = host["p_fwe"]
     host["p_fwe_region"] = p_of[host["component"]]
@@ -710,4 +819,6 @@ def network_test(b, bt, threshold, n_perm=10000, *, tail="both", missing_data=Fa
         out["design_info"] = glm[1]
     out["threshold"] = thr
     out["tail"] = tail
+    if intensity:
+        out["statistic"] = statistic
     return out

@@ -1,6 +1,6 @@
 // K_base: the classical baselines (fcd_baseline_normative, fcd_baseline_group_perm and fcd_baseline_network_bits with their _opt
-// and _glm forms, fcd_graph_components).  Not in the reference; oracles = tests/baseline_ref.py, baseline_missing_ref.py,
-// baseline_glm_ref.py, network_ref.py.  E(n) = the N - 1 connections that touch region n, walked as k = 0 .. N - 2 with the
+// and _glm forms, fcd_baseline_network_excess, fcd_graph_components and its _weighted form).  Not in the reference; oracles =
+// tests/baseline_ref.py, baseline_missing_ref.py, baseline_glm_ref.py, network_ref.py, network_intensity_ref.py.  E(n) = the N - 1 connections that touch region n, walked as k = 0 .. N - 2 with the
 // other endpoint m = k (k < n) or k + 1: rows tri(n) + k are contiguous for k < n, rows tri(m) + n are strided for k >= n.  A
 // connection is met by both its endpoints; what is written once per connection (z, z0, n_controls, count_t) is written by the
 // endpoint n > m.  Caller's stream, fixed reduction orders, no floating-point atomics: two calls agree bit for bit.
@@ -62,7 +62,12 @@
 //                      per round every set bit (n, m) pulls the larger label, and the region that label names, down to the
 //                      smaller (LDS atomicMin), then label[x] = label[label[x]]; until a round changes nothing, at most N
 //                      rounds.  Then extents, regions, maxima with integer LDS atomics.
+//   component intensity  (fcd_baseline_network_excess, fcd_graph_components_weighted; oracle = tests/network_intensity_ref.py)
+//                      network_bits_kernel<Stat, true> also stores max(|t| - threshold, 0) where a bit is set, and only there;
+//                      graph_components_weighted_kernel sums those values per component in a fixed order.
 #include "fcd_common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -640,7 +645,7 @@ __device__ __forceinline__ double glm_t2(const double4_t (&d)[RT], int r, double
 //   live               (permutation pass) is the connection live under the observed labelling, whose t^2 is t2o?
 //   alive              (bits pass) the same from the connection's own values: no second pass
 //   t2                 t^2 of result element r of group g, its sign-carrying numerator, whether it is defined
-//   lds_bytes, lds_slot   (host) its dynamic LDS, and the fcd_lds_attr slot of shell `which` = 0, 1, 2
+//   lds_bytes, lds_slot   (host) its dynamic LDS, and the fcd_lds_attr slot of shell `which` = 0, 1, 2, 3
 
 struct plain_args {
     const uint32_t *LW;
@@ -984,6 +989,12 @@ struct nb_kargs {
     nb_common c;
     A s;
 };
+// what the excess form takes on top: nb_kargs stays the argument of the plain form, byte for byte
+template <class A>
+struct nb_xargs : nb_kargs<A> {
+    double *excess;                    // (P, 32 W): written only where the bit is set
+    double thr;
+};
 
 // The bits pass: each connection once (half of the permutation pass's matrix work), nothing kept but one bit per (labelling,
 // connection).  A wave: 16 consecutive connections (piece blockIdx.x * 4 + wave of a row of bits) x G groups of labellings.
@@ -991,8 +1002,12 @@ struct nb_kargs {
 // 16 ks, lane 16 ks stores it (plain vector stores).  A piece behind the last connection (C <= 32 W - 16) is written as zeros.
 // No bit for a dead connection under any labelling, none for an undefined value; t of labelling 0 is NaN at either.  The
 // observed labelling is a call with P = 1.
-template <class Stat>
-__global__ __launch_bounds__(64 * GP_WAVES) void network_bits_kernel(nb_kargs<typename Stat::args> a) {
+// X, the excess form: behind the ballot a lane whose own bit is set takes the root and stores max(|t| - threshold, 0) at
+// excess[p 32 W + c] (plain vector stores; 16 lanes of a labelling write 128 contiguous bytes).  Nothing is stored, and no
+// root taken, for an unset bit; the product, t^2 and the compare are the plain form's, so its bits are.
+template <class Stat, bool X = false>
+__global__ __launch_bounds__(64 * GP_WAVES) void network_bits_kernel(
+    typename std::conditional<X, nb_xargs<typename Stat::args>, nb_kargs<typename Stat::args>>::type a) {
     constexpr int G = Stat::NB_G;
     Stat::prologue(a.s);
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1027,9 +1042,13 @@ __global__ __launch_bounds__(64 * GP_WAVES) void network_bits_kernel(nb_kargs<ty
             bool def;
             const double t2 = Stat::t2(x, a.s, g, r, num, def);
             const bool side = a.c.tail == 0 || (a.c.tail == 1 ? num > 0.0 : num < 0.0);
-            const unsigned long long mask = __ballot(valid && alive && def && side && t2 > a.c.thr2);
+            const bool set = valid && alive && def && side && t2 > a.c.thr2;
+            const unsigned long long mask = __ballot(set);
             const int64_t p = (pg0 + g) * 16 + ks + 4 * r;
             if (col == 0 && p < P) a.c.bits[p * a.c.W2 + piece] = (uint16_t)(mask >> (16 * ks));
+            if constexpr (X) {
+                if (set && p < P) a.excess[p * (16 * a.c.W2) + c] = fmax(sqrt(t2) - a.thr, 0.0);
+            }
             if (a.c.t && p == 0 && valid) a.c.t[c] = (alive && def) ? copysign(sqrt(t2), num) : __builtin_nan("");
         }
     }
@@ -1124,6 +1143,112 @@ __global__ __launch_bounds__(CC_T) void graph_components_kernel(const uint32_t *
     }
 }
 
+struct ccw_args {
+    const uint32_t *bits;
+    const double *weights;             // (B, 32 W): read only where the bit is set
+    int64_t C;
+    int N, W;
+    int32_t *component, *n_edges, *max_extent, *max_regions;
+    double *intensity, *max_intensity;
+};
+
+// The same with a weight per set bit.  LDS as above, then (8-byte aligned) s[N] doubles and the maximum as one 64-bit word.
+// Labels, extents and regions exactly as graph_components_kernel makes them; then, with no floating-point atomic:
+//   s[n]               one thread per region: the weights of the set bits of row n (connections tri(n) .. tri(n) + n - 1, each
+//                      connection in the row of its larger endpoint), added in ascending connection order;
+//   a component's sum  one thread per root: s[y] over its regions y in ascending order (y >= the root, its smallest region);
+//   the maximum        weights are >= 0, so the sums order as their bit patterns do: a 64-bit integer atomicMax.
+// Every sum is a fixed sequence of additions of this row's values alone: the same bits whatever B or the row's place.
+__global__ __launch_bounds__(CC_T) void graph_components_weighted_kernel(ccw_args a) {
+    extern __shared__ uint32_t cc_lds[];
+    const int N = a.N, W = a.W;
+    uint32_t *words = cc_lds;
+    int *label = (int *)(words + W), *extent = label + N, *regions = extent + N, *sc = regions + N;
+    double *s = (double *)(cc_lds + ((W + 3 * N + 4 + 1) & ~1));
+    unsigned long long *smax = (unsigned long long *)(s + N);
+    const int tid = threadIdx.x;
+    const uint32_t *__restrict__ src = a.bits + (int64_t)blockIdx.x * W;
+    const double *__restrict__ wt = a.weights + (int64_t)blockIdx.x * W * 32;
+    const uint32_t last = (a.C & 31) ? (1u << (a.C & 31)) - 1u : ~0u;      // bits behind C are ignored
+    for (int w = tid; w < W; w += CC_T) words[w] = src[w] & (w == W - 1 ? last : ~0u);
+    for (int x = tid; x < N; x += CC_T) {
+        label[x] = x;
+        extent[x] = 0;
+        regions[x] = 0;
+    }
+    if (tid < 4) sc[tid] = 0;
+    if (tid == 0) *smax = 0ull;
+    __syncthreads();
+    for (int round = 0; round < N; ++round) {                // the fixed point of graph_components_kernel
+        int ch = 0;
+        for (int w = tid; w < W; w += CC_T) {
+            cc_for_bits(w, words[w], [&](int n, int m) {
+                const int ln = label[n], lm = label[m];
+                if (ln != lm) {
+                    const int lo = ln < lm ? ln : lm, hi = ln < lm ? lm : ln;
+                    atomicMin(&label[hi], lo);
+                    atomicMin(&label[ln < lm ? m : n], lo);
+                    ch = 1;
+                }
+            });
+        }
+        if (ch) sc[0] = 1;
+        __syncthreads();
+        const int changed = sc[0];
+        for (int x = tid; x < N; x += CC_T) {
+            const int l = label[x], ll = label[l];
+            if (ll < l) atomicMin(&label[x], ll);
+        }
+        __syncthreads();
+        if (!changed) break;
+        if (tid == 0) sc[0] = 0;
+        __syncthreads();
+    }
+    for (int w = tid; w < W; w += CC_T) cc_for_bits(w, words[w], [&](int n, int) { atomicAdd(&extent[label[n]], 1); });
+    for (int n = tid; n < N; n += CC_T) {                    // row sums: word by word, set bits in ascending order
+        double sum = 0.0;
+        const int c0 = (int)fcd_tri(n), c1 = c0 + n;         // (n = 0: no row)
+        for (int w = c0 >> 5; w <= (c1 - 1) >> 5 && c1 > c0; ++w) {
+            uint32_t word = words[w];
+            if (w == c0 >> 5) word &= ~0u << (c0 & 31);
+            if (w == c1 >> 5) word &= (1u << (c1 & 31)) - 1u;
+            while (word) {
+                const int j = __ffs((int)word) - 1;
+                word &= word - 1u;
+                sum += wt[w * 32 + j];
+            }
+        }
+        s[n] = sum;
+    }
+    __syncthreads();
+    for (int x = tid; x < N; x += CC_T) {
+        const int l = label[x];
+        if (extent[l] > 0) atomicAdd(&regions[l], 1);
+    }
+    __syncthreads();
+    for (int x = tid; x < N; x += CC_T) {
+        const int e = extent[x], l = label[x];
+        double total = 0.0;
+        if (e > 0) {                                         // x is a root
+            atomicAdd(&sc[1], e);
+            atomicMax(&sc[2], e);
+            atomicMax(&sc[3], regions[x]);
+            for (int y = x; y < N; ++y)
+                if (label[y] == x) total += s[y];
+            atomicMax(smax, (unsigned long long)__double_as_longlong(total));
+        }
+        if (a.component) a.component[(int64_t)blockIdx.x * N + x] = extent[l] > 0 ? l : -1;
+        if (a.intensity) a.intensity[(int64_t)blockIdx.x * N + x] = total;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        a.n_edges[blockIdx.x] = sc[1];
+        a.max_extent[blockIdx.x] = sc[2];
+        a.max_regions[blockIdx.x] = sc[3];
+        a.max_intensity[blockIdx.x] = __longlong_as_double((long long)*smax);
+    }
+}
+
 // ---- host: checks, the statistics' host sides, the two sequences -----------------------------------------------------------
 
 struct bl_in {                         // what every permutation call is given
@@ -1169,7 +1294,7 @@ __host__ static int glm_check(fcd_ctx *ctx, const char *who, const bl_in &d, int
     return FCD_OK;
 }
 
-// one shell of one statistic; which = 0, 1, 2: observed, permutations, bits
+// one shell of one statistic; which = 0, 1, 2, 3: observed, permutations, bits, bits with excess
 template <class Stat, class A>
 __host__ static int bl_launch(fcd_ctx *ctx, void (*kern)(A), int which, dim3 grid, hipStream_t st, A &a) {
     const size_t shmem = Stat::lds_bytes(a.s);
@@ -1359,9 +1484,10 @@ __host__ static int gp_run(fcd_ctx *ctx, const char *who, const bl_in &d, const 
 }
 
 // The bits of P labellings (rows == NULL: of the observed one).  Workspace: XT (KS, C, 4) | Q (C) | the statistic's.
+// excess != nullptr: the excess form of the kernel, which also writes the excess of every set bit.
 template <class Host>
 __host__ static int nb_run(fcd_ctx *ctx, const char *who, const bl_in &d, const Host &h, double threshold, int tail, uint32_t *bits,
-                           double *t, hipStream_t st) {
+                           double *t, hipStream_t st, double *excess = nullptr) {
     typedef typename Host::any::args A;
     constexpr int PB = Host::any::NB_G * 16;                 // labellings per wave
     const int64_t C = d.C, P = d.P, gy = (P + PB - 1) / PB, W = (C + 31) / 32;
@@ -1371,7 +1497,9 @@ __host__ static int nb_run(fcd_ctx *ctx, const char *who, const bl_in &d, const 
     int rc = fcd_ws_reserve(ctx, base + h.bytes(d, KS));
     if (rc) return rc;
     double *XT = (double *)ctx->ws.p, *Q = XT + (int64_t)KS * C * 4;
-    nb_kargs<A> a;
+    nb_xargs<A> a;
+    a.excess = excess;
+    a.thr = threshold;
     a.c.XT = XT;
     a.c.Q = Q;
     a.c.C = C;
@@ -1384,9 +1512,11 @@ __host__ static int nb_run(fcd_ctx *ctx, const char *who, const bl_in &d, const 
     a.c.t = t;
     if ((rc = h.setup(ctx, st, d, KS, XT, Q, (char *)ctx->ws.p + base, a.s))) return rc;
     if ((rc = h.pack(st, d, KS, a.s, false))) return rc;
+    const dim3 grid((unsigned)((2 * W + GP_WAVES - 1) / GP_WAVES), (unsigned)gy);
     return h.pick([&](auto s) {
         typedef decltype(s) Stat;
-        return bl_launch<Stat>(ctx, network_bits_kernel<Stat>, 2, dim3((unsigned)((2 * W + GP_WAVES - 1) / GP_WAVES), (unsigned)gy), st, a);
+        if (excess) return bl_launch<Stat>(ctx, network_bits_kernel<Stat, true>, 3, grid, st, a);
+        return bl_launch<Stat>(ctx, network_bits_kernel<Stat>, 2, grid, st, static_cast<nb_kargs<A> &>(a));
     });
 }
 
@@ -1526,4 +1656,52 @@ extern "C" int fcd_baseline_network_bits_glm(fcd_ctx *ctx, const double *b, cons
     if (!rc) rc = nb_check(ctx, who, d, perms, "the identity (perms == NULL) is P = 1, not %lld", threshold, tail);
     if (rc) return rc;
     return nb_run(ctx, who, d, glm_host{design, (int)R, perms}, threshold, tail, bits, t, (hipStream_t)stream);
+}
+
+extern "C" int fcd_baseline_network_excess(fcd_ctx *ctx, const fcd_network_excess_desc *x) {
+    static const char *who = "fcd_baseline_network_excess";
+    if (!ctx) return FCD_ERR_ARG;
+    if (!x) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "null descriptor");
+    if (x->size != sizeof(fcd_network_excess_desc))
+        return fcd_fail_who(ctx, FCD_ERR_ARG, who, "descriptor size %lld, this library's is %lld", x->size,
+                            (long long)sizeof(fcd_network_excess_desc));
+    const bl_in d = {x->b, x->bt, x->C, x->H, x->U, x->P};
+    const bool glm = x->design != nullptr;
+    int rc = bl_check(ctx, who, !x->b || !x->bt || !x->bits || !x->excess, d);
+    if (rc) return rc;
+    if (glm && x->flags) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "flags 0x%llx with a design: the covariate form has no options", x->flags);
+    rc = glm ? glm_check(ctx, who, d, x->R) : opt_check(ctx, who, d, (int)x->flags);
+    if (!rc)
+        rc = glm ? nb_check(ctx, who, d, x->perms, "the identity (perms == NULL) is P = 1, not %lld", x->threshold, x->tail)
+                 : nb_check(ctx, who, d, x->labels, "the observed labelling (labels == NULL) is P = 1, not %lld", x->threshold, x->tail);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)x->stream;
+    if (glm) return nb_run(ctx, who, d, glm_host{x->design, (int)x->R, x->perms}, x->threshold, x->tail, x->bits, x->t, st, x->excess);
+    if (x->flags) return nb_run(ctx, who, d, opt_host{x->labels, (int)x->flags, nullptr, nullptr}, x->threshold, x->tail, x->bits, x->t, st, x->excess);
+    return nb_run(ctx, who, d, plain_host{x->labels}, x->threshold, x->tail, x->bits, x->t, st, x->excess);
+}
+
+extern "C" int fcd_graph_components_weighted(fcd_ctx *ctx, const fcd_components_desc *x) {
+    static const char *who = "fcd_graph_components_weighted";
+    if (!ctx) return FCD_ERR_ARG;
+    if (!x) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "null descriptor");
+    if (x->size != sizeof(fcd_components_desc))
+        return fcd_fail_who(ctx, FCD_ERR_ARG, who, "descriptor size %lld, this library's is %lld", x->size, (long long)sizeof(fcd_components_desc));
+    if (x->flags) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "unknown flags 0x%llx", x->flags);
+    if (!x->bits || !x->weights || !x->n_edges || !x->max_extent || !x->max_regions || !x->max_intensity)
+        return fcd_fail_who(ctx, FCD_ERR_ARG, who, "null pointer");
+    if (x->B < 1 || x->C < 1) return fcd_fail_who(ctx, FCD_ERR_ARG, who, "B=%lld and C=%lld must be >= 1", x->B, x->C);
+    const int64_t N = fcd_C_to_N(x->C);
+    if (N < 2) return fcd_fail_who(ctx, FCD_ERR_SHAPE, who, "C=%lld is not a triangular number", x->C);
+    if (N > NB_NMAX) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "%lld regions, at most %lld", N, NB_NMAX);
+    if (x->B > INT32_MAX) return fcd_fail_who(ctx, FCD_ERR_UNSUPPORTED, who, "shape too large (Nreg=%lld, B=%lld)", N, x->B);
+    const int64_t W = (x->C + 31) / 32;
+    const size_t shmem = (size_t)((W + 3 * N + 4 + 1) & ~(int64_t)1) * sizeof(uint32_t) + (size_t)(N + 1) * sizeof(double);
+    int rc = fcd_lds_attr(ctx, FCD_KA_COMPONENTS_W, (const void *)graph_components_weighted_kernel, shmem);
+    if (rc) return rc;
+    ccw_args a = {x->bits,      x->weights,    x->C,           (int)N,       (int)W,          x->component,
+                  x->n_edges,   x->max_extent, x->max_regions, x->intensity, x->max_intensity};
+    hipLaunchKernelGGL(graph_components_weighted_kernel, dim3((unsigned)x->B), dim3(CC_T), shmem, (hipStream_t)x->stream, a);
+    FCD_LAUNCH_CHECK();
+    return FCD_OK;
 }

@@ -19,10 +19,11 @@
 enum { FCD_KA_F_GENERIC = 0, FCD_KA_F_COND, FCD_KA_F_DIFF, FCD_KA_F_PAIR, FCD_KA_F_PAIR_T = FCD_KA_F_PAIR + 4,
        FCD_KA_F_PAIR_R = FCD_KA_F_PAIR_T + 4, FCD_KA_F_PAIR_S = FCD_KA_F_PAIR_R + 4,
        FCD_KA_F_PAIR_BIG = FCD_KA_F_PAIR_S + 4, FCD_KA_R_STEP = FCD_KA_F_PAIR_BIG + 4, FCD_KA_R_PIPE = FCD_KA_R_STEP + 4, FCD_KA_CORR = FCD_KA_R_PIPE + 4, FCD_KA_COMPONENTS = FCD_KA_CORR + 1,
-       FCD_KA_GLM = FCD_KA_COMPONENTS + 1,      // 3 kernels (observed, permutations, bits) x 4 design widths
-       FCD_KA_PARTIAL = FCD_KA_GLM + 12,        // fcd_corr_partial's inversion kernel
+       FCD_KA_GLM = FCD_KA_COMPONENTS + 1,      // 4 kernels (observed, permutations, bits, bits with excess) x 4 design widths
+       FCD_KA_PARTIAL = FCD_KA_GLM + 16,        // fcd_corr_partial's inversion kernel
        FCD_KA_EIGH = FCD_KA_PARTIAL + 1,        // fcd_sym_eigh's Jacobi kernel
-       FCD_KA_N = FCD_KA_EIGH + 1 };
+       FCD_KA_COMPONENTS_W = FCD_KA_EIGH + 1,   // fcd_graph_components_weighted's kernel
+       FCD_KA_N = FCD_KA_COMPONENTS_W + 1 };
 
 #define FCD_NAN_SLOTS 256
 #define FCD_F_SLOTS 64

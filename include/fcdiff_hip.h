@@ -790,6 +790,66 @@ int fcd_baseline_network_bits_glm(fcd_ctx *ctx, const double *b, const double *b
  * FCD_ERR_ARG for a null pointer other than component, or a size < 1. */
 int fcd_graph_components(fcd_ctx *ctx, const uint32_t *bits, int64_t B, int64_t C, int32_t *component, int32_t *n_edges,
                          int32_t *max_extent, int32_t *max_regions, fcd_stream stream);
+/* Component intensity (the second size of the NBS toolbox): the sum over a component's connections of the excess
+ * e = max(|t| - threshold, 0).  Two entry points, each with one descriptor; a member an entry point does not name is not read.
+ *
+ * The bits pass with the excess of every set bit.  Which statistic: design != NULL the covariate form (design, R, perms; flags
+ * must be 0; labels is not read); otherwise flags = 0 the pooled t on complete data and flags = FCD_BASELINE_MISSING |
+ * FCD_BASELINE_WELCH the options (labels; design, R and perms are not read).  bits (P, W) and t (C,) of labelling 0 (nullable)
+ * exactly as fcd_baseline_network_bits, _opt or _glm writes them: the same kernel shell, tile product, t^2 and compare.  excess
+ * (P, 32 W) fp64: excess[p 32 W + c] = max(sqrt(t^2) - threshold, 0) WHERE BIT (p, c) IS SET, and nothing is stored anywhere
+ * else -- the buffer may be uninitialised, what lies at an unset bit stays.  t = +/-inf (complete separation) gives +inf.  The
+ * root is taken for set bits only.  A row equal to the observed labelling (the identity) gives the observed excess bit for bit.
+ * Refusals: those of the bits entry point of the statistic, a null descriptor or excess, size != sizeof(fcd_network_excess_desc)
+ * (FCD_ERR_ARG), flags with a design (FCD_ERR_UNSUPPORTED). */
+typedef struct fcd_network_excess_desc {
+    uint32_t size;             /* sizeof(fcd_network_excess_desc): the version of the layout */
+    uint32_t flags;            /* FCD_BASELINE_MISSING | FCD_BASELINE_WELCH; 0 with a design */
+    int64_t C, H, U, P;
+    double threshold;          /* finite, > 0 */
+    int32_t tail;              /* FCD_TAIL_* */
+    int32_t R;                 /* design columns, 1 .. 9 */
+    fcd_stream stream;         /* every launch goes here */
+    /* device, read */
+    const double *b;           /* (C, H) */
+    const double *bt;          /* (C, U) */
+    const uint8_t *labels;     /* (P, S), or NULL with P = 1: the observed labelling */
+    const double *design;      /* (S, R), or NULL: no covariates */
+    const uint16_t *perms;     /* (P, S), or NULL with P = 1: the identity */
+    /* device, written */
+    uint32_t *bits;            /* (P, W) */
+    double *excess;            /* (P, 32 W), only where the bit is set */
+    double *t;                 /* (C,) or NULL */
+} fcd_network_excess_desc;
+int fcd_baseline_network_excess(fcd_ctx *ctx, const fcd_network_excess_desc *d);
+/* The components with a weight per set bit: bits (B, W), weights (B, 32 W) fp64, >= 0 (+inf allowed) where the bit is set and
+ * read nowhere else.  component, n_edges, max_extent, max_regions as fcd_graph_components gives them.  intensity (B, Nreg),
+ * nullable: the sum of the weights of a component's connections at the index of its label, 0.0 everywhere else;
+ * max_intensity (B,): the largest of them, 0.0 where no bit is set.  Summation order: per region n the set bits of its row
+ * (connections tri(n) .. tri(n) + n - 1) in ascending order, then per component these row sums over its regions in ascending
+ * order; the maximum is an integer compare of the bit patterns.  No floating-point atomic: a row of bits gives the same
+ * bits of result whatever B and wherever it stands.  One workgroup per row, 8 (Nreg + 1) bytes of LDS more than
+ * fcd_graph_components (86 KB at 1024 regions, one workgroup per CU).  One launch, no workspace.
+ * Refusals as fcd_graph_components; also a null descriptor, weights or max_intensity, size != sizeof(fcd_components_desc)
+ * (FCD_ERR_ARG), flags != 0 (FCD_ERR_UNSUPPORTED). */
+typedef struct fcd_components_desc {
+    uint32_t size;             /* sizeof(fcd_components_desc): the version of the layout */
+    uint32_t flags;            /* 0 */
+    int64_t B;                 /* rows of bits */
+    int64_t C;                 /* connections, triangular, at most 1024 regions */
+    fcd_stream stream;         /* the launch goes here */
+    /* device, read */
+    const uint32_t *bits;      /* (B, W) */
+    const double *weights;     /* (B, 32 W) */
+    /* device, written */
+    int32_t *component;        /* (B, Nreg) or NULL */
+    int32_t *n_edges;          /* (B,) */
+    int32_t *max_extent;       /* (B,) */
+    int32_t *max_regions;      /* (B,) */
+    double *intensity;         /* (B, Nreg) or NULL */
+    double *max_intensity;     /* (B,) */
+} fcd_components_desc;
+int fcd_graph_components_weighted(fcd_ctx *ctx, const fcd_components_desc *d);
 
 /* ---- variational updates ------------------------------------------------------------------ */
 /* UnsharedRegionFit._update_lq_F, fit.py:157-174 (+ _eval_q_R_w 382-406). */
