@@ -58,16 +58,33 @@ from .gibbs import (GibbsEngine, run_chains, allreduce_counts, pool_u32, pair_sw
                     COUNT_MAX_NREG, COUNT_MAX_U, region_sets_csr, patient_groups_csr, patient_group_contrasts,
                     patient_traits_scores, PATIENT_TRAIT_BINS)
 
-# The knobs of a gibbs fit that attach one of the sampler's accumulators: knob, its period knob, what the messages call it,
-# the row of gibbs.ACCUMULATORS, and the attributes the pooled buffers and the number of sweeps behind them are left in.
-FitAccumulator = collections.namedtuple("FitAccumulator", "knob every label engine results sweeps")
+# The knobs of a gibbs fit that attach one of the sampler's accumulators, in the order _run_gibbs() checks, attaches and
+# collects them (the region sets before the groups and traits that take them as rows): knob (a flag, or with `give` a
+# collection that is on unless None), its period knob, what the messages call it, the row of gibbs.ACCUMULATORS, the attributes
+# the pooled buffers and the number of sweeps behind them are left in, and the attributes that describe those buffers (`meta`).
+# Three optional hooks, names of methods of the fit: check(a, N, U) refuses before any engine is made (default
+# _check_accumulator_row), give(eng) hands the collection to the engine before its accumulator is attached, collect(eng) fills
+# `meta` and reshapes after the buffers were pooled.
+FitAccumulator = collections.namedtuple("FitAccumulator", "knob every label engine results sweeps meta check give collect")
+_ENGINE_ROW = {a.key: a for a in ACCUMULATORS}
 GIBBS_ACCUMULATORS = (
-    FitAccumulator("connection_marginals", "connection_every", "connection counts", ACCUMULATORS[0],
-                   ("connection_counts",), "connection_sweeps"),
-    FitAccumulator("anomaly_counts", "anomaly_counts_every", "anomaly-count histograms", ACCUMULATORS[1],
-                   ("patient_count_hist", "region_count_hist"), "anomaly_count_sweeps"),
-    FitAccumulator("coanomaly", "coanomaly_every", "co-anomaly counts", ACCUMULATORS[2],
-                   ("region_pair_counts", "patient_pair_counts"), "coanomaly_sweeps"),
+    FitAccumulator("connection_marginals", "connection_every", "connection counts", _ENGINE_ROW["pair"],
+                   ("connection_counts",), "connection_sweeps", (), None, None, None),
+    FitAccumulator("anomaly_counts", "anomaly_counts_every", "anomaly-count histograms", _ENGINE_ROW["count"],
+                   ("patient_count_hist", "region_count_hist"), "anomaly_count_sweeps", (), "_check_anomaly_counts", None, None),
+    FitAccumulator("coanomaly", "coanomaly_every", "co-anomaly counts", _ENGINE_ROW["coanomaly"],
+                   ("region_pair_counts", "patient_pair_counts"), "coanomaly_sweeps", (), None, None, "_collect_coanomaly"),
+    FitAccumulator("region_sets", "region_sets_every", "region-set histograms", _ENGINE_ROW["region_set"],
+                   ("region_set_hist", "region_set_prevalence_hist"), "region_set_sweeps", ("region_set_names", "region_set_sizes"),
+                   "_check_region_sets", "_give_region_sets", "_collect_region_sets"),
+    FitAccumulator("patient_groups", "patient_groups_every", "patient-group histograms", _ENGINE_ROW["patient_group"],
+                   ("patient_group_hist", "patient_group_joint_hist"), "patient_group_sweeps",
+                   ("patient_group_names", "patient_group_sizes", "patient_group_rows", "patient_group_pairs"),
+                   "_check_patient_groups", "_give_patient_groups", "_collect_patient_groups"),
+    FitAccumulator("patient_traits", "patient_traits_every", "patient-trait histograms", _ENGINE_ROW["patient_trait"],
+                   ("patient_trait_hist", "patient_trait_sum"), "patient_trait_sweeps",
+                   ("patient_trait_names", "patient_trait_n_known", "patient_trait_rows"),
+                   "_check_patient_traits", "_give_patient_traits", "_collect_patient_traits"),
 )
 
 
@@ -784,48 +801,18 @@ class UnsharedRegionFit(object):
         t = self._torch()
         self.coanomaly_states = 0
         for a in GIBBS_ACCUMULATORS:
-            for name in a.results:
+            for name in a.results + a.meta:
                 setattr(self, name, None)
             setattr(self, a.sweeps, 0)
-            if getattr(self, a.knob):
-                self._check_accumulator(a.every, a.label, sites=a.engine.sites(N, U) if a.engine.sites else 1)
-        (self.region_set_hist, self.region_set_prevalence_hist, self.region_set_sweeps) = (None, None, 0)
-        (self.region_set_names, self.region_set_sizes) = (None, None)
-        if self.region_sets is not None:            # (beside the loop: the knob is a collection, not a flag)
-            region_sets_csr(self.region_sets, N)
-            self._check_accumulator("region_sets_every", "region-set histograms")
-            if U > COUNT_MAX_U:
-                raise ValueError("region-set histograms are made for at most %d patients (here %d)" % (COUNT_MAX_U, U))
-        (self.patient_group_hist, self.patient_group_joint_hist, self.patient_group_sweeps) = (None, None, 0)
-        (self.patient_group_names, self.patient_group_sizes) = (None, None)
-        (self.patient_group_rows, self.patient_group_pairs) = (None, None)
-        if self.patient_groups is not None:
-            self._refuse_patient_groups_shared()
-            patient_group_contrasts(self.patient_group_contrasts, *patient_groups_csr(self.patient_groups, U))
-            self._check_accumulator("patient_groups_every", "patient-group histograms")
-        (self.patient_trait_hist, self.patient_trait_sum, self.patient_trait_sweeps) = (None, None, 0)
-        (self.patient_trait_names, self.patient_trait_n_known, self.patient_trait_rows) = (None, None, None)
-        if self.patient_traits is not None:
-            self._refuse_patient_traits_shared()
-            patient_traits_scores(self.patient_traits, U)
-            self._check_accumulator("patient_traits_every", "patient-trait histograms")
-        if self.anomaly_counts and (N > COUNT_MAX_NREG or U > COUNT_MAX_U):
-            raise ValueError("anomaly-count histograms are made for at most %d regions and %d patients (here %d, %d)"
-                             % (COUNT_MAX_NREG, COUNT_MAX_U, N, U))
+        live = [a for a in GIBBS_ACCUMULATORS if self._accumulator_on(a)]
+        for a in live:
+            getattr(self, a.check or "_check_accumulator_row")(a, N, U)
         eng = GibbsEngine(self._d["S_B"], self._d["lM"], N, U, self.n_chains, chain0=self.chain0, seed=self.seed,
                           edge_index=self._edge_mode(), ctx=self._context())
-        for a in GIBBS_ACCUMULATORS:
-            if getattr(self, a.knob):
-                eng._attach(a.engine, getattr(self, a.every))
-        if self.region_sets is not None:
-            eng.set_region_sets(self.region_sets)
-            eng.attach_region_set_accumulator(self.region_sets_every)
-        if self.patient_groups is not None:         # (after the region sets: they are rows of these histograms)
-            eng.set_patient_groups(self.patient_groups, self.patient_group_contrasts)
-            eng.attach_patient_group_accumulator(self.patient_groups_every)
-        if self.patient_traits is not None:         # (after the region sets, for the same reason)
-            eng.set_patient_traits(self.patient_traits)
-            eng.attach_patient_trait_accumulator(self.patient_traits_every)
+        for a in live:      # (in the table's order: the region sets are set before the accumulators that take them as rows)
+            if a.give:
+                getattr(self, a.give)(eng)
+            getattr(eng, "attach_%s_accumulator" % a.engine.key)(getattr(self, a.every))
         pi2 = self._pi2()
         eng.set_hyper(np.asarray(self.model.gamma, dtype=np.float64), pi2)
         eng.init(float(pi2[1]))
@@ -877,38 +864,78 @@ class UnsharedRegionFit(object):
             self._lq_F = np.log(cnt[:3 * C].reshape(C, 1, 3) / total)
             p1 = cnt[3 * C:3 * C + N * U].reshape(N, U) / total
             self._lq_R = np.log(np.stack([1.0 - p1, p1], axis=2))
-        for a in GIBBS_ACCUMULATORS:
-            if getattr(eng, a.engine.attr) is not None:
-                for (name, buf) in zip(a.results, eng._acc_buffers(a.engine)):
-                    setattr(self, name, pool_u32(buf).cpu().numpy())
-                setattr(self, a.sweeps, getattr(eng, a.engine.key + "_sweeps"))
-        if eng.region_set_acc is not None:
-            (self.region_set_hist, self.region_set_prevalence_hist) = (pool_u32(b).cpu().numpy() for b in eng.region_set_acc)
-            self.region_set_sweeps = eng.region_set_sweeps
-            (self.region_set_names, self.region_set_sizes) = (list(eng.region_names), np.diff(eng.region_offsets).astype(np.int64))
-        if getattr(eng, "patient_group_acc", None) is not None:
-            (hg, hj) = (pool_u32(b).cpu().numpy() for b in eng.patient_group_acc)
-            sizes = np.diff(eng.group_offsets).astype(np.int64)
-            self.patient_group_hist = hg
-            self.patient_group_joint_hist = [
-                hj[hg.shape[1] * lo:hg.shape[1] * hi].reshape(hg.shape[1], sizes[a] + 1, sizes[b] + 1)
-                for ((a, b), lo, hi) in zip(eng.group_contrasts, eng.group_bin_offsets[:-1], eng.group_bin_offsets[1:])]
-            self.patient_group_sweeps = eng.patient_group_sweeps
-            (self.patient_group_names, self.patient_group_sizes) = (list(eng.group_names), sizes)
-            (self.patient_group_rows, self.patient_group_pairs) = (eng.patient_group_row_names(), eng.group_contrasts.copy())
-        if getattr(eng, "patient_trait_acc", None) is not None:
-            (th, ts) = eng.patient_trait_acc
-            self.patient_trait_hist = pool_u32(th).cpu().numpy()
-            self.patient_trait_sum = allreduce_counts(ts.clone()).cpu().numpy()        # (int64 already)
-            self.patient_trait_sweeps = eng.patient_trait_sweeps
-            (self.patient_trait_names, self.patient_trait_n_known) = (list(eng.trait_names), eng.trait_n_known.copy())
-            self.patient_trait_rows = eng.patient_trait_row_names()
-        if eng.coanomaly_acc is not None:
-            states = t.tensor([eng.coanomaly_sweeps * eng.G], dtype=t.int64, device=eng.cnt_f.device)
-            self.coanomaly_states = int(allreduce_counts(states).cpu()[0])
+        for a in live:
+            bufs = getattr(eng, a.engine.attr)
+            for (name, buf, dtype) in zip(a.results, bufs if a.engine.paired else (bufs,), a.engine.dtypes):
+                # (uint32 counts pool as int64 values; an int64 buffer of signed sums is summed as it is, on a copy)
+                setattr(self, name, (pool_u32(buf) if dtype == "int32" else allreduce_counts(buf.clone())).cpu().numpy())
+            setattr(self, a.sweeps, getattr(eng, a.engine.key + "_sweeps"))
+            if a.collect:
+                getattr(self, a.collect)(eng)
         (gamma, pi) = eng.hyper_values()
         self.model.gamma = gamma
         self.model.pi = pi
+
+    # ---- the rows of GIBBS_ACCUMULATORS: which are on, and the hooks they name ----
+    def _accumulator_on(self, a):
+        knob = getattr(self, a.knob)
+        return knob is not None if a.give else bool(knob)
+
+    def _check_accumulator_row(self, a, N, U):
+        self._check_accumulator(a.every, a.label, sites=a.engine.sites(N, U) if a.engine.sites else 1)
+
+    def _check_anomaly_counts(self, a, N, U):
+        self._check_accumulator_row(a, N, U)
+        if N > COUNT_MAX_NREG or U > COUNT_MAX_U:
+            raise ValueError("anomaly-count histograms are made for at most %d regions and %d patients (here %d, %d)"
+                             % (COUNT_MAX_NREG, COUNT_MAX_U, N, U))
+
+    def _collect_coanomaly(self, eng):
+        t = self._torch()
+        states = t.tensor([eng.coanomaly_sweeps * eng.G], dtype=t.int64, device=eng.cnt_f.device)
+        self.coanomaly_states = int(allreduce_counts(states).cpu()[0])
+
+    def _check_region_sets(self, a, N, U):
+        region_sets_csr(self.region_sets, N)
+        self._check_accumulator_row(a, N, U)
+        if U > COUNT_MAX_U:
+            raise ValueError("region-set histograms are made for at most %d patients (here %d)" % (COUNT_MAX_U, U))
+
+    def _give_region_sets(self, eng):
+        eng.set_region_sets(self.region_sets)
+
+    def _collect_region_sets(self, eng):
+        (self.region_set_names, self.region_set_sizes) = (list(eng.region_names), np.diff(eng.region_offsets).astype(np.int64))
+
+    def _check_patient_groups(self, a, N, U):
+        self._refuse_patient_groups_shared()
+        patient_group_contrasts(self.patient_group_contrasts, *patient_groups_csr(self.patient_groups, U))
+        self._check_accumulator_row(a, N, U)
+
+    def _give_patient_groups(self, eng):
+        eng.set_patient_groups(self.patient_groups, self.patient_group_contrasts)
+
+    def _collect_patient_groups(self, eng):
+        """The names behind the histograms, and the flat joint histogram as one (R, |a|+1, |b|+1) array per contrast."""
+        (hj, R) = (self.patient_group_joint_hist, self.patient_group_hist.shape[1])
+        sizes = np.diff(eng.group_offsets).astype(np.int64)
+        self.patient_group_joint_hist = [
+            hj[R * lo:R * hi].reshape(R, sizes[a] + 1, sizes[b] + 1)
+            for ((a, b), lo, hi) in zip(eng.group_contrasts, eng.group_bin_offsets[:-1], eng.group_bin_offsets[1:])]
+        (self.patient_group_names, self.patient_group_sizes) = (list(eng.group_names), sizes)
+        (self.patient_group_rows, self.patient_group_pairs) = (eng.patient_group_row_names(), eng.group_contrasts.copy())
+
+    def _check_patient_traits(self, a, N, U):
+        self._refuse_patient_traits_shared()
+        patient_traits_scores(self.patient_traits, U)
+        self._check_accumulator_row(a, N, U)
+
+    def _give_patient_traits(self, eng):
+        eng.set_patient_traits(self.patient_traits)
+
+    def _collect_patient_traits(self, eng):
+        (self.patient_trait_names, self.patient_trait_n_known) = (list(eng.trait_names), eng.trait_n_known.copy())
+        self.patient_trait_rows = eng.patient_trait_row_names()
 
     def _check_accumulator(self, knob, what, sites=1):
         """A uint32 accumulator of the gibbs run: its period self.<knob> is an integer >= 1 and, at that period, chains x

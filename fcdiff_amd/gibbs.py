@@ -24,53 +24,43 @@ from . import util
 PAIR_COUNT_MAX = (1 << 32) - 1
 COUNT_MAX_NREG, COUNT_MAX_U = 1023, 512      # largest shape of the anomalous-region histograms (fcd_gibbs_count_tally)
 
-# The uint32 accumulators GibbsEngine.run() can add to after a counted sweep, in the order it checks and attaches them.
-# Engine attributes of one: `attr` holds the buffers (None: detached; one tensor, or a pair where `paired`), <key>_every the
-# period and <key>_sweeps the sweeps added so far.  shapes: engine -> shape of each buffer; setter: the library's entry point
-# (buffers, Nreg, U, every); sites: None, or (Nreg, U) -> how many sites of a chain one counter can take per sweep; label:
-# the accumulator's name in the error messages.
-Accumulator = collections.namedtuple("Accumulator", "key attr paired shapes setter sites label")
-ACCUMULATORS = (
-    Accumulator("pair", "pair_acc", False, lambda e: ((e.C, e.U, 3, 3),), "fcd_gibbs_set_pair_accumulator", None, "pair"),
-    Accumulator("count", "count_hist", True, lambda e: ((e.U, e.Nreg + 1), (e.Nreg, e.U + 1)),
-                "fcd_gibbs_set_count_accumulator", None, "count"),
-    # (a diagonal entry counts up to G x U or G x Nreg sites per sweep)
-    Accumulator("coanomaly", "coanomaly_acc", True, lambda e: ((e.Nreg, e.Nreg), (e.U, e.U)),
-                "fcd_gibbs_set_coanomaly_accumulator", lambda Nreg, U: max(Nreg, U), "co-anomaly"),
-)
-(_PAIR, _COUNT, _COANOMALY) = ACCUMULATORS
-# Further accumulators: run() walks them after ACCUMULATORS under the same rule, reading the engine's attribute with a default
-# of None (an engine that never heard of one makes no context call for it).  A new accumulator goes here: tests pin the three
-# rows above.  The region-set histograms take their shapes from the sets of set_region_sets().
 REGION_SET_MAX_SIZE, REGION_SET_MAX_SETS = 1023, 1024     # fcd_region_sets_set
-EXTRA_ACCUMULATORS = (
-    Accumulator("region_set", "region_set_acc", True,
-                lambda e: ((e.region_J, e.U, e.region_smax + 1), (e.region_J, e.U + 1)),
-                "fcd_gibbs_set_region_set_accumulator", None, "region-set"),
-)
-(_REGION_SET,) = EXTRA_ACCUMULATORS
-# The patient-group histograms, in a tuple of their own (tests unpack the two above by length): run() walks it last, under the
-# rule of EXTRA_ACCUMULATORS.  Shapes from set_patient_groups(): (J, R, Umax+1) and the flat joint histograms of the contrasts.
 PATIENT_GROUP_MAX_U, PATIENT_GROUP_MAX_GROUPS, PATIENT_GROUP_MAX_CONTRASTS = 512, 64, 64     # fcd_patient_groups_set
 PATIENT_GROUP_MAX_BINS = 16384          # (|a|+1)(|b|+1) of a contrast: the LDS of the workgroup that owns a joint row
-GROUP_ACCUMULATORS = (
+PATIENT_TRAIT_MAX_U, PATIENT_TRAIT_MAX_TRAITS, PATIENT_TRAIT_BINS = 512, 16, 128     # fcd_patient_traits_set
+
+# The accumulators GibbsEngine.run() can add to after a counted sweep, in the order it checks and attaches them (the order of
+# FCD_ACC_* in fcd_common.h).  Engine attributes of one: `attr` holds the buffers (None: detached; one tensor, or a pair where
+# `paired`), <key>_every the period and <key>_sweeps the sweeps added so far.  shapes: engine -> shape of each buffer; dtypes:
+# of each buffer ("int32" holds uint32 counts, like cnt_f; "int64" sums of signed scores); setter: the library's entry point
+# (buffers, Nreg, U, every); sites: None, or (Nreg, U) -> how many sites of a chain one counter can take per sweep; label: the
+# accumulator's name in the error messages; send: None, or the engine's method that puts on the shared context what the
+# setter's kernels read there (sets, groups, traits), called before the setter.
+Accumulator = collections.namedtuple("Accumulator", "key attr paired shapes dtypes setter sites label send")
+ACCUMULATORS = (
+    Accumulator("pair", "pair_acc", False, lambda e: ((e.C, e.U, 3, 3),), ("int32",),
+                "fcd_gibbs_set_pair_accumulator", None, "pair", None),
+    Accumulator("count", "count_hist", True, lambda e: ((e.U, e.Nreg + 1), (e.Nreg, e.U + 1)), ("int32", "int32"),
+                "fcd_gibbs_set_count_accumulator", None, "count", None),
+    # (a diagonal entry counts up to G x U or G x Nreg sites per sweep)
+    Accumulator("coanomaly", "coanomaly_acc", True, lambda e: ((e.Nreg, e.Nreg), (e.U, e.U)), ("int32", "int32"),
+                "fcd_gibbs_set_coanomaly_accumulator", lambda Nreg, U: max(Nreg, U), "co-anomaly", None),
+    # (shapes from the sets of set_region_sets())
+    Accumulator("region_set", "region_set_acc", True,
+                lambda e: ((e.region_J, e.U, e.region_smax + 1), (e.region_J, e.U + 1)), ("int32", "int32"),
+                "fcd_gibbs_set_region_set_accumulator", None, "region-set", "_send_region_sets"),
+    # (shapes from set_patient_groups(): (J, R, Umax+1) and the flat joint histograms of the contrasts)
     Accumulator("patient_group", "patient_group_acc", True,
                 lambda e: ((e.group_J, e.patient_group_rows(), e.group_umax + 1),
-                           (max(1, e.patient_group_rows() * int(e.group_bin_offsets[-1])),)),
-                "fcd_gibbs_set_patient_group_accumulator", None, "patient-group"),
-)
-(_PATIENT_GROUP,) = GROUP_ACCUMULATORS
-# The rank-sum (AUC) accumulator of the patient traits, again in a tuple of its own, walked last.  Its first buffer is uint32
-# like the others, (Q, R, Umax+1 + NB + 3); the second, (Q, R, Umax+1), is INT64 (sums of signed scores):
-# attach_patient_trait_accumulator() makes it, patient_trait_host() reads it as it is.
-PATIENT_TRAIT_MAX_U, PATIENT_TRAIT_MAX_TRAITS, PATIENT_TRAIT_BINS = 512, 16, 128     # fcd_patient_traits_set
-TRAIT_ACCUMULATORS = (
+                           (max(1, e.patient_group_rows() * int(e.group_bin_offsets[-1])),)), ("int32", "int32"),
+                "fcd_gibbs_set_patient_group_accumulator", None, "patient-group", "_send_patient_groups"),
+    # (rank sums of the patient traits: (Q, R, Umax+1 + NB + 3) counts and (Q, R, Umax+1) sums)
     Accumulator("patient_trait", "patient_trait_acc", True,
                 lambda e: ((e.trait_Q, e.patient_trait_rows(), e.trait_umax + 1 + PATIENT_TRAIT_BINS + 3),
-                           (e.trait_Q, e.patient_trait_rows(), e.trait_umax + 1)),
-                "fcd_gibbs_set_patient_trait_accumulator", None, "patient-trait"),
+                           (e.trait_Q, e.patient_trait_rows(), e.trait_umax + 1)), ("int32", "int64"),
+                "fcd_gibbs_set_patient_trait_accumulator", None, "patient-trait", "_send_patient_traits"),
 )
-(_PATIENT_TRAIT,) = TRAIT_ACCUMULATORS
+(_PAIR, _COUNT, _COANOMALY, _REGION_SET, _PATIENT_GROUP, _PATIENT_TRAIT) = ACCUMULATORS
 
 
 # the wording of _index_sets_csr()'s refusals for the two axes: knob, one set, many, a member, the mask's name and extent
@@ -302,36 +292,21 @@ class GibbsEngine(object):
         self.cnt_f = torch.zeros((self.C, 3), dtype=torch.int32, device=dev)
         self.cnt_r = torch.zeros((self.Nreg, self.U), dtype=torch.int32, device=dev)
         self.n_accumulated = 0
-        self.pair_acc = None        # (C, U, 3, 3) counts of (f_c, mixture case) that run() adds to (attach_pair_accumulator)
-        self.pair_every = 1
-        self.pair_sweeps = 0        # sweeps added to pair_acc so far
-        self.count_hist = None      # (hist_patient (U, Nreg+1), hist_region (Nreg, U+1)) that run() adds to (attach_count_accumulator)
-        self.count_every = 1
-        self.count_sweeps = 0       # sweeps added to count_hist so far
-        self.coanomaly_acc = None   # (region_pairs (Nreg, Nreg), patient_pairs (U, U)) that run() adds to (attach_coanomaly_accumulator)
-        self.coanomaly_every = 1
-        self.coanomaly_sweeps = 0   # sweeps added to coanomaly_acc so far
+        for a in ACCUMULATORS:      # a.attr: the buffers run() adds to (None until attach_<key>_accumulator()), period, sweeps so far
+            self._detach(a)
+            setattr(self, a.key + "_every", 1)
         self.region_names = None    # the sets of set_region_sets(): names, CSR offsets and members, their number, the largest
         self.region_offsets = self.region_members = None
         self.region_J = self.region_smax = 0
-        self.region_set_acc = None  # (hist_set (J, U, S_max+1), hist_prev (J, U+1)) that run() adds to (attach_region_set_accumulator)
-        self.region_set_every = 1
-        self.region_set_sweeps = 0  # sweeps added to region_set_acc so far
         self.group_names = None     # the groups of set_patient_groups(): names, CSR offsets and members, contrasts (P, 2) and
         self.group_offsets = self.group_members = self.group_contrasts = None      # the bin offsets of their joint histograms
         self.group_bin_offsets = None
         self.group_J = self.group_umax = 0
         self.group_with_sets = False        # the rows of patient_group_acc include the region sets it was attached with
-        self.patient_group_acc = None       # (hist_group (J, R, Umax+1), hist_joint flat) that run() adds to (attach_patient_group_accumulator)
-        self.patient_group_every = 1
-        self.patient_group_sweeps = 0       # sweeps added to patient_group_acc so far
         self.trait_names = None     # the traits of set_patient_traits(): names, scores (Q, U) int32, known (Q, U) bool, n_known (Q,)
         self.trait_scores = self.trait_known = self.trait_n_known = None
         self.trait_Q = self.trait_umax = 0
         self.trait_with_sets = False        # the rows of patient_trait_acc include the region sets it was attached with
-        self.patient_trait_acc = None       # (trait_hist (Q, R, Umax+1+NB+3) uint32-in-int32, trait_sum (Q, R, Umax+1) int64) that run() adds to
-        self.patient_trait_every = 1
-        self.patient_trait_sweeps = 0       # sweeps added to patient_trait_acc so far
         self.ctx.call("fcd_ctx_reserve", self.Nreg, self.U, self.G)
         self.lMd = self.lMf = None
         if region_major:
@@ -416,21 +391,14 @@ class GibbsEngine(object):
         counters from sweep `accumulate_from` on (None: never), runs the (pi, gamma) M-step on this rank's pooled counts
         every `mstep_every` sweeps (0: never -- several ranks all-reduce the returned counts and call mstep()), and
         packs the r words of the next f pass.  Returns the counts tensor of the last sweep (or None).
-        With a pair accumulator attached (attach_pair_accumulator) the same call also adds the (f_c, mixture case) counts
-        of every `pair_every`-th sweep from `accumulate_from` on, and with a count accumulator attached
-        (attach_count_accumulator) the histograms of the anomalous-region counts of every `count_every`-th sweep, and with
-        a co-anomaly accumulator attached (attach_coanomaly_accumulator) the two pair matrices of every
-        `coanomaly_every`-th sweep, and with a region-set accumulator attached (attach_region_set_accumulator) the
-        histograms over the region sets of every `region_set_every`-th sweep, and with a patient-group accumulator attached
-        (attach_patient_group_accumulator) the histograms over the patient groups of every `patient_group_every`-th sweep, and
-        with a patient-trait accumulator attached (attach_patient_trait_accumulator) the rank-sum histograms and sums of every
-        `patient_trait_every`-th sweep; a call that could overflow any of them raises ValueError.
+        The same call also adds to every attached accumulator of ACCUMULATORS (attach_<key>_accumulator) at every
+        <key>_every-th sweep from `accumulate_from` on; a call that could overflow a counter of one raises ValueError.
         """
         acc = accumulate_from is not None
         live = []                   # (accumulator, sweeps this call adds to it), attached ones only
-        # (in this order, and nothing of an accumulator is read unless it is attached)
-        for a in ACCUMULATORS + EXTRA_ACCUMULATORS + GROUP_ACCUMULATORS + TRAIT_ACCUMULATORS:
-            if not acc or (getattr(self, a.attr) if a in ACCUMULATORS else getattr(self, a.attr, None)) is None:
+        # (in the table's order, and nothing more of an accumulator is read unless it is attached)
+        for a in ACCUMULATORS:
+            if not acc or getattr(self, a.attr) is None:
                 continue
             n = pair_sweeps_in(int(sweep0), int(n_sweeps), int(accumulate_from), getattr(self, a.key + "_every"))
             total = getattr(self, a.key + "_sweeps") + n
@@ -442,12 +410,8 @@ class GibbsEngine(object):
         # (attached for this call only: the context is shared, no other engine's sweeps may add to these buffers)
         try:
             for (a, _n) in live:
-                if a is _REGION_SET:
-                    self._send_region_sets()
-                if a is _PATIENT_GROUP:
-                    self._send_patient_groups()
-                if a is _PATIENT_TRAIT:
-                    self._send_patient_traits()
+                if a.send:
+                    getattr(self, a.send)()
                 self.ctx.call(a.setter, *([_lib.dptr(b) for b in self._acc_buffers(a)]
                                           + [self.Nreg, self.U, getattr(self, a.key + "_every")]))
             self._run(sweep0, n_sweeps, mstep_every, accumulate_from, want_counts)
@@ -478,8 +442,9 @@ class GibbsEngine(object):
         if every < 1:
             raise ValueError("every must be >= 1")
         t = self.torch
-        # (uint32 on the device, held in int32 tensors like cnt_f; _acc_host() reads them back as uint32)
-        bufs = tuple(t.zeros(shape, dtype=t.int32, device=self.f_state.device) for shape in a.shapes(self))
+        # (uint32 on the device is held in int32 tensors like cnt_f; _acc_host() reads those back as uint32)
+        bufs = tuple(t.zeros(shape, dtype=getattr(t, dtype), device=self.f_state.device)
+                     for (shape, dtype) in zip(a.shapes(self), a.dtypes))
         setattr(self, a.attr, bufs if a.paired else bufs[0])
         setattr(self, a.key + "_every", every)
         setattr(self, a.key + "_sweeps", 0)
@@ -492,8 +457,33 @@ class GibbsEngine(object):
     def _acc_host(self, a):
         if getattr(self, a.attr) is None:
             raise ValueError("no %s accumulator is attached" % a.label)
-        out = tuple(self.host(b).view(np.uint32) for b in self._acc_buffers(a))
+        out = tuple(self.host(b).view(np.uint32) if dtype == "int32" else self.host(b)
+                    for (b, dtype) in zip(self._acc_buffers(a), a.dtypes))
         return out if a.paired else out[0]
+
+    # ---- what the patient-group and patient-trait accumulators (`what`: "group", "trait") share: rows, and the context ----
+    def _rows(self, a, what):
+        """R: the regions and, while an attached accumulator has them or else if region sets are set, the region sets after them."""
+        with_sets = getattr(self, what + "_with_sets") if getattr(self, a.attr) is not None else bool(self.region_J)
+        return self.Nreg + (self.region_J if with_sets else 0)
+
+    def _row_names(self, R):
+        """The names of R rows: the region indices as str, then "set:<name>" for the region sets."""
+        return [str(n) for n in range(self.Nreg)] + ["set:" + s for s in (self.region_names or [])[:R - self.Nreg]]
+
+    def _send_rows(self, what, R, setter, *args):
+        """
+        As _send_region_sets(), for the groups or traits (`what`) of this engine: the shared context holds them (and, where
+        the R rows include them, this engine's region sets) before a launch.
+        """
+        with_sets = R > self.Nreg
+        if with_sets:
+            self._send_region_sets()
+        owner = getattr(self.ctx, "patient_%ss_owner" % what, None)
+        if owner is not None and owner[0]() is self and owner[1] == with_sets:
+            return
+        self.ctx.call(setter, *(args + (1 if with_sets else 0,)))
+        setattr(self.ctx, "patient_%ss_owner" % what, (weakref.ref(self), with_sets))
 
     # ---- (f_c, mixture case) counts for the connection posteriors ----
     def attach_pair_accumulator(self, every=1):
@@ -550,9 +540,9 @@ class GibbsEngine(object):
         """
         if self.region_set_acc is not None:
             raise ValueError("detach the region-set accumulator before changing the sets")
-        if getattr(self, "patient_group_acc", None) is not None:
+        if self.patient_group_acc is not None:
             raise ValueError("detach the patient-group accumulator before changing the sets: they may be rows of it")
-        if getattr(self, "patient_trait_acc", None) is not None:
+        if self.patient_trait_acc is not None:
             raise ValueError("detach the patient-trait accumulator before changing the sets: they may be rows of it")
         if sets is None:
             (self.region_names, self.region_offsets, self.region_members) = (None, None, None)
@@ -639,29 +629,19 @@ class GibbsEngine(object):
 
     def patient_group_rows(self):
         """R: the regions and, while an attached accumulator has them or else if region sets are set, the region sets after them."""
-        with_sets = self.group_with_sets if self.patient_group_acc is not None else bool(self.region_J)
-        return self.Nreg + (self.region_J if with_sets else 0)
+        return self._rows(_PATIENT_GROUP, "group")
 
     def patient_group_row_names(self):
         """The names of the R rows: the region indices as str, then "set:<name>" for the region sets."""
-        R = self.patient_group_rows()
-        return [str(n) for n in range(self.Nreg)] + ["set:" + s for s in (self.region_names or [])[:R - self.Nreg]]
+        return self._row_names(self.patient_group_rows())
 
     def _send_patient_groups(self):
-        """As _send_region_sets(): the shared context holds this engine's groups (and, as rows, its region sets) before a launch."""
         if not self.group_J:
             raise ValueError("no patient groups: call set_patient_groups() first")
-        with_sets = self.patient_group_rows() > self.Nreg
-        if with_sets:
-            self._send_region_sets()
-        owner = getattr(self.ctx, "patient_groups_owner", None)
-        if owner is not None and owner[0]() is self and owner[1] == with_sets:
-            return
-        self.ctx.call("fcd_patient_groups_set", self.group_offsets.ctypes.data_as(C.c_void_p),
-                      self.group_members.ctypes.data_as(C.c_void_p), self.group_J,
-                      self.group_contrasts.ctypes.data_as(C.c_void_p) if len(self.group_contrasts) else None,
-                      len(self.group_contrasts), 1 if with_sets else 0)
-        self.ctx.patient_groups_owner = (weakref.ref(self), with_sets)
+        self._send_rows("group", self.patient_group_rows(), "fcd_patient_groups_set",
+                        self.group_offsets.ctypes.data_as(C.c_void_p), self.group_members.ctypes.data_as(C.c_void_p), self.group_J,
+                        self.group_contrasts.ctypes.data_as(C.c_void_p) if len(self.group_contrasts) else None,
+                        len(self.group_contrasts))
 
     def attach_patient_group_accumulator(self, every=1):
         """
@@ -724,27 +704,17 @@ class GibbsEngine(object):
 
     def patient_trait_rows(self):
         """R: the regions and, while an attached accumulator has them or else if region sets are set, the region sets after them."""
-        with_sets = self.trait_with_sets if self.patient_trait_acc is not None else bool(self.region_J)
-        return self.Nreg + (self.region_J if with_sets else 0)
+        return self._rows(_PATIENT_TRAIT, "trait")
 
     def patient_trait_row_names(self):
         """The names of the R rows: the region indices as str, then "set:<name>" for the region sets."""
-        R = self.patient_trait_rows()
-        return [str(n) for n in range(self.Nreg)] + ["set:" + s for s in (self.region_names or [])[:R - self.Nreg]]
+        return self._row_names(self.patient_trait_rows())
 
     def _send_patient_traits(self):
-        """As _send_patient_groups(): the shared context holds this engine's traits (and, as rows, its region sets) before a launch."""
         if not self.trait_Q:
             raise ValueError("no patient traits: call set_patient_traits() first")
-        with_sets = self.patient_trait_rows() > self.Nreg
-        if with_sets:
-            self._send_region_sets()
-        owner = getattr(self.ctx, "patient_traits_owner", None)
-        if owner is not None and owner[0]() is self and owner[1] == with_sets:
-            return
-        self.ctx.call("fcd_patient_traits_set", self.trait_scores.ctypes.data_as(C.c_void_p),
-                      self.trait_known.ctypes.data_as(C.c_void_p), self.trait_Q, self.U, 1 if with_sets else 0)
-        self.ctx.patient_traits_owner = (weakref.ref(self), with_sets)
+        self._send_rows("trait", self.patient_trait_rows(), "fcd_patient_traits_set",
+                        self.trait_scores.ctypes.data_as(C.c_void_p), self.trait_known.ctypes.data_as(C.c_void_p), self.trait_Q, self.U)
 
     def attach_patient_trait_accumulator(self, every=1):
         """
@@ -760,20 +730,14 @@ class GibbsEngine(object):
             raise ValueError("no patient traits: call set_patient_traits() first")
         self.patient_trait_acc = None
         self.trait_with_sets = bool(self.region_J)
-        (hist, _placeholder) = self._attach(_PATIENT_TRAIT, every)
-        t = self.torch
-        self.patient_trait_acc = (hist, t.zeros(_PATIENT_TRAIT.shapes(self)[1], dtype=t.int64, device=hist.device))
-        return self.patient_trait_acc
+        return self._attach(_PATIENT_TRAIT, every)
 
     def detach_patient_trait_accumulator(self):
         self._detach(_PATIENT_TRAIT)
 
     def patient_trait_host(self):
         """The attached buffers as NumPy arrays (trait_hist (Q, R, Umax+1+NB+3) uint32, trait_sum (Q, R, Umax+1) int64)."""
-        if self.patient_trait_acc is None:
-            raise ValueError("no patient-trait accumulator is attached")
-        (hist, total) = self.patient_trait_acc
-        return self.host(hist).view(np.uint32), self.host(total)
+        return self._acc_host(_PATIENT_TRAIT)
 
     def patient_trait_tally(self, trait_hist, trait_sum):
         """trait_hist (Q, R, Umax+1+NB+3) uint32-in-int32, trait_sum (Q, R, Umax+1) int64 tensors += the statistics of the current state."""

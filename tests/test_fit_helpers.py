@@ -133,67 +133,89 @@ def test_data_digest_sees_in_place_edits():
     assert UnsharedRegionFit._array_key(bt) != UnsharedRegionFit._array_key(bt.copy())
 
 
-@pytest.mark.parametrize("row", [0, 1, 2])
+# ---- GibbsEngine.run() over the rows of gibbs.ACCUMULATORS, on the stand-ins of tests/engine_stand_in.py ----
+
+ROWS = (      # key, attr, paired, setter, label, sites at Nreg = 7 and U = 12
+    ("pair", "pair_acc", False, "fcd_gibbs_set_pair_accumulator", "pair", 1),
+    ("count", "count_hist", True, "fcd_gibbs_set_count_accumulator", "count", 1),
+    ("coanomaly", "coanomaly_acc", True, "fcd_gibbs_set_coanomaly_accumulator", "co-anomaly", 12),
+    ("region_set", "region_set_acc", True, "fcd_gibbs_set_region_set_accumulator", "region-set", 1),
+    ("patient_group", "patient_group_acc", True, "fcd_gibbs_set_patient_group_accumulator", "patient-group", 1),
+    ("patient_trait", "patient_trait_acc", True, "fcd_gibbs_set_patient_trait_accumulator", "patient-trait", 1),
+)
+
+
+def test_the_table_has_six_rows_in_the_order_of_the_enum():
+    from fcdiff_amd import gibbs
+    assert [a.key for a in gibbs.ACCUMULATORS] == [row[0] for row in ROWS]
+    assert [a.dtypes for a in gibbs.ACCUMULATORS] == [("int32",)] + [("int32", "int32")] * 4 + [("int32", "int64")]
+    assert [a.send for a in gibbs.ACCUMULATORS] == [None, None, None, "_send_region_sets", "_send_patient_groups",
+                                                    "_send_patient_traits"]
+
+
+@pytest.mark.parametrize("row", [0, 1, 2, 3, 4, 5])
 def test_engine_accumulators_share_one_overflow_rule(row):
     """
-    GibbsEngine.run() over the rows of gibbs.ACCUMULATORS, on stand-ins made with __new__ (no library, no GPU): the rows are
-    checked in the table's order and nothing of a row is read unless its buffers are attached (the first stand-in has
-    nothing of the later rows: touching one is an AttributeError, not the ValueError asked for); a counter takes exactly
-    PAIR_COUNT_MAX // (G * sites) accumulated sweeps; the accumulator is attached for the call only, also when the call
+    The rows are checked in the table's order and a row's refusal comes before anything more of a later row is used (the
+    first stand-in has the later rows attached but without their periods: going on past the refusal is an AttributeError, not
+    the ValueError asked for); a counter takes exactly PAIR_COUNT_MAX // (G * sites) accumulated sweeps, earlier sweeps and
+    the period counted; a refusal makes no context call; the accumulator is attached for the call only, also when the call
     fails, and only a call that returned advances the counter.
     """
-    import torch
+    import weakref
+    from engine_stand_in import one_word_buffers, stand_in_engine
     from fcdiff_amd import gibbs
     a = gibbs.ACCUMULATORS[row]
-    assert (a.key, a.attr, a.label) == (("pair", "pair_acc", "pair"), ("count", "count_hist", "count"),
-                                        ("coanomaly", "coanomaly_acc", "co-anomaly"))[row]
+    (key, attr, paired, setter, label, want_sites) = ROWS[row]
+    assert (a.key, a.attr, a.paired, a.setter, a.label) == (key, attr, paired, setter, label)
     (G, N, U) = (1000, 7, 12)
     sites = a.sites(N, U) if a.sites else 1
-    assert sites == (1, 1, 12)[row]
+    assert sites == want_sites and (a.sites is None) == (key != "coanomaly")
     limit = gibbs.PAIR_COUNT_MAX // (G * sites)
-    wording = "the %s accumulator would overflow uint32: 1000 chains x %s" % (a.label, "12 sites x " if row == 2 else "")
+    wording = "the %s accumulator would overflow uint32: 1000 chains x %s" % (label, "12 sites x " if sites > 1 else "")
 
     def stand_in(later_rows):
-        eng = gibbs.GibbsEngine.__new__(gibbs.GibbsEngine)
-        (eng.G, eng.Nreg, eng.U) = (G, N, U)
-        for other in gibbs.ACCUMULATORS[:row] + (gibbs.ACCUMULATORS[row + 1:] if later_rows else ()):
-            setattr(eng, other.attr, None)
-        setattr(eng, a.attr, (None, None) if a.paired else torch.zeros(1, dtype=torch.int32))
-        setattr(eng, a.key + "_every", 1)
-        setattr(eng, a.key + "_sweeps", 0)
+        eng = stand_in_engine(G, N, U, attached=(key,), groups=[[0, 1], [5]], traits=[np.arange(12.0)])
+        # (the context already holds what this engine's rows need there)
+        eng.ctx.region_sets_owner = weakref.ref(eng)
+        eng.ctx.patient_groups_owner = eng.ctx.patient_traits_owner = (weakref.ref(eng), False)
+        for other in gibbs.ACCUMULATORS[row + 1:] if later_rows else ():
+            setattr(eng, other.attr, one_word_buffers(other))
         return eng
 
-    eng = stand_in(False)
+    eng = stand_in(True)
     with pytest.raises(ValueError, match=wording + "%d accumulated sweeps" % (limit + 1)):
         eng.run(0, limit + 1, accumulate_from=0)
-    setattr(eng, a.key + "_sweeps", limit - 4)                       # earlier sweeps count too
+    setattr(eng, key + "_sweeps", limit - 4)                         # earlier sweeps count too
     with pytest.raises(ValueError, match=wording):
         eng.run(limit - 4, 10, accumulate_from=limit + 1)
-    setattr(eng, a.key + "_every", 3)                                # ... and only every third sweep from accumulate_from on
+    setattr(eng, key + "_every", 3)                                  # ... and only every third sweep from accumulate_from on
     with pytest.raises(ValueError, match=wording):
         eng.run(0, 13, accumulate_from=0)
+    assert eng.ctx.calls == []                                       # refused before anything was sent or attached
 
-    class Recorder(object):
-        def __init__(self):
-            self.calls = []
-
-        def call(self, name, *args):
-            self.calls.append((name, args[-3:]))
-    eng = stand_in(True)
-    (eng.ctx, eng.n_accumulated, eng._run) = (Recorder(), 0, lambda *args: None)
+    eng = stand_in(False)
     eng.run(0, limit, accumulate_from=0)                             # exactly full
-    assert getattr(eng, a.key + "_sweeps") == limit
-    assert eng.ctx.calls == [(a.setter, (N, U, 1)), (a.setter, (0, 0, 1))]
+    assert getattr(eng, key + "_sweeps") == limit
+    assert eng.ctx.calls == [(setter, (N, U, 1)), (setter, (0, 0, 1))]
     with pytest.raises(ValueError, match=wording + "%d accumulated sweeps" % (limit + 1)):
         eng.run(limit, 1, accumulate_from=0)
     eng.run(limit, 5, accumulate_from=None)                          # nothing is counted, nothing attached
-    assert getattr(eng, a.key + "_sweeps") == limit and len(eng.ctx.calls) == 2
+    assert getattr(eng, key + "_sweeps") == limit and len(eng.ctx.calls) == 2
 
     def failing(*args):
         raise RuntimeError("the sweeps failed")
-    setattr(eng, a.key + "_sweeps", 0)
+    setattr(eng, key + "_sweeps", 0)
     eng._run = failing
     with pytest.raises(RuntimeError):
         eng.run(0, 4, accumulate_from=1)
-    assert getattr(eng, a.key + "_sweeps") == 0
-    assert eng.ctx.calls[2:] == [(a.setter, (N, U, 1)), (a.setter, (0, 0, 1))]
+    assert getattr(eng, key + "_sweeps") == 0                        # detached again, and the counter did not advance
+    assert eng.ctx.calls[2:] == [(setter, (N, U, 1)), (setter, (0, 0, 1))]
+
+
+def test_an_engine_with_nothing_attached_makes_no_context_call():
+    from engine_stand_in import stand_in_engine
+    eng = stand_in_engine(64, 7, 3)
+    eng.run(0, 5, accumulate_from=1)
+    assert eng.ctx.calls == [] and eng.n_accumulated == 4
+

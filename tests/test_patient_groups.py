@@ -1,18 +1,18 @@
 """
 Patient groups and contrasts without a GPU: the NumPy restatement of tests/patient_groups_ref.py against explicit loops, the
 three input forms of `patient_groups` and the refusals of groups and contrasts, the arithmetic of patient_group_posterior() on
-hand-made histograms, the knobs of the fit on a stand-in engine, GibbsEngine.run()'s handling of the new accumulator row on
+hand-made histograms, the knobs of the fit on a stand-in engine, what GibbsEngine.run() sends to a shared context on
 stand-ins, the shared fit's refusal, and header against binding.
 """
 import os
 import re
-import weakref
 
 import numpy as np
 import numpy.testing as nptest
 import pytest
 
 import patient_groups_ref as PG
+from engine_stand_in import stand_in_engine
 from conftest import ROOT
 from fcdiff_amd import _lib
 from fcdiff_amd import gibbs
@@ -140,111 +140,29 @@ def test_header_and_binding_agree_on_the_new_symbols():
     assert lib.fcd_gibbs_set_patient_group_accumulator(None, None, None, 4, 2, 1) == _lib.FCD_ERR_ARG
 
 
-def test_the_new_row_has_a_tuple_of_its_own():
-    assert [a.key for a in gibbs.ACCUMULATORS] == ["pair", "count", "coanomaly"]
-    assert [a.key for a in gibbs.EXTRA_ACCUMULATORS] == ["region_set"]
-    (a,) = gibbs.GROUP_ACCUMULATORS
-    assert (a.key, a.attr, a.paired, a.setter, a.sites, a.label) == (
-        "patient_group", "patient_group_acc", True, "fcd_gibbs_set_patient_group_accumulator", None, "patient-group")
-
-
-class Recorder(object):
-    def __init__(self):
-        self.calls = []
-
-    def call(self, name, *args):
-        self.calls.append((name, args[-3:]))
-
-
-def stand_in_engine(G, N, U, groups, contrasts=None, sets=None):
-    import torch
-    eng = gibbs.GibbsEngine.__new__(gibbs.GibbsEngine)
-    (eng.G, eng.Nreg, eng.U) = (G, N, U)
-    for other in gibbs.ACCUMULATORS + gibbs.EXTRA_ACCUMULATORS:
-        setattr(eng, other.attr, None)
-    (eng.region_names, eng.region_offsets, eng.region_members, eng.region_J, eng.region_smax) = (None, None, None, 0, 0)
-    if sets is not None:
-        (eng.region_names, eng.region_offsets, eng.region_members) = gibbs.region_sets_csr(sets, N)
-        (eng.region_J, eng.region_smax) = (len(eng.region_names), int(np.diff(eng.region_offsets).max()))
-    (eng.group_names, eng.group_offsets, eng.group_members) = gibbs.patient_groups_csr(groups, U)
-    (eng.group_contrasts, eng.group_bin_offsets) = gibbs.patient_group_contrasts(contrasts, eng.group_names, eng.group_offsets,
-                                                                                 eng.group_members)
-    (eng.group_J, eng.group_umax) = (len(eng.group_names), int(np.diff(eng.group_offsets).max()))
-    eng.group_with_sets = sets is not None
-    eng.patient_group_acc = (torch.zeros(1, dtype=torch.int32), torch.zeros(1, dtype=torch.int32))
-    (eng.patient_group_every, eng.patient_group_sweeps) = (1, 0)
-    (eng.ctx, eng.n_accumulated, eng._run) = (Recorder(), 0, lambda *args: None)
-    return eng
-
-
-def test_new_row_shares_the_overflow_rule():
-    """The stand-in pattern of tests/test_region_sets.py for the row of gibbs.GROUP_ACCUMULATORS: each tally adds at most G to a bin."""
-    (a,) = gibbs.GROUP_ACCUMULATORS
-    (G, N, U) = (1000, 7, 12)
-    limit = gibbs.PAIR_COUNT_MAX // G
-    wording = "the patient-group accumulator would overflow uint32: 1000 chains x "
-
-    def stand_in():
-        eng = stand_in_engine(G, N, U, [[0, 1], [5]])
-        eng.ctx.patient_groups_owner = (weakref.ref(eng), False)      # (the context already holds this engine's groups)
-        return eng
-    eng = stand_in()
-    with pytest.raises(ValueError, match=wording + "%d accumulated sweeps" % (limit + 1)):
-        eng.run(0, limit + 1, accumulate_from=0)
-    (eng.patient_group_sweeps, eng.patient_group_every) = (limit - 4, 3)
-    with pytest.raises(ValueError, match=wording):
-        eng.run(0, 13, accumulate_from=0)
-    assert eng.ctx.calls == []                                        # refused before anything was attached
-    eng = stand_in()
-    eng.run(0, limit, accumulate_from=0)                              # exactly full
-    assert eng.patient_group_sweeps == limit
-    assert eng.ctx.calls == [(a.setter, (N, U, 1)), (a.setter, (0, 0, 1))]
-    eng.run(limit, 5, accumulate_from=None)                           # nothing is counted, nothing attached
-    assert eng.patient_group_sweeps == limit and len(eng.ctx.calls) == 2
-
-    def failing(*args):
-        raise RuntimeError("the sweeps failed")
-    (eng.patient_group_sweeps, eng._run) = (0, failing)
-    with pytest.raises(RuntimeError):
-        eng.run(0, 4, accumulate_from=1)
-    assert eng.patient_group_sweeps == 0                              # detached again, and the counter did not advance
-    assert eng.ctx.calls[2:] == [(a.setter, (N, U, 1)), (a.setter, (0, 0, 1))]
-
-
 def test_a_shared_context_gets_this_engine_s_groups_and_sets_first():
-    (a,) = gibbs.GROUP_ACCUMULATORS
-    eng = stand_in_engine(64, 7, 6, {"a": [0, 1], "b": [2, 5]}, [("a", "b")], sets=[[0, 1], [6]])
+    setter = "fcd_gibbs_set_patient_group_accumulator"
+    eng = stand_in_engine(64, 7, 6, attached=("patient_group",), groups={"a": [0, 1], "b": [2, 5]}, contrasts=[("a", "b")],
+                          sets=[[0, 1], [6]])
     eng.patient_group_every = 2
     assert eng.patient_group_rows() == 9
     assert eng.patient_group_row_names() == [str(n) for n in range(7)] + ["set:0", "set:1"]
     eng.run(0, 5, accumulate_from=1)
-    assert [c[0] for c in eng.ctx.calls] == ["fcd_region_sets_set", "fcd_patient_groups_set", a.setter, a.setter]
+    assert [c[0] for c in eng.ctx.calls] == ["fcd_region_sets_set", "fcd_patient_groups_set", setter, setter]
     assert eng.ctx.calls[1][1][1:] == (1, 1)                          # P = 1, with the sets as rows
     assert eng.ctx.calls[2][1] == (7, 6, 2)
     eng.run(5, 2, accumulate_from=1)                                  # now the context holds this engine's
-    assert [c[0] for c in eng.ctx.calls[4:]] == [a.setter, a.setter]
+    assert [c[0] for c in eng.ctx.calls[4:]] == [setter, setter]
     assert eng.patient_group_sweeps == 2 + 1                          # sweeps 1, 3 and 5
     with pytest.raises(ValueError, match="detach the patient-group accumulator"):
         eng.set_region_sets([[0]])                                    # the sets are rows of the attached buffers
     with pytest.raises(ValueError, match="detach the patient-group accumulator"):
         eng.set_patient_groups([[0]])
-    plain = stand_in_engine(64, 7, 6, [[0, 1]])                       # without sets: the regions alone, no contrast
+    plain = stand_in_engine(64, 7, 6, attached=("patient_group",), groups=[[0, 1]])     # without sets: the regions alone, no contrast
     assert plain.patient_group_rows() == 7
     plain.run(0, 2, accumulate_from=0)
-    assert [c[0] for c in plain.ctx.calls] == ["fcd_patient_groups_set", a.setter, a.setter]
+    assert [c[0] for c in plain.ctx.calls] == ["fcd_patient_groups_set", setter, setter]
     assert plain.ctx.calls[0][1][1:] == (0, 0)
-
-
-def test_an_engine_without_the_attribute_makes_no_context_call():
-    eng = gibbs.GibbsEngine.__new__(gibbs.GibbsEngine)
-    (eng.G, eng.Nreg, eng.U) = (64, 7, 3)
-    for other in gibbs.ACCUMULATORS:
-        setattr(eng, other.attr, None)
-    (eng.ctx, eng.n_accumulated, eng._run) = (Recorder(), 0, lambda *args: None)
-    eng.counts = None
-    assert not hasattr(eng, "patient_group_acc")
-    eng.run(0, 5, accumulate_from=1)
-    assert eng.ctx.calls == [] and eng.n_accumulated == 4
 
 
 # ---- the posterior's arithmetic on hand-made histograms ----

@@ -1,18 +1,18 @@
 """
 Patient traits without a GPU: the rank transform patient_traits_scores() and its refusals, the NumPy restatement of
 tests/patient_traits_ref.py against brute-force pair counting, the integer AUC bin rule, the arithmetic of
-patient_trait_posterior() on hand-made histograms, the host refusals of the query, GibbsEngine.run()'s handling of the new
-accumulator row on stand-ins, and header against binding.
+patient_trait_posterior() on hand-made histograms, the host refusals of the query, what GibbsEngine.run() sends to a shared
+context on stand-ins, and header against binding.
 """
 import os
 import re
-import weakref
 
 import numpy as np
 import numpy.testing as nptest
 import pytest
 
 import patient_traits_ref as PT
+from engine_stand_in import stand_in_engine
 from conftest import ROOT
 from fcdiff_amd import _lib
 from fcdiff_amd import gibbs
@@ -77,6 +77,7 @@ def test_scores_refusals(traits, U, match):
 def test_scores_at_the_limits():
     (names, scores, _known, n_known) = gibbs.patient_traits_scores(np.tile(np.arange(512.0), (16, 1)), 512)
     assert len(names) == 16 and n_known.tolist() == [512] * 16
+    assert (gibbs.PATIENT_TRAIT_MAX_U, gibbs.PATIENT_TRAIT_MAX_TRAITS, gibbs.PATIENT_TRAIT_BINS) == (512, 16, PT.NB)
     nptest.assert_array_equal(scores[5], 2 * np.arange(512) - 511)
 
 
@@ -286,7 +287,7 @@ def test_fit_refuses_before_the_run(knobs):
     assert fit._ctx is None
 
 
-# ---- header, binding, and the accumulator row on stand-in engines ----
+# ---- header, binding, and the shared context on stand-in engines ----
 
 def test_header_and_binding_agree_on_the_new_symbols():
     text = open(os.path.join(ROOT, "include", "fcdiff_hip.h")).read()
@@ -303,101 +304,26 @@ def test_header_and_binding_agree_on_the_new_symbols():
     assert lib.fcd_gibbs_set_patient_trait_accumulator(None, None, None, 4, 2, 1) == _lib.FCD_ERR_ARG
 
 
-def test_the_new_row_has_a_tuple_of_its_own():
-    (a,) = gibbs.TRAIT_ACCUMULATORS
-    assert (a.key, a.attr, a.paired, a.setter, a.sites, a.label) == (
-        "patient_trait", "patient_trait_acc", True, "fcd_gibbs_set_patient_trait_accumulator", None, "patient-trait")
-    assert (gibbs.PATIENT_TRAIT_MAX_U, gibbs.PATIENT_TRAIT_MAX_TRAITS, gibbs.PATIENT_TRAIT_BINS) == (512, 16, PT.NB)
-
-
-class Recorder(object):
-    def __init__(self):
-        self.calls = []
-
-    def call(self, name, *args):
-        self.calls.append((name, args[-3:]))
-
-
-def stand_in_engine(G, N, U, traits, sets=None):
-    import torch
-    eng = gibbs.GibbsEngine.__new__(gibbs.GibbsEngine)
-    (eng.G, eng.Nreg, eng.U) = (G, N, U)
-    for other in gibbs.ACCUMULATORS + gibbs.EXTRA_ACCUMULATORS + gibbs.GROUP_ACCUMULATORS:
-        setattr(eng, other.attr, None)
-    (eng.region_names, eng.region_offsets, eng.region_members, eng.region_J, eng.region_smax) = (None, None, None, 0, 0)
-    if sets is not None:
-        (eng.region_names, eng.region_offsets, eng.region_members) = gibbs.region_sets_csr(sets, N)
-        (eng.region_J, eng.region_smax) = (len(eng.region_names), int(np.diff(eng.region_offsets).max()))
-    (eng.trait_names, scores, known, eng.trait_n_known) = gibbs.patient_traits_scores(traits, U)
-    (eng.trait_scores, eng.trait_known) = (np.ascontiguousarray(scores), np.ascontiguousarray(known.astype(np.uint8)))
-    (eng.trait_Q, eng.trait_umax) = (len(eng.trait_names), int(eng.trait_n_known.max()))
-    eng.trait_with_sets = sets is not None
-    eng.patient_trait_acc = (torch.zeros(1, dtype=torch.int32), torch.zeros(1, dtype=torch.int64))
-    (eng.patient_trait_every, eng.patient_trait_sweeps) = (1, 0)
-    (eng.ctx, eng.n_accumulated, eng._run) = (Recorder(), 0, lambda *args: None)
-    return eng
-
-
-def test_new_row_shares_the_overflow_rule():
-    (a,) = gibbs.TRAIT_ACCUMULATORS
-    (G, N, U) = (1000, 7, 12)
-    limit = gibbs.PAIR_COUNT_MAX // G
-    wording = "the patient-trait accumulator would overflow uint32: 1000 chains x "
-
-    def stand_in():
-        eng = stand_in_engine(G, N, U, [np.arange(12.0)])
-        eng.ctx.patient_traits_owner = (weakref.ref(eng), False)       # (the context already holds this engine's traits)
-        return eng
-    eng = stand_in()
-    with pytest.raises(ValueError, match=wording + "%d accumulated sweeps" % (limit + 1)):
-        eng.run(0, limit + 1, accumulate_from=0)
-    assert eng.ctx.calls == []                                        # refused before anything was attached
-    eng.run(0, limit, accumulate_from=0)                              # exactly full
-    assert eng.patient_trait_sweeps == limit
-    assert eng.ctx.calls == [(a.setter, (N, U, 1)), (a.setter, (0, 0, 1))]
-    eng.run(limit, 5, accumulate_from=None)                           # nothing is counted, nothing attached
-    assert eng.patient_trait_sweeps == limit and len(eng.ctx.calls) == 2
-
-    def failing(*args):
-        raise RuntimeError("the sweeps failed")
-    (eng.patient_trait_sweeps, eng._run) = (0, failing)
-    with pytest.raises(RuntimeError):
-        eng.run(0, 4, accumulate_from=1)
-    assert eng.patient_trait_sweeps == 0                              # detached again, and the counter did not advance
-    assert eng.ctx.calls[2:] == [(a.setter, (N, U, 1)), (a.setter, (0, 0, 1))]
-
-
 def test_a_shared_context_gets_this_engine_s_traits_and_sets_first():
-    (a,) = gibbs.TRAIT_ACCUMULATORS
-    eng = stand_in_engine(64, 7, 6, {"dose": [1, 2, 3, NAN, 5, 5]}, sets=[[0, 1], [6]])
+    setter = "fcd_gibbs_set_patient_trait_accumulator"
+    eng = stand_in_engine(64, 7, 6, attached=("patient_trait",), traits={"dose": [1, 2, 3, NAN, 5, 5]}, sets=[[0, 1], [6]])
     eng.patient_trait_every = 2
     assert eng.patient_trait_rows() == 9
     assert eng.patient_trait_row_names() == [str(n) for n in range(7)] + ["set:0", "set:1"]
     eng.run(0, 5, accumulate_from=1)
-    assert [c[0] for c in eng.ctx.calls] == ["fcd_region_sets_set", "fcd_patient_traits_set", a.setter, a.setter]
+    assert [c[0] for c in eng.ctx.calls] == ["fcd_region_sets_set", "fcd_patient_traits_set", setter, setter]
     assert eng.ctx.calls[1][1] == (1, 6, 1)                           # Q = 1, U = 6, with the sets as rows
     assert eng.ctx.calls[2][1] == (7, 6, 2)
     eng.run(5, 2, accumulate_from=1)                                  # now the context holds this engine's
-    assert [c[0] for c in eng.ctx.calls[4:]] == [a.setter, a.setter]
+    assert [c[0] for c in eng.ctx.calls[4:]] == [setter, setter]
     assert eng.patient_trait_sweeps == 2 + 1                          # sweeps 1, 3 and 5
     with pytest.raises(ValueError, match="detach the patient-trait accumulator"):
         eng.set_region_sets([[0]])                                    # the sets are rows of the attached buffers
     with pytest.raises(ValueError, match="detach the patient-trait accumulator"):
         eng.set_patient_traits([[1, 2, 3, 4, 5, 6]])
-    plain = stand_in_engine(64, 7, 6, [[1, 2, 3, 4, 5, 6]])           # without sets: the regions alone
+    plain = stand_in_engine(64, 7, 6, attached=("patient_trait",), traits=[[1, 2, 3, 4, 5, 6]])    # without sets: the regions alone
     assert plain.patient_trait_rows() == 7
     plain.run(0, 2, accumulate_from=0)
-    assert [c[0] for c in plain.ctx.calls] == ["fcd_patient_traits_set", a.setter, a.setter]
+    assert [c[0] for c in plain.ctx.calls] == ["fcd_patient_traits_set", setter, setter]
     assert plain.ctx.calls[0][1] == (1, 6, 0)
 
-
-def test_an_engine_without_the_attribute_makes_no_context_call():
-    eng = gibbs.GibbsEngine.__new__(gibbs.GibbsEngine)
-    (eng.G, eng.Nreg, eng.U) = (64, 7, 3)
-    for other in gibbs.ACCUMULATORS:
-        setattr(eng, other.attr, None)
-    (eng.ctx, eng.n_accumulated, eng._run) = (Recorder(), 0, lambda *args: None)
-    eng.counts = None
-    assert not hasattr(eng, "patient_trait_acc")
-    eng.run(0, 5, accumulate_from=1)
-    assert eng.ctx.calls == [] and eng.n_accumulated == 4

@@ -1,16 +1,16 @@
 """
 Region-set counts without a GPU: the NumPy restatement of tests/region_sets_ref.py against brute force, the three input
-forms of `region_sets` and their refusals, GibbsEngine.run()'s handling of the extra accumulator row on stand-ins, and the
+forms of `region_sets` and their refusals, what GibbsEngine.run() sends to a shared context on a stand-in, and the
 defaults and refusals of region_set_posterior().
 """
 import itertools
-import weakref
 
 import numpy as np
 import numpy.testing as nptest
 import pytest
 
 import region_sets_ref as RS
+from engine_stand_in import stand_in_engine
 from fcdiff_amd import _lib
 from fcdiff_amd import gibbs
 
@@ -124,106 +124,18 @@ def test_new_symbols_load_and_abi_stays_4():
     assert lib.fcd_gibbs_set_region_set_accumulator(None, None, None, 4, 2, 1) == _lib.FCD_ERR_ARG
 
 
-def test_the_pinned_table_keeps_its_three_rows():
-    assert [a.key for a in gibbs.ACCUMULATORS] == ["pair", "count", "coanomaly"]
-    (a,) = gibbs.EXTRA_ACCUMULATORS
-    assert (a.key, a.attr, a.paired, a.setter, a.sites, a.label) == (
-        "region_set", "region_set_acc", True, "fcd_gibbs_set_region_set_accumulator", None, "region-set")
-
-
-class Recorder(object):
-    def __init__(self):
-        self.calls = []
-
-    def call(self, name, *args):
-        self.calls.append((name, args[-3:]))
-
-
-def test_extra_row_shares_the_overflow_rule():
-    """
-    The stand-in pattern of tests/test_fit_helpers.py for the row of gibbs.EXTRA_ACCUMULATORS: a counter takes exactly
-    PAIR_COUNT_MAX // G accumulated sweeps; the accumulator is attached for the call only, also when the call fails, and
-    only a call that returned advances the counter.
-    """
-    import torch
-    (a,) = gibbs.EXTRA_ACCUMULATORS
-    (G, N, U) = (1000, 7, 12)
-    limit = gibbs.PAIR_COUNT_MAX // G
-    wording = "the region-set accumulator would overflow uint32: 1000 chains x "
-
-    def stand_in():
-        eng = gibbs.GibbsEngine.__new__(gibbs.GibbsEngine)
-        (eng.G, eng.Nreg, eng.U) = (G, N, U)
-        for other in gibbs.ACCUMULATORS:
-            setattr(eng, other.attr, None)
-        eng.region_set_acc = (torch.zeros(1, dtype=torch.int32), torch.zeros(1, dtype=torch.int32))
-        (eng.region_set_every, eng.region_set_sweeps) = (1, 0)
-        eng.ctx = Recorder()
-        eng.ctx.region_sets_owner = weakref.ref(eng)         # (the context already holds this engine's sets)
-        (eng.n_accumulated, eng._run) = (0, lambda *args: None)
-        return eng
-
-    eng = stand_in()
-    with pytest.raises(ValueError, match=wording + "%d accumulated sweeps" % (limit + 1)):
-        eng.run(0, limit + 1, accumulate_from=0)
-    eng.region_set_sweeps = limit - 4                                # earlier sweeps count too
-    with pytest.raises(ValueError, match=wording):
-        eng.run(limit - 4, 10, accumulate_from=limit + 1)
-    (eng.region_set_sweeps, eng.region_set_every) = (limit - 4, 3)   # ... and only every third sweep from accumulate_from on
-    with pytest.raises(ValueError, match=wording):
-        eng.run(0, 13, accumulate_from=0)
-    assert eng.ctx.calls == []                                       # refused before anything was attached
-
-    eng = stand_in()
-    eng.run(0, limit, accumulate_from=0)                             # exactly full
-    assert eng.region_set_sweeps == limit
-    assert eng.ctx.calls == [(a.setter, (N, U, 1)), (a.setter, (0, 0, 1))]
-    with pytest.raises(ValueError, match=wording + "%d accumulated sweeps" % (limit + 1)):
-        eng.run(limit, 1, accumulate_from=0)
-    eng.run(limit, 5, accumulate_from=None)                          # nothing is counted, nothing attached
-    assert eng.region_set_sweeps == limit and len(eng.ctx.calls) == 2
-
-    def failing(*args):
-        raise RuntimeError("the sweeps failed")
-    eng.region_set_sweeps = 0
-    eng._run = failing
-    with pytest.raises(RuntimeError):
-        eng.run(0, 4, accumulate_from=1)
-    assert eng.region_set_sweeps == 0
-    assert eng.ctx.calls[2:] == [(a.setter, (N, U, 1)), (a.setter, (0, 0, 1))]
-
-
 def test_a_context_that_holds_other_sets_gets_this_engine_s_first():
     """The context is shared between engines: run() sends the engine's own sets before it attaches its buffers."""
-    import torch
-    (a,) = gibbs.EXTRA_ACCUMULATORS
-    eng = gibbs.GibbsEngine.__new__(gibbs.GibbsEngine)
-    (eng.G, eng.Nreg, eng.U) = (64, 7, 3)
-    for other in gibbs.ACCUMULATORS:
-        setattr(eng, other.attr, None)
-    (eng.region_names, eng.region_offsets, eng.region_members) = gibbs.region_sets_csr([[0, 1], [6]], 7)
-    (eng.region_J, eng.region_smax) = (2, 2)
-    eng.region_set_acc = (torch.zeros(1, dtype=torch.int32), torch.zeros(1, dtype=torch.int32))
-    (eng.region_set_every, eng.region_set_sweeps) = (2, 0)
-    (eng.ctx, eng.n_accumulated, eng._run) = (Recorder(), 0, lambda *args: None)
+    setter = "fcd_gibbs_set_region_set_accumulator"
+    eng = stand_in_engine(64, 7, 3, attached=("region_set",), sets=[[0, 1], [6]])
+    assert (eng.region_J, eng.region_smax) == (2, 2)
+    eng.region_set_every = 2
     eng.run(0, 5, accumulate_from=1)
-    assert [c[0] for c in eng.ctx.calls] == ["fcd_region_sets_set", a.setter, a.setter]
+    assert [c[0] for c in eng.ctx.calls] == ["fcd_region_sets_set", setter, setter]
     assert eng.ctx.calls[0][1][-1] == 2 and eng.ctx.calls[1][1] == (7, 3, 2)
     eng.run(5, 2, accumulate_from=1)                                  # now the context's sets are this engine's
-    assert [c[0] for c in eng.ctx.calls[3:]] == [a.setter, a.setter]
+    assert [c[0] for c in eng.ctx.calls[3:]] == [setter, setter]
     assert eng.region_set_sweeps == 2 + 1                             # sweeps 1, 3 and 5
-
-
-def test_an_engine_without_the_attribute_makes_no_context_call():
-    eng = gibbs.GibbsEngine.__new__(gibbs.GibbsEngine)
-    (eng.G, eng.Nreg, eng.U) = (64, 7, 3)
-    for other in gibbs.ACCUMULATORS:
-        setattr(eng, other.attr, None)
-    (eng.ctx, eng.n_accumulated, eng._run) = (Recorder(), 0, lambda *args: None)
-    eng.counts = None
-    assert not hasattr(eng, "region_set_acc")
-    eng.run(0, 5, accumulate_from=1)
-    assert eng.ctx.calls == [] and eng.n_accumulated == 4
 
 
 def test_fit_defaults_and_refusals_without_a_run():
